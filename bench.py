@@ -46,6 +46,44 @@ BASELINE_C5 = ("final_scene", 1920, 1080, 5000)  # BASELINE.json configs[4]
 # ------------------------------------------------------------------------------------------------
 # CPU baseline legs (oracle = test infrastructure; it is only ever the thing compared against)
 # ------------------------------------------------------------------------------------------------
+_NATIVE_DIR = None
+
+
+def native_oracle_dir():
+    """Compiles the timed CPU-baseline library (f64, no operation counters, gcc -O3 -march=native) for the host that runs
+    the benchmark, once per process tree (forked workers inherit it), into a private temporary directory: the checkout
+    may belong to another user, so nothing is written into it.  Returns the directory."""
+    global _NATIVE_DIR
+    if _NATIVE_DIR is None:
+        import atexit
+        import shutil
+        import tempfile
+
+        from oracle import oracle as orc_mod
+
+        d = tempfile.mkdtemp(prefix="rtmi_bench_oracle_")
+        atexit.register(lambda pid=os.getpid(): os.getpid() == pid and shutil.rmtree(d, ignore_errors=True))
+        subprocess.run(["make", "-B", "-C", orc_mod._HERE, "native", "OUT=" + d], check=True, stdout=subprocess.DEVNULL)
+        _NATIVE_DIR = d
+    return _NATIVE_DIR
+
+
+def native_oracle():
+    """Oracle("f64", native=True), loaded from native_oracle_dir().  The binding takes its libraries from its build
+    directory and would rebuild the native one there: for this one load it is pointed at the private directory, with
+    the library marked as built.  (The oracle module's own interface is all this relies on, so that the benchmark also
+    runs against other builds of the project for comparison.)"""
+    from oracle import oracle as orc_mod
+
+    d = native_oracle_dir()
+    build_dir = orc_mod._BUILD
+    orc_mod._BUILD, orc_mod._NATIVE_BUILT = d, True
+    try:
+        return orc_mod.Oracle("f64", native=True)
+    finally:
+        orc_mod._BUILD = build_dir
+
+
 def cpu_sample(scene, nx, ny, spp, nrows, native, seed_scene=1):
     """Renders `nrows` evenly spaced rows of the workload at `spp` samples per pixel with the f64 oracle
     (literal restatement, recursive color).  native=True: the uninstrumented -march=native build (timing);
@@ -53,7 +91,7 @@ def cpu_sample(scene, nx, ny, spp, nrows, native, seed_scene=1):
     from oracle.oracle import Oracle
     from raytracing_rust_amd import scenes
 
-    orc = Oracle("f64", native=native)
+    orc = native_oracle() if native else Oracle("f64")
     cam, world = scenes.build(orc, scene, nx, ny, seed=seed_scene)
     rows = [int((k + 0.5) * ny / nrows) for k in range(nrows)]
     orc.reset_counters()
@@ -70,10 +108,9 @@ _ALLCORE = {}
 
 
 def _allcore_init(scene, nx, ny):
-    from oracle.oracle import Oracle
     from raytracing_rust_amd import scenes
 
-    orc = Oracle("f64", native=True)
+    orc = native_oracle()
     cam, world = scenes.build(orc, scene, nx, ny, seed=1)
     _ALLCORE.update(orc=orc, cam=cam, world=world, nx=nx, ny=ny)
 
@@ -119,9 +156,7 @@ def cpu_sample_allcore(scene, nx, ny, rows_per_worker, nproc, target_s):
     Must run BEFORE the process touches the GPU (fork).  Returns (samples, seconds, spp of the timed batch)."""
     import multiprocessing as mp
 
-    from oracle import oracle as orc_mod
-
-    orc_mod.build_native()  # once, in the parent: the workers inherit the "built" flag
+    native_oracle_dir()  # once, in the parent: the workers inherit the directory
     total_rows = rows_per_worker * nproc
     rows = [int((k + 0.5) * ny / total_rows) for k in range(total_rows)]
     ctx = mp.get_context("fork")
@@ -320,6 +355,37 @@ def cold_one_shot(scene_name, nx, ny, ns, flags, ppm_path, spawned_at):
     }
 
 
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs, all files together (headline: 1920x1080 x 7 float32 = 58.1 MB)
+
+
+def fold_path_sig(sig):
+    """uint64 path signatures -> their 24-bit xor fold as float32 (exact: integers below 2**24; no float type holds all
+    64 bits).  A path that changes anywhere changes the fold with probability 1 - 2**-24."""
+    import numpy as np
+
+    s = sig.astype(np.uint64)
+    return ((s ^ (s >> np.uint64(24)) ^ (s >> np.uint64(48))) & np.uint64(0xFFFFFF)).astype(np.float32)
+
+
+def dump_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES):
+    """Writes per-pixel arrays ({name: [ny, nx, ...]}, float32 or float64) as dirpath/<name>.npy.  Images too large for
+    `budget` are sampled: the same seeded, sorted set of pixels for every run with the same arguments, their row-major
+    indices in pixel_index.npy.  Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    ny, nx = next(iter(arrays.values())).shape[:2]
+    npix = ny * nx
+    if sum(a.nbytes for a in arrays.values()) > budget - 4096:  # (headroom for the .npy headers)
+        k = (budget - 4096) // (sum(a.nbytes for a in arrays.values()) // npix + 8)  # + the float64 index of a pixel
+        idx = np.sort(np.random.default_rng(0).choice(npix, size=k, replace=False))
+        arrays = {name: a.reshape((npix,) + a.shape[2:])[idx] for name, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def load_profile_summary(path, workload):
     """profiles/pmc_summary.json (tools/pmc_summary.py): per workload the HBM bytes and the SQ counter sums of
     one launch of the dominant kernel, from rocprofv3 --pmc passes committed under profiles/."""
@@ -373,7 +439,13 @@ def main():
     ap.add_argument("--no-baseline-config", action="store_true",
                     help="N > 1: skip the extra strong-scaled run of BASELINE config C5 (final_scene x5000spp)")
     ap.add_argument("--launch-timeout", type=int, default=3000, help="seconds the self-launcher waits for its ranks")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the image the last timed step computed (linear radiance and rgb8) "
+                         "and the per-pixel path signatures of the same render (folded to 24 bits) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (larger images: a fixed, seeded pixel sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing in this process has initialised the GPU (torch is not even imported).
@@ -470,9 +542,10 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    def timed_run(ns, steps, warmup):
+    def timed_run(ns, steps, warmup, keep_last=False):
         """`warmup` untimed + `steps` timed whole-image renders at ns samples per pixel (tiles of this rank + the one
-        gather), bracketed by barrier + synchronize; returns max-over-ranks seconds and the per-launch kernel times."""
+        gather), bracketed by barrier + synchronize; returns max-over-ranks seconds and the per-launch kernel times.
+        keep_last: also returns a host copy of what the last timed step gathered (rank 0), taken after the clock stops."""
         params = rdist.rank_params(nx, ny, ns, rank, world, seed=42, flags=args.flags, spp_chunks=args.chunks,
                                    shade_threshold=args.shade_threshold, sample_buffer_bytes=args.sample_buffer_mb << 20)
         local = rdist.new_local_framebuffer(params, device)
@@ -498,18 +571,20 @@ def main():
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
         t0 = time.perf_counter()
         for k in range(steps):
-            step(evs[k])
+            last = step(evs[k])
         fence()
         elapsed = time.perf_counter() - t0
+        # (the gathered tensor may be a view of the local framebuffer, which the next render overwrites: copied now)
+        last = last.cpu().numpy() if keep_last and last is not None else None
         el = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
         kernel_ms = [a.elapsed_time(b) for a, b in evs]
         return {"elapsed": float(el.item()), "kernel_ms": float(np.mean(kernel_ms)), "render_ms": float(np.mean(render_ms)),
-                "params": params, "step": step}
+                "params": params, "step": step, "last": last}
 
     ns = args.spp * world
-    run = timed_run(ns, args.steps, args.warmup)
+    run = timed_run(ns, args.steps, args.warmup, keep_last=bool(args.dump_outputs))
     elapsed, kernel_ms_avg, render_ms_avg, params, step = (run["elapsed"], run["kernel_ms"], run["render_ms"],
                                                            run["params"], run["step"])
 
@@ -543,6 +618,13 @@ def main():
         dist.destroy_process_group()  # the ranks are done; rank 0 goes on alone
     if rank != 0:
         return
+
+    # ---- --dump-outputs: the per-pixel path signatures of the same render (rank 0, whole image, after the clock: the
+    # signature adds work).  The headline scene renders black, as the reference's does; the signatures pin its paths.
+    sig_render = None
+    if args.dump_outputs:
+        sig_render = scene.render(cam, nx, ny, ns, sig=True, seed=42, flags=args.flags, spp_chunks=args.chunks,
+                                  shade_threshold=args.shade_threshold, sample_buffer_bytes=args.sample_buffer_mb << 20)
 
     # ---- the persistent C-ABI handle (rtmi_multi_*): N = 1 in this process on [0]; N > 1 in a fresh child of rank 0
     # over all N devices, after the other ranks have finished (their processes exit; nothing else runs on the GPUs)
@@ -679,6 +761,16 @@ def main():
         }
     else:
         out["cpu_baseline"] = None
+    if args.dump_outputs:
+        # linear and rgb8: the image of the last timed step; path_sig: from the signature render, whose image must be
+        # the same
+        lin_last, rgb_last = rdist.untile(params, run["last"])
+        arrays = {"linear": lin_last, "rgb8": rgb_last.astype(np.float32), "path_sig": fold_path_sig(sig_render["sig"])}
+        out["dump_outputs"] = {
+            "dir": os.path.abspath(args.dump_outputs), "arrays": dump_outputs(args.dump_outputs, arrays),
+            "path_sig_render_image_equal": bool(np.array_equal(sig_render["linear"], lin_last)
+                                                and np.array_equal(sig_render["rgb8"], rgb_last)),
+            "path_sig_nonzero_pixels": int(np.count_nonzero(sig_render["sig"]))}
     print(json.dumps(out), flush=True)
 
 

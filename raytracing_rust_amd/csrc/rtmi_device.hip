@@ -931,7 +931,14 @@ extern "C" int rtmi_untile(const rtmi_render_params *p, const rtmi_texel *g, flo
 // ---- blocking host API ---------------------------------------------------------------------------------
 static int ensure_streams(rtmi_scene *s) {
     if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    if (!s->copy_stream) {
+        // The progress polls must not queue behind the render.  The runtime gives streams at most GPU_MAX_HW_QUEUES
+        // hardware queues per priority and shares the least used one beyond that (with 2, the two streams of a handle
+        // landed on one queue and every poll waited for the whole render); another priority is another pool.
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&s->copy_stream, hipStreamNonBlocking, greatest));
+    }
     return RTMI_OK;
 }
 // Waits for `done_ev` of every listed scene; meanwhile (about every 50 ms) reads the devices' unit counters through
