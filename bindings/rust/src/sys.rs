@@ -354,4 +354,17 @@ extern "C" {
         out: *mut f32,
         n: u32,
     ) -> c_int;
+    /// ray-primitive and shading arithmetic of the render kernels (include/rtmi.h: RTMI_PROBE_GEOM_*)
+    pub fn rtmi_probe_geom(
+        op: c_int,
+        prim_a: *const f32,
+        prim_b: *const f32,
+        meta: *const RtmiPrimMeta,
+        n_prims: u32,
+        xforms: *const RtmiXform,
+        n_xforms: u32,
+        input: *const f32,
+        out: *mut f32,
+        n: u32,
+    ) -> c_int;
 }

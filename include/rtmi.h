@@ -478,6 +478,27 @@ int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out, u
  * the n inputs (a, b: 3 floats each) out[13*i..] = world->object ray (origin a, direction b: 6 floats), object->world
  * hit record (point a, normal b: 6 floats), and 1.0 when a rotation was applied.  xforms: outermost wrapper first. */
 int rtmi_probe_xform(const rtmi_xform *xforms, uint32_t count, const float *a, const float *b, float *out, uint32_t n);
+/* Ray-primitive and shading arithmetic as the render kernels evaluate it, one case per thread.  The primitives are given
+ * in the scene description's own form (planes A and B: 4 floats each per primitive, meta, xforms) and laid out on the
+ * device as rtmi_scene_create lays them out.  in: n cases of RTMI_PROBE_GEOM_IN floats = origin (3), direction (3), time,
+ * t_min, t_max, primitive index (int32 bits), then six op-specific words; out: n cases of RTMI_PROBE_GEOM_OUT floats.
+ *   PRIM   : {hit, t, face} of prim_test, prim_test_vals and prim_test_uniform (9 words), then 0 when all three kept the
+ *            primitive index; t = t_max on a miss.  The index must be the same within every 64 consecutive cases (a
+ *            list scan's wave-uniform index).
+ *   AABB   : box min (3), max (3) in the op words; {aabb_hit, aabb_hit_t, its t_enter}.
+ *   MEDIUM : ConstantMedium's two boundary queries (medium.rs:29-30) against the static sphere at the index: {h1, t1, h2, t2}.
+ *   SHADE  : v = direction, n = op words 0..2, ni_over_nt, cosine, ref_idx = op words 3..5;
+ *            {reflect(v, n) (3), refract ok, its vector (3), schlick(cosine, ref_idx)}.
+ *   UV     : normal = op words 0..2, two book flags = op words 3, 4 (non-zero: the book's pi/2 instead of FRAC_2_PI,
+ *            RTMI_FLAG_UV_BOOK); {u, v} of get_sphere_uv with the first flag, then {u, v} with the second.
+ * RTMI_ERR_INVALID for an unknown op, a primitive index outside [0, n_prims), a transform chain outside [0, n_xforms) or
+ * a PRIM group with two indices; RTMI_ERR_DEVICE without a device. */
+enum { RTMI_PROBE_GEOM_PRIM = 0, RTMI_PROBE_GEOM_AABB = 1, RTMI_PROBE_GEOM_MEDIUM = 2, RTMI_PROBE_GEOM_SHADE = 3,
+       RTMI_PROBE_GEOM_UV = 4 };
+#define RTMI_PROBE_GEOM_IN 16
+#define RTMI_PROBE_GEOM_OUT 10
+int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b, const rtmi_prim_meta *meta, uint32_t n_prims,
+                    const rtmi_xform *xforms, uint32_t n_xforms, const float *in, float *out, uint32_t n);
 
 #ifdef __cplusplus
 }

@@ -103,6 +103,10 @@ def _load(name):
         "orc_rtmi_logf": (C.c_float, [C.c_float]),
         "orc_rtmi_atan2f": (C.c_float, [C.c_float, C.c_float]),
         "orc_rtmi_asinf": (C.c_float, [C.c_float]),
+        "orc_probe_aabb": (i, [vp, vp, vp, d, d, i]),
+        "orc_probe_medium": (None, [vp, vp, vp, d, i, vp]),
+        "orc_probe_shade": (None, [vp, vp, d, d, d, vp]),
+        "orc_probe_uv": (None, [vp, i, vp]),
     }
     for name_, (res, args) in sig.items():
         fn = getattr(lib, name_)
@@ -265,6 +269,32 @@ class Oracle:
             return None
         return {"t": out[0], "u": out[1], "v": out[2], "p": out[3:6].copy(), "normal": out[6:9].copy(),
                 "mat_kind": mk.value}
+
+    def aabb_hit(self, origin, direction, box, t_min, t_max, flags=0):
+        """aabb.rs:31-44 on the ray's derived 1/d (t_min / t_max beyond +-1.7e308: the precision's +-MAX)"""
+        o, d, b = _d3(origin), _d3(direction), np.ascontiguousarray(np.asarray(box, np.float64).reshape(6))
+        return bool(self.lib.orc_probe_aabb(o.ctypes.data, d.ctypes.data, b.ctypes.data, t_min, t_max, flags))
+
+    def medium_queries(self, boundary, origin, direction, time=0.0, flags=0):
+        """ConstantMedium's two boundary queries (medium.rs:29-30): (h1, t1, h2, t2)"""
+        o, d = _d3(origin), _d3(direction)
+        out = np.zeros(4)
+        self.lib.orc_probe_medium(boundary.h, o.ctypes.data, d.ctypes.data, time, flags, out.ctypes.data)
+        return bool(out[0]), out[1], bool(out[2]), out[3]
+
+    def shade(self, v, n, ni_over_nt, cosine, ref_idx):
+        """material.rs:9-28: (reflect(v, n), refract ok, refracted vector, schlick(cosine, ref_idx))"""
+        vv, nn = _d3(v), _d3(n)
+        out = np.zeros(8)
+        self.lib.orc_probe_shade(vv.ctypes.data, nn.ctypes.data, ni_over_nt, cosine, ref_idx, out.ctypes.data)
+        return out[0:3].copy(), bool(out[3]), out[4:7].copy(), out[7]
+
+    def sphere_uv(self, n, flags=0):
+        """get_sphere_uv (sphere.rs:9-15) of a unit normal: (u, v)"""
+        nn = _d3(n)
+        out = np.zeros(2)
+        self.lib.orc_probe_uv(nn.ctypes.data, flags, out.ctypes.data)
+        return out[0], out[1]
 
     def bounding_box(self, hittable, t0=0.0, t1=1.0):
         out = np.zeros(6)

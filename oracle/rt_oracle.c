@@ -1274,3 +1274,40 @@ ORC_API float orc_rtmi_sinf(float x) { return rtmi_sinf(x); }
 ORC_API float orc_rtmi_logf(float x) { return rtmi_logf(x); }
 ORC_API float orc_rtmi_atan2f(float y, float x) { return rtmi_atan2f(y, x); }
 ORC_API float orc_rtmi_asinf(float x) { return rtmi_asinf(x); }
+/* pieces of the hot path that have no hittable of their own, for the per-operation tests (tests/test_geom_contract.py);
+ * each only calls the functions above */
+ORC_API int orc_probe_aabb(const double *o, const double *d, const double *box6, double t_min, double t_max, int flags) {
+    g_flags = flags;
+    Ray r = ray_new(v3((REAL)o[0], (REAL)o[1], (REAL)o[2]), v3((REAL)d[0], (REAL)d[1], (REAL)d[2]), (REAL)0);
+    AABB b = {v3((REAL)box6[0], (REAL)box6[1], (REAL)box6[2]), v3((REAL)box6[3], (REAL)box6[4], (REAL)box6[5])};
+    REAL tmn = t_min <= -1.7e308 ? -R_MAX : (REAL)t_min;
+    REAL tmx = t_max >= 1.7e308 ? R_MAX : (REAL)t_max;
+    return aabb_hit(&b, &r, tmn, tmx);
+}
+/* ConstantMedium's two boundary queries (medium.rs:29-30) as H_MEDIUM makes them; out4 = {h1, t1, h2, t2} */
+ORC_API void orc_probe_medium(void *boundary, const double *o, const double *d, double time, int flags, double *out4) {
+    g_flags = flags;
+    Ray r = ray_new(v3((REAL)o[0], (REAL)o[1], (REAL)o[2]), v3((REAL)d[0], (REAL)d[1], (REAL)d[2]), (REAL)time);
+    HitRecord h1, h2;
+    out4[0] = out4[1] = out4[2] = out4[3] = 0.0;
+    if (hit((Hittable *)boundary, &r, -R_MAX, R_MAX, &h1)) {
+        out4[0] = 1.0; out4[1] = h1.t;
+        if (hit((Hittable *)boundary, &r, h1.t + (REAL)0.0001, R_MAX, &h2)) { out4[2] = 1.0; out4[3] = h2.t; }
+    }
+}
+/* material.rs:9-28: out8 = {reflect(v, n) (3), refract ok, its vector (3), schlick(cosine, ref_idx)} */
+ORC_API void orc_probe_shade(const double *v, const double *n, double ni_over_nt, double cosine, double ref_idx, double *out8) {
+    V3 vv = v3((REAL)v[0], (REAL)v[1], (REAL)v[2]), nn = v3((REAL)n[0], (REAL)n[1], (REAL)n[2]);
+    V3 rf = reflect(vv, nn), rr = v3(0, 0, 0);
+    int ok = refract(vv, nn, (REAL)ni_over_nt, &rr);
+    out8[0] = rf.x; out8[1] = rf.y; out8[2] = rf.z;
+    out8[3] = ok; out8[4] = rr.x; out8[5] = rr.y; out8[6] = rr.z;
+    out8[7] = schlick((REAL)cosine, (REAL)ref_idx);
+}
+/* sphere.rs:9-15 (flags: ORC_UV_BOOK) */
+ORC_API void orc_probe_uv(const double *n, int flags, double *out2) {
+    g_flags = flags;
+    REAL u, v;
+    get_sphere_uv(v3((REAL)n[0], (REAL)n[1], (REAL)n[2]), &u, &v);
+    out2[0] = u; out2[1] = v;
+}

@@ -41,6 +41,8 @@ ITEM_LIST, ITEM_BVH = 0, 1
 ITEMFLAG_FLIP, ITEMFLAG_MEDIUM, ITEMFLAG_SAVE_T0, ITEMFLAG_DEFERRED, ITEMFLAG_NESTED_MEDIUM = 1, 2, 4, 8, 16
 ITEMFLAG_LISTSCAN_BEGIN, ITEMFLAG_LISTSCAN_MEMBER, ITEMFLAG_LISTSCAN_END = 32, 64, 128
 RTMI_ITEMFLAG_GATE_OUTER_SHIFT = 12  # DEFERRED items: how many leading transforms belong to the enclosing BVH item (bits 12..15)
+PROBE_GEOM_PRIM, PROBE_GEOM_AABB, PROBE_GEOM_MEDIUM, PROBE_GEOM_SHADE, PROBE_GEOM_UV = 0, 1, 2, 3, 4  # rtmi_probe_geom
+PROBE_GEOM_IN, PROBE_GEOM_OUT = 16, 10  # floats per case
 XF_TRANSLATE, XF_ROTATE_X, XF_ROTATE_Y, XF_ROTATE_Z, XF_GATE_MIN, XF_GATE_MAX, XF_INNER_MEDIUM = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -132,7 +134,8 @@ class Stats(C.Structure):
 RTMI_SYMBOLS = ["rtmi_device_count", "rtmi_last_error", "rtmi_build_hash", "rtmi_scene_create", "rtmi_scene_destroy", "rtmi_release_cached", "rtmi_local_tiles",
                 "rtmi_render_prepare", "rtmi_render_device", "rtmi_scene_status", "rtmi_render", "rtmi_render_multi", "rtmi_multi_create",
                 "rtmi_multi_prepare", "rtmi_multi_render", "rtmi_multi_destroy", "rtmi_multi_collective", "rtmi_partial_image", "rtmi_untile",
-                "rtmi_ppm_p3", "rtmi_write_ppm", "rtmi_probe_math", "rtmi_probe_philox", "rtmi_probe_xform"]
+                "rtmi_ppm_p3", "rtmi_write_ppm", "rtmi_probe_math", "rtmi_probe_philox", "rtmi_probe_xform",
+                "rtmi_probe_geom"]
 
 _rtmi = None
 _host = None
@@ -194,6 +197,8 @@ def load_rtmi():
     lib.rtmi_probe_philox.argtypes = [vp, vp, vp, C.c_uint32]
     lib.rtmi_probe_xform.restype = C.c_int
     lib.rtmi_probe_xform.argtypes = [C.POINTER(Xform), C.c_uint32, vp, vp, vp, C.c_uint32]
+    lib.rtmi_probe_geom.restype = C.c_int
+    lib.rtmi_probe_geom.argtypes = [C.c_int, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32]
     _rtmi = lib
     return lib
 

@@ -1473,6 +1473,61 @@ extern "C" int rtmi_probe_xform(const rtmi_xform *xforms, uint32_t count, const 
     (void)hipFree(dx); (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
     return RTMI_OK;
 }
+extern "C" int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b, const rtmi_prim_meta *meta, uint32_t n_prims,
+                               const rtmi_xform *xforms, uint32_t n_xforms, const float *in, float *out, uint32_t n) {
+    if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
+    if (op < RTMI_PROBE_GEOM_PRIM || op > RTMI_PROBE_GEOM_UV) return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: unknown op");
+    if (n == 0) return RTMI_OK;
+    if (!in || !out || (n_prims && (!prim_a || !prim_b || !meta)) || (n_xforms && !xforms))
+        return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: missing array");
+    uint32_t has_prim_xf = 0u;
+    for (uint32_t p = 0; p < n_prims; p++) {
+        const uint32_t cnt = (meta[p].flags >> RTMI_PRIMFLAG_XF_COUNT_SHIFT) & RTMI_PRIM_XF_MAX;
+        const uint64_t first = meta[p].flags >> RTMI_PRIMFLAG_XF_FIRST_SHIFT;
+        if (meta[p].type < RTMI_PRIM_SPHERE || meta[p].type > RTMI_PRIM_CUBE) return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: primitive type");
+        if (cnt && first + cnt > n_xforms) return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: transform chain out of range");
+        if (cnt) has_prim_xf = 1u;
+    }
+    if (op == RTMI_PROBE_GEOM_PRIM || op == RTMI_PROBE_GEOM_MEDIUM) {
+        for (uint32_t i = 0; i < n; i++) {
+            int32_t idx;
+            memcpy(&idx, in + (size_t)RTMI_PROBE_GEOM_IN * i + 9, 4);
+            if (idx < 0 || (uint32_t)idx >= n_prims) return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: primitive index out of range");
+            int32_t lead;
+            memcpy(&lead, in + (size_t)RTMI_PROBE_GEOM_IN * (i & ~63u) + 9, 4);
+            if (op == RTMI_PROBE_GEOM_PRIM && idx != lead)
+                return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: PRIM cases must share one primitive per 64");
+        }
+    }
+    struct Bufs { // released on every path
+        float *rec = nullptr, *in = nullptr, *out = nullptr;
+        rtmi_xform *xf = nullptr;
+        ~Bufs() { (void)hipFree(rec); (void)hipFree(in); (void)hipFree(out); (void)hipFree(xf); }
+    } b;
+    std::vector<float> lr((size_t)(n_prims ? n_prims : 1) * 20, 0.0f); // leaf records as rtmi_scene_create builds them
+    for (uint32_t p = 0; p < n_prims; p++) {
+        float *r = &lr[(size_t)p * 20];
+        memcpy(r, prim_a + (size_t)p * 4, 16);
+        memcpy(r + 4, prim_b + (size_t)p * 4, 16);
+        memcpy(r + 8, &meta[p], 16);
+    }
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.rec), lr.size() * 4));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.xf), (n_xforms ? n_xforms : 1) * sizeof(rtmi_xform)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.in), (size_t)n * RTMI_PROBE_GEOM_IN * 4));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.out), (size_t)n * RTMI_PROBE_GEOM_OUT * 4));
+    HIP_TRY(hipMemcpy(b.rec, lr.data(), lr.size() * 4, hipMemcpyHostToDevice));
+    if (n_xforms) HIP_TRY(hipMemcpy(b.xf, xforms, n_xforms * sizeof(rtmi_xform), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b.in, in, (size_t)n * RTMI_PROBE_GEOM_IN * 4, hipMemcpyHostToDevice));
+    DevScene sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.leaf_rec = reinterpret_cast<const float4 *>(b.rec);
+    sc.xforms = b.xf;
+    sc.has_prim_xf = has_prim_xf;
+    hipLaunchKernelGGL(rtmi_geom_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, op, sc, b.in, b.out, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, b.out, (size_t)n * RTMI_PROBE_GEOM_OUT * 4, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
 extern "C" int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out, uint32_t n) {
     if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
     uint32_t *dc = nullptr, *dk = nullptr, *dout = nullptr;

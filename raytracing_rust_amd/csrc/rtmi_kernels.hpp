@@ -544,4 +544,60 @@ __global__ void rtmi_philox_probe_kernel(const uint32_t *ctr, const uint32_t *ke
     philox(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], key[2 * i], key[2 * i + 1], o0, o1, o2, o3);
     out[4 * i] = o0; out[4 * i + 1] = o1; out[4 * i + 2] = o2; out[4 * i + 3] = o3;
 }
+// ray-primitive and shading arithmetic exactly as the render kernels call it (rtmi_probe_geom, include/rtmi.h): the
+// production inline functions on a DevScene whose leaf records and transforms are laid out as rtmi_scene_create lays
+// them out.  One wavefront per block; the host has checked that every 64 consecutive PRIM cases share one primitive
+// index, so the index handed to prim_test_uniform is wave-uniform as in a list scan.
+__global__ void __launch_bounds__(64) rtmi_geom_probe_kernel(int op, DevScene sc, const float *in, float *out, uint32_t n) {
+    const uint32_t i = min(blockIdx.x * 64u + threadIdx.x, n - 1u); // tail lanes repeat the last case, write nothing
+    const bool live = blockIdx.x * 64u + threadIdx.x < n;
+    const float *a = in + RTMI_PROBE_GEOM_IN * (size_t)i;
+    float res[RTMI_PROBE_GEOM_OUT];
+    for (int k = 0; k < RTMI_PROBE_GEOM_OUT; k++) res[k] = 0.0f;
+    RayF r;
+    r.o = f3(a[0], a[1], a[2]);
+    r.d = f3(a[3], a[4], a[5]);
+    ray_derive(r);
+    const float time = a[6], t_min = a[7], t_max = a[8];
+    const int idx = __float_as_int(a[9]);
+    if (op == RTMI_PROBE_GEOM_PRIM) {
+        const PrimRec *pr = reinterpret_cast<const PrimRec *>(sc.leaf_rec + (size_t)idx * 5);
+        const float4 A = pr->A, B = pr->B;
+        const rtmi_prim_meta M = pr->M;
+        float t0 = t_max, t1 = t_max, t2 = t_max;
+        int pf0 = 0, pf1 = 0, pf2 = 0;
+        const bool h0 = prim_test<true>(sc, M.type, idx, r, time, t_min, t_max, t0, pf0);
+        const bool h1 = prim_test_vals<true>(sc, M.type, idx, A, B, M.inv_dt, M.flags, r, time, t_min, t_max, t1, pf1);
+        const int uidx = __builtin_amdgcn_readfirstlane(idx);
+        const bool h2 = prim_test_uniform<true>(sc, uidx, r, time, t_min, t_max, t2, pf2);
+        res[0] = h0 ? 1.0f : 0.0f; res[1] = t0; res[2] = (float)(pf0 & 7);
+        res[3] = h1 ? 1.0f : 0.0f; res[4] = t1; res[5] = (float)(pf1 & 7);
+        res[6] = h2 ? 1.0f : 0.0f; res[7] = t2; res[8] = (float)(pf2 & 7);
+        res[9] = (float)((pf0 >> 3) - idx) + (float)((pf1 >> 3) - idx) + (float)((pf2 >> 3) - uidx); // 0: index kept
+    } else if (op == RTMI_PROBE_GEOM_AABB) {
+        float te = 0.0f;
+        res[0] = aabb_hit(a[10], a[11], a[12], a[13], a[14], a[15], r, t_min, t_max) ? 1.0f : 0.0f;
+        res[1] = aabb_hit_t(a[10], a[11], a[12], a[13], a[14], a[15], r, t_min, t_max, te) ? 1.0f : 0.0f;
+        res[2] = te;
+    } else if (op == RTMI_PROBE_GEOM_MEDIUM) {
+        bool h1 = false, h2 = false;
+        float q1 = 0.0f, q2 = 0.0f;
+        sphere_two_queries(r, reinterpret_cast<const PrimRec *>(sc.leaf_rec + (size_t)idx * 5)->A, h1, q1, h2, q2);
+        res[0] = h1 ? 1.0f : 0.0f; res[1] = q1; res[2] = h2 ? 1.0f : 0.0f; res[3] = q2;
+    } else if (op == RTMI_PROBE_GEOM_SHADE) { // v = ray direction, n = a[10..12], ni_over_nt = a[13], cosine = a[14], ref_idx = a[15]
+        const F3 nn = f3(a[10], a[11], a[12]);
+        const F3 rf = reflect(r.d, nn);
+        F3 rr = f3(0.0f, 0.0f, 0.0f);
+        const bool ok = refract(r.d, nn, a[13], rr);
+        res[0] = rf.x; res[1] = rf.y; res[2] = rf.z;
+        res[3] = ok ? 1.0f : 0.0f; res[4] = rr.x; res[5] = rr.y; res[6] = rr.z;
+        res[7] = schlick(a[14], a[15]);
+    } else if (op == RTMI_PROBE_GEOM_UV) { // the normal = a[10..12]; `book` read at run time, as the render reads it
+        const F3 nn = f3(a[10], a[11], a[12]);
+        sphere_uv(nn, a[13] != 0.0f, res[0], res[1]);
+        sphere_uv(nn, a[14] != 0.0f, res[2], res[3]);
+    }
+    if (live)
+        for (int k = 0; k < RTMI_PROBE_GEOM_OUT; k++) out[RTMI_PROBE_GEOM_OUT * (size_t)i + k] = res[k];
+}
 #endif // RTMI_LEAN_TU

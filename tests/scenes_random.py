@@ -218,5 +218,56 @@ def random_camera(api, seed, nx, ny):
                       aperture, float(np.linalg.norm(look_from)), 0.0, 1.0)
 
 
-def build(api, seed, nx, ny, only=None, instanced=False):
+class _Placed:
+    """The same scene `scale` times larger and shifted by `offset`: every length (centres, radii, extents, translations,
+    camera position and focus distance, lens aperture) times `scale`, every position plus `offset`, media densities
+    divided by `scale`.  A Rotate turns about the origin, so with an offset it is taken about the shifted origin instead:
+    Traslate(Rotate(Traslate(h, -offset)), offset) — the primitives below it keep their shifted coordinates.  Everything
+    else (textures, materials, lists, trees, constants) passes through."""
+
+    def __init__(self, api, scale, offset):
+        self._api, self._s, self._o = api, float(scale), np.asarray(offset, np.float64)
+        self._shifted = bool(np.any(self._o != 0.0))
+
+    def __getattr__(self, name):
+        return getattr(self._api, name)
+
+    def _p(self, v):
+        return np.asarray(v, np.float64) * self._s + self._o
+
+    def Sphere(self, center, radius, material):
+        return self._api.Sphere(self._p(center), radius * self._s, material)
+
+    def MovingSphere(self, center0, center1, time0, time1, radius, material):
+        return self._api.MovingSphere(self._p(center0), self._p(center1), time0, time1, radius * self._s, material)
+
+    def Rect(self, plane, x0, y0, x1, y1, k, material):
+        kk, a, b = {self._api.PLANE_YZ: (0, 1, 2), self._api.PLANE_ZX: (1, 2, 0), self._api.PLANE_XY: (2, 0, 1)}[plane]
+        s, o = self._s, self._o
+        return self._api.Rect(plane, x0 * s + o[a], y0 * s + o[b], x1 * s + o[a], y1 * s + o[b], k * s + o[kk], material)
+
+    def Cube(self, p_min, p_max, material):
+        return self._api.Cube(self._p(p_min), self._p(p_max), material)
+
+    def Traslate(self, hittable, offset):
+        return self._api.Traslate(hittable, np.asarray(offset, np.float64) * self._s)
+
+    def Rotate(self, axis, hittable, angle):
+        if not self._shifted:
+            return self._api.Rotate(axis, hittable, angle)
+        inner = self._api.Rotate(axis, self._api.Traslate(hittable, -self._o), angle)
+        return self._api.Traslate(inner, self._o)
+
+    def ConstantMedium(self, boundary, density, texture):
+        return self._api.ConstantMedium(boundary, density / self._s, texture)
+
+    def Camera(self, look_from, look_at, view_up, vertical_fov, aspect, aperture, focus_dist, time0, time1):
+        return self._api.Camera(self._p(look_from), self._p(look_at), view_up, vertical_fov, aspect, aperture * self._s,
+                                focus_dist * self._s, time0, time1)
+
+
+def build(api, seed, nx, ny, only=None, instanced=False, scale=1.0, offset=(0.0, 0.0, 0.0)):
+    """scale, offset: the scene away from the unit box (_Placed); the defaults build exactly the scene of old"""
+    if scale != 1.0 or any(offset):
+        api = _Placed(api, scale, offset)
     return random_camera(api, seed, nx, ny), random_scene(api, seed, only, instanced)

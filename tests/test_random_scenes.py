@@ -16,14 +16,24 @@ if os.environ.get("RTMI_RANDOM_SEEDS"):  # e.g. "25-200": an ad-hoc wider sweep
     _lo, _hi = os.environ["RTMI_RANDOM_SEEDS"].split("-")
     SEEDS = list(range(int(_lo), int(_hi) + 1))
 TOL = 1e-4  # north star: per-channel linear radiance
+# the same scenes away from the unit box (scenes_random.build scale / offset): coordinates of the size of final_scene's
+# and random_spheres', where the traversals' pruning margins and the gated trees work at other magnitudes
+PLACEMENTS = [("scale1_64", 1.0 / 64.0, (0.0, 0.0, 0.0)), ("scale300", 300.0, (0.0, 0.0, 0.0)),
+              ("offset700", 1.0, (700.0, 0.0, -700.0))]
+UNIT = (1.0, (0.0, 0.0, 0.0))
+
+
+def _cases(seeds, placed_seeds):
+    return [pytest.param(s, UNIT, id=str(s)) for s in seeds] + [
+        pytest.param(s, (sc, off), id="%d-%s" % (s, name)) for name, sc, off in PLACEMENTS for s in placed_seeds]
 
 
 @pytest.mark.parametrize("instanced", [False, True], ids=["plain", "instanced"])
-@pytest.mark.parametrize("seed", SEEDS[:12])
-def test_mirror_equals_f64_oracle_and_lowers(host, orc64, seed, instanced):
+@pytest.mark.parametrize("seed,placement", _cases(SEEDS[:12], SEEDS[:8]))
+def test_mirror_equals_f64_oracle_and_lowers(host, orc64, seed, placement, instanced):
     nx, ny = 16, 12
-    cam, world = scenes_random.build(host, seed, nx, ny, instanced=instanced)
-    camo, worldo = scenes_random.build(orc64, seed, nx, ny, instanced=instanced)
+    cam, world = scenes_random.build(host, seed, nx, ny, instanced=instanced, scale=placement[0], offset=placement[1])
+    camo, worldo = scenes_random.build(orc64, seed, nx, ny, instanced=instanced, scale=placement[0], offset=placement[1])
     row = 5
     ref = orc64.render(camo, worldo, nx, ny, 1, seed=42, rows=(row, row + 1))
     for i in range(nx):
@@ -36,14 +46,15 @@ def test_mirror_equals_f64_oracle_and_lowers(host, orc64, seed, instanced):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("instanced", [False, True], ids=["plain", "instanced"])
-@pytest.mark.parametrize("seed", SEEDS)
-def test_device_equals_fp32_oracle_on_random_scenes(host, orc32, seed, instanced):
+@pytest.mark.parametrize("seed,placement", _cases(SEEDS, SEEDS[:8]))
+def test_device_equals_fp32_oracle_on_random_scenes(host, orc32, seed, placement, instanced):
     """instanced: members of nested lists and BVH leaves wrapped in their own Traslate / Rotate / FlipNormals chains
-    (reference: traslate.rs:17-24, rotate.rs:84-113 under bvh.rs:11-12)."""
+    (reference: traslate.rs:17-24, rotate.rs:84-113 under bvh.rs:11-12).  placement: the scene
+    scaled and shifted away from the unit box (PLACEMENTS)."""
     nx, ny, ns = 40, 24, 6
-    cam, world = scenes_random.build(host, seed, nx, ny, instanced=instanced)
+    cam, world = scenes_random.build(host, seed, nx, ny, instanced=instanced, scale=placement[0], offset=placement[1])
     sc = host.lower(world)
-    camo, worldo = scenes_random.build(orc32, seed, nx, ny, instanced=instanced)
+    camo, worldo = scenes_random.build(orc32, seed, nx, ny, instanced=instanced, scale=placement[0], offset=placement[1])
     sky = SKY if seed % 3 == 0 else 0
     ref = orc32.render(camo, worldo, nx, ny, ns, seed=42, flags=ARITH_DEVICE | THROUGHPUT_FORM | sky)
     dsky = abi.RTMI_FLAG_SKY if sky else 0
