@@ -368,3 +368,64 @@ extern "C" {
         n: u32,
     ) -> c_int;
 }
+
+// ---- include/rtmi_f64.h: the f64 render mode ---------------------------------------------------------------------------
+// Declarations only: lowering a scene's double planes on the Rust side is not provided.
+
+pub const RTMI_SAMPLE_SLOT_BYTES_F64: u32 = 24;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiSceneF64 {
+    pub n_items: u32,
+    pub n_prims: u32,
+    pub n_nodes: u32,
+    pub n_xforms: u32,
+    pub n_materials: u32,
+    pub n_textures: u32,
+    pub n_perlin: u32,
+    pub pad: u32,
+    pub prim_a: *const f64,
+    pub prim_b: *const f64,
+    pub prim_dt: *const f64,
+    pub prim_gate: *const f64,
+    pub nodes: *const f64,
+    pub xforms: *const f64,
+    pub item_neg_inv_density: *const f64,
+    pub item_root: *const f64,
+    pub material_param: *const f64,
+    pub texture_f: *const f64,
+    pub perlin_ranvec: *const f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiCameraF64 {
+    pub origin: [f64; 3],
+    pub lower_left_corner: [f64; 3],
+    pub horizontal: [f64; 3],
+    pub vertical: [f64; 3],
+    pub u: [f64; 3],
+    pub v: [f64; 3],
+    pub time0: f64,
+    pub time1: f64,
+    pub lens_radius: f64,
+}
+
+extern "C" {
+    /// attaches the double planes of the scene the handle was created from
+    pub fn rtmi_scene_attach_f64(scene: *mut RtmiScene, planes: *const RtmiSceneF64) -> c_int;
+    /// blocking whole-image render in double; t_min as a double (0.001, color.rs:7)
+    pub fn rtmi_render_f64(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCameraF64,
+        params: *const RtmiRenderParams,
+        t_min: f64,
+        out_linear_rgb: *mut f64,
+        out_rgb8: *mut u8,
+        out_path_sig: *mut u64,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the f64 kernel's sin / log / atan2 / asin / division / sqrt on the device
+    pub fn rtmi_probe_math_f64(op: c_int, x: *const f64, y: *const f64, out: *mut f64, n: u32) -> c_int;
+}

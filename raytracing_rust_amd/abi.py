@@ -131,11 +131,34 @@ class Stats(C.Structure):
 
 
 # every entry point include/rtmi.h declares (tests check that the library exports them all)
+class SceneF64(C.Structure):
+    """rtmi_scene_f64 (include/rtmi_f64.h): the double planes of the f64 render mode."""
+    _fields_ = [("n_items", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_xforms", C.c_uint32),
+                ("n_materials", C.c_uint32), ("n_textures", C.c_uint32), ("n_perlin", C.c_uint32), ("pad", C.c_uint32),
+                ("prim_a", C.POINTER(C.c_double)), ("prim_b", C.POINTER(C.c_double)), ("prim_dt", C.POINTER(C.c_double)),
+                ("prim_gate", C.POINTER(C.c_double)), ("nodes", C.POINTER(C.c_double)), ("xforms", C.POINTER(C.c_double)),
+                ("item_neg_inv_density", C.POINTER(C.c_double)), ("item_root", C.POINTER(C.c_double)),
+                ("material_param", C.POINTER(C.c_double)), ("texture_f", C.POINTER(C.c_double)),
+                ("perlin_ranvec", C.POINTER(C.c_double))]
+
+
+class CameraF64(C.Structure):
+    """rtmi_camera_f64 (include/rtmi_f64.h)."""
+    _fields_ = [("origin", C.c_double * 3), ("lower_left_corner", C.c_double * 3), ("horizontal", C.c_double * 3),
+                ("vertical", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3),
+                ("time0", C.c_double), ("time1", C.c_double), ("lens_radius", C.c_double)]
+
+
+SAMPLE_SLOT_BYTES_F64 = 24  # RTMI_SAMPLE_SLOT_BYTES_F64
+
 RTMI_SYMBOLS = ["rtmi_device_count", "rtmi_last_error", "rtmi_build_hash", "rtmi_scene_create", "rtmi_scene_destroy", "rtmi_release_cached", "rtmi_local_tiles",
                 "rtmi_render_prepare", "rtmi_render_device", "rtmi_scene_status", "rtmi_render", "rtmi_render_multi", "rtmi_multi_create",
                 "rtmi_multi_prepare", "rtmi_multi_render", "rtmi_multi_destroy", "rtmi_multi_collective", "rtmi_partial_image", "rtmi_untile",
                 "rtmi_ppm_p3", "rtmi_write_ppm", "rtmi_probe_math", "rtmi_probe_philox", "rtmi_probe_xform",
                 "rtmi_probe_geom"]
+
+# the functions of include/rtmi_f64.h (the f64 render mode), kept apart from those of include/rtmi.h
+RTMI_F64_SYMBOLS = ["rtmi_scene_attach_f64", "rtmi_render_f64", "rtmi_probe_math_f64"]
 
 _rtmi = None
 _host = None
@@ -199,6 +222,12 @@ def load_rtmi():
     lib.rtmi_probe_xform.argtypes = [C.POINTER(Xform), C.c_uint32, vp, vp, vp, C.c_uint32]
     lib.rtmi_probe_geom.restype = C.c_int
     lib.rtmi_probe_geom.argtypes = [C.c_int, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32]
+    lib.rtmi_scene_attach_f64.restype = C.c_int
+    lib.rtmi_scene_attach_f64.argtypes = [vp, C.POINTER(SceneF64)]
+    lib.rtmi_render_f64.restype = C.c_int
+    lib.rtmi_render_f64.argtypes = [vp, C.POINTER(CameraF64), C.POINTER(RenderParams), C.c_double, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_probe_math_f64.restype = C.c_int
+    lib.rtmi_probe_math_f64.argtypes = [C.c_int, vp, vp, vp, C.c_uint32]
     _rtmi = lib
     return lib
 
@@ -249,6 +278,10 @@ def load_host():
         "rth_lowered_desc": (i, [vp, C.POINTER(SceneDesc)]),
         "rth_upload": (i, [vp, i]),
         "rth_render": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, C.POINTER(Stats)]),
+        "rth_lowered_desc_f64": (i, [vp, C.POINTER(SceneF64)]),
+        "rth_camera_lower_f64": (i, [vp, C.POINTER(CameraF64)]),
+        "rth_attach_f64": (i, [vp]),
+        "rth_render_f64": (i, [vp, vp, C.POINTER(RenderParams), d, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),
@@ -260,6 +293,7 @@ def load_host():
         "rth_multi_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_multi_render": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_camera_render": (i, [vp, vp, u32, u32, u32, u64, u32, i, vp, vp, C.POINTER(Stats)]),
+        "rth_camera_render_f64": (i, [vp, vp, u32, u32, u32, u64, u32, i, vp, vp, C.POINTER(Stats)]),
         "rth_hit": (i, [vp, vp, vp, d, d, d, u64, vp, vp]),
         "rth_bounding_box": (i, [vp, d, d, vp, vp]),
         "rth_tex_value": (i, [vp, d, d, vp, vp]),

@@ -35,6 +35,8 @@
 #include "rtmi_math.h"
 
 #include "rtmi_kernels.hpp"
+#include "rtmi_f64_types.hpp"
+#include "rtmi_f64_plan.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -91,6 +93,12 @@ struct rtmi_scene {
     hipStream_t copy_stream = nullptr; // progress polls while a launch runs
     uint64_t units_total = 0;          // work units of the last enqueued call (progress denominator)
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    // f64 render mode (include/rtmi_f64.h): the attached double planes on the device, freed with the handle
+    bool has_f64 = false;
+    DevSceneF64 f64{};
+    std::vector<void *> f64_allocs;
+    double *f64_samples = nullptr; // the f64 mode's per-sample buffer (grow-only, at most RTMI_F64_MAX_BUFFER_BYTES)
+    size_t f64_samples_bytes = 0;
 };
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
@@ -516,6 +524,8 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     for (void *p : s->allocs) (void)hipFree(p);
+    for (void *p : s->f64_allocs) (void)hipFree(p);
+    if (s->f64_samples) (void)hipFree(s->f64_samples);
     if (s->partial) (void)hipFree(s->partial);
     if (s->samples) { // parked for the next handle on this device (see g_parked); no kernel may still write it
         if (s->busy_recorded) (void)hipEventSynchronize(s->busy);
@@ -1540,5 +1550,196 @@ extern "C" int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint3
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dout, n * 16, hipMemcpyDeviceToHost));
     (void)hipFree(dc); (void)hipFree(dk); (void)hipFree(dout);
+    return RTMI_OK;
+}
+
+// ======================================================================================
+// f64 render mode (include/rtmi_f64.h): attach, blocking render, probe.  The kernels are in rtmi_f64.hip.
+// ======================================================================================
+extern "C" int rtmi_scene_attach_f64(rtmi_scene *s, const rtmi_scene_f64 *w) {
+    if (!s || !w) return fail(RTMI_ERR_INVALID, "NULL argument");
+    const rtmi_scene_desc &m = s->meta;
+    if (w->n_items != m.n_items || w->n_prims != m.n_prims || w->n_nodes != m.n_nodes || w->n_xforms != m.n_xforms ||
+        w->n_materials != m.n_materials || w->n_textures != m.n_textures || w->n_perlin != m.n_perlin)
+        return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_f64: counts differ from the handle's scene description");
+    struct Plane { const double *src; size_t n; const double **dst; const char *name; };
+    DevSceneF64 d{};
+    const Plane planes[] = {
+        {w->prim_a, (size_t)w->n_prims * 4, &d.prim_a, "prim_a"}, {w->prim_b, (size_t)w->n_prims * 4, &d.prim_b, "prim_b"},
+        {w->prim_dt, (size_t)w->n_prims, &d.prim_dt, "prim_dt"}, {w->nodes, (size_t)w->n_nodes * 12, &d.nodes, "nodes"},
+        {w->xforms, (size_t)w->n_xforms * 4, &d.xforms, "xforms"},
+        {w->item_neg_inv_density, (size_t)w->n_items, &d.item_nid, "item_neg_inv_density"},
+        {w->item_root, (size_t)w->n_items * 6, &d.item_root, "item_root"},
+        {w->material_param, (size_t)w->n_materials, &d.mparam, "material_param"},
+        {w->texture_f, (size_t)w->n_textures * 4, &d.texf, "texture_f"},
+        {w->perlin_ranvec, (size_t)w->n_perlin * 768, &d.ranvec, "perlin_ranvec"}};
+    for (const Plane &p : planes)
+        if (p.n && !p.src) return fail(RTMI_ERR_INVALID, std::string("rtmi_scene_attach_f64: plane ") + p.name + " is NULL");
+    // prim_gate is part of the description (rtmi_scene_f64) but the exact walk of this mode does not read it
+    if (w->n_prims && !w->prim_gate) return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_f64: plane prim_gate is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running f64 render may read the old planes
+    for (void *p : s->f64_allocs) (void)hipFree(p);
+    s->f64_allocs.clear();
+    s->has_f64 = false;
+    for (const Plane &p : planes) {
+        void *dp = nullptr;
+        HIP_TRY(hipMalloc(&dp, (p.n ? p.n : 1) * sizeof(double)));
+        s->f64_allocs.push_back(dp);
+        if (p.n) HIP_TRY(hipMemcpy(dp, p.src, p.n * sizeof(double), hipMemcpyHostToDevice));
+        *p.dst = static_cast<const double *>(dp);
+    }
+    s->f64 = d;
+    s->has_f64 = true;
+    return RTMI_OK;
+}
+
+extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const rtmi_render_params *p_in, double t_min,
+                               double *out_linear, uint8_t *out_rgb8, uint64_t *out_path_sig, rtmi_stats *stats) {
+    if (!s || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    rtmi_render_params p = *p_in;
+    if (out_path_sig) p.flags |= RTMI_FLAG_PATH_SIG;
+    if (p.tile_world != 1) return fail(RTMI_ERR_INVALID, "rtmi_render_f64 renders the whole image: tile_world must be 1");
+    const uint32_t unsupported = RTMI_FLAG_PROGRESSIVE | RTMI_FLAG_ASYNC | RTMI_FLAG_BLOCK_COOP | RTMI_FLAG_PROFILE | RTMI_FLAG_TEST_OVERFLOW;
+    if (p.flags & unsupported) return fail(RTMI_ERR_UNSUPPORTED, "rtmi_render_f64: PROGRESSIVE, ASYNC, BLOCK_COOP, PROFILE and TEST_OVERFLOW are not supported in the f64 mode");
+    if (s->needs_insd) return fail(RTMI_ERR_UNSUPPORTED, "rtmi_render_f64: scenes with DEFERRED, LISTSCAN or NESTED_MEDIUM items are not supported in the f64 mode");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_f64) return fail(RTMI_ERR_INVALID, "rtmi_render_f64: no f64 planes attached (rtmi_scene_attach_f64)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = ensure_streams(s))) return rc;
+    hipStream_t st = s->stream;
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
+    const uint32_t ntiles = local_tiles_of(&p, 0);
+    const bool sig = (p.flags & RTMI_FLAG_PATH_SIG) != 0u;
+    // passes (rtmi_f64_plan.hpp): RTMI_SAMPLE_SLOT_BYTES_F64 per pixel sample, at most 45 GiB and 2^32 - 1 slots per pass;
+    // the default budget is half the free HBM
+    const size_t per_sample = (size_t)ntiles * 64 * RTMI_SAMPLE_SLOT_BYTES_F64;
+    size_t free_b = 0;
+    if (!p.sample_buffer_bytes) {
+        size_t total_b = 0;
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    }
+    uint32_t chunk_spp = 0, pass_ns = 0;
+    if (!rtmi_f64_plan(ntiles, p.ns, p.sample_buffer_bytes, free_b, (uint64_t)s->slots * 4u, p.spp_chunks, chunk_spp, pass_ns))
+        return fail(RTMI_ERR_UNSUPPORTED, "rtmi_render_f64: image too large for one sample per pass");
+    // call-local device memory, freed on every return path
+    struct Scratch {
+        std::vector<void *> v;
+        ~Scratch() { for (void *q : v) (void)hipFree(q); }
+        int get(size_t bytes, void **out) {
+            *out = nullptr;
+            if (hipMalloc(out, bytes ? bytes : 1) != hipSuccess) return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc failed");
+            v.push_back(*out);
+            return RTMI_OK;
+        }
+    } scratch;
+    double *d_samples = nullptr, *d_acc = nullptr, *d_lin = nullptr;
+    uint32_t *d_q = nullptr, *d_queue = nullptr;
+    unsigned long long *d_sig = nullptr;
+    const size_t texels = (size_t)ntiles * 64;
+    if ((size_t)pass_ns * per_sample > s->f64_samples_bytes) { // the handle's buffer grows to the largest pass planned
+        if (s->f64_samples) { HIP_TRY(hipFree(s->f64_samples)); s->f64_samples = nullptr; s->f64_samples_bytes = 0; }
+        if (hipMalloc(reinterpret_cast<void **>(&s->f64_samples), (size_t)pass_ns * per_sample) != hipSuccess)
+            return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc of the per-sample buffer failed");
+        s->f64_samples_bytes = (size_t)pass_ns * per_sample;
+    }
+    d_samples = s->f64_samples;
+    if ((rc = scratch.get(texels * 3 * sizeof(double), reinterpret_cast<void **>(&d_acc)))) return rc;
+    if ((rc = scratch.get(texels * 3 * sizeof(double), reinterpret_cast<void **>(&d_lin)))) return rc;
+    if ((rc = scratch.get(texels * sizeof(uint32_t), reinterpret_cast<void **>(&d_q)))) return rc;
+    if ((rc = scratch.get(sizeof(uint32_t), reinterpret_cast<void **>(&d_queue)))) return rc;
+    if (sig) {
+        if ((rc = scratch.get(texels * sizeof(unsigned long long), reinterpret_cast<void **>(&d_sig)))) return rc;
+        HIP_TRY(hipMemsetAsync(d_sig, 0, texels * sizeof(unsigned long long), st));
+    }
+    DevParams P{};
+    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth;
+    P.t_min = (float)t_min;
+    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
+    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p); P.ntiles_local = ntiles;
+    P.chunk_spp = chunk_spp;
+    P.pass_stride = pass_ns;
+    P.path_sig = d_sig;
+    P.shade_threshold = p.shade_threshold ? p.shade_threshold : 40u;
+    if (P.shade_threshold > 64u) P.shade_threshold = 64u;
+    P.queue = d_queue;
+    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
+    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    DevParamsF64 Q{};
+    Q.t_min = t_min;
+    Q.samples = d_samples;
+    DevCameraF64 C{};
+    C.origin = D3{cam->origin[0], cam->origin[1], cam->origin[2]};
+    C.llc = D3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
+    C.horizontal = D3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
+    C.vertical = D3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
+    C.u = D3{cam->u[0], cam->u[1], cam->u[2]};
+    C.v = D3{cam->v[0], cam->v[1], cam->v[2]};
+    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    const uint32_t blocks = (uint32_t)(s->slots / 20) * 4u * 2u; // CUs x 4 SIMDs x 2 wavefronts (the kernel's occupancy: 255 VGPRs)
+    HIP_TRY(hipEventRecord(s->ev[0], st));
+    float ms_render = 0.0f;
+    for (uint32_t s0 = 0; s0 < p.ns; s0 += pass_ns) {
+        const uint32_t cnt = p.ns - s0 < pass_ns ? p.ns - s0 : pass_ns;
+        P.pass_s0 = s0; P.pass_cnt = cnt;
+        P.nchunks = (cnt + chunk_spp - 1) / chunk_spp;
+        HIP_TRY(hipMemsetAsync(d_queue, 0, sizeof(uint32_t), st));
+        HIP_TRY(hipEventRecord(s->ev[1], st));
+        HIP_TRY(rtmi_f64_launch_render(sig, blocks, st, s->dev, s->f64, C, P, Q));
+        HIP_TRY(hipEventRecord(s->ev[2], st));
+        HIP_TRY(rtmi_f64_launch_resolve(st, d_samples, d_acc, d_lin, d_q, P, s0 == 0, s0 + cnt >= p.ns));
+        HIP_TRY(hipEventSynchronize(s->ev[2]));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+        ms_render += ms;
+    }
+    HIP_TRY(hipEventRecord(s->ev[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::vector<double> h_lin(texels * 3);
+    std::vector<uint32_t> h_q(texels);
+    std::vector<unsigned long long> h_sig(sig ? texels : 0);
+    HIP_TRY(hipMemcpy(h_lin.data(), d_lin, texels * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_q.data(), d_q, texels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (sig) HIP_TRY(hipMemcpy(h_sig.data(), d_sig, texels * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    // un-tiling: texel = tile * 64 + ly * 8 + lx, tiles counted from the top-left; row 0 of the outputs = top row
+    const uint32_t txn = tiles_x_of(&p);
+    for (uint32_t row = 0; row < p.ny; row++)
+        for (uint32_t x = 0; x < p.nx; x++) {
+            const size_t t = (size_t)(row / RTMI_TILE) * txn + x / RTMI_TILE, k = t * 64 + (row % RTMI_TILE) * 8 + x % RTMI_TILE;
+            const size_t o = (size_t)row * p.nx + x;
+            if (out_linear) for (int ch = 0; ch < 3; ch++) out_linear[3 * o + ch] = h_lin[3 * k + ch];
+            if (out_rgb8) for (int ch = 0; ch < 3; ch++) out_rgb8[3 * o + ch] = (uint8_t)((h_q[k] >> (8 * ch)) & 255u);
+            if (out_path_sig) out_path_sig[o] = h_sig[k];
+        }
+    if (stats) {
+        float ms_all = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[1]));
+        fill_stats(s, &p, stats, ms_render, ms_all);
+        stats->kernel = RTMI_KERNEL_PERLANE;
+    }
+    return RTMI_OK;
+}
+
+extern "C" int rtmi_probe_math_f64(int op, const double *x, const double *y, double *out, uint32_t n) {
+    if (op < 0 || op > 5) return fail(RTMI_ERR_INVALID, "rtmi_probe_math_f64: unknown op");
+    if (!x || !out || ((op == 2 || op == 4) && !y)) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (n == 0) return RTMI_OK;
+    if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
+    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    const size_t bytes = (size_t)n * sizeof(double);
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dx), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dy), bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dout), bytes);
+    if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rtmi_f64_launch_probe(op, dx, dy, dout, n);
+    if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
+    if (dx) (void)hipFree(dx);
+    if (dy) (void)hipFree(dy);
+    if (dout) (void)hipFree(dout);
+    if (e != hipSuccess) return fail(RTMI_ERR_DEVICE, std::string("rtmi_probe_math_f64: ") + hipGetErrorString(e));
     return RTMI_OK;
 }

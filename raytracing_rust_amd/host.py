@@ -118,23 +118,76 @@ class Scene:
         }
         return out
 
-    def upload(self, device=0):
+    def desc_f64(self):
+        """The double planes of the f64 render mode (rtmi_scene_f64, include/rtmi_f64.h)."""
+        d = abi.SceneF64()
+        self.host._check(self.host.lib.rth_lowered_desc_f64(self.h, C.byref(d)))
+        return d
+
+    def arrays_f64(self):
+        """numpy copies of the double planes (for CPU tests of the wide lowering)."""
+        d = self.desc_f64()
+
+        def view(ptr, n, cols):
+            if n == 0:
+                return np.zeros((0, cols))
+            return np.ctypeslib.as_array(ptr, shape=(n * cols,)).copy().reshape(n, cols)
+
+        return {"prim_a": view(d.prim_a, d.n_prims, 4), "prim_b": view(d.prim_b, d.n_prims, 4),
+                "prim_dt": view(d.prim_dt, d.n_prims, 1)[:, 0], "prim_gate": view(d.prim_gate, d.n_prims, 8),
+                "nodes": view(d.nodes, d.n_nodes, 12), "xforms": view(d.xforms, d.n_xforms, 4),
+                "item_neg_inv_density": view(d.item_neg_inv_density, d.n_items, 1)[:, 0],
+                "item_root": view(d.item_root, d.n_items, 6), "material_param": view(d.material_param, d.n_materials, 1)[:, 0],
+                "texture_f": view(d.texture_f, d.n_textures, 4), "perlin_ranvec": view(d.perlin_ranvec, d.n_perlin, 768)}
+
+    def upload(self, device=0, f64=False):
+        """Copies the scene to `device`; f64=True also attaches the double planes of the f64 render mode."""
         self.host._check(self.host.lib.rth_upload(self.h, device))
         self.uploaded = True
+        self.f64_attached = False
+        if f64:
+            self.attach_f64()
         return self
 
-    def render(self, cam, nx, ny, ns, sig=False, out=None, **kw):
+    def attach_f64(self):
+        """Attaches the double planes to the uploaded handle (rtmi_scene_attach_f64)."""
+        self.host._check(self.host.lib.rth_attach_f64(self.h))
+        self.f64_attached = True
+        return self
+
+    def render(self, cam, nx, ny, ns, sig=False, out=None, precision="f32", **kw):
         """Blocking whole-image render -> dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], stats[, sig u64 [ny,nx]]).
-        `out` = (linear, rgb8) arrays to reuse."""
+        `out` = (linear, rgb8) arrays to reuse.  precision="f64": the f64 render mode (include/rtmi_f64.h) — linear is
+        float64, t_min (default 0.001) is passed as a double; the double planes are attached on first use."""
         if not self.uploaded:
             self.upload(kw.pop("device", 0))
         kw.pop("device", None)
+        if precision == "f64":
+            return self._render_f64(cam, nx, ny, ns, sig, **kw)
+        if precision != "f32":
+            raise ValueError("precision must be 'f32' or 'f64'")
         p = default_params(nx, ny, ns, **kw)
         lin, rgb = out if out is not None else (np.zeros((ny, nx, 3), np.float32), np.zeros((ny, nx, 3), np.uint8))
         sg = np.zeros((ny, nx), np.uint64) if sig else None
         st = abi.Stats()
         self.host._check(self.host.lib.rth_render(self.h, cam.h, C.byref(p), lin.ctypes.data, rgb.ctypes.data,
                                                    sg.ctypes.data if sig else None, C.byref(st)))
+        out = {"linear": lin, "rgb8": rgb, "stats": _stats(st)}
+        if sig:
+            out["sig"] = sg
+        return out
+
+    def _render_f64(self, cam, nx, ny, ns, sig, **kw):
+        if not getattr(self, "f64_attached", False):
+            self.attach_f64()
+        t_min = float(kw.get("t_min", 0.001))
+        p = default_params(nx, ny, ns, **kw)
+        lin = np.zeros((ny, nx, 3), np.float64)
+        rgb = np.zeros((ny, nx, 3), np.uint8)
+        sg = np.zeros((ny, nx), np.uint64) if sig else None
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_f64(self.h, cam.h, C.byref(p), t_min, lin.ctypes.data, rgb.ctypes.data,
+                                                       sg.ctypes.data if sig else None, C.byref(st)))
         out = {"linear": lin, "rgb8": rgb, "stats": _stats(st)}
         if sig:
             out["sig"] = sg
@@ -220,8 +273,18 @@ def _stats(st):
 
 
 class _Camera(_Obj):
-    def render(self, world, nx, ny, ns, seed=42, flags=0, device=0):
-        """Camera::render(world, nx, ny, ns): lower + upload + render + free, like one create_image call."""
+    def render(self, world, nx, ny, ns, seed=42, flags=0, device=0, precision="f32"):
+        """Camera::render(world, nx, ny, ns): lower + upload + render + free, like one create_image call.
+        precision="f64": the f64 render mode (include/rtmi_f64.h); linear is float64."""
+        if precision == "f64":  # rth_camera_render_f64: the device handle and its planes are freed after the render
+            lin = np.zeros((ny, nx, 3), np.float64)
+            rgb = np.zeros((ny, nx, 3), np.uint8)
+            st = abi.Stats()
+            self.host._check(self.host.lib.rth_camera_render_f64(self.h, world.h, nx, ny, ns, seed, flags, device,
+                                                                  lin.ctypes.data, rgb.ctypes.data, C.byref(st)))
+            return {"linear": lin, "rgb8": rgb, "stats": _stats(st)}
+        if precision != "f32":
+            raise ValueError("precision must be 'f32' or 'f64'")
         lin = np.zeros((ny, nx, 3), np.float32)
         rgb = np.zeros((ny, nx, 3), np.uint8)
         st = abi.Stats()
@@ -242,6 +305,11 @@ class _Camera(_Obj):
     def lower(self):
         c = abi.Camera()
         self.host._check(self.host.lib.rth_camera_lower(self.h, C.byref(c)))
+        return c
+
+    def lower_f64(self):
+        c = abi.CameraF64()
+        self.host._check(self.host.lib.rth_camera_lower_f64(self.h, C.byref(c)))
         return c
 
 

@@ -490,7 +490,8 @@ bool SceneBuilder::texture_needs_uv(int tex) const {
 int SolidTexture::lower(SceneBuilder &b) const {
     rtmi_texture t{};
     t.kind = RTMI_TEX_SOLID; t.f0 = (float)color_.x; t.f1 = (float)color_.y; t.f2 = (float)color_.z;
-    return b.add_texture(t);
+    const double f[4] = {color_.x, color_.y, color_.z, 0.0};
+    return b.add_texture(t, f);
 }
 int CheckerTexture::lower(SceneBuilder &b) const {
     rtmi_texture t{};
@@ -508,11 +509,13 @@ int NoiseTexture::lower(SceneBuilder &b) const {
         pn.perm[i] = (int32_t)noise_.perm_x_[(size_t)i];
         pn.perm[256 + i] = (int32_t)noise_.perm_y_[(size_t)i];
         pn.perm[512 + i] = (int32_t)noise_.perm_z_[(size_t)i];
+        for (int k = 0; k < 3; k++) b.out.wide.perlin_ranvec.push_back(noise_.ran_vec_[(size_t)i][k]);
     }
     b.out.perlin.push_back(pn);
     rtmi_texture t{};
     t.kind = RTMI_TEX_NOISE; t.i0 = (int32_t)b.out.perlin.size() - 1; t.f0 = (float)scale_;
-    return b.add_texture(t);
+    const double f[4] = {scale_, 0.0, 0.0, 0.0};
+    return b.add_texture(t, f);
 }
 int ImageTexture::lower(SceneBuilder &b) const {
     if ((size_t)nx_ * ny_ * 3 != data_.size() || nx_ == 0 || ny_ == 0) throw Panic("ImageTexture: data size != 3*nx*ny");
@@ -529,7 +532,7 @@ static int lower_mat(SceneBuilder &b, int kind, const Texture *tex, double param
     m.kind = kind; m.param = (float)param;
     m.tex = tex ? b.texture_index(tex) : 0;
     m.flags = (tex && b.texture_needs_uv(m.tex)) ? RTMI_MATFLAG_NEEDS_UV : 0u;
-    return b.add_material(m);
+    return b.add_material(m, param);
 }
 int Lambertian::lower(SceneBuilder &b) const { return lower_mat(b, RTMI_MAT_LAMBERTIAN, albedo_.get(), 0.0); }
 int Metal::lower(SceneBuilder &b) const { return lower_mat(b, RTMI_MAT_METAL, albedo_.get(), fuzz_); }
@@ -546,7 +549,8 @@ static const Hittable *strip_flips(const Hittable *h, bool &flip) {
 // Rotate (rotate.rs:21-28), in any order and number — and returns the innermost object.  `chain` (optional) receives the
 // transforms outermost first, exactly as lower_item records an item's chain: Traslate<H> / Rotate<H> are generic over
 // any Hittable, so the reference lets them sit anywhere, e.g. as the children of a BVHNode (bvh.rs:11-12).
-static const Hittable *strip_wrappers(const Hittable *h, bool &flip, std::vector<rtmi_xform> *chain) {
+static const Hittable *strip_wrappers(const Hittable *h, bool &flip, std::vector<rtmi_xform> *chain,
+                                      std::vector<double> *chain_w = nullptr) { // chain_w: x, y, z, 0 of each, before rounding
     for (;;) {
         if (auto f = dynamic_cast<const FlipNormals *>(h)) { flip = !flip; h = f->inner().get(); continue; }
         if (auto t = dynamic_cast<const Traslate *>(h)) {
@@ -554,6 +558,7 @@ static const Hittable *strip_wrappers(const Hittable *h, bool &flip, std::vector
                 rtmi_xform x{};
                 x.kind = RTMI_XF_TRANSLATE; x.x = (float)t->offset_.x; x.y = (float)t->offset_.y; x.z = (float)t->offset_.z;
                 chain->push_back(x);
+                if (chain_w) chain_w->insert(chain_w->end(), {t->offset_.x, t->offset_.y, t->offset_.z, 0.0});
             }
             h = t->hitable_.get();
             continue;
@@ -563,6 +568,7 @@ static const Hittable *strip_wrappers(const Hittable *h, bool &flip, std::vector
                 rtmi_xform x{};
                 x.kind = RTMI_XF_ROTATE_X + (int)r->axis_; x.x = (float)r->sin_theta_; x.y = (float)r->cos_theta_;
                 chain->push_back(x);
+                if (chain_w) chain_w->insert(chain_w->end(), {r->sin_theta_, r->cos_theta_, 0.0, 0.0});
             }
             h = r->hittable_.get();
             continue;
@@ -598,17 +604,21 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
     // an instanced primitive: its own Traslate / Rotate chain (outermost first) goes to `xforms`, referenced from the
     // meta word; FlipNormals anywhere in the chain only toggles the flag (negation commutes with both)
     std::vector<rtmi_xform> chain;
-    const Hittable &h = *strip_wrappers(&h0, flip, &chain);
+    std::vector<double> chain_w;
+    const Hittable &h = *strip_wrappers(&h0, flip, &chain, &chain_w);
+    double Aw[4] = {0, 0, 0, 0}, Bw[4] = {0, 0, 0, 0}, dt_w = 1.0; // the same values in double (f64 render mode)
     m.flags = flip ? RTMI_PRIMFLAG_FLIP : 0u;
     if (!chain.empty()) {
         if (chain.size() > RTMI_PRIM_XF_MAX) throw Unsupported("more than 15 Traslate/Rotate wrappers around one primitive");
         if (out.xforms.size() + chain.size() >= (1u << 20)) throw Unsupported("too many instance transforms");
         m.flags |= ((uint32_t)chain.size() << RTMI_PRIMFLAG_XF_COUNT_SHIFT) | ((uint32_t)out.xforms.size() << RTMI_PRIMFLAG_XF_FIRST_SHIFT);
         out.xforms.insert(out.xforms.end(), chain.begin(), chain.end());
+        out.wide.xforms.insert(out.wide.xforms.end(), chain_w.begin(), chain_w.end());
     }
     m.inv_dt = 0.0f;
     if (auto s = dynamic_cast<const Sphere *>(&h)) {
         A[0] = (float)s->center_.x; A[1] = (float)s->center_.y; A[2] = (float)s->center_.z; A[3] = (float)s->radius_;
+        Aw[0] = s->center_.x; Aw[1] = s->center_.y; Aw[2] = s->center_.z; Aw[3] = s->radius_;
         m.material = material_index(s->material_.get());
         if (force_moving) { // c0 + (time - 0)*1 * 0 == c0 exactly: same bits, one code path in the BVH
             m.type = RTMI_PRIM_MSPHERE; m.inv_dt = 1.0f;
@@ -622,17 +632,23 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
         A[0] = c0[0]; A[1] = c0[1]; A[2] = c0[2]; A[3] = (float)ms->radius_;
         B[0] = c1[0] - c0[0]; B[1] = c1[1] - c0[1]; B[2] = c1[2] - c0[2]; B[3] = t0;
         m.inv_dt = 1.0f / (t1 - t0);
+        Aw[0] = ms->center0_.x; Aw[1] = ms->center0_.y; Aw[2] = ms->center0_.z; Aw[3] = ms->radius_;
+        Bw[0] = ms->center1_.x - ms->center0_.x; Bw[1] = ms->center1_.y - ms->center0_.y; Bw[2] = ms->center1_.z - ms->center0_.z;
+        Bw[3] = ms->time0_;
+        dt_w = ms->time1_ - ms->time0_; // the divisor of sphere.rs:115-118
         m.type = RTMI_PRIM_MSPHERE;
         m.material = material_index(ms->material_.get());
     } else if (auto r = dynamic_cast<const Rect *>(&h)) {
         A[0] = (float)r->x0_; A[1] = (float)r->y0_; A[2] = (float)r->x1_; A[3] = (float)r->y1_;
         B[0] = (float)r->k_;
+        Aw[0] = r->x0_; Aw[1] = r->y0_; Aw[2] = r->x1_; Aw[3] = r->y1_; Bw[0] = r->k_;
         m.flags |= ((uint32_t)r->plane_) << RTMI_PRIMFLAG_PLANE_SHIFT;
         m.type = RTMI_PRIM_RECT;
         m.material = material_index(r->material_.get());
     } else if (auto c = dynamic_cast<const Cube *>(&h)) {
         A[0] = (float)c->p_min_.x; A[1] = (float)c->p_min_.y; A[2] = (float)c->p_min_.z; A[3] = (float)c->p_max_.x;
         B[0] = (float)c->p_max_.y; B[1] = (float)c->p_max_.z;
+        Aw[0] = c->p_min_.x; Aw[1] = c->p_min_.y; Aw[2] = c->p_min_.z; Aw[3] = c->p_max_.x; Bw[0] = c->p_max_.y; Bw[1] = c->p_max_.z;
         m.type = RTMI_PRIM_CUBE;
         m.material = material_index(c->material_.get());
     } else {
@@ -644,6 +660,10 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
     const float big = 3.40282346638528859811704183484516925e+38f;
     const float gate[8] = {-big, -big, -big, 0.0f, big, big, big, 0.0f}; // no gate unless a BVH sets one
     out.prim_gate.insert(out.prim_gate.end(), gate, gate + 8);
+    out.wide.prim_a.insert(out.wide.prim_a.end(), Aw, Aw + 4);
+    out.wide.prim_b.insert(out.wide.prim_b.end(), Bw, Bw + 4);
+    out.wide.prim_dt.push_back(dt_w);
+    out.wide.prim_gate.insert(out.wide.prim_gate.end(), gate, gate + 8);
     out.prim_box.push_back(AABB(Vec3(0, 0, 0), Vec3(0, 0, 0)));
     out.prim_has_box.push_back(0);
     return (int)out.prim_meta.size() - 1;
@@ -654,6 +674,10 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
 static float sat_f32(double v) {
     const double big = 3.40282346638528859811704183484516925e+38;
     return v > big ? (float)big : (v < -big ? (float)-big : (float)v);
+}
+// the same box in double, unrounded (f64 render mode): min.xyz, max.xyz at w[0..5]
+static void put_box_w(double *w, const AABB &b) {
+    w[0] = b.min.x; w[1] = b.min.y; w[2] = b.min.z; w[3] = b.max.x; w[4] = b.max.y; w[5] = b.max.z;
 }
 static void put_box(float mn[3], float mx[3], const AABB &b) {
     mn[0] = sat_f32(b.min.x); mn[1] = sat_f32(b.min.y); mn[2] = sat_f32(b.min.z);
@@ -847,6 +871,8 @@ int32_t SceneBuilder::lower_bvh(const BVHNode &n, uint32_t depth, bool force_mov
     if (depth > out.max_bvh_depth) out.max_bvh_depth = depth;
     const int32_t id = (int32_t)out.nodes.size();
     out.nodes.push_back(rtmi_bvh_node{});
+    out.wide.nodes.resize(out.wide.nodes.size() + 12, 0.0);
+    const auto wnode = [&]() { return &out.wide.nodes[(size_t)id * 12]; }; // lmin lmax rmin rmax
     int32_t child[2] = {0, 0};
     const size_t pend_begin = pending_media_.size();
     for (int c = 0; c < 2; c++) {
@@ -854,6 +880,7 @@ int32_t SceneBuilder::lower_bvh(const BVHNode &n, uint32_t depth, bool force_mov
             child[1] = child[0];
             rtmi_bvh_node &me = out.nodes[(size_t)id];
             for (int k = 0; k < 3; k++) { me.rmin[k] = me.lmin[k]; me.rmax[k] = me.lmax[k]; }
+            for (int k = 0; k < 6; k++) wnode()[6 + k] = wnode()[k];
             // the reference evaluates the object on both sides (bvh.rs:73-74): for its primitives that is the same answer
             // twice, but every medium below it is evaluated — and draws — a second time, after all of the first visit's
             const size_t pend_end = pending_media_.size();
@@ -873,23 +900,26 @@ int32_t SceneBuilder::lower_bvh(const BVHNode &n, uint32_t depth, bool force_mov
             child[c] = lower_bvh(*sub, depth + 1, force_moving, pad, unbounded_leaves, flip_all != flip);
             rtmi_bvh_node &me = out.nodes[(size_t)id];
             put_box(c == 0 ? me.lmin : me.rmin, c == 0 ? me.lmax : me.rmax, sub->bbox_);
+            put_box_w(wnode() + 6 * c, sub->bbox_);
         } else if (auto lst = dynamic_cast<const HittableList *>(h)) {
             // a HittableList as a child (bvh.rs:11-12 takes any Hittable): a subtree of always-passing nodes over its members
             AABB cb(Vec3(0, 0, 0), Vec3(0, 0, 0));
             child[c] = lower_list_leaf(*lst, n, depth + 1, flip != flip_all, force_moving, pad, unbounded_leaves, cb);
             rtmi_bvh_node &me = out.nodes[(size_t)id];
             put_box(c == 0 ? me.lmin : me.rmin, c == 0 ? me.lmax : me.rmax, cb);
+            put_box_w(wnode() + 6 * c, cb);
         } else {
             AABB lb(Vec3(0, 0, 0), Vec3(0, 0, 0));
             child[c] = lower_leaf(*h, n, flip != flip_all, force_moving, pad, unbounded_leaves, lb);
             rtmi_bvh_node &me = out.nodes[(size_t)id];
             put_box(c == 0 ? me.lmin : me.rmin, c == 0 ? me.lmax : me.rmax, lb);
+            put_box_w(wnode() + 6 * c, lb);
         }
     }
     {
         rtmi_bvh_node &me = out.nodes[(size_t)id];
-        if (child[0] == RTMI_NO_SUBTREE) { child[0] = child[1]; for (int k = 0; k < 3; k++) { me.lmin[k] = me.rmin[k]; me.lmax[k] = me.rmax[k]; } }
-        if (child[1] == RTMI_NO_SUBTREE) { child[1] = child[0]; for (int k = 0; k < 3; k++) { me.rmin[k] = me.lmin[k]; me.rmax[k] = me.lmax[k]; } }
+        if (child[0] == RTMI_NO_SUBTREE) { child[0] = child[1]; for (int k = 0; k < 3; k++) { me.lmin[k] = me.rmin[k]; me.lmax[k] = me.rmax[k]; } for (int k = 0; k < 6; k++) wnode()[k] = wnode()[6 + k]; }
+        if (child[1] == RTMI_NO_SUBTREE) { child[1] = child[0]; for (int k = 0; k < 3; k++) { me.rmin[k] = me.lmin[k]; me.rmax[k] = me.lmax[k]; } for (int k = 0; k < 6; k++) wnode()[6 + k] = wnode()[k]; }
         me.left = child[0];
         me.right = child[1];
     }
@@ -907,6 +937,9 @@ int32_t SceneBuilder::lower_leaf(const Hittable &hh, const BVHNode &n, bool flip
         put_box(gmn, gmx, n.bbox_);
         float *g = &out.prim_gate[(size_t)prim * 8];
         g[0] = gmn[0]; g[1] = gmn[1]; g[2] = gmn[2]; g[4] = gmx[0]; g[5] = gmx[1]; g[6] = gmx[2];
+        double *gw = &out.wide.prim_gate[(size_t)prim * 8], bw[6];
+        put_box_w(bw, n.bbox_);
+        gw[0] = bw[0]; gw[1] = bw[1]; gw[2] = bw[2]; gw[4] = bw[3]; gw[5] = bw[4]; gw[6] = bw[5];
         AABB tbx(Vec3(0, 0, 0), Vec3(0, 0, 0));
         if (true_bounds(h, tbx)) { out.prim_box[(size_t)prim] = tbx; out.prim_has_box[(size_t)prim] = 1; }
     }
@@ -978,11 +1011,13 @@ int32_t SceneBuilder::lower_list_leaf(const HittableList &l, const BVHNode &hold
         if (dp > out.max_bvh_depth) out.max_bvh_depth = dp;
         const int32_t id = (int32_t)out.nodes.size();
         out.nodes.push_back(rtmi_bvh_node{});
+        out.wide.nodes.resize(out.wide.nodes.size() + 12, 0.0);
         const size_t mid = lo + (hi - lo) / 2;
         AABB bl(Vec3(0, 0, 0), Vec3(0, 0, 0)), br(Vec3(0, 0, 0), Vec3(0, 0, 0));
         const int32_t cl = build(lo, mid, dp + 1, bl), cr = build(mid, hi, dp + 1, br);
         rtmi_bvh_node &me = out.nodes[(size_t)id];
         put_box(me.lmin, me.lmax, bl); put_box(me.rmin, me.rmax, br);
+        put_box_w(&out.wide.nodes[(size_t)id * 12], bl); put_box_w(&out.wide.nodes[(size_t)id * 12 + 6], br);
         me.left = cl; me.right = cr;
         bo = everything; // an internal node of the list: no box test in the reference
         return id;
@@ -1230,7 +1265,7 @@ void SceneBuilder::lower_scan_group(const Hittable &top, const DeferredMedium &d
     end.first = deferred.rank; // leaves of the enclosing tree that precede the list in traversal order (ties)
     end.alt_first = -1;
     end.flags = RTMI_ITEMFLAG_DEFERRED | RTMI_ITEMFLAG_LISTSCAN_END;
-    out.items.push_back(end);
+    push_item(end, 0.0, nullptr);
     run_item_ = -1;
 }
 
@@ -1241,11 +1276,15 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
     it.xform_first = (int32_t)out.xforms.size();
     bool flip = false, medium = false, nested = false;
     float inner_neg_inv_density = 0.0f;
+    double inner_nid_w = 0.0, nid_w = 0.0, root_w[6] = {0, 0, 0, 0, 0, 0}; // the same values in double (f64 render mode)
     uint32_t medium_outer = 0;
     const Hittable *h = &top;
     if (deferred) { // a child of a BVHNode lowered as an item: it sits inside the transforms of that BVH item — a copy of them first —
         flip = deferred->flip; // ... and inside the FlipNormals around that item or around its ancestors within the tree
-        for (int k = 0; k < deferred->chain_count; k++) out.xforms.push_back(out.xforms[(size_t)(deferred->chain_first + k)]);
+        for (int k = 0; k < deferred->chain_count; k++) {
+            out.xforms.push_back(out.xforms[(size_t)(deferred->chain_first + k)]);
+            for (int q = 0; q < 4; q++) out.wide.xforms.push_back(out.wide.xforms[(size_t)(deferred->chain_first + k) * 4 + q]);
+        }
         it.xform_count = deferred->chain_count;
     }
     for (;;) { // peel wrappers, outermost first
@@ -1255,7 +1294,8 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
                 if (nested) throw Unsupported("ConstantMedium nested more than once is not lowered");
                 if ((uint32_t)it.xform_count != medium_outer) throw Unsupported("Traslate / Rotate between a ConstantMedium and the ConstantMedium that is its boundary is not lowered");
                 nested = true;
-                inner_neg_inv_density = -(1.0f / (float)m->density_); // (its phase function never shows: the hit record is the outer medium's)
+                inner_neg_inv_density = -(1.0f / (float)m->density_);
+                inner_nid_w = -(1.0 / m->density_); // (its phase function never shows: the hit record is the outer medium's)
                 h = m->boundary_.get();
                 continue;
             }
@@ -1264,6 +1304,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
             medium = true;
             it.medium_material = material_index(m->phase_function_.get());
             it.neg_inv_density = -(1.0f / (float)m->density_);
+            nid_w = -(1.0 / m->density_);
             h = m->boundary_.get();
             continue;
         }
@@ -1271,6 +1312,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
             rtmi_xform x{};
             x.kind = RTMI_XF_TRANSLATE; x.x = (float)t->offset_.x; x.y = (float)t->offset_.y; x.z = (float)t->offset_.z;
             out.xforms.push_back(x); it.xform_count++;
+            out.wide.xforms.insert(out.wide.xforms.end(), {t->offset_.x, t->offset_.y, t->offset_.z, 0.0});
             h = t->hitable_.get();
             continue;
         }
@@ -1278,6 +1320,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
             rtmi_xform x{};
             x.kind = RTMI_XF_ROTATE_X + (int)r->axis_; x.x = (float)r->sin_theta_; x.y = (float)r->cos_theta_;
             out.xforms.push_back(x); it.xform_count++;
+            out.wide.xforms.insert(out.wide.xforms.end(), {r->sin_theta_, r->cos_theta_, 0.0, 0.0});
             h = r->hittable_.get();
             continue;
         }
@@ -1290,6 +1333,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
         rtmi_xform r{};
         r.kind = RTMI_XF_INNER_MEDIUM; r.x = inner_neg_inv_density;
         out.xforms.push_back(r);
+        out.wide.xforms.insert(out.wide.xforms.end(), {inner_nid_w, 0.0, 0.0, 0.0});
     };
     if (!deferred) push_inner_medium();
     if (deferred) {
@@ -1307,6 +1351,9 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
             g0.kind = RTMI_XF_GATE_MIN; g0.x = gmn[0]; g0.y = gmn[1]; g0.z = gmn[2];
             g1.kind = RTMI_XF_GATE_MAX; g1.x = gmx[0]; g1.y = gmx[1]; g1.z = gmx[2];
             out.xforms.push_back(g0); out.xforms.push_back(g1);
+            double bw[6];
+            put_box_w(bw, deferred->gate);
+            out.wide.xforms.insert(out.wide.xforms.end(), {bw[0], bw[1], bw[2], 0.0, bw[3], bw[4], bw[5], 0.0});
         }
         push_inner_medium();
     }
@@ -1328,6 +1375,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
         pending_media_.clear();
         it.kind = RTMI_ITEM_BVH;
         put_box(it.root_min, it.root_max, bvh->bbox_);
+        put_box_w(root_w, bvh->bbox_);
         double scale = 0.0;
         for (int k = 0; k < 3; k++) scale = std::fmax(scale, std::fmax(std::fabs(bvh->bbox_.min[k]), std::fabs(bvh->bbox_.max[k])));
         AABB tb(Vec3(0, 0, 0), Vec3(0, 0, 0));
@@ -1387,7 +1435,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
             it.flags = 0u;
             it.first = push_prim(*h, flip, false);
             it.count = 1;
-            out.items.push_back(it);
+            push_item(it, nid_w, root_w);
             run_item_ = (int)out.items.size() - 1;
             return;
         }
@@ -1404,12 +1452,15 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
         for (int32_t q = it.first; q < it.first + it.count; q++) {
             float *g = &out.prim_gate[(size_t)q * 8];
             g[0] = gmn[0]; g[1] = gmn[1]; g[2] = gmn[2]; g[4] = gmx[0]; g[5] = gmx[1]; g[6] = gmx[2];
+            double *gw = &out.wide.prim_gate[(size_t)q * 8], bw[6];
+            put_box_w(bw, deferred->gate);
+            gw[0] = bw[0]; gw[1] = bw[1]; gw[2] = bw[2]; gw[4] = bw[3]; gw[5] = bw[4]; gw[6] = bw[5];
         }
     }
     if (it.kind == RTMI_ITEM_BVH && !pending_media_.empty()) { // media that were children of this BVH: deferred items, in order
         if (medium) throw Unsupported("a ConstantMedium whose boundary BVHNode holds media or instanced subtrees is not lowered");
         if (!deferred) it.flags |= RTMI_ITEMFLAG_SAVE_T0; // (a deferred BVH item's own deferred children share its group's T0)
-        out.items.push_back(it);
+        push_item(it, nid_w, root_w);
         const std::vector<PendingMedium> pend = std::move(pending_media_);
         pending_media_.clear();
         for (const PendingMedium &pm : pend) {
@@ -1418,7 +1469,7 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
         }
         return;
     }
-    out.items.push_back(it);
+    push_item(it, nid_w, root_w);
 }
 
 void SceneBuilder::lower_world(const Hittable &world) {
@@ -1433,6 +1484,17 @@ void SceneBuilder::lower_world(const Hittable &world) {
     if (out.max_bvh_depth > RTMI_MAX_BVH_DEPTH) throw Unsupported("BVH deeper than RTMI_MAX_BVH_DEPTH");
 }
 
+rtmi_scene_f64 LoweredScene::desc_f64() const {
+    rtmi_scene_f64 d{};
+    d.n_items = (uint32_t)items.size(); d.n_prims = (uint32_t)prim_meta.size(); d.n_nodes = (uint32_t)nodes.size();
+    d.n_xforms = (uint32_t)xforms.size(); d.n_materials = (uint32_t)materials.size(); d.n_textures = (uint32_t)textures.size();
+    d.n_perlin = (uint32_t)perlin.size();
+    d.prim_a = wide.prim_a.data(); d.prim_b = wide.prim_b.data(); d.prim_dt = wide.prim_dt.data(); d.prim_gate = wide.prim_gate.data();
+    d.nodes = wide.nodes.data(); d.xforms = wide.xforms.data();
+    d.item_neg_inv_density = wide.item_nid.data(); d.item_root = wide.item_root.data();
+    d.material_param = wide.material_param.data(); d.texture_f = wide.texture_f.data(); d.perlin_ranvec = wide.perlin_ranvec.data();
+    return d;
+}
 rtmi_scene_desc LoweredScene::desc() const {
     rtmi_scene_desc d{};
     d.abi_version = RTMI_ABI_VERSION;
@@ -1492,6 +1554,14 @@ rtmi_camera Camera::lower() const {
     float *dst[6] = {c.origin, c.lower_left_corner, c.horizontal, c.vertical, c.u, c.v};
     for (int i = 0; i < 6; i++) { dst[i][0] = (float)src[i]->x; dst[i][1] = (float)src[i]->y; dst[i][2] = (float)src[i]->z; }
     c.time0 = (float)time0_; c.time1 = (float)time1_; c.lens_radius = (float)lens_radius_;
+    return c;
+}
+rtmi_camera_f64 Camera::lower_f64() const {
+    rtmi_camera_f64 c{};
+    const Vec3 *src[6] = {&origin_, &lower_left_corner_, &horizontal_, &vertical_, &u_, &v_};
+    double *dst[6] = {c.origin, c.lower_left_corner, c.horizontal, c.vertical, c.u, c.v};
+    for (int i = 0; i < 6; i++) { dst[i][0] = src[i]->x; dst[i][1] = src[i]->y; dst[i][2] = src[i]->z; }
+    c.time0 = time0_; c.time1 = time1_; c.lens_radius = lens_radius_;
     return c;
 }
 

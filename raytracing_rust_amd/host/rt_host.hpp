@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "rtmi.h"
+#include "rtmi_f64.h"
 
 namespace rt {
 
@@ -347,7 +348,14 @@ struct LoweredScene {
     // ray times for which every MovingSphere inside a BVH stays inside the boxes built for it (its own
     // [time0, time1]); outside, librtmi falls back from pruned to exact traversal
     float bvh_time_lo = -3.40282346638528859811704183484516925e+38f, bvh_time_hi = 3.40282346638528859811704183484516925e+38f;
+    // The same values before their rounding to fp32, for the f64 render mode (include/rtmi_f64.h): one entry per entry of
+    // the planes above, same indices
+    struct Wide {
+        std::vector<double> prim_a, prim_b, prim_dt, prim_gate, nodes, xforms, item_nid, item_root, material_param, texture_f,
+            perlin_ranvec;
+    } wide;
     rtmi_scene_desc desc() const;
+    rtmi_scene_f64 desc_f64() const;
 };
 
 #define RTMI_NO_SUBTREE (-1) /* lower_bvh: nothing but media below (they become deferred items).  Not a child reference:
@@ -356,8 +364,16 @@ class SceneBuilder {
   public:
     int texture_index(const Texture *t);   // lowers on first use
     int material_index(const Material *m); // lowers on first use
-    int add_texture(const rtmi_texture &t) { out.textures.push_back(t); return (int)out.textures.size() - 1; }
-    int add_material(const rtmi_material &m) { out.materials.push_back(m); return (int)out.materials.size() - 1; }
+    int add_texture(const rtmi_texture &t, const double *f = nullptr) { // f: f0..f3 before rounding (NULL: zeros)
+        out.textures.push_back(t);
+        for (int k = 0; k < 4; k++) out.wide.texture_f.push_back(f ? f[k] : 0.0);
+        return (int)out.textures.size() - 1;
+    }
+    int add_material(const rtmi_material &m, double param = 0.0) {
+        out.materials.push_back(m);
+        out.wide.material_param.push_back(param);
+        return (int)out.materials.size() - 1;
+    }
     bool texture_needs_uv(int tex) const;
     void lower_world(const Hittable &world);
     LoweredScene out;
@@ -369,6 +385,11 @@ class SceneBuilder {
     std::vector<PendingMedium> pending_media_;
     void collect_media(const Hittable *h, const BVHNode &parent, bool flip_all);
     void lower_item(const Hittable &h, const DeferredMedium *deferred = nullptr);
+    void push_item(const rtmi_item &it, double nid_w, const double *root_w) { // the item and its wide values (root_w: 6 or NULL)
+        out.items.push_back(it);
+        out.wide.item_nid.push_back(nid_w);
+        for (int k = 0; k < 6; k++) out.wide.item_root.push_back(root_w ? root_w[k] : 0.0);
+    }
     int push_prim(const Hittable &h, bool flip, bool force_moving);
     int32_t lower_bvh(const BVHNode &n, uint32_t depth, bool force_moving, double pad, bool unbounded_leaves, bool flip_all);
     int32_t lower_leaf(const Hittable &h, const BVHNode &n, bool flip, bool force_moving, double pad, bool unbounded_leaves, AABB &lb);
@@ -417,6 +438,7 @@ class Camera {
            double aperture, double focus_dist, double time0, double time1);
     Ray get_ray(double s, double t) const;
     rtmi_camera lower() const;
+    rtmi_camera_f64 lower_f64() const; // the same state in double (the f64 render mode)
     // The addition the north star asks for: the triple loop of create_image on the GPU.
     Image render(const Hittable &world, uint32_t nx, uint32_t ny, uint32_t ns, const RenderOptions &opt = {}) const;
     Vec3 origin_, lower_left_corner_, horizontal_, vertical_, u_, v_;

@@ -242,6 +242,31 @@ RTH_API int rth_render(void *lowered, void *cam, const rtmi_render_params *p, fl
         return RTH_OK;
     });
 }
+// ---- f64 render mode (include/rtmi_f64.h) ------------------------------------------------------------
+RTH_API int rth_lowered_desc_f64(void *lowered, rtmi_scene_f64 *out) {
+    return guard([&] { *out = LOW(lowered)->lowered->desc_f64(); return RTH_OK; });
+}
+RTH_API int rth_camera_lower_f64(void *cam, rtmi_camera_f64 *out) { return guard([&] { *out = CAM(cam).lower_f64(); return RTH_OK; }); }
+// attaches the lowered scene's double planes to its uploaded handle (rtmi_scene_attach_f64)
+RTH_API int rth_attach_f64(void *lowered) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_scene_f64 w = o->lowered->desc_f64();
+        if (int rc = rtmi_scene_attach_f64(o->dev, &w)) throw std::runtime_error(std::string("rtmi_scene_attach_f64: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+RTH_API int rth_render_f64(void *lowered, void *cam, const rtmi_render_params *p, double t_min, double *out_linear, uint8_t *out_rgb8,
+                           uint64_t *out_path_sig, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera_f64 c = CAM(cam).lower_f64();
+        if (rtmi_render_f64(o->dev, &c, p, t_min, out_linear, out_rgb8, out_path_sig, stats)) throw std::runtime_error(std::string("rtmi_render_f64: ") + rtmi_last_error());
+        return RTH_OK;
+    });
+}
 RTH_API int rth_render_device(void *lowered, void *cam, const rtmi_render_params *p, void *d_texels, void *stream,
                               rtmi_stats *stats) {
     return guard([&] {
@@ -339,6 +364,29 @@ RTH_API int rth_camera_render(void *cam, void *world, uint32_t nx, uint32_t ny, 
         if (out_linear) memcpy(out_linear, img.linear.data(), img.linear.size() * sizeof(float));
         if (out_rgb8) memcpy(out_rgb8, img.rgb8.data(), img.rgb8.size());
         if (stats) *stats = img.stats;
+        return RTH_OK;
+    });
+}
+
+// the f64 render mode in one call, like rth_camera_render: lower + create + attach + render + destroy (nothing stays resident)
+RTH_API int rth_camera_render_f64(void *cam, void *world, uint32_t nx, uint32_t ny, uint32_t ns, uint64_t seed, uint32_t flags,
+                                  int device, double *out_linear, uint8_t *out_rgb8, rtmi_stats *stats) {
+    return guard([&] {
+        const LoweredScene ls = lower_scene(*H(world));
+        const rtmi_scene_desc d = ls.desc();
+        const rtmi_scene_f64 w = ls.desc_f64();
+        rtmi_render_params p{};
+        p.nx = nx; p.ny = ny; p.ns = ns; p.max_depth = 50; p.t_min = 0.001f; p.flags = flags; p.seed = seed;
+        p.tile_rank = 0; p.tile_world = 1;
+        const rtmi_camera_f64 c = CAM(cam).lower_f64();
+        rtmi_scene *scene = nullptr;
+        if (int rc = rtmi_scene_create(&d, device, &scene))
+            throw std::runtime_error(std::string("rtmi_scene_create: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        int rc = rtmi_scene_attach_f64(scene, &w);
+        if (!rc) rc = rtmi_render_f64(scene, &c, &p, 0.001, out_linear, out_rgb8, nullptr, stats); // t_min: color.rs:7
+        const std::string err = rc ? rtmi_last_error() : "";
+        rtmi_scene_destroy(scene);
+        if (rc) throw std::runtime_error("rtmi_render_f64: " + err);
         return RTH_OK;
     });
 }
