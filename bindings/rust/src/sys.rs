@@ -429,3 +429,29 @@ extern "C" {
     /// the f64 kernel's sin / log / atan2 / asin / division / sqrt on the device
     pub fn rtmi_probe_math_f64(op: c_int, x: *const f64, y: *const f64, out: *mut f64, n: u32) -> c_int;
 }
+
+// ---- include/rtmi_adaptive.h: noise-targeted adaptive sampling -----------------------------------------------------------
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiAdaptive {
+    pub min_spp: u32,
+    pub step_spp: u32,
+    pub abs_tol: f64,
+    pub rel_tol: f64,
+}
+
+extern "C" {
+    /// blocking whole-image adaptive render: per-tile sample counts up to params.ns, per-pixel standard errors
+    pub fn rtmi_render_adaptive(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        adaptive: *const RtmiAdaptive,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_spp: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+}

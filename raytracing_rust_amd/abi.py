@@ -160,6 +160,15 @@ RTMI_SYMBOLS = ["rtmi_device_count", "rtmi_last_error", "rtmi_build_hash", "rtmi
 # the functions of include/rtmi_f64.h (the f64 render mode), kept apart from those of include/rtmi.h
 RTMI_F64_SYMBOLS = ["rtmi_scene_attach_f64", "rtmi_render_f64", "rtmi_probe_math_f64"]
 
+
+class Adaptive(C.Structure):
+    """rtmi_adaptive (include/rtmi_adaptive.h): the noise target of an adaptive render."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("abs_tol", C.c_double), ("rel_tol", C.c_double)]
+
+
+# the functions of include/rtmi_adaptive.h (adaptive sampling), kept apart from those of include/rtmi.h
+RTMI_ADAPTIVE_SYMBOLS = ["rtmi_render_adaptive"]
+
 _rtmi = None
 _host = None
 
@@ -228,6 +237,9 @@ def load_rtmi():
     lib.rtmi_render_f64.argtypes = [vp, C.POINTER(CameraF64), C.POINTER(RenderParams), C.c_double, vp, vp, vp, C.POINTER(Stats)]
     lib.rtmi_probe_math_f64.restype = C.c_int
     lib.rtmi_probe_math_f64.argtypes = [C.c_int, vp, vp, vp, C.c_uint32]
+    lib.rtmi_render_adaptive.restype = C.c_int
+    lib.rtmi_render_adaptive.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp,
+                                         C.POINTER(Stats)]
     _rtmi = lib
     return lib
 
@@ -282,6 +294,7 @@ def load_host():
         "rth_camera_lower_f64": (i, [vp, C.POINTER(CameraF64)]),
         "rth_attach_f64": (i, [vp]),
         "rth_render_f64": (i, [vp, vp, C.POINTER(RenderParams), d, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_render_adaptive": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

@@ -37,6 +37,8 @@
 #include "rtmi_kernels.hpp"
 #include "rtmi_f64_types.hpp"
 #include "rtmi_f64_plan.hpp"
+#include "rtmi_adaptive.h"
+#include "rtmi_adaptive_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -99,6 +101,14 @@ struct rtmi_scene {
     std::vector<void *> f64_allocs;
     double *f64_samples = nullptr; // the f64 mode's per-sample buffer (grow-only, at most RTMI_F64_MAX_BUFFER_BYTES)
     size_t f64_samples_bytes = 0;
+    // adaptive sampling (include/rtmi_adaptive.h), grow-only, freed with the handle: sum | m | M2 per pixel and channel,
+    // two active-tile lists and their count word, the standard errors and counts of the retired tiles
+    double *ad_state = nullptr;   // [tile][9][64]
+    uint32_t *ad_lists = nullptr; // [2][tiles] + count
+    float *ad_stderr = nullptr;   // [tile][64][3]
+    uint32_t *ad_spp = nullptr;   // [tile][64]
+    size_t ad_tiles = 0;
+    uint32_t *h_ad_count = nullptr; // pinned: the active count read back after every step
 };
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
@@ -526,6 +536,11 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : s->f64_allocs) (void)hipFree(p);
     if (s->f64_samples) (void)hipFree(s->f64_samples);
+    if (s->ad_state) (void)hipFree(s->ad_state);
+    if (s->ad_lists) (void)hipFree(s->ad_lists);
+    if (s->ad_stderr) (void)hipFree(s->ad_stderr);
+    if (s->ad_spp) (void)hipFree(s->ad_spp);
+    if (s->h_ad_count) (void)hipHostFree(s->h_ad_count);
     if (s->partial) (void)hipFree(s->partial);
     if (s->samples) { // parked for the next handle on this device (see g_parked); no kernel may still write it
         if (s->busy_recorded) (void)hipEventSynchronize(s->busy);
@@ -1742,4 +1757,221 @@ extern "C" int rtmi_probe_math_f64(int op, const double *x, const double *y, dou
     if (dout) (void)hipFree(dout);
     if (e != hipSuccess) return fail(RTMI_ERR_DEVICE, std::string("rtmi_probe_math_f64: ") + hipGetErrorString(e));
     return RTMI_OK;
+}
+
+// ---- adaptive sampling (include/rtmi_adaptive.h) ---------------------------------------------------------------------
+// Steps of samples per active tile; after every step the adaptive resolve retires the converged tiles and lists the
+// others, and the host reads the count back (4 B) and plans the next step for that many tiles, so a small active set
+// still gets enough units to fill the chip.  The per-sample buffer holds the active tiles only (indexed by list position).
+extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
+                                    const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
+                                    uint32_t *out_spp, rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !a || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (a->min_spp < 2u) return fail(RTMI_ERR_INVALID, "min_spp must be at least 2 (a variance needs two samples)");
+    if (a->min_spp > p_in->ns) return fail(RTMI_ERR_INVALID, "min_spp must not exceed ns");
+    if (a->step_spp == 0u) return fail(RTMI_ERR_INVALID, "step_spp must be positive");
+    if (!std::isfinite(a->abs_tol) || !(a->abs_tol >= 0.0) || !std::isfinite(a->rel_tol) || !(a->rel_tol >= 0.0))
+        return fail(RTMI_ERR_INVALID, "abs_tol and rel_tol must be finite and non-negative");
+    const uint32_t accepted = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                              RTMI_FLAG_UV_BOOK;
+    if (p_in->flags & ~accepted)
+        return fail(RTMI_ERR_UNSUPPORTED, "adaptive sampling accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and "
+                                          "UV_BOOK only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)");
+    if (p_in->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, "adaptive sampling renders the whole image: tile_world must be 1");
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = ensure_streams(s))) return rc;
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // buffers below may be reallocated
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    struct BusyMark {
+        rtmi_scene *s; hipStream_t st;
+        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
+    } busy_mark{s, stream};
+    const uint32_t T = local_tiles_of(&p, 0);
+    const size_t ntex = (size_t)T * 64;
+    if (ntex > s->texel_count) {
+        if (s->texels) { HIP_TRY(hipFree(s->texels)); s->texels = nullptr; s->texel_count = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->texels), ntex * sizeof(rtmi_texel)));
+        s->texel_count = ntex;
+    }
+    if ((rc = ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex))) return rc;
+    if (T > s->ad_tiles) {
+        if (s->ad_state) { HIP_TRY(hipFree(s->ad_state)); s->ad_state = nullptr; }
+        if (s->ad_lists) { HIP_TRY(hipFree(s->ad_lists)); s->ad_lists = nullptr; }
+        if (s->ad_stderr) { HIP_TRY(hipFree(s->ad_stderr)); s->ad_stderr = nullptr; }
+        if (s->ad_spp) { HIP_TRY(hipFree(s->ad_spp)); s->ad_spp = nullptr; }
+        s->ad_tiles = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_state), ntex * 9 * sizeof(double)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_lists), (2 * (size_t)T + 1) * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_stderr), ntex * 3 * sizeof(float)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_spp), ntex * sizeof(uint32_t)));
+        s->ad_tiles = T;
+    }
+    if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
+    { // the per-sample buffer for the largest step (every tile, max(min_spp, step_spp) samples) before the clock starts
+        rtmi_render_params q = p;
+        q.ns = a->min_spp > a->step_spp ? a->min_spp : (a->step_spp < p.ns ? a->step_spp : p.ns);
+        uint32_t chunk_spp = 0, pass_ns = 0;
+        if ((rc = plan_and_reserve(s, &q, T, chunk_spp, pass_ns))) return rc;
+    }
+
+    DevParams P{};
+    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth; P.t_min = p.t_min;
+    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
+    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p);
+    DevCamera C;
+    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
+    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
+    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
+    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
+    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
+    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
+    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
+    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
+    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
+    const bool coop = fast && !sync && coop_ok && !inst;
+    P.stack_depth = s->meta.max_bvh_depth + 1u;
+    P.shade_threshold = p.shade_threshold ? (p.shade_threshold > 64u ? 64u : p.shade_threshold) : 40u;
+    P.status = s->status;
+    P.queue = s->status + 1;
+    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
+    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    const bool use_alt = s->dev.gate != nullptr && s->has_alt && !(p.flags & RTMI_FLAG_REF_TREE);
+    P.use_alt = use_alt ? 1u : 0u;
+    const uint32_t deepest = (use_alt && s->meta.alt_max_depth > s->meta.max_bvh_depth) ? s->meta.alt_max_depth : s->meta.max_bvh_depth;
+    P.spill_cap = 64u * (deepest + 2u);
+    if (use_alt) {
+        const uint32_t wide = 64u * (3u * s->meta.alt_max_depth + 2u);
+        if (wide > P.spill_cap) P.spill_cap = wide;
+    }
+    const bool ext = use_alt || s->meta.n_nodes != 0u;
+    P.coop_cap = ext ? RTMI_COOP_CAP : P.spill_cap;
+    if (coop) {
+        const size_t spill_bytes = (size_t)s->slots * P.spill_cap * sizeof(uint2);
+        if (spill_bytes > s->spill_bytes) {
+            if (s->spill) { HIP_TRY(hipFree(s->spill)); s->spill = nullptr; s->spill_bytes = 0; }
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->spill), spill_bytes));
+            s->spill_bytes = spill_bytes;
+        }
+    }
+    P.spill = s->spill;
+    const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
+    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
+                                                       (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
+    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
+    s->last_kernel = coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
+
+    rtmi_progress_fn fn = reinterpret_cast<rtmi_progress_fn>(static_cast<uintptr_t>(p.progress_fn));
+    void *user = reinterpret_cast<void *>(static_cast<uintptr_t>(p.progress_user));
+    const uint64_t total = (uint64_t)T * p.ns; // tile-samples: every tile at ns
+    uint64_t settled = 0, shown = 0;           // tile-samples of finished steps, retired tiles counted at ns
+    bool cancelled = false;
+
+    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
+    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    {
+        std::vector<uint32_t> all(T);
+        for (uint32_t t = 0; t < T; t++) all[t] = t;
+        HIP_TRY(hipMemcpyAsync(s->ad_lists, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream)); // (`all` is pageable and goes out of scope)
+    }
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    uint32_t *lists[2] = {s->ad_lists, s->ad_lists + T}, *count = s->ad_lists + 2 * (size_t)T;
+    uint32_t n_active = T, n = 0, cur = 0, blocks_total = 0, chunks_total = 0;
+    uint64_t units_before = 0;
+    while (n_active > 0 && n < p.ns && !cancelled) {
+        const uint32_t c = n == 0 ? a->min_spp : (a->step_spp < p.ns - n ? a->step_spp : p.ns - n);
+        rtmi_render_params q = p;
+        q.ns = c;
+        uint32_t chunk_spp = 0, pass_ns = 0;
+        if ((rc = plan_and_reserve(s, &q, n_active, chunk_spp, pass_ns))) return rc;
+        P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+        HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), stream));
+        uint64_t units_step = 0;
+        for (uint32_t s0 = 0; s0 < c; s0 += pass_ns) { // sub-passes when the per-sample buffer does not hold the step
+            P.pass_s0 = n + s0;
+            P.pass_cnt = c - s0 < pass_ns ? c - s0 : pass_ns;
+            P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
+            const uint64_t nitems = (uint64_t)n_active * P.nchunks;
+            if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
+            const uint32_t blocks = (uint32_t)(nitems < run_slots ? nitems : run_slots);
+            blocks_total += blocks; chunks_total += P.nchunks; units_step += nitems;
+            HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, stream, s->dev, C, P, lists[cur]));
+            AdaptiveResolve A;
+            A.tiles_in = lists[cur]; A.tiles_out = lists[cur ^ 1]; A.n_out = count;
+            A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+            A.abs_tol = a->abs_tol; A.rel_tol = a->rel_tol; A.ns = p.ns;
+            A.first = (n == 0 && s0 == 0) ? 1 : 0;
+            A.decide = s0 + P.pass_cnt >= c ? 1 : 0;
+            HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
+            hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, 0);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(s->h_ad_count, count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(s->ev[1], stream));
+        // wait for the step; meanwhile report progress from the unit counters (as wait_with_progress does)
+        const uint64_t step_ts = (uint64_t)n_active * c;
+        while (fn) {
+            const hipError_t qe = hipEventQuery(s->ev[1]);
+            if (qe == hipSuccess) break;
+            if (qe != hipErrorNotReady) return fail(RTMI_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(qe));
+            unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
+            HIP_TRY(hipMemcpyAsync(w, s->status, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream));
+            HIP_TRY(hipStreamSynchronize(s->copy_stream));
+            uint64_t u = (uint64_t)w[3] + w[1];
+            u = u > units_before ? u - units_before : 0;
+            if (u > units_step) u = units_step;
+            uint64_t done = settled + (units_step ? step_ts * u / units_step : 0);
+            if (done < shown) done = shown;
+            shown = done;
+            if (!cancelled && fn(done, total, user) != 0) cancelled = true;
+            struct timespec ts = {0, 50 * 1000 * 1000};
+            nanosleep(&ts, nullptr);
+        }
+        HIP_TRY(hipEventSynchronize(s->ev[1]));
+        units_before += units_step;
+        const uint32_t next = *s->h_ad_count;
+        settled += (uint64_t)(n_active - next) * (p.ns - n) + (uint64_t)next * c; // a retired tile counts at ns
+        n += c;
+        n_active = next;
+        cur ^= 1;
+    }
+    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    HIP_TRY(hipEventSynchronize(s->ev[2]));
+    if (fn && !cancelled && fn(total, total, user) != 0) cancelled = true;
+    if (cancelled) return fail(RTMI_ERR_CANCELLED, "cancelled by the progress callback");
+    if ((rc = check_overflow(s))) return rc;
+    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    std::vector<float> h_se(ntex * 3);
+    std::vector<uint32_t> h_spp(ntex);
+    HIP_TRY(hipMemcpy(h_se.data(), s->ad_stderr, ntex * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_spp.data(), s->ad_spp, ntex * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    const uint32_t txn = tiles_x_of(&p);
+    uint64_t traced = 0;
+    for (uint32_t row = 0; row < p.ny; row++)
+        for (uint32_t px = 0; px < p.nx; px++) {
+            const size_t t = (size_t)((row / RTMI_TILE) * txn + px / RTMI_TILE) * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE;
+            const size_t o = (size_t)row * p.nx + px;
+            traced += h_spp[t];
+            if (out_spp) out_spp[o] = h_spp[t];
+            if (out_stderr) { out_stderr[o * 3] = h_se[t * 3]; out_stderr[o * 3 + 1] = h_se[t * 3 + 1]; out_stderr[o * 3 + 2] = h_se[t * 3 + 2]; }
+        }
+    if (stats) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
+        stats->render_ms = ms; // first launch to last resolve, the per-step read-backs included
+        stats->kernel_ms = ms;
+        stats->samples = traced;
+        stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
+    }
+    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
 }

@@ -1,0 +1,214 @@
+// rtmi_kernel_coop.inc — body of the wave-cooperative render kernel (rtmi_kernels.hpp), included INSIDE the kernels that
+// run it: rtmi_render_coop (TILE_LIST = false) and the adaptive-sampling kernel rtmi_adaptive_coop (rtmi_adaptive.hip,
+// TILE_LIST = true).  The including function provides sc, cam, P, SIG, PROF, WPS, EXT, INSTL, TILE_LIST and `tiles`; see
+// rtmi_kernel_perlane.inc for why this is a textual body.
+    constexpr bool INST = INSTL >= 1; // instanced primitives, media inside transforms
+    constexpr bool INSD = INSTL >= 2; // DEFERRED items, list scans, nested media
+    __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
+    unsigned long long *prof = prof_lds;
+    if (PROF) {
+        if (threadIdx.x < 2 * RTMI_PROF_SLOTS) prof_lds[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[]; // per wave: pool | ctx | best
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    CoopWork cw;
+    cw.cap = (int)P.coop_cap;
+    // per wave: pool | ctx | best | dummy | (lean: word ring) | (INSD: group state, RTMI_COOP_PARK_WORDS)
+    constexpr uint32_t lds_tail = (EXT ? 0u : RTMI_RNG_RING_WORDS) + (INSD ? RTMI_COOP_PARK_WORDS : 0u);
+    cw.wlds = lds_dyn + (size_t)wave * (2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS + lds_tail);
+    // INSD: the state of a group of DEFERRED items lives in LDS, not in registers that would stay live through every
+    // traversal of every scene (parked: 20 VGPRs spilled -> see DESIGN.md §8d): per lane t0 | scan cl | scan holder | scan pf
+    uint32_t *park = cw.wlds + 2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS + (EXT ? 0u : RTMI_RNG_RING_WORDS) + lane;
+    cw.spill_cap = (int)P.spill_cap;
+    cw.spill = P.spill + (size_t)(blockIdx.x * WAVES_PER_BLOCK + wave) * P.spill_cap;
+    unsigned long long sig = 0ull;
+    WaveWork w;
+    w.ltile = 0u; w.ps_base = 0u; w.obase = 0u; w.x0 = 0u; w.y0 = 0u; w.cols = 0u; w.n_valid = 0u; w.next = 0u; w.total = 0u;
+    bool queue_empty = false;
+    const uint32_t k0 = P.key0, k1 = P.key1;
+    const int threshold = (int)P.shade_threshold;
+    // Three scalars of the trace loop in registers of their OWN: as members of the kernel-argument block they sit in
+    // eight-register tuples, and when the allocator spills such a tuple (this kernel keeps ~100 scalars in VGPR lanes) it
+    // restores all eight registers wherever one member is read — found as 48 v_readlane per list scan for the sake of t_min.
+    // The copy through an asm statement is a live range the coalescer cannot fold back into the tuple (r04: final_scene
+    // +1.5 %, cornell_box +4 % together with the one-pointer primitive records; giving every scene POINTER its own pair
+    // the same way lost 2 % / 7 % — profiles/r04_experiments/own_sgprs_ab.log: the allocator is not to be out-guessed twice)
+    float t_min;
+    uint32_t n_items, use_alt_w;
+    asm volatile("s_mov_b32 %0, %3\n s_mov_b32 %1, %4\n s_mov_b32 %2, %5" : "=&s"(t_min), "=&s"(n_items), "=&s"(use_alt_w) : "s"(P.t_min), "s"(sc.n_items), "s"(P.use_alt));
+    const bool use_alt = use_alt_w != 0u;
+
+    uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
+    bool alive = false, done = false, have_hit = false, overflow = false;
+    // lean instantiation (scenes without alternative trees): word ring in LDS behind pool | ctx | best
+    typename std::conditional<EXT, RngReg, RngRing>::type g;
+    rng_attach(g, cw.wlds + 2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS);
+    rng_init(g, 0, 0);
+    Path pa;
+    pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
+    float closest = RTMI_FLT_MAX;
+    int best_item = -1, best_pf = 0;
+    bool best_medium = false;
+    unsigned long long tstamp = PROF ? __builtin_readcyclecounter() : 0ull;
+
+    for (;;) {
+        // ================= phase A =================
+        for (;;) {
+            if (__ballot(!have_hit && !done) == 0ull) break;
+            prof_time<PROF>(prof, 31, tstamp); // loop overhead / phase switching
+            { // lanes whose path ended take the next (sample, pixel) item of the chunk
+                const bool want = !have_hit && !done && !alive;
+                if (__ballot(want) != 0ull) {
+                    uint32_t smp = 0u, px = 0u, j = 0u;
+                    if (work_take<TILE_LIST>(w, queue_empty, want, P, oidx, ltile, smp, px, j, tiles)) {
+                        camera_sample(cam, P, g, k0, k1, smp, j * P.nx + px, px, j, pa);
+                        alive = true;
+                    } else if (want) {
+                        done = true;
+                    }
+                }
+            }
+            const bool need = !have_hit && !done;
+            prof_tick<PROF>(prof, 0, need);
+            prof_time<PROF>(prof, 25, tstamp); // camera samples
+            RayF W;
+            W.o = pa.ro; W.d = pa.rd;
+            ray_derive(W);
+            if (need) { closest = RTMI_FLT_MAX; best_item = -1; best_pf = 0; best_medium = false; }
+            // INSD, parked in LDS: [0] the closest hit before a BVH item whose media / instanced-subtree children follow as DEFERRED
+            // items (T0); [64] / [128] / [192] the scan of a list with media that was a child of a BVHNode (rtmi.h, LISTSCAN): its
+            // closest hit so far, who holds it (item, bit 31: a medium; RTMI_PARK_NONE: nobody) and the primitive
+            int grp_first = 0x7fffffff;    // the index of the SAVE_T0 item (or of the first deferred one), and whether it is the enclosing tree
+            bool grp_tree = false;
+            if (INSD) park[0] = __float_as_uint(RTMI_FLT_MAX);
+            for (uint32_t it = 0; it < n_items; it++) { // executed by all 64 lanes
+                const rtmi_item I = RTMI_UNIFORM_LOAD(rtmi_item, &sc.items[it].it);
+                if (INSD && (I.flags & RTMI_ITEMFLAG_SAVE_T0)) {
+                    park[0] = __float_as_uint(closest); grp_first = (int)it; grp_tree = I.kind == RTMI_ITEM_BVH && !(I.flags & RTMI_ITEMFLAG_DEFERRED);
+                }
+                if (INSD && (I.flags & RTMI_ITEMFLAG_LISTSCAN_END)) { // wave-uniform: the terminator of a list scan
+                    const uint32_t holder = park[128];
+                    if (need && holder != RTMI_PARK_NONE) {
+                        ListScan ls;
+                        ls.cl = __uint_as_float(park[64]); ls.item = (int)(holder & 0x7fffffffu); ls.pf = (int)park[192]; ls.medium = (holder >> 31) != 0u; ls.has = true;
+                        listscan_fold(ls, I.first, closest, best_item, best_pf, best_medium, grp_first, grp_tree);
+                    }
+                    continue;
+                }
+                if (INSD && (I.flags & RTMI_ITEMFLAG_LISTSCAN_BEGIN)) { park[64] = park[0]; park[128] = RTMI_PARK_NONE; }
+                const bool scan = INSD && (I.flags & RTMI_ITEMFLAG_LISTSCAN_MEMBER) != 0u; // wave-uniform
+                RayF R = W;
+                if (I.xform_count > 0) { // both transforms of a chain of two in ONE scalar fetch (they follow the item record)
+                    struct XPair { rtmi_xform x0, x1; };
+                    const XPair XP = RTMI_UNIFORM_LOAD(XPair, reinterpret_cast<const XPair *>(&sc.items[it].x0));
+                    if (xform_ray_item<true>(sc.xforms, I.xform_first, I.xform_count, XP.x0, XP.x1, R.o, R.d)) ray_derive(R);
+                }
+                const int slot = 1 + (it < 11u ? (int)it : 11);
+                if (!(I.flags & RTMI_ITEMFLAG_MEDIUM)) {
+                    float t;
+                    int pf;
+                    // ONE query site (three inlined copies of the traversal made the INSD instantiations twice the code of the
+                    // others): a DEFERRED item — an instanced subtree that was a child of a BVHNode, or a primitive member of a
+                    // list scan (rtmi.h) — is reached through its gate and queried up to the t_max its group was entered with
+                    // (the scan's closest hit so far); what its hit means is decided afterwards
+                    bool reach = need;
+                    float qmax = closest;
+                    const bool dfi = INSD && (I.flags & RTMI_ITEMFLAG_DEFERRED) != 0u; // wave-uniform
+                    if (dfi) {
+                        const float t0_saved = __uint_as_float(park[0]);
+                        reach = need && deferred_gate(sc, I, W, t_min, t0_saved);
+                        qmax = scan ? __uint_as_float(park[64]) : t0_saved;
+                    }
+                    if (geom_query_coop<PROF, EXT, EXT, INST>(sc, I, use_alt, reach, R, pa.rtime, t_min, qmax, cw, t, pf, overflow, prof, slot)) {
+                        if (scan) {
+                            park[64] = __float_as_uint(t); park[128] = it; park[192] = (uint32_t)pf;
+                        } else if (!dfi || deferred_bvh_wins(I.count, t, closest, best_item, best_pf, grp_first, grp_tree)) {
+                            closest = t; best_item = (int)it; best_pf = pf; best_medium = false;
+                        }
+                    }
+                    prof_time<PROF>(prof, I.kind == RTMI_ITEM_BVH ? (it == 0 ? 27 : 28) : 26, tstamp);
+                } else {
+                    // ConstantMedium::hit — medium.rs:28-56
+                    float t1 = 0.0f, t2 = 0.0f, tm;
+                    int pf;
+                    bool h1, h2;
+                    if (I.flags & RTMI_ITEMFLAG_DEV_MEDIUM_SPHERE) {
+                        // boundary = one static sphere (wave-uniform test; the sphere travels in the item record): both
+                        // boundary queries are roots of the same quadratic, evaluated once (same expressions as two
+                        // Sphere::hit calls: same bits)
+                        h1 = false; h2 = false;
+                        if (need) sphere_two_queries(R, make_float4(I.root_min[0], I.root_min[1], I.root_min[2], I.root_max[0]), h1, t1, h2, t2);
+                    } else {
+                        // INSD: a medium that was a child of a BVHNode (rtmi.h, DEFERRED) is reached through its parent's box
+                        const bool dfr = INSD && (I.flags & RTMI_ITEMFLAG_DEFERRED) != 0u; // wave-uniform
+                        bool reach = need;
+                        float t0_saved = RTMI_FLT_MAX;
+                        if (dfr) {
+                            t0_saved = scan ? __uint_as_float(park[64]) : __uint_as_float(park[0]); // the interval's end: the scan's closest hit, or T0
+                            reach = need && deferred_gate(sc, I, W, t_min, __uint_as_float(park[0]));
+                        }
+                        h1 = geom_query_coop<PROF, EXT, false, INST>(sc, I, use_alt, reach, R, pa.rtime, -RTMI_FLT_MAX, RTMI_FLT_MAX, cw, t1, pf, overflow, prof, slot);
+                        h2 = geom_query_coop<PROF, EXT, false, INST>(sc, I, use_alt, reach && h1, R, pa.rtime, t1 + 0.0001f, RTMI_FLT_MAX, cw, t2, pf, overflow, prof, slot);
+                        if (INSD && (I.flags & RTMI_ITEMFLAG_NESTED_MEDIUM)) { // wave-uniform: the boundary is itself a medium (rtmi.h)
+                            if (reach && h1 && h2) h1 = nested_medium_interval(sc, I, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), g, k0, k1, t1, t2);
+                        }
+                        if (dfr) { // its interval ends at the t_max the BVH was entered with; its hit must beat what the tree found
+                            if (reach && h1 && h2 && medium_sample(t1, t2, t_min, t0_saved, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
+                                if (scan) { park[64] = __float_as_uint(tm); park[128] = it | 0x80000000u; }
+                                else if (tm < closest) { closest = tm; best_item = (int)it; best_medium = true; }
+                            }
+                            h1 = false; // done
+                        }
+                    }
+                    if (need && h1 && h2) {
+                        // (one square root per medium: sharing it between the media of a query measured -1.1 %,
+                        // profiles/r03_experiments/wdn_shared_norm_ab.log)
+                        if (medium_sample(t1, t2, t_min, closest, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
+                            closest = tm; best_item = (int)it; best_medium = true;
+                        }
+                    }
+                    prof_time<PROF>(prof, 29, tstamp); // media
+                }
+            }
+            if (need) {
+                if (best_item >= 0) {
+                    have_hit = true;
+                } else { // miss: black background (color.rs:21)
+                    if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
+                    path_end(P, oidx, pa);
+                    if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                    alive = false;
+                }
+            }
+            if (__popcll(__ballot(have_hit)) >= threshold) break;
+        }
+        // ================= phase B =================
+        if (__ballot(have_hit) == 0ull) break;
+        prof_tick<PROF>(prof, 16, have_hit);
+        {
+            const bool shading = have_hit;
+            have_hit = false;
+            if (SIG && shading) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
+            // all lanes call (wavefront texture lookup); the traversal pool is idle now: LDS scratch
+            const bool goes_on = shade_hit<decltype(g), INST>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
+                                           reinterpret_cast<float *>(cw.wlds));
+            if (shading && !goes_on) {
+                path_end(P, oidx, pa);
+                if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                alive = false;
+            }
+        }
+        prof_time<PROF>(prof, 30, tstamp); // shading
+    }
+    if (P.ext & RTMI_EXT_TEST_OVERFLOW) overflow = true; // test knob: exercise the error path
+    if (__ballot(overflow) != 0ull && lane == 0) atomicAdd(P.status, 1u); // reported loudly by the host
+
+    if (PROF) {
+        __syncthreads();
+        if (threadIdx.x < 2 * RTMI_PROF_SLOTS && prof_lds[threadIdx.x] != 0ull) {
+            if (threadIdx.x == 2 * 18) atomicMax(P.prof + threadIdx.x, prof_lds[threadIdx.x]); // slot 18: a maximum
+            else atomicAdd(P.prof + threadIdx.x, prof_lds[threadIdx.x]);
+        }
+    }

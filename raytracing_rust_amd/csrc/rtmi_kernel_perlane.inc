@@ -1,0 +1,155 @@
+// rtmi_kernel_perlane.inc — body of the per-lane two-phase render kernel (rtmi_kernels.hpp), included INSIDE the kernels
+// that run it: rtmi_render_kernel (TILE_LIST = false) and the adaptive-sampling kernel rtmi_adaptive_kernel (rtmi_adaptive.hip,
+// TILE_LIST = true: the queue runs over a list of tiles, see wave_work).  The including function provides sc, cam, P, FAST, SIG,
+// PROF, TILE_LIST and `tiles`.  A textual body and not a force-inlined function: inlining one changed the instruction stream
+// of every existing instantiation (same instructions in another order and register assignment), and those must stay
+// bit-for-bit what they were.
+    __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
+    unsigned long long *prof = prof_lds;
+    if (PROF) {
+        if (threadIdx.x < 2 * RTMI_PROF_SLOTS) prof_lds[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    // per wave: [0] node refs, [1] entry distances (FAST only); entry-major so lanes never bank-conflict
+    __shared__ uint32_t lds_stack[WAVES_PER_BLOCK][FAST ? 2 : 1][RTMI_MAX_BVH_DEPTH][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    uint32_t *stack = &lds_stack[wave][0][0][lane];
+    unsigned long long sig = 0ull;
+    WaveWork w;
+    w.ltile = 0u; w.ps_base = 0u; w.obase = 0u; w.x0 = 0u; w.y0 = 0u; w.cols = 0u; w.n_valid = 0u; w.next = 0u; w.total = 0u;
+    bool queue_empty = false;
+    const uint32_t k0 = P.key0, k1 = P.key1;
+    const int threshold = (int)P.shade_threshold;
+
+    uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
+    bool alive = false, done = false, have_hit = false;
+    RngReg g;
+    rng_init(g, 0, 0);
+    Path pa;
+    pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
+    float closest = RTMI_FLT_MAX;
+    int best_item = -1, best_pf = 0;
+    bool best_medium = false;
+
+    for (;;) {
+        // ================= phase A: trace until enough lanes hold a hit =================
+        for (;;) {
+            if (__ballot(!have_hit && !done) == 0ull) break;
+            { // lanes whose path ended take the next (sample, pixel) item of the chunk
+                const bool want = !have_hit && !done && !alive;
+                if (__ballot(want) != 0ull) {
+                    uint32_t smp = 0u, px = 0u, j = 0u;
+                    if (work_take<TILE_LIST>(w, queue_empty, want, P, oidx, ltile, smp, px, j, tiles)) {
+                        camera_sample(cam, P, g, k0, k1, smp, j * P.nx + px, px, j, pa);
+                        alive = true;
+                    } else if (want) {
+                        done = true;
+                    }
+                }
+            }
+            const bool need = !have_hit && !done;
+            prof_tick<PROF>(prof, 0, need);
+            if (need) {
+                // ---- world.hit(ray, 0.001, f64::MAX): scan of the top-level list (hittable.rs:37-47)
+                RayF W;
+                W.o = pa.ro; W.d = pa.rd;
+                ray_derive(W);
+                closest = RTMI_FLT_MAX;
+                best_item = -1; best_pf = 0; best_medium = false;
+                float t0_saved = RTMI_FLT_MAX; // the closest hit before a BVH item whose media / instanced-subtree children follow as DEFERRED items
+                int grp_first = 0x7fffffff;    // ... the index of that item (or of the first deferred one), and whether it is the enclosing tree
+                bool grp_tree = false;
+                ListScan ls; // a list with media that was a child of a BVHNode (rtmi.h, LISTSCAN)
+                ls.cl = RTMI_FLT_MAX; ls.item = -1; ls.pf = 0; ls.medium = false; ls.has = false;
+                for (uint32_t it = 0; it < sc.n_items; it++) {
+                    const rtmi_item I = sc.items[it].it;
+                    if (I.flags & RTMI_ITEMFLAG_SAVE_T0) {
+                        t0_saved = closest; grp_first = (int)it; grp_tree = I.kind == RTMI_ITEM_BVH && !(I.flags & RTMI_ITEMFLAG_DEFERRED);
+                    }
+                    if (I.flags & RTMI_ITEMFLAG_LISTSCAN_END) { // the terminator: the scan's result meets the closest hit so far
+                        listscan_fold(ls, I.first, closest, best_item, best_pf, best_medium, grp_first, grp_tree);
+                        continue;
+                    }
+                    if (I.flags & RTMI_ITEMFLAG_LISTSCAN_BEGIN) { ls.cl = t0_saved; ls.has = false; }
+                    const bool scan = (I.flags & RTMI_ITEMFLAG_LISTSCAN_MEMBER) != 0u;
+                    RayF R = W;
+                    if (I.xform_count > 0) {
+                        if (xform_ray(sc.xforms, I.xform_first, I.xform_count, R.o, R.d)) ray_derive(R);
+                    }
+                    const int slot = 1 + (it < 11u ? (int)it : 11);
+                    if (!(I.flags & RTMI_ITEMFLAG_MEDIUM)) {
+                        float t;
+                        int pf;
+                        if (scan) { // a primitive member of the list scan: t_max = the scan's closest hit so far
+                            if (deferred_gate(sc, I, W, P.t_min, t0_saved) &&
+                                geom_query<FAST, PROF>(sc, I, R, pa.rtime, P.t_min, ls.cl, stack, t, pf, prof, slot)) {
+                                ls.cl = t; ls.item = (int)it; ls.pf = pf; ls.medium = false; ls.has = true;
+                            }
+                        } else if (I.flags & RTMI_ITEMFLAG_DEFERRED) { // an instanced subtree that was a child of a BVHNode (rtmi.h)
+                            if (deferred_gate(sc, I, W, P.t_min, t0_saved) &&
+                                geom_query<FAST, PROF>(sc, I, R, pa.rtime, P.t_min, t0_saved, stack, t, pf, prof, slot) &&
+                                deferred_bvh_wins(I.count, t, closest, best_item, best_pf, grp_first, grp_tree)) {
+                                closest = t; best_item = (int)it; best_pf = pf; best_medium = false;
+                            }
+                        } else if (geom_query<FAST, PROF>(sc, I, R, pa.rtime, P.t_min, closest, stack, t, pf, prof, slot)) {
+                            closest = t; best_item = (int)it; best_pf = pf; best_medium = false;
+                        }
+                    } else {
+                        // ConstantMedium::hit — medium.rs:28-56
+                        float t1, t2, tm;
+                        int pf;
+                        // a medium that was a child of a BVHNode (rtmi.h, DEFERRED): reached through its parent's box, its
+                        // interval clamped to the t_max the BVH was entered with, accepted when closer than the tree's hit
+                        const bool dfr = (I.flags & RTMI_ITEMFLAG_DEFERRED) != 0u;
+                        const float qmax = scan ? ls.cl : (dfr ? t0_saved : closest);
+                        if (!dfr || deferred_gate(sc, I, W, P.t_min, t0_saved)) {
+                        if (geom_query<FAST, PROF>(sc, I, R, pa.rtime, -RTMI_FLT_MAX, RTMI_FLT_MAX, stack, t1, pf, prof, slot)) {
+                            if (geom_query<FAST, PROF>(sc, I, R, pa.rtime, t1 + 0.0001f, RTMI_FLT_MAX, stack, t2, pf, prof, slot)) {
+                                const float dn = medium_dir_norm(sc, I.flags, I.xform_first, W);
+                                if ((I.flags & RTMI_ITEMFLAG_NESTED_MEDIUM) && !nested_medium_interval(sc, I, dn, g, k0, k1, t1, t2)) {
+                                    // the inner medium returned no hit to one of the outer medium's two queries
+                                } else
+                                if (medium_sample(t1, t2, P.t_min, qmax, dn, I.neg_inv_density, g, k0, k1, tm)) {
+                                    if (scan) { ls.cl = tm; ls.item = (int)it; ls.medium = true; ls.has = true; }
+                                    else if (!dfr || tm < closest) { closest = tm; best_item = (int)it; best_medium = true; }
+                                }
+                            }
+                        }
+                        }
+                    }
+                }
+                if (best_item >= 0) {
+                    have_hit = true;
+                } else { // miss: black background (color.rs:21); the path ends
+                    if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
+                    path_end(P, oidx, pa);
+                    if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                    alive = false;
+                }
+            }
+            if (__popcll(__ballot(have_hit)) >= threshold) break;
+        }
+        // ================= phase B: shade every lane that holds a hit =================
+        if (__ballot(have_hit) == 0ull) break; // nobody holds a hit and nobody can trace: all done
+        prof_tick<PROF>(prof, 16, have_hit);
+        {
+            const bool shading = have_hit;
+            have_hit = false;
+            if (SIG && shading) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
+            // all lanes call (wavefront texture lookup); the traversal stacks are idle now: LDS scratch
+            const bool goes_on = shade_hit(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
+                                           reinterpret_cast<float *>(&lds_stack[wave][0][0][0]));
+            if (shading && !goes_on) {
+                // absorbed, emitter or depth limit: the path ends
+                path_end(P, oidx, pa);
+                if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                alive = false;
+            }
+        }
+    }
+
+    if (PROF) {
+        __syncthreads();
+        if (threadIdx.x < 2 * RTMI_PROF_SLOTS && prof_lds[threadIdx.x] != 0ull) atomicAdd(P.prof + threadIdx.x, prof_lds[threadIdx.x]);
+    }

@@ -531,11 +531,15 @@ struct WaveWork { // wave-uniform (kept in SGPRs: every field passes through rea
     uint32_t ltile, ps_base, obase, x0, y0, cols, n_valid, next, total;
 };
 __device__ __forceinline__ uint32_t rfl(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ WaveWork wave_work(const DevParams &P, uint32_t unit) {
+// TILE_LIST (adaptive sampling, include/rtmi_adaptive.h): the queue runs over the P.ntiles_local entries of `tiles`, the
+// local tiles still rendered; the per-sample buffer is indexed by the position in that list, everything else by the tile.
+template <bool TILE_LIST = false>
+__device__ __forceinline__ WaveWork wave_work(const DevParams &P, uint32_t unit, const uint32_t *tiles = nullptr) {
     WaveWork w;
     const bool has_work = unit < P.ntiles_local * P.nchunks;
     const uint32_t chunk = unit / P.ntiles_local; // chunk-major: all tiles of chunk 0 first
-    const uint32_t ltile = unit - chunk * P.ntiles_local;
+    const uint32_t lpos = unit - chunk * P.ntiles_local;
+    const uint32_t ltile = TILE_LIST ? (has_work ? tiles[rfl(lpos)] : 0u) : lpos;
     const uint32_t tile = ltile * P.tile_world + P.tile_rank;
     const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
     const uint32_t x0 = tx * RTMI_TILE, y0 = ty * RTMI_TILE;
@@ -553,7 +557,7 @@ __device__ __forceinline__ WaveWork wave_work(const DevParams &P, uint32_t unit)
     w.ps_base = rfl(s_begin << 6);
     // slot of item ps = sample << 6 | pixel in the per-sample buffer: (ltile * stride + sample - pass_s0) * 64 + pixel
     // = obase + ps in uint32 arithmetic (the host keeps the buffer below 2^32 slots)
-    w.obase = rfl((ltile * P.pass_stride - P.pass_s0) * 64u);
+    w.obase = rfl((lpos * P.pass_stride - P.pass_s0) * 64u);
     w.total = rfl((has_work && s_end > s_begin) ? (s_end - s_begin) * cols * rows : 0u);
     w.next = 0u;
     return w;
@@ -563,8 +567,10 @@ __device__ __forceinline__ WaveWork wave_work(const DevParams &P, uint32_t unit)
 // unit or, when that is exhausted, from the next units of the global queue.  Returns false for lanes that
 // wanted but found the queue empty: they are done for good.  The loop ends for every wavefront: the
 // counter only grows and the number of units is fixed.
+template <bool TILE_LIST = false>
 __device__ __forceinline__ bool work_take(WaveWork &w, bool &queue_empty, bool want, const DevParams &P, uint32_t &oidx,
-                                          uint32_t &ltile, uint32_t &smp, uint32_t &px, uint32_t &j) {
+                                          uint32_t &ltile, uint32_t &smp, uint32_t &px, uint32_t &j,
+                                          const uint32_t *tiles = nullptr) {
     bool got = false;
     for (;;) {
         const bool still = want && !got;
@@ -576,7 +582,7 @@ __device__ __forceinline__ bool work_take(WaveWork &w, bool &queue_empty, bool w
             if ((threadIdx.x & 63) == 0) u = atomicAdd(P.queue, 1u);
             u = rfl(u);
             if (u >= P.ntiles_local * P.nchunks) { queue_empty = true; break; }
-            w = wave_work(P, u);
+            w = wave_work<TILE_LIST>(P, u, tiles);
             continue;
         }
         const uint32_t k = w.next + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));

@@ -193,6 +193,27 @@ class Scene:
             out["sig"] = sg
         return out
 
+    def render_adaptive(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, precision="f32", **kw):
+        """Adaptive sampling (include/rtmi_adaptive.h): every 8x8 tile gets min_spp samples, then step_spp more per step
+        while some in-image pixel has stderr > abs_tol + rel_tol * |mean|, up to ns.  Returns dict(linear f32 [ny,nx,3],
+        rgb8 u8 [ny,nx,3], stderr f32 [ny,nx,3], spp u32 [ny,nx], stats).  A tile is bit for bit the tile of
+        render(ns = its spp).  progress: callable(done, total) in tile-samples, total = tiles x ns."""
+        if precision != "f32":
+            raise Unsupported("adaptive sampling has no f64 mode")
+        if not self.uploaded:
+            self.upload(kw.pop("device", 0))
+        kw.pop("device", None)
+        p = default_params(nx, ny, ns, **kw)
+        a = abi.Adaptive(min_spp, step_spp, abs_tol, rel_tol)
+        lin = np.zeros((ny, nx, 3), np.float32)
+        rgb = np.zeros((ny, nx, 3), np.uint8)
+        se = np.zeros((ny, nx, 3), np.float32)
+        spp = np.zeros((ny, nx), np.uint32)
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_adaptive(self.h, cam.h, C.byref(p), C.byref(a), lin.ctypes.data,
+                                                            rgb.ctypes.data, se.ctypes.data, spp.ctypes.data, C.byref(st)))
+        return {"linear": lin, "rgb8": rgb, "stderr": se, "spp": spp, "stats": _stats(st)}
+
     def render_multi(self, cam, nx, ny, ns, devices, **kw):
         """Whole image on several GPUs of this process (rtmi_render_multi): tiles t % len(devices), one gather.
         A device may be listed more than once (single-GPU rehearsal).  Bit-identical to render()."""

@@ -33,6 +33,7 @@
 
 #include "rtmi.h"
 #include "rtmi_f64.h"
+#include "rtmi_adaptive.h"
 
 namespace rt {
 

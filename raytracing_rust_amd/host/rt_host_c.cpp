@@ -242,6 +242,19 @@ RTH_API int rth_render(void *lowered, void *cam, const rtmi_render_params *p, fl
         return RTH_OK;
     });
 }
+// adaptive sampling (include/rtmi_adaptive.h): RTH_UNSUPPORTED for what rtmi_render_adaptive does not support
+RTH_API int rth_render_adaptive(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_adaptive *a, float *out_linear,
+                                uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_adaptive(o->dev, &c, p, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
 // ---- f64 render mode (include/rtmi_f64.h) ------------------------------------------------------------
 RTH_API int rth_lowered_desc_f64(void *lowered, rtmi_scene_f64 *out) {
     return guard([&] { *out = LOW(lowered)->lowered->desc_f64(); return RTH_OK; });
