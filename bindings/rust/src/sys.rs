@@ -455,3 +455,20 @@ extern "C" {
         stats: *mut RtmiStats,
     ) -> c_int;
 }
+
+// ---- include/rtmi_features.h: first-hit albedo, normal and depth buffers for denoisers ------------------------------------
+
+extern "C" {
+    /// blocking whole-image first-hit features: albedo, normal, depth and hit count per pixel (the render's first bounce)
+    pub fn rtmi_render_features(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        out_albedo: *mut f32,
+        out_normal: *mut f32,
+        out_depth: *mut f32,
+        out_hits: *mut u32,
+        out_path_sig: *mut u64,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+}

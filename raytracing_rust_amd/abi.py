@@ -169,6 +169,9 @@ class Adaptive(C.Structure):
 # the functions of include/rtmi_adaptive.h (adaptive sampling), kept apart from those of include/rtmi.h
 RTMI_ADAPTIVE_SYMBOLS = ["rtmi_render_adaptive"]
 
+# the functions of include/rtmi_features.h (first-hit features for denoisers), kept apart from those of include/rtmi.h
+RTMI_FEATURES_SYMBOLS = ["rtmi_render_features"]
+
 _rtmi = None
 _host = None
 
@@ -240,6 +243,8 @@ def load_rtmi():
     lib.rtmi_render_adaptive.restype = C.c_int
     lib.rtmi_render_adaptive.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp,
                                          C.POINTER(Stats)]
+    lib.rtmi_render_features.restype = C.c_int
+    lib.rtmi_render_features.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]
     _rtmi = lib
     return lib
 
@@ -295,6 +300,7 @@ def load_host():
         "rth_attach_f64": (i, [vp]),
         "rth_render_f64": (i, [vp, vp, C.POINTER(RenderParams), d, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_adaptive": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_render_features": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

@@ -39,6 +39,8 @@
 #include "rtmi_f64_plan.hpp"
 #include "rtmi_adaptive.h"
 #include "rtmi_adaptive_launch.hpp"
+#include "rtmi_features.h"
+#include "rtmi_features_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -109,6 +111,12 @@ struct rtmi_scene {
     uint32_t *ad_spp = nullptr;   // [tile][64]
     size_t ad_tiles = 0;
     uint32_t *h_ad_count = nullptr; // pinned: the active count read back after every step
+    // first-hit features (include/rtmi_features.h), grow-only, freed with the handle: the f64 sums carried between passes
+    // and the four output planes
+    double *ft_state = nullptr; // [tile][8][64]
+    size_t ft_state_bytes = 0;
+    float *ft_planes = nullptr; // albedo [ny*nx*3] | normal [ny*nx*3] | depth [ny*nx] | hits [ny*nx] (uint32)
+    size_t ft_planes_bytes = 0;
 };
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
@@ -541,6 +549,8 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->ad_stderr) (void)hipFree(s->ad_stderr);
     if (s->ad_spp) (void)hipFree(s->ad_spp);
     if (s->h_ad_count) (void)hipHostFree(s->h_ad_count);
+    if (s->ft_state) (void)hipFree(s->ft_state);
+    if (s->ft_planes) (void)hipFree(s->ft_planes);
     if (s->partial) (void)hipFree(s->partial);
     if (s->samples) { // parked for the next handle on this device (see g_parked); no kernel may still write it
         if (s->busy_recorded) (void)hipEventSynchronize(s->busy);
@@ -582,13 +592,14 @@ static int check_params(const rtmi_render_params *p) {
 }
 
 // Plan of one render call: unit size, samples per pass; (re)allocates the per-sample buffer and the f64 sums.
+// slot_bytes: the size of one per-sample slot (rtmi_render_features stores 32-B FeatSlots).
 static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t ntiles_local, uint32_t &chunk_spp,
-                            uint32_t &pass_ns) {
+                            uint32_t &pass_ns, size_t slot_bytes = RTMI_SAMPLE_SLOT_BYTES) {
     // ---- per-sample buffer and passes.  Every finished path stores its radiance (12 B) in
     // samples[local tile][sample of the pass][pixel]; the resolve kernel adds them in sample order.  With
     // 288 GB of HBM the whole sample range normally fits (headline: 25 GB); otherwise the range is rendered
     // in passes and the f64 sums are carried between them — the same additions in the same order.
-    const size_t per_sample = (size_t)ntiles_local * 64 * RTMI_SAMPLE_SLOT_BYTES;
+    const size_t per_sample = (size_t)ntiles_local * 64 * slot_bytes;
     size_t want = p->sample_buffer_bytes ? (size_t)p->sample_buffer_bytes : ((size_t)45 << 30);
     if (want > ((size_t)45 << 30)) want = (size_t)45 << 30; // slots are addressed with 32 bits (< 2^32 x 12 B = 48 GiB)
     uint64_t max_pass = want / per_sample;
@@ -1974,4 +1985,138 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
         stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
     }
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
+// ---- first-hit features (include/rtmi_features.h) ---------------------------------------------------------------------
+// The per-lane features kernel (rtmi_features.hip) in passes of the render's plan, sized for 32-B slots; a resolve per
+// pass carries the f64 sums and writes the planes after the last one.  Progress and cancellation as rtmi_render's.
+extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_albedo,
+                                    float *out_normal, float *out_depth, uint32_t *out_hits, uint64_t *out_path_sig,
+                                    rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    const uint32_t accepted = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                              RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG;
+    if (p_in->flags & ~accepted)
+        return fail(RTMI_ERR_UNSUPPORTED, "features accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
+                                          "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)");
+    if (p_in->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, "features cover the whole image: tile_world must be 1");
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = ensure_streams(s))) return rc;
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // buffers below may be reallocated
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    struct BusyMark {
+        rtmi_scene *s; hipStream_t st;
+        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
+    } busy_mark{s, stream};
+    const uint32_t T = local_tiles_of(&p, 0);
+    const size_t ntex = (size_t)T * 64, npix = (size_t)p.nx * p.ny;
+    if (ntex * 8 * sizeof(double) > s->ft_state_bytes) {
+        if (s->ft_state) { HIP_TRY(hipFree(s->ft_state)); s->ft_state = nullptr; s->ft_state_bytes = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ft_state), ntex * 8 * sizeof(double)));
+        s->ft_state_bytes = ntex * 8 * sizeof(double);
+    }
+    if (npix * 8 * sizeof(float) > s->ft_planes_bytes) {
+        if (s->ft_planes) { HIP_TRY(hipFree(s->ft_planes)); s->ft_planes = nullptr; s->ft_planes_bytes = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ft_planes), npix * 8 * sizeof(float)));
+        s->ft_planes_bytes = npix * 8 * sizeof(float);
+    }
+    if (out_path_sig && ntex > s->sig_count) {
+        if (s->d_sig) { HIP_TRY(hipFree(s->d_sig)); s->d_sig = nullptr; s->sig_count = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_sig), ntex * sizeof(unsigned long long)));
+        s->sig_count = ntex;
+    }
+    // the per-sample buffer, planned for 32-B slots, before the clock starts
+    uint32_t chunk_spp = 0, pass_ns = 0;
+    if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns, RTMI_FEAT_SLOT_BYTES))) return rc;
+
+    DevParams P{};
+    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth; P.t_min = p.t_min;
+    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
+    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p); P.ntiles_local = T;
+    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+    DevCamera C;
+    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
+    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
+    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
+    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
+    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
+    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
+    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    // pruned traversal needs the BVH boxes to contain their moving spheres at every ray time (as render_device_locked)
+    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
+    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sig = out_path_sig != nullptr;
+    P.stack_depth = s->meta.max_bvh_depth + 1u;
+    P.shade_threshold = p.shade_threshold ? (p.shade_threshold > 64u ? 64u : p.shade_threshold) : 40u;
+    P.status = s->status;
+    P.queue = s->status + 1;
+    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
+    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    P.path_sig = sig ? s->d_sig : nullptr;
+    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
+    s->last_kernel = RTMI_KERNEL_PERLANE;
+
+    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
+    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
+    s->units_total = 0;
+    FeaturesResolve R;
+    R.slots = reinterpret_cast<const FeatSlot *>(s->samples);
+    R.state = s->ft_state;
+    R.albedo = s->ft_planes; R.normal = s->ft_planes + npix * 3; R.depth = s->ft_planes + npix * 6;
+    R.hits = reinterpret_cast<uint32_t *>(s->ft_planes + npix * 7);
+    uint32_t blocks_total = 0, chunks_total = 0;
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    for (uint32_t s0 = 0; s0 < p.ns; s0 += pass_ns) { // one pass unless the per-sample buffer is smaller than ns samples
+        P.pass_s0 = s0;
+        P.pass_cnt = p.ns - s0 < pass_ns ? p.ns - s0 : pass_ns;
+        P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
+        const uint64_t nitems = (uint64_t)T * P.nchunks;
+        if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
+        const uint32_t blocks = (uint32_t)(nitems < run_slots ? nitems : run_slots);
+        blocks_total += blocks; chunks_total += P.nchunks;
+        s->units_total += nitems;
+        HIP_TRY(rtmi_features_launch_render(fast, sig, blocks, stream, s->dev, C, P));
+        const bool last = s0 + P.pass_cnt >= p.ns;
+        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
+        R.first = s0 == 0 ? 1 : 0;
+        R.last = last ? 1 : 0;
+        HIP_TRY(rtmi_features_launch_resolve(stream, P, R));
+        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, last ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    rtmi_scene *one[1] = {s};
+    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
+    if ((rc = check_overflow(s))) return rc;
+    if (out_albedo) HIP_TRY(hipMemcpy(out_albedo, R.albedo, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_normal) HIP_TRY(hipMemcpy(out_normal, R.normal, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_depth) HIP_TRY(hipMemcpy(out_depth, R.depth, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_hits) HIP_TRY(hipMemcpy(out_hits, R.hits, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out_path_sig) {
+        s->h_sig.resize(ntex);
+        HIP_TRY(hipMemcpy(s->h_sig.data(), s->d_sig, ntex * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        const uint32_t txn = tiles_x_of(&p);
+        for (uint32_t row = 0; row < p.ny; row++)
+            for (uint32_t px = 0; px < p.nx; px++) {
+                const uint32_t t = (row / RTMI_TILE) * txn + px / RTMI_TILE;
+                out_path_sig[(size_t)row * p.nx + px] = s->h_sig[(size_t)t * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE];
+            }
+    }
+    if (stats) {
+        float ms_r = 0.f, ms_all = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
+        stats->render_ms = ms_r;
+        stats->kernel_ms = ms_all;
+        stats->samples = (uint64_t)npix * p.ns;
+        stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
+    }
+    return RTMI_OK;
 }

@@ -1,9 +1,10 @@
 // rtmi_kernel_perlane.inc — body of the per-lane two-phase render kernel (rtmi_kernels.hpp), included INSIDE the kernels
 // that run it: rtmi_render_kernel (TILE_LIST = false) and the adaptive-sampling kernel rtmi_adaptive_kernel (rtmi_adaptive.hip,
 // TILE_LIST = true: the queue runs over a list of tiles, see wave_work).  The including function provides sc, cam, P, FAST, SIG,
-// PROF, TILE_LIST and `tiles`.  A textual body and not a force-inlined function: inlining one changed the instruction stream
-// of every existing instantiation (same instructions in another order and register assignment), and those must stay
-// bit-for-bit what they were.
+// PROF, TILE_LIST, FEATURES and `tiles`.  FEATURES (rtmi_features_kernel, rtmi_features.hip): every path ends at its first
+// interaction, which writes a FeatSlot (rtmi_shade.hpp) to the per-sample buffer instead of a radiance.  A textual body
+// and not a force-inlined function: inlining one changed the instruction stream of every existing instantiation (same
+// instructions in another order and register assignment), and those must stay bit-for-bit what they were.
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
     unsigned long long *prof = prof_lds;
     if (PROF) {
@@ -122,8 +123,12 @@
                 if (best_item >= 0) {
                     have_hit = true;
                 } else { // miss: black background (color.rs:21); the path ends
+                    if constexpr (FEATURES) {
+                        feat_miss(P, oidx, pa);
+                    } else {
                     if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
                     path_end(P, oidx, pa);
+                    }
                     if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                     alive = false;
                 }
@@ -138,6 +143,16 @@
             have_hit = false;
             if (SIG && shading) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
             // all lanes call (wavefront texture lookup); the traversal stacks are idle now: LDS scratch
+            if constexpr (FEATURES) { // the first interaction ends every path: its record goes to the feature slot
+                ShadeFeat feat;
+                shade_hit<RngReg, true, true>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium,
+                                              pa, reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), &feat);
+                if (shading) {
+                    feat_hit(P, oidx, pa, closest, feat);
+                    if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                    alive = false;
+                }
+            } else {
             const bool goes_on = shade_hit(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
                                            reinterpret_cast<float *>(&lds_stack[wave][0][0][0]));
             if (shading && !goes_on) {
@@ -145,6 +160,7 @@
                 path_end(P, oidx, pa);
                 if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                 alive = false;
+            }
             }
         }
     }

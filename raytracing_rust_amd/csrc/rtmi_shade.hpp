@@ -346,15 +346,23 @@ __device__ __forceinline__ bool nested_medium_interval(const DevScene &sc, const
     return true;
 }
 
+// First-hit features of one sample (include/rtmi_features.h): what shade_hit<.., FEAT = true> hands out.
+struct ShadeFeat {
+    F3 albedo; // texture value (Lambertian, Metal, Isotropic), (1,1,1) (Dielectric), min(emitted, 1) (DiffuseLight)
+    F3 normal; // the normal the material's scatter sees (after FlipNormals and FACE_FORWARD); 0 for a medium event
+};
+
 // HitRecord of the closest hit (hittable.rs:9-16), built once, then
 // color(): emitted + attenuation * color(scattered) — color.rs:8-15, in throughput form.
 // ALL 64 lanes call this together (the texture lookup is a wavefront operation, tex_value_wave); lanes with
 // active = true hold a hit to shade.  Returns true when the lane's path continues (pa holds the scattered ray),
 // false when it ended (or the lane was not active).  `scratch`: 64 floats of LDS private to the wavefront.
-template <typename RngT, bool INST = true>
+// FEAT (features kernels, rtmi_features.hip): the record and the texture value (looked up whatever max_depth says) go
+// to *feat of every active lane instead of a scatter; no draws, and the path always ends.
+template <typename RngT, bool INST = true, bool FEAT = false>
 __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth, uint32_t ext, RngT &g, uint32_t k0, uint32_t k1,
                                           bool active, float closest, int best_item, int best_pf, bool best_medium, Path &pa,
-                                          float *scratch) {
+                                          float *scratch, ShadeFeat *feat = nullptr) {
     F3 hp = f3(0, 0, 0), hn = f3(1, 0, 0);
     float hu = 0.0f, hv = 0.0f;
     rtmi_material M;
@@ -452,10 +460,10 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
         textured = M.kind == RTMI_MAT_LAMBERTIAN || M.kind == RTMI_MAT_METAL || M.kind == RTMI_MAT_ISOTROPIC;
         const bool want_sample = can_scatter && (M.kind == RTMI_MAT_LAMBERTIAN || M.kind == RTMI_MAT_ISOTROPIC ||
                                                  (M.kind == RTMI_MAT_METAL && M.param > 0.0f));
-        if (want_sample) rs = random_in_unit_sphere(g, k0, k1);
+        if (!FEAT && want_sample) rs = random_in_unit_sphere(g, k0, k1);
     }
     const int kind = M.kind;
-    const bool want_tex = active && (kind == RTMI_MAT_DIFFUSE_LIGHT || (can_scatter && textured));
+    const bool want_tex = active && (kind == RTMI_MAT_DIFFUSE_LIGHT || ((FEAT || can_scatter) && textured));
     const F3 tv = tex_value_wave(sc, want_tex, T0, hu, hv, hp, scratch); // every lane of the wavefront
     bool scattered = false;
     if (active) {
@@ -464,6 +472,13 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
         F3 nd = rd, att = f3(1, 1, 1);
         // opt-in RTMI_FLAG_FACE_FORWARD (wave-uniform): the opaque materials see the normal turned against the ray
         if ((ext & RTMI_EXT_FACE_FORWARD) && kind != RTMI_MAT_DIELECTRIC && dot(rd, hn) > 0.0f) hn = -hn;
+        if constexpr (FEAT) {
+            feat->albedo = kind == RTMI_MAT_DIELECTRIC ? f3(1, 1, 1)
+                           : kind == RTMI_MAT_DIFFUSE_LIGHT ? f3(fminf(tv.x, 1.0f), fminf(tv.y, 1.0f), fminf(tv.z, 1.0f))
+                           : textured ? tv : f3(0, 0, 0);
+            feat->normal = best_medium ? f3(0, 0, 0) : hn;
+            return false;
+        }
         if (can_scatter) {
             if (kind == RTMI_MAT_LAMBERTIAN) { // material.rs:49-53 (contract: dir = normal + rand)
                 nd = hn + rs;
@@ -609,4 +624,32 @@ __device__ __forceinline__ bool work_take(WaveWork &w, bool &queue_empty, bool w
 // `col += color(..)` — tests/test.rs:69: the path's radiance goes to its slot of the per-sample buffer
 __device__ __forceinline__ void path_end(const DevParams &P, uint32_t oidx, const Path &pa) {
     P.samples[oidx] = Rad3{pa.L.x, pa.L.y, pa.L.z};
+}
+
+// Features kernels (include/rtmi_features.h): the per-sample buffer holds 32-B FeatSlots in the slots of the 12-B radiances
+// (same indexing; the host plans the passes with RTMI_FEAT_SLOT_BYTES).  dist < 0 marks a sample without a first
+// interaction (a miss); a medium event is a hit whose normal is 0.
+struct __attribute__((aligned(8))) FeatSlot {
+    float albedo[3];
+    float normal[3];
+    double dist; // (double)t * |d| of the world ray, no fused operations; -1 for a miss
+};
+#define RTMI_FEAT_SLOT_BYTES 32u
+static_assert(sizeof(FeatSlot) == RTMI_FEAT_SLOT_BYTES, "FeatSlot layout");
+__device__ __forceinline__ void feat_hit(const DevParams &P, uint32_t oidx, const Path &pa, float t, const ShadeFeat &f) {
+    const double dx = (double)pa.rd.x, dy = (double)pa.rd.y, dz = (double)pa.rd.z;
+    FeatSlot o;
+    o.albedo[0] = f.albedo.x; o.albedo[1] = f.albedo.y; o.albedo[2] = f.albedo.z;
+    o.normal[0] = f.normal.x; o.normal[1] = f.normal.y; o.normal[2] = f.normal.z;
+    o.dist = (double)t * sqrt(dx * dx + dy * dy + dz * dz);
+    reinterpret_cast<FeatSlot *>(P.samples)[oidx] = o;
+}
+// a miss: the sky colour under RTMI_FLAG_SKY (the first bounce's throughput is 1), otherwise 0
+__device__ __forceinline__ void feat_miss(const DevParams &P, uint32_t oidx, const Path &pa) {
+    const F3 a = P.sky ? sky_color(pa.rd) : f3(0, 0, 0);
+    FeatSlot o;
+    o.albedo[0] = a.x; o.albedo[1] = a.y; o.albedo[2] = a.z;
+    o.normal[0] = 0.0f; o.normal[1] = 0.0f; o.normal[2] = 0.0f;
+    o.dist = -1.0;
+    reinterpret_cast<FeatSlot *>(P.samples)[oidx] = o;
 }

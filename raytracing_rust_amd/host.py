@@ -214,6 +214,31 @@ class Scene:
                                                             rgb.ctypes.data, se.ctypes.data, spp.ctypes.data, C.byref(st)))
         return {"linear": lin, "rgb8": rgb, "stderr": se, "spp": spp, "stats": _stats(st)}
 
+    def render_features(self, cam, nx, ny, ns, sig=False, precision="f32", **kw):
+        """First-hit features for denoisers (include/rtmi_features.h): the first interaction of render()'s paths, per
+        sample, averaged in f64.  Returns dict(albedo f32 [ny,nx,3], normal f32 [ny,nx,3], depth f32 [ny,nx] (+inf where
+        no sample hit), hits u32 [ny,nx], stats[, sig u64 [ny,nx]]); sig equals render(max_depth=0, sig=True)["sig"].
+        Row 0 is the top row.  A scene resident on a device list (upload_multi) raises Unsupported."""
+        if precision != "f32":
+            raise Unsupported("first-hit features have no f64 mode")
+        if not self.uploaded and not getattr(self, "multi_devices", None):
+            self.upload(kw.pop("device", 0))
+        kw.pop("device", None)
+        p = default_params(nx, ny, ns, **kw)
+        alb = np.zeros((ny, nx, 3), np.float32)
+        nrm = np.zeros((ny, nx, 3), np.float32)
+        dep = np.zeros((ny, nx), np.float32)
+        hits = np.zeros((ny, nx), np.uint32)
+        sg = np.zeros((ny, nx), np.uint64) if sig else None
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_features(self.h, cam.h, C.byref(p), alb.ctypes.data, nrm.ctypes.data,
+                                                            dep.ctypes.data, hits.ctypes.data, sg.ctypes.data if sig else None,
+                                                            C.byref(st)))
+        out = {"albedo": alb, "normal": nrm, "depth": dep, "hits": hits, "stats": _stats(st)}
+        if sig:
+            out["sig"] = sg
+        return out
+
     def render_multi(self, cam, nx, ny, ns, devices, **kw):
         """Whole image on several GPUs of this process (rtmi_render_multi): tiles t % len(devices), one gather.
         A device may be listed more than once (single-GPU rehearsal).  Bit-identical to render()."""
@@ -523,6 +548,22 @@ def ppm_p3(rgb8):
     buf = C.create_string_buffer(need)
     n = lib.rtmi_ppm_p3(nx, ny, rgb8.ctypes.data, buf, need)
     return buf.raw[:n]
+
+
+def pfm_bytes(plane):
+    """A float32 plane as PFM, the float format denoiser tools read: [ny,nx,3] -> "PF" (colour), [ny,nx] -> "Pf"
+    (greyscale).  The scale is -1 (little-endian samples) and rows run bottom to top, so row 0 of the array (the top row,
+    as every output here) is written last."""
+    a = np.asarray(plane)
+    if a.ndim == 3 and a.shape[2] == 3:
+        tag = b"PF"
+    elif a.ndim == 2:
+        tag = b"Pf"
+    else:
+        raise ValueError("pfm_bytes takes an [ny,nx,3] or [ny,nx] array, not %r" % (a.shape,))
+    ny, nx = a.shape[:2]
+    body = np.ascontiguousarray(a[::-1], dtype="<f4").tobytes()
+    return tag + b"\n%d %d\n-1.0\n" % (nx, ny) + body
 
 
 def write_ppm(path, rgb8, fmt=3):

@@ -34,6 +34,7 @@
 #include "rtmi.h"
 #include "rtmi_f64.h"
 #include "rtmi_adaptive.h"
+#include "rtmi_features.h"
 
 namespace rt {
 

@@ -255,6 +255,22 @@ RTH_API int rth_render_adaptive(void *lowered, void *cam, const rtmi_render_para
         return RTH_OK;
     });
 }
+// first-hit features (include/rtmi_features.h): RTH_UNSUPPORTED for what rtmi_render_features does not support, a
+// multi-GPU handle (rth_upload_multi) among it
+RTH_API int rth_render_features(void *lowered, void *cam, const rtmi_render_params *p, float *out_albedo, float *out_normal,
+                                float *out_depth, uint32_t *out_hits, uint64_t *out_path_sig, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi)
+            throw Unsupported("rtmi_render_features: multi-GPU handles have no features entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_features(o->dev, &c, p, out_albedo, out_normal, out_depth, out_hits, out_path_sig, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_features: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_features: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
 // ---- f64 render mode (include/rtmi_f64.h) ------------------------------------------------------------
 RTH_API int rth_lowered_desc_f64(void *lowered, rtmi_scene_f64 *out) {
     return guard([&] { *out = LOW(lowered)->lowered->desc_f64(); return RTH_OK; });
