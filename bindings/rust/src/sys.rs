@@ -472,3 +472,37 @@ extern "C" {
         stats: *mut RtmiStats,
     ) -> c_int;
 }
+
+// ---- include/rtmi_denoise.h: the a-trous denoiser guided by first-hit features --------------------------------------------
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiDenoiseParams {
+    pub iterations: u32,
+    pub normal_power: u32,
+    pub sigma_l: f32,
+    pub sigma_z: f32,
+    pub eps_l: f32,
+    pub eps_z: f32,
+    pub albedo_min: f32,
+    pub flags: u32,
+}
+
+extern "C" {
+    /// blocking a-trous denoise of host planes (colour, albedo, normal, depth, optional standard error)
+    pub fn rtmi_denoise(
+        device: c_int,
+        nx: u32,
+        ny: u32,
+        p: *const RtmiDenoiseParams,
+        linear: *const f32,
+        albedo: *const f32,
+        normal: *const f32,
+        depth: *const f32,
+        stderr_rgb: *const f32,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+    ) -> c_int;
+    /// the filter's rtmi_expf on the device
+    pub fn rtmi_probe_expf(device: c_int, x: *const f32, out: *mut f32, n: u32) -> c_int;
+}

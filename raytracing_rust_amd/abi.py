@@ -172,6 +172,16 @@ RTMI_ADAPTIVE_SYMBOLS = ["rtmi_render_adaptive"]
 # the functions of include/rtmi_features.h (first-hit features for denoisers), kept apart from those of include/rtmi.h
 RTMI_FEATURES_SYMBOLS = ["rtmi_render_features"]
 
+
+class DenoiseParams(C.Structure):
+    """rtmi_denoise_params (include/rtmi_denoise.h): the a-trous filter's settings (32 bytes)."""
+    _fields_ = [("iterations", C.c_uint32), ("normal_power", C.c_uint32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("eps_l", C.c_float), ("eps_z", C.c_float), ("albedo_min", C.c_float), ("flags", C.c_uint32)]
+
+
+# the functions of include/rtmi_denoise.h (the a-trous denoiser), kept apart from those of include/rtmi.h
+RTMI_DENOISE_SYMBOLS = ["rtmi_denoise", "rtmi_probe_expf"]
+
 _rtmi = None
 _host = None
 
@@ -245,6 +255,10 @@ def load_rtmi():
                                          C.POINTER(Stats)]
     lib.rtmi_render_features.restype = C.c_int
     lib.rtmi_render_features.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_denoise.restype = C.c_int
+    lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
+    lib.rtmi_probe_expf.restype = C.c_int
+    lib.rtmi_probe_expf.argtypes = [C.c_int, vp, vp, C.c_uint32]
     _rtmi = lib
     return lib
 

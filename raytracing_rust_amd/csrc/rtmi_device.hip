@@ -120,6 +120,8 @@ struct rtmi_scene {
 };
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
+// the message rtmi_last_error returns, set by the entry points of the other translation units (rtmi_denoise.hip)
+__attribute__((visibility("hidden"))) int rtmi_fail(int code, const char *msg) { return fail(code, msg); }
 
 #ifndef RTMI_BUILD_HASH
 #define RTMI_BUILD_HASH "unknown"

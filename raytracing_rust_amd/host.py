@@ -144,6 +144,7 @@ class Scene:
         """Copies the scene to `device`; f64=True also attaches the double planes of the f64 render mode."""
         self.host._check(self.host.lib.rth_upload(self.h, device))
         self.uploaded = True
+        self.device = device
         self.f64_attached = False
         if f64:
             self.attach_f64()
@@ -238,6 +239,20 @@ class Scene:
         if sig:
             out["sig"] = sg
         return out
+
+    def render_denoised(self, cam, nx, ny, ns, denoise=None, **kw):
+        """A render and its denoised image: render_adaptive(min_spp=ns, step_spp=1) (render()'s image plus its standard
+        errors), render_features with the same ns and keywords, then denoise() of the three on the scene's device.
+        `denoise` = dict of denoise() keywords.  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], noisy = the adaptive
+        dict, features = the features dict).  ns >= 2; the other restrictions are those of the two renders."""
+        if ns < 2:
+            raise ValueError("render_denoised needs ns >= 2 (a standard error needs two samples)")
+        noisy = self.render_adaptive(cam, nx, ny, ns, min_spp=ns, step_spp=1, **kw)
+        kw.pop("device", None)
+        ft = self.render_features(cam, nx, ny, ns, **kw)
+        out = _denoise(noisy["linear"], ft["albedo"], ft["normal"], ft["depth"], stderr=noisy["stderr"],
+                       device=self.device, **(denoise or {}))
+        return {"linear": out["linear"], "rgb8": out["rgb8"], "noisy": noisy, "features": ft}
 
     def render_multi(self, cam, nx, ny, ns, devices, **kw):
         """Whole image on several GPUs of this process (rtmi_render_multi): tiles t % len(devices), one gather.
@@ -548,6 +563,41 @@ def ppm_p3(rgb8):
     buf = C.create_string_buffer(need)
     n = lib.rtmi_ppm_p3(nx, ny, rgb8.ctypes.data, buf, need)
     return buf.raw[:n]
+
+
+def denoise(linear, albedo, normal, depth, stderr=None, iterations=5, normal_power=128, sigma_l=4.0, sigma_z=1.0,
+            eps_l=1e-10, eps_z=1e-3, albedo_min=1e-3, device=0):
+    """The a-trous denoiser of include/rtmi_denoise.h on `device`: linear, albedo, normal (and stderr, or None) are float32
+    [ny,nx,3], depth is float32 [ny,nx] (non-finite = no surface), row 0 the top row.  Returns dict(linear f32 [ny,nx,3],
+    rgb8 u8 [ny,nx,3]).  ValueError for a shape or dtype mismatch, HostError for what rtmi_denoise refuses."""
+    depth = np.asarray(depth)
+    if depth.ndim != 2:
+        raise ValueError("depth must be [ny, nx], not %r" % (depth.shape,))
+    ny, nx = depth.shape
+    planes = {"linear": linear, "albedo": albedo, "normal": normal, "depth": depth}
+    if stderr is not None:
+        planes["stderr"] = stderr
+    for name, a in planes.items():
+        a = np.asarray(a)
+        want = (ny, nx) if name == "depth" else (ny, nx, 3)
+        if a.shape != want:
+            raise ValueError("%s must have the shape %r, not %r" % (name, want, a.shape))
+        if a.dtype != np.float32:
+            raise ValueError("%s must be float32, not %s" % (name, a.dtype))
+        planes[name] = np.ascontiguousarray(a)
+    p = abi.DenoiseParams(iterations, normal_power, sigma_l, sigma_z, eps_l, eps_z, albedo_min, 0)
+    lin = np.zeros((ny, nx, 3), np.float32)
+    rgb = np.zeros((ny, nx, 3), np.uint8)
+    lib = abi.load_rtmi()
+    rc = lib.rtmi_denoise(device, nx, ny, C.byref(p), planes["linear"].ctypes.data, planes["albedo"].ctypes.data,
+                          planes["normal"].ctypes.data, planes["depth"].ctypes.data,
+                          planes["stderr"].ctypes.data if stderr is not None else None, lin.ctypes.data, rgb.ctypes.data)
+    if rc != 0:
+        raise {2: Unsupported}.get(rc, HostError)("rtmi_denoise failed (%d): %s" % (rc, lib.rtmi_last_error().decode()))
+    return {"linear": lin, "rgb8": rgb}
+
+
+_denoise = denoise
 
 
 def pfm_bytes(plane):
