@@ -506,3 +506,36 @@ extern "C" {
     /// the filter's rtmi_expf on the device
     pub fn rtmi_probe_expf(device: c_int, x: *const f32, out: *mut f32, n: u32) -> c_int;
 }
+
+// ---- include/rtmi_nee.h: next-event estimation with MIS toward the scene's area lights ---------------------------------
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiLight {
+    pub item: i32,
+    pub prim: i32,
+    pub kind: i32,
+    pub material: i32,
+    pub area: f64,
+    pub weight: f64,
+    pub select_p: f64,
+    pub cdf: f64,
+}
+
+extern "C" {
+    /// the light table of a flat description (host code, no device): at most `cap` lights, the full count in `count`
+    pub fn rtmi_lights_from_desc(desc: *const RtmiSceneDesc, out: *mut RtmiLight, cap: u32, count: *mut u32) -> c_int;
+    /// derives the light table of `desc` (the handle's own description) and uploads it
+    pub fn rtmi_scene_attach_lights(scene: *mut RtmiScene, desc: *const RtmiSceneDesc) -> c_int;
+    /// blocking whole-image NEE render: the image, its standard errors and rtmi_render's path signature
+    pub fn rtmi_render_nee(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_path_sig: *mut u64,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+}

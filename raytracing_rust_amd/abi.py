@@ -182,6 +182,16 @@ class DenoiseParams(C.Structure):
 # the functions of include/rtmi_denoise.h (the a-trous denoiser), kept apart from those of include/rtmi.h
 RTMI_DENOISE_SYMBOLS = ["rtmi_denoise", "rtmi_probe_expf"]
 
+
+class Light(C.Structure):
+    """rtmi_light (include/rtmi_nee.h): one eligible light occurrence of a scene description (48 bytes)."""
+    _fields_ = [("item", C.c_int32), ("prim", C.c_int32), ("kind", C.c_int32), ("material", C.c_int32),
+                ("area", C.c_double), ("weight", C.c_double), ("select_p", C.c_double), ("cdf", C.c_double)]
+
+
+# the functions of include/rtmi_nee.h (next-event estimation), kept apart from those of include/rtmi.h
+RTMI_NEE_SYMBOLS = ["rtmi_lights_from_desc", "rtmi_scene_attach_lights", "rtmi_render_nee"]
+
 _rtmi = None
 _host = None
 
@@ -255,6 +265,12 @@ def load_rtmi():
                                          C.POINTER(Stats)]
     lib.rtmi_render_features.restype = C.c_int
     lib.rtmi_render_features.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_lights_from_desc.restype = C.c_int
+    lib.rtmi_lights_from_desc.argtypes = [C.POINTER(SceneDesc), C.POINTER(Light), C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.rtmi_scene_attach_lights.restype = C.c_int
+    lib.rtmi_scene_attach_lights.argtypes = [vp, C.POINTER(SceneDesc)]
+    lib.rtmi_render_nee.restype = C.c_int
+    lib.rtmi_render_nee.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -315,6 +331,8 @@ def load_host():
         "rth_render_f64": (i, [vp, vp, C.POINTER(RenderParams), d, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_adaptive": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_features": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_attach_lights": (i, [vp]),
+        "rth_render_nee": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

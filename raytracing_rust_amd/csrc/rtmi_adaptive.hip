@@ -31,7 +31,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void rtmi_adaptive_coop(De
 template <bool FAST>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_adaptive_kernel(DevScene sc, DevCamera cam, DevParams P,
                                                                             const uint32_t *tiles) {
-    constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false;
+    constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false, NEE = false;
+    const DevLights nl{};
 #include "rtmi_kernel_perlane.inc"
 }
 

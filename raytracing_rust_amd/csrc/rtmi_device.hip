@@ -19,6 +19,7 @@
 #include <dlfcn.h>
 #include <time.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +42,8 @@
 #include "rtmi_adaptive_launch.hpp"
 #include "rtmi_features.h"
 #include "rtmi_features_launch.hpp"
+#include "rtmi_nee.h"
+#include "rtmi_nee_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -117,6 +120,12 @@ struct rtmi_scene {
     size_t ft_state_bytes = 0;
     float *ft_planes = nullptr; // albedo [ny*nx*3] | normal [ny*nx*3] | depth [ny*nx] | hits [ny*nx] (uint32)
     size_t ft_planes_bytes = 0;
+    // next-event estimation (include/rtmi_nee.h): the attached light table and per-primitive light index, freed with the
+    // handle
+    bool has_lights = false;
+    NeeLight *nee_lights = nullptr;    // [max(n, 1)]
+    int32_t *nee_prim_light = nullptr; // [max(n_prims, 1)]
+    uint32_t nee_n = 0;
 };
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
@@ -553,6 +562,8 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->h_ad_count) (void)hipHostFree(s->h_ad_count);
     if (s->ft_state) (void)hipFree(s->ft_state);
     if (s->ft_planes) (void)hipFree(s->ft_planes);
+    if (s->nee_lights) (void)hipFree(s->nee_lights);
+    if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
     if (s->partial) (void)hipFree(s->partial);
     if (s->samples) { // parked for the next handle on this device (see g_parked); no kernel may still write it
         if (s->busy_recorded) (void)hipEventSynchronize(s->busy);
@@ -2121,4 +2132,297 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
         stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
     }
     return RTMI_OK;
+}
+
+// ---- next-event estimation (include/rtmi_nee.h) -------------------------------------------------------------------------
+// The light table of a description: the eligible occurrences (item, prim) in item order, primitives in the order the item
+// reaches them.  Host code only (no HIP call), so the CPU tests can call it.
+static int nee_lights_of(const rtmi_scene_desc *d, std::vector<rtmi_light> &out) {
+    out.clear();
+    if (!d) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (d->abi_version != RTMI_ABI_VERSION) return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: abi_version mismatch");
+    if ((d->n_items && !d->items) || (d->n_prims && (!d->prim_a || !d->prim_b || !d->prim_meta)) ||
+        (d->n_nodes && !d->nodes) || (d->n_materials && !d->materials) || (d->n_textures && !d->textures))
+        return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: a non-empty array is NULL");
+    // every (item, prim) the world list can report, and how many items reach each primitive
+    std::vector<std::pair<int32_t, int32_t>> occ;
+    std::vector<int32_t> last_item(d->n_prims, -1);
+    std::vector<uint32_t> n_items_of(d->n_prims, 0u);
+    auto reach = [&](int32_t it, int64_t prim) -> bool {
+        if (prim < 0 || prim >= (int64_t)d->n_prims) return false;
+        if (last_item[prim] != it) { last_item[prim] = it; n_items_of[prim]++; occ.push_back({it, (int32_t)prim}); }
+        return true;
+    };
+    for (uint32_t it = 0; it < d->n_items; it++) {
+        const rtmi_item &I = d->items[it];
+        if (I.kind == RTMI_ITEM_LIST) {
+            for (int64_t k = 0; k < I.count; k++)
+                if (!reach((int32_t)it, (int64_t)I.first + k)) return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: primitive out of range");
+        } else if (I.kind == RTMI_ITEM_BVH) {
+            if (I.first < 0 || (uint32_t)I.first >= d->n_nodes) return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: root out of range");
+            std::vector<int32_t> stack{I.first};
+            uint64_t visits = 0;
+            while (!stack.empty()) {
+                const int32_t n = stack.back();
+                stack.pop_back();
+                if (++visits > 2ull * d->n_nodes + 2ull) return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: the tree is not a tree");
+                for (const int32_t c : {d->nodes[n].left, d->nodes[n].right}) {
+                    if (c >= 0) {
+                        if ((uint32_t)c >= d->n_nodes) return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: node out of range");
+                        stack.push_back(c);
+                    } else if (!reach((int32_t)it, (int64_t)((uint32_t)c & 0x0fffffffu))) {
+                        return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: primitive out of range");
+                    }
+                }
+            }
+        } else {
+            return fail(RTMI_ERR_INVALID, "rtmi_lights_from_desc: unknown item kind");
+        }
+    }
+    std::sort(occ.begin(), occ.end());
+    double total = 0.0;
+    for (const auto &o : occ) {
+        const rtmi_item &I = d->items[o.first];
+        const rtmi_prim_meta &M = d->prim_meta[o.second];
+        const float *A = d->prim_a + (size_t)o.second * 4;
+        if (n_items_of[o.second] != 1u) continue;              // reported by more than one item: not one occurrence
+        if (I.xform_count != 0 || (I.flags & RTMI_ITEMFLAG_MEDIUM)) continue;
+        if ((M.flags >> RTMI_PRIMFLAG_XF_COUNT_SHIFT) & RTMI_PRIM_XF_MAX) continue;
+        if (M.material < 0 || (uint32_t)M.material >= d->n_materials) continue;
+        const rtmi_material &m = d->materials[M.material];
+        if (m.kind != RTMI_MAT_DIFFUSE_LIGHT) continue;
+        double area;
+        if (M.type == RTMI_PRIM_RECT) {
+            if (!(A[0] < A[2]) || !(A[1] < A[3])) continue;      // never hit (rect.rs)
+            area = ((double)A[2] - (double)A[0]) * ((double)A[3] - (double)A[1]);
+        } else if (M.type == RTMI_PRIM_SPHERE ||
+                   (M.type == RTMI_PRIM_MSPHERE && d->prim_b[(size_t)o.second * 4] == 0.0f && d->prim_b[(size_t)o.second * 4 + 1] == 0.0f &&
+                    d->prim_b[(size_t)o.second * 4 + 2] == 0.0f && std::isfinite(M.inv_dt) && std::isfinite(d->prim_b[(size_t)o.second * 4 + 3]))) {
+            // (a MSPHERE without displacement is how the lowerings store a static Sphere among moving ones: c0 at all times)
+            if (!(A[3] > 0.0f) || !std::isfinite(A[0]) || !std::isfinite(A[1]) || !std::isfinite(A[2])) continue;
+            area = 4.0 * M_PI * (double)A[3] * (double)A[3];
+        } else {
+            continue;                                            // MSPHERE, CUBE
+        }
+        double w = 1.0;
+        if (m.tex >= 0 && (uint32_t)m.tex < d->n_textures && d->textures[m.tex].kind == RTMI_TEX_SOLID) {
+            const rtmi_texture &t = d->textures[m.tex];
+            w = std::max(std::max((double)t.f0, (double)t.f1), (double)t.f2);
+        }
+        if (!(w > 0.0) || !std::isfinite(area * w) || !(area > 0.0)) continue;
+        rtmi_light L{};
+        L.item = o.first; L.prim = o.second; L.kind = M.type == RTMI_PRIM_RECT ? RTMI_PRIM_RECT : RTMI_PRIM_SPHERE;
+        L.material = M.material;
+        L.area = area; L.weight = w;
+        out.push_back(L);
+        total += area * w;
+    }
+    double c = 0.0;
+    for (size_t i = 0; i < out.size(); i++) {
+        out[i].select_p = out[i].area * out[i].weight / total;
+        c += out[i].select_p;
+        out[i].cdf = i + 1 == out.size() ? 1.0 : c;
+    }
+    return RTMI_OK;
+}
+
+extern "C" int rtmi_lights_from_desc(const rtmi_scene_desc *desc, rtmi_light *out, uint32_t cap, uint32_t *count) {
+    if (!desc || !count || (cap && !out)) return fail(RTMI_ERR_INVALID, "NULL argument");
+    std::vector<rtmi_light> v;
+    const int rc = nee_lights_of(desc, v);
+    if (rc) return rc;
+    for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
+    *count = (uint32_t)v.size();
+    return RTMI_OK;
+}
+
+extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d) {
+    if (!s || !d) return fail(RTMI_ERR_INVALID, "NULL argument");
+    const rtmi_scene_desc &m = s->meta;
+    if (d->n_items != m.n_items || d->n_prims != m.n_prims || d->n_nodes != m.n_nodes || d->n_xforms != m.n_xforms ||
+        d->n_materials != m.n_materials || d->n_textures != m.n_textures)
+        return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_lights: counts differ from the handle's scene description");
+    std::vector<rtmi_light> v;
+    int rc = nee_lights_of(d, v);
+    if (rc) return rc;
+    std::vector<NeeLight> dl(v.size() ? v.size() : 1);
+    std::vector<int32_t> pl(d->n_prims ? d->n_prims : 1, -1);
+    for (size_t i = 0; i < v.size(); i++) {
+        NeeLight &L = dl[i];
+        const float *A = d->prim_a + (size_t)v[i].prim * 4;
+        L.geo = make_float4(A[0], A[1], A[2], A[3]);
+        L.k = d->prim_b[(size_t)v[i].prim * 4];
+        L.plane = v[i].kind == RTMI_PRIM_RECT ? (int32_t)((d->prim_meta[v[i].prim].flags >> RTMI_PRIMFLAG_PLANE_SHIFT) & 3u) : -1;
+        L.item = v[i].item; L.prim = v[i].prim;
+        L.area = (float)v[i].area; L.p_sel = (float)v[i].select_p; L.cdf = (float)v[i].cdf;
+        L.pad = 0;
+        pl[v[i].prim] = (int32_t)i;
+    }
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running NEE render may read the old table
+    if (s->nee_lights) { HIP_TRY(hipFree(s->nee_lights)); s->nee_lights = nullptr; }
+    if (s->nee_prim_light) { HIP_TRY(hipFree(s->nee_prim_light)); s->nee_prim_light = nullptr; }
+    s->has_lights = false;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->nee_lights), dl.size() * sizeof(NeeLight)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->nee_prim_light), pl.size() * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(s->nee_lights, dl.data(), dl.size() * sizeof(NeeLight), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->nee_prim_light, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    s->nee_n = (uint32_t)v.size();
+    s->has_lights = true;
+    return RTMI_OK;
+}
+
+// The per-lane NEE kernel (rtmi_nee.hip) in passes of the render's plan; adaptive sampling's resolve over the list of all
+// tiles carries sum, m and M2 between passes and writes texels and standard errors after the last one.
+extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
+                               uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
+    // every argument check comes before the first use of the device
+    if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    const uint32_t accepted = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                              RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG;
+    if (p_in->flags & ~accepted)
+        return fail(RTMI_ERR_UNSUPPORTED, "NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
+                                          "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)");
+    if (p_in->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, "NEE renders the whole image: tile_world must be 1");
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_lights) return fail(RTMI_ERR_INVALID, "rtmi_render_nee: no light table attached (rtmi_scene_attach_lights)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = ensure_streams(s))) return rc;
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // buffers below may be reallocated
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    struct BusyMark {
+        rtmi_scene *s; hipStream_t st;
+        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
+    } busy_mark{s, stream};
+    const uint32_t T = local_tiles_of(&p, 0);
+    const size_t ntex = (size_t)T * 64;
+    if (ntex > s->texel_count) {
+        if (s->texels) { HIP_TRY(hipFree(s->texels)); s->texels = nullptr; s->texel_count = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->texels), ntex * sizeof(rtmi_texel)));
+        s->texel_count = ntex;
+    }
+    if ((rc = ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex))) return rc;
+    if (T > s->ad_tiles) { // adaptive sampling's buffers (include/rtmi_adaptive.h), shared
+        if (s->ad_state) { HIP_TRY(hipFree(s->ad_state)); s->ad_state = nullptr; }
+        if (s->ad_lists) { HIP_TRY(hipFree(s->ad_lists)); s->ad_lists = nullptr; }
+        if (s->ad_stderr) { HIP_TRY(hipFree(s->ad_stderr)); s->ad_stderr = nullptr; }
+        if (s->ad_spp) { HIP_TRY(hipFree(s->ad_spp)); s->ad_spp = nullptr; }
+        s->ad_tiles = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_state), ntex * 9 * sizeof(double)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_lists), (2 * (size_t)T + 1) * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_stderr), ntex * 3 * sizeof(float)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_spp), ntex * sizeof(uint32_t)));
+        s->ad_tiles = T;
+    }
+    if (out_path_sig && ntex > s->sig_count) {
+        if (s->d_sig) { HIP_TRY(hipFree(s->d_sig)); s->d_sig = nullptr; s->sig_count = 0; }
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_sig), ntex * sizeof(unsigned long long)));
+        s->sig_count = ntex;
+    }
+    uint32_t chunk_spp = 0, pass_ns = 0;
+    if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
+
+    DevParams P{};
+    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth; P.t_min = p.t_min;
+    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
+    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p); P.ntiles_local = T;
+    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+    DevCamera C;
+    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
+    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
+    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
+    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
+    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
+    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
+    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
+    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sig = out_path_sig != nullptr;
+    P.stack_depth = s->meta.max_bvh_depth + 1u;
+    P.shade_threshold = p.shade_threshold ? (p.shade_threshold > 64u ? 64u : p.shade_threshold) : 40u;
+    P.status = s->status;
+    P.queue = s->status + 1;
+    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
+    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    P.path_sig = sig ? s->d_sig : nullptr;
+    DevLights L;
+    L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n;
+    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
+    s->last_kernel = RTMI_KERNEL_PERLANE;
+
+    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
+    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
+    {
+        std::vector<uint32_t> all(T);
+        for (uint32_t t = 0; t < T; t++) all[t] = t;
+        HIP_TRY(hipMemcpyAsync(s->ad_lists, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream)); // (`all` is pageable and goes out of scope)
+    }
+    s->units_total = 0;
+    AdaptiveResolve A;
+    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
+    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
+    uint32_t blocks_total = 0, chunks_total = 0;
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    for (uint32_t s0 = 0; s0 < p.ns; s0 += pass_ns) { // one pass unless the per-sample buffer is smaller than ns samples
+        P.pass_s0 = s0;
+        P.pass_cnt = p.ns - s0 < pass_ns ? p.ns - s0 : pass_ns;
+        P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
+        const uint64_t nitems = (uint64_t)T * P.nchunks;
+        if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
+        const uint32_t blocks = (uint32_t)(nitems < run_slots ? nitems : run_slots);
+        blocks_total += blocks; chunks_total += P.nchunks;
+        s->units_total += nitems;
+        HIP_TRY(rtmi_nee_launch_render(fast, sig, blocks, stream, s->dev, C, P, L));
+        const bool last = s0 + P.pass_cnt >= p.ns;
+        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
+        A.first = s0 == 0 ? 1 : 0;
+        A.decide = last ? 1 : 0;
+        if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
+        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
+        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, last ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    rtmi_scene *one[1] = {s};
+    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
+    if ((rc = check_overflow(s))) return rc;
+    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    const uint32_t txn = tiles_x_of(&p);
+    if (out_stderr) {
+        std::vector<float> h_se(ntex * 3);
+        HIP_TRY(hipMemcpy(h_se.data(), s->ad_stderr, ntex * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        for (uint32_t row = 0; row < p.ny; row++)
+            for (uint32_t px = 0; px < p.nx; px++) {
+                const size_t t = (size_t)((row / RTMI_TILE) * txn + px / RTMI_TILE) * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE;
+                const size_t o = (size_t)row * p.nx + px;
+                out_stderr[o * 3] = h_se[t * 3]; out_stderr[o * 3 + 1] = h_se[t * 3 + 1]; out_stderr[o * 3 + 2] = h_se[t * 3 + 2];
+            }
+    }
+    if (out_path_sig) {
+        s->h_sig.resize(ntex);
+        HIP_TRY(hipMemcpy(s->h_sig.data(), s->d_sig, ntex * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (uint32_t row = 0; row < p.ny; row++)
+            for (uint32_t px = 0; px < p.nx; px++) {
+                const uint32_t t = (row / RTMI_TILE) * txn + px / RTMI_TILE;
+                out_path_sig[(size_t)row * p.nx + px] = s->h_sig[(size_t)t * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE];
+            }
+    }
+    if (stats) {
+        float ms_r = 0.f, ms_all = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
+        stats->render_ms = ms_r;
+        stats->kernel_ms = ms_all;
+        stats->samples = (uint64_t)p.nx * p.ny * p.ns;
+        stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
+    }
+    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
 }

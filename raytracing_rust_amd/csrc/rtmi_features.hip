@@ -20,7 +20,8 @@
 
 template <bool FAST, bool SIG>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_features_kernel(DevScene sc, DevCamera cam, DevParams P) {
-    constexpr bool PROF = false, TILE_LIST = false, FEATURES = true;
+    constexpr bool PROF = false, TILE_LIST = false, FEATURES = true, NEE = false;
+    const DevLights nl{};
     const uint32_t *const tiles = nullptr;
 #include "rtmi_kernel_perlane.inc"
 }

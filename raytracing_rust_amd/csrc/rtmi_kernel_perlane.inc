@@ -1,8 +1,11 @@
 // rtmi_kernel_perlane.inc — body of the per-lane two-phase render kernel (rtmi_kernels.hpp), included INSIDE the kernels
 // that run it: rtmi_render_kernel (TILE_LIST = false) and the adaptive-sampling kernel rtmi_adaptive_kernel (rtmi_adaptive.hip,
 // TILE_LIST = true: the queue runs over a list of tiles, see wave_work).  The including function provides sc, cam, P, FAST, SIG,
-// PROF, TILE_LIST, FEATURES and `tiles`.  FEATURES (rtmi_features_kernel, rtmi_features.hip): every path ends at its first
-// interaction, which writes a FeatSlot (rtmi_shade.hpp) to the per-sample buffer instead of a radiance.  A textual body
+// PROF, TILE_LIST, FEATURES, NEE, `nl` and `tiles`.  FEATURES (rtmi_features_kernel, rtmi_features.hip): every path ends at
+// its first interaction, which writes a FeatSlot (rtmi_shade.hpp) to the per-sample buffer instead of a radiance.  NEE
+// (rtmi_nee_kernel, rtmi_nee.hip; include/rtmi_nee.h): a lane holds either its path ray or a pending shadow ray toward a
+// light sample (NeeLane); both are traced by the same item scan, the shadow ray with the light-sample stream swapped in
+// for the path's, and never touch the signature.  `nl`: the light table (DevLights).  A textual body
 // and not a force-inlined function: inlining one changed the instruction stream of every existing instantiation (same
 // instructions in another order and register assignment), and those must stay bit-for-bit what they were.
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
@@ -25,8 +28,16 @@
 
     uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
     bool alive = false, done = false, have_hit = false;
-    RngReg g;
+    typename std::conditional<NEE, RngNee, RngReg>::type g;
     rng_init(g, 0, 0);
+    NeeLane ne;
+    typename std::conditional<NEE, RngNee, RngReg>::type gn; // NEE: the light-sample stream (swapped with g for a shadow ray)
+    if constexpr (NEE) {
+        rng_set_stream(g, 0u);
+        rng_init(gn, 0, 0);
+        rng_set_stream(gn, 3u);
+        ne.cont_rd = f3(0, 0, 1); ne.c = f3(0, 0, 0); ne.pb = 0.0f; ne.light = 0; ne.shadow = false;
+    }
     Path pa;
     pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
     float closest = RTMI_FLT_MAX;
@@ -43,6 +54,7 @@
                     uint32_t smp = 0u, px = 0u, j = 0u;
                     if (work_take<TILE_LIST>(w, queue_empty, want, P, oidx, ltile, smp, px, j, tiles)) {
                         camera_sample(cam, P, g, k0, k1, smp, j * P.nx + px, px, j, pa);
+                        if constexpr (NEE) { rng_init(gn, smp, j * P.nx + px); ne.pb = 0.0f; }
                         alive = true;
                     } else if (want) {
                         done = true;
@@ -122,6 +134,8 @@
                 }
                 if (best_item >= 0) {
                     have_hit = true;
+                } else if (NEE && ne.shadow) { // the shadow ray left the world: V = 0; the path goes on
+                    if constexpr (NEE) { pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t; }
                 } else { // miss: black background (color.rs:21); the path ends
                     if constexpr (FEATURES) {
                         feat_miss(P, oidx, pa);
@@ -141,16 +155,33 @@
         {
             const bool shading = have_hit;
             have_hit = false;
-            if (SIG && shading) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
+            if (SIG && shading && !(NEE && ne.shadow)) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
             // all lanes call (wavefront texture lookup); the traversal stacks are idle now: LDS scratch
             if constexpr (FEATURES) { // the first interaction ends every path: its record goes to the feature slot
                 ShadeFeat feat;
-                shade_hit<RngReg, true, true>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium,
+                shade_hit<decltype(g), true, true>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium,
                                               pa, reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), &feat);
                 if (shading) {
                     feat_hit(P, oidx, pa, closest, feat);
                     if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                     alive = false;
+                }
+            } else if constexpr (NEE) {
+                const bool was_shadow = ne.shadow;
+                const bool goes_on = shade_hit<decltype(g), true, false, true>(
+                    sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
+                    reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), nullptr, &nl, &ne, &gn);
+                if (shading) {
+                    if (was_shadow) { // the light sample is counted: the path's continuation is traced next
+                        pa.rd = ne.cont_rd; ne.shadow = false;
+                        const auto t = g; g = gn; gn = t;
+                    } else if (!goes_on) {
+                        path_end(P, oidx, pa);
+                        if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                        alive = false;
+                    } else if (ne.shadow) { // a shadow ray was sampled: trace it with the light-sample stream
+                        const auto t = g; g = gn; gn = t;
+                    }
                 }
             } else {
             const bool goes_on = shade_hit(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,

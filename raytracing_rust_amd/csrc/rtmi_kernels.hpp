@@ -19,7 +19,8 @@
 // ----------------------------------------------------------------------------------
 template <bool FAST, bool SIG, bool PROF>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_render_kernel(DevScene sc, DevCamera cam, DevParams P) {
-    constexpr bool TILE_LIST = false, FEATURES = false;
+    constexpr bool TILE_LIST = false, FEATURES = false, NEE = false;
+    const DevLights nl{};
     const uint32_t *const tiles = nullptr;
 #include "rtmi_kernel_perlane.inc"
 }

@@ -153,6 +153,65 @@ __device__ __forceinline__ void rng_take2(RngReg &g, uint32_t k0, uint32_t k1, u
     g.pos = need ? pos - 2u : pos + 2u; // 3->1, 4->2
 }
 
+// ---- RngNee: RngReg with the stream id in a register (next-event estimation, include/rtmi_nee.h) -------------------
+// The NEE kernel keeps two of these per lane: the path's stream 0 and the light-sample stream 3.  A lane that traces a
+// shadow ray swaps them, so the item scan's medium draws come from stream 3 without a second copy of the scan.  Same
+// word selection as RngReg; only the fourth counter word differs.
+struct RngNee {
+    uint32_t block, sample, pixel;
+    uint32_t b0, b1, b2, b3;
+    uint32_t pos;
+    uint32_t stream;
+};
+__device__ __forceinline__ void rng_init(RngNee &g, uint32_t sample, uint32_t pixel) {
+    g.block = 0; g.sample = sample; g.pixel = pixel; g.pos = 4;
+}
+__device__ __forceinline__ void rng_attach(RngNee &, uint32_t *) {}
+__device__ __forceinline__ void rng_set_stream(RngNee &g, uint32_t stream) { g.stream = stream; }
+__device__ __forceinline__ void rng_set_stream(RngReg &, uint32_t) {}
+__device__ __forceinline__ float rng_uniform(RngNee &g, uint32_t k0, uint32_t k1) {
+    if (g.pos == 4) {
+        philox(g.block, g.sample, g.pixel, g.stream, k0, k1, g.b0, g.b1, g.b2, g.b3);
+        g.block++;
+        g.pos = 0;
+    }
+    const bool bit0 = (g.pos & 1u) != 0u, bit1 = (g.pos & 2u) != 0u;
+    const uint32_t y0 = RTMI_SEL(bit0, g.b1, g.b0), y1 = RTMI_SEL(bit0, g.b3, g.b2);
+    const uint32_t w = RTMI_SEL(bit1, y1, y0);
+    g.pos++;
+    return rtmi_u01(w);
+}
+__device__ __forceinline__ void rng_take3(RngNee &g, uint32_t k0, uint32_t k1, uint32_t &w0, uint32_t &w1, uint32_t &w2) {
+    uint32_t n0 = 0u, n1 = 0u, n2 = 0u, n3 = 0u;
+    const uint32_t pos = g.pos;
+    const bool need = pos >= 2u;
+    if (need) {
+        philox(g.block, g.sample, g.pixel, g.stream, k0, k1, n0, n1, n2, n3);
+        g.block++;
+    }
+    const bool bit0 = (pos & 1u) != 0u, bit1 = (pos & 2u) != 0u, full = pos == 4u;
+    const uint32_t y0 = RTMI_SEL(bit0, g.b1, g.b0), y1 = RTMI_SEL(bit0, g.b2, g.b1), y2 = RTMI_SEL(bit0, g.b3, g.b2),
+                   y3 = RTMI_SEL(bit0, n0, g.b3), y4 = RTMI_SEL(bit0, n1, n0);
+    const uint32_t z0 = RTMI_SEL(bit1, y2, y0), z1 = RTMI_SEL(bit1, y3, y1), z2 = RTMI_SEL(bit1, y4, y2);
+    w0 = RTMI_SEL(full, n0, z0); w1 = RTMI_SEL(full, n1, z1); w2 = RTMI_SEL(full, n2, z2);
+    g.b0 = RTMI_SEL(need, n0, g.b0); g.b1 = RTMI_SEL(need, n1, g.b1); g.b2 = RTMI_SEL(need, n2, g.b2); g.b3 = RTMI_SEL(need, n3, g.b3);
+    g.pos = need ? pos - 1u : pos + 3u;
+}
+__device__ __forceinline__ void rng_take2(RngNee &g, uint32_t k0, uint32_t k1, uint32_t &w0, uint32_t &w1) {
+    uint32_t n0 = 0u, n1 = 0u, n2 = 0u, n3 = 0u;
+    const uint32_t pos = g.pos;
+    const bool need = pos >= 3u;
+    if (need) {
+        philox(g.block, g.sample, g.pixel, g.stream, k0, k1, n0, n1, n2, n3);
+        g.block++;
+    }
+    const bool bit0 = (pos & 1u) != 0u, bit1 = (pos & 2u) != 0u, full = pos == 4u;
+    const uint32_t y0 = RTMI_SEL(bit0, g.b1, g.b0), y1 = RTMI_SEL(bit0, g.b2, g.b1), y2 = RTMI_SEL(bit0, g.b3, g.b2), y3 = RTMI_SEL(bit0, n0, g.b3);
+    const uint32_t z0 = RTMI_SEL(bit1, y2, y0), z1 = RTMI_SEL(bit1, y3, y1);
+    w0 = RTMI_SEL(full, n0, z0); w1 = RTMI_SEL(full, n1, z1);
+    g.b0 = RTMI_SEL(need, n0, g.b0); g.b1 = RTMI_SEL(need, n1, g.b1); g.b2 = RTMI_SEL(need, n2, g.b2); g.b3 = RTMI_SEL(need, n3, g.b3);
+    g.pos = need ? pos - 2u : pos + 2u;
+}
 
 // src/util.rs:4-13 (draws x, y, z per trial)
 template <typename RngT>

@@ -352,6 +352,92 @@ struct ShadeFeat {
     F3 normal; // the normal the material's scatter sees (after FlipNormals and FACE_FORWARD); 0 for a medium event
 };
 
+// ---- next-event estimation (include/rtmi_nee.h, rtmi_nee.hip) --------------------------------------------------------
+// One eligible light occurrence on the device, built by rtmi_scene_attach_lights from the table of rtmi_lights_from_desc.
+struct NeeLight {
+    float4 geo;     // RECT {a0, b0, a1, b1} (plane A of the primitive) | SPHERE {cx, cy, cz, r}
+    float k;        // RECT: the plane's coordinate
+    int32_t plane;  // RECT: 0 = YZ (a = y, b = z), 1 = ZX (a = z, b = x), 2 = XY (a = x, b = y); SPHERE: -1
+    int32_t item, prim;
+    float area, p_sel, cdf;
+    int32_t pad;
+}; // 48 B
+struct DevLights {
+    const NeeLight *lights;
+    const int32_t *prim_light; // per primitive: index of its light, or -1
+    uint32_t n;
+};
+// per-lane NEE state of the NEE kernel
+struct NeeLane {
+    F3 cont_rd; // while a shadow ray is traced: the direction of the path's continuation (its origin is the shadow ray's)
+    F3 c;       // the pending light sample: T * albedo * (p_b p_l / (p_b^2 + p_l^2)); Le comes from the shadow hit
+    float pb;   // density p_b of the scatter that produced the path's current ray; 0 = weight 1 at an emitter hit
+    int light;  // the light the pending shadow ray was sampled on
+    bool shadow; // the lane traces (or holds the hit of) a shadow ray
+};
+#define RTMI_NEE_2_OVER_PI 0.63661977236758134f
+#define RTMI_NEE_INV_4PI 0.079577471545947668f
+// the Lambertian's density of direction w at a vertex with scatter normal n: (2/pi) max(0, cos)^3 (normal + unit ball)
+__device__ __forceinline__ float nee_pb_lambert(F3 w, F3 n) {
+    const float c = dot(w, n) / __builtin_sqrtf(dot(w, w) * dot(n, n));
+    return c > 0.0f ? RTMI_NEE_2_OVER_PI * (c * c * c) : 0.0f;
+}
+// power-heuristic factors, as ratios (no overflow): light sample p_b p_l / (p_b^2 + p_l^2), BSDF hit p_b^2 / (p_b^2 + p_l^2)
+__device__ __forceinline__ float nee_mis_light(float pb, float pl) {
+    const float r = pb < pl ? pb / pl : pl / pb;
+    return r / (1.0f + r * r);
+}
+__device__ __forceinline__ float nee_mis_bsdf(float pb, float pl) {
+    if (pb >= pl) { const float r = pl / pb; return 1.0f / (1.0f + r * r); }
+    const float r = pb / pl, r2 = r * r;
+    return r2 / (1.0f + r2);
+}
+__device__ __forceinline__ F3 nee_rect_point(const NeeLight &L, float a, float b) {
+    return L.plane == 0 ? f3(L.k, a, b) : (L.plane == 1 ? f3(b, L.k, a) : f3(a, b, L.k));
+}
+__device__ __forceinline__ float nee_axis(const NeeLight &L, F3 w) { return L.plane == 0 ? w.x : (L.plane == 1 ? w.y : w.z); }
+// p_l = p_sel * p_L of the light at the point q seen from x (rect: d^2 / (|cos_l| A); sphere: the cone's, 0 from inside)
+__device__ __forceinline__ float nee_pdf(const NeeLight &L, F3 x, F3 q) {
+    if (L.plane >= 0) {
+        const F3 w = q - x;
+        const float d2 = dot(w, w);
+        return L.p_sel * (d2 * __builtin_sqrtf(d2)) / (__builtin_fabsf(nee_axis(L, w)) * L.area);
+    }
+    const F3 dc = f3(L.geo.x, L.geo.y, L.geo.z) - x;
+    const float s = (L.geo.w * L.geo.w) / dot(dc, dc);
+    if (!(s < 1.0f)) return 0.0f;
+    const float omc = s / (1.0f + __builtin_sqrtf(1.0f - s)); // 1 - cos(theta_max) without cancellation
+    return L.p_sel / (2.0f * RTMI_PI_F * omc);
+}
+// A point on light L for the vertex x from two uniforms: the direction (unnormalised, q - x) and p_l; false = no sample
+__device__ __forceinline__ bool nee_sample(const NeeLight &L, F3 x, float u1, float u2, F3 &dir, float &pl) {
+    if (L.plane >= 0) { // uniform on the rect
+        const F3 q = nee_rect_point(L, L.geo.x + u1 * (L.geo.z - L.geo.x), L.geo.y + u2 * (L.geo.w - L.geo.y));
+        dir = q - x;
+        pl = nee_pdf(L, x, q);
+        return true;
+    }
+    // uniform direction in the cone the sphere subtends from x
+    const F3 dc = f3(L.geo.x, L.geo.y, L.geo.z) - x;
+    const float dist2 = dot(dc, dc), r2 = L.geo.w * L.geo.w;
+    const float s = r2 / dist2;
+    if (!(s < 1.0f)) return false;
+    const float omc = s / (1.0f + __builtin_sqrtf(1.0f - s));
+    const float om = u1 * omc; // 1 - cos(theta)
+    const float ct = 1.0f - om, st = __builtin_sqrtf(fmaxf(0.0f, om * (2.0f - om)));
+    const float phi = 2.0f * RTMI_PI_F * u2;
+    const float dist = __builtin_sqrtf(dist2);
+    const F3 w = vdiv(dc, dist);
+    const float sg = w.z >= 0.0f ? 1.0f : -1.0f; // orthonormal basis around w (Duff et al. 2017)
+    const float a = -1.0f / (sg + w.z), b = w.x * w.y * a;
+    const F3 t1 = f3(1.0f + sg * w.x * w.x * a, sg * b, -sg * w.x), t2 = f3(b, sg + w.y * w.y * a, -w.y);
+    const F3 d = w * ct + t1 * (st * __builtin_cosf(phi)) + t2 * (st * __builtin_sinf(phi));
+    const float tq = dist * ct - __builtin_sqrtf(fmaxf(0.0f, r2 - dist2 * (st * st))); // the near intersection
+    dir = d * tq;
+    pl = L.p_sel / (2.0f * RTMI_PI_F * omc);
+    return tq > 0.0f;
+}
+
 // HitRecord of the closest hit (hittable.rs:9-16), built once, then
 // color(): emitted + attenuation * color(scattered) — color.rs:8-15, in throughput form.
 // ALL 64 lanes call this together (the texture lookup is a wavefront operation, tex_value_wave); lanes with
@@ -359,10 +445,16 @@ struct ShadeFeat {
 // false when it ended (or the lane was not active).  `scratch`: 64 floats of LDS private to the wavefront.
 // FEAT (features kernels, rtmi_features.hip): the record and the texture value (looked up whatever max_depth says) go
 // to *feat of every active lane instead of a scatter; no draws, and the path always ends.
-template <typename RngT, bool INST = true, bool FEAT = false>
+// NEE (next-event estimation kernels, rtmi_nee.hip; include/rtmi_nee.h): a lane whose ne->shadow is set holds the hit of
+// its shadow ray: it draws nothing and adds ne->c * Le when the hit is the sampled light occurrence.  A path lane weights
+// an emitter hit of an eligible light by nee_mis_bsdf, and at a scattering Lambertian / Isotropic vertex draws a light
+// sample from *gn (stream 3): on success pa.rd becomes the shadow ray, ne->cont_rd keeps the continuation and ne->shadow
+// is set.
+template <typename RngT, bool INST = true, bool FEAT = false, bool NEE = false>
 __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth, uint32_t ext, RngT &g, uint32_t k0, uint32_t k1,
                                           bool active, float closest, int best_item, int best_pf, bool best_medium, Path &pa,
-                                          float *scratch, ShadeFeat *feat = nullptr) {
+                                          float *scratch, ShadeFeat *feat = nullptr, const DevLights *nl = nullptr,
+                                          NeeLane *ne = nullptr, RngT *gn = nullptr) {
     F3 hp = f3(0, 0, 0), hn = f3(1, 0, 0);
     float hu = 0.0f, hv = 0.0f;
     rtmi_material M;
@@ -460,14 +552,36 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
         textured = M.kind == RTMI_MAT_LAMBERTIAN || M.kind == RTMI_MAT_METAL || M.kind == RTMI_MAT_ISOTROPIC;
         const bool want_sample = can_scatter && (M.kind == RTMI_MAT_LAMBERTIAN || M.kind == RTMI_MAT_ISOTROPIC ||
                                                  (M.kind == RTMI_MAT_METAL && M.param > 0.0f));
-        if (!FEAT && want_sample) rs = random_in_unit_sphere(g, k0, k1);
+        if (!FEAT && want_sample && !(NEE && ne->shadow)) rs = random_in_unit_sphere(g, k0, k1);
     }
     const int kind = M.kind;
-    const bool want_tex = active && (kind == RTMI_MAT_DIFFUSE_LIGHT || ((FEAT || can_scatter) && textured));
+    // (NEE: a shadow lane looks up an emitter's texture only)
+    const bool want_tex = NEE ? active && (kind == RTMI_MAT_DIFFUSE_LIGHT || (can_scatter && textured && !ne->shadow))
+                              : active && (kind == RTMI_MAT_DIFFUSE_LIGHT || ((FEAT || can_scatter) && textured));
     const F3 tv = tex_value_wave(sc, want_tex, T0, hu, hv, hp, scratch); // every lane of the wavefront
     bool scattered = false;
     if (active) {
+        if constexpr (NEE) {
+            if (ne->shadow) { // V = 1 iff the shadow ray's closest hit is the sampled occurrence; Le = its texture value
+                const NeeLight &Ls = nl->lights[ne->light];
+                if (!best_medium && kind == RTMI_MAT_DIFFUSE_LIGHT && best_item == Ls.item && (best_pf >> 3) == Ls.prim)
+                    pa.L = pa.L + ne->c * tv;
+                return false;
+            }
+            if (kind == RTMI_MAT_DIFFUSE_LIGHT) { // weight 1 (tv * 1 == tv) unless an eligible light ends a diffuse scatter
+                float w = 1.0f;
+                if (!best_medium && ne->pb > 0.0f) {
+                    const int li = nl->prim_light[best_pf >> 3];
+                    if (li >= 0 && nl->lights[li].item == best_item) {
+                        const float pl = nee_pdf(nl->lights[li], pa.ro, hp);
+                        if (pl > 0.0f) w = nee_mis_bsdf(ne->pb, pl);
+                    }
+                }
+                pa.L = pa.L + pa.T * (tv * w);
+            }
+        } else {
         if (kind == RTMI_MAT_DIFFUSE_LIGHT) pa.L = pa.L + pa.T * tv; // material.rs:148-150
+        }
         const F3 rd = pa.rd;
         F3 nd = rd, att = f3(1, 1, 1);
         // opt-in RTMI_FLAG_FACE_FORWARD (wave-uniform): the opaque materials see the normal turned against the ray
@@ -519,10 +633,38 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
                 scattered = true;
             }
         }
+        F3 sdir = nd;
+        if constexpr (NEE) { // the light sample of a scattering Lambertian / Isotropic vertex (draw order: rtmi_nee.h)
+            ne->pb = 0.0f;
+            if (scattered && nl->n > 0u && (kind == RTMI_MAT_LAMBERTIAN || kind == RTMI_MAT_ISOTROPIC)) {
+                const bool iso = kind == RTMI_MAT_ISOTROPIC;
+                ne->pb = iso ? RTMI_NEE_INV_4PI : nee_pb_lambert(nd, hn);
+                uint32_t w0, w1, w2;
+                rng_take3(*gn, k0, k1, w0, w1, w2);
+                const float us = rtmi_u01(w0);
+                uint32_t lo = 0u, hi = nl->n - 1u; // the first light whose cdf exceeds us
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (us < nl->lights[mid].cdf) hi = mid; else lo = mid + 1u;
+                }
+                F3 dir;
+                float pl;
+                if (nee_sample(nl->lights[lo], hp, rtmi_u01(w1), rtmi_u01(w2), dir, pl)) {
+                    const float pbl = iso ? RTMI_NEE_INV_4PI : nee_pb_lambert(dir, hn);
+                    if (pbl > 0.0f && pl > 0.0f && pl < RTMI_FLT_MAX) {
+                        ne->c = (pa.T * tv) * nee_mis_light(pbl, pl);
+                        ne->light = (int)lo;
+                        ne->cont_rd = nd;
+                        ne->shadow = true;
+                        sdir = dir;
+                    }
+                }
+            }
+        }
         if (scattered) {
             pa.T = pa.T * att;
             pa.ro = hp;
-            pa.rd = nd;
+            pa.rd = sdir;
             pa.depth++;
         }
     }

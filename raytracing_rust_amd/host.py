@@ -140,14 +140,40 @@ class Scene:
                 "item_root": view(d.item_root, d.n_items, 6), "material_param": view(d.material_param, d.n_materials, 1)[:, 0],
                 "texture_f": view(d.texture_f, d.n_textures, 4), "perlin_ranvec": view(d.perlin_ranvec, d.n_perlin, 768)}
 
-    def upload(self, device=0, f64=False):
-        """Copies the scene to `device`; f64=True also attaches the double planes of the f64 render mode."""
+    def upload(self, device=0, f64=False, nee=False):
+        """Copies the scene to `device`; f64=True also attaches the double planes of the f64 render mode, nee=True the
+        light table of next-event estimation (include/rtmi_nee.h)."""
         self.host._check(self.host.lib.rth_upload(self.h, device))
         self.uploaded = True
         self.device = device
         self.f64_attached = False
+        self.lights_attached = False
         if f64:
             self.attach_f64()
+        if nee:
+            self.attach_lights()
+        return self
+
+    def lights(self):
+        """The light table of next-event estimation (rtmi_lights_from_desc, include/rtmi_nee.h) as a numpy structured
+        array with the fields item, prim, kind, material, area, weight, select_p, cdf.  Host code: needs no GPU."""
+        lib = abi.load_rtmi()
+        d = self.desc()
+        n = C.c_uint32(0)
+        if lib.rtmi_lights_from_desc(C.byref(d), None, 0, C.byref(n)):
+            raise HostError("rtmi_lights_from_desc: " + (lib.rtmi_last_error() or b"").decode())
+        buf = (abi.Light * max(n.value, 1))()
+        if lib.rtmi_lights_from_desc(C.byref(d), buf, n.value, C.byref(n)):
+            raise HostError("rtmi_lights_from_desc: " + (lib.rtmi_last_error() or b"").decode())
+        dt = np.dtype([("item", "<i4"), ("prim", "<i4"), ("kind", "<i4"), ("material", "<i4"), ("area", "<f8"),
+                       ("weight", "<f8"), ("select_p", "<f8"), ("cdf", "<f8")])
+        assert dt.itemsize == C.sizeof(abi.Light) == 48
+        return np.frombuffer(bytes(buf)[:n.value * 48], dtype=dt).copy()
+
+    def attach_lights(self):
+        """Derives the light table and attaches it to the uploaded handle (rtmi_scene_attach_lights)."""
+        self.host._check(self.host.lib.rth_attach_lights(self.h))
+        self.lights_attached = True
         return self
 
     def attach_f64(self):
@@ -240,14 +266,44 @@ class Scene:
             out["sig"] = sg
         return out
 
-    def render_denoised(self, cam, nx, ny, ns, denoise=None, **kw):
+    def render_nee(self, cam, nx, ny, ns, sig=False, precision="f32", **kw):
+        """Next-event estimation (include/rtmi_nee.h): render()'s paths with a light sample at every diffuse vertex,
+        combined by the power heuristic; an estimator of the same image.  Returns dict(linear f32 [ny,nx,3], rgb8 u8
+        [ny,nx,3], stderr f32 [ny,nx,3], stats[, sig u64 [ny,nx]]); sig equals render(sig=True)["sig"].  The light table
+        is attached on first use.  A scene resident on a device list (upload_multi) raises Unsupported."""
+        if precision != "f32":
+            raise Unsupported("next-event estimation has no f64 mode")
+        if not self.uploaded and not getattr(self, "multi_devices", None):
+            self.upload(kw.pop("device", 0))
+        kw.pop("device", None)
+        if self.uploaded and not getattr(self, "lights_attached", False):
+            self.attach_lights()
+        p = default_params(nx, ny, ns, **kw)
+        lin = np.zeros((ny, nx, 3), np.float32)
+        rgb = np.zeros((ny, nx, 3), np.uint8)
+        se = np.zeros((ny, nx, 3), np.float32)
+        sg = np.zeros((ny, nx), np.uint64) if sig else None
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_nee(self.h, cam.h, C.byref(p), lin.ctypes.data, rgb.ctypes.data,
+                                                       se.ctypes.data, sg.ctypes.data if sig else None, C.byref(st)))
+        out = {"linear": lin, "rgb8": rgb, "stderr": se, "stats": _stats(st)}
+        if sig:
+            out["sig"] = sg
+        return out
+
+    def render_denoised(self, cam, nx, ny, ns, denoise=None, nee=False, **kw):
         """A render and its denoised image: render_adaptive(min_spp=ns, step_spp=1) (render()'s image plus its standard
         errors), render_features with the same ns and keywords, then denoise() of the three on the scene's device.
         `denoise` = dict of denoise() keywords.  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], noisy = the adaptive
-        dict, features = the features dict).  ns >= 2; the other restrictions are those of the two renders."""
+        dict, features = the features dict).  ns >= 2; the other restrictions are those of the two renders.
+        nee=True: the noisy image and its standard errors come from render_nee (the same paths, so the features still
+        describe them)."""
         if ns < 2:
             raise ValueError("render_denoised needs ns >= 2 (a standard error needs two samples)")
-        noisy = self.render_adaptive(cam, nx, ny, ns, min_spp=ns, step_spp=1, **kw)
+        if nee:
+            noisy = self.render_nee(cam, nx, ny, ns, **kw)
+        else:
+            noisy = self.render_adaptive(cam, nx, ny, ns, min_spp=ns, step_spp=1, **kw)
         kw.pop("device", None)
         ft = self.render_features(cam, nx, ny, ns, **kw)
         out = _denoise(noisy["linear"], ft["albedo"], ft["normal"], ft["depth"], stderr=noisy["stderr"],

@@ -35,6 +35,7 @@
 #include "rtmi_f64.h"
 #include "rtmi_adaptive.h"
 #include "rtmi_features.h"
+#include "rtmi_nee.h"
 
 namespace rt {
 

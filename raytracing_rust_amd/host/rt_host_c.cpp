@@ -271,6 +271,33 @@ RTH_API int rth_render_features(void *lowered, void *cam, const rtmi_render_para
         return RTH_OK;
     });
 }
+// next-event estimation (include/rtmi_nee.h): attaches the light table of the lowered scene to its uploaded handle, then
+// renders; RTH_UNSUPPORTED for what rtmi_render_nee does not support, a multi-GPU handle among it
+RTH_API int rth_attach_lights(void *lowered) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi)
+            throw Unsupported("rtmi_scene_attach_lights: multi-GPU handles have no NEE entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_scene_desc d = o->lowered->desc();
+        if (int rc = rtmi_scene_attach_lights(o->dev, &d))
+            throw std::runtime_error(std::string("rtmi_scene_attach_lights: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+RTH_API int rth_render_nee(void *lowered, void *cam, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8,
+                           float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi) throw Unsupported("rtmi_render_nee: multi-GPU handles have no NEE entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_nee(o->dev, &c, p, out_linear, out_rgb8, out_stderr, out_path_sig, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_nee: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_nee: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
 // ---- f64 render mode (include/rtmi_f64.h) ------------------------------------------------------------
 RTH_API int rth_lowered_desc_f64(void *lowered, rtmi_scene_f64 *out) {
     return guard([&] { *out = LOW(lowered)->lowered->desc_f64(); return RTH_OK; });

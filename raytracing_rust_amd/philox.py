@@ -8,6 +8,7 @@ which is not reproducible.  This build replaces it with keyed counter streams:
     stream_id 0: render path, one stream per (pixel, sample)   [device + oracle]
     stream_id 1: scene construction inside the host library    [BVH axes, Perlin tables]
     stream_id 2: scene construction in the scene builders      [positions, albedos]
+    stream_id 3: next-event estimation's light samples         [light, point, shadow-ray media; include/rtmi_nee.h]
 
 The n-th draw of a stream is word n % 4 of block n // 4; a uniform is the top 24 bits
 of the word times 2^-24 (exact in fp32 and f64).
