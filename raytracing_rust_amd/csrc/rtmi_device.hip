@@ -81,14 +81,13 @@ struct rtmi_scene {
     uint32_t last_kernel = 0;       // RTMI_KERNEL_* of the last render enqueued on this handle (rtmi_stats.kernel)
     // scratch of the blocking host API (grow-only, so a host that renders frame after frame allocates once)
     rtmi_texel *texels = nullptr;
-    size_t texel_count = 0;
+    size_t texels_bytes = 0;
     unsigned long long *d_sig = nullptr;
-    size_t sig_count = 0;
+    size_t sig_bytes = 0;
     rtmi_texel *h_texels = nullptr;    // pinned host mirror of `texels` (hipHostMalloc: the D2H copy runs at link speed)
     size_t h_texel_count = 0;
     rtmi_texel *h_partial = nullptr;   // ... and of the partial images rtmi_partial_image fetches (RTMI_FLAG_PROGRESSIVE)
     size_t h_partial_count = 0;
-    std::vector<unsigned long long> h_sig;
     // Thread model (rtmi.h): render calls on one handle serialise.  `mu` orders the host side (planning, scratch
     // (re)allocation, enqueue, and for the blocking calls the wait and the copy-out); `busy` chains the device side: a
     // render enqueued on ANY stream first waits for the previous render of this handle, whose kernels use the same
@@ -604,6 +603,271 @@ static int check_params(const rtmi_render_params *p) {
     return RTMI_OK;
 }
 
+// ---- host-side plumbing shared by the render entry points ------------------------------------------------------------
+// records the end of a call's work on `st` on every return path after its first enqueue (thread model: `busy`)
+struct BusyMark {
+    rtmi_scene *s;
+    hipStream_t st;
+    ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
+};
+
+// Grow-only device buffer of the handle: reallocated when a call needs more than `have` bytes.  A render of this handle
+// enqueued asynchronously (rtmi_render_device) may still use the old buffer: it is released after that render.
+template <typename T>
+static int grow(rtmi_scene *s, T *&ptr, size_t &have, size_t want) {
+    if (want <= have) return RTMI_OK;
+    if (ptr) {
+        if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
+        HIP_TRY(hipFree(ptr));
+        ptr = nullptr;
+        have = 0;
+    }
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ptr), want));
+    have = want;
+    return RTMI_OK;
+}
+
+// pinned host mirror of a texel buffer (grow-only)
+static int ensure_host_texels(rtmi_texel **h, size_t *have, size_t want) {
+    if (want <= *have) return RTMI_OK;
+    if (*h) { HIP_TRY(hipHostFree(*h)); *h = nullptr; *have = 0; }
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(h), want * sizeof(rtmi_texel), hipHostMallocDefault));
+    *have = want;
+    return RTMI_OK;
+}
+
+// the handle's framebuffer for `ntex` texels and its pinned host mirror
+static int reserve_texels(rtmi_scene *s, size_t ntex) {
+    if (int rc = grow(s, s->texels, s->texels_bytes, ntex * sizeof(rtmi_texel))) return rc;
+    return ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex);
+}
+
+// adaptive sampling's buffers (include/rtmi_adaptive.h; NEE shares them), grown together for T tiles
+static int grow_adaptive(rtmi_scene *s, uint32_t T) {
+    if (T <= s->ad_tiles) return RTMI_OK;
+    const auto bytes = [](size_t tiles, size_t out[4]) {
+        out[0] = tiles * 64 * 9 * sizeof(double);
+        out[1] = (2 * tiles + 1) * sizeof(uint32_t);
+        out[2] = tiles * 64 * 3 * sizeof(float);
+        out[3] = tiles * 64 * sizeof(uint32_t);
+    };
+    size_t have[4], want[4];
+    bytes(s->ad_tiles, have);
+    bytes(T, want);
+    s->ad_tiles = 0; // nothing is valid until all four have grown
+    int rc;
+    if ((rc = grow(s, s->ad_state, have[0], want[0])) || (rc = grow(s, s->ad_lists, have[1], want[1])) ||
+        (rc = grow(s, s->ad_stderr, have[2], want[2])) || (rc = grow(s, s->ad_spp, have[3], want[3])))
+        return rc;
+    s->ad_tiles = T;
+    return RTMI_OK;
+}
+// adaptive sampling's first list of active tiles: all of them (NEE's resolve walks it as well)
+static int list_all_tiles(rtmi_scene *s, uint32_t T, hipStream_t stream) {
+    std::vector<uint32_t> all(T);
+    for (uint32_t t = 0; t < T; t++) all[t] = t;
+    HIP_TRY(hipMemcpyAsync(s->ad_lists, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream)); // (`all` is pageable and goes out of scope)
+    return RTMI_OK;
+}
+
+static int ensure_streams(rtmi_scene *s) {
+    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (!s->copy_stream) {
+        // The progress polls must not queue behind the render.  The runtime gives streams at most GPU_MAX_HW_QUEUES
+        // hardware queues per priority and shares the least used one beyond that (with 2, the two streams of a handle
+        // landed on one queue and every poll waited for the whole render); another priority is another pool.
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&s->copy_stream, hipStreamNonBlocking, greatest));
+    }
+    return RTMI_OK;
+}
+
+// start of a blocking call on the handle's own stream (the caller holds s->mu and has selected s->device): no earlier
+// render of this handle may still run, the buffers of the call may be reallocated
+static int begin_blocking(rtmi_scene *s) {
+    if (int rc = ensure_streams(s)) return rc;
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
+    return RTMI_OK;
+}
+
+// argument checks of the whole-image modes (adaptive sampling, features, NEE) after their NULL checks, in this order
+static int check_mode_params(const rtmi_render_params *p, uint32_t accepted, const char *flags_msg, const char *world_msg) {
+    if (int rc = check_params(p)) return rc;
+    if (p->flags & ~accepted) return fail(RTMI_ERR_UNSUPPORTED, flags_msg);
+    if (p->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, world_msg);
+    return RTMI_OK;
+}
+
+static DevCamera dev_camera(const rtmi_camera *cam) {
+    DevCamera C;
+    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
+    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
+    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
+    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
+    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
+    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
+    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    return C;
+}
+
+// pruned traversal needs the BVH boxes to contain their moving spheres at every ray time (camera.rs:65)
+static bool boxes_valid(const rtmi_scene *s, const rtmi_camera *cam) {
+    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
+    return cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
+}
+
+// the DevParams every f32 render call fills alike; the pass plan, the buffers and the traversal plan come later
+static DevParams dev_params(const rtmi_scene *s, const rtmi_render_params *p) {
+    DevParams P{};
+    P.nx = p->nx; P.ny = p->ny; P.ns = p->ns; P.max_depth = p->max_depth; P.t_min = p->t_min;
+    P.key0 = (uint32_t)p->seed; P.key1 = (uint32_t)(p->seed >> 32);
+    P.tile_rank = p->tile_rank; P.tile_world = p->tile_world; P.tiles_x = tiles_x_of(p);
+    P.ntiles_local = local_tiles_of(p, p->tile_rank);
+    P.stack_depth = s->meta.max_bvh_depth + 1u;
+    P.shade_threshold = p->shade_threshold ? (p->shade_threshold > 64u ? 64u : p->shade_threshold) : 40u; // tuned on C2..C5 (r02 sweep: 16..48)
+    P.status = s->status;
+    P.queue = s->status + 1;
+    P.sky = (p->flags & RTMI_FLAG_SKY) ? 1u : 0u;
+    P.ext = ((p->flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p->flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u) |
+            ((p->flags & RTMI_FLAG_TEST_OVERFLOW) ? RTMI_EXT_TEST_OVERFLOW : 0u);
+    return P;
+}
+
+#ifndef RTMI_COOP_CAP
+#define RTMI_COOP_CAP 512u
+#endif
+#ifndef RTMI_BLK_CAP /* entries of the workgroup's shared stack: 40 000 B of LDS per workgroup, four workgroups per CU */
+#define RTMI_BLK_CAP 2432u
+#endif
+// Traversal plan of the BVH-walking kernels: P.use_alt, P.spill_cap, P.coop_cap and P.spill (grown when the kernel is
+// the cooperative one); `ext` = the extended instantiation of the cooperative kernel.
+static int plan_traversal(rtmi_scene *s, const rtmi_render_params *p, bool coop, DevParams &P, bool &ext) {
+    // LDS part of the traversal stack: 512 entries cover the deepest stack ever seen on the reference scenes
+    // (447); deeper stacks continue in global memory (64 * (depth + 2) entries per wavefront, the bound of the
+    // depth-first order), so the LDS footprint (7.7 KB per wavefront) does not depend on the tree depth
+    const bool use_alt = s->dev.gate != nullptr && s->has_alt && !(p->flags & RTMI_FLAG_REF_TREE);
+    P.use_alt = use_alt ? 1u : 0u;
+    const uint32_t deepest = (use_alt && s->meta.alt_max_depth > s->meta.max_bvh_depth) ? s->meta.alt_max_depth : s->meta.max_bvh_depth;
+    P.spill_cap = 64u * (deepest + 2u);
+    if (use_alt) { // a 4-wide visit leaves up to three pending entries per level
+        const uint32_t wide = 64u * (3u * s->meta.alt_max_depth + 2u);
+        if (wide > P.spill_cap) P.spill_cap = wide;
+    }
+    // the lean kernel (no gates, no spill code) serves scenes without BVH items; everything else takes the extended
+    // one with a 512-entry LDS part
+    // (lean = scenes WITHOUT any BVH: its instantiation also carries the LDS word ring of the RNG, which pays exactly
+    // there, see rtmi_rng.hpp)
+    ext = use_alt || s->meta.n_nodes != 0u;
+    P.coop_cap = ext ? RTMI_COOP_CAP : P.spill_cap;
+    if (coop)
+        if (int rc = grow(s, s->spill, s->spill_bytes, (size_t)s->slots * P.spill_cap * sizeof(uint2))) return rc;
+    P.spill = s->spill;
+    return RTMI_OK;
+}
+
+// Pass protocol of the status words (rtmi_types.hpp), which progress reporting reads: a call starts with its overflow
+// word, the unit counter and the finished-units / finished-samples words at zero (the sticky word stays) ...
+static int begin_passes(rtmi_scene *s, hipStream_t stream) {
+    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
+    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    s->units_total = 0;
+    return RTMI_OK;
+}
+// ... and every pass ends with rtmi_pass_end_kernel: the pass's units from [1] to [3], its samples onto [4]
+static int units_done(rtmi_scene *s, uint64_t *units) { // read through the copy stream while a launch runs
+    unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(w, s->status, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream));
+    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    *units = (uint64_t)w[3] + w[1]; // finished passes + units handed out in the running one
+    return RTMI_OK;
+}
+
+struct PassCounts { uint32_t blocks = 0, chunks = 0; };
+// Samples [s0, s0 + count) of P.ntiles_local tiles in passes of P.pass_stride (the plan of plan_and_reserve): sets the
+// pass fields of P, calls launch(blocks, first, last) for the mode's render and resolve of each pass and ends the pass.
+// A pass of n items runs on min(ceil(n / items_per_block), max_blocks) blocks.  `finish`: the last pass ends the call
+// (it adds the call's overflows to the sticky word that rtmi_scene_status reports).
+template <typename Launch>
+static int run_passes(rtmi_scene *s, DevParams &P, hipStream_t stream, uint32_t s0, uint32_t count, bool finish,
+                      uint64_t max_blocks, uint32_t items_per_block, PassCounts &counts, Launch &&launch) {
+    for (uint32_t k = 0; k < count; k += P.pass_stride) { // one pass unless the per-sample buffer is smaller than count samples
+        P.pass_s0 = s0 + k;
+        P.pass_cnt = count - k < P.pass_stride ? count - k : P.pass_stride;
+        P.nchunks = (P.pass_cnt + P.chunk_spp - 1) / P.chunk_spp;
+        const uint64_t nitems = (uint64_t)P.ntiles_local * P.nchunks;
+        if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
+        const uint64_t nblocks = (nitems + items_per_block - 1) / items_per_block;
+        const uint32_t blocks = (uint32_t)(nblocks < max_blocks ? nblocks : max_blocks);
+        counts.blocks += blocks; counts.chunks += P.nchunks;
+        s->units_total += nitems;
+        const bool last = k + P.pass_cnt >= count;
+        if (int rc = launch(blocks, k == 0, last)) return rc;
+        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt,
+                           finish && last ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return RTMI_OK;
+}
+
+// this call's overflow word of a scene whose kernels have finished
+static int check_overflow(rtmi_scene *s) {
+    unsigned int st = 0;
+    HIP_TRY(hipMemcpy(&st, s->status, sizeof(st), hipMemcpyDeviceToHost));
+    if (st != 0) {
+        HIP_TRY(hipMemset(s->status + 2, 0, sizeof(unsigned int))); // reported here: not again by rtmi_scene_status
+        return fail(RTMI_ERR_DEVICE, "cooperative traversal pool overflow (results invalid, texels poisoned): use RTMI_FLAG_SYNC");
+    }
+    return RTMI_OK;
+}
+static void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, float ms_render, float ms_all,
+                       PassCounts counts = {}) {
+    stats->render_ms = ms_render;
+    stats->kernel_ms = ms_all;
+    // samples actually traced: pixels inside the image that belong to local tiles
+    uint64_t pix = 0;
+    const uint32_t txn = tiles_x_of(p), nl = local_tiles_of(p, p->tile_rank);
+    for (uint32_t lt = 0; lt < nl; lt++) {
+        const uint32_t t = lt * p->tile_world + p->tile_rank;
+        const uint32_t ty = t / txn, tx = t % txn;
+        const uint32_t w = (tx * RTMI_TILE + RTMI_TILE <= p->nx) ? RTMI_TILE : p->nx - tx * RTMI_TILE;
+        const uint32_t h = (ty * RTMI_TILE + RTMI_TILE <= p->ny) ? RTMI_TILE : p->ny - ty * RTMI_TILE;
+        pix += (uint64_t)w * h;
+    }
+    stats->samples = pix * p->ns;
+    stats->tiles = nl; stats->chunks = counts.chunks; stats->blocks = counts.blocks; stats->kernel = s->last_kernel;
+}
+// the same from the scene's events: ev[0] start, ev[1] before the last resolve, ev[2] end (all completed)
+static int fill_stats_from_events(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, PassCounts counts = {}) {
+    float ms_r = 0.f, ms_all = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
+    fill_stats(s, p, stats, ms_r, ms_all, counts);
+    return RTMI_OK;
+}
+
+// Tiled -> row-major image of N components per pixel (whole-image calls): texel = tile * 64 + ly * 8 + lx, tiles
+// counted from the top-left; row 0 of the output = top row
+template <int N, typename T, typename U>
+static void untile_to(const rtmi_render_params *p, const T *tiled, U *out) {
+    const uint32_t txn = tiles_x_of(p);
+    for (uint32_t row = 0; row < p->ny; row++)
+        for (uint32_t px = 0; px < p->nx; px++) {
+            const size_t k = (size_t)((row / RTMI_TILE) * txn + px / RTMI_TILE) * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE;
+            const size_t o = (size_t)row * p->nx + px;
+            for (int c = 0; c < N; c++) out[o * N + c] = tiled[k * N + c];
+        }
+}
+// ... of a device buffer of `ntex` texels
+template <int N, typename T, typename U>
+static int download_untiled(const rtmi_render_params *p, const T *d_tiled, size_t ntex, U *out) {
+    std::vector<T> h(ntex * N);
+    HIP_TRY(hipMemcpy(h.data(), d_tiled, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+    untile_to<N>(p, h.data(), out);
+    return RTMI_OK;
+}
+
 // Plan of one render call: unit size, samples per pass; (re)allocates the per-sample buffer and the f64 sums.
 // slot_bytes: the size of one per-sample slot (rtmi_render_features stores 32-B FeatSlots).
 static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t ntiles_local, uint32_t &chunk_spp,
@@ -630,14 +894,15 @@ static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t
             void *taken = nullptr;
             size_t taken_bytes = 0;
             if (parked_take(s->device, need, &taken, &taken_bytes)) { // a destroyed handle's buffer: no hipMalloc
-                if (s->samples) parked_give(s->device, s->samples, s->samples_bytes); // (smaller than the one taken)
+                if (s->samples) { // (smaller than the one taken) another handle may take it next: no render of this one may still write it
+                    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
+                    parked_give(s->device, s->samples, s->samples_bytes);
+                }
                 s->samples = static_cast<Rad3 *>(taken);
                 s->samples_bytes = taken_bytes;
             } else {
-                if (s->samples) { HIP_TRY(hipFree(s->samples)); s->samples = nullptr; s->samples_bytes = 0; }
                 parked_drop(s->device); // too small to serve this call: its memory may be what the allocation needs
-                HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->samples), need));
-                s->samples_bytes = need;
+                if (int rc = grow(s, s->samples, s->samples_bytes, need)) return rc;
             }
         }
     }
@@ -659,27 +924,7 @@ static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t
     if (chunk_spp < 1u) chunk_spp = 1u;
     // one pass when everything fits (its last chunk may be shorter); otherwise whole chunks per pass
     pass_ns = max_pass >= p->ns ? p->ns : (uint32_t)(max_pass / chunk_spp) * chunk_spp;
-
-    const size_t need = (size_t)ntiles_local * 64 * 3 * sizeof(double); // f64 sums carried between passes
-    if (need > s->partial_bytes) {
-        if (s->partial) { HIP_TRY(hipFree(s->partial)); s->partial = nullptr; s->partial_bytes = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->partial), need));
-        s->partial_bytes = need;
-    }
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_render_prepare(rtmi_scene *s, const rtmi_render_params *p) {
-    if (!s) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_params(p);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    const uint32_t ntiles_local = local_tiles_of(p, p->tile_rank);
-    if (ntiles_local == 0) return RTMI_OK;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // the buffer may be reallocated: no render may still use it
-    uint32_t chunk_spp = 0, pass_ns = 0;
-    return plan_and_reserve(s, p, ntiles_local, chunk_spp, pass_ns);
+    return grow(s, s->partial, s->partial_bytes, (size_t)ntiles_local * 64 * 3 * sizeof(double)); // f64 sums carried between passes
 }
 
 // (Re)allocates what a render with these parameters needs BEFORE the caller starts its event clock: an allocation of tens
@@ -690,6 +935,15 @@ static int reserve_before_clock(rtmi_scene *s, const rtmi_render_params *p) {
     if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // the buffer may be reallocated: no render may still use it
     uint32_t chunk_spp = 0, pass_ns = 0;
     return plan_and_reserve(s, p, ntiles_local, chunk_spp, pass_ns);
+}
+
+extern "C" int rtmi_render_prepare(rtmi_scene *s, const rtmi_render_params *p) {
+    if (!s) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    return reserve_before_clock(s, p);
 }
 
 // the enqueue itself; the caller holds s->mu
@@ -703,16 +957,9 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     // device side of the thread model: this render starts after the previous one of this handle has finished (a no-op
     // when both were given the same stream)
     if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    struct BusyMark { // records the end of this call's work on every return path after the first enqueue
-        rtmi_scene *s; hipStream_t st;
-        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
-    } busy_mark{s, stream};
+    BusyMark busy_mark{s, stream};
 
-    DevParams P{};
-    P.nx = p->nx; P.ny = p->ny; P.ns = p->ns; P.max_depth = p->max_depth; P.t_min = p->t_min;
-    P.key0 = (uint32_t)p->seed; P.key1 = (uint32_t)(p->seed >> 32);
-    P.tile_rank = p->tile_rank; P.tile_world = p->tile_world; P.tiles_x = tiles_x_of(p);
-    P.ntiles_local = local_tiles_of(p, p->tile_rank);
+    DevParams P = dev_params(s, p);
     if (P.ntiles_local == 0) {
         if (stats) memset(stats, 0, sizeof(*stats));
         return RTMI_OK;
@@ -729,24 +976,11 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     P.chunk_spp = chunk_spp;
     P.pass_stride = pass_ns;
     P.samples = s->samples;
-
-    DevCamera C;
-    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
-    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
-    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
-    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
-    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
-    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
-    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    const DevCamera C = dev_camera(cam);
 
     if (stats) HIP_TRY(hipEventRecord(s->ev[0], stream));
-    // pruned traversal needs the BVH boxes to contain their moving spheres at every ray time (camera.rs:65)
-    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
-    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
-    const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sigf = (p->flags & RTMI_FLAG_PATH_SIG) != 0u;
+    const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sigf = (p->flags & RTMI_FLAG_PATH_SIG) != 0u;
     const dim3 block(64 * WAVES_PER_BLOCK);
-    P.stack_depth = s->meta.max_bvh_depth + 1u;
-    P.shade_threshold = p->shade_threshold ? (p->shade_threshold > 64u ? 64u : p->shade_threshold) : 40u; // tuned on C2..C5 (r02 sweep: 16..48)
     const size_t dyn_lds = (size_t)WAVES_PER_BLOCK * 2u * P.stack_depth * 64u * sizeof(uint32_t);
     const bool prof = (p->flags & RTMI_FLAG_PROFILE) != 0u, sync = (p->flags & RTMI_FLAG_SYNC) != 0u;
     if (prof) {
@@ -760,55 +994,20 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     const bool async = (p->flags & RTMI_FLAG_ASYNC) != 0u && !s->has_deferred;
     const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
     const bool coop = fast && !sync && !async && coop_ok;
-    P.status = s->status;
-    P.queue = s->status + 1;
-    P.sky = (p->flags & RTMI_FLAG_SKY) ? 1u : 0u;
-    P.ext = ((p->flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p->flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u) |
-            ((p->flags & RTMI_FLAG_TEST_OVERFLOW) ? RTMI_EXT_TEST_OVERFLOW : 0u);
-    // this call's overflow word, the unit counter and the finished-units word start at zero; the sticky word stays
-    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
-    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
-    s->units_total = 0;
-    // LDS part of the traversal stack: 512 entries cover the deepest stack ever seen on the reference scenes
-    // (447); deeper stacks continue in global memory (64 * (depth + 2) entries per wavefront, the bound of the
-    // depth-first order), so the LDS footprint (7.7 KB per wavefront) does not depend on the tree depth
-    const bool use_alt = s->dev.gate != nullptr && s->has_alt && !(p->flags & RTMI_FLAG_REF_TREE);
-    P.use_alt = use_alt ? 1u : 0u;
-    const uint32_t deepest = (use_alt && s->meta.alt_max_depth > s->meta.max_bvh_depth) ? s->meta.alt_max_depth : s->meta.max_bvh_depth;
-    P.spill_cap = 64u * (deepest + 2u);
-    if (use_alt) { // a 4-wide visit leaves up to three pending entries per level
-        const uint32_t wide = 64u * (3u * s->meta.alt_max_depth + 2u);
-        if (wide > P.spill_cap) P.spill_cap = wide;
+    if ((rc = begin_passes(s, stream))) return rc;
+    bool ext = false;
+    if ((rc = plan_traversal(s, p, coop, P, ext))) return rc;
+    if (p->flags & (1u << 11)) { // test knob: the extended kernel with a pool this small that it spills all the time
+        ext = true;
+        P.coop_cap = 256u;
     }
-    // the lean kernel (no gates, no spill code) serves scenes without BVH items; everything else takes the extended
-    // one with a 512-entry LDS part
-    // (lean = scenes WITHOUT any BVH: its instantiation also carries the LDS word ring of the RNG, which pays exactly
-    // there, see rtmi_rng.hpp)
-    const bool ext = use_alt || s->meta.n_nodes != 0u || (p->flags & (1u << 11));
-#ifndef RTMI_COOP_CAP
-#define RTMI_COOP_CAP 512u
-#endif
-#ifndef RTMI_BLK_CAP /* entries of the workgroup's shared stack: 40 000 B of LDS per workgroup, four workgroups per CU */
-#define RTMI_BLK_CAP 2432u
-#endif
-    P.coop_cap = ext ? RTMI_COOP_CAP : P.spill_cap;
-    if (p->flags & (1u << 11)) P.coop_cap = 256u; // test knob: a pool this small spills all the time
     // persistent grid: as many wavefronts as the kernel instantiation keeps resident (4 SIMDs x its waves per SIMD)
     const uint32_t wps_req = (p->flags >> 8) & 7u; // experiment knob: requested waves per SIMD (0 = default)
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u; // the rare compositions: own instantiations
     const uint32_t wps_run = (coop && !prof && !sigf && !inst && (wps_req == 3u || wps_req == 5u)) ? wps_req : (coop && prof ? 3u : 4u);
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * wps_run;
-    if (coop) {
-        const size_t spill_bytes = (size_t)s->slots * P.spill_cap * sizeof(uint2);
-        if (spill_bytes > s->spill_bytes) {
-            if (s->spill) { HIP_TRY(hipFree(s->spill)); s->spill = nullptr; s->spill_bytes = 0; }
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->spill), spill_bytes));
-            s->spill_bytes = spill_bytes;
-        }
-    }
-    P.spill = s->spill;
     // workgroup-cooperative traversal (rtmi_bvh_block.hpp): alternative trees only, no diagnostics build
-    const bool bcoop = coop && (p->flags & RTMI_FLAG_BLOCK_COOP) != 0u && use_alt && s->all_alt && !prof && !inst &&
+    const bool bcoop = coop && (p->flags & RTMI_FLAG_BLOCK_COOP) != 0u && P.use_alt && s->all_alt && !prof && !inst &&
                        wps_req == 0u;
     const size_t bcoop_lds = (size_t)RTMI_BLK_LDS_WORDS(RTMI_BLK_CAP) * sizeof(uint32_t);
     // (test knob bit 11: a stack so small that rounds are throttled all the time — room for 64 visits when it is full)
@@ -817,22 +1016,13 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS + (ext ? 0u : RTMI_RNG_RING_WORDS) +
                                                               ((inst && (s->needs_insd || ext || sigf)) ? RTMI_COOP_PARK_WORDS : 0u)) * sizeof(uint32_t);
     const uint32_t ntex = P.ntiles_local * 64u;
-    uint32_t blocks_total = 0, chunks_total = 0;
-    for (uint32_t s0 = 0; s0 < p->ns; s0 += pass_ns) { // one pass unless the sample buffer is smaller than ns samples
-    P.pass_s0 = s0;
-    P.pass_cnt = p->ns - s0 < pass_ns ? p->ns - s0 : pass_ns;
-    P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
-    const uint64_t nitems = (uint64_t)P.ntiles_local * P.nchunks;
-    if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
     // two-phase kernels: persistent wavefronts that take units from the queue; async kernel: one block per unit
     // (workgroup-cooperative kernel: resident workgroups of RTMI_BLK_WAVES wavefronts; every wavefront takes units)
-    const uint64_t blk_slots = run_slots / RTMI_BLK_WAVES;
-    const uint64_t nblocks = async ? (nitems + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK
-                             : bcoop ? (nitems < blk_slots ? nitems : blk_slots)
-                                     : (nitems < run_slots ? nitems : run_slots);
-    const dim3 grid((uint32_t)nblocks);
-    blocks_total += grid.x; chunks_total += P.nchunks;
-    s->units_total += nitems;
+    const uint64_t max_blocks = async ? ~0ull : bcoop ? run_slots / RTMI_BLK_WAVES : run_slots;
+    PassCounts counts;
+    rc = run_passes(s, P, stream, 0, p->ns, true, max_blocks, async ? WAVES_PER_BLOCK : 1u, counts,
+                    [&](uint32_t blocks, bool first, bool last) -> int {
+    const dim3 grid(blocks);
 #define RTMI_LAUNCH(KERN, F, S, PR, LDS) hipLaunchKernelGGL((KERN<F, S, PR>), grid, block, LDS, stream, s->dev, C, P)
 #define RTMI_LAUNCH_COOP(S, PR, W, E, I)                                                                                 \
     do {                                                                                                                 \
@@ -883,43 +1073,17 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
 #undef RTMI_LAUNCH
 #undef RTMI_LAUNCH_COOP
     HIP_TRY(hipGetLastError());
-    const bool last = s0 + P.pass_cnt >= p->ns;
     if (stats && last) HIP_TRY(hipEventRecord(s->ev[1], stream));
     hipLaunchKernelGGL(rtmi_resolve_kernel, dim3((ntex + 255) / 256), dim3(256), 0, stream, s->samples, s->partial,
-                       reinterpret_cast<rtmi_texel *>(d_texels), P, s0 == 0 ? 1 : 0, last ? 1 : 0,
+                       reinterpret_cast<rtmi_texel *>(d_texels), P, first ? 1 : 0, last ? 1 : 0,
                        (p->flags & RTMI_FLAG_PROGRESSIVE) ? 1 : 0);
-    hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, last ? 1 : 0);
-    HIP_TRY(hipGetLastError());
-    } // passes
-    if (stats) {
-        HIP_TRY(hipEventRecord(s->ev[2], stream));
-        HIP_TRY(hipEventSynchronize(s->ev[2]));
-        float ms_r = 0.f, ms_all = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
-        stats->render_ms = ms_r;
-        stats->kernel_ms = ms_all;
-        // samples actually traced: pixels inside the image that belong to local tiles
-        uint64_t pix = 0;
-        const uint32_t txn = tiles_x_of(p);
-        for (uint32_t lt = 0; lt < P.ntiles_local; lt++) {
-            const uint32_t t = lt * p->tile_world + p->tile_rank;
-            const uint32_t ty = t / txn, tx = t % txn;
-            const uint32_t w = (tx * RTMI_TILE + RTMI_TILE <= p->nx) ? RTMI_TILE : p->nx - tx * RTMI_TILE;
-            const uint32_t h = (ty * RTMI_TILE + RTMI_TILE <= p->ny) ? RTMI_TILE : p->ny - ty * RTMI_TILE;
-            pix += (uint64_t)w * h;
-        }
-        stats->samples = pix * p->ns;
-        stats->tiles = P.ntiles_local; stats->chunks = chunks_total; stats->blocks = blocks_total;
-        stats->kernel = s->last_kernel;
-        unsigned int st = 0; // this call's overflow word (the kernels have finished: ev[2] was waited for)
-        HIP_TRY(hipMemcpy(&st, s->status, sizeof(st), hipMemcpyDeviceToHost));
-        if (st != 0) {
-            HIP_TRY(hipMemset(s->status + 2, 0, sizeof(unsigned int))); // reported here: not again by rtmi_scene_status
-            return fail(RTMI_ERR_DEVICE, "cooperative traversal pool overflow (results invalid, texels poisoned): use RTMI_FLAG_SYNC");
-        }
-    }
     return RTMI_OK;
+    });
+    if (rc || !stats) return rc;
+    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    HIP_TRY(hipEventSynchronize(s->ev[2]));
+    if ((rc = fill_stats_from_events(s, p, stats, counts))) return rc;
+    return check_overflow(s); // (the kernels have finished: ev[2] was waited for)
 }
 
 extern "C" int rtmi_render_device(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, void *d_texels,
@@ -978,18 +1142,6 @@ extern "C" int rtmi_untile(const rtmi_render_params *p, const rtmi_texel *g, flo
 }
 
 // ---- blocking host API ---------------------------------------------------------------------------------
-static int ensure_streams(rtmi_scene *s) {
-    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->copy_stream) {
-        // The progress polls must not queue behind the render.  The runtime gives streams at most GPU_MAX_HW_QUEUES
-        // hardware queues per priority and shares the least used one beyond that (with 2, the two streams of a handle
-        // landed on one queue and every poll waited for the whole render); another priority is another pool.
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&s->copy_stream, hipStreamNonBlocking, greatest));
-    }
-    return RTMI_OK;
-}
 // Waits for `done_ev` of every listed scene; meanwhile (about every 50 ms) reads the devices' unit counters through
 // their copy streams and reports progress to the caller's callback — what src/progressbar.rs:6-58 only pretends to.
 static int wait_with_progress(rtmi_scene *const *scenes, hipEvent_t *done_ev, uint32_t n, const rtmi_render_params *p) {
@@ -1009,10 +1161,8 @@ static int wait_with_progress(rtmi_scene *const *scenes, hipEvent_t *done_ev, ui
                 const hipError_t q = hipEventQuery(done_ev[i]);
                 if (q == hipErrorNotReady) {
                     all_done = false;
-                    unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
-                    HIP_TRY(hipMemcpyAsync(w, s->status, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream));
-                    HIP_TRY(hipStreamSynchronize(s->copy_stream));
-                    const uint64_t d = (uint64_t)w[3] + w[1]; // finished passes + units handed out in the running one
+                    uint64_t d = 0;
+                    if (int rc = units_done(s, &d)) return rc;
                     done += d < s->units_total ? d : s->units_total;
                 } else if (q == hipSuccess) {
                     done += s->units_total;
@@ -1035,40 +1185,6 @@ static int wait_with_progress(rtmi_scene *const *scenes, hipEvent_t *done_ev, ui
     if (fn && !cancelled && fn(total, total, user) != 0) cancelled = true;
     return cancelled ? fail(RTMI_ERR_CANCELLED, "cancelled by the progress callback") : RTMI_OK;
 }
-// this call's overflow word of a scene whose kernels have finished
-static int check_overflow(rtmi_scene *s) {
-    unsigned int st = 0;
-    HIP_TRY(hipMemcpy(&st, s->status, sizeof(st), hipMemcpyDeviceToHost));
-    if (st != 0) {
-        HIP_TRY(hipMemset(s->status + 2, 0, sizeof(unsigned int)));
-        return fail(RTMI_ERR_DEVICE, "cooperative traversal pool overflow (results invalid, texels poisoned): use RTMI_FLAG_SYNC");
-    }
-    return RTMI_OK;
-}
-static void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, float ms_render, float ms_all) {
-    stats->render_ms = ms_render;
-    stats->kernel_ms = ms_all;
-    uint64_t pix = 0;
-    const uint32_t txn = tiles_x_of(p), nl = local_tiles_of(p, p->tile_rank);
-    for (uint32_t lt = 0; lt < nl; lt++) {
-        const uint32_t t = lt * p->tile_world + p->tile_rank;
-        const uint32_t ty = t / txn, tx = t % txn;
-        const uint32_t w = (tx * RTMI_TILE + RTMI_TILE <= p->nx) ? RTMI_TILE : p->nx - tx * RTMI_TILE;
-        const uint32_t h = (ty * RTMI_TILE + RTMI_TILE <= p->ny) ? RTMI_TILE : p->ny - ty * RTMI_TILE;
-        pix += (uint64_t)w * h;
-    }
-    stats->samples = pix * p->ns;
-    stats->tiles = nl; stats->chunks = 0; stats->blocks = 0; stats->kernel = s->last_kernel;
-}
-
-// pinned host mirror of a texel buffer (grow-only)
-static int ensure_host_texels(rtmi_texel **h, size_t *have, size_t want) {
-    if (want <= *have) return RTMI_OK;
-    if (*h) { HIP_TRY(hipHostFree(*h)); *h = nullptr; *have = 0; }
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(h), want * sizeof(rtmi_texel), hipHostMallocDefault));
-    *have = want;
-    return RTMI_OK;
-}
 
 extern "C" int rtmi_render(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
                            uint8_t *out_rgb8, uint64_t *out_path_sig, rtmi_stats *stats) {
@@ -1081,20 +1197,11 @@ extern "C" int rtmi_render(rtmi_scene *s, const rtmi_camera *cam, const rtmi_ren
     if ((rc = ensure_streams(s))) return rc;
     rtmi_render_params p = *p_in;
     const size_t ntex = (size_t)rtmi_local_tiles(&p) * 64;
-    if (ntex > s->texel_count) {
-        if (s->texels) { HIP_TRY(hipFree(s->texels)); s->texels = nullptr; s->texel_count = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->texels), ntex * sizeof(rtmi_texel)));
-        s->texel_count = ntex;
-    }
-    if ((rc = ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex))) return rc;
+    if ((rc = reserve_texels(s, ntex))) return rc;
     p.flags &= ~RTMI_FLAG_PATH_SIG;
     p.path_sig = 0;
     if (out_path_sig) {
-        if (ntex > s->sig_count) {
-            if (s->d_sig) { HIP_TRY(hipFree(s->d_sig)); s->d_sig = nullptr; s->sig_count = 0; }
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_sig), ntex * sizeof(unsigned long long)));
-            s->sig_count = ntex;
-        }
+        if ((rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))) return rc;
         p.flags |= RTMI_FLAG_PATH_SIG;
         p.path_sig = reinterpret_cast<uint64_t>(s->d_sig);
     }
@@ -1120,16 +1227,7 @@ extern "C" int rtmi_render(rtmi_scene *s, const rtmi_camera *cam, const rtmi_ren
         if (rc) return rc;
     }
     HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_path_sig) {
-        s->h_sig.resize(ntex);
-        HIP_TRY(hipMemcpy(s->h_sig.data(), s->d_sig, ntex * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        const uint32_t txn = tiles_x_of(&p);
-        for (uint32_t row = 0; row < p.ny; row++)
-            for (uint32_t px = 0; px < p.nx; px++) {
-                const uint32_t t = (row / RTMI_TILE) * txn + px / RTMI_TILE;
-                out_path_sig[(size_t)row * p.nx + px] = s->h_sig[(size_t)t * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE];
-            }
-    }
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
 }
 
@@ -1144,7 +1242,7 @@ extern "C" int rtmi_partial_image(rtmi_scene *s, const rtmi_render_params *p_in,
     *spp_done = 0;
     rtmi_render_params p = *p_in;
     const size_t ntex = (size_t)rtmi_local_tiles(&p) * 64;
-    if (!s->texels || ntex > s->texel_count || !s->copy_stream) return fail(RTMI_ERR_INVALID, "no rtmi_render call of this size is running on the handle");
+    if (!s->texels || ntex * sizeof(rtmi_texel) > s->texels_bytes || !s->copy_stream) return fail(RTMI_ERR_INVALID, "no rtmi_render call of this size is running on the handle");
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = ensure_host_texels(&s->h_partial, &s->h_partial_count, ntex))) return rc;
     unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0}, w2[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
@@ -1407,11 +1505,8 @@ extern "C" int rtmi_multi_render(rtmi_multi *m, const rtmi_camera *cam, const rt
         HIP_TRY(hipSetDevice(m->devices[i]));
         if ((rc = check_overflow(m->scenes[i]))) return rc;
         if (stats) {
-            float ms_r = 0.f, ms_all = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms_r, m->scenes[i]->ev[0], m->scenes[i]->ev[1]));
-            HIP_TRY(hipEventElapsedTime(&ms_all, m->scenes[i]->ev[0], m->scenes[i]->ev[2]));
             rtmi_stats one{};
-            fill_stats(m->scenes[i], &params[i], &one, ms_r, ms_all);
+            if ((rc = fill_stats_from_events(m->scenes[i], &params[i], &one))) return rc;
             stats->samples += one.samples; stats->tiles += one.tiles; stats->kernel = one.kernel;
             if (one.render_ms > stats->render_ms) stats->render_ms = one.render_ms;
             if (one.kernel_ms > stats->kernel_ms) stats->kernel_ms = one.kernel_ms;
@@ -1648,9 +1743,8 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     std::lock_guard<std::mutex> lock(s->mu);
     if (!s->has_f64) return fail(RTMI_ERR_INVALID, "rtmi_render_f64: no f64 planes attached (rtmi_scene_attach_f64)");
     HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_streams(s))) return rc;
+    if ((rc = begin_blocking(s))) return rc;
     hipStream_t st = s->stream;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
     const uint32_t ntiles = local_tiles_of(&p, 0);
     const bool sig = (p.flags & RTMI_FLAG_PATH_SIG) != 0u;
     // passes (rtmi_f64_plan.hpp): RTMI_SAMPLE_SLOT_BYTES_F64 per pixel sample, at most 45 GiB and 2^32 - 1 slots per pass;
@@ -1679,12 +1773,8 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     uint32_t *d_q = nullptr, *d_queue = nullptr;
     unsigned long long *d_sig = nullptr;
     const size_t texels = (size_t)ntiles * 64;
-    if ((size_t)pass_ns * per_sample > s->f64_samples_bytes) { // the handle's buffer grows to the largest pass planned
-        if (s->f64_samples) { HIP_TRY(hipFree(s->f64_samples)); s->f64_samples = nullptr; s->f64_samples_bytes = 0; }
-        if (hipMalloc(reinterpret_cast<void **>(&s->f64_samples), (size_t)pass_ns * per_sample) != hipSuccess)
-            return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc of the per-sample buffer failed");
-        s->f64_samples_bytes = (size_t)pass_ns * per_sample;
-    }
+    if (grow(s, s->f64_samples, s->f64_samples_bytes, (size_t)pass_ns * per_sample)) // grows to the largest pass planned
+        return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc of the per-sample buffer failed");
     d_samples = s->f64_samples;
     if ((rc = scratch.get(texels * 3 * sizeof(double), reinterpret_cast<void **>(&d_acc)))) return rc;
     if ((rc = scratch.get(texels * 3 * sizeof(double), reinterpret_cast<void **>(&d_lin)))) return rc;
@@ -1737,22 +1827,14 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     }
     HIP_TRY(hipEventRecord(s->ev[1], st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::vector<double> h_lin(texels * 3);
-    std::vector<uint32_t> h_q(texels);
-    std::vector<unsigned long long> h_sig(sig ? texels : 0);
-    HIP_TRY(hipMemcpy(h_lin.data(), d_lin, texels * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_q.data(), d_q, texels * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (sig) HIP_TRY(hipMemcpy(h_sig.data(), d_sig, texels * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    // un-tiling: texel = tile * 64 + ly * 8 + lx, tiles counted from the top-left; row 0 of the outputs = top row
-    const uint32_t txn = tiles_x_of(&p);
-    for (uint32_t row = 0; row < p.ny; row++)
-        for (uint32_t x = 0; x < p.nx; x++) {
-            const size_t t = (size_t)(row / RTMI_TILE) * txn + x / RTMI_TILE, k = t * 64 + (row % RTMI_TILE) * 8 + x % RTMI_TILE;
-            const size_t o = (size_t)row * p.nx + x;
-            if (out_linear) for (int ch = 0; ch < 3; ch++) out_linear[3 * o + ch] = h_lin[3 * k + ch];
-            if (out_rgb8) for (int ch = 0; ch < 3; ch++) out_rgb8[3 * o + ch] = (uint8_t)((h_q[k] >> (8 * ch)) & 255u);
-            if (out_path_sig) out_path_sig[o] = h_sig[k];
-        }
+    if (out_linear && (rc = download_untiled<3>(&p, d_lin, texels, out_linear))) return rc;
+    if (out_rgb8) {
+        std::vector<uint32_t> q((size_t)p.nx * p.ny);
+        if ((rc = download_untiled<1>(&p, d_q, texels, q.data()))) return rc;
+        for (size_t o = 0; o < q.size(); o++)
+            for (int ch = 0; ch < 3; ch++) out_rgb8[3 * o + ch] = (uint8_t)((q[o] >> (8 * ch)) & 255u);
+    }
+    if (out_path_sig && (rc = download_untiled<1>(&p, d_sig, texels, out_path_sig))) return rc;
     if (stats) {
         float ms_all = 0.0f;
         HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[1]));
@@ -1792,50 +1874,27 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
                                     uint32_t *out_spp, rtmi_stats *stats) {
     // every argument check comes before the first use of the handle (and of the device)
     if (!p_in || !a || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
+    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                                         RTMI_FLAG_UV_BOOK,
+                               "adaptive sampling accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and "
+                               "UV_BOOK only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                               "adaptive sampling renders the whole image: tile_world must be 1");
     if (rc) return rc;
     if (a->min_spp < 2u) return fail(RTMI_ERR_INVALID, "min_spp must be at least 2 (a variance needs two samples)");
     if (a->min_spp > p_in->ns) return fail(RTMI_ERR_INVALID, "min_spp must not exceed ns");
     if (a->step_spp == 0u) return fail(RTMI_ERR_INVALID, "step_spp must be positive");
     if (!std::isfinite(a->abs_tol) || !(a->abs_tol >= 0.0) || !std::isfinite(a->rel_tol) || !(a->rel_tol >= 0.0))
         return fail(RTMI_ERR_INVALID, "abs_tol and rel_tol must be finite and non-negative");
-    const uint32_t accepted = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                              RTMI_FLAG_UV_BOOK;
-    if (p_in->flags & ~accepted)
-        return fail(RTMI_ERR_UNSUPPORTED, "adaptive sampling accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and "
-                                          "UV_BOOK only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)");
-    if (p_in->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, "adaptive sampling renders the whole image: tile_world must be 1");
     if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_streams(s))) return rc;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // buffers below may be reallocated
+    if ((rc = begin_blocking(s))) return rc;
     const rtmi_render_params &p = *p_in;
     hipStream_t stream = s->stream;
-    struct BusyMark {
-        rtmi_scene *s; hipStream_t st;
-        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
-    } busy_mark{s, stream};
+    BusyMark busy_mark{s, stream};
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64;
-    if (ntex > s->texel_count) {
-        if (s->texels) { HIP_TRY(hipFree(s->texels)); s->texels = nullptr; s->texel_count = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->texels), ntex * sizeof(rtmi_texel)));
-        s->texel_count = ntex;
-    }
-    if ((rc = ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex))) return rc;
-    if (T > s->ad_tiles) {
-        if (s->ad_state) { HIP_TRY(hipFree(s->ad_state)); s->ad_state = nullptr; }
-        if (s->ad_lists) { HIP_TRY(hipFree(s->ad_lists)); s->ad_lists = nullptr; }
-        if (s->ad_stderr) { HIP_TRY(hipFree(s->ad_stderr)); s->ad_stderr = nullptr; }
-        if (s->ad_spp) { HIP_TRY(hipFree(s->ad_spp)); s->ad_spp = nullptr; }
-        s->ad_tiles = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_state), ntex * 9 * sizeof(double)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_lists), (2 * (size_t)T + 1) * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_stderr), ntex * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_spp), ntex * sizeof(uint32_t)));
-        s->ad_tiles = T;
-    }
+    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T))) return rc;
     if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
     { // the per-sample buffer for the largest step (every tile, max(min_spp, step_spp) samples) before the clock starts
         rtmi_render_params q = p;
@@ -1844,50 +1903,15 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
         if ((rc = plan_and_reserve(s, &q, T, chunk_spp, pass_ns))) return rc;
     }
 
-    DevParams P{};
-    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth; P.t_min = p.t_min;
-    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
-    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p);
-    DevCamera C;
-    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
-    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
-    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
-    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
-    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
-    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
-    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
+    DevParams P = dev_params(s, &p);
+    const DevCamera C = dev_camera(cam);
     // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
-    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
-    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
     const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
     const bool coop = fast && !sync && coop_ok && !inst;
-    P.stack_depth = s->meta.max_bvh_depth + 1u;
-    P.shade_threshold = p.shade_threshold ? (p.shade_threshold > 64u ? 64u : p.shade_threshold) : 40u;
-    P.status = s->status;
-    P.queue = s->status + 1;
-    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
-    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
-    const bool use_alt = s->dev.gate != nullptr && s->has_alt && !(p.flags & RTMI_FLAG_REF_TREE);
-    P.use_alt = use_alt ? 1u : 0u;
-    const uint32_t deepest = (use_alt && s->meta.alt_max_depth > s->meta.max_bvh_depth) ? s->meta.alt_max_depth : s->meta.max_bvh_depth;
-    P.spill_cap = 64u * (deepest + 2u);
-    if (use_alt) {
-        const uint32_t wide = 64u * (3u * s->meta.alt_max_depth + 2u);
-        if (wide > P.spill_cap) P.spill_cap = wide;
-    }
-    const bool ext = use_alt || s->meta.n_nodes != 0u;
-    P.coop_cap = ext ? RTMI_COOP_CAP : P.spill_cap;
-    if (coop) {
-        const size_t spill_bytes = (size_t)s->slots * P.spill_cap * sizeof(uint2);
-        if (spill_bytes > s->spill_bytes) {
-            if (s->spill) { HIP_TRY(hipFree(s->spill)); s->spill = nullptr; s->spill_bytes = 0; }
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->spill), spill_bytes));
-            s->spill_bytes = spill_bytes;
-        }
-    }
-    P.spill = s->spill;
+    bool ext = false;
+    if ((rc = plan_traversal(s, &p, coop, P, ext))) return rc;
     const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
     const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
                                                        (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
@@ -1900,18 +1924,15 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
     uint64_t settled = 0, shown = 0;           // tile-samples of finished steps, retired tiles counted at ns
     bool cancelled = false;
 
-    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
-    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
-    {
-        std::vector<uint32_t> all(T);
-        for (uint32_t t = 0; t < T; t++) all[t] = t;
-        HIP_TRY(hipMemcpyAsync(s->ad_lists, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream)); // (`all` is pageable and goes out of scope)
-    }
+    if ((rc = begin_passes(s, stream)) || (rc = list_all_tiles(s, T, stream))) return rc;
     HIP_TRY(hipEventRecord(s->ev[0], stream));
     uint32_t *lists[2] = {s->ad_lists, s->ad_lists + T}, *count = s->ad_lists + 2 * (size_t)T;
-    uint32_t n_active = T, n = 0, cur = 0, blocks_total = 0, chunks_total = 0;
-    uint64_t units_before = 0;
+    uint32_t n_active = T, n = 0, cur = 0;
+    PassCounts counts;
+    AdaptiveResolve A;
+    A.n_out = count;
+    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.abs_tol = a->abs_tol; A.rel_tol = a->rel_tol; A.ns = p.ns;
     while (n_active > 0 && n < p.ns && !cancelled) {
         const uint32_t c = n == 0 ? a->min_spp : (a->step_spp < p.ns - n ? a->step_spp : p.ns - n);
         rtmi_render_params q = p;
@@ -1920,26 +1941,18 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
         if ((rc = plan_and_reserve(s, &q, n_active, chunk_spp, pass_ns))) return rc;
         P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
         HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), stream));
-        uint64_t units_step = 0;
-        for (uint32_t s0 = 0; s0 < c; s0 += pass_ns) { // sub-passes when the per-sample buffer does not hold the step
-            P.pass_s0 = n + s0;
-            P.pass_cnt = c - s0 < pass_ns ? c - s0 : pass_ns;
-            P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
-            const uint64_t nitems = (uint64_t)n_active * P.nchunks;
-            if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
-            const uint32_t blocks = (uint32_t)(nitems < run_slots ? nitems : run_slots);
-            blocks_total += blocks; chunks_total += P.nchunks; units_step += nitems;
+        A.tiles_in = lists[cur]; A.tiles_out = lists[cur ^ 1];
+        const uint64_t units_before = s->units_total;
+        // samples [n, n + c) in sub-passes when the per-sample buffer does not hold the step
+        rc = run_passes(s, P, stream, n, c, false, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
             HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, stream, s->dev, C, P, lists[cur]));
-            AdaptiveResolve A;
-            A.tiles_in = lists[cur]; A.tiles_out = lists[cur ^ 1]; A.n_out = count;
-            A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
-            A.abs_tol = a->abs_tol; A.rel_tol = a->rel_tol; A.ns = p.ns;
-            A.first = (n == 0 && s0 == 0) ? 1 : 0;
-            A.decide = s0 + P.pass_cnt >= c ? 1 : 0;
+            A.first = (n == 0 && first) ? 1 : 0;
+            A.decide = last ? 1 : 0;
             HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
-            hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, 0);
-            HIP_TRY(hipGetLastError());
-        }
+            return RTMI_OK;
+        });
+        if (rc) return rc;
+        const uint64_t units_step = s->units_total - units_before;
         HIP_TRY(hipMemcpyAsync(s->h_ad_count, count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipEventRecord(s->ev[1], stream));
         // wait for the step; meanwhile report progress from the unit counters (as wait_with_progress does)
@@ -1948,10 +1961,8 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
             const hipError_t qe = hipEventQuery(s->ev[1]);
             if (qe == hipSuccess) break;
             if (qe != hipErrorNotReady) return fail(RTMI_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(qe));
-            unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(w, s->status, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream));
-            HIP_TRY(hipStreamSynchronize(s->copy_stream));
-            uint64_t u = (uint64_t)w[3] + w[1];
+            uint64_t u = 0;
+            if ((rc = units_done(s, &u))) return rc;
             u = u > units_before ? u - units_before : 0;
             if (u > units_step) u = units_step;
             uint64_t done = settled + (units_step ? step_ts * u / units_step : 0);
@@ -1962,7 +1973,6 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
             nanosleep(&ts, nullptr);
         }
         HIP_TRY(hipEventSynchronize(s->ev[1]));
-        units_before += units_step;
         const uint32_t next = *s->h_ad_count;
         settled += (uint64_t)(n_active - next) * (p.ns - n) + (uint64_t)next * c; // a retired tile counts at ns
         n += c;
@@ -1975,27 +1985,17 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
     if (cancelled) return fail(RTMI_ERR_CANCELLED, "cancelled by the progress callback");
     if ((rc = check_overflow(s))) return rc;
     HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    std::vector<float> h_se(ntex * 3);
-    std::vector<uint32_t> h_spp(ntex);
-    HIP_TRY(hipMemcpy(h_se.data(), s->ad_stderr, ntex * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(h_spp.data(), s->ad_spp, ntex * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const uint32_t txn = tiles_x_of(&p);
-    uint64_t traced = 0;
-    for (uint32_t row = 0; row < p.ny; row++)
-        for (uint32_t px = 0; px < p.nx; px++) {
-            const size_t t = (size_t)((row / RTMI_TILE) * txn + px / RTMI_TILE) * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE;
-            const size_t o = (size_t)row * p.nx + px;
-            traced += h_spp[t];
-            if (out_spp) out_spp[o] = h_spp[t];
-            if (out_stderr) { out_stderr[o * 3] = h_se[t * 3]; out_stderr[o * 3 + 1] = h_se[t * 3 + 1]; out_stderr[o * 3 + 2] = h_se[t * 3 + 2]; }
-        }
+    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
+    const size_t npix = (size_t)p.nx * p.ny;
+    std::vector<uint32_t> spp_local(out_spp ? 0 : npix);
+    uint32_t *spp = out_spp ? out_spp : spp_local.data();
+    if ((rc = download_untiled<1>(&p, s->ad_spp, ntex, spp))) return rc;
     if (stats) {
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
-        stats->render_ms = ms; // first launch to last resolve, the per-step read-backs included
-        stats->kernel_ms = ms;
-        stats->samples = traced;
-        stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
+        fill_stats(s, &p, stats, ms, ms, counts); // first launch to last resolve, the per-step read-backs included
+        stats->samples = 0;                       // the samples traced: every pixel's own count
+        for (size_t o = 0; o < npix; o++) stats->samples += spp[o];
     }
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
 }
@@ -2008,102 +2008,55 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
                                     rtmi_stats *stats) {
     // every argument check comes before the first use of the handle (and of the device)
     if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
+    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG,
+                               "features accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
+                               "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                               "features cover the whole image: tile_world must be 1");
     if (rc) return rc;
-    const uint32_t accepted = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                              RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG;
-    if (p_in->flags & ~accepted)
-        return fail(RTMI_ERR_UNSUPPORTED, "features accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
-                                          "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)");
-    if (p_in->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, "features cover the whole image: tile_world must be 1");
     if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_streams(s))) return rc;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // buffers below may be reallocated
+    if ((rc = begin_blocking(s))) return rc;
     const rtmi_render_params &p = *p_in;
     hipStream_t stream = s->stream;
-    struct BusyMark {
-        rtmi_scene *s; hipStream_t st;
-        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
-    } busy_mark{s, stream};
+    BusyMark busy_mark{s, stream};
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64, npix = (size_t)p.nx * p.ny;
-    if (ntex * 8 * sizeof(double) > s->ft_state_bytes) {
-        if (s->ft_state) { HIP_TRY(hipFree(s->ft_state)); s->ft_state = nullptr; s->ft_state_bytes = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ft_state), ntex * 8 * sizeof(double)));
-        s->ft_state_bytes = ntex * 8 * sizeof(double);
-    }
-    if (npix * 8 * sizeof(float) > s->ft_planes_bytes) {
-        if (s->ft_planes) { HIP_TRY(hipFree(s->ft_planes)); s->ft_planes = nullptr; s->ft_planes_bytes = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ft_planes), npix * 8 * sizeof(float)));
-        s->ft_planes_bytes = npix * 8 * sizeof(float);
-    }
-    if (out_path_sig && ntex > s->sig_count) {
-        if (s->d_sig) { HIP_TRY(hipFree(s->d_sig)); s->d_sig = nullptr; s->sig_count = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_sig), ntex * sizeof(unsigned long long)));
-        s->sig_count = ntex;
-    }
+    if ((rc = grow(s, s->ft_state, s->ft_state_bytes, ntex * 8 * sizeof(double))) ||
+        (rc = grow(s, s->ft_planes, s->ft_planes_bytes, npix * 8 * sizeof(float))) ||
+        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        return rc;
     // the per-sample buffer, planned for 32-B slots, before the clock starts
     uint32_t chunk_spp = 0, pass_ns = 0;
     if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns, RTMI_FEAT_SLOT_BYTES))) return rc;
 
-    DevParams P{};
-    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth; P.t_min = p.t_min;
-    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
-    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p); P.ntiles_local = T;
+    DevParams P = dev_params(s, &p);
     P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
-    DevCamera C;
-    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
-    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
-    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
-    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
-    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
-    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
-    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
-    // pruned traversal needs the BVH boxes to contain their moving spheres at every ray time (as render_device_locked)
-    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
-    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sig = out_path_sig != nullptr;
-    P.stack_depth = s->meta.max_bvh_depth + 1u;
-    P.shade_threshold = p.shade_threshold ? (p.shade_threshold > 64u ? 64u : p.shade_threshold) : 40u;
-    P.status = s->status;
-    P.queue = s->status + 1;
-    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
-    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    const DevCamera C = dev_camera(cam);
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
     P.path_sig = sig ? s->d_sig : nullptr;
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
     s->last_kernel = RTMI_KERNEL_PERLANE;
 
-    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
-    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    if ((rc = begin_passes(s, stream))) return rc;
     if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
-    s->units_total = 0;
     FeaturesResolve R;
     R.slots = reinterpret_cast<const FeatSlot *>(s->samples);
     R.state = s->ft_state;
     R.albedo = s->ft_planes; R.normal = s->ft_planes + npix * 3; R.depth = s->ft_planes + npix * 6;
     R.hits = reinterpret_cast<uint32_t *>(s->ft_planes + npix * 7);
-    uint32_t blocks_total = 0, chunks_total = 0;
+    PassCounts counts;
     HIP_TRY(hipEventRecord(s->ev[0], stream));
-    for (uint32_t s0 = 0; s0 < p.ns; s0 += pass_ns) { // one pass unless the per-sample buffer is smaller than ns samples
-        P.pass_s0 = s0;
-        P.pass_cnt = p.ns - s0 < pass_ns ? p.ns - s0 : pass_ns;
-        P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
-        const uint64_t nitems = (uint64_t)T * P.nchunks;
-        if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
-        const uint32_t blocks = (uint32_t)(nitems < run_slots ? nitems : run_slots);
-        blocks_total += blocks; chunks_total += P.nchunks;
-        s->units_total += nitems;
+    rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
         HIP_TRY(rtmi_features_launch_render(fast, sig, blocks, stream, s->dev, C, P));
-        const bool last = s0 + P.pass_cnt >= p.ns;
         if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
-        R.first = s0 == 0 ? 1 : 0;
+        R.first = first ? 1 : 0;
         R.last = last ? 1 : 0;
         HIP_TRY(rtmi_features_launch_resolve(stream, P, R));
-        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, last ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
+        return RTMI_OK;
+    });
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(s->ev[2], stream));
     rtmi_scene *one[1] = {s};
     if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
@@ -2112,25 +2065,8 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
     if (out_normal) HIP_TRY(hipMemcpy(out_normal, R.normal, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_depth) HIP_TRY(hipMemcpy(out_depth, R.depth, npix * sizeof(float), hipMemcpyDeviceToHost));
     if (out_hits) HIP_TRY(hipMemcpy(out_hits, R.hits, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_path_sig) {
-        s->h_sig.resize(ntex);
-        HIP_TRY(hipMemcpy(s->h_sig.data(), s->d_sig, ntex * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        const uint32_t txn = tiles_x_of(&p);
-        for (uint32_t row = 0; row < p.ny; row++)
-            for (uint32_t px = 0; px < p.nx; px++) {
-                const uint32_t t = (row / RTMI_TILE) * txn + px / RTMI_TILE;
-                out_path_sig[(size_t)row * p.nx + px] = s->h_sig[(size_t)t * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE];
-            }
-    }
-    if (stats) {
-        float ms_r = 0.f, ms_all = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
-        stats->render_ms = ms_r;
-        stats->kernel_ms = ms_all;
-        stats->samples = (uint64_t)npix * p.ns;
-        stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
-    }
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
+    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return RTMI_OK;
 }
 
@@ -2279,150 +2215,64 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
                                uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     // every argument check comes before the first use of the device
     if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
+    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG,
+                               "NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
+                               "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                               "NEE renders the whole image: tile_world must be 1");
     if (rc) return rc;
-    const uint32_t accepted = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                              RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG;
-    if (p_in->flags & ~accepted)
-        return fail(RTMI_ERR_UNSUPPORTED, "NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
-                                          "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)");
-    if (p_in->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, "NEE renders the whole image: tile_world must be 1");
     if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     if (!s->has_lights) return fail(RTMI_ERR_INVALID, "rtmi_render_nee: no light table attached (rtmi_scene_attach_lights)");
     HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_streams(s))) return rc;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // buffers below may be reallocated
+    if ((rc = begin_blocking(s))) return rc;
     const rtmi_render_params &p = *p_in;
     hipStream_t stream = s->stream;
-    struct BusyMark {
-        rtmi_scene *s; hipStream_t st;
-        ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
-    } busy_mark{s, stream};
+    BusyMark busy_mark{s, stream};
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64;
-    if (ntex > s->texel_count) {
-        if (s->texels) { HIP_TRY(hipFree(s->texels)); s->texels = nullptr; s->texel_count = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->texels), ntex * sizeof(rtmi_texel)));
-        s->texel_count = ntex;
-    }
-    if ((rc = ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex))) return rc;
-    if (T > s->ad_tiles) { // adaptive sampling's buffers (include/rtmi_adaptive.h), shared
-        if (s->ad_state) { HIP_TRY(hipFree(s->ad_state)); s->ad_state = nullptr; }
-        if (s->ad_lists) { HIP_TRY(hipFree(s->ad_lists)); s->ad_lists = nullptr; }
-        if (s->ad_stderr) { HIP_TRY(hipFree(s->ad_stderr)); s->ad_stderr = nullptr; }
-        if (s->ad_spp) { HIP_TRY(hipFree(s->ad_spp)); s->ad_spp = nullptr; }
-        s->ad_tiles = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_state), ntex * 9 * sizeof(double)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_lists), (2 * (size_t)T + 1) * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_stderr), ntex * 3 * sizeof(float)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->ad_spp), ntex * sizeof(uint32_t)));
-        s->ad_tiles = T;
-    }
-    if (out_path_sig && ntex > s->sig_count) {
-        if (s->d_sig) { HIP_TRY(hipFree(s->d_sig)); s->d_sig = nullptr; s->sig_count = 0; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_sig), ntex * sizeof(unsigned long long)));
-        s->sig_count = ntex;
-    }
+    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
+        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        return rc;
     uint32_t chunk_spp = 0, pass_ns = 0;
     if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
 
-    DevParams P{};
-    P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth; P.t_min = p.t_min;
-    P.key0 = (uint32_t)p.seed; P.key1 = (uint32_t)(p.seed >> 32);
-    P.tile_rank = 0; P.tile_world = 1; P.tiles_x = tiles_x_of(&p); P.ntiles_local = T;
+    DevParams P = dev_params(s, &p);
     P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
-    DevCamera C;
-    C.origin = F3{cam->origin[0], cam->origin[1], cam->origin[2]};
-    C.llc = F3{cam->lower_left_corner[0], cam->lower_left_corner[1], cam->lower_left_corner[2]};
-    C.horizontal = F3{cam->horizontal[0], cam->horizontal[1], cam->horizontal[2]};
-    C.vertical = F3{cam->vertical[0], cam->vertical[1], cam->vertical[2]};
-    C.u = F3{cam->u[0], cam->u[1], cam->u[2]};
-    C.v = F3{cam->v[0], cam->v[1], cam->v[2]};
-    C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
-    const float cam_t_lo = cam->time0 < cam->time1 ? cam->time0 : cam->time1, cam_t_hi = cam->time0 < cam->time1 ? cam->time1 : cam->time0;
-    const bool boxes_valid = cam_t_lo >= s->meta.bvh_time_lo && cam_t_hi <= s->meta.bvh_time_hi;
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid, sig = out_path_sig != nullptr;
-    P.stack_depth = s->meta.max_bvh_depth + 1u;
-    P.shade_threshold = p.shade_threshold ? (p.shade_threshold > 64u ? 64u : p.shade_threshold) : 40u;
-    P.status = s->status;
-    P.queue = s->status + 1;
-    P.sky = (p.flags & RTMI_FLAG_SKY) ? 1u : 0u;
-    P.ext = ((p.flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p.flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    const DevCamera C = dev_camera(cam);
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
     P.path_sig = sig ? s->d_sig : nullptr;
     DevLights L;
     L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n;
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
     s->last_kernel = RTMI_KERNEL_PERLANE;
 
-    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
-    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    if ((rc = begin_passes(s, stream))) return rc;
     if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
-    {
-        std::vector<uint32_t> all(T);
-        for (uint32_t t = 0; t < T; t++) all[t] = t;
-        HIP_TRY(hipMemcpyAsync(s->ad_lists, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream)); // (`all` is pageable and goes out of scope)
-    }
-    s->units_total = 0;
+    if ((rc = list_all_tiles(s, T, stream))) return rc;
     AdaptiveResolve A;
     A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
     A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
     A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
-    uint32_t blocks_total = 0, chunks_total = 0;
+    PassCounts counts;
     HIP_TRY(hipEventRecord(s->ev[0], stream));
-    for (uint32_t s0 = 0; s0 < p.ns; s0 += pass_ns) { // one pass unless the per-sample buffer is smaller than ns samples
-        P.pass_s0 = s0;
-        P.pass_cnt = p.ns - s0 < pass_ns ? p.ns - s0 : pass_ns;
-        P.nchunks = (P.pass_cnt + chunk_spp - 1) / chunk_spp;
-        const uint64_t nitems = (uint64_t)T * P.nchunks;
-        if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
-        const uint32_t blocks = (uint32_t)(nitems < run_slots ? nitems : run_slots);
-        blocks_total += blocks; chunks_total += P.nchunks;
-        s->units_total += nitems;
+    rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
         HIP_TRY(rtmi_nee_launch_render(fast, sig, blocks, stream, s->dev, C, P, L));
-        const bool last = s0 + P.pass_cnt >= p.ns;
         if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
-        A.first = s0 == 0 ? 1 : 0;
+        A.first = first ? 1 : 0;
         A.decide = last ? 1 : 0;
         if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
         HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
-        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt, last ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
+        return RTMI_OK;
+    });
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(s->ev[2], stream));
     rtmi_scene *one[1] = {s};
     if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
     if ((rc = check_overflow(s))) return rc;
     HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    const uint32_t txn = tiles_x_of(&p);
-    if (out_stderr) {
-        std::vector<float> h_se(ntex * 3);
-        HIP_TRY(hipMemcpy(h_se.data(), s->ad_stderr, ntex * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        for (uint32_t row = 0; row < p.ny; row++)
-            for (uint32_t px = 0; px < p.nx; px++) {
-                const size_t t = (size_t)((row / RTMI_TILE) * txn + px / RTMI_TILE) * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE;
-                const size_t o = (size_t)row * p.nx + px;
-                out_stderr[o * 3] = h_se[t * 3]; out_stderr[o * 3 + 1] = h_se[t * 3 + 1]; out_stderr[o * 3 + 2] = h_se[t * 3 + 2];
-            }
-    }
-    if (out_path_sig) {
-        s->h_sig.resize(ntex);
-        HIP_TRY(hipMemcpy(s->h_sig.data(), s->d_sig, ntex * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (uint32_t row = 0; row < p.ny; row++)
-            for (uint32_t px = 0; px < p.nx; px++) {
-                const uint32_t t = (row / RTMI_TILE) * txn + px / RTMI_TILE;
-                out_path_sig[(size_t)row * p.nx + px] = s->h_sig[(size_t)t * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE];
-            }
-    }
-    if (stats) {
-        float ms_r = 0.f, ms_all = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
-        stats->render_ms = ms_r;
-        stats->kernel_ms = ms_all;
-        stats->samples = (uint64_t)p.nx * p.ny * p.ns;
-        stats->tiles = T; stats->chunks = chunks_total; stats->blocks = blocks_total; stats->kernel = s->last_kernel;
-    }
+    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
+    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
 }

@@ -193,6 +193,43 @@ def test_render_device_on_two_streams_of_one_handle_serialises_on_the_device(hos
 
 
 @pytest.mark.gpu
+def test_a_per_sample_buffer_is_parked_only_after_the_renders_that_write_it(host):
+    """A render that outgrows its handle's per-sample buffer X takes a parked larger one and parks X for other handles of
+    the device.  An asynchronous render of the same handle may still be writing X then: X is parked only after it has
+    finished, so that the next handle to take X does not write it at the same time.  All images equal serial renders.
+    (The overlap depends on timing: without the wait this test fails only when it happens.)"""
+    import torch
+
+    from raytracing_rust_amd import dist as rdist
+    from raytracing_rust_amd.host import release_cached
+
+    nx, ny, ns_small, ns_large, ns_parked = 256, 160, 256, 384, 512
+    flags = abi.RTMI_FLAG_FAST_CULL
+    cam, world = scenes_extra.build(host, "lit_final_scene", nx, ny, seed=1)
+    release_cached()
+    a, b, d = (host.lower(world).upload(0) for _ in range(3))
+    a.render(cam, nx, ny, ns_small, seed=7, flags=flags)  # A's buffer X: ns_small samples
+    d.render(cam, nx, ny, ns_parked, seed=7, flags=flags)  # D's buffer: ns_parked samples ...
+    d.upload(0)  # ... parked: D's handle is destroyed (a fresh one replaces it)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.Stream(dev)
+    params = [rdist.rank_params(nx, ny, ns, 0, 1, seed=42, flags=flags) for ns in (ns_small, ns_large)]
+    bufs = [rdist.new_local_framebuffer(p, dev) for p in params]
+    torch.cuda.synchronize()
+    a.render_device(cam, params[0], bufs[0].data_ptr(), stream.cuda_stream)  # writes X
+    a.render_device(cam, params[1], bufs[1].data_ptr(), stream.cuda_stream)  # takes D's buffer, parks X
+    got_b = b.render(cam, nx, ny, ns_small, seed=43, flags=flags)  # takes X
+    torch.cuda.synchronize()
+    a.check_status()
+    for k, ns in enumerate((ns_small, ns_large)):
+        lin, rgb = rdist.untile(params[k], bufs[k].cpu().numpy()[None])
+        want = d.render(cam, nx, ny, ns, seed=42, flags=flags)
+        assert np.array_equal(lin, want["linear"]) and np.array_equal(rgb, want["rgb8"]), ns
+    want = d.render(cam, nx, ny, ns_small, seed=43, flags=flags)
+    assert np.array_equal(got_b["linear"], want["linear"]) and np.array_equal(got_b["rgb8"], want["rgb8"])
+
+
+@pytest.mark.gpu
 def test_c5_x5000_as_eight_ranks_through_the_multi_handle(host):
     """BASELINE config C5 — final_scene 1920x1080x5000 spp tile-split over 8 GPUs — at FULL size through the C ABI's
     persistent handle, all eight ranks on this one GPU (rtmi_multi_create with the same device eight times: eight
