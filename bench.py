@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X render path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1 without a launcher (WORLD_SIZE unset): this process starts the N rank processes itself, as fresh
 children, BEFORE anything touches the GPU, waits for them and relays rank 0's JSON line.  Under
@@ -12,11 +12,15 @@ A "step" is one pass of the hot path over one batch: one whole render of the hea
 BASELINE.json — final_scene 1920x1080 at 1000 spp per GPU — with the scene already resident in HBM.  With N
 GPUs the image is tile-partitioned (tile % N == rank), every rank renders its tiles and ONE gather brings the
 framebuffer to rank 0; the per-GPU work is held fixed (spp = 1000 * N), i.e. weak scaling.  `value` is
-whole-job Msamples/s = nx*ny*spp*K / max-over-ranks wall time.  At N > 1 the BASELINE config C5 itself
-(final_scene 1920x1080x5000spp, strong-scaled: 5000/N spp-equivalent per GPU) is timed as well and reported
-next to it as `baseline_config`.
+whole-job Msamples/s = nx*ny*spp*K / max-over-ranks wall time.
 
-Printed by rank 0 as ONE JSON line, with
+A plain run does what the headline needs and nothing more: set-up, `--warmup` untimed and `--steps` timed steps,
+`--dump-outputs` if given, and the JSON line, printed by rank 0.  `--full` (off by default) adds every other leg:
+  wall_clock_to_ppm_s, checks : one more step, now with D2H, un-tiling, the P3 text and the file write (`--ppm-out`)
+  cold_start   : N = 1, a fresh child process: start -> scene -> one-shot render -> PPM (`--no-cold-start` skips it)
+  abi_multi    : the persistent C-ABI handle (rtmi_multi_*) and the blocking single-device call (`--abi-multi`)
+  baseline_config : N > 1, the BASELINE config C5 itself (final_scene 1920x1080x5000spp, strong-scaled: 5000/N
+                 spp-equivalent per GPU), timed after the headline (`--no-baseline-config` skips it)
   roofline     : what bounds the dominant kernel.  The scene (< 2 MB) is L2 resident, so HBM is not the bound
                  (measured traffic is < 1 % of peak): the kernel is VALU bound.  `frac` = algorithmic flops
                  (operation counts of the CPU oracle x SURVEY §8(d) cost table) / launch time (HIP events on the
@@ -24,8 +28,9 @@ Printed by rank 0 as ONE JSON line, with
                  rocprofv3 PMC pass (issue_frac, lane_util, wait_frac) and the measured HBM fraction.  The §8(d)
                  algorithmic-bytes figure is kept as a labelled secondary field (it prices L2 hits as HBM fetches
                  and is not a bound).
-  cpu_baseline : the uninstrumented f64 CPU oracle (-O3 -march=native, compiled on this host; a port of the
-                 reference's single-threaded loop) timed on a bounded sample of the same workload (N = 1 only)
+  cpu_baseline : the uninstrumented f64 CPU oracle (-O3 -march=native, compiled on the host that runs the benchmark;
+                 a port of the reference's single-threaded loop) timed on a bounded sample of the same workload, on
+                 one core and on all usable cores (N = 1 only; `--no-cpu-baseline` skips it)
 """
 import argparse
 import json
@@ -439,6 +444,9 @@ def main():
     ap.add_argument("--no-baseline-config", action="store_true",
                     help="N > 1: skip the extra strong-scaled run of BASELINE config C5 (final_scene x5000spp)")
     ap.add_argument("--launch-timeout", type=int, default=3000, help="seconds the self-launcher waits for its ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg: wall-clock to PPM, cold one-shot, persistent "
+                         "handle, BASELINE config C5 at N > 1, roofline, CPU baselines (the options above narrow it)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write the image the last timed step computed (linear radiance and rgb8) "
                          "and the per-pixel path signatures of the same render (folded to 24 bits) as DIR/<name>.npy, "
@@ -465,7 +473,7 @@ def main():
 
     # ---- N = 1: the cold one-shot, in a fresh child BEFORE this process touches the GPU (and before the CPU legs load the host)
     cold = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_cold_start:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.gpus == 1 and not args.no_cold_start:
         cmd = [sys.executable, os.path.abspath(__file__), "--scene", args.scene, "--nx", str(args.nx), "--ny", str(args.ny),
                "--spp", str(args.spp), "--flags", str(args.flags), "--ppm-out", args.ppm_out]
         try:
@@ -480,7 +488,7 @@ def main():
     allcore = None
     host_cores, usable_cores = host_core_counts()
     nproc_all = args.cpu_allcore_procs if args.cpu_allcore_procs >= 0 else min(usable_cores, 256)
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and nproc_all > 1:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and nproc_all > 1:
         # before anything initialises the GPU: the workers are forked
         rows_all = 8  # many thin rows per worker: balanced
         n_all, dt_all, spp_all = cpu_sample_allcore(args.scene, args.nx, args.ny, rows_all, nproc_all, args.cpu_allcore_seconds)
@@ -588,24 +596,25 @@ def main():
     elapsed, kernel_ms_avg, render_ms_avg, params, step = (run["elapsed"], run["kernel_ms"], run["render_ms"],
                                                            run["params"], run["step"])
 
-    # ---- wall-clock to PPM: one more pass, now including D2H, un-tiling, P3 text and the file write
-    fence()
-    t1 = time.perf_counter()
-    gathered = step()
+    # ---- --full, wall-clock to PPM: one more pass, now including D2H, un-tiling, P3 text and the file write
     wall_ppm = None
     checks = {}
-    if rank == 0:
-        g = gathered.cpu().numpy()
-        lin, rgb = rdist.untile(params, g)
-        write_ppm(args.ppm_out, rgb, 3)  # the P3 text of create_image, streamed (rtmi_write_ppm)
-        wall_ppm = time.perf_counter() - t1
-        checks = {"ppm_bytes": os.path.getsize(args.ppm_out), "rgb_max": int(rgb.max()), "linear_mean": float(lin.mean())}
-    scene.check_status()
-    fence()
+    if args.full:
+        fence()
+        t1 = time.perf_counter()
+        gathered = step()
+        if rank == 0:
+            g = gathered.cpu().numpy()
+            lin, rgb = rdist.untile(params, g)
+            write_ppm(args.ppm_out, rgb, 3)  # the P3 text of create_image, streamed (rtmi_write_ppm)
+            wall_ppm = time.perf_counter() - t1
+            checks = {"ppm_bytes": os.path.getsize(args.ppm_out), "rgb_max": int(rgb.max()), "linear_mean": float(lin.mean())}
+        scene.check_status()
+        fence()
 
-    # ---- N > 1: BASELINE config C5 by name (strong scaling: the fixed 5000 spp image split over the ranks)
+    # ---- --full, N > 1: BASELINE config C5 by name (strong scaling: the fixed 5000 spp image split over the ranks)
     baseline_cfg = None
-    if world > 1 and not args.no_baseline_config and (args.scene, nx, ny) == BASELINE_C5[:3]:
+    if args.full and world > 1 and not args.no_baseline_config and (args.scene, nx, ny) == BASELINE_C5[:3]:
         b = timed_run(BASELINE_C5[3], 2, 1)
         baseline_cfg = {"workload": "%s %dx%dx%dspp" % BASELINE_C5, "n_gpus": world, "scaling": "strong",
                         "per_gpu": "%.0f spp-equivalent" % (BASELINE_C5[3] / world), "steps": 2, "warmup": 1,
@@ -626,10 +635,10 @@ def main():
         sig_render = scene.render(cam, nx, ny, ns, sig=True, seed=42, flags=args.flags, spp_chunks=args.chunks,
                                   shade_threshold=args.shade_threshold, sample_buffer_bytes=args.sample_buffer_mb << 20)
 
-    # ---- the persistent C-ABI handle (rtmi_multi_*): N = 1 in this process on [0]; N > 1 in a fresh child of rank 0
-    # over all N devices, after the other ranks have finished (their processes exit; nothing else runs on the GPUs)
+    # ---- --full, the persistent C-ABI handle (rtmi_multi_*): N = 1 in this process on [0]; N > 1 in a fresh child of
+    # rank 0 over all N devices, after the other ranks have finished (their processes exit; nothing else runs on the GPUs)
     abi_multi = None
-    if args.abi_multi != "off":
+    if args.full and args.abi_multi != "off":
         devs = list(range(world)) if args.abi_multi == "auto" else [int(x) for x in args.abi_multi.split(",")]
         try:
             host.free_all()  # release this rank's scene and its per-sample buffer first
@@ -678,11 +687,12 @@ def main():
         },
         "kernel_ms_avg": round(kernel_ms_avg, 3),
         "render_kernel_ms_avg": round(render_ms_avg, 3),
-        "wall_clock_to_ppm_s": None if wall_ppm is None else round(wall_ppm, 4),
         "scene_build_s": round(t_build, 3),
         "scene_upload_s": round(t_upload, 3),
-        "checks": checks,
     }
+    if args.full:
+        out["wall_clock_to_ppm_s"] = None if wall_ppm is None else round(wall_ppm, 4)
+        out["checks"] = checks
     if baseline_cfg is not None:
         out["baseline_config"] = baseline_cfg
     if abi_multi is not None:
@@ -691,76 +701,77 @@ def main():
         out["cold_start"] = cold
         out["cold_wall_clock_to_ppm_s"] = cold.get("cold_wall_clock_to_ppm_s")
 
-    # ---- roofline + cpu baseline (rank 0).  Operation counts come from a small pass of the instrumented oracle;
+    # ---- --full: roofline + cpu baseline (rank 0).  Operation counts come from a small pass of the instrumented oracle;
     # the TIMED baseline is the uninstrumented -march=native build (N = 1 only).
-    _, _, counters = cpu_sample(args.scene, nx, ny, 4, 4, native=False)
-    work = roofline.per_sample(counters, ns)
-    samples_per_launch = total_samples / world  # this rank's launch
-    launch_s = render_ms_avg * 1e-3
-    achieved_tflops = work["flops"] * samples_per_launch / launch_s / 1e12
-    algo_gbs = work["bytes"] * samples_per_launch / launch_s / 1e9
-    kernel = "rtmi_render_coop" if (args.flags & 1) and not (args.flags & 24) else (
-        "rtmi_render_async" if args.flags & 16 else "rtmi_render_kernel")
-    prof = load_profile_summary(args.profile_json, "%s %dx%dx%dspp" % (args.scene, nx, ny, args.spp)) if world == 1 else None
-    rl = {
-        "bound": "valu",
-        "achieved": round(achieved_tflops, 4),
-        "peak": roofline.FP32_VALU_PEAK_TFLOPS,
-        "unit": "TFLOP/s",
-        "frac": round(achieved_tflops / roofline.FP32_VALU_PEAK_TFLOPS, 6),
-        "traffic": None,
-        "kernel": kernel,
-        "flops_per_sample": round(work["flops"], 2),
-        "samples_per_launch": samples_per_launch,
-        "launch_ms": round(render_ms_avg, 3),
-        "why": "scene < 2 MB is L2 resident; measured HBM traffic is < 1 % of peak: VALU issue under divergence binds",
-    }
-    if prof:
-        # Everything below comes from the rocprofv3 PMC passes COMMITTED under profiles/ (one launch of the same kernel
-        # and workload on an MI355X), not from this run: kept apart under `profiled`; only `traffic` (the contract's
-        # field) is repeated at the top level.
-        lib_hash = abi.load_rtmi().rtmi_build_hash().decode()
-        pf = {"source": prof.get("source"), "hbm_bytes_per_launch": prof.get("hbm_bytes_per_launch"),
-              # the committed counters belong to the build whose hash they carry; another library -> stale
-              "profiled_build": prof.get("build_hash"), "running_build": lib_hash,
-              "stale": prof.get("build_hash") != lib_hash}
-        rl["traffic"] = prof.get("hbm_bytes_per_launch")
-        sq = roofline.sq_fractions(prof)
-        if sq:
-            pf.update(sq)  # issue_frac, lane_util, wait_frac, profiled_launch_ms
-            if pf.get("profiled_launch_ms") and pf.get("hbm_bytes_per_launch"):
-                pf["hbm_frac"] = round(pf["hbm_bytes_per_launch"] / (pf["profiled_launch_ms"] * 1e-3) / 1e9 / roofline.HBM_PEAK_GBS, 6)
-            if "issue_frac" in pf and "lane_util" in pf:
-                # the EXECUTED-work figure: share of the chip's VALU lane-cycles that did something
-                pf["lane_cycle_frac"] = round(pf["issue_frac"] * pf["lane_util"], 4)
-        rl["profiled"] = pf
-        rl["frac_note"] = ("frac prices the REFERENCE algorithm's operation count (both children, unshrunk interval) at "
-                           "this launch time; the executed share of VALU lane-cycles is profiled.lane_cycle_frac")
-    rl["algorithmic_bytes"] = {
-        "bytes_per_sample": round(work["bytes"], 2), "gb_per_s": round(algo_gbs, 3),
-        "over_hbm_peak": round(algo_gbs / roofline.HBM_PEAK_GBS, 4),
-        "note": "SURVEY §8(d) cost table: prices every node/primitive test as an HBM fetch although the scene is L2 "
-                "resident; secondary figure, not a bound (may exceed 1)",
-    }
-    out["roofline"] = rl
-    if world == 1 and not args.no_cpu_baseline:
-        n_cpu, dt_cpu, _ = cpu_sample(args.scene, nx, ny, args.cpu_spp, args.cpu_rows, native=True)
-        cpu_ms = n_cpu / dt_cpu / 1e6
-        out["cpu_baseline"] = {
-            "value": round(cpu_ms, 5),
-            "unit": "Msamples/s",
-            "cores": 1,
-            "kind": "port",
-            "sample": "%d evenly spaced rows x %d px x %d spp of %s %dx%d (%.1f s; f64 oracle, recursive color, no "
-                      "operation counters, gcc -O3 -march=native on this host)"
-                      % (args.cpu_rows, nx, args.cpu_spp, args.scene, nx, ny, dt_cpu),
-            "gpu_over_cpu": round(value / cpu_ms, 1),
-            "host_cores": host_cores,
-            "usable_cores": usable_cores,
-            "all_cores": allcore,
+    if args.full:
+        _, _, counters = cpu_sample(args.scene, nx, ny, 4, 4, native=False)
+        work = roofline.per_sample(counters, ns)
+        samples_per_launch = total_samples / world  # this rank's launch
+        launch_s = render_ms_avg * 1e-3
+        achieved_tflops = work["flops"] * samples_per_launch / launch_s / 1e12
+        algo_gbs = work["bytes"] * samples_per_launch / launch_s / 1e9
+        kernel = "rtmi_render_coop" if (args.flags & 1) and not (args.flags & 24) else (
+            "rtmi_render_async" if args.flags & 16 else "rtmi_render_kernel")
+        prof = load_profile_summary(args.profile_json, "%s %dx%dx%dspp" % (args.scene, nx, ny, args.spp)) if world == 1 else None
+        rl = {
+            "bound": "valu",
+            "achieved": round(achieved_tflops, 4),
+            "peak": roofline.FP32_VALU_PEAK_TFLOPS,
+            "unit": "TFLOP/s",
+            "frac": round(achieved_tflops / roofline.FP32_VALU_PEAK_TFLOPS, 6),
+            "traffic": None,
+            "kernel": kernel,
+            "flops_per_sample": round(work["flops"], 2),
+            "samples_per_launch": samples_per_launch,
+            "launch_ms": round(render_ms_avg, 3),
+            "why": "scene < 2 MB is L2 resident; measured HBM traffic is < 1 % of peak: VALU issue under divergence binds",
         }
-    else:
-        out["cpu_baseline"] = None
+        if prof:
+            # Everything below comes from the rocprofv3 PMC passes COMMITTED under profiles/ (one launch of the same kernel
+            # and workload on an MI355X), not from this run: kept apart under `profiled`; only `traffic` (the contract's
+            # field) is repeated at the top level.
+            lib_hash = abi.load_rtmi().rtmi_build_hash().decode()
+            pf = {"source": prof.get("source"), "hbm_bytes_per_launch": prof.get("hbm_bytes_per_launch"),
+                  # the committed counters belong to the build whose hash they carry; another library -> stale
+                  "profiled_build": prof.get("build_hash"), "running_build": lib_hash,
+                  "stale": prof.get("build_hash") != lib_hash}
+            rl["traffic"] = prof.get("hbm_bytes_per_launch")
+            sq = roofline.sq_fractions(prof)
+            if sq:
+                pf.update(sq)  # issue_frac, lane_util, wait_frac, profiled_launch_ms
+                if pf.get("profiled_launch_ms") and pf.get("hbm_bytes_per_launch"):
+                    pf["hbm_frac"] = round(pf["hbm_bytes_per_launch"] / (pf["profiled_launch_ms"] * 1e-3) / 1e9 / roofline.HBM_PEAK_GBS, 6)
+                if "issue_frac" in pf and "lane_util" in pf:
+                    # the EXECUTED-work figure: share of the chip's VALU lane-cycles that did something
+                    pf["lane_cycle_frac"] = round(pf["issue_frac"] * pf["lane_util"], 4)
+            rl["profiled"] = pf
+            rl["frac_note"] = ("frac prices the REFERENCE algorithm's operation count (both children, unshrunk interval) at "
+                               "this launch time; the executed share of VALU lane-cycles is profiled.lane_cycle_frac")
+        rl["algorithmic_bytes"] = {
+            "bytes_per_sample": round(work["bytes"], 2), "gb_per_s": round(algo_gbs, 3),
+            "over_hbm_peak": round(algo_gbs / roofline.HBM_PEAK_GBS, 4),
+            "note": "SURVEY §8(d) cost table: prices every node/primitive test as an HBM fetch although the scene is L2 "
+                    "resident; secondary figure, not a bound (may exceed 1)",
+        }
+        out["roofline"] = rl
+        if world == 1 and not args.no_cpu_baseline:
+            n_cpu, dt_cpu, _ = cpu_sample(args.scene, nx, ny, args.cpu_spp, args.cpu_rows, native=True)
+            cpu_ms = n_cpu / dt_cpu / 1e6
+            out["cpu_baseline"] = {
+                "value": round(cpu_ms, 5),
+                "unit": "Msamples/s",
+                "cores": 1,
+                "kind": "port",
+                "sample": "%d evenly spaced rows x %d px x %d spp of %s %dx%d (%.1f s; f64 oracle, recursive color, no "
+                          "operation counters, gcc -O3 -march=native on this host)"
+                          % (args.cpu_rows, nx, args.cpu_spp, args.scene, nx, ny, dt_cpu),
+                "gpu_over_cpu": round(value / cpu_ms, 1),
+                "host_cores": host_cores,
+                "usable_cores": usable_cores,
+                "all_cores": allcore,
+            }
+        else:
+            out["cpu_baseline"] = None
     if args.dump_outputs:
         # linear and rgb8: the image of the last timed step; path_sig: from the signature render, whose image must be
         # the same

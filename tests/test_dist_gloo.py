@@ -119,7 +119,8 @@ def test_two_ranks_render_and_gather_on_the_gpu(tmp_path):
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     ppm = str(tmp_path / "n2.ppm")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1",
+    # --full: the PPM file is written by the wall-clock-to-PPM pass, which a plain run leaves out
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "1",
                         "--warmup", "1", "--no-cpu-baseline", "--no-baseline-config", "--scene", "cornell_box", "--nx", "200",
                         "--ny", "120", "--spp", "8", "--ppm-out", ppm], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -2,7 +2,7 @@
 # tools/baseline_table.sh — run on the GPU box: one bench line per BASELINE.json config (GPU x1 + bounded CPU sample)
 export TMPDIR=/tmp
 OUT=gpurun_out/baseline; mkdir -p $OUT
-run() { name=$1; shift; timeout -k 10 500 python3 bench.py --steps 2 --warmup 1 "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"; }
+run() { name=$1; shift; timeout -k 10 500 python3 bench.py --full --steps 2 --warmup 1 "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"; }
 run C1_two_spheres    --scene two_spheres    --nx 400  --ny 225  --spp 100  --cpu-rows 15 --cpu-spp 100
 run C2_random_spheres --scene random_spheres --nx 1200 --ny 800  --spp 500  --cpu-rows 16 --cpu-spp 64
 run C3_cornell_box    --scene cornell_box    --nx 800  --ny 800  --spp 1000 --cpu-rows 16 --cpu-spp 256

@@ -11,7 +11,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 echo "== bench $TAG $*" ; date
-timeout -k 10 400 python3 bench.py --no-cpu-baseline --abi-multi off --no-cold-start --no-collective-at-1 "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --abi-multi off --no-cold-start --no-collective-at-1 "$@" > $OUT/bench.json 2> $OUT/bench.err
 tail -c 1500 $OUT/bench.json
 echo "== rocprofv3 stats" ; date
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py "$@" --no-cpu-baseline --abi-multi off --no-cold-start --no-collective-at-1 > $OUT/stats_bench.json 2> $OUT/stats.err || echo "rocprof stats failed"
