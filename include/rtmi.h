@@ -471,7 +471,7 @@ int rtmi_write_ppm(const char *path, uint32_t nx, uint32_t ny, const uint8_t *rg
 /* Test hooks: evaluate pieces of the arithmetic contract ON THE DEVICE so that parity
  * tests can compare them bit-for-bit with a host evaluation of rtmi_math.h / Philox.
  * op: 0 rtmi_sinf(x), 1 rtmi_logf(x), 2 rtmi_atan2f(x,y), 3 rtmi_asinf(x), 4 x/y,
- * 5 sqrt(x), 6 rtmi_u01(bits of x).  ctr: n*4 words, key: n*2 words, out: n*4 words. */
+ * 5 sqrt(x), 6 rtmi_u01(bits of x), 7 rtmi_cosf(x).  ctr: n*4 words, key: n*2 words, out: n*4 words. */
 int rtmi_probe_math(int op, const float *x, const float *y, float *out, uint32_t n);
 int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out, uint32_t n);
 /* Instance transforms as the render kernels apply them (src/traslate.rs:18-24, src/rotate.rs:85-113): for each of

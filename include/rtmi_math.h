@@ -1,11 +1,12 @@
 /* rtmi_math.h — the fp32 transcendental contract of the rtmi device path.
  *
  * The reference computes in f64 and calls Rust std `sin`, `ln`, `atan2`, `asin`
- * (src/texture.rs:41,68; src/medium.rs:40; src/sphere.rs:10-11).  The MI355X path
+ * (src/texture.rs:41,68; src/medium.rs:40; src/sphere.rs:10-11); next-event estimation
+ * adds `cos` and `sin` of the cone sampler (include/rtmi_nee.h).  The MI355X path
  * computes in fp32.  A hit/miss decision that flips on a 1-ulp difference changes a
  * pixel by O(emission/spp), so "GPU == fixed-seed CPU result within 1e-4" is only
  * reachable when both sides evaluate these four functions to the SAME bits.  ocml's
- * sinf/logf and glibc's do not agree bit-for-bit, therefore the contract defines them
+ * sinf/cosf/logf and glibc's do not agree bit-for-bit, therefore the contract defines them
  * here, built only from operations that are correctly rounded on both x86-64 and
  * gfx950 (+ - * / sqrt fma rint, integer ops) — given `-ffp-contract=off` and no
  * fast-math on either side.  The polynomials are the classic single-precision
@@ -62,6 +63,26 @@ RTMI_HD float rtmi_sinf(float x) {
     r = __builtin_fmaf(-k, -0x1.777a5cp-25f, r);
     r = __builtin_fmaf(-k, -0x1.ee59dap-50f, r);
     int q = (int)k;
+    float z = r * r;
+    float ps = __builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
+    float s = __builtin_fmaf(ps * z, r, r);
+    float pc = __builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z,
+                              4.166664568298827e-2f);
+    float c = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
+    float v = (q & 1) ? c : s;
+    return (q & 2) ? -v : v;
+}
+
+/* cos(x) = sin(x + pi/2): rtmi_sinf's reduction and kernels with the quadrant shifted by one (no addition of pi/2 to
+ * x, which would round).  Same domain: |x| > 2^20 or non-finite returns 0.  Its consumer is the cone sampling of
+ * next-event estimation (include/rtmi_nee.h), phi in [0, 2 pi). */
+RTMI_HD float rtmi_cosf(float x) {
+    if (!(__builtin_fabsf(x) <= 1048576.0f)) return 0.0f;
+    float k = __builtin_rintf(x * RTMI_2_OVER_PI_F);
+    float r = __builtin_fmaf(-k, 0x1.921fb6p+0f, x);
+    r = __builtin_fmaf(-k, -0x1.777a5cp-25f, r);
+    r = __builtin_fmaf(-k, -0x1.ee59dap-50f, r);
+    int q = (int)k + 1;
     float z = r * r;
     float ps = __builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
     float s = __builtin_fmaf(ps * z, r, r);

@@ -36,6 +36,24 @@
  * arithmetic: with an empty light table rtmi_render_nee is rtmi_render bit for bit.  V = 1 iff world.hit of the shadow
  * ray (origin x, direction q - x, the path's time, (t_min, +inf)) returns the sampled occurrence — the item scan of a
  * path ray, media included, whose free-flight draws then come from stream 3; Le = the emitter's texture at that hit.
+ *
+ * Arithmetic (fp32, each operation rounded once, no fused operations; the order below is the specification, restated
+ * by oracle/rt_oracle.c color_nee).  Table: area, p_sel and cdf are the f64 values above rounded once to float; the sum
+ * of area * w is accumulated in table order and p_sel = (area * w) / sum.  Light choice: us = u01(w0); the first index i
+ * with us < cdf[i], by binary search (lo = 0, hi = n - 1; mid = (lo + hi) >> 1; us < cdf[mid] ? hi = mid : lo = mid + 1).
+ * p_b = c > 0 ? (float)(2/pi) * ((c * c) * c) : 0 with c = (w . n) / sqrt((w . w) * (n . n)), dot products summed x, y, z
+ * left to right.  Rect (a, b the plane's axes, k its coordinate): q = (a0 + u1 (a1 - a0), b0 + u2 (b1 - b0)) at k,
+ * p_l = (p_sel * (d2 * sqrt(d2))) / (|w_k| * area), w = q - x, d2 = w . w.  Sphere (centre c, radius r): dc = c - x,
+ * dist2 = dc . dc, s = (r * r) / dist2, no sample unless s < 1; omc = s / (1 + sqrt(1 - s)); om = u1 * omc; ct = 1 - om;
+ * st = sqrt(max(0, om * (2 - om))); phi = (2 * pi_f) * u2; w = dc / sqrt(dist2) per component; basis
+ * sg = w.z >= 0 ? 1 : -1, a = -1 / (sg + w.z), b = (w.x * w.y) * a, t1 = (1 + ((sg * w.x) * w.x) * a, sg * b, -sg * w.x),
+ * t2 = (b, sg + (w.y * w.y) * a, -w.y); d = (w * ct + t1 * (st * rtmi_cosf(phi))) + t2 * (st * rtmi_sinf(phi));
+ * tq = sqrt(dist2) * ct - sqrt(max(0, r * r - dist2 * (st * st))), no sample unless tq > 0; direction d * tq;
+ * p_l = p_sel / ((2 * pi_f) * omc).  The sample is taken when p_b > 0, p_l > 0 and p_l < FLT_MAX.  Weights as ratios:
+ * light sample r = min / max of (p_b, p_l), r / (1 + r * r); BSDF hit p_b >= p_l ? 1 / (1 + r * r) with r = p_l / p_b,
+ * else r2 / (1 + r2) with r2 = r * r, r = p_b / p_l (weight 1 when p_l = 0).  Accumulation: a BSDF hit adds
+ * L = L + T * (Le * weight); a light sample adds L = L + ((T * albedo) * mis) * Le when its shadow ray hits, after the
+ * vertex's own emission and before the continuation's.
  */
 #ifndef RTMI_NEE_H
 #define RTMI_NEE_H

@@ -30,6 +30,15 @@ COUNTER_NAMES = [
 ]
 
 PLANE_YZ, PLANE_ZX, PLANE_XY = 0, 1, 2
+
+# next-event estimation (include/rtmi_nee.h): kinds as RTMI_PRIM_SPHERE / RTMI_PRIM_RECT; geo = rect {a0, b0, a1, b1, k},
+# sphere {cx, cy, cz, r, 0}
+KIND_SPHERE, KIND_RECT = 0, 2
+EMITTER_DTYPE = np.dtype([("handle", "<u8"), ("kind", "<i4"), ("plane", "<i4"), ("geo", "<f8", (5,)),
+                          ("under_xform", "<i4"), ("in_medium", "<i4"), ("count", "<i4"), ("eligible", "<i4"),
+                          ("weight", "<f8"), ("area", "<f8")])  # OrcEmitter, 88 B
+LIGHT_DTYPE = np.dtype([("handle", "<u8"), ("kind", "<i4"), ("plane", "<i4"), ("geo", "<f8", (5,)), ("area", "<f8"),
+                        ("p_sel", "<f8"), ("cdf", "<f8")])  # OrcLight, 80 B
 AXIS_X, AXIS_Y, AXIS_Z = 0, 1, 2
 
 
@@ -90,6 +99,9 @@ def _load(name):
         "orc_camera": (vp, [d] * 15),
         "orc_camera_state": (None, [vp, vp]),
         "orc_render": (i, [vp, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp]),
+        "orc_render_samples": (i, [vp, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
+        "orc_render_nee": (i, [vp, vp, vp, i, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
+        "orc_emitters": (i, [vp, vp, i]),
         "orc_ppm_text": (C.c_size_t, [i, i, vp, vp, C.c_size_t]),
         "orc_hit": (i, [vp, vp, vp, d, d, d, i, u64, vp, vp]),
         "orc_bounding_box": (i, [vp, d, d, vp]),
@@ -100,6 +112,7 @@ def _load(name):
         "orc_reset_counters": (None, []),
         "orc_get_counters": (i, [vp, i]),
         "orc_rtmi_sinf": (C.c_float, [C.c_float]),
+        "orc_rtmi_cosf": (C.c_float, [C.c_float]),
         "orc_rtmi_logf": (C.c_float, [C.c_float]),
         "orc_rtmi_atan2f": (C.c_float, [C.c_float, C.c_float]),
         "orc_rtmi_asinf": (C.c_float, [C.c_float]),
@@ -247,6 +260,45 @@ class Oracle:
         if rc != 0:
             raise RuntimeError("orc_render failed")
         return {"linear": lin, "rgb": rgb, "mean": mean, "sig": sig}
+
+    def _outputs(self, nx, ny, ns, samples):
+        out = {"linear": np.zeros((ny, nx, 3), np.float32), "rgb": np.zeros((ny, nx, 3), np.int32),
+               "mean": np.zeros((ny, nx, 3), np.float64), "sig": np.zeros((ny, nx), np.uint64)}
+        if samples:
+            out["samples"] = np.zeros((ny, nx, ns, 3), np.float32)
+        ptrs = [out[k].ctypes.data for k in ("linear", "rgb", "mean", "sig")] + [out["samples"].ctypes.data if samples else None]
+        return out, ptrs
+
+    def render_samples(self, cam, world, nx, ny, ns, seed=42, flags=0, max_depth=50, t_min=0.001, rows=None):
+        """render() plus samples f32 [ny,nx,ns,3]: every sample's radiance as the fp32 value the device stores."""
+        r0, r1 = (0, ny) if rows is None else rows
+        out, ptrs = self._outputs(nx, ny, ns, True)
+        if self.lib.orc_render_samples(cam.h, world.h, nx, ny, ns, int(seed), flags, max_depth, t_min, r0, r1, *ptrs) != 0:
+            raise RuntimeError("orc_render_samples failed")
+        return out
+
+    def emitters(self, world):
+        """Every DiffuseLight rect or sphere leaf of the graph (EMITTER_DTYPE), in the order the graph first reaches
+        them: handle, kind, plane, geo, under_xform, in_medium, count (occurrences), weight, area, and whether it is
+        eligible as a light under include/rtmi_nee.h's rules."""
+        n = self.lib.orc_emitters(world.h, None, 0)
+        out = np.zeros(max(n, 1), EMITTER_DTYPE)
+        assert self.lib.orc_emitters(world.h, out.ctypes.data, n) == n
+        return out[:n]
+
+    def render_nee(self, cam, world, lights, nx, ny, ns, seed=42, flags=0, max_depth=50, t_min=0.001, rows=None,
+                   samples=False):
+        """rtmi_render_nee's estimator (include/rtmi_nee.h) with the light table `lights` (LIGHT_DTYPE, the device's
+        order; area, p_sel and cdf as the device's floats).  Returns render()'s dict (the throughput form is implied),
+        plus samples f32 [ny,nx,ns,3] when samples=True."""
+        r0, r1 = (0, ny) if rows is None else rows
+        lt = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+        out, ptrs = self._outputs(nx, ny, ns, samples)
+        rc = self.lib.orc_render_nee(cam.h, world.h, lt.ctypes.data if len(lt) else None, len(lt), nx, ny, ns, int(seed),
+                                     flags, max_depth, t_min, r0, r1, *ptrs)
+        if rc != 0:
+            raise RuntimeError("orc_render_nee failed")
+        return out
 
     def ppm_text(self, rgb):
         ny, nx = rgb.shape[:2]

@@ -193,6 +193,14 @@ static inline REAL m_sin(REAL x) {
     return sin(x);
 #endif
 }
+static inline REAL m_cos(REAL x) {
+#ifdef ORC_F32
+    if (DEVICE_ARITH) return rtmi_cosf(x);
+    return cosf(x);
+#else
+    return cos(x);
+#endif
+}
 static inline REAL m_log(REAL x) {
 #ifdef ORC_F32
     if (DEVICE_ARITH) return rtmi_logf(x);
@@ -250,6 +258,9 @@ typedef struct {
     REAL t, u, v;
     V3 p, normal;
     const Material *mat;
+    const Hittable *prim; /* the leaf primitive (sphere, moving sphere, rect, cube side) that produced the hit; NULL for
+                           * a medium's scattering event.  Not in the reference: next-event estimation matches its
+                           * shadow ray's hit against the sampled light by it (include/rtmi_nee.h) */
 } HitRecord; /* hittable.rs:9-16 */
 
 typedef struct { D3 min, max; } AABBd; /* scene set-up stays f64 like the reference */
@@ -552,8 +563,8 @@ static void get_sphere_uv(V3 p, REAL *u, REAL *v) {
 }
 
 /* sphere.rs:37-77 and :122-164 (identical bodies, centre differs) */
-static int sphere_hit_at(V3 center, REAL radius, const Material *mat, const Ray *r, REAL t_min, REAL t_max,
-                         HitRecord *rec) {
+static int sphere_hit_at(const Hittable *h, V3 center, REAL radius, const Material *mat, const Ray *r, REAL t_min,
+                         REAL t_max, HitRecord *rec) {
     V3 oc = v_sub(r->o, center);
     REAL a = v_dot(r->d, r->d);
     REAL b = v_dot(oc, r->d);
@@ -584,6 +595,7 @@ static int sphere_hit_at(V3 center, REAL radius, const Material *mat, const Ray 
         rec->normal = v_div(v_sub(rec->p, center), radius); /* outward; never face-forwarded */
         get_sphere_uv(rec->normal, &rec->u, &rec->v);
         rec->mat = mat;
+        rec->prim = h;
         return 1;
     }
     return 0;
@@ -627,6 +639,7 @@ static int rect_hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, Hit
     rec->normal = v3(0, 0, 0);
     v_set(&rec->normal, ka, 1.0);
     rec->mat = h->mat;
+    rec->prim = h;
     return 1;
 }
 
@@ -649,10 +662,10 @@ static int hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, HitRecor
     switch (h->kind) {
     case H_SPHERE: /* sphere.rs:37-77 */
         COUNT(C_SPHERE);
-        return sphere_hit_at(h->c0, h->radius, h->mat, r, t_min, t_max, rec);
+        return sphere_hit_at(h, h->c0, h->radius, h->mat, r, t_min, t_max, rec);
     case H_MOVING_SPHERE: /* sphere.rs:122-164 */
         COUNT(C_MSPHERE);
-        return sphere_hit_at(moving_center(h, r->time), h->radius, h->mat, r, t_min, t_max, rec);
+        return sphere_hit_at(h, moving_center(h, r->time), h->radius, h->mat, r, t_min, t_max, rec);
     case H_RECT:
         return rect_hit(h, r, t_min, t_max, rec);
     case H_CUBE: /* cube.rs:84-86 */
@@ -714,6 +727,7 @@ static int hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, HitRecor
                         rec->p = ray_at(r, t);
                         rec->normal = v3(1.0, 0.0, 0.0);
                         rec->mat = &h->phase;
+                        rec->prim = NULL;
                         return 1;
                     }
                 }
@@ -859,6 +873,165 @@ static V3 color_throughput(const RenderCtx *cx, Ray ray) {
         Ray scattered;
         V3 att;
         if (!mat_scatter(rec.mat, &ray, &rec, &scattered, &att)) break;
+        T = v_mul(T, att);
+        ray = scattered;
+    }
+    return L;
+}
+
+/* ================================================================================== */
+/* next-event estimation — include/rtmi_nee.h (not in the reference)                   */
+/* ================================================================================== */
+/* One entry of the light table in the device's order (rtmi_scene_attach_lights): the leaf, its geometry and the three
+ * float values the device keeps.  OrcLight is the exported layout (80 B); NeeL the working copy in REAL. */
+typedef struct {
+    uint64_t handle; /* the leaf Hittable (orc_emitters) */
+    int32_t kind;    /* 0 sphere, 2 rect (RTMI_PRIM_*) */
+    int32_t plane;   /* rect: 0 YZ, 1 ZX, 2 XY; sphere: -1 */
+    double geo[5];   /* rect {a0, b0, a1, b1, k}; sphere {cx, cy, cz, r, 0} */
+    double area, p_sel, cdf;
+} OrcLight;
+typedef struct {
+    const Hittable *h;
+    int plane;
+    REAL g0, g1, g2, g3, k;
+    REAL area, p_sel, cdf;
+} NeeL;
+
+#ifdef ORC_F32
+#define NEE_2_OVER_PI 0.63661977236758134f /* RTMI_NEE_2_OVER_PI */
+#define NEE_INV_4PI 0.079577471545947668f  /* RTMI_NEE_INV_4PI */
+#define NEE_PI RTMI_PI_F
+#else
+#define NEE_2_OVER_PI 0.636619772367581343075535053490057448
+#define NEE_INV_4PI 0.0795774715459476678844418816862571810
+#define NEE_PI 3.14159265358979323846264338327950288
+#endif
+
+/* the Lambertian's density of direction w about the scatter normal n: (2/pi) max(0, cos)^3 */
+static REAL nee_pb_lambert(V3 w, V3 n) {
+    REAL c = v_dot(w, n) / R_SQRT(v_dot(w, w) * v_dot(n, n));
+    return c > (REAL)0 ? NEE_2_OVER_PI * (c * c * c) : (REAL)0;
+}
+/* power heuristic as ratios: light sample p_b p_l / (p_b^2 + p_l^2), BSDF hit p_b^2 / (p_b^2 + p_l^2) */
+static REAL nee_mis_light(REAL pb, REAL pl) {
+    REAL r = pb < pl ? pb / pl : pl / pb;
+    return r / ((REAL)1 + r * r);
+}
+static REAL nee_mis_bsdf(REAL pb, REAL pl) {
+    if (pb >= pl) { REAL r = pl / pb; return (REAL)1 / ((REAL)1 + r * r); }
+    REAL r = pb / pl, r2 = r * r;
+    return r2 / ((REAL)1 + r2);
+}
+static V3 nee_rect_point(const NeeL *L, REAL a, REAL b) {
+    return L->plane == 0 ? v3(L->k, a, b) : (L->plane == 1 ? v3(b, L->k, a) : v3(a, b, L->k));
+}
+static REAL nee_axis(const NeeL *L, V3 w) { return L->plane == 0 ? w.x : (L->plane == 1 ? w.y : w.z); }
+/* p_l = p_sel p_L of the light at q seen from x; a sphere's from inside is 0 */
+static REAL nee_pdf(const NeeL *L, V3 x, V3 q) {
+    if (L->plane >= 0) {
+        V3 w = v_sub(q, x);
+        REAL d2 = v_dot(w, w);
+        return L->p_sel * (d2 * R_SQRT(d2)) / (R_FABS(nee_axis(L, w)) * L->area);
+    }
+    V3 dc = v_sub(v3(L->g0, L->g1, L->g2), x);
+    REAL s = (L->g3 * L->g3) / v_dot(dc, dc);
+    if (!(s < (REAL)1)) return 0;
+    REAL omc = s / ((REAL)1 + R_SQRT((REAL)1 - s));
+    return L->p_sel / ((REAL)2 * NEE_PI * omc);
+}
+/* a point on L for the vertex x: *dir = q - x (unnormalised) and *pl; 0 = no sample */
+static int nee_sample(const NeeL *L, V3 x, REAL u1, REAL u2, V3 *dir, REAL *pl) {
+    if (L->plane >= 0) {
+        V3 q = nee_rect_point(L, L->g0 + u1 * (L->g2 - L->g0), L->g1 + u2 * (L->g3 - L->g1));
+        *dir = v_sub(q, x);
+        *pl = nee_pdf(L, x, q);
+        return 1;
+    }
+    V3 dc = v_sub(v3(L->g0, L->g1, L->g2), x);
+    REAL dist2 = v_dot(dc, dc), r2 = L->g3 * L->g3;
+    REAL s = r2 / dist2;
+    if (!(s < (REAL)1)) return 0;
+    REAL omc = s / ((REAL)1 + R_SQRT((REAL)1 - s));
+    REAL om = u1 * omc;
+    REAL ct = (REAL)1 - om, st = R_SQRT(R_FMAX((REAL)0, om * ((REAL)2 - om)));
+    REAL phi = (REAL)2 * NEE_PI * u2;
+    REAL dist = R_SQRT(dist2);
+    V3 w = v_div(dc, dist);
+    REAL sg = w.z >= (REAL)0 ? (REAL)1 : (REAL)-1;
+    REAL a = (REAL)-1 / (sg + w.z), b = w.x * w.y * a;
+    V3 t1 = v3((REAL)1 + sg * w.x * w.x * a, sg * b, -sg * w.x), t2 = v3(b, sg + w.y * w.y * a, -w.y);
+    V3 d = v_add(v_add(v_scale(w, ct), v_scale(t1, st * m_cos(phi))), v_scale(t2, st * m_sin(phi)));
+    REAL tq = dist * ct - R_SQRT(R_FMAX((REAL)0, r2 - dist2 * (st * st)));
+    *dir = v_scale(d, tq);
+    *pl = L->p_sel / ((REAL)2 * NEE_PI * omc);
+    return tq > (REAL)0;
+}
+
+/* the light-sample stream of the current pixel sample: counter (block, sample, pixel, 3) */
+static Stream g_light_rng;
+
+/* color_throughput with one light sample per scattering Lambertian / Isotropic vertex, combined with the BSDF sample by
+ * the power heuristic — operation for operation shade_hit<.., NEE = true> (rtmi_shade.hpp) and the NEE kernel
+ * (rtmi_kernel_perlane.inc).  With n == 0 it is color_throughput. */
+static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
+    V3 L = v3(0, 0, 0), T = v3(1, 1, 1);
+    REAL pb = 0; /* density of the scatter that produced `ray`; 0 = weight 1 at an emitter hit */
+    for (int depth = 0;; depth++) {
+        HitRecord rec;
+        COUNT(C_QUERIES);
+        if (!hit(cx->world, &ray, cx->t_min, R_MAX, &rec)) {
+            if (g_flags & ORC_SKY) L = v_add(L, v_mul(T, sky_color(ray.d)));
+            break;
+        }
+        sig_add(rec.t, depth);
+        V3 emitted = mat_emitted(rec.mat, rec.u, rec.v, rec.p);
+        if (rec.mat->kind == MAT_DIFFUSE_LIGHT && rec.prim && pb > (REAL)0) {
+            for (int li = 0; li < n; li++) {
+                if (lights[li].h != rec.prim) continue;
+                REAL pl = nee_pdf(&lights[li], ray.o, rec.p);
+                if (pl > (REAL)0) emitted = v_scale(emitted, nee_mis_bsdf(pb, pl));
+                break;
+            }
+        }
+        L = v_add(L, v_mul(T, emitted));
+        if (depth >= cx->max_depth) break;
+        Ray scattered;
+        V3 att;
+        const int kind = rec.mat->kind;
+        if (!mat_scatter(rec.mat, &ray, &rec, &scattered, &att)) break;
+        pb = 0;
+        if (n > 0 && (kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC)) {
+            const int iso = kind == MAT_ISOTROPIC;
+            V3 hn = rec.normal; /* the normal the scatter saw (mat_scatter's FACE_FORWARD rule) */
+            if ((g_flags & ORC_FACE_FORWARD) && v_dot(ray.d, hn) > (REAL)0) hn = v_neg(hn);
+            pb = iso ? NEE_INV_4PI : nee_pb_lambert(scattered.d, hn);
+            uint32_t w0 = stream_u32(&g_light_rng), w1 = stream_u32(&g_light_rng), w2 = stream_u32(&g_light_rng);
+            REAL us = (REAL)rtmi_u01(w0);
+            int lo = 0, hi = n - 1; /* the first light whose cdf exceeds us */
+            while (lo < hi) {
+                int mid = (lo + hi) >> 1;
+                if (us < lights[mid].cdf) hi = mid; else lo = mid + 1;
+            }
+            V3 dir;
+            REAL pl;
+            if (nee_sample(&lights[lo], rec.p, (REAL)rtmi_u01(w1), (REAL)rtmi_u01(w2), &dir, &pl)) {
+                REAL pbl = iso ? NEE_INV_4PI : nee_pb_lambert(dir, hn);
+                if (pbl > (REAL)0 && pl > (REAL)0 && pl < R_MAX) {
+                    V3 c = v_scale(v_mul(T, att), nee_mis_light(pbl, pl));
+                    /* the shadow ray: the path's item scan, its media drawing from the light-sample stream */
+                    Ray sray = ray_new(rec.p, dir, ray.time);
+                    Stream keep = g_rng;
+                    g_rng = g_light_rng;
+                    HitRecord srec;
+                    int got = hit(cx->world, &sray, cx->t_min, R_MAX, &srec);
+                    g_light_rng = g_rng;
+                    g_rng = keep;
+                    if (got && srec.prim == lights[lo].h && srec.mat->kind == MAT_DIFFUSE_LIGHT)
+                        L = v_add(L, v_mul(c, mat_emitted(srec.mat, srec.u, srec.v, srec.p)));
+                }
+            }
+        }
         T = v_mul(T, att);
         ray = scattered;
     }
@@ -1158,23 +1331,129 @@ static int32_t as_i32(double x) {
     return (int32_t)x;
 }
 
-/* Renders output rows [row_begin,row_end) (row 0 = top = reference j = ny-1) and, inside
- * them, samples [0,ns).  out_linear: ny*nx*3 float (mean radiance before gamma);
- * out_rgb: ny*nx*3 int32 (the ir/ig/ib the reference prints); out_mean: ny*nx*3 double.
- * out_sig: ny*nx uint64 path signatures.  Any output pointer may be NULL. */
-ORC_API int orc_render(void *cam_, void *world_, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
-                       double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
-                       double *out_mean, uint64_t *out_sig) {
+/* ---- next-event estimation: emitters and the NEE render (include/rtmi_nee.h) ------------------------------------- */
+/* Every DiffuseLight rect or sphere leaf the object graph reaches, with what decides whether it is a light under
+ * rtmi_nee.h's rules (read here from the header, not from rtmi_lights_from_desc).  OrcEmitter is the exported layout. */
+typedef struct {
+    uint64_t handle;
+    int32_t kind, plane; /* as OrcLight */
+    double geo[5];       /* as OrcLight, the working precision's values */
+    int32_t under_xform; /* under a Traslate or Rotate chain */
+    int32_t in_medium;   /* part of a ConstantMedium's boundary */
+    int32_t count;       /* how many times the graph reaches the leaf */
+    int32_t eligible;
+    double weight; /* the largest channel of a SOLID texture, else 1 */
+    double area;   /* rect (x1 - x0) (y1 - y0); sphere 4 pi r^2 */
+} OrcEmitter; /* 88 B */
+
+typedef struct { OrcEmitter *v; int n, cap; } EmitterList;
+
+static void emitters_walk(const Hittable *h, int under_xform, int in_medium, EmitterList *out) {
+    switch (h->kind) {
+    case H_SPHERE:
+    case H_RECT: {
+        if (h->mat->kind != MAT_DIFFUSE_LIGHT) return;
+        for (int i = 0; i < out->n; i++) {
+            if (out->v[i].handle == (uint64_t)(uintptr_t)h) {
+                out->v[i].count++;
+                out->v[i].under_xform |= under_xform;
+                out->v[i].in_medium |= in_medium;
+                return;
+            }
+        }
+        if (out->n == out->cap) {
+            out->cap = out->cap ? 2 * out->cap : 16;
+            out->v = (OrcEmitter *)realloc(out->v, sizeof(OrcEmitter) * (size_t)out->cap);
+            if (!out->v) { fprintf(stderr, "orc: out of memory\n"); abort(); }
+        }
+        OrcEmitter *e = &out->v[out->n++];
+        memset(e, 0, sizeof(*e));
+        e->handle = (uint64_t)(uintptr_t)h;
+        e->under_xform = under_xform;
+        e->in_medium = in_medium;
+        e->count = 1;
+        const Texture *t = h->mat->tex;
+        e->weight = (t && t->kind == TEX_SOLID) ? fmax(fmax((double)t->color.x, (double)t->color.y), (double)t->color.z) : 1.0;
+        if (h->kind == H_RECT) {
+            e->kind = 2; e->plane = h->plane;
+            e->geo[0] = h->x0; e->geo[1] = h->y0; e->geo[2] = h->x1; e->geo[3] = h->y1; e->geo[4] = h->k;
+            e->area = ((double)h->x1 - (double)h->x0) * ((double)h->y1 - (double)h->y0);
+        } else {
+            e->kind = 0; e->plane = -1;
+            e->geo[0] = h->c0.x; e->geo[1] = h->c0.y; e->geo[2] = h->c0.z; e->geo[3] = h->radius; e->geo[4] = 0.0;
+            e->area = 4.0 * 3.14159265358979323846264338327950288 * (double)h->radius * (double)h->radius;
+        }
+        return;
+    }
+    case H_MOVING_SPHERE:
+    case H_CUBE: /* a cube's faces are one primitive of its own kind: never a light */
+        return;
+    case H_LIST:
+        for (int i = 0; i < h->n; i++) emitters_walk(h->items[i], under_xform, in_medium, out);
+        return;
+    case H_FLIP:
+        emitters_walk(h->child, under_xform, in_medium, out);
+        return;
+    case H_TRANSLATE:
+    case H_ROTATE:
+        emitters_walk(h->child, 1, in_medium, out);
+        return;
+    case H_MEDIUM:
+        emitters_walk(h->child, under_xform, 1, out);
+        return;
+    case H_BVH: /* a node of one object holds it twice (bvh.rs:46-48): one occurrence */
+        emitters_walk(h->left, under_xform, in_medium, out);
+        if (h->right != h->left) emitters_walk(h->right, under_xform, in_medium, out);
+        return;
+    }
+}
+
+/* Writes at most `cap` emitters to `out` in the order the graph first reaches them; returns how many there are. */
+ORC_API int orc_emitters(void *world, OrcEmitter *out, int cap) {
+    EmitterList l = {NULL, 0, 0};
+    emitters_walk((const Hittable *)world, 0, 0, &l);
+    for (int i = 0; i < l.n; i++) {
+        OrcEmitter *e = &l.v[i];
+        int geometry = e->kind == 2 ? (e->geo[0] < e->geo[2] && e->geo[1] < e->geo[3])
+                                    : (e->geo[3] > 0.0 && isfinite(e->geo[0]) && isfinite(e->geo[1]) && isfinite(e->geo[2]));
+        e->eligible = geometry && !e->under_xform && !e->in_medium && e->count == 1 && e->weight > 0.0 &&
+                      e->area > 0.0 && isfinite(e->area * e->weight);
+        if (i < cap) out[i] = *e;
+    }
+    free(l.v);
+    return l.n;
+}
+
+/* The pixel loop of orc_render for the three estimators the tests compare: the plain path (lights == NULL), NEE
+ * (nee != 0, with the n_lights entries of lights_in; always the throughput form) and either with every sample's fp32 radiance in
+ * out_samples [ny, nx, ns, 3] (may be NULL). */
+static int render_rows(void *cam_, void *world_, int nee, const OrcLight *lights_in, int n_lights, int nx, int ny,
+                       int ns, uint64_t seed, int flags, int max_depth, double t_min, int row_begin, int row_end,
+                       float *out_linear, int32_t *out_rgb, double *out_mean, uint64_t *out_sig, float *out_samples) {
     const Camera *cam = (Camera *)cam_;
     RenderCtx cx;
     cx.world = (Hittable *)world_;
     cx.max_depth = max_depth;
     cx.t_min = (REAL)t_min;
     g_flags = flags;
+    NeeL *lights = NULL;
+    if (lights_in && n_lights > 0) {
+        lights = (NeeL *)malloc(sizeof(NeeL) * (size_t)n_lights);
+        if (!lights) return 1;
+        for (int i = 0; i < n_lights; i++) {
+            const OrcLight *s = &lights_in[i];
+            NeeL *d = &lights[i];
+            d->h = (const Hittable *)(uintptr_t)s->handle;
+            d->plane = s->kind == 2 ? s->plane : -1;
+            d->g0 = (REAL)s->geo[0]; d->g1 = (REAL)s->geo[1]; d->g2 = (REAL)s->geo[2]; d->g3 = (REAL)s->geo[3];
+            d->k = (REAL)s->geo[4];
+            d->area = (REAL)s->area; d->p_sel = (REAL)s->p_sel; d->cdf = (REAL)s->cdf;
+        }
+    }
     if (row_begin < 0) row_begin = 0;
     if (row_end > ny) row_end = ny;
     for (int row = row_begin; row < row_end; row++) {
-        int j = ny - 1 - row; /* for j in (0..ny).rev() */
+        int j = ny - 1 - row;
         for (int i = 0; i < nx; i++) {
             double col[3] = {0.0, 0.0, 0.0};
             g_sig = 0;
@@ -1184,7 +1463,17 @@ ORC_API int orc_render(void *cam_, void *world_, int nx, int ny, int ns, uint64_
                 REAL u = ((REAL)i + rng_uniform()) / (REAL)nx;
                 REAL v = ((REAL)j + rng_uniform()) / (REAL)ny;
                 Ray ray = camera_get_ray(cam, u, v);
-                V3 c = (flags & ORC_THROUGHPUT_FORM) ? color_throughput(&cx, ray) : color(&cx, &ray, 0);
+                V3 c;
+                if (nee) {
+                    stream_init(&g_light_rng, seed, (uint32_t)s, (uint32_t)(j * nx + i), 3);
+                    c = color_nee(&cx, ray, lights, lights ? n_lights : 0);
+                } else {
+                    c = (flags & ORC_THROUGHPUT_FORM) ? color_throughput(&cx, ray) : color(&cx, &ray, 0);
+                }
+                if (out_samples) {
+                    float *o = out_samples + (((size_t)row * nx + i) * ns + s) * 3;
+                    o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z;
+                }
                 col[0] += (double)c.x; col[1] += (double)c.y; col[2] += (double)c.z;
             }
             size_t o = ((size_t)row * nx + i) * 3;
@@ -1197,7 +1486,37 @@ ORC_API int orc_render(void *cam_, void *world_, int nx, int ny, int ns, uint64_
             }
         }
     }
+    free(lights);
     return 0;
+}
+
+/* Renders output rows [row_begin,row_end) (row 0 = top = reference j = ny-1) and, inside
+ * them, samples [0,ns).  out_linear: ny*nx*3 float (mean radiance before gamma);
+ * out_rgb: ny*nx*3 int32 (the ir/ig/ib the reference prints); out_mean: ny*nx*3 double.
+ * out_sig: ny*nx uint64 path signatures.  Any output pointer may be NULL. */
+ORC_API int orc_render(void *cam_, void *world_, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
+                       double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
+                       double *out_mean, uint64_t *out_sig) {
+    return render_rows(cam_, world_, 0, NULL, 0, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
+                       out_rgb, out_mean, out_sig, NULL);
+}
+/* orc_render plus every sample's fp32 radiance: out_samples [ny, nx, ns, 3] (rows outside [row_begin, row_end) are
+ * not written) */
+ORC_API int orc_render_samples(void *cam_, void *world_, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
+                               double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
+                               double *out_mean, uint64_t *out_sig, float *out_samples) {
+    return render_rows(cam_, world_, 0, NULL, 0, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
+                       out_rgb, out_mean, out_sig, out_samples);
+}
+/* rtmi_render_nee's estimator (include/rtmi_nee.h) with the light table `lights` (n_lights entries, the device's
+ * order; area, p_sel and cdf already the floats rtmi_scene_attach_lights makes of them).  Paths, signatures and
+ * outputs as orc_render in the throughput form; the light samples come from stream 3. */
+ORC_API int orc_render_nee(void *cam_, void *world_, const OrcLight *lights, int n_lights, int nx, int ny, int ns,
+                           uint64_t seed, int flags, int max_depth, double t_min, int row_begin, int row_end,
+                           float *out_linear, int32_t *out_rgb, double *out_mean, uint64_t *out_sig, float *out_samples) {
+    if (n_lights < 0 || (n_lights > 0 && !lights)) return 1;
+    return render_rows(cam_, world_, 1, lights, n_lights, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min,
+                       row_begin, row_end, out_linear, out_rgb, out_mean, out_sig, out_samples);
 }
 
 /* P3 text exactly as tests/test.rs:59,79 : "P3\n{nx} {ny}\n255\n" then "{ir} {ig} {ib}\n" per pixel.
@@ -1271,6 +1590,7 @@ ORC_API int orc_get_counters(uint64_t *out, int n) {
 }
 /* host evaluation of the fp32 transcendental contract, for tests */
 ORC_API float orc_rtmi_sinf(float x) { return rtmi_sinf(x); }
+ORC_API float orc_rtmi_cosf(float x) { return rtmi_cosf(x); }
 ORC_API float orc_rtmi_logf(float x) { return rtmi_logf(x); }
 ORC_API float orc_rtmi_atan2f(float y, float x) { return rtmi_atan2f(y, x); }
 ORC_API float orc_rtmi_asinf(float x) { return rtmi_asinf(x); }

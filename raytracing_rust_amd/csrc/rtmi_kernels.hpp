@@ -143,7 +143,7 @@ __global__ void rtmi_pass_end_kernel(unsigned int *status, unsigned int units, u
 }
 
 // ---- device evaluation of the arithmetic contract, for parity tests --------------------
-// op: 0 sin, 1 log, 2 atan2(x,y), 3 asin, 4 x/y, 5 sqrt, 6 u01(bits of x), 16.. instance transforms
+// op: 0 sin, 1 log, 2 atan2(x,y), 3 asin, 4 x/y, 5 sqrt, 6 u01(bits of x), 7 cos, 16.. instance transforms
 __global__ void rtmi_math_probe_kernel(int op, const float *x, const float *y, float *out, uint32_t n) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -156,6 +156,7 @@ __global__ void rtmi_math_probe_kernel(int op, const float *x, const float *y, f
     case 4: r = x[i] / y[i]; break;
     case 5: r = __builtin_sqrtf(x[i]); break;
     case 6: r = rtmi_u01(__float_as_uint(x[i])); break;
+    case 7: r = rtmi_cosf(x[i]); break;
     default: { // 16 + 4*(axis) + which: instance transforms (rotate.rs:85-113) by sin/cos of 33 degrees
         const int axis = ((op - 16) >> 2) % 3, which = (op - 16) & 3;
         rtmi_xform X;

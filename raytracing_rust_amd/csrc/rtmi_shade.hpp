@@ -431,7 +431,7 @@ __device__ __forceinline__ bool nee_sample(const NeeLight &L, F3 x, float u1, fl
     const float sg = w.z >= 0.0f ? 1.0f : -1.0f; // orthonormal basis around w (Duff et al. 2017)
     const float a = -1.0f / (sg + w.z), b = w.x * w.y * a;
     const F3 t1 = f3(1.0f + sg * w.x * w.x * a, sg * b, -sg * w.x), t2 = f3(b, sg + w.y * w.y * a, -w.y);
-    const F3 d = w * ct + t1 * (st * __builtin_cosf(phi)) + t2 * (st * __builtin_sinf(phi));
+    const F3 d = w * ct + t1 * (st * rtmi_cosf(phi)) + t2 * (st * rtmi_sinf(phi));
     const float tq = dist * ct - __builtin_sqrtf(fmaxf(0.0f, r2 - dist2 * (st * st))); // the near intersection
     dir = d * tq;
     pl = L.p_sel / (2.0f * RTMI_PI_F * omc);

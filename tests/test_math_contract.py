@@ -33,6 +33,25 @@ def test_accuracy_against_libm(orc32):
     assert np.isnan(orc32.lib.orc_rtmi_asinf(1.0000001))  # like Rust's asin outside [-1,1]
 
 
+def test_cos_accuracy_against_libm(orc32):
+    """rtmi_cosf (NEE's cone sampler, phi = 2 pi u in [0, 2 pi)) against f64 libm: on the sampler's range, every 24-bit
+    uniform's phi included at a stride, and on the sin test's wide range with the same phase allowance."""
+    rng = np.random.default_rng(2)
+    u = (np.arange(0, 1 << 24, 97, dtype=np.int64).astype(np.float32) * np.float32(2.0 ** -24))
+    phi = np.float32(2.0) * np.float32(np.pi) * u
+    x = np.concatenate([phi, rng.uniform(0.0, 2 * np.pi, 20000), [0.0, -0.0, 2 * np.pi, np.pi, np.pi / 2]]).astype(np.float32)
+    c = _host_eval(orc32, "orc_rtmi_cosf", x)
+    assert np.max(np.abs(c - np.cos(x.astype(np.float64)))) < 1e-6
+    assert orc32.lib.orc_rtmi_cosf(0.0) == 1.0
+    w = np.concatenate([rng.uniform(-60000, 60000, 20000), rng.uniform(-10, 10, 20000)]).astype(np.float32)
+    cw = _host_eval(orc32, "orc_rtmi_cosf", w)
+    assert np.max(np.abs(cw - np.cos(w.astype(np.float64))) / (1.0 + np.abs(w) * 6e-8 / 1e-7)) < 1e-6
+    # the two share one reduction: sin^2 + cos^2 = 1 to a few ulp
+    s = _host_eval(orc32, "orc_rtmi_sinf", x)
+    assert np.max(np.abs(s.astype(np.float64) ** 2 + c.astype(np.float64) ** 2 - 1.0)) < 4e-7
+    assert _host_eval(orc32, "orc_rtmi_cosf", np.array([np.inf, np.nan, 2.0 ** 21], np.float32)).tolist() == [0.0, 0.0, 0.0]
+
+
 def test_u01_is_24_bit_exact():
     from raytracing_rust_amd.philox import Stream
 
@@ -53,6 +72,8 @@ def test_device_equals_host_bit_for_bit(orc32):
         1: ((rng.integers(0, 1 << 24, n)).astype(np.float32) * np.float32(2.0 ** -24), None, "orc_rtmi_logf"),
         2: (rng.normal(size=n).astype(np.float32), rng.normal(size=n).astype(np.float32), "orc_rtmi_atan2f"),
         3: (rng.uniform(-1.0, 1.0, n).astype(np.float32), None, "orc_rtmi_asinf"),
+        7: (np.concatenate([np.float32(2.0 * np.pi) * rng.uniform(0.0, 1.0, n // 2), rng.uniform(-60000, 60000, n // 2)]
+                           ).astype(np.float32), None, "orc_rtmi_cosf"),
     }
     for op, (x, y, name) in cases.items():
         out = np.zeros(n, np.float32)
