@@ -539,3 +539,55 @@ extern "C" {
         stats: *mut RtmiStats,
     ) -> c_int;
 }
+
+// ---- include/rtmi_env.h: image-based environment lighting with importance-sampled NEE -------------------------------
+
+pub const RTMI_ENV_MAX_SIDE: u32 = 16384;
+pub const RTMI_ENV_MAX_TEXELS: u32 = 1 << 25;
+pub const RTMI_ENV_PROBE_LOOKUP: c_int = 0;
+pub const RTMI_ENV_PROBE_SAMPLE: c_int = 1;
+
+/// an environment map: height * width * 3 floats, row-major, row 0 the top row (+y), finite and >= 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiEnvMap {
+    pub width: u32,
+    pub height: u32,
+    pub rgb: *const f32,
+}
+
+/// the options of rtmi_render_env
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiEnvRender {
+    pub nee: u32,
+    pub env_select_p: f32,
+}
+
+extern "C" {
+    /// the map's sampling tables (host code, no device); any output may be null
+    pub fn rtmi_env_tables(
+        map: *const RtmiEnvMap,
+        row_cdf: *mut f32,
+        row_p: *mut f32,
+        col_cdf: *mut f32,
+        col_p: *mut f32,
+        total: *mut f64,
+    ) -> c_int;
+    /// uploads a map and its tables to the handle (null detaches)
+    pub fn rtmi_scene_attach_env(scene: *mut RtmiScene, map: *const RtmiEnvMap) -> c_int;
+    /// blocking whole-image render with the attached map: the image, its standard errors and rtmi_render's path signature
+    pub fn rtmi_render_env(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiEnvRender,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_path_sig: *mut u64,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the device's lookup or light sample on the attached map (RTMI_ENV_PROBE_*)
+    pub fn rtmi_probe_env(scene: *mut RtmiScene, op: c_int, input: *const f32, out: *mut f32, n: u32) -> c_int;
+}

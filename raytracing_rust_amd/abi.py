@@ -192,6 +192,23 @@ class Light(C.Structure):
 # the functions of include/rtmi_nee.h (next-event estimation), kept apart from those of include/rtmi.h
 RTMI_NEE_SYMBOLS = ["rtmi_lights_from_desc", "rtmi_scene_attach_lights", "rtmi_render_nee"]
 
+
+class EnvMap(C.Structure):
+    """rtmi_env_map (include/rtmi_env.h): an environment map, height * width * 3 floats, row 0 the top row (16 bytes)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.c_void_p)]
+
+
+class EnvRender(C.Structure):
+    """rtmi_env_render (include/rtmi_env.h): the options of rtmi_render_env (8 bytes)."""
+    _fields_ = [("nee", C.c_uint32), ("env_select_p", C.c_float)]
+
+
+RTMI_ENV_PROBE_LOOKUP, RTMI_ENV_PROBE_SAMPLE = 0, 1
+RTMI_ENV_MAX_SIDE, RTMI_ENV_MAX_TEXELS = 16384, 1 << 25
+
+# the functions of include/rtmi_env.h (environment lighting), kept apart from those of the other headers
+RTMI_ENV_SYMBOLS = ["rtmi_env_tables", "rtmi_scene_attach_env", "rtmi_render_env", "rtmi_probe_env"]
+
 _rtmi = None
 _host = None
 
@@ -271,6 +288,15 @@ def load_rtmi():
     lib.rtmi_scene_attach_lights.argtypes = [vp, C.POINTER(SceneDesc)]
     lib.rtmi_render_nee.restype = C.c_int
     lib.rtmi_render_nee.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_env_tables.restype = C.c_int
+    lib.rtmi_env_tables.argtypes = [C.POINTER(EnvMap), vp, vp, vp, vp, C.POINTER(C.c_double)]
+    lib.rtmi_scene_attach_env.restype = C.c_int
+    lib.rtmi_scene_attach_env.argtypes = [vp, C.POINTER(EnvMap)]
+    lib.rtmi_render_env.restype = C.c_int
+    lib.rtmi_render_env.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(EnvRender), vp, vp, vp, vp,
+                                    C.POINTER(Stats)]
+    lib.rtmi_probe_env.restype = C.c_int
+    lib.rtmi_probe_env.argtypes = [vp, C.c_int, vp, vp, C.c_uint32]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -333,6 +359,9 @@ def load_host():
         "rth_render_features": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_attach_lights": (i, [vp]),
         "rth_render_nee": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_attach_env": (i, [vp, u32, u32, vp]),
+        "rth_render_env": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(EnvRender), vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_probe_env": (i, [vp, i, vp, vp, u32]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

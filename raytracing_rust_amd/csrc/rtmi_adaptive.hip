@@ -31,8 +31,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void rtmi_adaptive_coop(De
 template <bool FAST>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_adaptive_kernel(DevScene sc, DevCamera cam, DevParams P,
                                                                             const uint32_t *tiles) {
-    constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false, NEE = false;
+    constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false, NEE = false, ENV = false;
     const DevLights nl{};
+    const DevEnv ev{};
 #include "rtmi_kernel_perlane.inc"
 }
 

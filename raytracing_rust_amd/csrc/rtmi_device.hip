@@ -44,6 +44,8 @@
 #include "rtmi_features_launch.hpp"
 #include "rtmi_nee.h"
 #include "rtmi_nee_launch.hpp"
+#include "rtmi_env.h"
+#include "rtmi_env_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -125,6 +127,12 @@ struct rtmi_scene {
     NeeLight *nee_lights = nullptr;    // [max(n, 1)]
     int32_t *nee_prim_light = nullptr; // [max(n_prims, 1)]
     uint32_t nee_n = 0;
+    // environment lighting (include/rtmi_env.h): the attached map and its tables, freed with the handle
+    bool has_env = false;
+    float4 *env_texels = nullptr; // [h][w] {r, g, b, 0}
+    float *env_tables = nullptr;  // row_cdf [h] | row_p [h] | col_cdf [h][w] | col_p [h][w]
+    uint32_t env_w = 0, env_h = 0;
+    bool env_sampled = false;     // the map's total weight is > 0
 };
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
@@ -563,6 +571,8 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->ft_planes) (void)hipFree(s->ft_planes);
     if (s->nee_lights) (void)hipFree(s->nee_lights);
     if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
+    if (s->env_texels) (void)hipFree(s->env_texels);
+    if (s->env_tables) (void)hipFree(s->env_tables);
     if (s->partial) (void)hipFree(s->partial);
     if (s->samples) { // parked for the next handle on this device (see g_parked); no kernel may still write it
         if (s->busy_recorded) (void)hipEventSynchronize(s->busy);
@@ -2275,4 +2285,144 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
     if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
+// ---- environment lighting (include/rtmi_env.h) ------------------------------------------------------------------------
+extern "C" int rtmi_scene_attach_env(rtmi_scene *s, const rtmi_env_map *map) {
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    EnvTables t;
+    std::vector<float4> tex;
+    if (map) { // every check of the map comes before the first use of the device
+        if (int rc = rtmi_env_build_tables(map, t)) return rc;
+        tex.resize((size_t)map->width * map->height);
+        for (size_t k = 0; k < tex.size(); k++) tex[k] = make_float4(map->rgb[3 * k], map->rgb[3 * k + 1], map->rgb[3 * k + 2], 0.0f);
+    }
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running render may read the old map
+    if (s->env_texels) { HIP_TRY(hipFree(s->env_texels)); s->env_texels = nullptr; }
+    if (s->env_tables) { HIP_TRY(hipFree(s->env_tables)); s->env_tables = nullptr; }
+    s->has_env = false;
+    if (!map) return RTMI_OK;
+    const size_t n = tex.size(), H = map->height;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->env_texels), n * sizeof(float4)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->env_tables), (2 * H + 2 * n) * sizeof(float)));
+    HIP_TRY(hipMemcpy(s->env_texels, tex.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->env_tables, t.row_cdf.data(), H * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->env_tables + H, t.row_p.data(), H * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->env_tables + 2 * H, t.col_cdf.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s->env_tables + 2 * H + n, t.col_p.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    s->env_w = map->width; s->env_h = map->height;
+    s->env_sampled = t.total > 0.0;
+    s->has_env = true;
+    return RTMI_OK;
+}
+
+static DevEnv dev_env(const rtmi_scene *s, float p_env) {
+    const size_t H = s->env_h, n = (size_t)s->env_w * s->env_h;
+    DevEnv E;
+    E.texels = s->env_texels;
+    E.row_cdf = s->env_tables; E.row_p = s->env_tables + H; E.col_cdf = s->env_tables + 2 * H; E.col_p = s->env_tables + 2 * H + n;
+    E.w = s->env_w; E.h = s->env_h;
+    E.p_env = p_env;
+    return E;
+}
+
+// The per-lane environment kernel (rtmi_env.hip) in passes of the render's plan; adaptive sampling's resolve over the list
+// of all tiles, as rtmi_render_nee.
+extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, const rtmi_env_render *opts,
+                               float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
+    // every argument check comes before the first use of the device
+    if (!p_in || !cam || !opts) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (p_in->flags & RTMI_FLAG_SKY) return fail(RTMI_ERR_INVALID, "rtmi_render_env: RTMI_FLAG_SKY is refused, the map replaces the sky");
+    rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK |
+                                     RTMI_FLAG_PATH_SIG,
+                           "environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD, UV_BOOK and PATH_SIG "
+                           "only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                           "environment renders render the whole image: tile_world must be 1");
+    if (rc) return rc;
+    if (opts->nee > 1u) return fail(RTMI_ERR_INVALID, "rtmi_render_env: nee must be 0 or 1");
+    if (!(opts->env_select_p > 0.0f && opts->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, "rtmi_render_env: env_select_p must be in (0, 1]");
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_env) return fail(RTMI_ERR_INVALID, "rtmi_render_env: no environment map attached (rtmi_scene_attach_env)");
+    const bool nee = opts->nee != 0u;
+    if (nee && !s->has_lights)
+        return fail(RTMI_ERR_INVALID, "rtmi_render_env: nee = 1 needs the light table (rtmi_scene_attach_lights)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = begin_blocking(s))) return rc;
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    BusyMark busy_mark{s, stream};
+    const uint32_t T = local_tiles_of(&p, 0);
+    const size_t ntex = (size_t)T * 64;
+    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
+        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        return rc;
+    uint32_t chunk_spp = 0, pass_ns = 0;
+    if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
+
+    DevParams P = dev_params(s, &p);
+    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+    const DevCamera C = dev_camera(cam);
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
+    P.path_sig = sig ? s->d_sig : nullptr;
+    DevLights L{};
+    if (nee) { L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n; }
+    // p_env: the map's share of the light samples (rtmi_env.h)
+    const DevEnv E = dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? opts->env_select_p : 1.0f));
+    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
+    s->last_kernel = RTMI_KERNEL_PERLANE;
+
+    if ((rc = begin_passes(s, stream))) return rc;
+    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
+    if ((rc = list_all_tiles(s, T, stream))) return rc;
+    AdaptiveResolve A;
+    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
+    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
+    PassCounts counts;
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
+        HIP_TRY(rtmi_env_launch_render(fast, sig, nee, blocks, stream, s->dev, C, P, L, E));
+        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
+        A.first = first ? 1 : 0;
+        A.decide = last ? 1 : 0;
+        if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
+        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
+        return RTMI_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    rtmi_scene *one[1] = {s};
+    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
+    if ((rc = check_overflow(s))) return rc;
+    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
+    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
+    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
+extern "C" int rtmi_probe_env(rtmi_scene *s, int op, const float *in, float *out, uint32_t n) {
+    if (!s || (n > 0u && (!in || !out))) return fail(RTMI_ERR_INVALID, "NULL argument");
+    if (op != RTMI_ENV_PROBE_LOOKUP && op != RTMI_ENV_PROBE_SAMPLE) return fail(RTMI_ERR_INVALID, "rtmi_probe_env: unknown op");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_env) return fail(RTMI_ERR_INVALID, "rtmi_probe_env: no environment map attached (rtmi_scene_attach_env)");
+    if (n == 0u) return RTMI_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = begin_blocking(s)) return rc;
+    const size_t nin = (size_t)n * (op == RTMI_ENV_PROBE_LOOKUP ? 3u : 2u), nout = (size_t)n * 4u;
+    float *din = nullptr, *dout = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&din), nin * sizeof(float)));
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dout), nout * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(rtmi_env_launch_probe(op, dev_env(s, s->env_sampled ? 1.0f : 0.0f), din, dout, n, s->stream));
+    HIP_TRY(hipMemcpyAsync(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    (void)hipFree(din); (void)hipFree(dout);
+    return RTMI_OK;
 }

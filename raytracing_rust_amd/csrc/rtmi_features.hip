@@ -20,8 +20,9 @@
 
 template <bool FAST, bool SIG>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_features_kernel(DevScene sc, DevCamera cam, DevParams P) {
-    constexpr bool PROF = false, TILE_LIST = false, FEATURES = true, NEE = false;
+    constexpr bool PROF = false, TILE_LIST = false, FEATURES = true, NEE = false, ENV = false;
     const DevLights nl{};
+    const DevEnv ev{};
     const uint32_t *const tiles = nullptr;
 #include "rtmi_kernel_perlane.inc"
 }

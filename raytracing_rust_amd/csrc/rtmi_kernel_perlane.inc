@@ -5,7 +5,9 @@
 // its first interaction, which writes a FeatSlot (rtmi_shade.hpp) to the per-sample buffer instead of a radiance.  NEE
 // (rtmi_nee_kernel, rtmi_nee.hip; include/rtmi_nee.h): a lane holds either its path ray or a pending shadow ray toward a
 // light sample (NeeLane); both are traced by the same item scan, the shadow ray with the light-sample stream swapped in
-// for the path's, and never touch the signature.  `nl`: the light table (DevLights).  A textual body
+// for the path's, and never touch the signature.  `nl`: the light table (DevLights).  ENV (rtmi_env_kernel, rtmi_env.hip;
+// include/rtmi_env.h): a ray that leaves the world sees the map `ev` (DevEnv) instead of black or the sky; with NEE the
+// map is one more light, and a shadow ray toward it counts when it leaves the world.  A textual body
 // and not a force-inlined function: inlining one changed the instruction stream of every existing instantiation (same
 // instructions in another order and register assignment), and those must stay bit-for-bit what they were.
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
@@ -37,6 +39,7 @@
         rng_init(gn, 0, 0);
         rng_set_stream(gn, 3u);
         ne.cont_rd = f3(0, 0, 1); ne.c = f3(0, 0, 0); ne.pb = 0.0f; ne.light = 0; ne.shadow = false;
+        if constexpr (ENV) ne.env = false;
     }
     Path pa;
     pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
@@ -135,11 +138,30 @@
                 if (best_item >= 0) {
                     have_hit = true;
                 } else if (NEE && ne.shadow) { // the shadow ray left the world: V = 0; the path goes on
-                    if constexpr (NEE) { pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t; }
+                    if constexpr (NEE) {
+                        if constexpr (ENV) { // ... unless it aims at the map: V = 1
+                            float eu, evv, eth;
+                            if (ne.env && env_uv(pa.rd, eu, evv, eth)) pa.L = pa.L + ne.c * env_radiance(ev, eu, evv);
+                        }
+                        pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t;
+                    }
                 } else { // miss: black background (color.rs:21); the path ends
                     if constexpr (FEATURES) {
                         feat_miss(P, oidx, pa);
                     } else {
+                    if constexpr (ENV) { // the map, weighted by MIS after a diffuse scatter that took a light sample
+                        float eu, evv, eth;
+                        if (env_uv(pa.rd, eu, evv, eth)) {
+                            float w = 1.0f;
+                            if constexpr (NEE) {
+                                if (ne.pb > 0.0f) {
+                                    const float pe = env_pdf(ev, eu, evv, eth);
+                                    if (pe > 0.0f) w = nee_mis_bsdf(ne.pb, pe);
+                                }
+                            }
+                            pa.L = pa.L + pa.T * (env_radiance(ev, eu, evv) * w);
+                        }
+                    } else
                     if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
                     path_end(P, oidx, pa);
                     }
@@ -168,9 +190,9 @@
                 }
             } else if constexpr (NEE) {
                 const bool was_shadow = ne.shadow;
-                const bool goes_on = shade_hit<decltype(g), true, false, true>(
+                const bool goes_on = shade_hit<decltype(g), true, false, true, ENV>(
                     sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
-                    reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), nullptr, &nl, &ne, &gn);
+                    reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), nullptr, &nl, &ne, &gn, &ev);
                 if (shading) {
                     if (was_shadow) { // the light sample is counted: the path's continuation is traced next
                         pa.rd = ne.cont_rd; ne.shadow = false;

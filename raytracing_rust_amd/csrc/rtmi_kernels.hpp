@@ -19,8 +19,9 @@
 // ----------------------------------------------------------------------------------
 template <bool FAST, bool SIG, bool PROF>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_render_kernel(DevScene sc, DevCamera cam, DevParams P) {
-    constexpr bool TILE_LIST = false, FEATURES = false, NEE = false;
+    constexpr bool TILE_LIST = false, FEATURES = false, NEE = false, ENV = false;
     const DevLights nl{};
+    const DevEnv ev{};
     const uint32_t *const tiles = nullptr;
 #include "rtmi_kernel_perlane.inc"
 }

@@ -21,7 +21,8 @@
 
 template <bool FAST, bool SIG>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_nee_kernel(DevScene sc, DevCamera cam, DevParams P, DevLights nl) {
-    constexpr bool PROF = false, TILE_LIST = false, FEATURES = false, NEE = true;
+    constexpr bool PROF = false, TILE_LIST = false, FEATURES = false, NEE = true, ENV = false;
+    const DevEnv ev{};
     const uint32_t *const tiles = nullptr;
 #include "rtmi_kernel_perlane.inc"
 }

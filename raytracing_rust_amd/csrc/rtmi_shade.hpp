@@ -4,6 +4,7 @@
 #pragma once
 #include "rtmi_rng.hpp"
 #include "rtmi_geom.hpp"
+#include "rtmi_env.h"
 
 // ----------------------------------------------------------------------------------
 // textures — src/texture.rs, src/perlin.rs
@@ -374,6 +375,7 @@ struct NeeLane {
     float pb;   // density p_b of the scatter that produced the path's current ray; 0 = weight 1 at an emitter hit
     int light;  // the light the pending shadow ray was sampled on
     bool shadow; // the lane traces (or holds the hit of) a shadow ray
+    bool env;    // ENV kernels (rtmi_env.hip): the pending shadow ray aims at the environment map, not at `light`
 };
 #define RTMI_NEE_2_OVER_PI 0.63661977236758134f
 #define RTMI_NEE_INV_4PI 0.079577471545947668f
@@ -438,6 +440,90 @@ __device__ __forceinline__ bool nee_sample(const NeeLight &L, F3 x, float u1, fl
     return tq > 0.0f;
 }
 
+// ---- environment lighting (include/rtmi_env.h, rtmi_env.hip) ---------------------------------------------------------
+// The attached map on the device, built by rtmi_scene_attach_env: the texels as float4 {r, g, b, 0} (one 16-B load each)
+// and the tables of rtmi_env_tables; p_env is the render's (0: the map is not sampled).
+struct DevEnv {
+    const float4 *texels;  // [h][w]
+    const float *row_cdf;  // [h]
+    const float *row_p;    // [h]
+    const float *col_cdf;  // [h][w]
+    const float *col_p;    // [h][w]
+    uint32_t w, h;
+    float p_env;
+};
+// direction -> (u, v) and theta of the map; false for a direction that sees nothing (rtmi_env.h)
+__device__ __forceinline__ bool env_uv(F3 d, float &u, float &v, float &th) {
+    const float ax = __builtin_fabsf(d.x), ay = __builtin_fabsf(d.y), az = __builtin_fabsf(d.z);
+    if (!(ax <= RTMI_FLT_MAX && ay <= RTMI_FLT_MAX && az <= RTMI_FLT_MAX)) return false;
+    const float m = fmaxf(fmaxf(ax, ay), az);
+    if (!(m > 0.0f)) return false;
+    const F3 s = vdiv(d, m);
+    const F3 n = vdiv(s, __builtin_sqrtf(dot(s, s)));
+    const float phi = rtmi_atan2f(n.z, n.x);
+    th = rtmi_asinf(fminf(fmaxf(n.y, -1.0f), 1.0f));
+    u = 1.0f - (phi + RTMI_PI_F) / (2.0f * RTMI_PI_F);
+    v = (th + RTMI_PIO2_F) / RTMI_PI_F;
+    return true;
+}
+// env(d) at (u, v): bilinear, wrapped in x, clamped in y, each lerp a + f * (b - a)
+__device__ __forceinline__ F3 env_radiance(const DevEnv &E, float u, float v) {
+    const int W = (int)E.w, H = (int)E.h;
+    const float x = u * (float)E.w - 0.5f, y = (1.0f - v) * (float)E.h - 0.5f;
+    const float x0 = floorf(x), y0 = floorf(y);
+    const float fx = x - x0, fy = y - y0;
+    int i0 = (int)x0; // in [-1, W - 1]; the clamps only guard the loads
+    i0 = i0 < 0 ? i0 + W : i0;
+    i0 = min(max(i0, 0), W - 1);
+    const int i1 = i0 + 1 < W ? i0 + 1 : 0;
+    const int yi = (int)y0;
+    const int j0 = min(max(yi, 0), H - 1), j1 = min(max(yi + 1, 0), H - 1);
+    const float4 a = E.texels[(size_t)j0 * E.w + i0], b = E.texels[(size_t)j0 * E.w + i1];
+    const float4 c = E.texels[(size_t)j1 * E.w + i0], e = E.texels[(size_t)j1 * E.w + i1];
+    const F3 t0 = f3(a.x + fx * (b.x - a.x), a.y + fx * (b.y - a.y), a.z + fx * (b.z - a.z));
+    const F3 t1 = f3(c.x + fx * (e.x - c.x), c.y + fx * (e.y - c.y), c.z + fx * (e.z - c.z));
+    return f3(t0.x + fy * (t1.x - t0.x), t0.y + fy * (t1.y - t0.y), t0.z + fy * (t1.z - t0.z));
+}
+// the solid-angle density of the map's light sample in texel (i, j), ct = cos(theta) > 0
+__device__ __forceinline__ float env_pdf_texel(const DevEnv &E, uint32_t i, uint32_t j, float ct) {
+    return (((E.p_env * E.row_p[j]) * E.col_p[(size_t)j * E.w + i]) * (float)(E.w * E.h)) / (RTMI_ENV_2PI2_F * ct);
+}
+// the BSDF side: the density of the direction with (u, v, theta), in the texel the lookup finds for it
+__device__ __forceinline__ float env_pdf(const DevEnv &E, float u, float v, float th) {
+    if (!(E.p_env > 0.0f)) return 0.0f;
+    const float ct = rtmi_cosf(th);
+    if (!(ct > 0.0f)) return 0.0f;
+    const int i = min(max((int)floorf(u * (float)E.w), 0), (int)E.w - 1);
+    const int j = min(max((int)floorf((1.0f - v) * (float)E.h), 0), (int)E.h - 1);
+    return env_pdf_texel(E, (uint32_t)i, (uint32_t)j, ct);
+}
+// the first index with us < cdf[index] (rtmi_nee.h's search)
+__device__ __forceinline__ uint32_t env_search(const float *cdf, uint32_t n, float us) {
+    uint32_t lo = 0u, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (us < cdf[mid]) hi = mid; else lo = mid + 1u;
+    }
+    return lo;
+}
+// the map's light sample from two uniforms: a unit direction and its density; false = no sample
+__device__ __forceinline__ bool env_sample(const DevEnv &E, float u1, float u2, F3 &dir, float &pdf) {
+    const uint32_t j = env_search(E.row_cdf, E.h, u1);
+    const float *cc = E.col_cdf + (size_t)j * E.w;
+    const uint32_t i = env_search(cc, E.w, u2);
+    const float r0 = j > 0u ? E.row_cdf[j - 1u] : 0.0f, c0 = i > 0u ? cc[i - 1u] : 0.0f;
+    const float fy = fminf((u1 - r0) / (E.row_cdf[j] - r0), RTMI_ENV_ONE_MINUS);
+    const float fx = fminf((u2 - c0) / (cc[i] - c0), RTMI_ENV_ONE_MINUS);
+    const float u = ((float)i + fx) / (float)E.w, v = 1.0f - ((float)j + fy) / (float)E.h;
+    const float phi = (1.0f - u) * (2.0f * RTMI_PI_F) - RTMI_PI_F;
+    const float th = v * RTMI_PI_F - RTMI_PIO2_F;
+    const float ct = rtmi_cosf(th);
+    if (!(ct > 0.0f)) return false;
+    dir = f3(ct * rtmi_cosf(phi), rtmi_sinf(th), ct * rtmi_sinf(phi));
+    pdf = env_pdf_texel(E, i, j, ct);
+    return pdf > 0.0f && pdf < RTMI_FLT_MAX;
+}
+
 // HitRecord of the closest hit (hittable.rs:9-16), built once, then
 // color(): emitted + attenuation * color(scattered) — color.rs:8-15, in throughput form.
 // ALL 64 lanes call this together (the texture lookup is a wavefront operation, tex_value_wave); lanes with
@@ -450,11 +536,14 @@ __device__ __forceinline__ bool nee_sample(const NeeLight &L, F3 x, float u1, fl
 // an emitter hit of an eligible light by nee_mis_bsdf, and at a scattering Lambertian / Isotropic vertex draws a light
 // sample from *gn (stream 3): on success pa.rd becomes the shadow ray, ne->cont_rd keeps the continuation and ne->shadow
 // is set.
-template <typename RngT, bool INST = true, bool FEAT = false, bool NEE = false>
+// ENV (with NEE; environment kernels, rtmi_env.hip; include/rtmi_env.h): the map *ev is one more light, chosen with
+// probability ev->p_env; area-light densities scale by 1 - p_env; a shadow ray toward the map that hits anything adds
+// nothing.
+template <typename RngT, bool INST = true, bool FEAT = false, bool NEE = false, bool ENV = false>
 __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth, uint32_t ext, RngT &g, uint32_t k0, uint32_t k1,
                                           bool active, float closest, int best_item, int best_pf, bool best_medium, Path &pa,
                                           float *scratch, ShadeFeat *feat = nullptr, const DevLights *nl = nullptr,
-                                          NeeLane *ne = nullptr, RngT *gn = nullptr) {
+                                          NeeLane *ne = nullptr, RngT *gn = nullptr, const DevEnv *ev = nullptr) {
     F3 hp = f3(0, 0, 0), hn = f3(1, 0, 0);
     float hu = 0.0f, hv = 0.0f;
     rtmi_material M;
@@ -563,6 +652,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
     if (active) {
         if constexpr (NEE) {
             if (ne->shadow) { // V = 1 iff the shadow ray's closest hit is the sampled occurrence; Le = its texture value
+                if constexpr (ENV) {
+                    if (ne->env) return false; // toward the map: any hit occludes
+                }
                 const NeeLight &Ls = nl->lights[ne->light];
                 if (!best_medium && kind == RTMI_MAT_DIFFUSE_LIGHT && best_item == Ls.item && (best_pf >> 3) == Ls.prim)
                     pa.L = pa.L + ne->c * tv;
@@ -573,7 +665,8 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
                 if (!best_medium && ne->pb > 0.0f) {
                     const int li = nl->prim_light[best_pf >> 3];
                     if (li >= 0 && nl->lights[li].item == best_item) {
-                        const float pl = nee_pdf(nl->lights[li], pa.ro, hp);
+                        float pl = nee_pdf(nl->lights[li], pa.ro, hp);
+                        if constexpr (ENV) pl = (1.0f - ev->p_env) * pl;
                         if (pl > 0.0f) w = nee_mis_bsdf(ne->pb, pl);
                     }
                 }
@@ -634,6 +727,44 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
             }
         }
         F3 sdir = nd;
+        if constexpr (NEE && ENV) { // ... with the map as one more light (rtmi_env.h)
+            ne->pb = 0.0f;
+            if (scattered && (nl->n > 0u || ev->p_env > 0.0f) && (kind == RTMI_MAT_LAMBERTIAN || kind == RTMI_MAT_ISOTROPIC)) {
+                const bool iso = kind == RTMI_MAT_ISOTROPIC;
+                ne->pb = iso ? RTMI_NEE_INV_4PI : nee_pb_lambert(nd, hn);
+                uint32_t w0, w1, w2;
+                rng_take3(*gn, k0, k1, w0, w1, w2);
+                float us = rtmi_u01(w0);
+                const bool to_env = us < ev->p_env;
+                F3 dir = f3(0, 0, 0);
+                float pl = 0.0f;
+                bool ok = false;
+                uint32_t lo = 0u;
+                if (to_env) {
+                    ok = env_sample(*ev, rtmi_u01(w1), rtmi_u01(w2), dir, pl);
+                } else if (nl->n > 0u) {
+                    us = (us - ev->p_env) / (1.0f - ev->p_env);
+                    uint32_t hi = nl->n - 1u; // the first light whose cdf exceeds us
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (us < nl->lights[mid].cdf) hi = mid; else lo = mid + 1u;
+                    }
+                    ok = nee_sample(nl->lights[lo], hp, rtmi_u01(w1), rtmi_u01(w2), dir, pl);
+                    pl = (1.0f - ev->p_env) * pl;
+                }
+                if (ok) {
+                    const float pbl = iso ? RTMI_NEE_INV_4PI : nee_pb_lambert(dir, hn);
+                    if (pbl > 0.0f && pl > 0.0f && pl < RTMI_FLT_MAX) {
+                        ne->c = (pa.T * tv) * nee_mis_light(pbl, pl);
+                        ne->light = (int)lo;
+                        ne->env = to_env;
+                        ne->cont_rd = nd;
+                        ne->shadow = true;
+                        sdir = dir;
+                    }
+                }
+            }
+        } else
         if constexpr (NEE) { // the light sample of a scattering Lambertian / Isotropic vertex (draw order: rtmi_nee.h)
             ne->pb = 0.0f;
             if (scattered && nl->n > 0u && (kind == RTMI_MAT_LAMBERTIAN || kind == RTMI_MAT_ISOTROPIC)) {

@@ -176,6 +176,36 @@ class Scene:
         self.lights_attached = True
         return self
 
+    def attach_env(self, rgb):
+        """Attaches an environment map (include/rtmi_env.h): float32 [H, W, 3], row 0 the top row (+y), finite and >= 0.
+        Replaces an attached map; uploads the scene first when needed."""
+        a = np.asarray(rgb)
+        if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.float32:
+            raise ValueError("attach_env takes a float32 [H, W, 3] array, not %s %r" % (a.dtype, a.shape))
+        a = np.ascontiguousarray(a)
+        if not self.uploaded:
+            self.upload(0)
+        self.host._check(self.host.lib.rth_attach_env(self.h, a.shape[1], a.shape[0], a.ctypes.data))
+        self.env_attached = True
+        return self
+
+    def detach_env(self):
+        """Frees the attached environment map (rtmi_scene_attach_env with NULL)."""
+        if self.uploaded:
+            self.host._check(self.host.lib.rth_attach_env(self.h, 0, 0, None))
+        self.env_attached = False
+        return self
+
+    def probe_env(self, op, inp):
+        """rtmi_probe_env: the device's lookup (op RTMI_ENV_PROBE_LOOKUP, inp float32 [n, 3] directions -> [n, 4] = r, g, b,
+        pdf) or light sample (RTMI_ENV_PROBE_SAMPLE, inp float32 [n, 2] uniforms -> [n, 4] = direction, pdf) on the
+        attached map, with p_env = 1."""
+        inp = np.ascontiguousarray(inp, dtype=np.float32)
+        n = inp.shape[0]
+        out = np.zeros((n, 4), np.float32)
+        self.host._check(self.host.lib.rth_probe_env(self.h, int(op), inp.ctypes.data, out.ctypes.data, n))
+        return out
+
     def attach_f64(self):
         """Attaches the double planes to the uploaded handle (rtmi_scene_attach_f64)."""
         self.host._check(self.host.lib.rth_attach_f64(self.h))
@@ -291,16 +321,47 @@ class Scene:
             out["sig"] = sg
         return out
 
-    def render_denoised(self, cam, nx, ny, ns, denoise=None, nee=False, **kw):
+    def render_env(self, cam, nx, ny, ns, nee=True, env_select_p=0.5, sig=False, precision="f32", **kw):
+        """Environment lighting (include/rtmi_env.h): render()'s paths with the attached map (attach_env) where a ray
+        leaves the world; nee=True also samples the map (importance-sampled) and the area lights at every diffuse vertex,
+        env_select_p being the map's share when the scene has area lights.  Returns dict(linear f32 [ny,nx,3], rgb8 u8
+        [ny,nx,3], stderr f32 [ny,nx,3], stats[, sig u64 [ny,nx]]); sig equals render(sig=True)["sig"].  With nee=True the
+        light table is attached on first use.  A scene resident on a device list (upload_multi) raises Unsupported."""
+        if precision != "f32":
+            raise Unsupported("environment lighting has no f64 mode")
+        if not self.uploaded and not getattr(self, "multi_devices", None):
+            self.upload(kw.pop("device", 0))
+        kw.pop("device", None)
+        if nee and self.uploaded and not getattr(self, "lights_attached", False):
+            self.attach_lights()
+        p = default_params(nx, ny, ns, **kw)
+        o = abi.EnvRender(1 if nee else 0, env_select_p)
+        lin = np.zeros((ny, nx, 3), np.float32)
+        rgb = np.zeros((ny, nx, 3), np.uint8)
+        se = np.zeros((ny, nx, 3), np.float32)
+        sg = np.zeros((ny, nx), np.uint64) if sig else None
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_env(self.h, cam.h, C.byref(p), C.byref(o), lin.ctypes.data, rgb.ctypes.data,
+                                                       se.ctypes.data, sg.ctypes.data if sig else None, C.byref(st)))
+        out = {"linear": lin, "rgb8": rgb, "stderr": se, "stats": _stats(st)}
+        if sig:
+            out["sig"] = sg
+        return out
+
+    def render_denoised(self, cam, nx, ny, ns, denoise=None, nee=False, env=False, **kw):
         """A render and its denoised image: render_adaptive(min_spp=ns, step_spp=1) (render()'s image plus its standard
         errors), render_features with the same ns and keywords, then denoise() of the three on the scene's device.
         `denoise` = dict of denoise() keywords.  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], noisy = the adaptive
         dict, features = the features dict).  ns >= 2; the other restrictions are those of the two renders.
         nee=True: the noisy image and its standard errors come from render_nee (the same paths, so the features still
-        describe them)."""
+        describe them).  env=True: they come from render_env(nee=nee) with the attached map (env_select_p among the
+        keywords); pixels where no sample hits a surface are not filtered: they keep the map as seen."""
         if ns < 2:
             raise ValueError("render_denoised needs ns >= 2 (a standard error needs two samples)")
-        if nee:
+        if env:
+            noisy = self.render_env(cam, nx, ny, ns, nee=nee, **kw)
+            kw.pop("env_select_p", None)
+        elif nee:
             noisy = self.render_nee(cam, nx, ny, ns, **kw)
         else:
             noisy = self.render_adaptive(cam, nx, ny, ns, min_spp=ns, step_spp=1, **kw)
@@ -670,6 +731,66 @@ def pfm_bytes(plane):
     ny, nx = a.shape[:2]
     body = np.ascontiguousarray(a[::-1], dtype="<f4").tobytes()
     return tag + b"\n%d %d\n-1.0\n" % (nx, ny) + body
+
+
+def read_pfm(data):
+    """The inverse of pfm_bytes: PFM bytes ("PF" colour or "Pf" greyscale, either byte order) -> float32 [ny,nx,3] or
+    [ny,nx], row 0 the top row.  Loads HDR environment maps (Scene.attach_env)."""
+    parts, pos = [], 0
+    while len(parts) < 4:  # tag, width, height, scale: whitespace-separated tokens, then one whitespace byte
+        while pos < len(data) and data[pos:pos + 1].isspace():
+            pos += 1
+        end = pos
+        while end < len(data) and not data[end:end + 1].isspace():
+            end += 1
+        if end == pos:
+            raise ValueError("read_pfm: truncated header")
+        parts.append(data[pos:end])
+        pos = end
+    pos += 1
+    tag, nx, ny, scale = parts[0], int(parts[1]), int(parts[2]), float(parts[3])
+    if tag not in (b"PF", b"Pf") or nx <= 0 or ny <= 0 or scale == 0:
+        raise ValueError("read_pfm: not a PFM header: %r" % (parts,))
+    ch = 3 if tag == b"PF" else 1
+    dt = np.dtype("<f4" if scale < 0 else ">f4")
+    n = nx * ny * ch
+    if len(data) - pos < 4 * n:
+        raise ValueError("read_pfm: %d samples expected, %d bytes left" % (n, len(data) - pos))
+    a = np.frombuffer(data, dtype=dt, count=n, offset=pos).astype(np.float32)
+    a = a.reshape((ny, nx, 3) if ch == 3 else (ny, nx))[::-1]
+    return np.ascontiguousarray(a)
+
+
+def env_tables(rgb):
+    """The sampling tables of an environment map (rtmi_env_tables, include/rtmi_env.h): float32 [H, W, 3] -> dict(row_cdf
+    [H], row_p [H], col_cdf [H, W], col_p [H, W], total).  Host code: needs no GPU."""
+    a = np.asarray(rgb)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.float32:
+        raise ValueError("env_tables takes a float32 [H, W, 3] array, not %s %r" % (a.dtype, a.shape))
+    a = np.ascontiguousarray(a)
+    h, w = a.shape[:2]
+    lib = abi.load_rtmi()
+    out = {"row_cdf": np.zeros(h, np.float32), "row_p": np.zeros(h, np.float32), "col_cdf": np.zeros((h, w), np.float32),
+           "col_p": np.zeros((h, w), np.float32)}
+    total = C.c_double(0.0)
+    m = abi.EnvMap(w, h, a.ctypes.data)
+    rc = lib.rtmi_env_tables(C.byref(m), out["row_cdf"].ctypes.data, out["row_p"].ctypes.data, out["col_cdf"].ctypes.data,
+                             out["col_p"].ctypes.data, C.byref(total))
+    if rc != 0:
+        raise HostError("rtmi_env_tables failed (%d): %s" % (rc, lib.rtmi_last_error().decode()))
+    out["total"] = total.value
+    return out
+
+
+def env_from_sky(width, height):
+    """RTMI_FLAG_SKY's gradient as an environment map: float32 [height, width, 3], each texel the sky (f64, rounded once)
+    in the direction of its centre."""
+    j = np.arange(height, dtype=np.float64)
+    theta = (1.0 - (j + 0.5) / height) * np.pi - np.pi / 2
+    t = 0.5 * (np.sin(theta) + 1.0)
+    a = 1.0 - t
+    row = np.stack([a + t * 0.5, a + t * 0.7, a + t * 1.0], axis=-1)
+    return np.ascontiguousarray(np.broadcast_to(row[:, None, :], (height, width, 3)).astype(np.float32))
 
 
 def write_ppm(path, rgb8, fmt=3):

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rt_host.hpp"
+#include "rtmi_env.h"
 
 using namespace rt;
 
@@ -295,6 +296,42 @@ RTH_API int rth_render_nee(void *lowered, void *cam, const rtmi_render_params *p
         const int rc = rtmi_render_nee(o->dev, &c, p, out_linear, out_rgb8, out_stderr, out_path_sig, stats);
         if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_nee: ") + rtmi_last_error());
         if (rc) throw std::runtime_error(std::string("rtmi_render_nee: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+
+// environment lighting (include/rtmi_env.h): attaches a map (rgb = NULL detaches) to the uploaded handle, then renders;
+// RTH_UNSUPPORTED for what rtmi_render_env does not support, a multi-GPU handle among it
+RTH_API int rth_attach_env(void *lowered, uint32_t width, uint32_t height, const float *rgb) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi) throw Unsupported("rtmi_scene_attach_env: multi-GPU handles have no environment entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_env_map m{width, height, rgb};
+        if (int rc = rtmi_scene_attach_env(o->dev, rgb ? &m : nullptr))
+            throw std::runtime_error(std::string("rtmi_scene_attach_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+RTH_API int rth_render_env(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_env_render *opts, float *out_linear,
+                           uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi) throw Unsupported("rtmi_render_env: multi-GPU handles have no environment entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_env(o->dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_path_sig, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_env: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+RTH_API int rth_probe_env(void *lowered, int op, const float *in, float *out, uint32_t n) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        if (int rc = rtmi_probe_env(o->dev, op, in, out, n))
+            throw std::runtime_error(std::string("rtmi_probe_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
         return RTH_OK;
     });
 }
