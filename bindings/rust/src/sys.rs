@@ -591,3 +591,33 @@ extern "C" {
     /// the device's lookup or light sample on the attached map (RTMI_ENV_PROBE_*)
     pub fn rtmi_probe_env(scene: *mut RtmiScene, op: c_int, input: *const f32, out: *mut f32, n: u32) -> c_int;
 }
+
+// ---- include/rtmi_adaptive_nee.h: adaptive sampling with next-event estimation or environment lighting ---------------
+extern "C" {
+    /// blocking whole-image adaptive render with rtmi_render_nee's estimator: per-tile sample counts up to params.ns,
+    /// per-pixel standard errors
+    pub fn rtmi_render_adaptive_nee(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        adaptive: *const RtmiAdaptive,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_spp: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the same with rtmi_render_env's estimator and options on the attached map
+    pub fn rtmi_render_adaptive_env(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiEnvRender,
+        adaptive: *const RtmiAdaptive,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_spp: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+}

@@ -209,6 +209,10 @@ RTMI_ENV_MAX_SIDE, RTMI_ENV_MAX_TEXELS = 16384, 1 << 25
 # the functions of include/rtmi_env.h (environment lighting), kept apart from those of the other headers
 RTMI_ENV_SYMBOLS = ["rtmi_env_tables", "rtmi_scene_attach_env", "rtmi_render_env", "rtmi_probe_env"]
 
+# the functions of include/rtmi_adaptive_nee.h (adaptive sampling with NEE or environment lighting), kept apart from those
+# of the other headers
+RTMI_ADAPTIVE_NEE_SYMBOLS = ["rtmi_render_adaptive_env", "rtmi_render_adaptive_nee"]
+
 _rtmi = None
 _host = None
 
@@ -297,6 +301,12 @@ def load_rtmi():
                                     C.POINTER(Stats)]
     lib.rtmi_probe_env.restype = C.c_int
     lib.rtmi_probe_env.argtypes = [vp, C.c_int, vp, vp, C.c_uint32]
+    lib.rtmi_render_adaptive_nee.restype = C.c_int
+    lib.rtmi_render_adaptive_nee.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp,
+                                             vp, C.POINTER(Stats)]
+    lib.rtmi_render_adaptive_env.restype = C.c_int
+    lib.rtmi_render_adaptive_env.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(EnvRender),
+                                             C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -362,6 +372,9 @@ def load_host():
         "rth_attach_env": (i, [vp, u32, u32, vp]),
         "rth_render_env": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(EnvRender), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_probe_env": (i, [vp, i, vp, vp, u32]),
+        "rth_render_adaptive_nee": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_render_adaptive_env": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(EnvRender), C.POINTER(Adaptive), vp, vp, vp, vp,
+                                        C.POINTER(Stats)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

@@ -46,6 +46,8 @@
 #include "rtmi_nee_launch.hpp"
 #include "rtmi_env.h"
 #include "rtmi_env_launch.hpp"
+#include "rtmi_adaptive_nee.h"
+#include "rtmi_adaptive_nee_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -1876,57 +1878,45 @@ extern "C" int rtmi_probe_math_f64(int op, const double *x, const double *y, dou
 }
 
 // ---- adaptive sampling (include/rtmi_adaptive.h) ---------------------------------------------------------------------
-// Steps of samples per active tile; after every step the adaptive resolve retires the converged tiles and lists the
-// others, and the host reads the count back (4 B) and plans the next step for that many tiles, so a small active set
-// still gets enough units to fill the chip.  The per-sample buffer holds the active tiles only (indexed by list position).
-extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
-                                    const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
-                                    uint32_t *out_spp, rtmi_stats *stats) {
-    // every argument check comes before the first use of the handle (and of the device)
-    if (!p_in || !a || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                                         RTMI_FLAG_UV_BOOK,
-                               "adaptive sampling accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and "
-                               "UV_BOOK only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
-                               "adaptive sampling renders the whole image: tile_world must be 1");
-    if (rc) return rc;
+// the checks of the noise target, after those of the params (rtmi_render_adaptive and the entries of rtmi_adaptive_nee.h)
+static int check_adaptive(const rtmi_render_params *p, const rtmi_adaptive *a) {
     if (a->min_spp < 2u) return fail(RTMI_ERR_INVALID, "min_spp must be at least 2 (a variance needs two samples)");
-    if (a->min_spp > p_in->ns) return fail(RTMI_ERR_INVALID, "min_spp must not exceed ns");
+    if (a->min_spp > p->ns) return fail(RTMI_ERR_INVALID, "min_spp must not exceed ns");
     if (a->step_spp == 0u) return fail(RTMI_ERR_INVALID, "step_spp must be positive");
     if (!std::isfinite(a->abs_tol) || !(a->abs_tol >= 0.0) || !std::isfinite(a->rel_tol) || !(a->rel_tol >= 0.0))
         return fail(RTMI_ERR_INVALID, "abs_tol and rel_tol must be finite and non-negative");
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    const rtmi_render_params &p = *p_in;
+    return RTMI_OK;
+}
+
+// the buffers of an adaptive call for T tiles, before the clock starts: framebuffer, adaptive state, the pinned count
+// word and the per-sample buffer for the largest step (every tile, max(min_spp, step_spp) samples)
+static int adaptive_reserve(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, uint32_t T) {
+    int rc;
+    if ((rc = reserve_texels(s, (size_t)T * 64)) || (rc = grow_adaptive(s, T))) return rc;
+    if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
+    rtmi_render_params q = p;
+    q.ns = a->min_spp > a->step_spp ? a->min_spp : (a->step_spp < p.ns ? a->step_spp : p.ns);
+    uint32_t chunk_spp = 0, pass_ns = 0;
+    return plan_and_reserve(s, &q, T, chunk_spp, pass_ns);
+}
+
+// Steps of samples per active tile; after every step the adaptive resolve retires the converged tiles and lists the
+// others, and the host reads the count back (4 B) and plans the next step for that many tiles, so a small active set
+// still gets enough units to fill the chip.  The per-sample buffer holds the active tiles only (indexed by list position).
+// Shared by rtmi_render_adaptive and the entries of rtmi_adaptive_nee.h.  launch(blocks, tiles) enqueues the mode's
+// render kernel on s->stream for the pass fields of P over the active list `tiles` and returns an RTMI code; `kernel` is
+// the label of rtmi_stats.kernel.  The caller holds s->mu, has checked every argument, called begin_blocking and
+// adaptive_reserve and filled P with the mode's traversal plan.
+template <typename Launch>
+static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
+                          float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats,
+                          Launch &&launch) {
+    int rc;
     hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64;
-    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T))) return rc;
-    if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
-    { // the per-sample buffer for the largest step (every tile, max(min_spp, step_spp) samples) before the clock starts
-        rtmi_render_params q = p;
-        q.ns = a->min_spp > a->step_spp ? a->min_spp : (a->step_spp < p.ns ? a->step_spp : p.ns);
-        uint32_t chunk_spp = 0, pass_ns = 0;
-        if ((rc = plan_and_reserve(s, &q, T, chunk_spp, pass_ns))) return rc;
-    }
-
-    DevParams P = dev_params(s, &p);
-    const DevCamera C = dev_camera(cam);
-    // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
-    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
-    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
-    const bool coop = fast && !sync && coop_ok && !inst;
-    bool ext = false;
-    if ((rc = plan_traversal(s, &p, coop, P, ext))) return rc;
-    const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
-    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
-                                                       (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
-    s->last_kernel = coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
+    s->last_kernel = kernel;
 
     rtmi_progress_fn fn = reinterpret_cast<rtmi_progress_fn>(static_cast<uintptr_t>(p.progress_fn));
     void *user = reinterpret_cast<void *>(static_cast<uintptr_t>(p.progress_user));
@@ -1955,7 +1945,7 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
         const uint64_t units_before = s->units_total;
         // samples [n, n + c) in sub-passes when the per-sample buffer does not hold the step
         rc = run_passes(s, P, stream, n, c, false, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
-            HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, stream, s->dev, C, P, lists[cur]));
+            if (int lrc = launch(blocks, (const uint32_t *)lists[cur])) return lrc;
             A.first = (n == 0 && first) ? 1 : 0;
             A.decide = last ? 1 : 0;
             HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
@@ -2008,6 +1998,46 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
         for (size_t o = 0; o < npix; o++) stats->samples += spp[o];
     }
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
+extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
+                                    const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
+                                    uint32_t *out_spp, rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !a || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                                         RTMI_FLAG_UV_BOOK,
+                               "adaptive sampling accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and "
+                               "UV_BOOK only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                               "adaptive sampling renders the whole image: tile_world must be 1");
+    if (rc) return rc;
+    if ((rc = check_adaptive(p_in, a))) return rc;
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = begin_blocking(s))) return rc;
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    BusyMark busy_mark{s, stream};
+    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
+
+    DevParams P = dev_params(s, &p);
+    const DevCamera C = dev_camera(cam);
+    // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
+    const bool coop = fast && !sync && coop_ok && !inst;
+    bool ext = false;
+    if ((rc = plan_traversal(s, &p, coop, P, ext))) return rc;
+    const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
+    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
+                                                       (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
+    return adaptive_steps(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr,
+                          out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                              HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, stream, s->dev, C, P, tiles));
+                              return RTMI_OK;
+                          });
 }
 
 // ---- first-hit features (include/rtmi_features.h) ---------------------------------------------------------------------
@@ -2219,6 +2249,13 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     return RTMI_OK;
 }
 
+// the attached light table as the NEE kernels read it (the caller has checked s->has_lights)
+static DevLights dev_lights(const rtmi_scene *s) {
+    DevLights L;
+    L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n;
+    return L;
+}
+
 // The per-lane NEE kernel (rtmi_nee.hip) in passes of the render's plan; adaptive sampling's resolve over the list of all
 // tiles carries sum, m and M2 between passes and writes texels and standard errors after the last one.
 extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
@@ -2252,8 +2289,7 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     const DevCamera C = dev_camera(cam);
     const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
     P.path_sig = sig ? s->d_sig : nullptr;
-    DevLights L;
-    L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n;
+    const DevLights L = dev_lights(s);
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
     s->last_kernel = RTMI_KERNEL_PERLANE;
 
@@ -2327,6 +2363,14 @@ static DevEnv dev_env(const rtmi_scene *s, float p_env) {
     E.p_env = p_env;
     return E;
 }
+// the map of an environment render with these options; p_env: the map's share of the light samples (rtmi_env.h)
+static DevEnv dev_env_render(const rtmi_scene *s, const rtmi_env_render *opts) {
+    return dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? opts->env_select_p : 1.0f));
+}
+// the light table of an environment render: empty unless nee = 1
+static DevLights dev_env_lights(const rtmi_scene *s, bool nee) {
+    return nee ? dev_lights(s) : DevLights{};
+}
 
 // The per-lane environment kernel (rtmi_env.hip) in passes of the render's plan; adaptive sampling's resolve over the list
 // of all tiles, as rtmi_render_nee.
@@ -2370,10 +2414,8 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     const DevCamera C = dev_camera(cam);
     const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
     P.path_sig = sig ? s->d_sig : nullptr;
-    DevLights L{};
-    if (nee) { L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n; }
-    // p_env: the map's share of the light samples (rtmi_env.h)
-    const DevEnv E = dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? opts->env_select_p : 1.0f));
+    const DevLights L = dev_env_lights(s, nee);
+    const DevEnv E = dev_env_render(s, opts);
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
     s->last_kernel = RTMI_KERNEL_PERLANE;
 
@@ -2405,6 +2447,86 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
     if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
+// ---- adaptive sampling with NEE or environment lighting (include/rtmi_adaptive_nee.h) ---------------------------------
+// adaptive sampling's step loop (adaptive_steps) with the per-lane kernel of rtmi_adaptive_nee.hip: rtmi_render_nee's or
+// rtmi_render_env's estimator over the active-tile list
+#define RTMI_ADAPTIVE_NEE_FLAGS (RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK)
+extern "C" int rtmi_render_adaptive_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
+                                        const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
+                                        uint32_t *out_spp, rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !a || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY,
+                               "adaptive NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK only "
+                               "(not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                               "adaptive NEE renders the whole image: tile_world must be 1");
+    if (rc) return rc;
+    if ((rc = check_adaptive(p_in, a))) return rc;
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_lights) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_nee: no light table attached (rtmi_scene_attach_lights)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = begin_blocking(s))) return rc;
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    BusyMark busy_mark{s, stream};
+    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
+
+    DevParams P = dev_params(s, &p);
+    const DevCamera C = dev_camera(cam);
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
+    const DevLights L = dev_lights(s);
+    const DevEnv E{};
+    return adaptive_steps(s, p, a, P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+                          [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                              HIP_TRY(rtmi_adaptive_nee_launch_render(fast, true, false, blocks, stream, s->dev, C, P, tiles, L, E));
+                              return RTMI_OK;
+                          });
+}
+
+extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
+                                        const rtmi_env_render *opts, const rtmi_adaptive *a, float *out_linear,
+                                        uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !a || !cam || !opts) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (p_in->flags & RTMI_FLAG_SKY)
+        return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: RTMI_FLAG_SKY is refused, the map replaces the sky");
+    rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS,
+                           "adaptive environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD and UV_BOOK "
+                           "only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                           "adaptive environment renders render the whole image: tile_world must be 1");
+    if (rc) return rc;
+    if ((rc = check_adaptive(p_in, a))) return rc;
+    if (opts->nee > 1u) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: nee must be 0 or 1");
+    if (!(opts->env_select_p > 0.0f && opts->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: env_select_p must be in (0, 1]");
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_env) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: no environment map attached (rtmi_scene_attach_env)");
+    const bool nee = opts->nee != 0u;
+    if (nee && !s->has_lights)
+        return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: nee = 1 needs the light table (rtmi_scene_attach_lights)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = begin_blocking(s))) return rc;
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    BusyMark busy_mark{s, stream};
+    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
+
+    DevParams P = dev_params(s, &p);
+    const DevCamera C = dev_camera(cam);
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
+    const DevLights L = dev_env_lights(s, nee);
+    const DevEnv E = dev_env_render(s, opts);
+    return adaptive_steps(s, p, a, P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+                          [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                              HIP_TRY(rtmi_adaptive_nee_launch_render(fast, nee, true, blocks, stream, s->dev, C, P, tiles, L, E));
+                              return RTMI_OK;
+                          });
 }
 
 extern "C" int rtmi_probe_env(rtmi_scene *s, int op, const float *in, float *out, uint32_t n) {

@@ -250,16 +250,22 @@ class Scene:
             out["sig"] = sg
         return out
 
-    def render_adaptive(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, precision="f32", **kw):
+    def render_adaptive(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, precision="f32", nee=False,
+                        env=False, env_select_p=0.5, **kw):
         """Adaptive sampling (include/rtmi_adaptive.h): every 8x8 tile gets min_spp samples, then step_spp more per step
         while some in-image pixel has stderr > abs_tol + rel_tol * |mean|, up to ns.  Returns dict(linear f32 [ny,nx,3],
         rgb8 u8 [ny,nx,3], stderr f32 [ny,nx,3], spp u32 [ny,nx], stats).  A tile is bit for bit the tile of
-        render(ns = its spp).  progress: callable(done, total) in tile-samples, total = tiles x ns."""
+        render(ns = its spp).  progress: callable(done, total) in tile-samples, total = tiles x ns.
+        nee=True: the estimator of render_nee (include/rtmi_adaptive_nee.h), a tile bit for bit, stderr included, that of
+        render_nee(ns = its spp); the light table is attached on first use.  env=True: that of render_env(nee=nee,
+        env_select_p=env_select_p) with the attached map.  The defaults are the plain estimator."""
         if precision != "f32":
             raise Unsupported("adaptive sampling has no f64 mode")
         if not self.uploaded:
             self.upload(kw.pop("device", 0))
         kw.pop("device", None)
+        if nee and self.uploaded and not getattr(self, "lights_attached", False):
+            self.attach_lights()
         p = default_params(nx, ny, ns, **kw)
         a = abi.Adaptive(min_spp, step_spp, abs_tol, rel_tol)
         lin = np.zeros((ny, nx, 3), np.float32)
@@ -267,8 +273,14 @@ class Scene:
         se = np.zeros((ny, nx, 3), np.float32)
         spp = np.zeros((ny, nx), np.uint32)
         st = abi.Stats()
-        self.host._check(self.host.lib.rth_render_adaptive(self.h, cam.h, C.byref(p), C.byref(a), lin.ctypes.data,
-                                                            rgb.ctypes.data, se.ctypes.data, spp.ctypes.data, C.byref(st)))
+        outs = (lin.ctypes.data, rgb.ctypes.data, se.ctypes.data, spp.ctypes.data, C.byref(st))
+        if env:
+            o = abi.EnvRender(1 if nee else 0, env_select_p)
+            self.host._check(self.host.lib.rth_render_adaptive_env(self.h, cam.h, C.byref(p), C.byref(o), C.byref(a), *outs))
+        elif nee:
+            self.host._check(self.host.lib.rth_render_adaptive_nee(self.h, cam.h, C.byref(p), C.byref(a), *outs))
+        else:
+            self.host._check(self.host.lib.rth_render_adaptive(self.h, cam.h, C.byref(p), C.byref(a), *outs))
         return {"linear": lin, "rgb8": rgb, "stderr": se, "spp": spp, "stats": _stats(st)}
 
     def render_features(self, cam, nx, ny, ns, sig=False, precision="f32", **kw):

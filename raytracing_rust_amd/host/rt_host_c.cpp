@@ -9,6 +9,7 @@
 
 #include "rt_host.hpp"
 #include "rtmi_env.h"
+#include "rtmi_adaptive_nee.h"
 
 using namespace rt;
 
@@ -323,6 +324,35 @@ RTH_API int rth_render_env(void *lowered, void *cam, const rtmi_render_params *p
         const int rc = rtmi_render_env(o->dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_path_sig, stats);
         if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_env: ") + rtmi_last_error());
         if (rc) throw std::runtime_error(std::string("rtmi_render_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+// adaptive sampling with NEE or environment lighting (include/rtmi_adaptive_nee.h); RTH_UNSUPPORTED for what the two
+// entries do not support, a multi-GPU handle among it
+RTH_API int rth_render_adaptive_nee(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_adaptive *a,
+                                    float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi) throw Unsupported("rtmi_render_adaptive_nee: multi-GPU handles have no adaptive entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_adaptive_nee(o->dev, &c, p, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_nee: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive_nee: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+RTH_API int rth_render_adaptive_env(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_env_render *opts,
+                                    const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
+                                    uint32_t *out_spp, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi) throw Unsupported("rtmi_render_adaptive_env: multi-GPU handles have no adaptive entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_adaptive_env(o->dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_env: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
         return RTH_OK;
     });
 }
