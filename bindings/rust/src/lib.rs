@@ -180,6 +180,30 @@ impl Scene {
     }
 }
 
+/// The image of a roulette render with its standard errors and per-pixel bounce counts (include/rtmi_roulette.h).
+pub struct RouletteImage {
+    pub image: Image,
+    /// standard error of the mean, 3 floats per pixel
+    pub stderr: Vec<f32>,
+    /// the scatters made by the pixel's paths, summed over its samples
+    pub bounces: Vec<u32>,
+}
+
+impl Scene {
+    /// Blocking whole-image render with Russian-roulette path termination (rtmi_render_roulette).  The NEE estimators
+    /// need the light table, the map estimators the map, attached to the scene beforehand.
+    pub fn render_roulette(&mut self, cam: &RtmiCamera, p: &RtmiRenderParams, opts: &RtmiRoulette) -> Result<RouletteImage, RtmiError> {
+        let (nx, ny) = (p.nx as usize, p.ny as usize);
+        let image = Image { nx, ny, linear: vec![0.0; nx * ny * 3], rgb8: vec![0; nx * ny * 3], stats: RtmiStats::default() };
+        let mut out = RouletteImage { image, stderr: vec![0.0; nx * ny * 3], bounces: vec![0; nx * ny] };
+        check(unsafe {
+            rtmi_render_roulette(self.raw, cam, p, opts, out.image.linear.as_mut_ptr(), out.image.rgb8.as_mut_ptr(),
+                                 out.stderr.as_mut_ptr(), out.bounces.as_mut_ptr(), &mut out.image.stats)
+        })?;
+        Ok(out)
+    }
+}
+
 impl Drop for Scene {
     fn drop(&mut self) {
         unsafe { rtmi_scene_destroy(self.raw) }

@@ -621,3 +621,48 @@ extern "C" {
         stats: *mut RtmiStats,
     ) -> c_int;
 }
+
+// ---- include/rtmi_roulette.h: Russian-roulette path termination with a per-pixel bounce count --------------------------
+pub const RTMI_ROULETTE_PLAIN: u32 = 0;
+pub const RTMI_ROULETTE_NEE: u32 = 1;
+pub const RTMI_ROULETTE_ENV: u32 = 2;
+pub const RTMI_ROULETTE_ENV_NEE: u32 = 3;
+
+/// the options of the roulette entries: whose estimator, the first depth tested, the floor of the survival probability
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiRoulette {
+    pub estimator: u32,
+    pub min_depth: u32,
+    pub q_min: f32,
+    pub env_select_p: f32,
+}
+
+extern "C" {
+    /// blocking whole-image render with roulette; out_bounces: ny*nx, the scatters of the pixel's paths, summed
+    pub fn rtmi_render_roulette(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiRoulette,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_bounces: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the same under the noise target of rtmi_render_adaptive
+    pub fn rtmi_render_adaptive_roulette(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiRoulette,
+        adaptive: *const RtmiAdaptive,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_spp: *mut u32,
+        out_bounces: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+}

@@ -213,6 +213,19 @@ RTMI_ENV_SYMBOLS = ["rtmi_env_tables", "rtmi_scene_attach_env", "rtmi_render_env
 # of the other headers
 RTMI_ADAPTIVE_NEE_SYMBOLS = ["rtmi_render_adaptive_env", "rtmi_render_adaptive_nee"]
 
+
+class Roulette(C.Structure):
+    """rtmi_roulette (include/rtmi_roulette.h): the options of the Russian-roulette entries (16 bytes)."""
+    _fields_ = [("estimator", C.c_uint32), ("min_depth", C.c_uint32), ("q_min", C.c_float), ("env_select_p", C.c_float)]
+
+
+RTMI_ROULETTE_PLAIN, RTMI_ROULETTE_NEE, RTMI_ROULETTE_ENV, RTMI_ROULETTE_ENV_NEE = 0, 1, 2, 3
+ROULETTE_ESTIMATORS = {"plain": RTMI_ROULETTE_PLAIN, "nee": RTMI_ROULETTE_NEE, "env": RTMI_ROULETTE_ENV,
+                       "env_nee": RTMI_ROULETTE_ENV_NEE}
+
+# the functions of include/rtmi_roulette.h (Russian-roulette path termination), kept apart from those of the other headers
+RTMI_ROULETTE_SYMBOLS = ["rtmi_render_adaptive_roulette", "rtmi_render_roulette"]
+
 _rtmi = None
 _host = None
 
@@ -307,6 +320,12 @@ def load_rtmi():
     lib.rtmi_render_adaptive_env.restype = C.c_int
     lib.rtmi_render_adaptive_env.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(EnvRender),
                                              C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_render_roulette.restype = C.c_int
+    lib.rtmi_render_roulette.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Roulette), vp, vp, vp, vp,
+                                         C.POINTER(Stats)]
+    lib.rtmi_render_adaptive_roulette.restype = C.c_int
+    lib.rtmi_render_adaptive_roulette.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Roulette),
+                                                  C.POINTER(Adaptive), vp, vp, vp, vp, vp, C.POINTER(Stats)]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -375,6 +394,9 @@ def load_host():
         "rth_render_adaptive_nee": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_adaptive_env": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(EnvRender), C.POINTER(Adaptive), vp, vp, vp, vp,
                                         C.POINTER(Stats)]),
+        "rth_render_roulette": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Roulette), vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_render_adaptive_roulette": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Roulette), C.POINTER(Adaptive), vp, vp,
+                                             vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

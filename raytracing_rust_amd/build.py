@@ -20,17 +20,20 @@ RTMI_SRC = [os.path.join(_PKG, "csrc", "rtmi_device.hip"), os.path.join(_PKG, "c
             os.path.join(_PKG, "csrc", "rtmi_alt.hip"), os.path.join(_PKG, "csrc", "rtmi_f64.hip"),
             os.path.join(_PKG, "csrc", "rtmi_adaptive.hip"), os.path.join(_PKG, "csrc", "rtmi_features.hip"),
             os.path.join(_PKG, "csrc", "rtmi_denoise.hip"), os.path.join(_PKG, "csrc", "rtmi_nee.hip"),
-            os.path.join(_PKG, "csrc", "rtmi_env.hip"), os.path.join(_PKG, "csrc", "rtmi_adaptive_nee.hip")]
+            os.path.join(_PKG, "csrc", "rtmi_env.hip"), os.path.join(_PKG, "csrc", "rtmi_adaptive_nee.hip"),
+            os.path.join(_PKG, "csrc", "rtmi_roulette.hip")]
 HOST_SRC = [os.path.join(_PKG, "host", "rt_host.cpp"), os.path.join(_PKG, "host", "rt_host_c.cpp")]
 RTMI_DEPS = RTMI_SRC + sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hpp"))) + sorted(
     glob.glob(os.path.join(_PKG, "csrc", "*.inc"))) + [
     os.path.join(INCLUDE, "rtmi.h"), os.path.join(INCLUDE, "rtmi_f64.h"), os.path.join(INCLUDE, "rtmi_adaptive.h"),
     os.path.join(INCLUDE, "rtmi_features.h"), os.path.join(INCLUDE, "rtmi_denoise.h"), os.path.join(INCLUDE, "rtmi_nee.h"),
-    os.path.join(INCLUDE, "rtmi_env.h"), os.path.join(INCLUDE, "rtmi_adaptive_nee.h"), os.path.join(INCLUDE, "rtmi_math.h")]
+    os.path.join(INCLUDE, "rtmi_env.h"), os.path.join(INCLUDE, "rtmi_adaptive_nee.h"), os.path.join(INCLUDE, "rtmi_roulette.h"),
+    os.path.join(INCLUDE, "rtmi_math.h")]
 HOST_DEPS = HOST_SRC + [os.path.join(_PKG, "host", "rt_host.hpp"), os.path.join(INCLUDE, "rtmi.h"),
                         os.path.join(INCLUDE, "rtmi_f64.h"), os.path.join(INCLUDE, "rtmi_adaptive.h"),
                         os.path.join(INCLUDE, "rtmi_features.h"), os.path.join(INCLUDE, "rtmi_nee.h"),
-                        os.path.join(INCLUDE, "rtmi_env.h"), os.path.join(INCLUDE, "rtmi_adaptive_nee.h")]
+                        os.path.join(INCLUDE, "rtmi_env.h"), os.path.join(INCLUDE, "rtmi_adaptive_nee.h"),
+                        os.path.join(INCLUDE, "rtmi_roulette.h")]
 
 LIBRTMI = os.path.join(LIB_DIR, "librtmi.so")
 LIBHOST = os.path.join(LIB_DIR, "librt_host.so")
@@ -88,15 +91,16 @@ def build_rtmi(force=False, verbose=False):
     common = [_hipcc()] + _COMMON_FLAGS + ["-I" + INCLUDE, '-DRTMI_BUILD_HASH="%s"' % source_hash()]
     if verbose:
         common.insert(1, "-Rpass-analysis=kernel-resource-usage")
-    # ten translation units, compiled side by side: the headline kernels (rtmi_device.hip), the lean instantiations
+    # eleven translation units, compiled side by side: the headline kernels (rtmi_device.hip), the lean instantiations
     # with the default scheduler (rtmi_lean.hip), the two alternative kernels kept for the parity tests (rtmi_alt.hip),
     # the f64 render mode (rtmi_f64.hip), adaptive sampling (rtmi_adaptive.hip), the first-hit features
     # (rtmi_features.hip), the denoiser (rtmi_denoise.hip), next-event estimation (rtmi_nee.hip), environment
-    # lighting (rtmi_env.hip) and adaptive sampling with either (rtmi_adaptive_nee.hip)
+    # lighting (rtmi_env.hip), adaptive sampling with either (rtmi_adaptive_nee.hip) and Russian roulette over all of
+    # them (rtmi_roulette.hip)
     objs, procs = [], []
     for src, flags in ((RTMI_SRC[0], sched), (RTMI_SRC[1], []), (RTMI_SRC[2], sched), (RTMI_SRC[3], []),
                        (RTMI_SRC[4], sched), (RTMI_SRC[5], sched), (RTMI_SRC[6], []), (RTMI_SRC[7], sched),
-                       (RTMI_SRC[8], sched), (RTMI_SRC[9], sched)):
+                       (RTMI_SRC[8], sched), (RTMI_SRC[9], sched), (RTMI_SRC[10], sched)):
         obj = os.path.join(LIB_DIR, os.path.basename(src)[:-4] + ".o")
         procs.append((src, subprocess.Popen(common + flags + extra + ["-c", src, "-o", obj])))
         objs.append(obj)

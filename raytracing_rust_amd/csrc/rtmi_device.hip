@@ -48,6 +48,8 @@
 #include "rtmi_env_launch.hpp"
 #include "rtmi_adaptive_nee.h"
 #include "rtmi_adaptive_nee_launch.hpp"
+#include "rtmi_roulette.h"
+#include "rtmi_roulette_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -88,6 +90,8 @@ struct rtmi_scene {
     size_t texels_bytes = 0;
     unsigned long long *d_sig = nullptr;
     size_t sig_bytes = 0;
+    uint32_t *rr_bounces = nullptr;    // the bounce plane of the roulette entries (include/rtmi_roulette.h), tiled as d_sig
+    size_t rr_bytes = 0;
     rtmi_texel *h_texels = nullptr;    // pinned host mirror of `texels` (hipHostMalloc: the D2H copy runs at link speed)
     size_t h_texel_count = 0;
     rtmi_texel *h_partial = nullptr;   // ... and of the partial images rtmi_partial_image fetches (RTMI_FLAG_PROGRESSIVE)
@@ -583,6 +587,7 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->spill) (void)hipFree(s->spill);
     if (s->texels) (void)hipFree(s->texels);
     if (s->d_sig) (void)hipFree(s->d_sig);
+    if (s->rr_bounces) (void)hipFree(s->rr_bounces);
     if (s->status) (void)hipFree(s->status);
     if (s->h_texels) (void)hipHostFree(s->h_texels);
     if (s->h_partial) (void)hipHostFree(s->h_partial);
@@ -2527,6 +2532,82 @@ extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, c
                               HIP_TRY(rtmi_adaptive_nee_launch_render(fast, nee, true, blocks, stream, s->dev, C, P, tiles, L, E));
                               return RTMI_OK;
                           });
+}
+
+// ---- Russian-roulette path termination (include/rtmi_roulette.h) ------------------------------------------------------
+// Both entries are adaptive sampling's step loop (adaptive_steps) over the per-lane kernels of rtmi_roulette.hip; the
+// fixed render is the single step of ns samples over the list of all tiles (tolerances 0: every tile retires at ns), as
+// the resolve of rtmi_render_nee.  `a` = NULL: the fixed entry.
+static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
+                           const rtmi_roulette *o, const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8,
+                           float *out_stderr, uint32_t *out_spp, uint32_t *out_bounces, rtmi_stats *stats) {
+    const std::string nm = std::string(name) + ": ";
+    int rc = check_params(p_in);
+    if (rc) return rc;
+    if (o->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if (o->min_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "min_depth must be at least 1");
+    if (!std::isfinite(o->q_min) || !(o->q_min > 0.0f && o->q_min <= 1.0f)) return fail(RTMI_ERR_INVALID, nm + "q_min must be in (0, 1]");
+    const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
+    if (nee && env && !(o->env_select_p > 0.0f && o->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
+    if (env && (p_in->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (p_in->flags & RTMI_FLAG_PATH_SIG)
+        return fail(RTMI_ERR_UNSUPPORTED, nm + "PATH_SIG is refused: a roulette path has no counterpart to compare a signature with");
+    const std::string flags_msg = nm + "roulette renders accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK "
+                                       "only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)";
+    const std::string world_msg = nm + "roulette renders render the whole image: tile_world must be 1";
+    if ((rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY, flags_msg.c_str(), world_msg.c_str()))) return rc;
+    if (a && (rc = check_adaptive(p_in, a))) return rc;
+    if (!s) return fail(RTMI_ERR_INVALID, nm + "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (env && !s->has_env) return fail(RTMI_ERR_INVALID, nm + "no environment map attached (rtmi_scene_attach_env)");
+    if (nee && !s->has_lights) return fail(RTMI_ERR_INVALID, nm + "no light table attached (rtmi_scene_attach_lights)");
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = begin_blocking(s))) return rc;
+    const rtmi_render_params &p = *p_in;
+    hipStream_t stream = s->stream;
+    BusyMark busy_mark{s, stream};
+    const rtmi_adaptive fixed{p.ns, 1u, 0.0, 0.0}; // one step of ns samples
+    if (!a) a = &fixed;
+    const uint32_t T = local_tiles_of(&p, 0);
+    const size_t ntex = (size_t)T * 64;
+    if ((rc = adaptive_reserve(s, p, a, T)) || (rc = grow(s, s->rr_bounces, s->rr_bytes, ntex * sizeof(uint32_t)))) return rc;
+    HIP_TRY(hipMemsetAsync(s->rr_bounces, 0, ntex * sizeof(uint32_t), stream));
+
+    DevParams P = dev_params(s, &p);
+    const DevCamera C = dev_camera(cam);
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
+    const rtmi_env_render eo{nee ? 1u : 0u, nee ? o->env_select_p : 1.0f}; // not read, and not checked, without NEE
+    const DevLights L = nee ? dev_lights(s) : DevLights{};
+    const DevEnv E = env ? dev_env_render(s, &eo) : DevEnv{};
+    const DevRoulette R{s->rr_bounces, o->min_depth, o->q_min};
+    rc = adaptive_steps(s, p, a, P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+                        [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                            HIP_TRY(rtmi_roulette_launch_render(fast, nee, env, blocks, stream, s->dev, C, P, tiles, L, E, R));
+                            return RTMI_OK;
+                        });
+    if (rc) return rc;
+    if (out_bounces && (rc = download_untiled<1>(&p, s->rr_bounces, ntex, out_bounces))) return rc;
+    return RTMI_OK;
+}
+
+extern "C" int rtmi_render_roulette(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, const rtmi_roulette *opts,
+                                    float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_bounces,
+                                    rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !cam || !opts) return fail(RTMI_ERR_INVALID, "rtmi_render_roulette: NULL argument");
+    return render_roulette("rtmi_render_roulette", s, cam, p_in, opts, nullptr, out_linear, out_rgb8, out_stderr, nullptr,
+                           out_bounces, stats);
+}
+
+extern "C" int rtmi_render_adaptive_roulette(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
+                                             const rtmi_roulette *opts, const rtmi_adaptive *a, float *out_linear,
+                                             uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_bounces,
+                                             rtmi_stats *stats) {
+    if (!p_in || !cam || !opts || !a) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_roulette: NULL argument");
+    return render_roulette("rtmi_render_adaptive_roulette", s, cam, p_in, opts, a, out_linear, out_rgb8, out_stderr, out_spp,
+                           out_bounces, stats);
 }
 
 extern "C" int rtmi_probe_env(rtmi_scene *s, int op, const float *in, float *out, uint32_t n) {

@@ -10,6 +10,11 @@
 // map is one more light, and a shadow ray toward it counts when it leaves the world.  A textual body
 // and not a force-inlined function: inlining one changed the instruction stream of every existing instantiation (same
 // instructions in another order and register assignment), and those must stay bit-for-bit what they were.
+// RR (rtmi_roulette_kernel, rtmi_roulette.hip; include/rtmi_roulette.h) is a preprocessor switch for that reason: without
+// RTMI_PERLANE_RR this text is what it was.  With it the including function also provides `rr` (DevRoulette) and
+// roulette_survives, RTMI_RR_COUNT() (adds the written path's depth to rr.bounces) and RTMI_RR_END_PATH() (writes the
+// path, counts it and frees the lane): the test follows every scatter in phase B, and a lane whose continuation ends with a
+// shadow ray pending sets rr_end and is written where that shadow ray is handed back.
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
     unsigned long long *prof = prof_lds;
     if (PROF) {
@@ -33,6 +38,9 @@
     typename std::conditional<NEE, RngNee, RngReg>::type g;
     rng_init(g, 0, 0);
     NeeLane ne;
+#ifdef RTMI_PERLANE_RR
+    bool rr_end = false; // the path ends after its pending shadow ray
+#endif
     typename std::conditional<NEE, RngNee, RngReg>::type gn; // NEE: the light-sample stream (swapped with g for a shadow ray)
     if constexpr (NEE) {
         rng_set_stream(g, 0u);
@@ -144,6 +152,9 @@
                             if (ne.env && env_uv(pa.rd, eu, evv, eth)) pa.L = pa.L + ne.c * env_radiance(ev, eu, evv);
                         }
                         pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t;
+#ifdef RTMI_PERLANE_RR
+                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
+#endif
                     }
                 } else { // miss: black background (color.rs:21); the path ends
                     if constexpr (FEATURES) {
@@ -164,6 +175,9 @@
                     } else
                     if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
                     path_end(P, oidx, pa);
+#ifdef RTMI_PERLANE_RR
+                    RTMI_RR_COUNT();
+#endif
                     }
                     if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                     alive = false;
@@ -197,10 +211,25 @@
                     if (was_shadow) { // the light sample is counted: the path's continuation is traced next
                         pa.rd = ne.cont_rd; ne.shadow = false;
                         const auto t = g; g = gn; gn = t;
+#ifdef RTMI_PERLANE_RR
+                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
+#endif
                     } else if (!goes_on) {
                         path_end(P, oidx, pa);
+#ifdef RTMI_PERLANE_RR
+                        RTMI_RR_COUNT();
+#endif
                         if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                         alive = false;
+#ifdef RTMI_PERLANE_RR
+                    } else if (!roulette_survives(rr, g, k0, k1, pa)) { // g is still the path's stream here
+                        if (ne.shadow) { // the vertex's light sample is still traced and counted
+                            rr_end = true;
+                            const auto t = g; g = gn; gn = t;
+                        } else {
+                            RTMI_RR_END_PATH();
+                        }
+#endif
                     } else if (ne.shadow) { // a shadow ray was sampled: trace it with the light-sample stream
                         const auto t = g; g = gn; gn = t;
                     }
@@ -211,9 +240,17 @@
             if (shading && !goes_on) {
                 // absorbed, emitter or depth limit: the path ends
                 path_end(P, oidx, pa);
+#ifdef RTMI_PERLANE_RR
+                RTMI_RR_COUNT();
+#endif
                 if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                 alive = false;
             }
+#ifdef RTMI_PERLANE_RR
+            else if (shading && !roulette_survives(rr, g, k0, k1, pa)) {
+                RTMI_RR_END_PATH();
+            }
+#endif
             }
         }
     }

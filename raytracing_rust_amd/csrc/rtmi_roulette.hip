@@ -1,0 +1,75 @@
+// rtmi_roulette.hip — translation unit of Russian-roulette path termination (include/rtmi_roulette.h): the render kernels
+// and their launcher.  Compiled with the flags of rtmi_device.hip (-ffp-contract=off).
+//
+// The render kernel is the body of rtmi_render_kernel (rtmi_kernel_perlane.inc) with TILE_LIST = true, the NEE / ENV
+// switches of rtmi_adaptive_nee_kernel and the RR switch (RTMI_PERLANE_RR, a preprocessor switch: every other inclusion
+// of the body is the same text as before): the roulette test after a scatter, the end-after-its-shadow-ray flag and the
+// bounce count at every place a path is written.  One instantiation per FAST x estimator serves both entry points: the
+// fixed render runs over the list of all tiles.  No path signatures (SIG = false).  The resolve is adaptive sampling's
+// (rtmi_adaptive_resolve_kernel, rtmi_adaptive.hip).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+
+#include "rtmi.h"
+#include "rtmi_math.h"
+
+#define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
+#include "rtmi_kernels.hpp"
+#include "rtmi_roulette_launch.hpp"
+
+// The roulette test of rtmi_roulette.h, after a scatter has updated pa.T and pa.depth; g is the path's stream-0 state
+// (its sample and pixel words key the stateless stream-4 draw).  false: the continuation ends.
+template <typename RngT>
+__device__ __forceinline__ bool roulette_survives(const DevRoulette &rr, const RngT &g, uint32_t k0, uint32_t k1, Path &pa) {
+    if (pa.depth < rr.min_depth) return true;
+    const float m = fmaxf(fmaxf(pa.T.x, pa.T.y), pa.T.z);
+    if (m == 0.0f) return false;
+    const float q = fminf(fmaxf(m, rr.q_min), 1.0f);
+    if (q < 1.0f) {
+        uint32_t o0, o1, o2, o3;
+        philox(pa.depth, g.sample, g.pixel, 4u, k0, k1, o0, o1, o2, o3);
+        if (!(rtmi_u01(o0) < q)) return false;
+        pa.T = vdiv(pa.T, q);
+    }
+    return true;
+}
+
+#define RTMI_PERLANE_RR 1
+// the two statements the body uses where a roulette kernel writes a path: the bounce count (tiled as the path signatures;
+// a path that never scattered adds nothing) and the whole ending of a path that roulette cut
+#define RTMI_RR_COUNT() \
+    do { if (pa.depth != 0u) atomicAdd(rr.bounces + (size_t)ltile * 64 + (oidx & 63u), pa.depth); } while (0)
+#define RTMI_RR_END_PATH() \
+    do { path_end(P, oidx, pa); RTMI_RR_COUNT(); alive = false; } while (0)
+template <bool FAST, bool NEE, bool ENV>
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_roulette_kernel(DevScene sc, DevCamera cam, DevParams P,
+                                                                            const uint32_t *tiles, DevLights nl, DevEnv ev,
+                                                                            DevRoulette rr) {
+    constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false;
+#include "rtmi_kernel_perlane.inc"
+}
+#undef RTMI_RR_END_PATH
+#undef RTMI_RR_COUNT
+#undef RTMI_PERLANE_RR
+
+hipError_t rtmi_roulette_launch_render(bool fast, bool nee, bool env, uint32_t blocks, hipStream_t stream, const DevScene &sc,
+                                       const DevCamera &cam, const DevParams &P, const uint32_t *tiles, const DevLights &L,
+                                       const DevEnv &E, const DevRoulette &R) {
+    const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
+    if (nee && env) {
+        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, true, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, true, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+    } else if (nee) {
+        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, true, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, true, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+    } else if (env) {
+        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, false, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, false, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+    } else {
+        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, false, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, false, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+    }
+    return hipGetLastError();
+}

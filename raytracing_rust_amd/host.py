@@ -360,6 +360,58 @@ class Scene:
             out["sig"] = sg
         return out
 
+    def _roulette_opts(self, estimator, min_depth, q_min, env_select_p, kw):
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        if not self.uploaded and not getattr(self, "multi_devices", None):
+            self.upload(kw.pop("device", 0))
+        kw.pop("device", None)
+        if estimator in ("nee", "env_nee") and self.uploaded and not getattr(self, "lights_attached", False):
+            self.attach_lights()
+        return abi.Roulette(abi.ROULETTE_ESTIMATORS[estimator], min_depth, q_min, env_select_p)
+
+    def render_roulette(self, cam, nx, ny, ns, estimator="nee", min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32",
+                        **kw):
+        """Russian-roulette path termination (include/rtmi_roulette.h): the paths of render(), each ended after a scatter
+        at depth >= min_depth with probability 1 - q, q = clamp(largest channel of the throughput, q_min, 1), the
+        survivors weighted 1 / q.  estimator: "plain" (render), "nee" (render_nee), "env" (render_env(nee=False)) or
+        "env_nee" (render_env(nee=True, env_select_p)).  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], stderr f32
+        [ny,nx,3], bounces u32 [ny,nx] = the scatters of the pixel's paths, summed, stats).  min_depth > max_depth or
+        q_min = 1 gives the named render bit for bit."""
+        if precision != "f32":
+            raise Unsupported("Russian roulette has no f64 mode")
+        o = self._roulette_opts(estimator, min_depth, q_min, env_select_p, kw)
+        p = default_params(nx, ny, ns, **kw)
+        lin = np.zeros((ny, nx, 3), np.float32)
+        rgb = np.zeros((ny, nx, 3), np.uint8)
+        se = np.zeros((ny, nx, 3), np.float32)
+        bn = np.zeros((ny, nx), np.uint32)
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_roulette(self.h, cam.h, C.byref(p), C.byref(o), lin.ctypes.data, rgb.ctypes.data,
+                                                            se.ctypes.data, bn.ctypes.data, C.byref(st)))
+        return {"linear": lin, "rgb8": rgb, "stderr": se, "bounces": bn, "stats": _stats(st)}
+
+    def render_adaptive_roulette(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, estimator="nee",
+                                 min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32", **kw):
+        """render_roulette under the noise target of render_adaptive (ns is the cap).  Returns render_roulette's dict plus
+        spp u32 [ny,nx]; a tile that stops at n samples is bit for bit, bounces included, that tile of
+        render_roulette(ns=n)."""
+        if precision != "f32":
+            raise Unsupported("Russian roulette has no f64 mode")
+        o = self._roulette_opts(estimator, min_depth, q_min, env_select_p, kw)
+        p = default_params(nx, ny, ns, **kw)
+        a = abi.Adaptive(min_spp, step_spp, abs_tol, rel_tol)
+        lin = np.zeros((ny, nx, 3), np.float32)
+        rgb = np.zeros((ny, nx, 3), np.uint8)
+        se = np.zeros((ny, nx, 3), np.float32)
+        spp = np.zeros((ny, nx), np.uint32)
+        bn = np.zeros((ny, nx), np.uint32)
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_render_adaptive_roulette(self.h, cam.h, C.byref(p), C.byref(o), C.byref(a),
+                                                                     lin.ctypes.data, rgb.ctypes.data, se.ctypes.data,
+                                                                     spp.ctypes.data, bn.ctypes.data, C.byref(st)))
+        return {"linear": lin, "rgb8": rgb, "stderr": se, "spp": spp, "bounces": bn, "stats": _stats(st)}
+
     def render_denoised(self, cam, nx, ny, ns, denoise=None, nee=False, env=False, **kw):
         """A render and its denoised image: render_adaptive(min_spp=ns, step_spp=1) (render()'s image plus its standard
         errors), render_features with the same ns and keywords, then denoise() of the three on the scene's device.

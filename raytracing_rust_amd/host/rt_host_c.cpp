@@ -10,6 +10,7 @@
 #include "rt_host.hpp"
 #include "rtmi_env.h"
 #include "rtmi_adaptive_nee.h"
+#include "rtmi_roulette.h"
 
 using namespace rt;
 
@@ -353,6 +354,37 @@ RTH_API int rth_render_adaptive_env(void *lowered, void *cam, const rtmi_render_
         const int rc = rtmi_render_adaptive_env(o->dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
         if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_env: ") + rtmi_last_error());
         if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+// Russian-roulette path termination (include/rtmi_roulette.h); RTH_UNSUPPORTED for what the two entries do not support, a
+// multi-GPU handle among it
+RTH_API int rth_render_roulette(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_roulette *opts, float *out_linear,
+                                uint8_t *out_rgb8, float *out_stderr, uint32_t *out_bounces, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi) throw Unsupported("rtmi_render_roulette: multi-GPU handles have no roulette entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_roulette(o->dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_bounces, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_roulette: ") + rtmi_last_error());
+        if (rc) throw std::runtime_error(std::string("rtmi_render_roulette: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        return RTH_OK;
+    });
+}
+RTH_API int rth_render_adaptive_roulette(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_roulette *opts,
+                                         const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
+                                         uint32_t *out_spp, uint32_t *out_bounces, rtmi_stats *stats) {
+    return guard([&] {
+        Obj *o = LOW(lowered);
+        if (!o->dev && o->multi)
+            throw Unsupported("rtmi_render_adaptive_roulette: multi-GPU handles have no roulette entry (RTMI_ERR_UNSUPPORTED)");
+        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = rtmi_render_adaptive_roulette(o->dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, out_bounces, stats);
+        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_roulette: ") + rtmi_last_error());
+        if (rc)
+            throw std::runtime_error(std::string("rtmi_render_adaptive_roulette: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
         return RTH_OK;
     });
 }

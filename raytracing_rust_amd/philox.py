@@ -9,6 +9,7 @@ which is not reproducible.  This build replaces it with keyed counter streams:
     stream_id 1: scene construction inside the host library    [BVH axes, Perlin tables]
     stream_id 2: scene construction in the scene builders      [positions, albedos]
     stream_id 3: next-event estimation's light samples         [light, point, shadow-ray media; include/rtmi_nee.h]
+    stream_id 4: Russian roulette, stateless: word 0 of counter (depth, sample, pixel, 4) [include/rtmi_roulette.h]
 
 The n-th draw of a stream is word n % 4 of block n // 4; a uniform is the top 24 bits
 of the word times 2^-24 (exact in fp32 and f64).
@@ -60,6 +61,12 @@ class Stream:
     def range(self, n):
         """The build's `rng.gen_range(0..n)`."""
         return (self.u32() * n) >> 32
+
+
+def roulette_word(seed, depth, sample, pixel):
+    """The word of the Russian-roulette test made at `depth` of path (sample, pixel): word 0 of block `depth` of
+    stream_id 4 (include/rtmi_roulette.h); one evaluation per test, no sequential state."""
+    return philox4x32_10([depth, sample, pixel, 4], [seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF])[0]
 
 
 class SceneRng(Stream):

@@ -1,0 +1,177 @@
+"""The public interface of Russian-roulette path termination (include/rtmi_roulette.h), without a GPU.
+
+* the header compiles as C99 -pedantic;
+* librtmi.so exports exactly the functions the header declares, abi.py lists them, sys.rs and the host library declare
+  them, and the list is disjoint from every other list;
+* every bad argument is refused before any device work, with its name in the message: RTMI_ERR_INVALID for bad values,
+  SKY with the map estimators and a NULL scene, RTMI_ERR_UNSUPPORTED for PATH_SIG, the other flags and the tile split."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import pytest
+
+from raytracing_rust_amd import abi
+from raytracing_rust_amd.host import default_params
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+HEADER = os.path.join(INCLUDE, "rtmi_roulette.h")
+FORMS = ["fixed", "adaptive"]
+ESTIMATORS = [0, 1, 2, 3]
+
+
+def test_header_is_c99(tmp_path):
+    src = tmp_path / "c99.c"
+    src.write_text('#include "rtmi_roulette.h"\n'
+                   "int main(void) { rtmi_roulette o = {RTMI_ROULETTE_ENV_NEE, 3u, 0.05f, 0.5f}; rtmi_adaptive a = {2u, 1u, 0.0, 0.0};\n"
+                   "  (void)o; (void)a; (void)&rtmi_render_roulette; (void)&rtmi_render_adaptive_roulette;\n"
+                   "  return sizeof(rtmi_roulette) == 16 ? 0 : 1; }\n")
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-o", str(tmp_path / "c99")],
+                   check=True)
+    subprocess.run([str(tmp_path / "c99")], check=True)
+
+
+def test_exports_and_declarations_agree():
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
+    assert declared == sorted(abi.RTMI_ROULETTE_SYMBOLS) == ["rtmi_render_adaptive_roulette", "rtmi_render_roulette"]
+    lib = abi.load_rtmi()
+    for n in declared:
+        assert hasattr(lib, n), n
+    # nothing else of the family is exported
+    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
+    exported = sorted(set(re.findall(r"\b(rtmi_\w*roulette\w*)\b", out)))
+    assert exported == declared, exported
+    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
+    for n in declared:
+        assert re.search(r"pub fn %s\(" % n, sysrs), n
+    body = re.search(r"pub struct RtmiRoulette \{(.*?)\n\}", sysrs, re.S).group(1)
+    fields = re.findall(r"pub (\w+): (\w+),", body)
+    assert fields == [("estimator", "u32"), ("min_depth", "u32"), ("q_min", "f32"), ("env_select_p", "f32")]
+    assert [n for n, _ in abi.Roulette._fields_] == [n for n, _ in fields] and C.sizeof(abi.Roulette) == 16
+    for name, val in (("PLAIN", 0), ("NEE", 1), ("ENV", 2), ("ENV_NEE", 3)):
+        assert "RTMI_ROULETTE_%s: u32 = %d" % (name, val) in sysrs
+        assert re.search(r"#define RTMI_ROULETTE_%s %du\b" % (name, val), open(HEADER).read())
+        assert getattr(abi, "RTMI_ROULETTE_" + name) == val
+    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) |
+              set(abi.RTMI_FEATURES_SYMBOLS) | set(abi.RTMI_DENOISE_SYMBOLS) | set(abi.RTMI_NEE_SYMBOLS) |
+              set(abi.RTMI_ENV_SYMBOLS) | set(abi.RTMI_ADAPTIVE_NEE_SYMBOLS))
+    assert not set(declared) & others
+    host = abi.load_host()
+    for n in ("rth_render_roulette", "rth_render_adaptive_roulette"):
+        assert hasattr(host, n), n
+
+
+def _call(form, params=None, opts=None, adaptive=None, scene=None, cam=True, null_opts=False, null_params=False,
+          null_adaptive=False):
+    lib = abi.load_rtmi()
+    p = default_params(32, 24, 16) if params is None else params
+    o = abi.Roulette(abi.RTMI_ROULETTE_NEE, 3, 0.05, 0.5) if opts is None else opts
+    a = abi.Adaptive(4, 4, 0.0, 0.0) if adaptive is None else adaptive
+    c = abi.Camera()
+    pc, oc, cc = (None if null_params else C.byref(p)), (None if null_opts else C.byref(o)), (C.byref(c) if cam else None)
+    if form == "fixed":
+        rc = lib.rtmi_render_roulette(scene, cc, pc, oc, None, None, None, None, None)
+    else:
+        rc = lib.rtmi_render_adaptive_roulette(scene, cc, pc, oc, None if null_adaptive else C.byref(a), None, None, None, None,
+                                               None, None)
+    return rc, (lib.rtmi_last_error() or b"").decode()
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_null_arguments_and_bad_params_are_invalid(form):
+    rc, msg = _call(form)
+    assert rc == 1 and "scene" in msg, msg  # every value valid: the NULL scene is what is refused
+    for kw in ({"cam": False}, {"null_opts": True}, {"null_params": True}):
+        rc, msg = _call(form, **kw)
+        assert rc == 1 and "NULL" in msg, (kw, msg)
+    if form == "adaptive":
+        rc, msg = _call(form, null_adaptive=True)
+        assert rc == 1 and "NULL" in msg, msg
+    assert _call(form, params=default_params(0, 24, 16))[0] == 1
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("opts, what", [
+    (abi.Roulette(4, 3, 0.05, 0.5), "estimator"),
+    (abi.Roulette(0xffffffff, 3, 0.05, 0.5), "estimator"),
+    (abi.Roulette(1, 0, 0.05, 0.5), "min_depth"),
+    (abi.Roulette(0, 3, 0.0, 0.5), "q_min"),
+    (abi.Roulette(1, 3, -0.1, 0.5), "q_min"),
+    (abi.Roulette(2, 3, 1.0000001, 0.5), "q_min"),
+    (abi.Roulette(3, 3, float("nan"), 0.5), "q_min"),
+    (abi.Roulette(1, 3, float("inf"), 0.5), "q_min"),
+    (abi.Roulette(3, 3, 0.05, 0.0), "env_select_p"),
+    (abi.Roulette(3, 3, 0.05, -0.5), "env_select_p"),
+    (abi.Roulette(3, 3, 0.05, 1.0000001), "env_select_p"),
+    (abi.Roulette(3, 3, 0.05, float("nan")), "env_select_p"),
+    (abi.Roulette(3, 3, 0.05, float("inf")), "env_select_p"),
+])
+def test_bad_options_are_invalid_without_a_device(form, opts, what):
+    rc, msg = _call(form, opts=opts)
+    assert rc == 1 and what in msg, msg
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_valid_options_reach_the_scene_check(form):
+    # env_select_p is read by ENV_NEE only; min_depth above max_depth and q_min = 1 are valid (no test, no draw)
+    for o in (abi.Roulette(0, 1, 1.0, 0.0), abi.Roulette(1, 51, 0.05, float("nan")), abi.Roulette(2, 1000000, 1e-6, -1.0),
+              abi.Roulette(3, 3, 0.5, 1.0), abi.Roulette(3, 1, 1.0, 1e-6)):
+        rc, msg = _call(form, opts=o)
+        assert rc == 1 and "scene" in msg, (o.estimator, o.min_depth, o.q_min, o.env_select_p, msg)
+
+
+@pytest.mark.parametrize("adaptive, what", [
+    (abi.Adaptive(1, 4, 0.0, 0.0), "min_spp"), (abi.Adaptive(17, 4, 0.0, 0.0), "min_spp"), (abi.Adaptive(4, 0, 0.0, 0.0), "step_spp"),
+    (abi.Adaptive(4, 4, -1e-3, 0.0), "abs_tol"), (abi.Adaptive(4, 4, 0.0, float("nan")), "rel_tol"),
+])
+def test_bad_adaptive_arguments_are_invalid(adaptive, what):
+    rc, msg = _call("adaptive", adaptive=adaptive)
+    assert rc == 1 and what in msg, msg
+    rc, msg = _call("fixed", adaptive=adaptive)  # the fixed entry takes no noise target
+    assert rc == 1 and "scene" in msg, msg
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("est", ESTIMATORS)
+def test_sky_is_refused_with_the_map_estimators_only(form, est):
+    rc, msg = _call(form, opts=abi.Roulette(est, 3, 0.05, 0.5), params=default_params(32, 24, 16, flags=abi.RTMI_FLAG_SKY))
+    if est >= 2:
+        assert rc == 1 and "SKY" in msg, msg
+    else:
+        assert rc == 1 and "scene" in msg, msg
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("est", ESTIMATORS)
+def test_path_sig_is_unsupported(form, est):
+    rc, msg = _call(form, opts=abi.Roulette(est, 3, 0.05, 0.5),
+                    params=default_params(32, 24, 16, flags=abi.RTMI_FLAG_PATH_SIG | abi.RTMI_FLAG_FAST_CULL))
+    assert rc == 2 and "PATH_SIG" in msg, msg
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("flag", [abi.RTMI_FLAG_PROFILE, abi.RTMI_FLAG_ASYNC, abi.RTMI_FLAG_BLOCK_COOP, abi.RTMI_FLAG_PROGRESSIVE,
+                                  abi.RTMI_FLAG_TEST_OVERFLOW, 1 << 11, 1 << 20, 3 << 8])
+def test_unsupported_flags(form, flag):
+    rc, msg = _call(form, params=default_params(32, 24, 16, flags=flag | abi.RTMI_FLAG_FAST_CULL))
+    assert rc == 2 and "flags" in msg, msg
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_tile_split_is_unsupported(form):
+    for rank in (0, 1):
+        rc, msg = _call(form, params=default_params(32, 24, 16, tile_rank=rank, tile_world=2))
+        assert rc == 2 and "tile_world" in msg, msg
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_accepted_flags_reach_the_scene_check(form):
+    accepted = (abi.RTMI_FLAG_FAST_CULL | abi.RTMI_FLAG_SYNC | abi.RTMI_FLAG_REF_TREE | abi.RTMI_FLAG_FACE_FORWARD |
+                abi.RTMI_FLAG_UV_BOOK)
+    for est in ESTIMATORS:
+        for flags in (accepted | (abi.RTMI_FLAG_SKY if est < 2 else 0), 0, abi.RTMI_FLAG_SYNC, abi.RTMI_FLAG_REF_TREE):
+            rc, msg = _call(form, opts=abi.Roulette(est, 3, 0.05, 0.5), params=default_params(32, 24, 16, flags=flags))
+            assert rc == 1 and "scene" in msg, (est, flags, msg)
