@@ -16,24 +16,18 @@ _ROOT = os.path.dirname(_PKG)
 LIB_DIR = os.environ.get("RTMI_LIB_DIR") or os.path.join(_PKG, "lib")
 INCLUDE = os.path.join(_ROOT, "include")
 
-RTMI_SRC = [os.path.join(_PKG, "csrc", "rtmi_device.hip"), os.path.join(_PKG, "csrc", "rtmi_lean.hip"),
-            os.path.join(_PKG, "csrc", "rtmi_alt.hip"), os.path.join(_PKG, "csrc", "rtmi_f64.hip"),
-            os.path.join(_PKG, "csrc", "rtmi_adaptive.hip"), os.path.join(_PKG, "csrc", "rtmi_features.hip"),
-            os.path.join(_PKG, "csrc", "rtmi_denoise.hip"), os.path.join(_PKG, "csrc", "rtmi_nee.hip"),
-            os.path.join(_PKG, "csrc", "rtmi_env.hip"), os.path.join(_PKG, "csrc", "rtmi_adaptive_nee.hip"),
-            os.path.join(_PKG, "csrc", "rtmi_roulette.hip")]
+# The translation units of librtmi.so, compiled side by side, and whether each takes the iterative-maxocc scheduler
+# (build_rtmi): the headline kernels and the C ABI (rtmi_device), the lean instantiations (rtmi_lean), the two alternative
+# kernels kept for the parity tests (rtmi_alt), then one unit per render mode, named after its header in include/.
+_RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_alt.hip", True), ("rtmi_f64.hip", False),
+               ("rtmi_adaptive.hip", True), ("rtmi_features.hip", True), ("rtmi_denoise.hip", False), ("rtmi_nee.hip", True),
+               ("rtmi_env.hip", True), ("rtmi_adaptive_nee.hip", True), ("rtmi_roulette.hip", True))
+_PUBLIC_HEADERS = sorted(glob.glob(os.path.join(INCLUDE, "*.h")))
+RTMI_SRC = [os.path.join(_PKG, "csrc", name) for name, _ in _RTMI_UNITS]
 HOST_SRC = [os.path.join(_PKG, "host", "rt_host.cpp"), os.path.join(_PKG, "host", "rt_host_c.cpp")]
 RTMI_DEPS = RTMI_SRC + sorted(glob.glob(os.path.join(_PKG, "csrc", "*.hpp"))) + sorted(
-    glob.glob(os.path.join(_PKG, "csrc", "*.inc"))) + [
-    os.path.join(INCLUDE, "rtmi.h"), os.path.join(INCLUDE, "rtmi_f64.h"), os.path.join(INCLUDE, "rtmi_adaptive.h"),
-    os.path.join(INCLUDE, "rtmi_features.h"), os.path.join(INCLUDE, "rtmi_denoise.h"), os.path.join(INCLUDE, "rtmi_nee.h"),
-    os.path.join(INCLUDE, "rtmi_env.h"), os.path.join(INCLUDE, "rtmi_adaptive_nee.h"), os.path.join(INCLUDE, "rtmi_roulette.h"),
-    os.path.join(INCLUDE, "rtmi_math.h")]
-HOST_DEPS = HOST_SRC + [os.path.join(_PKG, "host", "rt_host.hpp"), os.path.join(INCLUDE, "rtmi.h"),
-                        os.path.join(INCLUDE, "rtmi_f64.h"), os.path.join(INCLUDE, "rtmi_adaptive.h"),
-                        os.path.join(INCLUDE, "rtmi_features.h"), os.path.join(INCLUDE, "rtmi_nee.h"),
-                        os.path.join(INCLUDE, "rtmi_env.h"), os.path.join(INCLUDE, "rtmi_adaptive_nee.h"),
-                        os.path.join(INCLUDE, "rtmi_roulette.h")]
+    glob.glob(os.path.join(_PKG, "csrc", "*.inc"))) + _PUBLIC_HEADERS
+HOST_DEPS = HOST_SRC + [os.path.join(_PKG, "host", "rt_host.hpp")] + _PUBLIC_HEADERS
 
 LIBRTMI = os.path.join(LIB_DIR, "librtmi.so")
 LIBHOST = os.path.join(LIB_DIR, "librt_host.so")
@@ -91,16 +85,9 @@ def build_rtmi(force=False, verbose=False):
     common = [_hipcc()] + _COMMON_FLAGS + ["-I" + INCLUDE, '-DRTMI_BUILD_HASH="%s"' % source_hash()]
     if verbose:
         common.insert(1, "-Rpass-analysis=kernel-resource-usage")
-    # eleven translation units, compiled side by side: the headline kernels (rtmi_device.hip), the lean instantiations
-    # with the default scheduler (rtmi_lean.hip), the two alternative kernels kept for the parity tests (rtmi_alt.hip),
-    # the f64 render mode (rtmi_f64.hip), adaptive sampling (rtmi_adaptive.hip), the first-hit features
-    # (rtmi_features.hip), the denoiser (rtmi_denoise.hip), next-event estimation (rtmi_nee.hip), environment
-    # lighting (rtmi_env.hip), adaptive sampling with either (rtmi_adaptive_nee.hip) and Russian roulette over all of
-    # them (rtmi_roulette.hip)
     objs, procs = [], []
-    for src, flags in ((RTMI_SRC[0], sched), (RTMI_SRC[1], []), (RTMI_SRC[2], sched), (RTMI_SRC[3], []),
-                       (RTMI_SRC[4], sched), (RTMI_SRC[5], sched), (RTMI_SRC[6], []), (RTMI_SRC[7], sched),
-                       (RTMI_SRC[8], sched), (RTMI_SRC[9], sched), (RTMI_SRC[10], sched)):
+    for src, (_, maxocc) in zip(RTMI_SRC, _RTMI_UNITS):
+        flags = sched if maxocc else []
         obj = os.path.join(LIB_DIR, os.path.basename(src)[:-4] + ".o")
         procs.append((src, subprocess.Popen(common + flags + extra + ["-c", src, "-o", obj])))
         objs.append(obj)

@@ -17,7 +17,7 @@
 
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
-#include "rtmi_adaptive_nee_launch.hpp"
+#include "rtmi_light_launch.hpp"
 
 template <bool FAST, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_adaptive_nee_kernel(DevScene sc, DevCamera cam, DevParams P,
@@ -30,17 +30,11 @@ hipError_t rtmi_adaptive_nee_launch_render(bool fast, bool nee, bool env, uint32
                                            const DevCamera &cam, const DevParams &P, const uint32_t *tiles, const DevLights &L,
                                            const DevEnv &E) {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
-    if (nee && env) {
-        if (fast) hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<true, true, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
-        else hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<false, true, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
-    } else if (nee) {
-        if (fast) hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<true, true, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
-        else hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<false, true, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
-    } else if (env) {
-        if (fast) hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<true, false, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
-        else hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<false, false, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
-    } else {
-        return hipErrorInvalidValue; // the plain estimator is rtmi_adaptive_kernel's
-    }
-    return hipGetLastError();
+    return rtmi_with_bools([&](auto NEE, auto ENV, auto FAST) {
+        if constexpr (!NEE() && !ENV()) return hipErrorInvalidValue; // the plain estimator is rtmi_adaptive_kernel's
+        else {
+            hipLaunchKernelGGL((rtmi_adaptive_nee_kernel<FAST(), NEE(), ENV()>), grid, block, 0, stream, sc, cam, P, tiles, L, E);
+            return hipGetLastError();
+        }
+    }, nee, env, fast);
 }

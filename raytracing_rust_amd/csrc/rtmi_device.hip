@@ -43,13 +43,10 @@
 #include "rtmi_features.h"
 #include "rtmi_features_launch.hpp"
 #include "rtmi_nee.h"
-#include "rtmi_nee_launch.hpp"
 #include "rtmi_env.h"
-#include "rtmi_env_launch.hpp"
 #include "rtmi_adaptive_nee.h"
-#include "rtmi_adaptive_nee_launch.hpp"
 #include "rtmi_roulette.h"
-#include "rtmi_roulette_launch.hpp"
+#include "rtmi_light_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -625,7 +622,7 @@ static int check_params(const rtmi_render_params *p) {
 struct BusyMark {
     rtmi_scene *s;
     hipStream_t st;
-    ~BusyMark() { if (hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; }
+    ~BusyMark() { if (s && hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; } // s = NULL: no call begun
 };
 
 // Grow-only device buffer of the handle: reallocated when a call needs more than `have` bytes.  A render of this handle
@@ -2005,6 +2002,148 @@ static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
 }
 
+// ---- one host path for the estimators of the whole-image modes -----------------------------------------------------------
+// The plain estimator, next-event estimation (rtmi_nee.h), environment lighting (rtmi_env.h) or both, in a fixed render, in
+// adaptive sampling's step loop (rtmi_adaptive.h, rtmi_adaptive_nee.h) and under Russian roulette (rtmi_roulette.h).  The
+// entry points differ in their argument checks and in the kernel they launch; what surrounds the launches is here.
+
+// an entry point's estimator: what it reads of the handle, and the entry's own words where the handle lacks it
+struct Estimator {
+    const char *name;       // the entry point, prefix of the attach refusals
+    bool nee, env;          // reads the light table (rtmi_scene_attach_lights) / the map (rtmi_scene_attach_env)
+    float env_select_p;     // rtmi_env_render's, read with the map only
+    const char *null_scene; // the refusal of a NULL handle
+    const char *no_lights;  // the refusal of a handle without the light table, after "name: "
+};
+
+// the checks of rtmi_env_render-style options, in `name`'s words
+static int check_env_opts(const char *name, const rtmi_env_render *o) {
+    if (o->nee > 1u) return fail(RTMI_ERR_INVALID, std::string(name) + ": nee must be 0 or 1");
+    if (!(o->env_select_p > 0.0f && o->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": env_select_p must be in (0, 1]");
+    return RTMI_OK;
+}
+static int refuse_sky(const char *name, const rtmi_render_params *p) {
+    if (p->flags & RTMI_FLAG_SKY)
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": RTMI_FLAG_SKY is refused, the map replaces the sky");
+    return RTMI_OK;
+}
+
+static DevEnv dev_env(const rtmi_scene *s, float p_env) {
+    const size_t H = s->env_h, n = (size_t)s->env_w * s->env_h;
+    DevEnv E;
+    E.texels = s->env_texels;
+    E.row_cdf = s->env_tables; E.row_p = s->env_tables + H; E.col_cdf = s->env_tables + 2 * H; E.col_p = s->env_tables + 2 * H + n;
+    E.w = s->env_w; E.h = s->env_h;
+    E.p_env = p_env;
+    return E;
+}
+// The light table and the map as the kernels of this estimator read them (the caller has checked that they are attached);
+// empty where it reads none.  p_env: the map's share of the light samples (rtmi_env.h).
+static void dev_lighting(const rtmi_scene *s, bool nee, bool env, float env_select_p, DevLights &L, DevEnv &E) {
+    L = DevLights{};
+    E = DevEnv{};
+    if (nee) { L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n; }
+    if (env) E = dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? env_select_p : 1.0f));
+}
+
+// a blocking call's hold on the handle from begin_call to its return, and the kernel arguments of its estimator
+struct RenderCall {
+    std::unique_lock<std::mutex> lock;
+    BusyMark busy{nullptr, nullptr};
+    DevParams P;
+    DevCamera C;
+    DevLights L;
+    DevEnv E;
+    bool fast = false;
+};
+
+// The end of an entry point's checks and the start of its device work, in this order: the handle, its lock, what the
+// estimator needs attached, then the device, no earlier render of the handle running, the busy mark.
+static int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
+    if (!s) return fail(RTMI_ERR_INVALID, m.null_scene);
+    c.lock = std::unique_lock<std::mutex>(s->mu);
+    if (m.env && !s->has_env)
+        return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no environment map attached (rtmi_scene_attach_env)");
+    if (m.nee && !s->has_lights) return fail(RTMI_ERR_INVALID, std::string(m.name) + ": " + m.no_lights);
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = begin_blocking(s)) return rc;
+    c.busy.s = s; c.busy.st = s->stream;
+    return RTMI_OK;
+}
+static void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, const rtmi_camera *cam,
+                        const rtmi_render_params &p) {
+    c.P = dev_params(s, &p);
+    c.C = dev_camera(cam);
+    c.fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
+    dev_lighting(s, m.nee, m.env, m.env_select_p, c.L, c.E);
+}
+// begin_call, adaptive sampling's buffers and the kernel arguments: what precedes adaptive_steps
+static int begin_adaptive(RenderCall &c, const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
+                          const rtmi_adaptive *a) {
+    int rc;
+    if ((rc = begin_call(c, m, s)) || (rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
+    kernel_args(c, m, s, cam, p);
+    return RTMI_OK;
+}
+
+// The fixed-sample-count render of rtmi_render_nee and rtmi_render_env: the estimator's per-lane kernel (TILE_LIST = false)
+// in passes of the render's plan; adaptive sampling's resolve over the list of all tiles carries sum, m and M2 between
+// passes and writes texels and standard errors after the last one.  launch(c, sig, blocks) enqueues the render kernel on
+// s->stream for the pass fields of c.P and returns an RTMI code.  The caller has checked every argument.
+template <typename Launch>
+static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p, float *out_linear,
+                        uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats, Launch &&launch) {
+    RenderCall c;
+    int rc;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    const uint32_t T = local_tiles_of(&p, 0);
+    const size_t ntex = (size_t)T * 64;
+    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
+        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        return rc;
+    uint32_t chunk_spp = 0, pass_ns = 0;
+    if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
+
+    kernel_args(c, m, s, cam, p);
+    DevParams &P = c.P;
+    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+    const bool sig = out_path_sig != nullptr;
+    P.path_sig = sig ? s->d_sig : nullptr;
+    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
+    s->last_kernel = RTMI_KERNEL_PERLANE;
+
+    if ((rc = begin_passes(s, stream))) return rc;
+    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
+    if ((rc = list_all_tiles(s, T, stream))) return rc;
+    AdaptiveResolve A;
+    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
+    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
+    PassCounts counts;
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
+        if (int lrc = launch(c, sig, blocks)) return lrc;
+        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
+        A.first = first ? 1 : 0;
+        A.decide = last ? 1 : 0;
+        if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
+        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
+        return RTMI_OK;
+    });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    rtmi_scene *one[1] = {s};
+    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
+    if ((rc = check_overflow(s))) return rc;
+    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
+    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
+    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
 extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
                                     const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
                                     uint32_t *out_spp, rtmi_stats *stats) {
@@ -2017,19 +2156,13 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
                                "adaptive sampling renders the whole image: tile_world must be 1");
     if (rc) return rc;
     if ((rc = check_adaptive(p_in, a))) return rc;
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
     const rtmi_render_params &p = *p_in;
-    hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
-    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
-
-    DevParams P = dev_params(s, &p);
-    const DevCamera C = dev_camera(cam);
+    const Estimator m{"rtmi_render_adaptive", false, false, 1.0f, "scene is NULL", ""};
+    RenderCall c;
+    if ((rc = begin_adaptive(c, m, s, cam, p, a))) return rc;
+    DevParams &P = c.P;
     // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
+    const bool fast = c.fast, sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
     const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
     const bool coop = fast && !sync && coop_ok && !inst;
@@ -2040,7 +2173,8 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
                                                        (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
     return adaptive_steps(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr,
                           out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
-                              HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, stream, s->dev, C, P, tiles));
+                              HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream, s->dev, c.C, P,
+                                                                  tiles));
                               return RTMI_OK;
                           });
 }
@@ -2254,15 +2388,7 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     return RTMI_OK;
 }
 
-// the attached light table as the NEE kernels read it (the caller has checked s->has_lights)
-static DevLights dev_lights(const rtmi_scene *s) {
-    DevLights L;
-    L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n;
-    return L;
-}
-
-// The per-lane NEE kernel (rtmi_nee.hip) in passes of the render's plan; adaptive sampling's resolve over the list of all
-// tiles carries sum, m and M2 between passes and writes texels and standard errors after the last one.
+// The per-lane NEE kernel (rtmi_nee.hip) in render_fixed.
 extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
                                uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     // every argument check comes before the first use of the device
@@ -2273,59 +2399,13 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
                                "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                                "NEE renders the whole image: tile_world must be 1");
     if (rc) return rc;
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (!s->has_lights) return fail(RTMI_ERR_INVALID, "rtmi_render_nee: no light table attached (rtmi_scene_attach_lights)");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    const rtmi_render_params &p = *p_in;
-    hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
-    const uint32_t T = local_tiles_of(&p, 0);
-    const size_t ntex = (size_t)T * 64;
-    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
-        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
-        return rc;
-    uint32_t chunk_spp = 0, pass_ns = 0;
-    if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
-
-    DevParams P = dev_params(s, &p);
-    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
-    const DevCamera C = dev_camera(cam);
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
-    P.path_sig = sig ? s->d_sig : nullptr;
-    const DevLights L = dev_lights(s);
-    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
-    s->last_kernel = RTMI_KERNEL_PERLANE;
-
-    if ((rc = begin_passes(s, stream))) return rc;
-    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
-    if ((rc = list_all_tiles(s, T, stream))) return rc;
-    AdaptiveResolve A;
-    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
-    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
-    A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
-    PassCounts counts;
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
-    rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
-        HIP_TRY(rtmi_nee_launch_render(fast, sig, blocks, stream, s->dev, C, P, L));
-        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
-        A.first = first ? 1 : 0;
-        A.decide = last ? 1 : 0;
-        if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
-        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
-        return RTMI_OK;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
-    rtmi_scene *one[1] = {s};
-    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
-    if ((rc = check_overflow(s))) return rc;
-    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
-    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
-    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
-    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+    const Estimator m{"rtmi_render_nee", true, false, 1.0f, "scene is NULL",
+                      "no light table attached (rtmi_scene_attach_lights)"};
+    return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
+                        [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
+                            HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L));
+                            return RTMI_OK;
+                        });
 }
 
 // ---- environment lighting (include/rtmi_env.h) ------------------------------------------------------------------------
@@ -2359,105 +2439,47 @@ extern "C" int rtmi_scene_attach_env(rtmi_scene *s, const rtmi_env_map *map) {
     return RTMI_OK;
 }
 
-static DevEnv dev_env(const rtmi_scene *s, float p_env) {
-    const size_t H = s->env_h, n = (size_t)s->env_w * s->env_h;
-    DevEnv E;
-    E.texels = s->env_texels;
-    E.row_cdf = s->env_tables; E.row_p = s->env_tables + H; E.col_cdf = s->env_tables + 2 * H; E.col_p = s->env_tables + 2 * H + n;
-    E.w = s->env_w; E.h = s->env_h;
-    E.p_env = p_env;
-    return E;
-}
-// the map of an environment render with these options; p_env: the map's share of the light samples (rtmi_env.h)
-static DevEnv dev_env_render(const rtmi_scene *s, const rtmi_env_render *opts) {
-    return dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? opts->env_select_p : 1.0f));
-}
-// the light table of an environment render: empty unless nee = 1
-static DevLights dev_env_lights(const rtmi_scene *s, bool nee) {
-    return nee ? dev_lights(s) : DevLights{};
-}
-
-// The per-lane environment kernel (rtmi_env.hip) in passes of the render's plan; adaptive sampling's resolve over the list
-// of all tiles, as rtmi_render_nee.
+// The per-lane environment kernel (rtmi_env.hip) in render_fixed.
 extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, const rtmi_env_render *opts,
                                float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     // every argument check comes before the first use of the device
     if (!p_in || !cam || !opts) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (p_in->flags & RTMI_FLAG_SKY) return fail(RTMI_ERR_INVALID, "rtmi_render_env: RTMI_FLAG_SKY is refused, the map replaces the sky");
+    const char *name = "rtmi_render_env";
+    int rc;
+    if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in))) return rc;
     rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK |
                                      RTMI_FLAG_PATH_SIG,
                            "environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD, UV_BOOK and PATH_SIG "
                            "only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                            "environment renders render the whole image: tile_world must be 1");
-    if (rc) return rc;
-    if (opts->nee > 1u) return fail(RTMI_ERR_INVALID, "rtmi_render_env: nee must be 0 or 1");
-    if (!(opts->env_select_p > 0.0f && opts->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, "rtmi_render_env: env_select_p must be in (0, 1]");
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (!s->has_env) return fail(RTMI_ERR_INVALID, "rtmi_render_env: no environment map attached (rtmi_scene_attach_env)");
+    if (rc || (rc = check_env_opts(name, opts))) return rc;
     const bool nee = opts->nee != 0u;
-    if (nee && !s->has_lights)
-        return fail(RTMI_ERR_INVALID, "rtmi_render_env: nee = 1 needs the light table (rtmi_scene_attach_lights)");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    const rtmi_render_params &p = *p_in;
-    hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
-    const uint32_t T = local_tiles_of(&p, 0);
-    const size_t ntex = (size_t)T * 64;
-    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
-        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
-        return rc;
-    uint32_t chunk_spp = 0, pass_ns = 0;
-    if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
-
-    DevParams P = dev_params(s, &p);
-    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
-    const DevCamera C = dev_camera(cam);
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
-    P.path_sig = sig ? s->d_sig : nullptr;
-    const DevLights L = dev_env_lights(s, nee);
-    const DevEnv E = dev_env_render(s, opts);
-    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
-    s->last_kernel = RTMI_KERNEL_PERLANE;
-
-    if ((rc = begin_passes(s, stream))) return rc;
-    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
-    if ((rc = list_all_tiles(s, T, stream))) return rc;
-    AdaptiveResolve A;
-    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
-    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
-    A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
-    PassCounts counts;
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
-    rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
-        HIP_TRY(rtmi_env_launch_render(fast, sig, nee, blocks, stream, s->dev, C, P, L, E));
-        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
-        A.first = first ? 1 : 0;
-        A.decide = last ? 1 : 0;
-        if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
-        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
-        return RTMI_OK;
-    });
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
-    rtmi_scene *one[1] = {s};
-    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
-    if ((rc = check_overflow(s))) return rc;
-    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
-    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
-    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
-    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+    const Estimator m{name, nee, true, opts->env_select_p, "scene is NULL",
+                      "nee = 1 needs the light table (rtmi_scene_attach_lights)"};
+    return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
+                        [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
+                            HIP_TRY(rtmi_env_launch_render(c.fast, sig, nee, blocks, s->stream, s->dev, c.C, c.P, c.L, c.E));
+                            return RTMI_OK;
+                        });
 }
 
 // ---- adaptive sampling with NEE or environment lighting (include/rtmi_adaptive_nee.h) ---------------------------------
 // adaptive sampling's step loop (adaptive_steps) with the per-lane kernel of rtmi_adaptive_nee.hip: rtmi_render_nee's or
 // rtmi_render_env's estimator over the active-tile list
 #define RTMI_ADAPTIVE_NEE_FLAGS (RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK)
+static int adaptive_lit(const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
+                        const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
+                        rtmi_stats *stats) {
+    RenderCall c;
+    if (int rc = begin_adaptive(c, m, s, cam, p, a)) return rc;
+    return adaptive_steps(s, p, a, c.P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+                          [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                              HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, m.nee, m.env, blocks, s->stream, s->dev, c.C,
+                                                                      c.P, tiles, c.L, c.E));
+                              return RTMI_OK;
+                          });
+}
+
 extern "C" int rtmi_render_adaptive_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
                                         const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
                                         uint32_t *out_spp, rtmi_stats *stats) {
@@ -2467,28 +2489,10 @@ extern "C" int rtmi_render_adaptive_nee(rtmi_scene *s, const rtmi_camera *cam, c
                                "adaptive NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK only "
                                "(not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                                "adaptive NEE renders the whole image: tile_world must be 1");
-    if (rc) return rc;
-    if ((rc = check_adaptive(p_in, a))) return rc;
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (!s->has_lights) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_nee: no light table attached (rtmi_scene_attach_lights)");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    const rtmi_render_params &p = *p_in;
-    hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
-    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
-
-    DevParams P = dev_params(s, &p);
-    const DevCamera C = dev_camera(cam);
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
-    const DevLights L = dev_lights(s);
-    const DevEnv E{};
-    return adaptive_steps(s, p, a, P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
-                          [&](uint32_t blocks, const uint32_t *tiles) -> int {
-                              HIP_TRY(rtmi_adaptive_nee_launch_render(fast, true, false, blocks, stream, s->dev, C, P, tiles, L, E));
-                              return RTMI_OK;
-                          });
+    if (rc || (rc = check_adaptive(p_in, a))) return rc;
+    const Estimator m{"rtmi_render_adaptive_nee", true, false, 1.0f, "scene is NULL",
+                      "no light table attached (rtmi_scene_attach_lights)"};
+    return adaptive_lit(m, s, cam, *p_in, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
 }
 
 extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
@@ -2496,52 +2500,27 @@ extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, c
                                         uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
     // every argument check comes before the first use of the handle (and of the device)
     if (!p_in || !a || !cam || !opts) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (p_in->flags & RTMI_FLAG_SKY)
-        return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: RTMI_FLAG_SKY is refused, the map replaces the sky");
+    const char *name = "rtmi_render_adaptive_env";
+    int rc;
+    if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in))) return rc;
     rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS,
                            "adaptive environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD and UV_BOOK "
                            "only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                            "adaptive environment renders render the whole image: tile_world must be 1");
-    if (rc) return rc;
-    if ((rc = check_adaptive(p_in, a))) return rc;
-    if (opts->nee > 1u) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: nee must be 0 or 1");
-    if (!(opts->env_select_p > 0.0f && opts->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: env_select_p must be in (0, 1]");
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (!s->has_env) return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: no environment map attached (rtmi_scene_attach_env)");
-    const bool nee = opts->nee != 0u;
-    if (nee && !s->has_lights)
-        return fail(RTMI_ERR_INVALID, "rtmi_render_adaptive_env: nee = 1 needs the light table (rtmi_scene_attach_lights)");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    const rtmi_render_params &p = *p_in;
-    hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
-    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
-
-    DevParams P = dev_params(s, &p);
-    const DevCamera C = dev_camera(cam);
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
-    const DevLights L = dev_env_lights(s, nee);
-    const DevEnv E = dev_env_render(s, opts);
-    return adaptive_steps(s, p, a, P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
-                          [&](uint32_t blocks, const uint32_t *tiles) -> int {
-                              HIP_TRY(rtmi_adaptive_nee_launch_render(fast, nee, true, blocks, stream, s->dev, C, P, tiles, L, E));
-                              return RTMI_OK;
-                          });
+    if (rc || (rc = check_adaptive(p_in, a)) || (rc = check_env_opts(name, opts))) return rc;
+    const Estimator m{name, opts->nee != 0u, true, opts->env_select_p, "scene is NULL",
+                      "nee = 1 needs the light table (rtmi_scene_attach_lights)"};
+    return adaptive_lit(m, s, cam, *p_in, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
 }
 
 // ---- Russian-roulette path termination (include/rtmi_roulette.h) ------------------------------------------------------
 // Both entries are adaptive sampling's step loop (adaptive_steps) over the per-lane kernels of rtmi_roulette.hip; the
 // fixed render is the single step of ns samples over the list of all tiles (tolerances 0: every tile retires at ns), as
-// the resolve of rtmi_render_nee.  `a` = NULL: the fixed entry.
+// the resolve of render_fixed.  `a` = NULL: the fixed entry.
 static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
                            const rtmi_roulette *o, const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8,
                            float *out_stderr, uint32_t *out_spp, uint32_t *out_bounces, rtmi_stats *stats) {
-    const std::string nm = std::string(name) + ": ";
+    const std::string nm = std::string(name) + ": ", null_scene = nm + "scene is NULL";
     int rc = check_params(p_in);
     if (rc) return rc;
     if (o->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
@@ -2549,9 +2528,9 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     if (!std::isfinite(o->q_min) || !(o->q_min > 0.0f && o->q_min <= 1.0f)) return fail(RTMI_ERR_INVALID, nm + "q_min must be in (0, 1]");
     const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
     const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    if (nee && env && !(o->env_select_p > 0.0f && o->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
-    if (env && (p_in->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    const rtmi_env_render eo{1u, o->env_select_p}; // env_select_p is read, and checked, only where both are sampled
+    if (nee && env && (rc = check_env_opts(name, &eo))) return rc;
+    if (env && (rc = refuse_sky(name, p_in))) return rc;
     if (p_in->flags & RTMI_FLAG_PATH_SIG)
         return fail(RTMI_ERR_UNSUPPORTED, nm + "PATH_SIG is refused: a roulette path has no counterpart to compare a signature with");
     const std::string flags_msg = nm + "roulette renders accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK "
@@ -2559,32 +2538,21 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     const std::string world_msg = nm + "roulette renders render the whole image: tile_world must be 1";
     if ((rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY, flags_msg.c_str(), world_msg.c_str()))) return rc;
     if (a && (rc = check_adaptive(p_in, a))) return rc;
-    if (!s) return fail(RTMI_ERR_INVALID, nm + "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (env && !s->has_env) return fail(RTMI_ERR_INVALID, nm + "no environment map attached (rtmi_scene_attach_env)");
-    if (nee && !s->has_lights) return fail(RTMI_ERR_INVALID, nm + "no light table attached (rtmi_scene_attach_lights)");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
     const rtmi_render_params &p = *p_in;
-    hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
     const rtmi_adaptive fixed{p.ns, 1u, 0.0, 0.0}; // one step of ns samples
     if (!a) a = &fixed;
-    const uint32_t T = local_tiles_of(&p, 0);
-    const size_t ntex = (size_t)T * 64;
-    if ((rc = adaptive_reserve(s, p, a, T)) || (rc = grow(s, s->rr_bounces, s->rr_bytes, ntex * sizeof(uint32_t)))) return rc;
-    HIP_TRY(hipMemsetAsync(s->rr_bounces, 0, ntex * sizeof(uint32_t), stream));
-
-    DevParams P = dev_params(s, &p);
-    const DevCamera C = dev_camera(cam);
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
-    const rtmi_env_render eo{nee ? 1u : 0u, nee ? o->env_select_p : 1.0f}; // not read, and not checked, without NEE
-    const DevLights L = nee ? dev_lights(s) : DevLights{};
-    const DevEnv E = env ? dev_env_render(s, &eo) : DevEnv{};
+    const Estimator m{name, nee, env, nee && env ? o->env_select_p : 1.0f, null_scene.c_str(),
+                      "no light table attached (rtmi_scene_attach_lights)"};
+    RenderCall c;
+    if ((rc = begin_adaptive(c, m, s, cam, p, a))) return rc;
+    const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
+    if ((rc = grow(s, s->rr_bounces, s->rr_bytes, ntex * sizeof(uint32_t)))) return rc;
+    HIP_TRY(hipMemsetAsync(s->rr_bounces, 0, ntex * sizeof(uint32_t), s->stream));
     const DevRoulette R{s->rr_bounces, o->min_depth, o->q_min};
-    rc = adaptive_steps(s, p, a, P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+    rc = adaptive_steps(s, p, a, c.P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
                         [&](uint32_t blocks, const uint32_t *tiles) -> int {
-                            HIP_TRY(rtmi_roulette_launch_render(fast, nee, env, blocks, stream, s->dev, C, P, tiles, L, E, R));
+                            HIP_TRY(rtmi_roulette_launch_render(c.fast, nee, env, blocks, s->stream, s->dev, c.C, c.P, tiles,
+                                                                c.L, c.E, R));
                             return RTMI_OK;
                         });
     if (rc) return rc;

@@ -22,7 +22,7 @@
 
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
-#include "rtmi_env_launch.hpp"
+#include "rtmi_light_launch.hpp"
 
 int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
 
@@ -37,18 +37,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_env_kernel(DevScene
 hipError_t rtmi_env_launch_render(bool fast, bool sig, bool nee, uint32_t blocks, hipStream_t stream, const DevScene &sc,
                                   const DevCamera &cam, const DevParams &P, const DevLights &L, const DevEnv &E) {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
-    if (nee) {
-        if (fast && sig) hipLaunchKernelGGL((rtmi_env_kernel<true, true, true>), grid, block, 0, stream, sc, cam, P, L, E);
-        else if (fast) hipLaunchKernelGGL((rtmi_env_kernel<true, false, true>), grid, block, 0, stream, sc, cam, P, L, E);
-        else if (sig) hipLaunchKernelGGL((rtmi_env_kernel<false, true, true>), grid, block, 0, stream, sc, cam, P, L, E);
-        else hipLaunchKernelGGL((rtmi_env_kernel<false, false, true>), grid, block, 0, stream, sc, cam, P, L, E);
-    } else {
-        if (fast && sig) hipLaunchKernelGGL((rtmi_env_kernel<true, true, false>), grid, block, 0, stream, sc, cam, P, L, E);
-        else if (fast) hipLaunchKernelGGL((rtmi_env_kernel<true, false, false>), grid, block, 0, stream, sc, cam, P, L, E);
-        else if (sig) hipLaunchKernelGGL((rtmi_env_kernel<false, true, false>), grid, block, 0, stream, sc, cam, P, L, E);
-        else hipLaunchKernelGGL((rtmi_env_kernel<false, false, false>), grid, block, 0, stream, sc, cam, P, L, E);
-    }
-    return hipGetLastError();
+    return rtmi_with_bools([&](auto NEE, auto FAST, auto SIG) {
+        hipLaunchKernelGGL((rtmi_env_kernel<FAST(), SIG(), NEE()>), grid, block, 0, stream, sc, cam, P, L, E);
+        return hipGetLastError();
+    }, nee, fast, sig);
 }
 
 // one item per thread: RTMI_ENV_PROBE_LOOKUP (env and the BSDF-side pdf of a direction) or RTMI_ENV_PROBE_SAMPLE (the

@@ -17,7 +17,7 @@
 
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
-#include "rtmi_nee_launch.hpp"
+#include "rtmi_light_launch.hpp"
 
 template <bool FAST, bool SIG>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_nee_kernel(DevScene sc, DevCamera cam, DevParams P, DevLights nl) {
@@ -30,9 +30,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_nee_kernel(DevScene
 hipError_t rtmi_nee_launch_render(bool fast, bool sig, uint32_t blocks, hipStream_t stream, const DevScene &sc,
                                   const DevCamera &cam, const DevParams &P, const DevLights &L) {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
-    if (fast && sig) hipLaunchKernelGGL((rtmi_nee_kernel<true, true>), grid, block, 0, stream, sc, cam, P, L);
-    else if (fast) hipLaunchKernelGGL((rtmi_nee_kernel<true, false>), grid, block, 0, stream, sc, cam, P, L);
-    else if (sig) hipLaunchKernelGGL((rtmi_nee_kernel<false, true>), grid, block, 0, stream, sc, cam, P, L);
-    else hipLaunchKernelGGL((rtmi_nee_kernel<false, false>), grid, block, 0, stream, sc, cam, P, L);
-    return hipGetLastError();
+    return rtmi_with_bools([&](auto FAST, auto SIG) {
+        hipLaunchKernelGGL((rtmi_nee_kernel<FAST(), SIG()>), grid, block, 0, stream, sc, cam, P, L);
+        return hipGetLastError();
+    }, fast, sig);
 }

@@ -17,7 +17,7 @@
 
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
-#include "rtmi_roulette_launch.hpp"
+#include "rtmi_light_launch.hpp"
 
 // The roulette test of rtmi_roulette.h, after a scatter has updated pa.T and pa.depth; g is the path's stream-0 state
 // (its sample and pixel words key the stateless stream-4 draw).  false: the continuation ends.
@@ -58,18 +58,8 @@ hipError_t rtmi_roulette_launch_render(bool fast, bool nee, bool env, uint32_t b
                                        const DevCamera &cam, const DevParams &P, const uint32_t *tiles, const DevLights &L,
                                        const DevEnv &E, const DevRoulette &R) {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
-    if (nee && env) {
-        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, true, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, true, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-    } else if (nee) {
-        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, true, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, true, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-    } else if (env) {
-        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, false, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, false, true>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-    } else {
-        if (fast) hipLaunchKernelGGL((rtmi_roulette_kernel<true, false, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-        else hipLaunchKernelGGL((rtmi_roulette_kernel<false, false, false>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
-    }
-    return hipGetLastError();
+    return rtmi_with_bools([&](auto NEE, auto ENV, auto FAST) {
+        hipLaunchKernelGGL((rtmi_roulette_kernel<FAST(), NEE(), ENV()>), grid, block, 0, stream, sc, cam, P, tiles, L, E, R);
+        return hipGetLastError();
+    }, nee, env, fast);
 }

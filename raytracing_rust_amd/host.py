@@ -250,6 +250,16 @@ class Scene:
             out["sig"] = sg
         return out
 
+    def _ready(self, kw, lights=False, multi_refuses=True):
+        """Before a render of the uploaded handle: uploads on first use (to the keyword `device`), drops `device` from the
+        keywords and, with lights=True, attaches the light table on first use.  multi_refuses: a scene resident on a
+        device list (upload_multi) is not uploaded, so that the native entry refuses it."""
+        if not self.uploaded and not (multi_refuses and getattr(self, "multi_devices", None)):
+            self.upload(kw.pop("device", 0))
+        kw.pop("device", None)
+        if lights and self.uploaded and not getattr(self, "lights_attached", False):
+            self.attach_lights()
+
     def render_adaptive(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, precision="f32", nee=False,
                         env=False, env_select_p=0.5, **kw):
         """Adaptive sampling (include/rtmi_adaptive.h): every 8x8 tile gets min_spp samples, then step_spp more per step
@@ -261,19 +271,10 @@ class Scene:
         env_select_p=env_select_p) with the attached map.  The defaults are the plain estimator."""
         if precision != "f32":
             raise Unsupported("adaptive sampling has no f64 mode")
-        if not self.uploaded:
-            self.upload(kw.pop("device", 0))
-        kw.pop("device", None)
-        if nee and self.uploaded and not getattr(self, "lights_attached", False):
-            self.attach_lights()
+        self._ready(kw, lights=nee, multi_refuses=False)
         p = default_params(nx, ny, ns, **kw)
         a = abi.Adaptive(min_spp, step_spp, abs_tol, rel_tol)
-        lin = np.zeros((ny, nx, 3), np.float32)
-        rgb = np.zeros((ny, nx, 3), np.uint8)
-        se = np.zeros((ny, nx, 3), np.float32)
-        spp = np.zeros((ny, nx), np.uint32)
-        st = abi.Stats()
-        outs = (lin.ctypes.data, rgb.ctypes.data, se.ctypes.data, spp.ctypes.data, C.byref(st))
+        out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr", "spp"))
         if env:
             o = abi.EnvRender(1 if nee else 0, env_select_p)
             self.host._check(self.host.lib.rth_render_adaptive_env(self.h, cam.h, C.byref(p), C.byref(o), C.byref(a), *outs))
@@ -281,7 +282,7 @@ class Scene:
             self.host._check(self.host.lib.rth_render_adaptive_nee(self.h, cam.h, C.byref(p), C.byref(a), *outs))
         else:
             self.host._check(self.host.lib.rth_render_adaptive(self.h, cam.h, C.byref(p), C.byref(a), *outs))
-        return {"linear": lin, "rgb8": rgb, "stderr": se, "spp": spp, "stats": _stats(st)}
+        return _result(out)
 
     def render_features(self, cam, nx, ny, ns, sig=False, precision="f32", **kw):
         """First-hit features for denoisers (include/rtmi_features.h): the first interaction of render()'s paths, per
@@ -290,23 +291,11 @@ class Scene:
         Row 0 is the top row.  A scene resident on a device list (upload_multi) raises Unsupported."""
         if precision != "f32":
             raise Unsupported("first-hit features have no f64 mode")
-        if not self.uploaded and not getattr(self, "multi_devices", None):
-            self.upload(kw.pop("device", 0))
-        kw.pop("device", None)
+        self._ready(kw)
         p = default_params(nx, ny, ns, **kw)
-        alb = np.zeros((ny, nx, 3), np.float32)
-        nrm = np.zeros((ny, nx, 3), np.float32)
-        dep = np.zeros((ny, nx), np.float32)
-        hits = np.zeros((ny, nx), np.uint32)
-        sg = np.zeros((ny, nx), np.uint64) if sig else None
-        st = abi.Stats()
-        self.host._check(self.host.lib.rth_render_features(self.h, cam.h, C.byref(p), alb.ctypes.data, nrm.ctypes.data,
-                                                            dep.ctypes.data, hits.ctypes.data, sg.ctypes.data if sig else None,
-                                                            C.byref(st)))
-        out = {"albedo": alb, "normal": nrm, "depth": dep, "hits": hits, "stats": _stats(st)}
-        if sig:
-            out["sig"] = sg
-        return out
+        out, outs = _outputs(ny, nx, ("albedo", "normal", "depth", "hits"), bool(sig))
+        self.host._check(self.host.lib.rth_render_features(self.h, cam.h, C.byref(p), *outs))
+        return _result(out)
 
     def render_nee(self, cam, nx, ny, ns, sig=False, precision="f32", **kw):
         """Next-event estimation (include/rtmi_nee.h): render()'s paths with a light sample at every diffuse vertex,
@@ -315,23 +304,11 @@ class Scene:
         is attached on first use.  A scene resident on a device list (upload_multi) raises Unsupported."""
         if precision != "f32":
             raise Unsupported("next-event estimation has no f64 mode")
-        if not self.uploaded and not getattr(self, "multi_devices", None):
-            self.upload(kw.pop("device", 0))
-        kw.pop("device", None)
-        if self.uploaded and not getattr(self, "lights_attached", False):
-            self.attach_lights()
+        self._ready(kw, lights=True)
         p = default_params(nx, ny, ns, **kw)
-        lin = np.zeros((ny, nx, 3), np.float32)
-        rgb = np.zeros((ny, nx, 3), np.uint8)
-        se = np.zeros((ny, nx, 3), np.float32)
-        sg = np.zeros((ny, nx), np.uint64) if sig else None
-        st = abi.Stats()
-        self.host._check(self.host.lib.rth_render_nee(self.h, cam.h, C.byref(p), lin.ctypes.data, rgb.ctypes.data,
-                                                       se.ctypes.data, sg.ctypes.data if sig else None, C.byref(st)))
-        out = {"linear": lin, "rgb8": rgb, "stderr": se, "stats": _stats(st)}
-        if sig:
-            out["sig"] = sg
-        return out
+        out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr"), bool(sig))
+        self.host._check(self.host.lib.rth_render_nee(self.h, cam.h, C.byref(p), *outs))
+        return _result(out)
 
     def render_env(self, cam, nx, ny, ns, nee=True, env_select_p=0.5, sig=False, precision="f32", **kw):
         """Environment lighting (include/rtmi_env.h): render()'s paths with the attached map (attach_env) where a ray
@@ -341,33 +318,17 @@ class Scene:
         light table is attached on first use.  A scene resident on a device list (upload_multi) raises Unsupported."""
         if precision != "f32":
             raise Unsupported("environment lighting has no f64 mode")
-        if not self.uploaded and not getattr(self, "multi_devices", None):
-            self.upload(kw.pop("device", 0))
-        kw.pop("device", None)
-        if nee and self.uploaded and not getattr(self, "lights_attached", False):
-            self.attach_lights()
+        self._ready(kw, lights=nee)
         p = default_params(nx, ny, ns, **kw)
         o = abi.EnvRender(1 if nee else 0, env_select_p)
-        lin = np.zeros((ny, nx, 3), np.float32)
-        rgb = np.zeros((ny, nx, 3), np.uint8)
-        se = np.zeros((ny, nx, 3), np.float32)
-        sg = np.zeros((ny, nx), np.uint64) if sig else None
-        st = abi.Stats()
-        self.host._check(self.host.lib.rth_render_env(self.h, cam.h, C.byref(p), C.byref(o), lin.ctypes.data, rgb.ctypes.data,
-                                                       se.ctypes.data, sg.ctypes.data if sig else None, C.byref(st)))
-        out = {"linear": lin, "rgb8": rgb, "stderr": se, "stats": _stats(st)}
-        if sig:
-            out["sig"] = sg
-        return out
+        out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr"), bool(sig))
+        self.host._check(self.host.lib.rth_render_env(self.h, cam.h, C.byref(p), C.byref(o), *outs))
+        return _result(out)
 
     def _roulette_opts(self, estimator, min_depth, q_min, env_select_p, kw):
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
-        if not self.uploaded and not getattr(self, "multi_devices", None):
-            self.upload(kw.pop("device", 0))
-        kw.pop("device", None)
-        if estimator in ("nee", "env_nee") and self.uploaded and not getattr(self, "lights_attached", False):
-            self.attach_lights()
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
         return abi.Roulette(abi.ROULETTE_ESTIMATORS[estimator], min_depth, q_min, env_select_p)
 
     def render_roulette(self, cam, nx, ny, ns, estimator="nee", min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32",
@@ -382,14 +343,9 @@ class Scene:
             raise Unsupported("Russian roulette has no f64 mode")
         o = self._roulette_opts(estimator, min_depth, q_min, env_select_p, kw)
         p = default_params(nx, ny, ns, **kw)
-        lin = np.zeros((ny, nx, 3), np.float32)
-        rgb = np.zeros((ny, nx, 3), np.uint8)
-        se = np.zeros((ny, nx, 3), np.float32)
-        bn = np.zeros((ny, nx), np.uint32)
-        st = abi.Stats()
-        self.host._check(self.host.lib.rth_render_roulette(self.h, cam.h, C.byref(p), C.byref(o), lin.ctypes.data, rgb.ctypes.data,
-                                                            se.ctypes.data, bn.ctypes.data, C.byref(st)))
-        return {"linear": lin, "rgb8": rgb, "stderr": se, "bounces": bn, "stats": _stats(st)}
+        out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr", "bounces"))
+        self.host._check(self.host.lib.rth_render_roulette(self.h, cam.h, C.byref(p), C.byref(o), *outs))
+        return _result(out)
 
     def render_adaptive_roulette(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, estimator="nee",
                                  min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32", **kw):
@@ -401,16 +357,9 @@ class Scene:
         o = self._roulette_opts(estimator, min_depth, q_min, env_select_p, kw)
         p = default_params(nx, ny, ns, **kw)
         a = abi.Adaptive(min_spp, step_spp, abs_tol, rel_tol)
-        lin = np.zeros((ny, nx, 3), np.float32)
-        rgb = np.zeros((ny, nx, 3), np.uint8)
-        se = np.zeros((ny, nx, 3), np.float32)
-        spp = np.zeros((ny, nx), np.uint32)
-        bn = np.zeros((ny, nx), np.uint32)
-        st = abi.Stats()
-        self.host._check(self.host.lib.rth_render_adaptive_roulette(self.h, cam.h, C.byref(p), C.byref(o), C.byref(a),
-                                                                     lin.ctypes.data, rgb.ctypes.data, se.ctypes.data,
-                                                                     spp.ctypes.data, bn.ctypes.data, C.byref(st)))
-        return {"linear": lin, "rgb8": rgb, "stderr": se, "spp": spp, "bounces": bn, "stats": _stats(st)}
+        out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr", "spp", "bounces"))
+        self.host._check(self.host.lib.rth_render_adaptive_roulette(self.h, cam.h, C.byref(p), C.byref(o), C.byref(a), *outs))
+        return _result(out)
 
     def render_denoised(self, cam, nx, ny, ns, denoise=None, nee=False, env=False, **kw):
         """A render and its denoised image: render_adaptive(min_spp=ns, step_spp=1) (render()'s image plus its standard
@@ -507,6 +456,31 @@ class Scene:
         self.host._check(self.host.lib.rth_render_device(self.h, cam.h, C.byref(params), C.c_void_p(d_texels_ptr),
                                                           C.c_void_p(stream or 0), C.byref(st) if st else None))
         return _stats(st) if st else None
+
+
+# the output planes of the render methods: channels after [ny, nx], dtype
+_PLANES = {"linear": ((3,), np.float32), "rgb8": ((3,), np.uint8), "stderr": ((3,), np.float32), "spp": ((), np.uint32),
+           "bounces": ((), np.uint32), "albedo": ((3,), np.float32), "normal": ((3,), np.float32), "depth": ((), np.float32),
+           "hits": ((), np.uint32)}
+
+
+def _outputs(ny, nx, names, sig=None):
+    """The zeroed planes `names` of a render as its result dict, and the trailing arguments of the native entry: the
+    planes' addresses in that order, the path signatures' (u64 [ny,nx]; NULL unless sig; sig=None: the entry takes none;
+    the methods that take them pass bool(sig)) and the stats.  _result() completes the dict after the call."""
+    out = {n: np.zeros((ny, nx) + _PLANES[n][0], _PLANES[n][1]) for n in names}
+    args = [a.ctypes.data for a in out.values()]
+    out["stats"] = abi.Stats()
+    if sig:
+        out["sig"] = np.zeros((ny, nx), np.uint64)
+    if sig is not None:
+        args.append(out["sig"].ctypes.data if sig else None)
+    return out, args + [C.byref(out["stats"])]
+
+
+def _result(out):
+    out["stats"] = _stats(out["stats"])
+    return out
 
 
 def _stats(st):

@@ -226,36 +226,49 @@ RTH_API void *rth_lower(void *world) {
 RTH_API int rth_lowered_desc(void *lowered, rtmi_scene_desc *out) {
     return guard([&] { *out = LOW(lowered)->lowered->desc(); return RTH_OK; });
 }
+// The uploaded device handle of a lowered scene.  `name` and `no_multi`: the rtmi entry and the kind of entry a scene
+// resident on a device list (rth_upload_multi) lacks, in the wrappers that refuse such a scene as Unsupported.
+static rtmi_scene *DEV(void *lowered, const char *name = nullptr, const char *no_multi = nullptr) {
+    Obj *o = LOW(lowered);
+    if (!o->dev && o->multi && no_multi)
+        throw Unsupported(std::string(name) + ": multi-GPU handles have no " + no_multi + " entry (RTMI_ERR_UNSUPPORTED)");
+    if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+    return o->dev;
+}
+// A non-zero return of the rtmi entry `name` as the wrapper's exception.  The older wrappers (PLAIN) throw "name: message";
+// the newer ones add the code, and the render modes among them map RTMI_ERR_UNSUPPORTED to Unsupported.
+enum ErrStyle { PLAIN, CODED, CODED_UNSUPPORTED };
+static int done(const char *name, int rc, ErrStyle style) {
+    if (!rc) return RTH_OK;
+    const std::string msg = std::string(name) + ": " + rtmi_last_error();
+    if (style == PLAIN) throw std::runtime_error(msg);
+    if (style == CODED_UNSUPPORTED && rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(msg);
+    throw std::runtime_error(msg + " (code " + std::to_string(rc) + ")");
+}
 RTH_API int rth_upload(void *lowered, int device) {
     return guard([&] {
         Obj *o = LOW(lowered);
         if (o->dev) { rtmi_scene_destroy(o->dev); o->dev = nullptr; }
         const rtmi_scene_desc d = o->lowered->desc();
-        if (int rc = rtmi_scene_create(&d, device, &o->dev)) throw std::runtime_error(std::string("rtmi_scene_create: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done("rtmi_scene_create", rtmi_scene_create(&d, device, &o->dev), CODED);
     });
 }
 RTH_API int rth_render(void *lowered, void *cam, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8,
                        uint64_t *out_path_sig, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        rtmi_scene *dev = DEV(lowered);
         const rtmi_camera c = CAM(cam).lower();
-        if (rtmi_render(o->dev, &c, p, out_linear, out_rgb8, out_path_sig, stats)) throw std::runtime_error(std::string("rtmi_render: ") + rtmi_last_error());
-        return RTH_OK;
+        return done("rtmi_render", rtmi_render(dev, &c, p, out_linear, out_rgb8, out_path_sig, stats), PLAIN);
     });
 }
 // adaptive sampling (include/rtmi_adaptive.h): RTH_UNSUPPORTED for what rtmi_render_adaptive does not support
 RTH_API int rth_render_adaptive(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_adaptive *a, float *out_linear,
                                 uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        rtmi_scene *dev = DEV(lowered);
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_adaptive(o->dev, &c, p, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done("rtmi_render_adaptive", rtmi_render_adaptive(dev, &c, p, a, out_linear, out_rgb8, out_stderr, out_spp, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 // first-hit features (include/rtmi_features.h): RTH_UNSUPPORTED for what rtmi_render_features does not support, a
@@ -263,42 +276,30 @@ RTH_API int rth_render_adaptive(void *lowered, void *cam, const rtmi_render_para
 RTH_API int rth_render_features(void *lowered, void *cam, const rtmi_render_params *p, float *out_albedo, float *out_normal,
                                 float *out_depth, uint32_t *out_hits, uint64_t *out_path_sig, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi)
-            throw Unsupported("rtmi_render_features: multi-GPU handles have no features entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_features";
+        rtmi_scene *dev = DEV(lowered, name, "features");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_features(o->dev, &c, p, out_albedo, out_normal, out_depth, out_hits, out_path_sig, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_features: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_features: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_render_features(dev, &c, p, out_albedo, out_normal, out_depth, out_hits, out_path_sig, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 // next-event estimation (include/rtmi_nee.h): attaches the light table of the lowered scene to its uploaded handle, then
 // renders; RTH_UNSUPPORTED for what rtmi_render_nee does not support, a multi-GPU handle among it
 RTH_API int rth_attach_lights(void *lowered) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi)
-            throw Unsupported("rtmi_scene_attach_lights: multi-GPU handles have no NEE entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
-        const rtmi_scene_desc d = o->lowered->desc();
-        if (int rc = rtmi_scene_attach_lights(o->dev, &d))
-            throw std::runtime_error(std::string("rtmi_scene_attach_lights: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        const char *name = "rtmi_scene_attach_lights";
+        rtmi_scene *dev = DEV(lowered, name, "NEE");
+        const rtmi_scene_desc d = LOW(lowered)->lowered->desc();
+        return done(name, rtmi_scene_attach_lights(dev, &d), CODED);
     });
 }
 RTH_API int rth_render_nee(void *lowered, void *cam, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8,
                            float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi) throw Unsupported("rtmi_render_nee: multi-GPU handles have no NEE entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_nee";
+        rtmi_scene *dev = DEV(lowered, name, "NEE");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_nee(o->dev, &c, p, out_linear, out_rgb8, out_stderr, out_path_sig, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_nee: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_nee: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_render_nee(dev, &c, p, out_linear, out_rgb8, out_stderr, out_path_sig, stats), CODED_UNSUPPORTED);
     });
 }
 
@@ -306,26 +307,20 @@ RTH_API int rth_render_nee(void *lowered, void *cam, const rtmi_render_params *p
 // RTH_UNSUPPORTED for what rtmi_render_env does not support, a multi-GPU handle among it
 RTH_API int rth_attach_env(void *lowered, uint32_t width, uint32_t height, const float *rgb) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi) throw Unsupported("rtmi_scene_attach_env: multi-GPU handles have no environment entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_scene_attach_env";
+        rtmi_scene *dev = DEV(lowered, name, "environment");
         const rtmi_env_map m{width, height, rgb};
-        if (int rc = rtmi_scene_attach_env(o->dev, rgb ? &m : nullptr))
-            throw std::runtime_error(std::string("rtmi_scene_attach_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_scene_attach_env(dev, rgb ? &m : nullptr), CODED);
     });
 }
 RTH_API int rth_render_env(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_env_render *opts, float *out_linear,
                            uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi) throw Unsupported("rtmi_render_env: multi-GPU handles have no environment entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_env";
+        rtmi_scene *dev = DEV(lowered, name, "environment");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_env(o->dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_path_sig, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_env: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_render_env(dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_path_sig, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 // adaptive sampling with NEE or environment lighting (include/rtmi_adaptive_nee.h); RTH_UNSUPPORTED for what the two
@@ -333,28 +328,22 @@ RTH_API int rth_render_env(void *lowered, void *cam, const rtmi_render_params *p
 RTH_API int rth_render_adaptive_nee(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_adaptive *a,
                                     float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi) throw Unsupported("rtmi_render_adaptive_nee: multi-GPU handles have no adaptive entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_adaptive_nee";
+        rtmi_scene *dev = DEV(lowered, name, "adaptive");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_adaptive_nee(o->dev, &c, p, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_nee: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive_nee: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_render_adaptive_nee(dev, &c, p, a, out_linear, out_rgb8, out_stderr, out_spp, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 RTH_API int rth_render_adaptive_env(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_env_render *opts,
                                     const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
                                     uint32_t *out_spp, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi) throw Unsupported("rtmi_render_adaptive_env: multi-GPU handles have no adaptive entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_adaptive_env";
+        rtmi_scene *dev = DEV(lowered, name, "adaptive");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_adaptive_env(o->dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_env: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_adaptive_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_render_adaptive_env(dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 // Russian-roulette path termination (include/rtmi_roulette.h); RTH_UNSUPPORTED for what the two entries do not support, a
@@ -362,40 +351,27 @@ RTH_API int rth_render_adaptive_env(void *lowered, void *cam, const rtmi_render_
 RTH_API int rth_render_roulette(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_roulette *opts, float *out_linear,
                                 uint8_t *out_rgb8, float *out_stderr, uint32_t *out_bounces, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi) throw Unsupported("rtmi_render_roulette: multi-GPU handles have no roulette entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_roulette";
+        rtmi_scene *dev = DEV(lowered, name, "roulette");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_roulette(o->dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_bounces, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_roulette: ") + rtmi_last_error());
-        if (rc) throw std::runtime_error(std::string("rtmi_render_roulette: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name, rtmi_render_roulette(dev, &c, p, opts, out_linear, out_rgb8, out_stderr, out_bounces, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 RTH_API int rth_render_adaptive_roulette(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_roulette *opts,
                                          const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr,
                                          uint32_t *out_spp, uint32_t *out_bounces, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev && o->multi)
-            throw Unsupported("rtmi_render_adaptive_roulette: multi-GPU handles have no roulette entry (RTMI_ERR_UNSUPPORTED)");
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        const char *name = "rtmi_render_adaptive_roulette";
+        rtmi_scene *dev = DEV(lowered, name, "roulette");
         const rtmi_camera c = CAM(cam).lower();
-        const int rc = rtmi_render_adaptive_roulette(o->dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, out_bounces, stats);
-        if (rc == RTMI_ERR_UNSUPPORTED) throw Unsupported(std::string("rtmi_render_adaptive_roulette: ") + rtmi_last_error());
-        if (rc)
-            throw std::runtime_error(std::string("rtmi_render_adaptive_roulette: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done(name,
+                    rtmi_render_adaptive_roulette(dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, out_bounces, stats),
+                    CODED_UNSUPPORTED);
     });
 }
 RTH_API int rth_probe_env(void *lowered, int op, const float *in, float *out, uint32_t n) {
-    return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
-        if (int rc = rtmi_probe_env(o->dev, op, in, out, n))
-            throw std::runtime_error(std::string("rtmi_probe_env: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
-    });
+    return guard([&] { return done("rtmi_probe_env", rtmi_probe_env(DEV(lowered), op, in, out, n), CODED); });
 }
 // ---- f64 render mode (include/rtmi_f64.h) ------------------------------------------------------------
 RTH_API int rth_lowered_desc_f64(void *lowered, rtmi_scene_f64 *out) {
@@ -405,41 +381,30 @@ RTH_API int rth_camera_lower_f64(void *cam, rtmi_camera_f64 *out) { return guard
 // attaches the lowered scene's double planes to its uploaded handle (rtmi_scene_attach_f64)
 RTH_API int rth_attach_f64(void *lowered) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
-        const rtmi_scene_f64 w = o->lowered->desc_f64();
-        if (int rc = rtmi_scene_attach_f64(o->dev, &w)) throw std::runtime_error(std::string("rtmi_scene_attach_f64: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        rtmi_scene *dev = DEV(lowered);
+        const rtmi_scene_f64 w = LOW(lowered)->lowered->desc_f64();
+        return done("rtmi_scene_attach_f64", rtmi_scene_attach_f64(dev, &w), CODED);
     });
 }
 RTH_API int rth_render_f64(void *lowered, void *cam, const rtmi_render_params *p, double t_min, double *out_linear, uint8_t *out_rgb8,
                            uint64_t *out_path_sig, rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        rtmi_scene *dev = DEV(lowered);
         const rtmi_camera_f64 c = CAM(cam).lower_f64();
-        if (rtmi_render_f64(o->dev, &c, p, t_min, out_linear, out_rgb8, out_path_sig, stats)) throw std::runtime_error(std::string("rtmi_render_f64: ") + rtmi_last_error());
-        return RTH_OK;
+        return done("rtmi_render_f64", rtmi_render_f64(dev, &c, p, t_min, out_linear, out_rgb8, out_path_sig, stats), PLAIN);
     });
 }
 RTH_API int rth_render_device(void *lowered, void *cam, const rtmi_render_params *p, void *d_texels, void *stream,
                               rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
+        rtmi_scene *dev = DEV(lowered);
         const rtmi_camera c = CAM(cam).lower();
-        if (rtmi_render_device(o->dev, &c, p, d_texels, stream, stats)) throw std::runtime_error(std::string("rtmi_render_device: ") + rtmi_last_error());
-        return RTH_OK;
+        return done("rtmi_render_device", rtmi_render_device(dev, &c, p, d_texels, stream, stats), PLAIN);
     });
 }
 // overflow report of the asynchronous render calls since the last report (rtmi_scene_status)
 RTH_API int rth_scene_status(void *lowered) {
-    return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
-        if (rtmi_scene_status(o->dev, nullptr)) throw std::runtime_error(std::string("rtmi_scene_status: ") + rtmi_last_error());
-        return RTH_OK;
-    });
+    return guard([&] { return done("rtmi_scene_status", rtmi_scene_status(DEV(lowered), nullptr), PLAIN); });
 }
 // whole image on several GPUs of this process (rtmi_render_multi): uploads the lowered scene to every listed device
 RTH_API int rth_render_multi(void *lowered, void *cam, const rtmi_render_params *p, const int *devices, uint32_t n,
@@ -447,17 +412,13 @@ RTH_API int rth_render_multi(void *lowered, void *cam, const rtmi_render_params 
     return guard([&] {
         const rtmi_scene_desc d = LOW(lowered)->lowered->desc();
         const rtmi_camera c = CAM(cam).lower();
-        if (rtmi_render_multi(&d, devices, n, &c, p, out_linear, out_rgb8, stats)) throw std::runtime_error(std::string("rtmi_render_multi: ") + rtmi_last_error());
-        return RTH_OK;
+        return done("rtmi_render_multi", rtmi_render_multi(&d, devices, n, &c, p, out_linear, out_rgb8, stats), PLAIN);
     });
 }
 // RTMI_FLAG_PROGRESSIVE: the image of the passes finished so far (only from inside the progress callback of rth_render)
 RTH_API int rth_partial_image(void *lowered, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8, uint32_t *spp_done) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
-        if (rtmi_partial_image(o->dev, p, out_linear, out_rgb8, spp_done)) throw std::runtime_error(std::string("rtmi_partial_image: ") + rtmi_last_error());
-        return RTH_OK;
+        return done("rtmi_partial_image", rtmi_partial_image(DEV(lowered), p, out_linear, out_rgb8, spp_done), PLAIN);
     });
 }
 // the lowered scene resident on a list of GPUs of this process (rtmi_multi_create); replaces an earlier list
@@ -466,8 +427,7 @@ RTH_API int rth_upload_multi(void *lowered, const int *devices, uint32_t n) {
         Obj *o = LOW(lowered);
         if (o->multi) { rtmi_multi_destroy(o->multi); o->multi = nullptr; }
         const rtmi_scene_desc d = o->lowered->desc();
-        if (int rc = rtmi_multi_create(&d, devices, n, &o->multi)) throw std::runtime_error(std::string("rtmi_multi_create: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
-        return RTH_OK;
+        return done("rtmi_multi_create", rtmi_multi_create(&d, devices, n, &o->multi), CODED);
     });
 }
 RTH_API int rth_multi_free(void *lowered) {
@@ -482,32 +442,26 @@ RTH_API int rth_multi_collective(void *lowered) {
     Obj *o = LOW(lowered);
     return o && o->multi ? rtmi_multi_collective(o->multi) : -1;
 }
+// the handle of a lowered scene resident on a device list
+static rtmi_multi *MULTI(void *lowered) {
+    Obj *o = LOW(lowered);
+    if (!o->multi) throw std::runtime_error("scene not resident on a device list: call rth_upload_multi first");
+    return o->multi;
+}
 RTH_API int rth_multi_prepare(void *lowered, const rtmi_render_params *p) {
-    return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->multi) throw std::runtime_error("scene not resident on a device list: call rth_upload_multi first");
-        if (rtmi_multi_prepare(o->multi, p)) throw std::runtime_error(std::string("rtmi_multi_prepare: ") + rtmi_last_error());
-        return RTH_OK;
-    });
+    return guard([&] { return done("rtmi_multi_prepare", rtmi_multi_prepare(MULTI(lowered), p), PLAIN); });
 }
 RTH_API int rth_multi_render(void *lowered, void *cam, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8,
                              rtmi_stats *stats) {
     return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->multi) throw std::runtime_error("scene not resident on a device list: call rth_upload_multi first");
+        rtmi_multi *multi = MULTI(lowered);
         const rtmi_camera c = CAM(cam).lower();
-        if (rtmi_multi_render(o->multi, &c, p, out_linear, out_rgb8, stats)) throw std::runtime_error(std::string("rtmi_multi_render: ") + rtmi_last_error());
-        return RTH_OK;
+        return done("rtmi_multi_render", rtmi_multi_render(multi, &c, p, out_linear, out_rgb8, stats), PLAIN);
     });
 }
 // allocate the render buffers for `p` ahead of the first render call (optional)
 RTH_API int rth_render_prepare(void *lowered, const rtmi_render_params *p) {
-    return guard([&] {
-        Obj *o = LOW(lowered);
-        if (!o->dev) throw std::runtime_error("scene not uploaded: call rth_upload first");
-        if (rtmi_render_prepare(o->dev, p)) throw std::runtime_error(std::string("rtmi_render_prepare: ") + rtmi_last_error());
-        return RTH_OK;
-    });
+    return guard([&] { return done("rtmi_render_prepare", rtmi_render_prepare(DEV(lowered), p), PLAIN); });
 }
 // Camera::render / create_image in one call (lower + upload + render + free)
 RTH_API int rth_camera_render(void *cam, void *world, uint32_t nx, uint32_t ny, uint32_t ns, uint64_t seed, uint32_t flags,
@@ -535,8 +489,7 @@ RTH_API int rth_camera_render_f64(void *cam, void *world, uint32_t nx, uint32_t 
         p.tile_rank = 0; p.tile_world = 1;
         const rtmi_camera_f64 c = CAM(cam).lower_f64();
         rtmi_scene *scene = nullptr;
-        if (int rc = rtmi_scene_create(&d, device, &scene))
-            throw std::runtime_error(std::string("rtmi_scene_create: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+        done("rtmi_scene_create", rtmi_scene_create(&d, device, &scene), CODED);
         int rc = rtmi_scene_attach_f64(scene, &w);
         if (!rc) rc = rtmi_render_f64(scene, &c, &p, 0.001, out_linear, out_rgb8, nullptr, stats); // t_min: color.rs:7
         const std::string err = rc ? rtmi_last_error() : "";

@@ -183,10 +183,24 @@ def test_checks_come_before_device_work():
     """The refusals of a handle without a map or light table are tested on the device (tests/test_gpu_env.py); here: the
     checks precede the entry points' first device call."""
     src = open(os.path.join(ROOT, "raytracing_rust_amd", "csrc", "rtmi_device.hip")).read()
-    body = src[src.index('extern "C" int rtmi_render_env('):]
-    body = body[:body.index("\n}\n")]
-    for check in ("RTMI_FLAG_SKY", "env_select_p", "!s->has_env", "!s->has_lights"):
-        assert body.index(check) < body.index("hipSetDevice"), check
+
+    def body_of(signature):
+        body = src[src.index(signature):]
+        return body[:body.index("\n}\n")]
+
+    # The entry point calls the two option checks, then hands over to render_fixed, which begins with begin_call; none of
+    # them touches the device before that.
+    entry = body_of('extern "C" int rtmi_render_env(')
+    assert entry.index("refuse_sky(") < entry.index("check_env_opts(") < entry.index("render_fixed(")
+    assert "hip" not in entry[:entry.index("render_fixed(")]
+    assert "RTMI_FLAG_SKY" in body_of("static int refuse_sky(") and "hip" not in body_of("static int refuse_sky(")
+    assert "env_select_p" in body_of("static int check_env_opts(") and "hip" not in body_of("static int check_env_opts(")
+    fixed = body_of("static int render_fixed(")
+    assert "hip" not in fixed[:fixed.index("begin_call(")]
+    # begin_call holds the attach checks and the path's first device call
+    begin = body_of("static int begin_call(")
+    for check in ("!s->has_env", "!s->has_lights"):
+        assert begin.index(check) < begin.index("hipSetDevice"), check
     body = src[src.index('extern "C" int rtmi_scene_attach_env('):]
     assert body.index("rtmi_env_build_tables") < body.index("hipSetDevice")
     body = src[src.index('extern "C" int rtmi_probe_env('):]

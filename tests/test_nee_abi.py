@@ -113,5 +113,16 @@ def test_missing_attach_is_checked_before_device_work():
     """The refusal of a handle without a light table (RTMI_ERR_INVALID) is tested on the device
     (tests/test_gpu_nee.py); here: the check precedes the entry point's first device call."""
     src = open(os.path.join(ROOT, "raytracing_rust_amd", "csrc", "rtmi_device.hip")).read()
-    body = src[src.index('extern "C" int rtmi_render_nee('):]
-    assert body.index("!s->has_lights") < body.index("hipSetDevice")
+
+    def body_of(signature):
+        body = src[src.index(signature):]
+        return body[:body.index("\n}\n")]
+
+    # the entry point hands over to render_fixed, which begins with begin_call; neither touches the device before that
+    entry = body_of('extern "C" int rtmi_render_nee(')
+    assert "hip" not in entry[:entry.index("render_fixed(")]
+    fixed = body_of("static int render_fixed(")
+    assert "hip" not in fixed[:fixed.index("begin_call(")]
+    # begin_call holds the check and the path's first device call
+    begin = body_of("static int begin_call(")
+    assert begin.index("!s->has_lights") < begin.index("hipSetDevice")
