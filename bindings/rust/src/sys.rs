@@ -18,6 +18,8 @@ pub const RTMI_FLAG_FACE_FORWARD: u32 = 128;
 pub const RTMI_FLAG_UV_BOOK: u32 = 4096;
 /// opt-in: after every pass the framebuffer holds the image of the samples so far (rtmi_partial_image)
 pub const RTMI_FLAG_PROGRESSIVE: u32 = 16384;
+/// include/rtmi_light_coop.h: the NEE / environment entries trace on the wave-cooperative kernel (same bits)
+pub const RTMI_FLAG_LIGHT_COOP: u32 = 65536;
 pub const RTMI_OK: i32 = 0;
 pub const RTMI_ERR_INVALID: i32 = 1;
 pub const RTMI_ERR_UNSUPPORTED: i32 = 2;

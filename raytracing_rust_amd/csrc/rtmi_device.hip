@@ -46,6 +46,7 @@
 #include "rtmi_env.h"
 #include "rtmi_adaptive_nee.h"
 #include "rtmi_roulette.h"
+#include "rtmi_light_coop.h"
 #include "rtmi_light_launch.hpp"
 
 // ======================================================================================
@@ -1907,17 +1908,18 @@ static int adaptive_reserve(rtmi_scene *s, const rtmi_render_params &p, const rt
 // still gets enough units to fill the chip.  The per-sample buffer holds the active tiles only (indexed by list position).
 // Shared by rtmi_render_adaptive and the entries of rtmi_adaptive_nee.h.  launch(blocks, tiles) enqueues the mode's
 // render kernel on s->stream for the pass fields of P over the active list `tiles` and returns an RTMI code; `kernel` is
-// the label of rtmi_stats.kernel.  The caller holds s->mu, has checked every argument, called begin_blocking and
-// adaptive_reserve and filled P with the mode's traversal plan.
+// the label of rtmi_stats.kernel, `wps` the waves per SIMD that kernel keeps resident (the persistent grid).  The caller
+// holds s->mu, has checked every argument, called begin_blocking and adaptive_reserve and filled P with the mode's
+// traversal plan.
 template <typename Launch>
 static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
-                          float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats,
-                          Launch &&launch) {
+                          uint32_t wps, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
+                          rtmi_stats *stats, Launch &&launch) {
     int rc;
     hipStream_t stream = s->stream;
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64;
-    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
+    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * wps;
     s->last_kernel = kernel;
 
     rtmi_progress_fn fn = reinterpret_cast<rtmi_progress_fn>(static_cast<uintptr_t>(p.progress_fn));
@@ -2056,6 +2058,10 @@ struct RenderCall {
     DevLights L;
     DevEnv E;
     bool fast = false;
+    // RTMI_FLAG_LIGHT_COOP (rtmi_light_coop.h): the estimator runs on the wave-cooperative kernel, with this pool form
+    // and this much dynamic LDS per block
+    bool coop = false, ext = false;
+    size_t coop_lds = 0;
 };
 
 // The end of an entry point's checks and the start of its device work, in this order: the handle, its lock, what the
@@ -2078,6 +2084,36 @@ static void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, 
     c.fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
     dev_lighting(s, m.nee, m.env, m.env_select_p, c.L, c.E);
 }
+// RTMI_FLAG_LIGHT_COOP (rtmi_light_coop.h), after kernel_args: the selection of the cooperative kernel (the rule of
+// rtmi_render_adaptive: level-0 scenes under fast-cull, no SYNC) and, where it runs, its traversal plan in c.P
+#define RTMI_LIGHT_COOP_KNOBS (RTMI_FLAG_LIGHT_COOP | (1u << 11))
+static uint32_t light_coop_bits(const rtmi_render_params *p) { // the bits the flag adds to an entry's accepted ones
+    return (p && (p->flags & RTMI_FLAG_LIGHT_COOP)) ? RTMI_LIGHT_COOP_KNOBS : 0u;
+}
+static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_params &p) {
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
+    c.coop = (p.flags & RTMI_FLAG_LIGHT_COOP) != 0u && c.fast && !(p.flags & RTMI_FLAG_SYNC) && coop_ok && !inst;
+    if (!c.coop) return RTMI_OK;
+    if (int rc = plan_traversal(s, &p, true, c.P, c.ext)) return rc;
+    if (p.flags & (1u << 11)) { // test knob, as in render_device_locked: a pool this small that it spills all the time
+        c.ext = true;
+        c.P.coop_cap = 256u;
+    }
+    c.coop_lds = (size_t)WAVES_PER_BLOCK * (2u * c.P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
+                                            (c.ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
+    return RTMI_OK;
+}
+// the persistent grid of the call's render kernel, in wavefronts: CUs x 4 SIMDs x the waves per SIMD it was compiled for
+static uint64_t light_run_slots(const rtmi_scene *s, const RenderCall &c) {
+    return (uint64_t)(s->slots / 20) * 4u * (c.coop ? (uint32_t)RTMI_LIGHT_COOP_WPS : 4u);
+}
+// the cooperative launch of a lighting entry's callable: the fixed render's pass (tiles = NULL) or one over the active list
+static int launch_light_coop(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks, const uint32_t *tiles) {
+    HIP_TRY(rtmi_light_coop_launch_render(tiles != nullptr, sig, c.ext, m.nee, m.env, blocks, c.coop_lds, s->stream, s->dev, c.C,
+                                          c.P, tiles, c.L, c.E));
+    return RTMI_OK;
+}
 // begin_call, adaptive sampling's buffers and the kernel arguments: what precedes adaptive_steps
 static int begin_adaptive(RenderCall &c, const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
                           const rtmi_adaptive *a) {
@@ -2087,7 +2123,8 @@ static int begin_adaptive(RenderCall &c, const Estimator &m, rtmi_scene *s, cons
     return RTMI_OK;
 }
 
-// The fixed-sample-count render of rtmi_render_nee and rtmi_render_env: the estimator's per-lane kernel (TILE_LIST = false)
+// The fixed-sample-count render of rtmi_render_nee and rtmi_render_env: the estimator's per-lane kernel, or under
+// RTMI_FLAG_LIGHT_COOP its cooperative one (c.coop: the callable launches that), TILE_LIST = false,
 // in passes of the render's plan; adaptive sampling's resolve over the list of all tiles carries sum, m and M2 between
 // passes and writes texels and standard errors after the last one.  launch(c, sig, blocks) enqueues the render kernel on
 // s->stream for the pass fields of c.P and returns an RTMI code.  The caller has checked every argument.
@@ -2107,12 +2144,13 @@ static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *ca
     if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
 
     kernel_args(c, m, s, cam, p);
+    if ((rc = plan_light_coop(c, s, p))) return rc;
     DevParams &P = c.P;
     P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
     const bool sig = out_path_sig != nullptr;
     P.path_sig = sig ? s->d_sig : nullptr;
-    const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
-    s->last_kernel = RTMI_KERNEL_PERLANE;
+    const uint64_t run_slots = light_run_slots(s, c);
+    s->last_kernel = c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
 
     if ((rc = begin_passes(s, stream))) return rc;
     if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
@@ -2171,7 +2209,7 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
     const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
     const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
                                                        (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
-    return adaptive_steps(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr,
+    return adaptive_steps(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, 4u, out_linear, out_rgb8, out_stderr,
                           out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
                               HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream, s->dev, c.C, P,
                                                                   tiles));
@@ -2388,13 +2426,13 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     return RTMI_OK;
 }
 
-// The per-lane NEE kernel (rtmi_nee.hip) in render_fixed.
+// The per-lane NEE kernel (rtmi_nee.hip), or the cooperative one (rtmi_light_coop.hip), in render_fixed.
 extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
                                uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     // every argument check comes before the first use of the device
     if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG,
+                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG | light_coop_bits(p_in),
                                "NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
                                "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                                "NEE renders the whole image: tile_world must be 1");
@@ -2403,6 +2441,7 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
                       "no light table attached (rtmi_scene_attach_lights)"};
     return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
                         [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
+                            if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
                             HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L));
                             return RTMI_OK;
                         });
@@ -2439,7 +2478,7 @@ extern "C" int rtmi_scene_attach_env(rtmi_scene *s, const rtmi_env_map *map) {
     return RTMI_OK;
 }
 
-// The per-lane environment kernel (rtmi_env.hip) in render_fixed.
+// The per-lane environment kernel (rtmi_env.hip), or the cooperative one (rtmi_light_coop.hip), in render_fixed.
 extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, const rtmi_env_render *opts,
                                float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     // every argument check comes before the first use of the device
@@ -2448,7 +2487,7 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     int rc;
     if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in))) return rc;
     rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK |
-                                     RTMI_FLAG_PATH_SIG,
+                                     RTMI_FLAG_PATH_SIG | light_coop_bits(p_in),
                            "environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD, UV_BOOK and PATH_SIG "
                            "only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                            "environment renders render the whole image: tile_world must be 1");
@@ -2458,22 +2497,27 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
                       "nee = 1 needs the light table (rtmi_scene_attach_lights)"};
     return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
                         [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
+                            if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
                             HIP_TRY(rtmi_env_launch_render(c.fast, sig, nee, blocks, s->stream, s->dev, c.C, c.P, c.L, c.E));
                             return RTMI_OK;
                         });
 }
 
 // ---- adaptive sampling with NEE or environment lighting (include/rtmi_adaptive_nee.h) ---------------------------------
-// adaptive sampling's step loop (adaptive_steps) with the per-lane kernel of rtmi_adaptive_nee.hip: rtmi_render_nee's or
-// rtmi_render_env's estimator over the active-tile list
+// adaptive sampling's step loop (adaptive_steps) with the per-lane kernel of rtmi_adaptive_nee.hip, or under
+// RTMI_FLAG_LIGHT_COOP the cooperative one of rtmi_light_coop.hip: rtmi_render_nee's or rtmi_render_env's estimator over
+// the active-tile list
 #define RTMI_ADAPTIVE_NEE_FLAGS (RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK)
 static int adaptive_lit(const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
                         const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
                         rtmi_stats *stats) {
     RenderCall c;
-    if (int rc = begin_adaptive(c, m, s, cam, p, a)) return rc;
-    return adaptive_steps(s, p, a, c.P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+    int rc;
+    if ((rc = begin_adaptive(c, m, s, cam, p, a)) || (rc = plan_light_coop(c, s, p))) return rc;
+    return adaptive_steps(s, p, a, c.P, c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE,
+                          c.coop ? (uint32_t)RTMI_LIGHT_COOP_WPS : 4u, out_linear, out_rgb8, out_stderr, out_spp, stats,
                           [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                              if (c.coop) return launch_light_coop(c, m, s, false, blocks, tiles);
                               HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, m.nee, m.env, blocks, s->stream, s->dev, c.C,
                                                                       c.P, tiles, c.L, c.E));
                               return RTMI_OK;
@@ -2485,7 +2529,7 @@ extern "C" int rtmi_render_adaptive_nee(rtmi_scene *s, const rtmi_camera *cam, c
                                         uint32_t *out_spp, rtmi_stats *stats) {
     // every argument check comes before the first use of the handle (and of the device)
     if (!p_in || !a || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY,
+    int rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY | light_coop_bits(p_in),
                                "adaptive NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK only "
                                "(not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                                "adaptive NEE renders the whole image: tile_world must be 1");
@@ -2503,7 +2547,7 @@ extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, c
     const char *name = "rtmi_render_adaptive_env";
     int rc;
     if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in))) return rc;
-    rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS,
+    rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | light_coop_bits(p_in),
                            "adaptive environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD and UV_BOOK "
                            "only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                            "adaptive environment renders render the whole image: tile_world must be 1");
@@ -2549,7 +2593,7 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     if ((rc = grow(s, s->rr_bounces, s->rr_bytes, ntex * sizeof(uint32_t)))) return rc;
     HIP_TRY(hipMemsetAsync(s->rr_bounces, 0, ntex * sizeof(uint32_t), s->stream));
     const DevRoulette R{s->rr_bounces, o->min_depth, o->q_min};
-    rc = adaptive_steps(s, p, a, c.P, RTMI_KERNEL_PERLANE, out_linear, out_rgb8, out_stderr, out_spp, stats,
+    rc = adaptive_steps(s, p, a, c.P, RTMI_KERNEL_PERLANE, 4u, out_linear, out_rgb8, out_stderr, out_spp, stats,
                         [&](uint32_t blocks, const uint32_t *tiles) -> int {
                             HIP_TRY(rtmi_roulette_launch_render(c.fast, nee, env, blocks, s->stream, s->dev, c.C, c.P, tiles,
                                                                 c.L, c.E, R));

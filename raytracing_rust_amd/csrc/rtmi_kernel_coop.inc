@@ -1,7 +1,9 @@
 // rtmi_kernel_coop.inc — body of the wave-cooperative render kernel (rtmi_kernels.hpp), included INSIDE the kernels that
-// run it: rtmi_render_coop (TILE_LIST = false) and the adaptive-sampling kernel rtmi_adaptive_coop (rtmi_adaptive.hip,
-// TILE_LIST = true).  The including function provides sc, cam, P, SIG, PROF, WPS, EXT, INSTL, TILE_LIST and `tiles`; see
-// rtmi_kernel_perlane.inc for why this is a textual body.
+// run it: rtmi_render_coop (TILE_LIST = false), the adaptive-sampling kernel rtmi_adaptive_coop (rtmi_adaptive.hip,
+// TILE_LIST = true) and the lighting kernels of rtmi_light_coop.hip (NEE / ENV, include/rtmi_light_coop.h).  The including
+// function provides sc, cam, P, SIG, PROF, EXT, INSTL, TILE_LIST, NEE, ENV, `tiles`, `nl` and `ev`; see
+// rtmi_kernel_perlane.inc for why this is a textual body and for what NEE and ENV mean: the lane-level logic of a pending
+// shadow ray (NeeLane, the two swapped Philox states) and of the map is that body's, around this body's item scan.
     constexpr bool INST = INSTL >= 1; // instanced primitives, media inside transforms
     constexpr bool INSD = INSTL >= 2; // DEFERRED items, list scans, nested media
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
@@ -43,9 +45,19 @@
     uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
     bool alive = false, done = false, have_hit = false, overflow = false;
     // lean instantiation (scenes without alternative trees): word ring in LDS behind pool | ctx | best
-    typename std::conditional<EXT, RngReg, RngRing>::type g;
+    // (NEE: the register RNG with the stream id in both pool forms; the ring's words stay unused)
+    typename std::conditional<NEE, RngNee, typename std::conditional<EXT, RngReg, RngRing>::type>::type g;
     rng_attach(g, cw.wlds + 2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS);
     rng_init(g, 0, 0);
+    NeeLane ne;
+    decltype(g) gn; // NEE: the light-sample stream (swapped with g for a shadow ray)
+    if constexpr (NEE) {
+        rng_set_stream(g, 0u);
+        rng_init(gn, 0, 0);
+        rng_set_stream(gn, 3u);
+        ne.cont_rd = f3(0, 0, 1); ne.c = f3(0, 0, 0); ne.pb = 0.0f; ne.light = 0; ne.shadow = false;
+        if constexpr (ENV) ne.env = false;
+    }
     Path pa;
     pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
     float closest = RTMI_FLT_MAX;
@@ -64,6 +76,7 @@
                     uint32_t smp = 0u, px = 0u, j = 0u;
                     if (work_take<TILE_LIST>(w, queue_empty, want, P, oidx, ltile, smp, px, j, tiles)) {
                         camera_sample(cam, P, g, k0, k1, smp, j * P.nx + px, px, j, pa);
+                        if constexpr (NEE) { rng_init(gn, smp, j * P.nx + px); ne.pb = 0.0f; }
                         alive = true;
                     } else if (want) {
                         done = true;
@@ -175,7 +188,28 @@
             if (need) {
                 if (best_item >= 0) {
                     have_hit = true;
+                } else if (NEE && ne.shadow) { // the shadow ray left the world: V = 0; the path goes on
+                    if constexpr (NEE) {
+                        if constexpr (ENV) { // ... unless it aims at the map: V = 1
+                            float eu, evv, eth;
+                            if (ne.env && env_uv(pa.rd, eu, evv, eth)) pa.L = pa.L + ne.c * env_radiance(ev, eu, evv);
+                        }
+                        pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t;
+                    }
                 } else { // miss: black background (color.rs:21)
+                    if constexpr (ENV) { // the map, weighted by MIS after a diffuse scatter that took a light sample
+                        float eu, evv, eth;
+                        if (env_uv(pa.rd, eu, evv, eth)) {
+                            float w = 1.0f;
+                            if constexpr (NEE) {
+                                if (ne.pb > 0.0f) {
+                                    const float pe = env_pdf(ev, eu, evv, eth);
+                                    if (pe > 0.0f) w = nee_mis_bsdf(ne.pb, pe);
+                                }
+                            }
+                            pa.L = pa.L + pa.T * (env_radiance(ev, eu, evv) * w);
+                        }
+                    } else
                     if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
                     path_end(P, oidx, pa);
                     if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
@@ -190,14 +224,33 @@
         {
             const bool shading = have_hit;
             have_hit = false;
-            if (SIG && shading) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
+            if (SIG && shading && !(NEE && ne.shadow)) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
             // all lanes call (wavefront texture lookup); the traversal pool is idle now: LDS scratch
+            if constexpr (NEE) {
+                const bool was_shadow = ne.shadow;
+                const bool goes_on = shade_hit<decltype(g), INST, false, true, ENV>(
+                    sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
+                    reinterpret_cast<float *>(cw.wlds), nullptr, &nl, &ne, &gn, &ev);
+                if (shading) {
+                    if (was_shadow) { // the light sample is counted: the path's continuation is traced next
+                        pa.rd = ne.cont_rd; ne.shadow = false;
+                        const auto t = g; g = gn; gn = t;
+                    } else if (!goes_on) {
+                        path_end(P, oidx, pa);
+                        if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
+                        alive = false;
+                    } else if (ne.shadow) { // a shadow ray was sampled: trace it with the light-sample stream
+                        const auto t = g; g = gn; gn = t;
+                    }
+                }
+            } else {
             const bool goes_on = shade_hit<decltype(g), INST>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
                                            reinterpret_cast<float *>(cw.wlds));
             if (shading && !goes_on) {
                 path_end(P, oidx, pa);
                 if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                 alive = false;
+            }
             }
         }
         prof_time<PROF>(prof, 30, tstamp); // shading

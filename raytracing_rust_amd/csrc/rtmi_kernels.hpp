@@ -36,7 +36,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_render_kernel(DevSc
 // primitives).  Forced on the BASELINE scenes level 2 costs 10-14 % (profiles/r04_experiments/force_inst_ab.log), hence two levels.
 template <bool SIG, bool PROF, int WPS, bool EXT, int INSTL>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, WPS) void rtmi_render_coop(DevScene sc, DevCamera cam, DevParams P) {
-    constexpr bool TILE_LIST = false;
+    constexpr bool TILE_LIST = false, NEE = false, ENV = false;
+    const DevLights nl{};
+    const DevEnv ev{};
     const uint32_t *const tiles = nullptr;
 #include "rtmi_kernel_coop.inc"
 }

@@ -41,6 +41,18 @@ hipError_t rtmi_adaptive_nee_launch_render(bool fast, bool nee, bool env, uint32
                                            const DevCamera &cam, const DevParams &P, const uint32_t *tiles, const DevLights &L,
                                            const DevEnv &E);
 
+// RTMI_FLAG_LIGHT_COOP (include/rtmi_light_coop.h, rtmi_light_coop.hip): the estimators above on the wave-cooperative
+// kernel.  tile_list: one pass over the P.ntiles_local active tiles of `tiles` (no signatures), otherwise the fixed render's
+// pass; ext: the pool form of plan_traversal; lds: the dynamic LDS of a block (the formula of rtmi_render_coop's launch);
+// nee / env not both false.  The kernels are compiled for RTMI_LIGHT_COOP_WPS waves per SIMD: the persistent grid is
+// CUs x 4 SIMDs x that many wavefronts.
+#ifndef RTMI_LIGHT_COOP_WPS
+#define RTMI_LIGHT_COOP_WPS 3
+#endif
+hipError_t rtmi_light_coop_launch_render(bool tile_list, bool sig, bool ext, bool nee, bool env, uint32_t blocks, size_t lds,
+                                         hipStream_t stream, const DevScene &sc, const DevCamera &cam, const DevParams &P,
+                                         const uint32_t *tiles, const DevLights &L, const DevEnv &E);
+
 // the roulette parameters and the bounce plane: a kernel argument of their own, as DevLights and DevEnv are (DevParams
 // goes to every kernel)
 struct DevRoulette {
