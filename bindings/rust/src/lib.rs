@@ -192,6 +192,7 @@ pub struct RouletteImage {
 impl Scene {
     /// Blocking whole-image render with Russian-roulette path termination (rtmi_render_roulette).  The NEE estimators
     /// need the light table, the map estimators the map, attached to the scene beforehand.
+    /// `p.flags | sys::RTMI_FLAG_ROULETTE_COOP` (include/rtmi_roulette_coop.h) traces on the wave-cooperative kernel: same bits.
     pub fn render_roulette(&mut self, cam: &RtmiCamera, p: &RtmiRenderParams, opts: &RtmiRoulette) -> Result<RouletteImage, RtmiError> {
         let (nx, ny) = (p.nx as usize, p.ny as usize);
         let image = Image { nx, ny, linear: vec![0.0; nx * ny * 3], rgb8: vec![0; nx * ny * 3], stats: RtmiStats::default() };

@@ -20,6 +20,7 @@ pub const RTMI_FLAG_UV_BOOK: u32 = 4096;
 pub const RTMI_FLAG_PROGRESSIVE: u32 = 16384;
 /// include/rtmi_light_coop.h: the NEE / environment entries trace on the wave-cooperative kernel (same bits)
 pub const RTMI_FLAG_LIGHT_COOP: u32 = 65536;
+pub const RTMI_FLAG_ROULETTE_COOP: u32 = 131072;
 pub const RTMI_OK: i32 = 0;
 pub const RTMI_ERR_INVALID: i32 = 1;
 pub const RTMI_ERR_UNSUPPORTED: i32 = 2;

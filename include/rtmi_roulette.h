@@ -43,7 +43,8 @@
  * Outputs, standard errors (Welford, as rtmi_adaptive.h), passes, progress and cancellation: those of rtmi_render_nee
  * (rtmi_render_roulette) and rtmi_render_adaptive_nee (rtmi_render_adaptive_roulette).  Results do not depend on
  * FAST_CULL, SYNC, REF_TREE, shade_threshold or sample_buffer_bytes.  Both run the per-lane kernel
- * (stats.kernel = RTMI_KERNEL_PERLANE).
+ * (stats.kernel = RTMI_KERNEL_PERLANE).  include/rtmi_roulette_coop.h adds an opt-in flag that runs them on the
+ * wave-cooperative kernel, with the same bits.
  *
  * Adaptive form.  rtmi_adaptive.h's steps and convergence test on the roulette estimator.  The roulette stream is keyed
  * by (seed, sample, pixel, depth) as well, so a tile that stops at n samples is bit for bit, in linear, rgb8, stderr and

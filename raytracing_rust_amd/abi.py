@@ -31,6 +31,7 @@ RTMI_FLAG_UV_BOOK = 4096
 RTMI_FLAG_TEST_OVERFLOW = 8192
 RTMI_FLAG_PROGRESSIVE = 16384  # opt-in: the framebuffer holds the image of the samples so far after every pass
 RTMI_FLAG_LIGHT_COOP = 65536  # include/rtmi_light_coop.h: NEE / environment renders on the wave-cooperative kernel
+RTMI_FLAG_ROULETTE_COOP = 131072  # include/rtmi_roulette_coop.h: roulette renders on the wave-cooperative kernel
 RTMI_ERR_DEVICE = 3
 RTMI_ERR_CANCELLED = 5
 RTMI_TEXEL_POISON = 0x80000000

@@ -47,6 +47,7 @@
 #include "rtmi_adaptive_nee.h"
 #include "rtmi_roulette.h"
 #include "rtmi_light_coop.h"
+#include "rtmi_roulette_coop.h"
 #include "rtmi_light_launch.hpp"
 
 // ======================================================================================
@@ -2058,10 +2059,12 @@ struct RenderCall {
     DevLights L;
     DevEnv E;
     bool fast = false;
-    // RTMI_FLAG_LIGHT_COOP (rtmi_light_coop.h): the estimator runs on the wave-cooperative kernel, with this pool form
-    // and this much dynamic LDS per block
+    // RTMI_FLAG_LIGHT_COOP (rtmi_light_coop.h), RTMI_FLAG_ROULETTE_COOP (rtmi_roulette_coop.h): the estimator runs on the
+    // wave-cooperative kernel, with this pool form and this much dynamic LDS per block; wps: the waves per SIMD the call's
+    // render kernel was compiled for
     bool coop = false, ext = false;
     size_t coop_lds = 0;
+    uint32_t wps = 4u;
 };
 
 // The end of an entry point's checks and the start of its device work, in this order: the handle, its lock, what the
@@ -2085,16 +2088,19 @@ static void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, 
     dev_lighting(s, m.nee, m.env, m.env_select_p, c.L, c.E);
 }
 // RTMI_FLAG_LIGHT_COOP (rtmi_light_coop.h), after kernel_args: the selection of the cooperative kernel (the rule of
-// rtmi_render_adaptive: level-0 scenes under fast-cull, no SYNC) and, where it runs, its traversal plan in c.P
-#define RTMI_LIGHT_COOP_KNOBS (RTMI_FLAG_LIGHT_COOP | (1u << 11))
-static uint32_t light_coop_bits(const rtmi_render_params *p) { // the bits the flag adds to an entry's accepted ones
-    return (p && (p->flags & RTMI_FLAG_LIGHT_COOP)) ? RTMI_LIGHT_COOP_KNOBS : 0u;
+// rtmi_render_adaptive: level-0 scenes under fast-cull, no SYNC) and, where it runs, its traversal plan in c.P.
+// RTMI_FLAG_ROULETTE_COOP (rtmi_roulette_coop.h) is the same rule under the roulette entries' flag: `flag` names the
+// entry's own bit, `wps` the waves per SIMD its cooperative kernel was compiled for.
+static uint32_t light_coop_bits(const rtmi_render_params *p, uint32_t flag = RTMI_FLAG_LIGHT_COOP) { // the bits the flag adds to an entry's accepted ones
+    return (p && (p->flags & flag)) ? (flag | (1u << 11)) : 0u;
 }
-static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_params &p) {
+static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_params &p, uint32_t flag = RTMI_FLAG_LIGHT_COOP,
+                           uint32_t wps = RTMI_LIGHT_COOP_WPS) {
     const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
-    c.coop = (p.flags & RTMI_FLAG_LIGHT_COOP) != 0u && c.fast && !(p.flags & RTMI_FLAG_SYNC) && coop_ok && !inst;
+    c.coop = (p.flags & flag) != 0u && c.fast && !(p.flags & RTMI_FLAG_SYNC) && coop_ok && !inst;
     if (!c.coop) return RTMI_OK;
+    c.wps = wps;
     if (int rc = plan_traversal(s, &p, true, c.P, c.ext)) return rc;
     if (p.flags & (1u << 11)) { // test knob, as in render_device_locked: a pool this small that it spills all the time
         c.ext = true;
@@ -2106,7 +2112,7 @@ static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_param
 }
 // the persistent grid of the call's render kernel, in wavefronts: CUs x 4 SIMDs x the waves per SIMD it was compiled for
 static uint64_t light_run_slots(const rtmi_scene *s, const RenderCall &c) {
-    return (uint64_t)(s->slots / 20) * 4u * (c.coop ? (uint32_t)RTMI_LIGHT_COOP_WPS : 4u);
+    return (uint64_t)(s->slots / 20) * 4u * c.wps;
 }
 // the cooperative launch of a lighting entry's callable: the fixed render's pass (tiles = NULL) or one over the active list
 static int launch_light_coop(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks, const uint32_t *tiles) {
@@ -2514,9 +2520,8 @@ static int adaptive_lit(const Estimator &m, rtmi_scene *s, const rtmi_camera *ca
     RenderCall c;
     int rc;
     if ((rc = begin_adaptive(c, m, s, cam, p, a)) || (rc = plan_light_coop(c, s, p))) return rc;
-    return adaptive_steps(s, p, a, c.P, c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE,
-                          c.coop ? (uint32_t)RTMI_LIGHT_COOP_WPS : 4u, out_linear, out_rgb8, out_stderr, out_spp, stats,
-                          [&](uint32_t blocks, const uint32_t *tiles) -> int {
+    return adaptive_steps(s, p, a, c.P, c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, c.wps, out_linear, out_rgb8,
+                          out_stderr, out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
                               if (c.coop) return launch_light_coop(c, m, s, false, blocks, tiles);
                               HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, m.nee, m.env, blocks, s->stream, s->dev, c.C,
                                                                       c.P, tiles, c.L, c.E));
@@ -2558,7 +2563,8 @@ extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, c
 }
 
 // ---- Russian-roulette path termination (include/rtmi_roulette.h) ------------------------------------------------------
-// Both entries are adaptive sampling's step loop (adaptive_steps) over the per-lane kernels of rtmi_roulette.hip; the
+// Both entries are adaptive sampling's step loop (adaptive_steps) over the per-lane kernels of rtmi_roulette.hip, or under
+// RTMI_FLAG_ROULETTE_COOP (rtmi_roulette_coop.h) the cooperative ones of rtmi_roulette_coop.hip (plan_light_coop); the
 // fixed render is the single step of ns samples over the list of all tiles (tolerances 0: every tile retires at ns), as
 // the resolve of render_fixed.  `a` = NULL: the fixed entry.
 static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
@@ -2580,7 +2586,9 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     const std::string flags_msg = nm + "roulette renders accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK "
                                        "only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)";
     const std::string world_msg = nm + "roulette renders render the whole image: tile_world must be 1";
-    if ((rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY, flags_msg.c_str(), world_msg.c_str()))) return rc;
+    if ((rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY | light_coop_bits(p_in, RTMI_FLAG_ROULETTE_COOP),
+                                flags_msg.c_str(), world_msg.c_str())))
+        return rc;
     if (a && (rc = check_adaptive(p_in, a))) return rc;
     const rtmi_render_params &p = *p_in;
     const rtmi_adaptive fixed{p.ns, 1u, 0.0, 0.0}; // one step of ns samples
@@ -2588,13 +2596,20 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     const Estimator m{name, nee, env, nee && env ? o->env_select_p : 1.0f, null_scene.c_str(),
                       "no light table attached (rtmi_scene_attach_lights)"};
     RenderCall c;
-    if ((rc = begin_adaptive(c, m, s, cam, p, a))) return rc;
+    if ((rc = begin_adaptive(c, m, s, cam, p, a)) ||
+        (rc = plan_light_coop(c, s, p, RTMI_FLAG_ROULETTE_COOP, rtmi_roulette_coop_wps(nee, env))))
+        return rc;
     const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
     if ((rc = grow(s, s->rr_bounces, s->rr_bytes, ntex * sizeof(uint32_t)))) return rc;
     HIP_TRY(hipMemsetAsync(s->rr_bounces, 0, ntex * sizeof(uint32_t), s->stream));
     const DevRoulette R{s->rr_bounces, o->min_depth, o->q_min};
-    rc = adaptive_steps(s, p, a, c.P, RTMI_KERNEL_PERLANE, 4u, out_linear, out_rgb8, out_stderr, out_spp, stats,
-                        [&](uint32_t blocks, const uint32_t *tiles) -> int {
+    rc = adaptive_steps(s, p, a, c.P, c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, c.wps, out_linear, out_rgb8,
+                        out_stderr, out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                            if (c.coop) {
+                                HIP_TRY(rtmi_roulette_coop_launch_render(c.ext, nee, env, blocks, c.coop_lds, s->stream, s->dev,
+                                                                         c.C, c.P, tiles, c.L, c.E, R));
+                                return RTMI_OK;
+                            }
                             HIP_TRY(rtmi_roulette_launch_render(c.fast, nee, env, blocks, s->stream, s->dev, c.C, c.P, tiles,
                                                                 c.L, c.E, R));
                             return RTMI_OK;

@@ -4,6 +4,9 @@
 // function provides sc, cam, P, SIG, PROF, EXT, INSTL, TILE_LIST, NEE, ENV, `tiles`, `nl` and `ev`; see
 // rtmi_kernel_perlane.inc for why this is a textual body and for what NEE and ENV mean: the lane-level logic of a pending
 // shadow ray (NeeLane, the two swapped Philox states) and of the map is that body's, around this body's item scan.
+// RR (rtmi_roulette_coop_kernel, rtmi_roulette_coop.hip; include/rtmi_roulette_coop.h) is a preprocessor switch as
+// RTMI_PERLANE_RR is there, and for its reason: without RTMI_COOP_RR this text is what it was.  With it the including
+// function also provides `rr` (DevRoulette) and rtmi_roulette_dev.hpp; the statements are that body's, at the same places.
     constexpr bool INST = INSTL >= 1; // instanced primitives, media inside transforms
     constexpr bool INSD = INSTL >= 2; // DEFERRED items, list scans, nested media
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
@@ -50,6 +53,9 @@
     rng_attach(g, cw.wlds + 2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS);
     rng_init(g, 0, 0);
     NeeLane ne;
+#ifdef RTMI_COOP_RR
+    bool rr_end = false; // the path ends after its pending shadow ray
+#endif
     decltype(g) gn; // NEE: the light-sample stream (swapped with g for a shadow ray)
     if constexpr (NEE) {
         rng_set_stream(g, 0u);
@@ -195,6 +201,9 @@
                             if (ne.env && env_uv(pa.rd, eu, evv, eth)) pa.L = pa.L + ne.c * env_radiance(ev, eu, evv);
                         }
                         pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t;
+#ifdef RTMI_COOP_RR
+                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
+#endif
                     }
                 } else { // miss: black background (color.rs:21)
                     if constexpr (ENV) { // the map, weighted by MIS after a diffuse scatter that took a light sample
@@ -212,6 +221,9 @@
                     } else
                     if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
                     path_end(P, oidx, pa);
+#ifdef RTMI_COOP_RR
+                    RTMI_RR_COUNT();
+#endif
                     if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                     alive = false;
                 }
@@ -235,10 +247,25 @@
                     if (was_shadow) { // the light sample is counted: the path's continuation is traced next
                         pa.rd = ne.cont_rd; ne.shadow = false;
                         const auto t = g; g = gn; gn = t;
+#ifdef RTMI_COOP_RR
+                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
+#endif
                     } else if (!goes_on) {
                         path_end(P, oidx, pa);
+#ifdef RTMI_COOP_RR
+                        RTMI_RR_COUNT();
+#endif
                         if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                         alive = false;
+#ifdef RTMI_COOP_RR
+                    } else if (!roulette_survives(rr, g, k0, k1, pa)) { // g is still the path's stream here
+                        if (ne.shadow) { // the vertex's light sample is still traced and counted
+                            rr_end = true;
+                            const auto t = g; g = gn; gn = t;
+                        } else {
+                            RTMI_RR_END_PATH();
+                        }
+#endif
                     } else if (ne.shadow) { // a shadow ray was sampled: trace it with the light-sample stream
                         const auto t = g; g = gn; gn = t;
                     }
@@ -248,9 +275,17 @@
                                            reinterpret_cast<float *>(cw.wlds));
             if (shading && !goes_on) {
                 path_end(P, oidx, pa);
+#ifdef RTMI_COOP_RR
+                RTMI_RR_COUNT();
+#endif
                 if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
                 alive = false;
             }
+#ifdef RTMI_COOP_RR
+            else if (shading && !roulette_survives(rr, g, k0, k1, pa)) {
+                RTMI_RR_END_PATH();
+            }
+#endif
             }
         }
         prof_time<PROF>(prof, 30, tstamp); // shading

@@ -65,3 +65,17 @@ struct DevRoulette {
 hipError_t rtmi_roulette_launch_render(bool fast, bool nee, bool env, uint32_t blocks, hipStream_t stream, const DevScene &sc,
                                        const DevCamera &cam, const DevParams &P, const uint32_t *tiles, const DevLights &L,
                                        const DevEnv &E, const DevRoulette &R);
+
+// RTMI_FLAG_ROULETTE_COOP (include/rtmi_roulette_coop.h, rtmi_roulette_coop.hip): the same pass on the wave-cooperative
+// kernel.  ext / lds as in rtmi_light_coop_launch_render.  The NEE / ENV kernels are compiled for RTMI_LIGHT_COOP_WPS waves
+// per SIMD, the two plain ones for RTMI_ROULETTE_COOP_PLAIN_WPS (4 as rtmi_adaptive_coop: they keep no NeeLane, no second
+// stream and no map, and fit without scratch): the host sizes the persistent grid per kernel.
+#ifndef RTMI_ROULETTE_COOP_PLAIN_WPS
+#define RTMI_ROULETTE_COOP_PLAIN_WPS 4
+#endif
+constexpr uint32_t rtmi_roulette_coop_wps(bool nee, bool env) {
+    return nee || env ? (uint32_t)RTMI_LIGHT_COOP_WPS : (uint32_t)RTMI_ROULETTE_COOP_PLAIN_WPS;
+}
+hipError_t rtmi_roulette_coop_launch_render(bool ext, bool nee, bool env, uint32_t blocks, size_t lds, hipStream_t stream,
+                                            const DevScene &sc, const DevCamera &cam, const DevParams &P, const uint32_t *tiles,
+                                            const DevLights &L, const DevEnv &E, const DevRoulette &R);

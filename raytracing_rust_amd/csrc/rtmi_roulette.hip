@@ -19,30 +19,9 @@
 #include "rtmi_kernels.hpp"
 #include "rtmi_light_launch.hpp"
 
-// The roulette test of rtmi_roulette.h, after a scatter has updated pa.T and pa.depth; g is the path's stream-0 state
-// (its sample and pixel words key the stateless stream-4 draw).  false: the continuation ends.
-template <typename RngT>
-__device__ __forceinline__ bool roulette_survives(const DevRoulette &rr, const RngT &g, uint32_t k0, uint32_t k1, Path &pa) {
-    if (pa.depth < rr.min_depth) return true;
-    const float m = fmaxf(fmaxf(pa.T.x, pa.T.y), pa.T.z);
-    if (m == 0.0f) return false;
-    const float q = fminf(fmaxf(m, rr.q_min), 1.0f);
-    if (q < 1.0f) {
-        uint32_t o0, o1, o2, o3;
-        philox(pa.depth, g.sample, g.pixel, 4u, k0, k1, o0, o1, o2, o3);
-        if (!(rtmi_u01(o0) < q)) return false;
-        pa.T = vdiv(pa.T, q);
-    }
-    return true;
-}
+#include "rtmi_roulette_dev.hpp" // roulette_survives, RTMI_RR_COUNT(), RTMI_RR_END_PATH(): shared with rtmi_roulette_coop.hip
 
 #define RTMI_PERLANE_RR 1
-// the two statements the body uses where a roulette kernel writes a path: the bounce count (tiled as the path signatures;
-// a path that never scattered adds nothing) and the whole ending of a path that roulette cut
-#define RTMI_RR_COUNT() \
-    do { if (pa.depth != 0u) atomicAdd(rr.bounces + (size_t)ltile * 64 + (oidx & 63u), pa.depth); } while (0)
-#define RTMI_RR_END_PATH() \
-    do { path_end(P, oidx, pa); RTMI_RR_COUNT(); alive = false; } while (0)
 template <bool FAST, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_roulette_kernel(DevScene sc, DevCamera cam, DevParams P,
                                                                             const uint32_t *tiles, DevLights nl, DevEnv ev,
@@ -50,8 +29,6 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_roulette_kernel(Dev
     constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false;
 #include "rtmi_kernel_perlane.inc"
 }
-#undef RTMI_RR_END_PATH
-#undef RTMI_RR_COUNT
 #undef RTMI_PERLANE_RR
 
 hipError_t rtmi_roulette_launch_render(bool fast, bool nee, bool env, uint32_t blocks, hipStream_t stream, const DevScene &sc,

@@ -77,10 +77,11 @@ def default_params(nx, ny, ns, seed=42, flags=0, max_depth=50, t_min=0.001, tile
     return p
 
 
-def _coop_flags(kw, coop):
-    """coop=True of the lighting renders: ORs RTMI_FLAG_LIGHT_COOP (include/rtmi_light_coop.h) into the keyword `flags`."""
+def _coop_flags(kw, coop, flag=abi.RTMI_FLAG_LIGHT_COOP):
+    """coop=True of the lighting renders: ORs RTMI_FLAG_LIGHT_COOP (include/rtmi_light_coop.h) into the keyword `flags`;
+    the roulette renders pass their own flag, RTMI_FLAG_ROULETTE_COOP (include/rtmi_roulette_coop.h)."""
     if coop:
-        kw["flags"] = int(kw.get("flags", 0)) | abi.RTMI_FLAG_LIGHT_COOP
+        kw["flags"] = int(kw.get("flags", 0)) | flag
     return kw
 
 
@@ -355,15 +356,20 @@ class Scene:
         return abi.Roulette(abi.ROULETTE_ESTIMATORS[estimator], min_depth, q_min, env_select_p)
 
     def render_roulette(self, cam, nx, ny, ns, estimator="nee", min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32",
-                        **kw):
+                        coop=False, **kw):
         """Russian-roulette path termination (include/rtmi_roulette.h): the paths of render(), each ended after a scatter
         at depth >= min_depth with probability 1 - q, q = clamp(largest channel of the throughput, q_min, 1), the
         survivors weighted 1 / q.  estimator: "plain" (render), "nee" (render_nee), "env" (render_env(nee=False)) or
         "env_nee" (render_env(nee=True, env_select_p)).  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], stderr f32
         [ny,nx,3], bounces u32 [ny,nx] = the scatters of the pixel's paths, summed, stats).  min_depth > max_depth or
-        q_min = 1 gives the named render bit for bit."""
+        q_min = 1 gives the named render bit for bit.
+        coop=True (RTMI_FLAG_ROULETTE_COOP, include/rtmi_roulette_coop.h): under RTMI_FLAG_FAST_CULL the wave-cooperative
+        kernel traces the same paths; every plane, bounces included, has the same bits, stats["kernel"] tells which kernel
+        ran (scenes with instanced primitives or media under transforms, SYNC and renders without FAST_CULL stay
+        per-lane).  Timing: DESIGN.md §20."""
         if precision != "f32":
             raise Unsupported("Russian roulette has no f64 mode")
+        _coop_flags(kw, coop, abi.RTMI_FLAG_ROULETTE_COOP)
         o = self._roulette_opts(estimator, min_depth, q_min, env_select_p, kw)
         p = default_params(nx, ny, ns, **kw)
         out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr", "bounces"))
@@ -371,12 +377,15 @@ class Scene:
         return _result(out)
 
     def render_adaptive_roulette(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, estimator="nee",
-                                 min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32", **kw):
+                                 min_depth=3, q_min=0.05, env_select_p=0.5, precision="f32", coop=False,
+                                 **kw):
         """render_roulette under the noise target of render_adaptive (ns is the cap).  Returns render_roulette's dict plus
         spp u32 [ny,nx]; a tile that stops at n samples is bit for bit, bounces included, that tile of
-        render_roulette(ns=n)."""
+        render_roulette(ns=n).  coop=True (RTMI_FLAG_ROULETTE_COOP): as in render_roulette, same bits, spp included, on the
+        wave-cooperative kernel."""
         if precision != "f32":
             raise Unsupported("Russian roulette has no f64 mode")
+        _coop_flags(kw, coop, abi.RTMI_FLAG_ROULETTE_COOP)
         o = self._roulette_opts(estimator, min_depth, q_min, env_select_p, kw)
         p = default_params(nx, ny, ns, **kw)
         a = abi.Adaptive(min_spp, step_spp, abs_tol, rel_tol)
