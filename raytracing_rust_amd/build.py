@@ -66,10 +66,9 @@ def _hipcc():
     return shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
-def build_rtmi(force=False, verbose=False):
-    if not force and not _stale(LIBRTMI, RTMI_DEPS):
-        return LIBRTMI
-    os.makedirs(LIB_DIR, exist_ok=True)
+def unit_command(maxocc, build_hash, include=INCLUDE, verbose=False):
+    """The hipcc command line of one translation unit of librtmi.so, up to its own arguments (-c / -S, source, output).
+    `maxocc`: the unit's entry in _RTMI_UNITS.  build_rtmi and tools/device_asm.py both compile with it."""
     # -fno-slp-vectorize: ROCm 7.2's SLP vectoriser packs the scalar F3 arithmetic into v_pk_mul/add_f32 and gets the
     # operand selection wrong in at least one place (hit point/normal of a sphere under Rotate about Z: every
     # pixel differed from the oracle, found by tests/test_random_scenes.py; fine with the function out of line,
@@ -83,14 +82,20 @@ def build_rtmi(force=False, verbose=False):
     # translation unit of their own (csrc/rtmi_lean.hip) with the default one.
     extra = os.environ.get("RTMI_EXTRA_CFLAGS", "").split()
     sched = [] if os.environ.get("RTMI_DEFAULT_SCHED") else ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]
-    common = [_hipcc()] + _COMMON_FLAGS + ["-I" + INCLUDE, '-DRTMI_BUILD_HASH="%s"' % source_hash()]
-    if verbose:
-        common.insert(1, "-Rpass-analysis=kernel-resource-usage")
+    analysis = ["-Rpass-analysis=kernel-resource-usage"] if verbose else []
+    return [_hipcc()] + analysis + _COMMON_FLAGS + ["-I" + include, '-DRTMI_BUILD_HASH="%s"' % build_hash] + (
+        sched if maxocc else []) + extra
+
+
+def build_rtmi(force=False, verbose=False):
+    if not force and not _stale(LIBRTMI, RTMI_DEPS):
+        return LIBRTMI
+    os.makedirs(LIB_DIR, exist_ok=True)
+    build_hash = source_hash()
     objs, procs = [], []
     for src, (_, maxocc) in zip(RTMI_SRC, _RTMI_UNITS):
-        flags = sched if maxocc else []
         obj = os.path.join(LIB_DIR, os.path.basename(src)[:-4] + ".o")
-        procs.append((src, subprocess.Popen(common + flags + extra + ["-c", src, "-o", obj])))
+        procs.append((src, subprocess.Popen(unit_command(maxocc, build_hash, verbose=verbose) + ["-c", src, "-o", obj])))
         objs.append(obj)
     failed = [src for src, p in procs if p.wait() != 0]
     if failed:

@@ -132,15 +132,10 @@ __global__ __launch_bounds__(256) void rtmi_adaptive_resolve_kernel(const Rad3 *
 hipError_t rtmi_adaptive_launch_render(int which, uint32_t blocks, size_t lds, hipStream_t stream, const DevScene &sc,
                                        const DevCamera &cam, const DevParams &P, const uint32_t *tiles) {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
-    if (which == RTMI_AD_COOP_LEAN || which == RTMI_AD_COOP_EXT) {
-        const void *fn = which == RTMI_AD_COOP_EXT ? reinterpret_cast<const void *>(&rtmi_adaptive_coop<true>)
-                                                   : reinterpret_cast<const void *>(&rtmi_adaptive_coop<false>);
-        if (lds > 48u * 1024u) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        if (which == RTMI_AD_COOP_EXT) hipLaunchKernelGGL(rtmi_adaptive_coop<true>, grid, block, lds, stream, sc, cam, P, tiles);
-        else hipLaunchKernelGGL(rtmi_adaptive_coop<false>, grid, block, lds, stream, sc, cam, P, tiles);
+    if (which == RTMI_AD_COOP_EXT) {
+        return rtmi_launch_lds(&rtmi_adaptive_coop<true>, grid, block, lds, stream, sc, cam, P, tiles);
+    } else if (which == RTMI_AD_COOP_LEAN) {
+        return rtmi_launch_lds(&rtmi_adaptive_coop<false>, grid, block, lds, stream, sc, cam, P, tiles);
     } else if (which == RTMI_AD_PERLANE_FAST) {
         hipLaunchKernelGGL(rtmi_adaptive_kernel<true>, grid, block, 0, stream, sc, cam, P, tiles);
     } else {

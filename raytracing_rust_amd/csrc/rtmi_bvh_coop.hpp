@@ -3,6 +3,7 @@
 // kernel instantiation inlines the whole path); arithmetic contract as stated there.
 #pragma once
 #include "rtmi_bvh.hpp"
+#include "rtmi_rng.hpp"
 
 // ----------------------------------------------------------------------------------
 // wave-cooperative BVH traversal (FAST semantics; RTMI_FLAG_COOP)
@@ -37,7 +38,23 @@ __device__ __forceinline__ float sort2f(uint32_t s) {
 // (< 2^25); a leaf is 1<<25 | type<<22 | primitive (< 2^22).  rtmi_scene_create stores both children of every
 // node in this encoding in the node record's reserved words.
 
-// Work space of one wavefront.  LDS (uint32 words): pool [cap][2] | ctx [64][12] floats | best [64] uint64 | dummy [64][2].
+// LDS of one wavefront of the cooperative kernel, as offsets in uint32 words: pool [cap][2] | ctx [64][12] floats |
+// best [64] uint64 | dummy [64][2] | (lean pool form, !ext: the word ring of RngRing) | (INSD instantiations: the parked
+// group state, RTMI_COOP_PARK_WORDS).  The one statement of this layout: the traversal and the kernel body index by it and
+// the host sizes the allocation by words(); the pool starts at 0.  The traversal reaches pool, ctx, best and dummy only,
+// whose offsets do not depend on ext and insd.
+struct CoopLds {
+    uint32_t cap; // pool entries
+    bool ext, insd;
+    constexpr uint32_t ctx() const { return 2u * cap; }
+    constexpr uint32_t best() const { return ctx() + 64u * 12u; }
+    constexpr uint32_t dummy() const { return best() + 128u; }
+    constexpr uint32_t ring() const { return dummy() + RTMI_COOP_DUMMY_WORDS; }
+    constexpr uint32_t park() const { return ring() + (ext ? 0u : RTMI_RNG_RING_WORDS); }
+    constexpr uint32_t words() const { return park() + (insd ? RTMI_COOP_PARK_WORDS : 0u); }
+};
+
+// Work space of one wavefront: its LDS (CoopLds) and the global part of its stack.
 // The pool in LDS is the TOP of the logical LIFO; when it runs full its older half moves to `spill` (global
 // memory, private to the wavefront) and comes back when the LDS part is empty, so the logical stack and
 // its depth-first bound of 64 * (tree depth + 1) entries are unchanged while the LDS footprint does not
@@ -68,8 +85,9 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
     // fence + wave barrier, and plain accesses let the compiler keep the LDS address space (ds_read/write_b64;
     // volatile ones became flat loads/stores with a full wait each — five per iteration).
     uint2 *pool = reinterpret_cast<uint2 *>(wlds);
-    float4 *ctx = reinterpret_cast<float4 *>(wlds + 2 * cap);
-    unsigned long long *best = reinterpret_cast<unsigned long long *>(wlds + 2 * cap + 64 * 12);
+    const CoopLds lds{(uint32_t)cap, false, false};
+    float4 *ctx = reinterpret_cast<float4 *>(wlds + lds.ctx());
+    unsigned long long *best = reinterpret_cast<unsigned long long *>(wlds + lds.best());
 
     const unsigned long long m_act = __ballot(active);
     have = false;
@@ -152,7 +170,7 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
         int at = top + before;
         // Unconditional stores: a child that is not published goes to the worker's own dummy entry behind `best` — a
         // v_cndmask on the address instead of an exec-mask region (three scalar instructions) per child.
-        const int dummy = cap + 64 * 6 + 64 + lane; // in uint2 units from `pool`: behind ctx (64 x 48 B) and best (64 x 8 B)
+        const int dummy = cap + (int)((lds.dummy() - lds.ctx()) / 2u) + lane; // in uint2 units from `pool`: its cap entries, then ctx and best
 #pragma unroll
         for (int c = 0; c < 4; c++) {
             const bool on = (wkeep & (1u << c)) != 0u;

@@ -1029,8 +1029,8 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     // (test knob bit 11: a stack so small that rounds are throttled all the time — room for 64 visits when it is full)
     if (bcoop) P.coop_cap = (p->flags & (1u << 11)) ? 3u * RTMI_BLK_THREADS + 64u : RTMI_BLK_CAP;
     s->last_kernel = bcoop ? RTMI_KERNEL_BLOCK_COOP : coop ? RTMI_KERNEL_WAVE_COOP : async ? RTMI_KERNEL_ASYNC : RTMI_KERNEL_PERLANE;
-    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS + (ext ? 0u : RTMI_RNG_RING_WORDS) +
-                                                              ((inst && (s->needs_insd || ext || sigf)) ? RTMI_COOP_PARK_WORDS : 0u)) * sizeof(uint32_t);
+    const bool insd = inst && (s->needs_insd || ext || sigf); // the level-2 instantiations (below) park their group state in LDS
+    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, insd}.words() * sizeof(uint32_t);
     const uint32_t ntex = P.ntiles_local * 64u;
     // two-phase kernels: persistent wavefronts that take units from the queue; async kernel: one block per unit
     // (workgroup-cooperative kernel: resident workgroups of RTMI_BLK_WAVES wavefronts; every wavefront takes units)
@@ -1040,13 +1040,8 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
                     [&](uint32_t blocks, bool first, bool last) -> int {
     const dim3 grid(blocks);
 #define RTMI_LAUNCH(KERN, F, S, PR, LDS) hipLaunchKernelGGL((KERN<F, S, PR>), grid, block, LDS, stream, s->dev, C, P)
-#define RTMI_LAUNCH_COOP(S, PR, W, E, I)                                                                                 \
-    do {                                                                                                                 \
-        if (coop_lds > 48u * 1024u)                                                                                      \
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&rtmi_render_coop<S, PR, W, E, I>),               \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)coop_lds));                     \
-        hipLaunchKernelGGL((rtmi_render_coop<S, PR, W, E, I>), grid, block, coop_lds, stream, s->dev, C, P);             \
-    } while (0)
+#define RTMI_LAUNCH_COOP(S, PR, W, E, I) \
+    HIP_TRY(rtmi_launch_lds(&rtmi_render_coop<S, PR, W, E, I>, grid, block, coop_lds, stream, s->dev, C, P))
     if (bcoop) {
         const dim3 blk(RTMI_BLK_THREADS);
         if (sigf) hipLaunchKernelGGL((rtmi_render_bcoop<true, false>), grid, blk, bcoop_lds, stream, s->dev, C, P);
@@ -1059,7 +1054,7 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
             // need level 1 only when they have trees: measured faster there than level 1's own instantiation (forced on
             // final_scene -5.2 % against -7.8 %, random_spheres -3.4 % / -3.1 %); without trees level 1 is the faster one
             // (cornell_box -9.5 % against -18 %) — profiles/r04_experiments/inst_levels_ab3_parked.log
-            if (s->needs_insd || ext || sigf) {
+            if (insd) {
                 if (sigf) RTMI_LAUNCH_COOP(true, false, 4, true, 2);
                 else if (ext) RTMI_LAUNCH_COOP(false, false, 4, true, 2);
                 else RTMI_LAUNCH_COOP(false, false, 4, false, 2);
@@ -2106,8 +2101,7 @@ static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_param
         c.ext = true;
         c.P.coop_cap = 256u;
     }
-    c.coop_lds = (size_t)WAVES_PER_BLOCK * (2u * c.P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
-                                            (c.ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
+    c.coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{c.P.coop_cap, c.ext, false}.words() * sizeof(uint32_t);
     return RTMI_OK;
 }
 // the persistent grid of the call's render kernel, in wavefronts: CUs x 4 SIMDs x the waves per SIMD it was compiled for
@@ -2213,8 +2207,7 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
     bool ext = false;
     if ((rc = plan_traversal(s, &p, coop, P, ext))) return rc;
     const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
-    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * (2u * P.coop_cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS +
-                                                       (ext ? 0u : RTMI_RNG_RING_WORDS)) * sizeof(uint32_t);
+    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, false}.words() * sizeof(uint32_t);
     return adaptive_steps(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, 4u, out_linear, out_rgb8, out_stderr,
                           out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
                               HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream, s->dev, c.C, P,

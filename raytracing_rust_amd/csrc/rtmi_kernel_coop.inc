@@ -2,30 +2,29 @@
 // run it: rtmi_render_coop (TILE_LIST = false), the adaptive-sampling kernel rtmi_adaptive_coop (rtmi_adaptive.hip,
 // TILE_LIST = true) and the lighting kernels of rtmi_light_coop.hip (NEE / ENV, include/rtmi_light_coop.h).  The including
 // function provides sc, cam, P, SIG, PROF, EXT, INSTL, TILE_LIST, NEE, ENV, `tiles`, `nl` and `ev`; see
-// rtmi_kernel_perlane.inc for why this is a textual body and for what NEE and ENV mean: the lane-level logic of a pending
-// shadow ray (NeeLane, the two swapped Philox states) and of the map is that body's, around this body's item scan.
-// RR (rtmi_roulette_coop_kernel, rtmi_roulette_coop.hip; include/rtmi_roulette_coop.h) is a preprocessor switch as
-// RTMI_PERLANE_RR is there, and for its reason: without RTMI_COOP_RR this text is what it was.  With it the including
-// function also provides `rr` (DevRoulette) and rtmi_roulette_dev.hpp; the statements are that body's, at the same places.
+// rtmi_kernel_perlane.inc for why this is a textual body, for what NEE and ENV mean and for the RR switch (RTMI_PATH_RR;
+// rtmi_roulette_coop_kernel, rtmi_roulette_coop.hip; include/rtmi_roulette_coop.h).  The lane-level path logic is the
+// rtmi_path_*.inc fragments', shared with that body; this one provides them the wave's LDS (CoopLds; its pool is phase B's
+// scratch), the Philox state `g` in the form the pool allows, and the item scan that all 64 lanes execute together.
     constexpr bool INST = INSTL >= 1; // instanced primitives, media inside transforms
     constexpr bool INSD = INSTL >= 2; // DEFERRED items, list scans, nested media
+    constexpr bool FEATURES = false; // no feature kernel runs this body
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
     unsigned long long *prof = prof_lds;
     if (PROF) {
         if (threadIdx.x < 2 * RTMI_PROF_SLOTS) prof_lds[threadIdx.x] = 0ull;
         __syncthreads();
     }
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[]; // per wave: pool | ctx | best
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[]; // per wave: CoopLds (rtmi_bvh_coop.hpp)
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     CoopWork cw;
     cw.cap = (int)P.coop_cap;
-    // per wave: pool | ctx | best | dummy | (lean: word ring) | (INSD: group state, RTMI_COOP_PARK_WORDS)
-    constexpr uint32_t lds_tail = (EXT ? 0u : RTMI_RNG_RING_WORDS) + (INSD ? RTMI_COOP_PARK_WORDS : 0u);
-    cw.wlds = lds_dyn + (size_t)wave * (2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS + lds_tail);
+    const CoopLds lds{(uint32_t)cw.cap, EXT, INSD};
+    cw.wlds = lds_dyn + (size_t)wave * lds.words();
     // INSD: the state of a group of DEFERRED items lives in LDS, not in registers that would stay live through every
     // traversal of every scene (parked: 20 VGPRs spilled -> see DESIGN.md §8d): per lane t0 | scan cl | scan holder | scan pf
-    uint32_t *park = cw.wlds + 2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS + (EXT ? 0u : RTMI_RNG_RING_WORDS) + lane;
+    uint32_t *park = cw.wlds + lds.park() + lane;
     cw.spill_cap = (int)P.spill_cap;
     cw.spill = P.spill + (size_t)(blockIdx.x * WAVES_PER_BLOCK + wave) * P.spill_cap;
     unsigned long long sig = 0ull;
@@ -47,28 +46,11 @@
 
     uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
     bool alive = false, done = false, have_hit = false, overflow = false;
-    // lean instantiation (scenes without alternative trees): word ring in LDS behind pool | ctx | best
+    // lean instantiation (scenes without alternative trees): word ring in LDS behind pool | ctx | best | dummy
     // (NEE: the register RNG with the stream id in both pool forms; the ring's words stay unused)
     typename std::conditional<NEE, RngNee, typename std::conditional<EXT, RngReg, RngRing>::type>::type g;
-    rng_attach(g, cw.wlds + 2u * cw.cap + 64u * 12u + 128u + RTMI_COOP_DUMMY_WORDS);
-    rng_init(g, 0, 0);
-    NeeLane ne;
-#ifdef RTMI_COOP_RR
-    bool rr_end = false; // the path ends after its pending shadow ray
-#endif
-    decltype(g) gn; // NEE: the light-sample stream (swapped with g for a shadow ray)
-    if constexpr (NEE) {
-        rng_set_stream(g, 0u);
-        rng_init(gn, 0, 0);
-        rng_set_stream(gn, 3u);
-        ne.cont_rd = f3(0, 0, 1); ne.c = f3(0, 0, 0); ne.pb = 0.0f; ne.light = 0; ne.shadow = false;
-        if constexpr (ENV) ne.env = false;
-    }
-    Path pa;
-    pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
-    float closest = RTMI_FLT_MAX;
-    int best_item = -1, best_pf = 0;
-    bool best_medium = false;
+    rng_attach(g, cw.wlds + lds.ring());
+#include "rtmi_path_lane.inc"
     unsigned long long tstamp = PROF ? __builtin_readcyclecounter() : 0ull;
 
     for (;;) {
@@ -76,19 +58,7 @@
         for (;;) {
             if (__ballot(!have_hit && !done) == 0ull) break;
             prof_time<PROF>(prof, 31, tstamp); // loop overhead / phase switching
-            { // lanes whose path ended take the next (sample, pixel) item of the chunk
-                const bool want = !have_hit && !done && !alive;
-                if (__ballot(want) != 0ull) {
-                    uint32_t smp = 0u, px = 0u, j = 0u;
-                    if (work_take<TILE_LIST>(w, queue_empty, want, P, oidx, ltile, smp, px, j, tiles)) {
-                        camera_sample(cam, P, g, k0, k1, smp, j * P.nx + px, px, j, pa);
-                        if constexpr (NEE) { rng_init(gn, smp, j * P.nx + px); ne.pb = 0.0f; }
-                        alive = true;
-                    } else if (want) {
-                        done = true;
-                    }
-                }
-            }
+#include "rtmi_path_take.inc"
             const bool need = !have_hit && !done;
             prof_tick<PROF>(prof, 0, need);
             prof_time<PROF>(prof, 25, tstamp); // camera samples
@@ -192,102 +162,16 @@
                 }
             }
             if (need) {
-                if (best_item >= 0) {
-                    have_hit = true;
-                } else if (NEE && ne.shadow) { // the shadow ray left the world: V = 0; the path goes on
-                    if constexpr (NEE) {
-                        if constexpr (ENV) { // ... unless it aims at the map: V = 1
-                            float eu, evv, eth;
-                            if (ne.env && env_uv(pa.rd, eu, evv, eth)) pa.L = pa.L + ne.c * env_radiance(ev, eu, evv);
-                        }
-                        pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t;
-#ifdef RTMI_COOP_RR
-                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
-#endif
-                    }
-                } else { // miss: black background (color.rs:21)
-                    if constexpr (ENV) { // the map, weighted by MIS after a diffuse scatter that took a light sample
-                        float eu, evv, eth;
-                        if (env_uv(pa.rd, eu, evv, eth)) {
-                            float w = 1.0f;
-                            if constexpr (NEE) {
-                                if (ne.pb > 0.0f) {
-                                    const float pe = env_pdf(ev, eu, evv, eth);
-                                    if (pe > 0.0f) w = nee_mis_bsdf(ne.pb, pe);
-                                }
-                            }
-                            pa.L = pa.L + pa.T * (env_radiance(ev, eu, evv) * w);
-                        }
-                    } else
-                    if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
-                    path_end(P, oidx, pa);
-#ifdef RTMI_COOP_RR
-                    RTMI_RR_COUNT();
-#endif
-                    if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                    alive = false;
-                }
+#include "rtmi_path_traced.inc"
             }
             if (__popcll(__ballot(have_hit)) >= threshold) break;
         }
         // ================= phase B =================
-        if (__ballot(have_hit) == 0ull) break;
-        prof_tick<PROF>(prof, 16, have_hit);
-        {
-            const bool shading = have_hit;
-            have_hit = false;
-            if (SIG && shading && !(NEE && ne.shadow)) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
-            // all lanes call (wavefront texture lookup); the traversal pool is idle now: LDS scratch
-            if constexpr (NEE) {
-                const bool was_shadow = ne.shadow;
-                const bool goes_on = shade_hit<decltype(g), INST, false, true, ENV>(
-                    sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
-                    reinterpret_cast<float *>(cw.wlds), nullptr, &nl, &ne, &gn, &ev);
-                if (shading) {
-                    if (was_shadow) { // the light sample is counted: the path's continuation is traced next
-                        pa.rd = ne.cont_rd; ne.shadow = false;
-                        const auto t = g; g = gn; gn = t;
-#ifdef RTMI_COOP_RR
-                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
-#endif
-                    } else if (!goes_on) {
-                        path_end(P, oidx, pa);
-#ifdef RTMI_COOP_RR
-                        RTMI_RR_COUNT();
-#endif
-                        if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                        alive = false;
-#ifdef RTMI_COOP_RR
-                    } else if (!roulette_survives(rr, g, k0, k1, pa)) { // g is still the path's stream here
-                        if (ne.shadow) { // the vertex's light sample is still traced and counted
-                            rr_end = true;
-                            const auto t = g; g = gn; gn = t;
-                        } else {
-                            RTMI_RR_END_PATH();
-                        }
-#endif
-                    } else if (ne.shadow) { // a shadow ray was sampled: trace it with the light-sample stream
-                        const auto t = g; g = gn; gn = t;
-                    }
-                }
-            } else {
-            const bool goes_on = shade_hit<decltype(g), INST>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
-                                           reinterpret_cast<float *>(cw.wlds));
-            if (shading && !goes_on) {
-                path_end(P, oidx, pa);
-#ifdef RTMI_COOP_RR
-                RTMI_RR_COUNT();
-#endif
-                if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                alive = false;
-            }
-#ifdef RTMI_COOP_RR
-            else if (shading && !roulette_survives(rr, g, k0, k1, pa)) {
-                RTMI_RR_END_PATH();
-            }
-#endif
-            }
-        }
+#define RTMI_PATH_SCRATCH cw.wlds
+#define RTMI_PATH_INST INST
+#include "rtmi_path_shade.inc"
+#undef RTMI_PATH_SCRATCH
+#undef RTMI_PATH_INST
         prof_time<PROF>(prof, 30, tstamp); // shading
     }
     if (P.ext & RTMI_EXT_TEST_OVERFLOW) overflow = true; // test knob: exercise the error path

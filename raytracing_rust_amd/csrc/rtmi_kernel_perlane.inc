@@ -11,10 +11,12 @@
 // and not a force-inlined function: inlining one changed the instruction stream of every existing instantiation (same
 // instructions in another order and register assignment), and those must stay bit-for-bit what they were.
 // RR (rtmi_roulette_kernel, rtmi_roulette.hip; include/rtmi_roulette.h) is a preprocessor switch for that reason: without
-// RTMI_PERLANE_RR this text is what it was.  With it the including function also provides `rr` (DevRoulette) and
+// RTMI_PATH_RR this text is what it was.  With it the including function also provides `rr` (DevRoulette) and
 // roulette_survives, RTMI_RR_COUNT() (adds the written path's depth to rr.bounces) and RTMI_RR_END_PATH() (writes the
 // path, counts it and frees the lane): the test follows every scatter in phase B, and a lane whose continuation ends with a
 // shadow ray pending sets rr_end and is written where that shadow ray is handed back.
+// The lane-level path logic is the rtmi_path_*.inc fragments', shared with rtmi_kernel_coop.inc; this body provides them
+// the per-lane traversal stacks (phase B's scratch), the register Philox state `g` and the item scan each lane runs alone.
     __shared__ unsigned long long prof_lds[PROF ? 2 * RTMI_PROF_SLOTS : 1];
     unsigned long long *prof = prof_lds;
     if (PROF) {
@@ -36,42 +38,13 @@
     uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
     bool alive = false, done = false, have_hit = false;
     typename std::conditional<NEE, RngNee, RngReg>::type g;
-    rng_init(g, 0, 0);
-    NeeLane ne;
-#ifdef RTMI_PERLANE_RR
-    bool rr_end = false; // the path ends after its pending shadow ray
-#endif
-    typename std::conditional<NEE, RngNee, RngReg>::type gn; // NEE: the light-sample stream (swapped with g for a shadow ray)
-    if constexpr (NEE) {
-        rng_set_stream(g, 0u);
-        rng_init(gn, 0, 0);
-        rng_set_stream(gn, 3u);
-        ne.cont_rd = f3(0, 0, 1); ne.c = f3(0, 0, 0); ne.pb = 0.0f; ne.light = 0; ne.shadow = false;
-        if constexpr (ENV) ne.env = false;
-    }
-    Path pa;
-    pa.ro = f3(0, 0, 0); pa.rd = f3(0, 0, 1); pa.rtime = 0.0f; pa.T = f3(1, 1, 1); pa.L = f3(0, 0, 0); pa.depth = 0;
-    float closest = RTMI_FLT_MAX;
-    int best_item = -1, best_pf = 0;
-    bool best_medium = false;
+#include "rtmi_path_lane.inc"
 
     for (;;) {
         // ================= phase A: trace until enough lanes hold a hit =================
         for (;;) {
             if (__ballot(!have_hit && !done) == 0ull) break;
-            { // lanes whose path ended take the next (sample, pixel) item of the chunk
-                const bool want = !have_hit && !done && !alive;
-                if (__ballot(want) != 0ull) {
-                    uint32_t smp = 0u, px = 0u, j = 0u;
-                    if (work_take<TILE_LIST>(w, queue_empty, want, P, oidx, ltile, smp, px, j, tiles)) {
-                        camera_sample(cam, P, g, k0, k1, smp, j * P.nx + px, px, j, pa);
-                        if constexpr (NEE) { rng_init(gn, smp, j * P.nx + px); ne.pb = 0.0f; }
-                        alive = true;
-                    } else if (want) {
-                        done = true;
-                    }
-                }
-            }
+#include "rtmi_path_take.inc"
             const bool need = !have_hit && !done;
             prof_tick<PROF>(prof, 0, need);
             if (need) {
@@ -143,116 +116,16 @@
                         }
                     }
                 }
-                if (best_item >= 0) {
-                    have_hit = true;
-                } else if (NEE && ne.shadow) { // the shadow ray left the world: V = 0; the path goes on
-                    if constexpr (NEE) {
-                        if constexpr (ENV) { // ... unless it aims at the map: V = 1
-                            float eu, evv, eth;
-                            if (ne.env && env_uv(pa.rd, eu, evv, eth)) pa.L = pa.L + ne.c * env_radiance(ev, eu, evv);
-                        }
-                        pa.rd = ne.cont_rd; ne.shadow = false; const auto t = g; g = gn; gn = t;
-#ifdef RTMI_PERLANE_RR
-                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
-#endif
-                    }
-                } else { // miss: black background (color.rs:21); the path ends
-                    if constexpr (FEATURES) {
-                        feat_miss(P, oidx, pa);
-                    } else {
-                    if constexpr (ENV) { // the map, weighted by MIS after a diffuse scatter that took a light sample
-                        float eu, evv, eth;
-                        if (env_uv(pa.rd, eu, evv, eth)) {
-                            float w = 1.0f;
-                            if constexpr (NEE) {
-                                if (ne.pb > 0.0f) {
-                                    const float pe = env_pdf(ev, eu, evv, eth);
-                                    if (pe > 0.0f) w = nee_mis_bsdf(ne.pb, pe);
-                                }
-                            }
-                            pa.L = pa.L + pa.T * (env_radiance(ev, eu, evv) * w);
-                        }
-                    } else
-                    if (P.sky) pa.L = pa.L + pa.T * sky_color(pa.rd);
-                    path_end(P, oidx, pa);
-#ifdef RTMI_PERLANE_RR
-                    RTMI_RR_COUNT();
-#endif
-                    }
-                    if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                    alive = false;
-                }
+#include "rtmi_path_traced.inc"
             }
             if (__popcll(__ballot(have_hit)) >= threshold) break;
         }
         // ================= phase B: shade every lane that holds a hit =================
-        if (__ballot(have_hit) == 0ull) break; // nobody holds a hit and nobody can trace: all done
-        prof_tick<PROF>(prof, 16, have_hit);
-        {
-            const bool shading = have_hit;
-            have_hit = false;
-            if (SIG && shading && !(NEE && ne.shadow)) sig += (unsigned long long)sig_mix(__float_as_uint(closest), pa.depth);
-            // all lanes call (wavefront texture lookup); the traversal stacks are idle now: LDS scratch
-            if constexpr (FEATURES) { // the first interaction ends every path: its record goes to the feature slot
-                ShadeFeat feat;
-                shade_hit<decltype(g), true, true>(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium,
-                                              pa, reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), &feat);
-                if (shading) {
-                    feat_hit(P, oidx, pa, closest, feat);
-                    if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                    alive = false;
-                }
-            } else if constexpr (NEE) {
-                const bool was_shadow = ne.shadow;
-                const bool goes_on = shade_hit<decltype(g), true, false, true, ENV>(
-                    sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
-                    reinterpret_cast<float *>(&lds_stack[wave][0][0][0]), nullptr, &nl, &ne, &gn, &ev);
-                if (shading) {
-                    if (was_shadow) { // the light sample is counted: the path's continuation is traced next
-                        pa.rd = ne.cont_rd; ne.shadow = false;
-                        const auto t = g; g = gn; gn = t;
-#ifdef RTMI_PERLANE_RR
-                        if (rr_end) { rr_end = false; RTMI_RR_END_PATH(); } // roulette ended the continuation at this shadow ray's vertex
-#endif
-                    } else if (!goes_on) {
-                        path_end(P, oidx, pa);
-#ifdef RTMI_PERLANE_RR
-                        RTMI_RR_COUNT();
-#endif
-                        if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                        alive = false;
-#ifdef RTMI_PERLANE_RR
-                    } else if (!roulette_survives(rr, g, k0, k1, pa)) { // g is still the path's stream here
-                        if (ne.shadow) { // the vertex's light sample is still traced and counted
-                            rr_end = true;
-                            const auto t = g; g = gn; gn = t;
-                        } else {
-                            RTMI_RR_END_PATH();
-                        }
-#endif
-                    } else if (ne.shadow) { // a shadow ray was sampled: trace it with the light-sample stream
-                        const auto t = g; g = gn; gn = t;
-                    }
-                }
-            } else {
-            const bool goes_on = shade_hit(sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
-                                           reinterpret_cast<float *>(&lds_stack[wave][0][0][0]));
-            if (shading && !goes_on) {
-                // absorbed, emitter or depth limit: the path ends
-                path_end(P, oidx, pa);
-#ifdef RTMI_PERLANE_RR
-                RTMI_RR_COUNT();
-#endif
-                if (SIG) { atomicAdd(P.path_sig + (size_t)ltile * 64 + (oidx & 63u), sig); sig = 0ull; }
-                alive = false;
-            }
-#ifdef RTMI_PERLANE_RR
-            else if (shading && !roulette_survives(rr, g, k0, k1, pa)) {
-                RTMI_RR_END_PATH();
-            }
-#endif
-            }
-        }
+#define RTMI_PATH_SCRATCH &lds_stack[wave][0][0][0]
+#define RTMI_PATH_INST true
+#include "rtmi_path_shade.inc"
+#undef RTMI_PATH_SCRATCH
+#undef RTMI_PATH_INST
     }
 
     if (PROF) {

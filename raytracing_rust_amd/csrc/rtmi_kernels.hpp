@@ -50,6 +50,20 @@ extern template __global__ void rtmi_render_coop<false, false, 4, false, 1>(DevS
 extern template __global__ void rtmi_render_coop<false, false, 4, false, 2>(DevScene, DevCamera, DevParams);
 #endif
 
+// Host: launch of a kernel whose block takes `lds` bytes of dynamic LDS.  Up to 48 KB a block gets as it is; above that
+// the kernel's limit is raised first (the cooperative kernels with a deep pool).  The error of either step.
+template <typename... Params, typename... Args>
+inline hipError_t rtmi_launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                                  const Args &...args) {
+    if (lds > 48u * 1024u) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
 // ----------------------------------------------------------------------------------
 // The workgroup-cooperative kernel (RTMI_FLAG_BLOCK_COOP) and the asynchronous state-machine kernel (RTMI_FLAG_ASYNC)
 // are defined in rtmi_kernels_alt.hpp and instantiated in rtmi_alt.hip — measured slower than the default, kept as

@@ -37,14 +37,8 @@ hipError_t rtmi_light_coop_launch_render(bool tile_list, bool sig, bool ext, boo
     return rtmi_with_bools([&](auto TL, auto SIG, auto EXT, auto NEE, auto ENV) {
         if constexpr ((!NEE() && !ENV()) || (TL() && SIG())) return hipErrorInvalidValue; // the plain estimator is rtmi_render_coop's
         else {
-            const auto kernel = &rtmi_light_coop_kernel<TL(), SIG(), EXT(), NEE(), ENV()>;
-            if (lds > 48u * 1024u) {
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-            }
-            hipLaunchKernelGGL(kernel, grid, block, lds, stream, sc, cam, P, tiles, L, E);
-            return hipGetLastError();
+            return rtmi_launch_lds(&rtmi_light_coop_kernel<TL(), SIG(), EXT(), NEE(), ENV()>, grid, block, lds, stream, sc, cam,
+                                   P, tiles, L, E);
         }
     }, tile_list, sig, ext, nee, env);
 }

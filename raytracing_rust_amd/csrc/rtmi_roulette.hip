@@ -2,7 +2,7 @@
 // and their launcher.  Compiled with the flags of rtmi_device.hip (-ffp-contract=off).
 //
 // The render kernel is the body of rtmi_render_kernel (rtmi_kernel_perlane.inc) with TILE_LIST = true, the NEE / ENV
-// switches of rtmi_adaptive_nee_kernel and the RR switch (RTMI_PERLANE_RR, a preprocessor switch: every other inclusion
+// switches of rtmi_adaptive_nee_kernel and the RR switch (RTMI_PATH_RR, a preprocessor switch: every other inclusion
 // of the body is the same text as before): the roulette test after a scatter, the end-after-its-shadow-ray flag and the
 // bounce count at every place a path is written.  One instantiation per FAST x estimator serves both entry points: the
 // fixed render runs over the list of all tiles.  No path signatures (SIG = false).  The resolve is adaptive sampling's
@@ -21,7 +21,7 @@
 
 #include "rtmi_roulette_dev.hpp" // roulette_survives, RTMI_RR_COUNT(), RTMI_RR_END_PATH(): shared with rtmi_roulette_coop.hip
 
-#define RTMI_PERLANE_RR 1
+#define RTMI_PATH_RR 1
 template <bool FAST, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_roulette_kernel(DevScene sc, DevCamera cam, DevParams P,
                                                                             const uint32_t *tiles, DevLights nl, DevEnv ev,
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_roulette_kernel(Dev
     constexpr bool SIG = false, PROF = false, TILE_LIST = true, FEATURES = false;
 #include "rtmi_kernel_perlane.inc"
 }
-#undef RTMI_PERLANE_RR
+#undef RTMI_PATH_RR
 
 hipError_t rtmi_roulette_launch_render(bool fast, bool nee, bool env, uint32_t blocks, hipStream_t stream, const DevScene &sc,
                                        const DevCamera &cam, const DevParams &P, const uint32_t *tiles, const DevLights &L,

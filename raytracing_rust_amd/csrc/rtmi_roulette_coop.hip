@@ -3,8 +3,8 @@
 // (-ffp-contract=off).
 //
 // The kernel is the body of rtmi_render_coop (rtmi_kernel_coop.inc) with TILE_LIST = true, the NEE / ENV switches of
-// rtmi_light_coop_kernel and the RR switch (RTMI_COOP_RR, a preprocessor switch: every other inclusion of the body is the
-// same text as before): the statements of rtmi_roulette_kernel (rtmi_kernel_perlane.inc under RTMI_PERLANE_RR) at the
+// rtmi_light_coop_kernel and the RR switch (RTMI_PATH_RR, a preprocessor switch: every other inclusion of the body is the
+// same text as before): the statements of rtmi_roulette_kernel (rtmi_kernel_perlane.inc under RTMI_PATH_RR) at the
 // same places, so per-lane program order is that kernel's and every plane, the bounce count included, has its bits.  One
 // instantiation per pool form x estimator serves both entry points: the fixed render runs over the list of all tiles.
 // (NEE, ENV) = (0, 0) is the plain estimator: g is RngRing (lean) or RngReg (ext), whose sample and pixel words key the
@@ -26,7 +26,7 @@
 
 #include "rtmi_roulette_dev.hpp" // roulette_survives, RTMI_RR_COUNT(), RTMI_RR_END_PATH(): shared with rtmi_roulette.hip
 
-#define RTMI_COOP_RR 1
+#define RTMI_PATH_RR 1
 template <bool EXT, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, rtmi_roulette_coop_wps(NEE, ENV)) void rtmi_roulette_coop_kernel(
     DevScene sc, DevCamera cam, DevParams P, const uint32_t *tiles, DevLights nl, DevEnv ev, DevRoulette rr) {
@@ -34,20 +34,14 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, rtmi_roulette_coop_wps(NEE, E
     constexpr int INSTL = 0;
 #include "rtmi_kernel_coop.inc"
 }
-#undef RTMI_COOP_RR
+#undef RTMI_PATH_RR
 
 hipError_t rtmi_roulette_coop_launch_render(bool ext, bool nee, bool env, uint32_t blocks, size_t lds, hipStream_t stream,
                                             const DevScene &sc, const DevCamera &cam, const DevParams &P, const uint32_t *tiles,
                                             const DevLights &L, const DevEnv &E, const DevRoulette &R) {
     const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
     return rtmi_with_bools([&](auto EXT, auto NEE, auto ENV) {
-        const auto kernel = &rtmi_roulette_coop_kernel<EXT(), NEE(), ENV()>;
-        if (lds > 48u * 1024u) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kernel, grid, block, lds, stream, sc, cam, P, tiles, L, E, R);
-        return hipGetLastError();
+        return rtmi_launch_lds(&rtmi_roulette_coop_kernel<EXT(), NEE(), ENV()>, grid, block, lds, stream, sc, cam, P, tiles,
+                               L, E, R);
     }, ext, nee, env);
 }

@@ -1,6 +1,6 @@
 // rtmi_roulette_dev.hpp — what the two roulette translation units share (include/rtmi_roulette.h): the roulette test and
 // the two statements a kernel body uses where a roulette kernel writes a path.  Included by rtmi_roulette.hip (the
-// per-lane body under RTMI_PERLANE_RR) and rtmi_roulette_coop.hip (the cooperative body under RTMI_COOP_RR), after
+// per-lane body) and rtmi_roulette_coop.hip (the cooperative body), both under RTMI_PATH_RR, after
 // rtmi_kernels.hpp and rtmi_light_launch.hpp (DevRoulette).
 #pragma once
 
