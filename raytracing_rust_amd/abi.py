@@ -228,6 +228,21 @@ ROULETTE_ESTIMATORS = {"plain": RTMI_ROULETTE_PLAIN, "nee": RTMI_ROULETTE_NEE, "
 # the functions of include/rtmi_roulette.h (Russian-roulette path termination), kept apart from those of the other headers
 RTMI_ROULETTE_SYMBOLS = ["rtmi_render_adaptive_roulette", "rtmi_render_roulette"]
 
+
+
+class SessionOpts(C.Structure):
+    """rtmi_session_opts (include/rtmi_session.h): what a render session traces and on which lattice (32 bytes)."""
+    _fields_ = [("estimator", C.c_uint32), ("rr", C.c_uint32), ("min_depth", C.c_uint32), ("q_min", C.c_float),
+                ("env_select_p", C.c_float), ("first_sample", C.c_uint32), ("min_spp", C.c_uint32), ("step_spp", C.c_uint32)]
+
+
+RTMI_SESSION_BLOB_VERSION, RTMI_SESSION_BLOB_HEADER, RTMI_SESSION_BLOB_IDENTITY = 1, 216, 196
+
+# the functions of include/rtmi_session.h (render sessions), kept apart from those of the other headers
+SESSION_SYMBOLS = ["rtmi_session_create", "rtmi_session_destroy", "rtmi_session_export", "rtmi_session_image",
+                   "rtmi_session_import", "rtmi_session_merge", "rtmi_session_refine", "rtmi_session_render",
+                   "rtmi_session_spp"]
+
 _rtmi = None
 _host = None
 
@@ -328,6 +343,24 @@ def load_rtmi():
     lib.rtmi_render_adaptive_roulette.restype = C.c_int
     lib.rtmi_render_adaptive_roulette.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Roulette),
                                                   C.POINTER(Adaptive), vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_session_create.restype = C.c_int
+    lib.rtmi_session_create.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(SessionOpts), C.POINTER(vp)]
+    lib.rtmi_session_destroy.restype = None
+    lib.rtmi_session_destroy.argtypes = [vp]
+    lib.rtmi_session_render.restype = C.c_int
+    lib.rtmi_session_render.argtypes = [vp, C.c_uint32, C.POINTER(Stats)]
+    lib.rtmi_session_refine.restype = C.c_int
+    lib.rtmi_session_refine.argtypes = [vp, C.c_double, C.c_double, C.c_uint32, C.POINTER(Stats)]
+    lib.rtmi_session_image.restype = C.c_int
+    lib.rtmi_session_image.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.rtmi_session_export.restype = C.c_int
+    lib.rtmi_session_export.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.rtmi_session_import.restype = C.c_int
+    lib.rtmi_session_import.argtypes = [vp, vp, C.c_size_t]
+    lib.rtmi_session_merge.restype = C.c_int
+    lib.rtmi_session_merge.argtypes = [vp, vp]
+    lib.rtmi_session_spp.restype = C.c_int
+    lib.rtmi_session_spp.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -399,6 +432,15 @@ def load_host():
         "rth_render_roulette": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Roulette), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_render_adaptive_roulette": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(Roulette), C.POINTER(Adaptive), vp, vp,
                                              vp, vp, vp, C.POINTER(Stats)]),
+        "rth_session_create": (vp, [vp, vp, C.POINTER(RenderParams), C.POINTER(SessionOpts)]),
+        "rth_session_close": (i, [vp]),
+        "rth_session_render": (i, [vp, u32, C.POINTER(Stats)]),
+        "rth_session_refine": (i, [vp, d, d, u32, C.POINTER(Stats)]),
+        "rth_session_image": (i, [vp, vp, vp, vp, vp, vp]),
+        "rth_session_export": (i, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "rth_session_import": (i, [vp, vp, C.c_size_t]),
+        "rth_session_merge": (i, [vp, vp]),
+        "rth_session_spp": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

@@ -393,6 +393,29 @@ class Scene:
         self.host._check(self.host.lib.rth_render_adaptive_roulette(self.h, cam.h, C.byref(p), C.byref(o), C.byref(a), *outs))
         return _result(out)
 
+    def session(self, cam, nx, ny, estimator="plain", roulette=None, env_select_p=0.5, first_sample=0, lattice=None, coop=False,
+                **kw):
+        """A render session (include/rtmi_session.h): the accumulation state of a render kept across calls, so that it can
+        be continued, refined, read at any point, saved, restored and merged.  estimator: "plain", "nee", "env" or
+        "env_nee"; roulette: None or dict(min_depth, q_min) (rtmi_roulette.h); first_sample: the session's samples are
+        [first_sample, first_sample + n); lattice: None for a FIXED session (Session.render) or (min_spp, step_spp) for a
+        REFINE session (Session.refine).  coop=True selects the wave-cooperative kernel under the rule of the estimator's
+        one-shot entry.  The other keywords are default_params' (ns is not read).  The light table is attached on first use.
+        A scene resident on a device list (upload_multi) raises Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        rr = roulette is not None
+        _coop_flags(kw, coop, abi.RTMI_FLAG_ROULETTE_COOP if rr else abi.RTMI_FLAG_LIGHT_COOP)
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, 1, **kw)
+        min_spp, step_spp = (0, 0) if lattice is None else lattice
+        o = abi.SessionOpts(abi.ROULETTE_ESTIMATORS[estimator], 1 if rr else 0, roulette["min_depth"] if rr else 0,
+                            roulette["q_min"] if rr else 0.0, env_select_p, first_sample, min_spp, step_spp)
+        h = self.host.lib.rth_session_create(self.h, cam.h, C.byref(p), C.byref(o))
+        if not h:
+            self.host._raise()
+        return Session(self.host, h, nx, ny, keep=(self, cam, p))
+
     def render_denoised(self, cam, nx, ny, ns, denoise=None, nee=False, env=False, coop=False, **kw):
         """A render and its denoised image: render_adaptive(min_spp=ns, step_spp=1) (render()'s image plus its standard
         errors), render_features with the same ns and keywords, then denoise() of the three on the scene's device.
@@ -499,6 +522,81 @@ _PLANES = {"linear": ((3,), np.float32), "rgb8": ((3,), np.uint8), "stderr": ((3
            "hits": ((), np.uint32)}
 
 
+class Session:
+    """A render session of Scene.session (include/rtmi_session.h).  Calls on it serialise with every other call on its
+    scene.  close() frees its device state (76 B per tile-padded pixel); Host.free_all() closes what is still open."""
+
+    def __init__(self, host, h, nx, ny, keep=()):
+        self.host, self.h, self.nx, self.ny, self.keep = host, h, nx, ny, keep
+        host._sessions = getattr(host, "_sessions", []) + [self]
+
+    def _handle(self):
+        if not self.h:
+            raise HostError("the session is closed")
+        return self.h
+
+    def render(self, spp):
+        """FIXED sessions: spp more samples for every tile.  Returns the call's stats."""
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_session_render(self._handle(), spp, C.byref(st)))
+        return _stats(st)
+
+    def refine(self, abs_tol, rel_tol, cap):
+        """REFINE sessions: advance to the noise target under the cap; a call may tighten, never loosen.  The image then
+        equals render_adaptive's (or render_adaptive_roulette's) with this call's arguments, and no sample was traced
+        twice.  Returns the call's stats (samples = the paths this call traced)."""
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_session_refine(self._handle(), abs_tol, rel_tol, cap, C.byref(st)))
+        return _stats(st)
+
+    def image(self):
+        """The session as it stands: dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], stderr f32 [ny,nx,3], spp u32 [ny,nx],
+        bounces u32 [ny,nx] (zeros without roulette))."""
+        out = {n: np.zeros((self.ny, self.nx) + _PLANES[n][0], _PLANES[n][1]) for n in ("linear", "rgb8", "stderr", "spp", "bounces")}
+        self.host._check(self.host.lib.rth_session_image(self._handle(), *[a.ctypes.data for a in out.values()]))
+        return out
+
+    def spp(self):
+        """(min, max) of the tiles' sample counts."""
+        lo, hi = C.c_uint32(0), C.c_uint32(0)
+        self.host._check(self.host.lib.rth_session_spp(self._handle(), C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def save(self):
+        """The session as a blob (bytes; the layout is in include/rtmi_session.h)."""
+        need = C.c_size_t(0)
+        self.host._check(self.host.lib.rth_session_export(self._handle(), None, 0, C.byref(need)))
+        buf = C.create_string_buffer(need.value)
+        self.host._check(self.host.lib.rth_session_export(self._handle(), buf, need.value, C.byref(need)))
+        return buf.raw
+
+    def load(self, blob):
+        """Restores a blob of save() into this session, which must have the same identity (HostError otherwise, the
+        session unchanged); clears the failed state."""
+        blob = bytes(blob)
+        self.host._check(self.host.lib.rth_session_import(self._handle(), blob, len(blob)))
+
+    def merge(self, other):
+        """Takes in the samples of `other`, a FIXED session of equal identity whose range starts where this one's ends."""
+        self.host._check(self.host.lib.rth_session_merge(self._handle(), other._handle()))
+
+    def render_for(self, seconds, step_spp):
+        """render(step_spp) until the wall clock passes `seconds` (at least one step).  Returns the spp reached."""
+        import time
+
+        t0 = time.monotonic()
+        while True:
+            self.render(step_spp)
+            if time.monotonic() - t0 >= seconds:
+                return self.spp()[1]
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.host._sessions = [s for s in getattr(self.host, "_sessions", []) if s is not self]
+            self.host._check(self.host.lib.rth_session_close(h))
+
+
 def _outputs(ny, nx, names, sig=None):
     """The zeroed planes `names` of a render as its result dict, and the trailing arguments of the native entry: the
     planes' addresses in that order, the path signatures' (u64 [ny,nx]; NULL unless sig; sig=None: the entry takes none;
@@ -586,6 +684,8 @@ class Host:
         self.lib.rth_seed_scene_rng(int(seed))
 
     def free_all(self):
+        for ses in list(getattr(self, "_sessions", [])):  # sessions before their scenes
+            ses.close()
         self.lib.rth_free_all()
 
     # ---- textures (src/texture.rs) ----

@@ -3,6 +3,7 @@
 // crosses the boundary: constructors return NULL and functions return a non-zero code,
 // with the message in rth_last_error().  Where the reference panics the code is RTH_PANIC.
 #include <cstring>
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "rtmi_env.h"
 #include "rtmi_adaptive_nee.h"
 #include "rtmi_roulette.h"
+#include "rtmi_session.h"
 
 using namespace rt;
 
@@ -34,6 +36,7 @@ struct Obj {
 };
 std::mutex g_mu;
 std::vector<Obj *> g_objs;
+std::vector<rtmi_session *> g_sessions; // the live render sessions (rth_session_*): freed before their scenes
 
 Obj *reg(Obj *o) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -87,6 +90,8 @@ RTH_API const char *rth_last_error(void) { return g_err.c_str(); }
 RTH_API int rth_last_error_code(void) { return g_code; }
 RTH_API void rth_free_all(void) {
     std::lock_guard<std::mutex> lk(g_mu);
+    for (rtmi_session *ss : g_sessions) rtmi_session_destroy(ss);
+    g_sessions.clear();
     for (Obj *o : g_objs) {
         if (o->dev) rtmi_scene_destroy(o->dev);
         if (o->multi) rtmi_multi_destroy(o->multi);
@@ -369,6 +374,65 @@ RTH_API int rth_render_adaptive_roulette(void *lowered, void *cam, const rtmi_re
                     rtmi_render_adaptive_roulette(dev, &c, p, opts, a, out_linear, out_rgb8, out_stderr, out_spp, out_bounces, stats),
                     CODED_UNSUPPORTED);
     });
+}
+// render sessions (include/rtmi_session.h): the entries one to one on the uploaded handle; RTH_UNSUPPORTED for what they do
+// not support, a multi-GPU handle among it.  A session is freed by rth_session_close or, at the latest, by rth_free_all
+// (before the scenes); re-uploading its scene (rth_upload) while it lives is the caller's error.
+static rtmi_session *SES(void *h) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (rtmi_session *ss : g_sessions)
+        if (ss == h) return ss;
+    throw std::runtime_error("handle is not a live render session");
+}
+RTH_API void *rth_session_create(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_session_opts *opts) {
+    return guard_new([&] {
+        const char *name = "rtmi_session_create";
+        rtmi_scene *dev = DEV(lowered, name, "session");
+        const rtmi_camera c = CAM(cam).lower();
+        rtmi_session *ss = nullptr;
+        done(name, rtmi_session_create(dev, &c, p, opts, &ss), CODED_UNSUPPORTED);
+        std::lock_guard<std::mutex> lk(g_mu);
+        g_sessions.push_back(ss);
+        return (void *)ss;
+    });
+}
+RTH_API int rth_session_close(void *session) {
+    return guard([&] {
+        rtmi_session *ss = SES(session);
+        {
+            std::lock_guard<std::mutex> lk(g_mu);
+            g_sessions.erase(std::find(g_sessions.begin(), g_sessions.end(), ss));
+        }
+        rtmi_session_destroy(ss);
+        return RTH_OK;
+    });
+}
+RTH_API int rth_session_render(void *session, uint32_t add_spp, rtmi_stats *stats) {
+    return guard([&] { return done("rtmi_session_render", rtmi_session_render(SES(session), add_spp, stats), CODED_UNSUPPORTED); });
+}
+RTH_API int rth_session_refine(void *session, double abs_tol, double rel_tol, uint32_t cap, rtmi_stats *stats) {
+    return guard([&] {
+        return done("rtmi_session_refine", rtmi_session_refine(SES(session), abs_tol, rel_tol, cap, stats), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_session_image(void *session, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
+                              uint32_t *out_bounces) {
+    return guard([&] {
+        return done("rtmi_session_image", rtmi_session_image(SES(session), out_linear, out_rgb8, out_stderr, out_spp, out_bounces),
+                    CODED);
+    });
+}
+RTH_API int rth_session_export(void *session, void *buf, size_t cap, size_t *need) {
+    return guard([&] { return done("rtmi_session_export", rtmi_session_export(SES(session), buf, cap, need), CODED); });
+}
+RTH_API int rth_session_import(void *session, const void *buf, size_t len) {
+    return guard([&] { return done("rtmi_session_import", rtmi_session_import(SES(session), buf, len), CODED); });
+}
+RTH_API int rth_session_merge(void *dst, void *src) {
+    return guard([&] { return done("rtmi_session_merge", rtmi_session_merge(SES(dst), SES(src)), CODED_UNSUPPORTED); });
+}
+RTH_API int rth_session_spp(void *session, uint32_t *min_spp, uint32_t *max_spp) {
+    return guard([&] { return done("rtmi_session_spp", rtmi_session_spp(SES(session), min_spp, max_spp), CODED); });
 }
 RTH_API int rth_probe_env(void *lowered, int op, const float *in, float *out, uint32_t n) {
     return guard([&] { return done("rtmi_probe_env", rtmi_probe_env(DEV(lowered), op, in, out, n), CODED); });
