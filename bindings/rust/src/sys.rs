@@ -669,3 +669,86 @@ extern "C" {
         stats: *mut RtmiStats,
     ) -> c_int;
 }
+
+// ---- include/rtmi_query.h: ray queries (closest hit and occlusion for batches of rays) ----
+
+/// rtmi_ray: one query ray (32 bytes); t_max = +inf or >= FLT_MAX means the render's t_max
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiRay {
+    pub o: [f32; 3],
+    pub t_min: f32,
+    pub d: [f32; 3],
+    pub t_max: f32,
+}
+
+/// rtmi_hit: the record of a closest hit (48 bytes); a miss has t = +inf, item = prim = material = -1, the rest 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiHit {
+    pub t: f32,
+    pub u: f32,
+    pub v: f32,
+    pub p: [f32; 3],
+    pub n: [f32; 3],
+    pub item: i32,
+    pub prim: i32,
+    pub material: i32,
+}
+
+/// rtmi_query_params: one call's batch (24 bytes); ray i draws from the Philox stream keyed seed + first_ray + i
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiQueryParams {
+    pub n: u32,
+    pub flags: u32,
+    pub seed: u64,
+    pub first_ray: u64,
+}
+
+extern "C" {
+    /// optional: the places of the FlipNormals among the wrappers (bit g of an entry: between transforms g - 1 and g of the
+    /// chain, outermost first), so that the zeros of rtmi_trace's normals carry the reference's signs; NULL arrays detach
+    pub fn rtmi_scene_attach_flips(
+        scene: *mut RtmiScene,
+        prim_gaps: *const u32,
+        n_prims: u32,
+        item_gaps: *const u32,
+        n_items: u32,
+    ) -> c_int;
+    /// blocking, host pointers; time: n floats or NULL (time 0); kernel_ms: optional
+    pub fn rtmi_trace(
+        scene: *mut RtmiScene,
+        params: *const RtmiQueryParams,
+        rays: *const RtmiRay,
+        time: *const f32,
+        hits_out: *mut RtmiHit,
+        kernel_ms: *mut f64,
+    ) -> c_int;
+    /// occluded_out[i] = 1 iff rtmi_trace's hit i is a hit: the same predicate with the same draws
+    pub fn rtmi_occluded(
+        scene: *mut RtmiScene,
+        params: *const RtmiQueryParams,
+        rays: *const RtmiRay,
+        time: *const f32,
+        occluded_out: *mut u8,
+        kernel_ms: *mut f64,
+    ) -> c_int;
+    /// asynchronous, device pointers, enqueued on `stream` (a hipStream_t); writes exactly n records
+    pub fn rtmi_trace_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiQueryParams,
+        d_rays: *const c_void,
+        d_time: *const c_void,
+        d_hits: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    pub fn rtmi_occluded_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiQueryParams,
+        d_rays: *const c_void,
+        d_time: *const c_void,
+        d_occluded: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+}

@@ -1,0 +1,88 @@
+/* rtmi_query.h — ray queries: closest hit and occlusion for batches of caller-supplied rays, on the MI355X (gfx950)
+ * device path.  See DESIGN.md §23.
+ *
+ * Every render entry starts from the camera and returns pixels.  These entries hand out the operation all of them are
+ * built on, the reference's world.hit(ray, t_min, t_max) (hittable.rs:37-47 and everything below it: the top-level list
+ * scan, the BVHs, the instances and the constant media), for picking, visibility and ambient-occlusion terms, light
+ * placement checks, or an integrator of the host's own on top of this traversal.
+ *
+ * Semantics.  For ray i of a batch, hit[i] is the Option<HitRecord> of world.hit(&Ray{o, d, time[i]}, t_min, t_max), in the
+ * fp32 arithmetic contract, exactly as the render kernels evaluate it for a path ray.
+ *   Random numbers.  Only ConstantMedium::hit draws.  Ray i draws from the Philox4x32-10 stream with the key
+ *     (seed + first_ray + i) mod 2^64, counter (0, 0, 0, 0), stream id 0, in the order the reference's hit makes the draws:
+ *     list order, BVH in-order, and the deferred / nested / list-scan media rules of rtmi.h.  first_ray makes the result
+ *     independent of how a batch is split into calls.
+ *   t_max.  +inf or any value >= FLT_MAX means the render's t_max, FLT_MAX.  t_min is the caller's; the render uses 0.001.
+ *   Occlusion.  occluded[i] is 1 iff hit[i] is Some, bit for bit, with the same stream: the same predicate, evaluated by
+ *     a scan that stops at the first accepted hit.
+ *   Flags.  0 (the reference-topology traversal) and RTMI_FLAG_FAST_CULL (pruned; same results).  Every other bit is
+ *     RTMI_ERR_UNSUPPORTED.  The pruned traversal needs the BVH boxes to hold at every ray time: with a time plane and a
+ *     scene whose [bvh_time_lo, bvh_time_hi] is bounded, or without one when 0 lies outside that range, the exact
+ *     traversal runs whatever the flag says.
+ * The calls follow the handle's thread model (rtmi.h): calls on one handle serialise.  They allocate none of the
+ * handle's render scratch: a handle that is only queried never gets a per-sample radiance buffer.
+ */
+#ifndef RTMI_QUERY_H
+#define RTMI_QUERY_H
+
+#include "rtmi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct {
+    float o[3], t_min, d[3], t_max;
+} rtmi_ray; /* 32 B */
+
+/* Miss: item = prim = material = -1, t = +inf, the rest 0.
+ * Surface hit: item = the top-level item that won, prim = the primitive, material = prim_meta[prim].material, n = the
+ *   record's normal after the transforms and FlipNormals, never face-forwarded, (u, v) = the record's, always computed.
+ * Medium hit: prim = -1, material = items[item].medium_material, n = (1, 0, 0) handed back through the medium's outer
+ *   wrappers and negated under RTMI_ITEMFLAG_FLIP, u = v = 0 (medium.rs:47-48).
+ * The sign of a zero in n: negation and rotation commute in value but not in the sign of an exact zero, and the scene
+ * description keeps only the parity of the FlipNormals around a primitive.  With the table of rtmi_scene_attach_flips
+ * the flips are applied at their places among the Traslate / Rotate wrappers, as the reference applies them; without
+ * it they are applied after all of them, and a zero component can carry the other sign. */
+typedef struct {
+    float t, u, v, p[3], n[3];
+    int32_t item, prim, material;
+} rtmi_hit; /* 48 B */
+
+typedef struct {
+    uint32_t n;         /* rays in this call */
+    uint32_t flags;     /* 0 or RTMI_FLAG_FAST_CULL */
+    uint64_t seed;
+    uint64_t first_ray; /* index of this call's ray 0 in the caller's batch */
+} rtmi_query_params; /* 24 B */
+
+/* Optional: where the FlipNormals sit among the wrappers, so that rtmi_trace's normals have the reference's bits in
+ * their zeros too.  prim_gaps[i], bit g: an odd number of flips between transforms g - 1 and g of primitive i's own chain
+ * (outermost first; bit 0: outside the whole chain, where the flips of enclosing lists and tree nodes sit; bit count:
+ * directly around the primitive); item_gaps[i] likewise for item i's chain, for a medium item the flips around the medium
+ * only.  The parities must be those of RTMI_PRIMFLAG_FLIP and, for items that are no media, RTMI_ITEMFLAG_FLIP.  The
+ * counts must be the scene's; the arrays are copied.  NULL arrays detach.  The host mirror's lowering produces the table
+ * and rth_upload attaches it. */
+int rtmi_scene_attach_flips(rtmi_scene *scene, const uint32_t *prim_gaps, uint32_t n_prims, const uint32_t *item_gaps,
+                            uint32_t n_items);
+
+/* Blocking, host pointers.  time: n floats, or NULL for time 0.  kernel_ms: optional, the kernel's time by HIP events.
+ * n == 0 is RTMI_OK and launches nothing.  RTMI_ERR_INVALID, with the entry's name in rtmi_last_error(), for a NULL
+ * scene, params, rays or output and for a ray with a non-finite component (t_max may be +inf), a zero direction or
+ * t_min > t_max; the message names the ray. */
+int rtmi_trace(rtmi_scene *scene, const rtmi_query_params *params, const rtmi_ray *rays, const float *time,
+               rtmi_hit *hits_out, double *kernel_ms);
+int rtmi_occluded(rtmi_scene *scene, const rtmi_query_params *params, const rtmi_ray *rays, const float *time,
+                  uint8_t *occluded_out, double *kernel_ms);
+
+/* Asynchronous, DEVICE pointers on the scene's device, enqueued on `stream` (a hipStream_t) like rtmi_render_device
+ * without stats.  They write exactly n records and nothing beyond, and take the caller's word for the rays. */
+int rtmi_trace_device(rtmi_scene *scene, const rtmi_query_params *params, const void *d_rays, const void *d_time,
+                      void *d_hits, void *stream);
+int rtmi_occluded_device(rtmi_scene *scene, const rtmi_query_params *params, const void *d_rays, const void *d_time,
+                         void *d_occluded, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RTMI_QUERY_H */

@@ -243,6 +243,25 @@ SESSION_SYMBOLS = ["rtmi_session_create", "rtmi_session_destroy", "rtmi_session_
                    "rtmi_session_import", "rtmi_session_merge", "rtmi_session_refine", "rtmi_session_render",
                    "rtmi_session_spp"]
 
+class Ray(C.Structure):
+    """rtmi_ray (include/rtmi_query.h): one query ray (32 bytes)."""
+    _fields_ = [("o", C.c_float * 3), ("t_min", C.c_float), ("d", C.c_float * 3), ("t_max", C.c_float)]
+
+
+class Hit(C.Structure):
+    """rtmi_hit (include/rtmi_query.h): the record of a closest hit, or of a miss (48 bytes)."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("p", C.c_float * 3), ("n", C.c_float * 3),
+                ("item", C.c_int32), ("prim", C.c_int32), ("material", C.c_int32)]
+
+
+class QueryParams(C.Structure):
+    """rtmi_query_params (include/rtmi_query.h): one call's batch (24 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64), ("first_ray", C.c_uint64)]
+
+
+# the functions of include/rtmi_query.h (ray queries), kept apart from those of the other headers
+RTMI_QUERY_SYMBOLS = ["rtmi_occluded", "rtmi_occluded_device", "rtmi_scene_attach_flips", "rtmi_trace", "rtmi_trace_device"]
+
 _rtmi = None
 _host = None
 
@@ -361,6 +380,14 @@ def load_rtmi():
     lib.rtmi_session_merge.argtypes = [vp, vp]
     lib.rtmi_session_spp.restype = C.c_int
     lib.rtmi_session_spp.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    for name in ("rtmi_trace", "rtmi_occluded"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]
+    lib.rtmi_scene_attach_flips.restype = C.c_int
+    lib.rtmi_scene_attach_flips.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32]
+    for name in ("rtmi_trace_device", "rtmi_occluded_device"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, C.POINTER(QueryParams), vp, vp, vp, vp]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -441,6 +468,10 @@ def load_host():
         "rth_session_import": (i, [vp, vp, C.c_size_t]),
         "rth_session_merge": (i, [vp, vp]),
         "rth_session_spp": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "rth_trace": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
+        "rth_occluded": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
+        "rth_trace_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),
+        "rth_occluded_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

@@ -52,6 +52,8 @@
 #include "rtmi_light_launch.hpp"
 #include "rtmi_session.h"
 #include "rtmi_session_launch.hpp"
+#include "rtmi_query.h"
+#include "rtmi_query_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -129,6 +131,14 @@ struct rtmi_scene {
     size_t ft_state_bytes = 0;
     float *ft_planes = nullptr; // albedo [ny*nx*3] | normal [ny*nx*3] | depth [ny*nx] | hits [ny*nx] (uint32)
     size_t ft_planes_bytes = 0;
+    // ray queries (include/rtmi_query.h), grow-only, freed with the handle: the device copies of a host-form batch
+    float4 *q_rays = nullptr;   // [n][2]
+    size_t q_rays_bytes = 0;
+    float *q_time = nullptr;    // [n]
+    size_t q_time_bytes = 0;
+    float4 *q_out = nullptr;    // trace: [n][3] hit records; occluded: [n] bytes
+    size_t q_out_bytes = 0;
+    uint32_t *q_flip_gaps = nullptr; // rtmi_scene_attach_flips: [n_prims] | [n_items], or NULL
     // next-event estimation (include/rtmi_nee.h): the attached light table and per-primitive light index, freed with the
     // handle
     bool has_lights = false;
@@ -577,6 +587,10 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->h_ad_count) (void)hipHostFree(s->h_ad_count);
     if (s->ft_state) (void)hipFree(s->ft_state);
     if (s->ft_planes) (void)hipFree(s->ft_planes);
+    if (s->q_rays) (void)hipFree(s->q_rays);
+    if (s->q_time) (void)hipFree(s->q_time);
+    if (s->q_out) (void)hipFree(s->q_out);
+    if (s->q_flip_gaps) (void)hipFree(s->q_flip_gaps);
     if (s->nee_lights) (void)hipFree(s->nee_lights);
     if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
     if (s->env_texels) (void)hipFree(s->env_texels);
@@ -2287,6 +2301,141 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
     if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
     if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return RTMI_OK;
+}
+
+// ---- ray queries (include/rtmi_query.h) ---------------------------------------------------------------------------------
+// The checks both forms of an entry share, in this order: params, flags, scene; *go = false: n == 0, nothing to launch.
+// Then, for a batch with rays, the ray and output pointers.
+static int query_check(const char *name, const rtmi_scene *s, const rtmi_query_params *p, const void *rays, const void *out, bool *go) {
+    *go = false;
+    if (!p) return fail(RTMI_ERR_INVALID, std::string(name) + ": params is NULL");
+    if (p->flags & ~RTMI_FLAG_FAST_CULL)
+        return fail(RTMI_ERR_UNSUPPORTED, std::string(name) + ": ray queries accept the flags 0 and FAST_CULL only");
+    if (!s) return fail(RTMI_ERR_INVALID, std::string(name) + ": scene is NULL");
+    if (p->n == 0) return RTMI_OK;
+    if (!rays) return fail(RTMI_ERR_INVALID, std::string(name) + ": rays is NULL");
+    if (!out) return fail(RTMI_ERR_INVALID, std::string(name) + ": output is NULL");
+    *go = true;
+    return RTMI_OK;
+}
+// what the host forms refuse of a ray; the device forms take the caller's word
+static int query_check_rays(const char *name, const rtmi_ray *rays, const float *time, uint32_t n) {
+    const auto bad = [&](uint32_t i, const char *what) {
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": ray " + std::to_string(i) + " " + what);
+    };
+    for (uint32_t i = 0; i < n; i++) {
+        const rtmi_ray &r = rays[i];
+        bool finite = std::isfinite(r.t_min) && !std::isnan(r.t_max) && r.t_max != -std::numeric_limits<float>::infinity();
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(r.o[k]) && std::isfinite(r.d[k]);
+        if (time) finite = finite && std::isfinite(time[i]);
+        if (!finite) return bad(i, "has a non-finite component");
+        if (r.d[0] == 0.0f && r.d[1] == 0.0f && r.d[2] == 0.0f) return bad(i, "has a zero direction");
+        if (r.t_min > r.t_max) return bad(i, "has t_min > t_max");
+    }
+    return RTMI_OK;
+}
+// The pruned closest-hit traversal needs the BVH boxes to hold at every ray time (boxes_valid): with a time plane the
+// scene's range must be unbounded, without one it must contain 0.  Wave-uniform, decided here.
+static bool query_fast(const rtmi_scene *s, const rtmi_query_params *p, bool has_time) {
+    if (!(p->flags & RTMI_FLAG_FAST_CULL)) return false;
+    const float lo = s->meta.bvh_time_lo, hi = s->meta.bvh_time_hi;
+    if (has_time) return lo <= -RTMI_FLT_MAX && hi >= RTMI_FLT_MAX; // no MovingSphere inside a BVH (rtmi.h)
+    return lo <= 0.0f && 0.0f <= hi;
+}
+static QueryBatch query_batch(const rtmi_scene *s, const rtmi_query_params *p, const void *d_rays, const void *d_time, void *d_out,
+                              bool any) {
+    QueryBatch B{};
+    B.prim_gaps = s->q_flip_gaps;
+    B.item_gaps = s->q_flip_gaps ? s->q_flip_gaps + s->meta.n_prims : nullptr;
+    B.rays = reinterpret_cast<const float4 *>(d_rays);
+    B.time = reinterpret_cast<const float *>(d_time);
+    if (any) B.occluded = reinterpret_cast<uint8_t *>(d_out); else B.hits = reinterpret_cast<float4 *>(d_out);
+    B.n = p->n;
+    const uint64_t key = p->seed + p->first_ray; // mod 2^64
+    B.key0 = (uint32_t)key; B.key1 = (uint32_t)(key >> 32);
+    return B;
+}
+// the asynchronous forms: enqueued on the caller's stream behind the handle's previous call, like rtmi_render_device
+static int query_device(const char *name, bool any, rtmi_scene *s, const rtmi_query_params *p, const void *d_rays, const void *d_time,
+                        void *d_out, void *stream_) {
+    bool go;
+    if (int rc = query_check(name, s, p, d_rays, d_out, &go)) return rc;
+    if (!go) return RTMI_OK;
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    BusyMark busy_mark{s, stream};
+    HIP_TRY(rtmi_query_launch(any, query_fast(s, p, d_time != nullptr), stream, s->dev, query_batch(s, p, d_rays, d_time, d_out, any)));
+    return RTMI_OK;
+}
+// the blocking forms: the batch goes through the handle's query buffers (none of its render scratch) on its own stream
+static int query_host(const char *name, bool any, rtmi_scene *s, const rtmi_query_params *p, const rtmi_ray *rays, const float *time,
+                      void *out, double *kernel_ms) {
+    bool go;
+    int rc;
+    if ((rc = query_check(name, s, p, rays, out, &go))) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (!go) return RTMI_OK;
+    if ((rc = query_check_rays(name, rays, time, p->n))) return rc;
+    const Estimator m{name, false, false, 1.0f, "scene is NULL", ""};
+    RenderCall c;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    const size_t n = p->n, out_bytes = any ? n : n * sizeof(rtmi_hit);
+    if ((rc = grow(s, s->q_rays, s->q_rays_bytes, n * sizeof(rtmi_ray))) ||
+        (time && (rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(float)))) || (rc = grow(s, s->q_out, s->q_out_bytes, out_bytes)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(s->q_rays, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
+    if (time) HIP_TRY(hipMemcpyAsync(s->q_time, time, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    HIP_TRY(rtmi_query_launch(any, query_fast(s, p, time != nullptr), stream, s->dev,
+                              query_batch(s, p, s->q_rays, time ? s->q_time : nullptr, s->q_out, any)));
+    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    HIP_TRY(hipMemcpyAsync(out, s->q_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (kernel_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *kernel_ms = (double)ms;
+    }
+    return RTMI_OK;
+}
+extern "C" int rtmi_scene_attach_flips(rtmi_scene *s, const uint32_t *prim_gaps, uint32_t n_prims, const uint32_t *item_gaps,
+                                       uint32_t n_items) {
+    const char *name = "rtmi_scene_attach_flips";
+    if (!s) return fail(RTMI_ERR_INVALID, std::string(name) + ": scene is NULL");
+    const bool detach = !prim_gaps && !item_gaps;
+    if (!detach && (n_prims != s->meta.n_prims || n_items != s->meta.n_items))
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": the counts are not the scene's");
+    if (!detach && ((n_prims && !prim_gaps) || (n_items && !item_gaps))) return fail(RTMI_ERR_INVALID, std::string(name) + ": NULL array");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running query may read the old table
+    if (s->q_flip_gaps) { HIP_TRY(hipFree(s->q_flip_gaps)); s->q_flip_gaps = nullptr; }
+    if (detach) return RTMI_OK;
+    uint32_t *d = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), ((size_t)n_prims + n_items + 1u) * sizeof(uint32_t)));
+    s->q_flip_gaps = d;
+    if (n_prims) HIP_TRY(hipMemcpy(d, prim_gaps, (size_t)n_prims * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (n_items) HIP_TRY(hipMemcpy(d + n_prims, item_gaps, (size_t)n_items * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return RTMI_OK;
+}
+extern "C" int rtmi_trace(rtmi_scene *s, const rtmi_query_params *p, const rtmi_ray *rays, const float *time, rtmi_hit *hits_out,
+                          double *kernel_ms) {
+    return query_host("rtmi_trace", false, s, p, rays, time, hits_out, kernel_ms);
+}
+extern "C" int rtmi_occluded(rtmi_scene *s, const rtmi_query_params *p, const rtmi_ray *rays, const float *time, uint8_t *occluded_out,
+                             double *kernel_ms) {
+    return query_host("rtmi_occluded", true, s, p, rays, time, occluded_out, kernel_ms);
+}
+extern "C" int rtmi_trace_device(rtmi_scene *s, const rtmi_query_params *p, const void *d_rays, const void *d_time, void *d_hits,
+                                 void *stream) {
+    return query_device("rtmi_trace_device", false, s, p, d_rays, d_time, d_hits, stream);
+}
+extern "C" int rtmi_occluded_device(rtmi_scene *s, const rtmi_query_params *p, const void *d_rays, const void *d_time,
+                                    void *d_occluded, void *stream) {
+    return query_device("rtmi_occluded_device", true, s, p, d_rays, d_time, d_occluded, stream);
 }
 
 // ---- next-event estimation (include/rtmi_nee.h) -------------------------------------------------------------------------

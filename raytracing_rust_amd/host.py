@@ -515,6 +515,97 @@ class Scene:
                                                           C.c_void_p(stream or 0), C.byref(st) if st else None))
         return _stats(st) if st else None
 
+    def trace(self, origins, directions, times=None, t_min=0.001, t_max=float("inf"), seed=0, first_ray=0,
+              flags=abi.RTMI_FLAG_FAST_CULL):
+        """Closest hits of a batch of rays (include/rtmi_query.h): for ray i the record of the reference's
+        world.hit(Ray(origins[i], directions[i], times[i]), t_min, t_max), with ConstantMedium draws from the Philox stream
+        keyed seed + first_ray + i.  origins, directions: float32 [n, 3]; times: [n] or None (time 0); t_min, t_max: a
+        scalar or [n] each (t_max = inf: the render's).  Returns dict(hit bool [n], t, u, v [n], p, normal [n, 3], item,
+        prim, material int32 [n]); a miss has t = +inf, the indices -1 and the rest 0.  flags: RTMI_FLAG_FAST_CULL or 0
+        (the reference-topology traversal), same results.
+        With torch tensors on the scene's device the call is enqueued on torch's current stream (rtmi_trace_device) and
+        returns torch tensors on that device: no host copy is made.  A scene resident on a device list raises Unsupported."""
+        return self._query(False, origins, directions, times, t_min, t_max, seed, first_ray, flags)
+
+    def occluded(self, origins, directions, times=None, t_min=0.001, t_max=float("inf"), seed=0, first_ray=0,
+                 flags=abi.RTMI_FLAG_FAST_CULL):
+        """bool [n]: whether trace() of the same arguments finds a hit — the same predicate with the same draws, by a
+        scan that stops at the first accepted hit (rtmi_occluded, include/rtmi_query.h)."""
+        return self._query(True, origins, directions, times, t_min, t_max, seed, first_ray, flags)
+
+    def _query(self, any_hit, origins, directions, times, t_min, t_max, seed, first_ray, flags):
+        self._ready({})
+        lib = self.host.lib
+        if hasattr(origins, "data_ptr") and hasattr(origins, "is_cuda"):
+            return self._query_torch(any_hit, origins, directions, times, t_min, t_max, seed, first_ray, flags)
+        o, d = (np.ascontiguousarray(a, dtype=np.float32) for a in (origins, directions))
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("origins and directions are [n, 3] arrays, not %r and %r" % (o.shape, d.shape))
+        n = o.shape[0]
+        rays = np.empty(n, RAY_DTYPE)
+        rays["o"], rays["d"], rays["t_min"], rays["t_max"] = o, d, t_min, t_max
+        tm = None if times is None else np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.float32), (n,)))
+        p = abi.QueryParams(n, int(flags), int(seed) & (2 ** 64 - 1), int(first_ray) & (2 ** 64 - 1))
+        ms = C.c_double(0.0)
+        out = np.zeros(n, np.uint8 if any_hit else HIT_DTYPE)
+        fn = lib.rth_occluded if any_hit else lib.rth_trace
+        self.host._check(fn(self.h, C.byref(p), rays.ctypes.data, None if tm is None else tm.ctypes.data, out.ctypes.data,
+                            C.byref(ms)))
+        if any_hit:
+            return out.astype(bool)
+        res = {k: np.ascontiguousarray(out[k]) for k in ("t", "u", "v", "p", "item", "prim", "material")}
+        res["normal"] = np.ascontiguousarray(out["n"])
+        res["hit"] = res["item"] >= 0
+        res["kernel_ms"] = ms.value
+        return res
+
+    def _query_torch(self, any_hit, origins, directions, times, t_min, t_max, seed, first_ray, flags):
+        import torch
+
+        dev = origins.device
+        if dev.type != "cuda" or (dev.index or 0) != self.device:
+            raise ValueError("the rays are on %s, the scene is on device %d" % (dev, self.device))
+        if origins.dtype != torch.float32 or directions.dtype != torch.float32 or origins.dim() != 2 or \
+                origins.shape[1] != 3 or directions.shape != origins.shape or directions.device != dev:
+            raise ValueError("origins and directions are float32 [n, 3] tensors on one device")
+        n = origins.shape[0]
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        rays[:, 0:3], rays[:, 4:7] = origins, directions
+        rays[:, 3] = torch.as_tensor(t_min, dtype=torch.float32, device=dev)
+        rays[:, 7] = torch.as_tensor(t_max, dtype=torch.float32, device=dev)
+        tm = None if times is None else torch.as_tensor(times, dtype=torch.float32, device=dev).expand(n).contiguous()
+        out = torch.empty((n,), dtype=torch.uint8, device=dev) if any_hit else torch.empty((n, 12), dtype=torch.float32, device=dev)
+        if n:
+            p = abi.QueryParams(n, int(flags), int(seed) & (2 ** 64 - 1), int(first_ray) & (2 ** 64 - 1))
+            fn = self.host.lib.rth_occluded_device if any_hit else self.host.lib.rth_trace_device
+            self.host._check(fn(self.h, C.byref(p), C.c_void_p(rays.data_ptr()), C.c_void_p(tm.data_ptr()) if tm is not None else None,
+                                C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        if any_hit:
+            return out != 0
+        ids = out[:, 9:12].contiguous().view(torch.int32)
+        return {"hit": ids[:, 0] >= 0, "t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "p": out[:, 3:6], "normal": out[:, 6:9],
+                "item": ids[:, 0], "prim": ids[:, 1], "material": ids[:, 2]}
+
+
+# rtmi_ray and rtmi_hit (include/rtmi_query.h) as numpy sees them
+RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("t_min", "<f4"), ("d", "<f4", (3,)), ("t_max", "<f4")])
+HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("p", "<f4", (3,)), ("n", "<f4", (3,)), ("item", "<i4"),
+                      ("prim", "<i4"), ("material", "<i4")])
+
+
+def primary_rays(cam, nx, ny):
+    """The pixel-centre rays of a camera from its lens centre, for picking and timing: (origins, directions), float32
+    [ny, nx, 3] each, row 0 the top row.  cam: a Camera of Host or its lowered form (abi.Camera).  Pixel (column i, row j
+    from the bottom) looks along ((llc + horizontal * u) + vertical * v) - origin with u = (i + 0.5) / nx and
+    v = (j + 0.5) / ny, in float32 as the device's camera_sample computes a direction."""
+    c = cam.lower() if hasattr(cam, "lower") else cam
+    f32 = np.float32
+    llc, hor, ver, org = (np.array(list(x), f32) for x in (c.lower_left_corner, c.horizontal, c.vertical, c.origin))
+    u = ((np.arange(nx, dtype=f32) + f32(0.5)) / f32(nx)).astype(f32)
+    v = ((np.arange(ny, dtype=f32)[::-1] + f32(0.5)) / f32(ny)).astype(f32)
+    d = ((llc + hor * u[None, :, None]) + ver * v[:, None, None]) - org
+    return np.ascontiguousarray(np.broadcast_to(org, (ny, nx, 3))), np.ascontiguousarray(d.astype(f32))
+
 
 # the output planes of the render methods: channels after [ny, nx], dtype
 _PLANES = {"linear": ((3,), np.float32), "rgb8": ((3,), np.uint8), "stderr": ((3,), np.float32), "spp": ((), np.uint32),

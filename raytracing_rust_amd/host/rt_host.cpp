@@ -550,9 +550,15 @@ static const Hittable *strip_flips(const Hittable *h, bool &flip) {
 // transforms outermost first, exactly as lower_item records an item's chain: Traslate<H> / Rotate<H> are generic over
 // any Hittable, so the reference lets them sit anywhere, e.g. as the children of a BVHNode (bvh.rs:11-12).
 static const Hittable *strip_wrappers(const Hittable *h, bool &flip, std::vector<rtmi_xform> *chain,
-                                      std::vector<double> *chain_w = nullptr) { // chain_w: x, y, z, 0 of each, before rounding
+                                      std::vector<double> *chain_w = nullptr, // chain_w: x, y, z, 0 of each, before rounding
+                                      uint32_t *flip_gaps = nullptr) {        // (with chain) the flips' places: rt_host.hpp
     for (;;) {
-        if (auto f = dynamic_cast<const FlipNormals *>(h)) { flip = !flip; h = f->inner().get(); continue; }
+        if (auto f = dynamic_cast<const FlipNormals *>(h)) {
+            flip = !flip;
+            if (flip_gaps && chain) *flip_gaps ^= 1u << (chain->size() < 31 ? chain->size() : 31);
+            h = f->inner().get();
+            continue;
+        }
         if (auto t = dynamic_cast<const Traslate *>(h)) {
             if (chain) {
                 rtmi_xform x{};
@@ -605,7 +611,8 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
     // meta word; FlipNormals anywhere in the chain only toggles the flag (negation commutes with both)
     std::vector<rtmi_xform> chain;
     std::vector<double> chain_w;
-    const Hittable &h = *strip_wrappers(&h0, flip, &chain, &chain_w);
+    uint32_t flip_gaps = flip ? 1u : 0u; // the caller's flips sit outside the primitive's own chain
+    const Hittable &h = *strip_wrappers(&h0, flip, &chain, &chain_w, &flip_gaps);
     double Aw[4] = {0, 0, 0, 0}, Bw[4] = {0, 0, 0, 0}, dt_w = 1.0; // the same values in double (f64 render mode)
     m.flags = flip ? RTMI_PRIMFLAG_FLIP : 0u;
     if (!chain.empty()) {
@@ -657,6 +664,7 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
     out.prim_a.insert(out.prim_a.end(), A, A + 4);
     out.prim_b.insert(out.prim_b.end(), B, B + 4);
     out.prim_meta.push_back(m);
+    out.prim_flip_gaps.push_back(flip_gaps);
     const float big = 3.40282346638528859811704183484516925e+38f;
     const float gate[8] = {-big, -big, -big, 0.0f, big, big, big, 0.0f}; // no gate unless a BVH sets one
     out.prim_gate.insert(out.prim_gate.end(), gate, gate + 8);
@@ -1275,12 +1283,15 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
     it.alt_first = -1;
     it.xform_first = (int32_t)out.xforms.size();
     bool flip = false, medium = false, nested = false;
+    uint32_t flip_gaps = 0u; // the places of the flips in the item's chain (rt_host.hpp); a medium's: those around the medium
     float inner_neg_inv_density = 0.0f;
     double inner_nid_w = 0.0, nid_w = 0.0, root_w[6] = {0, 0, 0, 0, 0, 0}; // the same values in double (f64 render mode)
     uint32_t medium_outer = 0;
     const Hittable *h = &top;
     if (deferred) { // a child of a BVHNode lowered as an item: it sits inside the transforms of that BVH item — a copy of them first —
         flip = deferred->flip; // ... and inside the FlipNormals around that item or around its ancestors within the tree
+        flip_gaps = deferred->outer_gaps; // the enclosing item's flips keep their places; those inside the tree sit behind its chain
+        if ((__builtin_parity(flip_gaps) != 0) != flip) flip_gaps ^= 1u << (deferred->chain_count < 31 ? deferred->chain_count : 31);
         for (int k = 0; k < deferred->chain_count; k++) {
             out.xforms.push_back(out.xforms[(size_t)(deferred->chain_first + k)]);
             for (int q = 0; q < 4; q++) out.wide.xforms.push_back(out.wide.xforms[(size_t)(deferred->chain_first + k) * 4 + q]);
@@ -1288,7 +1299,12 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
         it.xform_count = deferred->chain_count;
     }
     for (;;) { // peel wrappers, outermost first
-        if (auto f = dynamic_cast<const FlipNormals *>(h)) { flip = !flip; h = f->inner().get(); continue; }
+        if (auto f = dynamic_cast<const FlipNormals *>(h)) {
+            flip = !flip;
+            if (!medium) flip_gaps ^= 1u << (it.xform_count < 31 ? it.xform_count : 31);
+            h = f->inner().get();
+            continue;
+        }
         if (auto m = dynamic_cast<const ConstantMedium *>(h)) {
             if (medium) { // a medium as the boundary of a medium (medium.rs:11-15 is generic): one level, no wrappers in between
                 if (nested) throw Unsupported("ConstantMedium nested more than once is not lowered");
@@ -1367,7 +1383,8 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
             pending_media_.clear();
             run_item_ = -1;
             for (size_t k = 0; k < pend.size(); k++) {
-                const DeferredMedium dm{pend[k].gate, it.xform_first, it.xform_count, k == 0 && !deferred, pend[k].rank, pend[k].flip != flip};
+                DeferredMedium dm{pend[k].gate, it.xform_first, it.xform_count, k == 0 && !deferred, pend[k].rank, pend[k].flip != flip};
+                dm.outer_gaps = flip_gaps;
                 lower_item(*pend[k].obj, &dm);
             }
             return;
@@ -1460,16 +1477,17 @@ void SceneBuilder::lower_item(const Hittable &top, const DeferredMedium *deferre
     if (it.kind == RTMI_ITEM_BVH && !pending_media_.empty()) { // media that were children of this BVH: deferred items, in order
         if (medium) throw Unsupported("a ConstantMedium whose boundary BVHNode holds media or instanced subtrees is not lowered");
         if (!deferred) it.flags |= RTMI_ITEMFLAG_SAVE_T0; // (a deferred BVH item's own deferred children share its group's T0)
-        push_item(it, nid_w, root_w);
+        push_item(it, nid_w, root_w, flip_gaps);
         const std::vector<PendingMedium> pend = std::move(pending_media_);
         pending_media_.clear();
         for (const PendingMedium &pm : pend) {
-            const DeferredMedium dm{pm.gate, it.xform_first, it.xform_count, false, pm.rank, pm.flip != flip};
+            DeferredMedium dm{pm.gate, it.xform_first, it.xform_count, false, pm.rank, pm.flip != flip};
+            dm.outer_gaps = flip_gaps;
             lower_item(*pm.obj, &dm);
         }
         return;
     }
-    push_item(it, nid_w, root_w);
+    push_item(it, nid_w, root_w, flip_gaps);
 }
 
 void SceneBuilder::lower_world(const Hittable &world) {
@@ -1600,6 +1618,37 @@ Image DeviceScene::render(const Camera &cam, uint32_t nx, uint32_t ny, uint32_t 
     if (rtmi_multi_render(handle_, &c, &p, img.linear.data(), img.rgb8.data(), &img.stats))
         throw std::runtime_error(std::string("rtmi_multi_render: ") + rtmi_last_error());
     return img;
+}
+Scene::Scene(const Hittable &world, int device) {
+    const LoweredScene ls = lower_scene(world);
+    const rtmi_scene_desc d = ls.desc(); // borrowed for the call: rtmi_scene_create copies it to the device
+    if (int rc = rtmi_scene_create(&d, device, &handle_))
+        throw std::runtime_error(std::string("rtmi_scene_create: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+    if (int rc = rtmi_scene_attach_flips(handle_, ls.prim_flip_gaps.data(), (uint32_t)ls.prim_flip_gaps.size(), ls.item_flip_gaps.data(),
+                                         (uint32_t)ls.item_flip_gaps.size()))
+        throw std::runtime_error(std::string("rtmi_scene_attach_flips: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+}
+Scene::~Scene() { rtmi_scene_destroy(handle_); }
+static rtmi_query_params query_params(const std::vector<rtmi_ray> &rays, const std::vector<float> &time, const QueryOptions &opt) {
+    if (!time.empty() && time.size() != rays.size()) throw std::runtime_error("ray query: time holds one value per ray, or none");
+    if (rays.size() > 0xffffffffull) throw std::runtime_error("ray query: more than 2^32 - 1 rays in one call");
+    rtmi_query_params p{};
+    p.n = (uint32_t)rays.size(); p.flags = opt.flags; p.seed = opt.seed; p.first_ray = opt.first_ray;
+    return p;
+}
+std::vector<rtmi_hit> Scene::trace(const std::vector<rtmi_ray> &rays, const std::vector<float> &time, const QueryOptions &opt) {
+    const rtmi_query_params p = query_params(rays, time, opt);
+    std::vector<rtmi_hit> out(rays.size());
+    if (int rc = rtmi_trace(handle_, &p, rays.data(), time.empty() ? nullptr : time.data(), out.data(), nullptr))
+        throw std::runtime_error(std::string("rtmi_trace: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+    return out;
+}
+std::vector<uint8_t> Scene::occluded(const std::vector<rtmi_ray> &rays, const std::vector<float> &time, const QueryOptions &opt) {
+    const rtmi_query_params p = query_params(rays, time, opt);
+    std::vector<uint8_t> out(rays.size());
+    if (int rc = rtmi_occluded(handle_, &p, rays.data(), time.empty() ? nullptr : time.data(), out.data(), nullptr))
+        throw std::runtime_error(std::string("rtmi_occluded: ") + rtmi_last_error() + " (code " + std::to_string(rc) + ")");
+    return out;
 }
 Image Camera::render(const Hittable &world, uint32_t nx, uint32_t ny, uint32_t ns, const RenderOptions &opt) const {
     if (!opt.devices.empty()) // several GPUs of this process: tiles t % n, one gather

@@ -35,6 +35,7 @@
 #include "rtmi_f64.h"
 #include "rtmi_adaptive.h"
 #include "rtmi_features.h"
+#include "rtmi_query.h"
 #include "rtmi_nee.h"
 
 namespace rt {
@@ -351,6 +352,13 @@ struct LoweredScene {
     // ray times for which every MovingSphere inside a BVH stays inside the boxes built for it (its own
     // [time0, time1]); outside, librtmi falls back from pruned to exact traversal
     float bvh_time_lo = -3.40282346638528859811704183484516925e+38f, bvh_time_hi = 3.40282346638528859811704183484516925e+38f;
+    // Where the FlipNormals around a primitive / inside an item's chain sit among its Traslate / Rotate wrappers, for the
+    // ray queries' normals (rtmi_scene_attach_flips, include/rtmi_query.h): bit g of prim_flip_gaps[i] = an odd number of
+    // flips between transforms g - 1 and g of primitive i's own chain (outermost first; bit 0: outside the whole chain,
+    // which is also where the flips of the enclosing lists and tree nodes sit; bit count: directly around the primitive);
+    // item_flip_gaps[i] likewise for item i's chain (a medium item: the flips around the medium only).  The flags of the
+    // description keep the parity alone, which is all a render needs.
+    std::vector<uint32_t> prim_flip_gaps, item_flip_gaps;
     // The same values before their rounding to fp32, for the f64 render mode (include/rtmi_f64.h): one entry per entry of
     // the planes above, same indices
     struct Wide {
@@ -383,13 +391,14 @@ class SceneBuilder {
   private:
     // a ConstantMedium that was a child of a BVHNode, lowered as an item of its own behind the BVH item (rt_host.cpp)
     struct PendingMedium { const Hittable *obj; AABB gate; int32_t rank; bool flip; }; // rank: primitives pushed before it (in-order position)
-    struct DeferredMedium { AABB gate; int32_t chain_first; int32_t chain_count; bool save_t0; int32_t rank; bool flip; uint32_t scan = 0u; }; // scan: LISTSCAN flags of a member
+    struct DeferredMedium { AABB gate; int32_t chain_first; int32_t chain_count; bool save_t0; int32_t rank; bool flip; uint32_t scan = 0u; uint32_t outer_gaps = 0u; }; // scan: LISTSCAN flags of a member; outer_gaps: the enclosing item's flip places
     void lower_scan_group(const Hittable &top, const DeferredMedium &deferred);
     std::vector<PendingMedium> pending_media_;
     void collect_media(const Hittable *h, const BVHNode &parent, bool flip_all);
     void lower_item(const Hittable &h, const DeferredMedium *deferred = nullptr);
-    void push_item(const rtmi_item &it, double nid_w, const double *root_w) { // the item and its wide values (root_w: 6 or NULL)
+    void push_item(const rtmi_item &it, double nid_w, const double *root_w, uint32_t flip_gaps = 0u) { // the item and its wide values (root_w: 6 or NULL)
         out.items.push_back(it);
+        out.item_flip_gaps.push_back(flip_gaps);
         out.wide.item_nid.push_back(nid_w);
         for (int k = 0; k < 6; k++) out.wide.item_root.push_back(root_w ? root_w[k] : 0.0);
     }
@@ -467,6 +476,29 @@ class DeviceScene {
   private:
     std::vector<int> devices_;
     rtmi_multi *handle_ = nullptr;
+};
+// A world resident on one GPU for ray queries (include/rtmi_query.h): lowered and uploaded once, then any number of
+// batches of caller-supplied rays traced against it — picking, visibility and ambient-occlusion terms, a host's own
+// integrator.  Not copyable; calls on one scene serialise (the handle's thread model).
+struct QueryOptions {
+    uint64_t seed = 0;      // ray i draws its ConstantMedium numbers from the Philox stream keyed seed + first_ray + i
+    uint64_t first_ray = 0; // index of the call's ray 0 in the caller's batch: splitting a batch changes nothing
+    uint32_t flags = RTMI_FLAG_FAST_CULL; // or 0: the reference-topology traversal, same results
+};
+class Scene {
+  public:
+    explicit Scene(const Hittable &world, int device = 0);
+    ~Scene();
+    Scene(const Scene &) = delete;
+    Scene &operator=(const Scene &) = delete;
+    // hit[i] = world.hit(rays[i], its t_min, its t_max) at time[i] (time empty: 0); a miss has item = -1 and t = +inf
+    std::vector<rtmi_hit> trace(const std::vector<rtmi_ray> &rays, const std::vector<float> &time = {}, const QueryOptions &opt = {});
+    // occluded[i] = 1 iff trace()'s hit i is a hit: the same predicate, stopped at the first accepted hit
+    std::vector<uint8_t> occluded(const std::vector<rtmi_ray> &rays, const std::vector<float> &time = {}, const QueryOptions &opt = {});
+    rtmi_scene *handle() const { return handle_; }
+
+  private:
+    rtmi_scene *handle_ = nullptr;
 };
 // tests/test.rs:55-85 — note the argument order (ny, nx, ns, cam, world)
 std::string create_image(size_t ny, size_t nx, size_t ns, const Camera &cam, const Hittable &world,

@@ -13,6 +13,7 @@
 #include "rtmi_adaptive_nee.h"
 #include "rtmi_roulette.h"
 #include "rtmi_session.h"
+#include "rtmi_query.h"
 
 using namespace rt;
 
@@ -255,7 +256,11 @@ RTH_API int rth_upload(void *lowered, int device) {
         Obj *o = LOW(lowered);
         if (o->dev) { rtmi_scene_destroy(o->dev); o->dev = nullptr; }
         const rtmi_scene_desc d = o->lowered->desc();
-        return done("rtmi_scene_create", rtmi_scene_create(&d, device, &o->dev), CODED);
+        if (int rc = done("rtmi_scene_create", rtmi_scene_create(&d, device, &o->dev), CODED)) return rc;
+        // the places of the FlipNormals in the wrapper chains, for the normals of the ray queries (include/rtmi_query.h)
+        const LoweredScene &ls = *o->lowered;
+        return done("rtmi_scene_attach_flips", rtmi_scene_attach_flips(o->dev, ls.prim_flip_gaps.data(), (uint32_t)ls.prim_flip_gaps.size(),
+                                                                        ls.item_flip_gaps.data(), (uint32_t)ls.item_flip_gaps.size()), CODED);
     });
 }
 RTH_API int rth_render(void *lowered, void *cam, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8,
@@ -285,6 +290,37 @@ RTH_API int rth_render_features(void *lowered, void *cam, const rtmi_render_para
         rtmi_scene *dev = DEV(lowered, name, "features");
         const rtmi_camera c = CAM(cam).lower();
         return done(name, rtmi_render_features(dev, &c, p, out_albedo, out_normal, out_depth, out_hits, out_path_sig, stats),
+                    CODED_UNSUPPORTED);
+    });
+}
+// ray queries (include/rtmi_query.h) on the uploaded handle: host pointers and blocking, or device pointers enqueued on
+// `stream`; RTH_UNSUPPORTED for the flags the queries do not carry and for a multi-GPU handle
+RTH_API int rth_trace(void *lowered, const rtmi_query_params *p, const rtmi_ray *rays, const float *time, rtmi_hit *hits_out,
+                      double *kernel_ms) {
+    return guard([&] {
+        const char *name = "rtmi_trace";
+        return done(name, rtmi_trace(DEV(lowered, name, "ray-query"), p, rays, time, hits_out, kernel_ms), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_occluded(void *lowered, const rtmi_query_params *p, const rtmi_ray *rays, const float *time, uint8_t *occluded_out,
+                         double *kernel_ms) {
+    return guard([&] {
+        const char *name = "rtmi_occluded";
+        return done(name, rtmi_occluded(DEV(lowered, name, "ray-query"), p, rays, time, occluded_out, kernel_ms), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_trace_device(void *lowered, const rtmi_query_params *p, const void *d_rays, const void *d_time, void *d_hits,
+                             void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_trace_device";
+        return done(name, rtmi_trace_device(DEV(lowered, name, "ray-query"), p, d_rays, d_time, d_hits, stream), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_occluded_device(void *lowered, const rtmi_query_params *p, const void *d_rays, const void *d_time, void *d_occluded,
+                                void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_occluded_device";
+        return done(name, rtmi_occluded_device(DEV(lowered, name, "ray-query"), p, d_rays, d_time, d_occluded, stream),
                     CODED_UNSUPPORTED);
     });
 }

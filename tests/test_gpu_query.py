@@ -1,0 +1,263 @@
+"""Ray queries (include/rtmi_query.h) on the device.
+
+The feature is defined as the reference's `world.hit` for a batch of caller-supplied rays, so every output word is
+checked against the unchanged fp32 oracle (tests/query_ref.py builds the ray sets and the oracle's records once per scene):
+1. oracle parity on every ray of the fan and bounce sets of seven scenes, media included, in both flag settings;
+2. the same on randomly composed scenes and on the media-in-BVH worlds (deferred items, list scans, nested media);
+3. occlusion is the same predicate: equal to trace's hit flag on all of those rays, and right at t_max = t and its
+   two neighbours, where sphere and rect bounds differ in strictness (the oracle decides);
+4. the result does not depend on how a batch is split into calls, nor on the form (host or device pointers), and the
+   device form writes exactly n records;
+5. item, prim and material name what was hit;
+6. trace of a render's primary rays finds the depth and hit flags of render_features(ns=1).
+
+The normals are compared as bit patterns like everything else: the lowering records where the FlipNormals sit among the
+Traslate / Rotate wrappers (rtmi_scene_attach_flips, attached by upload), because a negation inside a Rotate and one
+outside it differ in the sign of an exact zero."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import query_ref as Q
+import scenes_random
+import test_media_in_bvh as media_worlds
+from raytracing_rust_amd import abi, scenes
+
+FC = abi.RTMI_FLAG_FAST_CULL
+SCENES = ["cornell_box", "two_spheres", "earth", "random_spheres", "final_scene", "lit_smoke", "hollow_glass"]
+MEDIA_FREE = ["cornell_box", "two_spheres", "earth", "random_spheres", "hollow_glass"]
+_CACHE = {}
+
+
+def _sets(orc32, name):
+    """the ray sets and oracle records of a named scene, built once"""
+    if name not in _CACHE:
+        world = Q.build_world(orc32, name)
+        look_from, look_at = Q.scene_camera(name)
+        _CACHE[name] = Q.ray_sets(orc32, world, look_from, look_at, 1024, shutter=(0.0, 1.0) if name == "random_spheres" else None,
+                                  intervals=name in MEDIA_FREE)
+        orc32.free_all()
+    return _CACHE[name]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _same(a, b):
+    return sorted(a) == sorted(b) and all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a if k != "kernel_ms")
+
+
+def _trace(sc, s, flags, **kw):
+    return sc.trace(s["o"], s["d"], s["times"], t_min=Q.T_MIN, seed=Q.SEED, flags=flags, **kw)
+
+
+def _tree_prims(a, root):
+    out, todo = set(), [root]
+    while todo:
+        n = a["nodes"][todo.pop()]
+        for ch in (n.left, n.right):
+            if ch >= 0:
+                todo.append(ch)
+            else:
+                out.add(ch & 0x0FFFFFFF)
+    return out
+
+
+def _check_indices(a, got, what):
+    """test 5: item, prim and material of every hit"""
+    trees = {}
+    for i in np.flatnonzero(got["hit"]):
+        item, prim, mat = int(got["item"][i]), int(got["prim"][i]), int(got["material"][i])
+        assert 0 <= item < len(a["items"]), (what, i)
+        it = a["items"][item]
+        if prim < 0:  # a medium event
+            assert prim == -1 and (it.flags & 2) and mat == it.medium_material, (what, i, item, prim, mat)
+            continue
+        if it.kind == 1:  # RTMI_ITEM_BVH
+            if item not in trees:
+                trees[item] = _tree_prims(a, it.first)
+            assert prim in trees[item], (what, i, item, prim)
+        else:
+            assert it.first <= prim < it.first + it.count, (what, i, item, prim)
+        assert a["prim_meta"][prim].material == mat, (what, i, prim, mat)
+
+
+def _check_set(sc, a, s, what):
+    """tests 1, 3 (first half) and 5 on one ray set: both flag settings against the oracle's records"""
+    ref = s["ref"]
+    exact, fast = _trace(sc, s, 0), _trace(sc, s, FC)
+    assert _same(exact, fast), what
+    got = fast
+    assert np.array_equal(got["hit"], ref["hit"]), (what, np.flatnonzero(got["hit"] != ref["hit"])[:8])
+    for k in ("t", "u", "v", "p"):
+        bad = np.flatnonzero((_bits(got[k]) != _bits(ref[k])).reshape(len(ref["hit"]), -1).any(axis=1))
+        assert bad.size == 0, (what, k, bad[:8], got[k][bad[:2]], ref[k][bad[:2]])
+    kinds = np.array([m.kind for m in a["materials"]] + [-1])
+    assert np.array_equal(kinds[got["material"]], ref["mat_kind"]), what
+    miss = ~got["hit"]
+    assert np.all(got["item"][miss] == -1) and np.all(got["prim"][miss] == -1) and np.all(got["material"][miss] == -1), what
+    assert np.all(np.isposinf(got["t"][miss])) and not np.any(got["p"][miss]) and not np.any(got["normal"][miss]), what
+    for flags in (0, FC):
+        occ = sc.occluded(s["o"], s["d"], s["times"], t_min=Q.T_MIN, seed=Q.SEED, flags=flags)
+        assert occ.dtype == bool and np.array_equal(occ, got["hit"]), (what, flags, np.flatnonzero(occ != got["hit"])[:8])
+    _check_indices(a, got, what)
+    bad = np.flatnonzero((_bits(got["normal"]) != _bits(ref["normal"])).any(axis=1))  # (-0 against +0 counts)
+    assert bad.size == 0, (what, "normal", bad.size, bad[:8], got["normal"][bad[:2]], ref["normal"][bad[:2]])
+    return got
+
+
+# ---- 1. oracle parity, every ray -----------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_every_ray_equals_the_fp32_oracle(host, orc32, name):
+    sets = _sets(orc32, name)
+    sc = host.lower(Q.build_world(host, name)).upload(0)
+    a = sc.arrays()
+    for which, s in sets.items():
+        got = _check_set(sc, a, s, (name, which))
+        print(name, which, "rays", len(got["hit"]), "hits", int(got["hit"].sum()), "medium", int((got["prim"][got["hit"]] < 0).sum()))
+    if name == "final_scene":  # a kernel that never samples media cannot pass
+        assert int((sets["fan"]["ref"]["mat_kind"] == abi.MAT_ISOTROPIC).sum()) >= 64
+
+
+# ---- 2. rare compositions ------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("instanced", [False, True], ids=["plain", "instanced"])
+@pytest.mark.parametrize("seed", range(8))
+def test_random_scenes_equal_the_fp32_oracle(host, orc32, seed, instanced):
+    eye, centre = Q.random_fan_camera(host, seed)
+    oworld = scenes_random.random_scene(orc32, seed, None, instanced)
+    sets = Q.ray_sets(orc32, oworld, eye, centre, 512, shutter=(0.0, 1.0) if seed % 2 else None)
+    orc32.free_all()
+    sc = host.lower(scenes_random.random_scene(host, seed, None, instanced)).upload(0)
+    a = sc.arrays()
+    for which, s in sets.items():
+        _check_set(sc, a, s, (seed, instanced, which))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("build", [media_worlds.world_media_in_bvh, media_worlds.world_instanced_subtrees,
+                                   media_worlds.world_nested_media, media_worlds.world_media_in_lists_in_bvh],
+                         ids=lambda f: f.__name__)
+def test_media_in_bvh_worlds_equal_the_fp32_oracle(host, orc32, build):
+    sets = Q.ray_sets(orc32, build(orc32), (1.0, 3.0, 9.0), (0.0, 0.6, 0.5), 512)  # media_worlds.camera's eye and target
+    orc32.free_all()
+    sc = host.lower(build(host)).upload(0)
+    a = sc.arrays()
+    n_medium = 0
+    for which, s in sets.items():
+        got = _check_set(sc, a, s, (build.__name__, which))
+        n_medium += int((got["prim"][got["hit"]] < 0).sum())
+    if build is not media_worlds.world_instanced_subtrees:
+        assert n_medium > 0, build.__name__
+
+
+# ---- 3. occlusion at the end of the interval -----------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MEDIA_FREE)
+def test_interval_ends_follow_the_oracle(host, orc32, name):
+    sets = _sets(orc32, name)
+    sc = host.lower(Q.build_world(host, name)).upload(0)
+    seen = set()
+    for which, s in sets.items():
+        for idx, t_max, want in s["near"]:
+            o, d = s["o"][idx], s["d"][idx]
+            times = None if s["times"] is None else s["times"][idx]
+            for flags in (0, FC):
+                occ = sc.occluded(o, d, times, t_min=Q.T_MIN, t_max=t_max, flags=flags)
+                hit = sc.trace(o, d, times, t_min=Q.T_MIN, t_max=t_max, flags=flags)["hit"]
+                assert np.array_equal(occ, want), (name, which, flags, np.flatnonzero(occ != want)[:8])
+                assert np.array_equal(hit, want), (name, which, flags, np.flatnonzero(hit != want)[:8])
+            seen.update(want.tolist())
+    assert seen == {False, True}, (name, seen)  # both answers occur: the intervals are where the bounds decide
+
+
+# ---- 4. batching ---------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_result_does_not_depend_on_the_batching_or_the_form(host, orc32):
+    import torch
+
+    s = _sets(orc32, "final_scene")["fan"]
+    n = 1000
+    o, d = s["o"][:n], s["d"][:n]
+    sc = host.lower(Q.build_world(host, "final_scene")).upload(0)
+    full = sc.trace(o, d, seed=Q.SEED)
+    focc = sc.occluded(o, d, seed=Q.SEED)
+    assert np.array_equal(full["hit"], s["ref"]["hit"][:n]) and np.array_equal(focc, full["hit"])
+    keys = [k for k in full if k != "kernel_ms"]
+    for k in (1, 63, 64, 65, 999):
+        lo, hi = sc.trace(o[:k], d[:k], seed=Q.SEED), sc.trace(o[k:], d[k:], seed=Q.SEED, first_ray=k)
+        for key in keys:
+            assert np.concatenate([lo[key], hi[key]]).tobytes() == full[key].tobytes(), (k, key)
+        occ = np.concatenate([sc.occluded(o[:k], d[:k], seed=Q.SEED), sc.occluded(o[k:], d[k:], seed=Q.SEED, first_ray=k)])
+        assert np.array_equal(occ, focc), k
+    for m in (0, 1, 63, 65):
+        part = sc.trace(o[:m], d[:m], seed=Q.SEED)
+        for key in keys:
+            assert part[key].shape[0] == m and part[key].tobytes() == full[key][:m].tobytes(), (m, key)
+        assert np.array_equal(sc.occluded(o[:m], d[:m], seed=Q.SEED), focc[:m]), m
+    # the device form on torch tensors
+    dev = torch.device("cuda", 0)
+    to, td = torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev)
+    got = sc.trace(to, td, seed=Q.SEED)
+    for key in keys:
+        assert got[key].device == to.device and got[key].cpu().numpy().tobytes() == full[key].tobytes(), key
+    gocc = sc.occluded(to, td, seed=Q.SEED)
+    assert gocc.device == to.device and np.array_equal(gocc.cpu().numpy(), focc)
+    assert sc.trace(to[:0], td[:0])["hit"].shape[0] == 0 and sc.occluded(to[:0], td[:0]).shape[0] == 0
+    # exactly n records: the 64 records behind them keep the sentinel
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = to, Q.T_MIN, td, float("inf")
+    p = abi.QueryParams(n, FC, Q.SEED, 0)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    hits = torch.full((n + 64, 12), -7.25, dtype=torch.float32, device=dev)
+    host._check(host.lib.rth_trace_device(sc.h, C.byref(p), C.c_void_p(rays.data_ptr()), None, C.c_void_p(hits.data_ptr()), stream))
+    occ = torch.full((n + 64,), 0xA5, dtype=torch.uint8, device=dev)
+    host._check(host.lib.rth_occluded_device(sc.h, C.byref(p), C.c_void_p(rays.data_ptr()), None, C.c_void_p(occ.data_ptr()), stream))
+    torch.cuda.synchronize(dev)
+    hits, occ = hits.cpu().numpy(), occ.cpu().numpy()
+    assert np.all(hits[n:] == np.float32(-7.25)) and np.all(occ[n:] == 0xA5)
+    assert hits[:n, 0].tobytes() == full["t"].tobytes() and np.array_equal(occ[:n] != 0, focc)
+
+
+# ---- 5. indices: the light of cornell_box ----------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_the_ray_to_cornell_boxs_light_returns_the_light(host):
+    sc = host.lower(Q.build_world(host, "cornell_box")).upload(0)
+    a = sc.arrays()
+    lights = [i for i, m in enumerate(a["prim_meta"]) if a["materials"][m.material].kind == abi.MAT_DIFFUSE_LIGHT]
+    assert len(lights) == 1 and a["prim_meta"][lights[0]].type == 2  # one RECT
+    L = lights[0]
+    x0, y0, x1, y1 = (float(v) for v in a["prim_a"][L])
+    k, plane = float(a["prim_b"][L][0]), (a["prim_meta"][L].flags >> 8) & 3
+    ka, aa, ba = {0: (0, 1, 2), 1: (1, 2, 0), 2: (2, 0, 1)}[plane]  # rect.rs:40-44
+    centre = np.zeros(3)
+    centre[ka], centre[aa], centre[ba] = k, 0.5 * (x0 + x1), 0.5 * (y0 + y1)
+    eye = np.array(scenes.SCENES["cornell_box"][1])
+    o, d = eye.astype(np.float32)[None, :], (centre - eye).astype(np.float32)[None, :]
+    got = sc.trace(o, d)
+    assert got["hit"][0] and got["prim"][0] == L and a["prim_meta"][got["prim"][0]].type == 2
+    assert a["materials"][got["material"][0]].kind == abi.MAT_DIFFUSE_LIGHT
+    assert abs(float(got["t"][0]) - 1.0) < 1e-3 and np.allclose(got["p"][0], centre, atol=0.1)
+    assert sc.occluded(o, d)[0] and not sc.occluded(o, d, t_max=0.5)[0]
+
+
+# ---- 6. against the render -------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_trace_of_the_primary_rays_equals_the_features_depth(host):
+    from test_gpu_features import NX, NY, SEED, _build, _primary_rays
+
+    cam, world = _build(host, "cornell_box", aperture=0.0)
+    sc = host.lower(world).upload(0)
+    f = sc.render_features(cam, NX, NY, 1, seed=SEED)
+    org, dirs = _primary_rays(cam.lower(), NX, NY, SEED)
+    d = dirs.reshape(-1, 3)
+    got = sc.trace(np.tile(org, (d.shape[0], 1)), d, t_min=0.001)
+    hit = got["hit"].reshape(NY, NX)
+    assert np.array_equal(hit, f["hits"] == 1) and hit.sum() > NX * NY // 4
+    d64 = d.astype(np.float64)
+    dist = got["t"].astype(np.float64) * np.sqrt(d64[:, 0] * d64[:, 0] + d64[:, 1] * d64[:, 1] + d64[:, 2] * d64[:, 2])
+    depth = np.where(got["hit"], dist, np.inf).astype(np.float32).reshape(NY, NX)
+    assert depth.tobytes() == f["depth"].tobytes()
