@@ -752,3 +752,48 @@ extern "C" {
         stream: *mut c_void,
     ) -> c_int;
 }
+
+// ---- include/rtmi_radiance.h: radiance queries -------------------------------------------------------------------------
+
+/// rtmi_radiance_params: one call's batch, estimator and Philox indices (56 bytes); path (i, s) is the render's path of
+/// pixel index first_ray + i, sample first_sample + s under `seed`, its stream 0 read from word stream_skip on
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiRadianceParams {
+    pub n: u32,
+    pub spp: u32,
+    pub estimator: u32,
+    pub flags: u32,
+    pub max_depth: u32,
+    pub t_min: f32,
+    pub seed: u64,
+    pub first_ray: u64,
+    pub first_sample: u32,
+    pub stream_skip: u32,
+    pub env_select_p: f32,
+}
+
+extern "C" {
+    /// blocking, host pointers; time: n floats or NULL (time 0); each output optional, not all NULL; kernel_ms: optional
+    pub fn rtmi_radiance(
+        scene: *mut RtmiScene,
+        params: *const RtmiRadianceParams,
+        rays: *const RtmiRay,
+        time: *const f32,
+        out_mean: *mut f32,
+        out_stderr: *mut f32,
+        out_samples: *mut f32,
+        kernel_ms: *mut f64,
+    ) -> c_int;
+    /// asynchronous, device pointers, enqueued on `stream` (a hipStream_t); d_samples (n * spp * 12 bytes) is required
+    pub fn rtmi_radiance_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiRadianceParams,
+        d_rays: *const c_void,
+        d_time: *const c_void,
+        d_mean: *mut c_void,
+        d_stderr: *mut c_void,
+        d_samples: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+}

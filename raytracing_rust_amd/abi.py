@@ -262,6 +262,17 @@ class QueryParams(C.Structure):
 # the functions of include/rtmi_query.h (ray queries), kept apart from those of the other headers
 RTMI_QUERY_SYMBOLS = ["rtmi_occluded", "rtmi_occluded_device", "rtmi_scene_attach_flips", "rtmi_trace", "rtmi_trace_device"]
 
+
+class RadianceParams(C.Structure):
+    """rtmi_radiance_params (include/rtmi_radiance.h): one call's batch, estimator and Philox indices (56 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("spp", C.c_uint32), ("estimator", C.c_uint32), ("flags", C.c_uint32),
+                ("max_depth", C.c_uint32), ("t_min", C.c_float), ("seed", C.c_uint64), ("first_ray", C.c_uint64),
+                ("first_sample", C.c_uint32), ("stream_skip", C.c_uint32), ("env_select_p", C.c_float)]
+
+
+# the functions of include/rtmi_radiance.h (radiance queries), kept apart from those of the other headers
+RTMI_RADIANCE_SYMBOLS = ["rtmi_radiance", "rtmi_radiance_device"]
+
 _rtmi = None
 _host = None
 
@@ -388,6 +399,10 @@ def load_rtmi():
     for name in ("rtmi_trace_device", "rtmi_occluded_device"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [vp, C.POINTER(QueryParams), vp, vp, vp, vp]
+    lib.rtmi_radiance.restype = C.c_int
+    lib.rtmi_radiance.argtypes = [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
+    lib.rtmi_radiance_device.restype = C.c_int
+    lib.rtmi_radiance_device.argtypes = [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, vp]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -472,6 +487,8 @@ def load_host():
         "rth_occluded": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_trace_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),
         "rth_occluded_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),
+        "rth_radiance": (i, [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
+        "rth_radiance_device": (i, [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, vp]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

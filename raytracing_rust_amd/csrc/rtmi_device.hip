@@ -54,6 +54,8 @@
 #include "rtmi_session_launch.hpp"
 #include "rtmi_query.h"
 #include "rtmi_query_launch.hpp"
+#include "rtmi_radiance.h"
+#include "rtmi_radiance_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -139,6 +141,13 @@ struct rtmi_scene {
     float4 *q_out = nullptr;    // trace: [n][3] hit records; occluded: [n] bytes
     size_t q_out_bytes = 0;
     uint32_t *q_flip_gaps = nullptr; // rtmi_scene_attach_flips: [n_prims] | [n_items], or NULL
+    // radiance queries (include/rtmi_radiance.h), grow-only, freed with the handle: the per-sample buffer and the two
+    // per-ray outputs of a host-form batch (its rays go through q_rays and q_time); the chunk counter of the persistent
+    // wavefronts is the word behind the status words
+    Rad3 *rad_samples = nullptr; // [n][spp]
+    size_t rad_samples_bytes = 0;
+    float *rad_out = nullptr;    // mean [n][3] | stderr [n][3]
+    size_t rad_out_bytes = 0;
     // next-event estimation (include/rtmi_nee.h): the attached light table and per-primitive light index, freed with the
     // handle
     bool has_lights = false;
@@ -551,8 +560,9 @@ extern "C" int rtmi_scene_create(const rtmi_scene_desc *d, int device, rtmi_scen
         if (d->items[i].flags & (RTMI_ITEMFLAG_DEFERRED | RTMI_ITEMFLAG_NESTED_MEDIUM)) s->has_deferred = true;
     for (uint32_t i = 0; i < d->n_items; i++)
         if (d->items[i].flags & (RTMI_ITEMFLAG_SAVE_T0 | RTMI_ITEMFLAG_DEFERRED | RTMI_ITEMFLAG_NESTED_MEDIUM)) s->needs_insd = true;
-    if (hipMalloc(reinterpret_cast<void **>(&s->status), RTMI_STATUS_WORDS * sizeof(unsigned int)) != hipSuccess ||
-        hipMemset(s->status, 0, RTMI_STATUS_WORDS * sizeof(unsigned int)) != hipSuccess) {
+    // one word more than the status words: the chunk counter of the radiance queries (rtmi_radiance.h)
+    if (hipMalloc(reinterpret_cast<void **>(&s->status), (RTMI_STATUS_WORDS + 1) * sizeof(unsigned int)) != hipSuccess ||
+        hipMemset(s->status, 0, (RTMI_STATUS_WORDS + 1) * sizeof(unsigned int)) != hipSuccess) {
         rtmi_scene_destroy(s);
         return fail(RTMI_ERR_DEVICE, "allocating the status word failed");
     }
@@ -591,6 +601,8 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->q_time) (void)hipFree(s->q_time);
     if (s->q_out) (void)hipFree(s->q_out);
     if (s->q_flip_gaps) (void)hipFree(s->q_flip_gaps);
+    if (s->rad_samples) (void)hipFree(s->rad_samples);
+    if (s->rad_out) (void)hipFree(s->rad_out);
     if (s->nee_lights) (void)hipFree(s->nee_lights);
     if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
     if (s->env_texels) (void)hipFree(s->env_texels);
@@ -2436,6 +2448,141 @@ extern "C" int rtmi_trace_device(rtmi_scene *s, const rtmi_query_params *p, cons
 extern "C" int rtmi_occluded_device(rtmi_scene *s, const rtmi_query_params *p, const void *d_rays, const void *d_time,
                                     void *d_occluded, void *stream) {
     return query_device("rtmi_occluded_device", true, s, p, d_rays, d_time, d_occluded, stream);
+}
+
+// ---- radiance queries (include/rtmi_radiance.h) -------------------------------------------------------------------------
+// The checks both forms share, in this order: params, flags, the values, the ray and output pointers of a batch with rays.
+// Nothing here reads the handle, so each is answered for a NULL one too; the handle and what the estimator needs attached
+// follow in the entries (begin_call's rule, the one-shot entries').
+#define RTMI_RADIANCE_FLAGS (RTMI_FLAG_FAST_CULL | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK)
+static int radiance_check(const char *name, const rtmi_radiance_params *p, const void *rays, bool has_out, const char *out_msg) {
+    const std::string nm = std::string(name) + ": ";
+    if (!p) return fail(RTMI_ERR_INVALID, nm + "params is NULL");
+    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+        return fail(RTMI_ERR_UNSUPPORTED, nm + "radiance queries accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
+    if (p->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if (p->spp == 0u) return fail(RTMI_ERR_INVALID, nm + "spp must be at least 1");
+    if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
+    if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
+    if (p->first_ray > (1ull << 32) || p->first_ray + p->n > (1ull << 32))
+        return fail(RTMI_ERR_INVALID, nm + "first_ray + n must not exceed 2^32 (a ray index would wrap onto another ray's stream)");
+    if ((uint64_t)p->first_sample + p->spp > (1ull << 32))
+        return fail(RTMI_ERR_INVALID, nm + "first_sample + spp must not exceed 2^32 (a sample index would wrap onto another sample's stream)");
+    if ((uint64_t)p->n * p->spp >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "n * spp must be below 2^31");
+    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
+    if (p->estimator == RTMI_ROULETTE_ENV_NEE && !(p->env_select_p > 0.0f && p->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
+    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (p->n == 0u) return RTMI_OK;
+    if (!rays) return fail(RTMI_ERR_INVALID, nm + "rays is NULL");
+    if (!has_out) return fail(RTMI_ERR_INVALID, nm + out_msg);
+    return RTMI_OK;
+}
+// begin_call's attach checks for the asynchronous form, which takes the (locked) handle without waiting for its previous call
+static int radiance_attached(const Estimator &m, const rtmi_scene *s) {
+    if (m.env && !s->has_env)
+        return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no environment map attached (rtmi_scene_attach_env)");
+    if (m.nee && !s->has_lights) return fail(RTMI_ERR_INVALID, std::string(m.name) + ": " + m.no_lights);
+    return RTMI_OK;
+}
+static Estimator radiance_estimator(const char *name, const rtmi_radiance_params *p, const std::string &null_scene) {
+    const bool nee = p->estimator == RTMI_ROULETTE_NEE || p->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
+    return Estimator{name, nee, env, nee && env ? p->env_select_p : 1.0f, null_scene.c_str(),
+                     "no light table attached (rtmi_scene_attach_lights)"};
+}
+// The two launches of a call on `stream`: the path kernel on the persistent grid of the per-lane render kernels, fed by the
+// handle's chunk counter (zeroed here, on the call's stream: the handle serialises its calls), then the resolve.
+static int radiance_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_radiance_params *p, hipStream_t stream, const void *d_rays,
+                            const void *d_time, void *d_mean, void *d_stderr, void *d_samples) {
+    rtmi_render_params rp{};
+    rp.nx = 1u; rp.ny = 1u; rp.ns = 1u; rp.tile_world = 1u; // no image: the pass fields of DevParams stay unread
+    rp.max_depth = p->max_depth; rp.t_min = p->t_min; rp.seed = p->seed; rp.flags = p->flags;
+    DevParams P = dev_params(s, &rp);
+    P.samples = reinterpret_cast<Rad3 *>(d_samples);
+    DevLights L;
+    DevEnv E;
+    dev_lighting(s, m.nee, m.env, m.env_select_p, L, E);
+    RadianceBatch B{};
+    B.rays = reinterpret_cast<const float4 *>(d_rays);
+    B.time = reinterpret_cast<const float *>(d_time);
+    B.mean = reinterpret_cast<float *>(d_mean);
+    B.stderr_out = reinterpret_cast<float *>(d_stderr);
+    B.queue = s->status + RTMI_STATUS_WORDS;
+    B.n = p->n; B.spp = p->spp; B.total = p->n * p->spp;
+    B.first_ray = (uint32_t)p->first_ray; B.first_sample = p->first_sample;
+    B.skip_block = p->stream_skip >> 2; B.skip_pos = p->stream_skip & 3u;
+    // chunks of RTMI_RADIANCE_CHUNK items, smaller for a batch that would otherwise leave wavefronts of the grid without one
+    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
+    const uint32_t share = (uint32_t)(((uint64_t)B.total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
+    uint32_t cap = RTMI_RADIANCE_CHUNK;
+    if (const char *e = getenv("RTMI_RADIANCE_CHUNK")) { // tuning knob of tools/radiance_timing.py: a multiple of 64 in [64, 65536]
+        const long v = atol(e);
+        if (v >= 64 && v <= 65536) cap = (uint32_t)v & ~63u;
+    }
+    B.chunk = share < 64u ? 64u : (share > cap ? cap : share);
+    B.nchunks = (B.total + B.chunk - 1u) / B.chunk;
+    const rtmi_query_params q{p->n, p->flags & RTMI_FLAG_FAST_CULL, 0ull, 0ull};
+    HIP_TRY(hipMemsetAsync(B.queue, 0, sizeof(unsigned int), stream));
+    HIP_TRY(rtmi_radiance_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, B.nchunks < slots ? B.nchunks : slots, stream,
+                                 s->dev, P, B, L, E));
+    if (d_mean || d_stderr) HIP_TRY(rtmi_radiance_launch_resolve(stream, P.samples, B));
+    return RTMI_OK;
+}
+extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const rtmi_ray *rays, const float *time, float *out_mean,
+                             float *out_stderr, float *out_samples, double *kernel_ms) {
+    const char *name = "rtmi_radiance";
+    int rc;
+    if ((rc = radiance_check(name, p, rays, out_mean || out_stderr || out_samples, "every output is NULL"))) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n && (rc = query_check_rays(name, rays, time, p->n))) return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = radiance_estimator(name, p, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    if (p->n == 0u) return RTMI_OK;
+    RenderCall c;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    const size_t n = p->n, ns = n * p->spp;
+    if ((rc = grow(s, s->q_rays, s->q_rays_bytes, n * sizeof(rtmi_ray))) ||
+        (time && (rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(float)))) ||
+        (rc = grow(s, s->rad_samples, s->rad_samples_bytes, ns * sizeof(Rad3))) ||
+        (rc = grow(s, s->rad_out, s->rad_out_bytes, n * 6 * sizeof(float))))
+        return rc;
+    float *d_mean = s->rad_out, *d_stderr = s->rad_out + n * 3;
+    HIP_TRY(hipMemcpyAsync(s->q_rays, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
+    if (time) HIP_TRY(hipMemcpyAsync(s->q_time, time, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    if ((rc = radiance_enqueue(s, m, p, stream, s->q_rays, time ? s->q_time : nullptr, out_mean ? d_mean : nullptr,
+                               out_stderr ? d_stderr : nullptr, s->rad_samples)))
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, d_mean, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, d_stderr, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (kernel_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *kernel_ms = (double)ms;
+    }
+    return RTMI_OK;
+}
+extern "C" int rtmi_radiance_device(rtmi_scene *s, const rtmi_radiance_params *p, const void *d_rays, const void *d_time, void *d_mean,
+                                    void *d_stderr, void *d_samples, void *stream_) {
+    const char *name = "rtmi_radiance_device";
+    if (int rc = radiance_check(name, p, d_rays, d_samples != nullptr, "d_samples is NULL (the kernel's per-sample buffer)")) return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = radiance_estimator(name, p, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    if (p->n == 0u) return RTMI_OK;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = radiance_attached(m, s)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    BusyMark busy_mark{s, stream};
+    return radiance_enqueue(s, m, p, stream, d_rays, d_time, d_mean, d_stderr, d_samples);
 }
 
 // ---- next-event estimation (include/rtmi_nee.h) -------------------------------------------------------------------------

@@ -586,6 +586,129 @@ class Scene:
         return {"hit": ids[:, 0] >= 0, "t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "p": out[:, 3:6], "normal": out[:, 6:9],
                 "item": ids[:, 0], "prim": ids[:, 1], "material": ids[:, 2]}
 
+    def radiance(self, origins, directions, times=None, spp=1, estimator="plain", t_min=0.001, t_max=float("inf"), seed=0,
+                 first_ray=0, first_sample=0, stream_skip=0, max_depth=50, env_select_p=0.5, flags=abi.RTMI_FLAG_FAST_CULL,
+                 samples=False, path_t_min=0.001):
+        """Path-traced radiance along a batch of rays (include/rtmi_radiance.h): spp independent paths of render()'s
+        integrator per ray, each starting with the caller's ray instead of a camera ray.  estimator: "plain" (render),
+        "nee" (render_nee), "env" (render_env(nee=False)) or "env_nee" (render_env(nee=True, env_select_p)); the light
+        table is attached on first use, the map is the one of attach_env.  origins, directions: float32 [n, 3]; times: [n]
+        or None (time 0); t_min, t_max: a scalar or [n] each, the interval of the FIRST segment (t_max = inf: the
+        render's); path_t_min: the t_min of every later segment and of shadow rays.  Path (i, s) is the render's path of
+        pixel index first_ray + i, sample first_sample + s under `seed`, its stream read from word stream_skip on: with
+        stream_skip = 3 the rays and times of a pinhole camera give that render's samples bit for bit.
+        Returns dict(mean f32 [n, 3], stderr f32 [n, 3] (+inf for spp = 1), kernel_ms[, samples f32 [n, spp, 3]]).
+        With torch tensors on the scene's device the call is enqueued on torch's current stream (rtmi_radiance_device) and
+        returns torch tensors on that device (samples always among them: the buffer is the kernel's): no host copy is
+        made.  A scene resident on a device list raises Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        self._ready({}, lights=estimator in ("nee", "env_nee"))
+        torch_in = hasattr(origins, "data_ptr") and hasattr(origins, "is_cuda")
+        n = int(origins.shape[0])
+        p = abi.RadianceParams(n, int(spp), abi.ROULETTE_ESTIMATORS[estimator], int(flags), int(max_depth), float(path_t_min),
+                               int(seed) & (2 ** 64 - 1), int(first_ray) & (2 ** 64 - 1), int(first_sample), int(stream_skip),
+                               float(env_select_p))
+        if torch_in:
+            return self._radiance_torch(p, origins, directions, times, t_min, t_max)
+        o, d = (np.ascontiguousarray(a, dtype=np.float32) for a in (origins, directions))
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+            raise ValueError("origins and directions are [n, 3] arrays, not %r and %r" % (o.shape, d.shape))
+        rays = np.empty(n, RAY_DTYPE)
+        rays["o"], rays["d"], rays["t_min"], rays["t_max"] = o, d, t_min, t_max
+        tm = None if times is None else np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.float32), (n,)))
+        ms = C.c_double(0.0)
+        res = {"mean": np.zeros((n, 3), np.float32), "stderr": np.zeros((n, 3), np.float32)}
+        if samples:
+            res["samples"] = np.zeros((n, max(int(spp), 0), 3), np.float32)
+        self.host._check(self.host.lib.rth_radiance(self.h, C.byref(p), rays.ctypes.data, None if tm is None else tm.ctypes.data,
+                                                     res["mean"].ctypes.data, res["stderr"].ctypes.data,
+                                                     res["samples"].ctypes.data if samples else None, C.byref(ms)))
+        res["kernel_ms"] = ms.value
+        return res
+
+    def _radiance_torch(self, p, origins, directions, times, t_min, t_max):
+        import torch
+
+        dev = origins.device
+        if dev.type != "cuda" or (dev.index or 0) != self.device:
+            raise ValueError("the rays are on %s, the scene is on device %d" % (dev, self.device))
+        if origins.dtype != torch.float32 or directions.dtype != torch.float32 or origins.dim() != 2 or \
+                origins.shape[1] != 3 or directions.shape != origins.shape or directions.device != dev:
+            raise ValueError("origins and directions are float32 [n, 3] tensors on one device")
+        n = p.n
+        rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        rays[:, 0:3], rays[:, 4:7] = origins, directions
+        rays[:, 3] = torch.as_tensor(t_min, dtype=torch.float32, device=dev)
+        rays[:, 7] = torch.as_tensor(t_max, dtype=torch.float32, device=dev)
+        tm = None if times is None else torch.as_tensor(times, dtype=torch.float32, device=dev).expand(n).contiguous()
+        res = {"mean": torch.empty((n, 3), dtype=torch.float32, device=dev), "stderr": torch.empty((n, 3), dtype=torch.float32, device=dev),
+               "samples": torch.empty((n, p.spp, 3), dtype=torch.float32, device=dev)}
+        # every check of the entry is made for an empty batch too; it then launches nothing
+        self.host._check(self.host.lib.rth_radiance_device(
+            self.h, C.byref(p), C.c_void_p(rays.data_ptr()), C.c_void_p(tm.data_ptr()) if tm is not None else None,
+            C.c_void_p(res["mean"].data_ptr()), C.c_void_p(res["stderr"].data_ptr()), C.c_void_p(res["samples"].data_ptr()),
+            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return res
+
+    def irradiance(self, points, normals, spp, seed=0, **kw):
+        """Irradiance at surface points (probes, lightmap and vertex baking): E = integral of L cos(theta) over the
+        normal's hemisphere, estimated with spp cosine-distributed directions per point (irradiance_directions, drawn on
+        the host from Philox under `seed`), one radiance() path along each: E = pi * mean.  points, normals: [n, 3];
+        normals need not be unit length.  kw: radiance()'s keywords (estimator, max_depth, t_min, flags, ...); the rays are
+        stream_skip = 0 rays starting at the point, ray k of point i being ray i * spp + k of the batch.
+        Returns dict(irradiance f32 [n, 3], stderr f32 [n, 3]): the standard error of the estimate from the per-ray
+        values (+inf for spp = 1)."""
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if pts.ndim != 2 or pts.shape[1] != 3 or nrm.shape != pts.shape:
+            raise ValueError("points and normals are [n, 3] arrays, not %r and %r" % (pts.shape, nrm.shape))
+        spp = int(spp)
+        if spp < 1:
+            raise ValueError("spp must be at least 1")
+        for k in ("spp", "samples", "stream_skip", "times"):
+            if k in kw:
+                raise ValueError("irradiance() sets %s itself" % k)
+        n = pts.shape[0]
+        dirs = irradiance_directions(nrm, spp, seed)
+        r = self.radiance(np.repeat(pts, spp, axis=0), dirs.reshape(n * spp, 3), spp=1, seed=seed, stream_skip=0, **kw)
+        x = r["mean"].astype(np.float64).reshape(n, spp, 3)
+        mean = x.sum(axis=1) / float(spp)
+        if spp > 1:
+            se = np.sqrt(((x - mean[:, None, :]) ** 2).sum(axis=1) / (float(spp) * (float(spp) - 1.0)))
+        else:
+            se = np.full((n, 3), np.inf)
+        return {"irradiance": (np.pi * mean).astype(np.float32), "stderr": (np.pi * se).astype(np.float32)}
+
+
+IRRADIANCE_STREAM = 5  # the Philox stream id of irradiance()'s directions (0 path, 2 scene, 3 light samples, 4 roulette)
+
+
+def irradiance_directions(normals, spp, seed=0):
+    """Scene.irradiance's directions: float32 [n, spp, 3], unit length, cosine-distributed about each normal.  Direction
+    k of point i takes words 0 and 1 of the Philox block with counter (0, k, i, IRRADIANCE_STREAM) under the key `seed`
+    as 24-bit uniforms u1, u2 (philox.py): r = sqrt(u1), phi = 2 pi u2, (r cos phi, r sin phi, sqrt(1 - u1)) in an
+    orthonormal frame around the normal.  Host code: needs no GPU."""
+    from . import philox
+
+    nrm = np.asarray(normals, dtype=np.float64)
+    n = nrm.shape[0]
+    nrm = nrm / np.linalg.norm(nrm, axis=1, keepdims=True)
+    # the frame: the world axis least aligned with the normal, made orthogonal to it
+    axis = np.eye(3)[np.argmin(np.abs(nrm), axis=1)]
+    t = np.cross(axis, nrm)
+    t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(nrm, t)
+    kk, ii = np.meshgrid(np.arange(spp, dtype=np.uint32), np.arange(n, dtype=np.uint32))
+    w = philox.philox4x32_10_np(np.zeros_like(kk), kk, ii, np.full_like(kk, IRRADIANCE_STREAM), seed)
+    u1 = (w[0] >> np.uint32(8)).astype(np.float64) * (1.0 / 16777216.0)
+    u2 = (w[1] >> np.uint32(8)).astype(np.float64) * (1.0 / 16777216.0)
+    r, phi = np.sqrt(u1), 2.0 * np.pi * u2
+    x, y, z = r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - u1)
+    d = x[..., None] * t[:, None, :] + y[..., None] * b[:, None, :] + z[..., None] * nrm[:, None, :]
+    d /= np.linalg.norm(d, axis=2, keepdims=True)
+    return np.ascontiguousarray(d.astype(np.float32))
+
 
 # rtmi_ray and rtmi_hit (include/rtmi_query.h) as numpy sees them
 RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("t_min", "<f4"), ("d", "<f4", (3,)), ("t_max", "<f4")])

@@ -14,6 +14,7 @@
 #include "rtmi_roulette.h"
 #include "rtmi_session.h"
 #include "rtmi_query.h"
+#include "rtmi_radiance.h"
 
 using namespace rt;
 
@@ -321,6 +322,24 @@ RTH_API int rth_occluded_device(void *lowered, const rtmi_query_params *p, const
     return guard([&] {
         const char *name = "rtmi_occluded_device";
         return done(name, rtmi_occluded_device(DEV(lowered, name, "ray-query"), p, d_rays, d_time, d_occluded, stream),
+                    CODED_UNSUPPORTED);
+    });
+}
+// radiance queries (include/rtmi_radiance.h) on the uploaded handle, as the ray queries: host pointers and blocking, or
+// device pointers enqueued on `stream`; RTH_UNSUPPORTED for unknown flags and for a multi-GPU handle
+RTH_API int rth_radiance(void *lowered, const rtmi_radiance_params *p, const rtmi_ray *rays, const float *time, float *out_mean,
+                         float *out_stderr, float *out_samples, double *kernel_ms) {
+    return guard([&] {
+        const char *name = "rtmi_radiance";
+        return done(name, rtmi_radiance(DEV(lowered, name, "radiance-query"), p, rays, time, out_mean, out_stderr, out_samples, kernel_ms),
+                    CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_radiance_device(void *lowered, const rtmi_radiance_params *p, const void *d_rays, const void *d_time, void *d_mean,
+                                void *d_stderr, void *d_samples, void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_radiance_device";
+        return done(name, rtmi_radiance_device(DEV(lowered, name, "radiance-query"), p, d_rays, d_time, d_mean, d_stderr, d_samples, stream),
                     CODED_UNSUPPORTED);
     });
 }

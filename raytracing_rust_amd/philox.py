@@ -40,6 +40,23 @@ def philox4x32_10(ctr, key):
     return [c0, c1, c2, c3]
 
 
+def philox4x32_10_np(c0, c1, c2, c3, seed):
+    """philox4x32_10 over numpy arrays of counters (uint32, one shape) under the key of `seed`: the four output words as
+    uint32 arrays of that shape."""
+    import numpy as np
+
+    c0, c1, c2, c3 = (np.asarray(c, dtype=np.uint64) & np.uint64(0xFFFFFFFF) for c in (c0, c1, c2, c3))
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    lo32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c0
+        p1 = np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & lo32, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & lo32
+        k0 = (k0 + 0x9E3779B9) & 0xFFFFFFFF
+        k1 = (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return tuple(c.astype(np.uint32) for c in (c0, c1, c2, c3))
+
+
 class Stream:
     """Sequential draws from one Philox stream."""
 
