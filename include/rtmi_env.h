@@ -36,16 +36,19 @@
  *
  * Estimator (rtmi_render_env).  Paths are rtmi_render's (Philox stream 0), so out_path_sig is rtmi_render's bit for bit.
  * A ray that leaves the world adds L = L + T * (env(d) * w): w = 1 for camera rays, rays after Metal or Dielectric and
- * with nee = 0; after a Lambertian or Isotropic scatter that took a light sample w = nee_mis_bsdf(p_b, pdf) (include/
- * rtmi_nee.h), 1 when pdf = 0.  nee = 1 is rtmi_render_nee (include/rtmi_nee.h) with one more light: every scattering
+ * with nee = 0; after a Lambertian or Isotropic scatter whose vertex read its three stream-3 words (below), with
+ * p_b > 0, w = nee_mis_bsdf(p_b, pdf) (include/rtmi_nee.h), 1 when pdf = 0.  The weight does not ask what became of
+ * that vertex's light sample: whether it aimed at the map or at an area light, had no sample, or traced no shadow ray,
+ * sampling the map was a strategy available at the vertex.  nee = 1 is rtmi_render_nee (include/rtmi_nee.h) with one more light: every scattering
  * Lambertian or Isotropic vertex reads the three stream-3 words of rtmi_nee.h when the map or the light table can be
  * sampled; us = u01(w0) picks the map when us < p_env, else the area light of the table's CDF search with
  * (us - p_env) / (1 - p_env); u01(w1), u01(w2) pick the direction or the point.  p_env = env_select_p when the handle's
  * light table is not empty, 1 when it is, 0 when the map cannot be sampled; an area light's p_l (light sample and BSDF
  * hit alike) is (1 - p_env) * p_l.  The shadow ray toward the map is rtmi_render_nee's (origin x, the sampled direction,
  * the path's time, (t_min, +inf), the item scan with media, free-flight draws from stream 3); V = 1 iff it hits nothing;
- * the sample adds L = L + ((T * albedo) * mis) * env(d), mis = nee_mis_light(p_b, pdf).  With p_env = 0 the result is
- * rtmi_render_nee's bit for bit.
+ * the sample adds L = L + ((T * albedo) * mis) * env(d), mis = nee_mis_light(p_b, pdf); env(d) is looked up from the
+ * sampled direction d, through "Direction -> (u, v)" again, not from the (u, v) the sample was made of.  With p_env = 0
+ * the result is rtmi_render_nee's bit for bit.
  */
 #ifndef RTMI_ENV_H
 #define RTMI_ENV_H

@@ -27,7 +27,13 @@ COUNTER_NAMES = [
     "mat_fetch", "tex_solid", "tex_checker", "tex_noise", "tex_image", "sc_lambert", "sc_metal",
     "sc_dielectric", "sc_isotropic", "emit", "draws", "sphere_trials", "disk_trials", "sphere_accept",
     "rect_accept",
+    # the environment estimator and roulette (appended: the indices above keep their meaning)
+    "env_sample", "env_no_sample", "env_occluded", "env_unoccluded", "env_miss_mis", "env_miss_one", "env_area_sample",
+    "env_emit_scaled", "rr_test", "rr_draw", "rr_end_pending", "rr_end_bare", "rr_floor_survive", "rr_zero",
 ]
+ENV_COUNTERS = COUNTER_NAMES[24:32]
+ROULETTE_COUNTERS = COUNTER_NAMES[32:38]
+ROULETTE_ESTIMATORS = {"plain": 0, "nee": 1, "env": 2, "env_nee": 3}  # RTMI_ROULETTE_*
 
 PLANE_YZ, PLANE_ZX, PLANE_XY = 0, 1, 2
 
@@ -40,6 +46,26 @@ EMITTER_DTYPE = np.dtype([("handle", "<u8"), ("kind", "<i4"), ("plane", "<i4"), 
 LIGHT_DTYPE = np.dtype([("handle", "<u8"), ("kind", "<i4"), ("plane", "<i4"), ("geo", "<f8", (5,)), ("area", "<f8"),
                         ("p_sel", "<f8"), ("cdf", "<f8")])  # OrcLight, 80 B
 AXIS_X, AXIS_Y, AXIS_Z = 0, 1, 2
+
+
+class OrcEnv(C.Structure):
+    """The map and its sampling tables as orc_render_env takes them (OrcEnv, 56 B)."""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("rgb", C.c_void_p), ("row_cdf", C.c_void_p), ("row_p", C.c_void_p),
+                ("col_cdf", C.c_void_p), ("col_p", C.c_void_p), ("total", C.c_double)]
+
+
+def _env(env_rgb, tables):
+    """(OrcEnv, the arrays it points into) of a float32 [H, W, 3] map and its tables: a dict with row_cdf [H], row_p [H],
+    col_cdf [H, W], col_p [H, W] (float32) and total (float), as include/rtmi_env.h's rtmi_env_tables writes them."""
+    rgb = np.ascontiguousarray(env_rgb, dtype=np.float32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    h, w = rgb.shape[:2]
+    keep = [rgb]
+    for k, shape in (("row_cdf", (h,)), ("row_p", (h,)), ("col_cdf", (h, w)), ("col_p", (h, w))):
+        a = np.ascontiguousarray(tables[k], dtype=np.float32)
+        assert a.shape == shape, (k, a.shape)
+        keep.append(a)
+    return OrcEnv(w, h, *[a.ctypes.data for a in keep], float(tables["total"])), keep
 
 
 def build():
@@ -101,6 +127,10 @@ def _load(name):
         "orc_render": (i, [vp, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp]),
         "orc_render_samples": (i, [vp, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
         "orc_render_nee": (i, [vp, vp, vp, i, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
+        "orc_render_env": (i, [vp, vp, vp, i, vp, i, d, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
+        "orc_render_roulette": (i, [vp, vp, vp, i, vp, i, i, d, d, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp, vp]),
+        "orc_env_lookup": (i, [vp, d, i, vp, vp, C.c_long]),
+        "orc_env_sample": (i, [vp, d, i, vp, vp, C.c_long]),
         "orc_emitters": (i, [vp, vp, i]),
         "orc_ppm_text": (C.c_size_t, [i, i, vp, vp, C.c_size_t]),
         "orc_hit": (i, [vp, vp, vp, d, d, d, i, u64, vp, vp]),
@@ -298,6 +328,57 @@ class Oracle:
                                      flags, max_depth, t_min, r0, r1, *ptrs)
         if rc != 0:
             raise RuntimeError("orc_render_nee failed")
+        return out
+
+    def render_env(self, cam, world, lights, env_rgb, tables, nee, env_select_p, nx, ny, ns, seed=42, flags=0, max_depth=50,
+                   t_min=0.001, rows=None, samples=False):
+        """rtmi_render_env's estimator (include/rtmi_env.h): render_nee's arguments plus the map env_rgb (float32
+        [H, W, 3]), its sampling tables (see _env), nee (False / True) and env_select_p.  p_env follows the header: env_select_p
+        with a light table that is not empty, 1 with an empty one, 0 when tables["total"] is 0.  Returns render_nee's dict."""
+        r0, r1 = (0, ny) if rows is None else rows
+        lt = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
+        e, _keep = _env(env_rgb, tables)
+        out, ptrs = self._outputs(nx, ny, ns, samples)
+        rc = self.lib.orc_render_env(cam.h, world.h, lt.ctypes.data if len(lt) else None, len(lt), C.byref(e), 1 if nee else 0,
+                                     float(env_select_p), nx, ny, ns, int(seed), flags, max_depth, t_min, r0, r1, *ptrs)
+        if rc != 0:
+            raise RuntimeError("orc_render_env failed")
+        return out
+
+    def render_roulette(self, cam, world, lights, env_rgb, tables, estimator, min_depth, q_min, env_select_p, nx, ny, ns,
+                        seed=42, flags=0, max_depth=50, t_min=0.001, rows=None, samples=False):
+        """rtmi_render_roulette's estimator (include/rtmi_roulette.h): estimator "plain", "nee", "env" or "env_nee" with
+        the test from depth min_depth on and the floor q_min.  lights is read by "nee" and "env_nee", env_rgb and tables
+        (None otherwise) by "env" and "env_nee".  Returns render_nee's dict plus bounces u32 [ny, nx]: the sum over the
+        pixel's samples of the depth at which the path was written.  The throughput form is implied."""
+        r0, r1 = (0, ny) if rows is None else rows
+        est = ROULETTE_ESTIMATORS[estimator]
+        lt = np.ascontiguousarray(lights if lights is not None else [], dtype=LIGHT_DTYPE)
+        e, _keep = _env(env_rgb, tables) if est >= 2 else (None, None)
+        out, ptrs = self._outputs(nx, ny, ns, samples)
+        out["bounces"] = np.zeros((ny, nx), np.uint32)
+        rc = self.lib.orc_render_roulette(cam.h, world.h, lt.ctypes.data if len(lt) else None, len(lt),
+                                          C.byref(e) if e is not None else None, est, int(min_depth), float(q_min),
+                                          float(env_select_p), nx, ny, ns, int(seed), flags, max_depth, t_min, r0, r1, *ptrs,
+                                          out["bounces"].ctypes.data)
+        if rc != 0:
+            raise RuntimeError("orc_render_roulette failed")
+        return out
+
+    def env_lookup(self, env_rgb, tables, dirs, p_env=1.0, flags=ARITH_DEVICE):
+        """The oracle's env(d) and BSDF-side pdf of float32 directions [n, 3] -> float32 [n, 4] = r, g, b, pdf."""
+        e, _keep = _env(env_rgb, tables)
+        d = np.ascontiguousarray(dirs, dtype=np.float32)
+        out = np.zeros((len(d), 4), np.float32)
+        assert self.lib.orc_env_lookup(C.byref(e), float(p_env), flags, d.ctypes.data, out.ctypes.data, len(d)) == 0
+        return out
+
+    def env_sample(self, env_rgb, tables, u12, p_env=1.0, flags=ARITH_DEVICE):
+        """The oracle's light sample of float32 uniforms [n, 2] -> float32 [n, 4] = direction, pdf (zeros: no sample)."""
+        e, _keep = _env(env_rgb, tables)
+        u = np.ascontiguousarray(u12, dtype=np.float32)
+        out = np.zeros((len(u), 4), np.float32)
+        assert self.lib.orc_env_sample(C.byref(e), float(p_env), flags, u.ctypes.data, out.ctypes.data, len(u)) == 0
         return out
 
     def ppm_text(self, rgb):

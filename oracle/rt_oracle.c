@@ -83,7 +83,24 @@ enum {
     C_SAMPLES, C_QUERIES, C_AABB, C_SPHERE, C_MSPHERE, C_RECT, C_XFORM, C_MEDIUM, C_MEDIUM_DRAW,
     C_MAT_FETCH, C_TEX_SOLID, C_TEX_CHECKER, C_TEX_NOISE, C_TEX_IMAGE, C_SC_LAMBERT, C_SC_METAL,
     C_SC_DIELECTRIC, C_SC_ISOTROPIC, C_EMIT, C_DRAWS, C_SPHERE_TRIALS, C_DISK_TRIALS, C_SPHERE_ACCEPT,
-    C_RECT_ACCEPT, C_NCOUNTERS
+    C_RECT_ACCEPT,
+    /* environment estimator (include/rtmi_env.h) and roulette (include/rtmi_roulette.h): which branches a render reached.
+     * Appended only: the indices above keep their meaning. */
+    C_ENV_SAMPLE,        /* light samples aimed at the map (us < p_env)                                      */
+    C_ENV_NO_SAMPLE,     /* ... that had no sample: ct <= 0, or pdf outside (0, FLT_MAX)                     */
+    C_ENV_OCCLUDED,      /* shadow rays toward the map that hit something                                    */
+    C_ENV_UNOCCLUDED,    /* shadow rays toward the map that left the world                                   */
+    C_ENV_MISS_MIS,      /* misses weighted by nee_mis_bsdf                                                  */
+    C_ENV_MISS_ONE,      /* misses with weight 1 after a Lambertian / Isotropic vertex, under nee = 1        */
+    C_ENV_AREA_SAMPLE,   /* area-light samples taken with p_env > 0                                          */
+    C_ENV_EMIT_SCALED,   /* emitter hits whose weight used the (1 - p_env) scaling, p_env > 0                */
+    C_RR_TEST,           /* roulette tests made (a scatter reached min_depth)                                */
+    C_RR_DRAW,           /* roulette draws made (q < 1)                                                      */
+    C_RR_END_PENDING,    /* draws that ended the continuation of a vertex with a pending shadow ray          */
+    C_RR_END_BARE,       /* ... of a vertex without one                                                      */
+    C_RR_FLOOR_SURVIVE,  /* survivals with q == q_min: the floor binds                                       */
+    C_RR_ZERO,           /* continuations ended by m == 0                                                    */
+    C_NCOUNTERS
 };
 static uint64_t g_cnt[C_NCOUNTERS];
 #ifdef ORC_NO_COUNT /* the timed CPU-baseline build: no instrumentation on the hot path */
@@ -815,7 +832,42 @@ static int bounding_box(const Hittable *h, double t0, double t1, AABBd *out) {
 /* ================================================================================== */
 /* color — src/color.rs:6-23                                                           */
 /* ================================================================================== */
-typedef struct { const Hittable *world; int max_depth; REAL t_min; } RenderCtx;
+typedef struct {
+    const Hittable *world;
+    int max_depth;
+    REAL t_min;
+    int rr_min_depth; /* Russian roulette (include/rtmi_roulette.h): the first depth tested; 0 = off */
+    REAL rr_q_min;
+} RenderCtx;
+
+/* the depth at which the last colour loop wrote its path: the scatters it made (rtmi_roulette.h "Bounce count") */
+static int g_bounces;
+
+/* The test of include/rtmi_roulette.h, made after a scatter has set T = T * att and raised the depth to d; `pending`:
+ * the vertex holds a light sample whose shadow ray is not traced yet (counted only).  The draw is stateless: word 0 of
+ * philox(counter = (d, sample, pixel, 4), key = seed), sample and pixel being the words of the path's stream 0 (g_rng).
+ * Returns 1 when the continuation ends; a survivor's T is divided by q. */
+static int roulette_ends(const RenderCtx *cx, V3 *T, int d, int pending) {
+    if (cx->rr_min_depth <= 0 || d < cx->rr_min_depth) return 0;
+    COUNT(C_RR_TEST);
+    const REAL m = R_FMAX(R_FMAX(T->x, T->y), T->z);
+    if (m == (REAL)0) { COUNT(C_RR_ZERO); return 1; }
+    const REAL q = R_FMIN(R_FMAX(m, cx->rr_q_min), (REAL)1);
+    if (q < (REAL)1) {
+        COUNT(C_RR_DRAW);
+        const uint32_t ctr[4] = {(uint32_t)d, g_rng.ctr[1], g_rng.ctr[2], 4u};
+        uint32_t out[4];
+        philox4x32_10(ctr, g_rng.key, out);
+        const REAL u = (REAL)rtmi_u01(out[0]);
+        if (!(u < q)) {
+            if (pending) COUNT(C_RR_END_PENDING); else COUNT(C_RR_END_BARE);
+            return 1;
+        }
+        if (q == cx->rr_q_min) COUNT(C_RR_FLOOR_SURVIVE);
+        *T = v_div(*T, q);
+    }
+    return 0;
+}
 
 /* Path signature (validation aid, see include/rtmi.h): every hit query that finds a hit adds
  * mix(bits of (float)t, bounce index) to the pixel's wrapping uint64 signature. */
@@ -859,7 +911,8 @@ static V3 color(const RenderCtx *cx, const Ray *ray, int depth) {
  * recursion in exact arithmetic; differs by rounding order only. */
 static V3 color_throughput(const RenderCtx *cx, Ray ray) {
     V3 L = v3(0, 0, 0), T = v3(1, 1, 1);
-    for (int depth = 0;; depth++) {
+    int depth;
+    for (depth = 0;; depth++) {
         HitRecord rec;
         COUNT(C_QUERIES);
         if (!hit(cx->world, &ray, cx->t_min, R_MAX, &rec)) {
@@ -874,8 +927,10 @@ static V3 color_throughput(const RenderCtx *cx, Ray ray) {
         V3 att;
         if (!mat_scatter(rec.mat, &ray, &rec, &scattered, &att)) break;
         T = v_mul(T, att);
+        if (roulette_ends(cx, &T, depth + 1, 0)) { depth++; break; }
         ray = scattered;
     }
+    g_bounces = depth;
     return L;
 }
 
@@ -971,13 +1026,27 @@ static int nee_sample(const NeeL *L, V3 x, REAL u1, REAL u2, V3 *dir, REAL *pl) 
 /* the light-sample stream of the current pixel sample: counter (block, sample, pixel, 3) */
 static Stream g_light_rng;
 
+/* The shadow ray of a light sample from x toward `dir` at the path's time: the path's item scan, its media drawing their
+ * free flights from the light-sample stream.  Returns whether it hit anything (*srec). */
+static int shadow_hit(const RenderCtx *cx, V3 x, V3 dir, REAL time, HitRecord *srec) {
+    Ray sray = ray_new(x, dir, time);
+    Stream keep = g_rng;
+    g_rng = g_light_rng;
+    int got = hit(cx->world, &sray, cx->t_min, R_MAX, srec);
+    g_light_rng = g_rng;
+    g_rng = keep;
+    return got;
+}
+
 /* color_throughput with one light sample per scattering Lambertian / Isotropic vertex, combined with the BSDF sample by
- * the power heuristic — operation for operation shade_hit<.., NEE = true> (rtmi_shade.hpp) and the NEE kernel
- * (rtmi_kernel_perlane.inc).  With n == 0 it is color_throughput. */
+ * the power heuristic (include/rtmi_nee.h).  With n == 0 it is color_throughput.  The vertex's light sample is fixed
+ * (c, dir) before T takes the attenuation and before the roulette test; its shadow ray is traced after the test, also
+ * when the test ends the continuation (include/rtmi_roulette.h). */
 static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
     V3 L = v3(0, 0, 0), T = v3(1, 1, 1);
     REAL pb = 0; /* density of the scatter that produced `ray`; 0 = weight 1 at an emitter hit */
-    for (int depth = 0;; depth++) {
+    int depth;
+    for (depth = 0;; depth++) {
         HitRecord rec;
         COUNT(C_QUERIES);
         if (!hit(cx->world, &ray, cx->t_min, R_MAX, &rec)) {
@@ -1001,6 +1070,8 @@ static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
         const int kind = rec.mat->kind;
         if (!mat_scatter(rec.mat, &ray, &rec, &scattered, &att)) break;
         pb = 0;
+        int pending = 0, lo = 0;
+        V3 c = v3(0, 0, 0), dir = v3(0, 0, 0);
         if (n > 0 && (kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC)) {
             const int iso = kind == MAT_ISOTROPIC;
             V3 hn = rec.normal; /* the normal the scatter saw (mat_scatter's FACE_FORWARD rule) */
@@ -1008,33 +1079,230 @@ static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
             pb = iso ? NEE_INV_4PI : nee_pb_lambert(scattered.d, hn);
             uint32_t w0 = stream_u32(&g_light_rng), w1 = stream_u32(&g_light_rng), w2 = stream_u32(&g_light_rng);
             REAL us = (REAL)rtmi_u01(w0);
-            int lo = 0, hi = n - 1; /* the first light whose cdf exceeds us */
+            int hi = n - 1; /* the first light whose cdf exceeds us */
             while (lo < hi) {
                 int mid = (lo + hi) >> 1;
                 if (us < lights[mid].cdf) hi = mid; else lo = mid + 1;
             }
-            V3 dir;
             REAL pl;
             if (nee_sample(&lights[lo], rec.p, (REAL)rtmi_u01(w1), (REAL)rtmi_u01(w2), &dir, &pl)) {
                 REAL pbl = iso ? NEE_INV_4PI : nee_pb_lambert(dir, hn);
                 if (pbl > (REAL)0 && pl > (REAL)0 && pl < R_MAX) {
-                    V3 c = v_scale(v_mul(T, att), nee_mis_light(pbl, pl));
-                    /* the shadow ray: the path's item scan, its media drawing from the light-sample stream */
-                    Ray sray = ray_new(rec.p, dir, ray.time);
-                    Stream keep = g_rng;
-                    g_rng = g_light_rng;
-                    HitRecord srec;
-                    int got = hit(cx->world, &sray, cx->t_min, R_MAX, &srec);
-                    g_light_rng = g_rng;
-                    g_rng = keep;
-                    if (got && srec.prim == lights[lo].h && srec.mat->kind == MAT_DIFFUSE_LIGHT)
-                        L = v_add(L, v_mul(c, mat_emitted(srec.mat, srec.u, srec.v, srec.p)));
+                    c = v_scale(v_mul(T, att), nee_mis_light(pbl, pl));
+                    pending = 1;
                 }
             }
         }
         T = v_mul(T, att);
+        const int ends = roulette_ends(cx, &T, depth + 1, pending);
+        if (pending) {
+            HitRecord srec;
+            if (shadow_hit(cx, rec.p, dir, ray.time, &srec) && srec.prim == lights[lo].h && srec.mat->kind == MAT_DIFFUSE_LIGHT)
+                L = v_add(L, v_mul(c, mat_emitted(srec.mat, srec.u, srec.v, srec.p)));
+        }
+        if (ends) { depth++; break; }
         ray = scattered;
     }
+    g_bounces = depth;
+    return L;
+}
+
+/* ================================================================================== */
+/* environment lighting — include/rtmi_env.h (not in the reference)                    */
+/* ================================================================================== */
+/* The map and its sampling tables (rtmi_env_tables' outputs, passed in like the light table), and the render's p_env. */
+typedef struct {
+    int w, h;
+    const float *rgb;                               /* [h][w][3], row 0 the top row */
+    const float *row_cdf, *row_p, *col_cdf, *col_p; /* [h], [h], [h][w], [h][w] */
+    REAL p_env;
+} EnvMap;
+
+#ifdef ORC_F32
+#define ENV_PI RTMI_PI_F
+#define ENV_PIO2 RTMI_PIO2_F
+#define ENV_2PI2 19.739208802178716f     /* RTMI_ENV_2PI2_F */
+#define ENV_ONE_MINUS 0.99999994039535522f /* RTMI_ENV_ONE_MINUS */
+#else
+#define ENV_PI 3.14159265358979323846264338327950288
+#define ENV_PIO2 1.57079632679489661923132169163975144
+#define ENV_2PI2 19.7392088021787172376689819991737235
+#define ENV_ONE_MINUS 0.99999994039535522
+#endif
+
+/* "Direction -> (u, v)": 0 for a direction that sees nothing */
+static int env_uv(V3 d, REAL *u, REAL *v, REAL *theta) {
+    const REAL ax = R_FABS(d.x), ay = R_FABS(d.y), az = R_FABS(d.z);
+    if (!(ax <= R_MAX && ay <= R_MAX && az <= R_MAX)) return 0; /* a component that is not finite */
+    const REAL m = R_FMAX(R_FMAX(ax, ay), az);
+    if (!(m > (REAL)0)) return 0;
+    const V3 s = v_div(d, m);
+    const REAL l = R_SQRT((s.x * s.x + s.y * s.y) + s.z * s.z);
+    const V3 n = v_div(s, l);
+    const REAL phi = m_atan2(n.z, n.x);
+    *theta = m_asin(R_FMIN(R_FMAX(n.y, (REAL)-1), (REAL)1));
+    *u = (REAL)1 - (phi + ENV_PI) / ((REAL)2 * ENV_PI);
+    *v = (*theta + ENV_PIO2) / ENV_PI;
+    return 1;
+}
+static V3 env_texel(const EnvMap *E, int j, int i) {
+    const float *t = E->rgb + ((size_t)j * (size_t)E->w + (size_t)i) * 3;
+    return v3((REAL)t[0], (REAL)t[1], (REAL)t[2]);
+}
+static V3 env_lerp(V3 a, V3 b, REAL f) { /* a + f * (b - a) per channel */
+    return v3(a.x + f * (b.x - a.x), a.y + f * (b.y - a.y), a.z + f * (b.z - a.z));
+}
+static int env_clampi(long v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
+/* "Radiance env(d)" at d's (u, v): bilinear, columns wrapped, rows clamped */
+static V3 env_radiance(const EnvMap *E, REAL u, REAL v) {
+    const REAL x = u * (REAL)E->w - (REAL)0.5, y = ((REAL)1 - v) * (REAL)E->h - (REAL)0.5;
+    const REAL x0 = R_FLOOR(x), y0 = R_FLOOR(y);
+    const REAL fx = x - x0, fy = y - y0;
+    const long xi = (long)x0, yi = (long)y0;
+    const int i0 = (int)(((xi % E->w) + E->w) % E->w), i1 = (i0 + 1) % E->w;
+    const int j0 = env_clampi(yi, 0, E->h - 1), j1 = env_clampi(yi + 1, 0, E->h - 1);
+    const V3 t0 = env_lerp(env_texel(E, j0, i0), env_texel(E, j0, i1), fx);
+    const V3 t1 = env_lerp(env_texel(E, j1, i0), env_texel(E, j1, i1), fx);
+    return env_lerp(t0, t1, fy);
+}
+/* the light sample's density in texel (i, j) at cos(theta) = ct */
+static REAL env_pdf_texel(const EnvMap *E, int i, int j, REAL ct) {
+    const size_t k = (size_t)j * (size_t)E->w + (size_t)i;
+    return (((E->p_env * (REAL)E->row_p[j]) * (REAL)E->col_p[k]) * (REAL)(E->w * E->h)) / (ENV_2PI2 * ct);
+}
+/* the BSDF-side pdf of the direction with (u, v, theta) */
+static REAL env_pdf(const EnvMap *E, REAL u, REAL v, REAL theta) {
+    if (!(E->p_env > (REAL)0)) return 0;
+    const REAL ct = m_cos(theta);
+    if (!(ct > (REAL)0)) return 0;
+    const int i = env_clampi((long)R_FLOOR(u * (REAL)E->w), 0, E->w - 1);
+    const int j = env_clampi((long)R_FLOOR(((REAL)1 - v) * (REAL)E->h), 0, E->h - 1);
+    return env_pdf_texel(E, i, j, ct);
+}
+/* the first index with us < cdf[index] */
+static int env_search(const float *cdf, int n, REAL us) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (us < (REAL)cdf[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+/* "Light sample from two uniforms": a unit direction and its pdf; 0 = no sample */
+static int env_sample(const EnvMap *E, REAL u1, REAL u2, V3 *dir, REAL *pdf) {
+    const int j = env_search(E->row_cdf, E->h, u1);
+    const float *cc = E->col_cdf + (size_t)j * (size_t)E->w;
+    const int i = env_search(cc, E->w, u2);
+    const REAL r0 = j > 0 ? (REAL)E->row_cdf[j - 1] : (REAL)0, c0 = i > 0 ? (REAL)cc[i - 1] : (REAL)0;
+    const REAL fy = R_FMIN((u1 - r0) / ((REAL)E->row_cdf[j] - r0), ENV_ONE_MINUS);
+    const REAL fx = R_FMIN((u2 - c0) / ((REAL)cc[i] - c0), ENV_ONE_MINUS);
+    const REAL u = ((REAL)i + fx) / (REAL)E->w, v = (REAL)1 - ((REAL)j + fy) / (REAL)E->h;
+    const REAL phi = ((REAL)1 - u) * ((REAL)2 * ENV_PI) - ENV_PI;
+    const REAL theta = v * ENV_PI - ENV_PIO2;
+    const REAL ct = m_cos(theta);
+    if (!(ct > (REAL)0)) return 0;
+    *dir = v3(ct * m_cos(phi), m_sin(theta), ct * m_sin(phi));
+    *pdf = env_pdf_texel(E, i, j, ct);
+    return *pdf > (REAL)0 && *pdf < R_MAX;
+}
+
+/* rtmi_render_env's estimator ("Estimator" in include/rtmi_env.h): color_nee with the map where a ray leaves the world
+ * and, with nee != 0, the map as one more light.  nee == 0 is color_throughput plus the map at weight 1. */
+static V3 color_env(const RenderCtx *cx, Ray ray, const NeeL *lights, int n, const EnvMap *E, int nee) {
+    V3 L = v3(0, 0, 0), T = v3(1, 1, 1);
+    const REAL p_env = E->p_env, p_area = (REAL)1 - E->p_env;
+    REAL pb = 0;     /* density of the scatter that produced `ray`, set where the vertex read its stream-3 words */
+    int diffuse = 0; /* `ray` left a Lambertian or Isotropic vertex (counters only) */
+    int depth;
+    for (depth = 0;; depth++) {
+        HitRecord rec;
+        COUNT(C_QUERIES);
+        if (!hit(cx->world, &ray, cx->t_min, R_MAX, &rec)) { /* the map, with its weight */
+            REAL u, v, theta;
+            if (env_uv(ray.d, &u, &v, &theta)) {
+                REAL w = 1;
+                int weighted = 0;
+                if (nee && pb > (REAL)0) {
+                    const REAL pe = env_pdf(E, u, v, theta);
+                    if (pe > (REAL)0) { w = nee_mis_bsdf(pb, pe); weighted = 1; }
+                }
+                if (weighted) COUNT(C_ENV_MISS_MIS); else if (nee && diffuse) COUNT(C_ENV_MISS_ONE);
+                L = v_add(L, v_mul(T, v_scale(env_radiance(E, u, v), w)));
+            }
+            break;
+        }
+        sig_add(rec.t, depth);
+        V3 emitted = mat_emitted(rec.mat, rec.u, rec.v, rec.p);
+        if (nee && rec.mat->kind == MAT_DIFFUSE_LIGHT && rec.prim && pb > (REAL)0) {
+            for (int li = 0; li < n; li++) {
+                if (lights[li].h != rec.prim) continue;
+                REAL pl = p_area * nee_pdf(&lights[li], ray.o, rec.p);
+                if (pl > (REAL)0) {
+                    emitted = v_scale(emitted, nee_mis_bsdf(pb, pl));
+                    if (p_env > (REAL)0) COUNT(C_ENV_EMIT_SCALED);
+                }
+                break;
+            }
+        }
+        L = v_add(L, v_mul(T, emitted));
+        if (depth >= cx->max_depth) break;
+        Ray scattered;
+        V3 att;
+        const int kind = rec.mat->kind;
+        if (!mat_scatter(rec.mat, &ray, &rec, &scattered, &att)) break;
+        pb = 0;
+        diffuse = kind == MAT_LAMBERTIAN || kind == MAT_ISOTROPIC;
+        int pending = 0, to_env = 0, lo = 0;
+        V3 c = v3(0, 0, 0), dir = v3(0, 0, 0);
+        if (nee && diffuse && (n > 0 || p_env > (REAL)0)) { /* the map or the table can be sampled */
+            const int iso = kind == MAT_ISOTROPIC;
+            V3 hn = rec.normal;
+            if ((g_flags & ORC_FACE_FORWARD) && v_dot(ray.d, hn) > (REAL)0) hn = v_neg(hn);
+            pb = iso ? NEE_INV_4PI : nee_pb_lambert(scattered.d, hn);
+            uint32_t w0 = stream_u32(&g_light_rng), w1 = stream_u32(&g_light_rng), w2 = stream_u32(&g_light_rng);
+            REAL us = (REAL)rtmi_u01(w0), pl = 0;
+            int ok = 0;
+            if (us < p_env) { /* the map */
+                to_env = 1;
+                COUNT(C_ENV_SAMPLE);
+                ok = env_sample(E, (REAL)rtmi_u01(w1), (REAL)rtmi_u01(w2), &dir, &pl);
+                if (!ok) COUNT(C_ENV_NO_SAMPLE);
+            } else if (n > 0) { /* an area light, with the rest of us */
+                us = (us - p_env) / p_area;
+                int hi = n - 1;
+                while (lo < hi) {
+                    int mid = (lo + hi) >> 1;
+                    if (us < lights[mid].cdf) hi = mid; else lo = mid + 1;
+                }
+                ok = nee_sample(&lights[lo], rec.p, (REAL)rtmi_u01(w1), (REAL)rtmi_u01(w2), &dir, &pl);
+                pl = p_area * pl;
+                if (p_env > (REAL)0) COUNT(C_ENV_AREA_SAMPLE);
+            }
+            if (ok) {
+                REAL pbl = iso ? NEE_INV_4PI : nee_pb_lambert(dir, hn);
+                if (pbl > (REAL)0 && pl > (REAL)0 && pl < R_MAX) {
+                    c = v_scale(v_mul(T, att), nee_mis_light(pbl, pl));
+                    pending = 1;
+                }
+            }
+        }
+        T = v_mul(T, att);
+        const int ends = roulette_ends(cx, &T, depth + 1, pending);
+        if (pending) {
+            HitRecord srec;
+            const int got = shadow_hit(cx, rec.p, dir, ray.time, &srec);
+            if (to_env) { /* V = 1 iff the ray hits nothing; env(d) from the sampled direction */
+                REAL u, v, theta;
+                if (got) COUNT(C_ENV_OCCLUDED); else COUNT(C_ENV_UNOCCLUDED);
+                if (!got && env_uv(dir, &u, &v, &theta)) L = v_add(L, v_mul(c, env_radiance(E, u, v)));
+            } else if (got && srec.prim == lights[lo].h && srec.mat->kind == MAT_DIFFUSE_LIGHT) {
+                L = v_add(L, v_mul(c, mat_emitted(srec.mat, srec.u, srec.v, srec.p)));
+            }
+        }
+        if (ends) { depth++; break; }
+        ray = scattered;
+    }
+    g_bounces = depth;
     return L;
 }
 
@@ -1424,24 +1692,42 @@ ORC_API int orc_emitters(void *world, OrcEmitter *out, int cap) {
     return l.n;
 }
 
-/* The pixel loop of orc_render for the three estimators the tests compare: the plain path (lights == NULL), NEE
- * (nee != 0, with the n_lights entries of lights_in; always the throughput form) and either with every sample's fp32 radiance in
- * out_samples [ny, nx, ns, 3] (may be NULL). */
-static int render_rows(void *cam_, void *world_, int nee, const OrcLight *lights_in, int n_lights, int nx, int ny,
-                       int ns, uint64_t seed, int flags, int max_depth, double t_min, int row_begin, int row_end,
-                       float *out_linear, int32_t *out_rgb, double *out_mean, uint64_t *out_sig, float *out_samples) {
+/* What render_rows takes beyond orc_render's arguments; NULL = the plain path. */
+typedef struct {
+    int nee;                /* color_nee with the light table */
+    const OrcLight *lights; /* n_lights entries, the device's order */
+    int n_lights;
+    const EnvMap *env;      /* not NULL: color_env (with `nee` as its nee) */
+    int rr_min_depth;       /* roulette: 0 = off */
+    double rr_q_min;
+    float *out_samples;     /* [ny, nx, ns, 3] or NULL */
+    uint32_t *out_bounces;  /* [ny, nx] or NULL */
+} RowsExt;
+
+/* The pixel loop of orc_render for the estimators the tests compare: the plain path, NEE (always the throughput form),
+ * the environment estimator, each with or without roulette, every sample's fp32 radiance in out_samples and the
+ * per-pixel sum of the depths at which the paths were written in out_bounces. */
+static int render_rows(void *cam_, void *world_, const RowsExt *x, int nx, int ny, int ns, uint64_t seed, int flags,
+                       int max_depth, double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
+                       double *out_mean, uint64_t *out_sig) {
+    static const RowsExt plain = {0, NULL, 0, NULL, 0, 1.0, NULL, NULL};
+    if (!x) x = &plain;
     const Camera *cam = (Camera *)cam_;
+    const int nee = x->nee, n_lights = x->n_lights;
+    float *out_samples = x->out_samples;
     RenderCtx cx;
     cx.world = (Hittable *)world_;
     cx.max_depth = max_depth;
     cx.t_min = (REAL)t_min;
+    cx.rr_min_depth = x->rr_min_depth;
+    cx.rr_q_min = (REAL)(float)x->rr_q_min;
     g_flags = flags;
     NeeL *lights = NULL;
-    if (lights_in && n_lights > 0) {
+    if (x->lights && n_lights > 0) {
         lights = (NeeL *)malloc(sizeof(NeeL) * (size_t)n_lights);
         if (!lights) return 1;
         for (int i = 0; i < n_lights; i++) {
-            const OrcLight *s = &lights_in[i];
+            const OrcLight *s = &x->lights[i];
             NeeL *d = &lights[i];
             d->h = (const Hittable *)(uintptr_t)s->handle;
             d->plane = s->kind == 2 ? s->plane : -1;
@@ -1450,12 +1736,14 @@ static int render_rows(void *cam_, void *world_, int nee, const OrcLight *lights
             d->area = (REAL)s->area; d->p_sel = (REAL)s->p_sel; d->cdf = (REAL)s->cdf;
         }
     }
+    const int throughput = (flags & ORC_THROUGHPUT_FORM) || x->rr_min_depth > 0;
     if (row_begin < 0) row_begin = 0;
     if (row_end > ny) row_end = ny;
     for (int row = row_begin; row < row_end; row++) {
         int j = ny - 1 - row;
         for (int i = 0; i < nx; i++) {
             double col[3] = {0.0, 0.0, 0.0};
+            uint32_t bounces = 0;
             g_sig = 0;
             for (int s = 0; s < ns; s++) {
                 stream_init(&g_rng, seed, (uint32_t)s, (uint32_t)(j * nx + i), 0);
@@ -1464,12 +1752,16 @@ static int render_rows(void *cam_, void *world_, int nee, const OrcLight *lights
                 REAL v = ((REAL)j + rng_uniform()) / (REAL)ny;
                 Ray ray = camera_get_ray(cam, u, v);
                 V3 c;
-                if (nee) {
-                    stream_init(&g_light_rng, seed, (uint32_t)s, (uint32_t)(j * nx + i), 3);
+                g_bounces = 0;
+                if (x->env || nee) stream_init(&g_light_rng, seed, (uint32_t)s, (uint32_t)(j * nx + i), 3);
+                if (x->env) {
+                    c = color_env(&cx, ray, lights, lights ? n_lights : 0, x->env, nee);
+                } else if (nee) {
                     c = color_nee(&cx, ray, lights, lights ? n_lights : 0);
                 } else {
-                    c = (flags & ORC_THROUGHPUT_FORM) ? color_throughput(&cx, ray) : color(&cx, &ray, 0);
+                    c = throughput ? color_throughput(&cx, ray) : color(&cx, &ray, 0);
                 }
+                bounces += (uint32_t)g_bounces;
                 if (out_samples) {
                     float *o = out_samples + (((size_t)row * nx + i) * ns + s) * 3;
                     o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z;
@@ -1478,6 +1770,7 @@ static int render_rows(void *cam_, void *world_, int nee, const OrcLight *lights
             }
             size_t o = ((size_t)row * nx + i) * 3;
             if (out_sig) out_sig[(size_t)row * nx + i] = g_sig;
+            if (x->out_bounces) x->out_bounces[(size_t)row * nx + i] = bounces;
             for (int ch = 0; ch < 3; ch++) {
                 double m = col[ch] / (double)ns;
                 if (out_mean) out_mean[o + ch] = m;
@@ -1497,16 +1790,17 @@ static int render_rows(void *cam_, void *world_, int nee, const OrcLight *lights
 ORC_API int orc_render(void *cam_, void *world_, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
                        double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
                        double *out_mean, uint64_t *out_sig) {
-    return render_rows(cam_, world_, 0, NULL, 0, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
-                       out_rgb, out_mean, out_sig, NULL);
+    return render_rows(cam_, world_, NULL, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
+                       out_rgb, out_mean, out_sig);
 }
 /* orc_render plus every sample's fp32 radiance: out_samples [ny, nx, ns, 3] (rows outside [row_begin, row_end) are
  * not written) */
 ORC_API int orc_render_samples(void *cam_, void *world_, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
                                double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
                                double *out_mean, uint64_t *out_sig, float *out_samples) {
-    return render_rows(cam_, world_, 0, NULL, 0, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
-                       out_rgb, out_mean, out_sig, out_samples);
+    RowsExt x = {0, NULL, 0, NULL, 0, 1.0, out_samples, NULL};
+    return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
+                       out_rgb, out_mean, out_sig);
 }
 /* rtmi_render_nee's estimator (include/rtmi_nee.h) with the light table `lights` (n_lights entries, the device's
  * order; area, p_sel and cdf already the floats rtmi_scene_attach_lights makes of them).  Paths, signatures and
@@ -1515,8 +1809,89 @@ ORC_API int orc_render_nee(void *cam_, void *world_, const OrcLight *lights, int
                            uint64_t seed, int flags, int max_depth, double t_min, int row_begin, int row_end,
                            float *out_linear, int32_t *out_rgb, double *out_mean, uint64_t *out_sig, float *out_samples) {
     if (n_lights < 0 || (n_lights > 0 && !lights)) return 1;
-    return render_rows(cam_, world_, 1, lights, n_lights, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min,
-                       row_begin, row_end, out_linear, out_rgb, out_mean, out_sig, out_samples);
+    RowsExt x = {1, lights, n_lights, NULL, 0, 1.0, out_samples, NULL};
+    return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
+                       row_end, out_linear, out_rgb, out_mean, out_sig);
+}
+
+/* The exported map: the texels and the tables of rtmi_env_tables (the tests pass tests/env_ref.py's), 56 B. */
+typedef struct {
+    int32_t w, h;
+    const float *rgb, *row_cdf, *row_p, *col_cdf, *col_p;
+    double total; /* the f64 total weight: the map can be sampled iff total > 0 */
+} OrcEnv;
+/* p_env by include/rtmi_env.h's rule: env_select_p with a light table that is not empty, 1 with an empty one, 0 when
+ * the map cannot be sampled */
+static int env_map_of(const OrcEnv *e, int n_lights, double env_select_p, EnvMap *E) {
+    if (!e || e->w < 1 || e->h < 1 || !e->rgb || !e->row_cdf || !e->row_p || !e->col_cdf || !e->col_p) return 1;
+    E->w = e->w; E->h = e->h;
+    E->rgb = e->rgb; E->row_cdf = e->row_cdf; E->row_p = e->row_p; E->col_cdf = e->col_cdf; E->col_p = e->col_p;
+    E->p_env = !(e->total > 0.0) ? (REAL)0 : (n_lights > 0 ? (REAL)(float)env_select_p : (REAL)1);
+    return 0;
+}
+/* rtmi_render_env's estimator (include/rtmi_env.h): orc_render_nee's arguments plus the map, nee (0 or 1) and
+ * env_select_p.  With nee = 0 the light table is not read. */
+ORC_API int orc_render_env(void *cam_, void *world_, const OrcLight *lights, int n_lights, const OrcEnv *env, int nee,
+                           double env_select_p, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
+                           double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
+                           double *out_mean, uint64_t *out_sig, float *out_samples) {
+    EnvMap E;
+    if (n_lights < 0 || (n_lights > 0 && !lights) || (nee != 0 && nee != 1)) return 1;
+    if (env_map_of(env, n_lights, env_select_p, &E)) return 1;
+    RowsExt x = {nee, lights, n_lights, &E, 0, 1.0, out_samples, NULL};
+    return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
+                       row_end, out_linear, out_rgb, out_mean, out_sig);
+}
+/* rtmi_render_roulette's estimator (include/rtmi_roulette.h): estimator 0 plain, 1 NEE, 2 the map with nee = 0, 3 the
+ * map with nee = 1 and env_select_p (RTMI_ROULETTE_*); min_depth >= 1 and q_min in (0, 1].  out_bounces [ny, nx]: the
+ * sum over the pixel's samples of the depth at which the path was written. */
+ORC_API int orc_render_roulette(void *cam_, void *world_, const OrcLight *lights, int n_lights, const OrcEnv *env,
+                                int estimator, int min_depth, double q_min, double env_select_p, int nx, int ny, int ns,
+                                uint64_t seed, int flags, int max_depth, double t_min, int row_begin, int row_end,
+                                float *out_linear, int32_t *out_rgb, double *out_mean, uint64_t *out_sig,
+                                float *out_samples, uint32_t *out_bounces) {
+    EnvMap E;
+    if (estimator < 0 || estimator > 3 || min_depth < 1 || !(q_min > 0.0 && q_min <= 1.0)) return 1;
+    const int nee = estimator == 1 || estimator == 3, with_env = estimator >= 2;
+    if (n_lights < 0 || (n_lights > 0 && !lights)) return 1;
+    if (!nee) n_lights = 0;
+    if (with_env && env_map_of(env, n_lights, env_select_p, &E)) return 1;
+    RowsExt x = {nee, nee ? lights : NULL, n_lights, with_env ? &E : NULL, min_depth, q_min, out_samples, out_bounces};
+    return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
+                       row_end, out_linear, out_rgb, out_mean, out_sig);
+}
+/* The map functions alone: env(d) and the BSDF-side pdf of n directions (out: n x (r, g, b, pdf)) ... */
+ORC_API int orc_env_lookup(const OrcEnv *env, double p_env, int flags, const float *dirs, float *out, long n) {
+    EnvMap E;
+    if (env_map_of(env, 0, 1.0, &E)) return 1;
+    E.p_env = (REAL)(float)p_env;
+    g_flags = flags;
+    for (long k = 0; k < n; k++) {
+        REAL u, v, theta;
+        float *o = out + 4 * k;
+        o[0] = o[1] = o[2] = o[3] = 0.0f;
+        if (!env_uv(v3((REAL)dirs[3 * k], (REAL)dirs[3 * k + 1], (REAL)dirs[3 * k + 2]), &u, &v, &theta)) continue;
+        const V3 c = env_radiance(&E, u, v);
+        o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z;
+        o[3] = (float)env_pdf(&E, u, v, theta);
+    }
+    return 0;
+}
+/* ... and the light sample of n pairs of uniforms (out: n x (dx, dy, dz, pdf), all 0 where there is no sample) */
+ORC_API int orc_env_sample(const OrcEnv *env, double p_env, int flags, const float *u12, float *out, long n) {
+    EnvMap E;
+    if (env_map_of(env, 0, 1.0, &E)) return 1;
+    E.p_env = (REAL)(float)p_env;
+    g_flags = flags;
+    for (long k = 0; k < n; k++) {
+        V3 d;
+        REAL pdf;
+        float *o = out + 4 * k;
+        o[0] = o[1] = o[2] = o[3] = 0.0f;
+        if (!env_sample(&E, (REAL)u12[2 * k], (REAL)u12[2 * k + 1], &d, &pdf)) continue;
+        o[0] = (float)d.x; o[1] = (float)d.y; o[2] = (float)d.z; o[3] = (float)pdf;
+    }
+    return 0;
 }
 
 /* P3 text exactly as tests/test.rs:59,79 : "P3\n{nx} {ny}\n255\n" then "{ir} {ig} {ib}\n" per pixel.

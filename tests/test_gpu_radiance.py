@@ -6,7 +6,8 @@ shutter [0, 1]) for every sample s — direction from words 0 and 1 of stream (s
 makes one radiance call per s with first_sample = s, spp = 1, stream_skip = 3 and the rays in pixel-index order.
 1. plain == the fp32 oracle's render_samples, both flag settings, byte-identical between them;
 2. NEE == the oracle's render_nee(samples=True);
-3. ENV and ENV_NEE == the device's own render_env, through the numpy restatements of the resolve;
+3. ENV and ENV_NEE == the device's own render_env, through the numpy restatements of the resolve, and == the oracle's
+   render_env(samples=True), sample for sample;
 4. mean and stderr are the two numpy restatements of the returned samples; spp = 1 gives stderr = +inf;
 5. the result does not depend on how samples or rays are split into calls; the device form writes nothing beyond;
 6. the first segment's interval follows trace / occluded;
@@ -18,10 +19,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import env_ref
 import query_ref as Q
 import scenes_extra
 from nee_oracle_ref import oracle_lights, welford_stderr
-from oracle.oracle import ARITH_DEVICE, SKY, THROUGHPUT_FORM
+from oracle.oracle import ARITH_DEVICE, LIGHT_DTYPE, SKY, THROUGHPUT_FORM
 from raytracing_rust_amd import abi, env_from_sky, philox, scenes
 from raytracing_rust_amd.host import RAY_DTYPE, HostError, Unsupported
 from roulette_ref import image
@@ -138,6 +140,35 @@ def test_env_equals_the_devices_render(host, name, nee):
     assert _differing(lin, ref["linear"]) == 0, "%d channels of linear differ" % _differing(lin, ref["linear"])
     se = welford_stderr(got)
     assert _differing(se, ref["stderr"]) == 0, "%d channels of stderr differ" % _differing(se, ref["stderr"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["random_spheres", "lit_random_spheres", "lit_smoke"])
+@pytest.mark.parametrize("nee", [False, True], ids=["env", "env_nee"])
+def test_env_equals_oracle_samples(host, orc32, name, nee):
+    """The sun map, env_select_p = 0.25, the tables from tests/env_ref.py: random_spheres has no light (p_env = 1), the
+    other two share the light samples between the map and their lamps."""
+    cam_h, world_h = _build(host, name)
+    cam_o, world_o = _build(orc32, name)
+    sc = host.lower(world_h).upload(0, nee=True)
+    lights = oracle_lights(orc32, world_o, sc) if len(sc.lights()) else np.zeros(0, LIGHT_DTYPE)
+    assert (len(lights) > 0) == (name != "random_spheres")
+    m = env_ref.sun_map()
+    orc32.reset_counters()
+    ref = orc32.render_env(cam_o, world_o, lights, m, env_ref.tables(m), nee, 0.25, NX, NY, NS, seed=SEED,
+                           flags=ARITH_DEVICE | THROUGHPUT_FORM, samples=True)["samples"]
+    cnt = orc32.counters()
+    orc32.free_all()
+    assert (cnt["env_sample"] >= 100) == nee and (cnt["env_area_sample"] >= 100) == (nee and len(lights) > 0)
+    nonzero = float(np.mean(np.any(ref != 0.0, axis=-1)))
+    print("%s: %.1f %% of the oracle's samples are non-zero" % (name, 100.0 * nonzero))
+    assert nonzero >= 0.4, nonzero
+    sc.attach_env(m)
+    est = "env_nee" if nee else "env"
+    exact, fast = _gather(sc, cam_h, est, 0, env_select_p=0.25), _gather(sc, cam_h, est, FC, env_select_p=0.25)
+    assert exact.tobytes() == fast.tobytes(), "%s: %d channels differ between the flags" % (name, _differing(exact, fast))
+    bad = _differing(fast, ref)
+    assert bad == 0, "%s: %d of %d channels differ from the oracle" % (name, bad, ref.size)
 
 
 # ---- 4. / 5. mean, stderr and independence of splitting --------------------------------------------------------------------
