@@ -21,6 +21,8 @@ pub const RTMI_FLAG_PROGRESSIVE: u32 = 16384;
 /// include/rtmi_light_coop.h: the NEE / environment entries trace on the wave-cooperative kernel (same bits)
 pub const RTMI_FLAG_LIGHT_COOP: u32 = 65536;
 pub const RTMI_FLAG_ROULETTE_COOP: u32 = 131072;
+/// include/rtmi_light_tree.h: rtmi_render_nee picks its light by walking the light tree
+pub const RTMI_FLAG_LIGHT_TREE: u32 = 262144;
 pub const RTMI_OK: i32 = 0;
 pub const RTMI_ERR_INVALID: i32 = 1;
 pub const RTMI_ERR_UNSUPPORTED: i32 = 2;
@@ -593,6 +595,73 @@ extern "C" {
     ) -> c_int;
     /// the device's lookup or light sample on the attached map (RTMI_ENV_PROBE_*)
     pub fn rtmi_probe_env(scene: *mut RtmiScene, op: c_int, input: *const f32, out: *mut f32, n: u32) -> c_int;
+}
+
+// ---- include/rtmi_light_tree.h: position-aware light selection for next-event estimation ------------------------------
+
+pub const RTMI_LIGHT_TREE_LEAF: u32 = 0x8000_0000;
+pub const RTMI_LIGHT_TREE_PROBE_PICK: c_int = 0;
+pub const RTMI_LIGHT_TREE_PROBE_PMF: c_int = 1;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiLightNode {
+    pub c: [f32; 3],
+    pub r2: f32,
+    pub power: f32,
+    pub link: u32,
+    pub pad: [u32; 2],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiLightPath {
+    pub trail: u32,
+    pub depth: u32,
+}
+
+extern "C" {
+    /// the tree over the light table of a flat description (host code, no device): at most `cap` nodes and cap / 2 paths,
+    /// the full node count (2 * lights) in `n_nodes`
+    pub fn rtmi_light_tree_from_desc(
+        desc: *const RtmiSceneDesc,
+        nodes: *mut RtmiLightNode,
+        cap: u32,
+        n_nodes: *mut u32,
+        paths: *mut RtmiLightPath,
+    ) -> c_int;
+    /// the device's walk on the host: the light of each point for each uniform, and its probability
+    pub fn rtmi_light_tree_pick(
+        nodes: *const RtmiLightNode,
+        n_nodes: u32,
+        points: *const f32,
+        us: *const f32,
+        n: u32,
+        out_light: *mut u32,
+        out_p: *mut f32,
+    ) -> c_int;
+    /// ... and the reverse walk: the probability of a given light from a given point
+    pub fn rtmi_light_tree_pmf(
+        nodes: *const RtmiLightNode,
+        n_nodes: u32,
+        paths: *const RtmiLightPath,
+        points: *const f32,
+        lights: *const u32,
+        n: u32,
+        out_p: *mut f32,
+    ) -> c_int;
+    /// attaches the light table when it is missing, builds the tree and uploads it
+    pub fn rtmi_scene_attach_light_tree(scene: *mut RtmiScene, desc: *const RtmiSceneDesc) -> c_int;
+    /// the device's own walk on a batch (RTMI_LIGHT_TREE_PROBE_*)
+    pub fn rtmi_probe_light_tree(
+        scene: *mut RtmiScene,
+        op: c_int,
+        points: *const f32,
+        aux: *const c_void,
+        n: u32,
+        out_light: *mut u32,
+        out_p: *mut f32,
+    ) -> c_int;
 }
 
 // ---- include/rtmi_adaptive_nee.h: adaptive sampling with next-event estimation or environment lighting ---------------

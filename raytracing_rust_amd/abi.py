@@ -32,6 +32,7 @@ RTMI_FLAG_TEST_OVERFLOW = 8192
 RTMI_FLAG_PROGRESSIVE = 16384  # opt-in: the framebuffer holds the image of the samples so far after every pass
 RTMI_FLAG_LIGHT_COOP = 65536  # include/rtmi_light_coop.h: NEE / environment renders on the wave-cooperative kernel
 RTMI_FLAG_ROULETTE_COOP = 131072  # include/rtmi_roulette_coop.h: roulette renders on the wave-cooperative kernel
+RTMI_FLAG_LIGHT_TREE = 262144  # include/rtmi_light_tree.h: rtmi_render_nee picks its light by walking the light tree
 RTMI_ERR_DEVICE = 3
 RTMI_ERR_CANCELLED = 5
 RTMI_TEXEL_POISON = 0x80000000
@@ -195,6 +196,24 @@ class Light(C.Structure):
 RTMI_NEE_SYMBOLS = ["rtmi_lights_from_desc", "rtmi_scene_attach_lights", "rtmi_render_nee"]
 
 
+class LightNode(C.Structure):
+    """rtmi_light_node (include/rtmi_light_tree.h): one node of the light tree (32 bytes)."""
+    _fields_ = [("c", C.c_float * 3), ("r2", C.c_float), ("power", C.c_float), ("link", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class LightPath(C.Structure):
+    """rtmi_light_path (include/rtmi_light_tree.h): where a light's leaf lies in the tree (8 bytes)."""
+    _fields_ = [("trail", C.c_uint32), ("depth", C.c_uint32)]
+
+
+RTMI_LIGHT_TREE_LEAF = 0x80000000
+RTMI_LIGHT_TREE_PROBE_PICK, RTMI_LIGHT_TREE_PROBE_PMF = 0, 1
+
+# the functions of include/rtmi_light_tree.h (the light tree), kept apart from those of the other headers
+RTMI_LIGHT_TREE_SYMBOLS = ["rtmi_light_tree_from_desc", "rtmi_light_tree_pick", "rtmi_light_tree_pmf",
+                           "rtmi_scene_attach_light_tree", "rtmi_probe_light_tree"]
+
+
 class EnvMap(C.Structure):
     """rtmi_env_map (include/rtmi_env.h): an environment map, height * width * 3 floats, row 0 the top row (16 bytes)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.c_void_p)]
@@ -352,6 +371,17 @@ def load_rtmi():
     lib.rtmi_scene_attach_lights.argtypes = [vp, C.POINTER(SceneDesc)]
     lib.rtmi_render_nee.restype = C.c_int
     lib.rtmi_render_nee.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]
+    lib.rtmi_light_tree_from_desc.restype = C.c_int
+    lib.rtmi_light_tree_from_desc.argtypes = [C.POINTER(SceneDesc), C.POINTER(LightNode), C.c_uint32, C.POINTER(C.c_uint32),
+                                              C.POINTER(LightPath)]
+    lib.rtmi_light_tree_pick.restype = C.c_int
+    lib.rtmi_light_tree_pick.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
+    lib.rtmi_light_tree_pmf.restype = C.c_int
+    lib.rtmi_light_tree_pmf.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
+    lib.rtmi_scene_attach_light_tree.restype = C.c_int
+    lib.rtmi_scene_attach_light_tree.argtypes = [vp, C.POINTER(SceneDesc)]
+    lib.rtmi_probe_light_tree.restype = C.c_int
+    lib.rtmi_probe_light_tree.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, vp, vp]
     lib.rtmi_env_tables.restype = C.c_int
     lib.rtmi_env_tables.argtypes = [C.POINTER(EnvMap), vp, vp, vp, vp, C.POINTER(C.c_double)]
     lib.rtmi_scene_attach_env.restype = C.c_int
@@ -465,6 +495,8 @@ def load_host():
         "rth_render_features": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_attach_lights": (i, [vp]),
         "rth_render_nee": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]),
+        "rth_attach_light_tree": (i, [vp]),
+        "rth_probe_light_tree": (i, [vp, i, vp, vp, u32, vp, vp]),
         "rth_attach_env": (i, [vp, u32, u32, vp]),
         "rth_render_env": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(EnvRender), vp, vp, vp, vp, C.POINTER(Stats)]),
         "rth_probe_env": (i, [vp, i, vp, vp, u32]),

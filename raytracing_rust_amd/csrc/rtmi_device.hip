@@ -49,6 +49,7 @@
 #include "rtmi_roulette.h"
 #include "rtmi_light_coop.h"
 #include "rtmi_roulette_coop.h"
+#include "rtmi_light_tree.h"
 #include "rtmi_light_launch.hpp"
 #include "rtmi_session.h"
 #include "rtmi_session_launch.hpp"
@@ -154,6 +155,11 @@ struct rtmi_scene {
     NeeLight *nee_lights = nullptr;    // [max(n, 1)]
     int32_t *nee_prim_light = nullptr; // [max(n_prims, 1)]
     uint32_t nee_n = 0;
+    // light tree (include/rtmi_light_tree.h): the attached nodes (64-B aligned pairs) and paths, freed with the handle
+    bool has_light_tree = false;
+    float4 *lt_nodes = nullptr; // [max(lt_n, 2)][2]
+    uint2 *lt_paths = nullptr;  // [max(lt_n / 2, 1)]
+    uint32_t lt_n = 0;          // slots: 2 * lights
     // environment lighting (include/rtmi_env.h): the attached map and its tables, freed with the handle
     bool has_env = false;
     float4 *env_texels = nullptr; // [h][w] {r, g, b, 0}
@@ -605,6 +611,8 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->rad_out) (void)hipFree(s->rad_out);
     if (s->nee_lights) (void)hipFree(s->nee_lights);
     if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
+    if (s->lt_nodes) (void)hipFree(s->lt_nodes);
+    if (s->lt_paths) (void)hipFree(s->lt_paths);
     if (s->env_texels) (void)hipFree(s->env_texels);
     if (s->env_tables) (void)hipFree(s->env_tables);
     if (s->partial) (void)hipFree(s->partial);
@@ -2041,6 +2049,7 @@ struct Estimator {
     float env_select_p;     // rtmi_env_render's, read with the map only
     const char *null_scene; // the refusal of a NULL handle
     const char *no_lights;  // the refusal of a handle without the light table, after "name: "
+    bool tree = false;      // reads the light tree (rtmi_scene_attach_light_tree; RTMI_FLAG_LIGHT_TREE)
 };
 
 // the checks of rtmi_env_render-style options, in `name`'s words
@@ -2099,6 +2108,8 @@ static int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
     if (m.env && !s->has_env)
         return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no environment map attached (rtmi_scene_attach_env)");
     if (m.nee && !s->has_lights) return fail(RTMI_ERR_INVALID, std::string(m.name) + ": " + m.no_lights);
+    if (m.tree && !s->has_light_tree)
+        return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no light tree attached (rtmi_scene_attach_light_tree)");
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = begin_blocking(s)) return rc;
     c.busy.s = s; c.busy.st = s->stream;
@@ -2715,6 +2726,7 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     if (s->nee_lights) { HIP_TRY(hipFree(s->nee_lights)); s->nee_lights = nullptr; }
     if (s->nee_prim_light) { HIP_TRY(hipFree(s->nee_prim_light)); s->nee_prim_light = nullptr; }
     s->has_lights = false;
+    s->has_light_tree = false; // its leaves index the table it was built over (rtmi_light_tree.h)
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->nee_lights), dl.size() * sizeof(NeeLight)));
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->nee_prim_light), pl.size() * sizeof(int32_t)));
     HIP_TRY(hipMemcpy(s->nee_lights, dl.data(), dl.size() * sizeof(NeeLight), hipMemcpyHostToDevice));
@@ -2724,22 +2736,111 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     return RTMI_OK;
 }
 
-// The per-lane NEE kernel (rtmi_nee.hip), or the cooperative one (rtmi_light_coop.hip), in render_fixed.
+// ---- light tree (include/rtmi_light_tree.h) -----------------------------------------------------------------------------
+extern "C" int rtmi_scene_attach_light_tree(rtmi_scene *s, const rtmi_scene_desc *d) {
+    if (!s || !d) return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_light_tree: NULL argument");
+    const rtmi_scene_desc &m = s->meta;
+    if (d->n_items != m.n_items || d->n_prims != m.n_prims || d->n_nodes != m.n_nodes || d->n_xforms != m.n_xforms ||
+        d->n_materials != m.n_materials || d->n_textures != m.n_textures)
+        return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_light_tree: counts differ from the handle's scene description");
+    std::vector<rtmi_light_node> nodes;
+    std::vector<rtmi_light_path> paths;
+    int rc = rtmi_light_tree_build(d, nodes, paths); // every check of the description comes before the first use of the device
+    if (rc) return rc;
+    bool has_lights;
+    {
+        std::lock_guard<std::mutex> lock(s->mu);
+        has_lights = s->has_lights;
+    }
+    if (!has_lights && (rc = rtmi_scene_attach_lights(s, d))) return rc;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (s->nee_n * 2u != (uint32_t)nodes.size())
+        return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_light_tree: the attached light table is not this description's");
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running render may read the old tree
+    if (s->lt_nodes) { HIP_TRY(hipFree(s->lt_nodes)); s->lt_nodes = nullptr; }
+    if (s->lt_paths) { HIP_TRY(hipFree(s->lt_paths)); s->lt_paths = nullptr; }
+    s->has_light_tree = false;
+    const size_t nn = std::max<size_t>(nodes.size(), 2), np = std::max<size_t>(paths.size(), 1);
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->lt_nodes), nn * sizeof(rtmi_light_node))); // hipMalloc aligns to 256 B
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->lt_paths), np * sizeof(rtmi_light_path)));
+    HIP_TRY(hipMemset(s->lt_nodes, 0, nn * sizeof(rtmi_light_node)));
+    HIP_TRY(hipMemset(s->lt_paths, 0, np * sizeof(rtmi_light_path)));
+    if (!nodes.empty()) {
+        HIP_TRY(hipMemcpy(s->lt_nodes, nodes.data(), nodes.size() * sizeof(rtmi_light_node), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->lt_paths, paths.data(), paths.size() * sizeof(rtmi_light_path), hipMemcpyHostToDevice));
+    }
+    s->lt_n = (uint32_t)nodes.size();
+    s->has_light_tree = true;
+    return RTMI_OK;
+}
+
+static DevLightTree dev_light_tree(const rtmi_scene *s) {
+    DevLightTree T;
+    T.nodes = s->lt_nodes; T.paths = s->lt_paths; T.n = s->lt_n;
+    return T;
+}
+
+extern "C" int rtmi_probe_light_tree(rtmi_scene *s, int op, const float *points, const void *aux, uint32_t n, uint32_t *out_light,
+                                     float *out_p) {
+    const bool pick = op == RTMI_LIGHT_TREE_PROBE_PICK;
+    if (!s) return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: scene is NULL");
+    if (!pick && op != RTMI_LIGHT_TREE_PROBE_PMF) return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: unknown op");
+    if (n > 0u && (!points || !aux || !out_p || (pick && !out_light))) return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: NULL argument");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->has_light_tree)
+        return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: no light tree attached (rtmi_scene_attach_light_tree)");
+    if (n == 0u) return RTMI_OK;
+    if (s->lt_n == 0u) return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: the tree is empty (the scene has no eligible light)");
+    if (!pick)
+        for (uint32_t k = 0; k < n; k++)
+            if (static_cast<const uint32_t *>(aux)[k] >= s->lt_n / 2u)
+                return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: a light index is outside the table");
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = begin_blocking(s)) return rc;
+    // one device buffer, freed on every return: points [n][3] | aux [n] | light [n] | p [n]
+    struct DevBuf {
+        float *p = nullptr;
+        ~DevBuf() { if (p) (void)hipFree(p); }
+    } buf;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&buf.p), (size_t)n * 6 * sizeof(float)));
+    float *dpts = buf.p, *dp = buf.p + (size_t)n * 5;
+    uint32_t *daux = reinterpret_cast<uint32_t *>(buf.p + (size_t)n * 3), *dlight = daux + n;
+    HIP_TRY(hipMemcpyAsync(dpts, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(daux, aux, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(rtmi_light_tree_launch_probe(op, dev_light_tree(s), dpts, daux, n, dlight, dp, s->stream));
+    if (pick) HIP_TRY(hipMemcpyAsync(out_light, dlight, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(out_p, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return RTMI_OK;
+}
+
+// The per-lane NEE kernel (rtmi_nee.hip), or the cooperative one (rtmi_light_coop.hip), in render_fixed; under
+// RTMI_FLAG_LIGHT_TREE the per-lane kernel of rtmi_light_tree.hip.
 extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
                                uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats) {
     // every argument check comes before the first use of the device
     if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG | light_coop_bits(p_in),
+                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG | RTMI_FLAG_LIGHT_TREE | light_coop_bits(p_in),
                                "NEE accepts the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
                                "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
                                "NEE renders the whole image: tile_world must be 1");
     if (rc) return rc;
-    const Estimator m{"rtmi_render_nee", true, false, 1.0f, "scene is NULL",
-                      "no light table attached (rtmi_scene_attach_lights)"};
+    const bool tree = (p_in->flags & RTMI_FLAG_LIGHT_TREE) != 0u;
+    if (tree && (p_in->flags & RTMI_FLAG_LIGHT_COOP))
+        return fail(RTMI_ERR_UNSUPPORTED, "rtmi_render_nee: the flags LIGHT_TREE and LIGHT_COOP do not combine (rtmi_light_tree.h)");
+    Estimator m{"rtmi_render_nee", true, false, 1.0f, "scene is NULL",
+                "no light table attached (rtmi_scene_attach_lights)"};
+    m.tree = tree;
     return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
                         [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
                             if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
+                            if (tree) {
+                                HIP_TRY(rtmi_light_tree_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L,
+                                                                      dev_light_tree(s)));
+                                return RTMI_OK;
+                            }
                             HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L));
                             return RTMI_OK;
                         });

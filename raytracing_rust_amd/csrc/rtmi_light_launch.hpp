@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "rtmi_env.h"
+#include "rtmi_light_tree.h"
 
 // Run-time bools to template arguments: rtmi_with_bools(f, a, b, ...) returns f(std::bool_constant<a>{},
 // std::bool_constant<b>{}, ...), so a generic lambda names the kernel instantiation as kernel<A(), B()>.
@@ -22,6 +23,16 @@ hipError_t rtmi_with_bools(F &&f, bool b, Bools... rest) {
 
 hipError_t rtmi_nee_launch_render(bool fast, bool sig, uint32_t blocks, hipStream_t stream, const DevScene &sc,
                                   const DevCamera &cam, const DevParams &P, const DevLights &L);
+
+// RTMI_FLAG_LIGHT_TREE (include/rtmi_light_tree.h, rtmi_light_tree.hip): rtmi_nee_launch_render with the light of a vertex
+// taken from the tree T
+hipError_t rtmi_light_tree_launch_render(bool fast, bool sig, uint32_t blocks, hipStream_t stream, const DevScene &sc,
+                                         const DevCamera &cam, const DevParams &P, const DevLights &L, const DevLightTree &T);
+// n walks of the device (RTMI_LIGHT_TREE_PROBE_*): points 3 floats per item, aux a uniform's bits or a light index
+hipError_t rtmi_light_tree_launch_probe(int op, const DevLightTree &T, const float *points, const uint32_t *aux, uint32_t n,
+                                        uint32_t *out_light, float *out_p, hipStream_t stream);
+// the tree over the light table of a description (host code): 2 * lights nodes, one path per light; an RTMI code
+int rtmi_light_tree_build(const rtmi_scene_desc *d, std::vector<rtmi_light_node> &nodes, std::vector<rtmi_light_path> &paths);
 
 // the tables of rtmi_env_tables for one map, rounded to float
 struct EnvTables {

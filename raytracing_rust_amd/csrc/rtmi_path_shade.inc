@@ -1,7 +1,9 @@
 // rtmi_path_shade.inc — phase B of both kernel bodies: every lane that holds a hit shades it; the path scatters, hands
 // over to a pending shadow ray (the two Philox streams swap), is cut by roulette, or ends: written and counted here.
 // The including body defines RTMI_PATH_SCRATCH (the wave's LDS, idle during shading) and RTMI_PATH_INST (shade_hit's INST:
-// whether primitives can carry transforms) before the include and undefines them after it.
+// whether primitives can carry transforms) before the include and undefines them after it.  RTMI_PATH_TREE
+// (rtmi_light_tree.hip; include/rtmi_light_tree.h) is a preprocessor switch as RTMI_PATH_RR is: with it the including
+// function also provides `lt` (DevLightTree) and NEE's light comes from the tree; without it this text is what it was.
 if (__ballot(have_hit) == 0ull) break; // nobody holds a hit and nobody can trace: all done
 prof_tick<PROF>(prof, 16, have_hit);
 {
@@ -20,9 +22,15 @@ prof_tick<PROF>(prof, 16, have_hit);
         }
     } else if constexpr (NEE) {
         const bool was_shadow = ne.shadow;
+#ifdef RTMI_PATH_TREE
+        const bool goes_on = shade_hit<decltype(g), RTMI_PATH_INST, false, true, ENV, true>(
+            sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
+            reinterpret_cast<float *>(RTMI_PATH_SCRATCH), nullptr, &nl, &ne, &gn, &ev, &lt);
+#else
         const bool goes_on = shade_hit<decltype(g), RTMI_PATH_INST, false, true, ENV>(
             sc, P.max_depth, P.ext, g, k0, k1, shading, closest, best_item, best_pf, best_medium, pa,
             reinterpret_cast<float *>(RTMI_PATH_SCRATCH), nullptr, &nl, &ne, &gn, &ev);
+#endif
         if (shading) {
             if (was_shadow) { // the light sample is counted: the path's continuation is traced next
                 pa.rd = ne.cont_rd; ne.shadow = false;

@@ -440,6 +440,73 @@ __device__ __forceinline__ bool nee_sample(const NeeLight &L, F3 x, float u1, fl
     return tq > 0.0f;
 }
 
+// ---- light tree (include/rtmi_light_tree.h, rtmi_light_tree.hip) -----------------------------------------------------
+// The attached tree on the device, built by rtmi_scene_attach_light_tree: a node is two float4 {c.x, c.y, c.z, r2} and
+// {power, link, 0, 0}, a child pair one aligned 64-B block; a path is {trail, depth}.  The walks are host functions too:
+// rtmi_light_tree_pick and rtmi_light_tree_pmf run this text on the CPU.
+struct DevLightTree {
+    const float4 *nodes; // [n][2]
+    const uint2 *paths;  // [n / 2]
+    uint32_t n;          // slots: 2 * lights, 0 for an empty table
+};
+#define RTMI_LIGHT_TREE_ONE_MINUS 0.99999994f // 1 - 2^-24
+// importance of the node {a, power} from x: power / max(|c - x|^2, r2)
+__host__ __device__ __forceinline__ float light_tree_importance(const float4 &a, float power, float x, float y, float z) {
+    const float dx = a.x - x, dy = a.y - y, dz = a.z - z;
+    const float d2 = (dx * dx + dy * dy) + dz * dz;
+    return power / (d2 > a.w ? d2 : a.w);
+}
+// the importances of the child pair at `link`, and the children's own links
+__host__ __device__ __forceinline__ void light_tree_pair(const float4 *nodes, uint32_t link, float x, float y, float z, float &il,
+                                                         float &ir, uint32_t &link_l, uint32_t &link_r) {
+    const float4 *pr = nodes + (size_t)link * 2;
+    const float4 la = pr[0], lb = pr[1], ra = pr[2], rb = pr[3];
+    il = light_tree_importance(la, lb.x, x, y, z);
+    ir = light_tree_importance(ra, rb.x, x, y, z);
+    link_l = __builtin_bit_cast(uint32_t, lb.y);
+    link_r = __builtin_bit_cast(uint32_t, rb.y);
+}
+// the light of the vertex (x, y, z) for the uniform u, and its probability
+__host__ __device__ __forceinline__ uint32_t light_tree_pick(const float4 *nodes, float x, float y, float z, float u, float &p_out) {
+    uint32_t link = __builtin_bit_cast(uint32_t, nodes[3].y); // the root, slot 1
+    float p = 1.0f;
+    while (!(link & 0x80000000u)) {
+        float il, ir;
+        uint32_t ll, lr;
+        light_tree_pair(nodes, link, x, y, z, il, ir, ll, lr);
+        const float s = il + ir;
+        const float pl = il / s;
+        if (u < pl) {
+            const float v = u / pl;
+            u = v < RTMI_LIGHT_TREE_ONE_MINUS ? v : RTMI_LIGHT_TREE_ONE_MINUS;
+            p = p * pl;
+            link = ll;
+        } else {
+            const float pr = ir / s;
+            const float v = (u - pl) / pr;
+            u = v < RTMI_LIGHT_TREE_ONE_MINUS ? v : RTMI_LIGHT_TREE_ONE_MINUS;
+            p = p * pr;
+            link = lr;
+        }
+    }
+    p_out = p;
+    return link & 0x7fffffffu;
+}
+// the probability that the walk from (x, y, z) ends at the light with this path
+__host__ __device__ __forceinline__ float light_tree_pmf(const float4 *nodes, uint2 path, float x, float y, float z) {
+    uint32_t link = __builtin_bit_cast(uint32_t, nodes[3].y);
+    float p = 1.0f;
+    for (uint32_t d = 0u; d < path.y && !(link & 0x80000000u); d++) {
+        float il, ir;
+        uint32_t ll, lr;
+        light_tree_pair(nodes, link, x, y, z, il, ir, ll, lr);
+        const float s = il + ir;
+        if ((path.x >> d) & 1u) { p = p * (ir / s); link = lr; }
+        else { p = p * (il / s); link = ll; }
+    }
+    return p;
+}
+
 // ---- environment lighting (include/rtmi_env.h, rtmi_env.hip) ---------------------------------------------------------
 // The attached map on the device, built by rtmi_scene_attach_env: the texels as float4 {r, g, b, 0} (one 16-B load each)
 // and the tables of rtmi_env_tables; p_env is the render's (0: the map is not sampled).
@@ -539,11 +606,15 @@ __device__ __forceinline__ bool env_sample(const DevEnv &E, float u1, float u2, 
 // ENV (with NEE; environment kernels, rtmi_env.hip; include/rtmi_env.h): the map *ev is one more light, chosen with
 // probability ev->p_env; area-light densities scale by 1 - p_env; a shadow ray toward the map that hits anything adds
 // nothing.
-template <typename RngT, bool INST = true, bool FEAT = false, bool NEE = false, bool ENV = false>
+// TREE (with NEE, without ENV; rtmi_light_tree.hip; include/rtmi_light_tree.h): the light of a vertex comes from the walk of
+// the tree *lt from the vertex instead of the table's search, and the walk's probability (at a BSDF hit: the reverse
+// walk's, from the ray's origin) takes the light's p_sel.
+template <typename RngT, bool INST = true, bool FEAT = false, bool NEE = false, bool ENV = false, bool TREE = false>
 __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth, uint32_t ext, RngT &g, uint32_t k0, uint32_t k1,
                                           bool active, float closest, int best_item, int best_pf, bool best_medium, Path &pa,
                                           float *scratch, ShadeFeat *feat = nullptr, const DevLights *nl = nullptr,
-                                          NeeLane *ne = nullptr, RngT *gn = nullptr, const DevEnv *ev = nullptr) {
+                                          NeeLane *ne = nullptr, RngT *gn = nullptr, const DevEnv *ev = nullptr,
+                                          const DevLightTree *lt = nullptr) {
     F3 hp = f3(0, 0, 0), hn = f3(1, 0, 0);
     float hu = 0.0f, hv = 0.0f;
     rtmi_material M;
@@ -665,7 +736,14 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
                 if (!best_medium && ne->pb > 0.0f) {
                     const int li = nl->prim_light[best_pf >> 3];
                     if (li >= 0 && nl->lights[li].item == best_item) {
-                        float pl = nee_pdf(nl->lights[li], pa.ro, hp);
+                        float pl;
+                        if constexpr (TREE) {
+                            NeeLight Lt = nl->lights[li];
+                            Lt.p_sel = light_tree_pmf(lt->nodes, lt->paths[li], pa.ro.x, pa.ro.y, pa.ro.z);
+                            pl = nee_pdf(Lt, pa.ro, hp);
+                        } else {
+                            pl = nee_pdf(nl->lights[li], pa.ro, hp);
+                        }
                         if constexpr (ENV) pl = (1.0f - ev->p_env) * pl;
                         if (pl > 0.0f) w = nee_mis_bsdf(ne->pb, pl);
                     }
@@ -773,14 +851,25 @@ __device__ __forceinline__ bool shade_hit(const DevScene &sc, uint32_t max_depth
                 uint32_t w0, w1, w2;
                 rng_take3(*gn, k0, k1, w0, w1, w2);
                 const float us = rtmi_u01(w0);
-                uint32_t lo = 0u, hi = nl->n - 1u; // the first light whose cdf exceeds us
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (us < nl->lights[mid].cdf) hi = mid; else lo = mid + 1u;
-                }
+                uint32_t lo = 0u;
                 F3 dir;
                 float pl;
-                if (nee_sample(nl->lights[lo], hp, rtmi_u01(w1), rtmi_u01(w2), dir, pl)) {
+                bool sampled;
+                if constexpr (TREE) { // the walk from the vertex; its probability is the light's p_sel
+                    float psel;
+                    lo = light_tree_pick(lt->nodes, hp.x, hp.y, hp.z, us, psel);
+                    NeeLight Lt = nl->lights[lo];
+                    Lt.p_sel = psel;
+                    sampled = nee_sample(Lt, hp, rtmi_u01(w1), rtmi_u01(w2), dir, pl);
+                } else {
+                    uint32_t hi = nl->n - 1u; // the first light whose cdf exceeds us
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (us < nl->lights[mid].cdf) hi = mid; else lo = mid + 1u;
+                    }
+                    sampled = nee_sample(nl->lights[lo], hp, rtmi_u01(w1), rtmi_u01(w2), dir, pl);
+                }
+                if (sampled) {
                     const float pbl = iso ? RTMI_NEE_INV_4PI : nee_pb_lambert(dir, hn);
                     if (pbl > 0.0f && pl > 0.0f && pl < RTMI_FLT_MAX) {
                         ne->c = (pa.T * tv) * nee_mis_light(pbl, pl);

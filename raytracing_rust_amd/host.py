@@ -148,18 +148,22 @@ class Scene:
                 "item_root": view(d.item_root, d.n_items, 6), "material_param": view(d.material_param, d.n_materials, 1)[:, 0],
                 "texture_f": view(d.texture_f, d.n_textures, 4), "perlin_ranvec": view(d.perlin_ranvec, d.n_perlin, 768)}
 
-    def upload(self, device=0, f64=False, nee=False):
+    def upload(self, device=0, f64=False, nee=False, light_tree=False):
         """Copies the scene to `device`; f64=True also attaches the double planes of the f64 render mode, nee=True the
-        light table of next-event estimation (include/rtmi_nee.h)."""
+        light table of next-event estimation (include/rtmi_nee.h), light_tree=True that table and the light tree over it
+        (include/rtmi_light_tree.h; implies nee=True)."""
         self.host._check(self.host.lib.rth_upload(self.h, device))
         self.uploaded = True
         self.device = device
         self.f64_attached = False
         self.lights_attached = False
+        self.light_tree_attached = False
         if f64:
             self.attach_f64()
-        if nee:
+        if nee or light_tree:
             self.attach_lights()
+        if light_tree:
+            self.attach_light_tree()
         return self
 
     def lights(self):
@@ -182,7 +186,56 @@ class Scene:
         """Derives the light table and attaches it to the uploaded handle (rtmi_scene_attach_lights)."""
         self.host._check(self.host.lib.rth_attach_lights(self.h))
         self.lights_attached = True
+        self.light_tree_attached = False  # a new table detaches the tree built over the old one
         return self
+
+    def light_tree(self):
+        """The light tree (rtmi_light_tree_from_desc, include/rtmi_light_tree.h) as two numpy structured arrays: nodes
+        (c float32 [3], r2, power, link, pad uint32 [2]; 2 * lights of them, none for a scene without lights) and paths
+        (trail, depth; one per light).  Host code: needs no GPU."""
+        lib = abi.load_rtmi()
+        d = self.desc()
+        n = C.c_uint32(0)
+        if lib.rtmi_light_tree_from_desc(C.byref(d), None, 0, C.byref(n), None):
+            raise HostError("rtmi_light_tree_from_desc: " + (lib.rtmi_last_error() or b"").decode())
+        nodes = np.zeros(n.value, LIGHT_NODE_DTYPE)
+        paths = np.zeros(n.value // 2, LIGHT_PATH_DTYPE)
+        if n.value and lib.rtmi_light_tree_from_desc(C.byref(d), nodes.ctypes.data_as(C.POINTER(abi.LightNode)), n.value, C.byref(n),
+                                                     paths.ctypes.data_as(C.POINTER(abi.LightPath))):
+            raise HostError("rtmi_light_tree_from_desc: " + (lib.rtmi_last_error() or b"").decode())
+        return nodes, paths
+
+    def attach_light_tree(self):
+        """Builds the light tree and attaches it to the uploaded handle, with the light table when that is missing
+        (rtmi_scene_attach_light_tree).  A scene resident on a device list (upload_multi) raises Unsupported."""
+        self.host._check(self.host.lib.rth_attach_light_tree(self.h))
+        self.lights_attached = True
+        self.light_tree_attached = True
+        return self
+
+    def _light_probe(self, op, points, aux):
+        points = np.ascontiguousarray(points, dtype=np.float32)
+        if points.ndim != 2 or points.shape[1] != 3 or aux.shape != (points.shape[0],):
+            raise ValueError("the light tree's probes take points [n, 3] and n uniforms or light indices")
+        self._ready({})
+        if self.uploaded and not getattr(self, "light_tree_attached", False):
+            self.attach_light_tree()
+        n = points.shape[0]
+        light, p = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        self.host._check(self.host.lib.rth_probe_light_tree(self.h, op, points.ctypes.data, aux.ctypes.data, n, light.ctypes.data,
+                                                            p.ctypes.data))
+        return light, p
+
+    def light_pick(self, points, u):
+        """The device's walk of the attached light tree (rtmi_probe_light_tree, PICK): for points float32 [n, 3] and
+        uniforms u float32 [n] in [0, 1) the light each walk ends at (uint32 [n]) and its probability (float32 [n]).  The
+        tree is attached on first use."""
+        return self._light_probe(abi.RTMI_LIGHT_TREE_PROBE_PICK, points, np.ascontiguousarray(u, dtype=np.float32))
+
+    def light_pmf(self, points, lights):
+        """The device's reverse walk (rtmi_probe_light_tree, PMF): the probability (float32 [n]) that the walk from
+        points[k] ends at the light lights[k] (an index into lights())."""
+        return self._light_probe(abi.RTMI_LIGHT_TREE_PROBE_PMF, points, np.ascontiguousarray(lights, dtype=np.uint32))[1]
 
     def attach_env(self, rgb):
         """Attaches an environment map (include/rtmi_env.h): float32 [H, W, 3], row 0 the top row (+y), finite and >= 0.
@@ -310,7 +363,7 @@ class Scene:
         self.host._check(self.host.lib.rth_render_features(self.h, cam.h, C.byref(p), *outs))
         return _result(out)
 
-    def render_nee(self, cam, nx, ny, ns, sig=False, precision="f32", coop=False, **kw):
+    def render_nee(self, cam, nx, ny, ns, sig=False, precision="f32", coop=False, light_tree=False, **kw):
         """Next-event estimation (include/rtmi_nee.h): render()'s paths with a light sample at every diffuse vertex,
         combined by the power heuristic; an estimator of the same image.  Returns dict(linear f32 [ny,nx,3], rgb8 u8
         [ny,nx,3], stderr f32 [ny,nx,3], stats[, sig u64 [ny,nx]]); sig equals render(sig=True)["sig"].  The light table
@@ -319,11 +372,18 @@ class Scene:
         traces the same paths; every plane has the same bits, stats["kernel"] tells which kernel ran (scenes with
         instanced primitives or media under transforms, SYNC and renders without FAST_CULL stay per-lane).  Measured at
         64 spp on an MI355X (Timing): 1.59x faster on lit_final_scene, 1.40x on lit_random_spheres, 1.05x on
-        cornell_box and 1.09x on lit_smoke (no tree to walk); it lost on no scene measured.  Opt-in all the same."""
+        cornell_box and 1.09x on lit_smoke (no tree to walk); it lost on no scene measured.  Opt-in all the same.
+        light_tree=True (RTMI_FLAG_LIGHT_TREE, include/rtmi_light_tree.h): every vertex picks its light by walking the
+        light tree from its own position instead of from the one table; same paths and sig, another estimator of the same
+        image.  It pays under grids of many small lights and costs elsewhere: measured figures in DESIGN.md §25.  The tree is attached on first use.  With a
+        single light the bits are those of the table's render; beside coop=True the call raises Unsupported."""
         if precision != "f32":
             raise Unsupported("next-event estimation has no f64 mode")
         _coop_flags(kw, coop)
+        _coop_flags(kw, light_tree, abi.RTMI_FLAG_LIGHT_TREE)
         self._ready(kw, lights=True)
+        if light_tree and self.uploaded and not getattr(self, "light_tree_attached", False):
+            self.attach_light_tree()
         p = default_params(nx, ny, ns, **kw)
         out, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr"), bool(sig))
         self.host._check(self.host.lib.rth_render_nee(self.h, cam.h, C.byref(p), *outs))
@@ -709,6 +769,10 @@ def irradiance_directions(normals, spp, seed=0):
     d /= np.linalg.norm(d, axis=2, keepdims=True)
     return np.ascontiguousarray(d.astype(np.float32))
 
+
+# rtmi_light_node and rtmi_light_path (include/rtmi_light_tree.h) as numpy sees them
+LIGHT_NODE_DTYPE = np.dtype([("c", "<f4", (3,)), ("r2", "<f4"), ("power", "<f4"), ("link", "<u4"), ("pad", "<u4", (2,))])
+LIGHT_PATH_DTYPE = np.dtype([("trail", "<u4"), ("depth", "<u4")])
 
 # rtmi_ray and rtmi_hit (include/rtmi_query.h) as numpy sees them
 RAY_DTYPE = np.dtype([("o", "<f4", (3,)), ("t_min", "<f4"), ("d", "<f4", (3,)), ("t_max", "<f4")])

@@ -10,6 +10,7 @@
 
 #include "rt_host.hpp"
 #include "rtmi_env.h"
+#include "rtmi_light_tree.h"
 #include "rtmi_adaptive_nee.h"
 #include "rtmi_roulette.h"
 #include "rtmi_session.h"
@@ -351,6 +352,22 @@ RTH_API int rth_attach_lights(void *lowered) {
         rtmi_scene *dev = DEV(lowered, name, "NEE");
         const rtmi_scene_desc d = LOW(lowered)->lowered->desc();
         return done(name, rtmi_scene_attach_lights(dev, &d), CODED);
+    });
+}
+// ---- light tree (include/rtmi_light_tree.h) ---------------------------------------------------------
+RTH_API int rth_attach_light_tree(void *lowered) {
+    return guard([&] {
+        const char *name = "rtmi_scene_attach_light_tree";
+        rtmi_scene *dev = DEV(lowered, name, "light-tree");
+        const rtmi_scene_desc d = LOW(lowered)->lowered->desc();
+        return done(name, rtmi_scene_attach_light_tree(dev, &d), CODED);
+    });
+}
+RTH_API int rth_probe_light_tree(void *lowered, int op, const float *points, const void *aux, uint32_t n, uint32_t *out_light,
+                                 float *out_p) {
+    return guard([&] {
+        const char *name = "rtmi_probe_light_tree";
+        return done(name, rtmi_probe_light_tree(DEV(lowered, name, "light-tree"), op, points, aux, n, out_light, out_p), CODED);
     });
 }
 RTH_API int rth_render_nee(void *lowered, void *cam, const rtmi_render_params *p, float *out_linear, uint8_t *out_rgb8,
