@@ -866,3 +866,65 @@ extern "C" {
         stream: *mut c_void,
     ) -> c_int;
 }
+
+// ---- include/rtmi_gather.h: hemisphere gathers -------------------------------------------------------------------------
+
+pub const RTMI_GATHER_COSINE: u32 = 0;
+pub const RTMI_GATHER_SPHERE: u32 = 1;
+
+/// rtmi_gather_params: one call's points, mode, estimator and Philox indices (64 bytes, seed at offset 32); direction s of
+/// point i is drawn from the counter (0, first_sample + s, first_point + i, 5) under `seed`, and its path is the radiance
+/// query's of ray index first_point + i, sample first_sample + s, stream_skip 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiGatherParams {
+    pub n: u32,
+    pub spp: u32,
+    pub mode: u32,
+    pub estimator: u32,
+    pub flags: u32,
+    pub max_depth: u32,
+    pub t_min: f32,
+    pub seed: u64,
+    pub first_point: u64,
+    pub first_sample: u32,
+    pub slab_points: u32,
+    pub env_select_p: f32,
+}
+
+extern "C" {
+    /// blocking, host pointers; points n * 3 floats, normals n * 3 floats (COSINE) or NULL, time n floats or NULL;
+    /// out_value, out_stderr n * 3 floats, out_sh n * 27 floats (SPHERE), each optional, not all NULL
+    pub fn rtmi_gather(
+        scene: *mut RtmiScene,
+        params: *const RtmiGatherParams,
+        points: *const f32,
+        normals: *const f32,
+        time: *const f32,
+        out_value: *mut f32,
+        out_stderr: *mut f32,
+        out_sh: *mut f32,
+        kernel_ms: *mut f64,
+    ) -> c_int;
+    /// asynchronous, device pointers, enqueued on `stream` (a hipStream_t); d_scratch holds at least 12 * spp bytes
+    pub fn rtmi_gather_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiGatherParams,
+        d_points: *const c_void,
+        d_normals: *const c_void,
+        d_time: *const c_void,
+        d_value: *mut c_void,
+        d_stderr: *mut c_void,
+        d_sh: *mut c_void,
+        d_scratch: *mut c_void,
+        scratch_bytes: u64,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// the directions of a call on the host: n * spp * 3 floats; initialises no device
+    pub fn rtmi_gather_directions(
+        params: *const RtmiGatherParams,
+        normals: *const f32,
+        n: u32,
+        out_dirs: *mut f32,
+    ) -> c_int;
+}

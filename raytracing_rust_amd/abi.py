@@ -292,6 +292,23 @@ class RadianceParams(C.Structure):
 # the functions of include/rtmi_radiance.h (radiance queries), kept apart from those of the other headers
 RTMI_RADIANCE_SYMBOLS = ["rtmi_radiance", "rtmi_radiance_device"]
 
+RTMI_GATHER_COSINE = 0  # include/rtmi_gather.h: irradiance about a normal
+RTMI_GATHER_SPHERE = 1  # ... mean radiance over the sphere and its 9 SH coefficients
+RTMI_GATHER_STREAM = 5  # the Philox stream id of the directions
+GATHER_MODES = {"cosine": RTMI_GATHER_COSINE, "sphere": RTMI_GATHER_SPHERE}
+
+
+class GatherParams(C.Structure):
+    """rtmi_gather_params (include/rtmi_gather.h): one call's points, mode, estimator and Philox indices (64 bytes; seed at
+    offset 32)."""
+    _fields_ = [("n", C.c_uint32), ("spp", C.c_uint32), ("mode", C.c_uint32), ("estimator", C.c_uint32), ("flags", C.c_uint32),
+                ("max_depth", C.c_uint32), ("t_min", C.c_float), ("seed", C.c_uint64), ("first_point", C.c_uint64),
+                ("first_sample", C.c_uint32), ("slab_points", C.c_uint32), ("env_select_p", C.c_float)]
+
+
+# the functions of include/rtmi_gather.h (hemisphere gathers), kept apart from those of the other headers
+RTMI_GATHER_SYMBOLS = ["rtmi_gather", "rtmi_gather_device", "rtmi_gather_directions"]
+
 _rtmi = None
 _host = None
 
@@ -433,6 +450,12 @@ def load_rtmi():
     lib.rtmi_radiance.argtypes = [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
     lib.rtmi_radiance_device.restype = C.c_int
     lib.rtmi_radiance_device.argtypes = [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, vp]
+    lib.rtmi_gather.restype = C.c_int
+    lib.rtmi_gather.argtypes = [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
+    lib.rtmi_gather_device.restype = C.c_int
+    lib.rtmi_gather_device.argtypes = [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
+    lib.rtmi_gather_directions.restype = C.c_int
+    lib.rtmi_gather_directions.argtypes = [C.POINTER(GatherParams), vp, C.c_uint32, vp]
     lib.rtmi_denoise.restype = C.c_int
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
@@ -521,6 +544,8 @@ def load_host():
         "rth_occluded_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),
         "rth_radiance": (i, [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_radiance_device": (i, [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, vp]),
+        "rth_gather": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
+        "rth_gather_device": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),
         "rth_render_prepare": (i, [vp, C.POINTER(RenderParams)]),
         "rth_scene_status": (i, [vp]),

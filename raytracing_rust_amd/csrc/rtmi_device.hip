@@ -57,6 +57,8 @@
 #include "rtmi_query_launch.hpp"
 #include "rtmi_radiance.h"
 #include "rtmi_radiance_launch.hpp"
+#include "rtmi_gather.h"
+#include "rtmi_gather_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -2594,6 +2596,181 @@ extern "C" int rtmi_radiance_device(rtmi_scene *s, const rtmi_radiance_params *p
     if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
     BusyMark busy_mark{s, stream};
     return radiance_enqueue(s, m, p, stream, d_rays, d_time, d_mean, d_stderr, d_samples);
+}
+
+// ---- hemisphere gathers (include/rtmi_gather.h) ---------------------------------------------------------------------------
+// The checks both forms share, in radiance_check's order: params, flags, the values, then the pointers of a batch with
+// points.  Nothing here reads the handle, so each is answered for a NULL one too.
+static int gather_check(const char *name, const rtmi_gather_params *p, const void *points, const void *normals, bool has_out,
+                        bool has_sh, const char *out_msg) {
+    const std::string nm = std::string(name) + ": ";
+    if (!p) return fail(RTMI_ERR_INVALID, nm + "params is NULL");
+    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+        return fail(RTMI_ERR_UNSUPPORTED, nm + "gathers accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
+    if (p->mode > RTMI_GATHER_SPHERE) return fail(RTMI_ERR_INVALID, nm + "mode must be RTMI_GATHER_COSINE or RTMI_GATHER_SPHERE");
+    if (p->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if (p->spp == 0u) return fail(RTMI_ERR_INVALID, nm + "spp must be at least 1");
+    if (p->spp >= (1u << 31)) return fail(RTMI_ERR_INVALID, nm + "spp must be below 2^31 (one point's samples are one slab)");
+    if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
+    if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
+    if (p->first_point > (1ull << 32) || p->first_point + p->n > (1ull << 32))
+        return fail(RTMI_ERR_INVALID, nm + "first_point + n must not exceed 2^32 (a point index would wrap onto another point's stream)");
+    if ((uint64_t)p->first_sample + p->spp > (1ull << 32))
+        return fail(RTMI_ERR_INVALID, nm + "first_sample + spp must not exceed 2^32 (a sample index would wrap onto another sample's stream)");
+    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
+    if (p->estimator == RTMI_ROULETTE_ENV_NEE && !(p->env_select_p > 0.0f && p->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
+    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (p->mode == RTMI_GATHER_COSINE && has_sh)
+        return fail(RTMI_ERR_INVALID, nm + "the sh output belongs to RTMI_GATHER_SPHERE (convolve a probe with sh_irradiance instead)");
+    if (p->n == 0u) return RTMI_OK;
+    if (!points) return fail(RTMI_ERR_INVALID, nm + "points is NULL");
+    if (p->mode == RTMI_GATHER_COSINE && !normals) return fail(RTMI_ERR_INVALID, nm + "normals is NULL (RTMI_GATHER_COSINE)");
+    if (!has_out) return fail(RTMI_ERR_INVALID, nm + out_msg);
+    return RTMI_OK;
+}
+// what the host form refuses of a point; the device form takes the caller's word
+static int gather_check_points(const char *name, const rtmi_gather_params *p, const float *points, const float *normals,
+                               const float *time) {
+    const auto bad = [&](uint32_t i, const char *what) {
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": point " + std::to_string(i) + " " + what);
+    };
+    for (uint32_t i = 0; i < p->n; i++) {
+        bool finite = !time || std::isfinite(time[i]);
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(points[3 * (size_t)i + k]);
+        if (!finite) return bad(i, "has a non-finite component");
+        if (p->mode == RTMI_GATHER_COSINE) {
+            const float l = rtmi_gather_normal_length(normals + 3 * (size_t)i);
+            if (!(l > 0.0f) || !std::isfinite(l)) return bad(i, "has a zero or non-finite normal");
+        }
+    }
+    return RTMI_OK;
+}
+static Estimator gather_estimator(const char *name, const rtmi_gather_params *p, const std::string &null_scene) {
+    const bool nee = p->estimator == RTMI_ROULETTE_NEE || p->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
+    return Estimator{name, nee, env, nee && env ? p->env_select_p : 1.0f, null_scene.c_str(),
+                     "no light table attached (rtmi_scene_attach_lights)"};
+}
+// the points of a slab: `want` (params.slab_points, or the form's own default or capacity) held to [1, (2^31 - 1) / spp]
+static uint32_t gather_slab(const rtmi_gather_params *p, uint64_t want) {
+    const uint64_t most = ((1ull << 31) - 1u) / p->spp; // >= 1: spp < 2^31
+    return (uint32_t)(want < 1u ? 1u : (want > most ? most : want));
+}
+// The launches of one slab on `stream`: points [at, at + count) of the call through pointers to the slab's records; the
+// path kernel on the persistent grid of the per-lane render kernels, fed by the handle's chunk counter (zeroed here, on the
+// call's stream: the handle serialises its calls and a stream its launches), then the resolve.
+static int gather_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_gather_params *p, hipStream_t stream, uint32_t at,
+                          uint32_t count, const void *d_points, const void *d_normals, const void *d_time, void *d_value,
+                          void *d_stderr, void *d_sh, void *d_scratch) {
+    rtmi_render_params rp{};
+    rp.nx = 1u; rp.ny = 1u; rp.ns = 1u; rp.tile_world = 1u; // no image: the pass fields of DevParams stay unread
+    rp.max_depth = p->max_depth; rp.t_min = p->t_min; rp.seed = p->seed; rp.flags = p->flags;
+    DevParams P = dev_params(s, &rp);
+    P.samples = reinterpret_cast<Rad3 *>(d_scratch);
+    DevLights L;
+    DevEnv E;
+    dev_lighting(s, m.nee, m.env, m.env_select_p, L, E);
+    GatherBatch B{};
+    B.points = reinterpret_cast<const float *>(d_points);
+    B.normals = p->mode == RTMI_GATHER_COSINE ? reinterpret_cast<const float *>(d_normals) : nullptr;
+    B.time = reinterpret_cast<const float *>(d_time);
+    B.value = reinterpret_cast<float *>(d_value);
+    B.stderr_out = reinterpret_cast<float *>(d_stderr);
+    B.sh = reinterpret_cast<float *>(d_sh);
+    B.queue = s->status + RTMI_STATUS_WORDS;
+    B.n = count; B.spp = p->spp; B.total = count * p->spp;
+    B.first_point = (uint32_t)(p->first_point + at); B.first_sample = p->first_sample;
+    // chunks as radiance_enqueue sizes them
+    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
+    const uint32_t share = (uint32_t)(((uint64_t)B.total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
+    B.chunk = share < 64u ? 64u : (share > RTMI_RADIANCE_CHUNK ? RTMI_RADIANCE_CHUNK : share);
+    B.nchunks = (B.total + B.chunk - 1u) / B.chunk;
+    const rtmi_query_params q{count, p->flags & RTMI_FLAG_FAST_CULL, 0ull, 0ull};
+    HIP_TRY(hipMemsetAsync(B.queue, 0, sizeof(unsigned int), stream));
+    HIP_TRY(rtmi_gather_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, p->mode, B.nchunks < slots ? B.nchunks : slots,
+                               stream, s->dev, P, B, L, E));
+    if (d_value || d_stderr || d_sh) HIP_TRY(rtmi_gather_launch_resolve(p->mode, stream, P.samples, B, P.key0, P.key1));
+    return RTMI_OK;
+}
+extern "C" int rtmi_gather(rtmi_scene *s, const rtmi_gather_params *p, const float *points, const float *normals, const float *time,
+                           float *out_value, float *out_stderr, float *out_sh, double *kernel_ms) {
+    const char *name = "rtmi_gather";
+    int rc;
+    if ((rc = gather_check(name, p, points, normals, out_value || out_stderr || out_sh, out_sh != nullptr, "every output is NULL")))
+        return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (p->n && (rc = gather_check_points(name, p, points, normals, time))) return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = gather_estimator(name, p, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    if (p->n == 0u) return RTMI_OK;
+    RenderCall c;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    const bool cosine = p->mode == RTMI_GATHER_COSINE;
+    const uint32_t slab = gather_slab(p, p->slab_points ? p->slab_points : (256ull << 20) / (12ull * p->spp));
+    const size_t cap = slab < p->n ? slab : p->n; // points of the largest slab
+    // a slab's records go through the query buffers: points | normals in q_rays, times in q_time; its outputs through rad_out
+    if ((rc = grow(s, s->q_rays, s->q_rays_bytes, cap * 6 * sizeof(float))) ||
+        (time && (rc = grow(s, s->q_time, s->q_time_bytes, cap * sizeof(float)))) ||
+        (rc = grow(s, s->rad_samples, s->rad_samples_bytes, cap * p->spp * sizeof(Rad3))) ||
+        (rc = grow(s, s->rad_out, s->rad_out_bytes, cap * 33 * sizeof(float))))
+        return rc;
+    float *d_points = reinterpret_cast<float *>(s->q_rays), *d_normals = d_points + cap * 3;
+    float *d_value = s->rad_out, *d_stderr = s->rad_out + cap * 3, *d_sh = s->rad_out + cap * 6;
+    for (uint64_t at = 0; at < p->n; at += slab) {
+        const size_t cnt = p->n - at < slab ? (size_t)(p->n - at) : slab;
+        HIP_TRY(hipMemcpyAsync(d_points, points + 3 * at, cnt * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (cosine) HIP_TRY(hipMemcpyAsync(d_normals, normals + 3 * at, cnt * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (time) HIP_TRY(hipMemcpyAsync(s->q_time, time + at, cnt * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(s->ev[0], stream));
+        if ((rc = gather_enqueue(s, m, p, stream, (uint32_t)at, (uint32_t)cnt, d_points, d_normals, time ? s->q_time : nullptr,
+                                 out_value ? d_value : nullptr, out_stderr ? d_stderr : nullptr, out_sh ? d_sh : nullptr, s->rad_samples)))
+            return rc;
+        HIP_TRY(hipEventRecord(s->ev[1], stream));
+        if (out_value) HIP_TRY(hipMemcpyAsync(out_value + 3 * at, d_value, cnt * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr + 3 * at, d_stderr, cnt * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (out_sh) HIP_TRY(hipMemcpyAsync(out_sh + 27 * at, d_sh, cnt * 27 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (kernel_ms) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+            *kernel_ms += (double)ms;
+        }
+    }
+    return RTMI_OK;
+}
+extern "C" int rtmi_gather_device(rtmi_scene *s, const rtmi_gather_params *p, const void *d_points, const void *d_normals,
+                                  const void *d_time, void *d_value, void *d_stderr, void *d_sh, void *d_scratch,
+                                  uint64_t scratch_bytes, void *stream_) {
+    const char *name = "rtmi_gather_device";
+    if (int rc = gather_check(name, p, d_points, d_normals, d_value || d_stderr || d_sh, d_sh != nullptr, "every output is NULL")) return rc;
+    if (p->n && (!d_scratch || scratch_bytes < 12ull * p->spp))
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": d_scratch must hold one point's samples, scratch_bytes >= 12 * spp");
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = gather_estimator(name, p, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    if (p->n == 0u) return RTMI_OK;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = radiance_attached(m, s)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    BusyMark busy_mark{s, stream};
+    const uint64_t fits = scratch_bytes / (12ull * p->spp);
+    const uint32_t slab = gather_slab(p, p->slab_points && p->slab_points < fits ? p->slab_points : fits);
+    const char *pts = reinterpret_cast<const char *>(d_points), *nrm = reinterpret_cast<const char *>(d_normals);
+    const char *tm = reinterpret_cast<const char *>(d_time);
+    char *val = reinterpret_cast<char *>(d_value), *se = reinterpret_cast<char *>(d_stderr), *sh = reinterpret_cast<char *>(d_sh);
+    for (uint64_t at = 0; at < p->n; at += slab) {
+        const uint32_t cnt = p->n - at < slab ? (uint32_t)(p->n - at) : slab;
+        if (int rc = gather_enqueue(s, m, p, stream, (uint32_t)at, cnt, pts + 12 * at, nrm ? nrm + 12 * at : nullptr,
+                                    tm ? tm + 4 * at : nullptr, val ? val + 12 * at : nullptr, se ? se + 12 * at : nullptr,
+                                    sh ? sh + 108 * at : nullptr, d_scratch))
+            return rc;
+    }
+    return RTMI_OK;
 }
 
 // ---- next-event estimation (include/rtmi_nee.h) -------------------------------------------------------------------------

@@ -740,6 +740,80 @@ class Scene:
             se = np.full((n, 3), np.inf)
         return {"irradiance": (np.pi * mean).astype(np.float32), "stderr": (np.pi * se).astype(np.float32)}
 
+    def gather(self, points, normals=None, spp=16, mode="cosine", estimator="plain", seed=0, first_point=0, first_sample=0,
+               slab_points=0, times=None, flags=abi.RTMI_FLAG_FAST_CULL, max_depth=50, t_min=0.001, env_select_p=0.5, sh=True,
+               scratch_bytes=None):
+        """Light arriving at points (include/rtmi_gather.h): the device draws spp directions per point, traces one
+        radiance() path along each and reduces per point; no ray is built on the host.  mode "cosine": points and normals
+        [n, 3] (any length), value = the irradiance E = pi * mean over cosine-distributed directions.  mode "sphere":
+        points only, value = the mean radiance over uniform directions and, with sh=True, sh [n, 9, 3]: its projection on
+        the real spherical harmonics of bands 0..2 (sh_irradiance convolves it).  Path (i, s) is radiance()'s of the ray
+        (points[i], gather_directions(...)[i, s]) with first_ray = first_point + i, first_sample + s, stream_skip = 0,
+        t_min = path_t_min = t_min, bit for bit.  slab_points: points traced per launch (0: 256 MiB of samples); no output bit
+        depends on it.  Returns dict(value f32 [n, 3], stderr f32 [n, 3] (+inf for spp = 1), kernel_ms[, sh]).
+        With torch tensors on the scene's device the call is enqueued on torch's current stream (rtmi_gather_device) and
+        returns torch tensors on that device: no host copy is made; its per-sample scratch is a torch allocation of
+        scratch_bytes (default: one slab's).  A scene resident on a device list raises Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        if mode not in abi.GATHER_MODES:
+            raise ValueError("mode must be one of %s" % ", ".join(sorted(abi.GATHER_MODES)))
+        cosine = mode == "cosine"
+        if cosine and normals is None:
+            raise ValueError("mode 'cosine' needs normals")
+        self._ready({}, lights=estimator in ("nee", "env_nee"))
+        n, spp = int(points.shape[0]), int(spp)
+        want_sh = bool(sh) and not cosine
+        p = abi.GatherParams(n, spp, abi.GATHER_MODES[mode], abi.ROULETTE_ESTIMATORS[estimator], int(flags), int(max_depth),
+                             float(t_min), int(seed) & (2 ** 64 - 1), int(first_point) & (2 ** 64 - 1), int(first_sample),
+                             int(slab_points), float(env_select_p))
+        if hasattr(points, "data_ptr") and hasattr(points, "is_cuda"):
+            return self._gather_torch(p, points, normals if cosine else None, times, want_sh, scratch_bytes)
+        pts = np.ascontiguousarray(points, dtype=np.float32)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32) if cosine else None
+        if pts.ndim != 2 or pts.shape[1] != 3 or (cosine and nrm.shape != pts.shape):
+            raise ValueError("points and normals are [n, 3] arrays")
+        tm = None if times is None else np.ascontiguousarray(np.broadcast_to(np.asarray(times, np.float32), (n,)))
+        ms = C.c_double(0.0)
+        res = {"value": np.zeros((n, 3), np.float32), "stderr": np.zeros((n, 3), np.float32)}
+        if want_sh:
+            res["sh"] = np.zeros((n, 9, 3), np.float32)
+        self.host._check(self.host.lib.rth_gather(self.h, C.byref(p), pts.ctypes.data, nrm.ctypes.data if cosine else None,
+                                                   None if tm is None else tm.ctypes.data, res["value"].ctypes.data,
+                                                   res["stderr"].ctypes.data, res["sh"].ctypes.data if want_sh else None,
+                                                   C.byref(ms)))
+        res["kernel_ms"] = ms.value
+        return res
+
+    def _gather_torch(self, p, points, normals, times, want_sh, scratch_bytes):
+        import torch
+
+        dev = points.device
+        if dev.type != "cuda" or (dev.index or 0) != self.device:
+            raise ValueError("the points are on %s, the scene is on device %d" % (dev, self.device))
+        for a in (points,) if normals is None else (points, normals):
+            if a.dtype != torch.float32 or a.dim() != 2 or a.shape != (p.n, 3) or a.device != dev:
+                raise ValueError("points and normals are float32 [n, 3] tensors on one device")
+        pts = points.contiguous()
+        nrm = None if normals is None else normals.contiguous()
+        tm = None if times is None else torch.as_tensor(times, dtype=torch.float32, device=dev).expand(p.n).contiguous()
+        if scratch_bytes is None:  # one slab of the host form's size, or the whole batch if that is smaller
+            slab = p.slab_points or max((256 << 20) // (12 * max(p.spp, 1)), 1)
+            scratch_bytes = 12 * max(p.spp, 1) * max(min(slab, p.n), 1)
+        scratch_bytes = int(scratch_bytes)
+        scratch = torch.empty(((scratch_bytes + 3) // 4,), dtype=torch.float32, device=dev)
+        res = {"value": torch.empty((p.n, 3), dtype=torch.float32, device=dev),
+               "stderr": torch.empty((p.n, 3), dtype=torch.float32, device=dev)}
+        if want_sh:
+            res["sh"] = torch.empty((p.n, 9, 3), dtype=torch.float32, device=dev)
+        # every check of the entry is made for an empty batch too; it then launches nothing
+        self.host._check(self.host.lib.rth_gather_device(
+            self.h, C.byref(p), C.c_void_p(pts.data_ptr()), C.c_void_p(nrm.data_ptr()) if nrm is not None else None,
+            C.c_void_p(tm.data_ptr()) if tm is not None else None, C.c_void_p(res["value"].data_ptr()),
+            C.c_void_p(res["stderr"].data_ptr()), C.c_void_p(res["sh"].data_ptr()) if want_sh else None,
+            C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch_bytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
+
 
 IRRADIANCE_STREAM = 5  # the Philox stream id of irradiance()'s directions (0 path, 2 scene, 3 light samples, 4 roulette)
 
@@ -768,6 +842,52 @@ def irradiance_directions(normals, spp, seed=0):
     d = x[..., None] * t[:, None, :] + y[..., None] * b[:, None, :] + z[..., None] * nrm[:, None, :]
     d /= np.linalg.norm(d, axis=2, keepdims=True)
     return np.ascontiguousarray(d.astype(np.float32))
+
+
+def gather_directions(normals, spp, seed=0, mode="cosine", first_point=0, first_sample=0, n=None):
+    """Scene.gather's directions (rtmi_gather_directions, include/rtmi_gather.h): float32 [n, spp, 3], computed on the host
+    by the inline functions the kernels compile.  mode "cosine": about each of normals [n, 3]; mode "sphere": uniform, for n
+    points (normals is not read).  Needs no GPU."""
+    if mode not in abi.GATHER_MODES:
+        raise ValueError("mode must be one of %s" % ", ".join(sorted(abi.GATHER_MODES)))
+    nrm = None
+    if mode == "cosine":
+        nrm = np.ascontiguousarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[1] != 3:
+            raise ValueError("normals is an [n, 3] array, not %r" % (nrm.shape,))
+        n = nrm.shape[0]
+    elif n is None:
+        n = int(np.asarray(normals).shape[0])
+    p = abi.GatherParams(int(n), int(spp), abi.GATHER_MODES[mode], 0, 0, 1, 0.001, int(seed) & (2 ** 64 - 1),
+                         int(first_point) & (2 ** 64 - 1), int(first_sample), 0, 0.5)
+    out = np.zeros((int(n), max(int(spp), 0), 3), np.float32)
+    lib = abi.load_rtmi()
+    if lib.rtmi_gather_directions(C.byref(p), None if nrm is None else nrm.ctypes.data, int(n), out.ctypes.data):
+        raise ValueError((lib.rtmi_last_error() or b"").decode())
+    return out
+
+
+SH_COSINE_LOBE = (np.pi, 2.0 * np.pi / 3.0, np.pi / 4.0)  # A_l of bands 0..2: the clamped-cosine kernel's zonal factors
+
+
+def sh_basis(directions):
+    """The nine real spherical harmonics of include/rtmi_gather.h at unit directions [..., 3], float64 [..., 9]."""
+    d = np.asarray(directions, np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    c0, c1, c2, c20, c22 = 0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
+    return np.stack([np.full_like(x, c0), c1 * y, c1 * z, c1 * x, c2 * x * y, c2 * y * z, c20 * (3.0 * z * z - 1.0), c2 * x * z,
+                     c22 * (x * x - y * y)], axis=-1)
+
+
+def sh_irradiance(sh, normals):
+    """Irradiance from SH probes (Ramamoorthi and Hanrahan 2001): sh [n, 9, 3] of Scene.gather(mode="sphere"), normals
+    [n, 3] (any length) -> float64 [n, 3]: sum_k A_band(k) sh[k] Y_k(normal), the probe's radiance convolved with the
+    cosine lobe A = (pi, 2 pi / 3, pi / 4).  numpy."""
+    sh = np.asarray(sh, np.float64)
+    nrm = np.asarray(normals, np.float64)
+    nrm = nrm / np.linalg.norm(nrm, axis=-1, keepdims=True)
+    a = np.array([SH_COSINE_LOBE[0]] + [SH_COSINE_LOBE[1]] * 3 + [SH_COSINE_LOBE[2]] * 5)
+    return np.einsum("...k,...kc->...c", sh_basis(nrm) * a, sh)
 
 
 # rtmi_light_node and rtmi_light_path (include/rtmi_light_tree.h) as numpy sees them

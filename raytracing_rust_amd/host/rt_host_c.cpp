@@ -16,6 +16,7 @@
 #include "rtmi_session.h"
 #include "rtmi_query.h"
 #include "rtmi_radiance.h"
+#include "rtmi_gather.h"
 
 using namespace rt;
 
@@ -341,6 +342,25 @@ RTH_API int rth_radiance_device(void *lowered, const rtmi_radiance_params *p, co
     return guard([&] {
         const char *name = "rtmi_radiance_device";
         return done(name, rtmi_radiance_device(DEV(lowered, name, "radiance-query"), p, d_rays, d_time, d_mean, d_stderr, d_samples, stream),
+                    CODED_UNSUPPORTED);
+    });
+}
+// hemisphere gathers (include/rtmi_gather.h) on the uploaded handle, as the radiance queries
+RTH_API int rth_gather(void *lowered, const rtmi_gather_params *p, const float *points, const float *normals, const float *time,
+                       float *out_value, float *out_stderr, float *out_sh, double *kernel_ms) {
+    return guard([&] {
+        const char *name = "rtmi_gather";
+        return done(name, rtmi_gather(DEV(lowered, name, "gather"), p, points, normals, time, out_value, out_stderr, out_sh, kernel_ms),
+                    CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_gather_device(void *lowered, const rtmi_gather_params *p, const void *d_points, const void *d_normals,
+                              const void *d_time, void *d_value, void *d_stderr, void *d_sh, void *d_scratch, uint64_t scratch_bytes,
+                              void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_gather_device";
+        return done(name, rtmi_gather_device(DEV(lowered, name, "gather"), p, d_points, d_normals, d_time, d_value, d_stderr, d_sh,
+                                             d_scratch, scratch_bytes, stream),
                     CODED_UNSUPPORTED);
     });
 }
