@@ -928,3 +928,54 @@ extern "C" {
         out_dirs: *mut f32,
     ) -> c_int;
 }
+
+// ---- include/rtmi_temporal.h: temporal accumulation -------------------------------------------------------------------
+
+pub const RTMI_TEMPORAL_NO_DEMODULATE: u32 = 1;
+
+/// rtmi_temporal_params: the settings of a temporal history (32 bytes); defaults 32, 0, 0.05, 0.9, 1e-3, 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiTemporalParams {
+    pub max_history: u32,
+    pub alpha_min: f32,
+    pub depth_tol: f32,
+    pub normal_min: f32,
+    pub albedo_min: f32,
+    pub flags: u32,
+    pub reserved: [u32; 2],
+}
+
+/// opaque device-resident history of one image size on one device (rtmi_temporal.h: rtmi_temporal)
+#[repr(C)]
+pub struct RtmiTemporal {
+    _private: [u8; 0],
+}
+
+extern "C" {
+    pub fn rtmi_temporal_create(
+        device: c_int,
+        nx: u32,
+        ny: u32,
+        params: *const RtmiTemporalParams,
+        out: *mut *mut RtmiTemporal,
+    ) -> c_int;
+    /// blocking, host pointers; linear, albedo, normal ny * nx * 3 floats, depth ny * nx floats, stderr_rgb ny * nx * 3
+    /// floats or NULL; out_linear, out_stderr ny * nx * 3 floats, out_history ny * nx, out_motion ny * nx * 2, each optional
+    pub fn rtmi_temporal_push(
+        h: *mut RtmiTemporal,
+        cam: *const RtmiCamera,
+        linear: *const f32,
+        albedo: *const f32,
+        normal: *const f32,
+        depth: *const f32,
+        stderr_rgb: *const f32,
+        out_linear: *mut f32,
+        out_stderr: *mut f32,
+        out_history: *mut f32,
+        out_motion: *mut f32,
+    ) -> c_int;
+    /// forgets the previous frame, keeps the allocation
+    pub fn rtmi_temporal_reset(h: *mut RtmiTemporal) -> c_int;
+    pub fn rtmi_temporal_destroy(h: *mut RtmiTemporal);
+}

@@ -309,6 +309,18 @@ class GatherParams(C.Structure):
 # the functions of include/rtmi_gather.h (hemisphere gathers), kept apart from those of the other headers
 RTMI_GATHER_SYMBOLS = ["rtmi_gather", "rtmi_gather_device", "rtmi_gather_directions"]
 
+RTMI_TEMPORAL_NO_DEMODULATE = 1  # include/rtmi_temporal.h: accumulate the colour itself, not colour / albedo
+
+
+class TemporalParams(C.Structure):
+    """rtmi_temporal_params (include/rtmi_temporal.h): the settings of a temporal history (32 bytes)."""
+    _fields_ = [("max_history", C.c_uint32), ("alpha_min", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
+                ("albedo_min", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# the functions of include/rtmi_temporal.h (temporal accumulation), kept apart from those of the other headers
+RTMI_TEMPORAL_SYMBOLS = ["rtmi_temporal_create", "rtmi_temporal_destroy", "rtmi_temporal_push", "rtmi_temporal_reset"]
+
 _rtmi = None
 _host = None
 
@@ -460,6 +472,14 @@ def load_rtmi():
     lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
     lib.rtmi_probe_expf.restype = C.c_int
     lib.rtmi_probe_expf.argtypes = [C.c_int, vp, vp, C.c_uint32]
+    lib.rtmi_temporal_create.restype = C.c_int
+    lib.rtmi_temporal_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), C.POINTER(vp)]
+    lib.rtmi_temporal_push.restype = C.c_int
+    lib.rtmi_temporal_push.argtypes = [vp, C.POINTER(Camera), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.rtmi_temporal_reset.restype = C.c_int
+    lib.rtmi_temporal_reset.argtypes = [vp]
+    lib.rtmi_temporal_destroy.restype = None
+    lib.rtmi_temporal_destroy.argtypes = [vp]
     _rtmi = lib
     return lib
 

@@ -502,6 +502,29 @@ class Scene:
                        device=self.device, **(denoise or {}))
         return {"linear": out["linear"], "rgb8": out["rgb8"], "noisy": noisy, "features": ft}
 
+    def render_temporal(self, temporal, cam, nx, ny, ns, denoise=None, nee=False, env=False, coop=False, **kw):
+        """One frame of a sequence: render_denoised's two renders, then temporal.push (a Temporal of this size) of the
+        noisy image, its standard errors and the features under `cam`, then denoise() of the pushed linear and stderr
+        with this frame's features.  Returns render_denoised's dict plus accumulated = the push's dict.  denoise=False
+        skips the filter: linear is the accumulated image and rgb8 its quantisation (denoise() with iterations=0)."""
+        if ns < 2:
+            raise ValueError("render_temporal needs ns >= 2 (a standard error needs two samples)")
+        if coop and not (nee or env):
+            raise ValueError("coop=True needs nee=True or env=True: the plain adaptive render is cooperative by default")
+        if env:
+            noisy = self.render_env(cam, nx, ny, ns, nee=nee, coop=coop, **kw)
+            kw.pop("env_select_p", None)
+        elif nee:
+            noisy = self.render_nee(cam, nx, ny, ns, coop=coop, **kw)
+        else:
+            noisy = self.render_adaptive(cam, nx, ny, ns, min_spp=ns, step_spp=1, **kw)
+        kw.pop("device", None)
+        ft = self.render_features(cam, nx, ny, ns, **kw)
+        acc = temporal.push(cam, noisy["linear"], ft["albedo"], ft["normal"], ft["depth"], stderr=noisy["stderr"])
+        opts = {"iterations": 0} if denoise is False else (denoise or {})
+        out = _denoise(acc["linear"], ft["albedo"], ft["normal"], ft["depth"], stderr=acc["stderr"], device=self.device, **opts)
+        return {"linear": out["linear"], "rgb8": out["rgb8"], "noisy": noisy, "features": ft, "accumulated": acc}
+
     def render_multi(self, cam, nx, ny, ns, devices, **kw):
         """Whole image on several GPUs of this process (rtmi_render_multi): tiles t % len(devices), one gather.
         A device may be listed more than once (single-GPU rehearsal).  Bit-identical to render()."""
@@ -1084,6 +1107,8 @@ class Host:
     def free_all(self):
         for ses in list(getattr(self, "_sessions", [])):  # sessions before their scenes
             ses.close()
+        for tmp in list(_temporals):
+            tmp.close()
         self.lib.rth_free_all()
 
     # ---- textures (src/texture.rs) ----
@@ -1286,6 +1311,80 @@ def denoise(linear, albedo, normal, depth, stderr=None, iterations=5, normal_pow
 
 
 _denoise = denoise
+
+_temporals = []  # the open Temporal handles; Host.free_all() closes them
+
+
+class Temporal:
+    """The device-resident temporal history of include/rtmi_temporal.h for nx x ny images on `device`: push() reprojects
+    the frames pushed so far into the new frame's camera and blends them with it.  demodulate=False sets
+    RTMI_TEMPORAL_NO_DEMODULATE.  close() frees its device memory (184 B per pixel); Host.free_all() closes what is
+    still open.  HostError for what rtmi_temporal_create refuses."""
+
+    def __init__(self, nx, ny, device=0, max_history=32, alpha_min=0.0, depth_tol=0.05, normal_min=0.9, albedo_min=1e-3,
+                 demodulate=True):
+        self.lib = abi.load_rtmi()
+        self.nx, self.ny, self.device, self.h = int(nx), int(ny), device, None
+        p = abi.TemporalParams(max_history, alpha_min, depth_tol, normal_min, albedo_min,
+                               0 if demodulate else abi.RTMI_TEMPORAL_NO_DEMODULATE)
+        h = C.c_void_p()
+        self._check(self.lib.rtmi_temporal_create(device, self.nx, self.ny, C.byref(p), C.byref(h)), "rtmi_temporal_create")
+        self.h = h
+        _temporals.append(self)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, self.lib.rtmi_last_error().decode()))
+
+    def _handle(self):
+        if not self.h:
+            raise HostError("the temporal history is closed")
+        return self.h
+
+    def push(self, cam, linear, albedo, normal, depth, stderr=None, motion=False):
+        """One frame: cam is the camera it was rendered with (a Camera of Host or an abi.Camera); linear, albedo, normal
+        (and stderr, or None) are float32 [ny,nx,3], depth is float32 [ny,nx] (non-finite = no surface), row 0 the top row.
+        Returns dict(linear f32 [ny,nx,3], stderr f32 [ny,nx,3] or None, history f32 [ny,nx][, motion f32 [ny,nx,2]]):
+        linear and stderr are what denoise() takes.  ValueError for a shape or dtype mismatch, HostError for what
+        rtmi_temporal_push refuses (a stderr given on some pushes and not on others, a singular camera)."""
+        h = self._handle()
+        c = cam.lower() if hasattr(cam, "lower") else cam
+        ny, nx = self.ny, self.nx
+        planes = {"linear": linear, "albedo": albedo, "normal": normal, "depth": depth}
+        if stderr is not None:
+            planes["stderr"] = stderr
+        for name, a in planes.items():
+            a = np.asarray(a)
+            want = (ny, nx) if name == "depth" else (ny, nx, 3)
+            if a.shape != want:
+                raise ValueError("%s must have the shape %r, not %r" % (name, want, a.shape))
+            if a.dtype != np.float32:
+                raise ValueError("%s must be float32, not %s" % (name, a.dtype))
+            planes[name] = np.ascontiguousarray(a)
+        out = {"linear": np.zeros((ny, nx, 3), np.float32),
+               "stderr": np.zeros((ny, nx, 3), np.float32) if stderr is not None else None,
+               "history": np.zeros((ny, nx), np.float32)}
+        if motion:
+            out["motion"] = np.zeros((ny, nx, 2), np.float32)
+        rc = self.lib.rtmi_temporal_push(h, C.byref(c), planes["linear"].ctypes.data, planes["albedo"].ctypes.data,
+                                         planes["normal"].ctypes.data, planes["depth"].ctypes.data,
+                                         planes["stderr"].ctypes.data if stderr is not None else None,
+                                         out["linear"].ctypes.data,
+                                         out["stderr"].ctypes.data if stderr is not None else None,
+                                         out["history"].ctypes.data, out["motion"].ctypes.data if motion else None)
+        self._check(rc, "rtmi_temporal_push")
+        return out
+
+    def reset(self):
+        """Forgets the frames pushed so far; the next push is a first push."""
+        self._check(self.lib.rtmi_temporal_reset(self._handle()), "rtmi_temporal_reset")
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            if self in _temporals:
+                _temporals.remove(self)
+            self.lib.rtmi_temporal_destroy(h)
 
 
 def pfm_bytes(plane):
