@@ -979,3 +979,87 @@ extern "C" {
     pub fn rtmi_temporal_reset(h: *mut RtmiTemporal) -> c_int;
     pub fn rtmi_temporal_destroy(h: *mut RtmiTemporal);
 }
+
+// ---- include/rtmi_frame.h: the device-resident frame pipeline ---------------------------------------------------------
+
+pub const RTMI_FRAME_NO_TEMPORAL: u32 = 1;
+pub const RTMI_FRAME_NO_FILTER: u32 = 2;
+
+/// rtmi_frame_opts: the estimator (RTMI_ROULETTE_* numbering) and the embedded temporal and filter settings (96 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiFrameOpts {
+    pub estimator: u32,
+    pub env_select_p: f32,
+    pub temporal: RtmiTemporalParams,
+    pub denoise: RtmiDenoiseParams,
+    pub flags: u32,
+    pub reserved: [u32; 5],
+}
+
+/// rtmi_frame_out: the planes of a frame, host pointers (rtmi_frame_render) or device pointers
+/// (rtmi_frame_render_device); a NULL plane is not copied (96 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiFrameOut {
+    pub linear: *mut f32,
+    pub rgb8: *mut u8,
+    pub noisy_linear: *mut f32,
+    pub noisy_stderr: *mut f32,
+    pub albedo: *mut f32,
+    pub normal: *mut f32,
+    pub depth: *mut f32,
+    pub hits: *mut u32,
+    pub accum_linear: *mut f32,
+    pub accum_stderr: *mut f32,
+    pub history: *mut f32,
+    pub motion: *mut f32,
+}
+
+/// opaque frame handle
+#[repr(C)]
+pub struct RtmiFrame {
+    _private: [u8; 0],
+}
+
+extern "C" {
+    /// params fixes nx, ny, max_depth, t_min and flags; its ns and seed are not read
+    pub fn rtmi_frame_create(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiFrameOpts,
+        out: *mut *mut RtmiFrame,
+    ) -> c_int;
+    /// blocking; renders, accumulates and filters one frame and copies the planes asked for to the host
+    pub fn rtmi_frame_render(
+        frame: *mut RtmiFrame,
+        cam: *const RtmiCamera,
+        ns: u32,
+        seed: u64,
+        out: *const RtmiFrameOut,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the same with device pointers in `out`; blocking too
+    pub fn rtmi_frame_render_device(
+        frame: *mut RtmiFrame,
+        cam: *const RtmiCamera,
+        ns: u32,
+        seed: u64,
+        out: *const RtmiFrameOut,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// forgets the frames rendered so far, keeps the allocation
+    pub fn rtmi_frame_reset(frame: *mut RtmiFrame) -> c_int;
+    pub fn rtmi_frame_destroy(frame: *mut RtmiFrame);
+    /// the un-tiling kernel on the caller's host data, for tests
+    pub fn rtmi_probe_frame_untile(
+        device: c_int,
+        nx: u32,
+        ny: u32,
+        tiled: *const RtmiTexel,
+        tiled_stderr: *const f32,
+        out_linear: *mut f32,
+        out_stderr: *mut f32,
+        poisoned: *mut u32,
+    ) -> c_int;
+}

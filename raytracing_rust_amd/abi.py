@@ -321,6 +321,26 @@ class TemporalParams(C.Structure):
 # the functions of include/rtmi_temporal.h (temporal accumulation), kept apart from those of the other headers
 RTMI_TEMPORAL_SYMBOLS = ["rtmi_temporal_create", "rtmi_temporal_destroy", "rtmi_temporal_push", "rtmi_temporal_reset"]
 
+RTMI_FRAME_NO_TEMPORAL = 1  # include/rtmi_frame.h: no history, the chain render, features, filter
+RTMI_FRAME_NO_FILTER = 2  # the filter runs with 0 iterations: the accumulated image and its quantisation
+
+
+class FrameOpts(C.Structure):
+    """rtmi_frame_opts (include/rtmi_frame.h): the estimator and the embedded temporal and filter settings (96 bytes)."""
+    _fields_ = [("estimator", C.c_uint32), ("env_select_p", C.c_float), ("temporal", TemporalParams), ("denoise", DenoiseParams),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class FrameOut(C.Structure):
+    """rtmi_frame_out (include/rtmi_frame.h): the planes of a frame, host or device pointers, NULL = not copied (96 bytes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("linear", "rgb8", "noisy_linear", "noisy_stderr", "albedo", "normal", "depth", "hits",
+                                          "accum_linear", "accum_stderr", "history", "motion")]
+
+
+# the functions of include/rtmi_frame.h (the frame pipeline), kept apart from those of the other headers
+RTMI_FRAME_SYMBOLS = ["rtmi_frame_create", "rtmi_frame_destroy", "rtmi_frame_render", "rtmi_frame_render_device",
+                      "rtmi_frame_reset", "rtmi_probe_frame_untile"]
+
 _rtmi = None
 _host = None
 
@@ -480,6 +500,17 @@ def load_rtmi():
     lib.rtmi_temporal_reset.argtypes = [vp]
     lib.rtmi_temporal_destroy.restype = None
     lib.rtmi_temporal_destroy.argtypes = [vp]
+    lib.rtmi_frame_create.restype = C.c_int
+    lib.rtmi_frame_create.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(FrameOpts), C.POINTER(vp)]
+    for fn in (lib.rtmi_frame_render, lib.rtmi_frame_render_device):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.POINTER(Camera), C.c_uint32, C.c_uint64, C.POINTER(FrameOut), C.POINTER(Stats)]
+    lib.rtmi_frame_reset.restype = C.c_int
+    lib.rtmi_frame_reset.argtypes = [vp]
+    lib.rtmi_frame_destroy.restype = None
+    lib.rtmi_frame_destroy.argtypes = [vp]
+    lib.rtmi_probe_frame_untile.restype = C.c_int
+    lib.rtmi_probe_frame_untile.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
     _rtmi = lib
     return lib
 
@@ -558,6 +589,10 @@ def load_host():
         "rth_session_import": (i, [vp, vp, C.c_size_t]),
         "rth_session_merge": (i, [vp, vp]),
         "rth_session_spp": (i, [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+        "rth_frame_create": (vp, [vp, C.POINTER(RenderParams), C.POINTER(FrameOpts)]),
+        "rth_frame_close": (i, [vp]),
+        "rth_frame_render": (i, [vp, vp, u32, u64, C.POINTER(FrameOut), i, C.POINTER(Stats)]),
+        "rth_frame_reset": (i, [vp]),
         "rth_trace": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_occluded": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_trace_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),

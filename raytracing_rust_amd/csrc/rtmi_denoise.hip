@@ -15,6 +15,7 @@
 #include "rtmi.h"
 #include "rtmi_math.h"
 #include "rtmi_denoise.h"
+#include "rtmi_frame_launch.hpp"
 
 int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
 
@@ -183,16 +184,23 @@ __global__ void rtmi_expf_probe_kernel(const float *x, float *out, uint32_t n) {
 
 bool finite_f(float v) { return v == v && v - v == 0.0f; }
 
-int check_params(uint32_t nx, uint32_t ny, const rtmi_denoise_params *p) {
-    if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u) return rtmi_fail(RTMI_ERR_INVALID, "nx and ny must be in [1, 32768]");
-    if (p->iterations > 10u) return rtmi_fail(RTMI_ERR_INVALID, "iterations must be in [0, 10]");
+// the RTMI_ERR_INVALID checks, each message after `pre` (empty for rtmi_denoise, the entry's name for the frame handle)
+int check_ranges(const std::string &pre, uint32_t nx, uint32_t ny, const rtmi_denoise_params *p) {
+    const auto bad = [&](const char *msg) { return rtmi_fail(RTMI_ERR_INVALID, (pre + msg).c_str()); };
+    if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u) return bad("nx and ny must be in [1, 32768]");
+    if (p->iterations > 10u) return bad("iterations must be in [0, 10]");
     if (p->normal_power > 1024u || (p->normal_power & (p->normal_power - 1u)))
-        return rtmi_fail(RTMI_ERR_INVALID, "normal_power must be 0 or a power of two <= 1024");
+        return bad("normal_power must be 0 or a power of two <= 1024");
     if (!finite_f(p->sigma_l) || !(p->sigma_l >= 0.0f) || !finite_f(p->sigma_z) || !(p->sigma_z >= 0.0f))
-        return rtmi_fail(RTMI_ERR_INVALID, "sigma_l and sigma_z must be finite and >= 0");
+        return bad("sigma_l and sigma_z must be finite and >= 0");
     if (!finite_f(p->eps_l) || !(p->eps_l > 0.0f) || !finite_f(p->eps_z) || !(p->eps_z > 0.0f) ||
         !finite_f(p->albedo_min) || !(p->albedo_min > 0.0f))
-        return rtmi_fail(RTMI_ERR_INVALID, "eps_l, eps_z and albedo_min must be finite and > 0");
+        return bad("eps_l, eps_z and albedo_min must be finite and > 0");
+    return RTMI_OK;
+}
+
+int check_params(uint32_t nx, uint32_t ny, const rtmi_denoise_params *p) {
+    if (int rc = check_ranges("", nx, ny, p)) return rc;
     if (p->flags) return rtmi_fail(RTMI_ERR_UNSUPPORTED, "flags must be 0 (reserved)");
     return RTMI_OK;
 }
@@ -235,6 +243,50 @@ struct Stream {
 
 } // namespace
 
+// ---- the device half, shared with the frame handle (rtmi_frame_launch.hpp) --------------------------------------------
+int rtmi_denoise_check_ranges(const char *prefix, uint32_t nx, uint32_t ny, const rtmi_denoise_params *p) {
+    return check_ranges(prefix, nx, ny, p);
+}
+
+size_t rtmi_denoise_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t iterations) {
+    const size_t n = (size_t)nx * ny;
+    return iterations > 0 ? 3 * Scratch::round(n * 16) + Scratch::round(n * 8) : 0;
+}
+
+hipError_t rtmi_denoise_launch(hipStream_t stream, uint32_t nx, uint32_t ny, const rtmi_denoise_params &p, const float *linear,
+                               const float *albedo, const float *normal, const float *depth, const float *se, void *scratch,
+                               float *out, uint8_t *rgb8) {
+    const size_t n = (size_t)nx * ny;
+    const bool lum = se != nullptr, filter = p.iterations > 0;
+    Scratch m;
+    m.base = static_cast<char *>(scratch);
+    float4 *st[2] = {filter ? m.take<float4>(n) : nullptr, filter ? m.take<float4>(n) : nullptr};
+    float4 *d_guide = filter ? m.take<float4>(n) : nullptr;
+    float2 *d_grad = filter ? m.take<float2>(n) : nullptr;
+    m.base = nullptr; // the caller's memory
+    hipError_t e;
+    int cur = 0;
+    if (filter) {
+        const dim3 block(kBlock, kBlock), grid((nx + kBlock - 1) / kBlock, (ny + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(rtmi_denoise_prepass_kernel, grid, block, 0, stream, linear, albedo, normal, depth, se, st[0],
+                           d_guide, d_grad, nx, ny, p.albedo_min);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        DenoiseIter P{nx, ny, 1, 0, p.normal_power != 0u, p.sigma_l, p.sigma_z, p.eps_l, p.eps_z};
+        for (uint32_t pw = p.normal_power; pw > 1u; pw >>= 1) P.squarings++;
+        for (uint32_t i = 0; i < p.iterations; i++, cur ^= 1) {
+            P.step = 1 << i;
+            if (lum)
+                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<true>, grid, block, 0, stream, st[cur], st[cur ^ 1], d_guide, d_grad, P);
+            else
+                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<false>, grid, block, 0, stream, st[cur], st[cur ^ 1], d_guide, d_grad, P);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+    }
+    hipLaunchKernelGGL(rtmi_denoise_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st[cur], linear,
+                       albedo, depth, out, rgb8, (uint32_t)n, p.albedo_min, filter ? 0 : 1);
+    return hipGetLastError();
+}
+
 extern "C" int rtmi_denoise(int device, uint32_t nx, uint32_t ny, const rtmi_denoise_params *p, const float *linear,
                             const float *albedo, const float *normal, const float *depth, const float *stderr_rgb,
                             float *out_linear, uint8_t *out_rgb8) {
@@ -249,16 +301,14 @@ extern "C" int rtmi_denoise(int device, uint32_t nx, uint32_t ny, const rtmi_den
     const size_t n = (size_t)nx * ny;
     const bool lum = stderr_rgb != nullptr, filter = p->iterations > 0;
     Scratch m;
-    const size_t f3 = Scratch::round(n * 12), f1 = Scratch::round(n * 4), f4 = Scratch::round(n * 16),
-                 f2 = Scratch::round(n * 8), b3 = Scratch::round(n * 3);
-    const size_t bytes = 3 * f3 + f1 + (lum ? f3 : 0) + (filter ? 3 * f4 + f2 : 0) + f3 + b3;
+    const size_t f3 = Scratch::round(n * 12), f1 = Scratch::round(n * 4), b3 = Scratch::round(n * 3);
+    const size_t work = rtmi_denoise_scratch_bytes(nx, ny, p->iterations);
+    const size_t bytes = 3 * f3 + f1 + (lum ? f3 : 0) + work + f3 + b3;
     DN_TRY(hipMalloc(reinterpret_cast<void **>(&m.base), bytes));
     float *d_lin = m.take<float>(n * 3), *d_alb = m.take<float>(n * 3), *d_nrm = m.take<float>(n * 3);
     float *d_dep = m.take<float>(n);
     float *d_se = lum ? m.take<float>(n * 3) : nullptr;
-    float4 *st[2] = {filter ? m.take<float4>(n) : nullptr, filter ? m.take<float4>(n) : nullptr};
-    float4 *d_guide = filter ? m.take<float4>(n) : nullptr;
-    float2 *d_grad = filter ? m.take<float2>(n) : nullptr;
+    char *d_work = m.take<char>(work);
     float *d_out = m.take<float>(n * 3);
     uint8_t *d_rgb = m.take<uint8_t>(n * 3);
     Stream S;
@@ -266,28 +316,11 @@ extern "C" int rtmi_denoise(int device, uint32_t nx, uint32_t ny, const rtmi_den
     DN_TRY(hipMemcpyAsync(d_lin, linear, n * 12, hipMemcpyHostToDevice, S.s));
     DN_TRY(hipMemcpyAsync(d_alb, albedo, n * 12, hipMemcpyHostToDevice, S.s));
     DN_TRY(hipMemcpyAsync(d_dep, depth, n * 4, hipMemcpyHostToDevice, S.s));
-    int cur = 0;
     if (filter) {
         DN_TRY(hipMemcpyAsync(d_nrm, normal, n * 12, hipMemcpyHostToDevice, S.s));
         if (lum) DN_TRY(hipMemcpyAsync(d_se, stderr_rgb, n * 12, hipMemcpyHostToDevice, S.s));
-        const dim3 block(kBlock, kBlock), grid((nx + kBlock - 1) / kBlock, (ny + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(rtmi_denoise_prepass_kernel, grid, block, 0, S.s, d_lin, d_alb, d_nrm, d_dep, d_se, st[0],
-                           d_guide, d_grad, nx, ny, p->albedo_min);
-        DN_TRY(hipGetLastError());
-        DenoiseIter P{nx, ny, 1, 0, p->normal_power != 0u, p->sigma_l, p->sigma_z, p->eps_l, p->eps_z};
-        for (uint32_t pw = p->normal_power; pw > 1u; pw >>= 1) P.squarings++;
-        for (uint32_t i = 0; i < p->iterations; i++, cur ^= 1) {
-            P.step = 1 << i;
-            if (lum)
-                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<true>, grid, block, 0, S.s, st[cur], st[cur ^ 1], d_guide, d_grad, P);
-            else
-                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<false>, grid, block, 0, S.s, st[cur], st[cur ^ 1], d_guide, d_grad, P);
-            DN_TRY(hipGetLastError());
-        }
     }
-    hipLaunchKernelGGL(rtmi_denoise_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S.s, st[cur], d_lin,
-                       d_alb, d_dep, d_out, d_rgb, (uint32_t)n, p->albedo_min, filter ? 0 : 1);
-    DN_TRY(hipGetLastError());
+    DN_TRY(rtmi_denoise_launch(S.s, nx, ny, *p, d_lin, d_alb, d_nrm, d_dep, d_se, d_work, d_out, d_rgb));
     if (out_linear) DN_TRY(hipMemcpyAsync(out_linear, d_out, n * 12, hipMemcpyDeviceToHost, S.s));
     if (out_rgb8) DN_TRY(hipMemcpyAsync(out_rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost, S.s));
     DN_TRY(hipStreamSynchronize(S.s));

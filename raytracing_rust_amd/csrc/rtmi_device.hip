@@ -59,6 +59,7 @@
 #include "rtmi_radiance_launch.hpp"
 #include "rtmi_gather.h"
 #include "rtmi_gather_launch.hpp"
+#include "rtmi_frame_launch.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -1946,14 +1947,14 @@ static int adaptive_reserve(rtmi_scene *s, const rtmi_render_params &p, const rt
 // the label of rtmi_stats.kernel, `wps` the waves per SIMD that kernel keeps resident (the persistent grid).  The caller
 // holds s->mu, has checked every argument, called begin_blocking and adaptive_reserve and filled P with the mode's
 // traversal plan.
+// adaptive_steps_device: enqueue, wait and check overflow; texels, standard errors and counts stay in the scene's device
+// buffers (the frame handle, rtmi_frame_launch.hpp, stops here).  adaptive_download: their copies to the host.
 template <typename Launch>
-static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
-                          uint32_t wps, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
-                          rtmi_stats *stats, Launch &&launch) {
+static int adaptive_steps_device(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
+                                 uint32_t wps, PassCounts &counts, Launch &&launch) {
     int rc;
     hipStream_t stream = s->stream;
     const uint32_t T = local_tiles_of(&p, 0);
-    const size_t ntex = (size_t)T * 64;
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * wps;
     s->last_kernel = kernel;
 
@@ -1967,7 +1968,6 @@ static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi
     HIP_TRY(hipEventRecord(s->ev[0], stream));
     uint32_t *lists[2] = {s->ad_lists, s->ad_lists + T}, *count = s->ad_lists + 2 * (size_t)T;
     uint32_t n_active = T, n = 0, cur = 0;
-    PassCounts counts;
     AdaptiveResolve A;
     A.n_out = count;
     A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
@@ -2022,7 +2022,12 @@ static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi
     HIP_TRY(hipEventSynchronize(s->ev[2]));
     if (fn && !cancelled && fn(total, total, user) != 0) cancelled = true;
     if (cancelled) return fail(RTMI_ERR_CANCELLED, "cancelled by the progress callback");
-    if ((rc = check_overflow(s))) return rc;
+    return check_overflow(s);
+}
+static int adaptive_download(rtmi_scene *s, const rtmi_render_params &p, const PassCounts &counts, float *out_linear,
+                             uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
+    int rc;
+    const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
     HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
     if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
     const size_t npix = (size_t)p.nx * p.ny;
@@ -2037,6 +2042,14 @@ static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi
         for (size_t o = 0; o < npix; o++) stats->samples += spp[o];
     }
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+template <typename Launch>
+static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
+                          uint32_t wps, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
+                          rtmi_stats *stats, Launch &&launch) {
+    PassCounts counts;
+    if (int rc = adaptive_steps_device(s, p, a, P, kernel, wps, counts, launch)) return rc;
+    return adaptive_download(s, p, counts, out_linear, out_rgb8, out_stderr, out_spp, stats);
 }
 
 // ---- one host path for the estimators of the whole-image modes -----------------------------------------------------------
@@ -2170,17 +2183,17 @@ static int begin_adaptive(RenderCall &c, const Estimator &m, rtmi_scene *s, cons
 // in passes of the render's plan; adaptive sampling's resolve over the list of all tiles carries sum, m and M2 between
 // passes and writes texels and standard errors after the last one.  launch(c, sig, blocks) enqueues the render kernel on
 // s->stream for the pass fields of c.P and returns an RTMI code.  The caller has checked every argument.
+// render_fixed_device: after begin_call, enqueue, wait and check overflow; texels, standard errors and signatures stay in
+// the scene's device buffers (the frame handle, rtmi_frame_launch.hpp, stops here).  render_fixed adds their copies to the host.
 template <typename Launch>
-static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p, float *out_linear,
-                        uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats, Launch &&launch) {
-    RenderCall c;
+static int render_fixed_device(RenderCall &c, const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
+                               bool sig, rtmi_stats *stats, Launch &&launch) {
     int rc;
-    if ((rc = begin_call(c, m, s))) return rc;
     hipStream_t stream = s->stream;
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64;
     if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
-        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        (sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
         return rc;
     uint32_t chunk_spp = 0, pass_ns = 0;
     if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
@@ -2189,7 +2202,6 @@ static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *ca
     if ((rc = plan_light_coop(c, s, p))) return rc;
     DevParams &P = c.P;
     P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
-    const bool sig = out_path_sig != nullptr;
     P.path_sig = sig ? s->d_sig : nullptr;
     const uint64_t run_slots = light_run_slots(s, c);
     s->last_kernel = c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
@@ -2217,11 +2229,44 @@ static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *ca
     rtmi_scene *one[1] = {s};
     if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
     if ((rc = check_overflow(s))) return rc;
+    return stats ? fill_stats_from_events(s, &p, stats, counts) : RTMI_OK;
+}
+template <typename Launch>
+static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p, float *out_linear,
+                        uint8_t *out_rgb8, float *out_stderr, uint64_t *out_path_sig, rtmi_stats *stats, Launch &&launch) {
+    RenderCall c;
+    int rc;
+    if ((rc = begin_call(c, m, s)) || (rc = render_fixed_device(c, m, s, cam, p, out_path_sig != nullptr, stats, launch))) return rc;
+    const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
     HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
     if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
     if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
-    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+}
+
+// The plain estimator's adaptive render after begin_call: adaptive sampling's buffers, the kernel arguments, the kernel
+// selection and adaptive_steps_device (rtmi_render_adaptive; the frame handle with min_spp == ns, step_spp == 1).
+static int adaptive_plain_device(RenderCall &c, const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
+                                 const rtmi_adaptive *a, PassCounts &counts) {
+    int rc;
+    if ((rc = adaptive_reserve(s, p, a, local_tiles_of(&p, 0)))) return rc;
+    kernel_args(c, m, s, cam, p);
+    DevParams &P = c.P;
+    // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
+    const bool fast = c.fast, sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
+    const bool coop = fast && !sync && coop_ok && !inst;
+    bool ext = false;
+    if ((rc = plan_traversal(s, &p, coop, P, ext))) return rc;
+    const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
+    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, false}.words() * sizeof(uint32_t);
+    return adaptive_steps_device(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, 4u, counts,
+                                 [&](uint32_t blocks, const uint32_t *tiles) -> int {
+                                     HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream, s->dev, c.C,
+                                                                         P, tiles));
+                                     return RTMI_OK;
+                                 });
 }
 
 extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
@@ -2236,54 +2281,27 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
                                "adaptive sampling renders the whole image: tile_world must be 1");
     if (rc) return rc;
     if ((rc = check_adaptive(p_in, a))) return rc;
-    const rtmi_render_params &p = *p_in;
     const Estimator m{"rtmi_render_adaptive", false, false, 1.0f, "scene is NULL", ""};
     RenderCall c;
-    if ((rc = begin_adaptive(c, m, s, cam, p, a))) return rc;
-    DevParams &P = c.P;
-    // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
-    const bool fast = c.fast, sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
-    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
-    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
-    const bool coop = fast && !sync && coop_ok && !inst;
-    bool ext = false;
-    if ((rc = plan_traversal(s, &p, coop, P, ext))) return rc;
-    const int which = coop ? (ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
-    const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, false}.words() * sizeof(uint32_t);
-    return adaptive_steps(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, 4u, out_linear, out_rgb8, out_stderr,
-                          out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
-                              HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream, s->dev, c.C, P,
-                                                                  tiles));
-                              return RTMI_OK;
-                          });
+    PassCounts counts;
+    if ((rc = begin_call(c, m, s)) || (rc = adaptive_plain_device(c, m, s, cam, *p_in, a, counts))) return rc;
+    return adaptive_download(s, *p_in, counts, out_linear, out_rgb8, out_stderr, out_spp, stats);
 }
 
 // ---- first-hit features (include/rtmi_features.h) ---------------------------------------------------------------------
 // The per-lane features kernel (rtmi_features.hip) in passes of the render's plan, sized for 32-B slots; a resolve per
 // pass carries the f64 sums and writes the planes after the last one.  Progress and cancellation as rtmi_render's.
-extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_albedo,
-                                    float *out_normal, float *out_depth, uint32_t *out_hits, uint64_t *out_path_sig,
-                                    rtmi_stats *stats) {
-    // every argument check comes before the first use of the handle (and of the device)
-    if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
-                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG,
-                               "features accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
-                               "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
-                               "features cover the whole image: tile_world must be 1");
-    if (rc) return rc;
-    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    const rtmi_render_params &p = *p_in;
+// features_device: under the scene's lock and after begin_blocking, enqueue, wait and check overflow; the four planes stay
+// in s->ft_planes, the signatures in s->d_sig (the frame handle, rtmi_frame_launch.hpp, stops here).  The entry adds the
+// copies to the host.
+static int features_device(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p, bool sig, rtmi_stats *stats) {
+    int rc;
     hipStream_t stream = s->stream;
-    BusyMark busy_mark{s, stream};
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64, npix = (size_t)p.nx * p.ny;
     if ((rc = grow(s, s->ft_state, s->ft_state_bytes, ntex * 8 * sizeof(double))) ||
         (rc = grow(s, s->ft_planes, s->ft_planes_bytes, npix * 8 * sizeof(float))) ||
-        (out_path_sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        (sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
         return rc;
     // the per-sample buffer, planned for 32-B slots, before the clock starts
     uint32_t chunk_spp = 0, pass_ns = 0;
@@ -2292,7 +2310,7 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
     DevParams P = dev_params(s, &p);
     P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
     const DevCamera C = dev_camera(cam);
-    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sig = out_path_sig != nullptr;
+    const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
     P.path_sig = sig ? s->d_sig : nullptr;
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
     s->last_kernel = RTMI_KERNEL_PERLANE;
@@ -2319,12 +2337,33 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
     rtmi_scene *one[1] = {s};
     if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
     if ((rc = check_overflow(s))) return rc;
-    if (out_albedo) HIP_TRY(hipMemcpy(out_albedo, R.albedo, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_normal) HIP_TRY(hipMemcpy(out_normal, R.normal, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_depth) HIP_TRY(hipMemcpy(out_depth, R.depth, npix * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_hits) HIP_TRY(hipMemcpy(out_hits, R.hits, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return stats ? fill_stats_from_events(s, &p, stats, counts) : RTMI_OK;
+}
+extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_albedo,
+                                    float *out_normal, float *out_depth, uint32_t *out_hits, uint64_t *out_path_sig,
+                                    rtmi_stats *stats) {
+    // every argument check comes before the first use of the handle (and of the device)
+    if (!p_in || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
+    int rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
+                                         RTMI_FLAG_UV_BOOK | RTMI_FLAG_PATH_SIG,
+                               "features accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK and "
+                               "PATH_SIG only (not PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
+                               "features cover the whole image: tile_world must be 1");
+    if (rc) return rc;
+    if (!s) return fail(RTMI_ERR_INVALID, "scene is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = begin_blocking(s))) return rc;
+    const rtmi_render_params &p = *p_in;
+    BusyMark busy_mark{s, s->stream};
+    if ((rc = features_device(s, cam, p, out_path_sig != nullptr, stats))) return rc;
+    const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64, npix = (size_t)p.nx * p.ny;
+    const float *planes = s->ft_planes;
+    if (out_albedo) HIP_TRY(hipMemcpy(out_albedo, planes, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_normal) HIP_TRY(hipMemcpy(out_normal, planes + npix * 3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_depth) HIP_TRY(hipMemcpy(out_depth, planes + npix * 6, npix * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_hits) HIP_TRY(hipMemcpy(out_hits, planes + npix * 7, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
-    if (stats && (rc = fill_stats_from_events(s, &p, stats, counts))) return rc;
     return RTMI_OK;
 }
 
@@ -2992,6 +3031,16 @@ extern "C" int rtmi_probe_light_tree(rtmi_scene *s, int op, const float *points,
     return RTMI_OK;
 }
 
+// render_fixed's launch of the table's NEE kernel or of the environment kernel (m.env), per-lane or cooperative (c.coop)
+static int launch_lit_fixed(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks) {
+    if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
+    if (m.env)
+        HIP_TRY(rtmi_env_launch_render(c.fast, sig, m.nee, blocks, s->stream, s->dev, c.C, c.P, c.L, c.E));
+    else
+        HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L));
+    return RTMI_OK;
+}
+
 // The per-lane NEE kernel (rtmi_nee.hip), or the cooperative one (rtmi_light_coop.hip), in render_fixed; under
 // RTMI_FLAG_LIGHT_TREE the per-lane kernel of rtmi_light_tree.hip.
 extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
@@ -3012,14 +3061,12 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     m.tree = tree;
     return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
                         [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
-                            if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
-                            if (tree) {
+                            if (tree && !c.coop) {
                                 HIP_TRY(rtmi_light_tree_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L,
                                                                       dev_light_tree(s)));
                                 return RTMI_OK;
                             }
-                            HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L));
-                            return RTMI_OK;
+                            return launch_lit_fixed(c, m, s, sig, blocks);
                         });
 }
 
@@ -3072,11 +3119,7 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     const Estimator m{name, nee, true, opts->env_select_p, "scene is NULL",
                       "nee = 1 needs the light table (rtmi_scene_attach_lights)"};
     return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
-                        [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
-                            if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
-                            HIP_TRY(rtmi_env_launch_render(c.fast, sig, nee, blocks, s->stream, s->dev, c.C, c.P, c.L, c.E));
-                            return RTMI_OK;
-                        });
+                        [&](const RenderCall &c, bool sig, uint32_t blocks) -> int { return launch_lit_fixed(c, m, s, sig, blocks); });
 }
 
 // ---- adaptive sampling with NEE or environment lighting (include/rtmi_adaptive_nee.h) ---------------------------------
@@ -3727,4 +3770,57 @@ extern "C" int rtmi_session_merge(rtmi_session *dst, const rtmi_session *src) {
     }
     dst->n.assign(dst->T, nA + nB);
     return RTMI_OK;
+}
+
+// ---- the frame pipeline's seams (rtmi_frame_launch.hpp, include/rtmi_frame.h) ------------------------------------------
+// The device halves of the two renders of a frame, under one hold on the scene.  rtmi_frame.hip runs the rest of the frame
+// on s->stream before it ends the hold.
+struct RtmiFrameHold {
+    RenderCall c;
+    rtmi_scene *s = nullptr;
+};
+static Estimator frame_estimator(const RtmiFrameLit &m, const std::string &null_scene) {
+    return Estimator{m.name, m.nee, m.env, m.env ? m.env_select_p : 1.0f, null_scene.c_str(),
+                     "no light table attached (rtmi_scene_attach_lights)"};
+}
+int rtmi_frame_hold_begin(rtmi_scene *s, const RtmiFrameLit &m, RtmiFrameHold **hold) {
+    *hold = nullptr;
+    const std::string null_scene = std::string(m.name) + ": scene is NULL";
+    RtmiFrameHold *h = new (std::nothrow) RtmiFrameHold;
+    if (!h) return fail(RTMI_ERR_NOMEM, std::string(m.name) + ": out of host memory");
+    if (int rc = begin_call(h->c, frame_estimator(m, null_scene), s)) {
+        delete h;
+        return rc;
+    }
+    h->s = s;
+    *hold = h;
+    return RTMI_OK;
+}
+void rtmi_frame_hold_end(RtmiFrameHold *hold) { delete hold; } // ~RenderCall: the busy mark, then the lock
+int rtmi_frame_enqueue_lit(RtmiFrameHold *hold, const RtmiFrameLit &fm, const rtmi_camera *cam, const rtmi_render_params &p,
+                           rtmi_stats *stats) {
+    rtmi_scene *s = hold->s;
+    const Estimator m = frame_estimator(fm, "");
+    if (!fm.nee && !fm.env) {
+        const rtmi_adaptive a{p.ns, 1u, 0.0, 0.0};
+        PassCounts counts;
+        if (int rc = adaptive_plain_device(hold->c, m, s, cam, p, &a, counts)) return rc;
+        if (stats) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
+            fill_stats(s, &p, stats, ms, ms, counts); // every tile stops at ns: the samples are fill_stats'
+        }
+        return RTMI_OK;
+    }
+    return render_fixed_device(hold->c, m, s, cam, p, false, stats,
+                               [&](const RenderCall &c, bool sig, uint32_t blocks) -> int { return launch_lit_fixed(c, m, s, sig, blocks); });
+}
+int rtmi_frame_enqueue_first_hits(RtmiFrameHold *hold, const rtmi_camera *cam, const rtmi_render_params &p) {
+    return features_device(hold->s, cam, p, false, nullptr);
+}
+RtmiFramePlanes rtmi_frame_planes(const RtmiFrameHold *hold, const rtmi_render_params &p) {
+    const rtmi_scene *s = hold->s;
+    const size_t npix = (size_t)p.nx * p.ny;
+    return RtmiFramePlanes{s->device, s->stream, s->texels, s->ad_stderr, s->ft_planes, s->ft_planes + npix * 3, s->ft_planes + npix * 6,
+                           reinterpret_cast<const uint32_t *>(s->ft_planes + npix * 7)};
 }

@@ -17,6 +17,7 @@
 
 #include "rtmi.h"
 #include "rtmi_temporal.h"
+#include "rtmi_frame_launch.hpp"
 
 int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
 
@@ -185,20 +186,21 @@ __global__ __launch_bounds__(256) void rtmi_temporal_push_kernel(
 
 bool finite_f(float v) { return v == v && v - v == 0.0f; }
 
+// the RTMI_ERR_INVALID checks in `name`'s words (rtmi_temporal_create, or the frame handle's entry)
+int check_ranges(const std::string &name, uint32_t nx, uint32_t ny, const rtmi_temporal_params *p) {
+    const auto bad = [&](const char *msg) { return rtmi_fail(RTMI_ERR_INVALID, (name + ": " + msg).c_str()); };
+    if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u) return bad("nx and ny must be in [1, 32768]");
+    if (p->max_history < 1u || p->max_history > 65535u) return bad("max_history must be in [1, 65535]");
+    if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f)) return bad("alpha_min must be in [0, 1]");
+    if (!finite_f(p->depth_tol) || !(p->depth_tol >= 0.0f)) return bad("depth_tol must be finite and >= 0");
+    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f)) return bad("normal_min must be in [-1, 1]");
+    if (!finite_f(p->albedo_min) || !(p->albedo_min > 0.0f)) return bad("albedo_min must be finite and > 0");
+    if (p->reserved[0] || p->reserved[1]) return bad("reserved must be 0");
+    return RTMI_OK;
+}
+
 int check_params(uint32_t nx, uint32_t ny, const rtmi_temporal_params *p) {
-    if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u)
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: nx and ny must be in [1, 32768]");
-    if (p->max_history < 1u || p->max_history > 65535u)
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: max_history must be in [1, 65535]");
-    if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f))
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: alpha_min must be in [0, 1]");
-    if (!finite_f(p->depth_tol) || !(p->depth_tol >= 0.0f))
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: depth_tol must be finite and >= 0");
-    if (!(p->normal_min >= -1.0f && p->normal_min <= 1.0f))
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: normal_min must be in [-1, 1]");
-    if (!finite_f(p->albedo_min) || !(p->albedo_min > 0.0f))
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: albedo_min must be finite and > 0");
-    if (p->reserved[0] || p->reserved[1]) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: reserved must be 0");
+    if (int rc = check_ranges("rtmi_temporal_create", nx, ny, p)) return rc;
     if (p->flags & ~RTMI_TEMPORAL_NO_DEMODULATE) return rtmi_fail(RTMI_ERR_UNSUPPORTED, "rtmi_temporal_create: unknown flags bit");
     return RTMI_OK;
 }
@@ -244,15 +246,12 @@ struct rtmi_temporal {
     uint32_t nx = 0, ny = 0;
     rtmi_temporal_params params{};
     char *base = nullptr;  // one allocation, carved in 256-B aligned pieces
-    float4 *col[2] = {}, *geo[2] = {}, *var[2] = {};
+    RtmiTemporalHistory hist;
     float *d_lin = nullptr, *d_alb = nullptr, *d_nrm = nullptr, *d_dep = nullptr, *d_se = nullptr;
     float *o_lin = nullptr, *o_se = nullptr, *o_hist = nullptr;
     float2 *o_motion = nullptr;
     hipStream_t stream = nullptr;
-    int cur = 0;           // the copy that holds the previous frame
-    bool has_prev = false, with_se = false;
-    rtmi_camera prev_cam{};
-    float prev_m[9] = {};
+    bool with_se = false;
 };
 
 #define TP_TRY(fn, expr)                                                                                              \
@@ -273,11 +272,7 @@ static int temporal_alloc(rtmi_temporal *h) {
         at += bytes;
         return r;
     };
-    for (int k = 0; k < 2; k++) {
-        h->col[k] = reinterpret_cast<float4 *>(take(f4));
-        h->geo[k] = reinterpret_cast<float4 *>(take(f4));
-        h->var[k] = reinterpret_cast<float4 *>(take(f4));
-    }
+    rtmi_temporal_history_carve(h->hist, take(6 * f4), h->nx, h->ny);
     h->d_lin = reinterpret_cast<float *>(take(f3));
     h->d_alb = reinterpret_cast<float *>(take(f3));
     h->d_nrm = reinterpret_cast<float *>(take(f3));
@@ -324,32 +319,95 @@ extern "C" int rtmi_temporal_create(int device, uint32_t nx, uint32_t ny, const 
 
 extern "C" int rtmi_temporal_reset(rtmi_temporal *h) {
     if (!h) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_reset: NULL handle");
-    h->has_prev = false;
+    h->hist.has_prev = false;
     return RTMI_OK;
 }
 
-static int temporal_run(rtmi_temporal *h, const TemporalPush &P, const float *linear, const float *albedo, const float *normal,
+// ---- the device half, shared with the frame handle (rtmi_frame_launch.hpp) --------------------------------------------
+size_t rtmi_temporal_history_bytes(uint32_t nx, uint32_t ny) { return 6 * round256((size_t)nx * ny * 16); }
+
+void rtmi_temporal_history_carve(RtmiTemporalHistory &H, char *base, uint32_t nx, uint32_t ny) {
+    const size_t f4 = round256((size_t)nx * ny * 16);
+    for (int k = 0; k < 2; k++) {
+        H.col[k] = reinterpret_cast<float4 *>(base + (3 * k) * f4);
+        H.geo[k] = reinterpret_cast<float4 *>(base + (3 * k + 1) * f4);
+        H.var[k] = reinterpret_cast<float4 *>(base + (3 * k + 2) * f4);
+    }
+}
+
+int rtmi_temporal_check_ranges(const char *name, uint32_t nx, uint32_t ny, const rtmi_temporal_params *p) {
+    return check_ranges(name, nx, ny, p);
+}
+
+int rtmi_temporal_camera_matrix(const char *name, const rtmi_camera *cam, float m[9]) {
+    float fields[sizeof(rtmi_camera) / sizeof(float)];
+    static_assert(sizeof(rtmi_camera) == 84, "rtmi_camera is 21 floats");
+    memcpy(fields, cam, sizeof(rtmi_camera));
+    for (float f : fields)
+        if (!finite_f(f)) return rtmi_fail(RTMI_ERR_INVALID, (std::string(name) + ": non-finite camera field").c_str());
+    if (!camera_inverse(cam, m))
+        return rtmi_fail(RTMI_ERR_INVALID,
+                         (std::string(name) + ": singular camera (horizontal, vertical and the corner are coplanar)").c_str());
+    return RTMI_OK;
+}
+
+hipError_t rtmi_temporal_push_launch(hipStream_t stream, uint32_t nx, uint32_t ny, const rtmi_temporal_params &params,
+                                     const RtmiTemporalHistory &H, const rtmi_camera *cam, const float *linear, const float *albedo,
+                                     const float *normal, const float *depth, const float *se, float *out_linear, float *out_se,
+                                     float *out_hist, float2 *out_motion) {
+    TemporalPush P{};
+    P.nx = nx;
+    P.ny = ny;
+    P.has_prev = H.has_prev;
+    P.same_cam = H.has_prev && memcmp(&H.prev_cam, cam, sizeof(rtmi_camera)) == 0;
+    P.demodulate = !(params.flags & RTMI_TEMPORAL_NO_DEMODULATE);
+    P.max_history = (float)params.max_history;
+    P.alpha_min = params.alpha_min;
+    P.depth_tol = params.depth_tol;
+    P.normal_min = params.normal_min;
+    P.albedo_min = params.albedo_min;
+    for (int k = 0; k < 3; k++) {
+        P.org[k] = cam->origin[k];
+        P.llc[k] = cam->lower_left_corner[k];
+        P.hor[k] = cam->horizontal[k];
+        P.ver[k] = cam->vertical[k];
+        P.porg[k] = H.prev_cam.origin[k];
+    }
+    memcpy(P.m, H.prev_m, sizeof(P.m));
+    const int src = H.cur, dst = H.cur ^ 1;
+    const dim3 block(kBlock, kBlock), grid((nx + kBlock - 1) / kBlock, (ny + kBlock - 1) / kBlock);
+    if (se)
+        hipLaunchKernelGGL(rtmi_temporal_push_kernel<true>, grid, block, 0, stream, linear, albedo, normal, depth, se, H.col[src],
+                           H.geo[src], H.var[src], H.col[dst], H.geo[dst], H.var[dst], out_linear, out_se, out_hist, out_motion, P);
+    else
+        hipLaunchKernelGGL(rtmi_temporal_push_kernel<false>, grid, block, 0, stream, linear, albedo, normal, depth, se, H.col[src],
+                           H.geo[src], H.var[src], H.col[dst], H.geo[dst], H.var[dst], out_linear, out_se, out_hist, out_motion, P);
+    return hipGetLastError();
+}
+
+void rtmi_temporal_history_advance(RtmiTemporalHistory &H, const rtmi_camera *cam, const float m[9]) {
+    H.cur ^= 1;
+    H.has_prev = true;
+    H.prev_cam = *cam;
+    memcpy(H.prev_m, m, 9 * sizeof(float));
+}
+
+// the staging copies around one push
+static int temporal_run(rtmi_temporal *h, const rtmi_camera *cam, const float *linear, const float *albedo, const float *normal,
                         const float *depth, const float *se, float *out_linear, float *out_stderr, float *out_history,
                         float *out_motion) {
     const size_t n = (size_t)h->nx * h->ny;
-    const int src = h->cur, dst = h->cur ^ 1;
     hipStream_t s = h->stream;
     TP_TRY("rtmi_temporal_push", hipSetDevice(h->device));
     TP_TRY("rtmi_temporal_push", hipMemcpyAsync(h->d_lin, linear, n * 12, hipMemcpyHostToDevice, s));
-    if (P.demodulate) TP_TRY("rtmi_temporal_push", hipMemcpyAsync(h->d_alb, albedo, n * 12, hipMemcpyHostToDevice, s));
+    if (!(h->params.flags & RTMI_TEMPORAL_NO_DEMODULATE))
+        TP_TRY("rtmi_temporal_push", hipMemcpyAsync(h->d_alb, albedo, n * 12, hipMemcpyHostToDevice, s));
     TP_TRY("rtmi_temporal_push", hipMemcpyAsync(h->d_nrm, normal, n * 12, hipMemcpyHostToDevice, s));
     TP_TRY("rtmi_temporal_push", hipMemcpyAsync(h->d_dep, depth, n * 4, hipMemcpyHostToDevice, s));
     if (se) TP_TRY("rtmi_temporal_push", hipMemcpyAsync(h->d_se, se, n * 12, hipMemcpyHostToDevice, s));
-    const dim3 block(kBlock, kBlock), grid((h->nx + kBlock - 1) / kBlock, (h->ny + kBlock - 1) / kBlock);
-    if (se)
-        hipLaunchKernelGGL(rtmi_temporal_push_kernel<true>, grid, block, 0, s, h->d_lin, h->d_alb, h->d_nrm, h->d_dep, h->d_se,
-                           h->col[src], h->geo[src], h->var[src], h->col[dst], h->geo[dst], h->var[dst], h->o_lin, h->o_se,
-                           h->o_hist, h->o_motion, P);
-    else
-        hipLaunchKernelGGL(rtmi_temporal_push_kernel<false>, grid, block, 0, s, h->d_lin, h->d_alb, h->d_nrm, h->d_dep, h->d_se,
-                           h->col[src], h->geo[src], h->var[src], h->col[dst], h->geo[dst], h->var[dst], h->o_lin, h->o_se,
-                           h->o_hist, h->o_motion, P);
-    TP_TRY("rtmi_temporal_push", hipGetLastError());
+    TP_TRY("rtmi_temporal_push", rtmi_temporal_push_launch(s, h->nx, h->ny, h->params, h->hist, cam, h->d_lin, h->d_alb, h->d_nrm,
+                                                           h->d_dep, se ? h->d_se : nullptr, h->o_lin, h->o_se, h->o_hist,
+                                                           h->o_motion));
     if (out_linear) TP_TRY("rtmi_temporal_push", hipMemcpyAsync(out_linear, h->o_lin, n * 12, hipMemcpyDeviceToHost, s));
     if (out_stderr) TP_TRY("rtmi_temporal_push", hipMemcpyAsync(out_stderr, h->o_se, n * 12, hipMemcpyDeviceToHost, s));
     if (out_history) TP_TRY("rtmi_temporal_push", hipMemcpyAsync(out_history, h->o_hist, n * 4, hipMemcpyDeviceToHost, s));
@@ -364,47 +422,19 @@ extern "C" int rtmi_temporal_push(rtmi_temporal *h, const rtmi_camera *cam, cons
     // every argument check comes before the first HIP call; the handle comes last, so that a machine without a device
     // (where no handle can exist) still answers for every other argument
     if (!cam || !linear || !albedo || !normal || !depth) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_push: NULL argument");
-    float fields[sizeof(rtmi_camera) / sizeof(float)];
-    static_assert(sizeof(rtmi_camera) == 84, "rtmi_camera is 21 floats");
-    memcpy(fields, cam, sizeof(rtmi_camera));
-    for (float f : fields)
-        if (!finite_f(f)) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_push: non-finite camera field");
     float m[9];
-    if (!camera_inverse(cam, m))
-        return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_push: singular camera (horizontal, vertical and the corner are coplanar)");
+    if (int rc = rtmi_temporal_camera_matrix("rtmi_temporal_push", cam, m)) return rc;
     if (out_stderr && !stderr_rgb) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_push: out_stderr needs stderr_rgb");
     if (!h) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_push: NULL handle");
     const bool with_se = stderr_rgb != nullptr;
-    if (h->has_prev && with_se != h->with_se)
+    if (h->hist.has_prev && with_se != h->with_se)
         return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_push: stderr_rgb must be supplied on every push since the reset or on none");
-    TemporalPush P{};
-    P.nx = h->nx;
-    P.ny = h->ny;
-    P.has_prev = h->has_prev;
-    P.same_cam = h->has_prev && memcmp(&h->prev_cam, cam, sizeof(rtmi_camera)) == 0;
-    P.demodulate = !(h->params.flags & RTMI_TEMPORAL_NO_DEMODULATE);
-    P.max_history = (float)h->params.max_history;
-    P.alpha_min = h->params.alpha_min;
-    P.depth_tol = h->params.depth_tol;
-    P.normal_min = h->params.normal_min;
-    P.albedo_min = h->params.albedo_min;
-    for (int k = 0; k < 3; k++) {
-        P.org[k] = cam->origin[k];
-        P.llc[k] = cam->lower_left_corner[k];
-        P.hor[k] = cam->horizontal[k];
-        P.ver[k] = cam->vertical[k];
-        P.porg[k] = h->prev_cam.origin[k];
-    }
-    memcpy(P.m, h->prev_m, sizeof(P.m));
-    const int rc = temporal_run(h, P, linear, albedo, normal, depth, stderr_rgb, out_linear, out_stderr, out_history, out_motion);
+    const int rc = temporal_run(h, cam, linear, albedo, normal, depth, stderr_rgb, out_linear, out_stderr, out_history, out_motion);
     if (rc) {
-        h->has_prev = false;
+        h->hist.has_prev = false;
         return rc;
     }
-    h->cur ^= 1;
-    h->has_prev = true;
+    rtmi_temporal_history_advance(h->hist, cam, m);
     h->with_se = with_se;
-    h->prev_cam = *cam;
-    memcpy(h->prev_m, m, sizeof(m));
     return RTMI_OK;
 }

@@ -525,6 +525,29 @@ class Scene:
         out = _denoise(acc["linear"], ft["albedo"], ft["normal"], ft["depth"], stderr=acc["stderr"], device=self.device, **opts)
         return {"linear": out["linear"], "rgb8": out["rgb8"], "noisy": noisy, "features": ft, "accumulated": acc}
 
+    def frame(self, nx, ny, estimator="plain", temporal=(), denoise=(), coop=False, env_select_p=0.5, **kw):
+        """A frame handle (include/rtmi_frame.h): render_temporal's chain of five calls as one, with every plane kept on
+        the device between the stages and all device memory allocated here, once.  estimator: "plain",
+        "nee", "env" or "env_nee" (render_temporal's nee and env); temporal: dict of Temporal's keywords ({} or omitted: its
+        defaults) or None for no history (render_denoised's chain); denoise: dict of denoise()'s keywords ({} or omitted:
+        its defaults) or False for no filter (render_temporal(denoise=False)); coop=True (with a lit estimator): the lit
+        render gets RTMI_FLAG_LIGHT_COOP.  The other keywords are default_params' (ns and seed are Frame.render's).  The
+        light table is attached on first use.  A scene resident on a device list (upload_multi) raises Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        if coop and estimator == "plain":
+            raise ValueError("coop=True needs a lit estimator: the plain render is cooperative by default")
+        _coop_flags(kw, coop)
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, 2, **kw)
+        o = abi.FrameOpts(abi.ROULETTE_ESTIMATORS[estimator], env_select_p, _temporal_params(**dict(temporal or ())),
+                          _denoise_params(**dict(denoise or ())),
+                          (abi.RTMI_FRAME_NO_TEMPORAL if temporal is None else 0) | (abi.RTMI_FRAME_NO_FILTER if denoise is False else 0))
+        h = self.host.lib.rth_frame_create(self.h, C.byref(p), C.byref(o))
+        if not h:
+            self.host._raise()
+        return Frame(self.host, h, nx, ny, self.device, temporal is not None, keep=(self, p))
+
     def render_multi(self, cam, nx, ny, ns, devices, **kw):
         """Whole image on several GPUs of this process (rtmi_render_multi): tiles t % len(devices), one gather.
         A device may be listed more than once (single-GPU rehearsal).  Bit-identical to render()."""
@@ -1018,6 +1041,77 @@ class Session:
             self.host._check(self.host.lib.rth_session_close(h))
 
 
+# the planes of rtmi_frame_out in Frame.render's result: (group, name in the group, field, channels, dtype)
+_FRAME_PLANES = ((None, "linear", "linear", (3,), "float32"), (None, "rgb8", "rgb8", (3,), "uint8"),
+                 ("noisy", "linear", "noisy_linear", (3,), "float32"), ("noisy", "stderr", "noisy_stderr", (3,), "float32"),
+                 ("features", "albedo", "albedo", (3,), "float32"), ("features", "normal", "normal", (3,), "float32"),
+                 ("features", "depth", "depth", (), "float32"), ("features", "hits", "hits", (), "uint32"),
+                 ("accumulated", "linear", "accum_linear", (3,), "float32"), ("accumulated", "stderr", "accum_stderr", (3,), "float32"),
+                 ("accumulated", "history", "history", (), "float32"), ("accumulated", "motion", "motion", (2,), "float32"))
+
+
+class Frame:
+    """A frame handle of Scene.frame (include/rtmi_frame.h).  Calls on it serialise with every other call on its scene.
+    close() frees its device memory (227 B per pixel with every stage on); Host.free_all() closes what is still open.
+    Usable as a context manager."""
+
+    def __init__(self, host, h, nx, ny, device, temporal, keep=()):
+        self.host, self.h, self.nx, self.ny, self.device, self.temporal, self.keep = host, h, nx, ny, device, temporal, keep
+        host._frames = getattr(host, "_frames", []) + [self]
+
+    def _handle(self):
+        if not self.h:
+            raise HostError("the frame is closed")
+        return self.h
+
+    def render(self, cam, ns, seed=0, aux=False, out="numpy"):
+        """One frame under `cam` (a Camera of Host) with ns >= 2 samples per pixel.  Returns dict(linear f32 [ny,nx,3],
+        rgb8 u8 [ny,nx,3], stats); aux=True adds render_temporal's noisy = dict(linear, stderr), features = dict(albedo,
+        normal, depth, hits) and, with a history, accumulated = dict(linear, stderr, history, motion).  out="numpy": host
+        arrays; out="torch": torch tensors on the scene's device, written by the device form without a host copy."""
+        h = self._handle()
+        if out not in ("numpy", "torch"):
+            raise ValueError("out must be 'numpy' or 'torch'")
+        if out == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+        res, ptrs = {}, abi.FrameOut()
+        for group, name, field, ch, dtype in _FRAME_PLANES:
+            if (group and not aux) or (group == "accumulated" and not self.temporal):
+                continue
+            shape = (self.ny, self.nx) + ch
+            if out == "torch":
+                a = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+                setattr(ptrs, field, a.data_ptr())
+            else:
+                a = np.zeros(shape, dtype)
+                setattr(ptrs, field, a.ctypes.data)
+            (res.setdefault(group, {}) if group else res)[name] = a
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_frame_render(h, cam.h, ns, int(seed) & (2 ** 64 - 1), C.byref(ptrs),
+                                                         1 if out == "torch" else 0, C.byref(st)))
+        res["stats"] = _stats(st)
+        return res
+
+    def reset(self):
+        """Forgets the frames rendered so far: the next frame starts a fresh history."""
+        self.host._check(self.host.lib.rth_frame_reset(self._handle()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.host._frames = [f for f in getattr(self.host, "_frames", []) if f is not self]
+            self.host._check(self.host.lib.rth_frame_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 def _outputs(ny, nx, names, sig=None):
     """The zeroed planes `names` of a render as its result dict, and the trailing arguments of the native entry: the
     planes' addresses in that order, the path signatures' (u64 [ny,nx]; NULL unless sig; sig=None: the entry takes none;
@@ -1107,6 +1201,8 @@ class Host:
     def free_all(self):
         for ses in list(getattr(self, "_sessions", [])):  # sessions before their scenes
             ses.close()
+        for frm in list(getattr(self, "_frames", [])):  # ... and frames
+            frm.close()
         for tmp in list(_temporals):
             tmp.close()
         self.lib.rth_free_all()
@@ -1278,6 +1374,17 @@ def ppm_p3(rgb8):
     return buf.raw[:n]
 
 
+def _denoise_params(iterations=5, normal_power=128, sigma_l=4.0, sigma_z=1.0, eps_l=1e-10, eps_z=1e-3, albedo_min=1e-3):
+    """denoise()'s keywords as rtmi_denoise_params."""
+    return abi.DenoiseParams(iterations, normal_power, sigma_l, sigma_z, eps_l, eps_z, albedo_min, 0)
+
+
+def _temporal_params(max_history=32, alpha_min=0.0, depth_tol=0.05, normal_min=0.9, albedo_min=1e-3, demodulate=True):
+    """Temporal's keywords as rtmi_temporal_params."""
+    return abi.TemporalParams(max_history, alpha_min, depth_tol, normal_min, albedo_min,
+                              0 if demodulate else abi.RTMI_TEMPORAL_NO_DEMODULATE)
+
+
 def denoise(linear, albedo, normal, depth, stderr=None, iterations=5, normal_power=128, sigma_l=4.0, sigma_z=1.0,
             eps_l=1e-10, eps_z=1e-3, albedo_min=1e-3, device=0):
     """The a-trous denoiser of include/rtmi_denoise.h on `device`: linear, albedo, normal (and stderr, or None) are float32
@@ -1298,7 +1405,7 @@ def denoise(linear, albedo, normal, depth, stderr=None, iterations=5, normal_pow
         if a.dtype != np.float32:
             raise ValueError("%s must be float32, not %s" % (name, a.dtype))
         planes[name] = np.ascontiguousarray(a)
-    p = abi.DenoiseParams(iterations, normal_power, sigma_l, sigma_z, eps_l, eps_z, albedo_min, 0)
+    p = _denoise_params(iterations, normal_power, sigma_l, sigma_z, eps_l, eps_z, albedo_min)
     lin = np.zeros((ny, nx, 3), np.float32)
     rgb = np.zeros((ny, nx, 3), np.uint8)
     lib = abi.load_rtmi()
@@ -1325,8 +1432,7 @@ class Temporal:
                  demodulate=True):
         self.lib = abi.load_rtmi()
         self.nx, self.ny, self.device, self.h = int(nx), int(ny), device, None
-        p = abi.TemporalParams(max_history, alpha_min, depth_tol, normal_min, albedo_min,
-                               0 if demodulate else abi.RTMI_TEMPORAL_NO_DEMODULATE)
+        p = _temporal_params(max_history, alpha_min, depth_tol, normal_min, albedo_min, demodulate)
         h = C.c_void_p()
         self._check(self.lib.rtmi_temporal_create(device, self.nx, self.ny, C.byref(p), C.byref(h)), "rtmi_temporal_create")
         self.h = h

@@ -17,6 +17,7 @@
 #include "rtmi_query.h"
 #include "rtmi_radiance.h"
 #include "rtmi_gather.h"
+#include "rtmi_frame.h"
 
 using namespace rt;
 
@@ -41,6 +42,7 @@ struct Obj {
 std::mutex g_mu;
 std::vector<Obj *> g_objs;
 std::vector<rtmi_session *> g_sessions; // the live render sessions (rth_session_*): freed before their scenes
+std::vector<rtmi_frame *> g_frames;     // the live frame handles (rth_frame_*): freed before their scenes
 
 Obj *reg(Obj *o) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -96,6 +98,8 @@ RTH_API void rth_free_all(void) {
     std::lock_guard<std::mutex> lk(g_mu);
     for (rtmi_session *ss : g_sessions) rtmi_session_destroy(ss);
     g_sessions.clear();
+    for (rtmi_frame *f : g_frames) rtmi_frame_destroy(f);
+    g_frames.clear();
     for (Obj *o : g_objs) {
         if (o->dev) rtmi_scene_destroy(o->dev);
         if (o->multi) rtmi_multi_destroy(o->multi);
@@ -525,6 +529,49 @@ RTH_API int rth_session_merge(void *dst, void *src) {
 }
 RTH_API int rth_session_spp(void *session, uint32_t *min_spp, uint32_t *max_spp) {
     return guard([&] { return done("rtmi_session_spp", rtmi_session_spp(SES(session), min_spp, max_spp), CODED); });
+}
+// the frame pipeline (include/rtmi_frame.h): the entries one to one on the uploaded handle; RTH_UNSUPPORTED for what they do
+// not support, a multi-GPU handle among it.  A frame is freed by rth_frame_close or, at the latest, by rth_free_all (before
+// the scenes); re-uploading its scene (rth_upload) while it lives is the caller's error.
+static rtmi_frame *FRM(void *h) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (rtmi_frame *f : g_frames)
+        if (f == h) return f;
+    throw std::runtime_error("handle is not a live frame");
+}
+RTH_API void *rth_frame_create(void *lowered, const rtmi_render_params *p, const rtmi_frame_opts *opts) {
+    return guard_new([&] {
+        const char *name = "rtmi_frame_create";
+        rtmi_scene *dev = DEV(lowered, name, "frame");
+        rtmi_frame *f = nullptr;
+        done(name, rtmi_frame_create(dev, p, opts, &f), CODED_UNSUPPORTED);
+        std::lock_guard<std::mutex> lk(g_mu);
+        g_frames.push_back(f);
+        return (void *)f;
+    });
+}
+RTH_API int rth_frame_close(void *frame) {
+    return guard([&] {
+        rtmi_frame *f = FRM(frame);
+        {
+            std::lock_guard<std::mutex> lk(g_mu);
+            g_frames.erase(std::find(g_frames.begin(), g_frames.end(), f));
+        }
+        rtmi_frame_destroy(f);
+        return RTH_OK;
+    });
+}
+RTH_API int rth_frame_render(void *frame, void *cam, uint32_t ns, uint64_t seed, const rtmi_frame_out *out, int on_device,
+                             rtmi_stats *stats) {
+    return guard([&] {
+        const rtmi_camera c = CAM(cam).lower();
+        if (on_device)
+            return done("rtmi_frame_render_device", rtmi_frame_render_device(FRM(frame), &c, ns, seed, out, stats), CODED_UNSUPPORTED);
+        return done("rtmi_frame_render", rtmi_frame_render(FRM(frame), &c, ns, seed, out, stats), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_frame_reset(void *frame) {
+    return guard([&] { return done("rtmi_frame_reset", rtmi_frame_reset(FRM(frame)), CODED); });
 }
 RTH_API int rth_probe_env(void *lowered, int op, const float *in, float *out, uint32_t n) {
     return guard([&] { return done("rtmi_probe_env", rtmi_probe_env(DEV(lowered), op, in, out, n), CODED); });
