@@ -980,6 +980,100 @@ extern "C" {
     pub fn rtmi_temporal_destroy(h: *mut RtmiTemporal);
 }
 
+// ---- include/rtmi_tonemap.h: tone mapping with histogram auto-exposure -------------------------------------------------
+
+pub const RTMI_TONEMAP_CLAMP: u32 = 0;
+pub const RTMI_TONEMAP_REINHARD: u32 = 1;
+pub const RTMI_TONEMAP_ACES: u32 = 2;
+pub const RTMI_TONEMAP_GAMMA2: u32 = 0;
+pub const RTMI_TONEMAP_SRGB: u32 = 1;
+pub const RTMI_TONEMAP_MANUAL: u32 = 0;
+pub const RTMI_TONEMAP_AUTO: u32 = 1;
+
+/// rtmi_tonemap_params: the operator, the transfer function and the metering (64 bytes); defaults ACES, SRGB, AUTO, 0, 0,
+/// +inf, 0.18, -12, 12, 0.10, 0.95, 3, 1, log2_min, log2_max, 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiTonemapParams {
+    pub op: u32,
+    pub oetf: u32,
+    pub exposure: u32,
+    pub flags: u32,
+    pub ev: f32,
+    pub white: f32,
+    pub key: f32,
+    pub log2_min: f32,
+    pub log2_max: f32,
+    pub p_low: f32,
+    pub p_high: f32,
+    pub speed_up: f32,
+    pub speed_down: f32,
+    pub adapt_min: f32,
+    pub adapt_max: f32,
+    pub reserved: u32,
+}
+
+/// rtmi_tonemap_state: what one apply metered and applied (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiTonemapState {
+    pub exposure: f32,
+    pub adapted_log2: f32,
+    pub metered_log2: f32,
+    pub counted: u32,
+    pub kept: u32,
+    pub applies: u32,
+    pub reserved: [u32; 2],
+}
+
+/// opaque tone mapper of one image size on one device (rtmi_tonemap.h: rtmi_tonemap)
+#[repr(C)]
+pub struct RtmiTonemap {
+    _private: [u8; 0],
+}
+
+extern "C" {
+    pub fn rtmi_tonemap_create(
+        device: c_int,
+        nx: u32,
+        ny: u32,
+        params: *const RtmiTonemapParams,
+        out: *mut *mut RtmiTonemap,
+    ) -> c_int;
+    /// blocking, host pointers; linear ny * nx * 3 floats; out_rgb8 ny * nx * 3 bytes, out_display ny * nx * 3 floats and
+    /// out_state each optional, not all NULL
+    pub fn rtmi_tonemap_apply(
+        h: *mut RtmiTonemap,
+        linear: *const f32,
+        dt: f32,
+        out_rgb8: *mut u8,
+        out_display: *mut f32,
+        out_state: *mut RtmiTonemapState,
+    ) -> c_int;
+    /// asynchronous on `stream` (a hipStream_t), device pointers; d_linear and d_display 16-byte aligned, d_rgb8 and d_state 4
+    pub fn rtmi_tonemap_apply_device(
+        h: *mut RtmiTonemap,
+        d_linear: *const c_void,
+        dt: f32,
+        d_rgb8: *mut c_void,
+        d_display: *mut c_void,
+        d_state: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// the next apply is a first apply
+    pub fn rtmi_tonemap_reset(h: *mut RtmiTonemap) -> c_int;
+    pub fn rtmi_tonemap_destroy(h: *mut RtmiTonemap);
+    /// the metering kernel alone on host data: out_bins = 256 counts
+    pub fn rtmi_probe_tonemap_histogram(
+        device: c_int,
+        nx: u32,
+        ny: u32,
+        params: *const RtmiTonemapParams,
+        linear: *const f32,
+        out_bins: *mut u32,
+    ) -> c_int;
+}
+
 // ---- include/rtmi_frame.h: the device-resident frame pipeline ---------------------------------------------------------
 
 pub const RTMI_FRAME_NO_TEMPORAL: u32 = 1;

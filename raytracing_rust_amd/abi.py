@@ -341,6 +341,32 @@ class FrameOut(C.Structure):
 RTMI_FRAME_SYMBOLS = ["rtmi_frame_create", "rtmi_frame_destroy", "rtmi_frame_render", "rtmi_frame_render_device",
                       "rtmi_frame_reset", "rtmi_probe_frame_untile"]
 
+RTMI_TONEMAP_CLAMP, RTMI_TONEMAP_REINHARD, RTMI_TONEMAP_ACES = 0, 1, 2  # include/rtmi_tonemap.h: op
+RTMI_TONEMAP_GAMMA2, RTMI_TONEMAP_SRGB = 0, 1  # ... oetf: the reference's sqrt, the sRGB curve
+RTMI_TONEMAP_MANUAL, RTMI_TONEMAP_AUTO = 0, 1  # ... exposure
+TONEMAP_OPS = {"clamp": RTMI_TONEMAP_CLAMP, "reinhard": RTMI_TONEMAP_REINHARD, "aces": RTMI_TONEMAP_ACES}
+TONEMAP_OETFS = {"gamma2": RTMI_TONEMAP_GAMMA2, "srgb": RTMI_TONEMAP_SRGB}
+TONEMAP_EXPOSURES = {"manual": RTMI_TONEMAP_MANUAL, "auto": RTMI_TONEMAP_AUTO}
+
+
+class TonemapParams(C.Structure):
+    """rtmi_tonemap_params (include/rtmi_tonemap.h): the operator, the transfer function and the metering (64 bytes)."""
+    _fields_ = [("op", C.c_uint32), ("oetf", C.c_uint32), ("exposure", C.c_uint32), ("flags", C.c_uint32), ("ev", C.c_float),
+                ("white", C.c_float), ("key", C.c_float), ("log2_min", C.c_float), ("log2_max", C.c_float), ("p_low", C.c_float),
+                ("p_high", C.c_float), ("speed_up", C.c_float), ("speed_down", C.c_float), ("adapt_min", C.c_float),
+                ("adapt_max", C.c_float), ("reserved", C.c_uint32)]
+
+
+class TonemapState(C.Structure):
+    """rtmi_tonemap_state (include/rtmi_tonemap.h): what one apply metered and applied (32 bytes)."""
+    _fields_ = [("exposure", C.c_float), ("adapted_log2", C.c_float), ("metered_log2", C.c_float), ("counted", C.c_uint32),
+                ("kept", C.c_uint32), ("applies", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# the functions of include/rtmi_tonemap.h (tone mapping), kept apart from those of the other headers
+RTMI_TONEMAP_SYMBOLS = ["rtmi_probe_tonemap_histogram", "rtmi_tonemap_apply", "rtmi_tonemap_apply_device", "rtmi_tonemap_create",
+                        "rtmi_tonemap_destroy", "rtmi_tonemap_reset"]
+
 _rtmi = None
 _host = None
 
@@ -511,6 +537,18 @@ def load_rtmi():
     lib.rtmi_frame_destroy.argtypes = [vp]
     lib.rtmi_probe_frame_untile.restype = C.c_int
     lib.rtmi_probe_frame_untile.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
+    lib.rtmi_tonemap_create.restype = C.c_int
+    lib.rtmi_tonemap_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TonemapParams), C.POINTER(vp)]
+    lib.rtmi_tonemap_apply.restype = C.c_int
+    lib.rtmi_tonemap_apply.argtypes = [vp, vp, C.c_float, vp, vp, C.POINTER(TonemapState)]
+    lib.rtmi_tonemap_apply_device.restype = C.c_int
+    lib.rtmi_tonemap_apply_device.argtypes = [vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.rtmi_tonemap_reset.restype = C.c_int
+    lib.rtmi_tonemap_reset.argtypes = [vp]
+    lib.rtmi_tonemap_destroy.restype = None
+    lib.rtmi_tonemap_destroy.argtypes = [vp]
+    lib.rtmi_probe_tonemap_histogram.restype = C.c_int
+    lib.rtmi_probe_tonemap_histogram.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TonemapParams), vp, vp]
     _rtmi = lib
     return lib
 

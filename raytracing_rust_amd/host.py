@@ -1064,14 +1064,19 @@ class Frame:
             raise HostError("the frame is closed")
         return self.h
 
-    def render(self, cam, ns, seed=0, aux=False, out="numpy"):
+    def render(self, cam, ns, seed=0, aux=False, out="numpy", tonemap=None, dt=0.0):
         """One frame under `cam` (a Camera of Host) with ns >= 2 samples per pixel.  Returns dict(linear f32 [ny,nx,3],
         rgb8 u8 [ny,nx,3], stats); aux=True adds render_temporal's noisy = dict(linear, stderr), features = dict(albedo,
         normal, depth, hits) and, with a history, accumulated = dict(linear, stderr, history, motion).  out="numpy": host
-        arrays; out="torch": torch tensors on the scene's device, written by the device form without a host copy."""
+        arrays; out="torch": torch tensors on the scene's device, written by the device form without a host copy.
+        tonemap: a Tonemap of the frame's size and device (ValueError otherwise); rgb8 is then tonemap.apply(linear, dt)'s,
+        through the device form with out="torch" and the host form with out="numpy", and exposure = its state is added."""
         h = self._handle()
         if out not in ("numpy", "torch"):
             raise ValueError("out must be 'numpy' or 'torch'")
+        if tonemap is not None and (not isinstance(tonemap, Tonemap) or (tonemap.nx, tonemap.ny, tonemap.device) !=
+                                    (self.nx, self.ny, self.device)):
+            raise ValueError("tonemap must be a Tonemap of the frame's size (%d x %d) and device (%d)" % (self.nx, self.ny, self.device))
         if out == "torch":
             import torch
 
@@ -1092,6 +1097,9 @@ class Frame:
         self.host._check(self.host.lib.rth_frame_render(h, cam.h, ns, int(seed) & (2 ** 64 - 1), C.byref(ptrs),
                                                          1 if out == "torch" else 0, C.byref(st)))
         res["stats"] = _stats(st)
+        if tonemap is not None:
+            tm = tonemap.apply(res["linear"], dt=dt, sync=True)
+            res["rgb8"], res["exposure"] = tm["rgb8"], tm["exposure"]
         return res
 
     def reset(self):
@@ -1205,6 +1213,8 @@ class Host:
             frm.close()
         for tmp in list(_temporals):
             tmp.close()
+        for tm in list(_tonemaps):
+            tm.close()
         self.lib.rth_free_all()
 
     # ---- textures (src/texture.rs) ----
@@ -1491,6 +1501,135 @@ class Temporal:
             if self in _temporals:
                 _temporals.remove(self)
             self.lib.rtmi_temporal_destroy(h)
+
+
+_tonemaps = []  # the open Tonemap handles; Host.free_all() closes them
+
+
+def _tonemap_params(op="aces", oetf="srgb", exposure="auto", ev=0.0, white=float("inf"), key=0.18, log2_range=(-12, 12),
+                    percentiles=(0.10, 0.95), speed=(3.0, 1.0), adapt_range=None):
+    """Tonemap's keywords as rtmi_tonemap_params."""
+    for what, table, v in (("op", abi.TONEMAP_OPS, op), ("oetf", abi.TONEMAP_OETFS, oetf),
+                           ("exposure", abi.TONEMAP_EXPOSURES, exposure)):
+        if v not in table:
+            raise ValueError("%s must be one of %s, not %r" % (what, ", ".join(sorted(table)), v))
+    lo, hi = adapt_range if adapt_range is not None else log2_range
+    return abi.TonemapParams(abi.TONEMAP_OPS[op], abi.TONEMAP_OETFS[oetf], abi.TONEMAP_EXPOSURES[exposure], 0, ev, white, key,
+                             log2_range[0], log2_range[1], percentiles[0], percentiles[1], speed[0], speed[1], lo, hi, 0)
+
+
+def _tonemap_state(st):
+    return {"exposure": st.exposure, "adapted_log2": st.adapted_log2, "metered_log2": st.metered_log2,
+            "counted": int(st.counted), "kept": int(st.kept), "applies": int(st.applies)}
+
+
+class Tonemap:
+    """The tone mapper of include/rtmi_tonemap.h for nx x ny images on `device`: apply() meters the image's
+    log-luminance histogram, adapts the exposure over the applies (exposure="auto"; "manual": 2^ev), applies the curve
+    `op` ("clamp", "reinhard" with the white point `white`, "aces") and the transfer function `oetf` ("gamma2": the
+    reference's sqrt quantiser; "srgb").  log2_range: the histogram's range, percentiles: the shares of the samples the
+    mean leaves out below and keeps up to, speed: the adaptation's rates (up, down) per second, adapt_range: the bounds of
+    the adapted value (None: log2_range).  close() frees its device memory; Host.free_all() closes what is still open.
+    Usable as a context manager.  ValueError for an unknown name, HostError for what rtmi_tonemap_create refuses."""
+
+    def __init__(self, nx, ny, device=0, op="aces", oetf="srgb", exposure="auto", ev=0.0, white=float("inf"), key=0.18,
+                 log2_range=(-12, 12), percentiles=(0.10, 0.95), speed=(3.0, 1.0), adapt_range=None):
+        self.lib = abi.load_rtmi()
+        self.nx, self.ny, self.device, self.h = int(nx), int(ny), device, None
+        p = _tonemap_params(op, oetf, exposure, ev, white, key, log2_range, percentiles, speed, adapt_range)
+        h = C.c_void_p()
+        self._check(self.lib.rtmi_tonemap_create(device, self.nx, self.ny, C.byref(p), C.byref(h)), "rtmi_tonemap_create")
+        self.h = h
+        _tonemaps.append(self)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, self.lib.rtmi_last_error().decode()))
+
+    def _handle(self):
+        if not self.h:
+            raise HostError("the tone mapper is closed")
+        return self.h
+
+    def apply(self, linear, dt=0.0, display=False, sync=None):
+        """One image: linear is float32 [ny,nx,3], row 0 the top row; dt the seconds since the previous apply.
+        A numpy array goes through the blocking host form and returns dict(rgb8 u8 [ny,nx,3][, display f32 [ny,nx,3]],
+        exposure = dict(exposure, adapted_log2, metered_log2, counted, kept, applies)).  A torch tensor on the handle's device
+        goes through the device form on torch's current stream, without a copy or a wait: it returns tensors, with state =
+        the 32 bytes of rtmi_tonemap_state as a uint8 tensor, and the decoded exposure dict only with sync=True (which
+        waits for the stream).  ValueError for a shape, dtype, device or contiguity mismatch, HostError for what the entry
+        refuses (a misaligned tensor among it)."""
+        h = self._handle()
+        want = (self.ny, self.nx, 3)
+        if isinstance(linear, np.ndarray) or not hasattr(linear, "data_ptr"):
+            a = np.asarray(linear)
+            if a.shape != want:
+                raise ValueError("linear must have the shape %r, not %r" % (want, a.shape))
+            if a.dtype != np.float32:
+                raise ValueError("linear must be float32, not %s" % a.dtype)
+            a = np.ascontiguousarray(a)
+            out = {"rgb8": np.zeros(want, np.uint8)}
+            if display:
+                out["display"] = np.zeros(want, np.float32)
+            st = abi.TonemapState()
+            self._check(self.lib.rtmi_tonemap_apply(h, a.ctypes.data, dt, out["rgb8"].ctypes.data,
+                                                    out["display"].ctypes.data if display else None, C.byref(st)),
+                        "rtmi_tonemap_apply")
+            out["exposure"] = _tonemap_state(st)
+            return out
+        import torch
+
+        if tuple(linear.shape) != want:
+            raise ValueError("linear must have the shape %r, not %r" % (want, tuple(linear.shape)))
+        if linear.dtype != torch.float32:
+            raise ValueError("linear must be float32, not %s" % linear.dtype)
+        if not linear.is_cuda or linear.device.index != self.device:
+            raise ValueError("linear must be on the handle's device (cuda:%d), not %s" % (self.device, linear.device))
+        if not linear.is_contiguous():
+            raise ValueError("linear must be contiguous")
+        dev = linear.device
+        out = {"rgb8": torch.empty(want, dtype=torch.uint8, device=dev)}
+        if display:
+            out["display"] = torch.empty(want, dtype=torch.float32, device=dev)
+        out["state"] = torch.empty(32, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        self._check(self.lib.rtmi_tonemap_apply_device(h, linear.data_ptr(), dt, out["rgb8"].data_ptr(),
+                                                       out["display"].data_ptr() if display else None,
+                                                       out["state"].data_ptr(), stream.cuda_stream),
+                    "rtmi_tonemap_apply_device")
+        if sync:
+            stream.synchronize()
+            out["exposure"] = _tonemap_state(abi.TonemapState.from_buffer_copy(out["state"].cpu().numpy().tobytes()))
+        return out
+
+    def reset(self):
+        """The next apply is a first apply: it adopts the metered value instead of adapting toward it."""
+        self._check(self.lib.rtmi_tonemap_reset(self._handle()), "rtmi_tonemap_reset")
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            if self in _tonemaps:
+                _tonemaps.remove(self)
+            self.lib.rtmi_tonemap_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def tonemap(linear, device=0, display=False, **kw):
+    """One image through a Tonemap made for it (create, apply once, close): linear float32 [ny,nx,3]; kw: Tonemap's
+    keywords.  A first apply adopts the metered value, so exposure="auto" exposes the image for itself.  Returns
+    Tonemap.apply's dict."""
+    a = np.asarray(linear)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("linear must be [ny, nx, 3], not %r" % (a.shape,))
+    with Tonemap(a.shape[1], a.shape[0], device=device, **kw) as tm:
+        return tm.apply(a, display=display)
 
 
 def pfm_bytes(plane):
