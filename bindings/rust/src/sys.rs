@@ -980,6 +980,136 @@ extern "C" {
     pub fn rtmi_temporal_destroy(h: *mut RtmiTemporal);
 }
 
+// ---- include/rtmi_upscale.h: guided upscaling of a low-resolution frame ------------------------------------------------
+
+pub const RTMI_UPSCALE_BACKGROUND: u8 = 0;
+pub const RTMI_UPSCALE_GUIDED: u8 = 1;
+pub const RTMI_UPSCALE_NEAREST: u8 = 2;
+pub const RTMI_UPSCALE_MISMATCH: u8 = 3;
+
+/// rtmi_upscale_params: the reconstruction's edge-stopping settings (32 bytes); defaults 32, 0.05, 1e-3, 1e-3, 1e-3, 0
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiUpscaleParams {
+    pub normal_power: u32,
+    pub sigma_z: f32,
+    pub eps_z: f32,
+    pub albedo_min: f32,
+    pub w_min: f32,
+    pub flags: u32,
+    pub reserved: [u32; 2],
+}
+
+/// rtmi_upscale_in: the low-resolution planes (ly * lx pixels) and the full-resolution guide (ny * nx pixels) (64 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiUpscaleIn {
+    pub linear_lo: *const f32,
+    pub albedo_lo: *const f32,
+    pub normal_lo: *const f32,
+    pub depth_lo: *const f32,
+    pub albedo: *const f32,
+    pub normal: *const f32,
+    pub depth: *const f32,
+    pub reserved: *const c_void,
+}
+
+/// rtmi_upscale_out: the outputs, each optional, not all NULL (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiUpscaleOut {
+    pub linear: *mut f32,
+    pub rgb8: *mut u8,
+    pub cls: *mut u8,
+    pub reserved: *mut c_void,
+}
+
+/// rtmi_upscaler_opts: the low frame's options (RtmiFrameOpts, declared with rtmi_frame.h below), the reconstruction's and
+/// the low size (160 bytes); guide_ns defaults to 4
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiUpscalerOpts {
+    pub low: RtmiFrameOpts,
+    pub up: RtmiUpscaleParams,
+    pub lx: u32,
+    pub ly: u32,
+    pub guide_ns: u32,
+    pub reserved: [u32; 5],
+}
+
+/// rtmi_upscaler_out: the full-resolution planes and the low frame's (RtmiFrameOut); a NULL plane is not copied (144 bytes)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiUpscalerOut {
+    pub linear: *mut f32,
+    pub rgb8: *mut u8,
+    pub cls: *mut u8,
+    pub albedo: *mut f32,
+    pub normal: *mut f32,
+    pub depth: *mut f32,
+    pub low: RtmiFrameOut,
+}
+
+/// opaque upscaler handle
+#[repr(C)]
+pub struct RtmiUpscaler {
+    _private: [u8; 0],
+}
+
+extern "C" {
+    /// blocking, host pointers; 1 <= lx <= nx <= 32768, 1 <= ly <= ny <= 32768
+    pub fn rtmi_upscale(
+        device: c_int,
+        lx: u32,
+        ly: u32,
+        nx: u32,
+        ny: u32,
+        params: *const RtmiUpscaleParams,
+        input: *const RtmiUpscaleIn,
+        out: *const RtmiUpscaleOut,
+    ) -> c_int;
+    /// asynchronous on `stream` (a hipStream_t), device pointers; float planes 16-byte aligned, rgb8 and cls 4
+    pub fn rtmi_upscale_device(
+        device: c_int,
+        lx: u32,
+        ly: u32,
+        nx: u32,
+        ny: u32,
+        params: *const RtmiUpscaleParams,
+        d_in: *const RtmiUpscaleIn,
+        d_out: *const RtmiUpscaleOut,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// params fixes the full size and what the low frame reads from it; its ns and seed are not read
+    pub fn rtmi_upscaler_create(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiUpscalerOpts,
+        out: *mut *mut RtmiUpscaler,
+    ) -> c_int;
+    /// blocking; renders the low frame and the full-resolution features, reconstructs, copies the planes asked for to the host
+    pub fn rtmi_upscaler_render(
+        h: *mut RtmiUpscaler,
+        cam: *const RtmiCamera,
+        ns: u32,
+        seed: u64,
+        out: *const RtmiUpscalerOut,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the same with device pointers in `out`; blocking too
+    pub fn rtmi_upscaler_render_device(
+        h: *mut RtmiUpscaler,
+        cam: *const RtmiCamera,
+        ns: u32,
+        seed: u64,
+        out: *const RtmiUpscalerOut,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// forgets the frames rendered so far, keeps the allocation
+    pub fn rtmi_upscaler_reset(h: *mut RtmiUpscaler) -> c_int;
+    pub fn rtmi_upscaler_destroy(h: *mut RtmiUpscaler);
+}
+
 // ---- include/rtmi_tonemap.h: tone mapping with histogram auto-exposure -------------------------------------------------
 
 pub const RTMI_TONEMAP_CLAMP: u32 = 0;

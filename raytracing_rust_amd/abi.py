@@ -367,6 +367,40 @@ class TonemapState(C.Structure):
 RTMI_TONEMAP_SYMBOLS = ["rtmi_probe_tonemap_histogram", "rtmi_tonemap_apply", "rtmi_tonemap_apply_device", "rtmi_tonemap_create",
                         "rtmi_tonemap_destroy", "rtmi_tonemap_reset"]
 
+RTMI_UPSCALE_BACKGROUND, RTMI_UPSCALE_GUIDED, RTMI_UPSCALE_NEAREST, RTMI_UPSCALE_MISMATCH = 0, 1, 2, 3  # include/rtmi_upscale.h: cls
+
+
+class UpscaleParams(C.Structure):
+    """rtmi_upscale_params (include/rtmi_upscale.h): the reconstruction's edge-stopping settings (32 bytes)."""
+    _fields_ = [("normal_power", C.c_uint32), ("sigma_z", C.c_float), ("eps_z", C.c_float), ("albedo_min", C.c_float),
+                ("w_min", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class UpscaleIn(C.Structure):
+    """rtmi_upscale_in (include/rtmi_upscale.h): the low-resolution planes and the full-resolution guide (64 bytes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("linear_lo", "albedo_lo", "normal_lo", "depth_lo", "albedo", "normal", "depth", "reserved")]
+
+
+class UpscaleOut(C.Structure):
+    """rtmi_upscale_out (include/rtmi_upscale.h): the outputs, NULL = not written (32 bytes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("linear", "rgb8", "cls", "reserved")]
+
+
+class UpscalerOpts(C.Structure):
+    """rtmi_upscaler_opts (include/rtmi_upscale.h): the low frame's options, the reconstruction's and the low size (160 bytes)."""
+    _fields_ = [("low", FrameOpts), ("up", UpscaleParams), ("lx", C.c_uint32), ("ly", C.c_uint32), ("guide_ns", C.c_uint32),
+                ("reserved", C.c_uint32 * 5)]
+
+
+class UpscalerOut(C.Structure):
+    """rtmi_upscaler_out (include/rtmi_upscale.h): the full-resolution planes and the low frame's, NULL = not copied (144 bytes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("linear", "rgb8", "cls", "albedo", "normal", "depth")] + [("low", FrameOut)]
+
+
+# the functions of include/rtmi_upscale.h (guided upscaling), kept apart from those of the other headers
+RTMI_UPSCALE_SYMBOLS = ["rtmi_upscale", "rtmi_upscale_device", "rtmi_upscaler_create", "rtmi_upscaler_destroy", "rtmi_upscaler_render",
+                        "rtmi_upscaler_render_device", "rtmi_upscaler_reset"]
+
 _rtmi = None
 _host = None
 
@@ -549,6 +583,19 @@ def load_rtmi():
     lib.rtmi_tonemap_destroy.argtypes = [vp]
     lib.rtmi_probe_tonemap_histogram.restype = C.c_int
     lib.rtmi_probe_tonemap_histogram.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TonemapParams), vp, vp]
+    lib.rtmi_upscale.restype = C.c_int
+    lib.rtmi_upscale.argtypes = [C.c_int] + [C.c_uint32] * 4 + [C.POINTER(UpscaleParams), C.POINTER(UpscaleIn), C.POINTER(UpscaleOut)]
+    lib.rtmi_upscale_device.restype = C.c_int
+    lib.rtmi_upscale_device.argtypes = lib.rtmi_upscale.argtypes + [vp]
+    lib.rtmi_upscaler_create.restype = C.c_int
+    lib.rtmi_upscaler_create.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(UpscalerOpts), C.POINTER(vp)]
+    for fn in (lib.rtmi_upscaler_render, lib.rtmi_upscaler_render_device):
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.POINTER(Camera), C.c_uint32, C.c_uint64, C.POINTER(UpscalerOut), C.POINTER(Stats)]
+    lib.rtmi_upscaler_reset.restype = C.c_int
+    lib.rtmi_upscaler_reset.argtypes = [vp]
+    lib.rtmi_upscaler_destroy.restype = None
+    lib.rtmi_upscaler_destroy.argtypes = [vp]
     _rtmi = lib
     return lib
 
@@ -631,6 +678,10 @@ def load_host():
         "rth_frame_close": (i, [vp]),
         "rth_frame_render": (i, [vp, vp, u32, u64, C.POINTER(FrameOut), i, C.POINTER(Stats)]),
         "rth_frame_reset": (i, [vp]),
+        "rth_upscaler_create": (vp, [vp, C.POINTER(RenderParams), C.POINTER(UpscalerOpts)]),
+        "rth_upscaler_close": (i, [vp]),
+        "rth_upscaler_render": (i, [vp, vp, u32, u64, C.POINTER(UpscalerOut), i, C.POINTER(Stats)]),
+        "rth_upscaler_reset": (i, [vp]),
         "rth_trace": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_occluded": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_trace_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),

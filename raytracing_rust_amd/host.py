@@ -12,6 +12,7 @@ lowered to the flat scene of include/rtmi.h and rendered by the HIP kernels.  Th
 no CPU fallback for rendering: without the extension or without a GPU, render raises.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -547,6 +548,35 @@ class Scene:
         if not h:
             self.host._raise()
         return Frame(self.host, h, nx, ny, self.device, temporal is not None, keep=(self, p))
+
+    def upscaler(self, nx, ny, low=None, scale=2.0, guide_ns=4, estimator="plain", temporal=(), denoise=(), coop=False,
+                 env_select_p=0.5, upscale=None, **kw):
+        """An upscaler handle (include/rtmi_upscale.h): a frame handle at a low resolution whose image is
+        rebuilt at nx x ny on the device, guided by first-hit features rendered at the full size with guide_ns samples per
+        pixel.  low = (lx, ly): the low resolution; otherwise scale gives lx = ceil(nx / scale), ly = ceil(ny / scale).
+        estimator, temporal, denoise, coop, env_select_p and the other keywords: Scene.frame's, for the low frame.
+        upscale: dict of upscale()'s parameter keywords ({} or None: its defaults).  All device memory is allocated here,
+        once.  A scene resident on a device list (upload_multi) raises Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        if coop and estimator == "plain":
+            raise ValueError("coop=True needs a lit estimator: the plain render is cooperative by default")
+        if low is None:
+            if not scale >= 1.0:
+                raise ValueError("scale must be at least 1")
+            low = (int(math.ceil(nx / scale)), int(math.ceil(ny / scale)))
+        lx, ly = int(low[0]), int(low[1])
+        _coop_flags(kw, coop)
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, 2, **kw)
+        fo = abi.FrameOpts(abi.ROULETTE_ESTIMATORS[estimator], env_select_p, _temporal_params(**dict(temporal or ())),
+                           _denoise_params(**dict(denoise or ())),
+                           (abi.RTMI_FRAME_NO_TEMPORAL if temporal is None else 0) | (abi.RTMI_FRAME_NO_FILTER if denoise is False else 0))
+        o = abi.UpscalerOpts(fo, _upscale_params(**dict(upscale or ())), lx, ly, guide_ns)
+        h = self.host.lib.rth_upscaler_create(self.h, C.byref(p), C.byref(o))
+        if not h:
+            self.host._raise()
+        return Upscaler(self.host, h, nx, ny, lx, ly, self.device, keep=(self, p))
 
     def render_multi(self, cam, nx, ny, ns, devices, **kw):
         """Whole image on several GPUs of this process (rtmi_render_multi): tiles t % len(devices), one gather.
@@ -1120,6 +1150,88 @@ class Frame:
         return False
 
 
+# the planes of rtmi_upscaler_out in Upscaler.render's result: (group, name in the group, field, low size, channels, dtype)
+_UPSCALER_PLANES = ((None, "linear", "linear", False, (3,), "float32"), (None, "rgb8", "rgb8", False, (3,), "uint8"),
+                    (None, "cls", "cls", False, (), "uint8"),
+                    ("guide", "albedo", "albedo", False, (3,), "float32"), ("guide", "normal", "normal", False, (3,), "float32"),
+                    ("guide", "depth", "depth", False, (), "float32"),
+                    ("low", "linear", "linear", True, (3,), "float32"), ("low", "albedo", "albedo", True, (3,), "float32"),
+                    ("low", "normal", "normal", True, (3,), "float32"), ("low", "depth", "depth", True, (), "float32"))
+
+
+class Upscaler:
+    """An upscaler handle of Scene.upscaler (include/rtmi_upscale.h): nx x ny images rebuilt from lx x ly frames.  Calls on
+    one handle serialise on a lock of its own; a render holds its scene twice (the low frame, then the features and the
+    reconstruction), and another render of the scene may run between the two without touching the handle's planes.  close() frees its device memory (the low frame's, 40 B per low pixel
+    and 16 B per full pixel); Host.free_all() closes what is still open.  Usable as a context manager."""
+
+    def __init__(self, host, h, nx, ny, lx, ly, device, keep=()):
+        self.host, self.h, self.nx, self.ny, self.lx, self.ly, self.device, self.keep = host, h, nx, ny, lx, ly, device, keep
+        host._upscalers = getattr(host, "_upscalers", []) + [self]
+
+    def _handle(self):
+        if not self.h:
+            raise HostError("the upscaler is closed")
+        return self.h
+
+    def render(self, cam, ns, seed=0, aux=False, out="numpy", tonemap=None, dt=0.0):
+        """One frame under `cam` (a Camera of Host): the low frame with ns >= 2 samples per pixel, rebuilt at the full size.
+        Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], cls u8 [ny,nx] (0 background, 1 guided, 2 nearest-similar,
+        3 mismatch), stats); aux=True adds guide = dict(albedo, normal, depth) at the full size and low = dict(linear,
+        albedo, normal, depth) at the low size: what upscale() takes.  out="numpy": host arrays; out="torch": torch tensors
+        on the scene's device, written by the device form without a host copy.  tonemap: a Tonemap of the full size and
+        the scene's device (ValueError otherwise); rgb8 is then tonemap.apply(linear, dt)'s, as Frame.render composes it,
+        and exposure = its state is added."""
+        h = self._handle()
+        if out not in ("numpy", "torch"):
+            raise ValueError("out must be 'numpy' or 'torch'")
+        if tonemap is not None and (not isinstance(tonemap, Tonemap) or (tonemap.nx, tonemap.ny, tonemap.device) !=
+                                    (self.nx, self.ny, self.device)):
+            raise ValueError("tonemap must be a Tonemap of the full size (%d x %d) and device (%d)" % (self.nx, self.ny, self.device))
+        if out == "torch":
+            import torch
+
+            dev = torch.device("cuda", self.device)
+        res, ptrs = {}, abi.UpscalerOut()
+        for group, name, field, low, ch, dtype in _UPSCALER_PLANES:
+            if group and not aux:
+                continue
+            shape = ((self.ly, self.lx) if low else (self.ny, self.nx)) + ch
+            if out == "torch":
+                a = torch.empty(shape, dtype=getattr(torch, dtype), device=dev)
+                addr = a.data_ptr()
+            else:
+                a = np.zeros(shape, dtype)
+                addr = a.ctypes.data
+            setattr(ptrs.low if low else ptrs, field, addr)
+            (res.setdefault(group, {}) if group else res)[name] = a
+        st = abi.Stats()
+        self.host._check(self.host.lib.rth_upscaler_render(h, cam.h, ns, int(seed) & (2 ** 64 - 1), C.byref(ptrs),
+                                                            1 if out == "torch" else 0, C.byref(st)))
+        res["stats"] = _stats(st)
+        if tonemap is not None:
+            tm = tonemap.apply(res["linear"], dt=dt, sync=True)
+            res["rgb8"], res["exposure"] = tm["rgb8"], tm["exposure"]
+        return res
+
+    def reset(self):
+        """Forgets the frames rendered so far: the next frame starts a fresh history."""
+        self.host._check(self.host.lib.rth_upscaler_reset(self._handle()))
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.host._upscalers = [u for u in getattr(self.host, "_upscalers", []) if u is not self]
+            self.host._check(self.host.lib.rth_upscaler_close(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 def _outputs(ny, nx, names, sig=None):
     """The zeroed planes `names` of a render as its result dict, and the trailing arguments of the native entry: the
     planes' addresses in that order, the path signatures' (u64 [ny,nx]; NULL unless sig; sig=None: the entry takes none;
@@ -1211,6 +1323,8 @@ class Host:
             ses.close()
         for frm in list(getattr(self, "_frames", [])):  # ... and frames
             frm.close()
+        for ups in list(getattr(self, "_upscalers", [])):  # ... and upscalers
+            ups.close()
         for tmp in list(_temporals):
             tmp.close()
         for tm in list(_tonemaps):
@@ -1630,6 +1744,66 @@ def tonemap(linear, device=0, display=False, **kw):
         raise ValueError("linear must be [ny, nx, 3], not %r" % (a.shape,))
     with Tonemap(a.shape[1], a.shape[0], device=device, **kw) as tm:
         return tm.apply(a, display=display)
+
+
+def _upscale_params(normal_power=32, sigma_z=0.05, eps_z=1e-3, albedo_min=1e-3, w_min=1e-3):
+    """upscale()'s parameter keywords as rtmi_upscale_params."""
+    return abi.UpscaleParams(normal_power, sigma_z, eps_z, albedo_min, w_min, 0)
+
+
+def upscale(linear_lo, albedo_lo, normal_lo, depth_lo, albedo, normal, depth, device=0, **params):
+    """The guided reconstruction of include/rtmi_upscale.h: linear_lo, albedo_lo and normal_lo are float32
+    [ly,lx,3] and depth_lo float32 [ly,lx], the low-resolution image and its first-hit features; albedo, normal [ny,nx,3]
+    and depth [ny,nx] are the full-resolution guide (non-finite depth = no surface), lx <= nx and ly <= ny, row 0 the top
+    row.  params: normal_power=32, sigma_z=0.05, eps_z=1e-3, albedo_min=1e-3, w_min=1e-3.  numpy arrays go through the
+    blocking host form on `device`; torch tensors (all on one device, contiguous) go through the device form on torch's
+    current stream, without a copy or a wait.  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], cls u8 [ny,nx]: 0
+    background, 1 guided, 2 nearest-similar, 3 mismatch).  ValueError for a shape, dtype, device or contiguity mismatch,
+    HostError for what the entry refuses (a misaligned tensor among it)."""
+    names = ("linear_lo", "albedo_lo", "normal_lo", "depth_lo", "albedo", "normal", "depth")
+    planes = dict(zip(names, (linear_lo, albedo_lo, normal_lo, depth_lo, albedo, normal, depth)))
+    on_device = all(hasattr(a, "data_ptr") and not isinstance(a, np.ndarray) for a in planes.values())
+    if not on_device:
+        planes = {n: np.asarray(a) for n, a in planes.items()}
+    if planes["depth_lo"].ndim != 2 or planes["depth"].ndim != 2:
+        raise ValueError("depth_lo and depth must be [ly, lx] and [ny, nx]")
+    (ly, lx), (ny, nx) = tuple(planes["depth_lo"].shape), tuple(planes["depth"].shape)
+    if on_device:
+        import torch
+
+        f32, dev = torch.float32, planes["depth"].device
+    else:
+        f32 = np.float32
+    for n, a in planes.items():
+        want = ((ly, lx) if n.endswith("_lo") else (ny, nx)) + (() if n.startswith("depth") else (3,))
+        if tuple(a.shape) != want:
+            raise ValueError("%s must have the shape %r, not %r" % (n, want, tuple(a.shape)))
+        if a.dtype != f32:
+            raise ValueError("%s must be float32, not %s" % (n, a.dtype))
+        if on_device:
+            if not a.is_cuda or a.device != dev:
+                raise ValueError("%s must be on the device of depth (%s), not %s" % (n, dev, a.device))
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % n)
+        else:
+            planes[n] = np.ascontiguousarray(a)
+    p = _upscale_params(**params)
+    lib = abi.load_rtmi()
+    if on_device:
+        out = {"linear": torch.empty((ny, nx, 3), dtype=f32, device=dev), "rgb8": torch.empty((ny, nx, 3), dtype=torch.uint8, device=dev),
+               "cls": torch.empty((ny, nx), dtype=torch.uint8, device=dev)}
+        i = abi.UpscaleIn(*[planes[n].data_ptr() for n in names])
+        o = abi.UpscaleOut(out["linear"].data_ptr(), out["rgb8"].data_ptr(), out["cls"].data_ptr())
+        rc, what = lib.rtmi_upscale_device(dev.index, lx, ly, nx, ny, C.byref(p), C.byref(i), C.byref(o),
+                                           torch.cuda.current_stream(dev).cuda_stream), "rtmi_upscale_device"
+    else:
+        out = {"linear": np.zeros((ny, nx, 3), np.float32), "rgb8": np.zeros((ny, nx, 3), np.uint8), "cls": np.zeros((ny, nx), np.uint8)}
+        i = abi.UpscaleIn(*[planes[n].ctypes.data for n in names])
+        o = abi.UpscaleOut(out["linear"].ctypes.data, out["rgb8"].ctypes.data, out["cls"].ctypes.data)
+        rc, what = lib.rtmi_upscale(device, lx, ly, nx, ny, C.byref(p), C.byref(i), C.byref(o)), "rtmi_upscale"
+    if rc != 0:
+        raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, lib.rtmi_last_error().decode()))
+    return out
 
 
 def pfm_bytes(plane):

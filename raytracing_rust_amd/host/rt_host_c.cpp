@@ -18,6 +18,7 @@
 #include "rtmi_radiance.h"
 #include "rtmi_gather.h"
 #include "rtmi_frame.h"
+#include "rtmi_upscale.h"
 
 using namespace rt;
 
@@ -43,6 +44,7 @@ std::mutex g_mu;
 std::vector<Obj *> g_objs;
 std::vector<rtmi_session *> g_sessions; // the live render sessions (rth_session_*): freed before their scenes
 std::vector<rtmi_frame *> g_frames;     // the live frame handles (rth_frame_*): freed before their scenes
+std::vector<rtmi_upscaler *> g_upscalers; // the live upscalers (rth_upscaler_*): freed before their scenes
 
 Obj *reg(Obj *o) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -100,6 +102,8 @@ RTH_API void rth_free_all(void) {
     g_sessions.clear();
     for (rtmi_frame *f : g_frames) rtmi_frame_destroy(f);
     g_frames.clear();
+    for (rtmi_upscaler *u : g_upscalers) rtmi_upscaler_destroy(u);
+    g_upscalers.clear();
     for (Obj *o : g_objs) {
         if (o->dev) rtmi_scene_destroy(o->dev);
         if (o->multi) rtmi_multi_destroy(o->multi);
@@ -572,6 +576,49 @@ RTH_API int rth_frame_render(void *frame, void *cam, uint32_t ns, uint64_t seed,
 }
 RTH_API int rth_frame_reset(void *frame) {
     return guard([&] { return done("rtmi_frame_reset", rtmi_frame_reset(FRM(frame)), CODED); });
+}
+// guided upscaling (include/rtmi_upscale.h): the handle's entries one to one on the uploaded scene, as the frame wrappers; an
+// upscaler is freed by rth_upscaler_close or, at the latest, by rth_free_all (before the scenes).
+static rtmi_upscaler *UPS(void *h) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    for (rtmi_upscaler *u : g_upscalers)
+        if (u == h) return u;
+    throw std::runtime_error("handle is not a live upscaler");
+}
+RTH_API void *rth_upscaler_create(void *lowered, const rtmi_render_params *p, const rtmi_upscaler_opts *opts) {
+    return guard_new([&] {
+        const char *name = "rtmi_upscaler_create";
+        rtmi_scene *dev = DEV(lowered, name, "upscaler");
+        rtmi_upscaler *u = nullptr;
+        done(name, rtmi_upscaler_create(dev, p, opts, &u), CODED_UNSUPPORTED);
+        std::lock_guard<std::mutex> lk(g_mu);
+        g_upscalers.push_back(u);
+        return (void *)u;
+    });
+}
+RTH_API int rth_upscaler_close(void *upscaler) {
+    return guard([&] {
+        rtmi_upscaler *u = UPS(upscaler);
+        {
+            std::lock_guard<std::mutex> lk(g_mu);
+            g_upscalers.erase(std::find(g_upscalers.begin(), g_upscalers.end(), u));
+        }
+        rtmi_upscaler_destroy(u);
+        return RTH_OK;
+    });
+}
+RTH_API int rth_upscaler_render(void *upscaler, void *cam, uint32_t ns, uint64_t seed, const rtmi_upscaler_out *out, int on_device,
+                                rtmi_stats *stats) {
+    return guard([&] {
+        const rtmi_camera c = CAM(cam).lower();
+        if (on_device)
+            return done("rtmi_upscaler_render_device", rtmi_upscaler_render_device(UPS(upscaler), &c, ns, seed, out, stats),
+                        CODED_UNSUPPORTED);
+        return done("rtmi_upscaler_render", rtmi_upscaler_render(UPS(upscaler), &c, ns, seed, out, stats), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_upscaler_reset(void *upscaler) {
+    return guard([&] { return done("rtmi_upscaler_reset", rtmi_upscaler_reset(UPS(upscaler)), CODED); });
 }
 RTH_API int rth_probe_env(void *lowered, int op, const float *in, float *out, uint32_t n) {
     return guard([&] { return done("rtmi_probe_env", rtmi_probe_env(DEV(lowered), op, in, out, n), CODED); });
