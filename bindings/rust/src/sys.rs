@@ -980,6 +980,111 @@ extern "C" {
     pub fn rtmi_temporal_destroy(h: *mut RtmiTemporal);
 }
 
+// ---- include/rtmi_sparse.h: sparse renders (select, trace and patch chosen pixels) --------------------------------------
+
+/// rtmi_sparse_params: a list's length (host forms) or capacity (device forms), the samples per entry and the estimator
+/// (32 bytes); sample s of an entry is the full render's sample first_sample + s of that pixel
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiSparseParams {
+    pub n: u32,
+    pub ns: u32,
+    pub first_sample: u32,
+    pub estimator: u32,
+    pub env_select_p: f32,
+    pub reserved: [u32; 3],
+}
+
+extern "C" {
+    /// the bytes of scratch that serve every entry below; pure host code
+    pub fn rtmi_sparse_scratch_bytes(n_pixels: u64, capacity: u32, ns: u32) -> u64;
+    /// asynchronous, device pointers: the ascending list of the pixels whose byte b has b < 32 and bit b of accept_mask set;
+    /// d_count receives {written, selected}
+    pub fn rtmi_sparse_select_device(
+        device: c_int,
+        n: u32,
+        d_bytes: *const c_void,
+        accept_mask: u32,
+        capacity: u32,
+        d_list: *mut c_void,
+        d_count: *mut c_void,
+        d_scratch: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// blocking, host pointers; pixels: sp.n indices below nx * ny; each output optional, not all NULL
+    pub fn rtmi_sparse_render(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        cam: *const RtmiCamera,
+        sp: *const RtmiSparseParams,
+        pixels: *const u32,
+        out_mean: *mut f32,
+        out_stderr: *mut f32,
+        out_samples: *mut f32,
+        kernel_ms: *mut f64,
+    ) -> c_int;
+    /// asynchronous, device pointers; the entries are min(d_count[0], sp.n), read by the kernels (d_count NULL: sp.n);
+    /// d_samples (sp.n * ns * 12 bytes) is required
+    pub fn rtmi_sparse_render_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        cam: *const RtmiCamera,
+        sp: *const RtmiSparseParams,
+        d_pixels: *const c_void,
+        d_count: *const c_void,
+        d_mean: *mut c_void,
+        d_stderr: *mut c_void,
+        d_samples: *mut c_void,
+        d_scratch: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// asynchronous, device pointers: the records written to the planes at their pixels; each plane optional
+    pub fn rtmi_sparse_patch_device(
+        device: c_int,
+        n_pixels: u32,
+        d_list: *const c_void,
+        d_count: *const c_void,
+        capacity: u32,
+        d_mean: *const c_void,
+        d_linear: *mut c_void,
+        d_rgb8: *mut c_void,
+        d_bytes: *mut c_void,
+        mark: u32,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// select -> sparse render -> patch enqueued in one call; sp.n is the budget of pixels
+    pub fn rtmi_sparse_refine_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        cam: *const RtmiCamera,
+        sp: *const RtmiSparseParams,
+        accept_mask: u32,
+        mark: u32,
+        d_bytes: *mut c_void,
+        d_linear: *mut c_void,
+        d_rgb8: *mut c_void,
+        d_stderr: *mut c_void,
+        d_scratch: *mut c_void,
+        scratch_bytes: u64,
+        d_count_out: *mut c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// the blocking host-plane form; counts receives {patched, selected}
+    pub fn rtmi_sparse_refine(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        cam: *const RtmiCamera,
+        sp: *const RtmiSparseParams,
+        accept_mask: u32,
+        mark: u32,
+        bytes: *mut u8,
+        linear: *mut f32,
+        rgb8: *mut u8,
+        stderr_rgb: *mut f32,
+        counts: *mut u32,
+    ) -> c_int;
+}
+
 // ---- include/rtmi_upscale.h: guided upscaling of a low-resolution frame ------------------------------------------------
 
 pub const RTMI_UPSCALE_BACKGROUND: u8 = 0;

@@ -401,6 +401,17 @@ class UpscalerOut(C.Structure):
 RTMI_UPSCALE_SYMBOLS = ["rtmi_upscale", "rtmi_upscale_device", "rtmi_upscaler_create", "rtmi_upscaler_destroy", "rtmi_upscaler_render",
                         "rtmi_upscaler_render_device", "rtmi_upscaler_reset"]
 
+
+class SparseParams(C.Structure):
+    """rtmi_sparse_params (include/rtmi_sparse.h): a list's length or capacity, samples and estimator (32 bytes)."""
+    _fields_ = [("n", C.c_uint32), ("ns", C.c_uint32), ("first_sample", C.c_uint32), ("estimator", C.c_uint32),
+                ("env_select_p", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+# the functions of include/rtmi_sparse.h (sparse renders), kept apart from those of the other headers
+RTMI_SPARSE_SYMBOLS = ["rtmi_sparse_patch_device", "rtmi_sparse_refine", "rtmi_sparse_refine_device", "rtmi_sparse_render",
+                       "rtmi_sparse_render_device", "rtmi_sparse_scratch_bytes", "rtmi_sparse_select_device"]
+
 _rtmi = None
 _host = None
 
@@ -596,6 +607,21 @@ def load_rtmi():
     lib.rtmi_upscaler_reset.argtypes = [vp]
     lib.rtmi_upscaler_destroy.restype = None
     lib.rtmi_upscaler_destroy.argtypes = [vp]
+    lib.rtmi_sparse_scratch_bytes.restype = C.c_uint64
+    lib.rtmi_sparse_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.rtmi_sparse_select_device.restype = C.c_int
+    lib.rtmi_sparse_select_device.argtypes = [C.c_int, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    lib.rtmi_sparse_patch_device.restype = C.c_int
+    lib.rtmi_sparse_patch_device.argtypes = [C.c_int, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp]
+    sparse = [vp, C.POINTER(RenderParams), C.POINTER(Camera), C.POINTER(SparseParams)]
+    lib.rtmi_sparse_render.restype = C.c_int
+    lib.rtmi_sparse_render.argtypes = sparse + [vp, vp, vp, vp, C.POINTER(C.c_double)]
+    lib.rtmi_sparse_render_device.restype = C.c_int
+    lib.rtmi_sparse_render_device.argtypes = sparse + [vp] * 7
+    lib.rtmi_sparse_refine_device.restype = C.c_int
+    lib.rtmi_sparse_refine_device.argtypes = sparse + [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
+    lib.rtmi_sparse_refine.restype = C.c_int
+    lib.rtmi_sparse_refine.argtypes = sparse + [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
     _rtmi = lib
     return lib
 
@@ -688,6 +714,9 @@ def load_host():
         "rth_occluded_device": (i, [vp, C.POINTER(QueryParams), vp, vp, vp, vp]),
         "rth_radiance": (i, [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_radiance_device": (i, [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, vp]),
+        "rth_sparse_render": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams), vp, vp, vp, vp, C.POINTER(C.c_double)]),
+        "rth_sparse_render_device": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams)] + [vp] * 7),
+        "rth_sparse_refine": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams), u32, u32, vp, vp, vp, vp, vp, u64, vp, i, vp]),
         "rth_gather": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_gather_device": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),

@@ -59,6 +59,8 @@
 #include "rtmi_radiance_launch.hpp"
 #include "rtmi_gather.h"
 #include "rtmi_gather_launch.hpp"
+#include "rtmi_sparse.h"
+#include "rtmi_sparse_launch.hpp"
 #include "rtmi_frame_launch.hpp"
 
 // ======================================================================================
@@ -2809,6 +2811,305 @@ extern "C" int rtmi_gather_device(rtmi_scene *s, const rtmi_gather_params *p, co
                                     sh ? sh + 108 * at : nullptr, d_scratch))
             return rc;
     }
+    return RTMI_OK;
+}
+
+// ---- sparse renders (include/rtmi_sparse.h) ---------------------------------------------------------------------------------
+#define RTMI_SPARSE_MAX_PIXELS (32768ull * 32768ull)
+// the caller's scratch, in bytes from its start: control words | per-workgroup counts | list | mean | stderr | samples
+struct SparseScratch {
+    uint64_t counts, list, mean, se, samples, total;
+};
+static SparseScratch sparse_scratch(uint64_t n_pixels, uint32_t capacity, uint32_t ns) {
+    const auto up16 = [](uint64_t b) { return (b + 15ull) & ~15ull; };
+    SparseScratch L;
+    L.counts = 4ull * RTMI_SPARSE_HEAD_WORDS;
+    L.list = L.counts + up16(4ull * ((n_pixels + RTMI_SPARSE_SPAN - 1ull) / RTMI_SPARSE_SPAN));
+    L.mean = L.list + up16(4ull * capacity);
+    L.se = L.mean + up16(12ull * capacity);
+    L.samples = L.se + up16(12ull * capacity);
+    L.total = L.samples + up16(12ull * capacity * ns);
+    return L;
+}
+extern "C" uint64_t rtmi_sparse_scratch_bytes(uint64_t n_pixels, uint32_t capacity, uint32_t ns) {
+    return sparse_scratch(n_pixels, capacity, ns).total;
+}
+static bool sparse_misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1u)) != 0u; }
+// the end of the stateless entries' checks: the device
+static int sparse_device(const std::string &nm, int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RTMI_ERR_DEVICE, nm + "no HIP device available");
+    if (device < 0 || device >= n) return fail(RTMI_ERR_DEVICE, nm + "device index out of range");
+    HIP_TRY(hipSetDevice(device));
+    return RTMI_OK;
+}
+extern "C" int rtmi_sparse_select_device(int device, uint32_t n, const void *d_bytes, uint32_t accept_mask, uint32_t capacity,
+                                         void *d_list, void *d_count, void *d_scratch, void *stream) {
+    const std::string nm = "rtmi_sparse_select_device: ";
+    if (!d_bytes || !d_list || !d_count || !d_scratch) return fail(RTMI_ERR_INVALID, nm + "NULL argument");
+    if (n == 0u || n > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "n must be in 1 .. 32768^2");
+    if (capacity == 0u) return fail(RTMI_ERR_INVALID, nm + "capacity must be at least 1");
+    if (sparse_misaligned(d_list, 4) || sparse_misaligned(d_count, 4) || sparse_misaligned(d_scratch, 16))
+        return fail(RTMI_ERR_INVALID, nm + "misaligned list, count (4 bytes) or scratch (16 bytes)");
+    if (int rc = sparse_device(nm, device)) return rc;
+    uint32_t *scratch = reinterpret_cast<uint32_t *>(d_scratch);
+    HIP_TRY(rtmi_sparse_launch_select(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t *>(d_bytes), n, accept_mask,
+                                      capacity, reinterpret_cast<uint32_t *>(d_list), reinterpret_cast<uint32_t *>(d_count),
+                                      scratch + RTMI_SPARSE_HEAD_WORDS));
+    return RTMI_OK;
+}
+extern "C" int rtmi_sparse_patch_device(int device, uint32_t n_pixels, const void *d_list, const void *d_count, uint32_t capacity,
+                                        const void *d_mean, void *d_linear, void *d_rgb8, void *d_bytes, uint32_t mark, void *stream) {
+    const std::string nm = "rtmi_sparse_patch_device: ";
+    if (!d_list || !d_mean) return fail(RTMI_ERR_INVALID, nm + "NULL argument");
+    if (!d_linear && !d_rgb8 && !d_bytes) return fail(RTMI_ERR_INVALID, nm + "every plane is NULL");
+    if (n_pixels == 0u || n_pixels > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "n_pixels must be in 1 .. 32768^2");
+    if (capacity == 0u) return fail(RTMI_ERR_INVALID, nm + "capacity must be at least 1");
+    if (mark > 255u) return fail(RTMI_ERR_INVALID, nm + "mark must be a byte");
+    if (sparse_misaligned(d_list, 4) || sparse_misaligned(d_count, 4) || sparse_misaligned(d_mean, 4) || sparse_misaligned(d_linear, 4))
+        return fail(RTMI_ERR_INVALID, nm + "misaligned list, count, mean or linear (4 bytes)");
+    if (int rc = sparse_device(nm, device)) return rc;
+    HIP_TRY(rtmi_sparse_launch_patch(reinterpret_cast<hipStream_t>(stream), n_pixels, reinterpret_cast<const uint32_t *>(d_list),
+                                     reinterpret_cast<const uint32_t *>(d_count), capacity, reinterpret_cast<const float *>(d_mean),
+                                     nullptr, reinterpret_cast<float *>(d_linear), reinterpret_cast<uint8_t *>(d_rgb8), nullptr,
+                                     reinterpret_cast<uint8_t *>(d_bytes), mark));
+    return RTMI_OK;
+}
+static Estimator sparse_estimator(const char *name, const rtmi_sparse_params *sp, const std::string &null_scene) {
+    const bool nee = sp->estimator == RTMI_ROULETTE_NEE || sp->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool env = sp->estimator == RTMI_ROULETTE_ENV || sp->estimator == RTMI_ROULETTE_ENV_NEE;
+    return Estimator{name, nee, env, nee && env ? sp->env_select_p : 1.0f, null_scene.c_str(),
+                     "no light table attached (rtmi_scene_attach_lights)"};
+}
+// The checks the render and refine entries share, in this order: the pointers, the outputs, the values, what the estimator
+// needs attached (of a handle that is there), the reserved words, the flags.  The entry's own checks and the NULL handle
+// follow in the entries, so everything here is answered for a NULL handle too.
+static int sparse_check(const char *name, const rtmi_scene *s_in, const rtmi_render_params *p, const rtmi_camera *cam,
+                        const rtmi_sparse_params *sp, const void *pixels, const char *pixels_msg, bool has_out, const char *out_msg) {
+    const std::string nm = std::string(name) + ": ";
+    if (!p || !cam || !sp) return fail(RTMI_ERR_INVALID, nm + "NULL argument (params, cam or sp)");
+    if (!pixels) return fail(RTMI_ERR_INVALID, nm + pixels_msg);
+    if (!has_out) return fail(RTMI_ERR_INVALID, nm + out_msg);
+    if (sp->ns == 0u) return fail(RTMI_ERR_INVALID, nm + "ns must be at least 1");
+    if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
+    if (sp->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if ((uint64_t)sp->first_sample + sp->ns > (1ull << 32))
+        return fail(RTMI_ERR_INVALID, nm + "first_sample + ns must not exceed 2^32 (a sample index would wrap onto another sample's stream)");
+    if ((uint64_t)sp->n * sp->ns >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "n * ns must be below 2^31");
+    const bool env = sp->estimator == RTMI_ROULETTE_ENV || sp->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool nee = sp->estimator == RTMI_ROULETTE_NEE || sp->estimator == RTMI_ROULETTE_ENV_NEE;
+    if (sp->estimator == RTMI_ROULETTE_ENV_NEE && !(sp->env_select_p > 0.0f && sp->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
+    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (p->nx == 0u || p->ny == 0u || (uint64_t)p->nx * p->ny > 0xffffffffull)
+        return fail(RTMI_ERR_INVALID, nm + "the image must have 1 .. 2^32 - 1 pixels");
+    if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
+    if (s_in) {
+        rtmi_scene *s = const_cast<rtmi_scene *>(s_in);
+        std::lock_guard<std::mutex> lock(s->mu);
+        if (env && !s->has_env) return fail(RTMI_ERR_INVALID, nm + "no environment map attached (rtmi_scene_attach_env)");
+        if (nee && !s->has_lights) return fail(RTMI_ERR_INVALID, nm + "no light table attached (rtmi_scene_attach_lights)");
+    }
+    if (sp->reserved[0] || sp->reserved[1] || sp->reserved[2]) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
+    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+        return fail(RTMI_ERR_UNSUPPORTED, nm + "sparse renders accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
+    return RTMI_OK;
+}
+// The launches of a list on `stream`: the path kernel on the persistent grid of the per-lane render kernels, sized for the
+// capacity sp->n and fed by `queue` (zeroed here, on the call's stream), then the resolve.  The kernels read the count.
+static int sparse_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_params *p, const rtmi_camera *cam,
+                          const rtmi_sparse_params *sp, hipStream_t stream, const void *d_pixels, const void *d_count, void *d_mean,
+                          void *d_stderr, void *d_samples, unsigned int *queue) {
+    rtmi_render_params rp = *p;
+    rp.ns = 1u; rp.tile_rank = 0u; rp.tile_world = 1u; // the image's nx, ny, seed, max_depth, t_min and flags; no pass is planned
+    DevParams P = dev_params(s, &rp);
+    P.samples = reinterpret_cast<Rad3 *>(d_samples);
+    const DevCamera C = dev_camera(cam);
+    DevLights L;
+    DevEnv E;
+    dev_lighting(s, m.nee, m.env, m.env_select_p, L, E);
+    SparseBatch B{};
+    B.list = reinterpret_cast<const uint32_t *>(d_pixels);
+    B.count = reinterpret_cast<const uint32_t *>(d_count);
+    B.mean = reinterpret_cast<float *>(d_mean);
+    B.stderr_out = reinterpret_cast<float *>(d_stderr);
+    B.queue = queue;
+    B.n = sp->n; B.ns = sp->ns; B.first_sample = sp->first_sample;
+    // chunks as radiance_enqueue sizes them, for a full list
+    const uint32_t total = sp->n * sp->ns;
+    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
+    const uint32_t share = (uint32_t)(((uint64_t)total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
+    B.chunk = share < 64u ? 64u : (share > RTMI_RADIANCE_CHUNK ? RTMI_RADIANCE_CHUNK : share);
+    const uint32_t nchunks = (total + B.chunk - 1u) / B.chunk;
+    const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
+    HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned int), stream));
+    HIP_TRY(rtmi_sparse_launch(fast, m.nee, m.env, nchunks < slots ? nchunks : slots, stream, s->dev, C, P, B, L, E));
+    if (d_mean || d_stderr) HIP_TRY(rtmi_sparse_launch_resolve(stream, P.samples, B));
+    return RTMI_OK;
+}
+extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
+                                  const uint32_t *pixels, float *out_mean, float *out_stderr, float *out_samples, double *kernel_ms) {
+    const char *name = "rtmi_sparse_render";
+    int rc;
+    if ((rc = sparse_check(name, s, p, cam, sp, pixels, "pixels is NULL", out_mean || out_stderr || out_samples, "every output is NULL")))
+        return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const uint32_t npix = p->nx * p->ny;
+    for (uint32_t k = 0; k < sp->n; k++)
+        if (pixels[k] >= npix)
+            return fail(RTMI_ERR_INVALID, std::string(name) + ": pixels[" + std::to_string(k) + "] = " + std::to_string(pixels[k]) +
+                                              " is outside the image");
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = sparse_estimator(name, sp, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    if (sp->n == 0u) return RTMI_OK;
+    RenderCall c;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    const size_t n = sp->n, ns = n * sp->ns;
+    if ((rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(uint32_t))) ||
+        (rc = grow(s, s->rad_samples, s->rad_samples_bytes, ns * sizeof(Rad3))) ||
+        (rc = grow(s, s->rad_out, s->rad_out_bytes, n * 6 * sizeof(float))))
+        return rc;
+    float *d_mean = s->rad_out, *d_stderr = s->rad_out + n * 3;
+    HIP_TRY(hipMemcpyAsync(s->q_time, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    if ((rc = sparse_enqueue(s, m, p, cam, sp, stream, s->q_time, nullptr, out_mean ? d_mean : nullptr, out_stderr ? d_stderr : nullptr,
+                             s->rad_samples, s->status + RTMI_STATUS_WORDS)))
+        return rc;
+    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, d_mean, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, d_stderr, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (kernel_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *kernel_ms = (double)ms;
+    }
+    return RTMI_OK;
+}
+extern "C" int rtmi_sparse_render_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
+                                         const void *d_pixels, const void *d_count, void *d_mean, void *d_stderr, void *d_samples,
+                                         void *d_scratch, void *stream_) {
+    const char *name = "rtmi_sparse_render_device";
+    if (int rc = sparse_check(name, s, p, cam, sp, d_pixels, "d_pixels is NULL", d_samples != nullptr,
+                              "d_samples is NULL (the kernel's per-sample buffer)"))
+        return rc;
+    if (!d_scratch) return fail(RTMI_ERR_INVALID, std::string(name) + ": d_scratch is NULL");
+    if (sparse_misaligned(d_pixels, 4) || sparse_misaligned(d_count, 4) || sparse_misaligned(d_mean, 4) || sparse_misaligned(d_stderr, 4) ||
+        sparse_misaligned(d_samples, 4) || sparse_misaligned(d_scratch, 4))
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": misaligned pointer (4 bytes)");
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = sparse_estimator(name, sp, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    if (sp->n == 0u) return RTMI_OK;
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = radiance_attached(m, s)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    BusyMark busy_mark{s, stream};
+    return sparse_enqueue(s, m, p, cam, sp, stream, d_pixels, d_count, d_mean, d_stderr, d_samples,
+                          reinterpret_cast<unsigned int *>(d_scratch) + RTMI_SPARSE_QUEUE_WORD);
+}
+// the refine entries' own checks, after sparse_check: the planes, the scratch, the mark
+static int sparse_refine_check(const char *name, const rtmi_render_params *p, const rtmi_sparse_params *sp, uint32_t mark,
+                               bool device_form, const void *bytes, const void *linear, const void *se, const void *scratch,
+                               uint64_t scratch_bytes, const void *count_out) {
+    const std::string nm = std::string(name) + ": ";
+    const uint64_t npix = (uint64_t)p->nx * p->ny;
+    if (npix > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "the image must have at most 32768^2 pixels");
+    if (sp->n == 0u) return fail(RTMI_ERR_INVALID, nm + "sp->n, the budget of pixels, must be at least 1");
+    if (mark > 255u) return fail(RTMI_ERR_INVALID, nm + "mark must be a byte");
+    if (!device_form) return RTMI_OK;
+    if (!scratch) return fail(RTMI_ERR_INVALID, nm + "d_scratch is NULL");
+    if (sparse_misaligned(linear, 4) || sparse_misaligned(se, 4) || sparse_misaligned(count_out, 4) || sparse_misaligned(scratch, 16))
+        return fail(RTMI_ERR_INVALID, nm + "misaligned linear, stderr, count (4 bytes) or scratch (16 bytes)");
+    if (scratch_bytes < sparse_scratch(npix, sp->n, sp->ns).total)
+        return fail(RTMI_ERR_INVALID, nm + "scratch_bytes is below rtmi_sparse_scratch_bytes(nx * ny, sp->n, sp->ns)");
+    (void)bytes;
+    return RTMI_OK;
+}
+// select -> sparse render -> patch on `stream`; the list, the counts and the records live in the scratch
+static int sparse_refine_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_params *p, const rtmi_camera *cam,
+                                 const rtmi_sparse_params *sp, uint32_t accept_mask, uint32_t mark, hipStream_t stream, void *d_bytes,
+                                 void *d_linear, void *d_rgb8, void *d_stderr, void *d_scratch, void *d_count_out) {
+    const uint32_t npix = p->nx * p->ny;
+    const SparseScratch L = sparse_scratch(npix, sp->n, sp->ns);
+    char *base = reinterpret_cast<char *>(d_scratch);
+    uint32_t *head = reinterpret_cast<uint32_t *>(base), *count = head + RTMI_SPARSE_COUNT_WORD;
+    uint32_t *list = reinterpret_cast<uint32_t *>(base + L.list);
+    float *mean = reinterpret_cast<float *>(base + L.mean), *se = reinterpret_cast<float *>(base + L.se);
+    HIP_TRY(rtmi_sparse_launch_select(stream, reinterpret_cast<const uint8_t *>(d_bytes), npix, accept_mask, sp->n, list, count,
+                                      reinterpret_cast<uint32_t *>(base + L.counts)));
+    if (int rc = sparse_enqueue(s, m, p, cam, sp, stream, list, count, mean, se, base + L.samples, head + RTMI_SPARSE_QUEUE_WORD)) return rc;
+    HIP_TRY(rtmi_sparse_launch_patch(stream, npix, list, count, sp->n, mean, se, reinterpret_cast<float *>(d_linear),
+                                     reinterpret_cast<uint8_t *>(d_rgb8), reinterpret_cast<float *>(d_stderr),
+                                     reinterpret_cast<uint8_t *>(d_bytes), mark));
+    if (d_count_out) HIP_TRY(hipMemcpyAsync(d_count_out, count, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    return RTMI_OK;
+}
+extern "C" int rtmi_sparse_refine_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
+                                         uint32_t accept_mask, uint32_t mark, void *d_bytes, void *d_linear, void *d_rgb8, void *d_stderr,
+                                         void *d_scratch, uint64_t scratch_bytes, void *d_count_out, void *stream_) {
+    const char *name = "rtmi_sparse_refine_device";
+    int rc;
+    if ((rc = sparse_check(name, s, p, cam, sp, d_bytes, "d_bytes is NULL", true, "")) ||
+        (rc = sparse_refine_check(name, p, sp, mark, true, d_bytes, d_linear, d_stderr, d_scratch, scratch_bytes, d_count_out)))
+        return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = sparse_estimator(name, sp, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    std::lock_guard<std::mutex> lock(s->mu);
+    if ((rc = radiance_attached(m, s))) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    BusyMark busy_mark{s, stream};
+    return sparse_refine_enqueue(s, m, p, cam, sp, accept_mask, mark, stream, d_bytes, d_linear, d_rgb8, d_stderr, d_scratch, d_count_out);
+}
+extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
+                                  uint32_t accept_mask, uint32_t mark, uint8_t *bytes, float *linear, uint8_t *rgb8, float *stderr_rgb,
+                                  uint32_t *counts) {
+    const char *name = "rtmi_sparse_refine";
+    int rc;
+    if ((rc = sparse_check(name, s, p, cam, sp, bytes, "bytes is NULL", true, "")) ||
+        (rc = sparse_refine_check(name, p, sp, mark, false, bytes, linear, stderr_rgb, nullptr, 0, counts)))
+        return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = sparse_estimator(name, sp, null_scene);
+    RenderCall c;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    // one allocation per call, freed on every return path: bytes | scratch | linear | stderr | rgb8
+    const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
+    const size_t scratch_bytes = (size_t)sparse_scratch(npix, sp->n, sp->ns).total;
+    struct Mem {
+        char *base = nullptr;
+        ~Mem() { if (base) (void)hipFree(base); }
+    } mem;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), up + scratch_bytes + 12 * up + 12 * up + 3 * up));
+    char *d_bytes = mem.base, *d_scratch = d_bytes + up, *d_linear = d_scratch + scratch_bytes, *d_se = d_linear + 12 * up,
+         *d_rgb8 = d_se + 12 * up;
+    HIP_TRY(hipMemcpyAsync(d_bytes, bytes, npix, hipMemcpyHostToDevice, stream));
+    if (linear) HIP_TRY(hipMemcpyAsync(d_linear, linear, npix * 12, hipMemcpyHostToDevice, stream));
+    if (stderr_rgb) HIP_TRY(hipMemcpyAsync(d_se, stderr_rgb, npix * 12, hipMemcpyHostToDevice, stream));
+    if (rgb8) HIP_TRY(hipMemcpyAsync(d_rgb8, rgb8, npix * 3, hipMemcpyHostToDevice, stream));
+    if ((rc = sparse_refine_enqueue(s, m, p, cam, sp, accept_mask, mark, stream, d_bytes, linear ? d_linear : nullptr,
+                                    rgb8 ? d_rgb8 : nullptr, stderr_rgb ? d_se : nullptr, d_scratch, nullptr))) {
+        (void)hipStreamSynchronize(stream);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(bytes, d_bytes, npix, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && linear) e = hipMemcpyAsync(linear, d_linear, npix * 12, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && stderr_rgb) e = hipMemcpyAsync(stderr_rgb, d_se, npix * 12, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && rgb8) e = hipMemcpyAsync(rgb8, d_rgb8, npix * 3, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess && counts)
+        e = hipMemcpyAsync(counts, d_scratch + 4 * RTMI_SPARSE_COUNT_WORD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    const hipError_t e2 = hipStreamSynchronize(stream); // before the allocation is freed, whatever was enqueued
+    HIP_TRY(e);
+    HIP_TRY(e2);
     return RTMI_OK;
 }
 

@@ -890,6 +890,126 @@ class Scene:
             C.c_void_p(scratch.data_ptr()), C.c_uint64(scratch_bytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
 
+    def render_pixels(self, cam, nx, ny, pixels, ns, estimator="plain", seed=42, first_sample=0, samples=False, env_select_p=0.5,
+                      **kw):
+        """Chosen pixels of the nx x ny image under `cam` with the render's own paths (include/rtmi_sparse.h).  pixels: an
+        integer array of indices row * nx + i into the image's planes (row 0 the top row), or an [n, 2] array of (i, row); it may
+        be unsorted and may repeat a pixel.  Sample s
+        of entry k is, bit for bit, sample first_sample + s of that pixel in render (estimator "plain"), render_nee ("nee")
+        or render_env ("env": nee=False, "env_nee": nee=True with env_select_p) under `seed`: a camera with a lens included.
+        kw: flags, max_depth, t_min of default_params.  Returns dict(mean f32 [n, 3], stderr f32 [n, 3] (+inf for ns = 1),
+        kernel_ms[, samples f32 [n, ns, 3]]): with first_sample = 0 mean and stderr are the render's linear and stderr
+        planes at those pixels.  With a torch tensor on the scene's device the call is enqueued on torch's current stream
+        (rtmi_sparse_render_device) and returns torch tensors on that device, samples always among them: no host copy is
+        made.  A scene resident on a device list raises Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, 1, seed=seed, **kw)
+        if hasattr(pixels, "data_ptr") and hasattr(pixels, "is_cuda"):
+            return self._render_pixels_torch(cam, p, pixels, int(ns), estimator, int(first_sample), float(env_select_p))
+        px = np.asarray(pixels)
+        if px.ndim == 2 and px.shape[1] == 2:
+            px = px[:, 1].astype(np.int64) * nx + px[:, 0].astype(np.int64)
+        if px.ndim != 1 or (px.size and not np.issubdtype(px.dtype, np.integer)):
+            raise ValueError("pixels is an integer array of indices or an [n, 2] array of (i, row)")
+        if px.size and (px.min() < 0 or px.max() >= 2 ** 32):
+            raise ValueError("a pixel index is negative or does not fit 32 bits")
+        px = np.ascontiguousarray(px, dtype=np.uint32)
+        n = px.shape[0]
+        sp = abi.SparseParams(n, int(ns), int(first_sample), abi.ROULETTE_ESTIMATORS[estimator], float(env_select_p))
+        ms = C.c_double(0.0)
+        res = {"mean": np.zeros((n, 3), np.float32), "stderr": np.zeros((n, 3), np.float32)}
+        if samples:
+            res["samples"] = np.zeros((n, max(int(ns), 0), 3), np.float32)
+        self.host._check(self.host.lib.rth_sparse_render(self.h, cam.h, C.byref(p), C.byref(sp), px.ctypes.data, res["mean"].ctypes.data,
+                                                          res["stderr"].ctypes.data, res["samples"].ctypes.data if samples else None,
+                                                          C.byref(ms)))
+        res["kernel_ms"] = ms.value
+        return res
+
+    def _render_pixels_torch(self, cam, p, pixels, ns, estimator, first_sample, env_select_p, count=None):
+        import torch
+
+        dev = pixels.device
+        if dev.type != "cuda" or (dev.index or 0) != self.device:
+            raise ValueError("the pixels are on %s, the scene is on device %d" % (dev, self.device))
+        if pixels.is_floating_point() or pixels.dim() not in (1, 2) or (pixels.dim() == 2 and pixels.shape[1] != 2):
+            raise ValueError("pixels is an integer tensor of indices or an [n, 2] tensor of (i, row)")
+        if pixels.dim() == 2:
+            pixels = pixels[:, 1].to(torch.int64) * p.nx + pixels[:, 0].to(torch.int64)
+        px = pixels.to(torch.int32).contiguous()  # the words of a uint32 list
+        n = px.shape[0]
+        sp = abi.SparseParams(n, ns, first_sample, abi.ROULETTE_ESTIMATORS[estimator], env_select_p)
+        res = {"mean": torch.empty((n, 3), dtype=torch.float32, device=dev), "stderr": torch.empty((n, 3), dtype=torch.float32, device=dev),
+               "samples": torch.empty((n, ns, 3), dtype=torch.float32, device=dev)}
+        scratch = torch.empty((4,), dtype=torch.int32, device=dev)
+        # every check of the entry is made for an empty list too; it then launches nothing
+        self.host._check(self.host.lib.rth_sparse_render_device(
+            self.h, cam.h, C.byref(p), C.byref(sp), C.c_void_p(px.data_ptr()), C.c_void_p(count.data_ptr()) if count is not None else None,
+            C.c_void_p(res["mean"].data_ptr()), C.c_void_p(res["stderr"].data_ptr()), C.c_void_p(res["samples"].data_ptr()),
+            C.c_void_p(scratch.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return res  # px and scratch return to torch's allocator, which hands them out again on this stream behind the kernels
+
+    def refine_pixels(self, cam, planes, classes=(3,), ns=4, estimator="plain", seed=42, budget=None, mark=4, first_sample=0,
+                      env_select_p=0.5, **kw):
+        """Traces again the pixels of an image whose class is in `classes` and patches the results in (select -> sparse
+        render -> patch of include/rtmi_sparse.h, one native call).  planes: a dict with linear f32 [ny,nx,3], rgb8 u8
+        [ny,nx,3] and cls u8 [ny,nx], as Upscaler.render returns it (a stderr f32 [ny,nx,3] plane, when present, is patched
+        with the new standard errors).  A selected pixel gets render_pixels' mean of ns samples under `seed` (the bits of
+        the estimator's full render of ns samples at that pixel), its quantised rgb8, and cls = mark; no other element
+        changes.  budget: the most pixels to trace, the first in index order (None: every pixel of the image may be; the
+        scratch grows with it: 28 + 12 * ns bytes per pixel of budget).  torch tensors on the scene's device are patched in
+        place on torch's current stream, without a host copy; numpy planes are left alone and patched copies returned.
+        Returns the dict with refined = (pixels patched, pixels selected)."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        mask = _sparse_mask(classes)
+        cls = planes["cls"]
+        ny, nx = int(cls.shape[0]), int(cls.shape[1])
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, 1, seed=seed, **kw)
+        cap = nx * ny if budget is None else int(budget)
+        sp = abi.SparseParams(cap, int(ns), int(first_sample), abi.ROULETTE_ESTIMATORS[estimator], float(env_select_p))
+        names = [n for n in ("linear", "rgb8", "stderr") if planes.get(n) is not None]
+        torch_in = hasattr(cls, "data_ptr") and hasattr(cls, "is_cuda")
+        want = {"cls": (ny, nx), "linear": (ny, nx, 3), "rgb8": (ny, nx, 3), "stderr": (ny, nx, 3)}
+        out = dict(planes)
+        if torch_in:
+            import torch
+
+            dev = cls.device
+            if dev.type != "cuda" or (dev.index or 0) != self.device:
+                raise ValueError("the planes are on %s, the scene is on device %d" % (dev, self.device))
+            kinds = {"cls": torch.uint8, "rgb8": torch.uint8, "linear": torch.float32, "stderr": torch.float32}
+            for n in ["cls"] + names:
+                a = planes[n]
+                if a.dtype != kinds[n] or tuple(a.shape) != want[n] or a.device != dev or not a.is_contiguous():
+                    raise ValueError("plane %r must be a contiguous %s tensor of shape %r on the scene's device" % (n, kinds[n], want[n]))
+            nbytes = int(abi.load_rtmi().rtmi_sparse_scratch_bytes(nx * ny, max(cap, 0), max(int(ns), 0)))
+            scratch = torch.empty(((nbytes + 15) // 16, 4), dtype=torch.int32, device=dev)
+            counts = torch.zeros((2,), dtype=torch.int32, device=dev)
+            ptr = {n: C.c_void_p(planes[n].data_ptr()) for n in names}
+            self.host._check(self.host.lib.rth_sparse_refine(
+                self.h, cam.h, C.byref(p), C.byref(sp), mask, int(mark), C.c_void_p(cls.data_ptr()), ptr.get("linear"), ptr.get("rgb8"),
+                ptr.get("stderr"), C.c_void_p(scratch.data_ptr()), C.c_uint64(nbytes), C.c_void_p(counts.data_ptr()), 1,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            c = counts.cpu().numpy().view(np.uint32)  # the one read-back, for the caller's eyes only
+        else:
+            kinds = {"cls": np.uint8, "rgb8": np.uint8, "linear": np.float32, "stderr": np.float32}
+            for n in ["cls"] + names:
+                a = np.asarray(planes[n])
+                if a.dtype != kinds[n] or a.shape != want[n]:
+                    raise ValueError("plane %r must be a %s array of shape %r" % (n, np.dtype(kinds[n]).name, want[n]))
+                out[n] = np.array(a, order="C", copy=True)
+            c = np.zeros(2, np.uint32)
+            ptr = {n: out[n].ctypes.data for n in names}
+            self.host._check(self.host.lib.rth_sparse_refine(
+                self.h, cam.h, C.byref(p), C.byref(sp), mask, int(mark), out["cls"].ctypes.data, ptr.get("linear"), ptr.get("rgb8"),
+                ptr.get("stderr"), None, 0, c.ctypes.data, 0, None))
+        out["refined"] = (int(c[0]), int(c[1]))
+        return out
+
 
 IRRADIANCE_STREAM = 5  # the Philox stream id of irradiance()'s directions (0 path, 2 scene, 3 light samples, 4 roulette)
 
@@ -1804,6 +1924,92 @@ def upscale(linear_lo, albedo_lo, normal_lo, depth_lo, albedo, normal, depth, de
     if rc != 0:
         raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, lib.rtmi_last_error().decode()))
     return out
+
+
+def _sparse_mask(classes):
+    """The accept mask of a set of classes: bit c for every class c in 0..31."""
+    mask = 0
+    for c in classes:
+        if not 0 <= int(c) < 32:
+            raise ValueError("a class must be in 0..31, not %r" % (c,))
+        mask |= 1 << int(c)
+    return mask
+
+
+def _sparse_device_of(t, device):
+    if t.device.type != "cuda":
+        raise ValueError("the tensor is on %s, not on a GPU" % (t.device,))
+    return t.device.index if t.device.index is not None else device
+
+
+def sparse_select(bytes, classes, capacity=None, device=0):
+    """The ascending list of the pixels of a byte plane whose byte is in `classes` (rtmi_sparse_select_device of
+    include/rtmi_sparse.h): bytes of 32 and above are never selected.  capacity: the most indices to write (None: the
+    plane's size), the first in index order.  A torch uint8 tensor on a GPU is read in place and the call enqueued on
+    torch's current stream: returns (list int32 [capacity] (the words of a uint32 list; those past counts[0] are not
+    written), counts int32 [2] = (written, selected)) on that device, nothing is read back.  A numpy array goes through
+    `device` and comes back as (list uint32 [written], counts uint32 [2])."""
+    import torch
+
+    mask = _sparse_mask(classes)
+    torch_in = hasattr(bytes, "data_ptr") and hasattr(bytes, "is_cuda")
+    if torch_in:
+        if bytes.dtype != torch.uint8 or not bytes.is_contiguous():
+            raise ValueError("bytes must be a contiguous uint8 tensor")
+        b = bytes
+        device = _sparse_device_of(b, device)
+    else:
+        a = np.ascontiguousarray(bytes)
+        if a.dtype != np.uint8:
+            raise ValueError("bytes must be a uint8 array")
+        b = torch.from_numpy(a.reshape(-1)).to(torch.device("cuda", device))
+    n = b.numel()
+    cap = n if capacity is None else int(capacity)
+    lib = abi.load_rtmi()
+    dev = b.device
+    lst = torch.empty((max(cap, 1),), dtype=torch.int32, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    nbytes = int(lib.rtmi_sparse_scratch_bytes(n, 0, 0))
+    scratch = torch.empty(((nbytes + 15) // 16, 4), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.rtmi_sparse_select_device(device, n, C.c_void_p(b.data_ptr()), mask, cap, C.c_void_p(lst.data_ptr()),
+                                           C.c_void_p(counts.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise HostError((lib.rtmi_last_error() or b"").decode())
+    if torch_in:
+        return lst[:cap], counts
+    c = counts.cpu().numpy().view(np.uint32)
+    return lst[:int(c[0])].cpu().numpy().view(np.uint32), c
+
+
+def sparse_patch(pixels, mean, linear=None, rgb8=None, bytes=None, mark=4, count=None, device=0):
+    """Writes records back where they belong (rtmi_sparse_patch_device of include/rtmi_sparse.h), in place, on torch's
+    current stream: for each entry k of the int32 tensor `pixels` (of the first min(count[0], len) with a count tensor)
+    whose pixel p lies inside the planes, linear[p] = mean[k], rgb8[p] = its quantised value, bytes[p] = mark.  All are
+    contiguous torch tensors on one GPU: mean f32 [n, 3], linear f32 [..., 3], rgb8 u8 [..., 3], bytes u8 [...]; each plane
+    is optional, the planes' pixel count comes from the first one given."""
+    import torch
+
+    planes = [(linear, 3), (rgb8, 3), (bytes, 1)]
+    first = next(((a, ch) for a, ch in planes if a is not None), None)
+    if first is None:
+        raise ValueError("give at least one plane")
+    n_pixels = first[0].numel() // first[1]
+    for a, ch in planes:
+        if a is not None and (a.numel() != n_pixels * ch or not a.is_contiguous()):
+            raise ValueError("the planes must be contiguous and of one size")
+    if pixels.dtype != torch.int32 or mean.dtype != torch.float32 or not pixels.is_contiguous() or not mean.is_contiguous():
+        raise ValueError("pixels is a contiguous int32 tensor, mean a contiguous float32 tensor")
+    dev = pixels.device
+    device = _sparse_device_of(pixels, device)
+    lib = abi.load_rtmi()
+    ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        rc = lib.rtmi_sparse_patch_device(device, n_pixels, ptr(pixels), ptr(count), pixels.numel(), ptr(mean), ptr(linear), ptr(rgb8),
+                                          ptr(bytes), int(mark), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise HostError((lib.rtmi_last_error() or b"").decode())
 
 
 def pfm_bytes(plane):

@@ -16,6 +16,7 @@
 #include "rtmi_session.h"
 #include "rtmi_query.h"
 #include "rtmi_radiance.h"
+#include "rtmi_sparse.h"
 #include "rtmi_gather.h"
 #include "rtmi_frame.h"
 #include "rtmi_upscale.h"
@@ -351,6 +352,45 @@ RTH_API int rth_radiance_device(void *lowered, const rtmi_radiance_params *p, co
         const char *name = "rtmi_radiance_device";
         return done(name, rtmi_radiance_device(DEV(lowered, name, "radiance-query"), p, d_rays, d_time, d_mean, d_stderr, d_samples, stream),
                     CODED_UNSUPPORTED);
+    });
+}
+// sparse renders (include/rtmi_sparse.h) on the uploaded handle, as the radiance queries: chosen pixels of the image of `p`
+// under `cam`; host pointers and blocking, or device pointers enqueued on `stream`
+RTH_API int rth_sparse_render(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_sparse_params *sp, const uint32_t *pixels,
+                              float *out_mean, float *out_stderr, float *out_samples, double *kernel_ms) {
+    return guard([&] {
+        const char *name = "rtmi_sparse_render";
+        rtmi_scene *dev = DEV(lowered, name, "sparse-render");
+        const rtmi_camera c = CAM(cam).lower();
+        return done(name, rtmi_sparse_render(dev, p, &c, sp, pixels, out_mean, out_stderr, out_samples, kernel_ms), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_sparse_render_device(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_sparse_params *sp,
+                                     const void *d_pixels, const void *d_count, void *d_mean, void *d_stderr, void *d_samples,
+                                     void *d_scratch, void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_sparse_render_device";
+        rtmi_scene *dev = DEV(lowered, name, "sparse-render");
+        const rtmi_camera c = CAM(cam).lower();
+        return done(name, rtmi_sparse_render_device(dev, p, &c, sp, d_pixels, d_count, d_mean, d_stderr, d_samples, d_scratch, stream),
+                    CODED_UNSUPPORTED);
+    });
+}
+// select -> sparse render -> patch of the planes; device = 1: device planes, enqueued on `stream` (counts: 2 device words
+// or NULL); device = 0: host planes, blocking (counts: 2 host words or NULL; scratch and stream are not read)
+RTH_API int rth_sparse_refine(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_sparse_params *sp, uint32_t accept_mask,
+                              uint32_t mark, void *bytes, void *linear, void *rgb8, void *stderr_rgb, void *d_scratch,
+                              uint64_t scratch_bytes, void *counts, int device, void *stream) {
+    return guard([&] {
+        const char *name = device ? "rtmi_sparse_refine_device" : "rtmi_sparse_refine";
+        rtmi_scene *dev = DEV(lowered, name, "sparse-render");
+        const rtmi_camera c = CAM(cam).lower();
+        const int rc = device ? rtmi_sparse_refine_device(dev, p, &c, sp, accept_mask, mark, bytes, linear, rgb8, stderr_rgb, d_scratch,
+                                                          scratch_bytes, counts, stream)
+                              : rtmi_sparse_refine(dev, p, &c, sp, accept_mask, mark, static_cast<uint8_t *>(bytes),
+                                                   static_cast<float *>(linear), static_cast<uint8_t *>(rgb8),
+                                                   static_cast<float *>(stderr_rgb), static_cast<uint32_t *>(counts));
+        return done(name, rc, CODED_UNSUPPORTED);
     });
 }
 // hemisphere gathers (include/rtmi_gather.h) on the uploaded handle, as the radiance queries
