@@ -929,6 +929,82 @@ extern "C" {
     ) -> c_int;
 }
 
+// ---- include/rtmi_pixelwise.h: adaptive sampling per pixel, driven from the device -----------------------------------------
+
+pub const RTMI_PIXELWISE_MAX_STEPS: u32 = 1024;
+
+/// rtmi_pixelwise_opts: the steps, the estimator and the tolerances of a per-pixel adaptive render (48 bytes, abs_tol at
+/// offset 16)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiPixelwiseOpts {
+    pub min_spp: u32,
+    pub step_spp: u32,
+    pub estimator: u32,
+    pub pass_spp: u32,
+    pub abs_tol: f64,
+    pub rel_tol: f64,
+    pub env_select_p: f32,
+    pub reserved: [u32; 3],
+}
+
+extern "C" {
+    /// the bytes of the device form's scratch; pure host code, a multiple of 16
+    pub fn rtmi_pixelwise_scratch_bytes(n_pixels: u64, pass_spp: u32, steps: u32) -> u64;
+    /// 1 + ceil((ns - min_spp) / step_spp), 0 for bad arguments; pure host code
+    pub fn rtmi_pixelwise_steps(ns: u32, min_spp: u32, step_spp: u32) -> u32;
+    /// asynchronous, device pointers, every step enqueued on `stream` (a hipStream_t); the planes are each optional, not all
+    /// NULL; d_counts 2 * steps words or NULL
+    pub fn rtmi_render_pixelwise_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        cam: *const RtmiCamera,
+        opts: *const RtmiPixelwiseOpts,
+        d_linear: *mut c_void,
+        d_rgb8: *mut c_void,
+        d_stderr: *mut c_void,
+        d_spp: *mut c_void,
+        d_counts: *mut c_void,
+        d_scratch: *mut c_void,
+        scratch_bytes: u64,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// blocking, host planes, each optional, not all NULL; out_counts 2 * steps words or NULL
+    pub fn rtmi_render_pixelwise(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiPixelwiseOpts,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_spp: *mut u32,
+        out_counts: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the step kernel alone on host arrays, blocking (tests)
+    pub fn rtmi_probe_pixelwise_step(
+        device: c_int,
+        n_pixels: u32,
+        capacity: u32,
+        list: *const u32,
+        count: *const u32,
+        samples: *const f32,
+        state: *mut f64,
+        n_done: u32,
+        pass: u32,
+        decide: u32,
+        cap: u32,
+        abs_tol: f64,
+        rel_tol: f64,
+        active: *mut u8,
+        linear: *mut f32,
+        rgb8: *mut u8,
+        stderr_rgb: *mut f32,
+        spp: *mut u32,
+    ) -> c_int;
+}
+
 // ---- include/rtmi_temporal.h: temporal accumulation -------------------------------------------------------------------
 
 pub const RTMI_TEMPORAL_NO_DEMODULATE: u32 = 1;

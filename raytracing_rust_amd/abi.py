@@ -412,6 +412,17 @@ class SparseParams(C.Structure):
 RTMI_SPARSE_SYMBOLS = ["rtmi_sparse_patch_device", "rtmi_sparse_refine", "rtmi_sparse_refine_device", "rtmi_sparse_render",
                        "rtmi_sparse_render_device", "rtmi_sparse_scratch_bytes", "rtmi_sparse_select_device"]
 
+
+class PixelwiseOpts(C.Structure):
+    """rtmi_pixelwise_opts (include/rtmi_pixelwise.h): the steps, estimator and tolerances of a per-pixel adaptive render (48 bytes)."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("estimator", C.c_uint32), ("pass_spp", C.c_uint32),
+                ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("env_select_p", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+# the functions of include/rtmi_pixelwise.h (per-pixel adaptive sampling), kept apart from those of the other headers
+RTMI_PIXELWISE_SYMBOLS = ["rtmi_pixelwise_scratch_bytes", "rtmi_pixelwise_steps", "rtmi_probe_pixelwise_step", "rtmi_render_pixelwise",
+                          "rtmi_render_pixelwise_device"]
+
 _rtmi = None
 _host = None
 
@@ -622,6 +633,19 @@ def load_rtmi():
     lib.rtmi_sparse_refine_device.argtypes = sparse + [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     lib.rtmi_sparse_refine.restype = C.c_int
     lib.rtmi_sparse_refine.argtypes = sparse + [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.rtmi_pixelwise_scratch_bytes.restype = C.c_uint64
+    lib.rtmi_pixelwise_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.rtmi_pixelwise_steps.restype = C.c_uint32
+    lib.rtmi_pixelwise_steps.argtypes = [C.c_uint32] * 3
+    lib.rtmi_render_pixelwise_device.restype = C.c_int
+    lib.rtmi_render_pixelwise_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(Camera), C.POINTER(PixelwiseOpts)] + [vp] * 6 + [
+        C.c_uint64, vp]
+    lib.rtmi_render_pixelwise.restype = C.c_int
+    lib.rtmi_render_pixelwise.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 5 + [
+        C.POINTER(Stats)]
+    lib.rtmi_probe_pixelwise_step.restype = C.c_int
+    lib.rtmi_probe_pixelwise_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_double, C.c_double, vp, vp, vp, vp, vp]
     _rtmi = lib
     return lib
 
@@ -717,6 +741,8 @@ def load_host():
         "rth_sparse_render": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams), vp, vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_sparse_render_device": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams)] + [vp] * 7),
         "rth_sparse_refine": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams), u32, u32, vp, vp, vp, vp, vp, u64, vp, i, vp]),
+        "rth_render_pixelwise": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 5 + [C.POINTER(Stats)]),
+        "rth_render_pixelwise_device": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 6 + [u64, vp]),
         "rth_gather": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_gather_device": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),

@@ -61,6 +61,8 @@
 #include "rtmi_gather_launch.hpp"
 #include "rtmi_sparse.h"
 #include "rtmi_sparse_launch.hpp"
+#include "rtmi_pixelwise.h"
+#include "rtmi_pixelwise_launch.hpp"
 #include "rtmi_frame_launch.hpp"
 
 // ======================================================================================
@@ -154,6 +156,8 @@ struct rtmi_scene {
     size_t rad_samples_bytes = 0;
     float *rad_out = nullptr;    // mean [n][3] | stderr [n][3]
     size_t rad_out_bytes = 0;
+    char *px_mem = nullptr;      // per-pixel adaptive sampling, blocking form: scratch | linear | stderr | spp | rgb8
+    size_t px_mem_bytes = 0;
     // next-event estimation (include/rtmi_nee.h): the attached light table and per-primitive light index, freed with the
     // handle
     bool has_lights = false;
@@ -614,6 +618,7 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (s->q_flip_gaps) (void)hipFree(s->q_flip_gaps);
     if (s->rad_samples) (void)hipFree(s->rad_samples);
     if (s->rad_out) (void)hipFree(s->rad_out);
+    if (s->px_mem) (void)hipFree(s->px_mem);
     if (s->nee_lights) (void)hipFree(s->nee_lights);
     if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
     if (s->lt_nodes) (void)hipFree(s->lt_nodes);
@@ -3110,6 +3115,241 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
     const hipError_t e2 = hipStreamSynchronize(stream); // before the allocation is freed, whatever was enqueued
     HIP_TRY(e);
     HIP_TRY(e2);
+    return RTMI_OK;
+}
+
+// ---- per-pixel adaptive sampling (include/rtmi_pixelwise.h) -----------------------------------------------------------------
+// the caller's scratch, in bytes from its start: control words | count slots | per-workgroup counts of the select |
+// active bytes | list | state | samples
+struct PixelwiseScratch {
+    uint64_t counts, block_counts, active, list, state, samples, total;
+};
+static PixelwiseScratch pixelwise_scratch(uint64_t n_pixels, uint32_t pass, uint32_t steps) {
+    const auto up16 = [](uint64_t b) { return (b + 15ull) & ~15ull; };
+    PixelwiseScratch L;
+    L.counts = 4ull * RTMI_SPARSE_HEAD_WORDS;
+    L.block_counts = L.counts + up16(8ull * steps);
+    L.active = L.block_counts + up16(4ull * ((n_pixels + RTMI_SPARSE_SPAN - 1ull) / RTMI_SPARSE_SPAN));
+    L.list = L.active + up16(n_pixels);
+    L.state = L.list + up16(4ull * n_pixels);
+    L.samples = L.state + up16(72ull * n_pixels);
+    L.total = L.samples + up16(12ull * n_pixels * pass);
+    return L;
+}
+extern "C" uint64_t rtmi_pixelwise_scratch_bytes(uint64_t n_pixels, uint32_t pass_spp, uint32_t steps) {
+    return pixelwise_scratch(n_pixels, pass_spp, steps).total;
+}
+extern "C" uint32_t rtmi_pixelwise_steps(uint32_t ns, uint32_t min_spp, uint32_t step_spp) {
+    if (min_spp < 2u || min_spp > ns || step_spp == 0u) return 0u;
+    return 1u + (uint32_t)(((uint64_t)(ns - min_spp) + step_spp - 1ull) / step_spp);
+}
+// the most samples of one launch: a whole step (the first, or a later one, which the cap may shorten) or pass_spp
+static uint32_t pixelwise_pass(const rtmi_render_params *p, const rtmi_pixelwise_opts *o) {
+    const uint32_t rest = p->ns - o->min_spp, later = o->step_spp < rest ? o->step_spp : rest;
+    const uint32_t step = o->min_spp > later ? o->min_spp : later;
+    return o->pass_spp == 0u || o->pass_spp > step ? step : o->pass_spp;
+}
+static Estimator pixelwise_estimator(const char *name, const rtmi_pixelwise_opts *o, const std::string &null_scene) {
+    const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
+    return Estimator{name, nee, env, nee && env ? o->env_select_p : 1.0f, null_scene.c_str(),
+                     "no light table attached (rtmi_scene_attach_lights)"};
+}
+// The checks of both render forms, in the order of sparse_check (pointers, outputs, values, attachments of a handle that is
+// there, flags), then this header's own: the steps and tolerances, the size of a launch, the number of steps, the scratch and
+// the alignments (device form), the reserved words.  The NULL handle follows in the entries.
+struct PixelwisePlanes {
+    void *linear, *rgb8, *se, *spp, *counts;
+};
+static int pixelwise_check(const char *name, const rtmi_scene *s_in, const rtmi_render_params *p, const rtmi_camera *cam,
+                           const rtmi_pixelwise_opts *o, const PixelwisePlanes &out, bool device_form, const void *scratch,
+                           uint64_t scratch_bytes) {
+    const std::string nm = std::string(name) + ": ";
+    if (!p || !cam || !o) return fail(RTMI_ERR_INVALID, nm + "NULL argument (params, cam or opts)");
+    if (!out.linear && !out.rgb8 && !out.se && !out.spp) return fail(RTMI_ERR_INVALID, nm + "every plane is NULL");
+    if (p->ns == 0u) return fail(RTMI_ERR_INVALID, nm + "ns, the cap, must be at least 1");
+    if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
+    if (o->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
+    if (o->estimator == RTMI_ROULETTE_ENV_NEE && !(o->env_select_p > 0.0f && o->env_select_p <= 1.0f))
+        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
+    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    const uint64_t npix = (uint64_t)p->nx * p->ny;
+    if (npix == 0u || npix > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "the image must have 1 .. 32768^2 pixels");
+    if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
+    if (s_in) {
+        rtmi_scene *s = const_cast<rtmi_scene *>(s_in);
+        std::lock_guard<std::mutex> lock(s->mu);
+        if (env && !s->has_env) return fail(RTMI_ERR_INVALID, nm + "no environment map attached (rtmi_scene_attach_env)");
+        if (nee && !s->has_lights) return fail(RTMI_ERR_INVALID, nm + "no light table attached (rtmi_scene_attach_lights)");
+    }
+    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+        return fail(RTMI_ERR_UNSUPPORTED, nm + "per-pixel adaptive sampling accepts the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
+    const rtmi_adaptive a{o->min_spp, o->step_spp, o->abs_tol, o->rel_tol};
+    if (int rc = check_adaptive(p, &a)) return fail(rc, nm + g_err);
+    const uint32_t pass = pixelwise_pass(p, o);
+    if (npix * pass >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "nx * ny * (samples of a launch) must be below 2^31: lower pass_spp");
+    const uint32_t steps = rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp);
+    if (steps > RTMI_PIXELWISE_MAX_STEPS) return fail(RTMI_ERR_INVALID, nm + "more than 1024 steps");
+    if (device_form) {
+        if (!scratch) return fail(RTMI_ERR_INVALID, nm + "d_scratch is NULL");
+        if (scratch_bytes < pixelwise_scratch(npix, pass, steps).total)
+            return fail(RTMI_ERR_INVALID, nm + "scratch_bytes is below rtmi_pixelwise_scratch_bytes(nx * ny, pass, steps)");
+        if (sparse_misaligned(out.linear, 4) || sparse_misaligned(out.se, 4) || sparse_misaligned(out.spp, 4) ||
+            sparse_misaligned(out.counts, 4) || sparse_misaligned(scratch, 16))
+            return fail(RTMI_ERR_INVALID, nm + "misaligned linear, stderr, spp, counts (4 bytes) or scratch (16 bytes)");
+    }
+    if (o->reserved[0] || o->reserved[1] || o->reserved[2]) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
+    return RTMI_OK;
+}
+// Every step on `stream`: select the active pixels into the list (counts to the step's slot), then per sub-pass the path
+// kernel over the list from sample n_done on and the step kernel; the last sub-pass of a step decides.  h_count (blocking
+// form): pinned, the step's count is read after its select and the loop ends at the first empty step; *paths: the paths traced.
+static int pixelwise_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_params *p, const rtmi_camera *cam,
+                             const rtmi_pixelwise_opts *o, hipStream_t stream, const PixelwisePlanes &out, char *base,
+                             uint32_t *h_count, uint64_t *paths) {
+    const uint32_t npix = p->nx * p->ny, pass = pixelwise_pass(p, o), steps = rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp);
+    const PixelwiseScratch L = pixelwise_scratch(npix, pass, steps);
+    uint32_t *head = reinterpret_cast<uint32_t *>(base), *slots = reinterpret_cast<uint32_t *>(base + L.counts);
+    uint32_t *block_counts = reinterpret_cast<uint32_t *>(base + L.block_counts), *list = reinterpret_cast<uint32_t *>(base + L.list);
+    uint8_t *active = reinterpret_cast<uint8_t *>(base + L.active);
+    HIP_TRY(hipMemsetAsync(active, 1, npix, stream));
+    HIP_TRY(hipMemsetAsync(slots, 0, 8ull * steps, stream)); // a step that is never enqueued (blocking form) traced nothing
+    rtmi_sparse_params sp{};
+    sp.n = npix; sp.estimator = o->estimator; sp.env_select_p = o->env_select_p;
+    PixelwiseStep S{};
+    S.list = list;
+    S.samples = reinterpret_cast<const Rad3 *>(base + L.samples);
+    S.state = reinterpret_cast<double *>(base + L.state);
+    S.active = active;
+    S.linear = reinterpret_cast<float *>(out.linear); S.rgb8 = reinterpret_cast<uint8_t *>(out.rgb8);
+    S.stderr_out = reinterpret_cast<float *>(out.se); S.spp = reinterpret_cast<uint32_t *>(out.spp);
+    S.n_pixels = npix; S.capacity = npix; S.cap = p->ns;
+    S.abs_tol = o->abs_tol; S.rel_tol = o->rel_tol;
+    uint32_t n_done = 0u;
+    for (uint32_t k = 0; k < steps; k++) {
+        const uint32_t rest = p->ns - n_done, cnt = k == 0u ? o->min_spp : (o->step_spp < rest ? o->step_spp : rest);
+        uint32_t *slot = slots + 2u * k;
+        HIP_TRY(rtmi_sparse_launch_select(stream, active, npix, 2u /* byte 1 */, npix, list, slot, block_counts));
+        if (h_count) {
+            HIP_TRY(hipMemcpyAsync(h_count, slot, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (h_count[0] == 0u) break;
+            *paths += (uint64_t)h_count[0] * cnt;
+        }
+        S.count = slot;
+        for (uint32_t done = 0u; done < cnt;) {
+            const uint32_t take = cnt - done < pass ? cnt - done : pass;
+            sp.ns = take; sp.first_sample = n_done + done;
+            if (int rc = sparse_enqueue(s, m, p, cam, &sp, stream, list, slot, nullptr, nullptr, base + L.samples, head + RTMI_SPARSE_QUEUE_WORD))
+                return rc;
+            done += take;
+            S.n_done = sp.first_sample; S.pass = take; S.decide = done == cnt ? 1u : 0u;
+            HIP_TRY(rtmi_pixelwise_launch_step(stream, S));
+        }
+        n_done += cnt;
+    }
+    if (out.counts) HIP_TRY(hipMemcpyAsync(out.counts, slots, 8ull * steps, h_count ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
+    return RTMI_OK;
+}
+extern "C" int rtmi_render_pixelwise_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam,
+                                            const rtmi_pixelwise_opts *o, void *d_linear, void *d_rgb8, void *d_stderr, void *d_spp,
+                                            void *d_counts, void *d_scratch, uint64_t scratch_bytes, void *stream_) {
+    const char *name = "rtmi_render_pixelwise_device";
+    const PixelwisePlanes out{d_linear, d_rgb8, d_stderr, d_spp, d_counts};
+    if (int rc = pixelwise_check(name, s, p, cam, o, out, true, d_scratch, scratch_bytes)) return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = pixelwise_estimator(name, o, null_scene);
+    if (!s) return fail(RTMI_ERR_INVALID, null_scene);
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (int rc = radiance_attached(m, s)) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    BusyMark busy_mark{s, stream};
+    return pixelwise_enqueue(s, m, p, cam, o, stream, out, reinterpret_cast<char *>(d_scratch), nullptr, nullptr);
+}
+extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, const rtmi_pixelwise_opts *o,
+                                     float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts,
+                                     rtmi_stats *stats) {
+    const char *name = "rtmi_render_pixelwise";
+    int rc;
+    if ((rc = pixelwise_check(name, s, p, cam, o, PixelwisePlanes{out_linear, out_rgb8, out_stderr, out_spp, out_counts}, false, nullptr, 0)))
+        return rc;
+    const std::string null_scene = std::string(name) + ": scene is NULL";
+    const Estimator m = pixelwise_estimator(name, o, null_scene);
+    RenderCall c;
+    if ((rc = begin_call(c, m, s))) return rc;
+    hipStream_t stream = s->stream;
+    // the handle's memory, grow-only: scratch | linear | stderr | spp | rgb8
+    const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
+    const size_t scratch_bytes =
+        (size_t)pixelwise_scratch(npix, pixelwise_pass(p, o), rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp)).total;
+    if ((rc = grow(s, s->px_mem, s->px_mem_bytes, scratch_bytes + (12 + 12 + 4 + 3) * up))) return rc;
+    if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
+    char *d_linear = s->px_mem + scratch_bytes, *d_se = d_linear + 12 * up, *d_spp = d_se + 12 * up, *d_rgb8 = d_spp + 4 * up;
+    const PixelwisePlanes out{out_linear ? d_linear : nullptr, out_rgb8 ? d_rgb8 : nullptr, out_stderr ? d_se : nullptr,
+                              out_spp ? d_spp : nullptr, out_counts};
+    uint64_t paths = 0;
+    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    if ((rc = pixelwise_enqueue(s, m, p, cam, o, stream, out, s->px_mem, s->h_ad_count, &paths))) {
+        (void)hipStreamSynchronize(stream);
+        return rc;
+    }
+    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    if (out_linear) HIP_TRY(hipMemcpyAsync(out_linear, d_linear, npix * 12, hipMemcpyDeviceToHost, stream));
+    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, d_se, npix * 12, hipMemcpyDeviceToHost, stream));
+    if (out_spp) HIP_TRY(hipMemcpyAsync(out_spp, d_spp, npix * 4, hipMemcpyDeviceToHost, stream));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, d_rgb8, npix * 3, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (stats) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *stats = rtmi_stats{};
+        stats->kernel_ms = (double)ms;
+        stats->samples = paths;
+        stats->kernel = RTMI_KERNEL_PERLANE;
+    }
+    return RTMI_OK;
+}
+extern "C" int rtmi_probe_pixelwise_step(int device, uint32_t n_pixels, uint32_t capacity, const uint32_t *list, const uint32_t *count,
+                                         const float *samples, double *state, uint32_t n_done, uint32_t pass, uint32_t decide,
+                                         uint32_t cap, double abs_tol, double rel_tol, uint8_t *active, float *linear, uint8_t *rgb8,
+                                         float *stderr_rgb, uint32_t *spp) {
+    const std::string nm = "rtmi_probe_pixelwise_step: ";
+    if (!list || !samples || !state) return fail(RTMI_ERR_INVALID, nm + "NULL argument (list, samples or state)");
+    if (n_pixels == 0u || capacity == 0u || pass == 0u) return fail(RTMI_ERR_INVALID, nm + "n_pixels, capacity and pass must be at least 1");
+    if ((uint64_t)capacity * pass >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "capacity * pass must be below 2^31");
+    if (int rc = sparse_device(nm, device)) return rc;
+    // one allocation, every part rounded up to 16 bytes: state | samples | list | count | linear | stderr | spp | rgb8 | active
+    const auto up16 = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
+    const size_t n = n_pixels, bytes[9] = {72 * n, 12 * (size_t)capacity * pass, 4 * (size_t)capacity, 8, 12 * n, 12 * n, 4 * n, 3 * n, n};
+    void *host[9] = {state, const_cast<float *>(samples), const_cast<uint32_t *>(list), const_cast<uint32_t *>(count), linear, stderr_rgb,
+                     spp, rgb8, active};
+    size_t at[10] = {0};
+    for (int i = 0; i < 9; i++) at[i + 1] = at[i] + up16(bytes[i]);
+    struct Mem {
+        char *base = nullptr;
+        ~Mem() { if (base) (void)hipFree(base); }
+    } mem;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), at[9]));
+    char *d[9];
+    for (int i = 0; i < 9; i++) {
+        d[i] = host[i] ? mem.base + at[i] : nullptr;
+        if (host[i]) HIP_TRY(hipMemcpy(d[i], host[i], bytes[i], hipMemcpyHostToDevice));
+    }
+    PixelwiseStep S{};
+    S.state = reinterpret_cast<double *>(d[0]); S.samples = reinterpret_cast<const Rad3 *>(d[1]);
+    S.list = reinterpret_cast<const uint32_t *>(d[2]); S.count = reinterpret_cast<const uint32_t *>(d[3]);
+    S.linear = reinterpret_cast<float *>(d[4]); S.stderr_out = reinterpret_cast<float *>(d[5]);
+    S.spp = reinterpret_cast<uint32_t *>(d[6]); S.rgb8 = reinterpret_cast<uint8_t *>(d[7]); S.active = reinterpret_cast<uint8_t *>(d[8]);
+    S.n_pixels = n_pixels; S.capacity = capacity; S.n_done = n_done; S.pass = pass; S.decide = decide ? 1u : 0u; S.cap = cap;
+    S.abs_tol = abs_tol; S.rel_tol = rel_tol;
+    HIP_TRY(rtmi_pixelwise_launch_step(nullptr, S));
+    HIP_TRY(hipDeviceSynchronize());
+    for (int i = 0; i < 9; i++)
+        if (host[i] && i != 1 && i != 2 && i != 3) HIP_TRY(hipMemcpy(host[i], d[i], bytes[i], hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

@@ -1010,6 +1010,58 @@ class Scene:
         out["refined"] = (int(c[0]), int(c[1]))
         return out
 
+    def render_pixelwise(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, estimator="plain", seed=0, pass_spp=0,
+                         out="numpy", env_select_p=0.5, **kw):
+        """Adaptive sampling per pixel, driven from the device (include/rtmi_pixelwise.h): every pixel gets min_spp samples,
+        then step_spp more per step while, in some channel, its stderr > abs_tol + rel_tol * |mean|, up to ns (the last step
+        shortened to land on ns).  Each pixel is tested alone, where render_adaptive tests 8x8 tiles, and no step waits for
+        the host.  A pixel with spp = n is bit for bit, in linear, rgb8 and stderr, that pixel of render_adaptive(min_spp=n,
+        ns=n) (estimator "plain"), render_nee(ns=n) ("nee") or render_env(ns=n) ("env": nee=False, "env_nee": nee=True with
+        env_select_p) under `seed`.  pass_spp: at most this many samples per pixel in one launch (0: a whole step; the
+        per-sample buffer takes 12 * nx * ny * pass_spp bytes; the result does not depend on it).  kw: flags, max_depth,
+        t_min of default_params.  Returns dict(linear f32 [ny,nx,3], rgb8 u8 [ny,nx,3], stderr f32 [ny,nx,3], spp u32
+        [ny,nx], counts u32 [steps,2], samples): row k of counts is (written, selected) of step k's select, the pixels that
+        step traced; samples is the number of paths traced.  out="torch": the device form on torch's current stream; the
+        planes, counts (int32 words) and the scratch are torch tensors on the scene's device, nothing is copied to the host,
+        and samples is a function that reads counts back when called.  A scene resident on a device list raises
+        Unsupported."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        if out not in ("numpy", "torch"):
+            raise ValueError('out must be "numpy" or "torch"')
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, ns, seed=seed, **kw)
+        o = abi.PixelwiseOpts(int(min_spp), int(step_spp), abi.ROULETTE_ESTIMATORS[estimator], int(pass_spp), float(abs_tol),
+                              float(rel_tol), float(env_select_p))
+        lib = abi.load_rtmi()
+        steps = int(lib.rtmi_pixelwise_steps(p.ns, o.min_spp, o.step_spp))
+        rows = max(steps, 1)  # refused arguments (0 steps) reach the native entry, which names what is wrong
+        per_step = np.array([o.min_spp] + [min(o.step_spp, p.ns - n) for n in range(o.min_spp, p.ns, max(o.step_spp, 1))], np.uint64)
+        if out == "numpy":
+            res, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr", "spp"))
+            counts = np.zeros((rows, 2), np.uint32)
+            self.host._check(self.host.lib.rth_render_pixelwise(self.h, cam.h, C.byref(p), C.byref(o), *outs[:-1], counts.ctypes.data,
+                                                                 outs[-1]))
+            st = res.pop("stats")
+            res["counts"] = counts[:steps]
+            res["samples"] = int(st.samples)
+            return res
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        step = max(o.min_spp, min(o.step_spp, max(p.ns - o.min_spp, 0)))
+        nbytes = int(lib.rtmi_pixelwise_scratch_bytes(nx * ny, step if o.pass_spp == 0 or o.pass_spp > step else o.pass_spp, steps))
+        res = {"linear": torch.empty((ny, nx, 3), dtype=torch.float32, device=dev), "rgb8": torch.empty((ny, nx, 3), dtype=torch.uint8, device=dev),
+               "stderr": torch.empty((ny, nx, 3), dtype=torch.float32, device=dev), "spp": torch.empty((ny, nx), dtype=torch.int32, device=dev),
+               "counts": torch.empty((rows, 2), dtype=torch.int32, device=dev)}
+        scratch = torch.empty(((nbytes + 15) // 16, 4), dtype=torch.int32, device=dev)
+        self.host._check(self.host.lib.rth_render_pixelwise_device(
+            self.h, cam.h, C.byref(p), C.byref(o), *[C.c_void_p(res[n].data_ptr()) for n in ("linear", "rgb8", "stderr", "spp", "counts")],
+            C.c_void_p(scratch.data_ptr()), C.c_uint64(nbytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        counts = res["counts"] = res["counts"][:steps]
+        res["samples"] = lambda: int((counts[:, 0].cpu().numpy().astype(np.uint64) * per_step[:steps]).sum())
+        return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
+
 
 IRRADIANCE_STREAM = 5  # the Philox stream id of irradiance()'s directions (0 path, 2 scene, 3 light samples, 4 roulette)
 

@@ -17,6 +17,7 @@
 #include "rtmi_query.h"
 #include "rtmi_radiance.h"
 #include "rtmi_sparse.h"
+#include "rtmi_pixelwise.h"
 #include "rtmi_gather.h"
 #include "rtmi_frame.h"
 #include "rtmi_upscale.h"
@@ -391,6 +392,30 @@ RTH_API int rth_sparse_refine(void *lowered, void *cam, const rtmi_render_params
                                                    static_cast<float *>(linear), static_cast<uint8_t *>(rgb8),
                                                    static_cast<float *>(stderr_rgb), static_cast<uint32_t *>(counts));
         return done(name, rc, CODED_UNSUPPORTED);
+    });
+}
+// per-pixel adaptive sampling (include/rtmi_pixelwise.h) on the uploaded handle: host planes and blocking, or device planes
+// enqueued on `stream`
+RTH_API int rth_render_pixelwise(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_pixelwise_opts *o, float *out_linear,
+                                 uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts, rtmi_stats *stats) {
+    return guard([&] {
+        const char *name = "rtmi_render_pixelwise";
+        rtmi_scene *dev = DEV(lowered, name, "pixelwise");
+        const rtmi_camera c = CAM(cam).lower();
+        return done(name, rtmi_render_pixelwise(dev, &c, p, o, out_linear, out_rgb8, out_stderr, out_spp, out_counts, stats),
+                    CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_render_pixelwise_device(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_pixelwise_opts *o,
+                                        void *d_linear, void *d_rgb8, void *d_stderr, void *d_spp, void *d_counts, void *d_scratch,
+                                        uint64_t scratch_bytes, void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_render_pixelwise_device";
+        rtmi_scene *dev = DEV(lowered, name, "pixelwise");
+        const rtmi_camera c = CAM(cam).lower();
+        return done(name, rtmi_render_pixelwise_device(dev, p, &c, o, d_linear, d_rgb8, d_stderr, d_spp, d_counts, d_scratch, scratch_bytes,
+                                                       stream),
+                    CODED_UNSUPPORTED);
     });
 }
 // hemisphere gathers (include/rtmi_gather.h) on the uploaded handle, as the radiance queries
