@@ -2081,10 +2081,35 @@ static int check_env_opts(const char *name, const rtmi_env_render *o) {
         return fail(RTMI_ERR_INVALID, std::string(name) + ": env_select_p must be in (0, 1]");
     return RTMI_OK;
 }
-static int refuse_sky(const char *name, const rtmi_render_params *p) {
-    if (p->flags & RTMI_FLAG_SKY)
+static int refuse_sky(const char *name, uint32_t flags) {
+    if (flags & RTMI_FLAG_SKY)
         return fail(RTMI_ERR_INVALID, std::string(name) + ": RTMI_FLAG_SKY is refused, the map replaces the sky");
     return RTMI_OK;
+}
+// The estimator of an entry that selects it by an RTMI_ROULETTE_* value (rtmi_roulette.h): the roulette renders, the sessions
+// and the batch modes.  env_select_p is read where both the lights and the map are sampled.  lit_estimator: the same of an
+// entry that holds the two choices themselves.  null_scene must outlive the Estimator.
+static Estimator lit_estimator(const char *name, bool nee, bool env, float env_select_p, const char *null_scene) {
+    return Estimator{name, nee, env, env_select_p, null_scene, "no light table attached (rtmi_scene_attach_lights)"};
+}
+static Estimator estimator_of(const char *name, uint32_t estimator, float env_select_p, const char *null_scene) {
+    const bool nee = estimator == RTMI_ROULETTE_NEE || estimator == RTMI_ROULETTE_ENV_NEE;
+    const bool env = estimator == RTMI_ROULETTE_ENV || estimator == RTMI_ROULETTE_ENV_NEE;
+    return lit_estimator(name, nee, env, nee && env ? env_select_p : 1.0f, null_scene);
+}
+// The checks of that selection, two because each entry has checks of its own between them: the value, and what the chosen
+// estimator refuses of env_select_p (read, and checked, only where both are sampled) and of the flags.
+static int check_estimator(const char *name, uint32_t estimator) {
+    if (estimator > RTMI_ROULETTE_ENV_NEE)
+        return fail(RTMI_ERR_INVALID, std::string(name) + ": estimator must be one of RTMI_ROULETTE_* (0..3)");
+    return RTMI_OK;
+}
+static int check_estimator_opts(const char *name, uint32_t estimator, float env_select_p, uint32_t flags) {
+    const rtmi_env_render eo{1u, env_select_p};
+    if (estimator == RTMI_ROULETTE_ENV_NEE)
+        if (int rc = check_env_opts(name, &eo)) return rc;
+    const bool env = estimator == RTMI_ROULETTE_ENV || estimator == RTMI_ROULETTE_ENV_NEE;
+    return env ? refuse_sky(name, flags) : RTMI_OK;
 }
 
 static DevEnv dev_env(const rtmi_scene *s, float p_env) {
@@ -2122,14 +2147,26 @@ struct RenderCall {
     uint32_t wps = 4u;
 };
 
+// the map and the light table the estimator reads are attached to the handle (the caller holds s->mu)
+static int check_attached(const Estimator &m, const rtmi_scene *s) {
+    if (m.env && !s->has_env)
+        return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no environment map attached (rtmi_scene_attach_env)");
+    if (m.nee && !s->has_lights) return fail(RTMI_ERR_INVALID, std::string(m.name) + ": " + m.no_lights);
+    return RTMI_OK;
+}
+// the same among the argument checks of the sparse and per-pixel entries: of a handle that is there, under its lock
+static int check_attached_early(const Estimator &m, const rtmi_scene *s_in) {
+    if (!s_in) return RTMI_OK;
+    rtmi_scene *s = const_cast<rtmi_scene *>(s_in);
+    std::lock_guard<std::mutex> lock(s->mu);
+    return check_attached(m, s);
+}
 // The end of an entry point's checks and the start of its device work, in this order: the handle, its lock, what the
 // estimator needs attached, then the device, no earlier render of the handle running, the busy mark.
 static int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
     if (!s) return fail(RTMI_ERR_INVALID, m.null_scene);
     c.lock = std::unique_lock<std::mutex>(s->mu);
-    if (m.env && !s->has_env)
-        return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no environment map attached (rtmi_scene_attach_env)");
-    if (m.nee && !s->has_lights) return fail(RTMI_ERR_INVALID, std::string(m.name) + ": " + m.no_lights);
+    if (int rc = check_attached(m, s)) return rc;
     if (m.tree && !s->has_light_tree)
         return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no light tree attached (rtmi_scene_attach_light_tree)");
     HIP_TRY(hipSetDevice(s->device));
@@ -2137,6 +2174,24 @@ static int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
     c.busy.s = s; c.busy.st = s->stream;
     return RTMI_OK;
 }
+// An asynchronous call's hold on the handle, which it takes without waiting for the handle's previous call: the lock, what
+// the estimator needs attached, the device, the caller's stream behind that previous call (a no-op when both were given the
+// same stream), the busy mark.  The members are declared in RenderCall's order: the lock is taken before the mark, and the
+// mark ends (records the call's end) before the lock is released.
+struct AsyncCall {
+    std::unique_lock<std::mutex> lock;
+    BusyMark busy{nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    int begin(const Estimator &m, rtmi_scene *s, void *stream_) {
+        lock = std::unique_lock<std::mutex>(s->mu);
+        if (int rc = check_attached(m, s)) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        stream = reinterpret_cast<hipStream_t>(stream_);
+        if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+        busy.s = s; busy.st = stream;
+        return RTMI_OK;
+    }
+};
 static void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, const rtmi_camera *cam,
                         const rtmi_render_params &p) {
     c.P = dev_params(s, &p);
@@ -2432,12 +2487,9 @@ static int query_device(const char *name, bool any, rtmi_scene *s, const rtmi_qu
     bool go;
     if (int rc = query_check(name, s, p, d_rays, d_out, &go)) return rc;
     if (!go) return RTMI_OK;
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    BusyMark busy_mark{s, stream};
-    HIP_TRY(rtmi_query_launch(any, query_fast(s, p, d_time != nullptr), stream, s->dev, query_batch(s, p, d_rays, d_time, d_out, any)));
+    AsyncCall c;
+    if (int rc = c.begin(Estimator{name, false, false, 1.0f, "scene is NULL", ""}, s, stream_)) return rc;
+    HIP_TRY(rtmi_query_launch(any, query_fast(s, p, d_time != nullptr), c.stream, s->dev, query_batch(s, p, d_rays, d_time, d_out, any)));
     return RTMI_OK;
 }
 // the blocking forms: the batch goes through the handle's query buffers (none of its render scratch) on its own stream
@@ -2509,6 +2561,67 @@ extern "C" int rtmi_occluded_device(rtmi_scene *s, const rtmi_query_params *p, c
     return query_device("rtmi_occluded_device", true, s, p, d_rays, d_time, d_occluded, stream);
 }
 
+// ---- the batch modes (radiance queries, hemisphere gathers, sparse renders, per-pixel adaptive sampling) ----------------
+// What their host paths share: the chunks of the persistent wavefronts (batch_take, rtmi_batch.hpp), the kernel arguments
+// of a call, and the end of a blocking call that reads its records through the handle's rad_out and rad_samples.
+
+// The chunk rule.  `total` items on the persistent grid of the per-lane render kernels (`slots` wavefronts): chunks of `cap`
+// items, smaller (a multiple of 64, at least 64) for a batch that would otherwise leave wavefronts of the grid without one
+// (four chunks a wavefront), and one workgroup a wavefront, no more than there are chunks.
+struct BatchChunks {
+    uint32_t chunk, nchunks, blocks;
+};
+static BatchChunks batch_chunks(const rtmi_scene *s, uint32_t total, uint32_t cap = RTMI_RADIANCE_CHUNK) {
+    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
+    const uint32_t share = (uint32_t)(((uint64_t)total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
+    BatchChunks c;
+    c.chunk = share < 64u ? 64u : (share > cap ? cap : share);
+    c.nchunks = (total + c.chunk - 1u) / c.chunk;
+    c.blocks = c.nchunks < slots ? c.nchunks : slots;
+    return c;
+}
+// The kernel arguments of a batch call: the estimator's lights and map, and the DevParams of `rp` with no pass planned
+// (ns = 1, rank 0 of 1; the pass fields stay unread) and `d_samples` as the per-sample buffer.  rp: the caller's image
+// (sparse renders) or no_image (radiance queries and gathers).
+struct BatchArgs {
+    DevParams P;
+    DevLights L;
+    DevEnv E;
+};
+static rtmi_render_params no_image(uint32_t max_depth, float t_min, uint64_t seed, uint32_t flags) {
+    rtmi_render_params rp{};
+    rp.nx = 1u; rp.ny = 1u;
+    rp.max_depth = max_depth; rp.t_min = t_min; rp.seed = seed; rp.flags = flags;
+    return rp;
+}
+static BatchArgs batch_args(const rtmi_scene *s, const Estimator &m, rtmi_render_params rp, void *d_samples) {
+    rp.ns = 1u; rp.tile_rank = 0u; rp.tile_world = 1u;
+    BatchArgs a;
+    a.P = dev_params(s, &rp);
+    a.P.samples = reinterpret_cast<Rad3 *>(d_samples);
+    dev_lighting(s, m.nee, m.env, m.env_select_p, a.L, a.E);
+    return a;
+}
+// The handle's buffers of a blocking call of n entries and ns samples in all, and the end of that call, whose enqueue ran
+// between ev[0] and ev[1]: the records to the host, the wait, the kernels' milliseconds.
+static int batch_reserve(rtmi_scene *s, size_t n, size_t ns) {
+    if (int rc = grow(s, s->rad_samples, s->rad_samples_bytes, ns * sizeof(Rad3))) return rc;
+    return grow(s, s->rad_out, s->rad_out_bytes, n * 6 * sizeof(float));
+}
+static int batch_finish(rtmi_scene *s, size_t n, size_t ns, float *out_mean, float *out_stderr, float *out_samples, double *kernel_ms) {
+    hipStream_t stream = s->stream;
+    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, s->rad_out, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, s->rad_out + n * 3, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (kernel_ms) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        *kernel_ms = (double)ms;
+    }
+    return RTMI_OK;
+}
+
 // ---- radiance queries (include/rtmi_radiance.h) -------------------------------------------------------------------------
 // The checks both forms share, in this order: params, flags, the values, the ray and output pointers of a batch with rays.
 // Nothing here reads the handle, so each is answered for a NULL one too; the handle and what the estimator needs attached
@@ -2519,7 +2632,7 @@ static int radiance_check(const char *name, const rtmi_radiance_params *p, const
     if (!p) return fail(RTMI_ERR_INVALID, nm + "params is NULL");
     if (p->flags & ~RTMI_RADIANCE_FLAGS)
         return fail(RTMI_ERR_UNSUPPORTED, nm + "radiance queries accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
-    if (p->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if (int rc = check_estimator(name, p->estimator)) return rc;
     if (p->spp == 0u) return fail(RTMI_ERR_INVALID, nm + "spp must be at least 1");
     if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
     if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
@@ -2528,40 +2641,17 @@ static int radiance_check(const char *name, const rtmi_radiance_params *p, const
     if ((uint64_t)p->first_sample + p->spp > (1ull << 32))
         return fail(RTMI_ERR_INVALID, nm + "first_sample + spp must not exceed 2^32 (a sample index would wrap onto another sample's stream)");
     if ((uint64_t)p->n * p->spp >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "n * spp must be below 2^31");
-    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
-    if (p->estimator == RTMI_ROULETTE_ENV_NEE && !(p->env_select_p > 0.0f && p->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
-    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (int rc = check_estimator_opts(name, p->estimator, p->env_select_p, p->flags)) return rc;
     if (p->n == 0u) return RTMI_OK;
     if (!rays) return fail(RTMI_ERR_INVALID, nm + "rays is NULL");
     if (!has_out) return fail(RTMI_ERR_INVALID, nm + out_msg);
     return RTMI_OK;
 }
-// begin_call's attach checks for the asynchronous form, which takes the (locked) handle without waiting for its previous call
-static int radiance_attached(const Estimator &m, const rtmi_scene *s) {
-    if (m.env && !s->has_env)
-        return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no environment map attached (rtmi_scene_attach_env)");
-    if (m.nee && !s->has_lights) return fail(RTMI_ERR_INVALID, std::string(m.name) + ": " + m.no_lights);
-    return RTMI_OK;
-}
-static Estimator radiance_estimator(const char *name, const rtmi_radiance_params *p, const std::string &null_scene) {
-    const bool nee = p->estimator == RTMI_ROULETTE_NEE || p->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
-    return Estimator{name, nee, env, nee && env ? p->env_select_p : 1.0f, null_scene.c_str(),
-                     "no light table attached (rtmi_scene_attach_lights)"};
-}
 // The two launches of a call on `stream`: the path kernel on the persistent grid of the per-lane render kernels, fed by the
 // handle's chunk counter (zeroed here, on the call's stream: the handle serialises its calls), then the resolve.
 static int radiance_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_radiance_params *p, hipStream_t stream, const void *d_rays,
                             const void *d_time, void *d_mean, void *d_stderr, void *d_samples) {
-    rtmi_render_params rp{};
-    rp.nx = 1u; rp.ny = 1u; rp.ns = 1u; rp.tile_world = 1u; // no image: the pass fields of DevParams stay unread
-    rp.max_depth = p->max_depth; rp.t_min = p->t_min; rp.seed = p->seed; rp.flags = p->flags;
-    DevParams P = dev_params(s, &rp);
-    P.samples = reinterpret_cast<Rad3 *>(d_samples);
-    DevLights L;
-    DevEnv E;
-    dev_lighting(s, m.nee, m.env, m.env_select_p, L, E);
+    const BatchArgs a = batch_args(s, m, no_image(p->max_depth, p->t_min, p->seed, p->flags), d_samples);
     RadianceBatch B{};
     B.rays = reinterpret_cast<const float4 *>(d_rays);
     B.time = reinterpret_cast<const float *>(d_time);
@@ -2571,21 +2661,17 @@ static int radiance_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_radian
     B.n = p->n; B.spp = p->spp; B.total = p->n * p->spp;
     B.first_ray = (uint32_t)p->first_ray; B.first_sample = p->first_sample;
     B.skip_block = p->stream_skip >> 2; B.skip_pos = p->stream_skip & 3u;
-    // chunks of RTMI_RADIANCE_CHUNK items, smaller for a batch that would otherwise leave wavefronts of the grid without one
-    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
-    const uint32_t share = (uint32_t)(((uint64_t)B.total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
     uint32_t cap = RTMI_RADIANCE_CHUNK;
     if (const char *e = getenv("RTMI_RADIANCE_CHUNK")) { // tuning knob of tools/radiance_timing.py: a multiple of 64 in [64, 65536]
         const long v = atol(e);
         if (v >= 64 && v <= 65536) cap = (uint32_t)v & ~63u;
     }
-    B.chunk = share < 64u ? 64u : (share > cap ? cap : share);
-    B.nchunks = (B.total + B.chunk - 1u) / B.chunk;
+    const BatchChunks ch = batch_chunks(s, B.total, cap);
+    B.chunk = ch.chunk; B.nchunks = ch.nchunks;
     const rtmi_query_params q{p->n, p->flags & RTMI_FLAG_FAST_CULL, 0ull, 0ull};
     HIP_TRY(hipMemsetAsync(B.queue, 0, sizeof(unsigned int), stream));
-    HIP_TRY(rtmi_radiance_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, B.nchunks < slots ? B.nchunks : slots, stream,
-                                 s->dev, P, B, L, E));
-    if (d_mean || d_stderr) HIP_TRY(rtmi_radiance_launch_resolve(stream, P.samples, B));
+    HIP_TRY(rtmi_radiance_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, ch.blocks, stream, s->dev, a.P, B, a.L, a.E));
+    if (d_mean || d_stderr) HIP_TRY(rtmi_radiance_launch_resolve(stream, a.P.samples, B));
     return RTMI_OK;
 }
 extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const rtmi_ray *rays, const float *time, float *out_mean,
@@ -2596,7 +2682,7 @@ extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const
     if (kernel_ms) *kernel_ms = 0.0;
     if (p->n && (rc = query_check_rays(name, rays, time, p->n))) return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = radiance_estimator(name, p, null_scene);
+    const Estimator m = estimator_of(name, p->estimator, p->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (p->n == 0u) return RTMI_OK;
     RenderCall c;
@@ -2604,9 +2690,7 @@ extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const
     hipStream_t stream = s->stream;
     const size_t n = p->n, ns = n * p->spp;
     if ((rc = grow(s, s->q_rays, s->q_rays_bytes, n * sizeof(rtmi_ray))) ||
-        (time && (rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(float)))) ||
-        (rc = grow(s, s->rad_samples, s->rad_samples_bytes, ns * sizeof(Rad3))) ||
-        (rc = grow(s, s->rad_out, s->rad_out_bytes, n * 6 * sizeof(float))))
+        (time && (rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(float)))) || (rc = batch_reserve(s, n, ns)))
         return rc;
     float *d_mean = s->rad_out, *d_stderr = s->rad_out + n * 3;
     HIP_TRY(hipMemcpyAsync(s->q_rays, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
@@ -2616,32 +2700,19 @@ extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const
                                out_stderr ? d_stderr : nullptr, s->rad_samples)))
         return rc;
     HIP_TRY(hipEventRecord(s->ev[1], stream));
-    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, d_mean, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, d_stderr, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-        *kernel_ms = (double)ms;
-    }
-    return RTMI_OK;
+    return batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms);
 }
 extern "C" int rtmi_radiance_device(rtmi_scene *s, const rtmi_radiance_params *p, const void *d_rays, const void *d_time, void *d_mean,
                                     void *d_stderr, void *d_samples, void *stream_) {
     const char *name = "rtmi_radiance_device";
     if (int rc = radiance_check(name, p, d_rays, d_samples != nullptr, "d_samples is NULL (the kernel's per-sample buffer)")) return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = radiance_estimator(name, p, null_scene);
+    const Estimator m = estimator_of(name, p->estimator, p->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (p->n == 0u) return RTMI_OK;
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (int rc = radiance_attached(m, s)) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    BusyMark busy_mark{s, stream};
-    return radiance_enqueue(s, m, p, stream, d_rays, d_time, d_mean, d_stderr, d_samples);
+    AsyncCall c;
+    if (int rc = c.begin(m, s, stream_)) return rc;
+    return radiance_enqueue(s, m, p, c.stream, d_rays, d_time, d_mean, d_stderr, d_samples);
 }
 
 // ---- hemisphere gathers (include/rtmi_gather.h) ---------------------------------------------------------------------------
@@ -2654,7 +2725,7 @@ static int gather_check(const char *name, const rtmi_gather_params *p, const voi
     if (p->flags & ~RTMI_RADIANCE_FLAGS)
         return fail(RTMI_ERR_UNSUPPORTED, nm + "gathers accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     if (p->mode > RTMI_GATHER_SPHERE) return fail(RTMI_ERR_INVALID, nm + "mode must be RTMI_GATHER_COSINE or RTMI_GATHER_SPHERE");
-    if (p->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if (int rc = check_estimator(name, p->estimator)) return rc;
     if (p->spp == 0u) return fail(RTMI_ERR_INVALID, nm + "spp must be at least 1");
     if (p->spp >= (1u << 31)) return fail(RTMI_ERR_INVALID, nm + "spp must be below 2^31 (one point's samples are one slab)");
     if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
@@ -2663,10 +2734,7 @@ static int gather_check(const char *name, const rtmi_gather_params *p, const voi
         return fail(RTMI_ERR_INVALID, nm + "first_point + n must not exceed 2^32 (a point index would wrap onto another point's stream)");
     if ((uint64_t)p->first_sample + p->spp > (1ull << 32))
         return fail(RTMI_ERR_INVALID, nm + "first_sample + spp must not exceed 2^32 (a sample index would wrap onto another sample's stream)");
-    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
-    if (p->estimator == RTMI_ROULETTE_ENV_NEE && !(p->env_select_p > 0.0f && p->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
-    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (int rc = check_estimator_opts(name, p->estimator, p->env_select_p, p->flags)) return rc;
     if (p->mode == RTMI_GATHER_COSINE && has_sh)
         return fail(RTMI_ERR_INVALID, nm + "the sh output belongs to RTMI_GATHER_SPHERE (convolve a probe with sh_irradiance instead)");
     if (p->n == 0u) return RTMI_OK;
@@ -2692,12 +2760,6 @@ static int gather_check_points(const char *name, const rtmi_gather_params *p, co
     }
     return RTMI_OK;
 }
-static Estimator gather_estimator(const char *name, const rtmi_gather_params *p, const std::string &null_scene) {
-    const bool nee = p->estimator == RTMI_ROULETTE_NEE || p->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool env = p->estimator == RTMI_ROULETTE_ENV || p->estimator == RTMI_ROULETTE_ENV_NEE;
-    return Estimator{name, nee, env, nee && env ? p->env_select_p : 1.0f, null_scene.c_str(),
-                     "no light table attached (rtmi_scene_attach_lights)"};
-}
 // the points of a slab: `want` (params.slab_points, or the form's own default or capacity) held to [1, (2^31 - 1) / spp]
 static uint32_t gather_slab(const rtmi_gather_params *p, uint64_t want) {
     const uint64_t most = ((1ull << 31) - 1u) / p->spp; // >= 1: spp < 2^31
@@ -2709,14 +2771,7 @@ static uint32_t gather_slab(const rtmi_gather_params *p, uint64_t want) {
 static int gather_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_gather_params *p, hipStream_t stream, uint32_t at,
                           uint32_t count, const void *d_points, const void *d_normals, const void *d_time, void *d_value,
                           void *d_stderr, void *d_sh, void *d_scratch) {
-    rtmi_render_params rp{};
-    rp.nx = 1u; rp.ny = 1u; rp.ns = 1u; rp.tile_world = 1u; // no image: the pass fields of DevParams stay unread
-    rp.max_depth = p->max_depth; rp.t_min = p->t_min; rp.seed = p->seed; rp.flags = p->flags;
-    DevParams P = dev_params(s, &rp);
-    P.samples = reinterpret_cast<Rad3 *>(d_scratch);
-    DevLights L;
-    DevEnv E;
-    dev_lighting(s, m.nee, m.env, m.env_select_p, L, E);
+    const BatchArgs a = batch_args(s, m, no_image(p->max_depth, p->t_min, p->seed, p->flags), d_scratch);
     GatherBatch B{};
     B.points = reinterpret_cast<const float *>(d_points);
     B.normals = p->mode == RTMI_GATHER_COSINE ? reinterpret_cast<const float *>(d_normals) : nullptr;
@@ -2727,16 +2782,12 @@ static int gather_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_gather_p
     B.queue = s->status + RTMI_STATUS_WORDS;
     B.n = count; B.spp = p->spp; B.total = count * p->spp;
     B.first_point = (uint32_t)(p->first_point + at); B.first_sample = p->first_sample;
-    // chunks as radiance_enqueue sizes them
-    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
-    const uint32_t share = (uint32_t)(((uint64_t)B.total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
-    B.chunk = share < 64u ? 64u : (share > RTMI_RADIANCE_CHUNK ? RTMI_RADIANCE_CHUNK : share);
-    B.nchunks = (B.total + B.chunk - 1u) / B.chunk;
+    const BatchChunks ch = batch_chunks(s, B.total);
+    B.chunk = ch.chunk; B.nchunks = ch.nchunks;
     const rtmi_query_params q{count, p->flags & RTMI_FLAG_FAST_CULL, 0ull, 0ull};
     HIP_TRY(hipMemsetAsync(B.queue, 0, sizeof(unsigned int), stream));
-    HIP_TRY(rtmi_gather_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, p->mode, B.nchunks < slots ? B.nchunks : slots,
-                               stream, s->dev, P, B, L, E));
-    if (d_value || d_stderr || d_sh) HIP_TRY(rtmi_gather_launch_resolve(p->mode, stream, P.samples, B, P.key0, P.key1));
+    HIP_TRY(rtmi_gather_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, p->mode, ch.blocks, stream, s->dev, a.P, B, a.L, a.E));
+    if (d_value || d_stderr || d_sh) HIP_TRY(rtmi_gather_launch_resolve(p->mode, stream, a.P.samples, B, a.P.key0, a.P.key1));
     return RTMI_OK;
 }
 extern "C" int rtmi_gather(rtmi_scene *s, const rtmi_gather_params *p, const float *points, const float *normals, const float *time,
@@ -2748,7 +2799,7 @@ extern "C" int rtmi_gather(rtmi_scene *s, const rtmi_gather_params *p, const flo
     if (kernel_ms) *kernel_ms = 0.0;
     if (p->n && (rc = gather_check_points(name, p, points, normals, time))) return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = gather_estimator(name, p, null_scene);
+    const Estimator m = estimator_of(name, p->estimator, p->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (p->n == 0u) return RTMI_OK;
     RenderCall c;
@@ -2795,15 +2846,11 @@ extern "C" int rtmi_gather_device(rtmi_scene *s, const rtmi_gather_params *p, co
     if (p->n && (!d_scratch || scratch_bytes < 12ull * p->spp))
         return fail(RTMI_ERR_INVALID, std::string(name) + ": d_scratch must hold one point's samples, scratch_bytes >= 12 * spp");
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = gather_estimator(name, p, null_scene);
+    const Estimator m = estimator_of(name, p->estimator, p->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (p->n == 0u) return RTMI_OK;
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (int rc = radiance_attached(m, s)) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    BusyMark busy_mark{s, stream};
+    AsyncCall c;
+    if (int rc = c.begin(m, s, stream_)) return rc;
     const uint64_t fits = scratch_bytes / (12ull * p->spp);
     const uint32_t slab = gather_slab(p, p->slab_points && p->slab_points < fits ? p->slab_points : fits);
     const char *pts = reinterpret_cast<const char *>(d_points), *nrm = reinterpret_cast<const char *>(d_normals);
@@ -2811,7 +2858,7 @@ extern "C" int rtmi_gather_device(rtmi_scene *s, const rtmi_gather_params *p, co
     char *val = reinterpret_cast<char *>(d_value), *se = reinterpret_cast<char *>(d_stderr), *sh = reinterpret_cast<char *>(d_sh);
     for (uint64_t at = 0; at < p->n; at += slab) {
         const uint32_t cnt = p->n - at < slab ? (uint32_t)(p->n - at) : slab;
-        if (int rc = gather_enqueue(s, m, p, stream, (uint32_t)at, cnt, pts + 12 * at, nrm ? nrm + 12 * at : nullptr,
+        if (int rc = gather_enqueue(s, m, p, c.stream, (uint32_t)at, cnt, pts + 12 * at, nrm ? nrm + 12 * at : nullptr,
                                     tm ? tm + 4 * at : nullptr, val ? val + 12 * at : nullptr, se ? se + 12 * at : nullptr,
                                     sh ? sh + 108 * at : nullptr, d_scratch))
             return rc;
@@ -2839,9 +2886,14 @@ static SparseScratch sparse_scratch(uint64_t n_pixels, uint32_t capacity, uint32
 extern "C" uint64_t rtmi_sparse_scratch_bytes(uint64_t n_pixels, uint32_t capacity, uint32_t ns) {
     return sparse_scratch(n_pixels, capacity, ns).total;
 }
-static bool sparse_misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1u)) != 0u; }
-// the end of the stateless entries' checks: the device
-static int sparse_device(const std::string &nm, int device) {
+// one device allocation of a call, freed on every return path
+struct DeviceMem {
+    char *base = nullptr;
+    ~DeviceMem() { if (base) (void)hipFree(base); }
+};
+static bool misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1u)) != 0u; }
+// the end of the stateless entries' checks (select, patch, the step probe): the device
+static int use_device(const std::string &nm, int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RTMI_ERR_DEVICE, nm + "no HIP device available");
     if (device < 0 || device >= n) return fail(RTMI_ERR_DEVICE, nm + "device index out of range");
@@ -2854,9 +2906,9 @@ extern "C" int rtmi_sparse_select_device(int device, uint32_t n, const void *d_b
     if (!d_bytes || !d_list || !d_count || !d_scratch) return fail(RTMI_ERR_INVALID, nm + "NULL argument");
     if (n == 0u || n > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "n must be in 1 .. 32768^2");
     if (capacity == 0u) return fail(RTMI_ERR_INVALID, nm + "capacity must be at least 1");
-    if (sparse_misaligned(d_list, 4) || sparse_misaligned(d_count, 4) || sparse_misaligned(d_scratch, 16))
+    if (misaligned(d_list, 4) || misaligned(d_count, 4) || misaligned(d_scratch, 16))
         return fail(RTMI_ERR_INVALID, nm + "misaligned list, count (4 bytes) or scratch (16 bytes)");
-    if (int rc = sparse_device(nm, device)) return rc;
+    if (int rc = use_device(nm, device)) return rc;
     uint32_t *scratch = reinterpret_cast<uint32_t *>(d_scratch);
     HIP_TRY(rtmi_sparse_launch_select(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const uint8_t *>(d_bytes), n, accept_mask,
                                       capacity, reinterpret_cast<uint32_t *>(d_list), reinterpret_cast<uint32_t *>(d_count),
@@ -2871,20 +2923,14 @@ extern "C" int rtmi_sparse_patch_device(int device, uint32_t n_pixels, const voi
     if (n_pixels == 0u || n_pixels > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "n_pixels must be in 1 .. 32768^2");
     if (capacity == 0u) return fail(RTMI_ERR_INVALID, nm + "capacity must be at least 1");
     if (mark > 255u) return fail(RTMI_ERR_INVALID, nm + "mark must be a byte");
-    if (sparse_misaligned(d_list, 4) || sparse_misaligned(d_count, 4) || sparse_misaligned(d_mean, 4) || sparse_misaligned(d_linear, 4))
+    if (misaligned(d_list, 4) || misaligned(d_count, 4) || misaligned(d_mean, 4) || misaligned(d_linear, 4))
         return fail(RTMI_ERR_INVALID, nm + "misaligned list, count, mean or linear (4 bytes)");
-    if (int rc = sparse_device(nm, device)) return rc;
+    if (int rc = use_device(nm, device)) return rc;
     HIP_TRY(rtmi_sparse_launch_patch(reinterpret_cast<hipStream_t>(stream), n_pixels, reinterpret_cast<const uint32_t *>(d_list),
                                      reinterpret_cast<const uint32_t *>(d_count), capacity, reinterpret_cast<const float *>(d_mean),
                                      nullptr, reinterpret_cast<float *>(d_linear), reinterpret_cast<uint8_t *>(d_rgb8), nullptr,
                                      reinterpret_cast<uint8_t *>(d_bytes), mark));
     return RTMI_OK;
-}
-static Estimator sparse_estimator(const char *name, const rtmi_sparse_params *sp, const std::string &null_scene) {
-    const bool nee = sp->estimator == RTMI_ROULETTE_NEE || sp->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool env = sp->estimator == RTMI_ROULETTE_ENV || sp->estimator == RTMI_ROULETTE_ENV_NEE;
-    return Estimator{name, nee, env, nee && env ? sp->env_select_p : 1.0f, null_scene.c_str(),
-                     "no light table attached (rtmi_scene_attach_lights)"};
 }
 // The checks the render and refine entries share, in this order: the pointers, the outputs, the values, what the estimator
 // needs attached (of a handle that is there), the reserved words, the flags.  The entry's own checks and the NULL handle
@@ -2897,24 +2943,15 @@ static int sparse_check(const char *name, const rtmi_scene *s_in, const rtmi_ren
     if (!has_out) return fail(RTMI_ERR_INVALID, nm + out_msg);
     if (sp->ns == 0u) return fail(RTMI_ERR_INVALID, nm + "ns must be at least 1");
     if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
-    if (sp->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if (int rc = check_estimator(name, sp->estimator)) return rc;
     if ((uint64_t)sp->first_sample + sp->ns > (1ull << 32))
         return fail(RTMI_ERR_INVALID, nm + "first_sample + ns must not exceed 2^32 (a sample index would wrap onto another sample's stream)");
     if ((uint64_t)sp->n * sp->ns >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "n * ns must be below 2^31");
-    const bool env = sp->estimator == RTMI_ROULETTE_ENV || sp->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool nee = sp->estimator == RTMI_ROULETTE_NEE || sp->estimator == RTMI_ROULETTE_ENV_NEE;
-    if (sp->estimator == RTMI_ROULETTE_ENV_NEE && !(sp->env_select_p > 0.0f && sp->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
-    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    if (int rc = check_estimator_opts(name, sp->estimator, sp->env_select_p, p->flags)) return rc;
     if (p->nx == 0u || p->ny == 0u || (uint64_t)p->nx * p->ny > 0xffffffffull)
         return fail(RTMI_ERR_INVALID, nm + "the image must have 1 .. 2^32 - 1 pixels");
     if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
-    if (s_in) {
-        rtmi_scene *s = const_cast<rtmi_scene *>(s_in);
-        std::lock_guard<std::mutex> lock(s->mu);
-        if (env && !s->has_env) return fail(RTMI_ERR_INVALID, nm + "no environment map attached (rtmi_scene_attach_env)");
-        if (nee && !s->has_lights) return fail(RTMI_ERR_INVALID, nm + "no light table attached (rtmi_scene_attach_lights)");
-    }
+    if (int rc = check_attached_early(estimator_of(name, sp->estimator, sp->env_select_p, ""), s_in)) return rc;
     if (sp->reserved[0] || sp->reserved[1] || sp->reserved[2]) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
     if (p->flags & ~RTMI_RADIANCE_FLAGS)
         return fail(RTMI_ERR_UNSUPPORTED, nm + "sparse renders accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
@@ -2925,14 +2962,8 @@ static int sparse_check(const char *name, const rtmi_scene *s_in, const rtmi_ren
 static int sparse_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_params *p, const rtmi_camera *cam,
                           const rtmi_sparse_params *sp, hipStream_t stream, const void *d_pixels, const void *d_count, void *d_mean,
                           void *d_stderr, void *d_samples, unsigned int *queue) {
-    rtmi_render_params rp = *p;
-    rp.ns = 1u; rp.tile_rank = 0u; rp.tile_world = 1u; // the image's nx, ny, seed, max_depth, t_min and flags; no pass is planned
-    DevParams P = dev_params(s, &rp);
-    P.samples = reinterpret_cast<Rad3 *>(d_samples);
+    const BatchArgs a = batch_args(s, m, *p, d_samples); // the image's nx, ny, seed, max_depth, t_min and flags
     const DevCamera C = dev_camera(cam);
-    DevLights L;
-    DevEnv E;
-    dev_lighting(s, m.nee, m.env, m.env_select_p, L, E);
     SparseBatch B{};
     B.list = reinterpret_cast<const uint32_t *>(d_pixels);
     B.count = reinterpret_cast<const uint32_t *>(d_count);
@@ -2940,16 +2971,12 @@ static int sparse_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_p
     B.stderr_out = reinterpret_cast<float *>(d_stderr);
     B.queue = queue;
     B.n = sp->n; B.ns = sp->ns; B.first_sample = sp->first_sample;
-    // chunks as radiance_enqueue sizes them, for a full list
-    const uint32_t total = sp->n * sp->ns;
-    const uint32_t slots = (uint32_t)(s->slots / 20) * 4u * 4u;
-    const uint32_t share = (uint32_t)(((uint64_t)total / ((uint64_t)slots * 4u) + 63ull) & ~63ull);
-    B.chunk = share < 64u ? 64u : (share > RTMI_RADIANCE_CHUNK ? RTMI_RADIANCE_CHUNK : share);
-    const uint32_t nchunks = (total + B.chunk - 1u) / B.chunk;
+    const BatchChunks ch = batch_chunks(s, sp->n * sp->ns); // for a full list: the kernel counts the chunks of the entries there are
+    B.chunk = ch.chunk;
     const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
     HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned int), stream));
-    HIP_TRY(rtmi_sparse_launch(fast, m.nee, m.env, nchunks < slots ? nchunks : slots, stream, s->dev, C, P, B, L, E));
-    if (d_mean || d_stderr) HIP_TRY(rtmi_sparse_launch_resolve(stream, P.samples, B));
+    HIP_TRY(rtmi_sparse_launch(fast, m.nee, m.env, ch.blocks, stream, s->dev, C, a.P, B, a.L, a.E));
+    if (d_mean || d_stderr) HIP_TRY(rtmi_sparse_launch_resolve(stream, a.P.samples, B));
     return RTMI_OK;
 }
 extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
@@ -2965,17 +2992,14 @@ extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, co
             return fail(RTMI_ERR_INVALID, std::string(name) + ": pixels[" + std::to_string(k) + "] = " + std::to_string(pixels[k]) +
                                               " is outside the image");
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = sparse_estimator(name, sp, null_scene);
+    const Estimator m = estimator_of(name, sp->estimator, sp->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (sp->n == 0u) return RTMI_OK;
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
     hipStream_t stream = s->stream;
     const size_t n = sp->n, ns = n * sp->ns;
-    if ((rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(uint32_t))) ||
-        (rc = grow(s, s->rad_samples, s->rad_samples_bytes, ns * sizeof(Rad3))) ||
-        (rc = grow(s, s->rad_out, s->rad_out_bytes, n * 6 * sizeof(float))))
-        return rc;
+    if ((rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(uint32_t))) || (rc = batch_reserve(s, n, ns))) return rc;
     float *d_mean = s->rad_out, *d_stderr = s->rad_out + n * 3;
     HIP_TRY(hipMemcpyAsync(s->q_time, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipEventRecord(s->ev[0], stream));
@@ -2983,16 +3007,7 @@ extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, co
                              s->rad_samples, s->status + RTMI_STATUS_WORDS)))
         return rc;
     HIP_TRY(hipEventRecord(s->ev[1], stream));
-    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, d_mean, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, d_stderr, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (kernel_ms) {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-        *kernel_ms = (double)ms;
-    }
-    return RTMI_OK;
+    return batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms);
 }
 extern "C" int rtmi_sparse_render_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
                                          const void *d_pixels, const void *d_count, void *d_mean, void *d_stderr, void *d_samples,
@@ -3002,20 +3017,16 @@ extern "C" int rtmi_sparse_render_device(rtmi_scene *s, const rtmi_render_params
                               "d_samples is NULL (the kernel's per-sample buffer)"))
         return rc;
     if (!d_scratch) return fail(RTMI_ERR_INVALID, std::string(name) + ": d_scratch is NULL");
-    if (sparse_misaligned(d_pixels, 4) || sparse_misaligned(d_count, 4) || sparse_misaligned(d_mean, 4) || sparse_misaligned(d_stderr, 4) ||
-        sparse_misaligned(d_samples, 4) || sparse_misaligned(d_scratch, 4))
+    if (misaligned(d_pixels, 4) || misaligned(d_count, 4) || misaligned(d_mean, 4) || misaligned(d_stderr, 4) ||
+        misaligned(d_samples, 4) || misaligned(d_scratch, 4))
         return fail(RTMI_ERR_INVALID, std::string(name) + ": misaligned pointer (4 bytes)");
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = sparse_estimator(name, sp, null_scene);
+    const Estimator m = estimator_of(name, sp->estimator, sp->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (sp->n == 0u) return RTMI_OK;
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (int rc = radiance_attached(m, s)) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    BusyMark busy_mark{s, stream};
-    return sparse_enqueue(s, m, p, cam, sp, stream, d_pixels, d_count, d_mean, d_stderr, d_samples,
+    AsyncCall c;
+    if (int rc = c.begin(m, s, stream_)) return rc;
+    return sparse_enqueue(s, m, p, cam, sp, c.stream, d_pixels, d_count, d_mean, d_stderr, d_samples,
                           reinterpret_cast<unsigned int *>(d_scratch) + RTMI_SPARSE_QUEUE_WORD);
 }
 // the refine entries' own checks, after sparse_check: the planes, the scratch, the mark
@@ -3029,7 +3040,7 @@ static int sparse_refine_check(const char *name, const rtmi_render_params *p, co
     if (mark > 255u) return fail(RTMI_ERR_INVALID, nm + "mark must be a byte");
     if (!device_form) return RTMI_OK;
     if (!scratch) return fail(RTMI_ERR_INVALID, nm + "d_scratch is NULL");
-    if (sparse_misaligned(linear, 4) || sparse_misaligned(se, 4) || sparse_misaligned(count_out, 4) || sparse_misaligned(scratch, 16))
+    if (misaligned(linear, 4) || misaligned(se, 4) || misaligned(count_out, 4) || misaligned(scratch, 16))
         return fail(RTMI_ERR_INVALID, nm + "misaligned linear, stderr, count (4 bytes) or scratch (16 bytes)");
     if (scratch_bytes < sparse_scratch(npix, sp->n, sp->ns).total)
         return fail(RTMI_ERR_INVALID, nm + "scratch_bytes is below rtmi_sparse_scratch_bytes(nx * ny, sp->n, sp->ns)");
@@ -3064,15 +3075,11 @@ extern "C" int rtmi_sparse_refine_device(rtmi_scene *s, const rtmi_render_params
         (rc = sparse_refine_check(name, p, sp, mark, true, d_bytes, d_linear, d_stderr, d_scratch, scratch_bytes, d_count_out)))
         return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = sparse_estimator(name, sp, null_scene);
+    const Estimator m = estimator_of(name, sp->estimator, sp->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
-    std::lock_guard<std::mutex> lock(s->mu);
-    if ((rc = radiance_attached(m, s))) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    BusyMark busy_mark{s, stream};
-    return sparse_refine_enqueue(s, m, p, cam, sp, accept_mask, mark, stream, d_bytes, d_linear, d_rgb8, d_stderr, d_scratch, d_count_out);
+    AsyncCall c;
+    if ((rc = c.begin(m, s, stream_))) return rc;
+    return sparse_refine_enqueue(s, m, p, cam, sp, accept_mask, mark, c.stream, d_bytes, d_linear, d_rgb8, d_stderr, d_scratch, d_count_out);
 }
 extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
                                   uint32_t accept_mask, uint32_t mark, uint8_t *bytes, float *linear, uint8_t *rgb8, float *stderr_rgb,
@@ -3083,17 +3090,14 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
         (rc = sparse_refine_check(name, p, sp, mark, false, bytes, linear, stderr_rgb, nullptr, 0, counts)))
         return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = sparse_estimator(name, sp, null_scene);
+    const Estimator m = estimator_of(name, sp->estimator, sp->env_select_p, null_scene.c_str());
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
     hipStream_t stream = s->stream;
-    // one allocation per call, freed on every return path: bytes | scratch | linear | stderr | rgb8
+    // one allocation per call: bytes | scratch | linear | stderr | rgb8
     const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
     const size_t scratch_bytes = (size_t)sparse_scratch(npix, sp->n, sp->ns).total;
-    struct Mem {
-        char *base = nullptr;
-        ~Mem() { if (base) (void)hipFree(base); }
-    } mem;
+    DeviceMem mem;
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), up + scratch_bytes + 12 * up + 12 * up + 3 * up));
     char *d_bytes = mem.base, *d_scratch = d_bytes + up, *d_linear = d_scratch + scratch_bytes, *d_se = d_linear + 12 * up,
          *d_rgb8 = d_se + 12 * up;
@@ -3149,12 +3153,6 @@ static uint32_t pixelwise_pass(const rtmi_render_params *p, const rtmi_pixelwise
     const uint32_t step = o->min_spp > later ? o->min_spp : later;
     return o->pass_spp == 0u || o->pass_spp > step ? step : o->pass_spp;
 }
-static Estimator pixelwise_estimator(const char *name, const rtmi_pixelwise_opts *o, const std::string &null_scene) {
-    const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    return Estimator{name, nee, env, nee && env ? o->env_select_p : 1.0f, null_scene.c_str(),
-                     "no light table attached (rtmi_scene_attach_lights)"};
-}
 // The checks of both render forms, in the order of sparse_check (pointers, outputs, values, attachments of a handle that is
 // there, flags), then this header's own: the steps and tolerances, the size of a launch, the number of steps, the scratch and
 // the alignments (device form), the reserved words.  The NULL handle follows in the entries.
@@ -3169,25 +3167,16 @@ static int pixelwise_check(const char *name, const rtmi_scene *s_in, const rtmi_
     if (!out.linear && !out.rgb8 && !out.se && !out.spp) return fail(RTMI_ERR_INVALID, nm + "every plane is NULL");
     if (p->ns == 0u) return fail(RTMI_ERR_INVALID, nm + "ns, the cap, must be at least 1");
     if (p->max_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "max_depth must be at least 1");
-    if (o->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
-    const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    if (o->estimator == RTMI_ROULETTE_ENV_NEE && !(o->env_select_p > 0.0f && o->env_select_p <= 1.0f))
-        return fail(RTMI_ERR_INVALID, nm + "env_select_p must be in (0, 1]");
-    if (env && (p->flags & RTMI_FLAG_SKY)) return fail(RTMI_ERR_INVALID, nm + "RTMI_FLAG_SKY is refused, the map replaces the sky");
+    int rc;
+    if ((rc = check_estimator(name, o->estimator)) || (rc = check_estimator_opts(name, o->estimator, o->env_select_p, p->flags))) return rc;
     const uint64_t npix = (uint64_t)p->nx * p->ny;
     if (npix == 0u || npix > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "the image must have 1 .. 32768^2 pixels");
     if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
-    if (s_in) {
-        rtmi_scene *s = const_cast<rtmi_scene *>(s_in);
-        std::lock_guard<std::mutex> lock(s->mu);
-        if (env && !s->has_env) return fail(RTMI_ERR_INVALID, nm + "no environment map attached (rtmi_scene_attach_env)");
-        if (nee && !s->has_lights) return fail(RTMI_ERR_INVALID, nm + "no light table attached (rtmi_scene_attach_lights)");
-    }
+    if ((rc = check_attached_early(estimator_of(name, o->estimator, o->env_select_p, ""), s_in))) return rc;
     if (p->flags & ~RTMI_RADIANCE_FLAGS)
         return fail(RTMI_ERR_UNSUPPORTED, nm + "per-pixel adaptive sampling accepts the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     const rtmi_adaptive a{o->min_spp, o->step_spp, o->abs_tol, o->rel_tol};
-    if (int rc = check_adaptive(p, &a)) return fail(rc, nm + g_err);
+    if ((rc = check_adaptive(p, &a))) return fail(rc, nm + g_err);
     const uint32_t pass = pixelwise_pass(p, o);
     if (npix * pass >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "nx * ny * (samples of a launch) must be below 2^31: lower pass_spp");
     const uint32_t steps = rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp);
@@ -3196,8 +3185,8 @@ static int pixelwise_check(const char *name, const rtmi_scene *s_in, const rtmi_
         if (!scratch) return fail(RTMI_ERR_INVALID, nm + "d_scratch is NULL");
         if (scratch_bytes < pixelwise_scratch(npix, pass, steps).total)
             return fail(RTMI_ERR_INVALID, nm + "scratch_bytes is below rtmi_pixelwise_scratch_bytes(nx * ny, pass, steps)");
-        if (sparse_misaligned(out.linear, 4) || sparse_misaligned(out.se, 4) || sparse_misaligned(out.spp, 4) ||
-            sparse_misaligned(out.counts, 4) || sparse_misaligned(scratch, 16))
+        if (misaligned(out.linear, 4) || misaligned(out.se, 4) || misaligned(out.spp, 4) ||
+            misaligned(out.counts, 4) || misaligned(scratch, 16))
             return fail(RTMI_ERR_INVALID, nm + "misaligned linear, stderr, spp, counts (4 bytes) or scratch (16 bytes)");
     }
     if (o->reserved[0] || o->reserved[1] || o->reserved[2]) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
@@ -3260,15 +3249,11 @@ extern "C" int rtmi_render_pixelwise_device(rtmi_scene *s, const rtmi_render_par
     const PixelwisePlanes out{d_linear, d_rgb8, d_stderr, d_spp, d_counts};
     if (int rc = pixelwise_check(name, s, p, cam, o, out, true, d_scratch, scratch_bytes)) return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = pixelwise_estimator(name, o, null_scene);
+    const Estimator m = estimator_of(name, o->estimator, o->env_select_p, null_scene.c_str());
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (int rc = radiance_attached(m, s)) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
-    BusyMark busy_mark{s, stream};
-    return pixelwise_enqueue(s, m, p, cam, o, stream, out, reinterpret_cast<char *>(d_scratch), nullptr, nullptr);
+    AsyncCall c;
+    if (int rc = c.begin(m, s, stream_)) return rc;
+    return pixelwise_enqueue(s, m, p, cam, o, c.stream, out, reinterpret_cast<char *>(d_scratch), nullptr, nullptr);
 }
 extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, const rtmi_pixelwise_opts *o,
                                      float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts,
@@ -3278,7 +3263,7 @@ extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, cons
     if ((rc = pixelwise_check(name, s, p, cam, o, PixelwisePlanes{out_linear, out_rgb8, out_stderr, out_spp, out_counts}, false, nullptr, 0)))
         return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
-    const Estimator m = pixelwise_estimator(name, o, null_scene);
+    const Estimator m = estimator_of(name, o->estimator, o->env_select_p, null_scene.c_str());
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
     hipStream_t stream = s->stream;
@@ -3321,7 +3306,7 @@ extern "C" int rtmi_probe_pixelwise_step(int device, uint32_t n_pixels, uint32_t
     if (!list || !samples || !state) return fail(RTMI_ERR_INVALID, nm + "NULL argument (list, samples or state)");
     if (n_pixels == 0u || capacity == 0u || pass == 0u) return fail(RTMI_ERR_INVALID, nm + "n_pixels, capacity and pass must be at least 1");
     if ((uint64_t)capacity * pass >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "capacity * pass must be below 2^31");
-    if (int rc = sparse_device(nm, device)) return rc;
+    if (int rc = use_device(nm, device)) return rc;
     // one allocation, every part rounded up to 16 bytes: state | samples | list | count | linear | stderr | spp | rgb8 | active
     const auto up16 = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
     const size_t n = n_pixels, bytes[9] = {72 * n, 12 * (size_t)capacity * pass, 4 * (size_t)capacity, 8, 12 * n, 12 * n, 4 * n, 3 * n, n};
@@ -3329,10 +3314,7 @@ extern "C" int rtmi_probe_pixelwise_step(int device, uint32_t n_pixels, uint32_t
                      spp, rgb8, active};
     size_t at[10] = {0};
     for (int i = 0; i < 9; i++) at[i + 1] = at[i] + up16(bytes[i]);
-    struct Mem {
-        char *base = nullptr;
-        ~Mem() { if (base) (void)hipFree(base); }
-    } mem;
+    DeviceMem mem;
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), at[9]));
     char *d[9];
     for (int i = 0; i < 9; i++) {
@@ -3649,7 +3631,7 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     if (!p_in || !cam || !opts) return fail(RTMI_ERR_INVALID, "NULL argument");
     const char *name = "rtmi_render_env";
     int rc;
-    if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in))) return rc;
+    if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in->flags))) return rc;
     rc = check_mode_params(p_in, RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK |
                                      RTMI_FLAG_PATH_SIG | light_coop_bits(p_in),
                            "environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD, UV_BOOK and PATH_SIG "
@@ -3705,7 +3687,7 @@ extern "C" int rtmi_render_adaptive_env(rtmi_scene *s, const rtmi_camera *cam, c
     if (!p_in || !a || !cam || !opts) return fail(RTMI_ERR_INVALID, "NULL argument");
     const char *name = "rtmi_render_adaptive_env";
     int rc;
-    if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in))) return rc;
+    if ((rc = check_params(p_in)) || (rc = refuse_sky(name, p_in->flags))) return rc;
     rc = check_mode_params(p_in, RTMI_ADAPTIVE_NEE_FLAGS | light_coop_bits(p_in),
                            "adaptive environment renders accept the flags FAST_CULL, SYNC, REF_TREE, FACE_FORWARD and UV_BOOK "
                            "only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)",
@@ -3727,14 +3709,12 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     const std::string nm = std::string(name) + ": ", null_scene = nm + "scene is NULL";
     int rc = check_params(p_in);
     if (rc) return rc;
-    if (o->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if ((rc = check_estimator(name, o->estimator))) return rc;
     if (o->min_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "min_depth must be at least 1");
     if (!std::isfinite(o->q_min) || !(o->q_min > 0.0f && o->q_min <= 1.0f)) return fail(RTMI_ERR_INVALID, nm + "q_min must be in (0, 1]");
     const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
     const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    const rtmi_env_render eo{1u, o->env_select_p}; // env_select_p is read, and checked, only where both are sampled
-    if (nee && env && (rc = check_env_opts(name, &eo))) return rc;
-    if (env && (rc = refuse_sky(name, p_in))) return rc;
+    if ((rc = check_estimator_opts(name, o->estimator, o->env_select_p, p_in->flags))) return rc;
     if (p_in->flags & RTMI_FLAG_PATH_SIG)
         return fail(RTMI_ERR_UNSUPPORTED, nm + "PATH_SIG is refused: a roulette path has no counterpart to compare a signature with");
     const std::string flags_msg = nm + "roulette renders accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD and UV_BOOK "
@@ -3747,8 +3727,7 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
     const rtmi_render_params &p = *p_in;
     const rtmi_adaptive fixed{p.ns, 1u, 0.0, 0.0}; // one step of ns samples
     if (!a) a = &fixed;
-    const Estimator m{name, nee, env, nee && env ? o->env_select_p : 1.0f, null_scene.c_str(),
-                      "no light table attached (rtmi_scene_attach_lights)"};
+    const Estimator m = estimator_of(name, o->estimator, o->env_select_p, null_scene.c_str());
     RenderCall c;
     if ((rc = begin_adaptive(c, m, s, cam, p, a)) ||
         (rc = plan_light_coop(c, s, p, RTMI_FLAG_ROULETTE_COOP, rtmi_roulette_coop_wps(nee, env))))
@@ -3860,8 +3839,7 @@ static size_t session_blob_bytes(const rtmi_session *ss) {
 }
 
 static Estimator session_estimator(const rtmi_session *ss, const char *name, const std::string &null_scene) {
-    return Estimator{name, ss->nee, ss->env, ss->nee && ss->env ? ss->o.env_select_p : 1.0f, null_scene.c_str(),
-                     "no light table attached (rtmi_scene_attach_lights)"};
+    return lit_estimator(name, ss->nee, ss->env, ss->nee && ss->env ? ss->o.env_select_p : 1.0f, null_scene.c_str());
 }
 
 // the refusals every call on an existing session starts with
@@ -3887,16 +3865,14 @@ extern "C" int rtmi_session_create(rtmi_scene *s, const rtmi_camera *cam, const 
     p.ns = 1u; // not read
     int rc = check_params(&p);
     if (rc) return rc;
-    if (o->estimator > RTMI_ROULETTE_ENV_NEE) return fail(RTMI_ERR_INVALID, nm + "estimator must be one of RTMI_ROULETTE_* (0..3)");
+    if ((rc = check_estimator(name, o->estimator))) return rc;
     if (o->rr > 1u) return fail(RTMI_ERR_INVALID, nm + "rr must be 0 or 1");
     if (o->rr && o->min_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "min_depth must be at least 1");
     if (o->rr && (!std::isfinite(o->q_min) || !(o->q_min > 0.0f && o->q_min <= 1.0f)))
         return fail(RTMI_ERR_INVALID, nm + "q_min must be in (0, 1]");
     const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
     const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    const rtmi_env_render eo{1u, o->env_select_p}; // env_select_p is read, and checked, only where both are sampled
-    if (nee && env && (rc = check_env_opts(name, &eo))) return rc;
-    if (env && (rc = refuse_sky(name, &p))) return rc;
+    if ((rc = check_estimator_opts(name, o->estimator, o->env_select_p, p.flags))) return rc;
     if (p.flags & RTMI_FLAG_PATH_SIG) return fail(RTMI_ERR_UNSUPPORTED, nm + "PATH_SIG is refused: a session keeps no path signatures");
     const std::string flags_msg = nm + "sessions accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK, LIGHT_COOP and "
                                        "ROULETTE_COOP only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)";
@@ -4321,8 +4297,7 @@ struct RtmiFrameHold {
     rtmi_scene *s = nullptr;
 };
 static Estimator frame_estimator(const RtmiFrameLit &m, const std::string &null_scene) {
-    return Estimator{m.name, m.nee, m.env, m.env ? m.env_select_p : 1.0f, null_scene.c_str(),
-                     "no light table attached (rtmi_scene_attach_lights)"};
+    return lit_estimator(m.name, m.nee, m.env, m.env ? m.env_select_p : 1.0f, null_scene.c_str());
 }
 int rtmi_frame_hold_begin(rtmi_scene *s, const RtmiFrameLit &m, RtmiFrameHold **hold) {
     *hold = nullptr;

@@ -6,8 +6,8 @@
 //
 // The path kernel is rtmi_radiance_kernel (rtmi_radiance.hip) with another take step: the same fragments rtmi_path_lane.inc,
 // rtmi_path_scan.inc, rtmi_path_traced.inc and rtmi_path_shade.inc, the same items (item k = i * spp + s is sample s of point
-// i and slot k of the per-sample buffer), the same two-level refill from the handle's chunk counter (gather_take is a copy of
-// radiance_take: moving it would touch rtmi_radiance.hip).  The take reads one point record (12 B, a 12-B normal for COSINE, a
+// i and slot k of the per-sample buffer), the same two-level refill from the handle's chunk counter (batch_take,
+// rtmi_batch.hpp).  The take reads one point record (12 B, a 12-B normal for COSINE, a
 // 4-B time when there is a time plane) instead of a 32-B ray, draws the direction from stream 5 and starts the path the
 // radiance query starts for that ray with stream_skip = 0.  Every segment runs under (P.t_min, FLT_MAX), so the radiance
 // kernel's per-lane first-segment interval is not carried.  Instantiated for FAST x NEE x ENV x SPHERE.
@@ -25,6 +25,7 @@
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
 #include "rtmi_light_launch.hpp"
+#include "rtmi_batch.hpp"
 #include "rtmi_gather_launch.hpp"
 
 int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
@@ -40,39 +41,6 @@ __device__ __forceinline__ void gather_direction(uint32_t k0, uint32_t k1, uint3
     else rtmi_gather_cosine(rtmi_u01(w0), rtmi_u01(w1), n, d);
 }
 
-struct GatherWork { // wave-uniform: the wavefront's chunk, items [next, end)
-    uint32_t next, end;
-};
-// radiance_take of rtmi_radiance.hip.  Persistent wavefront; all 64 lanes call this together.  Every lane with want = true
-// receives the next item of the current chunk or, when that is exhausted, of the next chunks of the counter.  Returns false
-// for lanes that wanted but found the counter past the last chunk: they are done for good.
-__device__ __forceinline__ bool gather_take(GatherWork &w, bool &queue_empty, bool want, const GatherBatch &B, uint32_t &item) {
-    bool got = false;
-    for (;;) {
-        const bool still = want && !got;
-        const unsigned long long m = __ballot(still);
-        if (m == 0ull) break;
-        if (w.next >= w.end) { // wave-uniform: chunk exhausted, take the next one
-            if (queue_empty) break;
-            uint32_t u = 0u;
-            if ((threadIdx.x & 63) == 0) u = atomicAdd(B.queue, 1u);
-            u = rfl(u);
-            if (u >= B.nchunks) { queue_empty = true; break; }
-            const uint32_t begin = u * B.chunk; // < total < 2^31
-            w.next = rfl(begin);
-            w.end = rfl(B.total - begin < B.chunk ? B.total : begin + B.chunk);
-            continue;
-        }
-        const uint32_t k = w.next + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        w.next = rfl(w.next + (uint32_t)__popcll(m));
-        if (still && k < w.end) {
-            item = k;
-            got = true;
-        }
-    }
-    return got;
-}
-
 template <bool FAST, bool NEE, bool ENV, bool SPHERE>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_gather_kernel(DevScene sc, DevParams P, GatherBatch B, DevLights nl,
                                                                            DevEnv ev) {
@@ -84,7 +52,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_gather_kernel(DevSc
     const int wave = threadIdx.x >> 6;
     uint32_t *stack = &lds_stack[wave][0][0][lane];
     unsigned long long sig = 0ull; // SIG = false: named by the fragments, never live
-    GatherWork w;
+    BatchWork w;
     w.next = 0u; w.end = 0u;
     bool queue_empty = false;
     const uint32_t k0 = P.key0, k1 = P.key1;
@@ -102,7 +70,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_gather_kernel(DevSc
             { // lanes whose path ended take the next (point, sample) item, or are done when there is none
                 const bool want = !have_hit && !done && !alive;
                 if (__ballot(want) != 0ull) {
-                    if (gather_take(w, queue_empty, want, B, oidx)) {
+                    if (batch_take(w, queue_empty, want, B.queue, B.chunk, B.total, B.nchunks, oidx)) {
                         const uint32_t i = oidx / B.spp, s = oidx - i * B.spp;
                         const float *pt = B.points + 3 * (size_t)i;
                         pa.ro = f3(pt[0], pt[1], pt[2]);
@@ -145,9 +113,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_gather_kernel(DevSc
     }
 }
 
-// One lane per point: the f64 sum of its spp samples in sample order and Welford's recurrence (the arithmetic of
-// rtmi_radiance_resolve_kernel), the COSINE factor pi, and for SPHERE with an sh output the projection on the nine
-// harmonics of every sample's direction, drawn again from its counter.  spp == 1: no estimate, +inf.
+// One lane per point: the f64 sum of its spp samples in sample order and Welford's recurrence (rtmi_batch_welford.inc), the
+// COSINE factor pi, and for SPHERE with an sh output the projection on the nine harmonics of every sample's direction, drawn
+// again from its counter: that branch spells the loop out, with the projection inside it.  spp == 1: no estimate, +inf.
 template <bool SPHERE>
 __global__ __launch_bounds__(256) void rtmi_gather_resolve_kernel(const Rad3 *__restrict__ samples, GatherBatch B, uint32_t k0,
                                                                  uint32_t k1) {
@@ -184,18 +152,8 @@ __global__ __launch_bounds__(256) void rtmi_gather_resolve_kernel(const Rad3 *__
 #pragma unroll
             for (int ch = 0; ch < 3; ch++) B.sh[27 * (size_t)i + 3 * q + ch] = (float)(c * acc[q][ch]);
     } else {
-        for (uint32_t s = 0; s < B.spp; s++) {
-            const Rad3 v = src[s];
-            const double k = (double)(s + 1u);
-            const double x[3] = {(double)v.r, (double)v.g, (double)v.b};
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                sum[ch] += x[ch];
-                const double dl = x[ch] - m[ch];
-                m[ch] = m[ch] + dl / k;
-                M2[ch] = M2[ch] + dl * (x[ch] - m[ch]);
-            }
-        }
+        const uint32_t ns = B.spp;
+#include "rtmi_batch_welford.inc"
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {

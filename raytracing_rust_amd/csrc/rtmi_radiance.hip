@@ -5,17 +5,12 @@
 // The path kernel is the per-lane two-phase kernel (rtmi_kernel_perlane.inc) with another take step: the fragments
 // rtmi_path_lane.inc, rtmi_path_scan.inc, rtmi_path_traced.inc and rtmi_path_shade.inc are included as they are, so a path
 // is traced, shaded and ended by the text the render kernels run; rtmi_path_take.inc, the one camera-specific step, is
-// replaced by radiance_take below.  Instantiated for FAST x NEE x ENV; no profiling, signature, features, roulette or
+// replaced by the batch modes' take (batch_take, rtmi_batch.hpp, which describes the items and the two-level refill) and
+// the start of a caller's ray.  Instantiated for FAST x NEE x ENV; no profiling, signature, features, roulette or
 // cooperative variant.
 //
-// Items.  Item k = i * spp + s (sample fastest) is sample s of ray i and slot k of the per-sample buffer, written by
-// path_end: the lanes of a wavefront start on the same or neighbouring rays and walk the same subtrees on the first
-// segment, and the resolve reads a ray's samples as one contiguous run.
-// Refill.  Two levels, as work_take: a wavefront owns a chunk of consecutive items and deals them to the lanes whose path
-// has ended with a ballot and mbcnt, no memory traffic; when the chunk is exhausted it takes the next one from a device
-// counter while its other lanes finish paths of the previous chunk, so a wavefront drains once, at the end of the launch.
-// The counter is a word of the handle, zeroed on the call's stream before the launch; calls on one handle serialise (the
-// busy event), so no two launches ever share it (DESIGN.md §24 has the reason for the counter over a grid stride).
+// Items.  Item k = i * spp + s (sample fastest) is sample s of ray i and slot k of the per-sample buffer.  The chunk
+// counter is a word of the handle.  The resolve's sample loop is rtmi_batch_welford.inc.
 // First segment.  A lane flag `first` selects the ray's own (t_min, t_max) for the scan; it is cleared after the lane's
 // first scan, before any shadow ray can be pending, and every later scan runs under (P.t_min, FLT_MAX).
 #include <hip/hip_runtime.h>
@@ -29,6 +24,7 @@
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
 #include "rtmi_light_launch.hpp"
+#include "rtmi_batch.hpp"
 #include "rtmi_radiance_launch.hpp"
 
 // the stream of rng_init(g, sample, pixel), read from word 4 * block + pos on (pos in 0..3; wave-uniform)
@@ -44,39 +40,6 @@ __device__ __forceinline__ void rng_seek(RngT &g, uint32_t k0, uint32_t k1, uint
     }
 }
 
-struct RadianceWork { // wave-uniform: the wavefront's chunk, items [next, end)
-    uint32_t next, end;
-};
-// Persistent wavefront; all 64 lanes call this together.  Every lane with want = true receives the next item of the
-// current chunk or, when that is exhausted, of the next chunks of the counter.  Returns false for lanes that wanted but
-// found the counter past the last chunk: they are done for good.
-__device__ __forceinline__ bool radiance_take(RadianceWork &w, bool &queue_empty, bool want, const RadianceBatch &B, uint32_t &item) {
-    bool got = false;
-    for (;;) {
-        const bool still = want && !got;
-        const unsigned long long m = __ballot(still);
-        if (m == 0ull) break;
-        if (w.next >= w.end) { // wave-uniform: chunk exhausted, take the next one
-            if (queue_empty) break;
-            uint32_t u = 0u;
-            if ((threadIdx.x & 63) == 0) u = atomicAdd(B.queue, 1u);
-            u = rfl(u);
-            if (u >= B.nchunks) { queue_empty = true; break; }
-            const uint32_t begin = u * B.chunk; // < total < 2^31
-            w.next = rfl(begin);
-            w.end = rfl(B.total - begin < B.chunk ? B.total : begin + B.chunk);
-            continue;
-        }
-        const uint32_t k = w.next + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        w.next = rfl(w.next + (uint32_t)__popcll(m));
-        if (still && k < w.end) {
-            item = k;
-            got = true;
-        }
-    }
-    return got;
-}
-
 template <bool FAST, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_radiance_kernel(DevScene sc, DevParams P, RadianceBatch B, DevLights nl,
                                                                              DevEnv ev) {
@@ -88,7 +51,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_radiance_kernel(Dev
     const int wave = threadIdx.x >> 6;
     uint32_t *stack = &lds_stack[wave][0][0][lane];
     unsigned long long sig = 0ull; // SIG = false: named by the fragments, never live
-    RadianceWork w;
+    BatchWork w;
     w.next = 0u; w.end = 0u;
     bool queue_empty = false;
     const uint32_t k0 = P.key0, k1 = P.key1;
@@ -108,7 +71,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_radiance_kernel(Dev
             { // lanes whose path ended take the next (ray, sample) item, or are done when there is none
                 const bool want = !have_hit && !done && !alive;
                 if (__ballot(want) != 0ull) {
-                    if (radiance_take(w, queue_empty, want, B, oidx)) {
+                    if (batch_take(w, queue_empty, want, B.queue, B.chunk, B.total, B.nchunks, oidx)) {
                         const uint32_t i = oidx / B.spp, s = oidx - i * B.spp;
                         const float4 r0 = B.rays[2 * (size_t)i], r1 = B.rays[2 * (size_t)i + 1];
                         pa.ro = f3(r0.x, r0.y, r0.z);
@@ -150,25 +113,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_radiance_kernel(Dev
     }
 }
 
-// One lane per ray: the f64 sum of its spp samples in sample order (the additions of rtmi_resolve_kernel) and Welford's
-// recurrence of rtmi_adaptive.h (the arithmetic of rtmi_adaptive_resolve_kernel); spp == 1: no estimate, +inf.
+// One lane per ray: the f64 sum of its spp samples in sample order and Welford's recurrence (rtmi_batch_welford.inc);
+// spp == 1: no estimate, +inf.
 __global__ __launch_bounds__(256) void rtmi_radiance_resolve_kernel(const Rad3 *__restrict__ samples, RadianceBatch B) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B.n) return;
     const Rad3 *src = samples + (size_t)i * B.spp;
     double sum[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0}, M2[3] = {0.0, 0.0, 0.0};
-    for (uint32_t s = 0; s < B.spp; s++) {
-        const Rad3 v = src[s];
-        const double k = (double)(s + 1u);
-        const double x[3] = {(double)v.r, (double)v.g, (double)v.b};
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            sum[ch] += x[ch];
-            const double d = x[ch] - m[ch];
-            m[ch] = m[ch] + d / k;
-            M2[ch] = M2[ch] + d * (x[ch] - m[ch]);
-        }
-    }
+    const uint32_t ns = B.spp;
+#include "rtmi_batch_welford.inc"
     const double n = (double)B.spp;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {

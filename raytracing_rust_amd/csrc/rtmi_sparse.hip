@@ -11,9 +11,9 @@
 // ENV; no profiling, signature, features, roulette or cooperative variant.
 //
 // Items.  Item k * ns + s (sample fastest) is sample s of entry k and slot k * ns + s of the per-sample buffer, written by
-// path_end; the resolve reads an entry's samples as one contiguous run.  Work distribution is the radiance query's: a
-// wavefront owns a chunk of consecutive items and deals them to its lanes by ballot and mbcnt, and takes the next chunk
-// from a device counter (a word of the caller's scratch, zeroed on the call's stream).
+// path_end; the resolve reads an entry's samples as one contiguous run (rtmi_batch_welford.inc).  Work distribution is the
+// batch modes' (batch_take, rtmi_batch.hpp); the chunk counter is a word of the caller's scratch, zeroed on the call's
+// stream, and the number of items and of chunks is derived here from the device-side count.
 // Count.  The number of entries is min(count[0], n), read here: the grid is sized for n, the host never learns the count,
 // and a wavefront that finds the counter past the last chunk leaves at once.
 #include <hip/hip_runtime.h>
@@ -27,6 +27,7 @@
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
 #include "rtmi_light_launch.hpp"
+#include "rtmi_batch.hpp"
 #include "rtmi_sparse_launch.hpp"
 
 // ---- select ----------------------------------------------------------------------------------------------------------------
@@ -118,37 +119,6 @@ __global__ __launch_bounds__(256) void rtmi_sparse_scan_kernel(uint32_t *__restr
 }
 
 // ---- the path kernel -------------------------------------------------------------------------------------------------------
-struct SparseWork { // wave-uniform: the wavefront's chunk, items [next, end)
-    uint32_t next, end;
-};
-// radiance_take of rtmi_radiance.hip over `total` items in `nchunks` chunks, both derived from the device-side count
-__device__ __forceinline__ bool sparse_take(SparseWork &w, bool &queue_empty, bool want, const SparseBatch &B, uint32_t total,
-                                            uint32_t nchunks, uint32_t &item) {
-    bool got = false;
-    for (;;) {
-        const bool still = want && !got;
-        const unsigned long long m = __ballot(still);
-        if (m == 0ull) break;
-        if (w.next >= w.end) { // wave-uniform: chunk exhausted, take the next one
-            if (queue_empty) break;
-            uint32_t u = 0u;
-            if ((threadIdx.x & 63) == 0) u = atomicAdd(B.queue, 1u);
-            u = rfl(u);
-            if (u >= nchunks) { queue_empty = true; break; }
-            const uint32_t begin = u * B.chunk; // < total < 2^31
-            w.next = rfl(begin);
-            w.end = rfl(total - begin < B.chunk ? total : begin + B.chunk);
-            continue;
-        }
-        const uint32_t k = w.next + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        w.next = rfl(w.next + (uint32_t)__popcll(m));
-        if (still && k < w.end) {
-            item = k;
-            got = true;
-        }
-    }
-    return got;
-}
 __device__ __forceinline__ uint32_t sparse_entries(const SparseBatch &B) { // wave-uniform
     uint32_t e = B.n;
     if (B.count) {
@@ -169,7 +139,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_sparse_kernel(DevSc
     const int wave = threadIdx.x >> 6;
     uint32_t *stack = &lds_stack[wave][0][0][lane];
     unsigned long long sig = 0ull; // SIG = false: named by the fragments, never live
-    SparseWork w;
+    BatchWork w;
     w.next = 0u; w.end = 0u;
     bool queue_empty = false;
     const uint32_t k0 = P.key0, k1 = P.key1;
@@ -189,7 +159,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_sparse_kernel(DevSc
             { // lanes whose path ended take the next (entry, sample) item, or are done when there is none
                 const bool want = !have_hit && !done && !alive;
                 if (__ballot(want) != 0ull) {
-                    if (sparse_take(w, queue_empty, want, B, total, nchunks, oidx)) {
+                    if (batch_take(w, queue_empty, want, B.queue, B.chunk, total, nchunks, oidx)) {
                         const uint32_t k = oidx / B.ns, s = oidx - k * B.ns;
                         // the list indexes the image's planes, row 0 the top row; the render counts its rows from the
                         // bottom (work_take: j = ny - 1 - row) and keys its streams by j * nx + px
@@ -224,25 +194,15 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_sparse_kernel(DevSc
     }
 }
 
-// One lane per entry: the f64 sum of its ns samples in sample order (the additions of rtmi_resolve_kernel) and Welford's
-// recurrence in the operation order of rtmi_adaptive_resolve_kernel, the render's; ns == 1: no estimate, +inf.
+// One lane per entry: the f64 sum of its ns samples in sample order and Welford's recurrence (rtmi_batch_welford.inc);
+// ns == 1: no estimate, +inf.
 __global__ __launch_bounds__(256) void rtmi_sparse_resolve_kernel(const Rad3 *__restrict__ samples, SparseBatch B) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= sparse_entries(B)) return;
     const Rad3 *src = samples + (size_t)i * B.ns;
     double sum[3] = {0.0, 0.0, 0.0}, m[3] = {0.0, 0.0, 0.0}, M2[3] = {0.0, 0.0, 0.0};
-    for (uint32_t s = 0; s < B.ns; s++) {
-        const Rad3 v = src[s];
-        const double k = (double)(s + 1u);
-        const double x[3] = {(double)v.r, (double)v.g, (double)v.b};
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            sum[ch] += x[ch];
-            const double d = x[ch] - m[ch];
-            m[ch] = m[ch] + d / k;
-            M2[ch] = M2[ch] + d * (x[ch] - m[ch]);
-        }
-    }
+    const uint32_t ns = B.ns;
+#include "rtmi_batch_welford.inc"
     const double n = (double)B.ns;
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) {

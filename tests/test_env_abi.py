@@ -197,10 +197,12 @@ def test_checks_come_before_device_work():
     assert "env_select_p" in body_of("static int check_env_opts(") and "hip" not in body_of("static int check_env_opts(")
     fixed = body_of("static int render_fixed(")
     assert "hip" not in fixed[:fixed.index("begin_call(")]
-    # begin_call holds the attach checks and the path's first device call
+    # begin_call makes the attach checks (check_attached, no device call in it) before the path's first device call
     begin = body_of("static int begin_call(")
+    assert begin.index("check_attached(") < begin.index("hipSetDevice")
+    attached = body_of("static int check_attached(")
     for check in ("!s->has_env", "!s->has_lights"):
-        assert begin.index(check) < begin.index("hipSetDevice"), check
+        assert check in attached and "hip" not in attached, check
     body = src[src.index('extern "C" int rtmi_scene_attach_env('):]
     assert body.index("rtmi_env_build_tables") < body.index("hipSetDevice")
     body = src[src.index('extern "C" int rtmi_probe_env('):]
