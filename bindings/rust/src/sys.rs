@@ -929,6 +929,73 @@ extern "C" {
     ) -> c_int;
 }
 
+// ---- include/rtmi_window.h: adaptive sampling per pixel with a neighbourhood stopping rule -----------------------------------
+
+pub const RTMI_WINDOW_MAX_RADIUS: u32 = 16;
+
+/// rtmi_window_opts: the steps, the estimator, the tolerances and the window radius of a windowed adaptive render (48 bytes,
+/// abs_tol at offset 16, radius at offset 36)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct RtmiWindowOpts {
+    pub min_spp: u32,
+    pub step_spp: u32,
+    pub estimator: u32,
+    pub pass_spp: u32,
+    pub abs_tol: f64,
+    pub rel_tol: f64,
+    pub env_select_p: f32,
+    pub radius: u32,
+    pub reserved: [u32; 2],
+}
+
+extern "C" {
+    /// the bytes of the device form's scratch; pure host code, a multiple of 16
+    pub fn rtmi_window_scratch_bytes(n_pixels: u64, pass_spp: u32, steps: u32) -> u64;
+    /// 1 + ceil((ns - min_spp) / step_spp), 0 for bad arguments; pure host code
+    pub fn rtmi_window_steps(ns: u32, min_spp: u32, step_spp: u32) -> u32;
+    /// asynchronous, device pointers, every step enqueued on `stream` (a hipStream_t); the planes are each optional, not all
+    /// NULL; d_counts 2 * steps words or NULL
+    pub fn rtmi_render_window_device(
+        scene: *mut RtmiScene,
+        params: *const RtmiRenderParams,
+        cam: *const RtmiCamera,
+        opts: *const RtmiWindowOpts,
+        d_linear: *mut c_void,
+        d_rgb8: *mut c_void,
+        d_stderr: *mut c_void,
+        d_spp: *mut c_void,
+        d_counts: *mut c_void,
+        d_scratch: *mut c_void,
+        scratch_bytes: u64,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// blocking, host planes, each optional, not all NULL; out_counts 2 * steps words or NULL
+    pub fn rtmi_render_window(
+        scene: *mut RtmiScene,
+        cam: *const RtmiCamera,
+        params: *const RtmiRenderParams,
+        opts: *const RtmiWindowOpts,
+        out_linear: *mut f32,
+        out_rgb8: *mut u8,
+        out_stderr: *mut f32,
+        out_spp: *mut u32,
+        out_counts: *mut u32,
+        stats: *mut RtmiStats,
+    ) -> c_int;
+    /// the rule once on device planes of nx * ny bytes, enqueued on `stream`: d_active in and out, d_fail read only
+    pub fn rtmi_window_spread_device(
+        d_active: *mut c_void,
+        d_fail: *const c_void,
+        nx: u32,
+        ny: u32,
+        radius: u32,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// the same on host arrays, blocking (tests)
+    pub fn rtmi_probe_window_spread(device: c_int, nx: u32, ny: u32, radius: u32, active: *mut u8, fail: *const u8) -> c_int;
+}
+
 // ---- include/rtmi_pixelwise.h: adaptive sampling per pixel, driven from the device -----------------------------------------
 
 pub const RTMI_PIXELWISE_MAX_STEPS: u32 = 1024;

@@ -10,7 +10,7 @@ The package holds only what the hot path needs:
 Importing the package does not need a GPU; rendering does, and fails loudly without one.
 """
 from . import abi, scenes  # noqa: F401
-from .host import Frame, Host, HostError, Panic, Unsupported, Scene, Temporal, Tonemap, default_params, denoise, env_from_sky, env_tables, gather_directions, irradiance_directions, pfm_bytes, ppm_p3, primary_rays, read_pfm, release_cached, sh_irradiance, sparse_patch, sparse_select, tonemap, upscale, Upscaler, write_ppm  # noqa: F401
+from .host import Frame, Host, HostError, Panic, Unsupported, Scene, Temporal, Tonemap, default_params, denoise, env_from_sky, env_tables, gather_directions, irradiance_directions, pfm_bytes, ppm_p3, primary_rays, read_pfm, release_cached, sh_irradiance, sparse_patch, sparse_select, tonemap, upscale, Upscaler, window_spread, write_ppm  # noqa: F401
 
 __all__ = ["Frame", "Host", "HostError", "Panic", "Unsupported", "Scene", "Temporal", "Tonemap", "Upscaler", "upscale", "default_params", "denoise", "env_from_sky", "env_tables", "gather_directions", "irradiance_directions", "pfm_bytes", "ppm_p3",
-           "primary_rays", "read_pfm", "release_cached", "sh_irradiance", "sparse_patch", "sparse_select", "tonemap", "write_ppm", "abi", "scenes"]
+           "primary_rays", "read_pfm", "release_cached", "sh_irradiance", "sparse_patch", "sparse_select", "tonemap", "window_spread", "write_ppm", "abi", "scenes"]

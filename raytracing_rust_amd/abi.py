@@ -423,6 +423,21 @@ class PixelwiseOpts(C.Structure):
 RTMI_PIXELWISE_SYMBOLS = ["rtmi_pixelwise_scratch_bytes", "rtmi_pixelwise_steps", "rtmi_probe_pixelwise_step", "rtmi_render_pixelwise",
                           "rtmi_render_pixelwise_device"]
 
+
+
+class WindowOpts(C.Structure):
+    """rtmi_window_opts (include/rtmi_window.h): the steps, estimator, tolerances and window radius of a windowed adaptive
+    render (48 bytes)."""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("estimator", C.c_uint32), ("pass_spp", C.c_uint32),
+                ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("env_select_p", C.c_float), ("radius", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+RTMI_WINDOW_MAX_RADIUS = 16
+# the functions of include/rtmi_window.h (windowed adaptive sampling), kept apart from those of the other headers
+RTMI_WINDOW_SYMBOLS = ["rtmi_probe_window_spread", "rtmi_render_window", "rtmi_render_window_device", "rtmi_window_scratch_bytes",
+                       "rtmi_window_spread_device", "rtmi_window_steps"]
+
 _rtmi = None
 _host = None
 
@@ -643,6 +658,20 @@ def load_rtmi():
     lib.rtmi_render_pixelwise.restype = C.c_int
     lib.rtmi_render_pixelwise.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 5 + [
         C.POINTER(Stats)]
+    lib.rtmi_window_scratch_bytes.restype = C.c_uint64
+    lib.rtmi_window_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.rtmi_window_steps.restype = C.c_uint32
+    lib.rtmi_window_steps.argtypes = [C.c_uint32] * 3
+    lib.rtmi_render_window_device.restype = C.c_int
+    lib.rtmi_render_window_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(Camera), C.POINTER(WindowOpts)] + [vp] * 6 + [
+        C.c_uint64, vp]
+    lib.rtmi_render_window.restype = C.c_int
+    lib.rtmi_render_window.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(WindowOpts)] + [vp] * 5 + [
+        C.POINTER(Stats)]
+    lib.rtmi_window_spread_device.restype = C.c_int
+    lib.rtmi_window_spread_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    lib.rtmi_probe_window_spread.restype = C.c_int
+    lib.rtmi_probe_window_spread.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
     lib.rtmi_probe_pixelwise_step.restype = C.c_int
     lib.rtmi_probe_pixelwise_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                               C.c_double, C.c_double, vp, vp, vp, vp, vp]
@@ -743,6 +772,8 @@ def load_host():
         "rth_sparse_refine": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(SparseParams), u32, u32, vp, vp, vp, vp, vp, u64, vp, i, vp]),
         "rth_render_pixelwise": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 5 + [C.POINTER(Stats)]),
         "rth_render_pixelwise_device": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 6 + [u64, vp]),
+        "rth_render_window": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(WindowOpts)] + [vp] * 5 + [C.POINTER(Stats)]),
+        "rth_render_window_device": (i, [vp, vp, C.POINTER(RenderParams), C.POINTER(WindowOpts)] + [vp] * 6 + [u64, vp]),
         "rth_gather": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]),
         "rth_gather_device": (i, [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]),
         "rth_render_device": (i, [vp, vp, C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]),

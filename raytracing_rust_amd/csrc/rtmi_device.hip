@@ -63,6 +63,8 @@
 #include "rtmi_sparse_launch.hpp"
 #include "rtmi_pixelwise.h"
 #include "rtmi_pixelwise_launch.hpp"
+#include "rtmi_window.h"
+#include "rtmi_window_launch.hpp"
 #include "rtmi_frame_launch.hpp"
 
 // ======================================================================================
@@ -3123,12 +3125,29 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
 }
 
 // ---- per-pixel adaptive sampling (include/rtmi_pixelwise.h) -----------------------------------------------------------------
-// the caller's scratch, in bytes from its start: control words | count slots | per-workgroup counts of the select |
-// active bytes | list | state | samples
-struct PixelwiseScratch {
-    uint64_t counts, block_counts, active, list, state, samples, total;
+// The options of both headers' entries (rtmi_pixelwise_opts, rtmi_window_opts of include/rtmi_window.h) in one form: the
+// checks and the loop below serve both.  windowed: the scratch ends with the fail plane, and the texts name that header.
+struct PixelwiseForm {
+    uint32_t min_spp, step_spp, estimator, pass_spp;
+    double abs_tol, rel_tol;
+    float env_select_p;
+    uint32_t radius; // 0: each pixel alone, the launch sequence of rtmi_pixelwise.h
+    bool reserved_set, windowed;
 };
-static PixelwiseScratch pixelwise_scratch(uint64_t n_pixels, uint32_t pass, uint32_t steps) {
+static PixelwiseForm pixelwise_form(const rtmi_pixelwise_opts *o) {
+    return PixelwiseForm{o->min_spp, o->step_spp, o->estimator, o->pass_spp, o->abs_tol, o->rel_tol, o->env_select_p, 0u,
+                         (o->reserved[0] | o->reserved[1] | o->reserved[2]) != 0u, false};
+}
+static PixelwiseForm pixelwise_form(const rtmi_window_opts *o) {
+    return PixelwiseForm{o->min_spp, o->step_spp, o->estimator, o->pass_spp, o->abs_tol, o->rel_tol, o->env_select_p, o->radius,
+                         (o->reserved[0] | o->reserved[1]) != 0u, true};
+}
+// the caller's scratch, in bytes from its start: control words | count slots | per-workgroup counts of the select |
+// active bytes | list | state | samples, and with `windowed` | fail bytes
+struct PixelwiseScratch {
+    uint64_t counts, block_counts, active, list, state, samples, fail, total;
+};
+static PixelwiseScratch pixelwise_scratch(uint64_t n_pixels, uint32_t pass, uint32_t steps, bool windowed = false) {
     const auto up16 = [](uint64_t b) { return (b + 15ull) & ~15ull; };
     PixelwiseScratch L;
     L.counts = 4ull * RTMI_SPARSE_HEAD_WORDS;
@@ -3137,7 +3156,8 @@ static PixelwiseScratch pixelwise_scratch(uint64_t n_pixels, uint32_t pass, uint
     L.list = L.active + up16(n_pixels);
     L.state = L.list + up16(4ull * n_pixels);
     L.samples = L.state + up16(72ull * n_pixels);
-    L.total = L.samples + up16(12ull * n_pixels * pass);
+    L.fail = L.samples + up16(12ull * n_pixels * pass);
+    L.total = windowed ? L.fail + up16(n_pixels) : L.fail;
     return L;
 }
 extern "C" uint64_t rtmi_pixelwise_scratch_bytes(uint64_t n_pixels, uint32_t pass_spp, uint32_t steps) {
@@ -3148,7 +3168,7 @@ extern "C" uint32_t rtmi_pixelwise_steps(uint32_t ns, uint32_t min_spp, uint32_t
     return 1u + (uint32_t)(((uint64_t)(ns - min_spp) + step_spp - 1ull) / step_spp);
 }
 // the most samples of one launch: a whole step (the first, or a later one, which the cap may shorten) or pass_spp
-static uint32_t pixelwise_pass(const rtmi_render_params *p, const rtmi_pixelwise_opts *o) {
+static uint32_t pixelwise_pass(const rtmi_render_params *p, const PixelwiseForm *o) {
     const uint32_t rest = p->ns - o->min_spp, later = o->step_spp < rest ? o->step_spp : rest;
     const uint32_t step = o->min_spp > later ? o->min_spp : later;
     return o->pass_spp == 0u || o->pass_spp > step ? step : o->pass_spp;
@@ -3160,7 +3180,7 @@ struct PixelwisePlanes {
     void *linear, *rgb8, *se, *spp, *counts;
 };
 static int pixelwise_check(const char *name, const rtmi_scene *s_in, const rtmi_render_params *p, const rtmi_camera *cam,
-                           const rtmi_pixelwise_opts *o, const PixelwisePlanes &out, bool device_form, const void *scratch,
+                           const PixelwiseForm *o, const PixelwisePlanes &out, bool device_form, const void *scratch,
                            uint64_t scratch_bytes) {
     const std::string nm = std::string(name) + ": ";
     if (!p || !cam || !o) return fail(RTMI_ERR_INVALID, nm + "NULL argument (params, cam or opts)");
@@ -3174,35 +3194,40 @@ static int pixelwise_check(const char *name, const rtmi_scene *s_in, const rtmi_
     if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
     if ((rc = check_attached_early(estimator_of(name, o->estimator, o->env_select_p, ""), s_in))) return rc;
     if (p->flags & ~RTMI_RADIANCE_FLAGS)
-        return fail(RTMI_ERR_UNSUPPORTED, nm + "per-pixel adaptive sampling accepts the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
+        return fail(RTMI_ERR_UNSUPPORTED, nm + (o->windowed ? "windowed" : "per-pixel") +
+                                              " adaptive sampling accepts the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     const rtmi_adaptive a{o->min_spp, o->step_spp, o->abs_tol, o->rel_tol};
     if ((rc = check_adaptive(p, &a))) return fail(rc, nm + g_err);
+    if (o->radius > RTMI_WINDOW_MAX_RADIUS) return fail(RTMI_ERR_INVALID, nm + "radius must not exceed RTMI_WINDOW_MAX_RADIUS (16)");
     const uint32_t pass = pixelwise_pass(p, o);
     if (npix * pass >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "nx * ny * (samples of a launch) must be below 2^31: lower pass_spp");
     const uint32_t steps = rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp);
     if (steps > RTMI_PIXELWISE_MAX_STEPS) return fail(RTMI_ERR_INVALID, nm + "more than 1024 steps");
     if (device_form) {
         if (!scratch) return fail(RTMI_ERR_INVALID, nm + "d_scratch is NULL");
-        if (scratch_bytes < pixelwise_scratch(npix, pass, steps).total)
-            return fail(RTMI_ERR_INVALID, nm + "scratch_bytes is below rtmi_pixelwise_scratch_bytes(nx * ny, pass, steps)");
+        if (scratch_bytes < pixelwise_scratch(npix, pass, steps, o->windowed).total)
+            return fail(RTMI_ERR_INVALID, nm + "scratch_bytes is below " + (o->windowed ? "rtmi_window" : "rtmi_pixelwise") +
+                                              "_scratch_bytes(nx * ny, pass, steps)");
         if (misaligned(out.linear, 4) || misaligned(out.se, 4) || misaligned(out.spp, 4) ||
             misaligned(out.counts, 4) || misaligned(scratch, 16))
             return fail(RTMI_ERR_INVALID, nm + "misaligned linear, stderr, spp, counts (4 bytes) or scratch (16 bytes)");
     }
-    if (o->reserved[0] || o->reserved[1] || o->reserved[2]) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
+    if (o->reserved_set) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
     return RTMI_OK;
 }
 // Every step on `stream`: select the active pixels into the list (counts to the step's slot), then per sub-pass the path
 // kernel over the list from sample n_done on and the step kernel; the last sub-pass of a step decides.  h_count (blocking
 // form): pinned, the step's count is read after its select and the loop ends at the first empty step; *paths: the paths traced.
+// With a radius (include/rtmi_window.h) the deciding launch writes the fail plane instead and one spread follows it: a pixel
+// stays active while a pixel of its window fails.
 static int pixelwise_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_params *p, const rtmi_camera *cam,
-                             const rtmi_pixelwise_opts *o, hipStream_t stream, const PixelwisePlanes &out, char *base,
+                             const PixelwiseForm *o, hipStream_t stream, const PixelwisePlanes &out, char *base,
                              uint32_t *h_count, uint64_t *paths) {
     const uint32_t npix = p->nx * p->ny, pass = pixelwise_pass(p, o), steps = rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp);
-    const PixelwiseScratch L = pixelwise_scratch(npix, pass, steps);
+    const PixelwiseScratch L = pixelwise_scratch(npix, pass, steps, o->windowed);
     uint32_t *head = reinterpret_cast<uint32_t *>(base), *slots = reinterpret_cast<uint32_t *>(base + L.counts);
     uint32_t *block_counts = reinterpret_cast<uint32_t *>(base + L.block_counts), *list = reinterpret_cast<uint32_t *>(base + L.list);
-    uint8_t *active = reinterpret_cast<uint8_t *>(base + L.active);
+    uint8_t *active = reinterpret_cast<uint8_t *>(base + L.active), *failing = reinterpret_cast<uint8_t *>(base + L.fail);
     HIP_TRY(hipMemsetAsync(active, 1, npix, stream));
     HIP_TRY(hipMemsetAsync(slots, 0, 8ull * steps, stream)); // a step that is never enqueued (blocking form) traced nothing
     rtmi_sparse_params sp{};
@@ -3211,7 +3236,7 @@ static int pixelwise_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_rende
     S.list = list;
     S.samples = reinterpret_cast<const Rad3 *>(base + L.samples);
     S.state = reinterpret_cast<double *>(base + L.state);
-    S.active = active;
+    S.active = o->radius ? failing : active; // step 0 traces every pixel: every fail byte is written before it is read
     S.linear = reinterpret_cast<float *>(out.linear); S.rgb8 = reinterpret_cast<uint8_t *>(out.rgb8);
     S.stderr_out = reinterpret_cast<float *>(out.se); S.spp = reinterpret_cast<uint32_t *>(out.spp);
     S.n_pixels = npix; S.capacity = npix; S.cap = p->ns;
@@ -3237,16 +3262,16 @@ static int pixelwise_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_rende
             S.n_done = sp.first_sample; S.pass = take; S.decide = done == cnt ? 1u : 0u;
             HIP_TRY(rtmi_pixelwise_launch_step(stream, S));
         }
+        if (o->radius) HIP_TRY(rtmi_window_launch_spread(stream, active, failing, p->nx, p->ny, o->radius));
         n_done += cnt;
     }
     if (out.counts) HIP_TRY(hipMemcpyAsync(out.counts, slots, 8ull * steps, h_count ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, stream));
     return RTMI_OK;
 }
-extern "C" int rtmi_render_pixelwise_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam,
-                                            const rtmi_pixelwise_opts *o, void *d_linear, void *d_rgb8, void *d_stderr, void *d_spp,
-                                            void *d_counts, void *d_scratch, uint64_t scratch_bytes, void *stream_) {
-    const char *name = "rtmi_render_pixelwise_device";
-    const PixelwisePlanes out{d_linear, d_rgb8, d_stderr, d_spp, d_counts};
+// the device form and the blocking form of both headers' render entries; o: NULL for NULL opts
+static int pixelwise_render_device(const char *name, rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam,
+                                   const PixelwiseForm *o, const PixelwisePlanes &out, void *d_scratch, uint64_t scratch_bytes,
+                                   void *stream_) {
     if (int rc = pixelwise_check(name, s, p, cam, o, out, true, d_scratch, scratch_bytes)) return rc;
     const std::string null_scene = std::string(name) + ": scene is NULL";
     const Estimator m = estimator_of(name, o->estimator, o->env_select_p, null_scene.c_str());
@@ -3255,10 +3280,9 @@ extern "C" int rtmi_render_pixelwise_device(rtmi_scene *s, const rtmi_render_par
     if (int rc = c.begin(m, s, stream_)) return rc;
     return pixelwise_enqueue(s, m, p, cam, o, c.stream, out, reinterpret_cast<char *>(d_scratch), nullptr, nullptr);
 }
-extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, const rtmi_pixelwise_opts *o,
-                                     float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts,
-                                     rtmi_stats *stats) {
-    const char *name = "rtmi_render_pixelwise";
+static int pixelwise_render_host(const char *name, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p,
+                                 const PixelwiseForm *o, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
+                                 uint32_t *out_counts, rtmi_stats *stats) {
     int rc;
     if ((rc = pixelwise_check(name, s, p, cam, o, PixelwisePlanes{out_linear, out_rgb8, out_stderr, out_spp, out_counts}, false, nullptr, 0)))
         return rc;
@@ -3270,7 +3294,7 @@ extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, cons
     // the handle's memory, grow-only: scratch | linear | stderr | spp | rgb8
     const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
     const size_t scratch_bytes =
-        (size_t)pixelwise_scratch(npix, pixelwise_pass(p, o), rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp)).total;
+        (size_t)pixelwise_scratch(npix, pixelwise_pass(p, o), rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp), o->windowed).total;
     if ((rc = grow(s, s->px_mem, s->px_mem_bytes, scratch_bytes + (12 + 12 + 4 + 3) * up))) return rc;
     if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
     char *d_linear = s->px_mem + scratch_bytes, *d_se = d_linear + 12 * up, *d_spp = d_se + 12 * up, *d_rgb8 = d_spp + 4 * up;
@@ -3297,6 +3321,20 @@ extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, cons
         stats->kernel = RTMI_KERNEL_PERLANE;
     }
     return RTMI_OK;
+}
+extern "C" int rtmi_render_pixelwise_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam,
+                                            const rtmi_pixelwise_opts *o, void *d_linear, void *d_rgb8, void *d_stderr, void *d_spp,
+                                            void *d_counts, void *d_scratch, uint64_t scratch_bytes, void *stream_) {
+    const PixelwiseForm f = o ? pixelwise_form(o) : PixelwiseForm{};
+    return pixelwise_render_device("rtmi_render_pixelwise_device", s, p, cam, o ? &f : nullptr,
+                                   PixelwisePlanes{d_linear, d_rgb8, d_stderr, d_spp, d_counts}, d_scratch, scratch_bytes, stream_);
+}
+extern "C" int rtmi_render_pixelwise(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, const rtmi_pixelwise_opts *o,
+                                     float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts,
+                                     rtmi_stats *stats) {
+    const PixelwiseForm f = o ? pixelwise_form(o) : PixelwiseForm{};
+    return pixelwise_render_host("rtmi_render_pixelwise", s, cam, p, o ? &f : nullptr, out_linear, out_rgb8, out_stderr, out_spp,
+                                 out_counts, stats);
 }
 extern "C" int rtmi_probe_pixelwise_step(int device, uint32_t n_pixels, uint32_t capacity, const uint32_t *list, const uint32_t *count,
                                          const float *samples, double *state, uint32_t n_done, uint32_t pass, uint32_t decide,
@@ -3332,6 +3370,59 @@ extern "C" int rtmi_probe_pixelwise_step(int device, uint32_t n_pixels, uint32_t
     HIP_TRY(hipDeviceSynchronize());
     for (int i = 0; i < 9; i++)
         if (host[i] && i != 1 && i != 2 && i != 3) HIP_TRY(hipMemcpy(host[i], d[i], bytes[i], hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+
+// ---- windowed adaptive sampling (include/rtmi_window.h) -------------------------------------------------------------------
+// The render entries are the per-pixel ones above with a radius: the same checks, the same loop, one spread launch per step.
+static_assert(RTMI_WINDOW_MAX_RADIUS == RTMI_WINDOW_RADIUS_MAX, "the spread kernel's LDS is sized by the header's maximum");
+static_assert(sizeof(rtmi_window_opts) == 48 && offsetof(rtmi_window_opts, radius) == 36, "rtmi_window_opts is 48 bytes");
+extern "C" uint64_t rtmi_window_scratch_bytes(uint64_t n_pixels, uint32_t pass_spp, uint32_t steps) {
+    return pixelwise_scratch(n_pixels, pass_spp, steps, true).total;
+}
+extern "C" uint32_t rtmi_window_steps(uint32_t ns, uint32_t min_spp, uint32_t step_spp) {
+    return rtmi_pixelwise_steps(ns, min_spp, step_spp);
+}
+extern "C" int rtmi_render_window_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_window_opts *o,
+                                         void *d_linear, void *d_rgb8, void *d_stderr, void *d_spp, void *d_counts, void *d_scratch,
+                                         uint64_t scratch_bytes, void *stream_) {
+    const PixelwiseForm f = o ? pixelwise_form(o) : PixelwiseForm{};
+    return pixelwise_render_device("rtmi_render_window_device", s, p, cam, o ? &f : nullptr,
+                                   PixelwisePlanes{d_linear, d_rgb8, d_stderr, d_spp, d_counts}, d_scratch, scratch_bytes, stream_);
+}
+extern "C" int rtmi_render_window(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, const rtmi_window_opts *o,
+                                  float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts,
+                                  rtmi_stats *stats) {
+    const PixelwiseForm f = o ? pixelwise_form(o) : PixelwiseForm{};
+    return pixelwise_render_host("rtmi_render_window", s, cam, p, o ? &f : nullptr, out_linear, out_rgb8, out_stderr, out_spp, out_counts,
+                                 stats);
+}
+static int window_spread_check(const std::string &nm, const void *active, const void *failing, uint32_t nx, uint32_t ny, uint32_t radius) {
+    if (!active || !failing) return fail(RTMI_ERR_INVALID, nm + "NULL argument (active or fail)");
+    const uint64_t npix = (uint64_t)nx * ny;
+    if (npix == 0u || npix > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "the image must have 1 .. 32768^2 pixels");
+    if (radius > RTMI_WINDOW_MAX_RADIUS) return fail(RTMI_ERR_INVALID, nm + "radius must not exceed RTMI_WINDOW_MAX_RADIUS (16)");
+    return RTMI_OK;
+}
+extern "C" int rtmi_window_spread_device(void *d_active, const void *d_fail, uint32_t nx, uint32_t ny, uint32_t radius, void *stream) {
+    if (int rc = window_spread_check("rtmi_window_spread_device: ", d_active, d_fail, nx, ny, radius)) return rc;
+    HIP_TRY(rtmi_window_launch_spread(reinterpret_cast<hipStream_t>(stream), reinterpret_cast<uint8_t *>(d_active),
+                                      reinterpret_cast<const uint8_t *>(d_fail), nx, ny, radius));
+    return RTMI_OK;
+}
+extern "C" int rtmi_probe_window_spread(int device, uint32_t nx, uint32_t ny, uint32_t radius, uint8_t *active, const uint8_t *failing) {
+    const std::string nm = "rtmi_probe_window_spread: ";
+    if (int rc = window_spread_check(nm, active, failing, nx, ny, radius)) return rc;
+    if (int rc = use_device(nm, device)) return rc;
+    const size_t n = (size_t)nx * ny, up = (n + 15u) & ~(size_t)15u;
+    DeviceMem mem;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), 2 * up));
+    uint8_t *d_active = reinterpret_cast<uint8_t *>(mem.base), *d_fail = d_active + up;
+    HIP_TRY(hipMemcpy(d_active, active, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_fail, failing, n, hipMemcpyHostToDevice));
+    HIP_TRY(rtmi_window_launch_spread(nullptr, d_active, d_fail, nx, ny, radius));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(active, d_active, n, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 

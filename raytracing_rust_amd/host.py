@@ -1062,6 +1062,80 @@ class Scene:
         res["samples"] = lambda: int((counts[:, 0].cpu().numpy().astype(np.uint64) * per_step[:steps]).sum())
         return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
 
+    def render_windowed(self, cam, nx, ny, ns, min_spp, step_spp, radius=1, abs_tol=0.0, rel_tol=0.0, estimator="plain", seed=0,
+                        pass_spp=0, out="numpy", env_select_p=0.5, **kw):
+        """Adaptive sampling per pixel with a neighbourhood stopping rule, driven from the device (include/rtmi_window.h):
+        render_pixelwise's lattice, samples and own-pixel test, but a pixel stays alive while any pixel within the Chebyshev
+        radius `radius` of it (the window clipped at the image border) still fails its test below the cap.  radius=0 is
+        render_pixelwise bit for bit; a larger radius only adds samples, at every pixel; radius >= max(nx, ny) - 1 stops every
+        pixel at the same count (radius is at most abi.RTMI_WINDOW_MAX_RADIUS).  A pixel with spp = n is bit for bit the
+        estimator's fixed render at ns = n, as in render_pixelwise.  No inclusion holds against render_adaptive's 8x8 tiles.
+        The other arguments, out="torch" and the returned dict are render_pixelwise's."""
+        if estimator not in abi.ROULETTE_ESTIMATORS:
+            raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
+        if out not in ("numpy", "torch"):
+            raise ValueError('out must be "numpy" or "torch"')
+        self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        p = default_params(nx, ny, ns, seed=seed, **kw)
+        o = abi.WindowOpts(int(min_spp), int(step_spp), abi.ROULETTE_ESTIMATORS[estimator], int(pass_spp), float(abs_tol),
+                           float(rel_tol), float(env_select_p), int(radius))
+        lib = abi.load_rtmi()
+        steps = int(lib.rtmi_window_steps(p.ns, o.min_spp, o.step_spp))
+        rows = max(steps, 1)  # refused arguments (0 steps) reach the native entry, which names what is wrong
+        per_step = np.array([o.min_spp] + [min(o.step_spp, p.ns - n) for n in range(o.min_spp, p.ns, max(o.step_spp, 1))], np.uint64)
+        if out == "numpy":
+            res, outs = _outputs(ny, nx, ("linear", "rgb8", "stderr", "spp"))
+            counts = np.zeros((rows, 2), np.uint32)
+            self.host._check(self.host.lib.rth_render_window(self.h, cam.h, C.byref(p), C.byref(o), *outs[:-1], counts.ctypes.data,
+                                                              outs[-1]))
+            st = res.pop("stats")
+            res["counts"] = counts[:steps]
+            res["samples"] = int(st.samples)
+            return res
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        step = max(o.min_spp, min(o.step_spp, max(p.ns - o.min_spp, 0)))
+        nbytes = int(lib.rtmi_window_scratch_bytes(nx * ny, step if o.pass_spp == 0 or o.pass_spp > step else o.pass_spp, steps))
+        res = {"linear": torch.empty((ny, nx, 3), dtype=torch.float32, device=dev), "rgb8": torch.empty((ny, nx, 3), dtype=torch.uint8, device=dev),
+               "stderr": torch.empty((ny, nx, 3), dtype=torch.float32, device=dev), "spp": torch.empty((ny, nx), dtype=torch.int32, device=dev),
+               "counts": torch.empty((rows, 2), dtype=torch.int32, device=dev)}
+        scratch = torch.empty(((nbytes + 15) // 16, 4), dtype=torch.int32, device=dev)
+        self.host._check(self.host.lib.rth_render_window_device(
+            self.h, cam.h, C.byref(p), C.byref(o), *[C.c_void_p(res[n].data_ptr()) for n in ("linear", "rgb8", "stderr", "spp", "counts")],
+            C.c_void_p(scratch.data_ptr()), C.c_uint64(nbytes), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        counts = res["counts"] = res["counts"][:steps]
+        res["samples"] = lambda: int((counts[:, 0].cpu().numpy().astype(np.uint64) * per_step[:steps]).sum())
+        return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
+
+
+def window_spread(active, fail, radius, device=0):
+    """The stopping rule of include/rtmi_window.h applied once: active'[p] = active[p] != 0 and some fail byte != 0 within the
+    Chebyshev radius of p, the window clipped at the border; bytes 1 or 0.  active, fail: uint8 [ny, nx], both numpy arrays
+    (a new array is returned; the kernel runs on `device`, blocking) or both torch tensors on one GPU (active is updated in
+    place on torch's current stream and returned; nothing is copied to the host)."""
+    lib = abi.load_rtmi()
+
+    def refuse(rc):
+        if rc:
+            raise ValueError((lib.rtmi_last_error() or b"window_spread failed").decode())
+
+    if isinstance(active, np.ndarray) or isinstance(fail, np.ndarray):
+        a, f = np.array(active, np.uint8, order="C", copy=True), np.ascontiguousarray(fail, np.uint8)
+        if a.ndim != 2 or a.shape != f.shape:
+            raise ValueError("active and fail must be uint8 arrays of one shape [ny, nx]")
+        refuse(lib.rtmi_probe_window_spread(int(device), a.shape[1], a.shape[0], int(radius), a.ctypes.data, f.ctypes.data))
+        return a
+    import torch
+
+    if not (active.is_cuda and fail.device == active.device and active.dtype == fail.dtype == torch.uint8 and active.dim() == 2
+            and active.shape == fail.shape and active.is_contiguous() and fail.is_contiguous()):
+        raise ValueError("active and fail must be contiguous uint8 tensors of one shape [ny, nx] on one GPU")
+    with torch.cuda.device(active.device):
+        refuse(lib.rtmi_window_spread_device(C.c_void_p(active.data_ptr()), C.c_void_p(fail.data_ptr()), active.shape[1], active.shape[0],
+                                             int(radius), C.c_void_p(torch.cuda.current_stream(active.device).cuda_stream)))
+    return active
+
 
 IRRADIANCE_STREAM = 5  # the Philox stream id of irradiance()'s directions (0 path, 2 scene, 3 light samples, 4 roulette)
 

@@ -18,6 +18,7 @@
 #include "rtmi_radiance.h"
 #include "rtmi_sparse.h"
 #include "rtmi_pixelwise.h"
+#include "rtmi_window.h"
 #include "rtmi_gather.h"
 #include "rtmi_frame.h"
 #include "rtmi_upscale.h"
@@ -415,6 +416,27 @@ RTH_API int rth_render_pixelwise_device(void *lowered, void *cam, const rtmi_ren
         const rtmi_camera c = CAM(cam).lower();
         return done(name, rtmi_render_pixelwise_device(dev, p, &c, o, d_linear, d_rgb8, d_stderr, d_spp, d_counts, d_scratch, scratch_bytes,
                                                        stream),
+                    CODED_UNSUPPORTED);
+    });
+}
+// windowed adaptive sampling (include/rtmi_window.h) on the uploaded handle, as the per-pixel entries above
+RTH_API int rth_render_window(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_window_opts *o, float *out_linear,
+                              uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, uint32_t *out_counts, rtmi_stats *stats) {
+    return guard([&] {
+        const char *name = "rtmi_render_window";
+        rtmi_scene *dev = DEV(lowered, name, "windowed");
+        const rtmi_camera c = CAM(cam).lower();
+        return done(name, rtmi_render_window(dev, &c, p, o, out_linear, out_rgb8, out_stderr, out_spp, out_counts, stats), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rth_render_window_device(void *lowered, void *cam, const rtmi_render_params *p, const rtmi_window_opts *o, void *d_linear,
+                                     void *d_rgb8, void *d_stderr, void *d_spp, void *d_counts, void *d_scratch, uint64_t scratch_bytes,
+                                     void *stream) {
+    return guard([&] {
+        const char *name = "rtmi_render_window_device";
+        rtmi_scene *dev = DEV(lowered, name, "windowed");
+        const rtmi_camera c = CAM(cam).lower();
+        return done(name, rtmi_render_window_device(dev, p, &c, o, d_linear, d_rgb8, d_stderr, d_spp, d_counts, d_scratch, scratch_bytes, stream),
                     CODED_UNSUPPORTED);
     });
 }
