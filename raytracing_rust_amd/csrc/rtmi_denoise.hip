@@ -16,8 +16,8 @@
 #include "rtmi_math.h"
 #include "rtmi_denoise.h"
 #include "rtmi_frame_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
+#include "rtmi_image_dev.hpp"
 
 namespace {
 
@@ -30,8 +30,6 @@ struct DenoiseIter {
     int normal_on;     // normal_power != 0
     float sigma_l, sigma_z, eps_l, eps_z;
 };
-
-__device__ __forceinline__ bool surface(float z) { return __builtin_isfinite(z); }
 
 __device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
@@ -182,8 +180,6 @@ __global__ void rtmi_expf_probe_kernel(const float *x, float *out, uint32_t n) {
     if (i < n) out[i] = rtmi_expf(x[i]);
 }
 
-bool finite_f(float v) { return v == v && v - v == 0.0f; }
-
 // the RTMI_ERR_INVALID checks, each message after `pre` (empty for rtmi_denoise, the entry's name for the frame handle)
 int check_ranges(const std::string &pre, uint32_t nx, uint32_t ny, const rtmi_denoise_params *p) {
     const auto bad = [&](const char *msg) { return rtmi_fail(RTMI_ERR_INVALID, (pre + msg).c_str()); };
@@ -205,41 +201,7 @@ int check_params(uint32_t nx, uint32_t ny, const rtmi_denoise_params *p) {
     return RTMI_OK;
 }
 
-int device_ok(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return rtmi_fail(RTMI_ERR_DEVICE, "no HIP device available");
-    if (device < 0 || device >= n) return rtmi_fail(RTMI_ERR_DEVICE, "device index out of range");
-    return RTMI_OK;
-}
-
-// device scratch of one call, one allocation carved in 256-B aligned pieces, freed by the destructor
-struct Scratch {
-    char *base = nullptr;
-    size_t used = 0;
-    ~Scratch() {
-        if (base) (void)hipFree(base);
-    }
-    static size_t round(size_t b) { return (b + 255) & ~(size_t)255; }
-    template <typename T>
-    T *take(size_t count) {
-        T *r = reinterpret_cast<T *>(base + used);
-        used += round(count * sizeof(T));
-        return r;
-    }
-};
-
-struct Stream {
-    hipStream_t s = nullptr;
-    ~Stream() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
-
-#define DN_TRY(expr)                                                                                                  \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return rtmi_fail(RTMI_ERR_DEVICE, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
+#define DN_TRY(expr) RTMI_HIP_TRY("", false, expr, #expr)
 
 } // namespace
 
@@ -248,41 +210,38 @@ int rtmi_denoise_check_ranges(const char *prefix, uint32_t nx, uint32_t ny, cons
     return check_ranges(prefix, nx, ny, p);
 }
 
-size_t rtmi_denoise_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t iterations) {
+void rtmi_denoise_layout(RtmiDenoisePlanes &W, Carve256 &c, uint32_t nx, uint32_t ny, uint32_t iterations) {
+    if (iterations == 0) return;
     const size_t n = (size_t)nx * ny;
-    return iterations > 0 ? 3 * Scratch::round(n * 16) + Scratch::round(n * 8) : 0;
+    W.state[0] = c.take<float4>(n);
+    W.state[1] = c.take<float4>(n);
+    W.guide = c.take<float4>(n);
+    W.grad = c.take<float2>(n);
 }
 
 hipError_t rtmi_denoise_launch(hipStream_t stream, uint32_t nx, uint32_t ny, const rtmi_denoise_params &p, const float *linear,
-                               const float *albedo, const float *normal, const float *depth, const float *se, void *scratch,
-                               float *out, uint8_t *rgb8) {
+                               const float *albedo, const float *normal, const float *depth, const float *se,
+                               const RtmiDenoisePlanes &W, float *out, uint8_t *rgb8) {
     const size_t n = (size_t)nx * ny;
     const bool lum = se != nullptr, filter = p.iterations > 0;
-    Scratch m;
-    m.base = static_cast<char *>(scratch);
-    float4 *st[2] = {filter ? m.take<float4>(n) : nullptr, filter ? m.take<float4>(n) : nullptr};
-    float4 *d_guide = filter ? m.take<float4>(n) : nullptr;
-    float2 *d_grad = filter ? m.take<float2>(n) : nullptr;
-    m.base = nullptr; // the caller's memory
     hipError_t e;
     int cur = 0;
     if (filter) {
         const dim3 block(kBlock, kBlock), grid((nx + kBlock - 1) / kBlock, (ny + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(rtmi_denoise_prepass_kernel, grid, block, 0, stream, linear, albedo, normal, depth, se, st[0],
-                           d_guide, d_grad, nx, ny, p.albedo_min);
+        hipLaunchKernelGGL(rtmi_denoise_prepass_kernel, grid, block, 0, stream, linear, albedo, normal, depth, se, W.state[0],
+                           W.guide, W.grad, nx, ny, p.albedo_min);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        DenoiseIter P{nx, ny, 1, 0, p.normal_power != 0u, p.sigma_l, p.sigma_z, p.eps_l, p.eps_z};
-        for (uint32_t pw = p.normal_power; pw > 1u; pw >>= 1) P.squarings++;
+        DenoiseIter P{nx, ny, 1, normal_squarings(p.normal_power), p.normal_power != 0u, p.sigma_l, p.sigma_z, p.eps_l, p.eps_z};
         for (uint32_t i = 0; i < p.iterations; i++, cur ^= 1) {
             P.step = 1 << i;
             if (lum)
-                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<true>, grid, block, 0, stream, st[cur], st[cur ^ 1], d_guide, d_grad, P);
+                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<true>, grid, block, 0, stream, W.state[cur], W.state[cur ^ 1], W.guide, W.grad, P);
             else
-                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<false>, grid, block, 0, stream, st[cur], st[cur ^ 1], d_guide, d_grad, P);
+                hipLaunchKernelGGL(rtmi_denoise_iter_kernel<false>, grid, block, 0, stream, W.state[cur], W.state[cur ^ 1], W.guide, W.grad, P);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }
-    hipLaunchKernelGGL(rtmi_denoise_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, st[cur], linear,
+    hipLaunchKernelGGL(rtmi_denoise_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W.state[cur], linear,
                        albedo, depth, out, rgb8, (uint32_t)n, p.albedo_min, filter ? 0 : 1);
     return hipGetLastError();
 }
@@ -294,25 +253,29 @@ extern "C" int rtmi_denoise(int device, uint32_t nx, uint32_t ny, const rtmi_den
     if (!p || !linear || !albedo || !normal || !depth) return rtmi_fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_params(nx, ny, p);
     if (rc) return rc;
-    rc = device_ok(device);
+    rc = device_ok("", device);
     if (rc) return rc;
     if (!out_linear && !out_rgb8) return RTMI_OK;
     DN_TRY(hipSetDevice(device));
     const size_t n = (size_t)nx * ny;
     const bool lum = stderr_rgb != nullptr, filter = p->iterations > 0;
-    Scratch m;
-    const size_t f3 = Scratch::round(n * 12), f1 = Scratch::round(n * 4), b3 = Scratch::round(n * 3);
-    const size_t work = rtmi_denoise_scratch_bytes(nx, ny, p->iterations);
-    const size_t bytes = 3 * f3 + f1 + (lum ? f3 : 0) + work + f3 + b3;
-    DN_TRY(hipMalloc(reinterpret_cast<void **>(&m.base), bytes));
-    float *d_lin = m.take<float>(n * 3), *d_alb = m.take<float>(n * 3), *d_nrm = m.take<float>(n * 3);
-    float *d_dep = m.take<float>(n);
-    float *d_se = lum ? m.take<float>(n * 3) : nullptr;
-    char *d_work = m.take<char>(work);
-    float *d_out = m.take<float>(n * 3);
-    uint8_t *d_rgb = m.take<uint8_t>(n * 3);
-    Stream S;
-    DN_TRY(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
+    float *d_lin, *d_alb, *d_nrm, *d_dep, *d_se = nullptr, *d_out;
+    uint8_t *d_rgb;
+    RtmiDenoisePlanes W;
+    const auto layout = [&](Carve256 &c) {
+        d_lin = c.take<float>(n * 3);
+        d_alb = c.take<float>(n * 3);
+        d_nrm = c.take<float>(n * 3);
+        d_dep = c.take<float>(n);
+        if (lum) d_se = c.take<float>(n * 3);
+        rtmi_denoise_layout(W, c, nx, ny, p->iterations);
+        d_out = c.take<float>(n * 3);
+        d_rgb = c.take<uint8_t>(n * 3);
+    };
+    DeviceArena mem;
+    DN_TRY(mem.alloc(layout));
+    DeviceStream S;
+    DN_TRY(S.create());
     DN_TRY(hipMemcpyAsync(d_lin, linear, n * 12, hipMemcpyHostToDevice, S.s));
     DN_TRY(hipMemcpyAsync(d_alb, albedo, n * 12, hipMemcpyHostToDevice, S.s));
     DN_TRY(hipMemcpyAsync(d_dep, depth, n * 4, hipMemcpyHostToDevice, S.s));
@@ -320,7 +283,7 @@ extern "C" int rtmi_denoise(int device, uint32_t nx, uint32_t ny, const rtmi_den
         DN_TRY(hipMemcpyAsync(d_nrm, normal, n * 12, hipMemcpyHostToDevice, S.s));
         if (lum) DN_TRY(hipMemcpyAsync(d_se, stderr_rgb, n * 12, hipMemcpyHostToDevice, S.s));
     }
-    DN_TRY(rtmi_denoise_launch(S.s, nx, ny, *p, d_lin, d_alb, d_nrm, d_dep, d_se, d_work, d_out, d_rgb));
+    DN_TRY(rtmi_denoise_launch(S.s, nx, ny, *p, d_lin, d_alb, d_nrm, d_dep, d_se, W, d_out, d_rgb));
     if (out_linear) DN_TRY(hipMemcpyAsync(out_linear, d_out, n * 12, hipMemcpyDeviceToHost, S.s));
     if (out_rgb8) DN_TRY(hipMemcpyAsync(out_rgb8, d_rgb, n * 3, hipMemcpyDeviceToHost, S.s));
     DN_TRY(hipStreamSynchronize(S.s));
@@ -329,13 +292,17 @@ extern "C" int rtmi_denoise(int device, uint32_t nx, uint32_t ny, const rtmi_den
 
 extern "C" int rtmi_probe_expf(int device, const float *x, float *out, uint32_t n) {
     if (n > 0 && (!x || !out)) return rtmi_fail(RTMI_ERR_INVALID, "NULL argument");
-    int rc = device_ok(device);
+    int rc = device_ok("", device);
     if (rc) return rc;
     if (n == 0) return RTMI_OK;
     DN_TRY(hipSetDevice(device));
-    Scratch m;
-    DN_TRY(hipMalloc(reinterpret_cast<void **>(&m.base), 2 * Scratch::round((size_t)n * 4)));
-    float *dx = m.take<float>(n), *dout = m.take<float>(n);
+    float *dx, *dout;
+    const auto layout = [&](Carve256 &c) {
+        dx = c.take<float>(n);
+        dout = c.take<float>(n);
+    };
+    DeviceArena mem;
+    DN_TRY(mem.alloc(layout));
     DN_TRY(hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(rtmi_expf_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx, dout, n);
     DN_TRY(hipGetLastError());

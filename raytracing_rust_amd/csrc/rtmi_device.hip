@@ -66,6 +66,7 @@
 #include "rtmi_window.h"
 #include "rtmi_window_launch.hpp"
 #include "rtmi_frame_launch.hpp"
+#include "rtmi_hostkit.hpp"
 
 // ======================================================================================
 // host side of the C ABI
@@ -75,12 +76,7 @@ static int fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
-#define HIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return fail(RTMI_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));                 \
-    } while (0)
+#define HIP_TRY(expr) RTMI_HIP_TRY("", false, expr, #expr)
 
 struct rtmi_scene {
     int device = 0;
@@ -181,7 +177,7 @@ struct rtmi_scene {
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
 // the message rtmi_last_error returns, set by the entry points of the other translation units (rtmi_denoise.hip)
-__attribute__((visibility("hidden"))) int rtmi_fail(int code, const char *msg) { return fail(code, msg); }
+RTMI_HIDDEN int rtmi_fail(int code, const char *msg) { return fail(code, msg); }
 
 #ifndef RTMI_BUILD_HASH
 #define RTMI_BUILD_HASH "unknown"
@@ -1648,33 +1644,35 @@ extern "C" int rtmi_write_ppm(const char *path, uint32_t nx, uint32_t ny, const 
 // ---- probes (parity tests call these through the C ABI) ------------------------------
 extern "C" int rtmi_probe_math(int op, const float *x, const float *y, float *out, uint32_t n) {
     if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dx), n * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dy), n * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dout), n * 4));
-    HIP_TRY(hipMemcpy(dx, x, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dy, y ? y : x, n * 4, hipMemcpyHostToDevice));
+    if (n == 0) return RTMI_OK;
+    float *dx, *dy, *dout;
+    const auto layout = [&](Carve256 &c) { dx = c.take<float>(n); dy = c.take<float>(n); dout = c.take<float>(n); };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc(layout));
+    HIP_TRY(hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dy, y ? y : x, (size_t)n * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(rtmi_math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, dx, dy, dout, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dout);
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 extern "C" int rtmi_probe_xform(const rtmi_xform *xforms, uint32_t count, const float *a, const float *b, float *out, uint32_t n) {
     if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
-    rtmi_xform *dx = nullptr;
-    float *da = nullptr, *db = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dx), (count ? count : 1) * sizeof(rtmi_xform)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&da), n * 12));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&db), n * 12));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dout), n * 13 * 4));
+    if (n == 0) return RTMI_OK;
+    rtmi_xform *dx;
+    float *da, *db, *dout;
+    const auto layout = [&](Carve256 &c) {
+        dx = c.take<rtmi_xform>(count ? count : 1); da = c.take<float>((size_t)n * 3); db = c.take<float>((size_t)n * 3);
+        dout = c.take<float>((size_t)n * 13);
+    };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc(layout));
     if (count) HIP_TRY(hipMemcpy(dx, xforms, count * sizeof(rtmi_xform), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(da, a, n * 12, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db, b, n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(da, a, (size_t)n * 12, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db, b, (size_t)n * 12, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(rtmi_xform_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx, (int)count, da, db, dout, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, n * 13 * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 13 * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 extern "C" int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b, const rtmi_prim_meta *meta, uint32_t n_prims,
@@ -1703,11 +1701,6 @@ extern "C" int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b,
                 return fail(RTMI_ERR_INVALID, "rtmi_probe_geom: PRIM cases must share one primitive per 64");
         }
     }
-    struct Bufs { // released on every path
-        float *rec = nullptr, *in = nullptr, *out = nullptr;
-        rtmi_xform *xf = nullptr;
-        ~Bufs() { (void)hipFree(rec); (void)hipFree(in); (void)hipFree(out); (void)hipFree(xf); }
-    } b;
     std::vector<float> lr((size_t)(n_prims ? n_prims : 1) * 20, 0.0f); // leaf records as rtmi_scene_create builds them
     for (uint32_t p = 0; p < n_prims; p++) {
         float *r = &lr[(size_t)p * 20];
@@ -1715,35 +1708,41 @@ extern "C" int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b,
         memcpy(r + 4, prim_b + (size_t)p * 4, 16);
         memcpy(r + 8, &meta[p], 16);
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.rec), lr.size() * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.xf), (n_xforms ? n_xforms : 1) * sizeof(rtmi_xform)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.in), (size_t)n * RTMI_PROBE_GEOM_IN * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.out), (size_t)n * RTMI_PROBE_GEOM_OUT * 4));
-    HIP_TRY(hipMemcpy(b.rec, lr.data(), lr.size() * 4, hipMemcpyHostToDevice));
-    if (n_xforms) HIP_TRY(hipMemcpy(b.xf, xforms, n_xforms * sizeof(rtmi_xform), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.in, in, (size_t)n * RTMI_PROBE_GEOM_IN * 4, hipMemcpyHostToDevice));
+    float *d_rec, *d_in, *d_out;
+    rtmi_xform *d_xf;
+    const auto layout = [&](Carve256 &c) {
+        d_rec = c.take<float>(lr.size()); d_xf = c.take<rtmi_xform>(n_xforms ? n_xforms : 1);
+        d_in = c.take<float>((size_t)n * RTMI_PROBE_GEOM_IN); d_out = c.take<float>((size_t)n * RTMI_PROBE_GEOM_OUT);
+    };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc(layout));
+    HIP_TRY(hipMemcpy(d_rec, lr.data(), lr.size() * 4, hipMemcpyHostToDevice));
+    if (n_xforms) HIP_TRY(hipMemcpy(d_xf, xforms, n_xforms * sizeof(rtmi_xform), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in, in, (size_t)n * RTMI_PROBE_GEOM_IN * 4, hipMemcpyHostToDevice));
     DevScene sc;
     memset(&sc, 0, sizeof(sc));
-    sc.leaf_rec = reinterpret_cast<const float4 *>(b.rec);
-    sc.xforms = b.xf;
+    sc.leaf_rec = reinterpret_cast<const float4 *>(d_rec);
+    sc.xforms = d_xf;
     sc.has_prim_xf = has_prim_xf;
-    hipLaunchKernelGGL(rtmi_geom_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, op, sc, b.in, b.out, n);
+    hipLaunchKernelGGL(rtmi_geom_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, op, sc, d_in, d_out, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, b.out, (size_t)n * RTMI_PROBE_GEOM_OUT * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * RTMI_PROBE_GEOM_OUT * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 extern "C" int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out, uint32_t n) {
     if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
-    uint32_t *dc = nullptr, *dk = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dc), n * 16));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dk), n * 8));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dout), n * 16));
-    HIP_TRY(hipMemcpy(dc, ctr, n * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dk, key, n * 8, hipMemcpyHostToDevice));
+    if (n == 0) return RTMI_OK;
+    uint32_t *dc, *dk, *dout;
+    const auto layout = [&](Carve256 &c) {
+        dc = c.take<uint32_t>((size_t)n * 4); dk = c.take<uint32_t>((size_t)n * 2); dout = c.take<uint32_t>((size_t)n * 4);
+    };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc(layout));
+    HIP_TRY(hipMemcpy(dc, ctr, (size_t)n * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dk, key, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(rtmi_philox_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dc, dk, dout, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, dout, n * 16, hipMemcpyDeviceToHost));
-    (void)hipFree(dc); (void)hipFree(dk); (void)hipFree(dout);
+    HIP_TRY(hipMemcpy(out, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 
@@ -1909,18 +1908,15 @@ extern "C" int rtmi_probe_math_f64(int op, const double *x, const double *y, dou
     if (!x || !out || ((op == 2 || op == 4) && !y)) return fail(RTMI_ERR_INVALID, "NULL argument");
     if (n == 0) return RTMI_OK;
     if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
+    double *dx, *dy, *dout;
     const size_t bytes = (size_t)n * sizeof(double);
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dx), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dy), bytes);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dout), bytes);
+    const auto layout = [&](Carve256 &c) { dx = c.take<double>(n); dy = c.take<double>(n); dout = c.take<double>(n); };
+    DeviceArena mem;
+    hipError_t e = mem.alloc(layout);
     if (e == hipSuccess) e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dy, y ? y : x, bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = rtmi_f64_launch_probe(op, dx, dy, dout, n);
     if (e == hipSuccess) e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost);
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    if (dout) (void)hipFree(dout);
     if (e != hipSuccess) return fail(RTMI_ERR_DEVICE, std::string("rtmi_probe_math_f64: ") + hipGetErrorString(e));
     return RTMI_OK;
 }
@@ -2888,17 +2884,9 @@ static SparseScratch sparse_scratch(uint64_t n_pixels, uint32_t capacity, uint32
 extern "C" uint64_t rtmi_sparse_scratch_bytes(uint64_t n_pixels, uint32_t capacity, uint32_t ns) {
     return sparse_scratch(n_pixels, capacity, ns).total;
 }
-// one device allocation of a call, freed on every return path
-struct DeviceMem {
-    char *base = nullptr;
-    ~DeviceMem() { if (base) (void)hipFree(base); }
-};
-static bool misaligned(const void *p, uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1u)) != 0u; }
 // the end of the stateless entries' checks (select, patch, the step probe): the device
 static int use_device(const std::string &nm, int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RTMI_ERR_DEVICE, nm + "no HIP device available");
-    if (device < 0 || device >= n) return fail(RTMI_ERR_DEVICE, nm + "device index out of range");
+    if (int rc = device_ok(nm, device)) return rc;
     HIP_TRY(hipSetDevice(device));
     return RTMI_OK;
 }
@@ -3097,12 +3085,14 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
     if ((rc = begin_call(c, m, s))) return rc;
     hipStream_t stream = s->stream;
     // one allocation per call: bytes | scratch | linear | stderr | rgb8
-    const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
-    const size_t scratch_bytes = (size_t)sparse_scratch(npix, sp->n, sp->ns).total;
-    DeviceMem mem;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), up + scratch_bytes + 12 * up + 12 * up + 3 * up));
-    char *d_bytes = mem.base, *d_scratch = d_bytes + up, *d_linear = d_scratch + scratch_bytes, *d_se = d_linear + 12 * up,
-         *d_rgb8 = d_se + 12 * up;
+    const size_t npix = (size_t)p->nx * p->ny;
+    char *d_bytes, *d_scratch, *d_linear, *d_se, *d_rgb8;
+    const auto layout = [&](Carve16 &c) {
+        d_bytes = c.take<char>(npix); d_scratch = c.take<char>((size_t)sparse_scratch(npix, sp->n, sp->ns).total);
+        d_linear = c.take<char>(npix * 12); d_se = c.take<char>(npix * 12); d_rgb8 = c.take<char>(npix * 3);
+    };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc<16>(layout));
     HIP_TRY(hipMemcpyAsync(d_bytes, bytes, npix, hipMemcpyHostToDevice, stream));
     if (linear) HIP_TRY(hipMemcpyAsync(d_linear, linear, npix * 12, hipMemcpyHostToDevice, stream));
     if (stderr_rgb) HIP_TRY(hipMemcpyAsync(d_se, stderr_rgb, npix * 12, hipMemcpyHostToDevice, stream));
@@ -3346,18 +3336,18 @@ extern "C" int rtmi_probe_pixelwise_step(int device, uint32_t n_pixels, uint32_t
     if ((uint64_t)capacity * pass >= (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "capacity * pass must be below 2^31");
     if (int rc = use_device(nm, device)) return rc;
     // one allocation, every part rounded up to 16 bytes: state | samples | list | count | linear | stderr | spp | rgb8 | active
-    const auto up16 = [](size_t b) { return (b + 15u) & ~(size_t)15u; };
     const size_t n = n_pixels, bytes[9] = {72 * n, 12 * (size_t)capacity * pass, 4 * (size_t)capacity, 8, 12 * n, 12 * n, 4 * n, 3 * n, n};
     void *host[9] = {state, const_cast<float *>(samples), const_cast<uint32_t *>(list), const_cast<uint32_t *>(count), linear, stderr_rgb,
                      spp, rgb8, active};
-    size_t at[10] = {0};
-    for (int i = 0; i < 9; i++) at[i + 1] = at[i] + up16(bytes[i]);
-    DeviceMem mem;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), at[9]));
     char *d[9];
+    const auto layout = [&](Carve16 &c) { for (int i = 0; i < 9; i++) d[i] = c.take<char>(bytes[i]); };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc<16>(layout));
     for (int i = 0; i < 9; i++) {
-        d[i] = host[i] ? mem.base + at[i] : nullptr;
-        if (host[i]) HIP_TRY(hipMemcpy(d[i], host[i], bytes[i], hipMemcpyHostToDevice));
+        if (!host[i])
+            d[i] = nullptr; // the kernel skips a plane that is not asked for
+        else
+            HIP_TRY(hipMemcpy(d[i], host[i], bytes[i], hipMemcpyHostToDevice));
     }
     PixelwiseStep S{};
     S.state = reinterpret_cast<double *>(d[0]); S.samples = reinterpret_cast<const Rad3 *>(d[1]);
@@ -3414,10 +3404,11 @@ extern "C" int rtmi_probe_window_spread(int device, uint32_t nx, uint32_t ny, ui
     const std::string nm = "rtmi_probe_window_spread: ";
     if (int rc = window_spread_check(nm, active, failing, nx, ny, radius)) return rc;
     if (int rc = use_device(nm, device)) return rc;
-    const size_t n = (size_t)nx * ny, up = (n + 15u) & ~(size_t)15u;
-    DeviceMem mem;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&mem.base), 2 * up));
-    uint8_t *d_active = reinterpret_cast<uint8_t *>(mem.base), *d_fail = d_active + up;
+    const size_t n = (size_t)nx * ny;
+    uint8_t *d_active, *d_fail;
+    const auto layout = [&](Carve16 &c) { d_active = c.take<uint8_t>(n); d_fail = c.take<uint8_t>(n); };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc<16>(layout));
     HIP_TRY(hipMemcpy(d_active, active, n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_fail, failing, n, hipMemcpyHostToDevice));
     HIP_TRY(rtmi_window_launch_spread(nullptr, d_active, d_fail, nx, ny, radius));

@@ -23,8 +23,7 @@
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
 #include "rtmi_light_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
 
 template <bool FAST, bool SIG, bool NEE>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_env_kernel(DevScene sc, DevCamera cam, DevParams P, DevLights nl,

@@ -13,8 +13,7 @@
 #include "rtmi_frame.h"
 #include "rtmi_light_coop.h"
 #include "rtmi_frame_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
 
 namespace {
 
@@ -56,25 +55,15 @@ hipError_t launch_untile(hipStream_t stream, uint32_t nx, uint32_t ny, const rtm
     return hipGetLastError();
 }
 
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 const uint32_t kFeatureFlags = RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD |
                                RTMI_FLAG_UV_BOOK;               // what both renders accept
 const uint32_t kCoopFlags = RTMI_FLAG_LIGHT_COOP | (1u << 11); // the lit render's own (bit 11: its small-pool test knob)
 
-int fail(int code, const std::string &name, const char *msg) { return rtmi_fail(code, (name + ": " + msg).c_str()); }
-
-#define FR_TRY(name, expr)                                                                                             \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-            return rtmi_fail(e_ == hipErrorOutOfMemory ? RTMI_ERR_NOMEM : RTMI_ERR_DEVICE,                             \
-                             (std::string(name) + ": " #expr ": " + hipGetErrorString(e_)).c_str());                   \
-    } while (0)
+#define FR_TRY(name, expr) RTMI_HIP_TRY(std::string(name) + ": ", true, expr, #expr)
 
 } // namespace
 
-struct rtmi_frame {
+struct RTMI_HIDDEN rtmi_frame {
     rtmi_scene *s = nullptr;
     rtmi_render_params p{}; // ns and seed are set per call
     rtmi_frame_opts o{};
@@ -82,12 +71,12 @@ struct rtmi_frame {
     bool temporal = true;
     rtmi_denoise_params filter{}; // o.denoise, with 0 iterations under RTMI_FRAME_NO_FILTER
     int device = 0;
-    char *base = nullptr; // one allocation, carved in 256-B aligned pieces
+    DeviceArena mem; // one allocation, carved in 256-B aligned pieces
     RtmiTemporalHistory hist;
     float *noisy_lin = nullptr, *noisy_se = nullptr;
     float *acc_lin = nullptr, *acc_se = nullptr, *acc_hist = nullptr;
     float2 *acc_motion = nullptr;
-    char *scratch = nullptr; // the filter's state, guide and gradient planes
+    RtmiDenoisePlanes work; // the filter's state, guide and gradient planes
     float *out_lin = nullptr;
     uint8_t *out_rgb = nullptr;
     unsigned int *poisoned = nullptr;   // the un-tiling's count of poisoned texels
@@ -96,30 +85,22 @@ struct rtmi_frame {
 
 static int frame_alloc(rtmi_frame *f, const char *name) {
     const size_t n = (size_t)f->p.nx * f->p.ny;
-    const size_t f3 = round256(n * 12), f2 = round256(n * 8), f1 = round256(n * 4), b3 = round256(n * 3);
-    const size_t hist = f->temporal ? rtmi_temporal_history_bytes(f->p.nx, f->p.ny) : 0;
-    const size_t work = round256(rtmi_denoise_scratch_bytes(f->p.nx, f->p.ny, f->filter.iterations));
-    const size_t bytes = hist + 2 * f3 + (f->temporal ? 2 * f3 + f1 + f2 : 0) + work + f3 + b3 + 256;
-    FR_TRY(name, hipMalloc(reinterpret_cast<void **>(&f->base), bytes));
-    char *at = f->base;
-    const auto take = [&](size_t b) {
-        char *r = at;
-        at += b;
-        return r;
+    const auto layout = [&](Carve256 &c) {
+        if (f->temporal) rtmi_temporal_history_layout(f->hist, c, f->p.nx, f->p.ny);
+        f->noisy_lin = c.take<float>(n * 3);
+        f->noisy_se = c.take<float>(n * 3);
+        if (f->temporal) {
+            f->acc_lin = c.take<float>(n * 3);
+            f->acc_se = c.take<float>(n * 3);
+            f->acc_hist = c.take<float>(n);
+            f->acc_motion = c.take<float2>(n);
+        }
+        rtmi_denoise_layout(f->work, c, f->p.nx, f->p.ny, f->filter.iterations);
+        f->out_lin = c.take<float>(n * 3);
+        f->out_rgb = c.take<uint8_t>(n * 3);
+        f->poisoned = c.take<unsigned int>(1);
     };
-    if (f->temporal) rtmi_temporal_history_carve(f->hist, take(hist), f->p.nx, f->p.ny);
-    f->noisy_lin = reinterpret_cast<float *>(take(f3));
-    f->noisy_se = reinterpret_cast<float *>(take(f3));
-    if (f->temporal) {
-        f->acc_lin = reinterpret_cast<float *>(take(f3));
-        f->acc_se = reinterpret_cast<float *>(take(f3));
-        f->acc_hist = reinterpret_cast<float *>(take(f1));
-        f->acc_motion = reinterpret_cast<float2 *>(take(f2));
-    }
-    f->scratch = take(work);
-    f->out_lin = reinterpret_cast<float *>(take(f3));
-    f->out_rgb = reinterpret_cast<uint8_t *>(take(b3));
-    f->poisoned = reinterpret_cast<unsigned int *>(take(256));
+    FR_TRY(name, f->mem.alloc(layout));
     FR_TRY(name, hipHostMalloc(reinterpret_cast<void **>(&f->h_poisoned), 64, hipHostMallocDefault));
     return RTMI_OK;
 }
@@ -129,7 +110,7 @@ extern "C" void rtmi_frame_destroy(rtmi_frame *f) {
     RtmiFrameHold *hold = nullptr; // the scene's lock and its running work, as rtmi_session_destroy
     const RtmiFrameLit plain{"rtmi_frame_destroy", false, false, 1.0f};
     (void)rtmi_frame_hold_begin(f->s, plain, &hold);
-    if (f->base) (void)hipFree(f->base);
+    f->mem.release();
     if (f->h_poisoned) (void)hipHostFree(f->h_poisoned);
     rtmi_frame_hold_end(hold);
     delete f;
@@ -214,7 +195,7 @@ static int frame_chain(rtmi_frame *f, const char *name, const RtmiFramePlanes &R
         lin = f->acc_lin;
         se = f->acc_se;
     }
-    FR_TRY(name, rtmi_denoise_launch(st, nx, ny, f->filter, lin, R.albedo, R.normal, R.depth, se, f->scratch, f->out_lin, f->out_rgb));
+    FR_TRY(name, rtmi_denoise_launch(st, nx, ny, f->filter, lin, R.albedo, R.normal, R.depth, se, f->work, f->out_lin, f->out_rgb));
     const auto copy = [&](void *dst, const void *src, size_t bytes) {
         return dst ? hipMemcpyAsync(dst, src, bytes, kind, st) : hipSuccess;
     };
@@ -285,34 +266,29 @@ extern "C" int rtmi_probe_frame_untile(int device, uint32_t nx, uint32_t ny, con
     if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u) return fail(RTMI_ERR_INVALID, name, "nx and ny must be in [1, 32768]");
     if (!tiled) return fail(RTMI_ERR_INVALID, name, "NULL argument");
     if (out_stderr && !tiled_stderr) return fail(RTMI_ERR_INVALID, name, "out_stderr needs tiled_stderr");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RTMI_ERR_DEVICE, name, "no HIP device available");
-    if (device < 0 || device >= count) return fail(RTMI_ERR_DEVICE, name, "device index out of range");
+    if (int rc = device_ok(std::string(name) + ": ", device)) return rc;
     FR_TRY(name, hipSetDevice(device));
     const size_t n = (size_t)nx * ny, ntex = (size_t)((nx + 7u) / 8u) * ((ny + 7u) / 8u) * 64;
-    const size_t t4 = round256(ntex * 16), t3 = round256(ntex * 12), f3 = round256(n * 12);
-    char *base = nullptr;
-    FR_TRY(name, hipMalloc(reinterpret_cast<void **>(&base), t4 + t3 + 2 * f3 + 256));
-    rtmi_texel *d_tex = reinterpret_cast<rtmi_texel *>(base);
-    float *d_se = reinterpret_cast<float *>(base + t4), *d_lin = reinterpret_cast<float *>(base + t4 + t3);
-    float *d_ose = reinterpret_cast<float *>(base + t4 + t3 + f3);
-    unsigned int *d_poison = reinterpret_cast<unsigned int *>(base + t4 + t3 + 2 * f3);
-    unsigned int h_poison = 0;
-    const auto run = [&]() -> hipError_t {
-        hipError_t e;
-        if ((e = hipMemcpy(d_tex, tiled, ntex * 16, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if (tiled_stderr && (e = hipMemcpy(d_se, tiled_stderr, ntex * 12, hipMemcpyHostToDevice)) != hipSuccess) return e;
-        if ((e = hipMemset(d_poison, 0, sizeof(unsigned int))) != hipSuccess) return e;
-        if ((e = launch_untile(nullptr, nx, ny, d_tex, tiled_stderr ? d_se : nullptr, out_linear ? d_lin : nullptr,
-                               out_stderr ? d_ose : nullptr, d_poison)) != hipSuccess)
-            return e;
-        if (out_linear && (e = hipMemcpy(out_linear, d_lin, n * 12, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-        if (out_stderr && (e = hipMemcpy(out_stderr, d_ose, n * 12, hipMemcpyDeviceToHost)) != hipSuccess) return e;
-        return hipMemcpy(&h_poison, d_poison, sizeof(unsigned int), hipMemcpyDeviceToHost);
+    rtmi_texel *d_tex;
+    float *d_se, *d_lin, *d_ose;
+    unsigned int *d_poison, h_poison = 0;
+    const auto layout = [&](Carve256 &c) {
+        d_tex = c.take<rtmi_texel>(ntex);
+        d_se = c.take<float>(ntex * 3);
+        d_lin = c.take<float>(n * 3);
+        d_ose = c.take<float>(n * 3);
+        d_poison = c.take<unsigned int>(1);
     };
-    const hipError_t e = run();
-    (void)hipFree(base);
-    FR_TRY(name, e);
+    DeviceArena mem;
+    FR_TRY(name, mem.alloc(layout));
+    FR_TRY(name, hipMemcpy(d_tex, tiled, ntex * 16, hipMemcpyHostToDevice));
+    if (tiled_stderr) FR_TRY(name, hipMemcpy(d_se, tiled_stderr, ntex * 12, hipMemcpyHostToDevice));
+    FR_TRY(name, hipMemset(d_poison, 0, sizeof(unsigned int)));
+    FR_TRY(name, launch_untile(nullptr, nx, ny, d_tex, tiled_stderr ? d_se : nullptr, out_linear ? d_lin : nullptr,
+                               out_stderr ? d_ose : nullptr, d_poison));
+    if (out_linear) FR_TRY(name, hipMemcpy(out_linear, d_lin, n * 12, hipMemcpyDeviceToHost));
+    if (out_stderr) FR_TRY(name, hipMemcpy(out_stderr, d_ose, n * 12, hipMemcpyDeviceToHost));
+    FR_TRY(name, hipMemcpy(&h_poison, d_poison, sizeof(unsigned int), hipMemcpyDeviceToHost));
     if (poisoned) *poisoned = h_poison;
     return RTMI_OK;
 }

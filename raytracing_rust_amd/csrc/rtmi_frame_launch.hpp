@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "rtmi.h"
+#include "rtmi_carve.hpp"
 #include "rtmi_denoise.h"
 #include "rtmi_temporal.h"
 
@@ -54,8 +55,8 @@ struct RtmiTemporalHistory {
     rtmi_camera prev_cam{};
     float prev_m[9] = {};
 };
-RTMI_SEAM size_t rtmi_temporal_history_bytes(uint32_t nx, uint32_t ny);
-RTMI_SEAM void rtmi_temporal_history_carve(RtmiTemporalHistory &H, char *base, uint32_t nx, uint32_t ny);
+// the six planes of H as pieces of its owner's allocation, in the order col, geo, var of copy 0, then of copy 1
+RTMI_SEAM void rtmi_temporal_history_layout(RtmiTemporalHistory &H, Carve256 &c, uint32_t nx, uint32_t ny);
 // the RTMI_ERR_INVALID checks of rtmi_temporal_create (sizes, ranges, reserved words) in `name`'s words; the flags are the
 // caller's to check
 RTMI_SEAM int rtmi_temporal_check_ranges(const char *name, uint32_t nx, uint32_t ny, const rtmi_temporal_params *p);
@@ -73,10 +74,15 @@ RTMI_SEAM void rtmi_temporal_history_advance(RtmiTemporalHistory &H, const rtmi_
 // ---- rtmi_denoise.hip: prepass, iterations and finish on device planes ----------------------------------------------
 // the RTMI_ERR_INVALID checks of rtmi_denoise (sizes and ranges), each message after `prefix`; the flags are the caller's
 RTMI_SEAM int rtmi_denoise_check_ranges(const char *prefix, uint32_t nx, uint32_t ny, const rtmi_denoise_params *p);
-// the state, guide and gradient planes of a filter with `iterations` iterations (none for 0), in bytes
-RTMI_SEAM size_t rtmi_denoise_scratch_bytes(uint32_t nx, uint32_t ny, uint32_t iterations);
-// The launches of rtmi_denoise on `stream`: inputs, scratch and outputs on the stream's device; se may be NULL (no
+// the filter's working planes: the two states the iterations ping-pong between, the guide and the depth gradient
+struct RtmiDenoisePlanes {
+    float4 *state[2] = {}, *guide = nullptr;
+    float2 *grad = nullptr;
+};
+// W as pieces of its owner's allocation; a filter with 0 iterations takes none and leaves W's pointers NULL
+RTMI_SEAM void rtmi_denoise_layout(RtmiDenoisePlanes &W, Carve256 &c, uint32_t nx, uint32_t ny, uint32_t iterations);
+// The launches of rtmi_denoise on `stream`: inputs, working planes and outputs on the stream's device; se may be NULL (no
 // luminance weight), normal is read by the filter only.  out: [ny][nx][3] floats, rgb8: [ny][nx][3] bytes.
 RTMI_SEAM hipError_t rtmi_denoise_launch(hipStream_t stream, uint32_t nx, uint32_t ny, const rtmi_denoise_params &p,
                                          const float *linear, const float *albedo, const float *normal, const float *depth,
-                                         const float *se, void *scratch, float *out, uint8_t *rgb8);
+                                         const float *se, const RtmiDenoisePlanes &W, float *out, uint8_t *rgb8);

@@ -27,8 +27,7 @@
 #include "rtmi_light_launch.hpp"
 #include "rtmi_batch.hpp"
 #include "rtmi_gather_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
 
 static_assert(sizeof(rtmi_gather_params) == 64, "rtmi_gather_params layout");
 

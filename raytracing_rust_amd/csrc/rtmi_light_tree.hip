@@ -23,8 +23,7 @@
 #define RTMI_LEAN_TU 1 /* the plain kernels are defined in rtmi_device.hip */
 #include "rtmi_kernels.hpp"
 #include "rtmi_light_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
 
 static_assert(sizeof(rtmi_light_node) == 32 && sizeof(rtmi_light_path) == 8, "light tree layout");
 

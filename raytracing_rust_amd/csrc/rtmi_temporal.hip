@@ -18,8 +18,8 @@
 #include "rtmi.h"
 #include "rtmi_temporal.h"
 #include "rtmi_frame_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
+#include "rtmi_image_dev.hpp"
 
 namespace {
 
@@ -34,8 +34,6 @@ struct TemporalPush {
     float org[3], llc[3], hor[3], ver[3]; // the current camera
     float porg[3], m[9];                  // the previous camera's origin and inverse matrix, row-major
 };
-
-__device__ __forceinline__ bool surface(float z) { return __builtin_isfinite(z); }
 
 // Steps 1-7 of the header for one pixel per lane.  VAR: standard errors are supplied.
 template <bool VAR>
@@ -184,11 +182,9 @@ __global__ __launch_bounds__(256) void rtmi_temporal_push_kernel(
     out_motion[p] = make_float2(mx, my);
 }
 
-bool finite_f(float v) { return v == v && v - v == 0.0f; }
-
 // the RTMI_ERR_INVALID checks in `name`'s words (rtmi_temporal_create, or the frame handle's entry)
 int check_ranges(const std::string &name, uint32_t nx, uint32_t ny, const rtmi_temporal_params *p) {
-    const auto bad = [&](const char *msg) { return rtmi_fail(RTMI_ERR_INVALID, (name + ": " + msg).c_str()); };
+    const auto bad = [&](const char *msg) { return fail(RTMI_ERR_INVALID, name, msg); };
     if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u) return bad("nx and ny must be in [1, 32768]");
     if (p->max_history < 1u || p->max_history > 65535u) return bad("max_history must be in [1, 65535]");
     if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f)) return bad("alpha_min must be in [0, 1]");
@@ -202,13 +198,6 @@ int check_ranges(const std::string &name, uint32_t nx, uint32_t ny, const rtmi_t
 int check_params(uint32_t nx, uint32_t ny, const rtmi_temporal_params *p) {
     if (int rc = check_ranges("rtmi_temporal_create", nx, ny, p)) return rc;
     if (p->flags & ~RTMI_TEMPORAL_NO_DEMODULATE) return rtmi_fail(RTMI_ERR_UNSUPPORTED, "rtmi_temporal_create: unknown flags bit");
-    return RTMI_OK;
-}
-
-int device_ok(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return rtmi_fail(RTMI_ERR_DEVICE, "rtmi_temporal_create: no HIP device available");
-    if (device < 0 || device >= n) return rtmi_fail(RTMI_ERR_DEVICE, "rtmi_temporal_create: device index out of range");
     return RTMI_OK;
 }
 
@@ -237,15 +226,13 @@ bool camera_inverse(const rtmi_camera *cam, float m[9]) {
     return true;
 }
 
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 } // namespace
 
-struct rtmi_temporal {
+struct RTMI_HIDDEN rtmi_temporal {
     int device = 0;
     uint32_t nx = 0, ny = 0;
     rtmi_temporal_params params{};
-    char *base = nullptr;  // one allocation, carved in 256-B aligned pieces
+    DeviceArena mem; // one allocation, carved in 256-B aligned pieces
     RtmiTemporalHistory hist;
     float *d_lin = nullptr, *d_alb = nullptr, *d_nrm = nullptr, *d_dep = nullptr, *d_se = nullptr;
     float *o_lin = nullptr, *o_se = nullptr, *o_hist = nullptr;
@@ -254,43 +241,33 @@ struct rtmi_temporal {
     bool with_se = false;
 };
 
-#define TP_TRY(fn, expr)                                                                                              \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess)                                                                                         \
-            return rtmi_fail(RTMI_ERR_DEVICE, (std::string(fn ": " #expr ": ") + hipGetErrorString(e_)).c_str());     \
-    } while (0)
+#define TP_TRY(fn, expr) RTMI_HIP_TRY(fn ": ", false, expr, #expr)
 
 static int temporal_alloc(rtmi_temporal *h) {
     TP_TRY("rtmi_temporal_create", hipSetDevice(h->device));
     const size_t n = (size_t)h->nx * h->ny;
-    const size_t f4 = round256(n * 16), f3 = round256(n * 12), f2 = round256(n * 8), f1 = round256(n * 4);
-    TP_TRY("rtmi_temporal_create", hipMalloc(reinterpret_cast<void **>(&h->base), 6 * f4 + 6 * f3 + 2 * f1 + f2));
-    char *at = h->base;
-    const auto take = [&](size_t bytes) {
-        char *r = at;
-        at += bytes;
-        return r;
+    const auto layout = [&](Carve256 &c) {
+        rtmi_temporal_history_layout(h->hist, c, h->nx, h->ny);
+        h->d_lin = c.take<float>(n * 3);
+        h->d_alb = c.take<float>(n * 3);
+        h->d_nrm = c.take<float>(n * 3);
+        h->d_se = c.take<float>(n * 3);
+        h->o_lin = c.take<float>(n * 3);
+        h->o_se = c.take<float>(n * 3);
+        h->d_dep = c.take<float>(n);
+        h->o_hist = c.take<float>(n);
+        h->o_motion = c.take<float2>(n);
     };
-    rtmi_temporal_history_carve(h->hist, take(6 * f4), h->nx, h->ny);
-    h->d_lin = reinterpret_cast<float *>(take(f3));
-    h->d_alb = reinterpret_cast<float *>(take(f3));
-    h->d_nrm = reinterpret_cast<float *>(take(f3));
-    h->d_se = reinterpret_cast<float *>(take(f3));
-    h->o_lin = reinterpret_cast<float *>(take(f3));
-    h->o_se = reinterpret_cast<float *>(take(f3));
-    h->d_dep = reinterpret_cast<float *>(take(f1));
-    h->o_hist = reinterpret_cast<float *>(take(f1));
-    h->o_motion = reinterpret_cast<float2 *>(take(f2));
+    TP_TRY("rtmi_temporal_create", h->mem.alloc(layout));
     TP_TRY("rtmi_temporal_create", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     return RTMI_OK;
 }
 
 extern "C" void rtmi_temporal_destroy(rtmi_temporal *h) {
     if (!h) return;
-    if (h->base || h->stream) (void)hipSetDevice(h->device);
+    if (h->mem.base || h->stream) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->base) (void)hipFree(h->base);
+    h->mem.release();
     delete h;
 }
 
@@ -300,7 +277,7 @@ extern "C" int rtmi_temporal_create(int device, uint32_t nx, uint32_t ny, const 
     if (!p || !out) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_temporal_create: NULL argument");
     int rc = check_params(nx, ny, p);
     if (rc) return rc;
-    rc = device_ok(device);
+    rc = device_ok("rtmi_temporal_create: ", device);
     if (rc) return rc;
     rtmi_temporal *h = new (std::nothrow) rtmi_temporal;
     if (!h) return rtmi_fail(RTMI_ERR_NOMEM, "rtmi_temporal_create: out of host memory");
@@ -324,14 +301,12 @@ extern "C" int rtmi_temporal_reset(rtmi_temporal *h) {
 }
 
 // ---- the device half, shared with the frame handle (rtmi_frame_launch.hpp) --------------------------------------------
-size_t rtmi_temporal_history_bytes(uint32_t nx, uint32_t ny) { return 6 * round256((size_t)nx * ny * 16); }
-
-void rtmi_temporal_history_carve(RtmiTemporalHistory &H, char *base, uint32_t nx, uint32_t ny) {
-    const size_t f4 = round256((size_t)nx * ny * 16);
+void rtmi_temporal_history_layout(RtmiTemporalHistory &H, Carve256 &c, uint32_t nx, uint32_t ny) {
+    const size_t n = (size_t)nx * ny;
     for (int k = 0; k < 2; k++) {
-        H.col[k] = reinterpret_cast<float4 *>(base + (3 * k) * f4);
-        H.geo[k] = reinterpret_cast<float4 *>(base + (3 * k + 1) * f4);
-        H.var[k] = reinterpret_cast<float4 *>(base + (3 * k + 2) * f4);
+        H.col[k] = c.take<float4>(n);
+        H.geo[k] = c.take<float4>(n);
+        H.var[k] = c.take<float4>(n);
     }
 }
 
@@ -344,10 +319,8 @@ int rtmi_temporal_camera_matrix(const char *name, const rtmi_camera *cam, float 
     static_assert(sizeof(rtmi_camera) == 84, "rtmi_camera is 21 floats");
     memcpy(fields, cam, sizeof(rtmi_camera));
     for (float f : fields)
-        if (!finite_f(f)) return rtmi_fail(RTMI_ERR_INVALID, (std::string(name) + ": non-finite camera field").c_str());
-    if (!camera_inverse(cam, m))
-        return rtmi_fail(RTMI_ERR_INVALID,
-                         (std::string(name) + ": singular camera (horizontal, vertical and the corner are coplanar)").c_str());
+        if (!finite_f(f)) return fail(RTMI_ERR_INVALID, name, "non-finite camera field");
+    if (!camera_inverse(cam, m)) return fail(RTMI_ERR_INVALID, name, "singular camera (horizontal, vertical and the corner are coplanar)");
     return RTMI_OK;
 }
 

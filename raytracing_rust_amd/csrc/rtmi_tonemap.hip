@@ -13,8 +13,8 @@
 
 #include "rtmi.h"
 #include "rtmi_tonemap.h"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
+#include "rtmi_image_dev.hpp"
 
 namespace {
 
@@ -194,10 +194,6 @@ __device__ __forceinline__ void tone(float x, float w2, uint32_t &q, float &d) {
     }
 }
 
-struct alignas(4) Bytes12 {
-    uint32_t w[3];
-};
-
 // Step 3.  A lane takes four consecutive pixels: three 16-byte loads, one 12-byte store of rgb8 and three 16-byte stores of
 // display, so a wavefront reads 3072 contiguous bytes and writes runs of 768 and 3072.  The operator and the transfer function
 // are template parameters: the six bodies differ by an f64 sqrt against a log and an exp per channel, and a kernel that held
@@ -240,11 +236,9 @@ __global__ __launch_bounds__(kBlock) void rtmi_tonemap_apply_kernel(const float 
     }
 }
 
-bool finite_f(float v) { return v == v && v - v == 0.0f; }
-
 // the RTMI_ERR_INVALID and RTMI_ERR_UNSUPPORTED checks of a size and a parameter block, in `name`'s words
 int check_params(const char *name, uint32_t nx, uint32_t ny, const rtmi_tonemap_params *p) {
-    const auto bad = [&](const char *msg) { return rtmi_fail(RTMI_ERR_INVALID, (std::string(name) + ": " + msg).c_str()); };
+    const auto bad = [&](const char *msg) { return fail(RTMI_ERR_INVALID, name, msg); };
     if (nx == 0 || ny == 0 || nx > 32768u || ny > 32768u) return bad("nx and ny must be in [1, 32768]");
     if (p->op > RTMI_TONEMAP_ACES) return bad("op must be RTMI_TONEMAP_CLAMP, _REINHARD or _ACES");
     if (p->oetf > RTMI_TONEMAP_SRGB) return bad("oetf must be RTMI_TONEMAP_GAMMA2 or _SRGB");
@@ -261,19 +255,9 @@ int check_params(const char *name, uint32_t nx, uint32_t ny, const rtmi_tonemap_
     if (!finite_f(p->adapt_min)) return bad("adapt_min must be finite");
     if (!finite_f(p->adapt_max) || !(p->adapt_max >= p->adapt_min)) return bad("adapt_max must be finite and >= adapt_min");
     if (p->reserved) return bad("reserved must be 0");
-    if (p->flags) return rtmi_fail(RTMI_ERR_UNSUPPORTED, (std::string(name) + ": flags must be 0 (reserved)").c_str());
+    if (p->flags) return fail(RTMI_ERR_UNSUPPORTED, name, "flags must be 0 (reserved)");
     return RTMI_OK;
 }
-
-int device_ok(const char *name, int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
-        return rtmi_fail(RTMI_ERR_DEVICE, (std::string(name) + ": no HIP device available").c_str());
-    if (device < 0 || device >= n) return rtmi_fail(RTMI_ERR_DEVICE, (std::string(name) + ": device index out of range").c_str());
-    return RTMI_OK;
-}
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 hipError_t meter_launch(hipStream_t s, const float *d_linear, uint32_t *d_bins, uint32_t n, const rtmi_tonemap_params &p) {
     const float scale = 256.0f / (p.log2_max - p.log2_min);
@@ -294,29 +278,24 @@ void apply_launch_oetf(uint32_t oetf, dim3 grid, hipStream_t s, const float *lin
 
 } // namespace
 
-struct rtmi_tonemap {
+struct RTMI_HIDDEN rtmi_tonemap {
     int device = 0;
     uint32_t nx = 0, ny = 0;
     rtmi_tonemap_params params{};
-    char *base = nullptr; // the bins, then the record
+    DeviceArena mem; // the bins, then the record
     uint32_t *d_bins = nullptr;
     TonemapDev *d_dev = nullptr;
     bool fresh = true;  // the next apply is a first apply
     bool dirty = false; // an apply failed after its meter may have run: the next one zeroes the bins first
     // the host form's staging, allocated by its first call
-    char *stage = nullptr;
+    DeviceArena stage;
     float *s_lin = nullptr, *s_disp = nullptr;
     uint8_t *s_rgb = nullptr;
     rtmi_tonemap_state *s_state = nullptr;
     hipStream_t stream = nullptr;
 };
 
-#define TM_TRY(fn, expr)                                                                                              \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess)                                                                                         \
-            return rtmi_fail(RTMI_ERR_DEVICE, (std::string(fn ": " #expr ": ") + hipGetErrorString(e_)).c_str());     \
-    } while (0)
+#define TM_TRY(fn, expr) RTMI_HIP_TRY(fn ": ", false, expr, #expr)
 
 // the two or three kernels of one apply on `s`; nothing here allocates, waits or copies
 static hipError_t tonemap_kernels(rtmi_tonemap *h, hipStream_t s, const float *d_linear, float dt, uint8_t *d_rgb8,
@@ -364,13 +343,13 @@ static hipError_t tonemap_enqueue(rtmi_tonemap *h, hipStream_t s, const float *d
 
 extern "C" void rtmi_tonemap_destroy(rtmi_tonemap *h) {
     if (!h) return;
-    if (h->base || h->stage || h->stream) {
+    if (h->mem.base || h->stage.base || h->stream) {
         (void)hipSetDevice(h->device);
         (void)hipDeviceSynchronize(); // work enqueued on the caller's streams still reads the record
     }
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->base) (void)hipFree(h->base);
+    h->stage.release();
+    h->mem.release();
     delete h;
 }
 
@@ -380,7 +359,7 @@ extern "C" int rtmi_tonemap_create(int device, uint32_t nx, uint32_t ny, const r
     if (!p || !out) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_tonemap_create: NULL argument");
     int rc = check_params("rtmi_tonemap_create", nx, ny, p);
     if (rc) return rc;
-    rc = device_ok("rtmi_tonemap_create", device);
+    rc = device_ok("rtmi_tonemap_create: ", device);
     if (rc) return rc;
     rtmi_tonemap *h = new (std::nothrow) rtmi_tonemap;
     if (!h) return rtmi_fail(RTMI_ERR_NOMEM, "rtmi_tonemap_create: out of host memory");
@@ -390,11 +369,12 @@ extern "C" int rtmi_tonemap_create(int device, uint32_t nx, uint32_t ny, const r
     h->params = *p;
     const auto setup = [&]() -> int {
         TM_TRY("rtmi_tonemap_create", hipSetDevice(device));
-        const size_t bytes = kBins * sizeof(uint32_t) + sizeof(TonemapDev);
-        TM_TRY("rtmi_tonemap_create", hipMalloc(reinterpret_cast<void **>(&h->base), bytes));
-        h->d_bins = reinterpret_cast<uint32_t *>(h->base);
-        h->d_dev = reinterpret_cast<TonemapDev *>(h->base + kBins * sizeof(uint32_t));
-        TM_TRY("rtmi_tonemap_create", hipMemset(h->base, 0, bytes));
+        const auto layout = [&](Carve256 &c) {
+            h->d_bins = c.take<uint32_t>(kBins);
+            h->d_dev = c.take<TonemapDev>(1);
+        };
+        TM_TRY("rtmi_tonemap_create", h->mem.alloc(layout));
+        TM_TRY("rtmi_tonemap_create", hipMemset(h->mem.base, 0, h->mem.bytes));
         TM_TRY("rtmi_tonemap_create", hipDeviceSynchronize());
         return RTMI_OK;
     };
@@ -415,7 +395,7 @@ extern "C" int rtmi_tonemap_reset(rtmi_tonemap *h) {
 
 // the argument checks the two forms share, the handle left to the caller
 static int check_apply(const char *name, const void *linear, float dt, const void *rgb8, const void *display, const void *state) {
-    const auto bad = [&](const char *msg) { return rtmi_fail(RTMI_ERR_INVALID, (std::string(name) + ": " + msg).c_str()); };
+    const auto bad = [&](const char *msg) { return fail(RTMI_ERR_INVALID, name, msg); };
     if (!linear) return bad("NULL linear");
     if (!finite_f(dt) || !(dt >= 0.0f)) return bad("dt must be finite and >= 0");
     if (!rgb8 && !display && !state) return bad("every output is NULL");
@@ -425,7 +405,7 @@ static int check_apply(const char *name, const void *linear, float dt, const voi
 extern "C" int rtmi_tonemap_apply_device(rtmi_tonemap *h, const void *d_linear, float dt, void *d_rgb8, void *d_display,
                                          void *d_state, void *stream) {
     if (int rc = check_apply("rtmi_tonemap_apply_device", d_linear, dt, d_rgb8, d_display, d_state)) return rc;
-    if (((uintptr_t)d_linear & 15u) || ((uintptr_t)d_display & 15u) || ((uintptr_t)d_rgb8 & 3u) || ((uintptr_t)d_state & 3u))
+    if (misaligned(d_linear, 16) || misaligned(d_display, 16) || misaligned(d_rgb8, 4) || misaligned(d_state, 4))
         return rtmi_fail(RTMI_ERR_INVALID, "rtmi_tonemap_apply_device: misaligned pointer (d_linear and d_display need 16 bytes, "
                                            "d_rgb8 and d_state 4)");
     if (!h) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_tonemap_apply_device: NULL handle");
@@ -440,13 +420,14 @@ static int tonemap_run(rtmi_tonemap *h, const float *linear, float dt, uint8_t *
                        rtmi_tonemap_state *out_state) {
     const size_t n = (size_t)h->nx * h->ny;
     TM_TRY("rtmi_tonemap_apply", hipSetDevice(h->device));
-    if (!h->stage) {
-        const size_t f3 = round256(n * 12), b3 = round256(n * 3);
-        TM_TRY("rtmi_tonemap_apply", hipMalloc(reinterpret_cast<void **>(&h->stage), 2 * f3 + b3 + 256));
-        h->s_lin = reinterpret_cast<float *>(h->stage);
-        h->s_disp = reinterpret_cast<float *>(h->stage + f3);
-        h->s_rgb = reinterpret_cast<uint8_t *>(h->stage + 2 * f3);
-        h->s_state = reinterpret_cast<rtmi_tonemap_state *>(h->stage + 2 * f3 + b3);
+    if (!h->stage.base) {
+        const auto layout = [&](Carve256 &c) {
+            h->s_lin = c.take<float>(n * 3);
+            h->s_disp = c.take<float>(n * 3);
+            h->s_rgb = c.take<uint8_t>(n * 3);
+            h->s_state = c.take<rtmi_tonemap_state>(1);
+        };
+        TM_TRY("rtmi_tonemap_apply", h->stage.alloc(layout));
     }
     if (!h->stream) TM_TRY("rtmi_tonemap_apply", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     hipStream_t s = h->stream;
@@ -476,19 +457,18 @@ extern "C" int rtmi_probe_tonemap_histogram(int device, uint32_t nx, uint32_t ny
     if (!p || !linear || !out_bins) return rtmi_fail(RTMI_ERR_INVALID, "rtmi_probe_tonemap_histogram: NULL argument");
     int rc = check_params("rtmi_probe_tonemap_histogram", nx, ny, p);
     if (rc) return rc;
-    rc = device_ok("rtmi_probe_tonemap_histogram", device);
+    rc = device_ok("rtmi_probe_tonemap_histogram: ", device);
     if (rc) return rc;
     TM_TRY("rtmi_probe_tonemap_histogram", hipSetDevice(device));
-    const size_t n = (size_t)nx * ny, f3 = round256(n * 12);
-    struct Scratch {
-        char *base = nullptr;
-        ~Scratch() {
-            if (base) (void)hipFree(base);
-        }
-    } m;
-    TM_TRY("rtmi_probe_tonemap_histogram", hipMalloc(reinterpret_cast<void **>(&m.base), f3 + kBins * sizeof(uint32_t)));
-    float *d_lin = reinterpret_cast<float *>(m.base);
-    uint32_t *d_bins = reinterpret_cast<uint32_t *>(m.base + f3);
+    const size_t n = (size_t)nx * ny;
+    float *d_lin;
+    uint32_t *d_bins;
+    const auto layout = [&](Carve256 &c) {
+        d_lin = c.take<float>(n * 3);
+        d_bins = c.take<uint32_t>(kBins);
+    };
+    DeviceArena mem;
+    TM_TRY("rtmi_probe_tonemap_histogram", mem.alloc(layout));
     TM_TRY("rtmi_probe_tonemap_histogram", hipMemcpy(d_lin, linear, n * 12, hipMemcpyHostToDevice));
     TM_TRY("rtmi_probe_tonemap_histogram", hipMemset(d_bins, 0, kBins * sizeof(uint32_t)));
     TM_TRY("rtmi_probe_tonemap_histogram", meter_launch(nullptr, d_lin, d_bins, (uint32_t)n, *p));

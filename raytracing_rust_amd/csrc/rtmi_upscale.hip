@@ -16,8 +16,8 @@
 #include "rtmi_upscale.h"
 #include "rtmi_light_coop.h"
 #include "rtmi_frame_launch.hpp"
-
-int rtmi_fail(int code, const char *msg); // rtmi_device.hip: the message of rtmi_last_error
+#include "rtmi_hostkit.hpp"
+#include "rtmi_image_dev.hpp"
 
 namespace {
 
@@ -31,10 +31,6 @@ struct UpscaleArgs {
     float sigma_z, eps_z, albedo_min, w_min;
     int squarings; // log2(normal_power)
     int normal_on; // normal_power != 0
-};
-
-struct alignas(4) Bytes12 {
-    uint32_t w[3];
 };
 
 __device__ __forceinline__ uint32_t quantise(float v) {
@@ -318,10 +314,6 @@ __global__ __launch_bounds__(kTileLanes * kTileRows) void rtmi_upscale_staged_ke
     }
 }
 
-bool finite_f(float v) { return v == v && v - v == 0.0f; }
-
-int fail(int code, const std::string &name, const char *msg) { return rtmi_fail(code, (name + ": " + msg).c_str()); }
-
 // the RTMI_ERR_INVALID checks of the two sizes and a parameter block, in `name`'s words; the flags are the caller's
 int check_sizes(const char *name, uint32_t lx, uint32_t ly, uint32_t nx, uint32_t ny) {
     if (lx == 0 || ly == 0 || nx > 32768u || ny > 32768u || lx > nx || ly > ny)
@@ -359,15 +351,6 @@ int check_call(const char *name, uint32_t lx, uint32_t ly, uint32_t nx, uint32_t
     return RTMI_OK;
 }
 
-int device_ok(const char *name, int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(RTMI_ERR_DEVICE, name, "no HIP device available");
-    if (device < 0 || device >= n) return fail(RTMI_ERR_DEVICE, name, "device index out of range");
-    return RTMI_OK;
-}
-
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 constexpr size_t kStageLimit = 64 * 1024; // the LDS a workgroup of the staged variant may take
 
 // RTMI_UPSCALE_VARIANT = "direct" or "staged" picks the kernel for the measurements and the tests; unset: the default.
@@ -386,8 +369,7 @@ hipError_t upscale_launch(hipStream_t s, uint32_t lx, uint32_t ly, uint32_t nx, 
                           const float *lin_lo, const float *alb_lo, const float *nrm_lo, const float *z_lo, const float *albedo,
                           const float *normal, const float *depth, float *out_linear, uint8_t *out_rgb8, uint8_t *out_cls) {
     UpscaleArgs A{lin_lo, alb_lo, nrm_lo, z_lo, lx, ly, nx, nx * ny, (float)lx / (float)nx, (float)ly / (float)ny,
-                  p.sigma_z, p.eps_z, p.albedo_min, p.w_min, 0, p.normal_power != 0u};
-    for (uint32_t pw = p.normal_power; pw > 1u; pw >>= 1) A.squarings++;
+                  p.sigma_z, p.eps_z, p.albedo_min, p.w_min, normal_squarings(p.normal_power), p.normal_power != 0u};
     const bool wide = !(((uintptr_t)albedo | (uintptr_t)normal | (uintptr_t)depth) & 15u);
     // the staged variant's footprint: over 256 columns the tap position advances by 255*sx, its floor by less than that
     // plus 1, and the taps reach one column further: at most (int)(255*sx) + 3 columns, and one more for the fp32 roundings
@@ -414,13 +396,7 @@ hipError_t upscale_launch(hipStream_t s, uint32_t lx, uint32_t ly, uint32_t nx, 
     return hipGetLastError();
 }
 
-#define UP_TRY(name, expr)                                                                                             \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess)                                                                                          \
-            return rtmi_fail(e_ == hipErrorOutOfMemory ? RTMI_ERR_NOMEM : RTMI_ERR_DEVICE,                             \
-                             (std::string(name) + ": " #expr ": " + hipGetErrorString(e_)).c_str());                   \
-    } while (0)
+#define UP_TRY(name, expr) RTMI_HIP_TRY(std::string(name) + ": ", true, expr, #expr)
 
 // The flags that go to the lit render only and that the features render does not take: RTMI_FLAG_LIGHT_COOP and bit 11, the
 // cooperative render's unnamed small-pool test knob (rtmi_device.hip reads it as 1u << 11; rtmi_frame.hip strips the same two).
@@ -442,7 +418,7 @@ extern "C" int rtmi_upscale_device(int device, uint32_t lx, uint32_t ly, uint32_
     // every argument check comes before the first HIP call
     const char *name = "rtmi_upscale_device";
     int rc;
-    if ((rc = check_call(name, lx, ly, nx, ny, p, in, out, true)) || (rc = device_ok(name, device))) return rc;
+    if ((rc = check_call(name, lx, ly, nx, ny, p, in, out, true)) || (rc = device_ok(std::string(name) + ": ", device))) return rc;
     UP_TRY(name, hipSetDevice(device));
     UP_TRY(name, upscale_launch(static_cast<hipStream_t>(stream), lx, ly, nx, ny, *p, in->linear_lo, in->albedo_lo, in->normal_lo,
                                 in->depth_lo, in->albedo, in->normal, in->depth, out->linear, out->rgb8, out->cls));
@@ -453,29 +429,25 @@ extern "C" int rtmi_upscale(int device, uint32_t lx, uint32_t ly, uint32_t nx, u
                             const rtmi_upscale_in *in, const rtmi_upscale_out *out) {
     const char *name = "rtmi_upscale";
     int rc;
-    if ((rc = check_call(name, lx, ly, nx, ny, p, in, out, false)) || (rc = device_ok(name, device))) return rc;
+    if ((rc = check_call(name, lx, ly, nx, ny, p, in, out, false)) || (rc = device_ok(std::string(name) + ": ", device))) return rc;
     UP_TRY(name, hipSetDevice(device));
     const size_t nl = (size_t)lx * ly, n = (size_t)nx * ny;
-    const size_t l3 = round256(nl * 12), l1 = round256(nl * 4), f3 = round256(n * 12), f1 = round256(n * 4), b3 = round256(n * 3),
-                 b1 = round256(n);
-    struct Scratch {
-        char *base = nullptr;
-        ~Scratch() {
-            if (base) (void)hipFree(base);
-        }
-    } m;
-    UP_TRY(name, hipMalloc(reinterpret_cast<void **>(&m.base), 3 * l3 + l1 + 3 * f3 + f1 + b3 + b1));
-    char *at = m.base;
-    const auto take = [&](size_t b) {
-        char *r = at;
-        at += b;
-        return r;
+    float *d_lin_lo, *d_alb_lo, *d_nrm_lo, *d_z_lo, *d_alb, *d_nrm, *d_z, *d_lin;
+    uint8_t *d_rgb, *d_cls;
+    const auto layout = [&](Carve256 &c) {
+        d_lin_lo = c.take<float>(nl * 3);
+        d_alb_lo = c.take<float>(nl * 3);
+        d_nrm_lo = c.take<float>(nl * 3);
+        d_z_lo = c.take<float>(nl);
+        d_alb = c.take<float>(n * 3);
+        d_nrm = c.take<float>(n * 3);
+        d_z = c.take<float>(n);
+        d_lin = c.take<float>(n * 3);
+        d_rgb = c.take<uint8_t>(n * 3);
+        d_cls = c.take<uint8_t>(n);
     };
-    float *d_lin_lo = reinterpret_cast<float *>(take(l3)), *d_alb_lo = reinterpret_cast<float *>(take(l3));
-    float *d_nrm_lo = reinterpret_cast<float *>(take(l3)), *d_z_lo = reinterpret_cast<float *>(take(l1));
-    float *d_alb = reinterpret_cast<float *>(take(f3)), *d_nrm = reinterpret_cast<float *>(take(f3));
-    float *d_z = reinterpret_cast<float *>(take(f1)), *d_lin = reinterpret_cast<float *>(take(f3));
-    uint8_t *d_rgb = reinterpret_cast<uint8_t *>(take(b3)), *d_cls = reinterpret_cast<uint8_t *>(take(b1));
+    DeviceArena mem;
+    UP_TRY(name, mem.alloc(layout));
     UP_TRY(name, hipMemcpy(d_lin_lo, in->linear_lo, nl * 12, hipMemcpyHostToDevice));
     UP_TRY(name, hipMemcpy(d_alb_lo, in->albedo_lo, nl * 12, hipMemcpyHostToDevice));
     UP_TRY(name, hipMemcpy(d_nrm_lo, in->normal_lo, nl * 12, hipMemcpyHostToDevice));
@@ -492,13 +464,13 @@ extern "C" int rtmi_upscale(int device, uint32_t lx, uint32_t ly, uint32_t nx, u
 }
 
 // ---- the handle -----------------------------------------------------------------------------------------------------
-struct rtmi_upscaler {
+struct RTMI_HIDDEN rtmi_upscaler {
     std::mutex mu; // one render or reset at a time: the two steps of a render take the scene's hold one after the other
     rtmi_scene *s = nullptr;
     rtmi_frame *low = nullptr;
     rtmi_render_params p{}; // the full size; ns and seed are set per call
     rtmi_upscaler_opts o{};
-    char *base = nullptr; // one allocation, carved in 256-B aligned pieces
+    DeviceArena mem; // one allocation, carved in 256-B aligned pieces
     float *lo_lin = nullptr, *lo_alb = nullptr, *lo_nrm = nullptr, *lo_z = nullptr;
     float *out_lin = nullptr;
     uint8_t *out_rgb = nullptr, *out_cls = nullptr;
@@ -507,11 +479,11 @@ struct rtmi_upscaler {
 extern "C" void rtmi_upscaler_destroy(rtmi_upscaler *h) {
     if (!h) return;
     if (h->low) rtmi_frame_destroy(h->low); // under the scene's lock, after its running work
-    if (h->base) {
+    if (h->mem.base) {
         RtmiFrameHold *hold = nullptr;
         const RtmiFrameLit plain{"rtmi_upscaler_destroy", false, false, 1.0f};
         (void)rtmi_frame_hold_begin(h->s, plain, &hold);
-        (void)hipFree(h->base);
+        h->mem.release();
         rtmi_frame_hold_end(hold);
     }
     delete h;
@@ -548,26 +520,21 @@ extern "C" int rtmi_upscaler_create(rtmi_scene *s, const rtmi_render_params *p_i
     h->s = s;
     const auto alloc = [&]() -> int {
         const size_t nl = (size_t)o->lx * o->ly, n = (size_t)h->p.nx * h->p.ny;
-        const size_t l3 = round256(nl * 12), l1 = round256(nl * 4), f3 = round256(n * 12), b3 = round256(n * 3), b1 = round256(n);
+        const auto layout = [&](Carve256 &c) {
+            h->lo_lin = c.take<float>(nl * 3);
+            h->lo_alb = c.take<float>(nl * 3);
+            h->lo_nrm = c.take<float>(nl * 3);
+            h->lo_z = c.take<float>(nl);
+            h->out_lin = c.take<float>(n * 3);
+            h->out_rgb = c.take<uint8_t>(n * 3);
+            h->out_cls = c.take<uint8_t>(n);
+        };
         RtmiFrameHold *hold = nullptr; // the scene's device, under its lock
         const RtmiFrameLit plain{name, false, false, 1.0f};
         if (int r = rtmi_frame_hold_begin(s, plain, &hold)) return r;
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&h->base), 3 * l3 + l1 + f3 + b3 + b1);
+        const hipError_t e = h->mem.alloc(layout);
         rtmi_frame_hold_end(hold);
         UP_TRY(name, e);
-        char *at = h->base;
-        const auto take = [&](size_t b) {
-            char *r = at;
-            at += b;
-            return r;
-        };
-        h->lo_lin = reinterpret_cast<float *>(take(l3));
-        h->lo_alb = reinterpret_cast<float *>(take(l3));
-        h->lo_nrm = reinterpret_cast<float *>(take(l3));
-        h->lo_z = reinterpret_cast<float *>(take(l1));
-        h->out_lin = reinterpret_cast<float *>(take(f3));
-        h->out_rgb = reinterpret_cast<uint8_t *>(take(b3));
-        h->out_cls = reinterpret_cast<uint8_t *>(take(b1));
         return RTMI_OK;
     };
     if ((rc = alloc())) {

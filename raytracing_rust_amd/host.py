@@ -1242,18 +1242,76 @@ _PLANES = {"linear": ((3,), np.float32), "rgb8": ((3,), np.uint8), "stderr": ((3
            "hits": ((), np.uint32)}
 
 
-class Session:
-    """A render session of Scene.session (include/rtmi_session.h).  Calls on it serialise with every other call on its
-    scene.  close() frees its device state (76 B per tile-padded pixel); Host.free_all() closes what is still open."""
+def _rtmi_check(lib, rc, what):
+    """Raises for a refusal of librtmi's entry `what`: Unsupported for RTMI_ERR_UNSUPPORTED, HostError otherwise."""
+    if rc != 0:
+        raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, lib.rtmi_last_error().decode()))
 
-    def __init__(self, host, h, nx, ny, keep=()):
-        self.host, self.h, self.nx, self.ny, self.keep = host, h, nx, ny, keep
-        host._sessions = getattr(host, "_sessions", []) + [self]
+
+def _check_plane(name, a, want, f32=np.float32):
+    """The shape and dtype checks of an input plane (a numpy array, or a torch tensor with f32 = torch.float32)."""
+    if tuple(a.shape) != want:
+        raise ValueError("%s must have the shape %r, not %r" % (name, want, tuple(a.shape)))
+    if a.dtype != f32:
+        raise ValueError("%s must be float32, not %s" % (name, a.dtype))
+
+
+def _feature_planes(ny, nx, linear, albedo, normal, depth, stderr):
+    """The inputs of denoise() and Temporal.push() by name, checked, as contiguous arrays; stderr only when given."""
+    planes = {"linear": linear, "albedo": albedo, "normal": normal, "depth": depth}
+    if stderr is not None:
+        planes["stderr"] = stderr
+    for name, a in planes.items():
+        a = np.asarray(a)
+        _check_plane(name, a, (ny, nx) if name == "depth" else (ny, nx, 3))
+        planes[name] = np.ascontiguousarray(a)
+    return planes
+
+
+class _Handle:
+    """What the handle classes share: h (None once closed), the list of open handles that Host.free_all() closes, close()
+    and the context manager.  A subclass names itself in _closed ("the ... is closed") and frees h in _destroy."""
+    h = None
+
+    def _opened(self, h, registry):
+        self.h, self._open = h, registry
+        registry.append(self)
+
+    def _check(self, rc, what):  # the handles of librtmi's own entries; the others go through Host._check
+        _rtmi_check(self.lib, rc, what)
 
     def _handle(self):
         if not self.h:
-            raise HostError("the session is closed")
+            raise HostError("the %s is closed" % self._closed)
         return self.h
+
+    def close(self):
+        if self.h:
+            h, self.h = self.h, None
+            if self in self._open:
+                self._open.remove(self)
+            self._destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class Session(_Handle):
+    """A render session of Scene.session (include/rtmi_session.h).  Calls on it serialise with every other call on its
+    scene.  close() frees its device state (76 B per tile-padded pixel); Host.free_all() closes what is still open."""
+
+    _closed = "session"
+
+    def __init__(self, host, h, nx, ny, keep=()):
+        self.host, self.nx, self.ny, self.keep = host, nx, ny, keep
+        self._opened(h, host.__dict__.setdefault("_sessions", []))
+
+    def _destroy(self, h):
+        self.host._check(self.host.lib.rth_session_close(h))
 
     def render(self, spp):
         """FIXED sessions: spp more samples for every tile.  Returns the call's stats."""
@@ -1310,12 +1368,6 @@ class Session:
             if time.monotonic() - t0 >= seconds:
                 return self.spp()[1]
 
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            self.host._sessions = [s for s in getattr(self.host, "_sessions", []) if s is not self]
-            self.host._check(self.host.lib.rth_session_close(h))
-
 
 # the planes of rtmi_frame_out in Frame.render's result: (group, name in the group, field, channels, dtype)
 _FRAME_PLANES = ((None, "linear", "linear", (3,), "float32"), (None, "rgb8", "rgb8", (3,), "uint8"),
@@ -1326,19 +1378,19 @@ _FRAME_PLANES = ((None, "linear", "linear", (3,), "float32"), (None, "rgb8", "rg
                  ("accumulated", "history", "history", (), "float32"), ("accumulated", "motion", "motion", (2,), "float32"))
 
 
-class Frame:
+class Frame(_Handle):
     """A frame handle of Scene.frame (include/rtmi_frame.h).  Calls on it serialise with every other call on its scene.
     close() frees its device memory (227 B per pixel with every stage on); Host.free_all() closes what is still open.
     Usable as a context manager."""
 
-    def __init__(self, host, h, nx, ny, device, temporal, keep=()):
-        self.host, self.h, self.nx, self.ny, self.device, self.temporal, self.keep = host, h, nx, ny, device, temporal, keep
-        host._frames = getattr(host, "_frames", []) + [self]
+    _closed = "frame"
 
-    def _handle(self):
-        if not self.h:
-            raise HostError("the frame is closed")
-        return self.h
+    def __init__(self, host, h, nx, ny, device, temporal, keep=()):
+        self.host, self.nx, self.ny, self.device, self.temporal, self.keep = host, nx, ny, device, temporal, keep
+        self._opened(h, host.__dict__.setdefault("_frames", []))
+
+    def _destroy(self, h):
+        self.host._check(self.host.lib.rth_frame_close(h))
 
     def render(self, cam, ns, seed=0, aux=False, out="numpy", tonemap=None, dt=0.0):
         """One frame under `cam` (a Camera of Host) with ns >= 2 samples per pixel.  Returns dict(linear f32 [ny,nx,3],
@@ -1382,19 +1434,6 @@ class Frame:
         """Forgets the frames rendered so far: the next frame starts a fresh history."""
         self.host._check(self.host.lib.rth_frame_reset(self._handle()))
 
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            self.host._frames = [f for f in getattr(self.host, "_frames", []) if f is not self]
-            self.host._check(self.host.lib.rth_frame_close(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
 
 # the planes of rtmi_upscaler_out in Upscaler.render's result: (group, name in the group, field, low size, channels, dtype)
 _UPSCALER_PLANES = ((None, "linear", "linear", False, (3,), "float32"), (None, "rgb8", "rgb8", False, (3,), "uint8"),
@@ -1405,20 +1444,20 @@ _UPSCALER_PLANES = ((None, "linear", "linear", False, (3,), "float32"), (None, "
                     ("low", "normal", "normal", True, (3,), "float32"), ("low", "depth", "depth", True, (), "float32"))
 
 
-class Upscaler:
+class Upscaler(_Handle):
     """An upscaler handle of Scene.upscaler (include/rtmi_upscale.h): nx x ny images rebuilt from lx x ly frames.  Calls on
     one handle serialise on a lock of its own; a render holds its scene twice (the low frame, then the features and the
     reconstruction), and another render of the scene may run between the two without touching the handle's planes.  close() frees its device memory (the low frame's, 40 B per low pixel
     and 16 B per full pixel); Host.free_all() closes what is still open.  Usable as a context manager."""
 
-    def __init__(self, host, h, nx, ny, lx, ly, device, keep=()):
-        self.host, self.h, self.nx, self.ny, self.lx, self.ly, self.device, self.keep = host, h, nx, ny, lx, ly, device, keep
-        host._upscalers = getattr(host, "_upscalers", []) + [self]
+    _closed = "upscaler"
 
-    def _handle(self):
-        if not self.h:
-            raise HostError("the upscaler is closed")
-        return self.h
+    def __init__(self, host, h, nx, ny, lx, ly, device, keep=()):
+        self.host, self.nx, self.ny, self.lx, self.ly, self.device, self.keep = host, nx, ny, lx, ly, device, keep
+        self._opened(h, host.__dict__.setdefault("_upscalers", []))
+
+    def _destroy(self, h):
+        self.host._check(self.host.lib.rth_upscaler_close(h))
 
     def render(self, cam, ns, seed=0, aux=False, out="numpy", tonemap=None, dt=0.0):
         """One frame under `cam` (a Camera of Host): the low frame with ns >= 2 samples per pixel, rebuilt at the full size.
@@ -1463,19 +1502,6 @@ class Upscaler:
     def reset(self):
         """Forgets the frames rendered so far: the next frame starts a fresh history."""
         self.host._check(self.host.lib.rth_upscaler_reset(self._handle()))
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            self.host._upscalers = [u for u in getattr(self.host, "_upscalers", []) if u is not self]
-            self.host._check(self.host.lib.rth_upscaler_close(h))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def _outputs(ny, nx, names, sig=None):
@@ -1764,17 +1790,7 @@ def denoise(linear, albedo, normal, depth, stderr=None, iterations=5, normal_pow
     if depth.ndim != 2:
         raise ValueError("depth must be [ny, nx], not %r" % (depth.shape,))
     ny, nx = depth.shape
-    planes = {"linear": linear, "albedo": albedo, "normal": normal, "depth": depth}
-    if stderr is not None:
-        planes["stderr"] = stderr
-    for name, a in planes.items():
-        a = np.asarray(a)
-        want = (ny, nx) if name == "depth" else (ny, nx, 3)
-        if a.shape != want:
-            raise ValueError("%s must have the shape %r, not %r" % (name, want, a.shape))
-        if a.dtype != np.float32:
-            raise ValueError("%s must be float32, not %s" % (name, a.dtype))
-        planes[name] = np.ascontiguousarray(a)
+    planes = _feature_planes(ny, nx, linear, albedo, normal, depth, stderr)
     p = _denoise_params(iterations, normal_power, sigma_l, sigma_z, eps_l, eps_z, albedo_min)
     lin = np.zeros((ny, nx, 3), np.float32)
     rgb = np.zeros((ny, nx, 3), np.uint8)
@@ -1782,8 +1798,7 @@ def denoise(linear, albedo, normal, depth, stderr=None, iterations=5, normal_pow
     rc = lib.rtmi_denoise(device, nx, ny, C.byref(p), planes["linear"].ctypes.data, planes["albedo"].ctypes.data,
                           planes["normal"].ctypes.data, planes["depth"].ctypes.data,
                           planes["stderr"].ctypes.data if stderr is not None else None, lin.ctypes.data, rgb.ctypes.data)
-    if rc != 0:
-        raise {2: Unsupported}.get(rc, HostError)("rtmi_denoise failed (%d): %s" % (rc, lib.rtmi_last_error().decode()))
+    _rtmi_check(lib, rc, "rtmi_denoise")
     return {"linear": lin, "rgb8": rgb}
 
 
@@ -1792,30 +1807,24 @@ _denoise = denoise
 _temporals = []  # the open Temporal handles; Host.free_all() closes them
 
 
-class Temporal:
+class Temporal(_Handle):
     """The device-resident temporal history of include/rtmi_temporal.h for nx x ny images on `device`: push() reprojects
     the frames pushed so far into the new frame's camera and blends them with it.  demodulate=False sets
     RTMI_TEMPORAL_NO_DEMODULATE.  close() frees its device memory (184 B per pixel); Host.free_all() closes what is
-    still open.  HostError for what rtmi_temporal_create refuses."""
+    still open.  Usable as a context manager.  HostError for what rtmi_temporal_create refuses."""
+    _closed = "temporal history"
 
     def __init__(self, nx, ny, device=0, max_history=32, alpha_min=0.0, depth_tol=0.05, normal_min=0.9, albedo_min=1e-3,
                  demodulate=True):
         self.lib = abi.load_rtmi()
-        self.nx, self.ny, self.device, self.h = int(nx), int(ny), device, None
+        self.nx, self.ny, self.device = int(nx), int(ny), device
         p = _temporal_params(max_history, alpha_min, depth_tol, normal_min, albedo_min, demodulate)
         h = C.c_void_p()
         self._check(self.lib.rtmi_temporal_create(device, self.nx, self.ny, C.byref(p), C.byref(h)), "rtmi_temporal_create")
-        self.h = h
-        _temporals.append(self)
+        self._opened(h, _temporals)
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, self.lib.rtmi_last_error().decode()))
-
-    def _handle(self):
-        if not self.h:
-            raise HostError("the temporal history is closed")
-        return self.h
+    def _destroy(self, h):
+        self.lib.rtmi_temporal_destroy(h)
 
     def push(self, cam, linear, albedo, normal, depth, stderr=None, motion=False):
         """One frame: cam is the camera it was rendered with (a Camera of Host or an abi.Camera); linear, albedo, normal
@@ -1826,17 +1835,7 @@ class Temporal:
         h = self._handle()
         c = cam.lower() if hasattr(cam, "lower") else cam
         ny, nx = self.ny, self.nx
-        planes = {"linear": linear, "albedo": albedo, "normal": normal, "depth": depth}
-        if stderr is not None:
-            planes["stderr"] = stderr
-        for name, a in planes.items():
-            a = np.asarray(a)
-            want = (ny, nx) if name == "depth" else (ny, nx, 3)
-            if a.shape != want:
-                raise ValueError("%s must have the shape %r, not %r" % (name, want, a.shape))
-            if a.dtype != np.float32:
-                raise ValueError("%s must be float32, not %s" % (name, a.dtype))
-            planes[name] = np.ascontiguousarray(a)
+        planes = _feature_planes(ny, nx, linear, albedo, normal, depth, stderr)
         out = {"linear": np.zeros((ny, nx, 3), np.float32),
                "stderr": np.zeros((ny, nx, 3), np.float32) if stderr is not None else None,
                "history": np.zeros((ny, nx), np.float32)}
@@ -1854,13 +1853,6 @@ class Temporal:
     def reset(self):
         """Forgets the frames pushed so far; the next push is a first push."""
         self._check(self.lib.rtmi_temporal_reset(self._handle()), "rtmi_temporal_reset")
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            if self in _temporals:
-                _temporals.remove(self)
-            self.lib.rtmi_temporal_destroy(h)
 
 
 _tonemaps = []  # the open Tonemap handles; Host.free_all() closes them
@@ -1883,7 +1875,7 @@ def _tonemap_state(st):
             "counted": int(st.counted), "kept": int(st.kept), "applies": int(st.applies)}
 
 
-class Tonemap:
+class Tonemap(_Handle):
     """The tone mapper of include/rtmi_tonemap.h for nx x ny images on `device`: apply() meters the image's
     log-luminance histogram, adapts the exposure over the applies (exposure="auto"; "manual": 2^ev), applies the curve
     `op` ("clamp", "reinhard" with the white point `white`, "aces") and the transfer function `oetf` ("gamma2": the
@@ -1891,25 +1883,19 @@ class Tonemap:
     mean leaves out below and keeps up to, speed: the adaptation's rates (up, down) per second, adapt_range: the bounds of
     the adapted value (None: log2_range).  close() frees its device memory; Host.free_all() closes what is still open.
     Usable as a context manager.  ValueError for an unknown name, HostError for what rtmi_tonemap_create refuses."""
+    _closed = "tone mapper"
 
     def __init__(self, nx, ny, device=0, op="aces", oetf="srgb", exposure="auto", ev=0.0, white=float("inf"), key=0.18,
                  log2_range=(-12, 12), percentiles=(0.10, 0.95), speed=(3.0, 1.0), adapt_range=None):
         self.lib = abi.load_rtmi()
-        self.nx, self.ny, self.device, self.h = int(nx), int(ny), device, None
+        self.nx, self.ny, self.device = int(nx), int(ny), device
         p = _tonemap_params(op, oetf, exposure, ev, white, key, log2_range, percentiles, speed, adapt_range)
         h = C.c_void_p()
         self._check(self.lib.rtmi_tonemap_create(device, self.nx, self.ny, C.byref(p), C.byref(h)), "rtmi_tonemap_create")
-        self.h = h
-        _tonemaps.append(self)
+        self._opened(h, _tonemaps)
 
-    def _check(self, rc, what):
-        if rc != 0:
-            raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, self.lib.rtmi_last_error().decode()))
-
-    def _handle(self):
-        if not self.h:
-            raise HostError("the tone mapper is closed")
-        return self.h
+    def _destroy(self, h):
+        self.lib.rtmi_tonemap_destroy(h)
 
     def apply(self, linear, dt=0.0, display=False, sync=None):
         """One image: linear is float32 [ny,nx,3], row 0 the top row; dt the seconds since the previous apply.
@@ -1923,10 +1909,7 @@ class Tonemap:
         want = (self.ny, self.nx, 3)
         if isinstance(linear, np.ndarray) or not hasattr(linear, "data_ptr"):
             a = np.asarray(linear)
-            if a.shape != want:
-                raise ValueError("linear must have the shape %r, not %r" % (want, a.shape))
-            if a.dtype != np.float32:
-                raise ValueError("linear must be float32, not %s" % a.dtype)
+            _check_plane("linear", a, want)
             a = np.ascontiguousarray(a)
             out = {"rgb8": np.zeros(want, np.uint8)}
             if display:
@@ -1939,10 +1922,7 @@ class Tonemap:
             return out
         import torch
 
-        if tuple(linear.shape) != want:
-            raise ValueError("linear must have the shape %r, not %r" % (want, tuple(linear.shape)))
-        if linear.dtype != torch.float32:
-            raise ValueError("linear must be float32, not %s" % linear.dtype)
+        _check_plane("linear", linear, want, torch.float32)
         if not linear.is_cuda or linear.device.index != self.device:
             raise ValueError("linear must be on the handle's device (cuda:%d), not %s" % (self.device, linear.device))
         if not linear.is_contiguous():
@@ -1965,20 +1945,6 @@ class Tonemap:
     def reset(self):
         """The next apply is a first apply: it adopts the metered value instead of adapting toward it."""
         self._check(self.lib.rtmi_tonemap_reset(self._handle()), "rtmi_tonemap_reset")
-
-    def close(self):
-        if self.h:
-            h, self.h = self.h, None
-            if self in _tonemaps:
-                _tonemaps.remove(self)
-            self.lib.rtmi_tonemap_destroy(h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def tonemap(linear, device=0, display=False, **kw):
@@ -2022,10 +1988,7 @@ def upscale(linear_lo, albedo_lo, normal_lo, depth_lo, albedo, normal, depth, de
         f32 = np.float32
     for n, a in planes.items():
         want = ((ly, lx) if n.endswith("_lo") else (ny, nx)) + (() if n.startswith("depth") else (3,))
-        if tuple(a.shape) != want:
-            raise ValueError("%s must have the shape %r, not %r" % (n, want, tuple(a.shape)))
-        if a.dtype != f32:
-            raise ValueError("%s must be float32, not %s" % (n, a.dtype))
+        _check_plane(n, a, want, f32)
         if on_device:
             if not a.is_cuda or a.device != dev:
                 raise ValueError("%s must be on the device of depth (%s), not %s" % (n, dev, a.device))
@@ -2047,8 +2010,7 @@ def upscale(linear_lo, albedo_lo, normal_lo, depth_lo, albedo, normal, depth, de
         i = abi.UpscaleIn(*[planes[n].ctypes.data for n in names])
         o = abi.UpscaleOut(out["linear"].ctypes.data, out["rgb8"].ctypes.data, out["cls"].ctypes.data)
         rc, what = lib.rtmi_upscale(device, lx, ly, nx, ny, C.byref(p), C.byref(i), C.byref(o)), "rtmi_upscale"
-    if rc != 0:
-        raise {2: Unsupported}.get(rc, HostError)("%s failed (%d): %s" % (what, rc, lib.rtmi_last_error().decode()))
+    _rtmi_check(lib, rc, what)
     return out
 
 

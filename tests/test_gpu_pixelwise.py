@@ -157,6 +157,18 @@ def test_step_kernel_is_the_restatement(entries):
 
 
 @pytest.mark.gpu
+def test_step_kernel_on_one_pixel():
+    """The smallest call: one pixel, one entry, so every part of the probe's allocation is shorter than its alignment."""
+    x = np.array([[[0.5, 0.25, 0.125], [0.75, 0.25, 0.5], [0.25, 0.25, 0.25]]], np.float32)  # [entry][sample][channel]
+    blank = np.full((9, 1), -7.25)
+    for decide in (0, 1):
+        _, got = _check_step("one pixel, decide %d" % decide, 1, [0], None, x, blank, 0, decide, 24, 0.05, 0.1, _sentinel_planes(1))
+    assert got["spp"].tolist() == [3] and got["active"].tolist() == [1]  # the first channel's error is above the tolerance
+    carried, _ = ref.step([0], None, x[:, :2], blank, 1, 0, False, 99, 0, 0, {})
+    _check_step("one pixel, carried", 1, [0], 1, x[:, 2:], carried, 2, 1, 3, 0.05, 0.1, _sentinel_planes(1))
+
+
+@pytest.mark.gpu
 def test_step_kernel_special_values_and_lists():
     n = 100
     rng, lst, _ = _crafted(70, n, 7)
