@@ -133,7 +133,6 @@ class Stats(C.Structure):
                 ("tiles", C.c_uint32), ("chunks", C.c_uint32), ("blocks", C.c_uint32), ("kernel", C.c_uint32)]
 
 
-# every entry point include/rtmi.h declares (tests check that the library exports them all)
 class SceneF64(C.Structure):
     """rtmi_scene_f64 (include/rtmi_f64.h): the double planes of the f64 render mode."""
     _fields_ = [("n_items", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_xforms", C.c_uint32),
@@ -154,26 +153,10 @@ class CameraF64(C.Structure):
 
 SAMPLE_SLOT_BYTES_F64 = 24  # RTMI_SAMPLE_SLOT_BYTES_F64
 
-RTMI_SYMBOLS = ["rtmi_device_count", "rtmi_last_error", "rtmi_build_hash", "rtmi_scene_create", "rtmi_scene_destroy", "rtmi_release_cached", "rtmi_local_tiles",
-                "rtmi_render_prepare", "rtmi_render_device", "rtmi_scene_status", "rtmi_render", "rtmi_render_multi", "rtmi_multi_create",
-                "rtmi_multi_prepare", "rtmi_multi_render", "rtmi_multi_destroy", "rtmi_multi_collective", "rtmi_partial_image", "rtmi_untile",
-                "rtmi_ppm_p3", "rtmi_write_ppm", "rtmi_probe_math", "rtmi_probe_philox", "rtmi_probe_xform",
-                "rtmi_probe_geom"]
-
-# the functions of include/rtmi_f64.h (the f64 render mode), kept apart from those of include/rtmi.h
-RTMI_F64_SYMBOLS = ["rtmi_scene_attach_f64", "rtmi_render_f64", "rtmi_probe_math_f64"]
-
 
 class Adaptive(C.Structure):
     """rtmi_adaptive (include/rtmi_adaptive.h): the noise target of an adaptive render."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("abs_tol", C.c_double), ("rel_tol", C.c_double)]
-
-
-# the functions of include/rtmi_adaptive.h (adaptive sampling), kept apart from those of include/rtmi.h
-RTMI_ADAPTIVE_SYMBOLS = ["rtmi_render_adaptive"]
-
-# the functions of include/rtmi_features.h (first-hit features for denoisers), kept apart from those of include/rtmi.h
-RTMI_FEATURES_SYMBOLS = ["rtmi_render_features"]
 
 
 class DenoiseParams(C.Structure):
@@ -182,18 +165,10 @@ class DenoiseParams(C.Structure):
                 ("eps_l", C.c_float), ("eps_z", C.c_float), ("albedo_min", C.c_float), ("flags", C.c_uint32)]
 
 
-# the functions of include/rtmi_denoise.h (the a-trous denoiser), kept apart from those of include/rtmi.h
-RTMI_DENOISE_SYMBOLS = ["rtmi_denoise", "rtmi_probe_expf"]
-
-
 class Light(C.Structure):
     """rtmi_light (include/rtmi_nee.h): one eligible light occurrence of a scene description (48 bytes)."""
     _fields_ = [("item", C.c_int32), ("prim", C.c_int32), ("kind", C.c_int32), ("material", C.c_int32),
                 ("area", C.c_double), ("weight", C.c_double), ("select_p", C.c_double), ("cdf", C.c_double)]
-
-
-# the functions of include/rtmi_nee.h (next-event estimation), kept apart from those of include/rtmi.h
-RTMI_NEE_SYMBOLS = ["rtmi_lights_from_desc", "rtmi_scene_attach_lights", "rtmi_render_nee"]
 
 
 class LightNode(C.Structure):
@@ -209,10 +184,6 @@ class LightPath(C.Structure):
 RTMI_LIGHT_TREE_LEAF = 0x80000000
 RTMI_LIGHT_TREE_PROBE_PICK, RTMI_LIGHT_TREE_PROBE_PMF = 0, 1
 
-# the functions of include/rtmi_light_tree.h (the light tree), kept apart from those of the other headers
-RTMI_LIGHT_TREE_SYMBOLS = ["rtmi_light_tree_from_desc", "rtmi_light_tree_pick", "rtmi_light_tree_pmf",
-                           "rtmi_scene_attach_light_tree", "rtmi_probe_light_tree"]
-
 
 class EnvMap(C.Structure):
     """rtmi_env_map (include/rtmi_env.h): an environment map, height * width * 3 floats, row 0 the top row (16 bytes)."""
@@ -227,13 +198,6 @@ class EnvRender(C.Structure):
 RTMI_ENV_PROBE_LOOKUP, RTMI_ENV_PROBE_SAMPLE = 0, 1
 RTMI_ENV_MAX_SIDE, RTMI_ENV_MAX_TEXELS = 16384, 1 << 25
 
-# the functions of include/rtmi_env.h (environment lighting), kept apart from those of the other headers
-RTMI_ENV_SYMBOLS = ["rtmi_env_tables", "rtmi_scene_attach_env", "rtmi_render_env", "rtmi_probe_env"]
-
-# the functions of include/rtmi_adaptive_nee.h (adaptive sampling with NEE or environment lighting), kept apart from those
-# of the other headers
-RTMI_ADAPTIVE_NEE_SYMBOLS = ["rtmi_render_adaptive_env", "rtmi_render_adaptive_nee"]
-
 
 class Roulette(C.Structure):
     """rtmi_roulette (include/rtmi_roulette.h): the options of the Russian-roulette entries (16 bytes)."""
@@ -244,10 +208,6 @@ RTMI_ROULETTE_PLAIN, RTMI_ROULETTE_NEE, RTMI_ROULETTE_ENV, RTMI_ROULETTE_ENV_NEE
 ROULETTE_ESTIMATORS = {"plain": RTMI_ROULETTE_PLAIN, "nee": RTMI_ROULETTE_NEE, "env": RTMI_ROULETTE_ENV,
                        "env_nee": RTMI_ROULETTE_ENV_NEE}
 
-# the functions of include/rtmi_roulette.h (Russian-roulette path termination), kept apart from those of the other headers
-RTMI_ROULETTE_SYMBOLS = ["rtmi_render_adaptive_roulette", "rtmi_render_roulette"]
-
-
 
 class SessionOpts(C.Structure):
     """rtmi_session_opts (include/rtmi_session.h): what a render session traces and on which lattice (32 bytes)."""
@@ -257,10 +217,6 @@ class SessionOpts(C.Structure):
 
 RTMI_SESSION_BLOB_VERSION, RTMI_SESSION_BLOB_HEADER, RTMI_SESSION_BLOB_IDENTITY = 1, 216, 196
 
-# the functions of include/rtmi_session.h (render sessions), kept apart from those of the other headers
-SESSION_SYMBOLS = ["rtmi_session_create", "rtmi_session_destroy", "rtmi_session_export", "rtmi_session_image",
-                   "rtmi_session_import", "rtmi_session_merge", "rtmi_session_refine", "rtmi_session_render",
-                   "rtmi_session_spp"]
 
 class Ray(C.Structure):
     """rtmi_ray (include/rtmi_query.h): one query ray (32 bytes)."""
@@ -278,19 +234,12 @@ class QueryParams(C.Structure):
     _fields_ = [("n", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64), ("first_ray", C.c_uint64)]
 
 
-# the functions of include/rtmi_query.h (ray queries), kept apart from those of the other headers
-RTMI_QUERY_SYMBOLS = ["rtmi_occluded", "rtmi_occluded_device", "rtmi_scene_attach_flips", "rtmi_trace", "rtmi_trace_device"]
-
-
 class RadianceParams(C.Structure):
     """rtmi_radiance_params (include/rtmi_radiance.h): one call's batch, estimator and Philox indices (56 bytes)."""
     _fields_ = [("n", C.c_uint32), ("spp", C.c_uint32), ("estimator", C.c_uint32), ("flags", C.c_uint32),
                 ("max_depth", C.c_uint32), ("t_min", C.c_float), ("seed", C.c_uint64), ("first_ray", C.c_uint64),
                 ("first_sample", C.c_uint32), ("stream_skip", C.c_uint32), ("env_select_p", C.c_float)]
 
-
-# the functions of include/rtmi_radiance.h (radiance queries), kept apart from those of the other headers
-RTMI_RADIANCE_SYMBOLS = ["rtmi_radiance", "rtmi_radiance_device"]
 
 RTMI_GATHER_COSINE = 0  # include/rtmi_gather.h: irradiance about a normal
 RTMI_GATHER_SPHERE = 1  # ... mean radiance over the sphere and its 9 SH coefficients
@@ -306,9 +255,6 @@ class GatherParams(C.Structure):
                 ("first_sample", C.c_uint32), ("slab_points", C.c_uint32), ("env_select_p", C.c_float)]
 
 
-# the functions of include/rtmi_gather.h (hemisphere gathers), kept apart from those of the other headers
-RTMI_GATHER_SYMBOLS = ["rtmi_gather", "rtmi_gather_device", "rtmi_gather_directions"]
-
 RTMI_TEMPORAL_NO_DEMODULATE = 1  # include/rtmi_temporal.h: accumulate the colour itself, not colour / albedo
 
 
@@ -317,9 +263,6 @@ class TemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_uint32), ("alpha_min", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float),
                 ("albedo_min", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
-
-# the functions of include/rtmi_temporal.h (temporal accumulation), kept apart from those of the other headers
-RTMI_TEMPORAL_SYMBOLS = ["rtmi_temporal_create", "rtmi_temporal_destroy", "rtmi_temporal_push", "rtmi_temporal_reset"]
 
 RTMI_FRAME_NO_TEMPORAL = 1  # include/rtmi_frame.h: no history, the chain render, features, filter
 RTMI_FRAME_NO_FILTER = 2  # the filter runs with 0 iterations: the accumulated image and its quantisation
@@ -336,10 +279,6 @@ class FrameOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("linear", "rgb8", "noisy_linear", "noisy_stderr", "albedo", "normal", "depth", "hits",
                                           "accum_linear", "accum_stderr", "history", "motion")]
 
-
-# the functions of include/rtmi_frame.h (the frame pipeline), kept apart from those of the other headers
-RTMI_FRAME_SYMBOLS = ["rtmi_frame_create", "rtmi_frame_destroy", "rtmi_frame_render", "rtmi_frame_render_device",
-                      "rtmi_frame_reset", "rtmi_probe_frame_untile"]
 
 RTMI_TONEMAP_CLAMP, RTMI_TONEMAP_REINHARD, RTMI_TONEMAP_ACES = 0, 1, 2  # include/rtmi_tonemap.h: op
 RTMI_TONEMAP_GAMMA2, RTMI_TONEMAP_SRGB = 0, 1  # ... oetf: the reference's sqrt, the sRGB curve
@@ -362,10 +301,6 @@ class TonemapState(C.Structure):
     _fields_ = [("exposure", C.c_float), ("adapted_log2", C.c_float), ("metered_log2", C.c_float), ("counted", C.c_uint32),
                 ("kept", C.c_uint32), ("applies", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
-
-# the functions of include/rtmi_tonemap.h (tone mapping), kept apart from those of the other headers
-RTMI_TONEMAP_SYMBOLS = ["rtmi_probe_tonemap_histogram", "rtmi_tonemap_apply", "rtmi_tonemap_apply_device", "rtmi_tonemap_create",
-                        "rtmi_tonemap_destroy", "rtmi_tonemap_reset"]
 
 RTMI_UPSCALE_BACKGROUND, RTMI_UPSCALE_GUIDED, RTMI_UPSCALE_NEAREST, RTMI_UPSCALE_MISMATCH = 0, 1, 2, 3  # include/rtmi_upscale.h: cls
 
@@ -397,32 +332,16 @@ class UpscalerOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("linear", "rgb8", "cls", "albedo", "normal", "depth")] + [("low", FrameOut)]
 
 
-# the functions of include/rtmi_upscale.h (guided upscaling), kept apart from those of the other headers
-RTMI_UPSCALE_SYMBOLS = ["rtmi_upscale", "rtmi_upscale_device", "rtmi_upscaler_create", "rtmi_upscaler_destroy", "rtmi_upscaler_render",
-                        "rtmi_upscaler_render_device", "rtmi_upscaler_reset"]
-
-
 class SparseParams(C.Structure):
     """rtmi_sparse_params (include/rtmi_sparse.h): a list's length or capacity, samples and estimator (32 bytes)."""
     _fields_ = [("n", C.c_uint32), ("ns", C.c_uint32), ("first_sample", C.c_uint32), ("estimator", C.c_uint32),
                 ("env_select_p", C.c_float), ("reserved", C.c_uint32 * 3)]
 
 
-# the functions of include/rtmi_sparse.h (sparse renders), kept apart from those of the other headers
-RTMI_SPARSE_SYMBOLS = ["rtmi_sparse_patch_device", "rtmi_sparse_refine", "rtmi_sparse_refine_device", "rtmi_sparse_render",
-                       "rtmi_sparse_render_device", "rtmi_sparse_scratch_bytes", "rtmi_sparse_select_device"]
-
-
 class PixelwiseOpts(C.Structure):
     """rtmi_pixelwise_opts (include/rtmi_pixelwise.h): the steps, estimator and tolerances of a per-pixel adaptive render (48 bytes)."""
     _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("estimator", C.c_uint32), ("pass_spp", C.c_uint32),
                 ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("env_select_p", C.c_float), ("reserved", C.c_uint32 * 3)]
-
-
-# the functions of include/rtmi_pixelwise.h (per-pixel adaptive sampling), kept apart from those of the other headers
-RTMI_PIXELWISE_SYMBOLS = ["rtmi_pixelwise_scratch_bytes", "rtmi_pixelwise_steps", "rtmi_probe_pixelwise_step", "rtmi_render_pixelwise",
-                          "rtmi_render_pixelwise_device"]
-
 
 
 class WindowOpts(C.Structure):
@@ -434,9 +353,197 @@ class WindowOpts(C.Structure):
 
 
 RTMI_WINDOW_MAX_RADIUS = 16
-# the functions of include/rtmi_window.h (windowed adaptive sampling), kept apart from those of the other headers
-RTMI_WINDOW_SYMBOLS = ["rtmi_probe_window_spread", "rtmi_render_window", "rtmi_render_window_device", "rtmi_window_scratch_bytes",
-                       "rtmi_window_spread_device", "rtmi_window_steps"]
+
+
+# ---- the C ABI of librtmi.so: per header of include/, name -> (restype, argtypes) ---------------------------------------------
+# load_rtmi() applies these tables and the *_SYMBOLS lists below are their keys, so a function cannot be listed without a
+# signature.  tests/test_abi_signatures.py compares every entry with the prototype its header declares.
+def _tables():
+    vp, i, u32, u64, d, sz, P = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double, C.c_size_t, C.POINTER
+    cam, rp, st, desc = P(Camera), P(RenderParams), P(Stats), P(SceneDesc)
+    query = [vp, P(QueryParams), vp, vp, vp]
+    frame = [vp, cam, u32, u64]
+    upscale = [i, u32, u32, u32, u32, P(UpscaleParams), P(UpscaleIn), P(UpscaleOut)]
+    sparse = [vp, rp, cam, P(SparseParams)]
+    return {
+        "rtmi.h": {
+            "rtmi_device_count": (i, []),
+            "rtmi_last_error": (C.c_char_p, []),
+            "rtmi_build_hash": (C.c_char_p, []),
+            "rtmi_scene_create": (i, [desc, i, P(vp)]),
+            "rtmi_scene_destroy": (None, [vp]),
+            "rtmi_release_cached": (None, []),
+            "rtmi_local_tiles": (u32, [rp]),
+            "rtmi_render_prepare": (i, [vp, rp]),
+            "rtmi_render_device": (i, [vp, cam, rp, vp, vp, st]),
+            "rtmi_scene_status": (i, [vp, P(u32)]),
+            "rtmi_render": (i, [vp, cam, rp, vp, vp, vp, st]),
+            "rtmi_render_multi": (i, [desc, P(i), u32, cam, rp, vp, vp, st]),
+            "rtmi_multi_create": (i, [desc, P(i), u32, P(vp)]),
+            "rtmi_multi_prepare": (i, [vp, rp]),
+            "rtmi_multi_render": (i, [vp, cam, rp, vp, vp, st]),
+            "rtmi_multi_destroy": (None, [vp]),
+            "rtmi_multi_collective": (i, [vp]),
+            "rtmi_partial_image": (i, [vp, rp, vp, vp, P(u32)]),
+            "rtmi_untile": (i, [rp, vp, vp, vp]),
+            "rtmi_ppm_p3": (sz, [u32, u32, vp, vp, sz]),
+            "rtmi_write_ppm": (i, [C.c_char_p, u32, u32, vp, i]),
+            "rtmi_probe_math": (i, [i, vp, vp, vp, u32]),
+            "rtmi_probe_philox": (i, [vp, vp, vp, u32]),
+            "rtmi_probe_xform": (i, [P(Xform), u32, vp, vp, vp, u32]),
+            "rtmi_probe_geom": (i, [i, vp, vp, vp, u32, vp, u32, vp, vp, u32]),
+        },
+        "rtmi_math.h": {},  # inline helpers only
+        "rtmi_f64.h": {
+            "rtmi_scene_attach_f64": (i, [vp, P(SceneF64)]),
+            "rtmi_render_f64": (i, [vp, P(CameraF64), rp, d, vp, vp, vp, st]),
+            "rtmi_probe_math_f64": (i, [i, vp, vp, vp, u32]),
+        },
+        "rtmi_adaptive.h": {
+            "rtmi_render_adaptive": (i, [vp, cam, rp, P(Adaptive), vp, vp, vp, vp, st]),
+        },
+        "rtmi_features.h": {
+            "rtmi_render_features": (i, [vp, cam, rp, vp, vp, vp, vp, vp, st]),
+        },
+        "rtmi_denoise.h": {
+            "rtmi_denoise": (i, [i, u32, u32, P(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]),
+            "rtmi_probe_expf": (i, [i, vp, vp, u32]),
+        },
+        "rtmi_nee.h": {
+            "rtmi_lights_from_desc": (i, [desc, P(Light), u32, P(u32)]),
+            "rtmi_scene_attach_lights": (i, [vp, desc]),
+            "rtmi_render_nee": (i, [vp, cam, rp, vp, vp, vp, vp, st]),
+        },
+        "rtmi_light_coop.h": {},  # a flag of the NEE / environment entries
+        "rtmi_light_tree.h": {
+            "rtmi_light_tree_from_desc": (i, [desc, P(LightNode), u32, P(u32), P(LightPath)]),
+            "rtmi_light_tree_pick": (i, [vp, u32, vp, vp, u32, vp, vp]),
+            "rtmi_light_tree_pmf": (i, [vp, u32, vp, vp, vp, u32, vp]),
+            "rtmi_scene_attach_light_tree": (i, [vp, desc]),
+            "rtmi_probe_light_tree": (i, [vp, i, vp, vp, u32, vp, vp]),
+        },
+        "rtmi_env.h": {
+            "rtmi_env_tables": (i, [P(EnvMap), vp, vp, vp, vp, P(d)]),
+            "rtmi_scene_attach_env": (i, [vp, P(EnvMap)]),
+            "rtmi_render_env": (i, [vp, cam, rp, P(EnvRender), vp, vp, vp, vp, st]),
+            "rtmi_probe_env": (i, [vp, i, vp, vp, u32]),
+        },
+        "rtmi_adaptive_nee.h": {
+            "rtmi_render_adaptive_env": (i, [vp, cam, rp, P(EnvRender), P(Adaptive), vp, vp, vp, vp, st]),
+            "rtmi_render_adaptive_nee": (i, [vp, cam, rp, P(Adaptive), vp, vp, vp, vp, st]),
+        },
+        "rtmi_roulette.h": {
+            "rtmi_render_adaptive_roulette": (i, [vp, cam, rp, P(Roulette), P(Adaptive), vp, vp, vp, vp, vp, st]),
+            "rtmi_render_roulette": (i, [vp, cam, rp, P(Roulette), vp, vp, vp, vp, st]),
+        },
+        "rtmi_roulette_coop.h": {},  # a flag of the roulette entries
+        "rtmi_session.h": {
+            "rtmi_session_create": (i, [vp, cam, rp, P(SessionOpts), P(vp)]),
+            "rtmi_session_destroy": (None, [vp]),
+            "rtmi_session_export": (i, [vp, vp, sz, P(sz)]),
+            "rtmi_session_image": (i, [vp, vp, vp, vp, vp, vp]),
+            "rtmi_session_import": (i, [vp, vp, sz]),
+            "rtmi_session_merge": (i, [vp, vp]),
+            "rtmi_session_refine": (i, [vp, d, d, u32, st]),
+            "rtmi_session_render": (i, [vp, u32, st]),
+            "rtmi_session_spp": (i, [vp, P(u32), P(u32)]),
+        },
+        "rtmi_query.h": {
+            "rtmi_occluded": (i, query + [P(d)]),
+            "rtmi_occluded_device": (i, query + [vp]),
+            "rtmi_scene_attach_flips": (i, [vp, vp, u32, vp, u32]),
+            "rtmi_trace": (i, query + [P(d)]),
+            "rtmi_trace_device": (i, query + [vp]),
+        },
+        "rtmi_radiance.h": {
+            "rtmi_radiance": (i, [vp, P(RadianceParams), vp, vp, vp, vp, vp, P(d)]),
+            "rtmi_radiance_device": (i, [vp, P(RadianceParams), vp, vp, vp, vp, vp, vp]),
+        },
+        "rtmi_gather.h": {
+            "rtmi_gather": (i, [vp, P(GatherParams), vp, vp, vp, vp, vp, vp, P(d)]),
+            "rtmi_gather_device": (i, [vp, P(GatherParams), vp, vp, vp, vp, vp, vp, vp, u64, vp]),
+            "rtmi_gather_directions": (i, [P(GatherParams), vp, u32, vp]),
+        },
+        "rtmi_temporal.h": {
+            "rtmi_temporal_create": (i, [i, u32, u32, P(TemporalParams), P(vp)]),
+            "rtmi_temporal_destroy": (None, [vp]),
+            "rtmi_temporal_push": (i, [vp, cam, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+            "rtmi_temporal_reset": (i, [vp]),
+        },
+        "rtmi_frame.h": {
+            "rtmi_frame_create": (i, [vp, rp, P(FrameOpts), P(vp)]),
+            "rtmi_frame_destroy": (None, [vp]),
+            "rtmi_frame_render": (i, frame + [P(FrameOut), st]),
+            "rtmi_frame_render_device": (i, frame + [P(FrameOut), st]),
+            "rtmi_frame_reset": (i, [vp]),
+            "rtmi_probe_frame_untile": (i, [i, u32, u32, vp, vp, vp, vp, P(u32)]),
+        },
+        "rtmi_tonemap.h": {
+            "rtmi_probe_tonemap_histogram": (i, [i, u32, u32, P(TonemapParams), vp, vp]),
+            "rtmi_tonemap_apply": (i, [vp, vp, C.c_float, vp, vp, P(TonemapState)]),
+            "rtmi_tonemap_apply_device": (i, [vp, vp, C.c_float, vp, vp, vp, vp]),
+            "rtmi_tonemap_create": (i, [i, u32, u32, P(TonemapParams), P(vp)]),
+            "rtmi_tonemap_destroy": (None, [vp]),
+            "rtmi_tonemap_reset": (i, [vp]),
+        },
+        "rtmi_upscale.h": {
+            "rtmi_upscale": (i, upscale),
+            "rtmi_upscale_device": (i, upscale + [vp]),
+            "rtmi_upscaler_create": (i, [vp, rp, P(UpscalerOpts), P(vp)]),
+            "rtmi_upscaler_destroy": (None, [vp]),
+            "rtmi_upscaler_render": (i, frame + [P(UpscalerOut), st]),
+            "rtmi_upscaler_render_device": (i, frame + [P(UpscalerOut), st]),
+            "rtmi_upscaler_reset": (i, [vp]),
+        },
+        "rtmi_sparse.h": {
+            "rtmi_sparse_patch_device": (i, [i, u32, vp, vp, u32, vp, vp, vp, vp, u32, vp]),
+            "rtmi_sparse_refine": (i, sparse + [u32, u32, vp, vp, vp, vp, vp]),
+            "rtmi_sparse_refine_device": (i, sparse + [u32, u32, vp, vp, vp, vp, vp, u64, vp, vp]),
+            "rtmi_sparse_render": (i, sparse + [vp, vp, vp, vp, P(d)]),
+            "rtmi_sparse_render_device": (i, sparse + [vp] * 7),
+            "rtmi_sparse_scratch_bytes": (u64, [u64, u32, u32]),
+            "rtmi_sparse_select_device": (i, [i, u32, vp, u32, u32, vp, vp, vp, vp]),
+        },
+        "rtmi_pixelwise.h": {
+            "rtmi_pixelwise_scratch_bytes": (u64, [u64, u32, u32]),
+            "rtmi_pixelwise_steps": (u32, [u32] * 3),
+            "rtmi_probe_pixelwise_step": (i, [i, u32, u32, vp, vp, vp, vp, u32, u32, u32, u32, d, d, vp, vp, vp, vp, vp]),
+            "rtmi_render_pixelwise": (i, [vp, cam, rp, P(PixelwiseOpts)] + [vp] * 5 + [st]),
+            "rtmi_render_pixelwise_device": (i, [vp, rp, cam, P(PixelwiseOpts)] + [vp] * 6 + [u64, vp]),
+        },
+        "rtmi_window.h": {
+            "rtmi_probe_window_spread": (i, [i, u32, u32, u32, vp, vp]),
+            "rtmi_render_window": (i, [vp, cam, rp, P(WindowOpts)] + [vp] * 5 + [st]),
+            "rtmi_render_window_device": (i, [vp, rp, cam, P(WindowOpts)] + [vp] * 6 + [u64, vp]),
+            "rtmi_window_scratch_bytes": (u64, [u64, u32, u32]),
+            "rtmi_window_spread_device": (i, [vp, vp, u32, u32, u32, vp]),
+            "rtmi_window_steps": (u32, [u32] * 3),
+        },
+    }
+
+
+FAMILIES = _tables()  # header file name -> {function: (restype, argtypes)}
+RTMI_SYMBOLS = list(FAMILIES["rtmi.h"])
+RTMI_F64_SYMBOLS = list(FAMILIES["rtmi_f64.h"])
+RTMI_ADAPTIVE_SYMBOLS = list(FAMILIES["rtmi_adaptive.h"])
+RTMI_FEATURES_SYMBOLS = list(FAMILIES["rtmi_features.h"])
+RTMI_DENOISE_SYMBOLS = list(FAMILIES["rtmi_denoise.h"])
+RTMI_NEE_SYMBOLS = list(FAMILIES["rtmi_nee.h"])
+RTMI_LIGHT_TREE_SYMBOLS = list(FAMILIES["rtmi_light_tree.h"])
+RTMI_ENV_SYMBOLS = list(FAMILIES["rtmi_env.h"])
+RTMI_ADAPTIVE_NEE_SYMBOLS = list(FAMILIES["rtmi_adaptive_nee.h"])
+RTMI_ROULETTE_SYMBOLS = list(FAMILIES["rtmi_roulette.h"])
+SESSION_SYMBOLS = list(FAMILIES["rtmi_session.h"])
+RTMI_QUERY_SYMBOLS = list(FAMILIES["rtmi_query.h"])
+RTMI_RADIANCE_SYMBOLS = list(FAMILIES["rtmi_radiance.h"])
+RTMI_GATHER_SYMBOLS = list(FAMILIES["rtmi_gather.h"])
+RTMI_TEMPORAL_SYMBOLS = list(FAMILIES["rtmi_temporal.h"])
+RTMI_FRAME_SYMBOLS = list(FAMILIES["rtmi_frame.h"])
+RTMI_TONEMAP_SYMBOLS = list(FAMILIES["rtmi_tonemap.h"])
+RTMI_UPSCALE_SYMBOLS = list(FAMILIES["rtmi_upscale.h"])
+RTMI_SPARSE_SYMBOLS = list(FAMILIES["rtmi_sparse.h"])
+RTMI_PIXELWISE_SYMBOLS = list(FAMILIES["rtmi_pixelwise.h"])
+RTMI_WINDOW_SYMBOLS = list(FAMILIES["rtmi_window.h"])
 
 _rtmi = None
 _host = None
@@ -451,230 +558,11 @@ def load_rtmi():
     if not os.path.exists(path):
         _build.build_rtmi()
     lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-    vp = C.c_void_p
-    lib.rtmi_device_count.restype = C.c_int
-    lib.rtmi_last_error.restype = C.c_char_p
-    lib.rtmi_build_hash.restype = C.c_char_p
-    lib.rtmi_scene_create.restype = C.c_int
-    lib.rtmi_scene_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(vp)]
-    lib.rtmi_scene_destroy.restype = None
-    lib.rtmi_scene_destroy.argtypes = [vp]
-    lib.rtmi_release_cached.restype = None
-    lib.rtmi_release_cached.argtypes = []
-    lib.rtmi_local_tiles.restype = C.c_uint32
-    lib.rtmi_local_tiles.argtypes = [C.POINTER(RenderParams)]
-    lib.rtmi_render_device.restype = C.c_int
-    lib.rtmi_render_device.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]
-    lib.rtmi_scene_status.restype = C.c_int
-    lib.rtmi_scene_status.argtypes = [vp, C.POINTER(C.c_uint32)]
-    lib.rtmi_render_prepare.restype = C.c_int
-    lib.rtmi_render_prepare.argtypes = [vp, C.POINTER(RenderParams)]
-    lib.rtmi_render_multi.restype = C.c_int
-    lib.rtmi_render_multi.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.POINTER(Camera), C.POINTER(RenderParams),
-                                      vp, vp, C.POINTER(Stats)]
-    lib.rtmi_multi_create.restype = C.c_int
-    lib.rtmi_multi_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]
-    lib.rtmi_multi_prepare.restype = C.c_int
-    lib.rtmi_multi_prepare.argtypes = [vp, C.POINTER(RenderParams)]
-    lib.rtmi_multi_render.restype = C.c_int
-    lib.rtmi_multi_render.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, C.POINTER(Stats)]
-    lib.rtmi_multi_destroy.restype = None
-    lib.rtmi_multi_destroy.argtypes = [vp]
-    lib.rtmi_multi_collective.restype = C.c_int
-    lib.rtmi_multi_collective.argtypes = [vp]
-    lib.rtmi_render.restype = C.c_int
-    lib.rtmi_render.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, C.POINTER(Stats)]
-    lib.rtmi_partial_image.restype = C.c_int
-    lib.rtmi_partial_image.argtypes = [vp, C.POINTER(RenderParams), vp, vp, C.POINTER(C.c_uint32)]
-    lib.rtmi_untile.restype = C.c_int
-    lib.rtmi_untile.argtypes = [C.POINTER(RenderParams), vp, vp, vp]
-    lib.rtmi_ppm_p3.restype = C.c_size_t
-    lib.rtmi_ppm_p3.argtypes = [C.c_uint32, C.c_uint32, vp, vp, C.c_size_t]
-    lib.rtmi_write_ppm.restype = C.c_int
-    lib.rtmi_write_ppm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, vp, C.c_int]
-    lib.rtmi_probe_math.restype = C.c_int
-    lib.rtmi_probe_math.argtypes = [C.c_int, vp, vp, vp, C.c_uint32]
-    lib.rtmi_probe_philox.restype = C.c_int
-    lib.rtmi_probe_philox.argtypes = [vp, vp, vp, C.c_uint32]
-    lib.rtmi_probe_xform.restype = C.c_int
-    lib.rtmi_probe_xform.argtypes = [C.POINTER(Xform), C.c_uint32, vp, vp, vp, C.c_uint32]
-    lib.rtmi_probe_geom.restype = C.c_int
-    lib.rtmi_probe_geom.argtypes = [C.c_int, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, C.c_uint32]
-    lib.rtmi_scene_attach_f64.restype = C.c_int
-    lib.rtmi_scene_attach_f64.argtypes = [vp, C.POINTER(SceneF64)]
-    lib.rtmi_render_f64.restype = C.c_int
-    lib.rtmi_render_f64.argtypes = [vp, C.POINTER(CameraF64), C.POINTER(RenderParams), C.c_double, vp, vp, vp, C.POINTER(Stats)]
-    lib.rtmi_probe_math_f64.restype = C.c_int
-    lib.rtmi_probe_math_f64.argtypes = [C.c_int, vp, vp, vp, C.c_uint32]
-    lib.rtmi_render_adaptive.restype = C.c_int
-    lib.rtmi_render_adaptive.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp, vp,
-                                         C.POINTER(Stats)]
-    lib.rtmi_render_features.restype = C.c_int
-    lib.rtmi_render_features.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, vp, C.POINTER(Stats)]
-    lib.rtmi_lights_from_desc.restype = C.c_int
-    lib.rtmi_lights_from_desc.argtypes = [C.POINTER(SceneDesc), C.POINTER(Light), C.c_uint32, C.POINTER(C.c_uint32)]
-    lib.rtmi_scene_attach_lights.restype = C.c_int
-    lib.rtmi_scene_attach_lights.argtypes = [vp, C.POINTER(SceneDesc)]
-    lib.rtmi_render_nee.restype = C.c_int
-    lib.rtmi_render_nee.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), vp, vp, vp, vp, C.POINTER(Stats)]
-    lib.rtmi_light_tree_from_desc.restype = C.c_int
-    lib.rtmi_light_tree_from_desc.argtypes = [C.POINTER(SceneDesc), C.POINTER(LightNode), C.c_uint32, C.POINTER(C.c_uint32),
-                                              C.POINTER(LightPath)]
-    lib.rtmi_light_tree_pick.restype = C.c_int
-    lib.rtmi_light_tree_pick.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
-    lib.rtmi_light_tree_pmf.restype = C.c_int
-    lib.rtmi_light_tree_pmf.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]
-    lib.rtmi_scene_attach_light_tree.restype = C.c_int
-    lib.rtmi_scene_attach_light_tree.argtypes = [vp, C.POINTER(SceneDesc)]
-    lib.rtmi_probe_light_tree.restype = C.c_int
-    lib.rtmi_probe_light_tree.argtypes = [vp, C.c_int, vp, vp, C.c_uint32, vp, vp]
-    lib.rtmi_env_tables.restype = C.c_int
-    lib.rtmi_env_tables.argtypes = [C.POINTER(EnvMap), vp, vp, vp, vp, C.POINTER(C.c_double)]
-    lib.rtmi_scene_attach_env.restype = C.c_int
-    lib.rtmi_scene_attach_env.argtypes = [vp, C.POINTER(EnvMap)]
-    lib.rtmi_render_env.restype = C.c_int
-    lib.rtmi_render_env.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(EnvRender), vp, vp, vp, vp,
-                                    C.POINTER(Stats)]
-    lib.rtmi_probe_env.restype = C.c_int
-    lib.rtmi_probe_env.argtypes = [vp, C.c_int, vp, vp, C.c_uint32]
-    lib.rtmi_render_adaptive_nee.restype = C.c_int
-    lib.rtmi_render_adaptive_nee.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Adaptive), vp, vp, vp,
-                                             vp, C.POINTER(Stats)]
-    lib.rtmi_render_adaptive_env.restype = C.c_int
-    lib.rtmi_render_adaptive_env.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(EnvRender),
-                                             C.POINTER(Adaptive), vp, vp, vp, vp, C.POINTER(Stats)]
-    lib.rtmi_render_roulette.restype = C.c_int
-    lib.rtmi_render_roulette.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Roulette), vp, vp, vp, vp,
-                                         C.POINTER(Stats)]
-    lib.rtmi_render_adaptive_roulette.restype = C.c_int
-    lib.rtmi_render_adaptive_roulette.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Roulette),
-                                                  C.POINTER(Adaptive), vp, vp, vp, vp, vp, C.POINTER(Stats)]
-    lib.rtmi_session_create.restype = C.c_int
-    lib.rtmi_session_create.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(SessionOpts), C.POINTER(vp)]
-    lib.rtmi_session_destroy.restype = None
-    lib.rtmi_session_destroy.argtypes = [vp]
-    lib.rtmi_session_render.restype = C.c_int
-    lib.rtmi_session_render.argtypes = [vp, C.c_uint32, C.POINTER(Stats)]
-    lib.rtmi_session_refine.restype = C.c_int
-    lib.rtmi_session_refine.argtypes = [vp, C.c_double, C.c_double, C.c_uint32, C.POINTER(Stats)]
-    lib.rtmi_session_image.restype = C.c_int
-    lib.rtmi_session_image.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.rtmi_session_export.restype = C.c_int
-    lib.rtmi_session_export.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    lib.rtmi_session_import.restype = C.c_int
-    lib.rtmi_session_import.argtypes = [vp, vp, C.c_size_t]
-    lib.rtmi_session_merge.restype = C.c_int
-    lib.rtmi_session_merge.argtypes = [vp, vp]
-    lib.rtmi_session_spp.restype = C.c_int
-    lib.rtmi_session_spp.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    for name in ("rtmi_trace", "rtmi_occluded"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, C.POINTER(QueryParams), vp, vp, vp, C.POINTER(C.c_double)]
-    lib.rtmi_scene_attach_flips.restype = C.c_int
-    lib.rtmi_scene_attach_flips.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32]
-    for name in ("rtmi_trace_device", "rtmi_occluded_device"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, C.POINTER(QueryParams), vp, vp, vp, vp]
-    lib.rtmi_radiance.restype = C.c_int
-    lib.rtmi_radiance.argtypes = [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
-    lib.rtmi_radiance_device.restype = C.c_int
-    lib.rtmi_radiance_device.argtypes = [vp, C.POINTER(RadianceParams), vp, vp, vp, vp, vp, vp]
-    lib.rtmi_gather.restype = C.c_int
-    lib.rtmi_gather.argtypes = [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
-    lib.rtmi_gather_device.restype = C.c_int
-    lib.rtmi_gather_device.argtypes = [vp, C.POINTER(GatherParams), vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp]
-    lib.rtmi_gather_directions.restype = C.c_int
-    lib.rtmi_gather_directions.argtypes = [C.POINTER(GatherParams), vp, C.c_uint32, vp]
-    lib.rtmi_denoise.restype = C.c_int
-    lib.rtmi_denoise.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp, vp, vp]
-    lib.rtmi_probe_expf.restype = C.c_int
-    lib.rtmi_probe_expf.argtypes = [C.c_int, vp, vp, C.c_uint32]
-    lib.rtmi_temporal_create.restype = C.c_int
-    lib.rtmi_temporal_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TemporalParams), C.POINTER(vp)]
-    lib.rtmi_temporal_push.restype = C.c_int
-    lib.rtmi_temporal_push.argtypes = [vp, C.POINTER(Camera), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.rtmi_temporal_reset.restype = C.c_int
-    lib.rtmi_temporal_reset.argtypes = [vp]
-    lib.rtmi_temporal_destroy.restype = None
-    lib.rtmi_temporal_destroy.argtypes = [vp]
-    lib.rtmi_frame_create.restype = C.c_int
-    lib.rtmi_frame_create.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(FrameOpts), C.POINTER(vp)]
-    for fn in (lib.rtmi_frame_render, lib.rtmi_frame_render_device):
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.POINTER(Camera), C.c_uint32, C.c_uint64, C.POINTER(FrameOut), C.POINTER(Stats)]
-    lib.rtmi_frame_reset.restype = C.c_int
-    lib.rtmi_frame_reset.argtypes = [vp]
-    lib.rtmi_frame_destroy.restype = None
-    lib.rtmi_frame_destroy.argtypes = [vp]
-    lib.rtmi_probe_frame_untile.restype = C.c_int
-    lib.rtmi_probe_frame_untile.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
-    lib.rtmi_tonemap_create.restype = C.c_int
-    lib.rtmi_tonemap_create.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TonemapParams), C.POINTER(vp)]
-    lib.rtmi_tonemap_apply.restype = C.c_int
-    lib.rtmi_tonemap_apply.argtypes = [vp, vp, C.c_float, vp, vp, C.POINTER(TonemapState)]
-    lib.rtmi_tonemap_apply_device.restype = C.c_int
-    lib.rtmi_tonemap_apply_device.argtypes = [vp, vp, C.c_float, vp, vp, vp, vp]
-    lib.rtmi_tonemap_reset.restype = C.c_int
-    lib.rtmi_tonemap_reset.argtypes = [vp]
-    lib.rtmi_tonemap_destroy.restype = None
-    lib.rtmi_tonemap_destroy.argtypes = [vp]
-    lib.rtmi_probe_tonemap_histogram.restype = C.c_int
-    lib.rtmi_probe_tonemap_histogram.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.POINTER(TonemapParams), vp, vp]
-    lib.rtmi_upscale.restype = C.c_int
-    lib.rtmi_upscale.argtypes = [C.c_int] + [C.c_uint32] * 4 + [C.POINTER(UpscaleParams), C.POINTER(UpscaleIn), C.POINTER(UpscaleOut)]
-    lib.rtmi_upscale_device.restype = C.c_int
-    lib.rtmi_upscale_device.argtypes = lib.rtmi_upscale.argtypes + [vp]
-    lib.rtmi_upscaler_create.restype = C.c_int
-    lib.rtmi_upscaler_create.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(UpscalerOpts), C.POINTER(vp)]
-    for fn in (lib.rtmi_upscaler_render, lib.rtmi_upscaler_render_device):
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.POINTER(Camera), C.c_uint32, C.c_uint64, C.POINTER(UpscalerOut), C.POINTER(Stats)]
-    lib.rtmi_upscaler_reset.restype = C.c_int
-    lib.rtmi_upscaler_reset.argtypes = [vp]
-    lib.rtmi_upscaler_destroy.restype = None
-    lib.rtmi_upscaler_destroy.argtypes = [vp]
-    lib.rtmi_sparse_scratch_bytes.restype = C.c_uint64
-    lib.rtmi_sparse_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
-    lib.rtmi_sparse_select_device.restype = C.c_int
-    lib.rtmi_sparse_select_device.argtypes = [C.c_int, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
-    lib.rtmi_sparse_patch_device.restype = C.c_int
-    lib.rtmi_sparse_patch_device.argtypes = [C.c_int, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp]
-    sparse = [vp, C.POINTER(RenderParams), C.POINTER(Camera), C.POINTER(SparseParams)]
-    lib.rtmi_sparse_render.restype = C.c_int
-    lib.rtmi_sparse_render.argtypes = sparse + [vp, vp, vp, vp, C.POINTER(C.c_double)]
-    lib.rtmi_sparse_render_device.restype = C.c_int
-    lib.rtmi_sparse_render_device.argtypes = sparse + [vp] * 7
-    lib.rtmi_sparse_refine_device.restype = C.c_int
-    lib.rtmi_sparse_refine_device.argtypes = sparse + [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
-    lib.rtmi_sparse_refine.restype = C.c_int
-    lib.rtmi_sparse_refine.argtypes = sparse + [C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
-    lib.rtmi_pixelwise_scratch_bytes.restype = C.c_uint64
-    lib.rtmi_pixelwise_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
-    lib.rtmi_pixelwise_steps.restype = C.c_uint32
-    lib.rtmi_pixelwise_steps.argtypes = [C.c_uint32] * 3
-    lib.rtmi_render_pixelwise_device.restype = C.c_int
-    lib.rtmi_render_pixelwise_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(Camera), C.POINTER(PixelwiseOpts)] + [vp] * 6 + [
-        C.c_uint64, vp]
-    lib.rtmi_render_pixelwise.restype = C.c_int
-    lib.rtmi_render_pixelwise.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(PixelwiseOpts)] + [vp] * 5 + [
-        C.POINTER(Stats)]
-    lib.rtmi_window_scratch_bytes.restype = C.c_uint64
-    lib.rtmi_window_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
-    lib.rtmi_window_steps.restype = C.c_uint32
-    lib.rtmi_window_steps.argtypes = [C.c_uint32] * 3
-    lib.rtmi_render_window_device.restype = C.c_int
-    lib.rtmi_render_window_device.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(Camera), C.POINTER(WindowOpts)] + [vp] * 6 + [
-        C.c_uint64, vp]
-    lib.rtmi_render_window.restype = C.c_int
-    lib.rtmi_render_window.argtypes = [vp, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(WindowOpts)] + [vp] * 5 + [
-        C.POINTER(Stats)]
-    lib.rtmi_window_spread_device.restype = C.c_int
-    lib.rtmi_window_spread_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
-    lib.rtmi_probe_window_spread.restype = C.c_int
-    lib.rtmi_probe_window_spread.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
-    lib.rtmi_probe_pixelwise_step.restype = C.c_int
-    lib.rtmi_probe_pixelwise_step.argtypes = [C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
-                                              C.c_double, C.c_double, vp, vp, vp, vp, vp]
+    for table in FAMILIES.values():
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     _rtmi = lib
     return lib
 

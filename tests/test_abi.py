@@ -3,29 +3,22 @@ struct layouts match the header; the host-side helpers (untile, P3 writer) work 
 entry points that need a device fail loudly instead of falling back."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi, default_params, dist as rdist
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def _declared_functions():
-    text = open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
+# rtmi.h: its names carry no word of their own; its structs are tests/test_abi_layout.py's
+CORE = kit.Family("rtmi.h", abi.RTMI_SYMBOLS, includes=[])
 
 
 def test_library_exports_every_declared_symbol():
-    lib = abi.load_rtmi()
-    names = _declared_functions()
-    assert len(names) >= 11
-    for n in names:
-        assert hasattr(lib, n), "librtmi.so does not export " + n
-    assert sorted(abi.RTMI_SYMBOLS) == names
+    assert len(CORE.entries) >= 11
+    CORE.exports()
+    CORE.isolation()
 
 
 def test_struct_sizes_match_header_comments():
@@ -242,6 +235,7 @@ def test_headers_are_plain_c(tmp_path):
     inc = os.path.join(root, "include")
     for h in ("rtmi.h", "rtmi_math.h"):
         subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", os.path.join(inc, h)], check=True)
+    CORE.c99(tmp_path)
     src = tmp_path / "use.c"
     src.write_text('#include <stdio.h>\n#include "rtmi.h"\n'
                    'int main(void) { rtmi_render_params p; rtmi_scene_desc d; (void)p; (void)d;\n'

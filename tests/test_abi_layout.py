@@ -5,22 +5,15 @@ bindings/rust/src/sys.rs (#[repr(C)], what a Rust host binds — it cannot be co
 test compiles a C program FROM THE HEADER that prints sizeof / alignof of every public struct and offsetof / sizeof of
 every field, and demands the same numbers from ctypes and from the repr(C) layout rules applied to sys.rs — so a
 mistake in abi.py cannot propagate into the Rust source unseen, and a header change cannot leave either behind.
+The machinery is tests/abi_kit.py, which every other header's test shares.
 The boundary these structs stand for: Hittable (src/hittable.rs:18-21), Camera (src/camera.rs:20-68) and the arguments
 of create_image (tests/test.rs:55)."""
-import ctypes as C
-import os
-import re
-import subprocess
-
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-
-# C struct -> (ctypes class, Rust struct)
+# C struct -> (ctypes class, Rust struct); no size or offset is pinned here: the numbers come from the compiled header
 STRUCTS = {
     "rtmi_texture": (abi.Texture, "RtmiTexture"), "rtmi_perlin": (abi.Perlin, "RtmiPerlin"),
     "rtmi_image": (abi.ImageDesc, "RtmiImage"), "rtmi_material": (abi.Material, "RtmiMaterial"),
@@ -30,121 +23,34 @@ STRUCTS = {
     "rtmi_camera": (abi.Camera, "RtmiCamera"), "rtmi_render_params": (abi.RenderParams, "RtmiRenderParams"),
     "rtmi_texel": (abi.Texel, "RtmiTexel"), "rtmi_stats": (abi.Stats, "RtmiStats"),
 }
-RUST_SCALAR = {"i32": 4, "u32": 4, "f32": 4, "u64": 8, "f64": 8, "u8": 1, "i64": 8, "usize": 8}
-
-
-def header_structs():
-    """{struct name: [field names in order]} of every `typedef struct { ... } name;` with a body in rtmi.h."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    out = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, re.S):
-        fields = []
-        for decl in body.split(";"):
-            decl = decl.strip()
-            if not decl:
-                continue
-            # "const float *prim_a", "float f0, f1, f2", "float ranvec[256 * 4]", "float root_min[3], root_max[3]"
-            first, *rest = decl.split(",")
-            m = re.match(r"^(?:const\s+)?[\w\s]+?[\s\*]+(\w+)\s*(\[[^\]]*\])?$", first.strip())
-            assert m, (name, decl)
-            fields.append(m.group(1))
-            for r in rest:
-                fields.append(re.match(r"^\s*\*?\s*(\w+)", r).group(1))
-        out[name] = fields
-    return out
-
-
-@pytest.fixture(scope="module")
-def compiled_layout(tmp_path_factory):
-    """{struct: {"size", "align", "fields": [(name, offset, size)]}} printed by a C program built from the header."""
-    hs = header_structs()
-    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "rtmi.h"', "int main(void) {"]
-    for sname, fields in hs.items():
-        lines.append('  printf("S %s %%zu %%zu\\n", sizeof(%s), _Alignof(%s));' % (sname, sname, sname))
-        for f in fields:
-            lines.append('  printf("F %s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (sname, f, sname, f, sname, f))
-    lines += ["  return 0;", "}"]
-    d = tmp_path_factory.mktemp("abi_layout")
-    src, exe = str(d / "layout.c"), str(d / "layout")
-    open(src, "w").write("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-    out = {}
-    for ln in subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout.decode().splitlines():
-        t = ln.split()
-        if t[0] == "S":
-            out[t[1]] = {"size": int(t[2]), "align": int(t[3]), "fields": []}
-        else:
-            out[t[1]]["fields"].append((t[2], int(t[3]), int(t[4])))
-    return out
-
-
-def test_every_public_struct_of_the_header_is_covered(compiled_layout):
-    assert sorted(compiled_layout) == sorted(STRUCTS), "a struct of rtmi.h has no ctypes / Rust counterpart in this test"
-    assert sum(len(v["fields"]) for v in compiled_layout.values()) == sum(len(c._fields_) for c, _ in STRUCTS.values()) >= 110  # the parser saw the fields, not just the names
-
-
-@pytest.mark.parametrize("sname", sorted(STRUCTS))
-def test_ctypes_layout_equals_the_compiled_header(compiled_layout, sname):
-    want = compiled_layout[sname]
-    cty = STRUCTS[sname][0]
-    assert C.sizeof(cty) == want["size"] and C.alignment(cty) == want["align"], sname
-    got = [(n, getattr(cty, n).offset, getattr(cty, n).size) for n, _t in cty._fields_]
-    assert got == want["fields"], sname
-
-
-def rust_layout(rname):
-    """(size, align, [(name, offset, size)]) of a #[repr(C)] struct of sys.rs by the repr(C) rules: every field at the
-    next multiple of its alignment, the struct padded to a multiple of its largest field alignment."""
-    m = re.search(r"#\[repr\(C\)\]\s*(?:#\[derive\([^\)]*\)\]\s*)*pub struct %s \{(.*?)\n\}" % rname, SYS, re.S)
-    assert m, "sys.rs: no #[repr(C)] pub struct " + rname
-    off, amax, fields = 0, 1, []
-    for fname, ty in re.findall(r"pub (r#\w+|\w+): ([^,\n]+),", m.group(1)):
-        ty = ty.strip()
-        arr = re.match(r"\[(\w+); ([\d\s\*]+)\]", ty)
-        if arr:
-            align = RUST_SCALAR[arr.group(1)]
-            n = 1
-            for f in arr.group(2).split("*"):
-                n *= int(f)
-            size = align * n
-        elif ty.startswith("*"):
-            align = size = 8
-        else:
-            align = size = RUST_SCALAR[ty]
-        off = (off + align - 1) // align * align
-        fields.append((fname.replace("r#", ""), off, size))
-        off += size
-        amax = max(amax, align)
-    return (off + amax - 1) // amax * amax, amax, fields
-
-
-@pytest.mark.parametrize("sname", sorted(STRUCTS))
-def test_rust_repr_c_layout_equals_the_compiled_header(compiled_layout, sname):
-    want = compiled_layout[sname]
-    size, align, fields = rust_layout(STRUCTS[sname][1])
-    assert (size, align) == (want["size"], want["align"]), sname
-    assert fields == want["fields"], sname
-
-
-def test_constants_agree_three_ways():
-    """The #defines / enums a host needs, header vs abi.py vs sys.rs."""
-    text = open(HEADER).read()
-
-    def hdef(name):
-        m = re.search(r"#define\s+%s\s+\(?\(?(?:\w+\))?\s*(0x[0-9a-fA-F]+|\d+)u?" % name, text)
-        if m:
-            return int(m.group(1), 0)
-        m = re.search(r"\b%s\s*=\s*(\d+)" % name, text)
-        assert m, name
-        return int(m.group(1))
-
-    for name in ("RTMI_ABI_VERSION", "RTMI_MAX_BVH_DEPTH", "RTMI_TILE", "RTMI_SAMPLE_SLOT_BYTES", "RTMI_FLAG_FAST_CULL",
+CORE = kit.Family("rtmi.h", abi.RTMI_SYMBOLS, {s: v + (None, None) for s, v in STRUCTS.items()}, includes=[])
+# what a host needs, pinned by name: the constants test must have compared each of these
+ABI_CONSTANTS = ("RTMI_ABI_VERSION", "RTMI_MAX_BVH_DEPTH", "RTMI_TILE", "RTMI_SAMPLE_SLOT_BYTES", "RTMI_FLAG_FAST_CULL",
                  "RTMI_FLAG_PATH_SIG", "RTMI_FLAG_PROFILE", "RTMI_FLAG_SYNC", "RTMI_FLAG_ASYNC", "RTMI_FLAG_SKY",
                  "RTMI_FLAG_REF_TREE", "RTMI_FLAG_BLOCK_COOP", "RTMI_FLAG_FACE_FORWARD", "RTMI_FLAG_UV_BOOK",
                  "RTMI_FLAG_TEST_OVERFLOW", "RTMI_FLAG_PROGRESSIVE", "RTMI_PRIMFLAG_XF_COUNT_SHIFT",
                  "RTMI_PRIMFLAG_XF_FIRST_SHIFT", "RTMI_ITEMFLAG_MEDIUM_OUTER_SHIFT", "RTMI_ERR_DEVICE", "RTMI_ERR_CANCELLED",
-                 "RTMI_COLLECTIVE_NONE", "RTMI_COLLECTIVE_PEER_COPY", "RTMI_COLLECTIVE_RCCL"):
-        assert getattr(abi, name) == hdef(name), name
-    for name in ("RTMI_ABI_VERSION", "RTMI_MAX_BVH_DEPTH", "RTMI_FLAG_FAST_CULL", "RTMI_FLAG_PROGRESSIVE", "RTMI_SAMPLE_SLOT_BYTES"):
-        m = re.search(r"pub const %s: \w+ = (\d+)" % name, SYS)
-        assert m and int(m.group(1)) == hdef(name), "sys.rs: " + name
+                 "RTMI_COLLECTIVE_NONE", "RTMI_COLLECTIVE_PEER_COPY", "RTMI_COLLECTIVE_RCCL")
+RUST_CONSTANTS = ("RTMI_ABI_VERSION", "RTMI_MAX_BVH_DEPTH", "RTMI_FLAG_FAST_CULL", "RTMI_FLAG_PROGRESSIVE", "RTMI_SAMPLE_SLOT_BYTES")
+
+
+def test_every_public_struct_of_the_header_is_covered():
+    compiled = kit.compiled_layout("rtmi.h")
+    assert sorted(compiled) == sorted(STRUCTS), "a struct of rtmi.h has no ctypes / Rust counterpart in this test"
+    assert sum(len(v[2]) for v in compiled.values()) == sum(len(c._fields_) for c, _ in STRUCTS.values()) >= 110  # the parser saw the fields, not just the names
+
+
+@pytest.mark.parametrize("sname", sorted(STRUCTS))
+def test_ctypes_layout_equals_the_compiled_header(sname):
+    CORE.layout(only=sname, links=("ctypes",))
+
+
+@pytest.mark.parametrize("sname", sorted(STRUCTS))
+def test_rust_repr_c_layout_equals_the_compiled_header(sname):
+    CORE.layout(only=sname, links=("rust",))
+
+
+def test_constants_agree_three_ways():
+    """The #defines / enums a host needs, header vs abi.py vs sys.rs."""
+    in_abi, in_rust = CORE.constants()
+    assert not set(ABI_CONSTANTS) - set(in_abi) and not set(RUST_CONSTANTS) - set(in_rust)

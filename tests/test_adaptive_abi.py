@@ -6,65 +6,36 @@
 * every bad argument is refused before any device work: RTMI_ERR_INVALID for bad values and a NULL scene,
   RTMI_ERR_UNSUPPORTED for the flags and the tile split the mode does not carry."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
 from raytracing_rust_amd import abi
 from raytracing_rust_amd.host import default_params
 
-from test_abi_layout import rust_layout
+import abi_kit as kit
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_adaptive.h")
 FIELDS = ["min_spp", "step_spp", "abs_tol", "rel_tol"]
-
-
-def _c_layout(tmp_path):
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "rtmi_adaptive.h"', "int main(void) {",
-             '  printf("%zu %zu\\n", sizeof(rtmi_adaptive), _Alignof(rtmi_adaptive));']
-    for f in FIELDS:
-        lines.append('  printf("%s %%zu %%zu\\n", offsetof(rtmi_adaptive, %s), sizeof(((rtmi_adaptive *)0)->%s));' % (f, f, f))
-    lines += ["  return 0;", "}"]
-    src, exe = str(tmp_path / "l.c"), str(tmp_path / "l")
-    open(src, "w").write("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout.decode().split("\n")
-    size, align = map(int, out[0].split())
-    return size, align, [(t[0], int(t[1]), int(t[2])) for t in (ln.split() for ln in out[1:] if ln)]
+# isolated=False: the later adaptive headers (NEE, roulette, per pixel, windowed) take rtmi_adaptive and say the word
+FAMILY = kit.Family("rtmi_adaptive.h", ["rtmi_render_adaptive"], {"rtmi_adaptive": (abi.Adaptive, "RtmiAdaptive", 24, FIELDS)},
+                    word="adaptive", isolated=False, host=("rth_render_adaptive",))
 
 
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_adaptive.h"\n'
-                   "int main(void) { rtmi_adaptive a = {2u, 1u, 0.0, 0.0}; (void)a; (void)&rtmi_render_adaptive; return 0; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, body="rtmi_adaptive a = {2u, 1u, 0.0, 0.0}; (void)a;")
 
 
-def test_layout_chain_header_ctypes_rust(tmp_path):
-    size, align, fields = _c_layout(tmp_path)
-    assert [f[0] for f in fields] == FIELDS and (size, align) == (24, 8)
-    assert (C.sizeof(abi.Adaptive), C.alignment(abi.Adaptive)) == (size, align)
-    assert [(n, getattr(abi.Adaptive, n).offset, getattr(abi.Adaptive, n).size) for n, _ in abi.Adaptive._fields_] == fields
-    assert rust_layout("RtmiAdaptive") == (size, align, fields)
+def test_layout_chain_header_ctypes_rust():
+    FAMILY.layout()
+    assert kit.compiled_layout("rtmi_adaptive.h")["rtmi_adaptive"][:2] == (24, 8)
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_ADAPTIVE_SYMBOLS) == ["rtmi_render_adaptive"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    assert not set(declared) & (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS))
-    host = abi.load_host()
-    assert hasattr(host, "rth_render_adaptive")
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _call(params=None, adaptive=None, scene=None, cam=True):

@@ -7,48 +7,31 @@ GPU.
 * every bad argument is refused before any device work: RTMI_ERR_INVALID for bad values, SKY (env form) and a NULL
   scene, RTMI_ERR_UNSUPPORTED for the flags and the tile split the modes do not carry."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi
 from raytracing_rust_amd.host import default_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-HEADER = os.path.join(INCLUDE, "rtmi_adaptive_nee.h")
 FORMS = ["nee", "env"]
 
 
+# no word: the two names share theirs with rtmi_render_adaptive and rtmi_render_adaptive_roulette
+FAMILY = kit.Family("rtmi_adaptive_nee.h", ["rtmi_render_adaptive_env", "rtmi_render_adaptive_nee"],
+                    includes=["rtmi.h", "rtmi_adaptive.h", "rtmi_env.h"], host=("rth_render_adaptive_nee", "rth_render_adaptive_env"))
+
+
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_adaptive_nee.h"\n'
-                   "int main(void) { rtmi_adaptive a = {2u, 1u, 0.0, 0.0}; rtmi_env_render o = {1u, 0.5f}; (void)a; (void)o;\n"
-                   "  (void)&rtmi_render_adaptive_nee; (void)&rtmi_render_adaptive_env; return 0; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-c", "-o",
-                    str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, body="rtmi_adaptive a = {2u, 1u, 0.0, 0.0}; rtmi_env_render o = {1u, 0.5f}; (void)a; (void)o;")
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_ADAPTIVE_NEE_SYMBOLS) == ["rtmi_render_adaptive_env", "rtmi_render_adaptive_nee"]
+    FAMILY.exports()
     assert abi.RTMI_ADAPTIVE_NEE_SYMBOLS == ["rtmi_render_adaptive_env", "rtmi_render_adaptive_nee"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) |
-              set(abi.RTMI_FEATURES_SYMBOLS) | set(abi.RTMI_DENOISE_SYMBOLS) | set(abi.RTMI_NEE_SYMBOLS) |
-              set(abi.RTMI_ENV_SYMBOLS))
-    assert not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_render_adaptive_nee", "rth_render_adaptive_env"):
-        assert hasattr(host, n), n
+    FAMILY.layout()  # the header defines no struct
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _call(form, params=None, adaptive=None, opts=None, scene=None, cam=True, null_adaptive=False, null_opts=False,

@@ -10,7 +10,6 @@
 * the Python wrapper refuses shapes and dtypes that do not match before it calls."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -19,24 +18,20 @@ import pytest
 import denoise_ref as ref
 from raytracing_rust_amd import abi, denoise
 
-from test_abi_layout import rust_layout
+import abi_kit as kit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
-HEADER = os.path.join(INCLUDE, "rtmi_denoise.h")
 FIELDS = ["iterations", "normal_power", "sigma_l", "sigma_z", "eps_l", "eps_z", "albedo_min", "flags"]
+# isolated=False: the frame pipeline, the upscaler and the tone mapper embed rtmi_denoise_params and say the word
+FAMILY = kit.Family("rtmi_denoise.h", ["rtmi_denoise", "rtmi_probe_expf"],
+                    {"rtmi_denoise_params": (abi.DenoiseParams, "RtmiDenoiseParams", 32, FIELDS)},
+                    word="denoise", isolated=False, includes=["rtmi.h", "rtmi_math.h"])
 
 
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_denoise.h"\n'
-                   "int main(void) {\n"
-                   "  rtmi_denoise_params p = {5u, 128u, 4.0f, 1.0f, 1e-10f, 1e-3f, 1e-3f, 0u};\n"
-                   "  (void)p; (void)&rtmi_denoise; (void)&rtmi_probe_expf;\n"
-                   "  return rtmi_expf(0.0f) == 1.0f ? 0 : 1;\n"
-                   "}\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-c", "-o",
-                    str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="rtmi_expf(0.0f) == 1.0f",
+               body="rtmi_denoise_params p = {5u, 128u, 4.0f, 1.0f, 1e-10f, 1e-3f, 1e-3f, 0u}; (void)p;")
 
 
 def test_header_and_stdio_together(tmp_path):
@@ -47,44 +42,18 @@ def test_header_and_stdio_together(tmp_path):
                     str(tmp_path / "stdio.o")], check=True)
 
 
-def _c_layout(tmp_path):
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "rtmi_denoise.h"', "int main(void) {",
-             '  printf("%zu %zu\\n", sizeof(rtmi_denoise_params), _Alignof(rtmi_denoise_params));']
-    for f in FIELDS:
-        lines.append('  printf("%s %%zu %%zu\\n", offsetof(rtmi_denoise_params, %s), sizeof(((rtmi_denoise_params *)0)->%s));'
-                     % (f, f, f))
-    lines += ["  return 0;", "}"]
-    src, exe = str(tmp_path / "l.c"), str(tmp_path / "l")
-    open(src, "w").write("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + INCLUDE, src, "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout.decode().split("\n")
-    size, align = map(int, out[0].split())
-    return size, align, [(t[0], int(t[1]), int(t[2])) for t in (ln.split() for ln in out[1:] if ln)]
-
-
-def test_layout_chain_header_ctypes_rust(tmp_path):
-    size, align, fields = _c_layout(tmp_path)
-    assert [f[0] for f in fields] == FIELDS and (size, align) == (32, 4)
-    assert (C.sizeof(abi.DenoiseParams), C.alignment(abi.DenoiseParams)) == (size, align)
-    assert [(n, getattr(abi.DenoiseParams, n).offset, getattr(abi.DenoiseParams, n).size)
-            for n, _ in abi.DenoiseParams._fields_] == fields
-    assert rust_layout("RtmiDenoiseParams") == (size, align, fields)
+def test_layout_chain_header_ctypes_rust():
+    FAMILY.layout()
+    assert kit.compiled_layout("rtmi_denoise.h")["rtmi_denoise_params"][:2] == (32, 4)
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    text = text[:text.index("#define RTMI_EXPF_LOW")]  # the declarations; rtmi_expf below is an inline definition
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_DENOISE_SYMBOLS) == ["rtmi_denoise", "rtmi_probe_expf"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) |
-              set(abi.RTMI_FEATURES_SYMBOLS))
-    assert not set(declared) & others
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _params(**kw):

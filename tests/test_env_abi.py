@@ -7,8 +7,6 @@
 * read_pfm inverts pfm_bytes."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,67 +14,32 @@ import pytest
 from raytracing_rust_amd import abi, pfm_bytes, read_pfm
 from raytracing_rust_amd.host import default_params
 
-from test_abi_layout import rust_layout
+import abi_kit as kit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-HEADER = os.path.join(INCLUDE, "rtmi_env.h")
-STRUCTS = {"rtmi_env_map": (abi.EnvMap, "RtmiEnvMap", ["width", "height", "rgb"]),
-           "rtmi_env_render": (abi.EnvRender, "RtmiEnvRender", ["nee", "env_select_p"])}
+STRUCTS = {"rtmi_env_map": (abi.EnvMap, "RtmiEnvMap", 16, ["width", "height", "rgb"]),
+           "rtmi_env_render": (abi.EnvRender, "RtmiEnvRender", 8, ["nee", "env_select_p"])}
+# isolated=False: every later lighting header takes rtmi_env_render or names the map, and "env" is part of other words
+FAMILY = kit.Family("rtmi_env.h", ["rtmi_env_tables", "rtmi_probe_env", "rtmi_render_env", "rtmi_scene_attach_env"], STRUCTS,
+                    word="env", isolated=False, host=("rth_attach_env", "rth_render_env", "rth_probe_env"))
 
 
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include <stdio.h>\n#include "rtmi_env.h"\n'
-                   "typedef char map_ok[sizeof(rtmi_env_map) == 16 ? 1 : -1];\n"
-                   "typedef char opt_ok[sizeof(rtmi_env_render) == 8 ? 1 : -1];\n"
-                   "int main(void) { (void)&rtmi_env_tables; (void)&rtmi_scene_attach_env; (void)&rtmi_render_env;\n"
-                   "  (void)&rtmi_probe_env; return (int)sizeof(map_ok) + (int)sizeof(opt_ok) - 2; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-c", "-o",
-                    str(tmp_path / "c99.o")], check=True)
-
-
-def _c_layout(tmp_path, name, fields):
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "rtmi_env.h"', "int main(void) {",
-             '  printf("%%zu %%zu\\n", sizeof(%s), _Alignof(%s));' % (name, name)]
-    for f in fields:
-        lines.append('  printf("%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (f, name, f, name, f))
-    lines += ["  return 0;", "}"]
-    src, exe = str(tmp_path / ("%s.c" % name)), str(tmp_path / name)
-    open(src, "w").write("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + INCLUDE, src, "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout.decode().split("\n")
-    size, align = map(int, out[0].split())
-    return size, align, [(t[0], int(t[1]), int(t[2])) for t in (ln.split() for ln in out[1:] if ln)]
+    FAMILY.c99(tmp_path, before=("stdio.h",))
 
 
 @pytest.mark.parametrize("name", sorted(STRUCTS))
-def test_layout_chain_header_ctypes_rust(tmp_path, name):
-    cls, rname, fields = STRUCTS[name]
-    size, align, got = _c_layout(tmp_path, name, fields)
-    assert [f[0] for f in got] == fields
-    assert (C.sizeof(cls), C.alignment(cls)) == (size, align)
-    assert [(n, getattr(cls, n).offset, getattr(cls, n).size) for n, _ in cls._fields_] == got
-    assert rust_layout(rname) == (size, align, got)
+def test_layout_chain_header_ctypes_rust(name):
+    FAMILY.layout(only=name)
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_ENV_SYMBOLS) == ["rtmi_env_tables", "rtmi_probe_env", "rtmi_render_env",
-                                                        "rtmi_scene_attach_env"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) |
-              set(abi.RTMI_FEATURES_SYMBOLS) | set(abi.RTMI_DENOISE_SYMBOLS) | set(abi.RTMI_NEE_SYMBOLS))
-    assert not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_attach_env", "rth_render_env", "rth_probe_env"):
-        assert hasattr(host, n), n
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _call(params=None, cam=True, params_null=False, opts="default"):

@@ -4,10 +4,6 @@
   for its structs, with the machinery of test_abi_layout.py; librtmi.so exports exactly the functions it declares;
 * the double planes the host lowering keeps are the f64 oracle's values bit for bit (camera state, Perlin vectors, BVH
   root boxes), and every one of them rounds to the value the fp32 description carries."""
-import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,75 +11,28 @@ import pytest
 from raytracing_rust_amd import abi, scenes
 
 import scenes_extra
-from test_abi_layout import RUST_SCALAR, rust_layout  # noqa: F401  (repr(C) rules of sys.rs)
+import abi_kit as kit
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_f64.h")
-STRUCTS = {"rtmi_scene_f64": (abi.SceneF64, "RtmiSceneF64"), "rtmi_camera_f64": (abi.CameraF64, "RtmiCameraF64")}
-
-
-def _fields(sname):
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef\s+struct\s*\{([^{}]*)\}\s*%s\s*;" % sname, text).group(1)
-    out = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        first, *rest = decl.split(",")
-        out.append(re.match(r"^(?:const\s+)?[\w\s]+?[\s\*]+(\w+)\s*(\[[^\]]*\])?$", first.strip()).group(1))
-        out += [re.match(r"^\s*\*?\s*(\w+)", r).group(1) for r in rest]
-    return out
-
-
-@pytest.fixture(scope="module")
-def layout(tmp_path_factory):
-    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "rtmi_f64.h"', "int main(void) {"]
-    for s in STRUCTS:
-        lines.append('  printf("S %s %%zu %%zu\\n", sizeof(%s), _Alignof(%s));' % (s, s, s))
-        for f in _fields(s):
-            lines.append('  printf("F %s %s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (s, f, s, f, s, f))
-    lines += ["  return 0;", "}"]
-    d = tmp_path_factory.mktemp("f64_layout")
-    src, exe = str(d / "l.c"), str(d / "l")
-    open(src, "w").write("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-    out = {}
-    for ln in subprocess.run([exe], check=True, stdout=subprocess.PIPE).stdout.decode().splitlines():
-        t = ln.split()
-        if t[0] == "S":
-            out[t[1]] = {"size": int(t[2]), "align": int(t[3]), "fields": []}
-        else:
-            out[t[1]]["fields"].append((t[2], int(t[3]), int(t[4])))
-    return out
+STRUCTS = {"rtmi_scene_f64": (abi.SceneF64, "RtmiSceneF64", None, None), "rtmi_camera_f64": (abi.CameraF64, "RtmiCameraF64", None, None)}
+# isolated=False: "f64" is the name of a number format, which the other headers' comments use freely
+FAMILY = kit.Family("rtmi_f64.h", ["rtmi_probe_math_f64", "rtmi_render_f64", "rtmi_scene_attach_f64"], STRUCTS, word="f64",
+                    isolated=False)
 
 
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_f64.h"\nint main(void) { rtmi_scene_f64 s; rtmi_camera_f64 c; (void)s; (void)c; return 0; }\n')
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-o", str(tmp_path / "c99")], check=True)
+    FAMILY.c99(tmp_path, body="rtmi_scene_f64 s; rtmi_camera_f64 c; (void)s; (void)c;", run=True)
 
 
 @pytest.mark.parametrize("sname", sorted(STRUCTS))
-def test_layout_chain_header_ctypes_rust(layout, sname):
-    want = layout[sname]
-    cty, rname = STRUCTS[sname]
-    assert (C.sizeof(cty), C.alignment(cty)) == (want["size"], want["align"])
-    assert [(n, getattr(cty, n).offset, getattr(cty, n).size) for n, _ in cty._fields_] == want["fields"]
-    size, align, fields = rust_layout(rname)
-    assert (size, align, fields) == (want["size"], want["align"], want["fields"])
+def test_layout_chain_header_ctypes_rust(sname):
+    FAMILY.layout(only=sname)
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_F64_SYMBOLS) == ["rtmi_probe_math_f64", "rtmi_render_f64", "rtmi_scene_attach_f64"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    assert not set(declared) & set(abi.RTMI_SYMBOLS)
-    assert int(re.search(r"RTMI_SAMPLE_SLOT_BYTES_F64 (\d+)u", text).group(1)) == abi.SAMPLE_SLOT_BYTES_F64 == 24
+    FAMILY.exports()
+    FAMILY.isolation()
+    assert "RTMI_SAMPLE_SLOT_BYTES_F64" in FAMILY.constants()[1]
+    assert kit.header_constants("rtmi_f64.h")["RTMI_SAMPLE_SLOT_BYTES_F64"] == abi.SAMPLE_SLOT_BYTES_F64 == 24
 
 
 def test_attach_and_render_fail_cleanly_without_a_device(host):

@@ -6,42 +6,28 @@
   params, RTMI_ERR_UNSUPPORTED for the flags and the tile split the features do not carry;
 * pfm_bytes writes the PFM a denoiser reads: header, negative (little-endian) scale, rows bottom to top."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi, pfm_bytes
 from raytracing_rust_amd.host import default_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_features.h")
+
+# isolated=False: the denoiser, the frame pipeline and the upscaler all say which first-hit features they read
+FAMILY = kit.Family("rtmi_features.h", ["rtmi_render_features"], word="features", isolated=False, host=("rth_render_features",))
 
 
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_features.h"\n'
-                   "int main(void) { (void)&rtmi_render_features; return 0; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path)
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_FEATURES_SYMBOLS) == ["rtmi_render_features"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    others = set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS)
-    assert not set(declared) & others
-    host = abi.load_host()
-    assert hasattr(host, "rth_render_features")
+    FAMILY.exports()
+    FAMILY.layout()  # the header defines no struct
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _call(params=None, scene=None, cam=True, params_null=False):

@@ -10,101 +10,54 @@
   is NULL" on every machine; render checks its handle last, so a NULL handle shows every other refusal (the refusals that
   need a live handle: tests/test_gpu_frame.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import frame_ref as ref
 import temporal_ref
+import abi_kit as kit
 from raytracing_rust_amd import Frame, Scene, abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_frame.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_frame_create", "rtmi_frame_destroy", "rtmi_frame_render", "rtmi_frame_render_device", "rtmi_frame_reset",
            "rtmi_probe_frame_untile"]
 OPTS_OFFSETS = {"estimator": 0, "env_select_p": 4, "temporal": 8, "denoise": 40, "flags": 72, "reserved": 76}
 OUT_FIELDS = ["linear", "rgb8", "noisy_linear", "noisy_stderr", "albedo", "normal", "depth", "hits", "accum_linear",
               "accum_stderr", "history", "motion"]
 INVALID, UNSUPPORTED = 1, 2
-FAMILY_WORDS = ("nee", "env", "adaptive", "denoise", "features", "f64", "light", "temporal", "roulette", "session")
+# isolated=False: "frame" is an everyday word of the other headers' comments; the test below holds "rtmi_frame" out of them
+FAMILY = kit.Family("rtmi_frame.h", ENTRIES, {"rtmi_frame_opts": (abi.FrameOpts, "RtmiFrameOpts", 96, OPTS_OFFSETS),
+                                              "rtmi_frame_out": (abi.FrameOut, "RtmiFrameOut", 96, {f: 8 * k for k, f in enumerate(OUT_FIELDS)})},
+                    word="frame", isolated=False, includes=["rtmi.h", "rtmi_denoise.h", "rtmi_roulette.h", "rtmi_temporal.h"],
+                    documented=True, host=("rth_frame_create", "rth_frame_close", "rth_frame_render", "rth_frame_reset"))
 
 
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_frame.h"',
-             "typedef char size_opts[sizeof(rtmi_frame_opts) == 96 ? 1 : -1];",
-             "typedef char size_out[sizeof(rtmi_frame_out) == 96 ? 1 : -1];"]
-    for f, o in OPTS_OFFSETS.items():
-        lines.append("typedef char opts_%s[offsetof(rtmi_frame_opts, %s) == %d ? 1 : -1];" % (f, f, o))
-    for k, f in enumerate(OUT_FIELDS):
-        lines.append("typedef char out_%s[offsetof(rtmi_frame_out, %s) == %d ? 1 : -1];" % (f, f, 8 * k))
-    lines.append("int main(void) { " + " ".join("(void)&%s;" % n for n in ENTRIES) +
-                 " return RTMI_FRAME_NO_TEMPORAL == 1u && RTMI_FRAME_NO_FILTER == 2u ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_FRAME_NO_TEMPORAL == 1u && RTMI_FRAME_NO_FILTER == 2u")
 
 
 def test_ctypes_and_rust_match_the_header():
-    assert C.sizeof(abi.FrameOpts) == 96 and C.sizeof(abi.FrameOut) == 96
-    assert {n: getattr(abi.FrameOpts, n).offset for n, _ in abi.FrameOpts._fields_} == OPTS_OFFSETS
-    assert [n for n, _ in abi.FrameOut._fields_] == OUT_FIELDS
-    assert [getattr(abi.FrameOut, n).offset for n in OUT_FIELDS] == [8 * k for k in range(12)]
-    size = {"u32": 4, "f32": 4, "[u32; 5]": 20, "RtmiTemporalParams": 32, "RtmiDenoiseParams": 32}
-    body = re.search(r"pub struct RtmiFrameOpts \{(.*?)\n\}", SYS, re.S).group(1)
-    rf = [(fname, size[ty.strip()]) for fname, ty in re.findall(r"pub (\w+): ([^,\n]+),", body)]
-    assert rf == [(n, C.sizeof(t)) for n, t in abi.FrameOpts._fields_]
-    body = re.search(r"pub struct RtmiFrameOut \{(.*?)\n\}", SYS, re.S).group(1)
-    rf = re.findall(r"pub (\w+): (\*mut (?:f32|u8|u32)),", body)
-    assert [n for n, _ in rf] == OUT_FIELDS and len(rf) == 12
-    for name in ("RtmiFrameOpts", "RtmiFrameOut"):
-        assert re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct %s" % name, SYS), name
-    assert abi.RTMI_FRAME_NO_TEMPORAL == 1 and re.search(r"pub const RTMI_FRAME_NO_TEMPORAL: u32 = 1;", SYS)
-    assert abi.RTMI_FRAME_NO_FILTER == 2 and re.search(r"pub const RTMI_FRAME_NO_FILTER: u32 = 2;", SYS)
-    # the header documents every offset it has
-    text = open(HEADER).read()
-    for f, o in OPTS_OFFSETS.items():
-        assert re.search(r"\b%s(\[5\])?;\s*/\* offset +%d:" % (f, o), text), f
-    for k, f in enumerate(OUT_FIELDS):
-        assert re.search(r"\*%s;\s*/\* offset +%d:" % (f, 8 * k), text), f
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiFrameOpts", "RtmiFrameOut")
+    assert all(ty in ("*mut f32", "*mut u8", "*mut u32") for _, ty in kit.rust_fields("RtmiFrameOut"))
+    kit.assert_rust_const("RTMI_FRAME_NO_TEMPORAL", "u32", 1)
+    kit.assert_rust_const("RTMI_FRAME_NO_FILTER", "u32", 2)
+    in_abi, in_rust = FAMILY.constants()
+    assert in_abi == in_rust == ["RTMI_FRAME_NO_TEMPORAL", "RTMI_FRAME_NO_FILTER"]
+    assert abi.RTMI_FRAME_NO_TEMPORAL == 1 and abi.RTMI_FRAME_NO_FILTER == 2
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_FRAME_SYMBOLS) == ENTRIES
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    frame_block = SYS[SYS.index("include/rtmi_frame.h"):]
-    assert sorted(re.findall(r"pub fn (rtmi_\w+)\(", frame_block)) == declared
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*frame\w*)\b", out)))
-    assert exported == declared, exported  # the seams of rtmi_frame_launch.hpp are hidden
-    for n in exported:
-        assert not any(w in n for w in FAMILY_WORDS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_FRAME_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
-    host = abi.load_host()
-    for n in ("create", "close", "render", "reset"):
-        assert hasattr(host, "rth_frame_" + n), n
+    FAMILY.exports()  # the seams of rtmi_frame_launch.hpp are hidden
     assert Frame.render.__doc__ and Frame.__doc__ and Scene.frame.__doc__
 
 
 def test_nothing_was_added_to_the_other_headers():
-    assert "rtmi_frame" not in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    assert "RTMI_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    for other in ("rtmi_temporal.h", "rtmi_denoise.h", "rtmi_features.h"):
-        assert "rtmi_frame" not in open(os.path.join(ROOT, "include", other)).read(), other
-    assert "RTMI_FLAG_" not in re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    FAMILY.isolation()
+    for other in ("rtmi.h", "rtmi_temporal.h", "rtmi_denoise.h", "rtmi_features.h"):
+        assert "rtmi_frame" not in kit.header_text(other, comments=True), other
+    assert "RTMI_FLAG_" not in kit.header_text("rtmi_frame.h")
 
 
 # ---- the restatement --------------------------------------------------------------------------------------------------------

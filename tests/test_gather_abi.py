@@ -6,65 +6,42 @@
 * every bad argument that needs no handle is refused before a device is touched, with its code and the entry's name (the
   missing attachments need a handle: tests/test_gpu_gather.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_gather.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_gather", "rtmi_gather_device", "rtmi_gather_directions"]
 OFFSETS = {"n": 0, "spp": 4, "mode": 8, "estimator": 12, "flags": 16, "max_depth": 20, "t_min": 24, "seed": 32,
            "first_point": 40, "first_sample": 48, "slab_points": 52, "env_select_p": 56}
 
 
+FAMILY = kit.Family("rtmi_gather.h", ENTRIES, {"rtmi_gather_params": (abi.GatherParams, "RtmiGatherParams", 64, OFFSETS)},
+                    word="rtmi_gather", includes=["rtmi.h", "rtmi_math.h", "rtmi_radiance.h"], host=("rth_gather", "rth_gather_device"))
+
+
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_gather.h"',
-             "typedef char size_params[sizeof(rtmi_gather_params) == 64 ? 1 : -1];"]
-    for f, o in OFFSETS.items():
-        lines.append("typedef char off_%s[offsetof(rtmi_gather_params, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { float d[3], y[9]; rtmi_gather_sphere(0.25f, 0.5f, d); rtmi_gather_sh9(d, y); "
-                 "(void)&rtmi_gather; (void)&rtmi_gather_device; (void)&rtmi_gather_directions; "
-                 "return RTMI_GATHER_COSINE == 0u && RTMI_GATHER_SPHERE == 1u && y[0] > 0.0f ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, body="float d[3], y[9]; rtmi_gather_sphere(0.25f, 0.5f, d); rtmi_gather_sh9(d, y);",
+               holds="RTMI_GATHER_COSINE == 0u && RTMI_GATHER_SPHERE == 1u && y[0] > 0.0f")
 
 
 def test_ctypes_and_rust_match_the_header():
-    assert C.sizeof(abi.GatherParams) == 64
-    assert {n: getattr(abi.GatherParams, n).offset for n, _ in abi.GatherParams._fields_} == OFFSETS
-    scalar = {"u32": 4, "f32": 4, "u64": 8}
-    body = re.search(r"pub struct RtmiGatherParams \{(.*?)\n\}", SYS, re.S).group(1)
-    rf = [(fname, scalar[ty.strip()]) for fname, ty in re.findall(r"pub (\w+): ([^,\n]+),", body)]
-    assert rf == [(n, C.sizeof(t)) for n, t in abi.GatherParams._fields_]
-    assert re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct RtmiGatherParams", SYS)
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiGatherParams")
+    FAMILY.constants()
     assert (abi.RTMI_GATHER_COSINE, abi.RTMI_GATHER_SPHERE) == (0, 1)
-    assert re.search(r"pub const RTMI_GATHER_COSINE: u32 = 0;", SYS) and re.search(r"pub const RTMI_GATHER_SPHERE: u32 = 1;", SYS)
+    kit.assert_rust_const("RTMI_GATHER_COSINE", "u32", 0)
+    kit.assert_rust_const("RTMI_GATHER_SPHERE", "u32", 1)
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^int (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_GATHER_SYMBOLS) == ENTRIES
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-        assert re.search(r"pub fn %s\(" % n, SYS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_GATHER_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_gather", "rth_gather_device"):
-        assert hasattr(host, n), n
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
 
 
 def _call(entry, n=4, params=True, has_points=True, has_normals=True, outs=(True, True, False), points=None, normals=None,

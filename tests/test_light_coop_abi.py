@@ -11,10 +11,10 @@ wave-cooperative kernel, without a GPU.
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi
 from raytracing_rust_amd.host import Scene, default_params
 
@@ -35,14 +35,16 @@ def _header_define(path, name):
     return int(m.group(1), 0)
 
 
+# no entries and no word: the header is one flag of the NEE / environment entries
+FAMILY = kit.Family("rtmi_light_coop.h", [])
+
+
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi.h"\n#include "rtmi_light_coop.h"\n'
-                   "int main(void) { rtmi_render_params p; p.flags = RTMI_FLAG_FAST_CULL | RTMI_FLAG_LIGHT_COOP;\n"
-                   "  return p.flags == 65537u ? 0 : 1; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-o", str(tmp_path / "c99")],
-                   check=True)
-    assert subprocess.run([str(tmp_path / "c99")]).returncode == 0
+    FAMILY.c99(tmp_path, before=("rtmi.h",), run=True, body="rtmi_render_params p; p.flags = RTMI_FLAG_FAST_CULL | RTMI_FLAG_LIGHT_COOP;",
+               holds="p.flags == 65537u")
+    FAMILY.exports()
+    FAMILY.layout()  # no function, no struct
+    FAMILY.isolation()
 
 
 def test_flag_value_and_disjointness():
@@ -62,10 +64,8 @@ def test_flag_value_and_disjointness():
 
 
 def test_python_and_rust_constants():
-    assert abi.RTMI_FLAG_LIGHT_COOP == FLAG
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    m = re.search(r"pub const RTMI_FLAG_LIGHT_COOP: u32 = (\d+);", sysrs)
-    assert m and int(m.group(1)) == FLAG
+    assert FAMILY.constants() == (["RTMI_FLAG_LIGHT_COOP"], ["RTMI_FLAG_LIGHT_COOP"]) and abi.RTMI_FLAG_LIGHT_COOP == FLAG
+    kit.assert_rust_const("RTMI_FLAG_LIGHT_COOP", "u32", FLAG)
 
 
 def _call(entry, flags, scene=None):

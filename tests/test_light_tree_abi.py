@@ -6,70 +6,44 @@
 * RTMI_FLAG_LIGHT_TREE is a flag of rtmi_render_nee alone: there it reaches the scene check, beside RTMI_FLAG_LIGHT_COOP it
   is RTMI_ERR_UNSUPPORTED, and every other lighting entry answers it as an unknown flag."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import light_tree_scenes as lts
+import abi_kit as kit
 from raytracing_rust_amd import abi, default_params
 from raytracing_rust_amd.host import LIGHT_NODE_DTYPE, LIGHT_PATH_DTYPE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_light_tree.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_light_tree_from_desc", "rtmi_light_tree_pick", "rtmi_light_tree_pmf", "rtmi_probe_light_tree",
            "rtmi_scene_attach_light_tree"]
 FLAG = abi.RTMI_FLAG_LIGHT_TREE
 
 
+FAMILY = kit.Family("rtmi_light_tree.h", ENTRIES, {"rtmi_light_node": (abi.LightNode, "RtmiLightNode", 32, None),
+                                                   "rtmi_light_path": (abi.LightPath, "RtmiLightPath", 8, None)},
+                    word="light_tree", includes=["rtmi_nee.h"], host=("rth_attach_light_tree", "rth_probe_light_tree"))
+
+
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_light_tree.h"',
-             "typedef char size_node[sizeof(rtmi_light_node) == 32 ? 1 : -1];",
-             "typedef char size_path[sizeof(rtmi_light_path) == 8 ? 1 : -1];",
-             "typedef char off_link[offsetof(rtmi_light_node, link) == 20 ? 1 : -1];",
-             "typedef char off_depth[offsetof(rtmi_light_path, depth) == 4 ? 1 : -1];",
-             "int main(void) { (void)&rtmi_light_tree_from_desc; (void)&rtmi_light_tree_pick; (void)&rtmi_light_tree_pmf;",
-             "  (void)&rtmi_scene_attach_light_tree; (void)&rtmi_probe_light_tree;",
-             "  return RTMI_FLAG_LIGHT_TREE == 262144u && RTMI_LIGHT_TREE_PROBE_PMF == 1 ? 0 : 1; }"]
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_FLAG_LIGHT_TREE == 262144u && RTMI_LIGHT_TREE_PROBE_PMF == 1 && "
+               "offsetof(rtmi_light_node, link) == 20 && offsetof(rtmi_light_path, depth) == 4")
 
 
 def test_ctypes_numpy_and_rust_match_the_header():
-    assert C.sizeof(abi.LightNode) == LIGHT_NODE_DTYPE.itemsize == 32
-    assert C.sizeof(abi.LightPath) == LIGHT_PATH_DTYPE.itemsize == 8
-    assert FLAG == 1 << 18 and re.search(r"pub const RTMI_FLAG_LIGHT_TREE: u32 = 262144;", SYS)
-    size = {"u32": 4, "f32": 4, "[f32; 3]": 12, "[u32; 2]": 8}
-    for rust, ct, dt in (("RtmiLightNode", abi.LightNode, LIGHT_NODE_DTYPE), ("RtmiLightPath", abi.LightPath, LIGHT_PATH_DTYPE)):
-        assert re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct %s" % rust, SYS)
-        body = re.search(r"pub struct %s \{(.*?)\n\}" % rust, SYS, re.S).group(1)
-        rf = [(name, size[ty.strip()]) for name, ty in re.findall(r"pub (\w+): (\[[^\]]+\]|[^,\n]+),", body)]
-        assert rf == [(n, C.sizeof(t)) for n, t in ct._fields_]
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiLightNode", "RtmiLightPath")
+    assert "RTMI_FLAG_LIGHT_TREE" in FAMILY.constants()[1] and FLAG == 1 << 18
+    kit.assert_rust_const("RTMI_FLAG_LIGHT_TREE", "u32", 262144)
+    for ct, dt in ((abi.LightNode, LIGHT_NODE_DTYPE), (abi.LightPath, LIGHT_PATH_DTYPE)):
+        assert C.sizeof(ct) == dt.itemsize
         assert [(n, dt.fields[n][1], dt.fields[n][0].itemsize) for n in dt.names] == [
             (n, getattr(ct, n).offset, C.sizeof(t)) for n, t in ct._fields_]
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_LIGHT_TREE_SYMBOLS) == ENTRIES
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-        assert re.search(r"pub fn %s\(" % n, SYS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_LIGHT_TREE_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_attach_light_tree", "rth_probe_light_tree"):
-        assert hasattr(host, n), n
+    FAMILY.exports()
+    FAMILY.isolation()
 
 
 def _err(lib):

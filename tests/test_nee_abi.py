@@ -6,51 +6,38 @@
 * every bad argument, unsupported flag, tile split and missing light table is refused before any device work."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi
 from raytracing_rust_amd.host import default_params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_nee.h")
+
+
+FIELDS = ["item", "prim", "kind", "material", "area", "weight", "select_p", "cdf"]
+# isolated=False: "nee" names the estimator in every later lighting header, and is part of rtmi_render_adaptive_nee
+FAMILY = kit.Family("rtmi_nee.h", ["rtmi_lights_from_desc", "rtmi_render_nee", "rtmi_scene_attach_lights"],
+                    {"rtmi_light": (abi.Light, "RtmiLight", 48, FIELDS)}, word="nee", isolated=False,
+                    host=("rth_render_nee", "rth_attach_lights"))
 
 
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_nee.h"\n'
-                   "typedef char size_ok[sizeof(rtmi_light) == 48 ? 1 : -1];\n"
-                   "int main(void) { (void)&rtmi_render_nee; (void)&rtmi_lights_from_desc; (void)&rtmi_scene_attach_lights;\n"
-                   "  return (int)sizeof(size_ok) - 1; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path)
 
 
 def test_light_record_layout():
-    assert C.sizeof(abi.Light) == 48
-    assert [f[0] for f in abi.Light._fields_] == ["item", "prim", "kind", "material", "area", "weight", "select_p", "cdf"]
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    body = re.search(r"pub struct RtmiLight \{(.*?)\}", sysrs, re.S).group(1)
-    assert re.findall(r"pub (\w+):", body) == ["item", "prim", "kind", "material", "area", "weight", "select_p", "cdf"]
+    FAMILY.layout()
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_NEE_SYMBOLS) == ["rtmi_lights_from_desc", "rtmi_render_nee", "rtmi_scene_attach_lights"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) |
-              set(abi.RTMI_FEATURES_SYMBOLS) | set(abi.RTMI_DENOISE_SYMBOLS))
-    assert not set(declared) & others
-    host = abi.load_host()
-    assert hasattr(host, "rth_render_nee") and hasattr(host, "rth_attach_lights")
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _call(params=None, scene=None, cam=True, params_null=False):

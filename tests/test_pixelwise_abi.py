@@ -9,18 +9,13 @@
   render entries are called with a NULL scene and the probe with the device index -1, both checked last, so a valid set of
   arguments ends there on every machine (the missing attachments need a live handle: tests/test_gpu_pixelwise.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import Scene, abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_pixelwise.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_pixelwise_scratch_bytes", "rtmi_pixelwise_steps", "rtmi_probe_pixelwise_step", "rtmi_render_pixelwise",
            "rtmi_render_pixelwise_device"]
 OFFSETS = {"min_spp": 0, "step_spp": 4, "estimator": 8, "pass_spp": 12, "abs_tol": 16, "rel_tol": 24, "env_select_p": 32, "reserved": 36}
@@ -28,68 +23,29 @@ INVALID, UNSUPPORTED, DEVICE = 1, 2, 3
 FC = abi.RTMI_FLAG_FAST_CULL
 
 
+FAMILY = kit.Family("rtmi_pixelwise.h", ENTRIES, {"rtmi_pixelwise_opts": (abi.PixelwiseOpts, "RtmiPixelwiseOpts", 48, OFFSETS)},
+                    word="pixelwise", includes=["rtmi.h", "rtmi_adaptive.h", "rtmi_roulette.h"], documented=True,
+                    host=("rth_render_pixelwise", "rth_render_pixelwise_device"))
+
+
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_pixelwise.h"',
-             "typedef char size_opts[sizeof(rtmi_pixelwise_opts) == 48 ? 1 : -1];"]
-    for f, o in OFFSETS.items():
-        lines.append("typedef char off_%s[offsetof(rtmi_pixelwise_opts, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { " + " ".join("(void)&%s;" % n for n in ENTRIES) +
-                 " return RTMI_ROULETTE_ENV_NEE == 3u && RTMI_PIXELWISE_MAX_STEPS == 1024u ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_ROULETTE_ENV_NEE == 3u && RTMI_PIXELWISE_MAX_STEPS == 1024u")
 
 
 def test_ctypes_and_rust_match_the_header():
-    text = open(HEADER).read()
-    ct = abi.PixelwiseOpts
-    assert C.sizeof(ct) == 48
-    assert {n: getattr(ct, n).offset for n, _ in ct._fields_} == OFFSETS
-    block = SYS[SYS.index("include/rtmi_pixelwise.h"):SYS.index("include/rtmi_temporal.h")]
-    body = re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct RtmiPixelwiseOpts \{(.*?)\n\}", block, re.S).group(1)
-    size = {"u32": 4, "f32": 4, "f64": 8, "[u32; 3]": 12}
-    rf = re.findall(r"pub (\w+): ([^,\n]+),", body)
-    assert [n for n, _ in rf] == [n for n, _ in ct._fields_]
-    assert [size[t.strip()] for _, t in rf] == [C.sizeof(t) for _, t in ct._fields_]
-    assert [t.strip() in ("f32", "f64") for _, t in rf] == [t in (C.c_float, C.c_double) for _, t in ct._fields_]
-    decl = re.search(r"typedef struct \{(.*?)\}\s*rtmi_pixelwise_opts;\s*/\* (\d+) bytes \*/", text, re.S)
-    assert decl and int(decl.group(2)) == 48
-    for f, o in OFFSETS.items():
-        assert re.search(r"\b%s(\[\d\])?;\s*/\* offset +%d:" % (f, o), decl.group(1)), f
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiPixelwiseOpts")
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void|uint32_t|uint64_t) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_PIXELWISE_SYMBOLS) == ENTRIES and len(abi.RTMI_PIXELWISE_SYMBOLS) == 5
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    assert sorted(re.findall(r"pub fn (rtmi_\w*pixelwise\w*)\(", SYS)) == declared
-    block = SYS[SYS.index("include/rtmi_pixelwise.h"):SYS.index("include/rtmi_temporal.h")]
-    assert sorted(re.findall(r"pub fn (rtmi_\w+)\(", block)) == declared
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*pixelwise\w*)\b", out)))
-    assert exported == declared, exported
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_PIXELWISE_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_render_pixelwise", "rth_render_pixelwise_device"):
-        assert hasattr(host, n), n
-    assert Scene.render_pixelwise.__doc__
+    FAMILY.exports()
+    assert len(abi.RTMI_PIXELWISE_SYMBOLS) == 5 and Scene.render_pixelwise.__doc__
 
 
 def test_the_header_keeps_to_itself():
-    assert "RTMI_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rtmi_pixelwise.h":
-            assert "pixelwise" not in open(os.path.join(ROOT, "include", other)).read().lower(), other
-    assert re.findall(r'#include "(\w+\.h)"', open(HEADER).read()) == ["rtmi.h", "rtmi_adaptive.h", "rtmi_roulette.h"]
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 # ---- the two pure functions ---------------------------------------------------------------------------------------------------

@@ -6,75 +6,46 @@
 * every bad argument that is refused before a device is touched gives its code and names the entry."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi, primary_rays
 from raytracing_rust_amd.host import HIT_DTYPE, RAY_DTYPE
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_query.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_occluded", "rtmi_occluded_device", "rtmi_trace", "rtmi_trace_device"]
 
 
+CHECKS = {"rtmi_ray": (abi.Ray, "RtmiRay", 32, {"o": 0, "t_min": 12, "d": 16, "t_max": 28}),
+          "rtmi_hit": (abi.Hit, "RtmiHit", 48, {"t": 0, "u": 4, "v": 8, "p": 12, "n": 24, "item": 36, "prim": 40, "material": 44}),
+          "rtmi_query_params": (abi.QueryParams, "RtmiQueryParams", 24, {"n": 0, "flags": 4, "seed": 8, "first_ray": 16})}
+# no word: the entries are rtmi_trace, rtmi_occluded and rtmi_scene_attach_flips, which share none
+FAMILY = kit.Family("rtmi_query.h", ENTRIES + ["rtmi_scene_attach_flips"], CHECKS,
+                    host=("rth_trace", "rth_occluded", "rth_trace_device", "rth_occluded_device"))
+
+
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    checks = {"rtmi_ray": (32, {"o": 0, "t_min": 12, "d": 16, "t_max": 28}),
-              "rtmi_hit": (48, {"t": 0, "u": 4, "v": 8, "p": 12, "n": 24, "item": 36, "prim": 40, "material": 44}),
-              "rtmi_query_params": (24, {"n": 0, "flags": 4, "seed": 8, "first_ray": 16})}
-    lines = ['#include <stddef.h>', '#include "rtmi_query.h"']
-    for name, (size, offs) in checks.items():
-        lines.append("typedef char size_%s[sizeof(%s) == %d ? 1 : -1];" % (name, name, size))
-        for f, o in offs.items():
-            lines.append("typedef char off_%s_%s[offsetof(%s, %s) == %d ? 1 : -1];" % (name, f, name, f, o))
-    lines.append("int main(void) { (void)&rtmi_trace; (void)&rtmi_occluded; (void)&rtmi_trace_device; "
-                 "(void)&rtmi_occluded_device; return 0; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path)
 
 
 def test_ctypes_and_numpy_records_match_the_header():
-    for cty, size, offs in ((abi.Ray, 32, {"o": 0, "t_min": 12, "d": 16, "t_max": 28}),
-                            (abi.Hit, 48, {"t": 0, "u": 4, "v": 8, "p": 12, "n": 24, "item": 36, "prim": 40, "material": 44}),
-                            (abi.QueryParams, 24, {"n": 0, "flags": 4, "seed": 8, "first_ray": 16})):
-        assert C.sizeof(cty) == size
-        assert {n: getattr(cty, n).offset for n, _ in cty._fields_} == offs
+    FAMILY.layout(links=("ctypes",))
     for dt, cty in ((RAY_DTYPE, abi.Ray), (HIT_DTYPE, abi.Hit)):
         assert dt.itemsize == C.sizeof(cty)
         assert {n: dt.fields[n][1] for n in dt.names} == {n: getattr(cty, n).offset for n, _ in cty._fields_}
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_QUERY_SYMBOLS) == sorted(ENTRIES + ["rtmi_scene_attach_flips"])
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-        assert re.search(r"pub fn %s\(" % n, SYS), n
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) | set(abi.RTMI_FEATURES_SYMBOLS) |
-              set(abi.RTMI_DENOISE_SYMBOLS) | set(abi.RTMI_NEE_SYMBOLS) | set(abi.RTMI_ENV_SYMBOLS) |
-              set(abi.RTMI_ADAPTIVE_NEE_SYMBOLS) | set(abi.RTMI_ROULETTE_SYMBOLS) | set(abi.SESSION_SYMBOLS))
-    assert not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_trace", "rth_occluded", "rth_trace_device", "rth_occluded_device"):
-        assert hasattr(host, n), n
+    FAMILY.exports()
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def test_rust_structs_match_ctypes():
-    scalar = {"i32": 4, "u32": 4, "f32": 4, "u64": 8, "f64": 8, "u8": 1}
-    for rname, cty in {"RtmiRay": abi.Ray, "RtmiHit": abi.Hit, "RtmiQueryParams": abi.QueryParams}.items():
-        body = re.search(r"pub struct %s \{(.*?)\n\}" % rname, SYS, re.S).group(1)
-        rf = []
-        for fname, ty in re.findall(r"pub (\w+): ([^,\n]+),", body):
-            m = re.match(r"\[(\w+); (\d+)\]", ty.strip())
-            rf.append((fname, scalar[m.group(1)] * int(m.group(2)) if m else scalar[ty.strip()]))
-        assert rf == [(n, C.sizeof(t)) for n, t in cty._fields_], rname
+    FAMILY.layout(links=("rust",))
 
 
 def _call(entry, n=4, flags=0, scene=None, params=True, rays=True, out=True):

@@ -8,62 +8,41 @@
 * irradiance's direction generator: unit length, in the normal's hemisphere, cosine-distributed;
 * the vectorised Philox of philox.py is the scalar one."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi, irradiance_directions, philox
 from raytracing_rust_amd.host import RAY_DTYPE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_radiance.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_radiance", "rtmi_radiance_device"]
 OFFSETS = {"n": 0, "spp": 4, "estimator": 8, "flags": 12, "max_depth": 16, "t_min": 20, "seed": 24, "first_ray": 32,
            "first_sample": 40, "stream_skip": 44, "env_select_p": 48}
 
 
+FAMILY = kit.Family("rtmi_radiance.h", ENTRIES, {"rtmi_radiance_params": (abi.RadianceParams, "RtmiRadianceParams", 56, OFFSETS)},
+                    word="rtmi_radiance", includes=["rtmi.h", "rtmi_query.h", "rtmi_roulette.h"], host=("rth_radiance", "rth_radiance_device"),
+                    word_also_in={"rtmi_gather.h": "includes the header and takes its estimator rules",
+                                  "rtmi_sparse.h": "refers to the header's sample indexing in a comment"})
+
+
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_radiance.h"',
-             "typedef char size_params[sizeof(rtmi_radiance_params) == 56 ? 1 : -1];"]
-    for f, o in OFFSETS.items():
-        lines.append("typedef char off_%s[offsetof(rtmi_radiance_params, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { (void)&rtmi_radiance; (void)&rtmi_radiance_device; return RTMI_ROULETTE_ENV_NEE == 3u ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_ROULETTE_ENV_NEE == 3u")
 
 
 def test_ctypes_and_rust_match_the_header():
-    assert C.sizeof(abi.RadianceParams) == 56
-    assert {n: getattr(abi.RadianceParams, n).offset for n, _ in abi.RadianceParams._fields_} == OFFSETS
-    scalar = {"u32": 4, "f32": 4, "u64": 8}
-    body = re.search(r"pub struct RtmiRadianceParams \{(.*?)\n\}", SYS, re.S).group(1)
-    rf = [(fname, scalar[ty.strip()]) for fname, ty in re.findall(r"pub (\w+): ([^,\n]+),", body)]
-    assert rf == [(n, C.sizeof(t)) for n, t in abi.RadianceParams._fields_]
-    assert re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct RtmiRadianceParams", SYS)
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiRadianceParams")
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_RADIANCE_SYMBOLS) == ENTRIES
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-        assert re.search(r"pub fn %s\(" % n, SYS), n
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) | set(abi.RTMI_FEATURES_SYMBOLS) |
-              set(abi.RTMI_DENOISE_SYMBOLS) | set(abi.RTMI_NEE_SYMBOLS) | set(abi.RTMI_ENV_SYMBOLS) |
-              set(abi.RTMI_ADAPTIVE_NEE_SYMBOLS) | set(abi.RTMI_ROULETTE_SYMBOLS) | set(abi.SESSION_SYMBOLS) |
-              set(abi.RTMI_QUERY_SYMBOLS))
-    assert not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_radiance", "rth_radiance_device"):
-        assert hasattr(host, n), n
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
+    FAMILY.constants()
 
 
 def _rays(n):

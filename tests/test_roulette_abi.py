@@ -6,62 +6,39 @@
 * every bad argument is refused before any device work, with its name in the message: RTMI_ERR_INVALID for bad values,
   SKY with the map estimators and a NULL scene, RTMI_ERR_UNSUPPORTED for PATH_SIG, the other flags and the tile split."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi
 from raytracing_rust_amd.host import default_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-HEADER = os.path.join(INCLUDE, "rtmi_roulette.h")
 FORMS = ["fixed", "adaptive"]
 ESTIMATORS = [0, 1, 2, 3]
 
 
+# isolated=False: every later header takes its estimator from RTMI_ROULETTE_* and says so
+FAMILY = kit.Family("rtmi_roulette.h", ["rtmi_render_adaptive_roulette", "rtmi_render_roulette"],
+                    {"rtmi_roulette": (abi.Roulette, "RtmiRoulette", 16, ["estimator", "min_depth", "q_min", "env_select_p"])},
+                    word="roulette", isolated=False, includes=["rtmi.h", "rtmi_adaptive.h"],
+                    host=("rth_render_roulette", "rth_render_adaptive_roulette"))
+
+
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi_roulette.h"\n'
-                   "int main(void) { rtmi_roulette o = {RTMI_ROULETTE_ENV_NEE, 3u, 0.05f, 0.5f}; rtmi_adaptive a = {2u, 1u, 0.0, 0.0};\n"
-                   "  (void)o; (void)a; (void)&rtmi_render_roulette; (void)&rtmi_render_adaptive_roulette;\n"
-                   "  return sizeof(rtmi_roulette) == 16 ? 0 : 1; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-o", str(tmp_path / "c99")],
-                   check=True)
-    subprocess.run([str(tmp_path / "c99")], check=True)
+    FAMILY.c99(tmp_path, run=True, body="rtmi_roulette o = {RTMI_ROULETTE_ENV_NEE, 3u, 0.05f, 0.5f}; rtmi_adaptive a = {2u, 1u, 0.0, 0.0}; "
+               "(void)o; (void)a;")
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(rtmi_[a-z0-9_]+)\s*\(", text)))
-    assert declared == sorted(abi.RTMI_ROULETTE_SYMBOLS) == ["rtmi_render_adaptive_roulette", "rtmi_render_roulette"]
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    # nothing else of the family is exported
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*roulette\w*)\b", out)))
-    assert exported == declared, exported
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    for n in declared:
-        assert re.search(r"pub fn %s\(" % n, sysrs), n
-    body = re.search(r"pub struct RtmiRoulette \{(.*?)\n\}", sysrs, re.S).group(1)
-    fields = re.findall(r"pub (\w+): (\w+),", body)
-    assert fields == [("estimator", "u32"), ("min_depth", "u32"), ("q_min", "f32"), ("env_select_p", "f32")]
-    assert [n for n, _ in abi.Roulette._fields_] == [n for n, _ in fields] and C.sizeof(abi.Roulette) == 16
+    FAMILY.exports()  # nothing else of the family is exported
+    FAMILY.layout()
+    FAMILY.isolation()
+    assert kit.rust_fields("RtmiRoulette") == [("estimator", "u32"), ("min_depth", "u32"), ("q_min", "f32"), ("env_select_p", "f32")]
+    in_abi, in_rust = FAMILY.constants()
     for name, val in (("PLAIN", 0), ("NEE", 1), ("ENV", 2), ("ENV_NEE", 3)):
-        assert "RTMI_ROULETTE_%s: u32 = %d" % (name, val) in sysrs
-        assert re.search(r"#define RTMI_ROULETTE_%s %du\b" % (name, val), open(HEADER).read())
+        assert "RTMI_ROULETTE_" + name in in_abi and "RTMI_ROULETTE_" + name in in_rust
+        kit.assert_rust_const("RTMI_ROULETTE_" + name, "u32", val)
         assert getattr(abi, "RTMI_ROULETTE_" + name) == val
-    others = (set(abi.RTMI_SYMBOLS) | set(abi.RTMI_F64_SYMBOLS) | set(abi.RTMI_ADAPTIVE_SYMBOLS) |
-              set(abi.RTMI_FEATURES_SYMBOLS) | set(abi.RTMI_DENOISE_SYMBOLS) | set(abi.RTMI_NEE_SYMBOLS) |
-              set(abi.RTMI_ENV_SYMBOLS) | set(abi.RTMI_ADAPTIVE_NEE_SYMBOLS))
-    assert not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_render_roulette", "rth_render_adaptive_roulette"):
-        assert hasattr(host, n), n
 
 
 def _call(form, params=None, opts=None, adaptive=None, scene=None, cam=True, null_opts=False, null_params=False,

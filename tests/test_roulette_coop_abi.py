@@ -12,10 +12,10 @@ wave-cooperative kernel, without a GPU.
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import abi, host as host_mod
 from raytracing_rust_amd.host import Scene, default_params
 
@@ -39,20 +39,19 @@ def _header_define(path, name):
     return int(m.group(1), 0)
 
 
+# no entries and no word: the header is one flag of the roulette entries
+FAMILY = kit.Family("rtmi_roulette_coop.h", [], includes=["rtmi.h", "rtmi_roulette.h"])
+
+
 def test_header_is_c99(tmp_path):
-    src = tmp_path / "c99.c"
-    src.write_text('#include "rtmi.h"\n#include "rtmi_roulette.h"\n#include "rtmi_roulette_coop.h"\n'
-                   "int main(void) { rtmi_render_params p; rtmi_roulette o; o.estimator = RTMI_ROULETTE_PLAIN;\n"
-                   "  p.flags = RTMI_FLAG_FAST_CULL | RTMI_FLAG_ROULETTE_COOP;\n"
-                   "  return (p.flags == 131073u && o.estimator == 0u) ? 0 : 1; }\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, str(src), "-o", str(tmp_path / "c99")],
-                   check=True)
-    assert subprocess.run([str(tmp_path / "c99")]).returncode == 0
+    FAMILY.c99(tmp_path, before=("rtmi.h", "rtmi_roulette.h"), run=True,
+               body="rtmi_render_params p; rtmi_roulette o; o.estimator = RTMI_ROULETTE_PLAIN; p.flags = RTMI_FLAG_FAST_CULL | RTMI_FLAG_ROULETTE_COOP;",
+               holds="p.flags == 131073u && o.estimator == 0u")
     # the header alone pulls in what it names
-    alone = tmp_path / "alone.c"
-    alone.write_text('#include "rtmi_roulette_coop.h"\nint main(void) { rtmi_roulette o; o.min_depth = 1u; return (int)o.min_depth - 1; }\n')
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + INCLUDE, "-c", str(alone), "-o", str(tmp_path / "alone.o")],
-                   check=True)
+    FAMILY.c99(tmp_path, body="rtmi_roulette o; o.min_depth = 1u;", holds="o.min_depth == 1u")
+    FAMILY.exports()
+    FAMILY.layout()  # no function, no struct
+    FAMILY.isolation()
 
 
 def test_flag_value_and_disjointness():
@@ -75,10 +74,8 @@ def test_flag_value_and_disjointness():
 
 
 def test_python_and_rust_constants():
-    assert abi.RTMI_FLAG_ROULETTE_COOP == FLAG
-    sysrs = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
-    m = re.search(r"pub const RTMI_FLAG_ROULETTE_COOP: u32 = (\d+);", sysrs)
-    assert m and int(m.group(1)) == FLAG
+    assert FAMILY.constants() == (["RTMI_FLAG_ROULETTE_COOP"], ["RTMI_FLAG_ROULETTE_COOP"]) and abi.RTMI_FLAG_ROULETTE_COOP == FLAG
+    kit.assert_rust_const("RTMI_FLAG_ROULETTE_COOP", "u32", FLAG)
 
 
 def _call(entry, flags, estimator="nee", scene=None):

@@ -8,93 +8,44 @@
   stateless entries are called with the device index -1 and the others with a NULL scene, both checked last, so a valid
   set of arguments ends there on every machine (the missing attachments need a live handle: tests/test_gpu_sparse.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import Scene, abi, sparse_patch, sparse_select
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_sparse.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_sparse_patch_device", "rtmi_sparse_refine", "rtmi_sparse_refine_device", "rtmi_sparse_render",
            "rtmi_sparse_render_device", "rtmi_sparse_scratch_bytes", "rtmi_sparse_select_device"]
 OFFSETS = {"n": 0, "ns": 4, "first_sample": 8, "estimator": 12, "env_select_p": 16, "reserved": 20}
-FAMILY_WORDS = ("frame", "temporal", "tonemap", "denoise", "env", "nee", "light", "session", "gather", "query", "radiance",
-                "adaptive", "features", "f64", "roulette", "upscale")
+FAMILY = kit.Family("rtmi_sparse.h", ENTRIES, {"rtmi_sparse_params": (abi.SparseParams, "RtmiSparseParams", 32, OFFSETS)},
+                    word="sparse", includes=["rtmi.h", "rtmi_roulette.h"], documented=True,
+                    host=("rth_sparse_render", "rth_sparse_render_device", "rth_sparse_refine"))
 INVALID, UNSUPPORTED, DEVICE = 1, 2, 3
 FC = abi.RTMI_FLAG_FAST_CULL
 
 
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_sparse.h"',
-             "typedef char size_params[sizeof(rtmi_sparse_params) == 32 ? 1 : -1];"]
-    for f, o in OFFSETS.items():
-        lines.append("typedef char off_%s[offsetof(rtmi_sparse_params, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { " + " ".join("(void)&%s;" % n for n in ENTRIES) + " return RTMI_ROULETTE_ENV_NEE == 3u ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_ROULETTE_ENV_NEE == 3u")
 
 
 def test_ctypes_and_rust_match_the_header():
-    text = open(HEADER).read()
-    ct = abi.SparseParams
-    assert C.sizeof(ct) == 32
-    assert {n: getattr(ct, n).offset for n, _ in ct._fields_} == OFFSETS
-    block = SYS[SYS.index("include/rtmi_sparse.h"):SYS.index("include/rtmi_upscale.h")]
-    body = re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct RtmiSparseParams \{(.*?)\n\}", block, re.S).group(1)
-    size = {"u32": 4, "f32": 4, "[u32; 3]": 12}
-    rf = re.findall(r"pub (\w+): ([^,\n]+),", body)
-    assert [n for n, _ in rf] == [n for n, _ in ct._fields_]
-    assert [size[t.strip()] for _, t in rf] == [C.sizeof(t) for _, t in ct._fields_]
-    assert [t.strip() == "f32" for _, t in rf] == [t is C.c_float for _, t in ct._fields_]
-    decl = re.search(r"typedef struct \{([^}]*)\}\s*rtmi_sparse_params;\s*/\* (\d+) bytes \*/", text)
-    assert decl and int(decl.group(2)) == 32
-    for f, o in OFFSETS.items():
-        assert re.search(r"\b%s(\[\d\])?;\s*/\* offset +%d:" % (f, o), decl.group(1)), f
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiSparseParams")
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void|uint64_t) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_SPARSE_SYMBOLS) == ENTRIES and len(abi.RTMI_SPARSE_SYMBOLS) == 7
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    assert sorted(re.findall(r"pub fn (rtmi_\w*sparse\w*)\(", SYS)) == declared
-    assert SYS.index("include/rtmi_temporal.h") < SYS.index("include/rtmi_sparse.h") < SYS.index("include/rtmi_upscale.h")
-    block = SYS[SYS.index("include/rtmi_sparse.h"):SYS.index("include/rtmi_upscale.h")]
-    assert sorted(re.findall(r"pub fn (rtmi_\w+)\(", block)) == declared
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*sparse\w*)\b", out)))
-    assert exported == declared, exported
-    for n in exported:
-        assert "sparse" in n and not any(w in n for w in FAMILY_WORDS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_SPARSE_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
-    host = abi.load_host()
-    for n in ("rth_sparse_render", "rth_sparse_render_device", "rth_sparse_refine"):
-        assert hasattr(host, n), n
+    FAMILY.exports()
+    assert len(abi.RTMI_SPARSE_SYMBOLS) == 7
     assert Scene.render_pixels.__doc__ and Scene.refine_pixels.__doc__ and sparse_select.__doc__ and sparse_patch.__doc__
 
 
 def test_the_header_keeps_to_itself():
-    low = open(HEADER).read().lower()
+    FAMILY.isolation()
+    FAMILY.constants()
+    low = kit.header_text("rtmi_sparse.h", comments=True).lower()
     assert "upscale" not in low and "tonemap" not in low
-    assert "RTMI_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rtmi_sparse.h":
-            assert "sparse" not in open(os.path.join(ROOT, "include", other)).read().lower(), other
-    assert re.findall(r'#include "(\w+\.h)"', open(HEADER).read()) == ["rtmi.h", "rtmi_roulette.h"]
 
 
 def test_scratch_bytes():

@@ -8,49 +8,37 @@
   checks its handle last, so a NULL handle shows every other refusal (the refusals that need a live handle:
   tests/test_gpu_temporal.py)."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import temporal_ref as ref
+import abi_kit as kit
 from raytracing_rust_amd import Temporal, abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_temporal.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_temporal_create", "rtmi_temporal_destroy", "rtmi_temporal_push", "rtmi_temporal_reset"]
 OFFSETS = {"max_history": 0, "alpha_min": 4, "depth_tol": 8, "normal_min": 12, "albedo_min": 16, "flags": 20, "reserved": 24}
 DEFAULT = dict(max_history=32, alpha_min=0.0, depth_tol=0.05, normal_min=0.9, albedo_min=1e-3, flags=0, reserved=(0, 0))
 
 
+FAMILY = kit.Family("rtmi_temporal.h", ENTRIES, {"rtmi_temporal_params": (abi.TemporalParams, "RtmiTemporalParams", 32, OFFSETS)},
+                    word="temporal", word_also_in={"rtmi_frame.h": "embeds rtmi_temporal_params in rtmi_frame_opts",
+                                                   "rtmi_denoise.h": "says in a comment which filter input the accumulation feeds"})
+
+
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_temporal.h"',
-             "typedef char size_params[sizeof(rtmi_temporal_params) == 32 ? 1 : -1];",
-             "typedef char size_camera[sizeof(rtmi_camera) == 84 ? 1 : -1];"]
-    for f, o in OFFSETS.items():
-        lines.append("typedef char off_%s[offsetof(rtmi_temporal_params, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { (void)&rtmi_temporal_create; (void)&rtmi_temporal_push; (void)&rtmi_temporal_reset; "
-                 "(void)&rtmi_temporal_destroy; return RTMI_TEMPORAL_NO_DEMODULATE == 1u ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_TEMPORAL_NO_DEMODULATE == 1u && sizeof(rtmi_camera) == 84")
 
 
 def test_ctypes_and_rust_match_the_header():
-    assert C.sizeof(abi.TemporalParams) == 32 and C.sizeof(abi.Camera) == 84
-    assert {n: getattr(abi.TemporalParams, n).offset for n, _ in abi.TemporalParams._fields_} == OFFSETS
-    size = {"u32": 4, "f32": 4, "[u32; 2]": 8}
-    body = re.search(r"pub struct RtmiTemporalParams \{(.*?)\n\}", SYS, re.S).group(1)
-    rf = [(fname, size[ty.strip()]) for fname, ty in re.findall(r"pub (\w+): ([^,\n]+),", body)]
-    assert rf == [(n, C.sizeof(t)) for n, t in abi.TemporalParams._fields_]
-    assert re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct RtmiTemporalParams", SYS)
-    assert abi.RTMI_TEMPORAL_NO_DEMODULATE == 1 and re.search(r"pub const RTMI_TEMPORAL_NO_DEMODULATE: u32 = 1;", SYS)
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiTemporalParams")
+    assert C.sizeof(abi.Camera) == 84
+    assert FAMILY.constants() == (["RTMI_TEMPORAL_NO_DEMODULATE"], ["RTMI_TEMPORAL_NO_DEMODULATE"]) and abi.RTMI_TEMPORAL_NO_DEMODULATE == 1
+    kit.assert_rust_const("RTMI_TEMPORAL_NO_DEMODULATE", "u32", 1)
     # the defaults of the header's comments, of Temporal and of the restatement agree
-    text = open(HEADER).read()
+    text = kit.header_text("rtmi_temporal.h", comments=True)
     for field, value in (("max_history", "32"), ("alpha_min", "0"), ("depth_tol", "0.05"), ("normal_min", "0.9"),
                          ("albedo_min", "1e-3")):
         assert re.search(r"\b%s;\s*/\*[^*]*default %s \*/" % (field, re.escape(value)), text), field
@@ -58,18 +46,11 @@ def test_ctypes_and_rust_match_the_header():
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_TEMPORAL_SYMBOLS) == ENTRIES
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-        assert re.search(r"pub fn %s\(" % n, SYS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_TEMPORAL_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
+    FAMILY.exports()
+
+
+def test_the_header_keeps_to_itself():
+    FAMILY.isolation()
 
 
 def _create(nx=8, ny=8, params=True, out=True, device=-1, **fields):

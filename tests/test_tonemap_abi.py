@@ -10,19 +10,15 @@
   tests/test_gpu_tonemap.py)."""
 import ctypes as C
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 import tonemap_ref as ref
 from raytracing_rust_amd import Frame, Host, Tonemap, abi, tonemap
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_tonemap.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_probe_tonemap_histogram", "rtmi_tonemap_apply", "rtmi_tonemap_apply_device", "rtmi_tonemap_create",
            "rtmi_tonemap_destroy", "rtmi_tonemap_reset"]
 PARAM_OFFSETS = {"op": 0, "oetf": 4, "exposure": 8, "flags": 12, "ev": 16, "white": 20, "key": 24, "log2_min": 28, "log2_max": 32,
@@ -31,51 +27,27 @@ STATE_OFFSETS = {"exposure": 0, "adapted_log2": 4, "metered_log2": 8, "counted":
 DEFAULT = dict(op=2, oetf=1, exposure=1, flags=0, ev=0.0, white=math.inf, key=0.18, log2_min=-12.0, log2_max=12.0, p_low=0.10,
                p_high=0.95, speed_up=3.0, speed_down=1.0, adapt_min=-12.0, adapt_max=12.0, reserved=0)
 INVALID, UNSUPPORTED, DEVICE = 1, 2, 3
-FAMILY_WORDS = ("frame", "temporal", "gather", "light", "session", "nee", "env", "adaptive", "denoise", "features", "f64",
-                "roulette", "query", "radiance")
+FAMILY = kit.Family("rtmi_tonemap.h", ENTRIES, {"rtmi_tonemap_params": (abi.TonemapParams, "RtmiTonemapParams", 64, PARAM_OFFSETS),
+                                                "rtmi_tonemap_state": (abi.TonemapState, "RtmiTonemapState", 32, STATE_OFFSETS)},
+                    word="tonemap", includes=["rtmi.h", "rtmi_math.h", "rtmi_denoise.h"], documented=True)
 
 
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_tonemap.h"',
-             "typedef char size_params[sizeof(rtmi_tonemap_params) == 64 ? 1 : -1];",
-             "typedef char size_state[sizeof(rtmi_tonemap_state) == 32 ? 1 : -1];"]
-    for f, o in PARAM_OFFSETS.items():
-        lines.append("typedef char p_%s[offsetof(rtmi_tonemap_params, %s) == %d ? 1 : -1];" % (f, f, o))
-    for f, o in STATE_OFFSETS.items():
-        lines.append("typedef char s_%s[offsetof(rtmi_tonemap_state, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { " + " ".join("(void)&%s;" % n for n in ENTRIES) +
-                 " return RTMI_TONEMAP_CLAMP == 0u && RTMI_TONEMAP_REINHARD == 1u && RTMI_TONEMAP_ACES == 2u && "
-                 "RTMI_TONEMAP_GAMMA2 == 0u && RTMI_TONEMAP_SRGB == 1u && RTMI_TONEMAP_MANUAL == 0u && RTMI_TONEMAP_AUTO == 1u "
-                 "&& rtmi_logf(1.0f) == 0.0f && rtmi_expf(0.0f) == 1.0f ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-o", str(tmp_path / "c99"), "-lm"], check=True)
-    subprocess.run([str(tmp_path / "c99")], check=True)
+    FAMILY.c99(tmp_path, run=True, holds="RTMI_TONEMAP_CLAMP == 0u && RTMI_TONEMAP_REINHARD == 1u && RTMI_TONEMAP_ACES == 2u && "
+               "RTMI_TONEMAP_GAMMA2 == 0u && RTMI_TONEMAP_SRGB == 1u && RTMI_TONEMAP_MANUAL == 0u && RTMI_TONEMAP_AUTO == 1u "
+               "&& rtmi_logf(1.0f) == 0.0f && rtmi_expf(0.0f) == 1.0f")
 
 
 def test_ctypes_and_rust_match_the_header():
-    assert C.sizeof(abi.TonemapParams) == 64 and C.sizeof(abi.TonemapState) == 32
-    assert {n: getattr(abi.TonemapParams, n).offset for n, _ in abi.TonemapParams._fields_} == PARAM_OFFSETS
-    assert {n: getattr(abi.TonemapState, n).offset for n, _ in abi.TonemapState._fields_} == STATE_OFFSETS
-    size = {"u32": 4, "f32": 4, "[u32; 2]": 8}
-    for rust, ct in (("RtmiTonemapParams", abi.TonemapParams), ("RtmiTonemapState", abi.TonemapState)):
-        body = re.search(r"pub struct %s \{(.*?)\n\}" % rust, SYS, re.S).group(1)
-        rf = [(fname, ty.strip(), size[ty.strip()]) for fname, ty in re.findall(r"pub (\w+): ([^,\n]+),", body)]
-        assert [(n, s) for n, _, s in rf] == [(n, C.sizeof(t)) for n, t in ct._fields_], rust
-        assert [t == "f32" for _, t, _ in rf] == [t is C.c_float for _, t in ct._fields_], rust
-        assert re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct %s" % rust, SYS), rust
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiTonemapParams", "RtmiTonemapState")
+    in_abi, in_rust = FAMILY.constants()
+    assert in_abi == in_rust and len(in_abi) == 7
     for name, value in (("CLAMP", 0), ("REINHARD", 1), ("ACES", 2), ("GAMMA2", 0), ("SRGB", 1), ("MANUAL", 0), ("AUTO", 1)):
-        assert getattr(abi, "RTMI_TONEMAP_" + name) == value
-        assert re.search(r"pub const RTMI_TONEMAP_%s: u32 = %d;" % (name, value), SYS), name
-        assert re.search(r"#define RTMI_TONEMAP_%s %du\b" % (name, value), open(HEADER).read()), name
-    # the header documents every offset it has
-    text = open(HEADER).read()
-    for f, o in PARAM_OFFSETS.items():
-        assert re.search(r"\b%s;\s*/\* offset +%d:" % (f, o), text), f
-    for f, o in STATE_OFFSETS.items():
-        assert re.search(r"\b%s(\[2\])?;\s*/\* offset +%d:" % (f, o), text), f
+        assert getattr(abi, "RTMI_TONEMAP_" + name) == value and "RTMI_TONEMAP_" + name in in_abi
+        kit.assert_rust_const("RTMI_TONEMAP_" + name, "u32", value)
+    text = kit.header_text("rtmi_tonemap.h", comments=True)
     # the defaults of the header's comments, of Tonemap and of the restatement agree
     kw = dict(zip(Tonemap.__init__.__code__.co_varnames[1:], (None, None) + Tonemap.__init__.__defaults__))
     assert (kw["op"], kw["oetf"], kw["exposure"]) == ("aces", "srgb", "auto") == tuple(ref.DEFAULTS[k] for k in ("op", "oetf", "exposure"))
@@ -91,36 +63,14 @@ def test_ctypes_and_rust_match_the_header():
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_TONEMAP_SYMBOLS) == ENTRIES and len(abi.RTMI_TONEMAP_SYMBOLS) == 6
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    assert sorted(re.findall(r"pub fn (rtmi_\w*tonemap\w*)\(", SYS)) == declared
-    block = SYS[SYS.index("include/rtmi_tonemap.h"):SYS.index("include/rtmi_frame.h")]
-    assert sorted(re.findall(r"pub fn (rtmi_\w+)\(", block)) == declared  # before the frame block, which runs to the end
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*tonemap\w*)\b", out)))
-    assert exported == declared, exported
-    for n in exported:
-        assert "tonemap" in n and not any(w in n for w in FAMILY_WORDS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_TONEMAP_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
+    FAMILY.exports()
+    assert len(abi.RTMI_TONEMAP_SYMBOLS) == 6
     assert Tonemap.__doc__ and Tonemap.apply.__doc__ and tonemap.__doc__ and "tonemap" in Frame.render.__doc__
     assert hasattr(Tonemap, "__enter__") and hasattr(Tonemap, "__exit__") and hasattr(Tonemap, "reset") and hasattr(Tonemap, "close")
 
 
 def test_nothing_was_added_to_the_other_headers():
-    assert "RTMI_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rtmi_tonemap.h":
-            assert "tonemap" not in open(os.path.join(ROOT, "include", other)).read().lower(), other
-    includes = re.findall(r'#include "(\w+\.h)"', open(HEADER).read())
-    assert includes == ["rtmi.h", "rtmi_math.h", "rtmi_denoise.h"]
+    FAMILY.isolation()
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------

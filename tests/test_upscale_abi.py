@@ -11,20 +11,16 @@
 import ctypes as C
 import inspect
 import math
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import temporal_ref
 import upscale_ref as ref
+import abi_kit as kit
 from raytracing_rust_amd import Host, Scene, Upscaler, abi, upscale
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_upscale.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_upscale", "rtmi_upscale_device", "rtmi_upscaler_create", "rtmi_upscaler_destroy", "rtmi_upscaler_render",
            "rtmi_upscaler_render_device", "rtmi_upscaler_reset"]
 # struct: (C name, ctypes class, Rust name, size, offsets)
@@ -41,53 +37,33 @@ STRUCTS = (
 )
 DEFAULT = dict(normal_power=32, sigma_z=0.05, eps_z=1e-3, albedo_min=1e-3, w_min=1e-3, flags=0, reserved=(0, 0))
 INVALID, UNSUPPORTED, DEVICE = 1, 2, 3
-FAMILY_WORDS = ("frame", "temporal", "tonemap", "denoise", "env", "nee", "light", "session", "gather", "query", "radiance",
-                "roulette", "adaptive", "features", "f64")
 FC = abi.RTMI_FLAG_FAST_CULL
 nan, inf = math.nan, math.inf
 
 
+FAMILY = kit.Family("rtmi_upscale.h", ENTRIES, {c: (ct, rust, size, offsets) for c, ct, rust, size, offsets in STRUCTS}, word="upscale",
+                    includes=["rtmi.h", "rtmi_math.h", "rtmi_denoise.h", "rtmi_frame.h"], documented=True,
+                    host=("rth_upscaler_create", "rth_upscaler_close", "rth_upscaler_render", "rth_upscaler_reset"))
+
+
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_upscale.h"']
-    for cname, _, _, size, offsets in STRUCTS:
-        lines.append("typedef char size_%s[sizeof(%s) == %d ? 1 : -1];" % (cname, cname, size))
-        for f, o in offsets.items():
-            lines.append("typedef char o_%s_%s[offsetof(%s, %s) == %d ? 1 : -1];" % (cname, f, cname, f, o))
-    lines.append("int main(void) { " + " ".join("(void)&%s;" % n for n in ENTRIES) +
-                 " return RTMI_UPSCALE_BACKGROUND == 0u && RTMI_UPSCALE_GUIDED == 1u && RTMI_UPSCALE_NEAREST == 2u && "
-                 "RTMI_UPSCALE_MISMATCH == 3u && rtmi_expf(0.0f) == 1.0f ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_UPSCALE_BACKGROUND == 0u && RTMI_UPSCALE_GUIDED == 1u && RTMI_UPSCALE_NEAREST == 2u && "
+               "RTMI_UPSCALE_MISMATCH == 3u && rtmi_expf(0.0f) == 1.0f")
 
 
 def test_ctypes_and_rust_match_the_header():
-    text = open(HEADER).read()
-    size = {"u32": 4, "f32": 4, "[u32; 2]": 8, "[u32; 5]": 20, "RtmiFrameOpts": 96, "RtmiFrameOut": 96, "RtmiUpscaleParams": 32}
-    block = SYS[SYS.index("include/rtmi_upscale.h"):SYS.index("include/rtmi_tonemap.h")]
-    for cname, ct, rust, total, offsets in STRUCTS:
-        assert C.sizeof(ct) == total, cname
-        assert {n: getattr(ct, n).offset for n, _ in ct._fields_} == offsets, cname
-        body = re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct %s \{(.*?)\n\}" % rust, block, re.S).group(1)
-        rf = re.findall(r"pub (\w+): ([^,\n]+),", body)
-        assert [n for n, _ in rf] == [n for n, _ in ct._fields_], rust
-        assert [8 if t.startswith("*") else size[t.strip()] for _, t in rf] == [C.sizeof(t) for _, t in ct._fields_], rust
-        assert [t.strip() == "f32" for _, t in rf] == [t is C.c_float for _, t in ct._fields_], rust
-        # the header states the size and documents every offset it has
-        decl = re.search(r"typedef struct \{([^}]*)\}\s*%s;\s*/\* (\d+) bytes \*/" % cname, text)
-        assert decl and int(decl.group(2)) == total, cname
-        for f, o in offsets.items():
-            assert re.search(r"\b%s(\[\d\])?;\s*/\* offset +%d:" % (f, o), decl.group(1)), (cname, f)
+    FAMILY.layout()
+    kit.assert_plain_repr_c(*[rust for _, _, rust, _, _ in STRUCTS])
+    in_abi, in_rust = FAMILY.constants()
     for k, name in enumerate(("BACKGROUND", "GUIDED", "NEAREST", "MISMATCH")):
         assert getattr(abi, "RTMI_UPSCALE_" + name) == k == getattr(ref, name)
-        assert re.search(r"pub const RTMI_UPSCALE_%s: u8 = %d;" % (name, k), block), name
-        assert re.search(r"#define RTMI_UPSCALE_%s %du\b" % (name, k), text), name
+        assert "RTMI_UPSCALE_" + name in in_abi and "RTMI_UPSCALE_" + name in in_rust
+        kit.assert_rust_const("RTMI_UPSCALE_" + name, "u8", k)
 
 
 def test_the_defaults_agree():
-    text = open(HEADER).read()
+    text = kit.header_text("rtmi_upscale.h", comments=True)
     sig = inspect.signature(upscale)
     assert sig.parameters["device"].default == 0 and "params" in sig.parameters
     from raytracing_rust_amd import host as H
@@ -106,40 +82,15 @@ def test_the_defaults_agree():
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_UPSCALE_SYMBOLS) == ENTRIES and len(abi.RTMI_UPSCALE_SYMBOLS) == 7
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    assert sorted(re.findall(r"pub fn (rtmi_\w*upscale\w*)\(", SYS)) == declared
-    assert SYS.index("include/rtmi_upscale.h") < SYS.index("include/rtmi_tonemap.h") < SYS.index("include/rtmi_frame.h")
-    block = SYS[SYS.index("include/rtmi_upscale.h"):SYS.index("include/rtmi_tonemap.h")]
-    assert sorted(re.findall(r"pub fn (rtmi_\w+)\(", block)) == declared
-    assert "include/rtmi_frame.h" not in block
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*upscale\w*)\b", out)))
-    assert exported == declared, exported
-    for n in exported:
-        assert "upscale" in n and not any(w in n for w in FAMILY_WORDS), n
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_UPSCALE_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 40 and not set(declared) & others
-    host = abi.load_host()
-    for n in ("create", "close", "render", "reset"):
-        assert hasattr(host, "rth_upscaler_" + n), n
+    FAMILY.exports()
+    assert len(abi.RTMI_UPSCALE_SYMBOLS) == 7
     assert Upscaler.__doc__ and Upscaler.render.__doc__ and upscale.__doc__ and Scene.upscaler.__doc__
     assert all(hasattr(Upscaler, n) for n in ("__enter__", "__exit__", "reset", "close"))
     assert "_upscalers" in Host.free_all.__code__.co_consts or "_upscalers" in Host.free_all.__code__.co_names
 
 
 def test_nothing_was_added_to_the_other_headers():
-    assert "RTMI_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rtmi_upscale.h":
-            assert "upscale" not in open(os.path.join(ROOT, "include", other)).read().lower(), other
+    FAMILY.isolation()
 
 
 # ---- the stateless entries' refusals ------------------------------------------------------------------------------------------

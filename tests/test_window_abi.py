@@ -10,18 +10,13 @@
   render entries are called with a NULL scene and the probe with the device index -1, both checked last, so a valid set of
   arguments ends there on every machine (the missing attachments need a live handle: tests/test_gpu_window.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_kit as kit
 from raytracing_rust_amd import Scene, abi, window_spread
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtmi_window.h")
-SYS = open(os.path.join(ROOT, "bindings", "rust", "src", "sys.rs")).read()
 ENTRIES = ["rtmi_probe_window_spread", "rtmi_render_window", "rtmi_render_window_device", "rtmi_window_scratch_bytes",
            "rtmi_window_spread_device", "rtmi_window_steps"]
 OFFSETS = {"min_spp": 0, "step_spp": 4, "estimator": 8, "pass_spp": 12, "abs_tol": 16, "rel_tol": 24, "env_select_p": 32, "radius": 36,
@@ -31,82 +26,38 @@ FC = abi.RTMI_FLAG_FAST_CULL
 OTHER_WORDS = ("pixelwise", "sparse", "upscale", "tonemap", "rtmi_frame")
 
 
-def _block():
-    return SYS[SYS.index("include/rtmi_window.h"):SYS.index("include/rtmi_pixelwise.h")]
+FAMILY = kit.Family("rtmi_window.h", ENTRIES, {"rtmi_window_opts": (abi.WindowOpts, "RtmiWindowOpts", 48, OFFSETS)},
+                    word="window", includes=["rtmi.h", "rtmi_adaptive.h", "rtmi_roulette.h"], documented=True,
+                    host=("rth_render_window", "rth_render_window_device"))
 
 
 # ---- layout -----------------------------------------------------------------------------------------------------------------
 def test_header_is_c99_with_the_documented_layout(tmp_path):
-    lines = ['#include <stddef.h>', '#include "rtmi_window.h"', "typedef char size_opts[sizeof(rtmi_window_opts) == 48 ? 1 : -1];"]
-    for f, o in OFFSETS.items():
-        lines.append("typedef char off_%s[offsetof(rtmi_window_opts, %s) == %d ? 1 : -1];" % (f, f, o))
-    lines.append("int main(void) { " + " ".join("(void)&%s;" % n for n in ENTRIES) +
-                 " return RTMI_ROULETTE_ENV_NEE == 3u && RTMI_WINDOW_MAX_RADIUS == 16u ? 0 : 1; }")
-    src = tmp_path / "c99.c"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src),
-                    "-c", "-o", str(tmp_path / "c99.o")], check=True)
+    FAMILY.c99(tmp_path, holds="RTMI_ROULETTE_ENV_NEE == 3u && RTMI_WINDOW_MAX_RADIUS == 16u")
 
 
 def test_ctypes_and_rust_match_the_header():
-    text = open(HEADER).read()
-    ct = abi.WindowOpts
-    assert C.sizeof(ct) == 48 and abi.RTMI_WINDOW_MAX_RADIUS == 16
-    assert {n: getattr(ct, n).offset for n, _ in ct._fields_} == OFFSETS
-    block = _block()
-    assert "pub const RTMI_WINDOW_MAX_RADIUS: u32 = 16;" in block
-    body = re.search(r"#\[repr\(C\)\]\n#\[derive\(Clone, Copy\)\]\npub struct RtmiWindowOpts \{(.*?)\n\}", block, re.S).group(1)
-    size = {"u32": 4, "f32": 4, "f64": 8, "[u32; 2]": 8}
-    rf = re.findall(r"pub (\w+): ([^,\n]+),", body)
-    assert [n for n, _ in rf] == [n for n, _ in ct._fields_]
-    assert [size[t.strip()] for _, t in rf] == [C.sizeof(t) for _, t in ct._fields_]
-    assert [t.strip() in ("f32", "f64") for _, t in rf] == [t in (C.c_float, C.c_double) for _, t in ct._fields_]
-    decl = re.search(r"typedef struct \{(.*?)\}\s*rtmi_window_opts;\s*/\* (\d+) bytes \*/", text, re.S)
-    assert decl and int(decl.group(2)) == 48
-    for f, o in OFFSETS.items():
-        assert re.search(r"\b%s(\[\d\])?;\s*/\* offset +%d:" % (f, o), decl.group(1)), f
-    assert "#define RTMI_WINDOW_MAX_RADIUS 16u" in text
+    FAMILY.layout()
+    kit.assert_plain_repr_c("RtmiWindowOpts")
+    assert FAMILY.constants() == (["RTMI_WINDOW_MAX_RADIUS"], ["RTMI_WINDOW_MAX_RADIUS"]) and abi.RTMI_WINDOW_MAX_RADIUS == 16
+    kit.assert_rust_const("RTMI_WINDOW_MAX_RADIUS", "u32", 16)
+    assert "#define RTMI_WINDOW_MAX_RADIUS 16u" in kit.header_text("rtmi_window.h")
 
 
 def test_exports_and_declarations_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"^(?:int|void|uint32_t|uint64_t) (rtmi_[a-z0-9_]+)\s*\(", text, flags=re.M)))
-    assert declared == sorted(abi.RTMI_WINDOW_SYMBOLS) == ENTRIES and len(abi.RTMI_WINDOW_SYMBOLS) == 6
-    lib = abi.load_rtmi()
-    for n in declared:
-        assert hasattr(lib, n), n
-    assert sorted(re.findall(r"pub fn (rtmi_\w*window\w*)\(", SYS)) == declared
-    block = _block()
-    assert sorted(re.findall(r"pub fn (rtmi_\w+)\(", block)) == declared
-    markers = re.findall(r"include/rtmi_\w+\.h", block)  # the block holds no other block's marker string
-    assert set(markers) == {"include/rtmi_window.h"}, markers
-    assert SYS.index("include/rtmi_gather.h:") < SYS.index("include/rtmi_window.h") < SYS.index("include/rtmi_pixelwise.h")
-    out = subprocess.run(["nm", "-D", "--defined-only", lib._name], check=True, capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r"\b(rtmi_\w*window\w*)\b", out)))
-    assert exported == declared, exported
-    others = set()
-    for name in dir(abi):
-        if name.endswith("_SYMBOLS") and name != "RTMI_WINDOW_SYMBOLS":
-            others |= set(getattr(abi, name))
-    assert len(others) > 45 and not set(declared) & others
-    for n in declared:  # none of the new names reads as a member of a neighbouring family
+    FAMILY.exports()
+    assert len(abi.RTMI_WINDOW_SYMBOLS) == 6
+    for n in ENTRIES:  # none of the new names reads as a member of a neighbouring family
         assert not any(w in n for w in OTHER_WORDS), n
-    host = abi.load_host()
-    for n in ("rth_render_window", "rth_render_window_device"):
-        assert hasattr(host, n), n
     assert Scene.render_windowed.__doc__ and window_spread.__doc__
 
 
 def test_the_header_keeps_to_itself():
-    assert "RTMI_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "rtmi.h")).read()
-    text = open(HEADER).read()
+    FAMILY.isolation()
+    text = kit.header_text("rtmi_window.h", comments=True)
     for word in OTHER_WORDS:  # the neighbours are named by their DESIGN.md sections
         assert word not in text.lower(), word
     assert "DESIGN.md §31 / §32" in text
-    assert re.findall(r'#include "(\w+\.h)"', text) == ["rtmi.h", "rtmi_adaptive.h", "rtmi_roulette.h"]
-    for other in sorted(os.listdir(os.path.join(ROOT, "include"))):
-        if other != "rtmi_window.h":
-            assert "rtmi_window" not in open(os.path.join(ROOT, "include", other)).read().lower(), other
 
 
 # ---- the two pure functions ---------------------------------------------------------------------------------------------------
