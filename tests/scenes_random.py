@@ -266,8 +266,35 @@ class _Placed:
                                 focus_dist * self._s, time0, time1)
 
 
-def build(api, seed, nx, ny, only=None, instanced=False, scale=1.0, offset=(0.0, 0.0, 0.0)):
-    """scale, offset: the scene away from the unit box (_Placed); the defaults build exactly the scene of old"""
+class ExactOps:
+    """The same scene restricted to the operations that are correctly rounded everywhere (+ - * / and sqrt), so that two
+    double implementations can be held to each other bit for bit: a NoiseTexture (sin of the turbulence) and an
+    ImageTexture (atan2 / asin of a sphere's normal) become a grey SolidTexture, a ConstantMedium (log of a uniform)
+    becomes its boundary.  A CheckerTexture stays: its three sines enter only through the sign of their product, which a
+    last-place error cannot change unless a coordinate is exactly 0.  Everything else passes through; the generator's
+    draws do not depend on what the calls return, so the rest of the scene is the one of old."""
+
+    def __init__(self, api):
+        self._api = api
+
+    def __getattr__(self, name):
+        return getattr(self._api, name)
+
+    def NoiseTexture(self, scale):
+        return self._api.SolidTexture(0.5, 0.5, 0.5)
+
+    def ImageTexture(self, data, nx, ny):
+        return self._api.SolidTexture(0.5, 0.5, 0.5)
+
+    def ConstantMedium(self, boundary, density, texture):
+        return boundary
+
+
+def build(api, seed, nx, ny, only=None, instanced=False, scale=1.0, offset=(0.0, 0.0, 0.0), exact_ops=False):
+    """scale, offset: the scene away from the unit box (_Placed); exact_ops: without sin, log, atan2 and asin (ExactOps);
+    the defaults build exactly the scene of old"""
+    if exact_ops:
+        api = ExactOps(api)
     if scale != 1.0 or any(offset):
         api = _Placed(api, scale, offset)
     return random_camera(api, seed, nx, ny), random_scene(api, seed, only, instanced)
