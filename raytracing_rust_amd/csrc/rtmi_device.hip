@@ -78,18 +78,17 @@ static int fail(int code, const std::string &msg) {
 }
 #define HIP_TRY(expr) RTMI_HIP_TRY("", false, expr, #expr)
 
-struct rtmi_scene {
+// Every piece of device and pinned memory of the handle is an owner of rtmi_hostkit.hpp that knows its size; the members
+// free themselves when rtmi_scene_destroy deletes the handle.
+struct RTMI_HIDDEN rtmi_scene {
     int device = 0;
     DevScene dev{};
-    std::vector<void *> allocs;
+    DeviceList allocs;
     rtmi_scene_desc meta{}; // counts only (pointers nulled)
-    double *partial = nullptr; // f64 radiance sums [local tile][3][64], carried between passes
-    size_t partial_bytes = 0;
-    Rad3 *samples = nullptr; // per-sample radiance [local tile][pass samples][64], 12-B slots
-    size_t samples_bytes = 0;
-    uint2 *spill = nullptr;    // global part of the cooperative traversal stacks [wavefront slot][spill_cap]
-    size_t spill_bytes = 0;
-    unsigned int *status = nullptr; // RTMI_STATUS_WORDS device words, see rtmi_types.hpp
+    DeviceBuf<double> partial; // f64 radiance sums [local tile][3][64], carried between passes
+    DeviceBuf<Rad3> samples;   // per-sample radiance [local tile][pass samples][64], 12-B slots
+    DeviceBuf<uint2> spill;    // global part of the cooperative traversal stacks [wavefront slot][spill_cap]
+    DeviceBuf<unsigned int> status; // RTMI_STATUS_WORDS device words, see rtmi_types.hpp
     int slots = 0;                  // CUs x 16: resident wavefronts the render kernels are launched with
     bool has_alt = false;           // some BVH item carries an alternative tree
     bool all_alt = false;           // every BVH item does (and there is one): the workgroup-cooperative kernel can run
@@ -98,79 +97,64 @@ struct rtmi_scene {
                                     // state-machine kernel does not carry them, RTMI_FLAG_ASYNC then runs the per-lane kernel
     uint32_t last_kernel = 0;       // RTMI_KERNEL_* of the last render enqueued on this handle (rtmi_stats.kernel)
     // scratch of the blocking host API (grow-only, so a host that renders frame after frame allocates once)
-    rtmi_texel *texels = nullptr;
-    size_t texels_bytes = 0;
-    unsigned long long *d_sig = nullptr;
-    size_t sig_bytes = 0;
-    uint32_t *rr_bounces = nullptr;    // the bounce plane of the roulette entries (include/rtmi_roulette.h), tiled as d_sig
-    size_t rr_bytes = 0;
-    rtmi_texel *h_texels = nullptr;    // pinned host mirror of `texels` (hipHostMalloc: the D2H copy runs at link speed)
-    size_t h_texel_count = 0;
-    rtmi_texel *h_partial = nullptr;   // ... and of the partial images rtmi_partial_image fetches (RTMI_FLAG_PROGRESSIVE)
-    size_t h_partial_count = 0;
+    DeviceBuf<rtmi_texel> texels;
+    DeviceBuf<unsigned long long> d_sig;
+    DeviceBuf<uint32_t> rr_bounces;    // the bounce plane of the roulette entries (include/rtmi_roulette.h), tiled as d_sig
+    PinnedBuf<rtmi_texel> h_texels;    // pinned host mirror of `texels` (hipHostMalloc: the D2H copy runs at link speed)
+    PinnedBuf<rtmi_texel> h_partial;   // ... and of the partial images rtmi_partial_image fetches (RTMI_FLAG_PROGRESSIVE)
     // Thread model (rtmi.h): render calls on one handle serialise.  `mu` orders the host side (planning, scratch
     // (re)allocation, enqueue, and for the blocking calls the wait and the copy-out); `busy` chains the device side: a
     // render enqueued on ANY stream first waits for the previous render of this handle, whose kernels use the same
     // unit queue, status words and per-sample buffer.
     std::mutex mu;
-    hipEvent_t busy = nullptr;
+    DeviceEvent busy;
     bool busy_recorded = false;
-    hipStream_t stream = nullptr;      // launches of the blocking API (non-blocking stream)
-    hipStream_t copy_stream = nullptr; // progress polls while a launch runs
-    uint64_t units_total = 0;          // work units of the last enqueued call (progress denominator)
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DeviceStream stream;      // launches of the blocking API (non-blocking stream)
+    DeviceStream copy_stream; // progress polls while a launch runs
+    uint64_t units_total = 0; // work units of the last enqueued call (progress denominator)
+    DeviceEvent ev[3];
     // f64 render mode (include/rtmi_f64.h): the attached double planes on the device, freed with the handle
     bool has_f64 = false;
     DevSceneF64 f64{};
-    std::vector<void *> f64_allocs;
-    double *f64_samples = nullptr; // the f64 mode's per-sample buffer (grow-only, at most RTMI_F64_MAX_BUFFER_BYTES)
-    size_t f64_samples_bytes = 0;
+    DeviceList f64_allocs;
+    DeviceBuf<double> f64_samples; // the f64 mode's per-sample buffer (grow-only, at most RTMI_F64_MAX_BUFFER_BYTES)
     // adaptive sampling (include/rtmi_adaptive.h), grow-only, freed with the handle: sum | m | M2 per pixel and channel,
     // two active-tile lists and their count word, the standard errors and counts of the retired tiles
-    double *ad_state = nullptr;   // [tile][9][64]
-    uint32_t *ad_lists = nullptr; // [2][tiles] + count
-    float *ad_stderr = nullptr;   // [tile][64][3]
-    uint32_t *ad_spp = nullptr;   // [tile][64]
-    size_t ad_tiles = 0;
-    uint32_t *h_ad_count = nullptr; // pinned: the active count read back after every step
+    DeviceBuf<double> ad_state;   // [tile][9][64]
+    DeviceBuf<uint32_t> ad_lists; // [2][tiles] + count
+    DeviceBuf<float> ad_stderr;   // [tile][64][3]
+    DeviceBuf<uint32_t> ad_spp;   // [tile][64]
+    PinnedBuf<uint32_t> h_ad_count; // pinned: the active count read back after every step
     // first-hit features (include/rtmi_features.h), grow-only, freed with the handle: the f64 sums carried between passes
     // and the four output planes
-    double *ft_state = nullptr; // [tile][8][64]
-    size_t ft_state_bytes = 0;
-    float *ft_planes = nullptr; // albedo [ny*nx*3] | normal [ny*nx*3] | depth [ny*nx] | hits [ny*nx] (uint32)
-    size_t ft_planes_bytes = 0;
+    DeviceBuf<double> ft_state; // [tile][8][64]
+    DeviceBuf<float> ft_planes; // albedo [ny*nx*3] | normal [ny*nx*3] | depth [ny*nx] | hits [ny*nx] (uint32)
     // ray queries (include/rtmi_query.h), grow-only, freed with the handle: the device copies of a host-form batch
-    float4 *q_rays = nullptr;   // [n][2]
-    size_t q_rays_bytes = 0;
-    float *q_time = nullptr;    // [n]
-    size_t q_time_bytes = 0;
-    float4 *q_out = nullptr;    // trace: [n][3] hit records; occluded: [n] bytes
-    size_t q_out_bytes = 0;
-    uint32_t *q_flip_gaps = nullptr; // rtmi_scene_attach_flips: [n_prims] | [n_items], or NULL
+    DeviceBuf<float4> q_rays;   // [n][2]
+    DeviceBuf<float> q_time;    // [n]
+    DeviceBuf<float4> q_out;    // trace: [n][3] hit records; occluded: [n] bytes
+    DeviceBuf<uint32_t> q_flip_gaps; // rtmi_scene_attach_flips: [n_prims] | [n_items], or empty
     // radiance queries (include/rtmi_radiance.h), grow-only, freed with the handle: the per-sample buffer and the two
     // per-ray outputs of a host-form batch (its rays go through q_rays and q_time); the chunk counter of the persistent
     // wavefronts is the word behind the status words
-    Rad3 *rad_samples = nullptr; // [n][spp]
-    size_t rad_samples_bytes = 0;
-    float *rad_out = nullptr;    // mean [n][3] | stderr [n][3]
-    size_t rad_out_bytes = 0;
-    char *px_mem = nullptr;      // per-pixel adaptive sampling, blocking form: scratch | linear | stderr | spp | rgb8
-    size_t px_mem_bytes = 0;
+    DeviceBuf<Rad3> rad_samples; // [n][spp]
+    DeviceBuf<float> rad_out;    // mean [n][3] | stderr [n][3]
+    DeviceBuf<char> px_mem;      // per-pixel adaptive sampling, blocking form: scratch | linear | stderr | spp | rgb8
     // next-event estimation (include/rtmi_nee.h): the attached light table and per-primitive light index, freed with the
     // handle
     bool has_lights = false;
-    NeeLight *nee_lights = nullptr;    // [max(n, 1)]
-    int32_t *nee_prim_light = nullptr; // [max(n_prims, 1)]
+    DeviceBuf<NeeLight> nee_lights;    // [max(n, 1)]
+    DeviceBuf<int32_t> nee_prim_light; // [max(n_prims, 1)]
     uint32_t nee_n = 0;
     // light tree (include/rtmi_light_tree.h): the attached nodes (64-B aligned pairs) and paths, freed with the handle
     bool has_light_tree = false;
-    float4 *lt_nodes = nullptr; // [max(lt_n, 2)][2]
-    uint2 *lt_paths = nullptr;  // [max(lt_n / 2, 1)]
+    DeviceBuf<float4> lt_nodes; // [max(lt_n, 2)][2]
+    DeviceBuf<uint2> lt_paths;  // [max(lt_n / 2, 1)]
     uint32_t lt_n = 0;          // slots: 2 * lights
     // environment lighting (include/rtmi_env.h): the attached map and its tables, freed with the handle
     bool has_env = false;
-    float4 *env_texels = nullptr; // [h][w] {r, g, b, 0}
-    float *env_tables = nullptr;  // row_cdf [h] | row_p [h] | col_cdf [h][w] | col_p [h][w]
+    DeviceBuf<float4> env_texels; // [h][w] {r, g, b, 0}
+    DeviceBuf<float> env_tables;  // row_cdf [h] | row_p [h] | col_cdf [h][w] | col_p [h][w]
     uint32_t env_w = 0, env_h = 0;
     bool env_sampled = false;     // the map's total weight is > 0
 };
@@ -217,8 +201,10 @@ void parked_drop(int device) {
     if (it->second.ptr) (void)hipFree(it->second.ptr);
     g_parked.erase(it);
 }
-// parks `ptr` (no kernel uses it any more) unless a larger one is parked already; the loser is freed
-void parked_give(int device, void *ptr, size_t bytes) {
+// parks the allocation of `from` (no kernel uses it any more) unless a larger one is parked already; the loser is freed
+void parked_give(int device, DeviceBuf<Rad3> &from) {
+    size_t bytes = 0;
+    void *const ptr = from.give(&bytes);
     std::lock_guard<std::mutex> lock(g_parked_mu);
     ParkedSamples &slot = g_parked[device];
     if (slot.ptr && slot.bytes >= bytes) { (void)hipFree(ptr); return; }
@@ -248,8 +234,7 @@ static int upload(rtmi_scene *s, const T *src, size_t n, const T **dst) {
     *dst = nullptr;
     size_t bytes = (n ? n : 1) * sizeof(T);
     void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    s->allocs.push_back(p);
+    HIP_TRY(s->allocs.add(&p, bytes));
     if (n) HIP_TRY(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
     *dst = reinterpret_cast<const T *>(p);
     return RTMI_OK;
@@ -574,8 +559,8 @@ extern "C" int rtmi_scene_create(const rtmi_scene_desc *d, int device, rtmi_scen
     for (uint32_t i = 0; i < d->n_items; i++)
         if (d->items[i].flags & (RTMI_ITEMFLAG_SAVE_T0 | RTMI_ITEMFLAG_DEFERRED | RTMI_ITEMFLAG_NESTED_MEDIUM)) s->needs_insd = true;
     // one word more than the status words: the chunk counter of the radiance queries (rtmi_radiance.h)
-    if (hipMalloc(reinterpret_cast<void **>(&s->status), (RTMI_STATUS_WORDS + 1) * sizeof(unsigned int)) != hipSuccess ||
-        hipMemset(s->status, 0, (RTMI_STATUS_WORDS + 1) * sizeof(unsigned int)) != hipSuccess) {
+    if (s->status.alloc((RTMI_STATUS_WORDS + 1) * sizeof(unsigned int)) != hipSuccess ||
+        hipMemset(s->status.ptr, 0, (RTMI_STATUS_WORDS + 1) * sizeof(unsigned int)) != hipSuccess) {
         rtmi_scene_destroy(s);
         return fail(RTMI_ERR_DEVICE, "allocating the status word failed");
     }
@@ -585,11 +570,11 @@ extern "C" int rtmi_scene_create(const rtmi_scene_desc *d, int device, rtmi_scen
         s->slots = cus * 4 * 5; // 4 SIMDs x up to 5 wavefronts: capacity of the spill buffer; a launch uses cus * 4 * its waves per SIMD
     }
     for (int i = 0; i < 3; i++)
-        if (hipEventCreate(&s->ev[i]) != hipSuccess) {
+        if (hipEventCreate(&s->ev[i].e) != hipSuccess) {
             rtmi_scene_destroy(s);
             return fail(RTMI_ERR_DEVICE, "hipEventCreate failed");
         }
-    if (hipEventCreateWithFlags(&s->busy, hipEventDisableTiming) != hipSuccess) {
+    if (hipEventCreateWithFlags(&s->busy.e, hipEventDisableTiming) != hipSuccess) {
         rtmi_scene_destroy(s);
         return fail(RTMI_ERR_DEVICE, "hipEventCreate failed");
     }
@@ -597,49 +582,15 @@ extern "C" int rtmi_scene_create(const rtmi_scene_desc *d, int device, rtmi_scen
     return RTMI_OK;
 }
 
+// The members free themselves (rtmi_hostkit.hpp); only the per-sample buffer has somewhere else to go.  Works on the
+// half-built handle of a failed rtmi_scene_create as well.
 extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    for (void *p : s->allocs) (void)hipFree(p);
-    for (void *p : s->f64_allocs) (void)hipFree(p);
-    if (s->f64_samples) (void)hipFree(s->f64_samples);
-    if (s->ad_state) (void)hipFree(s->ad_state);
-    if (s->ad_lists) (void)hipFree(s->ad_lists);
-    if (s->ad_stderr) (void)hipFree(s->ad_stderr);
-    if (s->ad_spp) (void)hipFree(s->ad_spp);
-    if (s->h_ad_count) (void)hipHostFree(s->h_ad_count);
-    if (s->ft_state) (void)hipFree(s->ft_state);
-    if (s->ft_planes) (void)hipFree(s->ft_planes);
-    if (s->q_rays) (void)hipFree(s->q_rays);
-    if (s->q_time) (void)hipFree(s->q_time);
-    if (s->q_out) (void)hipFree(s->q_out);
-    if (s->q_flip_gaps) (void)hipFree(s->q_flip_gaps);
-    if (s->rad_samples) (void)hipFree(s->rad_samples);
-    if (s->rad_out) (void)hipFree(s->rad_out);
-    if (s->px_mem) (void)hipFree(s->px_mem);
-    if (s->nee_lights) (void)hipFree(s->nee_lights);
-    if (s->nee_prim_light) (void)hipFree(s->nee_prim_light);
-    if (s->lt_nodes) (void)hipFree(s->lt_nodes);
-    if (s->lt_paths) (void)hipFree(s->lt_paths);
-    if (s->env_texels) (void)hipFree(s->env_texels);
-    if (s->env_tables) (void)hipFree(s->env_tables);
-    if (s->partial) (void)hipFree(s->partial);
-    if (s->samples) { // parked for the next handle on this device (see g_parked); no kernel may still write it
-        if (s->busy_recorded) (void)hipEventSynchronize(s->busy);
-        parked_give(s->device, s->samples, s->samples_bytes);
+    if (s->samples.ptr) { // parked for the next handle on this device (see g_parked); no kernel may still write it
+        if (s->busy_recorded) (void)hipEventSynchronize(s->busy.e);
+        parked_give(s->device, s->samples);
     }
-    if (s->spill) (void)hipFree(s->spill);
-    if (s->texels) (void)hipFree(s->texels);
-    if (s->d_sig) (void)hipFree(s->d_sig);
-    if (s->rr_bounces) (void)hipFree(s->rr_bounces);
-    if (s->status) (void)hipFree(s->status);
-    if (s->h_texels) (void)hipHostFree(s->h_texels);
-    if (s->h_partial) (void)hipHostFree(s->h_partial);
-    if (s->busy) (void)hipEventDestroy(s->busy);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
-    for (int i = 0; i < 3; i++)
-        if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
     delete s;
 }
 
@@ -669,78 +620,62 @@ static int check_params(const rtmi_render_params *p) {
 struct BusyMark {
     rtmi_scene *s;
     hipStream_t st;
-    ~BusyMark() { if (s && hipEventRecord(s->busy, st) == hipSuccess) s->busy_recorded = true; } // s = NULL: no call begun
+    ~BusyMark() { if (s && hipEventRecord(s->busy.e, st) == hipSuccess) s->busy_recorded = true; } // s = NULL: no call begun
 };
 
-// Grow-only device buffer of the handle: reallocated when a call needs more than `have` bytes.  A render of this handle
+// Grow-only device buffer of the handle: reallocated when a call needs more than it holds.  A render of this handle
 // enqueued asynchronously (rtmi_render_device) may still use the old buffer: it is released after that render.
 template <typename T>
-static int grow(rtmi_scene *s, T *&ptr, size_t &have, size_t want) {
-    if (want <= have) return RTMI_OK;
-    if (ptr) {
-        if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
-        HIP_TRY(hipFree(ptr));
-        ptr = nullptr;
-        have = 0;
+static int grow(rtmi_scene *s, DeviceBuf<T> &buf, size_t want) {
+    if (want <= buf.bytes) return RTMI_OK;
+    if (buf.ptr) {
+        if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
+        HIP_TRY(buf.release());
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ptr), want));
-    have = want;
+    HIP_TRY(buf.alloc(want));
     return RTMI_OK;
 }
 
 // pinned host mirror of a texel buffer (grow-only)
-static int ensure_host_texels(rtmi_texel **h, size_t *have, size_t want) {
-    if (want <= *have) return RTMI_OK;
-    if (*h) { HIP_TRY(hipHostFree(*h)); *h = nullptr; *have = 0; }
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(h), want * sizeof(rtmi_texel), hipHostMallocDefault));
-    *have = want;
+static int grow_host_texels(PinnedBuf<rtmi_texel> &h, size_t ntex) {
+    HIP_TRY(h.grow(ntex * sizeof(rtmi_texel)));
     return RTMI_OK;
 }
 
 // the handle's framebuffer for `ntex` texels and its pinned host mirror
 static int reserve_texels(rtmi_scene *s, size_t ntex) {
-    if (int rc = grow(s, s->texels, s->texels_bytes, ntex * sizeof(rtmi_texel))) return rc;
-    return ensure_host_texels(&s->h_texels, &s->h_texel_count, ntex);
+    if (int rc = grow(s, s->texels, ntex * sizeof(rtmi_texel))) return rc;
+    return grow_host_texels(s->h_texels, ntex);
 }
 
-// adaptive sampling's buffers (include/rtmi_adaptive.h; NEE shares them), grown together for T tiles
+// adaptive sampling's buffers (include/rtmi_adaptive.h; NEE shares them), grown together for T tiles.  Each knows its own
+// size and is empty after a failed allocation, so a call goes on only when all four hold T tiles.
 static int grow_adaptive(rtmi_scene *s, uint32_t T) {
-    if (T <= s->ad_tiles) return RTMI_OK;
-    const auto bytes = [](size_t tiles, size_t out[4]) {
-        out[0] = tiles * 64 * 9 * sizeof(double);
-        out[1] = (2 * tiles + 1) * sizeof(uint32_t);
-        out[2] = tiles * 64 * 3 * sizeof(float);
-        out[3] = tiles * 64 * sizeof(uint32_t);
-    };
-    size_t have[4], want[4];
-    bytes(s->ad_tiles, have);
-    bytes(T, want);
-    s->ad_tiles = 0; // nothing is valid until all four have grown
+    const size_t tiles = T;
     int rc;
-    if ((rc = grow(s, s->ad_state, have[0], want[0])) || (rc = grow(s, s->ad_lists, have[1], want[1])) ||
-        (rc = grow(s, s->ad_stderr, have[2], want[2])) || (rc = grow(s, s->ad_spp, have[3], want[3])))
+    if ((rc = grow(s, s->ad_state, tiles * 64 * 9 * sizeof(double))) || (rc = grow(s, s->ad_lists, (2 * tiles + 1) * sizeof(uint32_t))) ||
+        (rc = grow(s, s->ad_stderr, tiles * 64 * 3 * sizeof(float))) || (rc = grow(s, s->ad_spp, tiles * 64 * sizeof(uint32_t))))
         return rc;
-    s->ad_tiles = T;
     return RTMI_OK;
 }
 // adaptive sampling's first list of active tiles: all of them (NEE's resolve walks it as well)
 static int list_all_tiles(rtmi_scene *s, uint32_t T, hipStream_t stream) {
     std::vector<uint32_t> all(T);
     for (uint32_t t = 0; t < T; t++) all[t] = t;
-    HIP_TRY(hipMemcpyAsync(s->ad_lists, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(s->ad_lists.ptr, all.data(), (size_t)T * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream)); // (`all` is pageable and goes out of scope)
     return RTMI_OK;
 }
 
 static int ensure_streams(rtmi_scene *s) {
-    if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (!s->copy_stream) {
+    if (!s->stream.s) HIP_TRY(hipStreamCreateWithFlags(&s->stream.s, hipStreamNonBlocking));
+    if (!s->copy_stream.s) {
         // The progress polls must not queue behind the render.  The runtime gives streams at most GPU_MAX_HW_QUEUES
         // hardware queues per priority and shares the least used one beyond that (with 2, the two streams of a handle
         // landed on one queue and every poll waited for the whole render); another priority is another pool.
         int least = 0, greatest = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&s->copy_stream, hipStreamNonBlocking, greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&s->copy_stream.s, hipStreamNonBlocking, greatest));
     }
     return RTMI_OK;
 }
@@ -749,8 +684,21 @@ static int ensure_streams(rtmi_scene *s) {
 // render of this handle may still run, the buffers of the call may be reallocated
 static int begin_blocking(rtmi_scene *s) {
     if (int rc = ensure_streams(s)) return rc;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
     return RTMI_OK;
+}
+
+// Replaces an attached table (the caller holds s->mu and has selected s->device), in this order: waits for the render
+// that may read the old one, drops the old buffers, clears the flag (NULL: the table has none), then `fill` allocates
+// and copies (a detach returns RTMI_OK at once).  After a failure the flag is false and every buffer is empty or owned.
+template <typename Fill, typename... Old>
+static int replace_attached(rtmi_scene *s, bool *flag, Fill &&fill, Old &...old) {
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
+    hipError_t released = hipSuccess;
+    ((released = released == hipSuccess ? old.release() : released), ...);
+    HIP_TRY(released);
+    if (flag) *flag = false;
+    return fill();
 }
 
 // argument checks of the whole-image modes (adaptive sampling, features, NEE) after their NULL checks, in this order
@@ -788,8 +736,8 @@ static DevParams dev_params(const rtmi_scene *s, const rtmi_render_params *p) {
     P.ntiles_local = local_tiles_of(p, p->tile_rank);
     P.stack_depth = s->meta.max_bvh_depth + 1u;
     P.shade_threshold = p->shade_threshold ? (p->shade_threshold > 64u ? 64u : p->shade_threshold) : 40u; // tuned on C2..C5 (r02 sweep: 16..48)
-    P.status = s->status;
-    P.queue = s->status + 1;
+    P.status = s->status.ptr;
+    P.queue = s->status.ptr + 1;
     P.sky = (p->flags & RTMI_FLAG_SKY) ? 1u : 0u;
     P.ext = ((p->flags & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) | ((p->flags & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u) |
             ((p->flags & RTMI_FLAG_TEST_OVERFLOW) ? RTMI_EXT_TEST_OVERFLOW : 0u);
@@ -823,24 +771,24 @@ static int plan_traversal(rtmi_scene *s, const rtmi_render_params *p, bool coop,
     ext = use_alt || s->meta.n_nodes != 0u;
     P.coop_cap = ext ? RTMI_COOP_CAP : P.spill_cap;
     if (coop)
-        if (int rc = grow(s, s->spill, s->spill_bytes, (size_t)s->slots * P.spill_cap * sizeof(uint2))) return rc;
-    P.spill = s->spill;
+        if (int rc = grow(s, s->spill, (size_t)s->slots * P.spill_cap * sizeof(uint2))) return rc;
+    P.spill = s->spill.ptr;
     return RTMI_OK;
 }
 
 // Pass protocol of the status words (rtmi_types.hpp), which progress reporting reads: a call starts with its overflow
 // word, the unit counter and the finished-units / finished-samples words at zero (the sticky word stays) ...
 static int begin_passes(rtmi_scene *s, hipStream_t stream) {
-    HIP_TRY(hipMemsetAsync(s->status, 0, 2 * sizeof(unsigned int), stream));
-    HIP_TRY(hipMemsetAsync(s->status + 3, 0, 2 * sizeof(unsigned int), stream));
+    HIP_TRY(hipMemsetAsync(s->status.ptr, 0, 2 * sizeof(unsigned int), stream));
+    HIP_TRY(hipMemsetAsync(s->status.ptr + 3, 0, 2 * sizeof(unsigned int), stream));
     s->units_total = 0;
     return RTMI_OK;
 }
 // ... and every pass ends with rtmi_pass_end_kernel: the pass's units from [1] to [3], its samples onto [4]
 static int units_done(rtmi_scene *s, uint64_t *units) { // read through the copy stream while a launch runs
     unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(w, s->status, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    HIP_TRY(hipMemcpyAsync(w, s->status.ptr, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream.s));
+    HIP_TRY(hipStreamSynchronize(s->copy_stream.s));
     *units = (uint64_t)w[3] + w[1]; // finished passes + units handed out in the running one
     return RTMI_OK;
 }
@@ -865,7 +813,7 @@ static int run_passes(rtmi_scene *s, DevParams &P, hipStream_t stream, uint32_t 
         s->units_total += nitems;
         const bool last = k + P.pass_cnt >= count;
         if (int rc = launch(blocks, k == 0, last)) return rc;
-        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status, (unsigned int)nitems, P.pass_cnt,
+        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status.ptr, (unsigned int)nitems, P.pass_cnt,
                            finish && last ? 1 : 0);
         HIP_TRY(hipGetLastError());
     }
@@ -875,9 +823,9 @@ static int run_passes(rtmi_scene *s, DevParams &P, hipStream_t stream, uint32_t 
 // this call's overflow word of a scene whose kernels have finished
 static int check_overflow(rtmi_scene *s) {
     unsigned int st = 0;
-    HIP_TRY(hipMemcpy(&st, s->status, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, s->status.ptr, sizeof(st), hipMemcpyDeviceToHost));
     if (st != 0) {
-        HIP_TRY(hipMemset(s->status + 2, 0, sizeof(unsigned int))); // reported here: not again by rtmi_scene_status
+        HIP_TRY(hipMemset(s->status.ptr + 2, 0, sizeof(unsigned int))); // reported here: not again by rtmi_scene_status
         return fail(RTMI_ERR_DEVICE, "cooperative traversal pool overflow (results invalid, texels poisoned): use RTMI_FLAG_SYNC");
     }
     return RTMI_OK;
@@ -902,8 +850,8 @@ static void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *s
 // the same from the scene's events: ev[0] start, ev[1] before the last resolve, ev[2] end (all completed)
 static int fill_stats_from_events(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, PassCounts counts = {}) {
     float ms_r = 0.f, ms_all = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0], s->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[2]));
+    HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0].e, s->ev[1].e));
+    HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0].e, s->ev[2].e));
     fill_stats(s, p, stats, ms_r, ms_all, counts);
     return RTMI_OK;
 }
@@ -943,27 +891,26 @@ static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t
     uint64_t max_pass = want / per_sample;
     if (max_pass < 1) max_pass = 1;
     if (max_pass > p->ns) max_pass = p->ns;
-    if (max_pass * per_sample > s->samples_bytes) {
+    if (max_pass * per_sample > s->samples.bytes) {
         if (!p->sample_buffer_bytes) { // default budget: never more than 3/4 of what is free on the device
             size_t free_b = 0, total_b = 0;
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            const size_t avail = (free_b + s->samples_bytes + parked_bytes(s->device)) / 4 * 3;
+            const size_t avail = (free_b + s->samples.bytes + parked_bytes(s->device)) / 4 * 3;
             if (max_pass * per_sample > avail) max_pass = avail / per_sample ? avail / per_sample : 1;
         }
-        if (max_pass * per_sample > s->samples_bytes) {
+        if (max_pass * per_sample > s->samples.bytes) {
             const size_t need = max_pass * per_sample;
             void *taken = nullptr;
             size_t taken_bytes = 0;
             if (parked_take(s->device, need, &taken, &taken_bytes)) { // a destroyed handle's buffer: no hipMalloc
-                if (s->samples) { // (smaller than the one taken) another handle may take it next: no render of this one may still write it
-                    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
-                    parked_give(s->device, s->samples, s->samples_bytes);
+                if (s->samples.ptr) { // (smaller than the one taken) another handle may take it next: no render of this one may still write it
+                    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
+                    parked_give(s->device, s->samples);
                 }
-                s->samples = static_cast<Rad3 *>(taken);
-                s->samples_bytes = taken_bytes;
+                s->samples.adopt(taken, taken_bytes);
             } else {
                 parked_drop(s->device); // too small to serve this call: its memory may be what the allocation needs
-                if (int rc = grow(s, s->samples, s->samples_bytes, need)) return rc;
+                if (int rc = grow(s, s->samples, need)) return rc;
             }
         }
     }
@@ -985,7 +932,7 @@ static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t
     if (chunk_spp < 1u) chunk_spp = 1u;
     // one pass when everything fits (its last chunk may be shorter); otherwise whole chunks per pass
     pass_ns = max_pass >= p->ns ? p->ns : (uint32_t)(max_pass / chunk_spp) * chunk_spp;
-    return grow(s, s->partial, s->partial_bytes, (size_t)ntiles_local * 64 * 3 * sizeof(double)); // f64 sums carried between passes
+    return grow(s, s->partial, (size_t)ntiles_local * 64 * 3 * sizeof(double)); // f64 sums carried between passes
 }
 
 // (Re)allocates what a render with these parameters needs BEFORE the caller starts its event clock: an allocation of tens
@@ -993,7 +940,7 @@ static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t
 static int reserve_before_clock(rtmi_scene *s, const rtmi_render_params *p) {
     const uint32_t ntiles_local = local_tiles_of(p, p->tile_rank);
     if (ntiles_local == 0) return RTMI_OK;
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // the buffer may be reallocated: no render may still use it
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e)); // the buffer may be reallocated: no render may still use it
     uint32_t chunk_spp = 0, pass_ns = 0;
     return plan_and_reserve(s, p, ntiles_local, chunk_spp, pass_ns);
 }
@@ -1017,7 +964,7 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     // device side of the thread model: this render starts after the previous one of this handle has finished (a no-op
     // when both were given the same stream)
-    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+    if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy.e, 0));
     BusyMark busy_mark{s, stream};
 
     DevParams P = dev_params(s, p);
@@ -1036,10 +983,10 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     if (rc) return rc;
     P.chunk_spp = chunk_spp;
     P.pass_stride = pass_ns;
-    P.samples = s->samples;
+    P.samples = s->samples.ptr;
     const DevCamera C = dev_camera(cam);
 
-    if (stats) HIP_TRY(hipEventRecord(s->ev[0], stream));
+    if (stats) HIP_TRY(hipEventRecord(s->ev[0].e, stream));
     const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sigf = (p->flags & RTMI_FLAG_PATH_SIG) != 0u;
     const dim3 block(64 * WAVES_PER_BLOCK);
     const size_t dyn_lds = (size_t)WAVES_PER_BLOCK * 2u * P.stack_depth * 64u * sizeof(uint32_t);
@@ -1129,15 +1076,15 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
 #undef RTMI_LAUNCH
 #undef RTMI_LAUNCH_COOP
     HIP_TRY(hipGetLastError());
-    if (stats && last) HIP_TRY(hipEventRecord(s->ev[1], stream));
-    hipLaunchKernelGGL(rtmi_resolve_kernel, dim3((ntex + 255) / 256), dim3(256), 0, stream, s->samples, s->partial,
+    if (stats && last) HIP_TRY(hipEventRecord(s->ev[1].e, stream));
+    hipLaunchKernelGGL(rtmi_resolve_kernel, dim3((ntex + 255) / 256), dim3(256), 0, stream, s->samples.ptr, s->partial.ptr,
                        reinterpret_cast<rtmi_texel *>(d_texels), P, first ? 1 : 0, last ? 1 : 0,
                        (p->flags & RTMI_FLAG_PROGRESSIVE) ? 1 : 0);
     return RTMI_OK;
     });
     if (rc || !stats) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
-    HIP_TRY(hipEventSynchronize(s->ev[2]));
+    HIP_TRY(hipEventRecord(s->ev[2].e, stream));
+    HIP_TRY(hipEventSynchronize(s->ev[2].e));
     if ((rc = fill_stats_from_events(s, p, stats, counts))) return rc;
     return check_overflow(s); // (the kernels have finished: ev[2] was waited for)
 }
@@ -1155,10 +1102,10 @@ extern "C" int rtmi_scene_status(rtmi_scene *s, uint32_t *overflows) {
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
     unsigned int st = 0;
-    HIP_TRY(hipMemcpy(&st, s->status + 2, sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, s->status.ptr + 2, sizeof(st), hipMemcpyDeviceToHost));
     if (overflows) *overflows = st;
     if (st != 0) {
-        HIP_TRY(hipMemset(s->status + 2, 0, sizeof(unsigned int)));
+        HIP_TRY(hipMemset(s->status.ptr + 2, 0, sizeof(unsigned int)));
         return fail(RTMI_ERR_DEVICE, "cooperative traversal pool overflow in an earlier render call (its texels are poisoned): use RTMI_FLAG_SYNC");
     }
     return RTMI_OK;
@@ -1257,34 +1204,34 @@ extern "C" int rtmi_render(rtmi_scene *s, const rtmi_camera *cam, const rtmi_ren
     p.flags &= ~RTMI_FLAG_PATH_SIG;
     p.path_sig = 0;
     if (out_path_sig) {
-        if ((rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))) return rc;
+        if ((rc = grow(s, s->d_sig, ntex * sizeof(unsigned long long)))) return rc;
         p.flags |= RTMI_FLAG_PATH_SIG;
-        p.path_sig = reinterpret_cast<uint64_t>(s->d_sig);
+        p.path_sig = reinterpret_cast<uint64_t>(s->d_sig.ptr);
     }
     if (p.progress_fn) {
         // asynchronous launch, then wait and report progress; stats from the scene's events afterwards
         if ((rc = reserve_before_clock(s, &p))) return rc;
-        HIP_TRY(hipEventRecord(s->ev[0], s->stream));
-        rc = render_device_locked(s, cam, &p, s->texels, s->stream, nullptr);
+        HIP_TRY(hipEventRecord(s->ev[0].e, s->stream.s));
+        rc = render_device_locked(s, cam, &p, s->texels.ptr, s->stream.s, nullptr);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(s->ev[2], s->stream));
+        HIP_TRY(hipEventRecord(s->ev[2].e, s->stream.s));
         rtmi_scene *one[1] = {s};
-        rc = wait_with_progress(one, &s->ev[2], 1, &p);
+        rc = wait_with_progress(one, &s->ev[2].e, 1, &p);
         if (rc) return rc;
         if ((rc = check_overflow(s))) return rc;
         if (stats) {
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[2].e));
             fill_stats(s, &p, stats, ms, ms);
         }
     } else {
         rtmi_stats local{};
-        rc = render_device_locked(s, cam, &p, s->texels, s->stream, stats ? stats : &local);
+        rc = render_device_locked(s, cam, &p, s->texels.ptr, s->stream.s, stats ? stats : &local);
         if (rc) return rc;
     }
-    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
-    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+    HIP_TRY(hipMemcpy(s->h_texels.ptr, s->texels.ptr, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig.ptr, ntex, out_path_sig))) return rc;
+    return rtmi_untile(&p, s->h_texels.ptr, out_linear, out_rgb8);
 }
 
 // RTMI_FLAG_PROGRESSIVE: the framebuffer of the running rtmi_render call as it stands (called from its progress callback:
@@ -1298,22 +1245,22 @@ extern "C" int rtmi_partial_image(rtmi_scene *s, const rtmi_render_params *p_in,
     *spp_done = 0;
     rtmi_render_params p = *p_in;
     const size_t ntex = (size_t)rtmi_local_tiles(&p) * 64;
-    if (!s->texels || ntex * sizeof(rtmi_texel) > s->texels_bytes || !s->copy_stream) return fail(RTMI_ERR_INVALID, "no rtmi_render call of this size is running on the handle");
+    if (!s->texels.ptr || ntex * sizeof(rtmi_texel) > s->texels.bytes || !s->copy_stream.s) return fail(RTMI_ERR_INVALID, "no rtmi_render call of this size is running on the handle");
     HIP_TRY(hipSetDevice(s->device));
-    if ((rc = ensure_host_texels(&s->h_partial, &s->h_partial_count, ntex))) return rc;
+    if ((rc = grow_host_texels(s->h_partial, ntex))) return rc;
     unsigned int w[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0}, w2[RTMI_STATUS_WORDS] = {0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(w, s->status, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream));
+    HIP_TRY(hipMemcpyAsync(w, s->status.ptr, sizeof(w), hipMemcpyDeviceToHost, s->copy_stream.s));
+    HIP_TRY(hipStreamSynchronize(s->copy_stream.s));
     if (w[4] == 0u) return RTMI_OK; // no pass has finished: nothing to show yet
     for (int attempt = 0; attempt < 2; attempt++) { // a consistent snapshot unless passes end faster than the copy
-        HIP_TRY(hipMemcpyAsync(s->h_partial, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost, s->copy_stream));
-        HIP_TRY(hipMemcpyAsync(w2, s->status, sizeof(w2), hipMemcpyDeviceToHost, s->copy_stream));
-        HIP_TRY(hipStreamSynchronize(s->copy_stream));
+        HIP_TRY(hipMemcpyAsync(s->h_partial.ptr, s->texels.ptr, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost, s->copy_stream.s));
+        HIP_TRY(hipMemcpyAsync(w2, s->status.ptr, sizeof(w2), hipMemcpyDeviceToHost, s->copy_stream.s));
+        HIP_TRY(hipStreamSynchronize(s->copy_stream.s));
         if (w2[4] == w[4]) break;
         w[4] = w2[4];
     }
     *spp_done = w[4] < p.ns ? w[4] : p.ns;
-    return rtmi_untile(&p, s->h_partial, out_linear, out_rgb8);
+    return rtmi_untile(&p, s->h_partial.ptr, out_linear, out_rgb8);
 }
 
 // ---- several GPUs of this process behind one handle: scene replicated, tiles t % n, one gather on devices[0] -----
@@ -1378,25 +1325,22 @@ bool force_rccl() {
 
 // The persistent multi-device handle.  Everything a render needs between calls lives here; rtmi_multi_render only
 // enqueues kernels and the one gather, waits, copies the gathered framebuffer out and un-tiles it.
-struct rtmi_multi {
+struct RTMI_HIDDEN rtmi_multi {
     std::vector<int> devices;
     bool distinct = true;
     std::vector<rtmi_scene *> scenes;    // one per listed device (a device listed twice holds two scenes)
-    std::vector<rtmi_texel *> texels;    // per device: tile-packed local framebuffer (grow-only)
-    size_t stride = 0;                   // texels per rank in those buffers and in `gathered`
-    rtmi_texel *gathered = nullptr;      // on devices[0]: n x stride texels, rank-major
-    rtmi_texel *h_gathered = nullptr;    // its pinned host mirror
-    size_t h_count = 0;
+    std::vector<DeviceBuf<rtmi_texel>> texels; // per device: tile-packed local framebuffer (grow-only)
+    DeviceBuf<rtmi_texel> gathered;      // on devices[0]: n x stride texels, rank-major
+    PinnedBuf<rtmi_texel> h_gathered;    // its pinned host mirror
     CommSet *commset = nullptr;          // RCCL communicators (distinct devices; n > 1 or RTMI_FORCE_RCCL), checked out at create
     std::mutex mu;                       // render calls on one handle serialise (rtmi.h, thread model)
 };
 
 extern "C" void rtmi_multi_destroy(rtmi_multi *m) {
     if (!m) return;
-    for (size_t i = 0; i < m->texels.size(); i++)
-        if (m->texels[i]) { (void)hipSetDevice(m->devices[i]); (void)hipFree(m->texels[i]); }
-    if (m->gathered) { (void)hipSetDevice(m->devices[0]); (void)hipFree(m->gathered); }
-    if (m->h_gathered) (void)hipHostFree(m->h_gathered);
+    for (size_t i = 0; i < m->texels.size(); i++) // each device's buffer is released with that device selected
+        if (m->texels[i].ptr) { (void)hipSetDevice(m->devices[i]); (void)m->texels[i].release(); }
+    if (m->gathered.ptr) { (void)hipSetDevice(m->devices[0]); (void)m->gathered.release(); }
     for (rtmi_scene *s : m->scenes) rtmi_scene_destroy(s);
     if (m->commset) { // back to the pool: the next handle on this device list takes it over
         std::lock_guard<std::mutex> lock(g_rccl_mutex);
@@ -1422,7 +1366,7 @@ extern "C" int rtmi_multi_create(const rtmi_scene_desc *desc, const int *devices
     }
     m->devices.assign(devices, devices + n);
     m->scenes.assign(n, nullptr);
-    m->texels.assign(n, nullptr);
+    m->texels = std::vector<DeviceBuf<rtmi_texel>>(n);
     // uploads to all devices at once: one host thread per device (hipMalloc / hipMemcpy of one device do not wait for
     // another's; the derived records — leaf, shading, pool-encoded nodes — are built per thread as well)
     std::vector<int> rcs(n, RTMI_OK);
@@ -1483,22 +1427,21 @@ static int multi_params(const rtmi_multi *m, const rtmi_render_params *p_in, std
 // framebuffers of a render of this size (grow-only); every rank padded to rank 0's size (the largest)
 static int multi_reserve_texels(rtmi_multi *m, const rtmi_render_params *p0) {
     const uint32_t n = (uint32_t)m->devices.size();
-    const size_t stride = (size_t)local_tiles_of(p0, 0) * 64;
-    if (stride > m->stride) {
-        m->stride = 0; // nothing is valid until every allocation below has succeeded
+    const size_t want = (size_t)local_tiles_of(p0, 0) * 64 * sizeof(rtmi_texel);
+    // what every buffer holds: the smallest one decides (a buffer whose allocation failed is empty)
+    size_t have = m->gathered.bytes / n;
+    for (uint32_t i = 0; i < n; i++) have = std::min(have, m->texels[i].bytes);
+    if (want > have) {
         for (uint32_t i = 0; i < n; i++) {
             HIP_TRY(hipSetDevice(m->devices[i]));
-            if (m->texels[i]) { HIP_TRY(hipFree(m->texels[i])); m->texels[i] = nullptr; }
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->texels[i]), stride * sizeof(rtmi_texel)));
+            HIP_TRY(m->texels[i].alloc(want));
             // ranks with fewer tiles than rank 0 never write their padding: zero it once
-            HIP_TRY(hipMemset(m->texels[i], 0, stride * sizeof(rtmi_texel)));
+            HIP_TRY(hipMemset(m->texels[i].ptr, 0, want));
         }
         HIP_TRY(hipSetDevice(m->devices[0]));
-        if (m->gathered) { HIP_TRY(hipFree(m->gathered)); m->gathered = nullptr; }
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&m->gathered), (size_t)n * stride * sizeof(rtmi_texel)));
-        m->stride = stride;
+        HIP_TRY(m->gathered.alloc((size_t)n * want));
     }
-    return ensure_host_texels(&m->h_gathered, &m->h_count, (size_t)n * m->stride);
+    return grow_host_texels(m->h_gathered, m->gathered.bytes / sizeof(rtmi_texel));
 }
 
 extern "C" int rtmi_multi_prepare(rtmi_multi *m, const rtmi_render_params *p_in) {
@@ -1531,10 +1474,10 @@ extern "C" int rtmi_multi_render(rtmi_multi *m, const rtmi_camera *cam, const rt
         std::lock_guard<std::mutex> slock(s->mu);
         HIP_TRY(hipSetDevice(m->devices[i]));
         if ((rc = reserve_before_clock(s, &params[i]))) return rc;
-        HIP_TRY(hipEventRecord(s->ev[0], s->stream));
-        if ((rc = render_device_locked(s, cam, &params[i], m->texels[i], s->stream, nullptr))) return rc;
-        HIP_TRY(hipEventRecord(s->ev[1], s->stream));
-        done[i] = s->ev[2];
+        HIP_TRY(hipEventRecord(s->ev[0].e, s->stream.s));
+        if ((rc = render_device_locked(s, cam, &params[i], m->texels[i].ptr, s->stream.s, nullptr))) return rc;
+        HIP_TRY(hipEventRecord(s->ev[1].e, s->stream.s));
+        done[i] = s->ev[2].e;
     }
     // the ONE exchange of the path: tile-packed framebuffers -> devices[0]
     if (m->commset) {
@@ -1542,18 +1485,18 @@ extern "C" int rtmi_multi_render(rtmi_multi *m, const rtmi_camera *cam, const rt
         for (uint32_t i = 0; i < n; i++) {
             HIP_TRY(hipSetDevice(m->devices[i]));
             // (recvbuff is read on the root only; the others pass a valid device pointer rather than NULL for argument checkers)
-            RCCL_TRY(g_rccl.Gather(m->texels[i], i == 0 ? m->gathered : m->texels[i], stride * sizeof(rtmi_texel), /*ncclInt8*/ 0, 0, m->commset->comms[i], m->scenes[i]->stream));
+            RCCL_TRY(g_rccl.Gather(m->texels[i].ptr, i == 0 ? m->gathered.ptr : m->texels[i].ptr, stride * sizeof(rtmi_texel), /*ncclInt8*/ 0, 0, m->commset->comms[i], m->scenes[i]->stream.s));
         }
         RCCL_TRY(g_rccl.GroupEnd());
     } else {
         for (uint32_t i = 0; i < n; i++) {
             HIP_TRY(hipSetDevice(m->devices[i]));
-            HIP_TRY(hipMemcpyPeerAsync(m->gathered + (size_t)i * stride, m->devices[0], m->texels[i], m->devices[i], stride * sizeof(rtmi_texel), m->scenes[i]->stream));
+            HIP_TRY(hipMemcpyPeerAsync(m->gathered.ptr + (size_t)i * stride, m->devices[0], m->texels[i].ptr, m->devices[i], stride * sizeof(rtmi_texel), m->scenes[i]->stream.s));
         }
     }
     for (uint32_t i = 0; i < n; i++) {
         HIP_TRY(hipSetDevice(m->devices[i]));
-        HIP_TRY(hipEventRecord(m->scenes[i]->ev[2], m->scenes[i]->stream));
+        HIP_TRY(hipEventRecord(m->scenes[i]->ev[2].e, m->scenes[i]->stream.s));
     }
     if ((rc = wait_with_progress(m->scenes.data(), done.data(), n, p_in))) return rc;
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -1569,8 +1512,8 @@ extern "C" int rtmi_multi_render(rtmi_multi *m, const rtmi_camera *cam, const rt
         }
     }
     HIP_TRY(hipSetDevice(m->devices[0]));
-    HIP_TRY(hipMemcpy(m->h_gathered, m->gathered, (size_t)n * stride * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    return rtmi_untile(&params[0], m->h_gathered, out_linear, out_rgb8);
+    HIP_TRY(hipMemcpy(m->h_gathered.ptr, m->gathered.ptr, (size_t)n * stride * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    return rtmi_untile(&params[0], m->h_gathered.ptr, out_linear, out_rgb8);
 }
 
 // one-shot form: create + render + destroy (pays uploads, allocations and the communicator look-up on every call)
@@ -1772,20 +1715,18 @@ extern "C" int rtmi_scene_attach_f64(rtmi_scene *s, const rtmi_scene_f64 *w) {
     if (w->n_prims && !w->prim_gate) return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_f64: plane prim_gate is NULL");
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running f64 render may read the old planes
-    for (void *p : s->f64_allocs) (void)hipFree(p);
-    s->f64_allocs.clear();
-    s->has_f64 = false;
-    for (const Plane &p : planes) {
-        void *dp = nullptr;
-        HIP_TRY(hipMalloc(&dp, (p.n ? p.n : 1) * sizeof(double)));
-        s->f64_allocs.push_back(dp);
-        if (p.n) HIP_TRY(hipMemcpy(dp, p.src, p.n * sizeof(double), hipMemcpyHostToDevice));
-        *p.dst = static_cast<const double *>(dp);
-    }
-    s->f64 = d;
-    s->has_f64 = true;
-    return RTMI_OK;
+    const auto fill = [&]() -> int { // (a running f64 render may read the old planes)
+        for (const Plane &p : planes) {
+            void *dp = nullptr;
+            HIP_TRY(s->f64_allocs.add(&dp, (p.n ? p.n : 1) * sizeof(double)));
+            if (p.n) HIP_TRY(hipMemcpy(dp, p.src, p.n * sizeof(double), hipMemcpyHostToDevice));
+            *p.dst = static_cast<const double *>(dp);
+        }
+        s->f64 = d;
+        s->has_f64 = true;
+        return RTMI_OK;
+    };
+    return replace_attached(s, &s->has_f64, fill, s->f64_allocs);
 }
 
 extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const rtmi_render_params *p_in, double t_min,
@@ -1803,7 +1744,7 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     if (!s->has_f64) return fail(RTMI_ERR_INVALID, "rtmi_render_f64: no f64 planes attached (rtmi_scene_attach_f64)");
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = begin_blocking(s))) return rc;
-    hipStream_t st = s->stream;
+    hipStream_t st = s->stream.s;
     const uint32_t ntiles = local_tiles_of(&p, 0);
     const bool sig = (p.flags & RTMI_FLAG_PATH_SIG) != 0u;
     // passes (rtmi_f64_plan.hpp): RTMI_SAMPLE_SLOT_BYTES_F64 per pixel sample, at most 45 GiB and 2^32 - 1 slots per pass;
@@ -1817,32 +1758,22 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     uint32_t chunk_spp = 0, pass_ns = 0;
     if (!rtmi_f64_plan(ntiles, p.ns, p.sample_buffer_bytes, free_b, (uint64_t)s->slots * 4u, p.spp_chunks, chunk_spp, pass_ns))
         return fail(RTMI_ERR_UNSUPPORTED, "rtmi_render_f64: image too large for one sample per pass");
-    // call-local device memory, freed on every return path
-    struct Scratch {
-        std::vector<void *> v;
-        ~Scratch() { for (void *q : v) (void)hipFree(q); }
-        int get(size_t bytes, void **out) {
-            *out = nullptr;
-            if (hipMalloc(out, bytes ? bytes : 1) != hipSuccess) return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc failed");
-            v.push_back(*out);
-            return RTMI_OK;
-        }
-    } scratch;
-    double *d_samples = nullptr, *d_acc = nullptr, *d_lin = nullptr;
+    double *d_acc = nullptr, *d_lin = nullptr;
     uint32_t *d_q = nullptr, *d_queue = nullptr;
     unsigned long long *d_sig = nullptr;
     const size_t texels = (size_t)ntiles * 64;
-    if (grow(s, s->f64_samples, s->f64_samples_bytes, (size_t)pass_ns * per_sample)) // grows to the largest pass planned
+    if (grow(s, s->f64_samples, (size_t)pass_ns * per_sample)) // grows to the largest pass planned
         return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc of the per-sample buffer failed");
-    d_samples = s->f64_samples;
-    if ((rc = scratch.get(texels * 3 * sizeof(double), reinterpret_cast<void **>(&d_acc)))) return rc;
-    if ((rc = scratch.get(texels * 3 * sizeof(double), reinterpret_cast<void **>(&d_lin)))) return rc;
-    if ((rc = scratch.get(texels * sizeof(uint32_t), reinterpret_cast<void **>(&d_q)))) return rc;
-    if ((rc = scratch.get(sizeof(uint32_t), reinterpret_cast<void **>(&d_queue)))) return rc;
-    if (sig) {
-        if ((rc = scratch.get(texels * sizeof(unsigned long long), reinterpret_cast<void **>(&d_sig)))) return rc;
-        HIP_TRY(hipMemsetAsync(d_sig, 0, texels * sizeof(unsigned long long), st));
-    }
+    double *const d_samples = s->f64_samples.ptr;
+    // call-local device memory, one allocation freed on every return path
+    const auto layout = [&](Carve256 &c) {
+        d_acc = c.take<double>(texels * 3); d_lin = c.take<double>(texels * 3);
+        d_q = c.take<uint32_t>(texels); d_queue = c.take<uint32_t>(1);
+        if (sig) d_sig = c.take<unsigned long long>(texels);
+    };
+    DeviceArena scratch;
+    if (scratch.alloc(layout) != hipSuccess) return fail(RTMI_ERR_NOMEM, "rtmi_render_f64: hipMalloc failed");
+    if (sig) HIP_TRY(hipMemsetAsync(d_sig, 0, texels * sizeof(unsigned long long), st));
     DevParams P{};
     P.nx = p.nx; P.ny = p.ny; P.ns = p.ns; P.max_depth = p.max_depth;
     P.t_min = (float)t_min;
@@ -1868,23 +1799,23 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     C.v = D3{cam->v[0], cam->v[1], cam->v[2]};
     C.time0 = cam->time0; C.time1 = cam->time1; C.lens_radius = cam->lens_radius;
     const uint32_t blocks = (uint32_t)(s->slots / 20) * 4u * 2u; // CUs x 4 SIMDs x 2 wavefronts (the kernel's occupancy: 255 VGPRs)
-    HIP_TRY(hipEventRecord(s->ev[0], st));
+    HIP_TRY(hipEventRecord(s->ev[0].e, st));
     float ms_render = 0.0f;
     for (uint32_t s0 = 0; s0 < p.ns; s0 += pass_ns) {
         const uint32_t cnt = p.ns - s0 < pass_ns ? p.ns - s0 : pass_ns;
         P.pass_s0 = s0; P.pass_cnt = cnt;
         P.nchunks = (cnt + chunk_spp - 1) / chunk_spp;
         HIP_TRY(hipMemsetAsync(d_queue, 0, sizeof(uint32_t), st));
-        HIP_TRY(hipEventRecord(s->ev[1], st));
+        HIP_TRY(hipEventRecord(s->ev[1].e, st));
         HIP_TRY(rtmi_f64_launch_render(sig, blocks, st, s->dev, s->f64, C, P, Q));
-        HIP_TRY(hipEventRecord(s->ev[2], st));
+        HIP_TRY(hipEventRecord(s->ev[2].e, st));
         HIP_TRY(rtmi_f64_launch_resolve(st, d_samples, d_acc, d_lin, d_q, P, s0 == 0, s0 + cnt >= p.ns));
-        HIP_TRY(hipEventSynchronize(s->ev[2]));
+        HIP_TRY(hipEventSynchronize(s->ev[2].e));
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[1], s->ev[2]));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[1].e, s->ev[2].e));
         ms_render += ms;
     }
-    HIP_TRY(hipEventRecord(s->ev[1], st));
+    HIP_TRY(hipEventRecord(s->ev[1].e, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (out_linear && (rc = download_untiled<3>(&p, d_lin, texels, out_linear))) return rc;
     if (out_rgb8) {
@@ -1896,7 +1827,7 @@ extern "C" int rtmi_render_f64(rtmi_scene *s, const rtmi_camera_f64 *cam, const 
     if (out_path_sig && (rc = download_untiled<1>(&p, d_sig, texels, out_path_sig))) return rc;
     if (stats) {
         float ms_all = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0], s->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0].e, s->ev[1].e));
         fill_stats(s, &p, stats, ms_render, ms_all);
         stats->kernel = RTMI_KERNEL_PERLANE;
     }
@@ -1937,7 +1868,7 @@ static int check_adaptive(const rtmi_render_params *p, const rtmi_adaptive *a) {
 static int adaptive_reserve(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, uint32_t T) {
     int rc;
     if ((rc = reserve_texels(s, (size_t)T * 64)) || (rc = grow_adaptive(s, T))) return rc;
-    if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
+    HIP_TRY(s->h_ad_count.grow(64));
     rtmi_render_params q = p;
     q.ns = a->min_spp > a->step_spp ? a->min_spp : (a->step_spp < p.ns ? a->step_spp : p.ns);
     uint32_t chunk_spp = 0, pass_ns = 0;
@@ -1948,7 +1879,7 @@ static int adaptive_reserve(rtmi_scene *s, const rtmi_render_params &p, const rt
 // others, and the host reads the count back (4 B) and plans the next step for that many tiles, so a small active set
 // still gets enough units to fill the chip.  The per-sample buffer holds the active tiles only (indexed by list position).
 // Shared by rtmi_render_adaptive and the entries of rtmi_adaptive_nee.h.  launch(blocks, tiles) enqueues the mode's
-// render kernel on s->stream for the pass fields of P over the active list `tiles` and returns an RTMI code; `kernel` is
+// render kernel on s->stream.s for the pass fields of P over the active list `tiles` and returns an RTMI code; `kernel` is
 // the label of rtmi_stats.kernel, `wps` the waves per SIMD that kernel keeps resident (the persistent grid).  The caller
 // holds s->mu, has checked every argument, called begin_blocking and adaptive_reserve and filled P with the mode's
 // traversal plan.
@@ -1958,7 +1889,7 @@ template <typename Launch>
 static int adaptive_steps_device(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
                                  uint32_t wps, PassCounts &counts, Launch &&launch) {
     int rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const uint32_t T = local_tiles_of(&p, 0);
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * wps;
     s->last_kernel = kernel;
@@ -1970,12 +1901,12 @@ static int adaptive_steps_device(rtmi_scene *s, const rtmi_render_params &p, con
     bool cancelled = false;
 
     if ((rc = begin_passes(s, stream)) || (rc = list_all_tiles(s, T, stream))) return rc;
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
-    uint32_t *lists[2] = {s->ad_lists, s->ad_lists + T}, *count = s->ad_lists + 2 * (size_t)T;
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
+    uint32_t *lists[2] = {s->ad_lists.ptr, s->ad_lists.ptr + T}, *count = s->ad_lists.ptr + 2 * (size_t)T;
     uint32_t n_active = T, n = 0, cur = 0;
     AdaptiveResolve A;
     A.n_out = count;
-    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.state = s->ad_state.ptr; A.texels = s->texels.ptr; A.stderr_out = s->ad_stderr.ptr; A.spp_out = s->ad_spp.ptr;
     A.abs_tol = a->abs_tol; A.rel_tol = a->rel_tol; A.ns = p.ns;
     while (n_active > 0 && n < p.ns && !cancelled) {
         const uint32_t c = n == 0 ? a->min_spp : (a->step_spp < p.ns - n ? a->step_spp : p.ns - n);
@@ -1983,7 +1914,7 @@ static int adaptive_steps_device(rtmi_scene *s, const rtmi_render_params &p, con
         q.ns = c;
         uint32_t chunk_spp = 0, pass_ns = 0;
         if ((rc = plan_and_reserve(s, &q, n_active, chunk_spp, pass_ns))) return rc;
-        P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+        P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples.ptr;
         HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), stream));
         A.tiles_in = lists[cur]; A.tiles_out = lists[cur ^ 1];
         const uint64_t units_before = s->units_total;
@@ -1992,17 +1923,17 @@ static int adaptive_steps_device(rtmi_scene *s, const rtmi_render_params &p, con
             if (int lrc = launch(blocks, (const uint32_t *)lists[cur])) return lrc;
             A.first = (n == 0 && first) ? 1 : 0;
             A.decide = last ? 1 : 0;
-            HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
+            HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples.ptr, P, A));
             return RTMI_OK;
         });
         if (rc) return rc;
         const uint64_t units_step = s->units_total - units_before;
-        HIP_TRY(hipMemcpyAsync(s->h_ad_count, count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(s->ev[1], stream));
+        HIP_TRY(hipMemcpyAsync(s->h_ad_count.ptr, count, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(s->ev[1].e, stream));
         // wait for the step; meanwhile report progress from the unit counters (as wait_with_progress does)
         const uint64_t step_ts = (uint64_t)n_active * c;
         while (fn) {
-            const hipError_t qe = hipEventQuery(s->ev[1]);
+            const hipError_t qe = hipEventQuery(s->ev[1].e);
             if (qe == hipSuccess) break;
             if (qe != hipErrorNotReady) return fail(RTMI_ERR_DEVICE, std::string("hipEventQuery: ") + hipGetErrorString(qe));
             uint64_t u = 0;
@@ -2016,15 +1947,15 @@ static int adaptive_steps_device(rtmi_scene *s, const rtmi_render_params &p, con
             struct timespec ts = {0, 50 * 1000 * 1000};
             nanosleep(&ts, nullptr);
         }
-        HIP_TRY(hipEventSynchronize(s->ev[1]));
-        const uint32_t next = *s->h_ad_count;
+        HIP_TRY(hipEventSynchronize(s->ev[1].e));
+        const uint32_t next = *s->h_ad_count.ptr;
         settled += (uint64_t)(n_active - next) * (p.ns - n) + (uint64_t)next * c; // a retired tile counts at ns
         n += c;
         n_active = next;
         cur ^= 1;
     }
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
-    HIP_TRY(hipEventSynchronize(s->ev[2]));
+    HIP_TRY(hipEventRecord(s->ev[2].e, stream));
+    HIP_TRY(hipEventSynchronize(s->ev[2].e));
     if (fn && !cancelled && fn(total, total, user) != 0) cancelled = true;
     if (cancelled) return fail(RTMI_ERR_CANCELLED, "cancelled by the progress callback");
     return check_overflow(s);
@@ -2033,20 +1964,20 @@ static int adaptive_download(rtmi_scene *s, const rtmi_render_params &p, const P
                              uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp, rtmi_stats *stats) {
     int rc;
     const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
-    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
+    HIP_TRY(hipMemcpy(s->h_texels.ptr, s->texels.ptr, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr.ptr, ntex, out_stderr))) return rc;
     const size_t npix = (size_t)p.nx * p.ny;
     std::vector<uint32_t> spp_local(out_spp ? 0 : npix);
     uint32_t *spp = out_spp ? out_spp : spp_local.data();
-    if ((rc = download_untiled<1>(&p, s->ad_spp, ntex, spp))) return rc;
+    if ((rc = download_untiled<1>(&p, s->ad_spp.ptr, ntex, spp))) return rc;
     if (stats) {
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[2].e));
         fill_stats(s, &p, stats, ms, ms, counts); // first launch to last resolve, the per-step read-backs included
         stats->samples = 0;                       // the samples traced: every pixel's own count
         for (size_t o = 0; o < npix; o++) stats->samples += spp[o];
     }
-    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+    return rtmi_untile(&p, s->h_texels.ptr, out_linear, out_rgb8);
 }
 template <typename Launch>
 static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi_adaptive *a, DevParams &P, uint32_t kernel,
@@ -2113,8 +2044,8 @@ static int check_estimator_opts(const char *name, uint32_t estimator, float env_
 static DevEnv dev_env(const rtmi_scene *s, float p_env) {
     const size_t H = s->env_h, n = (size_t)s->env_w * s->env_h;
     DevEnv E;
-    E.texels = s->env_texels;
-    E.row_cdf = s->env_tables; E.row_p = s->env_tables + H; E.col_cdf = s->env_tables + 2 * H; E.col_p = s->env_tables + 2 * H + n;
+    E.texels = s->env_texels.ptr;
+    E.row_cdf = s->env_tables.ptr; E.row_p = s->env_tables.ptr + H; E.col_cdf = s->env_tables.ptr + 2 * H; E.col_p = s->env_tables.ptr + 2 * H + n;
     E.w = s->env_w; E.h = s->env_h;
     E.p_env = p_env;
     return E;
@@ -2124,7 +2055,7 @@ static DevEnv dev_env(const rtmi_scene *s, float p_env) {
 static void dev_lighting(const rtmi_scene *s, bool nee, bool env, float env_select_p, DevLights &L, DevEnv &E) {
     L = DevLights{};
     E = DevEnv{};
-    if (nee) { L.lights = s->nee_lights; L.prim_light = s->nee_prim_light; L.n = s->nee_n; }
+    if (nee) { L.lights = s->nee_lights.ptr; L.prim_light = s->nee_prim_light.ptr; L.n = s->nee_n; }
     if (env) E = dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? env_select_p : 1.0f));
 }
 
@@ -2169,7 +2100,7 @@ static int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
         return fail(RTMI_ERR_INVALID, std::string(m.name) + ": no light tree attached (rtmi_scene_attach_light_tree)");
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = begin_blocking(s)) return rc;
-    c.busy.s = s; c.busy.st = s->stream;
+    c.busy.s = s; c.busy.st = s->stream.s;
     return RTMI_OK;
 }
 // An asynchronous call's hold on the handle, which it takes without waiting for the handle's previous call: the lock, what
@@ -2185,7 +2116,7 @@ struct AsyncCall {
         if (int rc = check_attached(m, s)) return rc;
         HIP_TRY(hipSetDevice(s->device));
         stream = reinterpret_cast<hipStream_t>(stream_);
-        if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy, 0));
+        if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy.e, 0));
         busy.s = s; busy.st = stream;
         return RTMI_OK;
     }
@@ -2225,7 +2156,7 @@ static uint64_t light_run_slots(const rtmi_scene *s, const RenderCall &c) {
 }
 // the cooperative launch of a lighting entry's callable: the fixed render's pass (tiles = NULL) or one over the active list
 static int launch_light_coop(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks, const uint32_t *tiles) {
-    HIP_TRY(rtmi_light_coop_launch_render(tiles != nullptr, sig, c.ext, m.nee, m.env, blocks, c.coop_lds, s->stream, s->dev, c.C,
+    HIP_TRY(rtmi_light_coop_launch_render(tiles != nullptr, sig, c.ext, m.nee, m.env, blocks, c.coop_lds, s->stream.s, s->dev, c.C,
                                           c.P, tiles, c.L, c.E));
     return RTMI_OK;
 }
@@ -2242,18 +2173,18 @@ static int begin_adaptive(RenderCall &c, const Estimator &m, rtmi_scene *s, cons
 // RTMI_FLAG_LIGHT_COOP its cooperative one (c.coop: the callable launches that), TILE_LIST = false,
 // in passes of the render's plan; adaptive sampling's resolve over the list of all tiles carries sum, m and M2 between
 // passes and writes texels and standard errors after the last one.  launch(c, sig, blocks) enqueues the render kernel on
-// s->stream for the pass fields of c.P and returns an RTMI code.  The caller has checked every argument.
+// s->stream.s for the pass fields of c.P and returns an RTMI code.  The caller has checked every argument.
 // render_fixed_device: after begin_call, enqueue, wait and check overflow; texels, standard errors and signatures stay in
 // the scene's device buffers (the frame handle, rtmi_frame_launch.hpp, stops here).  render_fixed adds their copies to the host.
 template <typename Launch>
 static int render_fixed_device(RenderCall &c, const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
                                bool sig, rtmi_stats *stats, Launch &&launch) {
     int rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64;
     if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, T)) ||
-        (sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+        (sig && (rc = grow(s, s->d_sig, ntex * sizeof(unsigned long long)))))
         return rc;
     uint32_t chunk_spp = 0, pass_ns = 0;
     if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns))) return rc;
@@ -2261,33 +2192,33 @@ static int render_fixed_device(RenderCall &c, const Estimator &m, rtmi_scene *s,
     kernel_args(c, m, s, cam, p);
     if ((rc = plan_light_coop(c, s, p))) return rc;
     DevParams &P = c.P;
-    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
-    P.path_sig = sig ? s->d_sig : nullptr;
+    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples.ptr;
+    P.path_sig = sig ? s->d_sig.ptr : nullptr;
     const uint64_t run_slots = light_run_slots(s, c);
     s->last_kernel = c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
 
     if ((rc = begin_passes(s, stream))) return rc;
-    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
+    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig.ptr, 0, ntex * sizeof(unsigned long long), stream));
     if ((rc = list_all_tiles(s, T, stream))) return rc;
     AdaptiveResolve A;
-    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + T; A.n_out = s->ad_lists + 2 * (size_t)T;
-    A.state = s->ad_state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.tiles_in = s->ad_lists.ptr; A.tiles_out = s->ad_lists.ptr + T; A.n_out = s->ad_lists.ptr + 2 * (size_t)T;
+    A.state = s->ad_state.ptr; A.texels = s->texels.ptr; A.stderr_out = s->ad_stderr.ptr; A.spp_out = s->ad_spp.ptr;
     A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = p.ns; // the last pass retires every tile at ns
     PassCounts counts;
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
     rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
         if (int lrc = launch(c, sig, blocks)) return lrc;
-        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
+        if (last) HIP_TRY(hipEventRecord(s->ev[1].e, stream));
         A.first = first ? 1 : 0;
         A.decide = last ? 1 : 0;
         if (last) HIP_TRY(hipMemsetAsync(A.n_out, 0, sizeof(uint32_t), stream));
-        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, P, A));
+        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples.ptr, P, A));
         return RTMI_OK;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    HIP_TRY(hipEventRecord(s->ev[2].e, stream));
     rtmi_scene *one[1] = {s};
-    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
+    if ((rc = wait_with_progress(one, &s->ev[2].e, 1, &p))) return rc;
     if ((rc = check_overflow(s))) return rc;
     return stats ? fill_stats_from_events(s, &p, stats, counts) : RTMI_OK;
 }
@@ -2298,10 +2229,10 @@ static int render_fixed(const Estimator &m, rtmi_scene *s, const rtmi_camera *ca
     int rc;
     if ((rc = begin_call(c, m, s)) || (rc = render_fixed_device(c, m, s, cam, p, out_path_sig != nullptr, stats, launch))) return rc;
     const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
-    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr, ntex, out_stderr))) return rc;
-    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
-    return rtmi_untile(&p, s->h_texels, out_linear, out_rgb8);
+    HIP_TRY(hipMemcpy(s->h_texels.ptr, s->texels.ptr, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    if (out_stderr && (rc = download_untiled<3>(&p, s->ad_stderr.ptr, ntex, out_stderr))) return rc;
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig.ptr, ntex, out_path_sig))) return rc;
+    return rtmi_untile(&p, s->h_texels.ptr, out_linear, out_rgb8);
 }
 
 // The plain estimator's adaptive render after begin_call: adaptive sampling's buffers, the kernel arguments, the kernel
@@ -2323,7 +2254,7 @@ static int adaptive_plain_device(RenderCall &c, const Estimator &m, rtmi_scene *
     const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, false}.words() * sizeof(uint32_t);
     return adaptive_steps_device(s, p, a, P, coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, 4u, counts,
                                  [&](uint32_t blocks, const uint32_t *tiles) -> int {
-                                     HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream, s->dev, c.C,
+                                     HIP_TRY(rtmi_adaptive_launch_render(which, blocks, coop ? coop_lds : 0, s->stream.s, s->dev, c.C,
                                                                          P, tiles));
                                      return RTMI_OK;
                                  });
@@ -2352,50 +2283,50 @@ extern "C" int rtmi_render_adaptive(rtmi_scene *s, const rtmi_camera *cam, const
 // The per-lane features kernel (rtmi_features.hip) in passes of the render's plan, sized for 32-B slots; a resolve per
 // pass carries the f64 sums and writes the planes after the last one.  Progress and cancellation as rtmi_render's.
 // features_device: under the scene's lock and after begin_blocking, enqueue, wait and check overflow; the four planes stay
-// in s->ft_planes, the signatures in s->d_sig (the frame handle, rtmi_frame_launch.hpp, stops here).  The entry adds the
+// in s->ft_planes.ptr, the signatures in s->d_sig.ptr (the frame handle, rtmi_frame_launch.hpp, stops here).  The entry adds the
 // copies to the host.
 static int features_device(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p, bool sig, rtmi_stats *stats) {
     int rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const uint32_t T = local_tiles_of(&p, 0);
     const size_t ntex = (size_t)T * 64, npix = (size_t)p.nx * p.ny;
-    if ((rc = grow(s, s->ft_state, s->ft_state_bytes, ntex * 8 * sizeof(double))) ||
-        (rc = grow(s, s->ft_planes, s->ft_planes_bytes, npix * 8 * sizeof(float))) ||
-        (sig && (rc = grow(s, s->d_sig, s->sig_bytes, ntex * sizeof(unsigned long long)))))
+    if ((rc = grow(s, s->ft_state, ntex * 8 * sizeof(double))) ||
+        (rc = grow(s, s->ft_planes, npix * 8 * sizeof(float))) ||
+        (sig && (rc = grow(s, s->d_sig, ntex * sizeof(unsigned long long)))))
         return rc;
     // the per-sample buffer, planned for 32-B slots, before the clock starts
     uint32_t chunk_spp = 0, pass_ns = 0;
     if ((rc = plan_and_reserve(s, &p, T, chunk_spp, pass_ns, RTMI_FEAT_SLOT_BYTES))) return rc;
 
     DevParams P = dev_params(s, &p);
-    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+    P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples.ptr;
     const DevCamera C = dev_camera(cam);
     const bool fast = (p.flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
-    P.path_sig = sig ? s->d_sig : nullptr;
+    P.path_sig = sig ? s->d_sig.ptr : nullptr;
     const uint64_t run_slots = (uint64_t)(s->slots / 20) * 4u * 4u;
     s->last_kernel = RTMI_KERNEL_PERLANE;
 
     if ((rc = begin_passes(s, stream))) return rc;
-    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig, 0, ntex * sizeof(unsigned long long), stream));
+    if (sig) HIP_TRY(hipMemsetAsync(s->d_sig.ptr, 0, ntex * sizeof(unsigned long long), stream));
     FeaturesResolve R;
-    R.slots = reinterpret_cast<const FeatSlot *>(s->samples);
-    R.state = s->ft_state;
-    R.albedo = s->ft_planes; R.normal = s->ft_planes + npix * 3; R.depth = s->ft_planes + npix * 6;
-    R.hits = reinterpret_cast<uint32_t *>(s->ft_planes + npix * 7);
+    R.slots = reinterpret_cast<const FeatSlot *>(s->samples.ptr);
+    R.state = s->ft_state.ptr;
+    R.albedo = s->ft_planes.ptr; R.normal = s->ft_planes.ptr + npix * 3; R.depth = s->ft_planes.ptr + npix * 6;
+    R.hits = reinterpret_cast<uint32_t *>(s->ft_planes.ptr + npix * 7);
     PassCounts counts;
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
     rc = run_passes(s, P, stream, 0, p.ns, true, run_slots, 1u, counts, [&](uint32_t blocks, bool first, bool last) -> int {
         HIP_TRY(rtmi_features_launch_render(fast, sig, blocks, stream, s->dev, C, P));
-        if (last) HIP_TRY(hipEventRecord(s->ev[1], stream));
+        if (last) HIP_TRY(hipEventRecord(s->ev[1].e, stream));
         R.first = first ? 1 : 0;
         R.last = last ? 1 : 0;
         HIP_TRY(rtmi_features_launch_resolve(stream, P, R));
         return RTMI_OK;
     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    HIP_TRY(hipEventRecord(s->ev[2].e, stream));
     rtmi_scene *one[1] = {s};
-    if ((rc = wait_with_progress(one, &s->ev[2], 1, &p))) return rc;
+    if ((rc = wait_with_progress(one, &s->ev[2].e, 1, &p))) return rc;
     if ((rc = check_overflow(s))) return rc;
     return stats ? fill_stats_from_events(s, &p, stats, counts) : RTMI_OK;
 }
@@ -2415,15 +2346,15 @@ extern "C" int rtmi_render_features(rtmi_scene *s, const rtmi_camera *cam, const
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = begin_blocking(s))) return rc;
     const rtmi_render_params &p = *p_in;
-    BusyMark busy_mark{s, s->stream};
+    BusyMark busy_mark{s, s->stream.s};
     if ((rc = features_device(s, cam, p, out_path_sig != nullptr, stats))) return rc;
     const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64, npix = (size_t)p.nx * p.ny;
-    const float *planes = s->ft_planes;
+    const float *planes = s->ft_planes.ptr;
     if (out_albedo) HIP_TRY(hipMemcpy(out_albedo, planes, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_normal) HIP_TRY(hipMemcpy(out_normal, planes + npix * 3, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
     if (out_depth) HIP_TRY(hipMemcpy(out_depth, planes + npix * 6, npix * sizeof(float), hipMemcpyDeviceToHost));
     if (out_hits) HIP_TRY(hipMemcpy(out_hits, planes + npix * 7, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig, ntex, out_path_sig))) return rc;
+    if (out_path_sig && (rc = download_untiled<1>(&p, s->d_sig.ptr, ntex, out_path_sig))) return rc;
     return RTMI_OK;
 }
 
@@ -2469,8 +2400,8 @@ static bool query_fast(const rtmi_scene *s, const rtmi_query_params *p, bool has
 static QueryBatch query_batch(const rtmi_scene *s, const rtmi_query_params *p, const void *d_rays, const void *d_time, void *d_out,
                               bool any) {
     QueryBatch B{};
-    B.prim_gaps = s->q_flip_gaps;
-    B.item_gaps = s->q_flip_gaps ? s->q_flip_gaps + s->meta.n_prims : nullptr;
+    B.prim_gaps = s->q_flip_gaps.ptr;
+    B.item_gaps = s->q_flip_gaps.ptr ? s->q_flip_gaps.ptr + s->meta.n_prims : nullptr;
     B.rays = reinterpret_cast<const float4 *>(d_rays);
     B.time = reinterpret_cast<const float *>(d_time);
     if (any) B.occluded = reinterpret_cast<uint8_t *>(d_out); else B.hits = reinterpret_cast<float4 *>(d_out);
@@ -2502,22 +2433,22 @@ static int query_host(const char *name, bool any, rtmi_scene *s, const rtmi_quer
     const Estimator m{name, false, false, 1.0f, "scene is NULL", ""};
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const size_t n = p->n, out_bytes = any ? n : n * sizeof(rtmi_hit);
-    if ((rc = grow(s, s->q_rays, s->q_rays_bytes, n * sizeof(rtmi_ray))) ||
-        (time && (rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(float)))) || (rc = grow(s, s->q_out, s->q_out_bytes, out_bytes)))
+    if ((rc = grow(s, s->q_rays, n * sizeof(rtmi_ray))) ||
+        (time && (rc = grow(s, s->q_time, n * sizeof(float)))) || (rc = grow(s, s->q_out, out_bytes)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(s->q_rays, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
-    if (time) HIP_TRY(hipMemcpyAsync(s->q_time, time, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
+    HIP_TRY(hipMemcpyAsync(s->q_rays.ptr, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
+    if (time) HIP_TRY(hipMemcpyAsync(s->q_time.ptr, time, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
     HIP_TRY(rtmi_query_launch(any, query_fast(s, p, time != nullptr), stream, s->dev,
-                              query_batch(s, p, s->q_rays, time ? s->q_time : nullptr, s->q_out, any)));
-    HIP_TRY(hipEventRecord(s->ev[1], stream));
-    HIP_TRY(hipMemcpyAsync(out, s->q_out, out_bytes, hipMemcpyDeviceToHost, stream));
+                              query_batch(s, p, s->q_rays.ptr, time ? s->q_time.ptr : nullptr, s->q_out.ptr, any)));
+    HIP_TRY(hipEventRecord(s->ev[1].e, stream));
+    HIP_TRY(hipMemcpyAsync(out, s->q_out.ptr, out_bytes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (kernel_ms) {
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[1].e));
         *kernel_ms = (double)ms;
     }
     return RTMI_OK;
@@ -2532,15 +2463,15 @@ extern "C" int rtmi_scene_attach_flips(rtmi_scene *s, const uint32_t *prim_gaps,
     if (!detach && ((n_prims && !prim_gaps) || (n_items && !item_gaps))) return fail(RTMI_ERR_INVALID, std::string(name) + ": NULL array");
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running query may read the old table
-    if (s->q_flip_gaps) { HIP_TRY(hipFree(s->q_flip_gaps)); s->q_flip_gaps = nullptr; }
-    if (detach) return RTMI_OK;
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), ((size_t)n_prims + n_items + 1u) * sizeof(uint32_t)));
-    s->q_flip_gaps = d;
-    if (n_prims) HIP_TRY(hipMemcpy(d, prim_gaps, (size_t)n_prims * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (n_items) HIP_TRY(hipMemcpy(d + n_prims, item_gaps, (size_t)n_items * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return RTMI_OK;
+    const auto fill = [&]() -> int { // (a running query may read the old table)
+        if (detach) return RTMI_OK;
+        HIP_TRY(s->q_flip_gaps.alloc(((size_t)n_prims + n_items + 1u) * sizeof(uint32_t)));
+        uint32_t *const d = s->q_flip_gaps.ptr;
+        if (n_prims) HIP_TRY(hipMemcpy(d, prim_gaps, (size_t)n_prims * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if (n_items) HIP_TRY(hipMemcpy(d + n_prims, item_gaps, (size_t)n_items * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return RTMI_OK;
+    };
+    return replace_attached(s, nullptr, fill, s->q_flip_gaps);
 }
 extern "C" int rtmi_trace(rtmi_scene *s, const rtmi_query_params *p, const rtmi_ray *rays, const float *time, rtmi_hit *hits_out,
                           double *kernel_ms) {
@@ -2603,18 +2534,18 @@ static BatchArgs batch_args(const rtmi_scene *s, const Estimator &m, rtmi_render
 // The handle's buffers of a blocking call of n entries and ns samples in all, and the end of that call, whose enqueue ran
 // between ev[0] and ev[1]: the records to the host, the wait, the kernels' milliseconds.
 static int batch_reserve(rtmi_scene *s, size_t n, size_t ns) {
-    if (int rc = grow(s, s->rad_samples, s->rad_samples_bytes, ns * sizeof(Rad3))) return rc;
-    return grow(s, s->rad_out, s->rad_out_bytes, n * 6 * sizeof(float));
+    if (int rc = grow(s, s->rad_samples, ns * sizeof(Rad3))) return rc;
+    return grow(s, s->rad_out, n * 6 * sizeof(float));
 }
 static int batch_finish(rtmi_scene *s, size_t n, size_t ns, float *out_mean, float *out_stderr, float *out_samples, double *kernel_ms) {
-    hipStream_t stream = s->stream;
-    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, s->rad_out, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, s->rad_out + n * 3, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
-    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
+    hipStream_t stream = s->stream.s;
+    if (out_mean) HIP_TRY(hipMemcpyAsync(out_mean, s->rad_out.ptr, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, s->rad_out.ptr + n * 3, n * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    if (out_samples) HIP_TRY(hipMemcpyAsync(out_samples, s->rad_samples.ptr, ns * sizeof(Rad3), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     if (kernel_ms) {
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[1].e));
         *kernel_ms = (double)ms;
     }
     return RTMI_OK;
@@ -2655,7 +2586,7 @@ static int radiance_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_radian
     B.time = reinterpret_cast<const float *>(d_time);
     B.mean = reinterpret_cast<float *>(d_mean);
     B.stderr_out = reinterpret_cast<float *>(d_stderr);
-    B.queue = s->status + RTMI_STATUS_WORDS;
+    B.queue = s->status.ptr + RTMI_STATUS_WORDS;
     B.n = p->n; B.spp = p->spp; B.total = p->n * p->spp;
     B.first_ray = (uint32_t)p->first_ray; B.first_sample = p->first_sample;
     B.skip_block = p->stream_skip >> 2; B.skip_pos = p->stream_skip & 3u;
@@ -2685,19 +2616,19 @@ extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const
     if (p->n == 0u) return RTMI_OK;
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const size_t n = p->n, ns = n * p->spp;
-    if ((rc = grow(s, s->q_rays, s->q_rays_bytes, n * sizeof(rtmi_ray))) ||
-        (time && (rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(float)))) || (rc = batch_reserve(s, n, ns)))
+    if ((rc = grow(s, s->q_rays, n * sizeof(rtmi_ray))) ||
+        (time && (rc = grow(s, s->q_time, n * sizeof(float)))) || (rc = batch_reserve(s, n, ns)))
         return rc;
-    float *d_mean = s->rad_out, *d_stderr = s->rad_out + n * 3;
-    HIP_TRY(hipMemcpyAsync(s->q_rays, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
-    if (time) HIP_TRY(hipMemcpyAsync(s->q_time, time, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
-    if ((rc = radiance_enqueue(s, m, p, stream, s->q_rays, time ? s->q_time : nullptr, out_mean ? d_mean : nullptr,
-                               out_stderr ? d_stderr : nullptr, s->rad_samples)))
+    float *d_mean = s->rad_out.ptr, *d_stderr = s->rad_out.ptr + n * 3;
+    HIP_TRY(hipMemcpyAsync(s->q_rays.ptr, rays, n * sizeof(rtmi_ray), hipMemcpyHostToDevice, stream));
+    if (time) HIP_TRY(hipMemcpyAsync(s->q_time.ptr, time, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
+    if ((rc = radiance_enqueue(s, m, p, stream, s->q_rays.ptr, time ? s->q_time.ptr : nullptr, out_mean ? d_mean : nullptr,
+                               out_stderr ? d_stderr : nullptr, s->rad_samples.ptr)))
         return rc;
-    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    HIP_TRY(hipEventRecord(s->ev[1].e, stream));
     return batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms);
 }
 extern "C" int rtmi_radiance_device(rtmi_scene *s, const rtmi_radiance_params *p, const void *d_rays, const void *d_time, void *d_mean,
@@ -2777,7 +2708,7 @@ static int gather_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_gather_p
     B.value = reinterpret_cast<float *>(d_value);
     B.stderr_out = reinterpret_cast<float *>(d_stderr);
     B.sh = reinterpret_cast<float *>(d_sh);
-    B.queue = s->status + RTMI_STATUS_WORDS;
+    B.queue = s->status.ptr + RTMI_STATUS_WORDS;
     B.n = count; B.spp = p->spp; B.total = count * p->spp;
     B.first_point = (uint32_t)(p->first_point + at); B.first_sample = p->first_sample;
     const BatchChunks ch = batch_chunks(s, B.total);
@@ -2802,35 +2733,35 @@ extern "C" int rtmi_gather(rtmi_scene *s, const rtmi_gather_params *p, const flo
     if (p->n == 0u) return RTMI_OK;
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const bool cosine = p->mode == RTMI_GATHER_COSINE;
     const uint32_t slab = gather_slab(p, p->slab_points ? p->slab_points : (256ull << 20) / (12ull * p->spp));
     const size_t cap = slab < p->n ? slab : p->n; // points of the largest slab
     // a slab's records go through the query buffers: points | normals in q_rays, times in q_time; its outputs through rad_out
-    if ((rc = grow(s, s->q_rays, s->q_rays_bytes, cap * 6 * sizeof(float))) ||
-        (time && (rc = grow(s, s->q_time, s->q_time_bytes, cap * sizeof(float)))) ||
-        (rc = grow(s, s->rad_samples, s->rad_samples_bytes, cap * p->spp * sizeof(Rad3))) ||
-        (rc = grow(s, s->rad_out, s->rad_out_bytes, cap * 33 * sizeof(float))))
+    if ((rc = grow(s, s->q_rays, cap * 6 * sizeof(float))) ||
+        (time && (rc = grow(s, s->q_time, cap * sizeof(float)))) ||
+        (rc = grow(s, s->rad_samples, cap * p->spp * sizeof(Rad3))) ||
+        (rc = grow(s, s->rad_out, cap * 33 * sizeof(float))))
         return rc;
-    float *d_points = reinterpret_cast<float *>(s->q_rays), *d_normals = d_points + cap * 3;
-    float *d_value = s->rad_out, *d_stderr = s->rad_out + cap * 3, *d_sh = s->rad_out + cap * 6;
+    float *d_points = reinterpret_cast<float *>(s->q_rays.ptr), *d_normals = d_points + cap * 3;
+    float *d_value = s->rad_out.ptr, *d_stderr = s->rad_out.ptr + cap * 3, *d_sh = s->rad_out.ptr + cap * 6;
     for (uint64_t at = 0; at < p->n; at += slab) {
         const size_t cnt = p->n - at < slab ? (size_t)(p->n - at) : slab;
         HIP_TRY(hipMemcpyAsync(d_points, points + 3 * at, cnt * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
         if (cosine) HIP_TRY(hipMemcpyAsync(d_normals, normals + 3 * at, cnt * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
-        if (time) HIP_TRY(hipMemcpyAsync(s->q_time, time + at, cnt * sizeof(float), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(s->ev[0], stream));
-        if ((rc = gather_enqueue(s, m, p, stream, (uint32_t)at, (uint32_t)cnt, d_points, d_normals, time ? s->q_time : nullptr,
-                                 out_value ? d_value : nullptr, out_stderr ? d_stderr : nullptr, out_sh ? d_sh : nullptr, s->rad_samples)))
+        if (time) HIP_TRY(hipMemcpyAsync(s->q_time.ptr, time + at, cnt * sizeof(float), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(s->ev[0].e, stream));
+        if ((rc = gather_enqueue(s, m, p, stream, (uint32_t)at, (uint32_t)cnt, d_points, d_normals, time ? s->q_time.ptr : nullptr,
+                                 out_value ? d_value : nullptr, out_stderr ? d_stderr : nullptr, out_sh ? d_sh : nullptr, s->rad_samples.ptr)))
             return rc;
-        HIP_TRY(hipEventRecord(s->ev[1], stream));
+        HIP_TRY(hipEventRecord(s->ev[1].e, stream));
         if (out_value) HIP_TRY(hipMemcpyAsync(out_value + 3 * at, d_value, cnt * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr + 3 * at, d_stderr, cnt * 3 * sizeof(float), hipMemcpyDeviceToHost, stream));
         if (out_sh) HIP_TRY(hipMemcpyAsync(out_sh + 27 * at, d_sh, cnt * 27 * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (kernel_ms) {
             float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[1].e));
             *kernel_ms += (double)ms;
         }
     }
@@ -2987,16 +2918,16 @@ extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, co
     if (sp->n == 0u) return RTMI_OK;
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     const size_t n = sp->n, ns = n * sp->ns;
-    if ((rc = grow(s, s->q_time, s->q_time_bytes, n * sizeof(uint32_t))) || (rc = batch_reserve(s, n, ns))) return rc;
-    float *d_mean = s->rad_out, *d_stderr = s->rad_out + n * 3;
-    HIP_TRY(hipMemcpyAsync(s->q_time, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
-    if ((rc = sparse_enqueue(s, m, p, cam, sp, stream, s->q_time, nullptr, out_mean ? d_mean : nullptr, out_stderr ? d_stderr : nullptr,
-                             s->rad_samples, s->status + RTMI_STATUS_WORDS)))
+    if ((rc = grow(s, s->q_time, n * sizeof(uint32_t))) || (rc = batch_reserve(s, n, ns))) return rc;
+    float *d_mean = s->rad_out.ptr, *d_stderr = s->rad_out.ptr + n * 3;
+    HIP_TRY(hipMemcpyAsync(s->q_time.ptr, pixels, n * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
+    if ((rc = sparse_enqueue(s, m, p, cam, sp, stream, s->q_time.ptr, nullptr, out_mean ? d_mean : nullptr, out_stderr ? d_stderr : nullptr,
+                             s->rad_samples.ptr, s->status.ptr + RTMI_STATUS_WORDS)))
         return rc;
-    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    HIP_TRY(hipEventRecord(s->ev[1].e, stream));
     return batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms);
 }
 extern "C" int rtmi_sparse_render_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
@@ -3083,7 +3014,7 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
     const Estimator m = estimator_of(name, sp->estimator, sp->env_select_p, null_scene.c_str());
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     // one allocation per call: bytes | scratch | linear | stderr | rgb8
     const size_t npix = (size_t)p->nx * p->ny;
     char *d_bytes, *d_scratch, *d_linear, *d_se, *d_rgb8;
@@ -3280,23 +3211,23 @@ static int pixelwise_render_host(const char *name, rtmi_scene *s, const rtmi_cam
     const Estimator m = estimator_of(name, o->estimator, o->env_select_p, null_scene.c_str());
     RenderCall c;
     if ((rc = begin_call(c, m, s))) return rc;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     // the handle's memory, grow-only: scratch | linear | stderr | spp | rgb8
     const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
     const size_t scratch_bytes =
         (size_t)pixelwise_scratch(npix, pixelwise_pass(p, o), rtmi_pixelwise_steps(p->ns, o->min_spp, o->step_spp), o->windowed).total;
-    if ((rc = grow(s, s->px_mem, s->px_mem_bytes, scratch_bytes + (12 + 12 + 4 + 3) * up))) return rc;
-    if (!s->h_ad_count) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_ad_count), 64, hipHostMallocDefault));
-    char *d_linear = s->px_mem + scratch_bytes, *d_se = d_linear + 12 * up, *d_spp = d_se + 12 * up, *d_rgb8 = d_spp + 4 * up;
+    if ((rc = grow(s, s->px_mem, scratch_bytes + (12 + 12 + 4 + 3) * up))) return rc;
+    HIP_TRY(s->h_ad_count.grow(64));
+    char *d_linear = s->px_mem.ptr + scratch_bytes, *d_se = d_linear + 12 * up, *d_spp = d_se + 12 * up, *d_rgb8 = d_spp + 4 * up;
     const PixelwisePlanes out{out_linear ? d_linear : nullptr, out_rgb8 ? d_rgb8 : nullptr, out_stderr ? d_se : nullptr,
                               out_spp ? d_spp : nullptr, out_counts};
     uint64_t paths = 0;
-    HIP_TRY(hipEventRecord(s->ev[0], stream));
-    if ((rc = pixelwise_enqueue(s, m, p, cam, o, stream, out, s->px_mem, s->h_ad_count, &paths))) {
+    HIP_TRY(hipEventRecord(s->ev[0].e, stream));
+    if ((rc = pixelwise_enqueue(s, m, p, cam, o, stream, out, s->px_mem.ptr, s->h_ad_count.ptr, &paths))) {
         (void)hipStreamSynchronize(stream);
         return rc;
     }
-    HIP_TRY(hipEventRecord(s->ev[1], stream));
+    HIP_TRY(hipEventRecord(s->ev[1].e, stream));
     if (out_linear) HIP_TRY(hipMemcpyAsync(out_linear, d_linear, npix * 12, hipMemcpyDeviceToHost, stream));
     if (out_stderr) HIP_TRY(hipMemcpyAsync(out_stderr, d_se, npix * 12, hipMemcpyDeviceToHost, stream));
     if (out_spp) HIP_TRY(hipMemcpyAsync(out_spp, d_spp, npix * 4, hipMemcpyDeviceToHost, stream));
@@ -3304,7 +3235,7 @@ static int pixelwise_render_host(const char *name, rtmi_scene *s, const rtmi_cam
     HIP_TRY(hipStreamSynchronize(stream));
     if (stats) {
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[1].e));
         *stats = rtmi_stats{};
         stats->kernel_ms = (double)ms;
         stats->samples = paths;
@@ -3543,18 +3474,17 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     }
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running NEE render may read the old table
-    if (s->nee_lights) { HIP_TRY(hipFree(s->nee_lights)); s->nee_lights = nullptr; }
-    if (s->nee_prim_light) { HIP_TRY(hipFree(s->nee_prim_light)); s->nee_prim_light = nullptr; }
-    s->has_lights = false;
-    s->has_light_tree = false; // its leaves index the table it was built over (rtmi_light_tree.h)
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->nee_lights), dl.size() * sizeof(NeeLight)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->nee_prim_light), pl.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(s->nee_lights, dl.data(), dl.size() * sizeof(NeeLight), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->nee_prim_light, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    s->nee_n = (uint32_t)v.size();
-    s->has_lights = true;
-    return RTMI_OK;
+    const auto fill = [&]() -> int { // (a running NEE render may read the old table)
+        s->has_light_tree = false; // its leaves index the table it was built over (rtmi_light_tree.h)
+        HIP_TRY(s->nee_lights.alloc(dl.size() * sizeof(NeeLight)));
+        HIP_TRY(s->nee_prim_light.alloc(pl.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(s->nee_lights.ptr, dl.data(), dl.size() * sizeof(NeeLight), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->nee_prim_light.ptr, pl.data(), pl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        s->nee_n = (uint32_t)v.size();
+        s->has_lights = true;
+        return RTMI_OK;
+    };
+    return replace_attached(s, &s->has_lights, fill, s->nee_lights, s->nee_prim_light);
 }
 
 // ---- light tree (include/rtmi_light_tree.h) -----------------------------------------------------------------------------
@@ -3578,27 +3508,26 @@ extern "C" int rtmi_scene_attach_light_tree(rtmi_scene *s, const rtmi_scene_desc
     if (s->nee_n * 2u != (uint32_t)nodes.size())
         return fail(RTMI_ERR_INVALID, "rtmi_scene_attach_light_tree: the attached light table is not this description's");
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running render may read the old tree
-    if (s->lt_nodes) { HIP_TRY(hipFree(s->lt_nodes)); s->lt_nodes = nullptr; }
-    if (s->lt_paths) { HIP_TRY(hipFree(s->lt_paths)); s->lt_paths = nullptr; }
-    s->has_light_tree = false;
-    const size_t nn = std::max<size_t>(nodes.size(), 2), np = std::max<size_t>(paths.size(), 1);
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->lt_nodes), nn * sizeof(rtmi_light_node))); // hipMalloc aligns to 256 B
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->lt_paths), np * sizeof(rtmi_light_path)));
-    HIP_TRY(hipMemset(s->lt_nodes, 0, nn * sizeof(rtmi_light_node)));
-    HIP_TRY(hipMemset(s->lt_paths, 0, np * sizeof(rtmi_light_path)));
-    if (!nodes.empty()) {
-        HIP_TRY(hipMemcpy(s->lt_nodes, nodes.data(), nodes.size() * sizeof(rtmi_light_node), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->lt_paths, paths.data(), paths.size() * sizeof(rtmi_light_path), hipMemcpyHostToDevice));
-    }
-    s->lt_n = (uint32_t)nodes.size();
-    s->has_light_tree = true;
-    return RTMI_OK;
+    const auto fill = [&]() -> int { // (a running render may read the old tree)
+        const size_t nn = std::max<size_t>(nodes.size(), 2), np = std::max<size_t>(paths.size(), 1);
+        HIP_TRY(s->lt_nodes.alloc(nn * sizeof(rtmi_light_node))); // hipMalloc aligns to 256 B
+        HIP_TRY(s->lt_paths.alloc(np * sizeof(rtmi_light_path)));
+        HIP_TRY(hipMemset(s->lt_nodes.ptr, 0, nn * sizeof(rtmi_light_node)));
+        HIP_TRY(hipMemset(s->lt_paths.ptr, 0, np * sizeof(rtmi_light_path)));
+        if (!nodes.empty()) {
+            HIP_TRY(hipMemcpy(s->lt_nodes.ptr, nodes.data(), nodes.size() * sizeof(rtmi_light_node), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(s->lt_paths.ptr, paths.data(), paths.size() * sizeof(rtmi_light_path), hipMemcpyHostToDevice));
+        }
+        s->lt_n = (uint32_t)nodes.size();
+        s->has_light_tree = true;
+        return RTMI_OK;
+    };
+    return replace_attached(s, &s->has_light_tree, fill, s->lt_nodes, s->lt_paths);
 }
 
 static DevLightTree dev_light_tree(const rtmi_scene *s) {
     DevLightTree T;
-    T.nodes = s->lt_nodes; T.paths = s->lt_paths; T.n = s->lt_n;
+    T.nodes = s->lt_nodes.ptr; T.paths = s->lt_paths.ptr; T.n = s->lt_n;
     return T;
 }
 
@@ -3619,20 +3548,20 @@ extern "C" int rtmi_probe_light_tree(rtmi_scene *s, int op, const float *points,
                 return fail(RTMI_ERR_INVALID, "rtmi_probe_light_tree: a light index is outside the table");
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = begin_blocking(s)) return rc;
-    // one device buffer, freed on every return: points [n][3] | aux [n] | light [n] | p [n]
-    struct DevBuf {
-        float *p = nullptr;
-        ~DevBuf() { if (p) (void)hipFree(p); }
-    } buf;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&buf.p), (size_t)n * 6 * sizeof(float)));
-    float *dpts = buf.p, *dp = buf.p + (size_t)n * 5;
-    uint32_t *daux = reinterpret_cast<uint32_t *>(buf.p + (size_t)n * 3), *dlight = daux + n;
-    HIP_TRY(hipMemcpyAsync(dpts, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(daux, aux, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rtmi_light_tree_launch_probe(op, dev_light_tree(s), dpts, daux, n, dlight, dp, s->stream));
-    if (pick) HIP_TRY(hipMemcpyAsync(out_light, dlight, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(out_p, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    // one device buffer, freed on every return
+    float *dpts, *dp;
+    uint32_t *daux, *dlight;
+    const auto layout = [&](Carve16 &c) {
+        dpts = c.take<float>((size_t)n * 3); daux = c.take<uint32_t>(n); dlight = c.take<uint32_t>(n); dp = c.take<float>(n);
+    };
+    DeviceArena buf;
+    HIP_TRY(buf.alloc<16>(layout));
+    HIP_TRY(hipMemcpyAsync(dpts, points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, s->stream.s));
+    HIP_TRY(hipMemcpyAsync(daux, aux, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream.s));
+    HIP_TRY(rtmi_light_tree_launch_probe(op, dev_light_tree(s), dpts, daux, n, dlight, dp, s->stream.s));
+    if (pick) HIP_TRY(hipMemcpyAsync(out_light, dlight, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream.s));
+    HIP_TRY(hipMemcpyAsync(out_p, dp, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream.s));
+    HIP_TRY(hipStreamSynchronize(s->stream.s));
     return RTMI_OK;
 }
 
@@ -3640,9 +3569,9 @@ extern "C" int rtmi_probe_light_tree(rtmi_scene *s, int op, const float *points,
 static int launch_lit_fixed(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks) {
     if (c.coop) return launch_light_coop(c, m, s, sig, blocks, nullptr);
     if (m.env)
-        HIP_TRY(rtmi_env_launch_render(c.fast, sig, m.nee, blocks, s->stream, s->dev, c.C, c.P, c.L, c.E));
+        HIP_TRY(rtmi_env_launch_render(c.fast, sig, m.nee, blocks, s->stream.s, s->dev, c.C, c.P, c.L, c.E));
     else
-        HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L));
+        HIP_TRY(rtmi_nee_launch_render(c.fast, sig, blocks, s->stream.s, s->dev, c.C, c.P, c.L));
     return RTMI_OK;
 }
 
@@ -3667,7 +3596,7 @@ extern "C" int rtmi_render_nee(rtmi_scene *s, const rtmi_camera *cam, const rtmi
     return render_fixed(m, s, cam, *p_in, out_linear, out_rgb8, out_stderr, out_path_sig, stats,
                         [&](const RenderCall &c, bool sig, uint32_t blocks) -> int {
                             if (tree && !c.coop) {
-                                HIP_TRY(rtmi_light_tree_launch_render(c.fast, sig, blocks, s->stream, s->dev, c.C, c.P, c.L,
+                                HIP_TRY(rtmi_light_tree_launch_render(c.fast, sig, blocks, s->stream.s, s->dev, c.C, c.P, c.L,
                                                                       dev_light_tree(s)));
                                 return RTMI_OK;
                             }
@@ -3687,23 +3616,22 @@ extern "C" int rtmi_scene_attach_env(rtmi_scene *s, const rtmi_env_map *map) {
     }
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy)); // a running render may read the old map
-    if (s->env_texels) { HIP_TRY(hipFree(s->env_texels)); s->env_texels = nullptr; }
-    if (s->env_tables) { HIP_TRY(hipFree(s->env_tables)); s->env_tables = nullptr; }
-    s->has_env = false;
-    if (!map) return RTMI_OK;
-    const size_t n = tex.size(), H = map->height;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->env_texels), n * sizeof(float4)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->env_tables), (2 * H + 2 * n) * sizeof(float)));
-    HIP_TRY(hipMemcpy(s->env_texels, tex.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->env_tables, t.row_cdf.data(), H * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->env_tables + H, t.row_p.data(), H * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->env_tables + 2 * H, t.col_cdf.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(s->env_tables + 2 * H + n, t.col_p.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    s->env_w = map->width; s->env_h = map->height;
-    s->env_sampled = t.total > 0.0;
-    s->has_env = true;
-    return RTMI_OK;
+    const auto fill = [&]() -> int { // (a running render may read the old map)
+        if (!map) return RTMI_OK;
+        const size_t n = tex.size(), H = map->height;
+        HIP_TRY(s->env_texels.alloc(n * sizeof(float4)));
+        HIP_TRY(s->env_tables.alloc((2 * H + 2 * n) * sizeof(float)));
+        HIP_TRY(hipMemcpy(s->env_texels.ptr, tex.data(), n * sizeof(float4), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->env_tables.ptr, t.row_cdf.data(), H * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->env_tables.ptr + H, t.row_p.data(), H * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->env_tables.ptr + 2 * H, t.col_cdf.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->env_tables.ptr + 2 * H + n, t.col_p.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        s->env_w = map->width; s->env_h = map->height;
+        s->env_sampled = t.total > 0.0;
+        s->has_env = true;
+        return RTMI_OK;
+    };
+    return replace_attached(s, &s->has_env, fill, s->env_texels, s->env_tables);
 }
 
 // The per-lane environment kernel (rtmi_env.hip), or the cooperative one (rtmi_light_coop.hip), in render_fixed.
@@ -3741,7 +3669,7 @@ static int adaptive_lit(const Estimator &m, rtmi_scene *s, const rtmi_camera *ca
     return adaptive_steps(s, p, a, c.P, c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, c.wps, out_linear, out_rgb8,
                           out_stderr, out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
                               if (c.coop) return launch_light_coop(c, m, s, false, blocks, tiles);
-                              HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, m.nee, m.env, blocks, s->stream, s->dev, c.C,
+                              HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, m.nee, m.env, blocks, s->stream.s, s->dev, c.C,
                                                                       c.P, tiles, c.L, c.E));
                               return RTMI_OK;
                           });
@@ -3815,22 +3743,22 @@ static int render_roulette(const char *name, rtmi_scene *s, const rtmi_camera *c
         (rc = plan_light_coop(c, s, p, RTMI_FLAG_ROULETTE_COOP, rtmi_roulette_coop_wps(nee, env))))
         return rc;
     const size_t ntex = (size_t)local_tiles_of(&p, 0) * 64;
-    if ((rc = grow(s, s->rr_bounces, s->rr_bytes, ntex * sizeof(uint32_t)))) return rc;
-    HIP_TRY(hipMemsetAsync(s->rr_bounces, 0, ntex * sizeof(uint32_t), s->stream));
-    const DevRoulette R{s->rr_bounces, o->min_depth, o->q_min};
+    if ((rc = grow(s, s->rr_bounces, ntex * sizeof(uint32_t)))) return rc;
+    HIP_TRY(hipMemsetAsync(s->rr_bounces.ptr, 0, ntex * sizeof(uint32_t), s->stream.s));
+    const DevRoulette R{s->rr_bounces.ptr, o->min_depth, o->q_min};
     rc = adaptive_steps(s, p, a, c.P, c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE, c.wps, out_linear, out_rgb8,
                         out_stderr, out_spp, stats, [&](uint32_t blocks, const uint32_t *tiles) -> int {
                             if (c.coop) {
-                                HIP_TRY(rtmi_roulette_coop_launch_render(c.ext, nee, env, blocks, c.coop_lds, s->stream, s->dev,
+                                HIP_TRY(rtmi_roulette_coop_launch_render(c.ext, nee, env, blocks, c.coop_lds, s->stream.s, s->dev,
                                                                          c.C, c.P, tiles, c.L, c.E, R));
                                 return RTMI_OK;
                             }
-                            HIP_TRY(rtmi_roulette_launch_render(c.fast, nee, env, blocks, s->stream, s->dev, c.C, c.P, tiles,
+                            HIP_TRY(rtmi_roulette_launch_render(c.fast, nee, env, blocks, s->stream.s, s->dev, c.C, c.P, tiles,
                                                                 c.L, c.E, R));
                             return RTMI_OK;
                         });
     if (rc) return rc;
-    if (out_bounces && (rc = download_untiled<1>(&p, s->rr_bounces, ntex, out_bounces))) return rc;
+    if (out_bounces && (rc = download_untiled<1>(&p, s->rr_bounces.ptr, ntex, out_bounces))) return rc;
     return RTMI_OK;
 }
 
@@ -3861,14 +3789,14 @@ extern "C" int rtmi_probe_env(rtmi_scene *s, int op, const float *in, float *out
     HIP_TRY(hipSetDevice(s->device));
     if (int rc = begin_blocking(s)) return rc;
     const size_t nin = (size_t)n * (op == RTMI_ENV_PROBE_LOOKUP ? 3u : 2u), nout = (size_t)n * 4u;
-    float *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&din), nin * sizeof(float)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dout), nout * sizeof(float)));
-    HIP_TRY(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(rtmi_env_launch_probe(op, dev_env(s, s->env_sampled ? 1.0f : 0.0f), din, dout, n, s->stream));
-    HIP_TRY(hipMemcpyAsync(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    (void)hipFree(din); (void)hipFree(dout);
+    float *din, *dout; // one device buffer, freed on every return
+    const auto layout = [&](Carve16 &c) { din = c.take<float>(nin); dout = c.take<float>(nout); };
+    DeviceArena buf;
+    HIP_TRY(buf.alloc<16>(layout));
+    HIP_TRY(hipMemcpyAsync(din, in, nin * sizeof(float), hipMemcpyHostToDevice, s->stream.s));
+    HIP_TRY(rtmi_env_launch_probe(op, dev_env(s, s->env_sampled ? 1.0f : 0.0f), din, dout, n, s->stream.s));
+    HIP_TRY(hipMemcpyAsync(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost, s->stream.s));
+    HIP_TRY(hipStreamSynchronize(s->stream.s));
     return RTMI_OK;
 }
 
@@ -3878,7 +3806,7 @@ extern "C" int rtmi_probe_env(rtmi_scene *s, int op, const float *in, float *out
 // plan_light_coop / plan_traversal, plan_and_reserve, run_passes, the adaptive resolve with decide = 0, which writes the
 // state back for every tile) over a list of tiles that all hold the same count; the convergence test, the read-out and the
 // merge are the kernels of rtmi_session.hip.
-struct rtmi_session {
+struct RTMI_HIDDEN rtmi_session {
     rtmi_scene *s = nullptr;
     rtmi_camera cam{};
     rtmi_render_params p{}; // ns = 1 (not read); the cooperative flag normalised to the one of the session's entries
@@ -3886,8 +3814,8 @@ struct rtmi_session {
     bool refine = false, nee = false, env = false, failed = false;
     uint32_t T = 0;
     std::vector<uint32_t> n; // [tile] the samples each tile holds
-    double *state = nullptr; // [tile][9][64]
-    uint32_t *bounces = nullptr, *d_counts = nullptr; // [tile][64], [tile]
+    DeviceBuf<double> state;               // [tile][9][64]
+    DeviceBuf<uint32_t> bounces, d_counts; // [tile][64], [tile]
     uint32_t last_cap = 0;   // the last refine call's cap and tolerances
     double last_abs = std::numeric_limits<double>::infinity(), last_rel = std::numeric_limits<double>::infinity();
     uint32_t scene_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -3989,14 +3917,13 @@ extern "C" int rtmi_session_create(rtmi_scene *s, const rtmi_camera *cam, const 
                                 nee ? s->nee_n : 0u, env ? s->env_w : 0u, env ? s->env_h : 0u};
     std::memcpy(ss->scene_counts, counts, sizeof(counts));
     const size_t T = ss->T;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&ss->state), T * 9 * 64 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ss->bounces), T * 64 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ss->d_counts), T * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(ss->state, 0, T * 9 * 64 * sizeof(double), s->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ss->bounces, 0, T * 64 * sizeof(uint32_t), s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    hipError_t e = ss->state.alloc(T * 9 * 64 * sizeof(double));
+    if (e == hipSuccess) e = ss->bounces.alloc(T * 64 * sizeof(uint32_t));
+    if (e == hipSuccess) e = ss->d_counts.alloc(T * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(ss->state.ptr, 0, T * 9 * 64 * sizeof(double), s->stream.s);
+    if (e == hipSuccess) e = hipMemsetAsync(ss->bounces.ptr, 0, T * 64 * sizeof(uint32_t), s->stream.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream.s);
     if (e != hipSuccess) {
-        (void)hipFree(ss->state); (void)hipFree(ss->bounces); (void)hipFree(ss->d_counts);
         delete ss;
         return fail(e == hipErrorOutOfMemory ? RTMI_ERR_NOMEM : RTMI_ERR_DEVICE, nm + hipGetErrorString(e));
     }
@@ -4009,8 +3936,8 @@ extern "C" void rtmi_session_destroy(rtmi_session *ss) {
     {
         std::lock_guard<std::mutex> lock(ss->s->mu);
         (void)hipSetDevice(ss->s->device);
-        if (ss->s->busy_recorded) (void)hipEventSynchronize(ss->s->busy);
-        (void)hipFree(ss->state); (void)hipFree(ss->bounces); (void)hipFree(ss->d_counts);
+        if (ss->s->busy_recorded) (void)hipEventSynchronize(ss->s->busy.e);
+        (void)ss->state.release(); (void)ss->bounces.release(); (void)ss->d_counts.release();
     }
     delete ss;
 }
@@ -4046,27 +3973,27 @@ static int session_begin(SessionCall &k, rtmi_session *ss, const Estimator &m) {
         return rc;
     }
     s->last_kernel = c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
-    if ((rc = begin_passes(s, s->stream))) return rc;
-    HIP_TRY(hipEventRecord(s->ev[0], s->stream));
-    HIP_TRY(hipEventRecord(s->ev[2], s->stream));
+    if ((rc = begin_passes(s, s->stream.s))) return rc;
+    HIP_TRY(hipEventRecord(s->ev[0].e, s->stream.s));
+    HIP_TRY(hipEventRecord(s->ev[2].e, s->stream.s));
     return RTMI_OK;
 }
 static int session_launch_render(const SessionCall &k, const rtmi_session *ss, const Estimator &m, uint32_t blocks, const uint32_t *tiles) {
     rtmi_scene *s = ss->s;
     const RenderCall &c = k.c;
     if (!ss->nee && !ss->env && !ss->o.rr) {
-        HIP_TRY(rtmi_adaptive_launch_render(k.which, blocks, c.coop ? c.coop_lds : 0, s->stream, s->dev, c.C, c.P, tiles));
+        HIP_TRY(rtmi_adaptive_launch_render(k.which, blocks, c.coop ? c.coop_lds : 0, s->stream.s, s->dev, c.C, c.P, tiles));
     } else if (ss->o.rr) {
-        const DevRoulette R{ss->bounces, ss->o.min_depth, ss->o.q_min};
+        const DevRoulette R{ss->bounces.ptr, ss->o.min_depth, ss->o.q_min};
         if (c.coop)
-            HIP_TRY(rtmi_roulette_coop_launch_render(c.ext, ss->nee, ss->env, blocks, c.coop_lds, s->stream, s->dev, c.C, c.P, tiles,
+            HIP_TRY(rtmi_roulette_coop_launch_render(c.ext, ss->nee, ss->env, blocks, c.coop_lds, s->stream.s, s->dev, c.C, c.P, tiles,
                                                      c.L, c.E, R));
         else
-            HIP_TRY(rtmi_roulette_launch_render(c.fast, ss->nee, ss->env, blocks, s->stream, s->dev, c.C, c.P, tiles, c.L, c.E, R));
+            HIP_TRY(rtmi_roulette_launch_render(c.fast, ss->nee, ss->env, blocks, s->stream.s, s->dev, c.C, c.P, tiles, c.L, c.E, R));
     } else if (c.coop) {
         return launch_light_coop(c, m, s, false, blocks, tiles);
     } else {
-        HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, ss->nee, ss->env, blocks, s->stream, s->dev, c.C, c.P, tiles, c.L, c.E));
+        HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, ss->nee, ss->env, blocks, s->stream.s, s->dev, c.C, c.P, tiles, c.L, c.E));
     }
     return RTMI_OK;
 }
@@ -4087,37 +4014,37 @@ static uint64_t session_pixels(const rtmi_session *ss, const std::vector<uint32_
 static int session_advance(SessionCall &k, rtmi_session *ss, const Estimator &m, const std::vector<uint32_t> &active, uint32_t from,
                            uint32_t cnt) {
     rtmi_scene *s = ss->s;
-    hipStream_t stream = s->stream;
+    hipStream_t stream = s->stream.s;
     DevParams &P = k.c.P;
     int rc;
     const uint32_t n_active = (uint32_t)active.size();
-    HIP_TRY(hipMemcpyAsync(s->ad_lists, active.data(), (size_t)n_active * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(s->ad_lists.ptr, active.data(), (size_t)n_active * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     rtmi_render_params q = ss->p;
     q.ns = cnt;
     uint32_t chunk_spp = 0, pass_ns = 0;
     if ((rc = plan_and_reserve(s, &q, n_active, chunk_spp, pass_ns))) return rc;
-    P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples;
+    P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples.ptr;
     AdaptiveResolve A;
-    A.tiles_in = s->ad_lists; A.tiles_out = s->ad_lists + ss->T; A.n_out = s->ad_lists + 2 * (size_t)ss->T;
-    A.state = ss->state; A.texels = s->texels; A.stderr_out = s->ad_stderr; A.spp_out = s->ad_spp;
+    A.tiles_in = s->ad_lists.ptr; A.tiles_out = s->ad_lists.ptr + ss->T; A.n_out = s->ad_lists.ptr + 2 * (size_t)ss->T;
+    A.state = ss->state.ptr; A.texels = s->texels.ptr; A.stderr_out = s->ad_stderr.ptr; A.spp_out = s->ad_spp.ptr;
     A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = 0xffffffffu;
     A.decide = 0; // never retires: sum, m and M2 go back to the session's planes after every sub-pass
     const uint32_t s0 = ss->o.first_sample;
     k.worked = true;
     rc = run_passes(s, P, stream, s0 + from, cnt, false, light_run_slots(s, k.c), 1u, k.counts,
                     [&](uint32_t blocks, bool first, bool) -> int {
-                        if (int lrc = session_launch_render(k, ss, m, blocks, (const uint32_t *)s->ad_lists)) return lrc;
+                        if (int lrc = session_launch_render(k, ss, m, blocks, (const uint32_t *)s->ad_lists.ptr)) return lrc;
                         DevParams Pr = P; // the resolve counts from the session's first sample: Welford's k = 1 there
                         Pr.pass_s0 = P.pass_s0 - s0;
                         A.first = (from == 0u && first) ? 1 : 0;
-                        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples, Pr, A));
+                        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples.ptr, Pr, A));
                         return RTMI_OK;
                     });
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2], stream));
+    HIP_TRY(hipEventRecord(s->ev[2].e, stream));
     rtmi_scene *one[1] = {s};
-    if ((rc = wait_with_progress(one, &s->ev[2], 1, &ss->p))) return rc;
+    if ((rc = wait_with_progress(one, &s->ev[2].e, 1, &ss->p))) return rc;
     for (uint32_t t : active) ss->n[t] = from + cnt;
     k.samples += session_pixels(ss, active) * cnt;
     return RTMI_OK;
@@ -4132,8 +4059,8 @@ static int session_end(SessionCall &k, rtmi_session *ss, int rc, rtmi_stats *sta
     }
     if (stats) {
         float ms = 0.f;
-        HIP_TRY(hipEventSynchronize(s->ev[2]));
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
+        HIP_TRY(hipEventSynchronize(s->ev[2].e));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[2].e));
         fill_stats(s, &ss->p, stats, ms, ms, k.counts);
         stats->samples = k.samples;
     }
@@ -4166,12 +4093,12 @@ extern "C" int rtmi_session_render(rtmi_session *ss, uint32_t add_spp, rtmi_stat
 // the tiles of `cand` (all at n samples) that fail the test under (abs_tol, rel_tol), in any order
 static int session_test(rtmi_session *ss, std::vector<uint32_t> &cand, uint32_t n, double abs_tol, double rel_tol) {
     rtmi_scene *s = ss->s;
-    hipStream_t stream = s->stream;
-    uint32_t *in = s->ad_lists, *outl = s->ad_lists + ss->T, *count = s->ad_lists + 2 * (size_t)ss->T;
+    hipStream_t stream = s->stream.s;
+    uint32_t *in = s->ad_lists.ptr, *outl = s->ad_lists.ptr + ss->T, *count = s->ad_lists.ptr + 2 * (size_t)ss->T;
     HIP_TRY(hipMemcpyAsync(in, cand.data(), cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), stream));
     SessionDecide D;
-    D.state = ss->state; D.tiles_in = in; D.n_in = (uint32_t)cand.size(); D.tiles_out = outl; D.n_out = count;
+    D.state = ss->state.ptr; D.tiles_in = in; D.n_in = (uint32_t)cand.size(); D.tiles_out = outl; D.n_out = count;
     D.nx = ss->p.nx; D.ny = ss->p.ny; D.tiles_x = tiles_x_of(&ss->p);
     D.n = n; D.abs_tol = abs_tol; D.rel_tol = rel_tol;
     HIP_TRY(rtmi_session_launch_decide(stream, D));
@@ -4253,18 +4180,18 @@ extern "C" int rtmi_session_image(rtmi_session *ss, float *out_linear, uint8_t *
         if (v == 0u) return fail(RTMI_ERR_INVALID, nm + "the session holds no samples yet");
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = begin_blocking(s))) return rc;
-    BusyMark busy{s, s->stream};
+    BusyMark busy{s, s->stream.s};
     const size_t ntex = (size_t)ss->T * 64;
     if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, ss->T))) return rc;
-    HIP_TRY(hipMemcpyAsync(ss->d_counts, ss->n.data(), (size_t)ss->T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    const SessionReadout R{ss->state, ss->d_counts, ss->T, s->texels, s->ad_stderr, s->ad_spp};
-    HIP_TRY(rtmi_session_launch_readout(s->stream, R));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(s->h_texels, s->texels, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_stderr && (rc = download_untiled<3>(&ss->p, s->ad_stderr, ntex, out_stderr))) return rc;
-    if (out_spp && (rc = download_untiled<1>(&ss->p, s->ad_spp, ntex, out_spp))) return rc;
-    if (out_bounces && (rc = download_untiled<1>(&ss->p, ss->bounces, ntex, out_bounces))) return rc;
-    return rtmi_untile(&ss->p, s->h_texels, out_linear, out_rgb8);
+    HIP_TRY(hipMemcpyAsync(ss->d_counts.ptr, ss->n.data(), (size_t)ss->T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream.s));
+    const SessionReadout R{ss->state.ptr, ss->d_counts.ptr, ss->T, s->texels.ptr, s->ad_stderr.ptr, s->ad_spp.ptr};
+    HIP_TRY(rtmi_session_launch_readout(s->stream.s, R));
+    HIP_TRY(hipStreamSynchronize(s->stream.s));
+    HIP_TRY(hipMemcpy(s->h_texels.ptr, s->texels.ptr, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
+    if (out_stderr && (rc = download_untiled<3>(&ss->p, s->ad_stderr.ptr, ntex, out_stderr))) return rc;
+    if (out_spp && (rc = download_untiled<1>(&ss->p, s->ad_spp.ptr, ntex, out_spp))) return rc;
+    if (out_bounces && (rc = download_untiled<1>(&ss->p, ss->bounces.ptr, ntex, out_bounces))) return rc;
+    return rtmi_untile(&ss->p, s->h_texels.ptr, out_linear, out_rgb8);
 }
 
 extern "C" int rtmi_session_export(rtmi_session *ss, void *buf, size_t cap, size_t *need) {
@@ -4278,16 +4205,16 @@ extern "C" int rtmi_session_export(rtmi_session *ss, void *buf, size_t cap, size
     rtmi_scene *s = ss->s;
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
     uint8_t *b = static_cast<uint8_t *>(buf);
     const std::vector<uint8_t> h = session_header(ss);
     std::memcpy(b, h.data(), h.size());
     size_t at = h.size();
     std::memcpy(b + at, ss->n.data(), (size_t)ss->T * 4);
     at += (size_t)ss->T * 4;
-    HIP_TRY(hipMemcpy(b + at, ss->state, (size_t)ss->T * 9 * 64 * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b + at, ss->state.ptr, (size_t)ss->T * 9 * 64 * 8, hipMemcpyDeviceToHost));
     at += (size_t)ss->T * 9 * 64 * 8;
-    HIP_TRY(hipMemcpy(b + at, ss->bounces, (size_t)ss->T * 64 * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(b + at, ss->bounces.ptr, (size_t)ss->T * 64 * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 
@@ -4317,10 +4244,10 @@ extern "C" int rtmi_session_import(rtmi_session *ss, const void *buf, size_t len
     rtmi_scene *s = ss->s;
     std::lock_guard<std::mutex> lock(s->mu);
     HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy));
-    HIP_TRY(hipMemcpy(ss->state, b + at, (size_t)ss->T * 9 * 64 * 8, hipMemcpyHostToDevice));
+    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
+    HIP_TRY(hipMemcpy(ss->state.ptr, b + at, (size_t)ss->T * 9 * 64 * 8, hipMemcpyHostToDevice));
     at += (size_t)ss->T * 9 * 64 * 8;
-    HIP_TRY(hipMemcpy(ss->bounces, b + at, (size_t)ss->T * 64 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ss->bounces.ptr, b + at, (size_t)ss->T * 64 * 4, hipMemcpyHostToDevice));
     ss->n = n;
     ss->last_cap = cap; ss->last_abs = abs_tol; ss->last_rel = rel_tol;
     ss->failed = false;
@@ -4352,17 +4279,17 @@ extern "C" int rtmi_session_merge(rtmi_session *dst, const rtmi_session *src) {
     }
     HIP_TRY(hipSetDevice(s->device));
     if ((rc = begin_blocking(s))) return rc;
-    if (s2 != s && s2->busy_recorded) HIP_TRY(hipEventSynchronize(s2->busy));
-    BusyMark busy{s, s->stream};
+    if (s2 != s && s2->busy_recorded) HIP_TRY(hipEventSynchronize(s2->busy.e));
+    BusyMark busy{s, s->stream.s};
     const size_t T = dst->T;
     if (nA == 0u) {
-        HIP_TRY(hipMemcpyAsync(dst->state, src->state, T * 9 * 64 * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(dst->bounces, src->bounces, T * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(dst->state.ptr, src->state.ptr, T * 9 * 64 * sizeof(double), hipMemcpyDeviceToDevice, s->stream.s));
+        HIP_TRY(hipMemcpyAsync(dst->bounces.ptr, src->bounces.ptr, T * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream.s));
     } else {
-        const SessionMerge M{dst->state, src->state, dst->bounces, src->bounces, dst->T, (double)nA, (double)nB};
-        HIP_TRY(rtmi_session_launch_merge(s->stream, M));
+        const SessionMerge M{dst->state.ptr, src->state.ptr, dst->bounces.ptr, src->bounces.ptr, dst->T, (double)nA, (double)nB};
+        HIP_TRY(rtmi_session_launch_merge(s->stream.s, M));
     }
-    const hipError_t e = hipStreamSynchronize(s->stream);
+    const hipError_t e = hipStreamSynchronize(s->stream.s);
     if (e != hipSuccess) {
         dst->failed = true;
         return fail(RTMI_ERR_DEVICE, nm + hipGetErrorString(e));
@@ -4373,7 +4300,7 @@ extern "C" int rtmi_session_merge(rtmi_session *dst, const rtmi_session *src) {
 
 // ---- the frame pipeline's seams (rtmi_frame_launch.hpp, include/rtmi_frame.h) ------------------------------------------
 // The device halves of the two renders of a frame, under one hold on the scene.  rtmi_frame.hip runs the rest of the frame
-// on s->stream before it ends the hold.
+// on s->stream.s before it ends the hold.
 struct RtmiFrameHold {
     RenderCall c;
     rtmi_scene *s = nullptr;
@@ -4405,7 +4332,7 @@ int rtmi_frame_enqueue_lit(RtmiFrameHold *hold, const RtmiFrameLit &fm, const rt
         if (int rc = adaptive_plain_device(hold->c, m, s, cam, p, &a, counts)) return rc;
         if (stats) {
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0], s->ev[2]));
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[2].e));
             fill_stats(s, &p, stats, ms, ms, counts); // every tile stops at ns: the samples are fill_stats'
         }
         return RTMI_OK;
@@ -4419,6 +4346,6 @@ int rtmi_frame_enqueue_first_hits(RtmiFrameHold *hold, const rtmi_camera *cam, c
 RtmiFramePlanes rtmi_frame_planes(const RtmiFrameHold *hold, const rtmi_render_params &p) {
     const rtmi_scene *s = hold->s;
     const size_t npix = (size_t)p.nx * p.ny;
-    return RtmiFramePlanes{s->device, s->stream, s->texels, s->ad_stderr, s->ft_planes, s->ft_planes + npix * 3, s->ft_planes + npix * 6,
-                           reinterpret_cast<const uint32_t *>(s->ft_planes + npix * 7)};
+    return RtmiFramePlanes{s->device, s->stream.s, s->texels.ptr, s->ad_stderr.ptr, s->ft_planes.ptr, s->ft_planes.ptr + npix * 3, s->ft_planes.ptr + npix * 6,
+                           reinterpret_cast<const uint32_t *>(s->ft_planes.ptr + npix * 7)};
 }

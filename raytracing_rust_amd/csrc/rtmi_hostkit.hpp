@@ -1,13 +1,14 @@
 // rtmi_hostkit.hpp — the host-side helpers the translation units share: the refusal composer, the device check, the
-// "return on a HIP error" macro and the owners of one device allocation and of one stream.  Everything is static inline, so
-// librtmi.so exports nothing from here.  What stays with each unit: whether out-of-memory answers RTMI_ERR_NOMEM, the order
-// in which a handle is torn down, and the caller-visible scratch layouts.  See DESIGN.md §34.
+// "return on a HIP error" macro and the owners of device memory, pinned memory, a stream and an event.  Everything is static
+// inline, so librtmi.so exports nothing from here.  What stays with each unit: whether out-of-memory answers RTMI_ERR_NOMEM,
+// the order in which a handle is torn down, and the caller-visible scratch layouts.  See DESIGN.md §34 and §36.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "rtmi.h"
 #include "rtmi_carve.hpp"
@@ -71,7 +72,65 @@ struct RTMI_HIDDEN DeviceArena {
     }
 };
 
-// One non-blocking stream, destroyed by the destructor.
+// One typed grow-only buffer that knows its size: device memory (hipMalloc), or with Pinned host memory (hipHostMalloc).
+// Freed by the destructor, or by release() where a handle fixes the moment; empty (ptr NULL, bytes 0) after a failure.
+template <typename T, bool Pinned = false>
+struct RTMI_HIDDEN DeviceBuf {
+    T *ptr = nullptr;
+    size_t bytes = 0;
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf &) = delete;
+    DeviceBuf &operator=(const DeviceBuf &) = delete;
+    ~DeviceBuf() { (void)release(); }
+    hipError_t release() {
+        T *const old = give();
+        return !old ? hipSuccess : Pinned ? hipHostFree(old) : hipFree(old);
+    }
+    // frees what it holds and allocates `want` bytes on the current device
+    hipError_t alloc(size_t want) {
+        hipError_t e = release();
+        void *p = nullptr;
+        if (e == hipSuccess) e = Pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+        if (e == hipSuccess) adopt(p, want);
+        return e;
+    }
+    // grow-only: no call when `want` bytes are there already
+    hipError_t grow(size_t want) { return want <= bytes ? hipSuccess : alloc(want); }
+    // hands the allocation to the caller, who frees it or gives it to another owner (adopt); nothing is held afterwards
+    T *give(size_t *had = nullptr) {
+        T *const p = ptr;
+        if (had) *had = bytes;
+        ptr = nullptr;
+        bytes = 0;
+        return p;
+    }
+    // takes over an allocation of `n` bytes; the buffer must be empty
+    void adopt(void *p, size_t n) { ptr = static_cast<T *>(p), bytes = n; }
+};
+template <typename T>
+using PinnedBuf = DeviceBuf<T, true>;
+
+// Device allocations made one by one and freed together (a scene's arrays: one allocation per array).
+struct RTMI_HIDDEN DeviceList {
+    std::vector<void *> all;
+    DeviceList() = default;
+    DeviceList(const DeviceList &) = delete;
+    DeviceList &operator=(const DeviceList &) = delete;
+    ~DeviceList() { (void)release(); }
+    hipError_t add(void **out, size_t bytes) {
+        all.reserve(all.size() + 1); // (so that the allocation cannot be lost to a failing push_back)
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e == hipSuccess) all.push_back(*out);
+        return e;
+    }
+    hipError_t release() {
+        for (void *p : all) (void)hipFree(p);
+        all.clear();
+        return hipSuccess;
+    }
+};
+
+// One stream, destroyed by the destructor; create() makes a non-blocking one.
 struct RTMI_HIDDEN DeviceStream {
     hipStream_t s = nullptr;
     DeviceStream() = default;
@@ -81,4 +140,15 @@ struct RTMI_HIDDEN DeviceStream {
         if (s) (void)hipStreamDestroy(s);
     }
     hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+};
+
+// One event, destroyed by the destructor (the handle creates it: timing or not is its choice).
+struct RTMI_HIDDEN DeviceEvent {
+    hipEvent_t e = nullptr;
+    DeviceEvent() = default;
+    DeviceEvent(const DeviceEvent &) = delete;
+    DeviceEvent &operator=(const DeviceEvent &) = delete;
+    ~DeviceEvent() {
+        if (e) (void)hipEventDestroy(e);
+    }
 };
