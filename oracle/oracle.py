@@ -30,9 +30,13 @@ COUNTER_NAMES = [
     # the environment estimator and roulette (appended: the indices above keep their meaning)
     "env_sample", "env_no_sample", "env_occluded", "env_unoccluded", "env_miss_mis", "env_miss_one", "env_area_sample",
     "env_emit_scaled", "rr_test", "rr_draw", "rr_end_pending", "rr_end_bare", "rr_floor_survive", "rr_zero",
+    # the light tree under render_nee (appended)
+    "tree_walk", "tree_left", "tree_right", "tree_floor", "tree_p_one", "tree_clamp", "tree_no_sample", "tree_hit_pmf",
+    "tree_hit_picked", "tree_hit_picked_mismatch",
 ]
 ENV_COUNTERS = COUNTER_NAMES[24:32]
 ROULETTE_COUNTERS = COUNTER_NAMES[32:38]
+TREE_COUNTERS = COUNTER_NAMES[38:48]
 ROULETTE_ESTIMATORS = {"plain": 0, "nee": 1, "env": 2, "env_nee": 3}  # RTMI_ROULETTE_*
 
 PLANE_YZ, PLANE_ZX, PLANE_XY = 0, 1, 2
@@ -45,6 +49,9 @@ EMITTER_DTYPE = np.dtype([("handle", "<u8"), ("kind", "<i4"), ("plane", "<i4"), 
                           ("weight", "<f8"), ("area", "<f8")])  # OrcEmitter, 88 B
 LIGHT_DTYPE = np.dtype([("handle", "<u8"), ("kind", "<i4"), ("plane", "<i4"), ("geo", "<f8", (5,)), ("area", "<f8"),
                         ("p_sel", "<f8"), ("cdf", "<f8")])  # OrcLight, 80 B
+# the light tree (include/rtmi_light_tree.h): rtmi_light_node and rtmi_light_path as the oracle reads them
+LIGHT_NODE_DTYPE = np.dtype([("c", "<f4", (3,)), ("r2", "<f4"), ("power", "<f4"), ("link", "<u4"), ("pad", "<u4", (2,))])  # 32 B
+LIGHT_PATH_DTYPE = np.dtype([("trail", "<u4"), ("depth", "<u4")])  # 8 B
 AXIS_X, AXIS_Y, AXIS_Z = 0, 1, 2
 
 
@@ -66,6 +73,13 @@ def _env(env_rgb, tables):
         assert a.shape == shape, (k, a.shape)
         keep.append(a)
     return OrcEnv(w, h, *[a.ctypes.data for a in keep], float(tables["total"])), keep
+
+
+def _tree(tree):
+    """(nodes, paths) of a light tree as contiguous arrays of the oracle's own dtypes; the bytes are taken as they are"""
+    nodes, paths = (np.ascontiguousarray(a) for a in tree)
+    assert nodes.dtype.itemsize == LIGHT_NODE_DTYPE.itemsize and paths.dtype.itemsize == LIGHT_PATH_DTYPE.itemsize
+    return nodes.view(LIGHT_NODE_DTYPE), paths.view(LIGHT_PATH_DTYPE)
 
 
 def build():
@@ -127,6 +141,9 @@ def _load(name):
         "orc_render": (i, [vp, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp]),
         "orc_render_samples": (i, [vp, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
         "orc_render_nee": (i, [vp, vp, vp, i, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
+        "orc_render_nee_tree": (i, [vp, vp, vp, i, vp, i, vp, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
+        "orc_light_tree_pick": (i, [vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]),
+        "orc_light_tree_pmf": (i, [vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp]),
         "orc_render_env": (i, [vp, vp, vp, i, vp, i, d, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp]),
         "orc_render_roulette": (i, [vp, vp, vp, i, vp, i, i, d, d, i, i, i, u64, i, i, d, i, i, vp, vp, vp, vp, vp, vp]),
         "orc_env_lookup": (i, [vp, d, i, vp, vp, C.c_long]),
@@ -317,18 +334,49 @@ class Oracle:
         return out[:n]
 
     def render_nee(self, cam, world, lights, nx, ny, ns, seed=42, flags=0, max_depth=50, t_min=0.001, rows=None,
-                   samples=False):
+                   samples=False, tree=None):
         """rtmi_render_nee's estimator (include/rtmi_nee.h) with the light table `lights` (LIGHT_DTYPE, the device's
-        order; area, p_sel and cdf as the device's floats).  Returns render()'s dict (the throughput form is implied),
-        plus samples f32 [ny,nx,ns,3] when samples=True."""
+        order; area, p_sel and cdf as the device's floats).  tree=(nodes, paths) (LIGHT_NODE_DTYPE, LIGHT_PATH_DTYPE; the
+        tree over that table): the estimator under RTMI_FLAG_LIGHT_TREE (include/rtmi_light_tree.h).  Returns render()'s
+        dict (the throughput form is implied), plus samples f32 [ny,nx,ns,3] when samples=True."""
         r0, r1 = (0, ny) if rows is None else rows
         lt = np.ascontiguousarray(lights, dtype=LIGHT_DTYPE)
         out, ptrs = self._outputs(nx, ny, ns, samples)
-        rc = self.lib.orc_render_nee(cam.h, world.h, lt.ctypes.data if len(lt) else None, len(lt), nx, ny, ns, int(seed),
-                                     flags, max_depth, t_min, r0, r1, *ptrs)
+        if tree is None:
+            rc = self.lib.orc_render_nee(cam.h, world.h, lt.ctypes.data if len(lt) else None, len(lt), nx, ny, ns, int(seed),
+                                         flags, max_depth, t_min, r0, r1, *ptrs)
+        else:
+            nodes, paths = _tree(tree)
+            rc = self.lib.orc_render_nee_tree(cam.h, world.h, lt.ctypes.data if len(lt) else None, len(lt),
+                                              nodes.ctypes.data if len(nodes) else None, len(nodes),
+                                              paths.ctypes.data if len(paths) else None, nx, ny, ns, int(seed), flags, max_depth,
+                                              t_min, r0, r1, *ptrs)
         if rc != 0:
             raise RuntimeError("orc_render_nee failed")
         return out
+
+    def light_tree_pick(self, nodes, points, us):
+        """The walk of include/rtmi_light_tree.h from float32 points [n, 3] with the uniforms us [n] -> (light uint32 [n],
+        probability float32 [n]); in this library's precision, the probability rounded to float."""
+        nodes, _ = _tree((nodes, np.zeros(0, LIGHT_PATH_DTYPE)))
+        x, u = np.ascontiguousarray(points, np.float32), np.ascontiguousarray(us, np.float32)
+        assert x.shape == (len(u), 3)
+        light, p = np.zeros(len(u), np.uint32), np.zeros(len(u), np.float32)
+        if self.lib.orc_light_tree_pick(nodes.ctypes.data, len(nodes), x.ctypes.data, u.ctypes.data, len(u), light.ctypes.data,
+                                        p.ctypes.data) != 0:
+            raise RuntimeError("orc_light_tree_pick failed")
+        return light, p
+
+    def light_tree_pmf(self, nodes, paths, points, lights):
+        """The reverse walk: the probability float32 [n] that the walk from points [n, 3] ends at lights [n]."""
+        nodes, paths = _tree((nodes, paths))
+        x, li = np.ascontiguousarray(points, np.float32), np.ascontiguousarray(lights, np.uint32)
+        assert x.shape == (len(li), 3)
+        p = np.zeros(len(li), np.float32)
+        if self.lib.orc_light_tree_pmf(nodes.ctypes.data, len(nodes), paths.ctypes.data, x.ctypes.data, li.ctypes.data, len(li),
+                                       p.ctypes.data) != 0:
+            raise RuntimeError("orc_light_tree_pmf failed")
+        return p
 
     def render_env(self, cam, world, lights, env_rgb, tables, nee, env_select_p, nx, ny, ns, seed=42, flags=0, max_depth=50,
                    t_min=0.001, rows=None, samples=False):

@@ -100,6 +100,17 @@ enum {
     C_RR_END_BARE,       /* ... of a vertex without one                                                      */
     C_RR_FLOOR_SURVIVE,  /* survivals with q == q_min: the floor binds                                       */
     C_RR_ZERO,           /* continuations ended by m == 0                                                    */
+    /* the light tree (include/rtmi_light_tree.h) under color_nee.  Appended only. */
+    C_TREE_WALK,         /* light samples chosen by a walk                                                   */
+    C_TREE_LEFT,         /* child choices of the walks: left ...                                             */
+    C_TREE_RIGHT,        /* ... and right                                                                    */
+    C_TREE_FLOOR,        /* node importances where r2 won the max                                            */
+    C_TREE_P_ONE,        /* interior nodes of a walk where pl or pr rounded to exactly 1                     */
+    C_TREE_CLAMP,        /* uniforms clamped to 1 - 2^-24                                                    */
+    C_TREE_NO_SAMPLE,    /* walks whose nee_sample returned 0                                                */
+    C_TREE_HIT_PMF,      /* BSDF hits of a table light weighted through the reverse walk                     */
+    C_TREE_HIT_PICKED,   /* ... whose light is the one the previous vertex's walk picked                     */
+    C_TREE_HIT_PICKED_MISMATCH, /* ... whose pmf differs from the probability that pick returned: stays 0    */
     C_NCOUNTERS
 };
 static uint64_t g_cnt[C_NCOUNTERS];
@@ -1023,6 +1034,97 @@ static int nee_sample(const NeeL *L, V3 x, REAL u1, REAL u2, V3 *dir, REAL *pl) 
     return tq > (REAL)0;
 }
 
+/* ---- the light tree — include/rtmi_light_tree.h, written from its "Selection" paragraph ---------------------------- */
+/* The exported layouts are rtmi_light_node (32 B) and rtmi_light_path (8 B).  The stored values are floats; every
+ * operation below is in REAL: the fp32 library rounds each once as the header says, the f64 library evaluates the same
+ * operations in double on the floats widened. */
+typedef struct {
+    float c[3];
+    float r2;
+    float power;
+    uint32_t link; /* interior: slot of the left child, the right one follows; leaf: TREE_LEAF | light */
+    uint32_t pad[2];
+} OrcLightNode;
+typedef struct {
+    uint32_t trail, depth;
+} OrcLightPath;
+typedef struct {
+    const OrcLightNode *nodes;
+    uint32_t n_nodes;
+    const OrcLightPath *paths; /* n_nodes / 2 entries; pick does not read them */
+} LightTree;
+#define TREE_LEAF 0x80000000u
+#define TREE_ONE_MINUS ((REAL)0.99999994039535522) /* 1 - 2^-24 */
+
+/* 0 when every walk over the tree stays inside it and ends: 2 * lights slots, the children of an interior node at an
+ * even link past their parent, every leaf a light of the table, no path deeper than 32 */
+static int tree_invalid(const LightTree *t) {
+    if (!t->nodes || t->n_nodes < 2u || (t->n_nodes & 1u)) return 1;
+    for (uint32_t i = 1; i < t->n_nodes; i++) {
+        const uint32_t link = t->nodes[i].link;
+        if (link & TREE_LEAF) {
+            if ((link & ~TREE_LEAF) >= t->n_nodes / 2u) return 1;
+        } else if (link <= i || (link & 1u) || link >= t->n_nodes - 1u) {
+            return 1;
+        }
+    }
+    if (t->paths)
+        for (uint32_t i = 0; i < t->n_nodes / 2u; i++)
+            if (t->paths[i].depth > 32u) return 1;
+    return 0;
+}
+/* I = N.power / max(d2, N.r2), d = N.c - x per component, d2 = (d.x * d.x + d.y * d.y) + d.z * d.z */
+static REAL tree_importance(const OrcLightNode *N, V3 x) {
+    const REAL dx = (REAL)N->c[0] - x.x, dy = (REAL)N->c[1] - x.y, dz = (REAL)N->c[2] - x.z;
+    const REAL d2 = (dx * dx + dy * dy) + dz * dz;
+    const REAL r2 = (REAL)N->r2;
+    if (!(d2 > r2)) COUNT(C_TREE_FLOOR);
+    return (REAL)N->power / (d2 > r2 ? d2 : r2);
+}
+/* the light the walk from x with the uniform u ends at, and its probability */
+static uint32_t tree_pick(const LightTree *t, V3 x, REAL u, REAL *p_out) {
+    uint32_t link = t->nodes[1].link;
+    REAL p = 1;
+    while (!(link & TREE_LEAF)) {
+        const OrcLightNode *Lc = &t->nodes[link], *Rc = &t->nodes[link + 1u];
+        const REAL il = tree_importance(Lc, x), ir = tree_importance(Rc, x);
+        const REAL s = il + ir;
+        const REAL pl = il / s;
+        REAL v;
+        if (pl == (REAL)1 || ir / s == (REAL)1) COUNT(C_TREE_P_ONE); /* counted only: pr is the else branch's */
+        if (u < pl) {
+            COUNT(C_TREE_LEFT);
+            v = u / pl;
+            p = p * pl;
+            link = Lc->link;
+        } else {
+            const REAL pr = ir / s;
+            COUNT(C_TREE_RIGHT);
+            v = (u - pl) / pr;
+            p = p * pr;
+            link = Rc->link;
+        }
+        u = v < TREE_ONE_MINUS ? v : TREE_ONE_MINUS;
+        if (!(v <= TREE_ONE_MINUS)) COUNT(C_TREE_CLAMP);
+    }
+    *p_out = p;
+    return link & ~TREE_LEAF;
+}
+/* the probability that the walk from x ends at light li: the product along paths[li] */
+static REAL tree_pmf(const LightTree *t, V3 x, uint32_t li) {
+    const uint32_t trail = t->paths[li].trail, depth = t->paths[li].depth;
+    uint32_t link = t->nodes[1].link;
+    REAL p = 1;
+    for (uint32_t d = 0; d < depth && !(link & TREE_LEAF); d++) {
+        const OrcLightNode *Lc = &t->nodes[link], *Rc = &t->nodes[link + 1u];
+        const REAL il = tree_importance(Lc, x), ir = tree_importance(Rc, x);
+        const REAL s = il + ir;
+        if ((trail >> d) & 1u) { p = p * (ir / s); link = Rc->link; }
+        else { p = p * (il / s); link = Lc->link; }
+    }
+    return p;
+}
+
 /* the light-sample stream of the current pixel sample: counter (block, sample, pixel, 3) */
 static Stream g_light_rng;
 
@@ -1041,10 +1143,16 @@ static int shadow_hit(const RenderCtx *cx, V3 x, V3 dir, REAL time, HitRecord *s
 /* color_throughput with one light sample per scattering Lambertian / Isotropic vertex, combined with the BSDF sample by
  * the power heuristic (include/rtmi_nee.h).  With n == 0 it is color_throughput.  The vertex's light sample is fixed
  * (c, dir) before T takes the attenuation and before the roulette test; its shadow ray is traced after the test, also
- * when the test ends the continuation (include/rtmi_roulette.h). */
-static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
+ * when the test ends the continuation (include/rtmi_roulette.h).
+ * With a light tree over a table of more than one light (include/rtmi_light_tree.h) the vertex's light is the walk's
+ * from the vertex, and the walk's probability takes p_sel's place in a working copy of the light: the pick's at the
+ * light sample, the reverse walk's from the ray's origin at a BSDF hit.  Nothing else changes. */
+static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n, const LightTree *tree) {
     V3 L = v3(0, 0, 0), T = v3(1, 1, 1);
     REAL pb = 0; /* density of the scatter that produced `ray`; 0 = weight 1 at an emitter hit */
+    const int walk = tree && n > 1;
+    int picked = -1;   /* the light the previous vertex's walk picked (meaningful while pb > 0) ... */
+    REAL picked_p = 0; /* ... and the probability the pick returned */
     int depth;
     for (depth = 0;; depth++) {
         HitRecord rec;
@@ -1058,7 +1166,19 @@ static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
         if (rec.mat->kind == MAT_DIFFUSE_LIGHT && rec.prim && pb > (REAL)0) {
             for (int li = 0; li < n; li++) {
                 if (lights[li].h != rec.prim) continue;
-                REAL pl = nee_pdf(&lights[li], ray.o, rec.p);
+                REAL pl;
+                if (walk) {
+                    NeeL Lt = lights[li];
+                    Lt.p_sel = tree_pmf(tree, ray.o, (uint32_t)li);
+                    COUNT(C_TREE_HIT_PMF);
+                    if (li == picked) {
+                        COUNT(C_TREE_HIT_PICKED);
+                        if (memcmp(&Lt.p_sel, &picked_p, sizeof(REAL)) != 0) COUNT(C_TREE_HIT_PICKED_MISMATCH);
+                    }
+                    pl = nee_pdf(&Lt, ray.o, rec.p);
+                } else {
+                    pl = nee_pdf(&lights[li], ray.o, rec.p);
+                }
                 if (pl > (REAL)0) emitted = v_scale(emitted, nee_mis_bsdf(pb, pl));
                 break;
             }
@@ -1079,13 +1199,27 @@ static V3 color_nee(const RenderCtx *cx, Ray ray, const NeeL *lights, int n) {
             pb = iso ? NEE_INV_4PI : nee_pb_lambert(scattered.d, hn);
             uint32_t w0 = stream_u32(&g_light_rng), w1 = stream_u32(&g_light_rng), w2 = stream_u32(&g_light_rng);
             REAL us = (REAL)rtmi_u01(w0);
-            int hi = n - 1; /* the first light whose cdf exceeds us */
-            while (lo < hi) {
-                int mid = (lo + hi) >> 1;
-                if (us < lights[mid].cdf) hi = mid; else lo = mid + 1;
+            NeeL Lt;               /* the working copy under the tree */
+            const NeeL *Ls;        /* the light that is sampled */
+            if (walk) {
+                COUNT(C_TREE_WALK);
+                lo = (int)tree_pick(tree, rec.p, us, &picked_p);
+                picked = lo;
+                Lt = lights[lo];
+                Lt.p_sel = picked_p;
+                Ls = &Lt;
+            } else {
+                int hi = n - 1; /* the first light whose cdf exceeds us */
+                while (lo < hi) {
+                    int mid = (lo + hi) >> 1;
+                    if (us < lights[mid].cdf) hi = mid; else lo = mid + 1;
+                }
+                Ls = &lights[lo];
             }
             REAL pl;
-            if (nee_sample(&lights[lo], rec.p, (REAL)rtmi_u01(w1), (REAL)rtmi_u01(w2), &dir, &pl)) {
+            const int sampled = nee_sample(Ls, rec.p, (REAL)rtmi_u01(w1), (REAL)rtmi_u01(w2), &dir, &pl);
+            if (walk && !sampled) COUNT(C_TREE_NO_SAMPLE);
+            if (sampled) {
                 REAL pbl = iso ? NEE_INV_4PI : nee_pb_lambert(dir, hn);
                 if (pbl > (REAL)0 && pl > (REAL)0 && pl < R_MAX) {
                     c = v_scale(v_mul(T, att), nee_mis_light(pbl, pl));
@@ -1702,6 +1836,7 @@ typedef struct {
     double rr_q_min;
     float *out_samples;     /* [ny, nx, ns, 3] or NULL */
     uint32_t *out_bounces;  /* [ny, nx] or NULL */
+    const LightTree *tree;  /* not NULL: color_nee selects by the light tree (read by the NEE path only) */
 } RowsExt;
 
 /* The pixel loop of orc_render for the estimators the tests compare: the plain path, NEE (always the throughput form),
@@ -1710,7 +1845,7 @@ typedef struct {
 static int render_rows(void *cam_, void *world_, const RowsExt *x, int nx, int ny, int ns, uint64_t seed, int flags,
                        int max_depth, double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
                        double *out_mean, uint64_t *out_sig) {
-    static const RowsExt plain = {0, NULL, 0, NULL, 0, 1.0, NULL, NULL};
+    static const RowsExt plain = {0, NULL, 0, NULL, 0, 1.0, NULL, NULL, NULL};
     if (!x) x = &plain;
     const Camera *cam = (Camera *)cam_;
     const int nee = x->nee, n_lights = x->n_lights;
@@ -1757,7 +1892,7 @@ static int render_rows(void *cam_, void *world_, const RowsExt *x, int nx, int n
                 if (x->env) {
                     c = color_env(&cx, ray, lights, lights ? n_lights : 0, x->env, nee);
                 } else if (nee) {
-                    c = color_nee(&cx, ray, lights, lights ? n_lights : 0);
+                    c = color_nee(&cx, ray, lights, lights ? n_lights : 0, x->tree);
                 } else {
                     c = throughput ? color_throughput(&cx, ray) : color(&cx, &ray, 0);
                 }
@@ -1798,7 +1933,7 @@ ORC_API int orc_render(void *cam_, void *world_, int nx, int ny, int ns, uint64_
 ORC_API int orc_render_samples(void *cam_, void *world_, int nx, int ny, int ns, uint64_t seed, int flags, int max_depth,
                                double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
                                double *out_mean, uint64_t *out_sig, float *out_samples) {
-    RowsExt x = {0, NULL, 0, NULL, 0, 1.0, out_samples, NULL};
+    RowsExt x = {0, NULL, 0, NULL, 0, 1.0, out_samples, NULL, NULL};
     return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags, max_depth, t_min, row_begin, row_end, out_linear,
                        out_rgb, out_mean, out_sig);
 }
@@ -1809,9 +1944,48 @@ ORC_API int orc_render_nee(void *cam_, void *world_, const OrcLight *lights, int
                            uint64_t seed, int flags, int max_depth, double t_min, int row_begin, int row_end,
                            float *out_linear, int32_t *out_rgb, double *out_mean, uint64_t *out_sig, float *out_samples) {
     if (n_lights < 0 || (n_lights > 0 && !lights)) return 1;
-    RowsExt x = {1, lights, n_lights, NULL, 0, 1.0, out_samples, NULL};
+    RowsExt x = {1, lights, n_lights, NULL, 0, 1.0, out_samples, NULL, NULL};
     return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
                        row_end, out_linear, out_rgb, out_mean, out_sig);
+}
+/* orc_render_nee under RTMI_FLAG_LIGHT_TREE (include/rtmi_light_tree.h): the tree over that table first (nodes: n_nodes
+ * = 2 * n_lights entries, paths: n_lights entries, as rtmi_light_tree_from_desc writes them), then orc_render_nee's
+ * arguments.  An empty table with n_nodes = 0, and a table of one light, render as orc_render_nee does. */
+ORC_API int orc_render_nee_tree(void *cam_, void *world_, const OrcLight *lights, int n_lights, const OrcLightNode *nodes,
+                                int n_nodes, const OrcLightPath *paths, int nx, int ny, int ns, uint64_t seed, int flags,
+                                int max_depth, double t_min, int row_begin, int row_end, float *out_linear, int32_t *out_rgb,
+                                double *out_mean, uint64_t *out_sig, float *out_samples) {
+    if (n_lights < 0 || (n_lights > 0 && !lights) || n_nodes != 2 * n_lights) return 1;
+    LightTree t = {nodes, (uint32_t)n_nodes, paths};
+    if (n_lights > 0 && (!paths || tree_invalid(&t))) return 1;
+    RowsExt x = {1, lights, n_lights, NULL, 0, 1.0, out_samples, NULL, n_lights > 0 ? &t : NULL};
+    return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
+                       row_end, out_linear, out_rgb, out_mean, out_sig);
+}
+/* The walks alone, as rtmi_light_tree_pick and rtmi_light_tree_pmf: points n * 3 floats, us n floats, lights n indices;
+ * out_light and out_p n entries (pick: either may be NULL).  1 for a NULL argument that is read, a tree that
+ * tree_invalid refuses and a light index outside the table. */
+ORC_API int orc_light_tree_pick(const OrcLightNode *nodes, uint32_t n_nodes, const float *points, const float *us, uint32_t n,
+                                uint32_t *out_light, float *out_p) {
+    LightTree t = {nodes, n_nodes, NULL};
+    if (tree_invalid(&t) || (n > 0 && (!points || !us))) return 1;
+    for (uint32_t k = 0; k < n; k++) {
+        REAL p;
+        const uint32_t li = tree_pick(&t, v3((REAL)points[3 * k], (REAL)points[3 * k + 1], (REAL)points[3 * k + 2]), (REAL)us[k], &p);
+        if (out_light) out_light[k] = li;
+        if (out_p) out_p[k] = (float)p;
+    }
+    return 0;
+}
+ORC_API int orc_light_tree_pmf(const OrcLightNode *nodes, uint32_t n_nodes, const OrcLightPath *paths, const float *points,
+                               const uint32_t *lights, uint32_t n, float *out_p) {
+    LightTree t = {nodes, n_nodes, paths};
+    if (!paths || tree_invalid(&t) || (n > 0 && (!points || !lights || !out_p))) return 1;
+    for (uint32_t k = 0; k < n; k++) {
+        if (lights[k] >= n_nodes / 2u) return 1;
+        out_p[k] = (float)tree_pmf(&t, v3((REAL)points[3 * k], (REAL)points[3 * k + 1], (REAL)points[3 * k + 2]), lights[k]);
+    }
+    return 0;
 }
 
 /* The exported map: the texels and the tables of rtmi_env_tables (the tests pass tests/env_ref.py's), 56 B. */
@@ -1838,7 +2012,7 @@ ORC_API int orc_render_env(void *cam_, void *world_, const OrcLight *lights, int
     EnvMap E;
     if (n_lights < 0 || (n_lights > 0 && !lights) || (nee != 0 && nee != 1)) return 1;
     if (env_map_of(env, n_lights, env_select_p, &E)) return 1;
-    RowsExt x = {nee, lights, n_lights, &E, 0, 1.0, out_samples, NULL};
+    RowsExt x = {nee, lights, n_lights, &E, 0, 1.0, out_samples, NULL, NULL};
     return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
                        row_end, out_linear, out_rgb, out_mean, out_sig);
 }
@@ -1856,7 +2030,7 @@ ORC_API int orc_render_roulette(void *cam_, void *world_, const OrcLight *lights
     if (n_lights < 0 || (n_lights > 0 && !lights)) return 1;
     if (!nee) n_lights = 0;
     if (with_env && env_map_of(env, n_lights, env_select_p, &E)) return 1;
-    RowsExt x = {nee, nee ? lights : NULL, n_lights, with_env ? &E : NULL, min_depth, q_min, out_samples, out_bounces};
+    RowsExt x = {nee, nee ? lights : NULL, n_lights, with_env ? &E : NULL, min_depth, q_min, out_samples, out_bounces, NULL};
     return render_rows(cam_, world_, &x, nx, ny, ns, seed, flags | ORC_THROUGHPUT_FORM, max_depth, t_min, row_begin,
                        row_end, out_linear, out_rgb, out_mean, out_sig);
 }

@@ -12,7 +12,8 @@ import pytest
 import env_oracle_ref as eo
 import env_ref
 from nee_oracle_ref import welford_stderr
-from oracle.oracle import ARITH_DEVICE, COUNTER_NAMES, ENV_COUNTERS, FACE_FORWARD, LIGHT_DTYPE, ROULETTE_COUNTERS, THROUGHPUT_FORM
+from oracle.oracle import (ARITH_DEVICE, COUNTER_NAMES, ENV_COUNTERS, FACE_FORWARD, LIGHT_DTYPE, ROULETTE_COUNTERS, THROUGHPUT_FORM,
+                           TREE_COUNTERS)
 from test_gpu_nee import _tile_z
 
 SEED = 42
@@ -29,9 +30,18 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+FIRST_38 = ["samples", "queries", "aabb", "sphere", "msphere", "rect", "xform", "medium", "medium_draw", "mat_fetch", "tex_solid",
+            "tex_checker", "tex_noise", "tex_image", "sc_lambert", "sc_metal", "sc_dielectric", "sc_isotropic", "emit", "draws",
+            "sphere_trials", "disk_trials", "sphere_accept", "rect_accept", "env_sample", "env_no_sample", "env_occluded",
+            "env_unoccluded", "env_miss_mis", "env_miss_one", "env_area_sample", "env_emit_scaled", "rr_test", "rr_draw",
+            "rr_end_pending", "rr_end_bare", "rr_floor_survive", "rr_zero"]
+
+
 def test_counter_indices_are_kept():
     assert COUNTER_NAMES.index("rect_accept") == 23 and COUNTER_NAMES[19] == "draws" and COUNTER_NAMES[0] == "samples"
-    assert COUNTER_NAMES[24:] == ENV_COUNTERS + ROULETTE_COUNTERS and len(set(COUNTER_NAMES)) == 38
+    assert COUNTER_NAMES[24:38] == ENV_COUNTERS + ROULETTE_COUNTERS and len(set(COUNTER_NAMES[:38])) == 38
+    assert COUNTER_NAMES[:38] == FIRST_38  # the 38 indices from before the light tree keep their names ...
+    assert COUNTER_NAMES[38:] == TREE_COUNTERS and len(set(COUNTER_NAMES)) == len(COUNTER_NAMES)  # ... and the tail is the tree's
 
 
 # ---- the map functions against numpy ----------------------------------------------------------------------------------------

@@ -145,7 +145,8 @@ def _footprints(orc, cam, n):
     return pts
 
 
-def _converges(orc, cam, world, f_of, le, albedo, ns):
+def _converges(orc, cam, world, f_of, le, albedo, ns, n_lights=1, tree=False):
+    """tree=True: the table's lights are selected through the light tree over them (include/rtmi_light_tree.h)"""
     pts = _footprints(orc, cam, NK)
     want, bound = np.zeros((NK, NK)), np.zeros((NK, NK))
     for r in range(NK):
@@ -154,9 +155,15 @@ def _converges(orc, cam, world, f_of, le, albedo, ns):
             want[r, c] = albedo * le * vals[0][0]
             bound[r, c] = albedo * le * (max(v[0] for v in vals) - min(v[0] for v in vals) + vals[0][1])
     em = orc.emitters(world)
-    assert int(em["eligible"].sum()) == 1
-    lights = light_table(em, [int(np.flatnonzero(em["eligible"])[0])])
-    out = orc.render_nee(cam, world, lights, NK, NK, ns, samples=True)
+    idx = np.flatnonzero(em["eligible"])
+    assert len(idx) == n_lights
+    lights = light_table(em, idx.tolist())
+    kw = {}
+    if tree:
+        from light_tree_oracle_ref import emitter_tree
+
+        kw["tree"] = emitter_tree(em[idx])
+    out = orc.render_nee(cam, world, lights, NK, NK, ns, samples=True, **kw)
     got = out["mean"][..., 0]
     se = welford_stderr(out["samples"])[..., 0].astype(np.float64)
     assert np.all(se > 0)
