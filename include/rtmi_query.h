@@ -69,7 +69,29 @@ int rtmi_scene_attach_flips(rtmi_scene *scene, const uint32_t *prim_gaps, uint32
 /* Blocking, host pointers.  time: n floats, or NULL for time 0.  kernel_ms: optional, the kernel's time by HIP events.
  * n == 0 is RTMI_OK and launches nothing.  RTMI_ERR_INVALID, with the entry's name in rtmi_last_error(), for a NULL
  * scene, params, rays or output and for a ray with a non-finite component (t_max may be +inf), a zero direction or
- * t_min > t_max; the message names the ray. */
+ * t_min > t_max; the message names the ray.
+ * Everything else is accepted: a direction that is not normalised, scaled by 2^-70 or 2^66, with components that are
+ * exactly +-0, an origin exactly on a surface with t_min = 0, negative t_min.  Such rays return the reference's record bit
+ * for bit (tests/test_gpu_query_edges.py, class A), a NaN slab value at a BVH box (0 * inf: the origin in a box plane,
+ * the direction parallel to it) included.
+ *   In-plane rays.  A ray that starts in the plane of a rect or of a cube face (o_k equal to the plane's constant) with
+ *     an infinite 1 / d_k — d_k = +-0, or a denormal d_k with |d_k| <= 2^-128, whose reciprocal overflows; denormals are
+ *     kept — is accepted by Rect::hit anywhere in that infinite plane, with t = 0 * inf = NaN (rect.rs:46-51), and the
+ *     NaN then fails every later comparison.  Such a hit is returned as it is: t, u, v and p are
+ *     NaN, the normal and the indices are the rect's.  In a scene of plain lists the record is the reference's, NaN for
+ *     NaN.  Below a BVH the hit flag is the reference's, and occluded equals it; which accepted leaf is returned can
+ *     differ: every leaf the reference reaches is tested, against the query's own interval, and the accepted leaves are
+ *     folded in sequence from left to right (a later leaf replaces the best so far unless best.t < t, which a NaN on
+ *     either side fails), where BVHNode::hit folds the two results of each node (bvh.rs:75-81).  The two agree whenever no
+ *     accepted t is NaN.  A rect with x0 > x1 or y0 > y1 is left out of the device's scene (nothing but an in-plane ray
+ *     could hit it): rays in its plane return the record of the world without it.
+ *   RTMI_FLAG_FAST_CULL and such rays.  The pruned traversal skips a leaf whose padded box the ray misses, which would
+ *     lose the acceptance above, so a ray for which a component of 1 / d is infinite takes the reference-topology
+ *     traversal whatever the flag says; its result is that of flags = 0, byte for byte, at that traversal's speed
+ *     (axis-aligned picking and shadow rays are such rays).  Not detected: a direction whose reciprocal is finite in
+ *     every component and that a Rotate inside the scene turns into one with a zero or denormal component, by
+ *     cancellation of two rounded products, for a ray that also starts exactly in a face plane of that rotated frame;
+ *     under RTMI_FLAG_FAST_CULL it can miss the NaN acceptance that flags = 0 returns. */
 int rtmi_trace(rtmi_scene *scene, const rtmi_query_params *params, const rtmi_ray *rays, const float *time,
                rtmi_hit *hits_out, double *kernel_ms);
 int rtmi_occluded(rtmi_scene *scene, const rtmi_query_params *params, const rtmi_ray *rays, const float *time,

@@ -10,9 +10,10 @@
 // would share.  Traversal stacks: the per-lane LDS columns of the per-lane render kernel (rtmi_kernel_perlane.inc),
 // 12 KB per wavefront with the entry distances of the pruned walk, 6 KB without.
 //
-// trace: the world scan is rtmi_path_scan.inc, the text the per-lane render kernel traces its path rays with, under the
-// ray's own (t_min, t_max), time and Philox key.  occluded: world_any (rtmi_query.hpp).  Instantiated for FAST x {trace,
-// occluded}; no profiling, signature or cooperative variant.
+// trace: world_closest (rtmi_query.hpp), the world scan of rtmi_path_scan.inc, the text the per-lane render kernel traces
+// its path rays with, under the ray's own (t_min, t_max), time and Philox key.  occluded: world_any (rtmi_query.hpp).
+// Instantiated for FAST x {trace, occluded}; no profiling, signature or cooperative variant.  In the FAST kernels a ray
+// with an infinite component of 1 / d takes the reference-topology traversal (query_ray_pruned, rtmi_query.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -27,8 +28,6 @@ static_assert(sizeof(rtmi_ray) == 32 && sizeof(rtmi_hit) == 48 && sizeof(rtmi_qu
 
 template <bool FAST, bool ANY>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_query_kernel(DevScene sc, QueryBatch B) {
-    constexpr bool PROF = false;
-    unsigned long long *prof = nullptr;
     // per wave: [0] node refs, [1] entry distances (FAST only); entry-major so lanes never bank-conflict
     __shared__ uint32_t lds_stack[WAVES_PER_BLOCK][FAST ? 2 : 1][RTMI_MAX_BVH_DEPTH][64];
     const int lane = threadIdx.x & 63;
@@ -49,19 +48,18 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_query_kernel(DevSce
         const uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
         RngReg g;
         rng_init(g, 0, 0);
+        // an infinite component of 1 / d (d_k = +-0 or denormal): the reference-topology traversal whatever the flag says
+        const bool pruned = FAST && query_ray_pruned(pa);
         if constexpr (ANY) {
-            B.occluded[i] = world_any<FAST>(sc, pa, t_min, t_max, stack, g, k0, k1) ? (uint8_t)1 : (uint8_t)0;
+            const bool any = pruned ? world_any<true>(sc, pa, t_min, t_max, stack, g, k0, k1)
+                                    : world_any<false>(sc, pa, t_min, t_max, stack, g, k0, k1);
+            B.occluded[i] = any ? (uint8_t)1 : (uint8_t)0;
         } else {
             float closest;
             int best_item, best_pf;
             bool best_medium;
-            {
-#define RTMI_SCAN_T_MIN t_min
-#define RTMI_SCAN_T_MAX t_max
-#include "rtmi_path_scan.inc"
-#undef RTMI_SCAN_T_MIN
-#undef RTMI_SCAN_T_MAX
-            }
+            if (pruned) world_closest<true>(sc, pa, t_min, t_max, stack, g, k0, k1, closest, best_item, best_pf, best_medium);
+            else world_closest<false>(sc, pa, t_min, t_max, stack, g, k0, k1, closest, best_item, best_pf, best_medium);
             F3 hp = f3(0, 0, 0), hn = f3(0, 0, 0);
             float ht = __builtin_inff(), hu = 0.0f, hv = 0.0f;
             int prim = -1, material = -1;

@@ -102,6 +102,39 @@ __device__ __forceinline__ void query_record(const DevScene &sc, const uint32_t 
     if (((PM.flags ^ iflags) & 1u) != 0u) hn = -hn;
 }
 
+// Which traversal a query ray takes under RTMI_FLAG_FAST_CULL.  The pruned walk (bvh_query<true>, rtmi_bvh.hpp) skips a
+// leaf whose padded box the ray misses, because no hit of the primitive lies outside that box.  One acceptance does:
+// Rect::hit of a ray in the rect's plane computes t = (k - o_k) * (1 / d_k) = 0 * inf = NaN when 1 / d_k is infinite, and
+// every comparison that would reject it is false (rect.rs:46-51), wherever the ray is in that infinite plane.  The
+// reference reaches the leaf through its parent's box and accepts; the pruned walk would not.  A render never traces such
+// a ray, a query can (the caller's shadow ray straight up, an occlusion test along a wall).  1 / d_k is infinite for
+// d_k = +-0 and for every denormal |d_k| <= 2^-128, where the division overflows (denormals are kept, and
+// rtmi_validate_rays accepts them), so the test is on the quotient itself, the value ray_derive hands to Rect::hit: a ray
+// with an infinite component of 1 / d takes the reference-topology traversal whatever the flag says, and trace and
+// occluded then evaluate the same predicate, the reference's.  (A rotation inside the scene can still produce such a
+// component from a direction that has none, by exact cancellation of two rounded products; such a ray must also start
+// exactly in a face plane of that rotated frame.  It is not detected here: include/rtmi_query.h.)
+__device__ __forceinline__ bool query_ray_pruned(const QueryRay &pa) {
+    const float ix = 1.0f / pa.rd.x, iy = 1.0f / pa.rd.y, iz = 1.0f / pa.rd.z; // aabb.rs:33, as ray_derive
+    const float m = fmaxf(fmaxf(__builtin_fabsf(ix), __builtin_fabsf(iy)), __builtin_fabsf(iz));
+    return m < __builtin_inff();
+}
+
+// world.hit(ray, t_min, t_max) of a query ray: the scan of rtmi_path_scan.inc, the text the per-lane render kernel traces
+// its path rays with, under the ray's own interval, time and Philox key.
+template <bool FAST, typename RngT>
+__device__ __forceinline__ void world_closest(const DevScene &sc, const QueryRay &pa, float t_min, float t_max, uint32_t *stack, RngT &g,
+                                              uint32_t k0, uint32_t k1, float &closest, int &best_item, int &best_pf,
+                                              bool &best_medium) {
+    constexpr bool PROF = false;
+    unsigned long long *prof = nullptr;
+#define RTMI_SCAN_T_MIN t_min
+#define RTMI_SCAN_T_MAX t_max
+#include "rtmi_path_scan.inc"
+#undef RTMI_SCAN_T_MIN
+#undef RTMI_SCAN_T_MAX
+}
+
 // BVHNode::hit (bvh.rs:70-89) as a predicate: does any leaf the reference reaches accept a hit in (t_min, t_max)?  The
 // reference tests every box and every leaf against the query's own interval, so which leaves are reached does not
 // depend on the order of the visit or on what other leaves returned: the walk needs no ordering and no entry

@@ -658,7 +658,9 @@ class Scene:
         keyed seed + first_ray + i.  origins, directions: float32 [n, 3]; times: [n] or None (time 0); t_min, t_max: a
         scalar or [n] each (t_max = inf: the render's).  Returns dict(hit bool [n], t, u, v [n], p, normal [n, 3], item,
         prim, material int32 [n]); a miss has t = +inf, the indices -1 and the rest 0.  flags: RTMI_FLAG_FAST_CULL or 0
-        (the reference-topology traversal), same results.
+        (the reference-topology traversal), same results.  A ray that starts in the plane of a rect or a cube face
+        with that component of the direction +-0 (or so small that its reciprocal overflows) is accepted there with t = NaN, as in the reference (t, u, v, p are NaN); below a BVH the leaf
+        that is returned for such a ray can differ from the reference's (include/rtmi_query.h, in-plane rays).
         With torch tensors on the scene's device the call is enqueued on torch's current stream (rtmi_trace_device) and
         returns torch tensors on that device: no host copy is made.  A scene resident on a device list raises Unsupported."""
         return self._query(False, origins, directions, times, t_min, t_max, seed, first_ray, flags)
@@ -666,7 +668,8 @@ class Scene:
     def occluded(self, origins, directions, times=None, t_min=0.001, t_max=float("inf"), seed=0, first_ray=0,
                  flags=abi.RTMI_FLAG_FAST_CULL):
         """bool [n]: whether trace() of the same arguments finds a hit — the same predicate with the same draws, by a
-        scan that stops at the first accepted hit (rtmi_occluded, include/rtmi_query.h)."""
+        scan that stops at the first accepted hit (rtmi_occluded, include/rtmi_query.h).  An in-plane ray that a rect
+        accepts with t = NaN is occluded, as trace() reports it hit."""
         return self._query(True, origins, directions, times, t_min, t_max, seed, first_ray, flags)
 
     def _query(self, any_hit, origins, directions, times, t_min, t_max, seed, first_ray, flags):

@@ -6,12 +6,13 @@ import numpy as np
 import scenes_extra
 import scenes_random
 from oracle.oracle import ARITH_DEVICE
-from raytracing_rust_amd import scenes
+from raytracing_rust_amd import abi, scenes
 
 SEED = 1000  # ray i of a set is traced with the oracle's seed SEED + i
 T_MIN = 0.001
 INF = float("inf")
 NO_HIT = {"hit": False}
+FC = abi.RTMI_FLAG_FAST_CULL
 
 
 def fan(rng, look_from, look_at, n):
@@ -92,3 +93,78 @@ def random_fan_camera(host, seed):
     centre = (np.array(list(c.lower_left_corner), np.float64) + 0.5 * np.array(list(c.horizontal), np.float64) +
               0.5 * np.array(list(c.vertical), np.float64))
     return org, centre
+
+
+# ---- the device's records against the oracle's (tests/test_gpu_query.py, tests/test_gpu_query_edges.py) ----------------------
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same(a, b):
+    return sorted(a) == sorted(b) and all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a if k != "kernel_ms")
+
+
+def interval(s):
+    """t_min, t_max of a ray set: its own per-ray arrays, or the sets' common (T_MIN, +inf)"""
+    return s.get("t_min", T_MIN), s.get("t_max", INF)
+
+
+def trace(sc, s, flags, **kw):
+    t_min, t_max = interval(s)
+    return sc.trace(s["o"], s["d"], s["times"], t_min=t_min, t_max=t_max, seed=SEED, flags=flags, **kw)
+
+
+def tree_prims(a, root):
+    out, todo = set(), [root]
+    while todo:
+        n = a["nodes"][todo.pop()]
+        for ch in (n.left, n.right):
+            if ch >= 0:
+                todo.append(ch)
+            else:
+                out.add(ch & 0x0FFFFFFF)
+    return out
+
+
+def check_indices(a, got, what):
+    """test 5: item, prim and material of every hit"""
+    trees = {}
+    for i in np.flatnonzero(got["hit"]):
+        item, prim, mat = int(got["item"][i]), int(got["prim"][i]), int(got["material"][i])
+        assert 0 <= item < len(a["items"]), (what, i)
+        it = a["items"][item]
+        if prim < 0:  # a medium event
+            assert prim == -1 and (it.flags & 2) and mat == it.medium_material, (what, i, item, prim, mat)
+            continue
+        if it.kind == 1:  # RTMI_ITEM_BVH
+            if item not in trees:
+                trees[item] = tree_prims(a, it.first)
+            assert prim in trees[item], (what, i, item, prim)
+        else:
+            assert it.first <= prim < it.first + it.count, (what, i, item, prim)
+        assert a["prim_meta"][prim].material == mat, (what, i, prim, mat)
+
+
+def check_set(sc, a, s, what):
+    """tests 1, 3 (first half) and 5 on one ray set: both flag settings against the oracle's records"""
+    ref = s["ref"]
+    exact, fast = trace(sc, s, 0), trace(sc, s, FC)
+    assert same(exact, fast), what
+    got = fast
+    assert np.array_equal(got["hit"], ref["hit"]), (what, np.flatnonzero(got["hit"] != ref["hit"])[:8])
+    for k in ("t", "u", "v", "p"):
+        bad = np.flatnonzero((bits(got[k]) != bits(ref[k])).reshape(len(ref["hit"]), -1).any(axis=1))
+        assert bad.size == 0, (what, k, bad[:8], got[k][bad[:2]], ref[k][bad[:2]])
+    kinds = np.array([m.kind for m in a["materials"]] + [-1])
+    assert np.array_equal(kinds[got["material"]], ref["mat_kind"]), what
+    miss = ~got["hit"]
+    assert np.all(got["item"][miss] == -1) and np.all(got["prim"][miss] == -1) and np.all(got["material"][miss] == -1), what
+    assert np.all(np.isposinf(got["t"][miss])) and not np.any(got["p"][miss]) and not np.any(got["normal"][miss]), what
+    t_min, t_max = interval(s)
+    for flags in (0, FC):
+        occ = sc.occluded(s["o"], s["d"], s["times"], t_min=t_min, t_max=t_max, seed=SEED, flags=flags)
+        assert occ.dtype == bool and np.array_equal(occ, got["hit"]), (what, flags, np.flatnonzero(occ != got["hit"])[:8])
+    check_indices(a, got, what)
+    bad = np.flatnonzero((bits(got["normal"]) != bits(ref["normal"])).any(axis=1))  # (-0 against +0 counts)
+    assert bad.size == 0, (what, "normal", bad.size, bad[:8], got["normal"][bad[:2]], ref["normal"][bad[:2]])
+    return got
