@@ -278,7 +278,8 @@ typedef struct {
                                 * level after level, which the default kernel (stack continued in global memory) renders.
                                 * An independent implementation for the parity tests, 23 % slower than the default. */
 /* Diagnostic knobs in the upper flag bits (results never depend on them): bits 8..10 = wavefronts per SIMD the
- * cooperative kernel is compiled for (3 or 5; default 4); bit 11 = a 256-entry LDS part of the traversal stack,
+ * cooperative kernel is compiled for (3 or 5; default 4; the value 4 asks for the general 4-wave instantiation where the
+ * one-tree one would run, rtmi_stats_instantiation below); bit 11 = a 256-entry LDS part of the traversal stack,
  * so that it spills to global memory all the time (tests/test_gpu_parity.py). */
 #define RTMI_FLAG_SKY 32u      /* opt-in extension, off by default: a ray that misses the world returns the gradient
                                 * the reference keeps commented out at src/color.rs:18-20 instead of black (:21) */
@@ -346,6 +347,18 @@ typedef struct {
     uint32_t kernel;   /* which render kernel ran (diagnostics; results never depend on it): RTMI_KERNEL_* */
 } rtmi_stats;
 enum { RTMI_KERNEL_PERLANE = 0, RTMI_KERNEL_WAVE_COOP = 1, RTMI_KERNEL_ASYNC = 2, RTMI_KERNEL_BLOCK_COOP = 3 };
+/* Diagnostics (results never depend on it): which instantiation of the wave-cooperative kernel a plain render (rtmi_render,
+ * rtmi_render_device with stats) launched.  RTMI_INST_COOP_ONE_TREE is the default kernel compiled for scenes whose every
+ * BVH item carries an alternative tree and whose every ConstantMedium is bounded by one static sphere, rendered through
+ * those trees (no RTMI_FLAG_REF_TREE, RTMI_FLAG_PATH_SIG or RTMI_FLAG_PROFILE, no waves-per-SIMD knob; knob value 4 of flag
+ * bits 8..10 asks for the general instantiation); RTMI_INST_COOP_GENERAL serves every other cooperative render,
+ * RTMI_INST_NONE means that another kernel ran.  rtmi_stats.kernel holds RTMI_KERNEL_* alone, as ever, unless the call sets
+ * the diagnostic knob RTMI_KNOB_REPORT_INST (flag bit 19) — then the instantiation rides in its bits 8..15, and the two
+ * accessors below take the word apart.  The knob is read by the plain render entries only. */
+enum { RTMI_INST_NONE = 0, RTMI_INST_COOP_GENERAL = 1, RTMI_INST_COOP_ONE_TREE = 2 };
+#define RTMI_KNOB_REPORT_INST 524288u
+static inline uint32_t rtmi_stats_kernel(const rtmi_stats *st) { return st->kernel & 255u; }
+static inline uint32_t rtmi_stats_instantiation(const rtmi_stats *st) { return (st->kernel >> 8) & 255u; }
 
 typedef struct rtmi_scene rtmi_scene;
 

@@ -133,6 +133,17 @@ class Stats(C.Structure):
                 ("tiles", C.c_uint32), ("chunks", C.c_uint32), ("blocks", C.c_uint32), ("kernel", C.c_uint32)]
 
 
+def stats_kernel(st):
+    """rtmi_stats_kernel (include/rtmi.h): RTMI_KERNEL_* of a Stats, whether or not the call set the report knob."""
+    return st.kernel & 255
+
+
+def stats_instantiation(st):
+    """rtmi_stats_instantiation (include/rtmi.h): which instantiation of the wave-cooperative kernel ran — 0 none, 1 the
+    general one, 2 the one-tree one — of a Stats whose call set the diagnostic knob, flag bit 19; 0 without the knob."""
+    return (st.kernel >> 8) & 255
+
+
 class SceneF64(C.Structure):
     """rtmi_scene_f64 (include/rtmi_f64.h): the double planes of the f64 render mode."""
     _fields_ = [("n_items", C.c_uint32), ("n_prims", C.c_uint32), ("n_nodes", C.c_uint32), ("n_xforms", C.c_uint32),

@@ -17,9 +17,10 @@ LIB_DIR = os.environ.get("RTMI_LIB_DIR") or os.path.join(_PKG, "lib")
 INCLUDE = os.path.join(_ROOT, "include")
 
 # The translation units of librtmi.so, compiled side by side, and whether each takes the iterative-maxocc scheduler
-# (build_rtmi): the headline kernels and the C ABI (rtmi_device), the lean instantiations (rtmi_lean), the two alternative
-# kernels kept for the parity tests (rtmi_alt), then one unit per render mode, named after its header in include/.
-_RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_alt.hip", True), ("rtmi_f64.hip", False),
+# (build_rtmi): the headline kernels and the C ABI (rtmi_device), the lean instantiations (rtmi_lean), the one-tree
+# instantiation of the headline kernel (rtmi_onetree), the two alternative kernels kept for the parity tests (rtmi_alt),
+# then one unit per render mode, named after its header in include/.
+_RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_onetree.hip", True), ("rtmi_alt.hip", True), ("rtmi_f64.hip", False),
                ("rtmi_adaptive.hip", True), ("rtmi_features.hip", True), ("rtmi_denoise.hip", False), ("rtmi_nee.hip", True),
                ("rtmi_env.hip", True), ("rtmi_adaptive_nee.hip", True), ("rtmi_roulette.hip", True),
                ("rtmi_light_coop.hip", True), ("rtmi_roulette_coop.hip", True), ("rtmi_session.hip", False),

@@ -22,7 +22,7 @@
 template <bool EXT>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void rtmi_adaptive_coop(DevScene sc, DevCamera cam, DevParams P,
                                                                              const uint32_t *tiles) {
-    constexpr bool SIG = false, PROF = false, TILE_LIST = true, NEE = false, ENV = false;
+    constexpr bool SIG = false, PROF = false, TILE_LIST = true, NEE = false, ENV = false, ONE_TREE = false;
     constexpr int WPS = 4, INSTL = 0;
     (void)WPS;
     const DevLights nl{};

@@ -342,7 +342,9 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
 }
 
 // geometry of one item for the whole wavefront: every lane calls it; `active` lanes own a query
-template <bool PROF, bool EXT, bool W4, bool INST>
+// ONE: the caller knows that every BVH item of the scene carries an alternative tree and that the call walks it
+// (rtmi_onetree.hip): the walk of the reference-topology tree is not compiled, `use_alt` is not read
+template <bool PROF, bool EXT, bool W4, bool INST, bool ONE = false>
 __device__ __forceinline__ bool geom_query_coop(const DevScene &sc, const rtmi_item &I, bool use_alt, bool active, const RayF &r,
                                                 float time, float q_min, float q_max, const CoopWork &cw,
                                                 float &t_out, int &pf_out, bool &overflow, unsigned long long *prof,
@@ -352,9 +354,14 @@ __device__ __forceinline__ bool geom_query_coop(const DevScene &sc, const rtmi_i
         const bool enter = active && aabb_hit(I.root_min[0], I.root_min[1], I.root_min[2], I.root_max[0], I.root_max[1],
                                               I.root_max[2], r, q_min, q_max);
         bool have = false;
+        static_assert(!ONE || (EXT && W4), "the one-tree form walks the gated 4-wide tree");
+        if constexpr (ONE) {
+            coop_bvh_query<PROF, EXT, W4, INST>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+        } else {
         const bool alt = EXT && W4 && use_alt && I.alt_first >= 0; // wave-uniform
         if (alt) coop_bvh_query<PROF, EXT, W4, INST>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
         else coop_bvh_query<PROF, EXT, false, INST>(sc, I.first, false, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+        }
         return have;
     }
     // HittableList::hit — hittable.rs:37-47

@@ -92,6 +92,9 @@ struct RTMI_HIDDEN rtmi_scene {
     int slots = 0;                  // CUs x 16: resident wavefronts the render kernels are launched with
     bool has_alt = false;           // some BVH item carries an alternative tree
     bool all_alt = false;           // every BVH item does (and there is one): the workgroup-cooperative kernel can run
+    bool all_sphere_media = true;   // every medium item is bounded by one static sphere (RTMI_ITEMFLAG_DEV_MEDIUM_SPHERE; also
+                                    // true without media): with all_alt what the one-tree instantiation asks of a scene
+    uint32_t last_inst = 0;         // RTMI_INST_* of the last plain render enqueued on this handle (rtmi_stats_instantiation)
     bool needs_insd = false;        // DEFERRED items, list scans, nested media: the INSTL = 2 instantiations (rtmi_kernels.hpp)
     bool has_deferred = false;      // media that were children of a BVHNode (RTMI_ITEMFLAG_DEFERRED): the asynchronous
                                     // state-machine kernel does not carry them, RTMI_FLAG_ASYNC then runs the per-lane kernel
@@ -463,6 +466,7 @@ extern "C" int rtmi_scene_create(const rtmi_scene_desc *d, int device, rtmi_scen
                 memcpy(it.root_min, d->prim_a + (size_t)it.first * 4, 3 * sizeof(float));
                 it.root_max[0] = d->prim_a[(size_t)it.first * 4 + 3];
             }
+            if ((it.flags & RTMI_ITEMFLAG_MEDIUM) && !(it.flags & RTMI_ITEMFLAG_DEV_MEDIUM_SPHERE)) s->all_sphere_media = false;
         }
         std::vector<DevItem> ditems(d->n_items);
         for (uint32_t i = 0; i < d->n_items; i++) {
@@ -846,6 +850,8 @@ static void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *s
     }
     stats->samples = pix * p->ns;
     stats->tiles = nl; stats->chunks = counts.chunks; stats->blocks = counts.blocks; stats->kernel = s->last_kernel;
+    // diagnostic knob (rtmi.h): the instantiation of the cooperative kernel rides in bits 8..15, for rtmi_stats_instantiation
+    if (p->flags & RTMI_KNOB_REPORT_INST) stats->kernel |= s->last_inst << 8;
 }
 // the same from the scene's events: ev[0] start, ev[1] before the last resolve, ev[2] end (all completed)
 static int fill_stats_from_events(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, PassCounts counts = {}) {
@@ -1021,6 +1027,14 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     // (test knob bit 11: a stack so small that rounds are throttled all the time — room for 64 visits when it is full)
     if (bcoop) P.coop_cap = (p->flags & (1u << 11)) ? 3u * RTMI_BLK_THREADS + 64u : RTMI_BLK_CAP;
     s->last_kernel = bcoop ? RTMI_KERNEL_BLOCK_COOP : coop ? RTMI_KERNEL_WAVE_COOP : async ? RTMI_KERNEL_ASYNC : RTMI_KERNEL_PERLANE;
+    // The one-tree instantiation of the cooperative kernel (rtmi_onetree.hip): the default one's shape for the scenes that
+    // execute a single one of its four traversal copies — every tree gated and walked through its alternative tree, every
+    // medium bounded by a static sphere.  Properties of the scene and of the call, never of the data a kernel meets: the
+    // general instantiation renders everything else.  The small-pool knob (bit 11) reaches it (it keeps the spill path);
+    // knob value 4 of the waves-per-SIMD bits asks for the general instantiation (tests, A/B inside one build).
+    const bool one_tree = coop && !bcoop && ext && !inst && !sigf && !prof && wps_req == 0u && P.use_alt != 0u &&
+                          !(p->flags & RTMI_FLAG_REF_TREE) && s->all_alt && s->all_sphere_media;
+    s->last_inst = !coop || bcoop ? RTMI_INST_NONE : one_tree ? RTMI_INST_COOP_ONE_TREE : RTMI_INST_COOP_GENERAL;
     const bool insd = inst && (s->needs_insd || ext || sigf); // the level-2 instantiations (below) park their group state in LDS
     const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, insd}.words() * sizeof(uint32_t);
     const uint32_t ntex = P.ntiles_local * 64u;
@@ -1058,6 +1072,7 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
         else if (sigf) RTMI_LAUNCH_COOP(true, false, 4, true, 0);
         else if (wps == 3) RTMI_LAUNCH_COOP(false, false, 3, true, 0);
         else if (wps == 5) RTMI_LAUNCH_COOP(false, false, 5, true, 0);
+        else if (one_tree) HIP_TRY(rtmi_launch_lds(&rtmi_render_coop<false, false, 4, true, 0, true>, grid, block, coop_lds, stream, s->dev, C, P));
         else if (ext) RTMI_LAUNCH_COOP(false, false, 4, true, 0);
         else RTMI_LAUNCH_COOP(false, false, 4, false, 0);
     } else if (!async) {

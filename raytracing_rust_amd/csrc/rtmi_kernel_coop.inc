@@ -1,7 +1,7 @@
 // rtmi_kernel_coop.inc — body of the wave-cooperative render kernel (rtmi_kernels.hpp), included INSIDE the kernels that
 // run it: rtmi_render_coop (TILE_LIST = false), the adaptive-sampling kernel rtmi_adaptive_coop (rtmi_adaptive.hip,
 // TILE_LIST = true) and the lighting kernels of rtmi_light_coop.hip (NEE / ENV, include/rtmi_light_coop.h).  The including
-// function provides sc, cam, P, SIG, PROF, EXT, INSTL, TILE_LIST, NEE, ENV, `tiles`, `nl` and `ev`; see
+// function provides sc, cam, P, SIG, PROF, EXT, INSTL, ONE_TREE, TILE_LIST, NEE, ENV, `tiles`, `nl` and `ev`; see
 // rtmi_kernel_perlane.inc for why this is a textual body, for what NEE and ENV mean and for the RR switch (RTMI_PATH_RR;
 // rtmi_roulette_coop_kernel, rtmi_roulette_coop.hip; include/rtmi_roulette_coop.h).  The lane-level path logic is the
 // rtmi_path_*.inc fragments', shared with that body; this one provides them the wave's LDS (CoopLds; its pool is phase B's
@@ -39,9 +39,13 @@
     // The copy through an asm statement is a live range the coalescer cannot fold back into the tuple (r04: final_scene
     // +1.5 %, cornell_box +4 % together with the one-pointer primitive records; giving every scene POINTER its own pair
     // the same way lost 2 % / 7 % — profiles/r04_experiments/own_sgprs_ab.log: the allocator is not to be out-guessed twice)
+    // ONE_TREE (rtmi_onetree.hip): the host has checked that the call walks alternative trees, that every BVH item has
+    // one and that every medium's boundary is a static sphere — use_alt is a constant, and neither the walk of the
+    // reference-topology tree nor the boundary queries of a general medium are compiled (DESIGN.md §37)
     float t_min;
-    uint32_t n_items, use_alt_w;
-    asm volatile("s_mov_b32 %0, %3\n s_mov_b32 %1, %4\n s_mov_b32 %2, %5" : "=&s"(t_min), "=&s"(n_items), "=&s"(use_alt_w) : "s"(P.t_min), "s"(sc.n_items), "s"(P.use_alt));
+    uint32_t n_items, use_alt_w = 1u;
+    if constexpr (ONE_TREE) asm volatile("s_mov_b32 %0, %2\n s_mov_b32 %1, %3" : "=&s"(t_min), "=&s"(n_items) : "s"(P.t_min), "s"(sc.n_items));
+    else asm volatile("s_mov_b32 %0, %3\n s_mov_b32 %1, %4\n s_mov_b32 %2, %5" : "=&s"(t_min), "=&s"(n_items), "=&s"(use_alt_w) : "s"(P.t_min), "s"(sc.n_items), "s"(P.use_alt));
     const bool use_alt = use_alt_w != 0u;
 
     uint32_t oidx = 0u, ltile = 0u; // slot of this lane's path in the per-sample buffer; its local tile (SIG only)
@@ -110,7 +114,7 @@
                         reach = need && deferred_gate(sc, I, W, t_min, t0_saved);
                         qmax = scan ? __uint_as_float(park[64]) : t0_saved;
                     }
-                    if (geom_query_coop<PROF, EXT, EXT, INST>(sc, I, use_alt, reach, R, pa.rtime, t_min, qmax, cw, t, pf, overflow, prof, slot)) {
+                    if (geom_query_coop<PROF, EXT, EXT, INST, ONE_TREE>(sc, I, use_alt, reach, R, pa.rtime, t_min, qmax, cw, t, pf, overflow, prof, slot)) {
                         if (scan) {
                             park[64] = __float_as_uint(t); park[128] = it; park[192] = (uint32_t)pf;
                         } else if (!dfi || deferred_bvh_wins(I.count, t, closest, best_item, best_pf, grp_first, grp_tree)) {
@@ -123,13 +127,13 @@
                     float t1 = 0.0f, t2 = 0.0f, tm;
                     int pf;
                     bool h1, h2;
-                    if (I.flags & RTMI_ITEMFLAG_DEV_MEDIUM_SPHERE) {
+                    if (ONE_TREE || (I.flags & RTMI_ITEMFLAG_DEV_MEDIUM_SPHERE)) {
                         // boundary = one static sphere (wave-uniform test; the sphere travels in the item record): both
                         // boundary queries are roots of the same quadratic, evaluated once (same expressions as two
                         // Sphere::hit calls: same bits)
                         h1 = false; h2 = false;
                         if (need) sphere_two_queries(R, make_float4(I.root_min[0], I.root_min[1], I.root_min[2], I.root_max[0]), h1, t1, h2, t2);
-                    } else {
+                    } else if constexpr (!ONE_TREE) {
                         // INSD: a medium that was a child of a BVHNode (rtmi.h, DEFERRED) is reached through its parent's box
                         const bool dfr = INSD && (I.flags & RTMI_ITEMFLAG_DEFERRED) != 0u; // wave-uniform
                         bool reach = need;

@@ -34,7 +34,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void rtmi_render_kernel(DevSc
 // INSTL: 0 = the instantiations of the common scenes: no transform code in their loops; 1 = scenes with instanced primitives or
 // media inside transforms (rtmi.h); 2 = also DEFERRED items, list scans, nested media (children of a BVHNode that are not
 // primitives).  Forced on the BASELINE scenes level 2 costs 10-14 % (profiles/r04_experiments/force_inst_ab.log), hence two levels.
-template <bool SIG, bool PROF, int WPS, bool EXT, int INSTL>
+// ONE_TREE: the instantiation of the scenes whose every tree is gated and whose every medium is bounded by a static sphere
+// (final_scene, random_spheres): one inlined copy of the traversal instead of four (rtmi_kernel_coop.inc).
+template <bool SIG, bool PROF, int WPS, bool EXT, int INSTL, bool ONE_TREE = false>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, WPS) void rtmi_render_coop(DevScene sc, DevCamera cam, DevParams P) {
     constexpr bool TILE_LIST = false, NEE = false, ENV = false;
     const DevLights nl{};
@@ -43,6 +45,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, WPS) void rtmi_render_coop(De
 #include "rtmi_kernel_coop.inc"
 }
 
+#ifndef RTMI_ONE_TREE_TU
+// the one-tree instantiation is compiled in rtmi_onetree.hip: a unit of its own, so that its scheduler strategy is its own
+extern template __global__ void rtmi_render_coop<false, false, 4, true, 0, true>(DevScene, DevCamera, DevParams);
+#endif
 #ifndef RTMI_LEAN_TU
 // the lean instantiations (EXT = false) are compiled in rtmi_lean.hip, with another machine-scheduler strategy
 extern template __global__ void rtmi_render_coop<false, false, 4, false, 0>(DevScene, DevCamera, DevParams);

@@ -25,7 +25,7 @@
 template <bool TILE_LIST, bool SIG, bool EXT, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, RTMI_LIGHT_COOP_WPS) void rtmi_light_coop_kernel(
     DevScene sc, DevCamera cam, DevParams P, const uint32_t *tiles, DevLights nl, DevEnv ev) {
-    constexpr bool PROF = false;
+    constexpr bool PROF = false, ONE_TREE = false;
     constexpr int INSTL = 0;
 #include "rtmi_kernel_coop.inc"
 }

@@ -30,7 +30,7 @@
 template <bool EXT, bool NEE, bool ENV>
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, rtmi_roulette_coop_wps(NEE, ENV)) void rtmi_roulette_coop_kernel(
     DevScene sc, DevCamera cam, DevParams P, const uint32_t *tiles, DevLights nl, DevEnv ev, DevRoulette rr) {
-    constexpr bool SIG = false, PROF = false, TILE_LIST = true;
+    constexpr bool SIG = false, PROF = false, TILE_LIST = true, ONE_TREE = false;
     constexpr int INSTL = 0;
 #include "rtmi_kernel_coop.inc"
 }
