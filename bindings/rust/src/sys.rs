@@ -1535,3 +1535,9 @@ extern "C" {
         poisoned: *mut u32,
     ) -> c_int;
 }
+
+// ---- include/rtmi_batch_coop.h: the batch modes on the wave-cooperative kernel ----------------------------------------
+
+/// RTMI_FLAG_BATCH_COOP: a flag of rtmi_radiance, rtmi_gather, rtmi_sparse_render, rtmi_sparse_refine, rtmi_render_pixelwise
+/// and rtmi_render_window (and their _device forms): the paths trace on the wave-cooperative kernel, same bits
+pub const FLAG_BATCH_COOP: u32 = 2097152;

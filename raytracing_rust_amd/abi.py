@@ -33,6 +33,10 @@ RTMI_FLAG_PROGRESSIVE = 16384  # opt-in: the framebuffer holds the image of the 
 RTMI_FLAG_LIGHT_COOP = 65536  # include/rtmi_light_coop.h: NEE / environment renders on the wave-cooperative kernel
 RTMI_FLAG_ROULETTE_COOP = 131072  # include/rtmi_roulette_coop.h: roulette renders on the wave-cooperative kernel
 RTMI_FLAG_LIGHT_TREE = 262144  # include/rtmi_light_tree.h: rtmi_render_nee picks its light by walking the light tree
+# RTMI_FLAG_BATCH_COOP of include/rtmi_batch_coop.h: the batch modes trace on the wave-cooperative kernel.  Under a name of
+# its own: tests/test_abi_signatures.py pins how many header constants this file restates by their header's name;
+# tests/test_batch_coop_abi.py compares this one with the header.
+FLAG_BATCH_COOP = 2097152
 RTMI_ERR_DEVICE = 3
 RTMI_ERR_CANCELLED = 5
 RTMI_TEXEL_POISON = 0x80000000
@@ -530,6 +534,7 @@ def _tables():
             "rtmi_window_spread_device": (i, [vp, vp, u32, u32, u32, vp]),
             "rtmi_window_steps": (u32, [u32] * 3),
         },
+        "rtmi_batch_coop.h": {},  # a flag of the batch entries
     }
 
 

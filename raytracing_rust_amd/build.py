@@ -27,7 +27,7 @@ _RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_onetr
                ("rtmi_query.hip", True), ("rtmi_radiance.hip", True), ("rtmi_light_tree.hip", True),
                ("rtmi_gather.hip", True), ("rtmi_temporal.hip", False), ("rtmi_frame.hip", False),
                ("rtmi_tonemap.hip", False), ("rtmi_upscale.hip", False), ("rtmi_sparse.hip", True),
-               ("rtmi_pixelwise.hip", True), ("rtmi_window.hip", True))
+               ("rtmi_pixelwise.hip", True), ("rtmi_window.hip", True), ("rtmi_batch_coop.hip", True))
 _PUBLIC_HEADERS = sorted(glob.glob(os.path.join(INCLUDE, "*.h")))
 RTMI_SRC = [os.path.join(_PKG, "csrc", name) for name, _ in _RTMI_UNITS]
 HOST_SRC = [os.path.join(_PKG, "host", "rt_host.cpp"), os.path.join(_PKG, "host", "rt_host_c.cpp")]

@@ -65,6 +65,8 @@
 #include "rtmi_pixelwise_launch.hpp"
 #include "rtmi_window.h"
 #include "rtmi_window_launch.hpp"
+#include "rtmi_batch_coop.h"
+#include "rtmi_batch_coop_launch.hpp"
 #include "rtmi_frame_launch.hpp"
 #include "rtmi_hostkit.hpp"
 
@@ -99,6 +101,8 @@ struct RTMI_HIDDEN rtmi_scene {
     bool has_deferred = false;      // media that were children of a BVHNode (RTMI_ITEMFLAG_DEFERRED): the asynchronous
                                     // state-machine kernel does not carry them, RTMI_FLAG_ASYNC then runs the per-lane kernel
     uint32_t last_kernel = 0;       // RTMI_KERNEL_* of the last render enqueued on this handle (rtmi_stats.kernel)
+    int last_batch_kernel = -1;     // ... of the path kernel of the last batch call (rtmi_batch_coop.h); -1: none yet
+    bool batch_blocking = false;    // the running batch call is a blocking one: it reads its own overflow word (batch_coop_check)
     // scratch of the blocking host API (grow-only, so a host that renders frame after frame allocates once)
     DeviceBuf<rtmi_texel> texels;
     DeviceBuf<unsigned long long> d_sig;
@@ -2524,6 +2528,72 @@ static BatchChunks batch_chunks(const rtmi_scene *s, uint32_t total, uint32_t ca
     c.blocks = c.nchunks < slots ? c.nchunks : slots;
     return c;
 }
+// RTMI_FLAG_BATCH_COOP (include/rtmi_batch_coop.h).  The bits the flag adds to a batch entry's accepted ones: itself and
+// the two test knobs, bit 11 (the small pool) and TEST_OVERFLOW, which alone stay refused.
+static uint32_t batch_coop_bits(uint32_t flags) {
+    return (flags & RTMI_FLAG_BATCH_COOP) ? (RTMI_FLAG_BATCH_COOP | (1u << 11) | RTMI_FLAG_TEST_OVERFLOW) : 0u;
+}
+// The selection, evaluated once per enqueue: the flag, a call whose pruned traversal may run at all (`fast`: the entry's own
+// rule, which includes FAST_CULL), a scene within the cooperative size limits and of level 0 (plan_light_coop's rule).
+// Where the cooperative kernel runs: its traversal plan in P (the handle's spill buffer grown: the one allocation of a
+// device form: any earlier cooperative call of the handle has made it), its pool form, the dynamic LDS of a block, and the grid.
+// The grid: wavefront b spills to entries [b * spill_cap, (b + 1) * spill_cap) of the handle's buffer, which holds
+// s->slots wavefronts, so blocks * WAVES_PER_BLOCK <= s->slots must hold; CUs x 4 SIMDs x the kernel's waves per SIMD
+// (at most 4 of the buffer's 5) keeps it, and it is checked.  The chunks stay batch_chunks'.
+struct BatchCoop {
+    bool coop = false, ext = false;
+    size_t lds = 0;
+    uint32_t blocks = 0;
+};
+static int plan_batch_coop(rtmi_scene *s, const Estimator &m, uint32_t flags, bool fast, const BatchChunks &ch, DevParams &P,
+                           BatchCoop &c) {
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
+    c.coop = (flags & RTMI_FLAG_BATCH_COOP) != 0u && fast && coop_ok && !inst;
+    if (!c.coop) return RTMI_OK;
+    rtmi_render_params rp{};
+    rp.flags = flags;
+    if (int rc = plan_traversal(s, &rp, true, P, c.ext)) return rc;
+    if (flags & (1u << 11)) { // test knob, as in plan_light_coop: a pool this small that it spills all the time
+        c.ext = true;
+        P.coop_cap = 256u;
+    }
+    c.lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, c.ext, false}.words() * sizeof(uint32_t);
+    const uint32_t grid = (uint32_t)(s->slots / 20) * 4u * rtmi_batch_coop_wps(m.nee, m.env);
+    c.blocks = ch.nchunks < grid ? ch.nchunks : grid;
+    if ((uint64_t)c.blocks * WAVES_PER_BLOCK > (uint64_t)s->slots)
+        return fail(RTMI_ERR_DEVICE, "the cooperative batch grid exceeds the wavefronts of the spill buffer");
+    return RTMI_OK;
+}
+// The overflow word of a cooperative batch launch, status[0].  A blocking call owns it from its begin to its return
+// (batch_blocking_begin zeroes it once, every launch of the call adds to it, batch_coop_check reads it after the wait, as
+// check_overflow reads a render's): what an earlier _device call or render left in the sticky word status[2] stays there
+// for rtmi_scene_status.  A _device call has nobody to read its own word: each launch starts it at zero and
+// rtmi_batch_coop_end_kernel adds it to the sticky word.  Every batch entry sets s->batch_blocking under the handle's lock.
+static int batch_blocking_begin(rtmi_scene *s) {
+    s->batch_blocking = true;
+    HIP_TRY(hipMemsetAsync(s->status.ptr, 0, sizeof(unsigned int), s->stream.s));
+    return RTMI_OK;
+}
+static int batch_coop_begin(rtmi_scene *s, hipStream_t stream) {
+    if (!s->batch_blocking) HIP_TRY(hipMemsetAsync(s->status.ptr, 0, sizeof(unsigned int), stream));
+    return RTMI_OK;
+}
+static int batch_coop_end(rtmi_scene *s, hipStream_t stream) {
+    if (!s->batch_blocking) HIP_TRY(rtmi_batch_coop_launch_end(stream, s->status.ptr));
+    return RTMI_OK;
+}
+// the end of a blocking batch call whose kernels have finished: the call's own overflow word
+static int batch_coop_check(rtmi_scene *s) {
+    if (s->last_batch_kernel != (int)RTMI_KERNEL_WAVE_COOP) return RTMI_OK;
+    unsigned int st = 0;
+    HIP_TRY(hipMemcpy(&st, s->status.ptr, sizeof(st), hipMemcpyDeviceToHost));
+    if (st != 0) {
+        HIP_TRY(hipMemset(s->status.ptr, 0, sizeof(unsigned int)));
+        return fail(RTMI_ERR_DEVICE, "cooperative traversal pool overflow (results invalid): run the call without RTMI_FLAG_BATCH_COOP");
+    }
+    return RTMI_OK;
+}
 // The kernel arguments of a batch call: the estimator's lights and map, and the DevParams of `rp` with no pass planned
 // (ns = 1, rank 0 of 1; the pass fields stay unread) and `d_samples` as the per-sample buffer.  rp: the caller's image
 // (sparse renders) or no_image (radiance queries and gathers).
@@ -2574,7 +2644,7 @@ static int batch_finish(rtmi_scene *s, size_t n, size_t ns, float *out_mean, flo
 static int radiance_check(const char *name, const rtmi_radiance_params *p, const void *rays, bool has_out, const char *out_msg) {
     const std::string nm = std::string(name) + ": ";
     if (!p) return fail(RTMI_ERR_INVALID, nm + "params is NULL");
-    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+    if (p->flags & ~(RTMI_RADIANCE_FLAGS | batch_coop_bits(p->flags)))
         return fail(RTMI_ERR_UNSUPPORTED, nm + "radiance queries accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     if (int rc = check_estimator(name, p->estimator)) return rc;
     if (p->spp == 0u) return fail(RTMI_ERR_INVALID, nm + "spp must be at least 1");
@@ -2595,7 +2665,7 @@ static int radiance_check(const char *name, const rtmi_radiance_params *p, const
 // handle's chunk counter (zeroed here, on the call's stream: the handle serialises its calls), then the resolve.
 static int radiance_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_radiance_params *p, hipStream_t stream, const void *d_rays,
                             const void *d_time, void *d_mean, void *d_stderr, void *d_samples) {
-    const BatchArgs a = batch_args(s, m, no_image(p->max_depth, p->t_min, p->seed, p->flags), d_samples);
+    BatchArgs a = batch_args(s, m, no_image(p->max_depth, p->t_min, p->seed, p->flags), d_samples);
     RadianceBatch B{};
     B.rays = reinterpret_cast<const float4 *>(d_rays);
     B.time = reinterpret_cast<const float *>(d_time);
@@ -2613,8 +2683,17 @@ static int radiance_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_radian
     const BatchChunks ch = batch_chunks(s, B.total, cap);
     B.chunk = ch.chunk; B.nchunks = ch.nchunks;
     const rtmi_query_params q{p->n, p->flags & RTMI_FLAG_FAST_CULL, 0ull, 0ull};
+    const bool fast = query_fast(s, &q, d_time != nullptr);
+    BatchCoop co;
+    if (int rc = plan_batch_coop(s, m, p->flags, fast, ch, a.P, co)) return rc;
+    s->last_batch_kernel = co.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
     HIP_TRY(hipMemsetAsync(B.queue, 0, sizeof(unsigned int), stream));
-    HIP_TRY(rtmi_radiance_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, ch.blocks, stream, s->dev, a.P, B, a.L, a.E));
+    if (co.coop) {
+        if (int rc = batch_coop_begin(s, stream)) return rc;
+        HIP_TRY(rtmi_batch_coop_launch_radiance(co.ext, m.nee, m.env, co.blocks, co.lds, stream, s->dev, a.P, B, a.L, a.E));
+        if (int rc = batch_coop_end(s, stream)) return rc;
+    } else
+    HIP_TRY(rtmi_radiance_launch(fast, m.nee, m.env, ch.blocks, stream, s->dev, a.P, B, a.L, a.E));
     if (d_mean || d_stderr) HIP_TRY(rtmi_radiance_launch_resolve(stream, a.P.samples, B));
     return RTMI_OK;
 }
@@ -2630,7 +2709,7 @@ extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (p->n == 0u) return RTMI_OK;
     RenderCall c;
-    if ((rc = begin_call(c, m, s))) return rc;
+    if ((rc = begin_call(c, m, s)) || (rc = batch_blocking_begin(s))) return rc;
     hipStream_t stream = s->stream.s;
     const size_t n = p->n, ns = n * p->spp;
     if ((rc = grow(s, s->q_rays, n * sizeof(rtmi_ray))) ||
@@ -2644,7 +2723,8 @@ extern "C" int rtmi_radiance(rtmi_scene *s, const rtmi_radiance_params *p, const
                                out_stderr ? d_stderr : nullptr, s->rad_samples.ptr)))
         return rc;
     HIP_TRY(hipEventRecord(s->ev[1].e, stream));
-    return batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms);
+    if ((rc = batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms))) return rc;
+    return batch_coop_check(s);
 }
 extern "C" int rtmi_radiance_device(rtmi_scene *s, const rtmi_radiance_params *p, const void *d_rays, const void *d_time, void *d_mean,
                                     void *d_stderr, void *d_samples, void *stream_) {
@@ -2656,6 +2736,7 @@ extern "C" int rtmi_radiance_device(rtmi_scene *s, const rtmi_radiance_params *p
     if (p->n == 0u) return RTMI_OK;
     AsyncCall c;
     if (int rc = c.begin(m, s, stream_)) return rc;
+    s->batch_blocking = false;
     return radiance_enqueue(s, m, p, c.stream, d_rays, d_time, d_mean, d_stderr, d_samples);
 }
 
@@ -2666,7 +2747,7 @@ static int gather_check(const char *name, const rtmi_gather_params *p, const voi
                         bool has_sh, const char *out_msg) {
     const std::string nm = std::string(name) + ": ";
     if (!p) return fail(RTMI_ERR_INVALID, nm + "params is NULL");
-    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+    if (p->flags & ~(RTMI_RADIANCE_FLAGS | batch_coop_bits(p->flags)))
         return fail(RTMI_ERR_UNSUPPORTED, nm + "gathers accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     if (p->mode > RTMI_GATHER_SPHERE) return fail(RTMI_ERR_INVALID, nm + "mode must be RTMI_GATHER_COSINE or RTMI_GATHER_SPHERE");
     if (int rc = check_estimator(name, p->estimator)) return rc;
@@ -2715,7 +2796,7 @@ static uint32_t gather_slab(const rtmi_gather_params *p, uint64_t want) {
 static int gather_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_gather_params *p, hipStream_t stream, uint32_t at,
                           uint32_t count, const void *d_points, const void *d_normals, const void *d_time, void *d_value,
                           void *d_stderr, void *d_sh, void *d_scratch) {
-    const BatchArgs a = batch_args(s, m, no_image(p->max_depth, p->t_min, p->seed, p->flags), d_scratch);
+    BatchArgs a = batch_args(s, m, no_image(p->max_depth, p->t_min, p->seed, p->flags), d_scratch);
     GatherBatch B{};
     B.points = reinterpret_cast<const float *>(d_points);
     B.normals = p->mode == RTMI_GATHER_COSINE ? reinterpret_cast<const float *>(d_normals) : nullptr;
@@ -2729,8 +2810,17 @@ static int gather_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_gather_p
     const BatchChunks ch = batch_chunks(s, B.total);
     B.chunk = ch.chunk; B.nchunks = ch.nchunks;
     const rtmi_query_params q{count, p->flags & RTMI_FLAG_FAST_CULL, 0ull, 0ull};
+    const bool fast = query_fast(s, &q, d_time != nullptr);
+    BatchCoop co;
+    if (int rc = plan_batch_coop(s, m, p->flags, fast, ch, a.P, co)) return rc;
+    s->last_batch_kernel = co.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
     HIP_TRY(hipMemsetAsync(B.queue, 0, sizeof(unsigned int), stream));
-    HIP_TRY(rtmi_gather_launch(query_fast(s, &q, d_time != nullptr), m.nee, m.env, p->mode, ch.blocks, stream, s->dev, a.P, B, a.L, a.E));
+    if (co.coop) {
+        if (int rc = batch_coop_begin(s, stream)) return rc;
+        HIP_TRY(rtmi_batch_coop_launch_gather(co.ext, m.nee, m.env, p->mode, co.blocks, co.lds, stream, s->dev, a.P, B, a.L, a.E));
+        if (int rc = batch_coop_end(s, stream)) return rc;
+    } else
+    HIP_TRY(rtmi_gather_launch(fast, m.nee, m.env, p->mode, ch.blocks, stream, s->dev, a.P, B, a.L, a.E));
     if (d_value || d_stderr || d_sh) HIP_TRY(rtmi_gather_launch_resolve(p->mode, stream, a.P.samples, B, a.P.key0, a.P.key1));
     return RTMI_OK;
 }
@@ -2747,7 +2837,7 @@ extern "C" int rtmi_gather(rtmi_scene *s, const rtmi_gather_params *p, const flo
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (p->n == 0u) return RTMI_OK;
     RenderCall c;
-    if ((rc = begin_call(c, m, s))) return rc;
+    if ((rc = begin_call(c, m, s)) || (rc = batch_blocking_begin(s))) return rc;
     hipStream_t stream = s->stream.s;
     const bool cosine = p->mode == RTMI_GATHER_COSINE;
     const uint32_t slab = gather_slab(p, p->slab_points ? p->slab_points : (256ull << 20) / (12ull * p->spp));
@@ -2780,7 +2870,7 @@ extern "C" int rtmi_gather(rtmi_scene *s, const rtmi_gather_params *p, const flo
             *kernel_ms += (double)ms;
         }
     }
-    return RTMI_OK;
+    return batch_coop_check(s);
 }
 extern "C" int rtmi_gather_device(rtmi_scene *s, const rtmi_gather_params *p, const void *d_points, const void *d_normals,
                                   const void *d_time, void *d_value, void *d_stderr, void *d_sh, void *d_scratch,
@@ -2795,6 +2885,7 @@ extern "C" int rtmi_gather_device(rtmi_scene *s, const rtmi_gather_params *p, co
     if (p->n == 0u) return RTMI_OK;
     AsyncCall c;
     if (int rc = c.begin(m, s, stream_)) return rc;
+    s->batch_blocking = false;
     const uint64_t fits = scratch_bytes / (12ull * p->spp);
     const uint32_t slab = gather_slab(p, p->slab_points && p->slab_points < fits ? p->slab_points : fits);
     const char *pts = reinterpret_cast<const char *>(d_points), *nrm = reinterpret_cast<const char *>(d_normals);
@@ -2889,7 +2980,7 @@ static int sparse_check(const char *name, const rtmi_scene *s_in, const rtmi_ren
     if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
     if (int rc = check_attached_early(estimator_of(name, sp->estimator, sp->env_select_p, ""), s_in)) return rc;
     if (sp->reserved[0] || sp->reserved[1] || sp->reserved[2]) return fail(RTMI_ERR_INVALID, nm + "reserved words must be zero");
-    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+    if (p->flags & ~(RTMI_RADIANCE_FLAGS | batch_coop_bits(p->flags)))
         return fail(RTMI_ERR_UNSUPPORTED, nm + "sparse renders accept the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     return RTMI_OK;
 }
@@ -2898,7 +2989,7 @@ static int sparse_check(const char *name, const rtmi_scene *s_in, const rtmi_ren
 static int sparse_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_params *p, const rtmi_camera *cam,
                           const rtmi_sparse_params *sp, hipStream_t stream, const void *d_pixels, const void *d_count, void *d_mean,
                           void *d_stderr, void *d_samples, unsigned int *queue) {
-    const BatchArgs a = batch_args(s, m, *p, d_samples); // the image's nx, ny, seed, max_depth, t_min and flags
+    BatchArgs a = batch_args(s, m, *p, d_samples); // the image's nx, ny, seed, max_depth, t_min and flags
     const DevCamera C = dev_camera(cam);
     SparseBatch B{};
     B.list = reinterpret_cast<const uint32_t *>(d_pixels);
@@ -2910,7 +3001,15 @@ static int sparse_enqueue(rtmi_scene *s, const Estimator &m, const rtmi_render_p
     const BatchChunks ch = batch_chunks(s, sp->n * sp->ns); // for a full list: the kernel counts the chunks of the entries there are
     B.chunk = ch.chunk;
     const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam);
+    BatchCoop co;
+    if (int rc = plan_batch_coop(s, m, p->flags, fast, ch, a.P, co)) return rc;
+    s->last_batch_kernel = co.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
     HIP_TRY(hipMemsetAsync(queue, 0, sizeof(unsigned int), stream));
+    if (co.coop) {
+        if (int rc = batch_coop_begin(s, stream)) return rc;
+        HIP_TRY(rtmi_batch_coop_launch_sparse(co.ext, m.nee, m.env, co.blocks, co.lds, stream, s->dev, C, a.P, B, a.L, a.E));
+        if (int rc = batch_coop_end(s, stream)) return rc;
+    } else
     HIP_TRY(rtmi_sparse_launch(fast, m.nee, m.env, ch.blocks, stream, s->dev, C, a.P, B, a.L, a.E));
     if (d_mean || d_stderr) HIP_TRY(rtmi_sparse_launch_resolve(stream, a.P.samples, B));
     return RTMI_OK;
@@ -2932,7 +3031,7 @@ extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, co
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     if (sp->n == 0u) return RTMI_OK;
     RenderCall c;
-    if ((rc = begin_call(c, m, s))) return rc;
+    if ((rc = begin_call(c, m, s)) || (rc = batch_blocking_begin(s))) return rc;
     hipStream_t stream = s->stream.s;
     const size_t n = sp->n, ns = n * sp->ns;
     if ((rc = grow(s, s->q_time, n * sizeof(uint32_t))) || (rc = batch_reserve(s, n, ns))) return rc;
@@ -2943,7 +3042,8 @@ extern "C" int rtmi_sparse_render(rtmi_scene *s, const rtmi_render_params *p, co
                              s->rad_samples.ptr, s->status.ptr + RTMI_STATUS_WORDS)))
         return rc;
     HIP_TRY(hipEventRecord(s->ev[1].e, stream));
-    return batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms);
+    if ((rc = batch_finish(s, n, ns, out_mean, out_stderr, out_samples, kernel_ms))) return rc;
+    return batch_coop_check(s);
 }
 extern "C" int rtmi_sparse_render_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
                                          const void *d_pixels, const void *d_count, void *d_mean, void *d_stderr, void *d_samples,
@@ -2962,6 +3062,7 @@ extern "C" int rtmi_sparse_render_device(rtmi_scene *s, const rtmi_render_params
     if (sp->n == 0u) return RTMI_OK;
     AsyncCall c;
     if (int rc = c.begin(m, s, stream_)) return rc;
+    s->batch_blocking = false;
     return sparse_enqueue(s, m, p, cam, sp, c.stream, d_pixels, d_count, d_mean, d_stderr, d_samples,
                           reinterpret_cast<unsigned int *>(d_scratch) + RTMI_SPARSE_QUEUE_WORD);
 }
@@ -3015,6 +3116,7 @@ extern "C" int rtmi_sparse_refine_device(rtmi_scene *s, const rtmi_render_params
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     AsyncCall c;
     if ((rc = c.begin(m, s, stream_))) return rc;
+    s->batch_blocking = false;
     return sparse_refine_enqueue(s, m, p, cam, sp, accept_mask, mark, c.stream, d_bytes, d_linear, d_rgb8, d_stderr, d_scratch, d_count_out);
 }
 extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam, const rtmi_sparse_params *sp,
@@ -3028,7 +3130,7 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
     const std::string null_scene = std::string(name) + ": scene is NULL";
     const Estimator m = estimator_of(name, sp->estimator, sp->env_select_p, null_scene.c_str());
     RenderCall c;
-    if ((rc = begin_call(c, m, s))) return rc;
+    if ((rc = begin_call(c, m, s)) || (rc = batch_blocking_begin(s))) return rc;
     hipStream_t stream = s->stream.s;
     // one allocation per call: bytes | scratch | linear | stderr | rgb8
     const size_t npix = (size_t)p->nx * p->ny;
@@ -3057,7 +3159,7 @@ extern "C" int rtmi_sparse_refine(rtmi_scene *s, const rtmi_render_params *p, co
     const hipError_t e2 = hipStreamSynchronize(stream); // before the allocation is freed, whatever was enqueued
     HIP_TRY(e);
     HIP_TRY(e2);
-    return RTMI_OK;
+    return batch_coop_check(s);
 }
 
 // ---- per-pixel adaptive sampling (include/rtmi_pixelwise.h) -----------------------------------------------------------------
@@ -3129,7 +3231,7 @@ static int pixelwise_check(const char *name, const rtmi_scene *s_in, const rtmi_
     if (npix == 0u || npix > RTMI_SPARSE_MAX_PIXELS) return fail(RTMI_ERR_INVALID, nm + "the image must have 1 .. 32768^2 pixels");
     if (!std::isfinite(p->t_min)) return fail(RTMI_ERR_INVALID, nm + "t_min must be finite");
     if ((rc = check_attached_early(estimator_of(name, o->estimator, o->env_select_p, ""), s_in))) return rc;
-    if (p->flags & ~RTMI_RADIANCE_FLAGS)
+    if (p->flags & ~(RTMI_RADIANCE_FLAGS | batch_coop_bits(p->flags)))
         return fail(RTMI_ERR_UNSUPPORTED, nm + (o->windowed ? "windowed" : "per-pixel") +
                                               " adaptive sampling accepts the flags FAST_CULL, SKY, FACE_FORWARD and UV_BOOK only");
     const rtmi_adaptive a{o->min_spp, o->step_spp, o->abs_tol, o->rel_tol};
@@ -3214,6 +3316,7 @@ static int pixelwise_render_device(const char *name, rtmi_scene *s, const rtmi_r
     if (!s) return fail(RTMI_ERR_INVALID, null_scene);
     AsyncCall c;
     if (int rc = c.begin(m, s, stream_)) return rc;
+    s->batch_blocking = false;
     return pixelwise_enqueue(s, m, p, cam, o, c.stream, out, reinterpret_cast<char *>(d_scratch), nullptr, nullptr);
 }
 static int pixelwise_render_host(const char *name, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p,
@@ -3225,7 +3328,7 @@ static int pixelwise_render_host(const char *name, rtmi_scene *s, const rtmi_cam
     const std::string null_scene = std::string(name) + ": scene is NULL";
     const Estimator m = estimator_of(name, o->estimator, o->env_select_p, null_scene.c_str());
     RenderCall c;
-    if ((rc = begin_call(c, m, s))) return rc;
+    if ((rc = begin_call(c, m, s)) || (rc = batch_blocking_begin(s))) return rc;
     hipStream_t stream = s->stream.s;
     // the handle's memory, grow-only: scratch | linear | stderr | spp | rgb8
     const size_t npix = (size_t)p->nx * p->ny, up = (npix + 15u) & ~(size_t)15u;
@@ -3254,9 +3357,9 @@ static int pixelwise_render_host(const char *name, rtmi_scene *s, const rtmi_cam
         *stats = rtmi_stats{};
         stats->kernel_ms = (double)ms;
         stats->samples = paths;
-        stats->kernel = RTMI_KERNEL_PERLANE;
+        stats->kernel = (uint32_t)s->last_batch_kernel; // every launch of the call selects alike
     }
-    return RTMI_OK;
+    return batch_coop_check(s);
 }
 extern "C" int rtmi_render_pixelwise_device(rtmi_scene *s, const rtmi_render_params *p, const rtmi_camera *cam,
                                             const rtmi_pixelwise_opts *o, void *d_linear, void *d_rgb8, void *d_stderr, void *d_spp,

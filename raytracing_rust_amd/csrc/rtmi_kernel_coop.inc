@@ -6,6 +6,19 @@
 // rtmi_roulette_coop_kernel, rtmi_roulette_coop.hip; include/rtmi_roulette_coop.h).  The lane-level path logic is the
 // rtmi_path_*.inc fragments', shared with that body; this one provides them the wave's LDS (CoopLds; its pool is phase B's
 // scratch), the Philox state `g` in the form the pool allows, and the item scan that all 64 lanes execute together.
+// Two seams, as rtmi_path_scan.inc has them, for the batch kernels of rtmi_batch_coop.hip (include/rtmi_batch_coop.h):
+// RTMI_COOP_TAKE names the file of the take step (default: rtmi_path_take.inc; with another one `cam`, `tiles` and TILE_LIST
+// are not read), and RTMI_COOP_T_MIN / RTMI_COOP_T_MAX are the scan's interval (default: the pinned scalar t_min and
+// RTMI_FLT_MAX; a batch kernel's may differ from lane to lane: it travels in the ray context of geom_query_coop).
+#ifndef RTMI_COOP_TAKE
+#define RTMI_COOP_TAKE "rtmi_path_take.inc"
+#define RTMI_COOP_TAKE_DEFAULTED
+#endif
+#ifndef RTMI_COOP_T_MIN
+#define RTMI_COOP_T_MIN t_min
+#define RTMI_COOP_T_MAX RTMI_FLT_MAX
+#define RTMI_COOP_T_DEFAULTED
+#endif
     constexpr bool INST = INSTL >= 1; // instanced primitives, media inside transforms
     constexpr bool INSD = INSTL >= 2; // DEFERRED items, list scans, nested media
     constexpr bool FEATURES = false; // no feature kernel runs this body
@@ -62,14 +75,14 @@
         for (;;) {
             if (__ballot(!have_hit && !done) == 0ull) break;
             prof_time<PROF>(prof, 31, tstamp); // loop overhead / phase switching
-#include "rtmi_path_take.inc"
+#include RTMI_COOP_TAKE
             const bool need = !have_hit && !done;
             prof_tick<PROF>(prof, 0, need);
             prof_time<PROF>(prof, 25, tstamp); // camera samples
             RayF W;
             W.o = pa.ro; W.d = pa.rd;
             ray_derive(W);
-            if (need) { closest = RTMI_FLT_MAX; best_item = -1; best_pf = 0; best_medium = false; }
+            if (need) { closest = RTMI_COOP_T_MAX; best_item = -1; best_pf = 0; best_medium = false; }
             // INSD, parked in LDS: [0] the closest hit before a BVH item whose media / instanced-subtree children follow as DEFERRED
             // items (T0); [64] / [128] / [192] the scan of a list with media that was a child of a BVHNode (rtmi.h, LISTSCAN): its
             // closest hit so far, who holds it (item, bit 31: a medium; RTMI_PARK_NONE: nobody) and the primitive
@@ -111,10 +124,10 @@
                     const bool dfi = INSD && (I.flags & RTMI_ITEMFLAG_DEFERRED) != 0u; // wave-uniform
                     if (dfi) {
                         const float t0_saved = __uint_as_float(park[0]);
-                        reach = need && deferred_gate(sc, I, W, t_min, t0_saved);
+                        reach = need && deferred_gate(sc, I, W, RTMI_COOP_T_MIN, t0_saved);
                         qmax = scan ? __uint_as_float(park[64]) : t0_saved;
                     }
-                    if (geom_query_coop<PROF, EXT, EXT, INST, ONE_TREE>(sc, I, use_alt, reach, R, pa.rtime, t_min, qmax, cw, t, pf, overflow, prof, slot)) {
+                    if (geom_query_coop<PROF, EXT, EXT, INST, ONE_TREE>(sc, I, use_alt, reach, R, pa.rtime, RTMI_COOP_T_MIN, qmax, cw, t, pf, overflow, prof, slot)) {
                         if (scan) {
                             park[64] = __float_as_uint(t); park[128] = it; park[192] = (uint32_t)pf;
                         } else if (!dfi || deferred_bvh_wins(I.count, t, closest, best_item, best_pf, grp_first, grp_tree)) {
@@ -140,7 +153,7 @@
                         float t0_saved = RTMI_FLT_MAX;
                         if (dfr) {
                             t0_saved = scan ? __uint_as_float(park[64]) : __uint_as_float(park[0]); // the interval's end: the scan's closest hit, or T0
-                            reach = need && deferred_gate(sc, I, W, t_min, __uint_as_float(park[0]));
+                            reach = need && deferred_gate(sc, I, W, RTMI_COOP_T_MIN, __uint_as_float(park[0]));
                         }
                         h1 = geom_query_coop<PROF, EXT, false, INST>(sc, I, use_alt, reach, R, pa.rtime, -RTMI_FLT_MAX, RTMI_FLT_MAX, cw, t1, pf, overflow, prof, slot);
                         h2 = geom_query_coop<PROF, EXT, false, INST>(sc, I, use_alt, reach && h1, R, pa.rtime, t1 + 0.0001f, RTMI_FLT_MAX, cw, t2, pf, overflow, prof, slot);
@@ -148,7 +161,7 @@
                             if (reach && h1 && h2) h1 = nested_medium_interval(sc, I, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), g, k0, k1, t1, t2);
                         }
                         if (dfr) { // its interval ends at the t_max the BVH was entered with; its hit must beat what the tree found
-                            if (reach && h1 && h2 && medium_sample(t1, t2, t_min, t0_saved, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
+                            if (reach && h1 && h2 && medium_sample(t1, t2, RTMI_COOP_T_MIN, t0_saved, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
                                 if (scan) { park[64] = __float_as_uint(tm); park[128] = it | 0x80000000u; }
                                 else if (tm < closest) { closest = tm; best_item = (int)it; best_medium = true; }
                             }
@@ -158,7 +171,7 @@
                     if (need && h1 && h2) {
                         // (one square root per medium: sharing it between the media of a query measured -1.1 %,
                         // profiles/r03_experiments/wdn_shared_norm_ab.log)
-                        if (medium_sample(t1, t2, t_min, closest, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
+                        if (medium_sample(t1, t2, RTMI_COOP_T_MIN, closest, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
                             closest = tm; best_item = (int)it; best_medium = true;
                         }
                     }
@@ -188,3 +201,12 @@
             else atomicAdd(P.prof + threadIdx.x, prof_lds[threadIdx.x]);
         }
     }
+#ifdef RTMI_COOP_TAKE_DEFAULTED
+#undef RTMI_COOP_TAKE
+#undef RTMI_COOP_TAKE_DEFAULTED
+#endif
+#ifdef RTMI_COOP_T_DEFAULTED
+#undef RTMI_COOP_T_MIN
+#undef RTMI_COOP_T_MAX
+#undef RTMI_COOP_T_DEFAULTED
+#endif

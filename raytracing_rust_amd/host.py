@@ -86,6 +86,11 @@ def _coop_flags(kw, coop, flag=abi.RTMI_FLAG_LIGHT_COOP):
     return kw
 
 
+def _batch_coop_flags(flags, coop):
+    """coop=True of the batch modes: ORs RTMI_FLAG_BATCH_COOP (include/rtmi_batch_coop.h) into a flags word."""
+    return int(flags) | (abi.FLAG_BATCH_COOP if coop else 0)
+
+
 class Scene:
     """A world lowered to the flat device description (and, after upload(), resident in HBM)."""
 
@@ -727,7 +732,7 @@ class Scene:
 
     def radiance(self, origins, directions, times=None, spp=1, estimator="plain", t_min=0.001, t_max=float("inf"), seed=0,
                  first_ray=0, first_sample=0, stream_skip=0, max_depth=50, env_select_p=0.5, flags=abi.RTMI_FLAG_FAST_CULL,
-                 samples=False, path_t_min=0.001):
+                 samples=False, path_t_min=0.001, coop=False):
         """Path-traced radiance along a batch of rays (include/rtmi_radiance.h): spp independent paths of render()'s
         integrator per ray, each starting with the caller's ray instead of a camera ray.  estimator: "plain" (render),
         "nee" (render_nee), "env" (render_env(nee=False)) or "env_nee" (render_env(nee=True, env_select_p)); the light
@@ -739,12 +744,16 @@ class Scene:
         Returns dict(mean f32 [n, 3], stderr f32 [n, 3] (+inf for spp = 1), kernel_ms[, samples f32 [n, spp, 3]]).
         With torch tensors on the scene's device the call is enqueued on torch's current stream (rtmi_radiance_device) and
         returns torch tensors on that device (samples always among them: the buffer is the kernel's): no host copy is
-        made.  A scene resident on a device list raises Unsupported."""
+        made.  A scene resident on a device list raises Unsupported.
+        coop=True (RTMI_FLAG_BATCH_COOP, include/rtmi_batch_coop.h): under RTMI_FLAG_FAST_CULL the wave-cooperative kernel
+        traces the paths where the scene allows it, the same bits in every output.  The dict does not change: these entries
+        have no rtmi_stats to report the kernel in."""
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
         self._ready({}, lights=estimator in ("nee", "env_nee"))
         torch_in = hasattr(origins, "data_ptr") and hasattr(origins, "is_cuda")
         n = int(origins.shape[0])
+        flags = _batch_coop_flags(flags, coop)
         p = abi.RadianceParams(n, int(spp), abi.ROULETTE_ESTIMATORS[estimator], int(flags), int(max_depth), float(path_t_min),
                                int(seed) & (2 ** 64 - 1), int(first_ray) & (2 ** 64 - 1), int(first_sample), int(stream_skip),
                                float(env_select_p))
@@ -790,14 +799,14 @@ class Scene:
             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return res
 
-    def irradiance(self, points, normals, spp, seed=0, **kw):
+    def irradiance(self, points, normals, spp, seed=0, coop=False, **kw):
         """Irradiance at surface points (probes, lightmap and vertex baking): E = integral of L cos(theta) over the
         normal's hemisphere, estimated with spp cosine-distributed directions per point (irradiance_directions, drawn on
         the host from Philox under `seed`), one radiance() path along each: E = pi * mean.  points, normals: [n, 3];
         normals need not be unit length.  kw: radiance()'s keywords (estimator, max_depth, t_min, flags, ...); the rays are
         stream_skip = 0 rays starting at the point, ray k of point i being ray i * spp + k of the batch.
         Returns dict(irradiance f32 [n, 3], stderr f32 [n, 3]): the standard error of the estimate from the per-ray
-        values (+inf for spp = 1)."""
+        values (+inf for spp = 1).  coop=True: radiance()'s."""
         pts = np.ascontiguousarray(points, dtype=np.float32)
         nrm = np.ascontiguousarray(normals, dtype=np.float32)
         if pts.ndim != 2 or pts.shape[1] != 3 or nrm.shape != pts.shape:
@@ -810,7 +819,7 @@ class Scene:
                 raise ValueError("irradiance() sets %s itself" % k)
         n = pts.shape[0]
         dirs = irradiance_directions(nrm, spp, seed)
-        r = self.radiance(np.repeat(pts, spp, axis=0), dirs.reshape(n * spp, 3), spp=1, seed=seed, stream_skip=0, **kw)
+        r = self.radiance(np.repeat(pts, spp, axis=0), dirs.reshape(n * spp, 3), spp=1, seed=seed, stream_skip=0, coop=coop, **kw)
         x = r["mean"].astype(np.float64).reshape(n, spp, 3)
         mean = x.sum(axis=1) / float(spp)
         if spp > 1:
@@ -821,7 +830,7 @@ class Scene:
 
     def gather(self, points, normals=None, spp=16, mode="cosine", estimator="plain", seed=0, first_point=0, first_sample=0,
                slab_points=0, times=None, flags=abi.RTMI_FLAG_FAST_CULL, max_depth=50, t_min=0.001, env_select_p=0.5, sh=True,
-               scratch_bytes=None):
+               scratch_bytes=None, coop=False):
         """Light arriving at points (include/rtmi_gather.h): the device draws spp directions per point, traces one
         radiance() path along each and reduces per point; no ray is built on the host.  mode "cosine": points and normals
         [n, 3] (any length), value = the irradiance E = pi * mean over cosine-distributed directions.  mode "sphere":
@@ -832,7 +841,8 @@ class Scene:
         depends on it.  Returns dict(value f32 [n, 3], stderr f32 [n, 3] (+inf for spp = 1), kernel_ms[, sh]).
         With torch tensors on the scene's device the call is enqueued on torch's current stream (rtmi_gather_device) and
         returns torch tensors on that device: no host copy is made; its per-sample scratch is a torch allocation of
-        scratch_bytes (default: one slab's).  A scene resident on a device list raises Unsupported."""
+        scratch_bytes (default: one slab's).  A scene resident on a device list raises Unsupported.
+        coop=True (RTMI_FLAG_BATCH_COOP): as in radiance(), same bits on the wave-cooperative kernel."""
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
         if mode not in abi.GATHER_MODES:
@@ -843,7 +853,7 @@ class Scene:
         self._ready({}, lights=estimator in ("nee", "env_nee"))
         n, spp = int(points.shape[0]), int(spp)
         want_sh = bool(sh) and not cosine
-        p = abi.GatherParams(n, spp, abi.GATHER_MODES[mode], abi.ROULETTE_ESTIMATORS[estimator], int(flags), int(max_depth),
+        p = abi.GatherParams(n, spp, abi.GATHER_MODES[mode], abi.ROULETTE_ESTIMATORS[estimator], _batch_coop_flags(flags, coop), int(max_depth),
                              float(t_min), int(seed) & (2 ** 64 - 1), int(first_point) & (2 ** 64 - 1), int(first_sample),
                              int(slab_points), float(env_select_p))
         if hasattr(points, "data_ptr") and hasattr(points, "is_cuda"):
@@ -894,7 +904,7 @@ class Scene:
         return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
 
     def render_pixels(self, cam, nx, ny, pixels, ns, estimator="plain", seed=42, first_sample=0, samples=False, env_select_p=0.5,
-                      **kw):
+                      coop=False, count=None, **kw):
         """Chosen pixels of the nx x ny image under `cam` with the render's own paths (include/rtmi_sparse.h).  pixels: an
         integer array of indices row * nx + i into the image's planes (row 0 the top row), or an [n, 2] array of (i, row); it may
         be unsorted and may repeat a pixel.  Sample s
@@ -904,13 +914,19 @@ class Scene:
         kernel_ms[, samples f32 [n, ns, 3]]): with first_sample = 0 mean and stderr are the render's linear and stderr
         planes at those pixels.  With a torch tensor on the scene's device the call is enqueued on torch's current stream
         (rtmi_sparse_render_device) and returns torch tensors on that device, samples always among them: no host copy is
-        made.  A scene resident on a device list raises Unsupported."""
+        made; count: with a torch list, an int32 tensor on the device whose first word is the number of entries to trace,
+        at most the list's length (the d_count of rtmi_sparse_render_device).  A scene resident on a device list raises
+        Unsupported.
+        coop=True (RTMI_FLAG_BATCH_COOP): as in radiance(), same bits on the wave-cooperative kernel."""
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
         self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        kw["flags"] = _batch_coop_flags(kw.get("flags", 0), coop)
         p = default_params(nx, ny, 1, seed=seed, **kw)
         if hasattr(pixels, "data_ptr") and hasattr(pixels, "is_cuda"):
-            return self._render_pixels_torch(cam, p, pixels, int(ns), estimator, int(first_sample), float(env_select_p))
+            return self._render_pixels_torch(cam, p, pixels, int(ns), estimator, int(first_sample), float(env_select_p), count)
+        if count is not None:
+            raise ValueError("count belongs to a torch list of pixels")
         px = np.asarray(pixels)
         if px.ndim == 2 and px.shape[1] == 2:
             px = px[:, 1].astype(np.int64) * nx + px[:, 0].astype(np.int64)
@@ -955,7 +971,7 @@ class Scene:
         return res  # px and scratch return to torch's allocator, which hands them out again on this stream behind the kernels
 
     def refine_pixels(self, cam, planes, classes=(3,), ns=4, estimator="plain", seed=42, budget=None, mark=4, first_sample=0,
-                      env_select_p=0.5, **kw):
+                      env_select_p=0.5, coop=False, **kw):
         """Traces again the pixels of an image whose class is in `classes` and patches the results in (select -> sparse
         render -> patch of include/rtmi_sparse.h, one native call).  planes: a dict with linear f32 [ny,nx,3], rgb8 u8
         [ny,nx,3] and cls u8 [ny,nx], as Upscaler.render returns it (a stderr f32 [ny,nx,3] plane, when present, is patched
@@ -964,13 +980,15 @@ class Scene:
         changes.  budget: the most pixels to trace, the first in index order (None: every pixel of the image may be; the
         scratch grows with it: 28 + 12 * ns bytes per pixel of budget).  torch tensors on the scene's device are patched in
         place on torch's current stream, without a host copy; numpy planes are left alone and patched copies returned.
-        Returns the dict with refined = (pixels patched, pixels selected)."""
+        Returns the dict with refined = (pixels patched, pixels selected).
+        coop=True (RTMI_FLAG_BATCH_COOP): as in radiance(), same bits on the wave-cooperative kernel."""
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
         mask = _sparse_mask(classes)
         cls = planes["cls"]
         ny, nx = int(cls.shape[0]), int(cls.shape[1])
         self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        kw["flags"] = _batch_coop_flags(kw.get("flags", 0), coop)
         p = default_params(nx, ny, 1, seed=seed, **kw)
         cap = nx * ny if budget is None else int(budget)
         sp = abi.SparseParams(cap, int(ns), int(first_sample), abi.ROULETTE_ESTIMATORS[estimator], float(env_select_p))
@@ -1014,7 +1032,7 @@ class Scene:
         return out
 
     def render_pixelwise(self, cam, nx, ny, ns, min_spp, step_spp, abs_tol=0.0, rel_tol=0.0, estimator="plain", seed=0, pass_spp=0,
-                         out="numpy", env_select_p=0.5, **kw):
+                         out="numpy", env_select_p=0.5, coop=False, **kw):
         """Adaptive sampling per pixel, driven from the device (include/rtmi_pixelwise.h): every pixel gets min_spp samples,
         then step_spp more per step while, in some channel, its stderr > abs_tol + rel_tol * |mean|, up to ns (the last step
         shortened to land on ns).  Each pixel is tested alone, where render_adaptive tests 8x8 tiles, and no step waits for
@@ -1027,12 +1045,16 @@ class Scene:
         step traced; samples is the number of paths traced.  out="torch": the device form on torch's current stream; the
         planes, counts (int32 words) and the scratch are torch tensors on the scene's device, nothing is copied to the host,
         and samples is a function that reads counts back when called.  A scene resident on a device list raises
-        Unsupported."""
+        Unsupported.
+        coop=True (RTMI_FLAG_BATCH_COOP, include/rtmi_batch_coop.h): the steps' paths trace on the wave-cooperative kernel
+        where the scene allows it, the same bits in every plane, spp and counts included; with out="numpy" the dict gains
+        "kernel", rtmi_stats.kernel of the blocking form (abi.RTMI_KERNEL_*)."""
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
         if out not in ("numpy", "torch"):
             raise ValueError('out must be "numpy" or "torch"')
         self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        kw["flags"] = _batch_coop_flags(kw.get("flags", 0), coop)
         p = default_params(nx, ny, ns, seed=seed, **kw)
         o = abi.PixelwiseOpts(int(min_spp), int(step_spp), abi.ROULETTE_ESTIMATORS[estimator], int(pass_spp), float(abs_tol),
                               float(rel_tol), float(env_select_p))
@@ -1048,6 +1070,8 @@ class Scene:
             st = res.pop("stats")
             res["counts"] = counts[:steps]
             res["samples"] = int(st.samples)
+            if coop:
+                res["kernel"] = int(st.kernel)
             return res
         import torch
 
@@ -1066,19 +1090,20 @@ class Scene:
         return res  # scratch returns to torch's allocator, which hands it out again on this stream only behind the kernels
 
     def render_windowed(self, cam, nx, ny, ns, min_spp, step_spp, radius=1, abs_tol=0.0, rel_tol=0.0, estimator="plain", seed=0,
-                        pass_spp=0, out="numpy", env_select_p=0.5, **kw):
+                        pass_spp=0, out="numpy", env_select_p=0.5, coop=False, **kw):
         """Adaptive sampling per pixel with a neighbourhood stopping rule, driven from the device (include/rtmi_window.h):
         render_pixelwise's lattice, samples and own-pixel test, but a pixel stays alive while any pixel within the Chebyshev
         radius `radius` of it (the window clipped at the image border) still fails its test below the cap.  radius=0 is
         render_pixelwise bit for bit; a larger radius only adds samples, at every pixel; radius >= max(nx, ny) - 1 stops every
         pixel at the same count (radius is at most abi.RTMI_WINDOW_MAX_RADIUS).  A pixel with spp = n is bit for bit the
         estimator's fixed render at ns = n, as in render_pixelwise.  No inclusion holds against render_adaptive's 8x8 tiles.
-        The other arguments, out="torch" and the returned dict are render_pixelwise's."""
+        The other arguments, out="torch", coop=True and the returned dict are render_pixelwise's."""
         if estimator not in abi.ROULETTE_ESTIMATORS:
             raise ValueError("estimator must be one of %s" % ", ".join(sorted(abi.ROULETTE_ESTIMATORS)))
         if out not in ("numpy", "torch"):
             raise ValueError('out must be "numpy" or "torch"')
         self._ready(kw, lights=estimator in ("nee", "env_nee"))
+        kw["flags"] = _batch_coop_flags(kw.get("flags", 0), coop)
         p = default_params(nx, ny, ns, seed=seed, **kw)
         o = abi.WindowOpts(int(min_spp), int(step_spp), abi.ROULETTE_ESTIMATORS[estimator], int(pass_spp), float(abs_tol),
                            float(rel_tol), float(env_select_p), int(radius))
@@ -1094,6 +1119,8 @@ class Scene:
             st = res.pop("stats")
             res["counts"] = counts[:steps]
             res["samples"] = int(st.samples)
+            if coop:
+                res["kernel"] = int(st.kernel)
             return res
         import torch
 
