@@ -9,6 +9,7 @@
 #pragma once
 #include "rtmi_f64_types.hpp"
 #include "rtmi_shade.hpp"
+#include "rtmi_sin_f64.hpp"
 
 __device__ __forceinline__ D3 d3(double x, double y, double z) { return D3{x, y, z}; }
 __device__ __forceinline__ D3 operator+(D3 a, D3 b) { return d3(a.x + b.x, a.y + b.y, a.z + b.z); }
@@ -231,6 +232,9 @@ __device__ __forceinline__ D3 random_in_unit_disk_d(RngReg &g, uint32_t k0, uint
 __device__ __forceinline__ double rng_uniform_d(RngReg &g, uint32_t k0, uint32_t k1) { return (double)rng_uniform(g, k0, k1); }
 
 // ---- textures — texture.rs, perlin.rs -------------------------------------------------------------------------------
+// f64::sin (texture.rs:41, :68): below 2^40 the double-double sine of rtmi_sin_f64.hpp, rounded once; it is what glibc's
+// returns for all but about 1 argument in 1000.  The device library's beyond.  One copy, called.
+__device__ __noinline__ double sin_d(double x) { return fabs(x) < rtmi_sin64::SIN_CR_LIMIT ? rtmi_sin64::sin_cr(x) : sin(x); }
 __device__ __forceinline__ uint64_t as_usize_d(double x) { // Rust `f64 as usize`: saturating, NaN -> 0
     if (!(x > 0.0)) return 0ull;
     if (x >= 18446744073709551615.0) return ~0ull;
@@ -261,7 +265,7 @@ __device__ D3 tex_value_d(const DevScene &sc, const DevSceneF64 &w, int tex, dou
         const rtmi_texture t = sc.texs[tex];
         const double *f = w.texf + 4 * (size_t)tex;
         if (t.kind == RTMI_TEX_CHECKER) { // texture.rs:39-48
-            const double s = sin(10.0 * p.x) * sin(10.0 * p.y) * sin(10.0 * p.z);
+            const double s = sin_d(10.0 * p.x) * sin_d(10.0 * p.y) * sin_d(10.0 * p.z);
             tex = s < 0.0 ? t.i0 : t.i1;
             continue;
         }
@@ -273,7 +277,7 @@ __device__ D3 tex_value_d(const DevScene &sc, const DevSceneF64 &w, int tex, dou
                 weight *= 0.5;
                 tp = tp * 2.0;
             }
-            const double g = 0.5 * (1.0 + sin(f[0] * p.x + 5.0 * fabs(accum)));
+            const double g = 0.5 * (1.0 + sin_d(f[0] * p.x + 5.0 * fabs(accum)));
             return d3(g, g, g);
         }
         if (t.kind == RTMI_TEX_IMAGE) { // texture.rs:86-108
@@ -609,7 +613,7 @@ __global__ void rtmi_math_probe_f64_kernel(int op, const double *x, const double
     if (i >= n) return;
     double r;
     switch (op) {
-    case 0: r = sin(x[i]); break;
+    case 0: r = sin_d(x[i]); break;
     case 1: r = log(x[i]); break;
     case 2: r = atan2(x[i], y[i]); break;
     case 3: r = asin(x[i]); break;

@@ -10,13 +10,18 @@
 // textures — src/texture.rs, src/perlin.rs
 // ----------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t as_usize_u32(float x) { // Rust `as usize`, see DESIGN.md
-    if (!(x > 0.0f)) return 0u;
-    if (x >= 4294967296.0f) return 0u; // fp32 values >= 2^32 are multiples of 512: low 8 bits are 0
-    return (uint32_t)x;
+    // Not positive, or NaN (med3 then gives the smaller of the other two): 0, the clamp's lower end.
+    // In [2^32, 2^64): fp32 values >= 2^32 are multiples of 512: low 8 bits are 0,
+    // as they are in 2^32 - 256, the clamp's upper end and the largest fp32 value the conversion holds.  From 2^64 on (and
+    // +inf) the 64-bit cast saturates to 2^64 - 1 (perlin.rs:83-85): low 8 bits 255, and the `+ 1` of the next cell wraps
+    // to 0 — as 0xFFFFFFFF does in 32 bits.  One clamp and one select: written as three early returns the cases became
+    // divergent branches (2 % of the headline frame).
+    const uint32_t r = (uint32_t)__builtin_amdgcn_fmed3f(x, 0.0f, 4294967040.0f);
+    return x >= 18446744073709551616.0f ? 0xFFFFFFFFu : r;
 }
 // ImageTexture's `(x) as usize` followed by the clamp to n - 1 (texture.rs:91-101): Rust's cast saturates, so any
-// x >= n — including +inf and values beyond 2^32, where as_usize_u32's wrap to 0 would pick the FIRST texel — lands
-// on n - 1; negative and NaN give 0.
+// x >= n — including +inf and values beyond 2^32, which as_usize_u32 reduces to their low bits alone (2^32 - 256, or
+// 0xFFFFFFFF from 2^64 on: right for a lattice cell, not for a size) — lands on n - 1; negative and NaN give 0.
 __device__ __forceinline__ uint32_t as_image_index(float x, uint32_t n) {
     if (!(x > 0.0f)) return 0u;
     if (x >= (float)n) return n - 1u;

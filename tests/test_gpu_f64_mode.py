@@ -2,7 +2,8 @@
 
 The mode traces the reference's paths in double with its literal arithmetic and the same Philox streams.  Beyond
 + - * / and sqrt, which both sides round correctly, only sin (checker, noise), log (media), atan2 and asin (sphere uv)
-are evaluated at render time, on the device by the device math library and in the oracle by glibc.  Hence:
+are evaluated at render time, on the device by the device math library (the sine below 2^40 by csrc/rtmi_sin_f64.hpp, the
+correctly rounded one: tests/test_sin_f64.py) and in the oracle by glibc.  Hence:
   * a scene that evaluates none of the four (cornell_box: rects, boxes, rotations, solid Lambertian, a light) is
     bit-identical — double radiance, rgb8 and path signatures;
   * other scenes differ by the ULPs of those four functions: the figures are printed and bounded.
