@@ -72,8 +72,11 @@ struct CoopWork {
 // W4: `root` is a node of the 4-wide alternative tree (sc.nodes4, always gated); a visit tests four child boxes,
 // keeps the nearest surviving child and pushes up to three.  Half the chain length of a binary tree: the
 // traversals are bound by their longest chain, not by their work.
+// QU: q_min is the same in every lane (the render bodies' pinned scalar t_min).  The workers then take it from the scalar,
+// and its word of the ray context carries the owner's 1/(d.d) instead: a worker that switches to the ray forms d.d for a
+// sphere leaf as before (five instructions) but no longer divides — the same quotient, computed once by the owner.
 #define RTMI_COOP_INLINE __forceinline__
-template <bool PROF, bool EXT, bool W4, bool INST>
+template <bool PROF, bool EXT, bool W4, bool INST, bool QU = false>
 __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, bool gated, float scale, bool active, const RayF &R,
                                                float time, float q_min, float q_max, const CoopWork &cw,
                                                bool &have, float &t_out, int &pf_out, bool &overflow,
@@ -102,18 +105,20 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
     W.o = f3(0, 0, 0); W.d = f3(0, 0, 1); W.inv_d = f3(0, 0, 0); W.a = 1.0f; W.inv_a = 1.0f;
     float wtime = 0.0f, wqmin = 0.0f, wqmax = 0.0f, wmabs = 0.0f;
     if (active) {
-        // 48 B per ray keeps the wave's LDS under 10 KB; a and inv_a are recomputed by a worker when it
+        // 48 B per ray keeps the wave's LDS under 10 KB; a (and, without QU, inv_a) are recomputed by a worker when it
         // first tests a sphere of this ray (same operations on the same values: bit-identical)
         ctx[lane * 3 + 0] = make_float4(R.o.x, R.o.y, R.o.z, time);
-        ctx[lane * 3 + 1] = make_float4(R.d.x, R.d.y, R.d.z, q_min);
+        ctx[lane * 3 + 1] = make_float4(R.d.x, R.d.y, R.d.z, QU ? R.inv_a : q_min);
         ctx[lane * 3 + 2] = make_float4(R.inv_d.x, R.inv_d.y, R.inv_d.z, q_max);
         cur = (uint32_t)root; ray = lane; cray = lane;
         tent = q_min; // root entry distance: conservative
         W.o = R.o; W.d = R.d; W.inv_d = R.inv_d;
         wtime = time; wqmin = q_min; wqmax = q_max;
+        if (QU) { W.a = R.a; W.inv_a = R.inv_a; aray = lane; }
         wmabs = scale * (1.0f / 8192.0f) *
                 fminf(fminf(__builtin_fabsf(W.inv_d.x), __builtin_fabsf(W.inv_d.y)), __builtin_fabsf(W.inv_d.z));
     }
+    if (QU) wqmin = q_min; // every lane, worker or not: the value stays a scalar
     int top = 0, gtop = 0; // entries in the LDS part / in the spilled (older) part of the stack
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -215,7 +220,8 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
             if (cur != COOP_NONE && ray != cray) { // switch ray context
                 const float4 c0 = ctx[ray * 3 + 0], c1 = ctx[ray * 3 + 1], c2 = ctx[ray * 3 + 2];
                 W.o = f3(c0.x, c0.y, c0.z); wtime = c0.w;
-                W.d = f3(c1.x, c1.y, c1.z); wqmin = c1.w;
+                W.d = f3(c1.x, c1.y, c1.z);
+                if (QU) W.inv_a = c1.w; else wqmin = c1.w;
                 W.inv_d = f3(c2.x, c2.y, c2.z); wqmax = c2.w;
                 // pruning margin scale/8192/|d|, over-estimated (never under: pruning less is always safe) by
                 // 1/|d| <= min_i 1/|d_i| — no division, no square root on a context switch
@@ -265,7 +271,7 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
                 int pf;
                 if (type <= RTMI_PRIM_MSPHERE && aray != ray) { // sphere.rs:40 needs d.d
                     W.a = dot(W.d, W.d);
-                    W.inv_a = 1.0f / W.a;
+                    if (!QU) W.inv_a = 1.0f / W.a;
                     aray = ray;
                 }
                 // the gate box is fetched together with the primitive's planes, not after its test: one memory latency
@@ -344,7 +350,8 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
 // geometry of one item for the whole wavefront: every lane calls it; `active` lanes own a query
 // ONE: the caller knows that every BVH item of the scene carries an alternative tree and that the call walks it
 // (rtmi_onetree.hip): the walk of the reference-topology tree is not compiled, `use_alt` is not read
-template <bool PROF, bool EXT, bool W4, bool INST, bool ONE = false>
+// QU: q_min is wave-uniform (coop_bvh_query)
+template <bool PROF, bool EXT, bool W4, bool INST, bool ONE = false, bool QU = false>
 __device__ __forceinline__ bool geom_query_coop(const DevScene &sc, const rtmi_item &I, bool use_alt, bool active, const RayF &r,
                                                 float time, float q_min, float q_max, const CoopWork &cw,
                                                 float &t_out, int &pf_out, bool &overflow, unsigned long long *prof,
@@ -356,11 +363,11 @@ __device__ __forceinline__ bool geom_query_coop(const DevScene &sc, const rtmi_i
         bool have = false;
         static_assert(!ONE || (EXT && W4), "the one-tree form walks the gated 4-wide tree");
         if constexpr (ONE) {
-            coop_bvh_query<PROF, EXT, W4, INST>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+            coop_bvh_query<PROF, EXT, W4, INST, QU>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
         } else {
         const bool alt = EXT && W4 && use_alt && I.alt_first >= 0; // wave-uniform
-        if (alt) coop_bvh_query<PROF, EXT, W4, INST>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
-        else coop_bvh_query<PROF, EXT, false, INST>(sc, I.first, false, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+        if (alt) coop_bvh_query<PROF, EXT, W4, INST, QU>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+        else coop_bvh_query<PROF, EXT, false, INST, QU>(sc, I.first, false, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
         }
         return have;
     }

@@ -19,6 +19,12 @@
 #define RTMI_COOP_T_MAX RTMI_FLT_MAX
 #define RTMI_COOP_T_DEFAULTED
 #endif
+#ifdef RTMI_COOP_T_DEFAULTED
+    constexpr bool T_MIN_UNIFORM = true; // a render body: the ray context carries 1/(d.d) in q_min's word (coop_bvh_query's QU),
+                                         // 1/(d.d) is pinned before the item loop, the media draw with block-local Philox keys
+#else
+    constexpr bool T_MIN_UNIFORM = false;
+#endif
     constexpr bool INST = INSTL >= 1; // instanced primitives, media inside transforms
     constexpr bool INSD = INSTL >= 2; // DEFERRED items, list scans, nested media
     constexpr bool FEATURES = false; // no feature kernel runs this body
@@ -89,6 +95,11 @@
             int grp_first = 0x7fffffff;    // the index of the SAVE_T0 item (or of the first deferred one), and whether it is the enclosing tree
             bool grp_tree = false;
             if (INSD) park[0] = __float_as_uint(RTMI_FLT_MAX);
+            // 1/(d.d) of the world ray is a result of THIS statement: without the empty asm the compiler folds the join of
+            // W.inv_a with the transformed R.inv_a below into one division of the joined d.d, once per item, although only an
+            // item under a rotation changes the value.  Here, not behind ray_derive: there it costs a spilled mask pair
+            // (DESIGN.md §39)
+            if constexpr (T_MIN_UNIFORM) asm volatile("" : "+v"(W.inv_a)); // (the batch kernels keep the code they had)
             for (uint32_t it = 0; it < n_items; it++) { // executed by all 64 lanes
                 const rtmi_item I = RTMI_UNIFORM_LOAD(rtmi_item, &sc.items[it].it);
                 if (INSD && (I.flags & RTMI_ITEMFLAG_SAVE_T0)) {
@@ -127,7 +138,7 @@
                         reach = need && deferred_gate(sc, I, W, RTMI_COOP_T_MIN, t0_saved);
                         qmax = scan ? __uint_as_float(park[64]) : t0_saved;
                     }
-                    if (geom_query_coop<PROF, EXT, EXT, INST, ONE_TREE>(sc, I, use_alt, reach, R, pa.rtime, RTMI_COOP_T_MIN, qmax, cw, t, pf, overflow, prof, slot)) {
+                    if (geom_query_coop<PROF, EXT, EXT, INST, ONE_TREE, T_MIN_UNIFORM>(sc, I, use_alt, reach, R, pa.rtime, RTMI_COOP_T_MIN, qmax, cw, t, pf, overflow, prof, slot)) {
                         if (scan) {
                             park[64] = __float_as_uint(t); park[128] = it; park[192] = (uint32_t)pf;
                         } else if (!dfi || deferred_bvh_wins(I.count, t, closest, best_item, best_pf, grp_first, grp_tree)) {
@@ -161,7 +172,7 @@
                             if (reach && h1 && h2) h1 = nested_medium_interval(sc, I, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), g, k0, k1, t1, t2);
                         }
                         if (dfr) { // its interval ends at the t_max the BVH was entered with; its hit must beat what the tree found
-                            if (reach && h1 && h2 && medium_sample(t1, t2, RTMI_COOP_T_MIN, t0_saved, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
+                            if (reach && h1 && h2 && medium_sample<T_MIN_UNIFORM>(t1, t2, RTMI_COOP_T_MIN, t0_saved, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
                                 if (scan) { park[64] = __float_as_uint(tm); park[128] = it | 0x80000000u; }
                                 else if (tm < closest) { closest = tm; best_item = (int)it; best_medium = true; }
                             }
@@ -171,7 +182,7 @@
                     if (need && h1 && h2) {
                         // (one square root per medium: sharing it between the media of a query measured -1.1 %,
                         // profiles/r03_experiments/wdn_shared_norm_ab.log)
-                        if (medium_sample(t1, t2, RTMI_COOP_T_MIN, closest, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
+                        if (medium_sample<T_MIN_UNIFORM>(t1, t2, RTMI_COOP_T_MIN, closest, medium_dir_norm<INST>(sc, I.flags, I.xform_first, W), I.neg_inv_density, g, k0, k1, tm)) {
                             closest = tm; best_item = (int)it; best_medium = true;
                         }
                     }

@@ -213,7 +213,11 @@ __global__ void rtmi_philox_probe_kernel(const uint32_t *ctr, const uint32_t *ke
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t o0, o1, o2, o3;
-    philox(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], key[2 * i], key[2 * i + 1], o0, o1, o2, o3);
+    // a wavefront whose cases share one key evaluates the form with block-local round keys (philox<true>, scalar keys only)
+    const uint32_t k0 = key[2 * i], k1 = key[2 * i + 1];
+    const uint32_t u0 = __builtin_amdgcn_readfirstlane(k0), u1 = __builtin_amdgcn_readfirstlane(k1);
+    if (__ballot(k0 != u0 || k1 != u1) == 0ull) philox<true>(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], u0, u1, o0, o1, o2, o3);
+    else philox(ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], k0, k1, o0, o1, o2, o3);
     out[4 * i] = o0; out[4 * i + 1] = o1; out[4 * i + 2] = o2; out[4 * i + 3] = o3;
 }
 // ray-primitive and shading arithmetic exactly as the render kernels call it (rtmi_probe_geom, include/rtmi.h): the

@@ -9,8 +9,16 @@
 // ----------------------------------------------------------------------------------
 // Philox4x32-10; stream = (block, sample, pixel, 0) under key = seed
 // ----------------------------------------------------------------------------------
+// LOCAL: the round keys are formed inside this block, by scalar additions on a copy of the two key registers that the
+// compiler cannot trace back to the kernel's arguments.  The default form lets it form the twenty round keys once per
+// kernel; where they were spilled, a block then restores them lane by lane (v_readlane and its hazard s_nop).  For
+// wave-uniform keys only (an SGPR constraint); the same additions, the same words.
+template <bool LOCAL = false>
 __device__ __forceinline__ void philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                        uint32_t &o0, uint32_t &o1, uint32_t &o2, uint32_t &o3) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (LOCAL) asm volatile("" : "+s"(k0), "+s"(k1));
+#endif
 #pragma unroll
     for (int r = 0; r < 10; r++) {
         // one 32x32->64 multiply per product (v_mad_u64_u32) instead of separate high and low multiplies:
@@ -49,12 +57,13 @@ __device__ __forceinline__ void rng_init(RngRing &g, uint32_t sample, uint32_t p
     g.sample = sample; g.pixel = pixel; g.rd = 0u; g.wr = 0u;
 }
 // all ACTIVE lanes call; afterwards every active lane holds at least n (<= 3) unread words
+template <bool LOCAL = false>
 __device__ __forceinline__ void rng_need(RngRing &g, uint32_t n, uint32_t k0, uint32_t k1) {
     const uint32_t have = g.wr - g.rd;
     if (__ballot(have < n) != 0ull) { // uniform over the active lanes
         if (have <= 4u) {
             uint32_t o0, o1, o2, o3;
-            philox(g.wr >> 2, g.sample, g.pixel, 0u, k0, k1, o0, o1, o2, o3);
+            philox<LOCAL>(g.wr >> 2, g.sample, g.pixel, 0u, k0, k1, o0, o1, o2, o3);
             uint32_t *w = g.ring + ((g.wr & 4u) << 6); // slots 0..3 or 4..7
             w[0] = o0; w[64] = o1; w[128] = o2; w[192] = o3;
             g.wr += 4u;
@@ -67,8 +76,9 @@ __device__ __forceinline__ uint32_t rng_word(RngRing &g) {
     return w;
 }
 // rng.gen::<f64>() of the reference (24-bit uniform, rtmi_u01)
+template <bool LOCAL = false>
 __device__ __forceinline__ float rng_uniform(RngRing &g, uint32_t k0, uint32_t k1) {
-    rng_need(g, 1u, k0, k1);
+    rng_need<LOCAL>(g, 1u, k0, k1);
     return rtmi_u01(rng_word(g));
 }
 __device__ __forceinline__ void rng_take3(RngRing &g, uint32_t k0, uint32_t k1, uint32_t &w0, uint32_t &w1, uint32_t &w2) {
@@ -104,9 +114,10 @@ __device__ __forceinline__ void rng_attach(RngReg &, uint32_t *) {}
 #define RTMI_SEL(c, a, b) ((c) ? (a) : (b))
 
 // rng.gen::<f64>() of the reference (24-bit uniform, rtmi_u01)
+template <bool LOCAL = false>
 __device__ __forceinline__ float rng_uniform(RngReg &g, uint32_t k0, uint32_t k1) {
     if (g.pos == 4) {
-        philox(g.block, g.sample, g.pixel, 0u, k0, k1, g.b0, g.b1, g.b2, g.b3);
+        philox<LOCAL>(g.block, g.sample, g.pixel, 0u, k0, k1, g.b0, g.b1, g.b2, g.b3);
         g.block++;
         g.pos = 0;
     }
@@ -169,9 +180,10 @@ __device__ __forceinline__ void rng_init(RngNee &g, uint32_t sample, uint32_t pi
 __device__ __forceinline__ void rng_attach(RngNee &, uint32_t *) {}
 __device__ __forceinline__ void rng_set_stream(RngNee &g, uint32_t stream) { g.stream = stream; }
 __device__ __forceinline__ void rng_set_stream(RngReg &, uint32_t) {}
+template <bool LOCAL = false>
 __device__ __forceinline__ float rng_uniform(RngNee &g, uint32_t k0, uint32_t k1) {
     if (g.pos == 4) {
-        philox(g.block, g.sample, g.pixel, g.stream, k0, k1, g.b0, g.b1, g.b2, g.b3);
+        philox<LOCAL>(g.block, g.sample, g.pixel, g.stream, k0, k1, g.b0, g.b1, g.b2, g.b3);
         g.block++;
         g.pos = 0;
     }

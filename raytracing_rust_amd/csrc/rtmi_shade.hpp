@@ -318,14 +318,17 @@ __device__ __forceinline__ void listscan_fold(const ListScan &ls, int rank, floa
     const bool wins = ls.medium ? ls.cl < closest : deferred_bvh_wins(rank, ls.cl, closest, best_item, best_pf, grp_first, grp_tree);
     if (wins) { closest = ls.cl; best_item = ls.item; best_pf = ls.pf; best_medium = ls.medium; }
 }
-template <typename RngT>
+// LOCAL: the draw's Philox block forms its round keys itself (philox<true>, rtmi_rng.hpp; wave-uniform keys only: the
+// cooperative kernel's item loop, where the default form restored them from spilled registers for every medium of
+// every round — DESIGN.md §39)
+template <bool LOCAL = false, typename RngT>
 __device__ __forceinline__ bool medium_sample(float t1, float t2, float t_min, float closest, float dn,
                                               float neg_inv_density, RngT &g, uint32_t k0, uint32_t k1, float &t_out) {
     if (t1 < t_min) t1 = t_min;
     if (t2 > closest) t2 = closest;
     if (t1 < t2) {
         const float dist_inside = (t2 - t1) * dn;
-        const float hit_distance = neg_inv_density * rtmi_logf(rng_uniform(g, k0, k1));
+        const float hit_distance = neg_inv_density * rtmi_logf(rng_uniform<LOCAL>(g, k0, k1));
         if (hit_distance < dist_inside) {
             t_out = t1 + hit_distance / dn;
             return true;
