@@ -37,6 +37,7 @@
 #include "rtmi_math.h"
 
 #include "rtmi_kernels.hpp"
+#include "rtmi_render_launch.hpp"
 #include "rtmi_f64_types.hpp"
 #include "rtmi_f64_plan.hpp"
 #include "rtmi_adaptive.h"
@@ -69,106 +70,104 @@
 #include "rtmi_batch_coop_launch.hpp"
 #include "rtmi_frame_launch.hpp"
 #include "rtmi_hostkit.hpp"
+#include "rtmi_host.hpp"
+
+// ======================================================================================
+// the launchers of rtmi_render_launch.hpp: the only place where the kernels of this unit are launched
+// ======================================================================================
+hipError_t rtmi_render_launch(const RenderLaunch &k, uint32_t blocks, hipStream_t stream, const DevScene &sc, const DevCamera &cam,
+                              const DevParams &P) {
+    const dim3 grid(blocks), block(64 * WAVES_PER_BLOCK);
+#define RTMI_LAUNCH(KERN, F, S, PR, LDS) hipLaunchKernelGGL((KERN<F, S, PR>), grid, block, LDS, stream, sc, cam, P)
+#define RTMI_LAUNCH_COOP(S, PR, W, E, I) return rtmi_launch_lds(&rtmi_render_coop<S, PR, W, E, I>, grid, block, k.coop_lds, stream, sc, cam, P)
+    if (k.bcoop) {
+        const dim3 blk(RTMI_BLK_THREADS);
+        if (k.sigf) hipLaunchKernelGGL((rtmi_render_bcoop<true, false>), grid, blk, k.bcoop_lds, stream, sc, cam, P);
+        else hipLaunchKernelGGL((rtmi_render_bcoop<false, false>), grid, blk, k.bcoop_lds, stream, sc, cam, P);
+    } else if (k.coop) {
+        if (k.inst) { // instanced primitives, media inside transforms: their own instantiations (no diagnostics builds)
+            // (with k.prof there is no instantiation: the host has refused that call)
+            // level 2 (DEFERRED items, list scans, nested media; its group state parked in LDS) also serves the scenes that
+            // need level 1 only when they have trees: measured faster there than level 1's own instantiation (forced on
+            // final_scene -5.2 % against -7.8 %, random_spheres -3.4 % / -3.1 %); without trees level 1 is the faster one
+            // (cornell_box -9.5 % against -18 %) — profiles/r04_experiments/inst_levels_ab3_parked.log
+            if (k.insd) {
+                if (k.sigf) RTMI_LAUNCH_COOP(true, false, 4, true, 2);
+                else if (k.ext) RTMI_LAUNCH_COOP(false, false, 4, true, 2);
+                else RTMI_LAUNCH_COOP(false, false, 4, false, 2);
+            } else {
+                RTMI_LAUNCH_COOP(false, false, 4, false, 1);
+            }
+        }
+        else if (k.prof) RTMI_LAUNCH_COOP(false, true, 3, true, 0);
+        else if (k.sigf) RTMI_LAUNCH_COOP(true, false, 4, true, 0);
+        else if (k.wps == 3) RTMI_LAUNCH_COOP(false, false, 3, true, 0);
+        else if (k.wps == 5) RTMI_LAUNCH_COOP(false, false, 5, true, 0);
+        else if (k.one_tree) return rtmi_launch_lds(&rtmi_render_coop<false, false, 4, true, 0, true>, grid, block, k.coop_lds, stream, sc, cam, P);
+        else if (k.ext) RTMI_LAUNCH_COOP(false, false, 4, true, 0);
+        else RTMI_LAUNCH_COOP(false, false, 4, false, 0);
+    } else if (!k.async) {
+        if (k.prof) { if (k.fast) RTMI_LAUNCH(rtmi_render_kernel, true, false, true, 0); else RTMI_LAUNCH(rtmi_render_kernel, false, false, true, 0); }
+        else if (k.fast && k.sigf) RTMI_LAUNCH(rtmi_render_kernel, true, true, false, 0);
+        else if (k.fast) RTMI_LAUNCH(rtmi_render_kernel, true, false, false, 0);
+        else if (k.sigf) RTMI_LAUNCH(rtmi_render_kernel, false, true, false, 0);
+        else RTMI_LAUNCH(rtmi_render_kernel, false, false, false, 0);
+    } else {
+        if (k.prof) { if (k.fast) RTMI_LAUNCH(rtmi_render_async, true, false, true, k.dyn_lds); else RTMI_LAUNCH(rtmi_render_async, false, false, true, k.dyn_lds); }
+        else if (k.fast && k.sigf) RTMI_LAUNCH(rtmi_render_async, true, true, false, k.dyn_lds);
+        else if (k.fast) RTMI_LAUNCH(rtmi_render_async, true, false, false, k.dyn_lds);
+        else if (k.sigf) RTMI_LAUNCH(rtmi_render_async, false, true, false, k.dyn_lds);
+        else RTMI_LAUNCH(rtmi_render_async, false, false, false, k.dyn_lds);
+    }
+#undef RTMI_LAUNCH
+#undef RTMI_LAUNCH_COOP
+    return hipGetLastError();
+}
+
+hipError_t rtmi_render_launch_resolve(hipStream_t stream, const Rad3 *samples, double *partial, rtmi_texel *out, const DevParams &P,
+                                      bool first, bool last, bool progressive) {
+    const uint32_t ntex = P.ntiles_local * 64u;
+    hipLaunchKernelGGL(rtmi_resolve_kernel, dim3((ntex + 255) / 256), dim3(256), 0, stream, samples, partial, out, P, first ? 1 : 0,
+                       last ? 1 : 0, progressive ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t rtmi_render_launch_pass_end(hipStream_t stream, unsigned int *status, unsigned int units, unsigned int pass_spp, bool last) {
+    hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, status, units, pass_spp, last ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t rtmi_render_launch_probe_math(int op, const float *x, const float *y, float *out, uint32_t n) {
+    hipLaunchKernelGGL(rtmi_math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, x, y, out, n);
+    return hipGetLastError();
+}
+
+hipError_t rtmi_render_launch_probe_xform(const rtmi_xform *xf, int count, const float *a, const float *b, float *out, uint32_t n) {
+    hipLaunchKernelGGL(rtmi_xform_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, xf, count, a, b, out, n);
+    return hipGetLastError();
+}
+
+hipError_t rtmi_render_launch_probe_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out, uint32_t n) {
+    hipLaunchKernelGGL(rtmi_philox_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, ctr, key, out, n);
+    return hipGetLastError();
+}
+
+hipError_t rtmi_render_launch_probe_geom(int op, const DevScene &sc, const float *in, float *out, uint32_t n) {
+    hipLaunchKernelGGL(rtmi_geom_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, op, sc, in, out, n);
+    return hipGetLastError();
+}
 
 // ======================================================================================
 // host side of the C ABI
 // ======================================================================================
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) {
-    g_err = msg;
-    return code;
-}
-#define HIP_TRY(expr) RTMI_HIP_TRY("", false, expr, #expr)
-
-// Every piece of device and pinned memory of the handle is an owner of rtmi_hostkit.hpp that knows its size; the members
-// free themselves when rtmi_scene_destroy deletes the handle.
-struct RTMI_HIDDEN rtmi_scene {
-    int device = 0;
-    DevScene dev{};
-    DeviceList allocs;
-    rtmi_scene_desc meta{}; // counts only (pointers nulled)
-    DeviceBuf<double> partial; // f64 radiance sums [local tile][3][64], carried between passes
-    DeviceBuf<Rad3> samples;   // per-sample radiance [local tile][pass samples][64], 12-B slots
-    DeviceBuf<uint2> spill;    // global part of the cooperative traversal stacks [wavefront slot][spill_cap]
-    DeviceBuf<unsigned int> status; // RTMI_STATUS_WORDS device words, see rtmi_types.hpp
-    int slots = 0;                  // CUs x 16: resident wavefronts the render kernels are launched with
-    bool has_alt = false;           // some BVH item carries an alternative tree
-    bool all_alt = false;           // every BVH item does (and there is one): the workgroup-cooperative kernel can run
-    bool all_sphere_media = true;   // every medium item is bounded by one static sphere (RTMI_ITEMFLAG_DEV_MEDIUM_SPHERE; also
-                                    // true without media): with all_alt what the one-tree instantiation asks of a scene
-    uint32_t last_inst = 0;         // RTMI_INST_* of the last plain render enqueued on this handle (rtmi_stats_instantiation)
-    bool needs_insd = false;        // DEFERRED items, list scans, nested media: the INSTL = 2 instantiations (rtmi_kernels.hpp)
-    bool has_deferred = false;      // media that were children of a BVHNode (RTMI_ITEMFLAG_DEFERRED): the asynchronous
-                                    // state-machine kernel does not carry them, RTMI_FLAG_ASYNC then runs the per-lane kernel
-    uint32_t last_kernel = 0;       // RTMI_KERNEL_* of the last render enqueued on this handle (rtmi_stats.kernel)
-    int last_batch_kernel = -1;     // ... of the path kernel of the last batch call (rtmi_batch_coop.h); -1: none yet
-    bool batch_blocking = false;    // the running batch call is a blocking one: it reads its own overflow word (batch_coop_check)
-    // scratch of the blocking host API (grow-only, so a host that renders frame after frame allocates once)
-    DeviceBuf<rtmi_texel> texels;
-    DeviceBuf<unsigned long long> d_sig;
-    DeviceBuf<uint32_t> rr_bounces;    // the bounce plane of the roulette entries (include/rtmi_roulette.h), tiled as d_sig
-    PinnedBuf<rtmi_texel> h_texels;    // pinned host mirror of `texels` (hipHostMalloc: the D2H copy runs at link speed)
-    PinnedBuf<rtmi_texel> h_partial;   // ... and of the partial images rtmi_partial_image fetches (RTMI_FLAG_PROGRESSIVE)
-    // Thread model (rtmi.h): render calls on one handle serialise.  `mu` orders the host side (planning, scratch
-    // (re)allocation, enqueue, and for the blocking calls the wait and the copy-out); `busy` chains the device side: a
-    // render enqueued on ANY stream first waits for the previous render of this handle, whose kernels use the same
-    // unit queue, status words and per-sample buffer.
-    std::mutex mu;
-    DeviceEvent busy;
-    bool busy_recorded = false;
-    DeviceStream stream;      // launches of the blocking API (non-blocking stream)
-    DeviceStream copy_stream; // progress polls while a launch runs
-    uint64_t units_total = 0; // work units of the last enqueued call (progress denominator)
-    DeviceEvent ev[3];
-    // f64 render mode (include/rtmi_f64.h): the attached double planes on the device, freed with the handle
-    bool has_f64 = false;
-    DevSceneF64 f64{};
-    DeviceList f64_allocs;
-    DeviceBuf<double> f64_samples; // the f64 mode's per-sample buffer (grow-only, at most RTMI_F64_MAX_BUFFER_BYTES)
-    // adaptive sampling (include/rtmi_adaptive.h), grow-only, freed with the handle: sum | m | M2 per pixel and channel,
-    // two active-tile lists and their count word, the standard errors and counts of the retired tiles
-    DeviceBuf<double> ad_state;   // [tile][9][64]
-    DeviceBuf<uint32_t> ad_lists; // [2][tiles] + count
-    DeviceBuf<float> ad_stderr;   // [tile][64][3]
-    DeviceBuf<uint32_t> ad_spp;   // [tile][64]
-    PinnedBuf<uint32_t> h_ad_count; // pinned: the active count read back after every step
-    // first-hit features (include/rtmi_features.h), grow-only, freed with the handle: the f64 sums carried between passes
-    // and the four output planes
-    DeviceBuf<double> ft_state; // [tile][8][64]
-    DeviceBuf<float> ft_planes; // albedo [ny*nx*3] | normal [ny*nx*3] | depth [ny*nx] | hits [ny*nx] (uint32)
-    // ray queries (include/rtmi_query.h), grow-only, freed with the handle: the device copies of a host-form batch
-    DeviceBuf<float4> q_rays;   // [n][2]
-    DeviceBuf<float> q_time;    // [n]
-    DeviceBuf<float4> q_out;    // trace: [n][3] hit records; occluded: [n] bytes
-    DeviceBuf<uint32_t> q_flip_gaps; // rtmi_scene_attach_flips: [n_prims] | [n_items], or empty
-    // radiance queries (include/rtmi_radiance.h), grow-only, freed with the handle: the per-sample buffer and the two
-    // per-ray outputs of a host-form batch (its rays go through q_rays and q_time); the chunk counter of the persistent
-    // wavefronts is the word behind the status words
-    DeviceBuf<Rad3> rad_samples; // [n][spp]
-    DeviceBuf<float> rad_out;    // mean [n][3] | stderr [n][3]
-    DeviceBuf<char> px_mem;      // per-pixel adaptive sampling, blocking form: scratch | linear | stderr | spp | rgb8
-    // next-event estimation (include/rtmi_nee.h): the attached light table and per-primitive light index, freed with the
-    // handle
-    bool has_lights = false;
-    DeviceBuf<NeeLight> nee_lights;    // [max(n, 1)]
-    DeviceBuf<int32_t> nee_prim_light; // [max(n_prims, 1)]
-    uint32_t nee_n = 0;
-    // light tree (include/rtmi_light_tree.h): the attached nodes (64-B aligned pairs) and paths, freed with the handle
-    bool has_light_tree = false;
-    DeviceBuf<float4> lt_nodes; // [max(lt_n, 2)][2]
-    DeviceBuf<uint2> lt_paths;  // [max(lt_n / 2, 1)]
-    uint32_t lt_n = 0;          // slots: 2 * lights
-    // environment lighting (include/rtmi_env.h): the attached map and its tables, freed with the handle
-    bool has_env = false;
-    DeviceBuf<float4> env_texels; // [h][w] {r, g, b, 0}
-    DeviceBuf<float> env_tables;  // row_cdf [h] | row_p [h] | col_cdf [h][w] | col_p [h][w]
-    uint32_t env_w = 0, env_h = 0;
-    bool env_sampled = false;     // the map's total weight is > 0
-};
 
 extern "C" const char *rtmi_last_error(void) { return g_err.c_str(); }
 // the message rtmi_last_error returns, set by the entry points of the other translation units (rtmi_denoise.hip)
-RTMI_HIDDEN int rtmi_fail(int code, const char *msg) { return fail(code, msg); }
+RTMI_HIDDEN int rtmi_fail(int code, const char *msg) {
+    g_err = msg;
+    return code;
+}
 
 #ifndef RTMI_BUILD_HASH
 #define RTMI_BUILD_HASH "unknown"
@@ -247,7 +246,7 @@ static int upload(rtmi_scene *s, const T *src, size_t n, const T **dst) {
     return RTMI_OK;
 }
 
-static int validate(const rtmi_scene_desc *d) {
+int validate(const rtmi_scene_desc *d) {
     if (!d) return fail(RTMI_ERR_INVALID, "desc is NULL");
     if (d->abi_version != RTMI_ABI_VERSION) return fail(RTMI_ERR_INVALID, "abi_version mismatch");
     if (d->n_items == 0 || !d->items) return fail(RTMI_ERR_INVALID, "scene has no items");
@@ -602,19 +601,12 @@ extern "C" void rtmi_scene_destroy(rtmi_scene *s) {
     delete s;
 }
 
-static inline uint32_t tiles_x_of(const rtmi_render_params *p) { return (p->nx + RTMI_TILE - 1) / RTMI_TILE; }
-static inline uint32_t tiles_y_of(const rtmi_render_params *p) { return (p->ny + RTMI_TILE - 1) / RTMI_TILE; }
-static inline uint32_t local_tiles_of(const rtmi_render_params *p, uint32_t rank) {
-    const uint32_t T = tiles_x_of(p) * tiles_y_of(p);
-    return rank < T ? (T - rank + p->tile_world - 1) / p->tile_world : 0;
-}
-
 extern "C" uint32_t rtmi_local_tiles(const rtmi_render_params *p) {
     if (!p || p->tile_world == 0) return 0;
     return local_tiles_of(p, p->tile_rank);
 }
 
-static int check_params(const rtmi_render_params *p) {
+int check_params(const rtmi_render_params *p) {
     if (!p) return fail(RTMI_ERR_INVALID, "params is NULL");
     if (p->nx == 0 || p->ny == 0 || p->ns == 0) return fail(RTMI_ERR_INVALID, "nx, ny and ns must be positive");
     if ((uint64_t)p->nx * p->ny > 0xffffffffull) return fail(RTMI_ERR_UNSUPPORTED, "image too large");
@@ -623,42 +615,21 @@ static int check_params(const rtmi_render_params *p) {
     return RTMI_OK;
 }
 
-// ---- host-side plumbing shared by the render entry points ------------------------------------------------------------
-// records the end of a call's work on `st` on every return path after its first enqueue (thread model: `busy`)
-struct BusyMark {
-    rtmi_scene *s;
-    hipStream_t st;
-    ~BusyMark() { if (s && hipEventRecord(s->busy.e, st) == hipSuccess) s->busy_recorded = true; } // s = NULL: no call begun
-};
-
-// Grow-only device buffer of the handle: reallocated when a call needs more than it holds.  A render of this handle
-// enqueued asynchronously (rtmi_render_device) may still use the old buffer: it is released after that render.
-template <typename T>
-static int grow(rtmi_scene *s, DeviceBuf<T> &buf, size_t want) {
-    if (want <= buf.bytes) return RTMI_OK;
-    if (buf.ptr) {
-        if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
-        HIP_TRY(buf.release());
-    }
-    HIP_TRY(buf.alloc(want));
-    return RTMI_OK;
-}
-
 // pinned host mirror of a texel buffer (grow-only)
-static int grow_host_texels(PinnedBuf<rtmi_texel> &h, size_t ntex) {
+int grow_host_texels(PinnedBuf<rtmi_texel> &h, size_t ntex) {
     HIP_TRY(h.grow(ntex * sizeof(rtmi_texel)));
     return RTMI_OK;
 }
 
 // the handle's framebuffer for `ntex` texels and its pinned host mirror
-static int reserve_texels(rtmi_scene *s, size_t ntex) {
+int reserve_texels(rtmi_scene *s, size_t ntex) {
     if (int rc = grow(s, s->texels, ntex * sizeof(rtmi_texel))) return rc;
     return grow_host_texels(s->h_texels, ntex);
 }
 
 // adaptive sampling's buffers (include/rtmi_adaptive.h; NEE shares them), grown together for T tiles.  Each knows its own
 // size and is empty after a failed allocation, so a call goes on only when all four hold T tiles.
-static int grow_adaptive(rtmi_scene *s, uint32_t T) {
+int grow_adaptive(rtmi_scene *s, uint32_t T) {
     const size_t tiles = T;
     int rc;
     if ((rc = grow(s, s->ad_state, tiles * 64 * 9 * sizeof(double))) || (rc = grow(s, s->ad_lists, (2 * tiles + 1) * sizeof(uint32_t))) ||
@@ -675,7 +646,7 @@ static int list_all_tiles(rtmi_scene *s, uint32_t T, hipStream_t stream) {
     return RTMI_OK;
 }
 
-static int ensure_streams(rtmi_scene *s) {
+int ensure_streams(rtmi_scene *s) {
     if (!s->stream.s) HIP_TRY(hipStreamCreateWithFlags(&s->stream.s, hipStreamNonBlocking));
     if (!s->copy_stream.s) {
         // The progress polls must not queue behind the render.  The runtime gives streams at most GPU_MAX_HW_QUEUES
@@ -690,7 +661,7 @@ static int ensure_streams(rtmi_scene *s) {
 
 // start of a blocking call on the handle's own stream (the caller holds s->mu and has selected s->device): no earlier
 // render of this handle may still run, the buffers of the call may be reallocated
-static int begin_blocking(rtmi_scene *s) {
+int begin_blocking(rtmi_scene *s) {
     if (int rc = ensure_streams(s)) return rc;
     if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
     return RTMI_OK;
@@ -710,7 +681,7 @@ static int replace_attached(rtmi_scene *s, bool *flag, Fill &&fill, Old &...old)
 }
 
 // argument checks of the whole-image modes (adaptive sampling, features, NEE) after their NULL checks, in this order
-static int check_mode_params(const rtmi_render_params *p, uint32_t accepted, const char *flags_msg, const char *world_msg) {
+int check_mode_params(const rtmi_render_params *p, uint32_t accepted, const char *flags_msg, const char *world_msg) {
     if (int rc = check_params(p)) return rc;
     if (p->flags & ~accepted) return fail(RTMI_ERR_UNSUPPORTED, flags_msg);
     if (p->tile_world != 1) return fail(RTMI_ERR_UNSUPPORTED, world_msg);
@@ -760,7 +731,7 @@ static DevParams dev_params(const rtmi_scene *s, const rtmi_render_params *p) {
 #endif
 // Traversal plan of the BVH-walking kernels: P.use_alt, P.spill_cap, P.coop_cap and P.spill (grown when the kernel is
 // the cooperative one); `ext` = the extended instantiation of the cooperative kernel.
-static int plan_traversal(rtmi_scene *s, const rtmi_render_params *p, bool coop, DevParams &P, bool &ext) {
+int plan_traversal(rtmi_scene *s, const rtmi_render_params *p, bool coop, DevParams &P, bool &ext) {
     // LDS part of the traversal stack: 512 entries cover the deepest stack ever seen on the reference scenes
     // (447); deeper stacks continue in global memory (64 * (depth + 2) entries per wavefront, the bound of the
     // depth-first order), so the LDS footprint (7.7 KB per wavefront) does not depend on the tree depth
@@ -786,7 +757,7 @@ static int plan_traversal(rtmi_scene *s, const rtmi_render_params *p, bool coop,
 
 // Pass protocol of the status words (rtmi_types.hpp), which progress reporting reads: a call starts with its overflow
 // word, the unit counter and the finished-units / finished-samples words at zero (the sticky word stays) ...
-static int begin_passes(rtmi_scene *s, hipStream_t stream) {
+int begin_passes(rtmi_scene *s, hipStream_t stream) {
     HIP_TRY(hipMemsetAsync(s->status.ptr, 0, 2 * sizeof(unsigned int), stream));
     HIP_TRY(hipMemsetAsync(s->status.ptr + 3, 0, 2 * sizeof(unsigned int), stream));
     s->units_total = 0;
@@ -801,35 +772,8 @@ static int units_done(rtmi_scene *s, uint64_t *units) { // read through the copy
     return RTMI_OK;
 }
 
-struct PassCounts { uint32_t blocks = 0, chunks = 0; };
-// Samples [s0, s0 + count) of P.ntiles_local tiles in passes of P.pass_stride (the plan of plan_and_reserve): sets the
-// pass fields of P, calls launch(blocks, first, last) for the mode's render and resolve of each pass and ends the pass.
-// A pass of n items runs on min(ceil(n / items_per_block), max_blocks) blocks.  `finish`: the last pass ends the call
-// (it adds the call's overflows to the sticky word that rtmi_scene_status reports).
-template <typename Launch>
-static int run_passes(rtmi_scene *s, DevParams &P, hipStream_t stream, uint32_t s0, uint32_t count, bool finish,
-                      uint64_t max_blocks, uint32_t items_per_block, PassCounts &counts, Launch &&launch) {
-    for (uint32_t k = 0; k < count; k += P.pass_stride) { // one pass unless the per-sample buffer is smaller than count samples
-        P.pass_s0 = s0 + k;
-        P.pass_cnt = count - k < P.pass_stride ? count - k : P.pass_stride;
-        P.nchunks = (P.pass_cnt + P.chunk_spp - 1) / P.chunk_spp;
-        const uint64_t nitems = (uint64_t)P.ntiles_local * P.nchunks;
-        if (nitems > 0x7fffffffull) return fail(RTMI_ERR_UNSUPPORTED, "too many (tile, chunk) items in one pass");
-        const uint64_t nblocks = (nitems + items_per_block - 1) / items_per_block;
-        const uint32_t blocks = (uint32_t)(nblocks < max_blocks ? nblocks : max_blocks);
-        counts.blocks += blocks; counts.chunks += P.nchunks;
-        s->units_total += nitems;
-        const bool last = k + P.pass_cnt >= count;
-        if (int rc = launch(blocks, k == 0, last)) return rc;
-        hipLaunchKernelGGL(rtmi_pass_end_kernel, dim3(1), dim3(1), 0, stream, s->status.ptr, (unsigned int)nitems, P.pass_cnt,
-                           finish && last ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-    }
-    return RTMI_OK;
-}
-
 // this call's overflow word of a scene whose kernels have finished
-static int check_overflow(rtmi_scene *s) {
+int check_overflow(rtmi_scene *s) {
     unsigned int st = 0;
     HIP_TRY(hipMemcpy(&st, s->status.ptr, sizeof(st), hipMemcpyDeviceToHost));
     if (st != 0) {
@@ -838,8 +782,8 @@ static int check_overflow(rtmi_scene *s) {
     }
     return RTMI_OK;
 }
-static void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, float ms_render, float ms_all,
-                       PassCounts counts = {}) {
+void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, float ms_render, float ms_all,
+                       PassCounts counts) {
     stats->render_ms = ms_render;
     stats->kernel_ms = ms_all;
     // samples actually traced: pixels inside the image that belong to local tiles
@@ -858,7 +802,7 @@ static void fill_stats(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *s
     if (p->flags & RTMI_KNOB_REPORT_INST) stats->kernel |= s->last_inst << 8;
 }
 // the same from the scene's events: ev[0] start, ev[1] before the last resolve, ev[2] end (all completed)
-static int fill_stats_from_events(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, PassCounts counts = {}) {
+int fill_stats_from_events(rtmi_scene *s, const rtmi_render_params *p, rtmi_stats *stats, PassCounts counts) {
     float ms_r = 0.f, ms_all = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms_r, s->ev[0].e, s->ev[1].e));
     HIP_TRY(hipEventElapsedTime(&ms_all, s->ev[0].e, s->ev[2].e));
@@ -866,31 +810,10 @@ static int fill_stats_from_events(rtmi_scene *s, const rtmi_render_params *p, rt
     return RTMI_OK;
 }
 
-// Tiled -> row-major image of N components per pixel (whole-image calls): texel = tile * 64 + ly * 8 + lx, tiles
-// counted from the top-left; row 0 of the output = top row
-template <int N, typename T, typename U>
-static void untile_to(const rtmi_render_params *p, const T *tiled, U *out) {
-    const uint32_t txn = tiles_x_of(p);
-    for (uint32_t row = 0; row < p->ny; row++)
-        for (uint32_t px = 0; px < p->nx; px++) {
-            const size_t k = (size_t)((row / RTMI_TILE) * txn + px / RTMI_TILE) * 64 + (row % RTMI_TILE) * RTMI_TILE + px % RTMI_TILE;
-            const size_t o = (size_t)row * p->nx + px;
-            for (int c = 0; c < N; c++) out[o * N + c] = tiled[k * N + c];
-        }
-}
-// ... of a device buffer of `ntex` texels
-template <int N, typename T, typename U>
-static int download_untiled(const rtmi_render_params *p, const T *d_tiled, size_t ntex, U *out) {
-    std::vector<T> h(ntex * N);
-    HIP_TRY(hipMemcpy(h.data(), d_tiled, h.size() * sizeof(T), hipMemcpyDeviceToHost));
-    untile_to<N>(p, h.data(), out);
-    return RTMI_OK;
-}
-
 // Plan of one render call: unit size, samples per pass; (re)allocates the per-sample buffer and the f64 sums.
 // slot_bytes: the size of one per-sample slot (rtmi_render_features stores 32-B FeatSlots).
-static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t ntiles_local, uint32_t &chunk_spp,
-                            uint32_t &pass_ns, size_t slot_bytes = RTMI_SAMPLE_SLOT_BYTES) {
+int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t ntiles_local, uint32_t &chunk_spp,
+                            uint32_t &pass_ns, size_t slot_bytes) {
     // ---- per-sample buffer and passes.  Every finished path stores its radiance (12 B) in
     // samples[local tile][sample of the pass][pixel]; the resolve kernel adds them in sample order.  With
     // 288 GB of HBM the whole sample range normally fits (headline: 25 GB); otherwise the range is rendered
@@ -947,7 +870,7 @@ static int plan_and_reserve(rtmi_scene *s, const rtmi_render_params *p, uint32_t
 
 // (Re)allocates what a render with these parameters needs BEFORE the caller starts its event clock: an allocation of tens
 // of GB can stall the host for seconds (see g_parked), and the kernel_ms of rtmi_stats are kernel time.  The caller holds s->mu.
-static int reserve_before_clock(rtmi_scene *s, const rtmi_render_params *p) {
+int reserve_before_clock(rtmi_scene *s, const rtmi_render_params *p) {
     const uint32_t ntiles_local = local_tiles_of(p, p->tile_rank);
     if (ntiles_local == 0) return RTMI_OK;
     if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e)); // the buffer may be reallocated: no render may still use it
@@ -965,7 +888,7 @@ extern "C" int rtmi_render_prepare(rtmi_scene *s, const rtmi_render_params *p) {
 }
 
 // the enqueue itself; the caller holds s->mu
-static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, void *d_texels,
+int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p, void *d_texels,
                                 void *stream_, rtmi_stats *stats) {
     if (!s || !cam || !d_texels) return fail(RTMI_ERR_INVALID, "NULL argument");
     int rc = check_params(p);
@@ -998,7 +921,6 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
 
     if (stats) HIP_TRY(hipEventRecord(s->ev[0].e, stream));
     const bool fast = (p->flags & RTMI_FLAG_FAST_CULL) != 0u && boxes_valid(s, cam), sigf = (p->flags & RTMI_FLAG_PATH_SIG) != 0u;
-    const dim3 block(64 * WAVES_PER_BLOCK);
     const size_t dyn_lds = (size_t)WAVES_PER_BLOCK * 2u * P.stack_depth * 64u * sizeof(uint32_t);
     const bool prof = (p->flags & RTMI_FLAG_PROFILE) != 0u, sync = (p->flags & RTMI_FLAG_SYNC) != 0u;
     if (prof) {
@@ -1041,66 +963,21 @@ static int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtm
     s->last_inst = !coop || bcoop ? RTMI_INST_NONE : one_tree ? RTMI_INST_COOP_ONE_TREE : RTMI_INST_COOP_GENERAL;
     const bool insd = inst && (s->needs_insd || ext || sigf); // the level-2 instantiations (below) park their group state in LDS
     const size_t coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{P.coop_cap, ext, insd}.words() * sizeof(uint32_t);
-    const uint32_t ntex = P.ntiles_local * 64u;
     // two-phase kernels: persistent wavefronts that take units from the queue; async kernel: one block per unit
     // (workgroup-cooperative kernel: resident workgroups of RTMI_BLK_WAVES wavefronts; every wavefront takes units)
     const uint64_t max_blocks = async ? ~0ull : bcoop ? run_slots / RTMI_BLK_WAVES : run_slots;
+    const RenderLaunch launch{bcoop, coop, async, inst, insd, prof, sigf, fast, ext, one_tree, wps_req, coop_lds, bcoop_lds, dyn_lds};
     PassCounts counts;
     rc = run_passes(s, P, stream, 0, p->ns, true, max_blocks, async ? WAVES_PER_BLOCK : 1u, counts,
                     [&](uint32_t blocks, bool first, bool last) -> int {
-    const dim3 grid(blocks);
-#define RTMI_LAUNCH(KERN, F, S, PR, LDS) hipLaunchKernelGGL((KERN<F, S, PR>), grid, block, LDS, stream, s->dev, C, P)
-#define RTMI_LAUNCH_COOP(S, PR, W, E, I) \
-    HIP_TRY(rtmi_launch_lds(&rtmi_render_coop<S, PR, W, E, I>, grid, block, coop_lds, stream, s->dev, C, P))
-    if (bcoop) {
-        const dim3 blk(RTMI_BLK_THREADS);
-        if (sigf) hipLaunchKernelGGL((rtmi_render_bcoop<true, false>), grid, blk, bcoop_lds, stream, s->dev, C, P);
-        else hipLaunchKernelGGL((rtmi_render_bcoop<false, false>), grid, blk, bcoop_lds, stream, s->dev, C, P);
-    } else if (coop) {
-        const uint32_t wps = wps_req;
-        if (inst) { // instanced primitives, media inside transforms: their own instantiations (no diagnostics builds)
-            if (prof) return fail(RTMI_ERR_UNSUPPORTED, "the profiling build has no instantiation for instanced primitives / media inside transforms");
-            // level 2 (DEFERRED items, list scans, nested media; its group state parked in LDS) also serves the scenes that
-            // need level 1 only when they have trees: measured faster there than level 1's own instantiation (forced on
-            // final_scene -5.2 % against -7.8 %, random_spheres -3.4 % / -3.1 %); without trees level 1 is the faster one
-            // (cornell_box -9.5 % against -18 %) — profiles/r04_experiments/inst_levels_ab3_parked.log
-            if (insd) {
-                if (sigf) RTMI_LAUNCH_COOP(true, false, 4, true, 2);
-                else if (ext) RTMI_LAUNCH_COOP(false, false, 4, true, 2);
-                else RTMI_LAUNCH_COOP(false, false, 4, false, 2);
-            } else {
-                RTMI_LAUNCH_COOP(false, false, 4, false, 1);
-            }
-        }
-        else if (prof) RTMI_LAUNCH_COOP(false, true, 3, true, 0);
-        else if (sigf) RTMI_LAUNCH_COOP(true, false, 4, true, 0);
-        else if (wps == 3) RTMI_LAUNCH_COOP(false, false, 3, true, 0);
-        else if (wps == 5) RTMI_LAUNCH_COOP(false, false, 5, true, 0);
-        else if (one_tree) HIP_TRY(rtmi_launch_lds(&rtmi_render_coop<false, false, 4, true, 0, true>, grid, block, coop_lds, stream, s->dev, C, P));
-        else if (ext) RTMI_LAUNCH_COOP(false, false, 4, true, 0);
-        else RTMI_LAUNCH_COOP(false, false, 4, false, 0);
-    } else if (!async) {
-        if (prof) { if (fast) RTMI_LAUNCH(rtmi_render_kernel, true, false, true, 0); else RTMI_LAUNCH(rtmi_render_kernel, false, false, true, 0); }
-        else if (fast && sigf) RTMI_LAUNCH(rtmi_render_kernel, true, true, false, 0);
-        else if (fast) RTMI_LAUNCH(rtmi_render_kernel, true, false, false, 0);
-        else if (sigf) RTMI_LAUNCH(rtmi_render_kernel, false, true, false, 0);
-        else RTMI_LAUNCH(rtmi_render_kernel, false, false, false, 0);
-    } else {
-        if (prof) { if (fast) RTMI_LAUNCH(rtmi_render_async, true, false, true, dyn_lds); else RTMI_LAUNCH(rtmi_render_async, false, false, true, dyn_lds); }
-        else if (fast && sigf) RTMI_LAUNCH(rtmi_render_async, true, true, false, dyn_lds);
-        else if (fast) RTMI_LAUNCH(rtmi_render_async, true, false, false, dyn_lds);
-        else if (sigf) RTMI_LAUNCH(rtmi_render_async, false, true, false, dyn_lds);
-        else RTMI_LAUNCH(rtmi_render_async, false, false, false, dyn_lds);
-    }
-#undef RTMI_LAUNCH
-#undef RTMI_LAUNCH_COOP
-    HIP_TRY(hipGetLastError());
-    if (stats && last) HIP_TRY(hipEventRecord(s->ev[1].e, stream));
-    hipLaunchKernelGGL(rtmi_resolve_kernel, dim3((ntex + 255) / 256), dim3(256), 0, stream, s->samples.ptr, s->partial.ptr,
-                       reinterpret_cast<rtmi_texel *>(d_texels), P, first ? 1 : 0, last ? 1 : 0,
-                       (p->flags & RTMI_FLAG_PROGRESSIVE) ? 1 : 0);
-    return RTMI_OK;
-    });
+                        // instanced primitives, media inside transforms: their own instantiations (no diagnostics builds)
+                        if (!bcoop && coop && inst && prof) return fail(RTMI_ERR_UNSUPPORTED, "the profiling build has no instantiation for instanced primitives / media inside transforms");
+                        HIP_TRY(rtmi_render_launch(launch, blocks, stream, s->dev, C, P));
+                        if (stats && last) HIP_TRY(hipEventRecord(s->ev[1].e, stream));
+                        HIP_TRY(rtmi_render_launch_resolve(stream, s->samples.ptr, s->partial.ptr, reinterpret_cast<rtmi_texel *>(d_texels), P,
+                                                           first, last, (p->flags & RTMI_FLAG_PROGRESSIVE) != 0u));
+                        return RTMI_OK;
+                    });
     if (rc || !stats) return rc;
     HIP_TRY(hipEventRecord(s->ev[2].e, stream));
     HIP_TRY(hipEventSynchronize(s->ev[2].e));
@@ -1166,7 +1043,7 @@ extern "C" int rtmi_untile(const rtmi_render_params *p, const rtmi_texel *g, flo
 // ---- blocking host API ---------------------------------------------------------------------------------
 // Waits for `done_ev` of every listed scene; meanwhile (about every 50 ms) reads the devices' unit counters through
 // their copy streams and reports progress to the caller's callback — what src/progressbar.rs:6-58 only pretends to.
-static int wait_with_progress(rtmi_scene *const *scenes, hipEvent_t *done_ev, uint32_t n, const rtmi_render_params *p) {
+int wait_with_progress(rtmi_scene *const *scenes, hipEvent_t *done_ev, uint32_t n, const rtmi_render_params *p) {
     rtmi_progress_fn fn = reinterpret_cast<rtmi_progress_fn>(static_cast<uintptr_t>(p->progress_fn));
     void *user = reinterpret_cast<void *>(static_cast<uintptr_t>(p->progress_user));
     uint64_t total = 0;
@@ -1282,277 +1159,6 @@ extern "C" int rtmi_partial_image(rtmi_scene *s, const rtmi_render_params *p_in,
     return rtmi_untile(&p, s->h_partial.ptr, out_linear, out_rgb8);
 }
 
-// ---- several GPUs of this process behind one handle: scene replicated, tiles t % n, one gather on devices[0] -----
-// RCCL is bound lazily (dlopen) so that single-GPU users of librtmi.so do not load it; inside a PyTorch process the
-// soname resolves to the copy torch already mapped.
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    int (*CommInitAll)(void **, int, const int *) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    int (*GroupStart)() = nullptr;
-    int (*GroupEnd)() = nullptr;
-    int (*Gather)(const void *, void *, size_t, int, int, void *, hipStream_t) = nullptr; // rccl.h ncclGather
-    const char *(*GetErrorString)(int) = nullptr;
-    std::string err;
-    bool load() {
-        if (lib) return true;
-        for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (lib) break;
-        }
-        if (!lib) { err = std::string("dlopen(librccl.so.1): ") + (dlerror() ? dlerror() : "not found"); return false; }
-        CommInitAll = reinterpret_cast<decltype(CommInitAll)>(dlsym(lib, "ncclCommInitAll"));
-        CommDestroy = reinterpret_cast<decltype(CommDestroy)>(dlsym(lib, "ncclCommDestroy"));
-        GroupStart = reinterpret_cast<decltype(GroupStart)>(dlsym(lib, "ncclGroupStart"));
-        GroupEnd = reinterpret_cast<decltype(GroupEnd)>(dlsym(lib, "ncclGroupEnd"));
-        Gather = reinterpret_cast<decltype(Gather)>(dlsym(lib, "ncclGather"));
-        GetErrorString = reinterpret_cast<decltype(GetErrorString)>(dlsym(lib, "ncclGetErrorString"));
-        if (!CommInitAll || !CommDestroy || !GroupStart || !GroupEnd || !Gather || !GetErrorString) {
-            err = "librccl lacks one of ncclCommInitAll/ncclCommDestroy/ncclGroupStart/ncclGroupEnd/ncclGather/ncclGetErrorString";
-            dlclose(lib); lib = nullptr;
-            return false;
-        }
-        return true;
-    }
-};
-RcclApi g_rccl;
-std::mutex g_rccl_mutex;
-// Communicator sets are expensive to make (ncclCommInitAll) and RCCL allows ONE thread at a time to enqueue on a
-// communicator: a set belongs to exactly one rtmi_multi handle while that handle lives (checked out at create,
-// handed back at destroy) and is kept for the next handle on the same device list afterwards, so that one-shot
-// calls (rtmi_render_multi) do not pay the initialisation per image and two live handles on one device list never
-// share communicators.  Sets live for the process lifetime.
-struct CommSet {
-    std::vector<void *> comms;
-    bool busy = false;
-};
-std::map<std::vector<int>, std::vector<CommSet *>> g_comm_pool;
-// RTMI_FORCE_RCCL=1 (environment, read at every rtmi_multi_create): also a ONE-entry device list gets a communicator,
-// so that the whole collective path — dlopen, ncclCommInitAll, grouped ncclGather on the render stream — runs on a
-// single GPU (tests, and bench.py's abi_multi leg at N = 1).  Without it a one-device handle needs no exchange.
-bool force_rccl() {
-    const char *e = getenv("RTMI_FORCE_RCCL");
-    return e && *e && *e != '0';
-}
-} // namespace
-#define RCCL_TRY(expr)                                                                                        \
-    do {                                                                                                      \
-        int r_ = (expr);                                                                                      \
-        if (r_ != 0) return fail(RTMI_ERR_DEVICE, std::string(#expr) + ": " + g_rccl.GetErrorString(r_));     \
-    } while (0)
-
-// The persistent multi-device handle.  Everything a render needs between calls lives here; rtmi_multi_render only
-// enqueues kernels and the one gather, waits, copies the gathered framebuffer out and un-tiles it.
-struct RTMI_HIDDEN rtmi_multi {
-    std::vector<int> devices;
-    bool distinct = true;
-    std::vector<rtmi_scene *> scenes;    // one per listed device (a device listed twice holds two scenes)
-    std::vector<DeviceBuf<rtmi_texel>> texels; // per device: tile-packed local framebuffer (grow-only)
-    DeviceBuf<rtmi_texel> gathered;      // on devices[0]: n x stride texels, rank-major
-    PinnedBuf<rtmi_texel> h_gathered;    // its pinned host mirror
-    CommSet *commset = nullptr;          // RCCL communicators (distinct devices; n > 1 or RTMI_FORCE_RCCL), checked out at create
-    std::mutex mu;                       // render calls on one handle serialise (rtmi.h, thread model)
-};
-
-extern "C" void rtmi_multi_destroy(rtmi_multi *m) {
-    if (!m) return;
-    for (size_t i = 0; i < m->texels.size(); i++) // each device's buffer is released with that device selected
-        if (m->texels[i].ptr) { (void)hipSetDevice(m->devices[i]); (void)m->texels[i].release(); }
-    if (m->gathered.ptr) { (void)hipSetDevice(m->devices[0]); (void)m->gathered.release(); }
-    for (rtmi_scene *s : m->scenes) rtmi_scene_destroy(s);
-    if (m->commset) { // back to the pool: the next handle on this device list takes it over
-        std::lock_guard<std::mutex> lock(g_rccl_mutex);
-        m->commset->busy = false;
-    }
-    delete m;
-}
-
-extern "C" int rtmi_multi_create(const rtmi_scene_desc *desc, const int *devices, uint32_t n, rtmi_multi **out) {
-    if (!out) return fail(RTMI_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!desc || !devices || n == 0) return fail(RTMI_ERR_INVALID, "NULL argument or empty device list");
-    int rc = validate(desc);
-    if (rc) return rc;
-    const int ndev = rtmi_device_count();
-    if (ndev <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available (the rtmi path has no CPU fallback)");
-    rtmi_multi *m = new (std::nothrow) rtmi_multi();
-    if (!m) return fail(RTMI_ERR_NOMEM, "out of host memory");
-    struct Guard { rtmi_multi *m; ~Guard() { if (m) rtmi_multi_destroy(m); } } guard{m};
-    for (uint32_t i = 0; i < n; i++) {
-        if (devices[i] < 0 || devices[i] >= ndev) return fail(RTMI_ERR_INVALID, "device index out of range");
-        for (uint32_t k = 0; k < i; k++) m->distinct = m->distinct && devices[k] != devices[i];
-    }
-    m->devices.assign(devices, devices + n);
-    m->scenes.assign(n, nullptr);
-    m->texels = std::vector<DeviceBuf<rtmi_texel>>(n);
-    // uploads to all devices at once: one host thread per device (hipMalloc / hipMemcpy of one device do not wait for
-    // another's; the derived records — leaf, shading, pool-encoded nodes — are built per thread as well)
-    std::vector<int> rcs(n, RTMI_OK);
-    std::vector<std::string> errs(n);
-    {
-        std::vector<std::thread> th;
-        for (uint32_t i = 0; i < n; i++)
-            th.emplace_back([&, i]() {
-                rcs[i] = rtmi_scene_create(desc, devices[i], &m->scenes[i]);
-                if (rcs[i] == RTMI_OK) {
-                    (void)hipSetDevice(devices[i]);
-                    rcs[i] = ensure_streams(m->scenes[i]);
-                }
-                if (rcs[i] != RTMI_OK) errs[i] = g_err; // g_err is thread-local
-            });
-        for (std::thread &t : th) t.join();
-    }
-    for (uint32_t i = 0; i < n; i++)
-        if (rcs[i] != RTMI_OK) return fail(rcs[i], "device " + std::to_string(devices[i]) + ": " + errs[i]);
-    if (m->distinct && (n > 1 || force_rccl())) { // communicators at create, not in the first render
-        std::lock_guard<std::mutex> lock(g_rccl_mutex);
-        if (!g_rccl.load()) return fail(RTMI_ERR_DEVICE, g_rccl.err);
-        std::vector<CommSet *> &pool = g_comm_pool[m->devices];
-        for (CommSet *c : pool)
-            if (!c->busy) { m->commset = c; break; }
-        if (!m->commset) {
-            CommSet *c = new CommSet();
-            c->comms.assign(n, nullptr);
-            int r = g_rccl.CommInitAll(c->comms.data(), (int)n, devices);
-            if (r != 0) { delete c; return fail(RTMI_ERR_DEVICE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r)); }
-            pool.push_back(c);
-            m->commset = c;
-        }
-        m->commset->busy = true;
-    }
-    guard.m = nullptr;
-    *out = m;
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_multi_collective(const rtmi_multi *m) {
-    if (!m) return -1;
-    return m->commset ? RTMI_COLLECTIVE_RCCL : (m->devices.size() > 1 ? RTMI_COLLECTIVE_PEER_COPY : RTMI_COLLECTIVE_NONE);
-}
-
-// whole-image parameters -> per-device parameters; validates what the multi-device entry points accept
-static int multi_params(const rtmi_multi *m, const rtmi_render_params *p_in, std::vector<rtmi_render_params> &params) {
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (p_in->tile_world != 1 || p_in->tile_rank != 0)
-        return fail(RTMI_ERR_INVALID, "multi-device render calls render the whole image: tile_rank/tile_world must be 0/1");
-    if (p_in->flags & (RTMI_FLAG_PATH_SIG | RTMI_FLAG_PROFILE)) return fail(RTMI_ERR_INVALID, "PATH_SIG / PROFILE are single-device diagnostics");
-    const uint32_t n = (uint32_t)m->devices.size();
-    params.assign(n, *p_in);
-    for (uint32_t i = 0; i < n; i++) { params[i].tile_world = n; params[i].tile_rank = i; }
-    return RTMI_OK;
-}
-// framebuffers of a render of this size (grow-only); every rank padded to rank 0's size (the largest)
-static int multi_reserve_texels(rtmi_multi *m, const rtmi_render_params *p0) {
-    const uint32_t n = (uint32_t)m->devices.size();
-    const size_t want = (size_t)local_tiles_of(p0, 0) * 64 * sizeof(rtmi_texel);
-    // what every buffer holds: the smallest one decides (a buffer whose allocation failed is empty)
-    size_t have = m->gathered.bytes / n;
-    for (uint32_t i = 0; i < n; i++) have = std::min(have, m->texels[i].bytes);
-    if (want > have) {
-        for (uint32_t i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(m->devices[i]));
-            HIP_TRY(m->texels[i].alloc(want));
-            // ranks with fewer tiles than rank 0 never write their padding: zero it once
-            HIP_TRY(hipMemset(m->texels[i].ptr, 0, want));
-        }
-        HIP_TRY(hipSetDevice(m->devices[0]));
-        HIP_TRY(m->gathered.alloc((size_t)n * want));
-    }
-    return grow_host_texels(m->h_gathered, m->gathered.bytes / sizeof(rtmi_texel));
-}
-
-extern "C" int rtmi_multi_prepare(rtmi_multi *m, const rtmi_render_params *p_in) {
-    if (!m) return fail(RTMI_ERR_INVALID, "NULL argument");
-    std::vector<rtmi_render_params> params;
-    int rc = multi_params(m, p_in, params);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(m->mu);
-    if ((rc = multi_reserve_texels(m, &params[0]))) return rc;
-    for (size_t i = 0; i < m->scenes.size(); i++)
-        if ((rc = rtmi_render_prepare(m->scenes[i], &params[i]))) return rc;
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_multi_render(rtmi_multi *m, const rtmi_camera *cam, const rtmi_render_params *p_in, float *out_linear,
-                                 uint8_t *out_rgb8, rtmi_stats *stats) {
-    if (!m || !cam) return fail(RTMI_ERR_INVALID, "NULL argument");
-    std::vector<rtmi_render_params> params;
-    int rc = multi_params(m, p_in, params);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lock(m->mu);
-    const uint32_t n = (uint32_t)m->devices.size();
-    if ((rc = multi_reserve_texels(m, &params[0]))) return rc;
-    // rank-major layout of the gathered buffer uses THIS call's stride (the buffers may be larger from an earlier call)
-    const size_t stride = (size_t)local_tiles_of(&params[0], 0) * 64;
-    std::vector<hipEvent_t> done(n);
-    // every device renders its tiles on its own stream, all concurrently
-    for (uint32_t i = 0; i < n; i++) {
-        rtmi_scene *s = m->scenes[i];
-        std::lock_guard<std::mutex> slock(s->mu);
-        HIP_TRY(hipSetDevice(m->devices[i]));
-        if ((rc = reserve_before_clock(s, &params[i]))) return rc;
-        HIP_TRY(hipEventRecord(s->ev[0].e, s->stream.s));
-        if ((rc = render_device_locked(s, cam, &params[i], m->texels[i].ptr, s->stream.s, nullptr))) return rc;
-        HIP_TRY(hipEventRecord(s->ev[1].e, s->stream.s));
-        done[i] = s->ev[2].e;
-    }
-    // the ONE exchange of the path: tile-packed framebuffers -> devices[0]
-    if (m->commset) {
-        RCCL_TRY(g_rccl.GroupStart());
-        for (uint32_t i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(m->devices[i]));
-            // (recvbuff is read on the root only; the others pass a valid device pointer rather than NULL for argument checkers)
-            RCCL_TRY(g_rccl.Gather(m->texels[i].ptr, i == 0 ? m->gathered.ptr : m->texels[i].ptr, stride * sizeof(rtmi_texel), /*ncclInt8*/ 0, 0, m->commset->comms[i], m->scenes[i]->stream.s));
-        }
-        RCCL_TRY(g_rccl.GroupEnd());
-    } else {
-        for (uint32_t i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(m->devices[i]));
-            HIP_TRY(hipMemcpyPeerAsync(m->gathered.ptr + (size_t)i * stride, m->devices[0], m->texels[i].ptr, m->devices[i], stride * sizeof(rtmi_texel), m->scenes[i]->stream.s));
-        }
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        HIP_TRY(hipSetDevice(m->devices[i]));
-        HIP_TRY(hipEventRecord(m->scenes[i]->ev[2].e, m->scenes[i]->stream.s));
-    }
-    if ((rc = wait_with_progress(m->scenes.data(), done.data(), n, p_in))) return rc;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    for (uint32_t i = 0; i < n; i++) {
-        HIP_TRY(hipSetDevice(m->devices[i]));
-        if ((rc = check_overflow(m->scenes[i]))) return rc;
-        if (stats) {
-            rtmi_stats one{};
-            if ((rc = fill_stats_from_events(m->scenes[i], &params[i], &one))) return rc;
-            stats->samples += one.samples; stats->tiles += one.tiles; stats->kernel = one.kernel;
-            if (one.render_ms > stats->render_ms) stats->render_ms = one.render_ms;
-            if (one.kernel_ms > stats->kernel_ms) stats->kernel_ms = one.kernel_ms;
-        }
-    }
-    HIP_TRY(hipSetDevice(m->devices[0]));
-    HIP_TRY(hipMemcpy(m->h_gathered.ptr, m->gathered.ptr, (size_t)n * stride * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    return rtmi_untile(&params[0], m->h_gathered.ptr, out_linear, out_rgb8);
-}
-
-// one-shot form: create + render + destroy (pays uploads, allocations and the communicator look-up on every call)
-extern "C" int rtmi_render_multi(const rtmi_scene_desc *desc, const int *devices, uint32_t n, const rtmi_camera *cam,
-                                 const rtmi_render_params *p_in, float *out_linear, uint8_t *out_rgb8, rtmi_stats *stats) {
-    if (!desc || !devices || !cam || n == 0) return fail(RTMI_ERR_INVALID, "NULL argument or empty device list");
-    int rc = check_params(p_in);
-    if (rc) return rc;
-    if (p_in->tile_world != 1 || p_in->tile_rank != 0)
-        return fail(RTMI_ERR_INVALID, "rtmi_render_multi renders the whole image: tile_rank/tile_world must be 0/1");
-    if (p_in->flags & (RTMI_FLAG_PATH_SIG | RTMI_FLAG_PROFILE)) return fail(RTMI_ERR_INVALID, "PATH_SIG / PROFILE are single-device diagnostics");
-    rtmi_multi *m = nullptr;
-    if ((rc = rtmi_multi_create(desc, devices, n, &m))) return rc;
-    rc = rtmi_multi_render(m, cam, p_in, out_linear, out_rgb8, stats);
-    const std::string keep = g_err; // destroy must not lose the message
-    rtmi_multi_destroy(m);
-    if (rc) g_err = keep;
-    return rc;
-}
-
 // P3 writer — tests/test.rs:59,79
 extern "C" size_t rtmi_ppm_p3(uint32_t nx, uint32_t ny, const uint8_t *rgb8, char *buf, size_t cap) {
     const size_t need = 40 + (size_t)nx * ny * 12;
@@ -1613,8 +1219,7 @@ extern "C" int rtmi_probe_math(int op, const float *x, const float *y, float *ou
     HIP_TRY(mem.alloc(layout));
     HIP_TRY(hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dy, y ? y : x, (size_t)n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rtmi_math_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, op, dx, dy, dout, n);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(rtmi_render_launch_probe_math(op, dx, dy, dout, n));
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
@@ -1632,8 +1237,7 @@ extern "C" int rtmi_probe_xform(const rtmi_xform *xforms, uint32_t count, const 
     if (count) HIP_TRY(hipMemcpy(dx, xforms, count * sizeof(rtmi_xform), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(da, a, (size_t)n * 12, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(db, b, (size_t)n * 12, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rtmi_xform_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx, (int)count, da, db, dout, n);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(rtmi_render_launch_probe_xform(dx, (int)count, da, db, dout, n));
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 13 * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
@@ -1686,8 +1290,7 @@ extern "C" int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b,
     sc.leaf_rec = reinterpret_cast<const float4 *>(d_rec);
     sc.xforms = d_xf;
     sc.has_prim_xf = has_prim_xf;
-    hipLaunchKernelGGL(rtmi_geom_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, op, sc, d_in, d_out, n);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(rtmi_render_launch_probe_geom(op, sc, d_in, d_out, n));
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n * RTMI_PROBE_GEOM_OUT * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
@@ -1702,8 +1305,7 @@ extern "C" int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint3
     HIP_TRY(mem.alloc(layout));
     HIP_TRY(hipMemcpy(dc, ctr, (size_t)n * 16, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dk, key, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(rtmi_philox_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dc, dk, dout, n);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(rtmi_render_launch_probe_philox(dc, dk, dout, n));
     HIP_TRY(hipMemcpy(out, dout, (size_t)n * 16, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
@@ -2012,16 +1614,6 @@ static int adaptive_steps(rtmi_scene *s, const rtmi_render_params &p, const rtmi
 // adaptive sampling's step loop (rtmi_adaptive.h, rtmi_adaptive_nee.h) and under Russian roulette (rtmi_roulette.h).  The
 // entry points differ in their argument checks and in the kernel they launch; what surrounds the launches is here.
 
-// an entry point's estimator: what it reads of the handle, and the entry's own words where the handle lacks it
-struct Estimator {
-    const char *name;       // the entry point, prefix of the attach refusals
-    bool nee, env;          // reads the light table (rtmi_scene_attach_lights) / the map (rtmi_scene_attach_env)
-    float env_select_p;     // rtmi_env_render's, read with the map only
-    const char *null_scene; // the refusal of a NULL handle
-    const char *no_lights;  // the refusal of a handle without the light table, after "name: "
-    bool tree = false;      // reads the light tree (rtmi_scene_attach_light_tree; RTMI_FLAG_LIGHT_TREE)
-};
-
 // the checks of rtmi_env_render-style options, in `name`'s words
 static int check_env_opts(const char *name, const rtmi_env_render *o) {
     if (o->nee > 1u) return fail(RTMI_ERR_INVALID, std::string(name) + ": nee must be 0 or 1");
@@ -2037,7 +1629,7 @@ static int refuse_sky(const char *name, uint32_t flags) {
 // The estimator of an entry that selects it by an RTMI_ROULETTE_* value (rtmi_roulette.h): the roulette renders, the sessions
 // and the batch modes.  env_select_p is read where both the lights and the map are sampled.  lit_estimator: the same of an
 // entry that holds the two choices themselves.  null_scene must outlive the Estimator.
-static Estimator lit_estimator(const char *name, bool nee, bool env, float env_select_p, const char *null_scene) {
+Estimator lit_estimator(const char *name, bool nee, bool env, float env_select_p, const char *null_scene) {
     return Estimator{name, nee, env, env_select_p, null_scene, "no light table attached (rtmi_scene_attach_lights)"};
 }
 static Estimator estimator_of(const char *name, uint32_t estimator, float env_select_p, const char *null_scene) {
@@ -2047,12 +1639,12 @@ static Estimator estimator_of(const char *name, uint32_t estimator, float env_se
 }
 // The checks of that selection, two because each entry has checks of its own between them: the value, and what the chosen
 // estimator refuses of env_select_p (read, and checked, only where both are sampled) and of the flags.
-static int check_estimator(const char *name, uint32_t estimator) {
+int check_estimator(const char *name, uint32_t estimator) {
     if (estimator > RTMI_ROULETTE_ENV_NEE)
         return fail(RTMI_ERR_INVALID, std::string(name) + ": estimator must be one of RTMI_ROULETTE_* (0..3)");
     return RTMI_OK;
 }
-static int check_estimator_opts(const char *name, uint32_t estimator, float env_select_p, uint32_t flags) {
+int check_estimator_opts(const char *name, uint32_t estimator, float env_select_p, uint32_t flags) {
     const rtmi_env_render eo{1u, env_select_p};
     if (estimator == RTMI_ROULETTE_ENV_NEE)
         if (int rc = check_env_opts(name, &eo)) return rc;
@@ -2078,23 +1670,6 @@ static void dev_lighting(const rtmi_scene *s, bool nee, bool env, float env_sele
     if (env) E = dev_env(s, !s->env_sampled ? 0.0f : (s->nee_n > 0u ? env_select_p : 1.0f));
 }
 
-// a blocking call's hold on the handle from begin_call to its return, and the kernel arguments of its estimator
-struct RenderCall {
-    std::unique_lock<std::mutex> lock;
-    BusyMark busy{nullptr, nullptr};
-    DevParams P;
-    DevCamera C;
-    DevLights L;
-    DevEnv E;
-    bool fast = false;
-    // RTMI_FLAG_LIGHT_COOP (rtmi_light_coop.h), RTMI_FLAG_ROULETTE_COOP (rtmi_roulette_coop.h): the estimator runs on the
-    // wave-cooperative kernel, with this pool form and this much dynamic LDS per block; wps: the waves per SIMD the call's
-    // render kernel was compiled for
-    bool coop = false, ext = false;
-    size_t coop_lds = 0;
-    uint32_t wps = 4u;
-};
-
 // the map and the light table the estimator reads are attached to the handle (the caller holds s->mu)
 static int check_attached(const Estimator &m, const rtmi_scene *s) {
     if (m.env && !s->has_env)
@@ -2111,7 +1686,7 @@ static int check_attached_early(const Estimator &m, const rtmi_scene *s_in) {
 }
 // The end of an entry point's checks and the start of its device work, in this order: the handle, its lock, what the
 // estimator needs attached, then the device, no earlier render of the handle running, the busy mark.
-static int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
+int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s) {
     if (!s) return fail(RTMI_ERR_INVALID, m.null_scene);
     c.lock = std::unique_lock<std::mutex>(s->mu);
     if (int rc = check_attached(m, s)) return rc;
@@ -2140,7 +1715,7 @@ struct AsyncCall {
         return RTMI_OK;
     }
 };
-static void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, const rtmi_camera *cam,
+void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, const rtmi_camera *cam,
                         const rtmi_render_params &p) {
     c.P = dev_params(s, &p);
     c.C = dev_camera(cam);
@@ -2154,8 +1729,7 @@ static void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, 
 static uint32_t light_coop_bits(const rtmi_render_params *p, uint32_t flag = RTMI_FLAG_LIGHT_COOP) { // the bits the flag adds to an entry's accepted ones
     return (p && (p->flags & flag)) ? (flag | (1u << 11)) : 0u;
 }
-static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_params &p, uint32_t flag = RTMI_FLAG_LIGHT_COOP,
-                           uint32_t wps = RTMI_LIGHT_COOP_WPS) {
+int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_params &p, uint32_t flag, uint32_t wps) {
     const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
     c.coop = (p.flags & flag) != 0u && c.fast && !(p.flags & RTMI_FLAG_SYNC) && coop_ok && !inst;
@@ -2170,11 +1744,11 @@ static int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_param
     return RTMI_OK;
 }
 // the persistent grid of the call's render kernel, in wavefronts: CUs x 4 SIMDs x the waves per SIMD it was compiled for
-static uint64_t light_run_slots(const rtmi_scene *s, const RenderCall &c) {
+uint64_t light_run_slots(const rtmi_scene *s, const RenderCall &c) {
     return (uint64_t)(s->slots / 20) * 4u * c.wps;
 }
 // the cooperative launch of a lighting entry's callable: the fixed render's pass (tiles = NULL) or one over the active list
-static int launch_light_coop(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks, const uint32_t *tiles) {
+int launch_light_coop(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks, const uint32_t *tiles) {
     HIP_TRY(rtmi_light_coop_launch_render(tiles != nullptr, sig, c.ext, m.nee, m.env, blocks, c.coop_lds, s->stream.s, s->dev, c.C,
                                           c.P, tiles, c.L, c.E));
     return RTMI_OK;
@@ -3777,7 +3351,6 @@ extern "C" int rtmi_render_env(rtmi_scene *s, const rtmi_camera *cam, const rtmi
 // adaptive sampling's step loop (adaptive_steps) with the per-lane kernel of rtmi_adaptive_nee.hip, or under
 // RTMI_FLAG_LIGHT_COOP the cooperative one of rtmi_light_coop.hip: rtmi_render_nee's or rtmi_render_env's estimator over
 // the active-tile list
-#define RTMI_ADAPTIVE_NEE_FLAGS (RTMI_FLAG_FAST_CULL | RTMI_FLAG_SYNC | RTMI_FLAG_REF_TREE | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK)
 static int adaptive_lit(const Estimator &m, rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params &p,
                         const rtmi_adaptive *a, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
                         rtmi_stats *stats) {
@@ -3915,504 +3488,6 @@ extern "C" int rtmi_probe_env(rtmi_scene *s, int op, const float *in, float *out
     HIP_TRY(rtmi_env_launch_probe(op, dev_env(s, s->env_sampled ? 1.0f : 0.0f), din, dout, n, s->stream.s));
     HIP_TRY(hipMemcpyAsync(out, dout, nout * sizeof(float), hipMemcpyDeviceToHost, s->stream.s));
     HIP_TRY(hipStreamSynchronize(s->stream.s));
-    return RTMI_OK;
-}
-
-// ---- render sessions (include/rtmi_session.h) --------------------------------------------------------------------------
-// A session owns what the one-shot entries keep for one call: per tile a count (on the host), the nine f64 planes and the
-// bounce plane (on the scene's device).  Its calls are the host path of the one-shot entries (begin_call, kernel_args,
-// plan_light_coop / plan_traversal, plan_and_reserve, run_passes, the adaptive resolve with decide = 0, which writes the
-// state back for every tile) over a list of tiles that all hold the same count; the convergence test, the read-out and the
-// merge are the kernels of rtmi_session.hip.
-struct RTMI_HIDDEN rtmi_session {
-    rtmi_scene *s = nullptr;
-    rtmi_camera cam{};
-    rtmi_render_params p{}; // ns = 1 (not read); the cooperative flag normalised to the one of the session's entries
-    rtmi_session_opts o{};
-    bool refine = false, nee = false, env = false, failed = false;
-    uint32_t T = 0;
-    std::vector<uint32_t> n; // [tile] the samples each tile holds
-    DeviceBuf<double> state;               // [tile][9][64]
-    DeviceBuf<uint32_t> bounces, d_counts; // [tile][64], [tile]
-    uint32_t last_cap = 0;   // the last refine call's cap and tolerances
-    double last_abs = std::numeric_limits<double>::infinity(), last_rel = std::numeric_limits<double>::infinity();
-    uint32_t scene_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-};
-
-static const uint32_t SESSION_RESULT_FLAGS = RTMI_FLAG_SKY | RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK;
-static const uint32_t SESSION_COOP_FLAGS = RTMI_FLAG_LIGHT_COOP | RTMI_FLAG_ROULETTE_COOP;
-
-// the blob's header (include/rtmi_session.h); first_sample: written in place of the session's own (merge compares two
-// sessions' identity blocks but for that field)
-static std::vector<uint8_t> session_header(const rtmi_session *ss, const uint32_t *first_sample = nullptr) {
-    std::vector<uint8_t> h(RTMI_SESSION_BLOB_HEADER, 0);
-    size_t at = 0;
-    const auto put = [&](const void *v, size_t nbytes) { std::memcpy(h.data() + at, v, nbytes); at += nbytes; };
-    const uint32_t version = RTMI_SESSION_BLOB_VERSION, kind = ss->refine ? 1u : 0u, flags = ss->p.flags & SESSION_RESULT_FLAGS;
-    put("RTMISESS", 8);
-    put(&version, 4); put(&ss->p.nx, 4); put(&ss->p.ny, 4); put(&ss->T, 4); put(&kind, 4);
-    rtmi_session_opts o = ss->o;
-    if (first_sample) o.first_sample = *first_sample;
-    put(&o, sizeof(rtmi_session_opts));
-    put(&ss->p.max_depth, 4); put(&ss->p.t_min, 4); put(&flags, 4); put(&ss->p.seed, 8);
-    put(ss->cam.origin, 12); put(ss->cam.lower_left_corner, 12); put(ss->cam.horizontal, 12); put(ss->cam.vertical, 12);
-    put(ss->cam.u, 12); put(ss->cam.v, 12); put(&ss->cam.time0, 4); put(&ss->cam.time1, 4); put(&ss->cam.lens_radius, 4);
-    put(ss->scene_counts, 32);
-    put(&ss->last_cap, 4); put(&ss->last_abs, 8); put(&ss->last_rel, 8);
-    return h; // at == RTMI_SESSION_BLOB_HEADER
-}
-static_assert(sizeof(rtmi_session_opts) == 32, "rtmi_session_opts is 32 bytes in the blob");
-static size_t session_blob_bytes(const rtmi_session *ss) {
-    return (size_t)RTMI_SESSION_BLOB_HEADER + (size_t)ss->T * (4u + 9u * 64u * 8u + 64u * 4u);
-}
-
-static Estimator session_estimator(const rtmi_session *ss, const char *name, const std::string &null_scene) {
-    return lit_estimator(name, ss->nee, ss->env, ss->nee && ss->env ? ss->o.env_select_p : 1.0f, null_scene.c_str());
-}
-
-// the refusals every call on an existing session starts with
-static int session_usable(const rtmi_session *ss, const std::string &nm, bool want_refine, bool any_kind = false) {
-    if (!ss) return fail(RTMI_ERR_INVALID, nm + "session is NULL");
-    if (ss->failed)
-        return fail(RTMI_ERR_INVALID, nm + "the session is failed (an earlier call failed or was cancelled after its device work "
-                                           "began): destroy it or import a checkpoint");
-    if (!any_kind && ss->refine != want_refine)
-        return fail(RTMI_ERR_INVALID, nm + (want_refine ? "this call needs a REFINE session: a FIXED one (min_spp == step_spp == 0) "
-                                                          "advances with rtmi_session_render"
-                                                        : "this call needs a FIXED session: a REFINE one advances with rtmi_session_refine"));
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_session_create(rtmi_scene *s, const rtmi_camera *cam, const rtmi_render_params *p_in,
-                                   const rtmi_session_opts *o, rtmi_session **out) {
-    // every argument check comes before the first use of the handle (and of the device)
-    const char *name = "rtmi_session_create";
-    const std::string nm = std::string(name) + ": ";
-    if (!p_in || !cam || !o || !out) return fail(RTMI_ERR_INVALID, nm + "NULL argument");
-    rtmi_render_params p = *p_in;
-    p.ns = 1u; // not read
-    int rc = check_params(&p);
-    if (rc) return rc;
-    if ((rc = check_estimator(name, o->estimator))) return rc;
-    if (o->rr > 1u) return fail(RTMI_ERR_INVALID, nm + "rr must be 0 or 1");
-    if (o->rr && o->min_depth == 0u) return fail(RTMI_ERR_INVALID, nm + "min_depth must be at least 1");
-    if (o->rr && (!std::isfinite(o->q_min) || !(o->q_min > 0.0f && o->q_min <= 1.0f)))
-        return fail(RTMI_ERR_INVALID, nm + "q_min must be in (0, 1]");
-    const bool nee = o->estimator == RTMI_ROULETTE_NEE || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    const bool env = o->estimator == RTMI_ROULETTE_ENV || o->estimator == RTMI_ROULETTE_ENV_NEE;
-    if ((rc = check_estimator_opts(name, o->estimator, o->env_select_p, p.flags))) return rc;
-    if (p.flags & RTMI_FLAG_PATH_SIG) return fail(RTMI_ERR_UNSUPPORTED, nm + "PATH_SIG is refused: a session keeps no path signatures");
-    const std::string flags_msg = nm + "sessions accept the flags FAST_CULL, SYNC, REF_TREE, SKY, FACE_FORWARD, UV_BOOK, LIGHT_COOP and "
-                                       "ROULETTE_COOP only (not PATH_SIG, PROFILE, ASYNC, BLOCK_COOP, PROGRESSIVE, TEST_OVERFLOW)";
-    const std::string world_msg = nm + "a session renders the whole image: tile_world must be 1";
-    if ((rc = check_mode_params(&p, RTMI_ADAPTIVE_NEE_FLAGS | RTMI_FLAG_SKY | SESSION_COOP_FLAGS, flags_msg.c_str(), world_msg.c_str())))
-        return rc;
-    const bool refine = o->min_spp != 0u || o->step_spp != 0u;
-    if (refine) {
-        if (o->min_spp < 2u) return fail(RTMI_ERR_INVALID, nm + "min_spp must be at least 2 (a variance needs two samples)");
-        if (o->step_spp == 0u) return fail(RTMI_ERR_INVALID, nm + "step_spp must be positive");
-        if (o->first_sample != 0u) return fail(RTMI_ERR_INVALID, nm + "first_sample must be 0 in a REFINE session");
-        if (o->min_spp >= (1u << 26)) return fail(RTMI_ERR_UNSUPPORTED, nm + "min_spp must be below 2^26");
-    }
-    if (o->first_sample >= (1u << 31)) return fail(RTMI_ERR_INVALID, nm + "first_sample must be below 2^31");
-    if (o->first_sample >= (1u << 26)) return fail(RTMI_ERR_UNSUPPORTED, nm + "sample indices must stay below 2^26");
-
-    rtmi_session *ss = new (std::nothrow) rtmi_session;
-    if (!ss) return fail(RTMI_ERR_NOMEM, nm + "out of host memory");
-    ss->s = s; ss->cam = *cam; ss->p = p; ss->o = *o;
-    ss->refine = refine; ss->nee = nee; ss->env = env;
-    if (!o->rr) { ss->o.min_depth = 0u; ss->o.q_min = 0.0f; } // not read: one representation in the identity block
-    if (!(nee && env)) ss->o.env_select_p = 0.0f;
-    if (ss->p.flags & SESSION_COOP_FLAGS)
-        ss->p.flags = (ss->p.flags & ~SESSION_COOP_FLAGS) | (o->rr ? RTMI_FLAG_ROULETTE_COOP : RTMI_FLAG_LIGHT_COOP);
-    ss->T = local_tiles_of(&p, 0);
-    ss->n.assign(ss->T, 0u);
-    const std::string null_scene = nm + "scene is NULL";
-    const Estimator m = session_estimator(ss, name, null_scene);
-    RenderCall c;
-    if ((rc = begin_call(c, m, s))) { delete ss; return rc; }
-    const uint32_t counts[8] = {s->meta.n_items, s->meta.n_prims, s->meta.n_nodes, s->meta.n_materials, s->meta.n_textures,
-                                nee ? s->nee_n : 0u, env ? s->env_w : 0u, env ? s->env_h : 0u};
-    std::memcpy(ss->scene_counts, counts, sizeof(counts));
-    const size_t T = ss->T;
-    hipError_t e = ss->state.alloc(T * 9 * 64 * sizeof(double));
-    if (e == hipSuccess) e = ss->bounces.alloc(T * 64 * sizeof(uint32_t));
-    if (e == hipSuccess) e = ss->d_counts.alloc(T * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(ss->state.ptr, 0, T * 9 * 64 * sizeof(double), s->stream.s);
-    if (e == hipSuccess) e = hipMemsetAsync(ss->bounces.ptr, 0, T * 64 * sizeof(uint32_t), s->stream.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream.s);
-    if (e != hipSuccess) {
-        delete ss;
-        return fail(e == hipErrorOutOfMemory ? RTMI_ERR_NOMEM : RTMI_ERR_DEVICE, nm + hipGetErrorString(e));
-    }
-    *out = ss;
-    return RTMI_OK;
-}
-
-extern "C" void rtmi_session_destroy(rtmi_session *ss) {
-    if (!ss) return;
-    {
-        std::lock_guard<std::mutex> lock(ss->s->mu);
-        (void)hipSetDevice(ss->s->device);
-        if (ss->s->busy_recorded) (void)hipEventSynchronize(ss->s->busy.e);
-        (void)ss->state.release(); (void)ss->bounces.release(); (void)ss->d_counts.release();
-    }
-    delete ss;
-}
-
-// One render or refine call's hold on the scene and its kernel plan: begin_call, the scene's scratch for the session's
-// tiles, the kernel arguments and the selection of the render kernel (the plain estimator without roulette follows
-// rtmi_render_adaptive's rule, the others plan_light_coop under their entries' flag).
-struct SessionCall {
-    RenderCall c;
-    int which = RTMI_AD_PERLANE; // the plain estimator without roulette: the kernel of rtmi_adaptive.hip
-    PassCounts counts;
-    uint64_t samples = 0;
-    bool worked = false; // some launch was enqueued
-};
-static int session_begin(SessionCall &k, rtmi_session *ss, const Estimator &m) {
-    rtmi_scene *s = ss->s;
-    RenderCall &c = k.c;
-    int rc;
-    if ((rc = begin_call(c, m, s)) || (rc = reserve_texels(s, (size_t)ss->T * 64)) || (rc = grow_adaptive(s, ss->T))) return rc;
-    kernel_args(c, m, s, &ss->cam, ss->p);
-    const rtmi_render_params &p = ss->p;
-    if (!ss->nee && !ss->env && !ss->o.rr) {
-        const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
-        const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
-        c.coop = c.fast && !(p.flags & RTMI_FLAG_SYNC) && coop_ok && !inst;
-        if ((rc = plan_traversal(s, &p, c.coop, c.P, c.ext))) return rc;
-        k.which = c.coop ? (c.ext ? RTMI_AD_COOP_EXT : RTMI_AD_COOP_LEAN) : (c.fast ? RTMI_AD_PERLANE_FAST : RTMI_AD_PERLANE);
-        c.coop_lds = (size_t)WAVES_PER_BLOCK * CoopLds{c.P.coop_cap, c.ext, false}.words() * sizeof(uint32_t);
-        c.wps = 4u;
-    } else if (ss->o.rr) {
-        if ((rc = plan_light_coop(c, s, p, RTMI_FLAG_ROULETTE_COOP, rtmi_roulette_coop_wps(ss->nee, ss->env)))) return rc;
-    } else if ((rc = plan_light_coop(c, s, p))) {
-        return rc;
-    }
-    s->last_kernel = c.coop ? RTMI_KERNEL_WAVE_COOP : RTMI_KERNEL_PERLANE;
-    if ((rc = begin_passes(s, s->stream.s))) return rc;
-    HIP_TRY(hipEventRecord(s->ev[0].e, s->stream.s));
-    HIP_TRY(hipEventRecord(s->ev[2].e, s->stream.s));
-    return RTMI_OK;
-}
-static int session_launch_render(const SessionCall &k, const rtmi_session *ss, const Estimator &m, uint32_t blocks, const uint32_t *tiles) {
-    rtmi_scene *s = ss->s;
-    const RenderCall &c = k.c;
-    if (!ss->nee && !ss->env && !ss->o.rr) {
-        HIP_TRY(rtmi_adaptive_launch_render(k.which, blocks, c.coop ? c.coop_lds : 0, s->stream.s, s->dev, c.C, c.P, tiles));
-    } else if (ss->o.rr) {
-        const DevRoulette R{ss->bounces.ptr, ss->o.min_depth, ss->o.q_min};
-        if (c.coop)
-            HIP_TRY(rtmi_roulette_coop_launch_render(c.ext, ss->nee, ss->env, blocks, c.coop_lds, s->stream.s, s->dev, c.C, c.P, tiles,
-                                                     c.L, c.E, R));
-        else
-            HIP_TRY(rtmi_roulette_launch_render(c.fast, ss->nee, ss->env, blocks, s->stream.s, s->dev, c.C, c.P, tiles, c.L, c.E, R));
-    } else if (c.coop) {
-        return launch_light_coop(c, m, s, false, blocks, tiles);
-    } else {
-        HIP_TRY(rtmi_adaptive_nee_launch_render(c.fast, ss->nee, ss->env, blocks, s->stream.s, s->dev, c.C, c.P, tiles, c.L, c.E));
-    }
-    return RTMI_OK;
-}
-// the pixels of `tiles` that lie inside the image
-static uint64_t session_pixels(const rtmi_session *ss, const std::vector<uint32_t> &tiles) {
-    const uint32_t txn = tiles_x_of(&ss->p);
-    uint64_t pix = 0;
-    for (uint32_t t : tiles) {
-        const uint32_t ty = t / txn, tx = t % txn;
-        const uint32_t w = (tx * RTMI_TILE + RTMI_TILE <= ss->p.nx) ? RTMI_TILE : ss->p.nx - tx * RTMI_TILE;
-        const uint32_t h = (ty * RTMI_TILE + RTMI_TILE <= ss->p.ny) ? RTMI_TILE : ss->p.ny - ty * RTMI_TILE;
-        pix += (uint64_t)w * h;
-    }
-    return pix;
-}
-// Samples [from, from + cnt) of the session's sequence for the tiles of `active`, which all hold `from`: one launch range
-// (pass_s0 uniform), in sub-passes when the per-sample buffer does not hold it; waits for it, reporting progress.
-static int session_advance(SessionCall &k, rtmi_session *ss, const Estimator &m, const std::vector<uint32_t> &active, uint32_t from,
-                           uint32_t cnt) {
-    rtmi_scene *s = ss->s;
-    hipStream_t stream = s->stream.s;
-    DevParams &P = k.c.P;
-    int rc;
-    const uint32_t n_active = (uint32_t)active.size();
-    HIP_TRY(hipMemcpyAsync(s->ad_lists.ptr, active.data(), (size_t)n_active * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    rtmi_render_params q = ss->p;
-    q.ns = cnt;
-    uint32_t chunk_spp = 0, pass_ns = 0;
-    if ((rc = plan_and_reserve(s, &q, n_active, chunk_spp, pass_ns))) return rc;
-    P.ntiles_local = n_active; P.chunk_spp = chunk_spp; P.pass_stride = pass_ns; P.samples = s->samples.ptr;
-    AdaptiveResolve A;
-    A.tiles_in = s->ad_lists.ptr; A.tiles_out = s->ad_lists.ptr + ss->T; A.n_out = s->ad_lists.ptr + 2 * (size_t)ss->T;
-    A.state = ss->state.ptr; A.texels = s->texels.ptr; A.stderr_out = s->ad_stderr.ptr; A.spp_out = s->ad_spp.ptr;
-    A.abs_tol = 0.0; A.rel_tol = 0.0; A.ns = 0xffffffffu;
-    A.decide = 0; // never retires: sum, m and M2 go back to the session's planes after every sub-pass
-    const uint32_t s0 = ss->o.first_sample;
-    k.worked = true;
-    rc = run_passes(s, P, stream, s0 + from, cnt, false, light_run_slots(s, k.c), 1u, k.counts,
-                    [&](uint32_t blocks, bool first, bool) -> int {
-                        if (int lrc = session_launch_render(k, ss, m, blocks, (const uint32_t *)s->ad_lists.ptr)) return lrc;
-                        DevParams Pr = P; // the resolve counts from the session's first sample: Welford's k = 1 there
-                        Pr.pass_s0 = P.pass_s0 - s0;
-                        A.first = (from == 0u && first) ? 1 : 0;
-                        HIP_TRY(rtmi_adaptive_launch_resolve(stream, s->samples.ptr, Pr, A));
-                        return RTMI_OK;
-                    });
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(s->ev[2].e, stream));
-    rtmi_scene *one[1] = {s};
-    if ((rc = wait_with_progress(one, &s->ev[2].e, 1, &ss->p))) return rc;
-    for (uint32_t t : active) ss->n[t] = from + cnt;
-    k.samples += session_pixels(ss, active) * cnt;
-    return RTMI_OK;
-}
-// the end of a render or refine call whose device work began: the failed mark, the overflow word, the stats
-static int session_end(SessionCall &k, rtmi_session *ss, int rc, rtmi_stats *stats) {
-    rtmi_scene *s = ss->s;
-    if (!rc && k.worked) rc = check_overflow(s);
-    if (rc) {
-        ss->failed = true;
-        return rc;
-    }
-    if (stats) {
-        float ms = 0.f;
-        HIP_TRY(hipEventSynchronize(s->ev[2].e));
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev[0].e, s->ev[2].e));
-        fill_stats(s, &ss->p, stats, ms, ms, k.counts);
-        stats->samples = k.samples;
-    }
-    return RTMI_OK;
-}
-// a count the kernels can index: below 2^31 by the contract of the header, below 2^26 by the (sample, pixel) packing
-static int session_check_count(const std::string &nm, uint64_t last) {
-    if (last > (1ull << 31)) return fail(RTMI_ERR_INVALID, nm + "the sample count would pass 2^31");
-    if (last > (1ull << 26)) return fail(RTMI_ERR_UNSUPPORTED, nm + "sample indices must stay below 2^26");
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_session_render(rtmi_session *ss, uint32_t add_spp, rtmi_stats *stats) {
-    const char *name = "rtmi_session_render";
-    const std::string nm = std::string(name) + ": ";
-    int rc = session_usable(ss, nm, false);
-    if (rc) return rc;
-    if (add_spp == 0u) return fail(RTMI_ERR_INVALID, nm + "add_spp must be positive");
-    const uint32_t from = ss->n.empty() ? 0u : ss->n[0];
-    if ((rc = session_check_count(nm, (uint64_t)ss->o.first_sample + from + add_spp))) return rc;
-    const std::string null_scene = nm + "scene is NULL";
-    const Estimator m = session_estimator(ss, name, null_scene);
-    SessionCall k;
-    if ((rc = session_begin(k, ss, m))) return rc;
-    std::vector<uint32_t> all(ss->T);
-    for (uint32_t t = 0; t < ss->T; t++) all[t] = t;
-    return session_end(k, ss, session_advance(k, ss, m, all, from, add_spp), stats);
-}
-
-// the tiles of `cand` (all at n samples) that fail the test under (abs_tol, rel_tol), in any order
-static int session_test(rtmi_session *ss, std::vector<uint32_t> &cand, uint32_t n, double abs_tol, double rel_tol) {
-    rtmi_scene *s = ss->s;
-    hipStream_t stream = s->stream.s;
-    uint32_t *in = s->ad_lists.ptr, *outl = s->ad_lists.ptr + ss->T, *count = s->ad_lists.ptr + 2 * (size_t)ss->T;
-    HIP_TRY(hipMemcpyAsync(in, cand.data(), cand.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), stream));
-    SessionDecide D;
-    D.state = ss->state.ptr; D.tiles_in = in; D.n_in = (uint32_t)cand.size(); D.tiles_out = outl; D.n_out = count;
-    D.nx = ss->p.nx; D.ny = ss->p.ny; D.tiles_x = tiles_x_of(&ss->p);
-    D.n = n; D.abs_tol = abs_tol; D.rel_tol = rel_tol;
-    HIP_TRY(rtmi_session_launch_decide(stream, D));
-    HIP_TRY(hipStreamSynchronize(stream));
-    uint32_t left = 0;
-    HIP_TRY(hipMemcpy(&left, count, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (left > cand.size()) return fail(RTMI_ERR_DEVICE, "rtmi_session_refine: the test listed more tiles than it was given");
-    cand.resize(left);
-    if (left) HIP_TRY(hipMemcpy(cand.data(), outl, (size_t)left * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_session_refine(rtmi_session *ss, double abs_tol, double rel_tol, uint32_t cap, rtmi_stats *stats) {
-    const char *name = "rtmi_session_refine";
-    const std::string nm = std::string(name) + ": ";
-    int rc = session_usable(ss, nm, true);
-    if (rc) return rc;
-    const uint32_t min_spp = ss->o.min_spp, step = ss->o.step_spp;
-    if (!std::isfinite(abs_tol) || !(abs_tol >= 0.0) || !std::isfinite(rel_tol) || !(rel_tol >= 0.0))
-        return fail(RTMI_ERR_INVALID, nm + "abs_tol and rel_tol must be finite and non-negative");
-    if (cap < min_spp) return fail(RTMI_ERR_INVALID, nm + "min_spp must not exceed the cap");
-    if ((rc = session_check_count(nm, cap))) return rc;
-    if (cap < ss->last_cap || abs_tol > ss->last_abs || rel_tol > ss->last_rel)
-        return fail(RTMI_ERR_INVALID, nm + "a call must not loosen: cap >= the previous cap, abs_tol and rel_tol <= the previous ones");
-    const std::string null_scene = nm + "scene is NULL";
-    const Estimator m = session_estimator(ss, name, null_scene);
-    SessionCall k;
-    if ((rc = session_begin(k, ss, m))) return rc;
-
-    std::map<uint32_t, std::vector<uint32_t>> parked; // count -> the tiles parked there, below the cap
-    for (uint32_t t = 0; t < ss->T; t++)
-        if (ss->n[t] < cap) parked[ss->n[t]].push_back(t);
-    std::vector<uint32_t> active; // the unsettled tiles, all at `cur`
-    uint32_t cur = 0;
-    while (!rc) {
-        if (active.empty()) {
-            if (parked.empty()) break;
-            cur = parked.begin()->first;
-        }
-        auto here = parked.find(cur);
-        if (here != parked.end()) { // the tiles carried from below join the tiles parked at this count
-            active.insert(active.end(), here->second.begin(), here->second.end());
-            parked.erase(here);
-        }
-        const bool on_lattice = cur >= min_spp && (cur - min_spp) % step == 0u;
-        if (on_lattice && (rc = session_test(ss, active, cur, abs_tol, rel_tol))) break; // off the lattice: no test, they continue
-        if (active.empty()) continue;
-        uint64_t next = cur < min_spp ? min_spp : (uint64_t)cur + step - (cur - min_spp) % step;
-        if (next > cap) next = cap;
-        if (!parked.empty() && parked.begin()->first < next) next = parked.begin()->first;
-        if ((rc = session_advance(k, ss, m, active, cur, (uint32_t)next - cur))) break;
-        cur = (uint32_t)next;
-        if (cur >= cap) break; // settled at the cap
-    }
-    if (!rc) { ss->last_cap = cap; ss->last_abs = abs_tol; ss->last_rel = rel_tol; }
-    return session_end(k, ss, rc, stats);
-}
-
-extern "C" int rtmi_session_spp(rtmi_session *ss, uint32_t *min_spp, uint32_t *max_spp) {
-    const std::string nm = "rtmi_session_spp: ";
-    if (int rc = session_usable(ss, nm, false, true)) return rc;
-    std::lock_guard<std::mutex> lock(ss->s->mu);
-    uint32_t lo = 0xffffffffu, hi = 0u;
-    for (uint32_t v : ss->n) { lo = v < lo ? v : lo; hi = v > hi ? v : hi; }
-    if (min_spp) *min_spp = ss->n.empty() ? 0u : lo;
-    if (max_spp) *max_spp = hi;
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_session_image(rtmi_session *ss, float *out_linear, uint8_t *out_rgb8, float *out_stderr, uint32_t *out_spp,
-                                  uint32_t *out_bounces) {
-    const char *name = "rtmi_session_image";
-    const std::string nm = std::string(name) + ": ";
-    int rc = session_usable(ss, nm, false, true);
-    if (rc) return rc;
-    rtmi_scene *s = ss->s;
-    std::unique_lock<std::mutex> lock(s->mu);
-    for (uint32_t v : ss->n)
-        if (v == 0u) return fail(RTMI_ERR_INVALID, nm + "the session holds no samples yet");
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    BusyMark busy{s, s->stream.s};
-    const size_t ntex = (size_t)ss->T * 64;
-    if ((rc = reserve_texels(s, ntex)) || (rc = grow_adaptive(s, ss->T))) return rc;
-    HIP_TRY(hipMemcpyAsync(ss->d_counts.ptr, ss->n.data(), (size_t)ss->T * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream.s));
-    const SessionReadout R{ss->state.ptr, ss->d_counts.ptr, ss->T, s->texels.ptr, s->ad_stderr.ptr, s->ad_spp.ptr};
-    HIP_TRY(rtmi_session_launch_readout(s->stream.s, R));
-    HIP_TRY(hipStreamSynchronize(s->stream.s));
-    HIP_TRY(hipMemcpy(s->h_texels.ptr, s->texels.ptr, ntex * sizeof(rtmi_texel), hipMemcpyDeviceToHost));
-    if (out_stderr && (rc = download_untiled<3>(&ss->p, s->ad_stderr.ptr, ntex, out_stderr))) return rc;
-    if (out_spp && (rc = download_untiled<1>(&ss->p, s->ad_spp.ptr, ntex, out_spp))) return rc;
-    if (out_bounces && (rc = download_untiled<1>(&ss->p, ss->bounces.ptr, ntex, out_bounces))) return rc;
-    return rtmi_untile(&ss->p, s->h_texels.ptr, out_linear, out_rgb8);
-}
-
-extern "C" int rtmi_session_export(rtmi_session *ss, void *buf, size_t cap, size_t *need) {
-    const std::string nm = "rtmi_session_export: ";
-    int rc = session_usable(ss, nm, false, true);
-    if (rc) return rc;
-    if (!need) return fail(RTMI_ERR_INVALID, nm + "NULL argument");
-    *need = session_blob_bytes(ss);
-    if (!buf) return RTMI_OK;
-    if (cap < *need) return fail(RTMI_ERR_INVALID, nm + "the buffer is smaller than the blob");
-    rtmi_scene *s = ss->s;
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
-    uint8_t *b = static_cast<uint8_t *>(buf);
-    const std::vector<uint8_t> h = session_header(ss);
-    std::memcpy(b, h.data(), h.size());
-    size_t at = h.size();
-    std::memcpy(b + at, ss->n.data(), (size_t)ss->T * 4);
-    at += (size_t)ss->T * 4;
-    HIP_TRY(hipMemcpy(b + at, ss->state.ptr, (size_t)ss->T * 9 * 64 * 8, hipMemcpyDeviceToHost));
-    at += (size_t)ss->T * 9 * 64 * 8;
-    HIP_TRY(hipMemcpy(b + at, ss->bounces.ptr, (size_t)ss->T * 64 * 4, hipMemcpyDeviceToHost));
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_session_import(rtmi_session *ss, const void *buf, size_t len) {
-    const std::string nm = "rtmi_session_import: ";
-    if (!ss || !buf) return fail(RTMI_ERR_INVALID, nm + "NULL argument");
-    const uint8_t *b = static_cast<const uint8_t *>(buf);
-    if (len < RTMI_SESSION_BLOB_HEADER || std::memcmp(b, "RTMISESS", 8) != 0) return fail(RTMI_ERR_INVALID, nm + "not a session blob (magic)");
-    uint32_t version = 0;
-    std::memcpy(&version, b + 8, 4);
-    if (version != RTMI_SESSION_BLOB_VERSION) return fail(RTMI_ERR_INVALID, nm + "unknown blob version");
-    const std::vector<uint8_t> h = session_header(ss);
-    if (std::memcmp(b, h.data(), RTMI_SESSION_BLOB_IDENTITY) != 0)
-        return fail(RTMI_ERR_INVALID, nm + "the blob's identity block differs from the session's");
-    if (len != session_blob_bytes(ss)) return fail(RTMI_ERR_INVALID, nm + "wrong blob length");
-    uint32_t cap = 0;
-    double abs_tol = 0.0, rel_tol = 0.0;
-    std::memcpy(&cap, b + 196, 4); std::memcpy(&abs_tol, b + 200, 8); std::memcpy(&rel_tol, b + 208, 8);
-    std::vector<uint32_t> n(ss->T);
-    size_t at = RTMI_SESSION_BLOB_HEADER;
-    std::memcpy(n.data(), b + at, (size_t)ss->T * 4);
-    at += (size_t)ss->T * 4;
-    for (uint32_t t = 0; t < ss->T; t++) {
-        if (n[t] > (1u << 26) || (!ss->refine && n[t] != n[0]) || (ss->refine && cap != 0u && n[t] > cap))
-            return fail(RTMI_ERR_INVALID, nm + "the blob's counts are not a session's");
-    }
-    rtmi_scene *s = ss->s;
-    std::lock_guard<std::mutex> lock(s->mu);
-    HIP_TRY(hipSetDevice(s->device));
-    if (s->busy_recorded) HIP_TRY(hipEventSynchronize(s->busy.e));
-    HIP_TRY(hipMemcpy(ss->state.ptr, b + at, (size_t)ss->T * 9 * 64 * 8, hipMemcpyHostToDevice));
-    at += (size_t)ss->T * 9 * 64 * 8;
-    HIP_TRY(hipMemcpy(ss->bounces.ptr, b + at, (size_t)ss->T * 64 * 4, hipMemcpyHostToDevice));
-    ss->n = n;
-    ss->last_cap = cap; ss->last_abs = abs_tol; ss->last_rel = rel_tol;
-    ss->failed = false;
-    return RTMI_OK;
-}
-
-extern "C" int rtmi_session_merge(rtmi_session *dst, const rtmi_session *src) {
-    const std::string nm = "rtmi_session_merge: ";
-    int rc;
-    if ((rc = session_usable(dst, nm, false)) || (rc = session_usable(src, nm, false))) return rc;
-    if (dst == src) return fail(RTMI_ERR_INVALID, nm + "dst and src are one session");
-    const std::vector<uint8_t> ha = session_header(dst), hb = session_header(src, &dst->o.first_sample);
-    if (std::memcmp(ha.data(), hb.data(), RTMI_SESSION_BLOB_IDENTITY) != 0) // equal identity except first_sample
-        return fail(RTMI_ERR_INVALID, nm + "the sessions' identity blocks differ");
-    const uint32_t nA = dst->n.empty() ? 0u : dst->n[0], nB = src->n.empty() ? 0u : src->n[0];
-    if ((uint64_t)src->o.first_sample != (uint64_t)dst->o.first_sample + nA)
-        return fail(RTMI_ERR_INVALID, nm + "the sample ranges are not adjacent: src.first_sample must equal dst.first_sample + dst's count");
-    if ((rc = session_check_count(nm, (uint64_t)dst->o.first_sample + nA + nB))) return rc;
-    if (dst->s->device != src->s->device)
-        return fail(RTMI_ERR_UNSUPPORTED, nm + "the sessions live on different devices: export one and import it next to the other");
-    if (nB == 0u) return RTMI_OK;
-    rtmi_scene *s = dst->s, *s2 = src->s;
-    std::unique_lock<std::mutex> l1(s->mu, std::defer_lock), l2;
-    if (s2 != s) {
-        l2 = std::unique_lock<std::mutex>(s2->mu, std::defer_lock);
-        std::lock(l1, l2);
-    } else {
-        l1.lock();
-    }
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = begin_blocking(s))) return rc;
-    if (s2 != s && s2->busy_recorded) HIP_TRY(hipEventSynchronize(s2->busy.e));
-    BusyMark busy{s, s->stream.s};
-    const size_t T = dst->T;
-    if (nA == 0u) {
-        HIP_TRY(hipMemcpyAsync(dst->state.ptr, src->state.ptr, T * 9 * 64 * sizeof(double), hipMemcpyDeviceToDevice, s->stream.s));
-        HIP_TRY(hipMemcpyAsync(dst->bounces.ptr, src->bounces.ptr, T * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s->stream.s));
-    } else {
-        const SessionMerge M{dst->state.ptr, src->state.ptr, dst->bounces.ptr, src->bounces.ptr, dst->T, (double)nA, (double)nB};
-        HIP_TRY(rtmi_session_launch_merge(s->stream.s, M));
-    }
-    const hipError_t e = hipStreamSynchronize(s->stream.s);
-    if (e != hipSuccess) {
-        dst->failed = true;
-        return fail(RTMI_ERR_DEVICE, nm + hipGetErrorString(e));
-    }
-    dst->n.assign(dst->T, nA + nB);
     return RTMI_OK;
 }
 

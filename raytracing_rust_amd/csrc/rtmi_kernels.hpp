@@ -57,9 +57,10 @@ extern template __global__ void rtmi_render_coop<false, false, 4, false, 2>(DevS
 #endif
 
 // Host: launch of a kernel whose block takes `lds` bytes of dynamic LDS.  Up to 48 KB a block gets as it is; above that
-// the kernel's limit is raised first (the cooperative kernels with a deep pool).  The error of either step.
+// the kernel's limit is raised first (the cooperative kernels with a deep pool).  The error of either step.  Hidden: where
+// an instantiation is not inlined it is no export of librtmi.so.
 template <typename... Params, typename... Args>
-inline hipError_t rtmi_launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+__attribute__((visibility("hidden"))) inline hipError_t rtmi_launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
                                   const Args &...args) {
     if (lds > 48u * 1024u) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),

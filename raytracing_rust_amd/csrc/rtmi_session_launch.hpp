@@ -1,5 +1,5 @@
 // rtmi_session_launch.hpp — launchers of the render-session kernels (include/rtmi_session.h), defined in rtmi_session.hip
-// and called by the session entry points in rtmi_device.hip.  All three work on the session's state alone, laid out
+// and called by the session entry points below them there.  All three work on the session's state alone, laid out
 // [tile][9][64] (sum r,g,b | m r,g,b | M2 r,g,b), one wavefront per tile, lane = pixel.
 #pragma once
 

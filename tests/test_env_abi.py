@@ -161,7 +161,7 @@ def test_checks_come_before_device_work():
     fixed = body_of("static int render_fixed(")
     assert "hip" not in fixed[:fixed.index("begin_call(")]
     # begin_call makes the attach checks (check_attached, no device call in it) before the path's first device call
-    begin = body_of("static int begin_call(")
+    begin = body_of("int begin_call(")
     assert begin.index("check_attached(") < begin.index("hipSetDevice")
     attached = body_of("static int check_attached(")
     for check in ("!s->has_env", "!s->has_lights"):

@@ -1,6 +1,6 @@
 """The owners of csrc/rtmi_hostkit.hpp (DeviceBuf, PinnedBuf, DeviceList, DeviceArena, DeviceStream, DeviceEvent), on the host.
 
-The three handles of rtmi_device.hip keep all their device and pinned memory in these owners and free nothing by hand, so a
+The three handles (rtmi_scene in rtmi_host.hpp, rtmi_multi in rtmi_multi.hip, rtmi_session in rtmi_session.hip) keep all their device and pinned memory in these owners and free nothing by hand, so a
 mistake here is a leak or a double free in every entry point, and no image test sees either.  This compiles the header
 alone against tests/hip_stub (the HIP calls it names, backed by malloc/free, with counters), under the address, leak and
 undefined-behaviour sanitizers, and runs it as a child process; nothing is loaded into Python.  DESIGN.md §36."""

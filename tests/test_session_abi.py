@@ -148,7 +148,7 @@ def test_calls_on_a_null_session_are_invalid():
 
 
 def test_entry_points_check_before_the_device():
-    src = open(os.path.join(ROOT, "raytracing_rust_amd", "csrc", "rtmi_device.hip")).read()
+    src = open(os.path.join(ROOT, "raytracing_rust_amd", "csrc", "rtmi_session.hip")).read()
 
     def body_of(signature):
         body = src[src.index(signature):]
