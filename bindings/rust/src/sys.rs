@@ -372,6 +372,21 @@ extern "C" {
         out: *mut f32,
         n: u32,
     ) -> c_int;
+    /// camera rays, samplers, medium sample and transform chains over scripted words (include/rtmi.h: RTMI_PROBE_PATH_*)
+    pub fn rtmi_probe_path(
+        scene: *mut RtmiScene,
+        op: c_int,
+        cams: *const RtmiCamera,
+        n_cams: u32,
+        xforms: *const RtmiXform,
+        n_xforms: u32,
+        input: *const f32,
+        words: *const u32,
+        out: *mut f32,
+        n: u32,
+    ) -> c_int;
+    /// word delivery of the Philox sources under lane divergence (include/rtmi.h)
+    pub fn rtmi_probe_stream(kind: c_int, seed: u64, script: *const u8, steps: u32, out: *mut u32, n: u32) -> c_int;
 }
 
 // ---- include/rtmi_f64.h: the f64 render mode ---------------------------------------------------------------------------

@@ -512,6 +512,47 @@ enum { RTMI_PROBE_GEOM_PRIM = 0, RTMI_PROBE_GEOM_AABB = 1, RTMI_PROBE_GEOM_MEDIU
 #define RTMI_PROBE_GEOM_OUT 10
 int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b, const rtmi_prim_meta *meta, uint32_t n_prims,
                     const rtmi_xform *xforms, uint32_t n_xforms, const float *in, float *out, uint32_t n);
+/* What happens between a hit and the next ray, as the render kernels evaluate it, one case per lane: the production
+ * camera_sample, rejection samplers, medium_sample and transform chains, drawing from a SCRIPTED word source instead of a
+ * Philox stream (a stream cannot be aimed at an event of probability 2^-72).  words: n cases of RTMI_PROBE_PATH_WORDS
+ * 32-bit words, delivered in order wherever the production code draws; a draw beyond the script delivers 0x80000000 (the
+ * samplers' p = 0, which they accept: the rejection loops end whatever the script holds) and raises the case's
+ * `exhausted`.  in: n cases of RTMI_PROBE_PATH_IN floats; out: n cases of RTMI_PROBE_PATH_OUT floats, of which the last
+ * two are the words consumed and exhausted (0 / 1), both as uint32 bits, for every op.
+ *   CAMERA          : in = {camera index, nx, ny, px, j} (uint32 bits); camera_sample of cams[index] for sample 0 of pixel
+ *                     (px, j) of an nx x ny image; out = ro (3), rd (3), rtime.
+ *   SPHERE, DISK    : random_in_unit_sphere / random_in_unit_disk; out = p (3).
+ *   MEDIUM_SAMPLE   : in = {t1, t2, t_min, closest, dn, neg_inv_density}; out = {taken (0 / 1), t_out (0 when not taken)}.
+ *   XFORM_ROUNDTRIP : in = world ray origin (3), direction (3), t, chain first and count (int32 bits), object-space
+ *                     normal (3); xform_ray down xforms[first .. first + count), p = o' + t d', xform_hit back;
+ *                     out = world point (3), world normal (3).
+ *   BOUNCE          : needs `scene` (every other op takes NULL).  in = ray origin (3), direction (3), time, t_min, t_max,
+ *                     the path's depth, then max_depth and flags (RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK) (uint32 bits;
+ *                     the last two are a render's per-launch values and must be the same in every case).  One turn of the
+ *                     per-lane path loop for a path with T = 1, L = 0: world_closest (the reference-topology walk) over the
+ *                     uploaded scene, its medium draws from the script, then shade_hit.  out = closest (+inf: no hit), item,
+ *                     primitive (-1: a medium or no hit) (int32 bits), medium (0 / 1), scattered (0 / 1), then the path's
+ *                     ro (3), rd (3), T (3), L (3) as shade_hit leaves them.
+ * RTMI_ERR_INVALID for an unknown op, a NULL array, a camera index outside [0, n_cams), nx or ny of 0, px >= nx, j >= ny,
+ * a chain outside [0, n_xforms) or longer than RTMI_PRIM_XF_MAX, BOUNCE without a scene, with other flags or with cases that
+ * differ in max_depth or flags; RTMI_ERR_DEVICE without a device. */
+enum { RTMI_PROBE_PATH_CAMERA = 0, RTMI_PROBE_PATH_SPHERE = 1, RTMI_PROBE_PATH_DISK = 2, RTMI_PROBE_PATH_MEDIUM_SAMPLE = 3,
+       RTMI_PROBE_PATH_XFORM_ROUNDTRIP = 4, RTMI_PROBE_PATH_BOUNCE = 5 };
+#define RTMI_PROBE_PATH_IN 12
+#define RTMI_PROBE_PATH_OUT 20
+#define RTMI_PROBE_PATH_WORDS 32
+int rtmi_probe_path(rtmi_scene *scene, int op, const rtmi_camera *cams, uint32_t n_cams, const rtmi_xform *xforms, uint32_t n_xforms,
+                    const float *in, const uint32_t *words, float *out, uint32_t n);
+/* Word delivery of the three Philox word sources of the render kernels while the lanes of a wavefront diverge.  kind: 0 the
+ * LDS ring (RngRing), 1 the register block (RngReg), 2 the register block with a stream id (RngNee, stream 3).  Lane i of
+ * the n lanes (wavefronts of 64) starts the stream (sample 0, pixel i) under the key `seed` and then follows its own row of
+ * script [n][steps] bytes, one byte per step: 0 = sits the step out, 1 = rng_uniform, 2 = rng_take2, 3 = rng_take3,
+ * 4 = rng_init for the lane's next sample (a new path joins).  out [n][steps][3] words: what each draw delivered, 0 where
+ * nothing was drawn; a single draw delivers a uniform, recorded as the word with its lower 8 bits cleared.
+ * RTMI_ERR_INVALID for an unknown kind, steps outside [1, RTMI_PROBE_STREAM_MAX_STEPS], a NULL array or a script byte
+ * above 4; RTMI_ERR_DEVICE without a device. */
+#define RTMI_PROBE_STREAM_MAX_STEPS 256
+int rtmi_probe_stream(int kind, uint64_t seed, const uint8_t *script, uint32_t steps, uint32_t *out, uint32_t n);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,14 @@ int rtmi_scene_attach_flips(rtmi_scene *scene, const uint32_t *prim_gaps, uint32
  * exactly +-0, an origin exactly on a surface with t_min = 0, negative t_min.  Such rays return the reference's record bit
  * for bit (tests/test_gpu_query_edges.py, class A), a NaN slab value at a BVH box (0 * inf: the origin in a box plane,
  * the direction parallel to it) included.
+ *   Supported range of |d|.  The hit record of a rect or cube needs no d.d and is the reference's at any scale.  Whatever
+ *     normalises the direction — a sphere's discriminant, a medium's |d|, and, where a mode scatters a caller's ray, the Metal and
+ *     Dielectric rules of its first segment — needs d.d = dx^2 + dy^2 + dz^2 to be a NORMAL fp32 number: 2^-63 <= |d| < 2^63
+ *     is always inside, and results there are scale-free (a power of two is exact).  Outside, fp32 differs from the
+ *     reference's f64, which is scale-free everywhere: where d.d overflows, d / |d| is 0; where d.d is a denormal
+ *     (denormals are kept), the normalised direction keeps only the bits d.d has left.  tests/test_path_contract.py pins
+ *     both (test_out_of_range_direction_magnitude_pins_documented_difference_from_the_reference), the device to the fp32
+ *     oracle bit for bit.  A caller with such rays rescales d by a power of two and t_min, t_max inversely: that is exact.
  *   In-plane rays.  A ray that starts in the plane of a rect or of a cube face (o_k equal to the plane's constant) with
  *     an infinite 1 / d_k — d_k = +-0, or a denormal d_k with |d_k| <= 2^-128, whose reciprocal overflows; denormals are
  *     kept — is accepted by Rect::hit anywhere in that infinite plane, with t = 0 * inf = NaN (rect.rs:46-51), and the

@@ -63,7 +63,13 @@ typedef struct {
  * NULL, spp == 0, max_depth == 0, an estimator outside 0..3, first_ray + n > 2^32, first_sample + spp > 2^32,
  * n * spp >= 2^31, ENV_NEE with env_select_p outside (0, 1], SKY with a map estimator, a missing attachment, and for a
  * ray that rtmi_trace refuses (the message names the ray).  RTMI_ERR_UNSUPPORTED for unknown flags.  All of these are
- * answered before any device work. */
+ * answered before any device work.
+ * Supported range of a caller's |d|: d.d must be a normal fp32 number (rtmi_query.h, "Supported range of |d|").  Outside it
+ * the FIRST segment's scatter differs from the reference: where d.d overflows (|d| >= 2^64 always) normalize(d) is 0, so
+ * a Metal reflects nothing and absorbs the path, and a Dielectric's cosine is inf / inf = NaN; where d.d is a denormal the
+ * scattered direction keeps only d.d's remaining bits.  Both are pinned against the fp32 oracle bit for bit
+ * (tests/test_path_contract.py, tests/test_gpu_path_contract.py).  Later segments are unaffected: scattered directions are
+ * O(1).  Rescaling d by a power of two, and the interval inversely, is exact and lifts the restriction. */
 int rtmi_radiance(rtmi_scene *scene, const rtmi_radiance_params *params, const rtmi_ray *rays, const float *time,
                   float *out_mean, float *out_stderr, float *out_samples, double *kernel_ms);
 

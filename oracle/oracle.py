@@ -167,6 +167,15 @@ def _load(name):
         "orc_probe_medium": (None, [vp, vp, vp, d, i, vp]),
         "orc_probe_shade": (None, [vp, vp, d, d, d, vp]),
         "orc_probe_uv": (None, [vp, i, vp]),
+        "orc_script": (None, [vp, C.c_uint32]),
+        "orc_script_consumed": (C.c_uint32, []),
+        "orc_sample_unit": (None, [i, vp]),
+        "orc_sample_unit_wrong": (None, [i, d, vp]),
+        "orc_medium_sample": (i, [d, d, d, d, d, d, i, vp]),
+        "orc_pixel_ray": (None, [vp, i, i, i, i, vp]),
+        "orc_camera_from_state": (vp, [vp]),
+        "orc_probe_point": (vp, [d, d, d, d]),
+        "orc_bounce": (None, [vp, vp, vp, d, d, d, i, i, i, vp]),
     }
     for name_, (res, args) in sig.items():
         fn = getattr(lib, name_)
@@ -515,6 +524,69 @@ class Oracle:
         out = np.zeros(21)
         self.lib.orc_camera_state(cam.h, out.ctypes.data)
         return out
+
+    # ---- the scripted word source (tests/test_path_contract.py): every call below sets the script, runs and clears it ----
+    def _scripted(self, words, call):
+        """call() with the render path's stream reading `words` (uint32) instead of Philox: (its result, words consumed,
+        exhausted: a draw went beyond the script and got 0x80000000)"""
+        w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1)
+        self.lib.orc_script(w.ctypes.data if len(w) else None, len(w))
+        try:
+            res = call()
+            used = int(self.lib.orc_script_consumed()) if len(w) else 0
+        finally:
+            self.lib.orc_script(None, 0)
+        return res, used, used > len(w)
+
+    def sample_unit(self, kind, words, wrong=None):
+        """random_in_unit_sphere (kind 0) / random_in_unit_disk (kind 1) over scripted words: (p, consumed, exhausted);
+        wrong=limit: the negative control that accepts |p|^2 <= limit instead of |p|^2 < 1"""
+        out = np.zeros(3)
+        if wrong is None:
+            call = lambda: self.lib.orc_sample_unit(kind, out.ctypes.data)  # noqa: E731
+        else:
+            call = lambda: self.lib.orc_sample_unit_wrong(kind, float(wrong), out.ctypes.data)  # noqa: E731
+        _, used, exh = self._scripted(words, call)
+        return out, used, exh
+
+    def medium_sample(self, t1, t2, t_min, t_max, dn, density, words, flags=0):
+        """ConstantMedium::hit after its two boundary queries (medium.rs:33-53): (taken, t, consumed, exhausted)"""
+        t = C.c_double(0.0)
+        tmx = 1.8e308 if t_max == float("inf") else t_max
+        tmn = -1.8e308 if t_min == -float("inf") else t_min
+        ok, used, exh = self._scripted(words, lambda: self.lib.orc_medium_sample(t1, t2, tmn, tmx, dn, density, flags, C.byref(t)))
+        return bool(ok), t.value, used, exh
+
+    def pixel_ray(self, cam, i, j, nx, ny, words):
+        """sample 0 of pixel (i, j) as the render takes it (tests/test.rs:66-68): (o (3), d (3), time), consumed, exhausted"""
+        out = np.zeros(7)
+        _, used, exh = self._scripted(words, lambda: self.lib.orc_pixel_ray(cam.h, i, j, nx, ny, out.ctypes.data))
+        return out, used, exh
+
+    def bounce(self, world, origin, direction, time, t_min, t_max, depth, max_depth, words, flags=0):
+        """one turn of color's loop for a path with T = 1, L = 0 at `depth` over scripted words: None without a hit, else
+        dict(t, p, normal, mat_kind, scattered, o, d, T, L, consumed, exhausted)"""
+        o, dd = _d3(origin), _d3(direction)
+        out = np.zeros(22)
+        tmx = 1.8e308 if t_max == float("inf") else t_max
+        _, used, exh = self._scripted(words, lambda: self.lib.orc_bounce(world.h, o.ctypes.data, dd.ctypes.data, time, t_min, tmx,
+                                                                         depth, max_depth, flags, out.ctypes.data))
+        if not out[0]:
+            return None
+        return {"t": out[1], "p": out[2:5].copy(), "normal": out[5:8].copy(), "mat_kind": int(out[8]), "scattered": bool(out[9]),
+                "o": out[10:13].copy(), "d": out[13:16].copy(), "T": out[16:19].copy(), "L": out[19:22].copy(),
+                "consumed": used, "exhausted": exh}
+
+    def ProbePoint(self, t, normal):
+        """test only: a hittable that reports a hit at parameter t with the given normal, whatever the ray; wrapped in
+        Traslate / Rotate, Oracle.hit returns the chain's round trip of that point"""
+        n = _d3(normal)
+        return _Obj(self.lib.orc_probe_point(t, n[0], n[1], n[2]))
+
+    def CameraFromState(self, state21):
+        """a camera from its 21 derived values (origin, lower_left_corner, horizontal, vertical, u, v, time0, time1, lens_radius)"""
+        s = np.ascontiguousarray(state21, dtype=np.float64).reshape(21)
+        return _Obj(self.lib.orc_camera_from_state(s.ctypes.data))
 
     def perlin_tables(self, tex):
         rv = np.zeros(768)

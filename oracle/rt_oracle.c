@@ -143,7 +143,19 @@ typedef struct {
     uint32_t ctr[4]; /* ctr[0] = next block index */
     uint32_t buf[4];
     int pos; /* 4 = empty */
+    const uint32_t *script; /* not NULL: the blocks come from this list instead of Philox (orc_script) */
 } Stream;
+
+/* the `rand::thread_rng()` of the render path: one stream per (pixel, sample) */
+static Stream g_rng;
+
+/* A scripted word source for the per-operation tests (tests/test_path_contract.py): while a script is set, every
+ * stream_init of the render path's stream points it at the start of the list, and the stream then delivers the list's
+ * words in order wherever the path draws.  A draw beyond the list delivers 0x80000000 (u = 0.5, the samplers' p = 0,
+ * which they accept: no rejection loop outlives the list).  The words are handed out through the stream's 4-word
+ * buffer, so a draw costs what it cost; the words consumed are counted from the blocks filled (orc_script_consumed). */
+static const uint32_t *g_script = NULL;
+static uint32_t g_script_len = 0;
 
 static void stream_init(Stream *s, uint64_t seed, uint32_t sample, uint32_t pixel, uint32_t stream_id) {
     s->key[0] = (uint32_t)seed;
@@ -153,18 +165,27 @@ static void stream_init(Stream *s, uint64_t seed, uint32_t sample, uint32_t pixe
     s->ctr[2] = pixel;
     s->ctr[3] = stream_id;
     s->pos = 4;
+    s->script = s == &g_rng ? g_script : NULL;
+}
+static void stream_fill(Stream *s) {
+    if (s->script) {
+        for (uint32_t k = 0; k < 4; k++) {
+            const uint64_t at = (uint64_t)s->ctr[0] * 4 + k;
+            s->buf[k] = at < g_script_len ? s->script[at] : 0x80000000u;
+        }
+    } else {
+        philox4x32_10(s->ctr, s->key, s->buf);
+    }
 }
 static uint32_t stream_u32(Stream *s) {
     if (s->pos == 4) {
-        philox4x32_10(s->ctr, s->key, s->buf);
+        stream_fill(s);
         s->ctr[0]++;
         s->pos = 0;
     }
     return s->buf[s->pos++];
 }
 
-/* the `rand::thread_rng()` of the render path: one stream per (pixel, sample) */
-static Stream g_rng;
 /* the `rand::thread_rng()` of scene construction (BVH axes, Perlin tables) */
 static Stream g_scene_rng;
 
@@ -294,7 +315,8 @@ typedef struct {
 typedef struct { D3 min, max; } AABBd; /* scene set-up stays f64 like the reference */
 typedef struct { V3 min, max; } AABB;
 
-enum { H_SPHERE = 0, H_MOVING_SPHERE, H_RECT, H_CUBE, H_LIST, H_FLIP, H_TRANSLATE, H_ROTATE, H_MEDIUM, H_BVH };
+enum { H_SPHERE = 0, H_MOVING_SPHERE, H_RECT, H_CUBE, H_LIST, H_FLIP, H_TRANSLATE, H_ROTATE, H_MEDIUM, H_BVH,
+       H_PROBE_POINT /* test only (orc_probe_point): a hit at a given t with a given normal, whatever the ray */ };
 struct Hittable {
     int kind;
     /* sphere / moving sphere */
@@ -686,6 +708,22 @@ static int list_hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, Hit
     return hit_anything;
 }
 
+/* ConstantMedium::hit after both boundary queries returned t1 and t2 — medium.rs:33-53; dn = ray.direction().norm() */
+static int medium_sample(REAL t1, REAL t2, REAL t_min, REAL t_max, REAL dn, REAL density, REAL *t_out) {
+    if (t1 < t_min) t1 = t_min;
+    if (t2 > t_max) t2 = t_max;
+    if (t1 < t2) {
+        REAL dist_inside = (t2 - t1) * dn;
+        COUNT(C_MEDIUM_DRAW);
+        REAL hit_distance = -((REAL)1.0 / density) * m_log(rng_uniform());
+        if (hit_distance < dist_inside) {
+            *t_out = t1 + hit_distance / dn;
+            return 1;
+        }
+    }
+    return 0;
+}
+
 static int hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, HitRecord *rec) {
     switch (h->kind) {
     case H_SPHERE: /* sphere.rs:37-77 */
@@ -700,6 +738,12 @@ static int hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, HitRecor
         return list_hit(h->sides, r, t_min, t_max, rec);
     case H_LIST:
         return list_hit(h, r, t_min, t_max, rec);
+    case H_PROBE_POINT: /* what every primitive does last: p = ray.point_at_parameter(t) in its own frame */
+        rec->t = h->radius; rec->u = 0; rec->v = 0;
+        rec->p = ray_at(r, h->radius);
+        rec->normal = h->c0;
+        rec->mat = NULL; rec->prim = NULL;
+        return 1;
     case H_FLIP: /* hittable.rs:78-83 */
         if (hit(h->child, r, t_min, t_max, rec)) {
             rec->normal = v_neg(rec->normal);
@@ -742,22 +786,15 @@ static int hit(const Hittable *h, const Ray *r, REAL t_min, REAL t_max, HitRecor
         HitRecord h1, h2;
         if (hit(h->child, r, -R_MAX, R_MAX, &h1)) {
             if (hit(h->child, r, h1.t + (REAL)0.0001, R_MAX, &h2)) {
-                if (h1.t < t_min) h1.t = t_min;
-                if (h2.t > t_max) h2.t = t_max;
-                if (h1.t < h2.t) {
-                    REAL dist_inside = (h2.t - h1.t) * v_norm(r->d);
-                    COUNT(C_MEDIUM_DRAW);
-                    REAL hit_distance = -((REAL)1.0 / h->density) * m_log(rng_uniform());
-                    if (hit_distance < dist_inside) {
-                        REAL t = h1.t + hit_distance / v_norm(r->d);
-                        rec->t = t;
-                        rec->u = 0; rec->v = 0;
-                        rec->p = ray_at(r, t);
-                        rec->normal = v3(1.0, 0.0, 0.0);
-                        rec->mat = &h->phase;
-                        rec->prim = NULL;
-                        return 1;
-                    }
+                REAL t;
+                if (medium_sample(h1.t, h2.t, t_min, t_max, v_norm(r->d), h->density, &t)) {
+                    rec->t = t;
+                    rec->u = 0; rec->v = 0;
+                    rec->p = ray_at(r, t);
+                    rec->normal = v3(1.0, 0.0, 0.0);
+                    rec->mat = &h->phase;
+                    rec->prim = NULL;
+                    return 1;
                 }
             }
         }
@@ -1464,6 +1501,12 @@ static Ray camera_get_ray(const Camera *c, REAL s, REAL t) {
     V3 dir = v_sub(v_add(v_add(c->llc, v_scale(c->horizontal, s)), v_scale(c->vertical, t)), origin);
     return ray_new(origin, dir, time);
 }
+/* one sample of pixel (i, j) from the render path's stream: u then v, then get_ray's draws — tests/test.rs:66-68 */
+static Ray pixel_ray(const Camera *cam, int i, int j, int nx, int ny) {
+    REAL u = ((REAL)i + rng_uniform()) / (REAL)nx;
+    REAL v = ((REAL)j + rng_uniform()) / (REAL)ny;
+    return camera_get_ray(cam, u, v);
+}
 
 /* ================================================================================== */
 /* exported builder API                                                                */
@@ -1589,6 +1632,12 @@ ORC_API void *orc_cube(double ax, double ay, double az, double bx, double by, do
     list_push(s, make_rect(0, ay, az, by, bz, bx, m));
     list_push(s, make_rect(0, ay, az, by, bz, ax, m));
     h->sides = s;
+    return h;
+}
+/* test only: the innermost object of a transform chain's round trip (tests/test_path_contract.py) */
+ORC_API void *orc_probe_point(double t, double nx, double ny, double nz) {
+    Hittable *h = new_hit(H_PROBE_POINT);
+    h->radius = (REAL)t; h->c0 = v3((REAL)nx, (REAL)ny, (REAL)nz);
     return h;
 }
 ORC_API void *orc_flip_normals(void *child) { Hittable *h = new_hit(H_FLIP); h->child = (Hittable *)child; return h; }
@@ -1883,9 +1932,7 @@ static int render_rows(void *cam_, void *world_, const RowsExt *x, int nx, int n
             for (int s = 0; s < ns; s++) {
                 stream_init(&g_rng, seed, (uint32_t)s, (uint32_t)(j * nx + i), 0);
                 COUNT(C_SAMPLES);
-                REAL u = ((REAL)i + rng_uniform()) / (REAL)nx;
-                REAL v = ((REAL)j + rng_uniform()) / (REAL)ny;
-                Ray ray = camera_get_ray(cam, u, v);
+                Ray ray = pixel_ray(cam, i, j, nx, ny);
                 V3 c;
                 g_bounces = 0;
                 if (x->env || nee) stream_init(&g_light_rng, seed, (uint32_t)s, (uint32_t)(j * nx + i), 3);
@@ -2131,6 +2178,85 @@ ORC_API void orc_get_ray(void *cam, double s, double t, uint64_t seed, double *o
     stream_init(&g_rng, seed, 0, 0, 0);
     Ray r = camera_get_ray((Camera *)cam, (REAL)s, (REAL)t);
     out7[0] = r.o.x; out7[1] = r.o.y; out7[2] = r.o.z; out7[3] = r.d.x; out7[4] = r.d.y; out7[5] = r.d.z; out7[6] = r.time;
+}
+/* ---- the scripted word source and the pieces of the path that draw from it (tests/test_path_contract.py); each only
+ *      calls the functions above ---- */
+/* words != NULL: the render path's stream reads this list from its next stream_init on (the caller keeps it alive);
+ * NULL: Philox again */
+ORC_API void orc_script(const uint32_t *words, uint32_t n) { g_script = words; g_script_len = words ? n : 0; }
+/* words the render path's stream has delivered since its last stream_init */
+ORC_API uint32_t orc_script_consumed(void) { return g_rng.ctr[0] * 4u - (uint32_t)(4 - g_rng.pos); }
+/* util.rs:4-24: kind 0 = random_in_unit_sphere, 1 = random_in_unit_disk */
+ORC_API void orc_sample_unit(int kind, double *out3) {
+    stream_init(&g_rng, 0, 0, 0, 0);
+    V3 p = kind == 0 ? random_in_unit_sphere() : random_in_unit_disk();
+    out3[0] = p.x; out3[1] = p.y; out3[2] = p.z;
+}
+/* the same samplers with `<= limit` for `< 1`: the negative controls of the acceptance band, never part of a render */
+ORC_API void orc_sample_unit_wrong(int kind, double limit, double *out3) {
+    stream_init(&g_rng, 0, 0, 0, 0);
+    for (;;) {
+        REAL x = rng_uniform(), y = rng_uniform(), z = kind == 0 ? rng_uniform() : (REAL)0.5;
+        V3 p = v3((REAL)2.0 * x - (REAL)1.0, (REAL)2.0 * y - (REAL)1.0, (REAL)2.0 * z - (REAL)1.0);
+        if (v_dot(p, p) <= (REAL)limit) { out3[0] = p.x; out3[1] = p.y; out3[2] = p.z; return; }
+    }
+}
+/* medium.rs:33-53 after the two boundary queries; returns 1 and the t of the scatter, or 0 */
+ORC_API int orc_medium_sample(double t1, double t2, double t_min, double t_max, double dn, double density, int flags, double *t_out) {
+    g_flags = flags;
+    stream_init(&g_rng, 0, 0, 0, 0);
+    REAL tmn = t_min <= -1.7e308 ? -R_MAX : (REAL)t_min;
+    REAL tmx = t_max >= 1.7e308 ? R_MAX : (REAL)t_max;
+    REAL t = 0;
+    int taken = medium_sample((REAL)t1, (REAL)t2, tmn, tmx, (REAL)dn, (REAL)density, &t);
+    *t_out = taken ? t : 0.0;
+    return taken;
+}
+/* sample 0 of pixel (i, j) of an nx x ny image as render_rows takes it */
+ORC_API void orc_pixel_ray(void *cam, int i, int j, int nx, int ny, double *out7) {
+    stream_init(&g_rng, 0, 0, (uint32_t)j * (uint32_t)nx + (uint32_t)i, 0);
+    Ray r = pixel_ray((Camera *)cam, i, j, nx, ny);
+    out7[0] = r.o.x; out7[1] = r.o.y; out7[2] = r.o.z; out7[3] = r.d.x; out7[4] = r.d.y; out7[5] = r.d.z; out7[6] = r.time;
+}
+/* One turn of color_throughput's loop for a path with T = 1, L = 0 at `depth`: world.hit under the ray's own interval, the
+ * emission, and the scatter unless depth >= max_depth.  Draws come from the render path's stream (a script, when set).
+ * out22 = {hit, t, hit point (3), normal (3), material kind, scattered, scattered origin (3), direction (3), T (3),
+ * L (3)}; without a hit only out[0] = 0 is written. */
+ORC_API void orc_bounce(void *world, const double *o, const double *d, double time, double t_min, double t_max, int depth,
+                        int max_depth, int flags, double *out22) {
+    g_flags = flags;
+    stream_init(&g_rng, 0, 0, 0, 0);
+    Ray r = ray_new(v3((REAL)o[0], (REAL)o[1], (REAL)o[2]), v3((REAL)d[0], (REAL)d[1], (REAL)d[2]), (REAL)time);
+    REAL tmn = t_min <= -1.7e308 ? -R_MAX : (REAL)t_min;
+    REAL tmx = t_max >= 1.7e308 ? R_MAX : (REAL)t_max;
+    HitRecord rec;
+    for (int k = 0; k < 22; k++) out22[k] = 0.0;
+    if (!hit((Hittable *)world, &r, tmn, tmx, &rec)) return;
+    out22[0] = 1.0; out22[1] = rec.t;
+    out22[2] = rec.p.x; out22[3] = rec.p.y; out22[4] = rec.p.z;
+    out22[5] = rec.normal.x; out22[6] = rec.normal.y; out22[7] = rec.normal.z;
+    out22[8] = rec.mat->kind;
+    V3 T = v3(1, 1, 1), L = v_mul(T, mat_emitted(rec.mat, rec.u, rec.v, rec.p));
+    Ray sc = r; V3 att;
+    if (depth < max_depth && mat_scatter(rec.mat, &r, &rec, &sc, &att)) {
+        out22[9] = 1.0;
+        T = v_mul(T, att);
+    }
+    out22[10] = sc.o.x; out22[11] = sc.o.y; out22[12] = sc.o.z; out22[13] = sc.d.x; out22[14] = sc.d.y; out22[15] = sc.d.z;
+    out22[16] = T.x; out22[17] = T.y; out22[18] = T.z; out22[19] = L.x; out22[20] = L.y; out22[21] = L.z;
+}
+/* a camera from its derived state (rtmi_camera's 21 values) instead of Camera::new's arguments: the working-precision
+ * fields are the given values rounded once */
+ORC_API void *orc_camera_from_state(const double *s21) {
+    Camera *c = (Camera *)arena_alloc(sizeof(Camera));
+    D3 *v[6] = {&c->origind, &c->llcd, &c->hord, &c->verd, &c->ud, &c->vd};
+    for (int i = 0; i < 6; i++) { v[i]->x = s21[3 * i]; v[i]->y = s21[3 * i + 1]; v[i]->z = s21[3 * i + 2]; }
+    c->time0d = s21[18]; c->time1d = s21[19]; c->lens_radiusd = s21[20];
+    c->origin = d3_to_v3(c->origind); c->llc = d3_to_v3(c->llcd);
+    c->horizontal = d3_to_v3(c->hord); c->vertical = d3_to_v3(c->verd);
+    c->u = d3_to_v3(c->ud); c->v = d3_to_v3(c->vd);
+    c->time0 = (REAL)c->time0d; c->time1 = (REAL)c->time1d; c->lens_radius = (REAL)c->lens_radiusd;
+    return c;
 }
 ORC_API void orc_reset_counters(void) { memset(g_cnt, 0, sizeof(g_cnt)); }
 ORC_API int orc_get_counters(uint64_t *out, int n) {

@@ -50,6 +50,9 @@ ITEMFLAG_LISTSCAN_BEGIN, ITEMFLAG_LISTSCAN_MEMBER, ITEMFLAG_LISTSCAN_END = 32, 6
 RTMI_ITEMFLAG_GATE_OUTER_SHIFT = 12  # DEFERRED items: how many leading transforms belong to the enclosing BVH item (bits 12..15)
 PROBE_GEOM_PRIM, PROBE_GEOM_AABB, PROBE_GEOM_MEDIUM, PROBE_GEOM_SHADE, PROBE_GEOM_UV = 0, 1, 2, 3, 4  # rtmi_probe_geom
 PROBE_GEOM_IN, PROBE_GEOM_OUT = 16, 10  # floats per case
+PROBE_PATH_CAMERA, PROBE_PATH_SPHERE, PROBE_PATH_DISK, PROBE_PATH_MEDIUM_SAMPLE, PROBE_PATH_XFORM_ROUNDTRIP = 0, 1, 2, 3, 4  # rtmi_probe_path
+PROBE_PATH_BOUNCE = 5
+PROBE_PATH_IN, PROBE_PATH_OUT, PROBE_PATH_WORDS = 12, 20, 32  # floats per case; scripted words per case
 XF_TRANSLATE, XF_ROTATE_X, XF_ROTATE_Y, XF_ROTATE_Z, XF_GATE_MIN, XF_GATE_MAX, XF_INNER_MEDIUM = 0, 1, 2, 3, 4, 5, 6
 
 
@@ -407,6 +410,8 @@ def _tables():
             "rtmi_probe_philox": (i, [vp, vp, vp, u32]),
             "rtmi_probe_xform": (i, [P(Xform), u32, vp, vp, vp, u32]),
             "rtmi_probe_geom": (i, [i, vp, vp, vp, u32, vp, u32, vp, vp, u32]),
+            "rtmi_probe_path": (i, [vp, i, vp, u32, vp, u32, vp, vp, vp, u32]),
+            "rtmi_probe_stream": (i, [i, u64, vp, u32, vp, u32]),
         },
         "rtmi_math.h": {},  # inline helpers only
         "rtmi_f64.h": {

@@ -38,6 +38,7 @@
 
 #include "rtmi_kernels.hpp"
 #include "rtmi_render_launch.hpp"
+#include "rtmi_probe_path_launch.hpp"
 #include "rtmi_f64_types.hpp"
 #include "rtmi_f64_plan.hpp"
 #include "rtmi_adaptive.h"
@@ -1292,6 +1293,89 @@ extern "C" int rtmi_probe_geom(int op, const float *prim_a, const float *prim_b,
     sc.has_prim_xf = has_prim_xf;
     HIP_TRY(rtmi_render_launch_probe_geom(op, sc, d_in, d_out, n));
     HIP_TRY(hipMemcpy(out, d_out, (size_t)n * RTMI_PROBE_GEOM_OUT * 4, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+extern "C" int rtmi_probe_path(rtmi_scene *s, int op, const rtmi_camera *cams, uint32_t n_cams, const rtmi_xform *xforms, uint32_t n_xforms,
+                               const float *in, const uint32_t *words, float *out, uint32_t n) {
+    if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
+    if (op < RTMI_PROBE_PATH_CAMERA || op > RTMI_PROBE_PATH_BOUNCE) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: unknown op");
+    if (op == RTMI_PROBE_PATH_BOUNCE && !s) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: BOUNCE needs a scene");
+    if (n == 0) return RTMI_OK;
+    if (!in || !words || !out || (n_cams && !cams) || (n_xforms && !xforms)) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: missing array");
+    for (uint32_t i = 0; i < n; i++) { // everything a lane indexes with, before any launch
+        const float *a = in + (size_t)RTMI_PROBE_PATH_IN * i;
+        if (op == RTMI_PROBE_PATH_CAMERA) {
+            uint32_t w[5];
+            memcpy(w, a, sizeof(w));
+            if (w[0] >= n_cams) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: camera index out of range");
+            if (w[1] == 0u || w[2] == 0u || w[3] >= w[1] || w[4] >= w[2]) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: pixel outside the image");
+        } else if (op == RTMI_PROBE_PATH_XFORM_ROUNDTRIP) {
+            int32_t fc[2];
+            memcpy(fc, a + 7, sizeof(fc));
+            if (fc[0] < 0 || fc[1] < 0 || (uint32_t)fc[1] > RTMI_PRIM_XF_MAX || (uint64_t)fc[0] + (uint64_t)fc[1] > n_xforms)
+                return fail(RTMI_ERR_INVALID, "rtmi_probe_path: transform chain out of range");
+        } else if (op == RTMI_PROBE_PATH_BOUNCE) { // max_depth and the flags are a launch's: one value each
+            if (memcmp(a + 10, in + 10, 8) != 0) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: BOUNCE cases differ in max_depth or flags");
+        }
+    }
+    for (uint32_t k = 0; k < n_xforms; k++)
+        if (xforms[k].kind < RTMI_XF_TRANSLATE || xforms[k].kind > RTMI_XF_ROTATE_Z) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: transform kind");
+    uint32_t bounce_words[2] = {0u, 0u}; // BOUNCE: max_depth and flags, the same in every case (checked above)
+    std::unique_lock<std::mutex> lock;
+    if (op == RTMI_PROBE_PATH_BOUNCE) {
+        memcpy(bounce_words, in + 10, sizeof(bounce_words));
+        if (bounce_words[1] & ~(uint32_t)(RTMI_FLAG_FACE_FORWARD | RTMI_FLAG_UV_BOOK)) return fail(RTMI_ERR_INVALID, "rtmi_probe_path: BOUNCE flags");
+        lock = std::unique_lock<std::mutex>(s->mu); // the handle is read under its mutex only; no device work before this
+        HIP_TRY(hipSetDevice(s->device));
+        if (int rc = begin_blocking(s)) return rc;
+    }
+    std::vector<DevCamera> dc(n_cams ? n_cams : 1);
+    for (uint32_t c = 0; c < n_cams; c++) dc[c] = dev_camera(&cams[c]);
+    DevCamera *d_cams;
+    rtmi_xform *d_xf;
+    float *d_in, *d_out;
+    uint32_t *d_words;
+    const auto layout = [&](Carve256 &c) {
+        d_cams = c.take<DevCamera>(dc.size()); d_xf = c.take<rtmi_xform>(n_xforms ? n_xforms : 1);
+        d_in = c.take<float>((size_t)n * RTMI_PROBE_PATH_IN); d_words = c.take<uint32_t>((size_t)n * RTMI_PROBE_PATH_WORDS);
+        d_out = c.take<float>((size_t)n * RTMI_PROBE_PATH_OUT);
+    };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc(layout));
+    HIP_TRY(hipMemcpy(d_cams, dc.data(), dc.size() * sizeof(DevCamera), hipMemcpyHostToDevice));
+    if (n_xforms) HIP_TRY(hipMemcpy(d_xf, xforms, n_xforms * sizeof(rtmi_xform), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_in, in, (size_t)n * RTMI_PROBE_PATH_IN * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_words, words, (size_t)n * RTMI_PROBE_PATH_WORDS * 4, hipMemcpyHostToDevice));
+    PathProbe B;
+    memset(&B, 0, sizeof(B));
+    B.cams = d_cams; B.xforms = d_xf; B.in = d_in; B.words = d_words; B.out = d_out; B.n = n;
+    if (op == RTMI_PROBE_PATH_BOUNCE) {
+        B.sc = s->dev;
+        B.max_depth = bounce_words[0];
+        B.ext = ((bounce_words[1] & RTMI_FLAG_FACE_FORWARD) ? RTMI_EXT_FACE_FORWARD : 0u) |
+                ((bounce_words[1] & RTMI_FLAG_UV_BOOK) ? RTMI_EXT_UV_BOOK : 0u);
+    }
+    HIP_TRY(rtmi_probe_path_launch(op, B));
+    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * RTMI_PROBE_PATH_OUT * 4, hipMemcpyDeviceToHost));
+    return RTMI_OK;
+}
+extern "C" int rtmi_probe_stream(int kind, uint64_t seed, const uint8_t *script, uint32_t steps, uint32_t *out, uint32_t n) {
+    if (rtmi_device_count() <= 0) return fail(RTMI_ERR_DEVICE, "no HIP device available");
+    if (kind < 0 || kind > 2) return fail(RTMI_ERR_INVALID, "rtmi_probe_stream: unknown kind");
+    if (steps < 1u || steps > RTMI_PROBE_STREAM_MAX_STEPS) return fail(RTMI_ERR_INVALID, "rtmi_probe_stream: steps out of range");
+    if (n == 0) return RTMI_OK;
+    if (!script || !out) return fail(RTMI_ERR_INVALID, "rtmi_probe_stream: missing array");
+    const size_t cells = (size_t)n * steps;
+    for (size_t c = 0; c < cells; c++)
+        if (script[c] > 4u) return fail(RTMI_ERR_INVALID, "rtmi_probe_stream: script byte above 4");
+    uint8_t *d_script;
+    uint32_t *d_out;
+    const auto layout = [&](Carve256 &c) { d_script = c.take<uint8_t>(cells); d_out = c.take<uint32_t>(cells * 3); };
+    DeviceArena mem;
+    HIP_TRY(mem.alloc(layout));
+    HIP_TRY(hipMemcpy(d_script, script, cells, hipMemcpyHostToDevice));
+    HIP_TRY(rtmi_probe_stream_launch(kind, (uint32_t)seed, (uint32_t)(seed >> 32), d_script, steps, d_out, n));
+    HIP_TRY(hipMemcpy(out, d_out, cells * 3 * 4, hipMemcpyDeviceToHost));
     return RTMI_OK;
 }
 extern "C" int rtmi_probe_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out, uint32_t n) {

@@ -37,10 +37,10 @@ def test_every_prototype_agrees_with_its_table_and_with_rust():
             assert [kit.rust_is_pointer(t) for t in rargs] == [kit.c_class(a) == "ptr" for a in proto[1]], name
             assert rret is None or kit.rust_is_pointer(rret) == (kit.c_class(proto[0]) == "ptr"), name
             seen_rust += 1
-    assert seen == sum(len(t) for t in abi.FAMILIES.values()) == 108
+    assert seen == sum(len(t) for t in abi.FAMILIES.values()) == 110
     for table in abi.FAMILIES.values():
         assert all(isinstance(args, list) for _, args in table.values())  # no function goes without argtypes
-    assert seen_rust == len(rust) == 108 - len(NOT_IN_RUST) == 99
+    assert seen_rust == len(rust) == 110 - len(NOT_IN_RUST) == 101
 
 
 class _Recorder:
