@@ -1556,3 +1556,38 @@ extern "C" {
 /// RTMI_FLAG_BATCH_COOP: a flag of rtmi_radiance, rtmi_gather, rtmi_sparse_render, rtmi_sparse_refine, rtmi_render_pixelwise
 /// and rtmi_render_window (and their _device forms): the paths trace on the wave-cooperative kernel, same bits
 pub const FLAG_BATCH_COOP: u32 = 2097152;
+
+// ---- include/rtmi_update.h: edits of a resident scene (move primitives, refit the trees on the device) -----------------
+// (the RTMI_SCENE_WORDS_* selectors of rtmu_probe_scene_words are 0..8 in the header's order)
+
+extern "C" {
+    /// mask[n_items]: 1 = a BVH item rtmu_scene_update_prims can refit; host code
+    pub fn rtmu_refittable(desc: *const RtmiSceneDesc, mask: *mut u8) -> c_int;
+    /// the refit of the items that own a primitive of [first, first + count), evaluated on the host into the caller's arrays
+    pub fn rtmu_refit_desc(
+        desc: *const RtmiSceneDesc,
+        first: u32,
+        count: u32,
+        items: *mut RtmiItem,
+        nodes: *mut RtmiBvhNode,
+        alt_nodes: *mut RtmiBvh4Node,
+        prim_gate: *mut f32,
+    ) -> c_int;
+    /// builds the handle's update tables ahead of its first update (which otherwise waits for the handle and allocates)
+    pub fn rtmu_scene_update_prepare(scene: *mut RtmiScene) -> c_int;
+    /// blocking; a, b: count * 4 floats each, b may be NULL
+    pub fn rtmu_scene_update_prims(scene: *mut RtmiScene, first: u32, count: u32, a: *const f32, b: *const f32) -> c_int;
+    /// the same from device memory, asynchronous on `stream`
+    pub fn rtmu_scene_update_prims_device(
+        scene: *mut RtmiScene,
+        first: u32,
+        count: u32,
+        d_a: *const c_void,
+        d_b: *const c_void,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// blocking; replaces transform records of item chains (and of list primitives' chains), kinds kept
+    pub fn rtmu_scene_update_xforms(scene: *mut RtmiScene, first: u32, count: u32, recs: *const RtmiXform) -> c_int;
+    /// test hook: one of the handle's device arrays copied to the host
+    pub fn rtmu_probe_scene_words(scene: *mut RtmiScene, which: c_int, out: *mut c_void, cap: usize, need: *mut usize) -> c_int;
+}

@@ -372,6 +372,11 @@ class WindowOpts(C.Structure):
 
 RTMI_WINDOW_MAX_RADIUS = 16
 
+# RTMI_SCENE_WORDS_* of include/rtmi_update.h, in the header's order: the device arrays rtmu_probe_scene_words copies out
+# (names of their own, like FLAG_BATCH_COOP above; tests/test_update_abi.py compares them with the header)
+SCENE_WORDS = {"items": 0, "prim_a": 1, "prim_b": 2, "gate": 3, "nodes": 4, "alt_nodes": 5, "leaf_rec": 6, "shade_prim": 7,
+               "xforms": 8}
+
 
 # ---- the C ABI of librtmi.so: per header of include/, name -> (restype, argtypes) ---------------------------------------------
 # load_rtmi() applies these tables and the *_SYMBOLS lists below are their keys, so a function cannot be listed without a
@@ -566,6 +571,50 @@ RTMI_SPARSE_SYMBOLS = list(FAMILIES["rtmi_sparse.h"])
 RTMI_PIXELWISE_SYMBOLS = list(FAMILIES["rtmi_pixelwise.h"])
 RTMI_WINDOW_SYMBOLS = list(FAMILIES["rtmi_window.h"])
 
+
+# ---- the scene updates (include/rtmi_update.h): a family of its own, prefix rtmu_ ----------------------------------------------
+# Not part of FAMILIES: those tables are the render ABI, whose size tests/test_abi_signatures.py pins; tests/test_update_abi.py
+# compares these two with the header, with sys.rs and with what the libraries export.  load_rtmi() applies UPDATE_ENTRIES;
+# the host library's wrappers are bound by bind_host_update(), which Host() calls.
+def _update_tables():
+    vp, i, u32, sz, P = C.c_void_p, C.c_int, C.c_uint32, C.c_size_t, C.POINTER
+    desc = P(SceneDesc)
+    entries = {
+        "rtmu_probe_scene_words": (i, [vp, i, vp, sz, P(sz)]),
+        "rtmu_refit_desc": (i, [desc, u32, u32, P(Item), P(BvhNode), P(Bvh4Node), vp]),
+        "rtmu_refittable": (i, [desc, vp]),
+        "rtmu_scene_update_prepare": (i, [vp]),
+        "rtmu_scene_update_prims": (i, [vp, u32, u32, vp, vp]),
+        "rtmu_scene_update_prims_device": (i, [vp, u32, u32, vp, vp, vp]),
+        "rtmu_scene_update_xforms": (i, [vp, u32, u32, P(Xform)]),
+    }
+    host = {
+        "rthu_refittable": (i, [vp, vp]),
+        "rthu_update_prepare": (i, [vp]),
+        "rthu_update_prims": (i, [vp, u32, u32, vp, vp]),
+        "rthu_update_prims_device": (i, [vp, u32, u32, vp, vp, vp]),
+        "rthu_update_xforms": (i, [vp, u32, u32, P(Xform)]),
+        "rthu_prims_of": (i, [vp, vp, vp, u32, P(u32)]),
+        "rthu_probe_scene_words": (i, [vp, i, vp, sz, P(sz)]),
+    }
+    return entries, host
+
+
+UPDATE_ENTRIES, UPDATE_HOST_ENTRIES = _update_tables()
+
+
+def _bind(lib, table):
+    for name, (res, args) in table.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
+def bind_host_update(lib):
+    """Sets the signatures of the update wrappers of librt_host.so (UPDATE_HOST_ENTRIES) on a loaded library."""
+    return _bind(lib, UPDATE_HOST_ENTRIES)
+
 _rtmi = None
 _host = None
 
@@ -584,6 +633,7 @@ def load_rtmi():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
+    _bind(lib, UPDATE_ENTRIES)
     _rtmi = lib
     return lib
 

@@ -20,7 +20,8 @@ INCLUDE = os.path.join(_ROOT, "include")
 # (build_rtmi): the headline kernels and the C ABI (rtmi_device), the lean instantiations (rtmi_lean), the one-tree
 # instantiation of the headline kernel (rtmi_onetree), the two alternative kernels kept for the parity tests (rtmi_alt),
 # then one unit per render mode, named after its header in include/, and the kernel-less host unit of the multi-device
-# handle (rtmi_multi), and the path probe over its scripted word source (rtmi_probe_path).
+# handle (rtmi_multi), the path probe over its scripted word source (rtmi_probe_path), and the
+# scene updates: a kernel-less host unit and the unit of its two kernels (rtmi_update, rtmi_update_dev).
 _RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_onetree.hip", True), ("rtmi_alt.hip", True), ("rtmi_f64.hip", False),
                ("rtmi_adaptive.hip", True), ("rtmi_features.hip", True), ("rtmi_denoise.hip", False), ("rtmi_nee.hip", True),
                ("rtmi_env.hip", True), ("rtmi_adaptive_nee.hip", True), ("rtmi_roulette.hip", True),
@@ -29,7 +30,8 @@ _RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_onetr
                ("rtmi_gather.hip", True), ("rtmi_temporal.hip", False), ("rtmi_frame.hip", False),
                ("rtmi_tonemap.hip", False), ("rtmi_upscale.hip", False), ("rtmi_sparse.hip", True),
                ("rtmi_pixelwise.hip", True), ("rtmi_window.hip", True), ("rtmi_batch_coop.hip", True),
-               ("rtmi_multi.hip", False), ("rtmi_probe_path.hip", False))
+               ("rtmi_multi.hip", False), ("rtmi_probe_path.hip", False), ("rtmi_update.hip", False),
+               ("rtmi_update_dev.hip", False))
 _PUBLIC_HEADERS = sorted(glob.glob(os.path.join(INCLUDE, "*.h")))
 RTMI_SRC = [os.path.join(_PKG, "csrc", name) for name, _ in _RTMI_UNITS]
 HOST_SRC = [os.path.join(_PKG, "host", "rt_host.cpp"), os.path.join(_PKG, "host", "rt_host_c.cpp")]

@@ -25,6 +25,8 @@
 #include "rtmi_render_launch.hpp"
 #include "rtmi_adaptive_launch.hpp"
 #include "rtmi_light_launch.hpp"
+#include "rtmi_refit.hpp"
+#include "rtmi_update_launch.hpp"
 #include "rtmi_hostkit.hpp"
 
 #define HIP_TRY(expr) RTMI_HIP_TRY("", false, expr, #expr)
@@ -115,6 +117,23 @@ struct RTMI_HIDDEN rtmi_scene {
     DeviceBuf<float> env_tables;  // row_cdf [h] | row_p [h] | col_cdf [h][w] | col_p [h][w]
     uint32_t env_w = 0, env_h = 0;
     bool env_sampled = false;     // the map's total weight is > 0
+    // scene updates (include/rtmi_update.h): the topology read back from the device on the first update — the plan of the
+    // refit, per primitive its type, whether it emits and the MEDIUM item that carries a copy of it —, its device tables and
+    // the scratch of the refit kernel, then the staging of the blocking form (grow-only); freed with the handle
+    bool up_ready = false;
+    RefitPlan up_plan;
+    std::vector<uint8_t> up_type, up_emits;
+    // ... and per transform record its kind, the item whose chain holds it (-1: a primitive's chain or none) and whether
+    // rtmu_scene_update_xforms may replace it (UP_XF_*, rtmi_update.hip)
+    std::vector<int32_t> up_xf_kind, up_xf_item, up_xf_slot; // slot: its place in that item's chain
+    std::vector<uint8_t> up_xf_state;
+    DeviceBuf<uint32_t> up_words;
+    DeviceBuf<RefitJob> up_jobs;
+    DeviceBuf<int32_t> up_medium_item; // [max(n_prims, 1)]
+    DeviceBuf<float4> up_scratch;      // [max(n_nodes, 1)][2]
+    uint32_t up_n_jobs = 0;
+    DeviceBuf<float> up_stage;         // planes A | B of a blocking update on the device
+    PinnedBuf<float> up_h_stage;       // ... and their pinned host copy
 };
 
 static inline uint32_t tiles_x_of(const rtmi_render_params *p) { return (p->nx + RTMI_TILE - 1) / RTMI_TILE; }

@@ -656,6 +656,120 @@ class Scene:
                                                           C.c_void_p(stream or 0), C.byref(st) if st else None))
         return _stats(st) if st else None
 
+    # ---- scene updates (include/rtmi_update.h): edits of the FLAT scene.  The host object graph this scene was lowered from
+    # (host.hit(...), a new host.lower(world)) keeps the old positions, and so do the double planes of the f64 mode.
+    def refittable(self):
+        """Per item of the description whether update_prims can refit it (rtmu_refittable): bool [n_items], True for the BVH
+        items whose primitives may move; LIST items are False, their primitives sit under no box and may always move."""
+        mask = np.zeros(max(self.desc().n_items, 1), np.uint8)
+        self.host._check(self.host.lib.rthu_refittable(self.h, mask.ctypes.data))
+        return mask[:self.desc().n_items] != 0
+
+    def _emitters_in(self, first, count):
+        """whether the range holds a primitive with a DIFFUSE_LIGHT material: a slice of a mask computed once (types and
+        materials do not change under the updates)"""
+        if getattr(self, "_emits", None) is None:
+            d = self.desc()
+            meta = np.ctypeslib.as_array(C.cast(d.prim_meta, C.POINTER(C.c_int32)), shape=(d.n_prims, 4)) if d.n_prims else np.zeros((0, 4), np.int32)
+            kinds = np.ctypeslib.as_array(C.cast(d.materials, C.POINTER(C.c_int32)), shape=(d.n_materials, 4))[:, 0] if d.n_materials else np.zeros(0, np.int32)
+            self._emits = kinds[meta[:, 0]] == abi.MAT_DIFFUSE_LIGHT  # (a copy: fancy indexing)
+        return bool(self._emits[first:first + count].any())
+
+    def prepare_updates(self):
+        """Builds the resident handle's update tables now (rtmu_scene_update_prepare): otherwise its first update does,
+        waiting for the calls enqueued on the handle and allocating — also the first update with torch tensors."""
+        self.host._check(self.host.lib.rthu_update_prepare(self.h))
+        return self
+
+    def update_prims(self, first, a, b=None):
+        """New planes A (and B) for the primitives [first, first + len(a)) of the scene, resident or not; a, b: float32
+        [n, 4] (rtmi.h, "primitives"); b=None keeps the planes B.  The trees of every BVH item the range touches are refit
+        on the device (rtmu_scene_update_prims); every handle bound to the scene stays valid.
+
+        numpy arrays: blocking.  The planes are also written into the lowered arrays and refit there (rtmu_refit_desc), so
+        desc() stays the description of what is resident; when the range holds an emitter, the light table and the light
+        tree that were attached are derived again from it and re-attached.
+
+        torch tensors on the scene's device: asynchronous on the current stream, no host copy (the _device entry) — and
+        the lowered arrays go STALE: desc(), arrays() and everything derived from them describe the scene before the
+        update.  Raises when the range holds an emitter while a light table is attached, which would have to be derived
+        from the stale description.  Inside refittable items finite planes, non-zero radii and cubes with min <= max are
+        the caller's contract.  The handle's first update waits for the handle and allocates: see prepare_updates().
+
+        Either form leaves the double planes of the f64 render mode at the positions the scene was lowered with: after an
+        update attach_f64() and render(precision="f64") raise Unsupported (and with the planes attached the update does)."""
+        if type(a).__module__.split(".")[0] == "torch":
+            return self._update_prims_torch(first, a, b)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 4 or (b is not None and b.shape != a.shape):
+            raise ValueError("update_prims takes float32 [n, 4] planes")
+        first, n = int(first), a.shape[0]
+        if first < 0 or first + n > self.desc().n_prims:
+            raise ValueError("primitives [%d, %d) are outside the scene's %d" % (first, first + n, self.desc().n_prims))
+        relight = n > 0 and self.uploaded and getattr(self, "lights_attached", False) and self._emitters_in(first, n)
+        tree = relight and getattr(self, "light_tree_attached", False)
+        self.host._check(self.host.lib.rthu_update_prims(self.h, first, n, a.ctypes.data, b.ctypes.data if b is not None else None))
+        if relight:
+            self.lights_attached = self.light_tree_attached = False
+            self.attach_lights()
+            if tree:
+                self.attach_light_tree()
+        return self
+
+    def _update_prims_torch(self, first, a, b):
+        import torch
+
+        if not self.uploaded:
+            raise HostError("update_prims with tensors needs an uploaded scene")
+        for t in (a,) if b is None else (a, b):
+            dev = t.device
+            if dev.type != "cuda" or (dev.index or 0) != self.device:
+                raise ValueError("the planes are on %s, the scene is on device %d" % (dev, self.device))
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 4 or t.shape != a.shape or not t.is_contiguous():
+                raise ValueError("update_prims takes contiguous float32 [n, 4] planes")
+        first, n = int(first), a.shape[0]
+        if first < 0 or first + n > self.desc().n_prims:
+            raise ValueError("primitives [%d, %d) are outside the scene's %d" % (first, first + n, self.desc().n_prims))
+        if n and getattr(self, "lights_attached", False) and self._emitters_in(first, n):
+            raise HostError("update_prims with tensors: the range holds an emitter and a light table is attached; the table "
+                            "would have to be derived from the stale host description (use numpy planes)")
+        self.host._check(self.host.lib.rthu_update_prims_device(
+            self.h, first, n, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
+            C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
+        return self
+
+    def update_xforms(self, first, records):
+        """Replaces the transform records [first, first + len(records)) of the flat scene (rtmu_scene_update_xforms):
+        records of the chains of top-level items (Traslate / Rotate around an item) and of list primitives' own chains.
+        records: abi.Xform objects or (kind, x, y, z) tuples — TRANSLATE: the offset; ROTATE_*: x = sin, y = cos of the
+        angle, as the lowering writes them; every record keeps its kind.  Blocking; the lowered array follows, so desc()
+        stays the description of what is resident.  No tree changes: items sit in a list, not under a box."""
+        recs = (abi.Xform * max(len(records), 1))(*[r if isinstance(r, abi.Xform) else abi.Xform(int(r[0]), r[1], r[2], r[3])
+                                                    for r in records])
+        self.host._check(self.host.lib.rthu_update_xforms(self.h, int(first), len(records), recs))
+        return self
+
+    def prims_of(self, obj):
+        """The indices (uint32, ascending) of the primitives of the flat scene that were lowered from a host object: from a
+        primitive itself, or from everything below a wrapper, a list, a ConstantMedium or a BVHNode."""
+        n = C.c_uint32(0)
+        self.host._check(self.host.lib.rthu_prims_of(self.h, obj.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        if n.value:
+            self.host._check(self.host.lib.rthu_prims_of(self.h, obj.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def device_words(self, which):
+        """One of the resident handle's device arrays as bytes (rtmu_probe_scene_words, a test hook): `which` is a key of
+        abi.SCENE_WORDS.  Waits for the calls enqueued on the handle."""
+        need = C.c_size_t(0)
+        self.host._check(self.host.lib.rthu_probe_scene_words(self.h, abi.SCENE_WORDS[which], None, 0, C.byref(need)))
+        out = np.zeros(need.value, np.uint8)
+        if need.value:
+            self.host._check(self.host.lib.rthu_probe_scene_words(self.h, abi.SCENE_WORDS[which], out.ctypes.data, need.value, None))
+        return out
+
     def trace(self, origins, directions, times=None, t_min=0.001, t_max=float("inf"), seed=0, first_ray=0,
               flags=abi.RTMI_FLAG_FAST_CULL):
         """Closest hits of a batch of rays (include/rtmi_query.h): for ray i the record of the reference's
@@ -1605,7 +1719,7 @@ class Host:
     precision = "host"
 
     def __init__(self):
-        self.lib = abi.load_host()
+        self.lib = abi.bind_host_update(abi.load_host())
 
     def _raise(self):
         msg = (self.lib.rth_last_error() or b"").decode()

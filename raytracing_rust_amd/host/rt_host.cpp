@@ -674,6 +674,7 @@ int SceneBuilder::push_prim(const Hittable &h0, bool flip, bool force_moving) {
     out.wide.prim_gate.insert(out.wide.prim_gate.end(), gate, gate + 8);
     out.prim_box.push_back(AABB(Vec3(0, 0, 0), Vec3(0, 0, 0)));
     out.prim_has_box.push_back(0);
+    out.prim_source.push_back(&h);
     return (int)out.prim_meta.size() - 1;
 }
 
@@ -1536,6 +1537,30 @@ LoweredScene lower_scene(const Hittable &world) {
     SceneBuilder b;
     b.lower_world(world);
     return std::move(b.out);
+}
+
+static void sources_below(const Hittable *h, std::vector<const Hittable *> &out) {
+    bool flip = false;
+    h = strip_wrappers(h, flip, nullptr);
+    if (auto l = dynamic_cast<const HittableList *>(h)) {
+        for (const auto &m : l->items()) sources_below(m.get(), out);
+    } else if (auto n = dynamic_cast<const BVHNode *>(h)) {
+        sources_below(n->left_.get(), out);
+        if (n->right_.get() != n->left_.get()) sources_below(n->right_.get(), out);
+    } else if (auto m = dynamic_cast<const ConstantMedium *>(h)) {
+        sources_below(m->boundary_.get(), out);
+    } else {
+        out.push_back(h);
+    }
+}
+std::vector<uint32_t> prims_of(const LoweredScene &ls, const Hittable &h) {
+    std::vector<const Hittable *> src;
+    sources_below(&h, src);
+    std::sort(src.begin(), src.end());
+    std::vector<uint32_t> out;
+    for (size_t p = 0; p < ls.prim_source.size(); p++)
+        if (std::binary_search(src.begin(), src.end(), ls.prim_source[p])) out.push_back((uint32_t)p);
+    return out;
 }
 
 // ======================================================================================

@@ -339,6 +339,8 @@ struct LoweredScene {
     std::vector<float> prim_gate;  // 8 floats per primitive: box of its parent BVHNode in the reference tree (rtmi.h)
     std::vector<AABB> prim_box;    // host only: true extent of a BVH primitive (its alternative tree is built on it)
     std::vector<char> prim_has_box;
+    std::vector<const Hittable *> prim_source; // host only: the object each primitive was lowered from, its wrappers stripped
+                                               // (prims_of; the world must outlive the lookups)
     uint32_t alt_max_depth = 0;    // deepest alternative tree (in 4-wide nodes)
     std::vector<rtmi_bvh4_node> alt_nodes; // the alternative trees
     std::vector<rtmi_bvh_node> nodes;
@@ -421,6 +423,10 @@ class SceneBuilder {
     std::map<const Material *, int> mat_ids_;
 };
 LoweredScene lower_scene(const Hittable &world);
+// The primitives of `ls` that were lowered from `h`: from a primitive itself, or from everything below a wrapper, a list, a
+// ConstantMedium or a BVHNode; ascending.  An object that occurs twice in the world (a node over one element does not
+// count: its leaf is stored once) names all its copies.
+std::vector<uint32_t> prims_of(const LoweredScene &ls, const Hittable &h);
 
 // ---- src/camera.rs + the render entry points -----------------------------------------------
 struct RenderOptions {

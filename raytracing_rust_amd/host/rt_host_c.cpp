@@ -22,6 +22,7 @@
 #include "rtmi_gather.h"
 #include "rtmi_frame.h"
 #include "rtmi_upscale.h"
+#include "rtmi_update.h"
 
 using namespace rt;
 
@@ -42,6 +43,8 @@ struct Obj {
     std::shared_ptr<LoweredScene> lowered;
     rtmi_scene *dev = nullptr;
     rtmi_multi *multi = nullptr; // the lowered scene resident on a device list (rth_upload_multi)
+    bool edited = false; // a scene update has edited the fp32 description (or the resident handle alone): the double planes
+                         // of the f64 render mode still hold the lowering's positions and are no longer attached
 };
 std::mutex g_mu;
 std::vector<Obj *> g_objs;
@@ -719,6 +722,8 @@ RTH_API int rth_camera_lower_f64(void *cam, rtmi_camera_f64 *out) { return guard
 RTH_API int rth_attach_f64(void *lowered) {
     return guard([&] {
         rtmi_scene *dev = DEV(lowered);
+        if (LOW(lowered)->edited)
+            throw Unsupported("rtmi_scene_attach_f64: the scene was edited by a scene update; its double planes hold the positions it was lowered with");
         const rtmi_scene_f64 w = LOW(lowered)->lowered->desc_f64();
         return done("rtmi_scene_attach_f64", rtmi_scene_attach_f64(dev, &w), CODED);
     });
@@ -729,6 +734,95 @@ RTH_API int rth_render_f64(void *lowered, void *cam, const rtmi_render_params *p
         rtmi_scene *dev = DEV(lowered);
         const rtmi_camera_f64 c = CAM(cam).lower_f64();
         return done("rtmi_render_f64", rtmi_render_f64(dev, &c, p, t_min, out_linear, out_rgb8, out_path_sig, stats), PLAIN);
+    });
+}
+// ---- scene updates (include/rtmi_update.h): edits of the FLAT scene; the object graph it was lowered from keeps the old
+// positions, and so do the double planes of the f64 render mode --------------------------------------------------------------
+RTH_API int rthu_refittable(void *lowered, uint8_t *mask) {
+    return guard([&] {
+        const rtmi_scene_desc d = LOW(lowered)->lowered->desc();
+        return done("rtmu_refittable", rtmu_refittable(&d, mask), CODED);
+    });
+}
+// New planes for [first, first + count) from host memory (b may be NULL): the resident handle first, when there is one —
+// it refuses what cannot be updated before anything changes —, then the lowered arrays and their refit, so that the
+// description stays the description of what is resident.
+RTH_API int rthu_update_prims(void *lowered, uint32_t first, uint32_t count, const float *a, const float *b) {
+    return guard([&] {
+        const char *name = "rtmu_scene_update_prims";
+        Obj *o = LOW(lowered);
+        LoweredScene &ls = *o->lowered;
+        if ((uint64_t)first + count > ls.prim_meta.size()) throw std::runtime_error(std::string(name) + ": the range leaves the primitives");
+        if (count == 0) return (int)RTH_OK;
+        if (!a) throw std::runtime_error(std::string(name) + ": a is NULL");
+        if (o->multi && !o->dev) DEV(lowered, name, "update");
+        if (o->dev)
+            if (int rc = done(name, rtmu_scene_update_prims(o->dev, first, count, a, b), CODED_UNSUPPORTED)) return rc;
+        const bool was_edited = o->edited;
+        o->edited = true;
+        const std::vector<float> old_a(ls.prim_a.begin() + (size_t)first * 4, ls.prim_a.begin() + (size_t)(first + count) * 4);
+        const std::vector<float> old_b(ls.prim_b.begin() + (size_t)first * 4, ls.prim_b.begin() + (size_t)(first + count) * 4);
+        std::copy(a, a + (size_t)count * 4, ls.prim_a.begin() + (size_t)first * 4);
+        if (b) std::copy(b, b + (size_t)count * 4, ls.prim_b.begin() + (size_t)first * 4);
+        const rtmi_scene_desc d = ls.desc();
+        const int rc = rtmu_refit_desc(&d, first, count, ls.items.data(), ls.nodes.data(), ls.alt_nodes.data(), d.prim_gate ? ls.prim_gate.data() : nullptr);
+        if (rc) { // (only without a resident handle: it refuses the same ranges)
+            o->edited = was_edited;
+            std::copy(old_a.begin(), old_a.end(), ls.prim_a.begin() + (size_t)first * 4);
+            std::copy(old_b.begin(), old_b.end(), ls.prim_b.begin() + (size_t)first * 4);
+        }
+        return done("rtmu_refit_desc", rc, CODED_UNSUPPORTED);
+    });
+}
+// ... from device memory, asynchronous on `stream`: the lowered arrays are NOT edited and go stale
+RTH_API int rthu_update_prepare(void *lowered) {
+    return guard([&] {
+        const char *name = "rtmu_scene_update_prepare";
+        return done(name, rtmu_scene_update_prepare(DEV(lowered, name, "update")), CODED);
+    });
+}
+RTH_API int rthu_update_prims_device(void *lowered, uint32_t first, uint32_t count, const void *d_a, const void *d_b, void *stream) {
+    return guard([&] {
+        const char *name = "rtmu_scene_update_prims_device";
+        const int rc = done(name, rtmu_scene_update_prims_device(DEV(lowered, name, "update"), first, count, d_a, d_b, stream), CODED_UNSUPPORTED);
+        if (count) LOW(lowered)->edited = true;
+        return rc;
+    });
+}
+// New transform records [first, first + count): the resident handle first, when there is one (it refuses what cannot be
+// replaced), then the lowered array.  Without a handle the kinds alone are checked here.
+RTH_API int rthu_update_xforms(void *lowered, uint32_t first, uint32_t count, const rtmi_xform *recs) {
+    return guard([&] {
+        const char *name = "rtmu_scene_update_xforms";
+        Obj *o = LOW(lowered);
+        LoweredScene &ls = *o->lowered;
+        if ((uint64_t)first + count > ls.xforms.size()) throw std::runtime_error(std::string(name) + ": the range leaves the transform records");
+        if (count == 0) return (int)RTH_OK;
+        if (!recs) throw std::runtime_error(std::string(name) + ": recs is NULL");
+        if (o->multi && !o->dev) DEV(lowered, name, "update");
+        if (o->dev)
+            if (int rc = done(name, rtmu_scene_update_xforms(o->dev, first, count, recs), CODED_UNSUPPORTED)) return rc;
+        for (uint32_t k = 0; k < count; k++)
+            if (recs[k].kind != ls.xforms[first + k].kind) throw std::runtime_error(std::string(name) + ": a record must keep its kind");
+        std::copy(recs, recs + count, ls.xforms.begin() + first);
+        o->edited = true;
+        return (int)RTH_OK;
+    });
+}
+// The primitives lowered from a host object (rt::prims_of): *n receives their number, out (when not NULL) the first
+// min(*n, cap) indices, ascending.
+RTH_API int rthu_prims_of(void *lowered, void *hittable, uint32_t *out, uint32_t cap, uint32_t *n) {
+    return guard([&] {
+        const std::vector<uint32_t> found = prims_of(*LOW(lowered)->lowered, *H(hittable));
+        if (n) *n = (uint32_t)found.size();
+        if (out) std::copy(found.begin(), found.begin() + std::min<size_t>(found.size(), cap), out);
+        return (int)RTH_OK;
+    });
+}
+RTH_API int rthu_probe_scene_words(void *lowered, int which, void *out, size_t cap, size_t *need) {
+    return guard([&] {
+        const char *name = "rtmu_probe_scene_words";
+        return done(name, rtmu_probe_scene_words(DEV(lowered, name, "update"), which, out, cap, need), CODED);
     });
 }
 RTH_API int rth_render_device(void *lowered, void *cam, const rtmi_render_params *p, void *d_texels, void *stream,
