@@ -1,5 +1,5 @@
 // rtmi_batch_coop_launch.hpp — launchers of the cooperative batch kernels (include/rtmi_batch_coop.h), defined in
-// rtmi_batch_coop.hip and called by radiance_enqueue, gather_enqueue and sparse_enqueue in rtmi_device.hip.  Included after
+// rtmi_batch_coop.hip and called by radiance_enqueue, gather_enqueue and sparse_enqueue in rtmi_batch.hip.  Included after
 // rtmi_light_launch.hpp and the three batch launch headers (RadianceBatch, GatherBatch, SparseBatch).
 #pragma once
 

@@ -1,6 +1,6 @@
 // rtmi_bvh_block.hpp — workgroup-cooperative BVH traversal: the wavefronts of a workgroup share ONE work stack.
-// Part of the single translation unit rtmi_device.hip (device code is header-only so that every
-// kernel instantiation inlines the whole path); arithmetic contract as stated there.
+// Header-only device code, included by every unit that instantiates a kernel (header-only so that every
+// kernel instantiation inlines the whole path); arithmetic contract as stated in rtmi_device.hip.
 #pragma once
 #include "rtmi_bvh_coop.hpp"
 

@@ -29,4 +29,4 @@ public:
 };
 
 using Carve256 = Carve<256>; // the image units: every plane starts on a 256-byte boundary
-using Carve16 = Carve<16>;   // the probes of rtmi_device.hip
+using Carve16 = Carve<16>;   // the probes of rtmi_device.hip and rtmi_batch.hip

@@ -1,5 +1,5 @@
 // rtmi_gather_launch.hpp — launchers of the hemisphere-gather kernels (include/rtmi_gather.h), defined in rtmi_gather.hip
-// and called by rtmi_gather / rtmi_gather_device in rtmi_device.hip.
+// and called by rtmi_gather / rtmi_gather_device in rtmi_batch.hip.
 #pragma once
 
 // one slab of points on the device; the per-sample buffer is P.samples of the launch ([n][spp] Rad3, item k = i * spp + s)

@@ -1,6 +1,6 @@
 // rtmi_geom.hpp — instance transforms, the per-frame ray, box / sphere / rect / cube tests.
-// Part of the single translation unit rtmi_device.hip (device code is header-only so that every
-// kernel instantiation inlines the whole path); arithmetic contract as stated there.
+// Header-only device code, included by every unit that instantiates a kernel (header-only so that every
+// kernel instantiation inlines the whole path); arithmetic contract as stated in rtmi_device.hip.
 #pragma once
 #include "rtmi_types.hpp"
 

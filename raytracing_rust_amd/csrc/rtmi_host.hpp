@@ -1,8 +1,9 @@
 // rtmi_host.hpp — what the host units of librtmi.so share: the scene handle, the call helpers of the
 // render entry points and the estimator layer of the whole-image modes.  Hidden, not installed.  The helpers declared here
-// are defined in rtmi_device.hip, which still holds these layers, and called by rtmi_multi.hip and by the entry points of
-// rtmi_session.hip; neither launches a kernel itself: each goes through a *_launch.hpp seam into the unit that instantiates
-// the kernel.  A helper that one unit alone calls is static in that unit, not here.
+// are defined in rtmi_device.hip, which still holds these layers, and called by rtmi_multi.hip, by the entry points of
+// rtmi_session.hip and by the batch modes in rtmi_batch.hip; none of them launches a kernel itself: each goes
+// through a *_launch.hpp seam into the unit that instantiates the kernel.  A helper that one unit alone calls is static in
+// that unit, not here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "rtmi_f64_types.hpp"
 #include "rtmi_adaptive.h"
 #include "rtmi_roulette.h"
+#include "rtmi_query.h"
 #include "rtmi_light_coop.h"
 #include "rtmi_render_launch.hpp"
 #include "rtmi_adaptive_launch.hpp"
@@ -208,6 +210,9 @@ RTMI_HIDDEN int check_mode_params(const rtmi_render_params *p, uint32_t accepted
 RTMI_HIDDEN int grow_host_texels(PinnedBuf<rtmi_texel> &h, size_t ntex);
 RTMI_HIDDEN int reserve_texels(rtmi_scene *s, size_t ntex);
 RTMI_HIDDEN int grow_adaptive(rtmi_scene *s, uint32_t T);
+RTMI_HIDDEN DevCamera dev_camera(const rtmi_camera *cam);
+RTMI_HIDDEN bool boxes_valid(const rtmi_scene *s, const rtmi_camera *cam);
+RTMI_HIDDEN DevParams dev_params(const rtmi_scene *s, const rtmi_render_params *p);
 RTMI_HIDDEN int plan_traversal(rtmi_scene *s, const rtmi_render_params *p, bool coop, DevParams &P, bool &ext);
 RTMI_HIDDEN int begin_passes(rtmi_scene *s, hipStream_t stream);
 RTMI_HIDDEN int check_overflow(rtmi_scene *s);
@@ -222,9 +227,14 @@ RTMI_HIDDEN int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, cons
 RTMI_HIDDEN int wait_with_progress(rtmi_scene *const *scenes, hipEvent_t *done_ev, uint32_t n, const rtmi_render_params *p);
 
 // ---- the estimator layer ---------------------------------------------------------------------------------------------------
+RTMI_HIDDEN int check_adaptive(const rtmi_render_params *p, const rtmi_adaptive *a);
 RTMI_HIDDEN Estimator lit_estimator(const char *name, bool nee, bool env, float env_select_p, const char *null_scene);
+RTMI_HIDDEN Estimator estimator_of(const char *name, uint32_t estimator, float env_select_p, const char *null_scene);
 RTMI_HIDDEN int check_estimator(const char *name, uint32_t estimator);
 RTMI_HIDDEN int check_estimator_opts(const char *name, uint32_t estimator, float env_select_p, uint32_t flags);
+RTMI_HIDDEN void dev_lighting(const rtmi_scene *s, bool nee, bool env, float env_select_p, DevLights &L, DevEnv &E);
+RTMI_HIDDEN int check_attached(const Estimator &m, const rtmi_scene *s);
+RTMI_HIDDEN int check_attached_early(const Estimator &m, const rtmi_scene *s_in);
 RTMI_HIDDEN int begin_call(RenderCall &c, const Estimator &m, rtmi_scene *s);
 RTMI_HIDDEN void kernel_args(RenderCall &c, const Estimator &m, const rtmi_scene *s, const rtmi_camera *cam,
                              const rtmi_render_params &p);
@@ -233,6 +243,27 @@ RTMI_HIDDEN int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_
 RTMI_HIDDEN uint64_t light_run_slots(const rtmi_scene *s, const RenderCall &c);
 RTMI_HIDDEN int launch_light_coop(const RenderCall &c, const Estimator &m, rtmi_scene *s, bool sig, uint32_t blocks,
                                   const uint32_t *tiles);
+RTMI_HIDDEN int query_check_rays(const char *name, const rtmi_ray *rays, const float *time, uint32_t n);
+RTMI_HIDDEN bool query_fast(const rtmi_scene *s, const rtmi_query_params *p, bool has_time);
+
+// An asynchronous call's hold on the handle, which it takes without waiting for the handle's previous call: the lock, what
+// the estimator needs attached, the device, the caller's stream behind that previous call (a no-op when both were given the
+// same stream), the busy mark.  The members are declared in RenderCall's order: the lock is taken before the mark, and the
+// mark ends (records the call's end) before the lock is released.
+struct AsyncCall {
+    std::unique_lock<std::mutex> lock;
+    BusyMark busy{nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    int begin(const Estimator &m, rtmi_scene *s, void *stream_) {
+        lock = std::unique_lock<std::mutex>(s->mu);
+        if (int rc = check_attached(m, s)) return rc;
+        HIP_TRY(hipSetDevice(s->device));
+        stream = reinterpret_cast<hipStream_t>(stream_);
+        if (s->busy_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->busy.e, 0));
+        busy.s = s; busy.st = stream;
+        return RTMI_OK;
+    }
+};
 
 // Samples [s0, s0 + count) of P.ntiles_local tiles in passes of P.pass_stride (the plan of plan_and_reserve): sets the
 // pass fields of P, calls launch(blocks, first, last) for the mode's render and resolve of each pass and ends the pass.

@@ -1,6 +1,6 @@
 // rtmi_kernels.hpp — render kernels (per-lane two-phase, wave-cooperative, async state machine), resolve, probes.
-// Part of the single translation unit rtmi_device.hip (device code is header-only so that every
-// kernel instantiation inlines the whole path); arithmetic contract as stated there.
+// Header-only device code, included by every unit that instantiates a kernel (header-only so that every
+// kernel instantiation inlines the whole path); arithmetic contract as stated in rtmi_device.hip.
 #pragma once
 #include "rtmi_bvh_coop.hpp"
 #include "rtmi_shade.hpp"

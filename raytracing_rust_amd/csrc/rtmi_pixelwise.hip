@@ -1,7 +1,7 @@
 // rtmi_pixelwise.hip — translation unit of per-pixel adaptive sampling (include/rtmi_pixelwise.h): the step kernel and its
 // launcher.  Compiled with the flags of rtmi_adaptive.hip (-ffp-contract=off: no fused operations, so numpy restates the
 // estimator bit for bit).  The select and the path kernel of a step are those of rtmi_sparse.hip, launched as they are by
-// the entries in rtmi_device.hip.
+// the entries in rtmi_batch.hip.
 //
 // One lane per list entry.  Entry k names pixel p = list[k] and owns records [k * pass, (k + 1) * pass) of the per-sample
 // buffer.  The lane loads the nine doubles of p from the structure-of-arrays state (an ascending list reads each row nearly

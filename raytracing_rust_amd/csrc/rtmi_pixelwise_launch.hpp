@@ -1,5 +1,5 @@
 // rtmi_pixelwise_launch.hpp — launcher of the step kernel of per-pixel adaptive sampling (include/rtmi_pixelwise.h), defined in
-// rtmi_pixelwise.hip and called by the rtmi_render_pixelwise entries in rtmi_device.hip.
+// rtmi_pixelwise.hip and called by the rtmi_render_pixelwise entries in rtmi_batch.hip.
 #pragma once
 
 // one launch of the step kernel: the entries of a list, their pass records of the per-sample buffer, the image's state

@@ -1,6 +1,6 @@
 // rtmi_prof.hpp — lane-activity and phase-time profiling hooks (PROF instantiations only).
-// Part of the single translation unit rtmi_device.hip (device code is header-only so that every
-// kernel instantiation inlines the whole path); arithmetic contract as stated there.
+// Header-only device code, included by every unit that instantiates a kernel (header-only so that every
+// kernel instantiation inlines the whole path); arithmetic contract as stated in rtmi_device.hip.
 #pragma once
 #include "rtmi_types.hpp"
 

@@ -1,5 +1,5 @@
 // rtmi_radiance_launch.hpp — launchers of the radiance-query kernels (include/rtmi_radiance.h), defined in
-// rtmi_radiance.hip and called by rtmi_radiance / rtmi_radiance_device in rtmi_device.hip.
+// rtmi_radiance.hip and called by rtmi_radiance / rtmi_radiance_device in rtmi_batch.hip.
 #pragma once
 
 // one batch of rays on the device; the per-sample buffer is P.samples of the launch ([n][spp] Rad3, item k = i * spp + s)

@@ -1,6 +1,6 @@
 // rtmi_shade.hpp — textures, Perlin noise, materials, camera sample, medium sample, shading of one hit.
-// Part of the single translation unit rtmi_device.hip (device code is header-only so that every
-// kernel instantiation inlines the whole path); arithmetic contract as stated there.
+// Header-only device code, included by every unit that instantiates a kernel (header-only so that every
+// kernel instantiation inlines the whole path); arithmetic contract as stated in rtmi_device.hip.
 #pragma once
 #include "rtmi_rng.hpp"
 #include "rtmi_geom.hpp"

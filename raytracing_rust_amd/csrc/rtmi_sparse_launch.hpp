@@ -1,5 +1,5 @@
 // rtmi_sparse_launch.hpp — launchers of the sparse-render kernels (include/rtmi_sparse.h), defined in rtmi_sparse.hip and
-// called by the rtmi_sparse_* entries in rtmi_device.hip.
+// called by the rtmi_sparse_* entries in rtmi_batch.hip.
 #pragma once
 
 // pixels of one workgroup of the select kernels: 256 lanes x 16 bytes

@@ -1,6 +1,6 @@
 // rtmi_types.hpp — vector type and the device-side views of scene, camera and render parameters.
-// Part of the single translation unit rtmi_device.hip (device code is header-only so that every
-// kernel instantiation inlines the whole path); arithmetic contract as stated there.
+// Header-only device code, included by every unit that instantiates a kernel (header-only so that every
+// kernel instantiation inlines the whole path); arithmetic contract as stated in rtmi_device.hip.
 #pragma once
 #include <cstddef>
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // rtmi_window.hip — translation unit of windowed adaptive sampling (include/rtmi_window.h): the spread kernel and its
 // launcher.  Compiled with the flags of rtmi_pixelwise.hip.  The select, the path kernel and the step kernel of a step are
-// those of rtmi_sparse.hip and rtmi_pixelwise.hip, launched as they are by the entries in rtmi_device.hip.
+// those of rtmi_sparse.hip and rtmi_pixelwise.hip, launched as they are by the entries in rtmi_batch.hip.
 //
 // active[p] = active[p] != 0 && some fail byte != 0 in the (2r + 1)^2 window of p clipped to the image.  The planes are
 // bytes and the window holds up to 33^2 taps, so no lane reads taps.  A wavefront owns 64 consecutive pixels of a row and

@@ -1,5 +1,5 @@
 // rtmi_window_launch.hpp — launcher of the spread kernel of windowed adaptive sampling (include/rtmi_window.h), defined in
-// rtmi_window.hip and called by the rtmi_render_window entries, rtmi_window_spread_device and the probe in rtmi_device.hip.
+// rtmi_window.hip and called by the rtmi_render_window entries, rtmi_window_spread_device and the probe in rtmi_batch.hip.
 #pragma once
 
 #define RTMI_WINDOW_RADIUS_MAX 16u // RTMI_WINDOW_MAX_RADIUS of the header; the kernel's LDS is sized by it

@@ -163,7 +163,7 @@ def test_checks_come_before_device_work():
     # begin_call makes the attach checks (check_attached, no device call in it) before the path's first device call
     begin = body_of("int begin_call(")
     assert begin.index("check_attached(") < begin.index("hipSetDevice")
-    attached = body_of("static int check_attached(")
+    attached = body_of("int check_attached(")
     for check in ("!s->has_env", "!s->has_lights"):
         assert check in attached and "hip" not in attached, check
     body = src[src.index('extern "C" int rtmi_scene_attach_env('):]

@@ -113,5 +113,5 @@ def test_missing_attach_is_checked_before_device_work():
     # begin_call makes the check (check_attached, no device call in it) before the path's first device call
     begin = body_of("int begin_call(")
     assert begin.index("check_attached(") < begin.index("hipSetDevice")
-    attached = body_of("static int check_attached(")
+    attached = body_of("int check_attached(")
     assert "!s->has_lights" in attached and "hip" not in attached
