@@ -1591,3 +1591,21 @@ extern "C" {
     /// test hook: one of the handle's device arrays copied to the host
     pub fn rtmu_probe_scene_words(scene: *mut RtmiScene, which: c_int, out: *mut c_void, cap: usize, need: *mut usize) -> c_int;
 }
+
+// ---- include/rtmi_relight.h: the light table and the light tree follow a scene update on the device -------------------
+// (the RTML_WORDS_* selectors of rtml_probe_light_words are 0..3 in the header's order)
+
+extern "C" {
+    /// on != 0: updates that move an emitter recompute the attached table and refit the tree instead of detaching them
+    pub fn rtml_scene_follow_lights(scene: *mut RtmiScene, on: c_int) -> c_int;
+    /// the same rules on the host: lights[n_lights] and the tree's nodes (32 B each, or NULL with n_nodes = 0) are rewritten
+    pub fn rtml_relight_desc(
+        desc: *const RtmiSceneDesc,
+        lights: *mut RtmiLight,
+        n_lights: u32,
+        nodes: *mut c_void,
+        n_nodes: u32,
+    ) -> c_int;
+    /// test hook: one of the handle's light arrays copied to the host
+    pub fn rtml_probe_light_words(scene: *mut RtmiScene, which: c_int, out: *mut c_void, cap: usize, need: *mut usize) -> c_int;
+}

@@ -615,6 +615,35 @@ def bind_host_update(lib):
     """Sets the signatures of the update wrappers of librt_host.so (UPDATE_HOST_ENTRIES) on a loaded library."""
     return _bind(lib, UPDATE_HOST_ENTRIES)
 
+
+# ---- the lights that follow an update (include/rtmi_relight.h): a family of its own, prefix rtml_ ----------------------------
+# As the update family above: outside FAMILIES, compared with the header, sys.rs and the libraries' exports by
+# tests/test_relight_abi.py.  load_rtmi() applies RELIGHT_ENTRIES; bind_host_relight(), which Host() calls, the wrappers'.
+# RTML_WORDS_* of the header, in its order: the light arrays rtml_probe_light_words copies out.
+LIGHT_WORDS = {"lights": 0, "prim_light": 1, "tree_nodes": 2, "tree_paths": 3}
+
+
+def _relight_tables():
+    i, u32, vp, sz, P = C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER
+    entries = {
+        "rtml_probe_light_words": (i, [vp, i, vp, sz, P(sz)]),
+        "rtml_relight_desc": (i, [P(SceneDesc), P(Light), u32, vp, u32]),
+        "rtml_scene_follow_lights": (i, [vp, i]),
+    }
+    host = {
+        "rthl_follow_lights": (i, [vp, i]),
+        "rthl_probe_light_words": (i, [vp, i, vp, sz, P(sz)]),
+    }
+    return entries, host
+
+
+RELIGHT_ENTRIES, RELIGHT_HOST_ENTRIES = _relight_tables()
+
+
+def bind_host_relight(lib):
+    """Sets the signatures of the relight wrappers of librt_host.so (RELIGHT_HOST_ENTRIES) on a loaded library."""
+    return _bind(lib, RELIGHT_HOST_ENTRIES)
+
 _rtmi = None
 _host = None
 
@@ -634,6 +663,7 @@ def load_rtmi():
             fn.restype = res
             fn.argtypes = args
     _bind(lib, UPDATE_ENTRIES)
+    _bind(lib, RELIGHT_ENTRIES)
     _rtmi = lib
     return lib
 

@@ -22,7 +22,8 @@ INCLUDE = os.path.join(_ROOT, "include")
 # kept for the parity tests (rtmi_alt), then one unit per render mode, named after its header in include/, and the
 # kernel-less host unit of the multi-device handle (rtmi_multi), the path probe over its scripted word source
 # (rtmi_probe_path), the scene updates: a kernel-less host unit and the unit of its two kernels (rtmi_update,
-# rtmi_update_dev), and the kernel-less host unit of the batch modes (rtmi_batch).
+# rtmi_update_dev), the kernel-less host unit of the batch modes (rtmi_batch), and the lights
+# that follow an update: again a kernel-less host unit and the unit of its kernel (rtmi_relight, rtmi_relight_dev; §44).
 _RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_onetree.hip", True), ("rtmi_alt.hip", True), ("rtmi_f64.hip", False),
                ("rtmi_adaptive.hip", True), ("rtmi_features.hip", True), ("rtmi_denoise.hip", False), ("rtmi_nee.hip", True),
                ("rtmi_env.hip", True), ("rtmi_adaptive_nee.hip", True), ("rtmi_roulette.hip", True),
@@ -32,7 +33,8 @@ _RTMI_UNITS = (("rtmi_device.hip", True), ("rtmi_lean.hip", False), ("rtmi_onetr
                ("rtmi_tonemap.hip", False), ("rtmi_upscale.hip", False), ("rtmi_sparse.hip", True),
                ("rtmi_pixelwise.hip", True), ("rtmi_window.hip", True), ("rtmi_batch_coop.hip", True),
                ("rtmi_multi.hip", False), ("rtmi_probe_path.hip", False), ("rtmi_update.hip", False),
-               ("rtmi_update_dev.hip", False), ("rtmi_batch.hip", False))
+               ("rtmi_update_dev.hip", False), ("rtmi_batch.hip", False), ("rtmi_relight.hip", False),
+               ("rtmi_relight_dev.hip", False))
 _PUBLIC_HEADERS = sorted(glob.glob(os.path.join(INCLUDE, "*.h")))
 RTMI_SRC = [os.path.join(_PKG, "csrc", name) for name, _ in _RTMI_UNITS]
 HOST_SRC = [os.path.join(_PKG, "host", "rt_host.cpp"), os.path.join(_PKG, "host", "rt_host_c.cpp")]

@@ -2265,6 +2265,7 @@ extern "C" int rtmi_scene_attach_lights(rtmi_scene *s, const rtmi_scene_desc *d)
     HIP_TRY(hipSetDevice(s->device));
     const auto fill = [&]() -> int { // (a running NEE render may read the old table)
         s->has_light_tree = false; // its leaves index the table it was built over (rtmi_light_tree.h)
+        s->rl_on = s->rl_ready = false; // ... and so do the tables of a handle that follows its lights (rtmi_relight.h)
         HIP_TRY(s->nee_lights.alloc(dl.size() * sizeof(NeeLight)));
         HIP_TRY(s->nee_prim_light.alloc(pl.size() * sizeof(int32_t)));
         HIP_TRY(hipMemcpy(s->nee_lights.ptr, dl.data(), dl.size() * sizeof(NeeLight), hipMemcpyHostToDevice));
@@ -2299,6 +2300,7 @@ extern "C" int rtmi_scene_attach_light_tree(rtmi_scene *s, const rtmi_scene_desc
     HIP_TRY(hipSetDevice(s->device));
     const auto fill = [&]() -> int { // (a running render may read the old tree)
         const size_t nn = std::max<size_t>(nodes.size(), 2), np = std::max<size_t>(paths.size(), 1);
+        s->rl_on = s->rl_ready = false; // the tables of a handle that follows its lights hold the old tree's slots (rtmi_relight.h)
         HIP_TRY(s->lt_nodes.alloc(nn * sizeof(rtmi_light_node))); // hipMalloc aligns to 256 B
         HIP_TRY(s->lt_paths.alloc(np * sizeof(rtmi_light_path)));
         HIP_TRY(hipMemset(s->lt_nodes.ptr, 0, nn * sizeof(rtmi_light_node)));

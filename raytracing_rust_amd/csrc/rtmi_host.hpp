@@ -29,6 +29,7 @@
 #include "rtmi_light_launch.hpp"
 #include "rtmi_refit.hpp"
 #include "rtmi_update_launch.hpp"
+#include "rtmi_relight_launch.hpp"
 #include "rtmi_hostkit.hpp"
 
 #define HIP_TRY(expr) RTMI_HIP_TRY("", false, expr, #expr)
@@ -136,6 +137,17 @@ struct RTMI_HIDDEN rtmi_scene {
     uint32_t up_n_jobs = 0;
     DeviceBuf<float> up_stage;         // planes A | B of a blocking update on the device
     PinnedBuf<float> up_h_stage;       // ... and their pinned host copy
+    // following lights (include/rtmi_relight.h): on, and the tables rtml_scene_follow_lights built from the attached table
+    // and tree, which hold until another table or tree is attached — per primitive the light that lists it (-1: none) and
+    // per light its plane and weight for the blocking update's check, then the kernel's tables; freed with the handle
+    bool rl_on = false, rl_ready = false;
+    std::vector<int32_t> rl_prim_light; // [n_prims]
+    std::vector<int32_t> rl_plane;      // [nee_n]: NeeLight::plane
+    std::vector<double> rl_weight_h;    // [nee_n]
+    DeviceBuf<double> rl_weight;        // [max(nee_n, 1)]
+    DeviceBuf<uint32_t> rl_words;       // the tree's slots by depth (RelightScene::words)
+    DeviceBuf<double> rl_scratch;       // aw [nee_n] | box [lt_n][7]
+    uint32_t rl_n_lvl = 0;              // 0: built without a tree
 };
 
 static inline uint32_t tiles_x_of(const rtmi_render_params *p) { return (p->nx + RTMI_TILE - 1) / RTMI_TILE; }

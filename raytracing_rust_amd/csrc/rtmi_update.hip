@@ -1,10 +1,12 @@
 // rtmi_update.hip — host unit of the scene updates (include/rtmi_update.h): the entry points, the tables a
 // handle builds on its first update and the ordering of an update among the calls on the handle.  No kernel here: the
 // scatter and the refit are reached through rtmi_update_launch.hpp.  rtmu_refittable and rtmu_refit_desc are the host
-// evaluation of rtmi_refit.hpp and touch no device.
+// evaluation of rtmi_refit.hpp and touch no device.  On a handle that follows its lights (include/rtmi_relight.h; §44) an
+// update that moves an emitter also enqueues the relight kernel, through rtmi_relight_launch.hpp.
 #include "rtmi_host.hpp"
 
 #include "rtmi_update.h"
+#include "rtmi_relight.hpp"
 
 #define UPD_TRY(expr) RTMI_HIP_TRY("rtmu_scene_update_prims: ", false, expr, #expr)
 #define UPX_TRY(expr) RTMI_HIP_TRY("rtmu_scene_update_xforms: ", false, expr, #expr)
@@ -140,10 +142,15 @@ static int admit(rtmi_scene *s, uint32_t first, uint32_t count) {
 
 // scatter and refit on `stream`, after the previous call on the handle; the handle's `busy` event follows them
 static int enqueue(rtmi_scene *s, uint32_t first, uint32_t count, const float *d_a, const float *d_b, hipStream_t stream) {
+    bool relight = false;
     for (uint32_t p = first; p < first + count; p++)
         if (s->up_emits[p]) { // the light table and the tree over it hold copies of this geometry
-            s->has_lights = false;
-            s->has_light_tree = false;
+            if (s->rl_on && s->rl_ready && s->has_lights) { // following (rtmi_relight.h): they are recomputed behind the refit
+                relight = true;
+            } else {
+                s->has_lights = false;
+                s->has_light_tree = false;
+            }
             break;
         }
     if (s->busy_recorded) UPD_TRY(hipStreamWaitEvent(stream, s->busy.e, 0));
@@ -158,6 +165,18 @@ static int enqueue(rtmi_scene *s, uint32_t first, uint32_t count, const float *d
     U.n_jobs = s->up_n_jobs;
     UPD_TRY(rtmi_update_scatter_launch(stream, U, first, count, d_a, d_b));
     UPD_TRY(rtmi_update_refit_launch(stream, U, first, count));
+    if (relight) {
+        RelightScene R{};
+        R.prim_a = s->dev.prim_a; R.prim_b = s->dev.prim_b;
+        R.lights = reinterpret_cast<float *>(s->nee_lights.ptr);
+        R.n = s->nee_n;
+        R.weight = s->rl_weight.ptr; R.words = s->rl_words.ptr;
+        R.aw = s->rl_scratch.ptr; R.box = s->rl_scratch.ptr + (s->nee_n ? s->nee_n : 1u);
+        const bool tree = s->has_light_tree && s->rl_n_lvl > 0u; // the tables were built over this tree: attaching another turns following off
+        R.nodes = tree ? reinterpret_cast<float *>(s->lt_nodes.ptr) : nullptr;
+        R.n_lvl = tree ? s->rl_n_lvl : 0u;
+        UPD_TRY(rtmi_relight_launch(stream, R));
+    }
     return RTMI_OK;
 }
 
@@ -199,6 +218,13 @@ extern "C" int rtmu_scene_update_prims(rtmi_scene *s, uint32_t first, uint32_t c
         if (s->up_type[p] == RTMI_PRIM_CUBE && (A[0] > A[3] || (B && (A[1] > B[0] || A[2] > B[1]))))
             return fail(RTMI_ERR_INVALID, name, "a cube of a refittable item is inverted (min > max)");
     }
+    if (s->rl_on && s->rl_ready && s->has_lights) // following: a listed light must stay a light (rtmi_relight.h)
+        for (uint32_t i = 0; i < count; i++) {
+            const int32_t li = s->rl_prim_light[first + i];
+            if (li < 0) continue;
+            if (const char *why = relight_degenerate(s->rl_plane[(size_t)li], a + (size_t)i * 4, s->rl_weight_h[(size_t)li]))
+                return fail(RTMI_ERR_INVALID, name, (std::string("the handle follows its lights and the new planes make ") + why).c_str());
+        }
     if (int rc = begin_blocking(s)) return rc;
     const size_t plane = (size_t)count * 4;
     UPD_TRY(s->up_h_stage.grow(2 * plane * sizeof(float)));

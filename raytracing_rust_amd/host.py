@@ -164,6 +164,7 @@ class Scene:
         self.f64_attached = False
         self.lights_attached = False
         self.light_tree_attached = False
+        self.following_lights = False
         if f64:
             self.attach_f64()
         if nee or light_tree:
@@ -174,7 +175,9 @@ class Scene:
 
     def lights(self):
         """The light table of next-event estimation (rtmi_lights_from_desc, include/rtmi_nee.h) as a numpy structured
-        array with the fields item, prim, kind, material, area, weight, select_p, cdf.  Host code: needs no GPU."""
+        array with the fields item, prim, kind, material, area, weight, select_p, cdf.  Host code: needs no GPU.  It is
+        the table of the host description, desc(): after an update_prims with torch tensors that description is stale,
+        as its planes are, while a handle that follows its lights (follow_lights) holds the moved table."""
         lib = abi.load_rtmi()
         d = self.desc()
         n = C.c_uint32(0)
@@ -193,12 +196,15 @@ class Scene:
         self.host._check(self.host.lib.rth_attach_lights(self.h))
         self.lights_attached = True
         self.light_tree_attached = False  # a new table detaches the tree built over the old one
+        self.following_lights = False  # ... and turns following off (follow_lights)
         return self
 
     def light_tree(self):
         """The light tree (rtmi_light_tree_from_desc, include/rtmi_light_tree.h) as two numpy structured arrays: nodes
         (c float32 [3], r2, power, link, pad uint32 [2]; 2 * lights of them, none for a scene without lights) and paths
-        (trail, depth; one per light).  Host code: needs no GPU."""
+        (trail, depth; one per light).  Host code: needs no GPU.  A fresh build over the host description, desc(): stale
+        after an update_prims with torch tensors, and not the tree of a handle that follows its lights (follow_lights),
+        which keeps the topology it was attached with (rtml_relight_desc restates it)."""
         lib = abi.load_rtmi()
         d = self.desc()
         n = C.c_uint32(0)
@@ -217,6 +223,7 @@ class Scene:
         self.host._check(self.host.lib.rth_attach_light_tree(self.h))
         self.lights_attached = True
         self.light_tree_attached = True
+        self.following_lights = False  # the tables of follow_lights index the old tree
         return self
 
     def _light_probe(self, op, points, aux):
@@ -675,6 +682,27 @@ class Scene:
             self._emits = kinds[meta[:, 0]] == abi.MAT_DIFFUSE_LIGHT  # (a copy: fancy indexing)
         return bool(self._emits[first:first + count].any())
 
+    def follow_lights(self, on=True):
+        """The attached light table and light tree follow the updates of this handle (rtml_scene_follow_lights,
+        include/rtmi_relight.h): an update_prims whose range holds an emitter then recomputes the table and refits the tree
+        on the device, behind the refit of the BVH items, instead of detaching them — in both forms, so torch tensors may
+        move the lamps.  Needs an uploaded scene with the light table attached (the tree too, if it is to follow); builds
+        the handle's tables now, waiting for the calls enqueued on it.  The tree keeps the topology it was attached with.
+        upload(), attach_lights() and attach_light_tree() turn following off again; on=False does so explicitly."""
+        self.host._check(self.host.lib.rthl_follow_lights(self.h, 1 if on else 0))
+        self.following_lights = bool(on)
+        return self
+
+    def light_words(self, which):
+        """One of the resident handle's light arrays as bytes (rtml_probe_light_words, a test hook): `which` is a key of
+        abi.LIGHT_WORDS.  Waits for the calls enqueued on the handle."""
+        need = C.c_size_t(0)
+        self.host._check(self.host.lib.rthl_probe_light_words(self.h, abi.LIGHT_WORDS[which], None, 0, C.byref(need)))
+        out = np.zeros(need.value, np.uint8)
+        if need.value:
+            self.host._check(self.host.lib.rthl_probe_light_words(self.h, abi.LIGHT_WORDS[which], out.ctypes.data, need.value, None))
+        return out
+
     def prepare_updates(self):
         """Builds the resident handle's update tables now (rtmu_scene_update_prepare): otherwise its first update does,
         waiting for the calls enqueued on the handle and allocating — also the first update with torch tensors."""
@@ -688,12 +716,14 @@ class Scene:
 
         numpy arrays: blocking.  The planes are also written into the lowered arrays and refit there (rtmu_refit_desc), so
         desc() stays the description of what is resident; when the range holds an emitter, the light table and the light
-        tree that were attached are derived again from it and re-attached.
+        tree that were attached are derived again from it and re-attached — unless the handle follows its lights
+        (follow_lights): then the device recomputes both behind the refit and nothing is re-attached.
 
         torch tensors on the scene's device: asynchronous on the current stream, no host copy (the _device entry) — and
         the lowered arrays go STALE: desc(), arrays() and everything derived from them describe the scene before the
         update.  Raises when the range holds an emitter while a light table is attached, which would have to be derived
-        from the stale description.  Inside refittable items finite planes, non-zero radii and cubes with min <= max are
+        from the stale description — unless the handle follows its lights (follow_lights): then the update also recomputes
+        the table and refits the light tree on the device, still without a wait or an allocation.  Inside refittable items finite planes, non-zero radii and cubes with min <= max are
         the caller's contract.  The handle's first update waits for the handle and allocates: see prepare_updates().
 
         Either form leaves the double planes of the f64 render mode at the positions the scene was lowered with: after an
@@ -707,7 +737,8 @@ class Scene:
         first, n = int(first), a.shape[0]
         if first < 0 or first + n > self.desc().n_prims:
             raise ValueError("primitives [%d, %d) are outside the scene's %d" % (first, first + n, self.desc().n_prims))
-        relight = n > 0 and self.uploaded and getattr(self, "lights_attached", False) and self._emitters_in(first, n)
+        relight = (n > 0 and self.uploaded and getattr(self, "lights_attached", False) and not getattr(self, "following_lights", False)
+                   and self._emitters_in(first, n))
         tree = relight and getattr(self, "light_tree_attached", False)
         self.host._check(self.host.lib.rthu_update_prims(self.h, first, n, a.ctypes.data, b.ctypes.data if b is not None else None))
         if relight:
@@ -731,9 +762,9 @@ class Scene:
         first, n = int(first), a.shape[0]
         if first < 0 or first + n > self.desc().n_prims:
             raise ValueError("primitives [%d, %d) are outside the scene's %d" % (first, first + n, self.desc().n_prims))
-        if n and getattr(self, "lights_attached", False) and self._emitters_in(first, n):
+        if n and getattr(self, "lights_attached", False) and not getattr(self, "following_lights", False) and self._emitters_in(first, n):
             raise HostError("update_prims with tensors: the range holds an emitter and a light table is attached; the table "
-                            "would have to be derived from the stale host description (use numpy planes)")
+                            "would have to be derived from the stale host description (use numpy planes, or follow_lights())")
         self.host._check(self.host.lib.rthu_update_prims_device(
             self.h, first, n, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()) if b is not None else None,
             C.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)))
@@ -1719,7 +1750,7 @@ class Host:
     precision = "host"
 
     def __init__(self):
-        self.lib = abi.bind_host_update(abi.load_host())
+        self.lib = abi.bind_host_relight(abi.bind_host_update(abi.load_host()))
 
     def _raise(self):
         msg = (self.lib.rth_last_error() or b"").decode()

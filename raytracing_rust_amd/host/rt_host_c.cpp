@@ -23,6 +23,7 @@
 #include "rtmi_frame.h"
 #include "rtmi_upscale.h"
 #include "rtmi_update.h"
+#include "rtmi_relight.h"
 
 using namespace rt;
 
@@ -823,6 +824,19 @@ RTH_API int rthu_probe_scene_words(void *lowered, int which, void *out, size_t c
     return guard([&] {
         const char *name = "rtmu_probe_scene_words";
         return done(name, rtmu_probe_scene_words(DEV(lowered, name, "update"), which, out, cap, need), CODED);
+    });
+}
+// ---- the lights that follow an update (include/rtmi_relight.h), on the uploaded handle -------------------------------------
+RTH_API int rthl_follow_lights(void *lowered, int on) {
+    return guard([&] {
+        const char *name = "rtml_scene_follow_lights";
+        return done(name, rtml_scene_follow_lights(DEV(lowered, name, "update"), on), CODED_UNSUPPORTED);
+    });
+}
+RTH_API int rthl_probe_light_words(void *lowered, int which, void *out, size_t cap, size_t *need) {
+    return guard([&] {
+        const char *name = "rtml_probe_light_words";
+        return done(name, rtml_probe_light_words(DEV(lowered, name, "update"), which, out, cap, need), CODED);
     });
 }
 RTH_API int rth_render_device(void *lowered, void *cam, const rtmi_render_params *p, void *d_texels, void *stream,
