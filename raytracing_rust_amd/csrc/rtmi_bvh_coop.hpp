@@ -27,6 +27,12 @@
 #define COOP_NONE 0xffffffffu
 #define RTMI_COOP_DUMMY_WORDS 128u /* one uint2 per lane behind `best`: target of the stores of children that are not published */
 #define COOP_SENTINEL 0xffffffffffffffffull
+// A round of the 4-wide walk that meets at most this many pending entries (holders + LDS part) is a quad round: four
+// lanes per entry, one per child.  At most 16 (64 lanes); 0 compiles the path out (A/B builds: -DRTMI_COOP_QUAD_MAX=0).
+#ifndef RTMI_COOP_QUAD_MAX
+#define RTMI_COOP_QUAD_MAX 16
+#endif
+static_assert(RTMI_COOP_QUAD_MAX >= 0 && RTMI_COOP_QUAD_MAX <= 16, "a quad round gives every entry four of the 64 lanes");
 __device__ __forceinline__ uint32_t f2sort(float f) {
     const uint32_t u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -75,8 +81,12 @@ struct CoopWork {
 // QU: q_min is the same in every lane (the render bodies' pinned scalar t_min).  The workers then take it from the scalar,
 // and its word of the ray context carries the owner's 1/(d.d) instead: a worker that switches to the ray forms d.d for a
 // sphere leaf as before (five instructions) but no longer divides — the same quotient, computed once by the owner.
+// SP: the forms of DESIGN.md §45 — node and leaf records addressed by 32-bit byte offsets from the scalar base, and quad
+// rounds in the sparse rounds of the extended 4-wide walk.  The one-tree instantiation and the profiling build take them;
+// in the other instantiations, which also carry the binary walk, they cost registers that those kernels do not have
+// (eight of them spilled to scratch), so those compile the walk as it was.
 #define RTMI_COOP_INLINE __forceinline__
-template <bool PROF, bool EXT, bool W4, bool INST, bool QU = false>
+template <bool PROF, bool EXT, bool W4, bool INST, bool QU = false, bool SP = false>
 __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, bool gated, float scale, bool active, const RayF &R,
                                                float time, float q_min, float q_max, const CoopWork &cw,
                                                bool &have, float &t_out, int &pf_out, bool &overflow,
@@ -135,12 +145,28 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
         // near / far plane of every slab picked by the sign of the ray direction (an index into the record, no
         // min/max pair per axis and box; measured final_scene +1.7 %, random_spheres +2.7 %).  A NaN from 0 * inf on a plane
         // the ray lies in is ignored by fmaxf / fminf: no constraint from that plane, which only culls less.
-        const uint32_t base = cur * 8u; // minx[4] miny[4] minz[4] maxx[4] maxy[4] maxz[4] child[4] -
-        const uint32_t sx = W.inv_d.x < 0.0f ? 3u : 0u, sy = W.inv_d.y < 0.0f ? 3u : 0u, sz = W.inv_d.z < 0.0f ? 3u : 0u;
-        const float4 nx4 = sc.nodes4[base + sx], fx4 = sc.nodes4[base + 3u - sx];
-        const float4 ny4 = sc.nodes4[base + 1u + sy], fy4 = sc.nodes4[base + 4u - sy];
-        const float4 nz4 = sc.nodes4[base + 2u + sz], fz4 = sc.nodes4[base + 5u - sz];
-        const float4 chf = sc.nodes4[base + 6u];
+        // The record is addressed by 32-bit byte offsets from the scalar base (gather16): an internal node's index is below
+        // 2^25 by the pool encoding (rtmi_scene_create refuses a larger tree), so cur * 128 + 127 stays below 2^32.  The
+        // max plane of an axis lies 48 B behind its min plane: every axis selects 0 or 48 for its near plane, flips both
+        // bits for the far one, and the axis itself (0, 16, 32) is a constant of the load instruction — no constant
+        // beyond the inline range, which would each hold a register across the loop.
+        float4 nx4, fx4, ny4, fy4, nz4, fz4, chf; // minx[4] miny[4] minz[4] maxx[4] maxy[4] maxz[4] child[4] -, 16 B each
+        if constexpr (SP) {
+            const uint32_t boff = cur << 7;
+            const uint32_t ox = boff + (W.inv_d.x < 0.0f ? 48u : 0u), oy = boff + (W.inv_d.y < 0.0f ? 48u : 0u),
+                           oz = boff + (W.inv_d.z < 0.0f ? 48u : 0u);
+            nx4 = gather16(sc.nodes4, ox); fx4 = gather16(sc.nodes4, ox ^ 48u);
+            ny4 = gather16<16u>(sc.nodes4, oy); fy4 = gather16<16u>(sc.nodes4, oy ^ 48u);
+            nz4 = gather16<32u>(sc.nodes4, oz); fz4 = gather16<32u>(sc.nodes4, oz ^ 48u);
+            chf = gather16<96u>(sc.nodes4, boff);
+        } else { // an index into the record per plane, widened per lane
+            const uint32_t base = cur * 8u;
+            const uint32_t sx = W.inv_d.x < 0.0f ? 3u : 0u, sy = W.inv_d.y < 0.0f ? 3u : 0u, sz = W.inv_d.z < 0.0f ? 3u : 0u;
+            nx4 = sc.nodes4[base + sx]; fx4 = sc.nodes4[base + 3u - sx];
+            ny4 = sc.nodes4[base + 1u + sy]; fy4 = sc.nodes4[base + 4u - sy];
+            nz4 = sc.nodes4[base + 2u + sz]; fz4 = sc.nodes4[base + 5u - sz];
+            chf = sc.nodes4[base + 6u];
+        }
         const float anx[4] = {nx4.x, nx4.y, nx4.z, nx4.w}, afx[4] = {fx4.x, fx4.y, fx4.z, fx4.w};
         const float any_[4] = {ny4.x, ny4.y, ny4.z, ny4.w}, afy[4] = {fy4.x, fy4.y, fy4.z, fy4.w};
         const float anz[4] = {nz4.x, nz4.y, nz4.z, nz4.w}, afz[4] = {fz4.x, fz4.y, fz4.z, fz4.w};
@@ -184,10 +210,42 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
         }
         top += __popcll(b0) + 2 * __popcll(b1);
     };
+    // Quad round: this lane's share of the visit of the node in `cur` — child lane & 3 alone, with visit4's expressions
+    // for that child on the same values (the same cull decision).  A surviving leaf child stays in `cur` for this round's
+    // leaf part; a surviving internal child is marked in bit 0 of `wkeep` and left in wch[0] / wtn[0] for publish1.
+    const auto visit1 = [&](float limit, uint32_t &wkeep) {
+        const uint32_t boff = (cur << 7) + 4u * ((uint32_t)lane & 3u); // visit4's offsets, plus the child's word of each plane
+        const uint32_t ox = boff + (W.inv_d.x < 0.0f ? 48u : 0u), oy = boff + (W.inv_d.y < 0.0f ? 48u : 0u),
+                       oz = boff + (W.inv_d.z < 0.0f ? 48u : 0u);
+        const float nx = gather4(sc.nodes4, ox), fx = gather4(sc.nodes4, ox ^ 48u);
+        const float ny = gather4<16u>(sc.nodes4, oy), fy = gather4<16u>(sc.nodes4, oy ^ 48u);
+        const float nz = gather4<32u>(sc.nodes4, oz), fz = gather4<32u>(sc.nodes4, oz ^ 48u);
+        const uint32_t ch = __float_as_uint(gather4<96u>(sc.nodes4, boff));
+        const float far0 = fminf(wqmax, limit);
+        const float tn = fmaxf(fmaxf(fmaxf(wqmin, (nx - W.o.x) * W.inv_d.x), (ny - W.o.y) * W.inv_d.y), (nz - W.o.z) * W.inv_d.z);
+        const float tf = fminf(fminf(fminf(far0, (fx - W.o.x) * W.inv_d.x), (fy - W.o.y) * W.inv_d.y), (fz - W.o.z) * W.inv_d.z);
+        const bool okc = !(tn > tf) && ch != COOP_NONE;
+        const bool leaf = (ch & (1u << 25)) != 0u;
+        wch[0] = ch; wtn[0] = tn;
+        wkeep = (okc && !leaf) ? 1u : 0u;
+        cur = (okc && leaf) ? ch : COOP_NONE;
+    };
+    // Publication of a quad round (all 64 lanes call; the pool is empty): one ballot, one store.
+    const auto publish1 = [&](uint32_t wkeep) {
+        const unsigned long long b0 = __ballot(wkeep != 0u);
+        const int at = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u));
+        const int dummy = cap + (int)((lds.dummy() - lds.ctx()) / 2u) + lane; // publish4's dummy entry
+        pool[wkeep != 0u ? at : dummy] = make_uint2(((uint32_t)ray << 26) | wch[0], __float_as_uint(wtn[0]));
+        top = __popcll(b0);
+    };
     // The hot loop runs until the LDS part is empty with all workers idle, or too full for 64 more pushes; the
     // rare handling of both (refill from / spill to global memory) sits in the outer loop, outside the hot
     // loop's register allocation.
+    constexpr bool QUADS = SP && W4 && EXT && RTMI_COOP_QUAD_MAX > 0;
     for (;;) {
+    // quad rounds only while nothing is spilled: the LDS part and the holders are then the whole logical stack, which a
+    // quad round leaves as at most 64 entries for 64 idle workers — the state a query starts from
+    const int qmax = gtop == 0 ? RTMI_COOP_QUAD_MAX : -1;
     for (;;) {
         // ---- idle workers take the deepest pending entries
         const bool needw = cur == COOP_NONE;
@@ -198,8 +256,37 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
             if (!EXT) overflow = true; // cannot happen: the LDS pool is the depth-first bound itself
             break;
         }
-        const int take = n_need < top ? n_need : top;
-        {
+        // A sparse round (wave-uniform): holders and pool entries together fill at most a quarter of the wavefront, so
+        // every entry gets four lanes, one per child of its node — a quad round
+        bool quad = false;
+        if constexpr (QUADS) quad = 64 - n_need + top <= qmax;
+        int busy; // workers with an entry this round = min(64, holders + pool entries)
+        if (quad) {
+            // holders hand their entries back: the pool then holds all `busy` pending entries of the wavefront
+            if (!needw) {
+                const unsigned long long m_hold = ~m_need;
+                const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m_hold >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_hold, 0u));
+                pool[top + r] = make_uint2(((uint32_t)ray << 26) | cur, __float_as_uint(tent));
+            }
+            busy = top + 64 - n_need;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            // lanes 4q .. 4q + 3 take the q-th entry from the top (a broadcast read); a leaf entry is tested by the first of them
+            cur = COOP_NONE;
+            if ((lane >> 2) < busy) {
+                const uint2 e = pool[busy - 1 - (lane >> 2)];
+                tent = __uint_as_float(e.y);
+                cur = e.x & 0x03ffffffu;
+                ray = (int)(e.x >> 26);
+                if ((cur & (1u << 25)) && (lane & 3) != 0) cur = COOP_NONE;
+            }
+            top = 0;
+            if (PROF && RTMI_PROF_ROUND_COUNTERS && lane == 0) { // quad rounds, and the most entries one of them met (rtmi_prof.hpp)
+                atomicAdd(&prof[RTMI_PROF_QUAD_ROUNDS], 1ull);
+                atomicMax(&prof[RTMI_PROF_QUAD_MAX_ENTRIES], (unsigned long long)busy);
+            }
+        } else {
+            const int take = n_need < top ? n_need : top;
             const int r = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m_need >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_need, 0u));
             if (needw && r < take) { // one exec-mask region (scalar instructions are the dear ones here: rtmi_geom.hpp)
                 const int idx = top - 1 - r;
@@ -208,9 +295,14 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
                 cur = e.x & 0x03ffffffu;
                 ray = (int)(e.x >> 26);
             }
+            top -= take;
+            busy = 64 - n_need + take;
         }
-        top -= take;
         prof_tick<PROF>(prof, slot, cur != COOP_NONE);
+        if (PROF && RTMI_PROF_ROUND_COUNTERS && lane == 0) { // rounds by busy workers (rtmi_prof.hpp)
+            const int bucket = busy <= 4 ? 0 : busy <= 8 ? 1 : busy <= 16 ? 2 : busy <= 32 ? 3 : 4;
+            atomicAdd(&prof[RTMI_PROF_ROUND_HIST + (slot == 1 ? 0 : RTMI_PROF_ROUND_BUCKETS) + bucket], 1ull);
+        }
         bool push = false;
         uint32_t push_ref = 0u;
         float push_t = 0.0f;
@@ -237,7 +329,8 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
             const float limit = key != COOP_SENTINEL ? lim : RTMI_FLT_MAX;
             if (tent > limit) cur = COOP_NONE; // (an idle worker's cur is COOP_NONE already: all its bits are set)
             if (W4 && !(cur & (1u << 25))) { // internal node of the 4-wide tree
-                visit4(limit, wkeep, npush);
+                if (quad) visit1(limit, wkeep);
+                else visit4(limit, wkeep, npush);
             } else if (!W4 && !(cur & (1u << 25))) { // internal node
                 const float4 *n = sc.nodes + (size_t)cur * 4;
                 const float4 n0 = n[0], n1 = n[1], n2 = n[2], n3 = n[3];
@@ -278,8 +371,15 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
                 // per leaf instead of two on the path of every accepted hit
                 bool hit;
                 if (EXT && gated) { // one 80-B record: planes, meta and the gate box arrive together
-                    const float4 *rec = sc.leaf_rec + (size_t)idx * 5;
-                    const float4 A = rec[0], B = rec[1], M = rec[2], g0 = rec[3], g1 = rec[4];
+                    float4 A, B, M, g0, g1;
+                    if constexpr (SP) {
+                        const uint32_t loff = (uint32_t)idx * 80u; // primitive index below 2^22 (pool encoding): below 2^29
+                        A = gather16(sc.leaf_rec, loff); B = gather16<16u>(sc.leaf_rec, loff); M = gather16<32u>(sc.leaf_rec, loff);
+                        g0 = gather16<48u>(sc.leaf_rec, loff); g1 = gather16<64u>(sc.leaf_rec, loff);
+                    } else {
+                        const float4 *rec = sc.leaf_rec + (size_t)idx * 5;
+                        A = rec[0]; B = rec[1]; M = rec[2]; g0 = rec[3]; g1 = rec[4];
+                    }
                     hit = prim_test_vals<INST>(sc, type, idx, A, B, M.z, __float_as_uint(M.y), W, wtime, wqmin, wqmax, t, pf);
                     // alternative tree: the reference reaches this leaf iff its parent's box passes
                     if (hit) hit = aabb_hit(g0.x, g0.y, g0.z, g1.x, g1.y, g1.z, W, wqmin, wqmax);
@@ -295,7 +395,8 @@ __device__ __forceinline__ void coop_bvh_query(const DevScene &sc, int root, boo
         }
         // ---- publish the far children
         if (W4) {
-            if (__ballot(npush != 0) != 0ull) publish4(wkeep, npush); // leaf-only rounds publish nothing
+            if (quad) publish1(wkeep);
+            else if (__ballot(npush != 0) != 0ull) publish4(wkeep, npush); // leaf-only rounds publish nothing
         } else {
         const unsigned long long m_push = __ballot(push);
         if (push) {
@@ -363,10 +464,10 @@ __device__ __forceinline__ bool geom_query_coop(const DevScene &sc, const rtmi_i
         bool have = false;
         static_assert(!ONE || (EXT && W4), "the one-tree form walks the gated 4-wide tree");
         if constexpr (ONE) {
-            coop_bvh_query<PROF, EXT, W4, INST, QU>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+            coop_bvh_query<PROF, EXT, W4, INST, QU, true>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
         } else {
         const bool alt = EXT && W4 && use_alt && I.alt_first >= 0; // wave-uniform
-        if (alt) coop_bvh_query<PROF, EXT, W4, INST, QU>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
+        if (alt) coop_bvh_query<PROF, EXT, W4, INST, QU, PROF>(sc, I.alt_first, true, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
         else coop_bvh_query<PROF, EXT, false, INST, QU>(sc, I.first, false, I.scale, enter, r, time, q_min, q_max, cw, have, t_out, pf_out, overflow, prof, slot);
         }
         return have;

@@ -273,6 +273,8 @@ int validate(const rtmi_scene_desc *d) {
     }
     // alternative-tree records: children in range, leaves typed like the primitive they name
     if (d->n_alt_nodes && !d->alt_nodes) return fail(RTMI_ERR_INVALID, "n_alt_nodes without alt_nodes");
+    // the traversals address a 128-B node record by a 32-bit byte offset and keep a node index in 25 bits of a pool entry
+    if (d->n_alt_nodes >= (1u << 25)) return fail(RTMI_ERR_UNSUPPORTED, "too many alternative tree nodes");
     for (uint32_t i = 0; i < d->n_alt_nodes; i++)
         for (int c = 0; c < 4; c++) {
             const int32_t ch = d->alt_nodes[i].child[c];
@@ -921,7 +923,7 @@ int render_device_locked(rtmi_scene *s, const rtmi_camera *cam, const rtmi_rende
     // (it implements the fast-cull semantics); RTMI_FLAG_SYNC = per-lane traversal; RTMI_FLAG_ASYNC =
     // per-lane state machine (kept for comparison)
     const bool async = (p->flags & RTMI_FLAG_ASYNC) != 0u && !s->has_deferred;
-    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25); // (n_alt_nodes < 2^25: validate())
     const bool coop = fast && !sync && !async && coop_ok;
     if ((rc = begin_passes(s, stream))) return rc;
     bool ext = false;
@@ -1784,7 +1786,7 @@ static uint32_t light_coop_bits(const rtmi_render_params *p, uint32_t flag = RTM
     return (p && (p->flags & flag)) ? (flag | (1u << 11)) : 0u;
 }
 int plan_light_coop(RenderCall &c, rtmi_scene *s, const rtmi_render_params &p, uint32_t flag, uint32_t wps) {
-    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25); // (n_alt_nodes < 2^25: validate())
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
     c.coop = (p.flags & flag) != 0u && c.fast && !(p.flags & RTMI_FLAG_SYNC) && coop_ok && !inst;
     if (!c.coop) return RTMI_OK;
@@ -1892,7 +1894,7 @@ static int adaptive_plain_device(RenderCall &c, const Estimator &m, rtmi_scene *
     DevParams &P = c.P;
     // kernel selection as in render_device_locked; the rare compositions (level-1/2 instantiations there) run per-lane
     const bool fast = c.fast, sync = (p.flags & RTMI_FLAG_SYNC) != 0u;
-    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25) && s->meta.n_alt_nodes < (1u << 25);
+    const bool coop_ok = s->meta.n_prims < (1u << 22) && s->meta.n_nodes < (1u << 25); // (n_alt_nodes < 2^25: validate())
     const bool inst = s->dev.has_prim_xf != 0u || s->dev.has_medium_outer != 0u;
     const bool coop = fast && !sync && coop_ok && !inst;
     bool ext = false;

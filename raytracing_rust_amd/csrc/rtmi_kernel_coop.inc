@@ -208,7 +208,7 @@
     if (PROF) {
         __syncthreads();
         if (threadIdx.x < 2 * RTMI_PROF_SLOTS && prof_lds[threadIdx.x] != 0ull) {
-            if (threadIdx.x == 2 * 18) atomicMax(P.prof + threadIdx.x, prof_lds[threadIdx.x]); // slot 18: a maximum
+            if (threadIdx.x == 2 * 18 || threadIdx.x == RTMI_PROF_QUAD_MAX_ENTRIES) atomicMax(P.prof + threadIdx.x, prof_lds[threadIdx.x]); // maxima
             else atomicAdd(P.prof + threadIdx.x, prof_lds[threadIdx.x]);
         }
     }

@@ -8,6 +8,20 @@
 // slot s: prof[2s] += active lanes, prof[2s+1] += 64 (one wave-iteration).  Accumulated in LDS,
 // flushed to global once per block.
 #define RTMI_PROF_SLOTS 32
+// Cooperative kernels: the ten words of slots 20..24 (the per-lane state machine's, which no cooperative kernel ticks) count
+// the traversal's pop rounds by the number of busy workers, buckets <= 4, <= 8, <= 16, <= 32, <= 64: five words for world
+// item 0, then five for every other BVH item together (the split of the TIME slots 27 / 28).
+#define RTMI_PROF_ROUND_HIST (2 * 20)
+#define RTMI_PROF_ROUND_BUCKETS 5
+// ... and two free words: the number of quad rounds (rtmi_bvh_coop.hpp) and, a maximum like slot 18, the most pending
+// entries a quad round met
+#define RTMI_PROF_QUAD_ROUNDS (2 * 17)
+#define RTMI_PROF_QUAD_MAX_ENTRIES (2 * 19)
+// 0 compiles the round counters out of the profiling build (-DRTMI_PROF_ROUND_COUNTERS=0): its TIME slots then measure the
+// traversal without the counters' LDS atomics
+#ifndef RTMI_PROF_ROUND_COUNTERS
+#define RTMI_PROF_ROUND_COUNTERS 1
+#endif
 template <bool PROF>
 __device__ __forceinline__ void prof_tick(unsigned long long *prof_lds, int slot, bool active) {
     if (PROF) {

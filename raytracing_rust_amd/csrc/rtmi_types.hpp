@@ -48,6 +48,20 @@ static_assert(sizeof(rtmi_item) == 64 && sizeof(rtmi_xform) == 16 && sizeof(DevI
 static_assert(offsetof(rtmi_item, flags) == 12 && offsetof(rtmi_item, medium_material) == 24, "item shading words at bytes 12..27");
 static_assert(offsetof(DevItem, x0) == 64 && offsetof(DevItem, x1) == 80, "embedded transforms at bytes 64 and 80");
 
+// 16-byte gather at `base` + `off` + IMM bytes.  `off` is a per-lane byte offset formed in 32-bit arithmetic by the caller,
+// who states why it cannot wrap; widened here without a sign, so with a wave-uniform `base` the load takes a scalar base
+// plus one 32-bit offset register (and IMM in the instruction) instead of a 64-bit address pair built per lane.
+template <uint32_t IMM = 0u>
+__device__ __forceinline__ float4 gather16(const float4 *base, uint32_t off) {
+    return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + (uint64_t)off + IMM);
+}
+
+// one word of such a record, addressed the same way
+template <uint32_t IMM = 0u>
+__device__ __forceinline__ float gather4(const float4 *base, uint32_t off) {
+    return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + (uint64_t)off + IMM);
+}
+
 struct PrimRec { // head of a leaf record (DevScene::leaf_rec, 80 B apart)
     float4 A, B;
     rtmi_prim_meta M;

@@ -12,6 +12,7 @@ from raytracing_rust_amd import Host, abi, dist as rdist, scenes
 NAMES = {0: "bounce loop (lanes with work)", 13: "list prim tests", 14: "traversal: at node", 15: "traversal: at leaf",
          16: "shade", 25: "TIME camera", 26: "TIME list items", 27: "TIME BVH item 0", 28: "TIME other BVH items",
          29: "TIME media", 30: "TIME shading", 31: "TIME loop overhead", 20: "async ST_ITEM", 21: "async ST_NODE", 22: "async ST_PRIM", 23: "async ST_SHADE", 24: "async ST_NEW"}
+HIST_BUCKETS = (4, 8, 16, 32, 64)  # csrc/rtmi_prof.hpp: RTMI_PROF_ROUND_HIST
 
 
 def run(name, nx, ny, ns, flags, threshold=0):
@@ -31,6 +32,17 @@ def run(name, nx, ny, ns, flags, threshold=0):
     tot_wave = 0
     print("  deepest cooperative pool: %d entries (capacity 64 x (max BVH depth + 2) = %d)" % (int(c[2 * 18]), 64 * (sc.arrays()["max_bvh_depth"] + 2)))
     c[2 * 18] = 0
+    if not flags & abi.RTMI_FLAG_ASYNC:  # cooperative kernels: the words of slots 20..24 are the histogram of pop rounds
+        for k, what in enumerate(("world item 0", "other BVH items")):
+            h = [int(v) for v in c[40 + 5 * k:45 + 5 * k]]
+            if sum(h):
+                print("  rounds by busy workers, %-16s" % what + "".join("  <=%d %5.1f%%" % (b, 100.0 * v / sum(h)) for b, v in zip(HIST_BUCKETS, h))
+                      + "  (%d rounds; <=16: %.1f%%)" % (sum(h), 100.0 * sum(h[:3]) / sum(h)))
+        rounds = int(c[40:50].sum())
+        if rounds:  # words 34 / 38: RTMI_PROF_QUAD_ROUNDS, RTMI_PROF_QUAD_MAX_ENTRIES
+            print("  quad rounds: %d of %d (%.1f%%), most entries entering one: %d" % (int(c[34]), rounds, 100.0 * int(c[34]) / rounds, int(c[38])))
+        c[40:50] = 0
+        c[34] = c[38] = 0
     for s in range(32):
         act, wav = int(c[2 * s]), int(c[2 * s + 1])
         if wav == 0:
